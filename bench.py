@@ -5,10 +5,12 @@
 A "step" is one pass of the hot path over one batch: one sample_p_zs_given_zt
 (dynamics forward + p(z_s|z_t) update + COM removal) for the B graphs of this rank.  Inputs
 (pockets, weights) are resident in HBM before the timed region; the per-step noise is drawn on
-the device inside it.  Rank 0 prints ONE JSON line (see the task contract) with two extra
-objects: "roofline" (dominant kernel, HIP-event timed on the launch stream inside the timed
-region) and "cpu_baseline" (the CPU oracle timed on this box's host cores on a bounded sample;
-N=1 only)."""
+the device inside it.  Rank 0 prints ONE JSON line (see the task contract).  A plain run does
+nothing beyond set-up, warm-up, the timed steps and the line.  --full adds "roofline" (dominant
+kernel, HIP-event timed on the launch stream inside the timed region, topped up after it), the
+legs that take runs of their own (rocprofv3 passes, secondary configurations, whole trajectory,
+dense mode) and "cpu_baseline" (the CPU oracle timed on the host's cores on a bounded sample;
+N=1 only).  --dump-outputs DIR writes what the last timed step computed."""
 import argparse
 import json
 import os
@@ -200,7 +202,8 @@ def secondary_legs(args):
     parent touches the GPU.  config 3 (batch 128, ragged sizes 3-8), a config-4 slice (64 pockets x 30 pharmacophores end to end
     through PharmacophoreDiff.sample) and the training step of config 5 (batch 256, a new batch every step)."""
     me = [sys.executable, os.path.abspath(__file__)]
-    light = ["--no-cpu-baseline", "--no-dense-leg", "--no-secondary", "--no-traffic", "--gpus", "1"]
+    # (--full with every leg switched off: the children run as they always have, roofline and its top-up steps included)
+    light = ["--full", "--no-cpu-baseline", "--no-dense-leg", "--no-secondary", "--no-traffic", "--gpus", "1"]
     out = {}
     # the training legs first: measured behind the config-4 slice (the most power-hungry child) two of their short runs in three read
     # 10-60 % slow on some boxes, and never when run on their own; 100 steps each, so that a stall of tens of ms weighs less
@@ -339,7 +342,18 @@ def main():
     ap.add_argument("--train", action="store_true",
                     help="secondary benchmark (BASELINE config 5): training steps (forward, backward kernels, Adam) at "
                          "batch 256 per GPU instead of the sampling metric")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the roofline object with its top-up steps after "
+                         "the timed region, the rocprofv3 child passes behind roofline.traffic / roofline.launches, the secondary "
+                         "configurations, the whole-trajectory leg, the dense-mode leg and the CPU baseline (the --no-* flags above "
+                         "then skip single legs). A plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last of them computed (the samples' coordinates and features, as "
+                         "the sampler hands them out) to DIR/<name>.npy in float32; the inputs are the same in every run with the "
+                         "same arguments")
     args = ap.parse_args()
+    if not args.full:
+        args.no_traffic = args.no_secondary = args.no_full_trajectory = args.no_dense_leg = args.no_cpu_baseline = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args.gpus)
 
@@ -352,10 +366,10 @@ def main():
     HOST_SHARE = pin_host_threads(local_rank, int(os.environ.get("LOCAL_WORLD_SIZE", world)))
     # children first: nothing in this process has touched the GPU yet (a process that has must not start other programs)
     headline = not args.train and args.sample_slice == 0
-    pmc, pmc_err, secondary = None, "not collected (--no-traffic, or a multi-rank run)", None
+    pmc, pmc_err, secondary = None, "not collected (a run without --full, --no-traffic, or a multi-rank run)", None
     if rank == 0 and world == 1 and headline:
         if not args.no_traffic:
-            inner = ["--no-cpu-baseline", "--no-dense-leg", "--no-full-trajectory", "--no-secondary", "--no-traffic", "--gpus", "1",
+            inner = ["--full", "--no-cpu-baseline", "--no-dense-leg", "--no-full-trajectory", "--no-secondary", "--no-traffic", "--gpus", "1",
                      "--steps", "20", "--warmup", "2", "--batch", str(args.batch), "--n-prot", str(args.n_prot), "--n-pharm", str(args.n_pharm),
                      "--arch", args.arch] + (["--pharm-sizes", args.pharm_sizes] if args.pharm_sizes else [])
             pmc, pmc_err = pmc_passes(inner)
@@ -461,6 +475,9 @@ def main():
         while (time.perf_counter() - tp) * 1e3 < args.prewarm_ms:
             run(min(max(K, W), 50), True)
             torch.cuda.synchronize()
+    # the pre-warm runs for a time, not a step count: the noise of the warm-up and the timed steps starts from the seed again,
+    # so that every run with the same arguments feeds the timed steps the same inputs (--dump-outputs)
+    gen.manual_seed(42 + rank)
     # the warm-up steps run with the events on: the library creates its event pairs on first use, and creating them
     # inside the timed region occasionally stalls the host for tens of milliseconds (observed at batch 128-256)
     run(W, True, event_every=1) if W > 0 else eng.sample_begin(torch.randn(Nf, 9, device=dev, generator=gen))
@@ -498,8 +515,10 @@ def main():
     dt = time.perf_counter() - t0
     prof = eng.profile_read()
     eng.profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng)
     in_region = prof[dom_cls][1]
-    if 0 < in_region < 20:                      # short timed regions: top the sample up to 20 launches, outside `value`
+    if args.full and 0 < in_region < 20:        # short timed regions: top the sample up to 20 launches, outside `value`
         eng.profile_enable(EV_MASK)
         run(20 - in_region, False)
         torch.cuda.synchronize()
@@ -705,10 +724,25 @@ def main():
                                                     carr, W, min(K, 50), Nf)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, prot_x.cpu(), prot_h.cpu(), prot_ptr, pharm_ptr, pp_src, pp_dst, T)
+    if not args.full:
+        # the roofline figures are read after the top-up steps (--full): a plain line carries the headline only.  The timed steps
+        # keep their HIP events, so that they are the same steps with and without --full
+        del out["roofline"]
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, eng):
+    """--dump-outputs: what the timed steps computed, read after the last of them -- the batch's current sample as the sampler
+    hands it to its caller (pf_sample_frame: pharm_x = coordinates in the pockets' frame [Nf, 3], pharm_h = features [Nf, 6],
+    unscaled), float32.  Reading it leaves the sampling state as it is."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    x, h = eng.sample_frame()
+    for name, t in (("pharm_x", x), ("pharm_h", h)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def full_trajectory(args, eng, coef, dev, rank, world, B, T, Nf, barrier, max_over_ranks, eng2_factory=None, coef_bounded=None):

@@ -1115,3 +1115,23 @@ def test_bench_rejects_more_ranks_than_a_shared_gpu_takes():
     rc, j, err = _bench_child(["--gpus", "8", "--steps", "2", "--warmup", "1"], timeout=120)
     assert rc != 0 and j is None
     assert "--gpus 8" in err and "GPU(s) visible" in err
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` run: K timed steps, `ms_per_step` on the line, none of the legs --full adds;
+    --dump-outputs writes the last timed step's samples (float32 .npy), and two runs with the same arguments compute the same
+    samples (the pre-warm runs for a time, the noise of the warm-up and the timed steps starts from its seed again)."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        rc, j, err = _bench_child(["--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(d)])
+        assert rc == 0 and j is not None, err[-2000:]
+        assert j["steps"] == 7 and j["warmup"] == 3 and j["ms_per_step"] > 0 and j["unit"] == "sample-steps/s"
+        assert abs(j["value"] - 32 * 1e3 / j["ms_per_step"]) <= 1e-6 * j["value"]
+        assert not [leg for leg in ("roofline", "secondary", "full_trajectory", "cpu_baseline") if leg in j]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("pharm_x", "pharm_h")})
+    for n, cols in (("pharm_x", 3), ("pharm_h", 6)):
+        a, b = dumps[0][n], dumps[1][n]
+        assert a.dtype == np.float32 and a.shape == (32 * 6, cols) and np.isfinite(a).all()
+        np.testing.assert_array_equal(a, b, err_msg=n)

@@ -1,7 +1,6 @@
 """CPU tests of the receptor / ligand ingestion (pocket_io) and the processed-dataset loader (dataset): the semantics of
 generate_pharmacophores.py:68-233 and protein_pharm_dataset.py:19-179 on hand-written files."""
 import gzip
-import os
 import pickle
 
 import numpy as np
@@ -310,8 +309,8 @@ def test_from_dgl_adapter_on_a_heterograph_shaped_like_the_references():
     """graph.from_dgl on DGL-style heterographs (tests/golden/ref_shim.HeteroGraph, the stand-in the goldens were recorded
     with): graphs assembled the way build_initial_complex_graph assembles them (dataset/protein_pharm_dataset.py:226-264:
     node types prot / pharm / prot_ph, edge types pp / pf / ff / fp, x_0 / h_0 node data) from the reference's recorded
-    outputs, single and batched with the stand-in's dgl.batch; when the reference is on this machine its own function builds
-    the graph."""
+    outputs, single and batched with the stand-in's dgl.batch; and one graph built from the pocket's inputs alone, step by step as
+    build_initial_complex_graph builds it."""
     import sys
     from helpers import GOLDEN, load
     sys.path.insert(0, GOLDEN)
@@ -341,12 +340,18 @@ def test_from_dgl_adapter_on_a_heterograph_shaped_like_the_references():
     own = pfa.batch([pfa.graph.from_dgl(hetero(i)) for i in pick])
     for f in ("prot_x", "prot_h", "prot_ptr", "pharm_ptr", "pp_src", "pp_dst", "pharm_x0", "pharm_h0", "prot_ph_x", "prot_ph_ptr"):
         assert torch.equal(getattr(gb, f), getattr(own, f)), f
-    if os.path.isdir("/root/reference/pharmacoforge"):        # build container only: the reference's own graph builder
-        ref_shim.install("/root/reference")
-        from pharmacoforge.dataset.protein_pharm_dataset import build_initial_complex_graph as ref_build
-        g = ref_build(z["plain_1_prot_x"], z["plain_1_prot_h"], {'pp': 3.5, 'pf': 8, 'fp': 8, 'ff': 9},
-                      pharm_atom_positions=z["plain_1_pharm_x"], pharm_atom_features=z["plain_1_pharm_h"],
-                      prot_ph_pos=z["plain_1_ph_x"], prot_ph_feat=z["plain_1_ph_h"])
-        pg = pfa.graph.from_dgl(g)
-        assert torch.equal(pg.pp_src, z["plain_1_pp_src"].long()) and torch.equal(pg.pp_dst, z["plain_1_pp_dst"].long())
-        assert torch.equal(pg.prot_x, z["plain_1_prot_x"]) and pg.num_nodes('pharm') == z["plain_1_pharm_x"].shape[0]
+    # pocket 1 as build_initial_complex_graph (dataset/protein_pharm_dataset.py:210-264) builds it: pp edges from
+    # torch_cluster.radius_graph(r = cutoffs['pp'], max_num_neighbors=100) -- the stand-in the goldens were recorded with --,
+    # empty pf / ff / fp edge types, x_0 / h_0 on every node type
+    pp = ref_shim.tc_radius_graph(z["plain_1_prot_x"], r=CUTOFFS['pp'], max_num_neighbors=100)
+    no = ([], [])
+    g = ref_shim.heterograph({('prot', 'pp', 'prot'): (pp[0], pp[1]), ('prot', 'pf', 'pharm'): no, ('pharm', 'ff', 'pharm'): no,
+                              ('pharm', 'fp', 'prot'): no},
+                             num_nodes_dict={'prot': z["plain_1_prot_x"].shape[0], 'pharm': z["plain_1_pharm_x"].shape[0],
+                                             'prot_ph': z["plain_1_ph_x"].shape[0]})
+    for nt, short in (("pharm", "pharm"), ("prot", "prot"), ("prot_ph", "ph")):
+        g.nodes[nt].data['x_0'] = z[f"plain_1_{short}_x"]
+        g.nodes[nt].data['h_0'] = z[f"plain_1_{short}_h"]
+    pg = pfa.graph.from_dgl(g)
+    assert torch.equal(pg.pp_src, z["plain_1_pp_src"].long()) and torch.equal(pg.pp_dst, z["plain_1_pp_dst"].long())
+    assert torch.equal(pg.prot_x, z["plain_1_prot_x"]) and pg.num_nodes('pharm') == z["plain_1_pharm_x"].shape[0]

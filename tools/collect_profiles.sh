@@ -10,7 +10,7 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py $ARGS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full $ARGS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 LIGHT="--no-cpu-baseline --no-dense-leg --no-full-trajectory --no-secondary --no-traffic"     # the profiled runs start no children of their own
 python3 bench.py $ARGS $LIGHT --breakdown --steps 20 --warmup 2 > /dev/null 2> $OUT/${TAG}_event_breakdown.txt || true
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 bench.py $ARGS $LIGHT > $OUT/${TAG}_stats.log 2>&1
