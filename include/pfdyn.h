@@ -65,8 +65,8 @@ typedef struct pf_config {
     int32_t abi_version;        /* = PF_ABI_VERSION */
     int32_t pharm_nf;           /* n_pharm_scalars (6) */
     int32_t rec_nf;             /* n_prot_scalars  (11) */
-    int32_t vector_size;        /* must be 16 */
-    int32_t n_hidden_scalars;   /* must be 128 */
+    int32_t vector_size;        /* 16 or 32 (16 with n_hidden_scalars 128: the specialised kernels) */
+    int32_t n_hidden_scalars;   /* 64..256, a multiple of 32; other than (128, 16): the width-generic family, inference only */
     int32_t n_convs;
     int32_t n_message_gvps;
     int32_t n_update_gvps;

@@ -538,6 +538,57 @@ __device__ __forceinline__ float pf_feat_update(const float hv, const float e, c
 #endif
 
 
+// ---- width-generic family (pf_wide.hip): inference at n_hidden_scalars S in 64..256 (multiples of 32) and vector_size
+// V in {16, 32}.  A workgroup of four waves owns PFW_ROWS rows (edges or nodes); its activations live in LDS, row-major.
+// Every scalar Linear runs on v_mfma_f32_16x16x4_f32 with the rows as the A operand (lane l: A[l & 15][k = l >> 4]) and the
+// weights as the B operand, packed by the host in fragment order -- tile t of 16 outputs, k-step ks, lane l <->
+// W[16 t + (l & 15)][4 ks + (l >> 4)] (zero beyond the matrix) -- so each wave streams one 256-byte fragment per k-step.
+#define PFW_ROWS 32
+#define PFW_MAXS 256
+#define PFW_MAXV 32
+struct WideGvp {           // one GVP (device pointers into the packed weights)
+    pf_gcf wh;             // [vi][H]  Wh as stored (H = max(vi, vo))
+    pf_gcf wu;             // [H][vo]  Wu as stored
+    pf_gcf wm;             // to_feats_out, fragment order: [ceil(so / 16)][ceil((si + H) / 4)][64]
+    pf_gcf bm;             // [so]
+    pf_gcf wg;             // scalar_to_vector_gates, fragment order: [ceil(vo / 16)][so / 4][64]
+    pf_gcf bg;             // [vo]
+    int vi, vo, si, so;
+};
+struct WideEncParams {     // Linear(nf + 1 -> S) + SiLU + LayerNorm of every node (dynamics_gvp.py:107-117, 143-151)
+    int Np, Nf, S, rec_nf, pharm_nf;
+    const float* prot_h0; const float* pharm_h;
+    const float* t; float t_scalar; const int* gid;     // t == NULL: every graph is at t_scalar
+    const float* w[2]; const float* b[2]; const float* ln_w[2]; const float* ln_b[2];   // 0 prot, 1 pharm; w: [nf + 1][S]
+    float* h_out;          // [N][S]
+};
+struct WideEdgeParams {    // the messages of one conv layer along the edge slots of a tile list (gvp.py:470-549)
+    const EdgeTile* tiles; int ntiles;
+    const int* dyn_cnt; const int* esrc; const int* edst; const float4* xn;
+    const float* h; const float* v;     // [N][S], [N][V][3]
+    int layer0;                         // the node vectors are zero (conv layer 0): v is not read
+    float* msg_s; float* msg_v;         // [slot][S], [slot][V][3]: one row per edge slot
+    const WideGvp* w;                   // [4 etypes][n_gvps]
+    int n_gvps, S, V;
+    float rbf_mu[PF_R]; float rbf_sigma;
+};
+struct WideNodeParams {    // aggregation + node update of one conv layer (gvp.py:488-532); the last one also runs the noise head
+    const NodeTile* tiles; int ntiles;
+    const int* dyn_cnt; const int* row_ids;
+    const int* in_start; const int* in_cnt; int N, pp_slot;
+    const float* msg_s; const float* msg_v;
+    const float* h_in; const float* v_in; int layer0;
+    float* h_out; float* v_out;
+    const int* gid; const float* gnorm; int B, norm_mode; float norm_value;
+    pf_gcf ln1_w[2]; pf_gcf ln1_b[2]; pf_gcf ln2_w[2]; pf_gcf ln2_b[2];
+    const WideGvp* upd[2]; int n_upd;
+    int S, V;
+    // noise head (dynamics_gvp.py:37-42) behind the centers' update: head != NULL
+    const WideGvp* head; int n_head;
+    pf_gcf w_out; pf_gcf b_out; int pharm_nf, node_base;   // to_scalar_output as stored: [pharm_nf][64]
+    float* eps_h; float* eps_x;
+};
+
 struct PreParams {         // protein encoder + pp precompute (encode_pre_tile)
     int Np, rec_nf, nke;   // nke = k-steps of the encoder Linear = (rec_nf + 2) / 2
     const float* prot_h0;

@@ -85,6 +85,10 @@ void pfk_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, 
 void pfk_drop_masks(const TrainCommon* c, uint32_t stream, int n_elems, float* out, hipStream_t s);
 void pfk_pp_radius(const float4* xn, const int* prot_ptr, int B, float r2, int maxn, int* deg, const int* row_off,
                    int* src, int* dst, int pass, hipStream_t s);
+// width-generic family (pf_wide.hip)
+void pfk_wide_encode(const WideEncParams* p, hipStream_t s);
+void pfk_wide_edge(const WideEdgeParams* p, hipStream_t s);
+void pfk_wide_node(const WideNodeParams* p, hipStream_t s);
 }
 
 namespace {
@@ -214,6 +218,13 @@ struct LaunchPolicy {
 struct pf_handle {
     LaunchPolicy pol;
     pf_config cfg{};
+    // width-generic family (pf_wide.hip): every inference call of a handle whose widths are not (128, 16) runs on it, and so does
+    // a (128, 16) handle created under PFDYN_WIDE=1.  spec: the widths of the specialised kernels -- their weights are packed and
+    // training is available; wide: inference goes to run_dynamics_wide
+    bool spec = true, wide = false;
+    std::vector<size_t> wide_off;           // per GVP (the GvpW table's order) the offsets of wh, wu, wm, bm, wg, bg in d_w
+    WideGvp* d_wgvp = nullptr;              // device table of the width-generic GVPs (same indexing as d_gvp)
+    size_t wide_out_w = 0, wide_out_b = 0;  // to_scalar_output as stored ([pharm_nf][64], [pharm_nf])
     std::string err;
     std::map<std::string, RawTensor> raw;
     bool committed = false;
@@ -588,6 +599,30 @@ static size_t push(std::vector<float>& w, const std::vector<float>& v) {
 }
 
 struct GvpOff { size_t wh, wu, wh_c, wu_c, a_main, a_main_c, b_main, a_gate, a_gate_c, b_gate; };
+
+// width-generic family: a Linear W [n_out][K] as the B operand of v_mfma_f32_16x16x4_f32, [tile of 16 outputs][k-step][64 lanes],
+// lane l <-> W[16 t + (l & 15)][4 ks + (l >> 4)] (pf_device.h: WideGvp); zero outside the matrix
+static std::vector<float> pack_wide_linear(const std::vector<float>& W, int n_out, int K) {
+    const int KS = (K + 3) / 4, NT = (n_out + 15) / 16;
+    std::vector<float> a((size_t)NT * KS * 64, 0.f);
+    for (int t = 0; t < NT; ++t)
+        for (int ks = 0; ks < KS; ++ks)
+            for (int l = 0; l < 64; ++l) {
+                const int n = 16 * t + (l & 15), k = 4 * ks + (l >> 4);
+                if (n < n_out && k < K) a[((size_t)t * KS + ks) * 64 + l] = W[(size_t)n * K + k];
+            }
+    return a;
+}
+// the six pieces of one GVP; appends their offsets (wh, wu, wm, bm, wg, bg) to off
+static void pack_wide_gvp(pf_handle* h, const GvpSpec& g, std::vector<size_t>& off) {
+    const int H = std::max(g.vi, g.vo);
+    off.push_back(push(h->h_w, h->raw[g.prefix + "Wh"].data));
+    off.push_back(push(h->h_w, h->raw[g.prefix + "Wu"].data));
+    off.push_back(push(h->h_w, pack_wide_linear(h->raw[g.prefix + "to_feats_out.0.weight"].data, g.so, g.si + H)));
+    off.push_back(push(h->h_w, h->raw[g.prefix + "to_feats_out.0.bias"].data));
+    off.push_back(push(h->h_w, pack_wide_linear(h->raw[g.prefix + "scalar_to_vector_gates.weight"].data, g.vo, g.so)));
+    off.push_back(push(h->h_w, h->raw[g.prefix + "scalar_to_vector_gates.bias"].data));
+}
 
 static GvpOff pack_gvp(pf_handle* h, const GvpSpec& g) {
     const int H = std::max(g.vi, g.vo);
@@ -971,7 +1006,7 @@ static bool share_now(pf_handle* h) {
         h->share_check = (h->l0flag_host && h->l0flag_host[1] == 0) ? 1 : 2;
     }
     if (h->share_check == 2) return false;           // (run_dynamics fails the call: a false claim is the caller's bug, not a mode)
-    return h->share_ok && !h->share_disable && h->prune && c.n_convs == 2 && h->rg_compact && l0_hoist_ok(h);
+    return !h->wide && h->share_ok && !h->share_disable && h->prune && c.n_convs == 2 && h->rg_compact && l0_hoist_ok(h);
 }
 // a build with these parameters has been enqueued: its stamp is what the next shared edge launch looks for
 static void build_done(pf_handle* h, bool share, bool with_records = false) {
@@ -1000,6 +1035,7 @@ static BuildParams build_params(pf_handle* h, bool share = false) {
 // conv layer 0 of an inference call runs on the row-group kernels: they encode the rows they read on the fly, so the
 // call's first launch is the edge build alone -- which the previous denoising step's update launch can do as well
 static bool encoders_on_the_fly(const pf_handle* h) {
+    if (h->wide) return false;          // (the width-generic family launches its encoders; pf_denoise_step: the update alone)
     const pf_config& c = h->cfg;
     const int prune_layer = (h->prune && c.n_convs >= 2) ? c.n_convs - 2 : -1;
     const int nt0 = c.n_convs == 1 ? h->n_edge_tiles_last : (prune_layer == 0 ? h->n_edge_tiles_act : h->n_edge_tiles);
@@ -1077,10 +1113,84 @@ static void n16_refresh(pf_handle* h, hipStream_t s) {
     h->n16_stale = false;
 }
 
+// One dynamics call on the width-generic family (pf_wide.hip): encoders, the edge build, per conv layer one message launch and
+// one node launch (the last one with the noise head).  The same tile lists as the specialised path: the last layer computes the
+// ff / pf messages and the centers only, the layer before it (receptive-field pruning) the active atoms and the centers.
+static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s, const float* t_scalar) {
+    const pf_config& c = h->cfg;
+    h->tail_done = false; h->last_tail = 0; h->last_hoist = 0;
+    h->cen_valid = false; h->last_cen = false; h->spec_valid = false; h->last_spec = 0; h->e0_saved = false;
+    // a pocket-group claim is verified as on the specialised path; the family then computes every graph itself
+    if (h->share_ok && h->share_check == 0) (void)share_now(h);
+    if (h->share_check == 2)
+        PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: the claim made for this batch is false -- a graph differs from its representative in "
+                               "coordinates or features (compared on the device); bind the batch again without the claim");
+    const int S = c.n_hidden_scalars, V = c.vector_size;
+    WideEncParams ep{};
+    ep.Np = h->Np; ep.Nf = h->Nf; ep.S = S; ep.rec_nf = c.rec_nf; ep.pharm_nf = c.pharm_nf;
+    ep.prot_h0 = h->d_prot_h0; ep.pharm_h = h->d_pharm_h;
+    ep.t = t_scalar ? nullptr : h->d_t; ep.t_scalar = t_scalar ? *t_scalar : 0.f; ep.gid = h->d_gid;
+    for (int nt = 0; nt < 2; ++nt) {
+        ep.w[nt] = h->d_w + h->enc_w[nt]; ep.b[nt] = h->d_w + h->enc_b[nt];
+        ep.ln_w[nt] = h->d_w + h->enc_lw[nt]; ep.ln_b[nt] = h->d_w + h->enc_lb[nt];
+    }
+    ep.h_out = h->d_h[0];
+    { ProfScope ps(h, pf_handle::K_ENCODE, s); pfk_wide_encode(&ep, s); }
+    if (!h->edges_built) {
+        const BuildParams bp = build_params(h, false);
+        { ProfScope ps(h, pf_handle::K_BUILD, s); pfk_build_edges(&bp, s); }
+        build_done(h, false);
+    }
+    const int prune_layer = (h->prune && c.n_convs >= 2) ? c.n_convs - 2 : -1;
+    h->last_family.assign(c.n_convs, 64);
+    int cur = 0;
+    for (int l = 0; l < c.n_convs; ++l) {
+        const bool last = l == c.n_convs - 1, pruned = l == prune_layer;
+        WideEdgeParams e{};
+        e.tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
+        e.ntiles = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles);
+        e.dyn_cnt = h->d_dyn_cnt; e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
+        e.h = h->d_h[cur]; e.v = h->d_v[cur]; e.layer0 = l == 0;
+        e.msg_s = h->d_msg_s; e.msg_v = h->d_msg_v;
+        e.w = h->d_wgvp + h->msg_base(l, 0); e.n_gvps = c.n_message_gvps; e.S = S; e.V = V;
+        linspace_f32(0.f, c.rbf_dmax, c.rbf_dim, e.rbf_mu);
+        e.rbf_sigma = (c.rbf_dmax - 0.f) / (float)c.rbf_dim;
+        { ProfScope ps(h, pf_handle::K_EDGE, s); pfk_wide_edge(&e, s); }
+        WideNodeParams n{};
+        n.tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
+        n.ntiles = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
+        n.dyn_cnt = h->d_dyn_cnt; n.row_ids = h->d_act_ids;
+        n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N; n.pp_slot = pruned ? 2 : 1;
+        n.msg_s = e.msg_s; n.msg_v = e.msg_v;
+        n.h_in = e.h; n.v_in = e.v; n.layer0 = e.layer0;
+        n.h_out = h->d_h[cur ^ 1]; n.v_out = h->d_v[cur ^ 1];
+        n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
+        for (int nt = 0; nt < 2; ++nt) {
+            const size_t* lo = &h->ln_off[(size_t)(l * 2 + nt) * 4];
+            n.ln1_w[nt] = h->d_w + lo[0]; n.ln1_b[nt] = h->d_w + lo[1];
+            n.ln2_w[nt] = h->d_w + lo[2]; n.ln2_b[nt] = h->d_w + lo[3];
+            n.upd[nt] = h->d_wgvp + h->upd_base(l, nt);
+        }
+        n.n_upd = c.n_update_gvps; n.S = S; n.V = V;
+        if (last) {             // the last layer's node tiles are the centers: the noise head follows in the same launch
+            n.head = h->d_wgvp + h->head_base(); n.n_head = c.n_noise_gvps;
+            n.w_out = h->d_w + h->wide_out_w; n.b_out = h->d_w + h->wide_out_b; n.pharm_nf = c.pharm_nf; n.node_base = h->Np;
+            n.eps_h = eps_h; n.eps_x = eps_x;
+            ProfScope ps(h, pf_handle::K_HEAD, s); pfk_wide_node(&n, s);
+        } else { ProfScope ps(h, pf_handle::K_NODE, s); pfk_wide_node(&n, s); }
+        cur ^= 1;
+    }
+    h->edges_built = false;                 // whoever moves the coordinates next rebuilds
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(err));
+    return PF_OK;
+}
+
 // step: this call is the dynamics call of a denoising step (pf_denoise_step) -- when the tail launch applies, the step's
 // sampler update and edge build run behind the noise head in the same launch and h->tail_done tells the caller
 static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s, const float* t_scalar = nullptr,
                         bool train = false, const StepParams* step = nullptr) {
+    if (h->wide && !train) return run_dynamics_wide(h, eps_h, eps_x, s, t_scalar);
     const pf_config& c = h->cfg;
     h->tail_done = false; h->last_tail = 0;
     // center hoist: the previous denoising step left h_c and P_ff / P_fp of every center for THIS call's timestep
@@ -1560,8 +1670,9 @@ int pf_create(const pf_config* cfg, pf_handle** out) {
     *out = nullptr;
     auto bad = [&](const char* m) { g_create_error = m; return PF_ERR_ARG; };
     if (cfg->abi_version != PF_ABI_VERSION) return bad("abi_version mismatch");
-    if (cfg->vector_size != PF_V) return bad("vector_size must be 16 (kernels are specialised)");
-    if (cfg->n_hidden_scalars != PF_S) return bad("n_hidden_scalars must be 128 (kernels are specialised)");
+    if (cfg->vector_size != 16 && cfg->vector_size != PFW_MAXV) return bad("vector_size must be 16 or 32");
+    if (cfg->n_hidden_scalars < 64 || cfg->n_hidden_scalars > PFW_MAXS || cfg->n_hidden_scalars % 32)
+        return bad("n_hidden_scalars must be a multiple of 32 in 64..256");
     if (cfg->rbf_dim != PF_R) return bad("rbf_dim must be 16");
     if (cfg->pharm_nf < 1 || cfg->pharm_nf > 16 || cfg->rec_nf < 1) return bad("pharm_nf must be in 1..16, rec_nf >= 1");
     if (cfg->n_convs < 1 || cfg->n_message_gvps < 1 || cfg->n_message_gvps > PF_MAX_GVPS || cfg->n_update_gvps < 1 ||
@@ -1578,6 +1689,14 @@ int pf_create(const pf_config* cfg, pf_handle** out) {
     pf_handle* h = new pf_handle();
     h->cfg = *cfg;
     h->init_tuning();
+    // (128, 16) runs on the specialised kernels; every other pair, and (128, 16) under PFDYN_WIDE=1, on the width-generic family
+    h->spec = cfg->n_hidden_scalars == PF_S && cfg->vector_size == PF_V;
+    const char* wv = getenv("PFDYN_WIDE");
+    h->wide = !h->spec || (wv && atoi(wv) != 0);
+    if (h->wide) {              // the specialised path's hoists, speculation and merged launches do not apply
+        h->l0_hoist = h->cen_hoist = h->pa_spec = false;
+        h->pol.hs_build = 0; h->pol.n16_mask = 0;
+    }
     *out = h;
     return PF_OK;
 }
@@ -1587,6 +1706,7 @@ void pf_destroy(pf_handle* h) {
     free_ws(h);
     if (h->d_w) (void)hipFree(h->d_w);
     if (h->d_gvp) (void)hipFree(h->d_gvp);
+    if (h->d_wgvp) (void)hipFree(h->d_wgvp);
     if (h->d_flat) (void)hipFree(h->d_flat);
     if (h->d_wpack) (void)hipFree(h->d_wpack);
     if (h->d_xstat) (void)hipFree(h->d_xstat);
@@ -1650,15 +1770,25 @@ int pf_commit_weights(pf_handle* h) {
     auto pack_all = [&]() {
         h->h_w.clear();
         offs.clear();
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int et = 0; et < 4; ++et)
-                for (int j = 0; j < c.n_message_gvps; ++j) offs.push_back(pack_gvp(h, msg_spec(c, l, et, j)));
-        h->n_msg_tot = (int)offs.size();
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int nt = 0; nt < 2; ++nt)
-                for (int j = 0; j < c.n_update_gvps; ++j) offs.push_back(pack_gvp(h, upd_spec(c, l, nt, j)));
-        h->n_upd_tot = (int)offs.size() - h->n_msg_tot;
-        for (int k = 0; k < c.n_noise_gvps; ++k) offs.push_back(pack_gvp(h, head_spec(c, k)));
+        h->wide_off.clear();
+        h->n_msg_tot = c.n_convs * 4 * c.n_message_gvps;
+        h->n_upd_tot = c.n_convs * 2 * c.n_update_gvps;
+        // every GVP in the GvpW table's order (message, update, head), the kernels' view of each
+        auto each_gvp = [&](auto fn) {
+            for (int l = 0; l < c.n_convs; ++l)
+                for (int et = 0; et < 4; ++et)
+                    for (int j = 0; j < c.n_message_gvps; ++j) fn(msg_spec(c, l, et, j));
+            for (int l = 0; l < c.n_convs; ++l)
+                for (int nt = 0; nt < 2; ++nt)
+                    for (int j = 0; j < c.n_update_gvps; ++j) fn(upd_spec(c, l, nt, j));
+            for (int k = 0; k < c.n_noise_gvps; ++k) fn(head_spec(c, k));
+        };
+        if (h->wide) {          // width-generic family: its GVPs and to_scalar_output as stored
+            each_gvp([&](const GvpSpec& g) { pack_wide_gvp(h, g, h->wide_off); });
+            h->wide_out_w = push(h->h_w, h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.weight"].data);
+            h->wide_out_b = push(h->h_w, h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.bias"].data);
+        }
+        if (h->spec) each_gvp([&](const GvpSpec& g) { offs.push_back(pack_gvp(h, g)); });
         for (int nt = 0; nt < 2; ++nt) {
             const std::string p = std::string("dynamics.") + kNtKey[nt] + "_encoder.";
             {   // encoder weight transposed to [nf+1][128]: coalesced loads of one input's column
@@ -1672,7 +1802,7 @@ int pf_commit_weights(pf_handle* h) {
             h->enc_lw[nt] = push(h->h_w, h->raw[p + "2.weight"].data);
             h->enc_lb[nt] = push(h->h_w, h->raw[p + "2.bias"].data);
         }
-        {   // protein encoder Linear [128][rec_nf+1] as A fragments [tile][k-step][lane]; k-step t, half hl <-> input 2t+hl
+        if (h->spec) {   // protein encoder Linear [128][rec_nf+1] as A fragments [tile][k-step][lane]; k-step t, half hl <-> input 2t+hl
             const RawTensor& W = h->raw["dynamics.prot_encoder.0.weight"];
             const RawTensor& Bv = h->raw["dynamics.prot_encoder.0.bias"];
             const int K = c.rec_nf + 1, nke = (K + 1) / 2;
@@ -1700,7 +1830,7 @@ int pf_commit_weights(pf_handle* h) {
                 lo[2] = push(h->h_w, h->raw[p2 + "weight"].data);
                 lo[3] = push(h->h_w, h->raw[p2 + "bias"].data);
             }
-        {   // to_scalar_output as A fragments: K = 64 (32 k-steps), rows = outputs
+        if (h->spec) {   // to_scalar_output as A fragments: K = 64 (32 k-steps), rows = outputs
             const RawTensor& W = h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.weight"];
             std::vector<float> a((size_t)32 * 64, 0.f);
             for (int ks = 0; ks < 32; ++ks)
@@ -1712,7 +1842,8 @@ int pf_commit_weights(pf_handle* h) {
             h->out_a = push(h->h_w, a);
             h->out_b = push(h->h_w, h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.bias"].data);
         }
-        {   // static hoist of conv layer 0 (pf_device.h L0H_*): pure copies of the first pp message GVP's pieces
+        h->l0c_off = 0;
+        if (h->spec) {   // static hoist of conv layer 0 (pf_device.h L0H_*): pure copies of the first pp message GVP's pieces
             const GvpSpec g = msg_spec(c, 0, ET_PP, 0);
             const std::vector<float>& W = h->raw[g.prefix + "to_feats_out.0.weight"].data;        // [128][144 + 17]
             const std::vector<float>& wh = h->raw[g.prefix + "Wh"].data;                          // [17][17]
@@ -1755,7 +1886,7 @@ int pf_commit_weights(pf_handle* h) {
                 h->l0c_off = push(h->h_w, cb);
             }
         }
-        {   // row-group quad streams, one contiguous stream per chain.  The pharm update chain of the last conv layer
+        if (h->spec) {   // row-group quad streams, one contiguous stream per chain.  The pharm update chain of the last conv layer
             // comes last and is followed by the noise head's chain and to_scalar_output: the fused node + head kernel
             // streams straight through.  RG_TAIL_PAD quads of padding: the prefetch ring reads ahead of the last quad used.
             h->rg_msg.assign((size_t)c.n_convs * 4, 0);
@@ -1815,8 +1946,8 @@ int pf_commit_weights(pf_handle* h) {
             st.resize(st.size() + (size_t)RG_TAIL_PAD * 256, 0.f);
             h->rgs_upd[(size_t)(c.n_convs - 1) * 2 + 1] = flush();
         }
-        h->n16_begin = h->h_w.size();            // everything packed from here on serves the n16 (inference-only) kernels
-        if (c.n_message_gvps >= 2 && c.n_update_gvps >= 1) {   // n16 quad streams: per chain wave 0's stream, then waves 1..3
+        h->n16_begin = h->spec ? h->h_w.size() : 0;     // everything packed from here on serves the n16 (inference-only) kernels
+        if (h->spec && c.n_message_gvps >= 2 && c.n_update_gvps >= 1) {   // n16 quad streams: per chain wave 0's stream, then waves 1..3
             h->n16_msg.assign((size_t)c.n_convs * 4, 0);
             h->n16_upd.assign((size_t)c.n_convs * 2, 0);
             std::vector<float> st;
@@ -1923,8 +2054,32 @@ int pf_commit_weights(pf_handle* h) {
         g.a_gate = h->d_w + o.a_gate; g.b_gate = h->d_w + o.b_gate;
         h->h_gvp.push_back(g);
     }
-    PF_HIP(h, hipMalloc((void**)&h->d_gvp, h->h_gvp.size() * sizeof(GvpW)));
-    PF_HIP(h, hipMemcpy(h->d_gvp, h->h_gvp.data(), h->h_gvp.size() * sizeof(GvpW), hipMemcpyHostToDevice));
+    if (!h->h_gvp.empty()) {
+        PF_HIP(h, hipMalloc((void**)&h->d_gvp, h->h_gvp.size() * sizeof(GvpW)));
+        PF_HIP(h, hipMemcpy(h->d_gvp, h->h_gvp.data(), h->h_gvp.size() * sizeof(GvpW), hipMemcpyHostToDevice));
+    }
+    if (h->d_wgvp) { (void)hipFree(h->d_wgvp); h->d_wgvp = nullptr; }
+    if (h->wide) {
+        std::vector<WideGvp> tab;
+        size_t i = 0;
+        auto add = [&](const GvpSpec& g) {
+            WideGvp w;
+            const size_t* o = &h->wide_off[i];
+            w.wh = h->d_w + o[0]; w.wu = h->d_w + o[1]; w.wm = h->d_w + o[2]; w.bm = h->d_w + o[3]; w.wg = h->d_w + o[4]; w.bg = h->d_w + o[5];
+            w.vi = g.vi; w.vo = g.vo; w.si = g.si; w.so = g.so;
+            tab.push_back(w);
+            i += 6;
+        };
+        for (int l = 0; l < c.n_convs; ++l)
+            for (int et = 0; et < 4; ++et)
+                for (int j = 0; j < c.n_message_gvps; ++j) add(msg_spec(c, l, et, j));
+        for (int l = 0; l < c.n_convs; ++l)
+            for (int nt = 0; nt < 2; ++nt)
+                for (int j = 0; j < c.n_update_gvps; ++j) add(upd_spec(c, l, nt, j));
+        for (int k = 0; k < c.n_noise_gvps; ++k) add(head_spec(c, k));
+        PF_HIP(h, hipMalloc((void**)&h->d_wgvp, tab.size() * sizeof(WideGvp)));
+        PF_HIP(h, hipMemcpy(h->d_wgvp, tab.data(), tab.size() * sizeof(WideGvp), hipMemcpyHostToDevice));
+    }
     h->h_w.clear();
     h->h_w.shrink_to_fit();
     {   // gradient path: the parameters once more as one flat vector in state-dict order, and where each GVP's tensors sit
@@ -2002,7 +2157,7 @@ int pf_commit_weights(pf_handle* h) {
     ++h->w_version;
     if (!h->d_l0c) PF_HIP(h, hipMalloc((void**)&h->d_l0c, 32 * sizeof(float)));
     if (h->d_ptab) { (void)hipFree(h->d_ptab); h->d_ptab = nullptr; }
-    PF_HIP(h, hipMalloc((void**)&h->d_ptab, (size_t)L0_PTAB_SLOTS * L0_NTAB * c.rec_nf * PF_S * sizeof(float)));
+    if (h->spec) PF_HIP(h, hipMalloc((void**)&h->d_ptab, (size_t)L0_PTAB_SLOTS * L0_NTAB * c.rec_nf * PF_S * sizeof(float)));
     return PF_OK;
 }
 
@@ -2253,19 +2408,22 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     // scratch
     // (a second set of message rows for the last conv layer: the fused launch of small n_convs = 2 batches writes them while conv
     // layer 0's are still being read)
-    const bool msg2 = c.n_convs == 2 && (long)h->n_edge_tiles_act * 32 <= h->pol.n16_rows_max;
+    const bool msg2 = !h->wide && c.n_convs == 2 && (long)h->n_edge_tiles_act * 32 <= h->pol.n16_rows_max;
+    // node state and message rows at the handle's widths; the tables of the specialised path's hoists only where it runs
+    const size_t S = (size_t)c.n_hidden_scalars, V3 = (size_t)3 * c.vector_size, SP = PF_S;
+    auto spec_only = [&](size_t b) { return h->spec ? b : (size_t)16; };
     const int64_t rec_slots = B <= 64 ? Ecap : 0;      // edge records: small batches only (the n16 fused launch)
     const size_t o_xn = place((size_t)N * 16),
                  o_fh = place((size_t)Nf * c.pharm_nf * 4 + 16), o_t = place((size_t)B * 4),
-                 o_h0 = place((size_t)N * PF_S * 4), o_h1 = place((size_t)N * PF_S * 4), o_v0 = place((size_t)N * 48 * 4), o_v1 = place((size_t)N * 48 * 4),
-                 o_ms = place((size_t)(Ecap + 1) * PF_S * 4), o_mv = place((size_t)(Ecap + 1) * 48 * 4),
+                 o_h0 = place((size_t)N * S * 4), o_h1 = place((size_t)N * S * 4), o_v0 = place((size_t)N * V3 * 4), o_v1 = place((size_t)N * V3 * 4),
+                 o_ms = place((size_t)(Ecap + 1) * S * 4), o_mv = place((size_t)(Ecap + 1) * V3 * 4),
                  o_ms2 = place(msg2 ? (size_t)(Ecap + 1) * PF_S * 4 : 16), o_mv2 = place(msg2 ? (size_t)(Ecap + 1) * 48 * 4 : 16),
                  o_eh = place((size_t)Nf * c.pharm_nf * 4 + 16), o_ex = place((size_t)Nf * 3 * 4 + 16), o_c0 = place((size_t)B * 3 * 4), o_c1 = place((size_t)B * 3 * 4),
-                 o_pre = place((size_t)std::max(Np, 1) * PF_S * 4), o_eorig = place(Ecap * 4), o_ptype = place((size_t)std::max(Np, 1) * 4),
+                 o_pre = place(spec_only((size_t)std::max(Np, 1) * SP * 4)), o_eorig = place(Ecap * 4), o_ptype = place((size_t)std::max(Np, 1) * 4),
                  o_rec = place((size_t)(h->pol.edge_rec ? 3 * rec_slots : 0) * 16 + 16),
-                 o_zs = place((size_t)std::max<int64_t>(n_pp, 1) * PF_S * 4), o_ptpg = place((size_t)B * L0_NTAB * c.rec_nf * PF_S * 4),
+                 o_zs = place(spec_only((size_t)std::max<int64_t>(n_pp, 1) * SP * 4)), o_ptpg = place(spec_only((size_t)B * L0_NTAB * c.rec_nf * SP * 4)),
                  o_xchg = place((size_t)2 * std::max(Nf, 1) * PF_XCHG_STRIDE * sizeof(unsigned int)),      // (+ the center hoist's copy)
-                 o_cenh = place((size_t)std::max(Nf, 1) * PF_S * 4), o_cenp = place((size_t)2 * std::max(Nf, 1) * PF_S * 4),
+                 o_cenh = place(spec_only((size_t)std::max(Nf, 1) * SP * 4)), o_cenp = place(spec_only((size_t)2 * std::max(Nf, 1) * SP * 4)),
                  o_snap = place((size_t)2 * (std::max(Nf, 1) * c.pharm_nf + 4) * 4);
     const size_t bytes = off;
     bool fresh = false;
@@ -2475,13 +2633,13 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     {
         ZeroBatch zb(s);
         zb.add(base, zero_bytes);
-        zb.add(h->d_v[0], (size_t)N * 48 * 4);
+        zb.add(h->d_v[0], (size_t)N * V3 * 4);
         if (fresh) {
-            zb.add(h->d_msg_s, (size_t)(Ecap + 1) * PF_S * 4);
-            zb.add(h->d_msg_v, (size_t)(Ecap + 1) * 48 * 4);
+            zb.add(h->d_msg_s, (size_t)(Ecap + 1) * S * 4);
+            zb.add(h->d_msg_v, (size_t)(Ecap + 1) * V3 * 4);
         } else {
-            zb.add(h->d_msg_s + (size_t)Ecap * PF_S, PF_S * 4);
-            zb.add(h->d_msg_v + (size_t)Ecap * 48, 48 * 4);
+            zb.add(h->d_msg_s + (size_t)Ecap * S, S * 4);
+            zb.add(h->d_msg_v + (size_t)Ecap * V3, V3 * 4);
         }
         if (h->d_msg_s2) {
             if (fresh) {
@@ -2811,6 +2969,7 @@ int64_t pf_debug_get_edges(pf_handle* h, int32_t etype, int32_t* host_src, int32
 int pf_debug_conv_layer(pf_handle* h, int32_t layer, const float* dev_prot_x, const float* dev_pharm_x,
                         const float* hp_, const float* vp_, const float* hf_, const float* vf_,
                         float* ohp, float* ovp, float* ohf, float* ovf, pf_stream stream) {
+    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: specialised to n_hidden_scalars 128 / vector_size 16", __func__);
     int rc = check_ready(h, true);
     if (rc) return rc;
     const pf_config& c = h->cfg;
@@ -3038,6 +3197,8 @@ int pf_get_flat_params(pf_handle* h, float* dev_flat, pf_stream stream) {
 
 int pf_train_forward(pf_handle* h, const float* dev_prot_x, const float* dev_pharm_x, const float* dev_pharm_h,
                      const float* dev_t, float dropout_p, uint32_t seed, float* dev_eps_h, float* dev_eps_x, pf_stream stream) {
+    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
+                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_pharm_x || !dev_pharm_h || !dev_t || !dev_eps_h || !dev_eps_x) PF_FAIL(h, PF_ERR_ARG, "pf_train_forward: null argument");
@@ -3067,6 +3228,8 @@ int pf_train_loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* 
                           const float* dev_eps_x, const float* dev_eps_h, const float* dev_alpha, const float* dev_sigma,
                           int32_t n_timesteps, float feat_norm, int32_t remove_com, int32_t weighted_loss, float dropout_p,
                           uint32_t seed, float* dev_out, pf_stream stream) {
+    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
+                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_pharm_x0 || !dev_pharm_h0 || !dev_t_int || !dev_eps_x || !dev_eps_h || !dev_alpha || !dev_sigma || !dev_out)
@@ -3128,10 +3291,14 @@ static int loss_backward(pf_handle* h, const float* g_pos, const float* g_pos2, 
 }
 
 int pf_train_loss_backward(pf_handle* h, const float* dev_g_pos, const float* dev_g_feat, float* dev_grad, pf_stream stream) {
+    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
+                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
     return loss_backward(h, dev_g_pos, nullptr, dev_g_feat, nullptr, dev_grad, stream, "pf_train_loss_backward");
 }
 
 int pf_train_loss_backward_out(pf_handle* h, const float* dev_g_out, float* dev_grad, pf_stream stream) {
+    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
+                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
     if (h && !dev_g_out) PF_FAIL(h, PF_ERR_ARG, "pf_train_loss_backward_out: null argument");
     // upstream gradients of the nine outputs: [0] and [1] of the two losses, [6] of their sum; the metrics carry none
     return loss_backward(h, dev_g_out, dev_g_out ? dev_g_out + 6 : nullptr, dev_g_out ? dev_g_out + 1 : nullptr,
@@ -3139,6 +3306,8 @@ int pf_train_loss_backward_out(pf_handle* h, const float* dev_g_out, float* dev_
 }
 
 int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, pf_stream stream) {
+    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
+                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!h->t_have_fwd) PF_FAIL(h, PF_ERR_STATE, "pf_train_backward: no pf_train_forward on this batch");
@@ -3459,6 +3628,7 @@ int pf_debug_xchg_timeouts(pf_handle* h, int32_t* n) {
 
 int pf_debug_chain(pf_handle* h, int32_t kind, int32_t layer, int32_t sub, int32_t n_rows, const float* dev_s_in, const float* dev_v_in,
                    float* dev_s_out, float* dev_v_out, pf_stream stream) {
+    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: specialised to n_hidden_scalars 128 / vector_size 16", __func__);
     int rc = check_ready(h, false);
     if (rc) return rc;
     const pf_config& c = h->cfg;
