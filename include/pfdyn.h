@@ -319,6 +319,11 @@ int pf_debug_kernel_family(pf_handle* h, int32_t layer, int32_t* rows_per_wave);
  * Also: pf_debug_kernel_family(layer = n_convs + 1) = 1 when the LAST call's ff / fp items started from those tables, (n_convs + 2) = 1
  * when it skipped regions computed ahead.  Synchronises the stream. */
 int pf_debug_ahead(pf_handle* h, int64_t* out /*[4]*/, pf_stream stream);
+/* the check of the rows computed ahead (PFDYN_PA_CHECK=1 at pf_create; zeros otherwise), cumulative since the handle's first batch:
+ * violations[0] = kept "pa" groups (those a conv-layer-0 launch skipped: j < min(pa_same[g], groups of g)) that the speculative
+ * items of the previous step did NOT compute; [1] = kept groups checked; [2] = kept groups of a graph in front of which the group
+ * count of the B regions changed between the two calls (where a map over the live counts goes wrong).  Synchronises the stream. */
+int pf_debug_pa_check(pf_handle* h, int64_t* violations /*[3]*/, pf_stream stream);
 /* the exchange time-outs of k_rg_node_hs_build counted on this handle since it was created (cumulative; pf_sample_status is the
  * product-path check and reports new ones per run).  Synchronises the device. */
 int pf_debug_xchg_timeouts(pf_handle* h, int32_t* n);

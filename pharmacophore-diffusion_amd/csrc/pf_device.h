@@ -244,6 +244,13 @@ struct EdgeParams {
     // [B] or NULL: per graph, the number of leading 16-slot groups of the "pa" region this launch skips -- their partial rows were
     // computed ahead (the previous step's last launch) and that step's build found the region unchanged up to there (BuildParams::pa_same)
     const int* pa_skip;
+    // [B] or NULL: conv layer 0's launch leaves the B kind-3 counts it consumed here (its first workgroup).  The speculative items of the
+    // merged last launch map their item number to (graph, 16-slot group) on this copy: the update + build of the same launch rewrite
+    // dyn_cnt, and nothing orders the two
+    int* cnt_snap;
+    // PFDYN_PA_CHECK: [Ecap / 16 + 1] the serial of the speculative launch that last computed each 16-slot group (the group's first
+    // slot / 16; regions are 32-aligned), or NULL
+    int* pa_gstamp; int pa_serial;
 };
 
 // static-hoist source block in the packed weights (pure copies of the first pp message GVP of conv layer 0 and of the

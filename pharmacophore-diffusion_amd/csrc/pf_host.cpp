@@ -38,6 +38,9 @@ void pfk_rg_node_hs_build(const NodeParams* p, const HeadParams* hp, const StepP
                           int avoid, int poll_max, const CenHoistParams* cp, const EdgeParams* es, const EncodeParams* ees, int spec_groups,
                           hipStream_t s);
 void pfk_n16_edge(const EdgeParams* p, const EncodeParams* enc, int layer0, hipStream_t s);
+void pfk_pa_spec(const EdgeParams* es, const EncodeParams* ees, int groups, int after, int k, int frac, int* word, hipStream_t s);
+void pfk_pa_check(const int* dyn_cnt, const int* cnt_snap, const int* reg, const int* pa_same, const int* gstamp, int serial, int B,
+                  unsigned long long* out, hipStream_t s);
 void pfk_n16_unit(const UnitParams* p, hipStream_t s);
 void pfk_n16_fused(const EdgeParams* p, const FusedParams* f, const EncodeParams* enc, hipStream_t s);
 void pfk_n16_tail(const TailParams* t, const StepParams* sp, const BuildParams* bp, hipStream_t s);
@@ -347,6 +350,16 @@ struct pf_handle {
     bool e0_saved = false; EdgeParams e0{}; EncodeParams ep0{}; int e0_groups = 0;
     int last_spec = 0;                      // the last dynamics call skipped "pa" regions computed ahead (pf_debug_kernel_family(n_convs + 2): 1)
                                             // when the next one begins: a time-out there is reported, late but never silently
+    int* d_pa_cnt = nullptr;                // [B] the kind-3 counts conv layer 0 consumed (EdgeParams::cnt_snap): the speculative items' map
+    // test knobs.  PFDYN_PA_SPEC_SPLIT=k: the speculative items leave the merged launch; items w < k run in a launch of their
+    // own just before it (the counts before the build), items w >= k just after it (the counts after the build); k > 0 fixed, "mid": half of
+    // the non-empty groups, "step": a fraction of them the host picks per step.  PFDYN_PA_CHECK=1: every speculative item stamps its group with the serial
+    // of the launch it belongs to, and a check in front of the next call's conv layer 0 counts the kept groups whose stamp is not that serial
+    int pa_spec_split = 0;                  // 0 off, > 0 fixed k, -1 mid, -2 per step
+    bool pa_check = false;
+    int pa_serial = 0, spec_serial = 0;
+    int* d_pa_gstamp = nullptr;             // [Ecap / 16 + 1] in the workspace (PFDYN_PA_CHECK only)
+    unsigned long long* d_pa_chk = nullptr; // [3] violations, kept groups checked, kept groups behind a changed prefix (per handle, cumulative)
     bool no_fixed_shapes = false;           // PFDYN_NO_FIXED_SHAPES: k_bwd_edge_level reads every level's GVP shape from the table (the A/B of its FX forms)
     ScaleArgs pend_scale{}; bool has_pend_scale = false;    // loss_backward -> pf_train_backward: the unit gradients' scaling, not yet launched
     bool no_fix_fuse = false;               // PFDYN_NO_FIX_FUSE: k_fix_apply and k_enc_group as two launches (the A/B of k_fix_enc_group)
@@ -422,6 +435,8 @@ struct pf_handle {
         if (const char* e = getenv("PFDYN_NO_L0_HOIST")) l0_hoist = atoi(e) == 0;
         if (const char* e = getenv("PFDYN_NO_CENTER_HOIST")) cen_hoist = atoi(e) == 0;
         if (const char* e = getenv("PFDYN_NO_PA_SPEC")) pa_spec = atoi(e) == 0;
+        if (const char* e = getenv("PFDYN_PA_SPEC_SPLIT")) pa_spec_split = !strcmp(e, "mid") ? -1 : (!strcmp(e, "step") ? -2 : std::max(atoi(e), 0));
+        if (const char* e = getenv("PFDYN_PA_CHECK")) pa_check = atoi(e) != 0;
         if (const char* e = getenv("PFDYN_NO_POCKET_SHARE")) share_disable = atoi(e) != 0;
         if (const char* e = getenv("PFDYN_TRAIN_TILE_NODE")) train_rg_node = atoi(e) == 0;
         if (const char* e = getenv("PFDYN_TRAIN_TILE_EDGE")) train_rg_edge = atoi(e) == 0;
@@ -961,7 +976,7 @@ static void pack_n16_head_last(pf_handle* h, const GvpSpec& g, int w, std::vecto
 // keep_ws: the inference workspace stays allocated (pf_set_pocket_batch re-carves it when the next batch fits: a
 // hipMalloc / hipFree pair of a few hundred MB per batch costs milliseconds)
 static void free_ws(pf_handle* h, bool keep_ws = false) {
-    if (h->d_ws && !keep_ws) { (void)hipFree(h->d_ws); h->d_ws = nullptr; h->ws_capacity = 0; h->d_xchg = nullptr; h->d_lpart = nullptr; h->d_xchg2 = nullptr; h->d_cen_h = h->d_cen_p = nullptr; h->d_snap[0] = h->d_snap[1] = nullptr; h->d_pa_stamp = h->d_pa_same = nullptr; }
+    if (h->d_ws && !keep_ws) { (void)hipFree(h->d_ws); h->d_ws = nullptr; h->ws_capacity = 0; h->d_xchg = nullptr; h->d_lpart = nullptr; h->d_xchg2 = nullptr; h->d_cen_h = h->d_cen_p = nullptr; h->d_snap[0] = h->d_snap[1] = nullptr; h->d_pa_stamp = h->d_pa_same = nullptr; h->d_pa_cnt = h->d_pa_gstamp = nullptr; }
     if (h->d_tws && !keep_ws) { (void)hipFree(h->d_tws); h->d_tws = nullptr; h->tws_capacity = 0; }
     if (h->d_tA && !keep_ws) { (void)hipFree(h->d_tA); h->d_tA = nullptr; h->tA_capacity = 0; }
     h->t_ws_ready = false;
@@ -1378,6 +1393,7 @@ static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s,
             }
             rg = 4;                                  // 16 slots per partial-row group
             if (l == 0 && e.x0_static && h->pa_spec && !shared && h->B <= 64 && !e.need) {      // what k_n16_pa_spec needs of this launch (the regions, streams and tables of conv layer 0)
+                e.cnt_snap = h->d_pa_cnt;                // (this launch leaves the kind-3 counts it consumed there: the speculative items' map)
                 h->e0 = e; h->ep0 = ep; h->e0_saved = true;
                 h->e0_groups = 0;
                 for (int g = 0; g < h->B; ++g) h->e0_groups += region_groups(3 * h->B + g, 16);
@@ -1419,7 +1435,13 @@ static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s,
             h->last_family[l] = 17;                      // pf_debug_kernel_family: 16-row items with conv layer 0's node update in front
             { ProfScope ps(h, pf_handle::K_EDGE_LAST, s); pfk_n16_fused(&e, &fz, &ep, s); }
         }
-        else if (n16e) { ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_n16_edge(&e, &ep, l == 0, s); }
+        else if (n16e) {
+            // PFDYN_PA_CHECK: the kept groups of the rows computed ahead must carry the serial of the launch that computed them (before this
+            // launch overwrites the count snapshot the check compares with)
+            if (l == 0 && e.pa_skip && h->d_pa_gstamp && h->d_pa_chk)
+                pfk_pa_check(h->d_dyn_cnt, h->d_pa_cnt, e.reg, e.pa_skip, h->d_pa_gstamp, h->spec_serial, h->B, h->d_pa_chk, s);
+            ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_n16_edge(&e, &ep, l == 0, s);
+        }
         else if (rg) { ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_rg_edge(&e, enc_fly ? &ep : nullptr, l == 0, rg, esplit, rgp, s); }
         else if (e.ntiles <= h->pol.coop_edge_max && !train) { ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_edge_msg_coop(&e, l == 0, s); }
         else if (e.ntiles <= ((last || pruned) ? h->pol.coop2_edge_max : h->pol.coop2_dense_max) && !train) { ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_edge_msg_coop2(&e, l == 0, s); }
@@ -1554,6 +1576,8 @@ static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s,
                             ees = h->ep0; ees.t_scalar = tn;
                             spec_groups = h->e0_groups;
                             h->spec_valid = true; h->spec_t = tn; h->spec_wver = h->w_version;
+                            es.pa_serial = h->spec_serial = ++h->pa_serial;
+                            es.pa_gstamp = h->d_pa_gstamp;
                         }
                     }
                     if (t_next == t_next) {
@@ -1572,7 +1596,16 @@ static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s,
                     // edge records for the next call's fused launch: radius ff edges, compact "pa" regions, the static hoist's element types
                     const bool with_rec = h->d_rec && !share_next && c.ff_k == 0 && bpn.act_ids && !bpn.pa_static && h->last_hoist == 16 && fuse_l0node;
                     if (with_rec) { bpn.rec = h->d_rec; bpn.ptype = h->d_ptype; }
-                    { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_node_hs_build(&n, &hp, step, &bpn, h->d_xstat, h->pol.xchg_sleep, h->pol.hsb_avoid, h->xchg_poll_max, &cp, &es, &ees, spec_groups, s); }
+                    // PFDYN_PA_SPEC_SPLIT (test knob): no speculative slots in the merged launch; items w < k run just before it (the kind-3
+                    // counts before the build), w >= k just after it (the counts after the build).  "mid" / "step": k is half / a per-step
+                    // fraction of the non-empty groups, fixed by the launch in front (k_pa_spec)
+                    const bool split = spec_groups > 0 && h->pa_spec_split != 0;
+                    if (split) {
+                        const int frac = h->pa_spec_split == -1 ? 128 : (h->pa_spec_split == -2 ? (int)((((uint32_t)h->pa_serial * 2654435761u) >> 16) & 255) + 1 : 0);
+                        pfk_pa_spec(&es, &ees, spec_groups, 0, std::max(h->pa_spec_split, 0), frac, h->d_pa_cnt + h->B, s);
+                    }
+                    { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_node_hs_build(&n, &hp, step, &bpn, h->d_xstat, h->pol.xchg_sleep, h->pol.hsb_avoid, h->xchg_poll_max, &cp, &es, &ees, split ? 0 : spec_groups, s); }
+                    if (split) pfk_pa_spec(&es, &ees, spec_groups, 1, 0, 0, h->d_pa_cnt + h->B, s);
                     build_done(h, share_next, with_rec);
                     h->tail_done = true; h->last_tail = 2;
                 } else { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_node(&n, &hp, enc_fly ? &ep : nullptr, l == 0, rgn, nsplit, s); }
@@ -1710,6 +1743,7 @@ void pf_destroy(pf_handle* h) {
     if (h->d_flat) (void)hipFree(h->d_flat);
     if (h->d_wpack) (void)hipFree(h->d_wpack);
     if (h->d_xstat) (void)hipFree(h->d_xstat);
+    if (h->d_pa_chk) (void)hipFree(h->d_pa_chk);
     if (h->xstat_host) (void)hipHostFree(h->xstat_host);
     if (h->d_tseg) (void)hipFree(h->d_tseg);
     if (h->d_gvpt) (void)hipFree(h->d_gvpt);
@@ -2403,7 +2437,9 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     const size_t o_dyn = place((size_t)5 * B * 4), o_act = place((size_t)(act_total + 1) * 4), o_flag = place(256), o_gnorm = place((size_t)2 * B * 4),
                  o_need = place((size_t)std::max(Np, 1) * 4),
                  o_lpart = place(64 + (size_t)((Nf + 63) / 64) * 8 * sizeof(float)),       // k_loss_eval's ticket (re-armed by its last block) + partial sums
-                 o_pastamp = place((size_t)std::max(Np, 1) * 4), o_pasame = place((size_t)B * 4);      // speculative "pa" messages: per-atom step stamps, per-graph verdicts
+                 o_pastamp = place((size_t)std::max(Np, 1) * 4), o_pasame = place((size_t)B * 4),      // speculative "pa" messages: per-atom step stamps, per-graph verdicts
+                 o_pacnt = place((size_t)(B + 1) * 4),                                                 // ... the kind-3 counts they are mapped on (+ PFDYN_PA_SPEC_SPLIT's k)
+                 o_pagst = place(h->pa_check ? (size_t)(std::max<int64_t>(Ecap, 1) / 16 + 1) * 4 : 16);      // PFDYN_PA_CHECK: per-group stamps
     const size_t zero_bytes = off;
     // scratch
     // (a second set of message rows for the last conv layer: the fused launch of small n_convs = 2 batches writes them while conv
@@ -2483,6 +2519,11 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     h->d_snap[0] = (float*)at(o_snap); h->d_snap[1] = h->d_snap[0] + (size_t)std::max(Nf, 1) * c.pharm_nf + 4;
     h->cen_valid = false; h->snap_cur = -1;
     h->d_pa_stamp = (int*)at(o_pastamp); h->d_pa_same = (int*)at(o_pasame); h->spec_valid = false; h->e0_saved = false;
+    h->d_pa_cnt = (int*)at(o_pacnt); h->d_pa_gstamp = h->pa_check ? (int*)at(o_pagst) : nullptr;
+    if (h->pa_check && !h->d_pa_chk) {                           // once per handle: the check's counters
+        PF_HIP(h, hipMalloc((void**)&h->d_pa_chk, 3 * sizeof(unsigned long long)));
+        PF_HIP(h, hipMemset(h->d_pa_chk, 0, 3 * sizeof(unsigned long long)));
+    }
     mark();      // 2: workspace ready
     // ---- stage the tables in pinned memory and upload them with one asynchronous copy
     const int sb = h->stage_next;
@@ -3586,6 +3627,20 @@ int pf_debug_ahead(pf_handle* h, int64_t* out, pf_stream stream) {
         }
     }
     if (h->cen_valid) { out[2] = 1; out[3] = h->Nf; }
+    return PF_OK;
+}
+
+int pf_debug_pa_check(pf_handle* h, int64_t* out, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!out) PF_FAIL(h, PF_ERR_ARG, "pf_debug_pa_check: null argument");
+    out[0] = out[1] = out[2] = 0;
+    PF_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+    if (h->d_pa_chk) {
+        unsigned long long v[3];
+        PF_HIP(h, hipMemcpy(v, h->d_pa_chk, sizeof(v), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 3; ++k) out[k] = (int64_t)v[k];
+    }
     return PF_OK;
 }
 

@@ -61,6 +61,7 @@ __global__ __launch_bounds__(256) void k_n16_edge(const int* __restrict__ a_dyn_
     const int item = (int)blockIdx.x;
     int sk = (L0 ? 0 : 1) << 8;
     N16_STAMP(sk, lane, wq);                              // kernel entry
+    if (L0 && p.cnt_snap && item == 0 && threadIdx.x < 64 && lane < a_regB) p.cnt_snap[lane] = a_dyn_cnt[3 * a_regB + lane];      // (EdgeParams::cnt_snap)
     int e0, nv, et;
     if (a_nreg > 0) {
         // compact work list (see k_rg_edge): every wave of the workgroup finds the item's region by the same wave scan
@@ -179,6 +180,7 @@ __global__ __launch_bounds__(256) void k_n16_edge_u(const int* __restrict__ a_dy
     const int gff = (a_s2g >> 16) & 7, gpf = (a_s2g >> 19) & 7, gfp = (a_s2g >> 22) & 7, a_B = (int)((unsigned)a_s2g >> 25) + 1;
     const int nff = a_B * gff, npf = a_B * gpf, nfp = a_B * gfp;
     int w = (int)blockIdx.x;
+    if (p.cnt_snap && w == 0 && threadIdx.x < 64 && lane < a_B) p.cnt_snap[lane] = a_dyn_cnt[3 * a_B + lane];      // (EdgeParams::cnt_snap)
 #ifdef EDGE_U_SWAP                                        // (diagnostic: ff and fp items trade places in the grid; needs nff == nfp)
     if (w < nff) w += nff + npf; else if (w >= nff + npf && w < nff + npf + nfp) w -= nff + npf;
 #endif

@@ -443,6 +443,19 @@ class PfEngine:
             self._ck(self.lib.pf_debug_ahead(self._h, out, _stream_ptr()), "pf_debug_ahead")
         return dict(zip(("pa_skipped", "pa_ahead", "center_hoist", "centers"), list(out)))
 
+    def pa_check_counts(self):
+        """The check of the rows computed ahead (pf_debug_pa_check; PFDYN_PA_CHECK=1 when the handle was created), cumulative:
+        dict(violations = kept "pa" groups the previous step's speculative items did not compute, checked = kept groups checked,
+        exposed = kept groups of a graph behind a changed group count of an earlier graph)."""
+        out = (ctypes.c_int64 * 3)()
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_debug_pa_check(self._h, out, _stream_ptr()), "pf_debug_pa_check")
+        return dict(zip(("violations", "checked", "exposed"), list(out)))
+
+    def pa_check(self) -> int:
+        """Violations counted by the check of the rows computed ahead (see pa_check_counts)."""
+        return self.pa_check_counts()["violations"]
+
     def l0_hoist(self) -> int:
         """Rows per hoisted wave of conv layer 0's pp messages in the last dynamics call (0: static hoist not used)."""
         r = ctypes.c_int32()
