@@ -118,7 +118,9 @@ static void linspace_f32(float start, float end, int steps, float* out) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------
-// Launch policy of the inference path: which kernel form a launch takes.  One place, one table.
+// Launch policy of the inference path: which kernel form a launch takes.  One place, one table.  The rows are implemented by the pieces of
+// run_dynamics: the edge rows by edge_launch (n16 form: edge_n16_form; row 1: fused_take_node), the node and "nodes + head" rows by node_launch
+// (bit 3's launch: tail_launch; the merged last launch of a denoising step: merged_step_launch), a head of its own by head_launch.
 //
 // The chip: 256 compute units (CUs) = 1,024 SIMDs.  A launch is in the LATENCY regime while it has about as many items
 // as the chip has places to put them (its duration is one item's chain of dependent GVPs), in the THROUGHPUT regime beyond.
@@ -147,13 +149,13 @@ static void linspace_f32(float start, float end, int steps, float* out) {
 //   layers; PFDYN_RG_ROWS_MAX=0)  |                            |   coop2_*_max, one wave per tile beyond
 //
 // Every threshold can be overridden from the environment (tests force every form onto the goldens; sweeps: tools/):
-//   PFDYN_N16 (bit 0: conv layers >= 1, bit 1: conv layer 0, bit 2: conv layer 0's node update fused into the last layer's edge
-//   launch when n_convs = 2, bit 3: the tail launch of a denoising step -- last node update + noise head + sampler update + edge
-//   build, one workgroup per graph: off unless asked for; default 7), PFDYN_TAIL_GRAPHS_MAX, PFDYN_TAIL_FORM (rg | n16), PFDYN_N16_ROWS_MAX (sets both n16 thresholds), PFDYN_N16_FUSE_ROWS_MAX, PFDYN_RG_ROWS_MAX,
-//   PFDYN_RG2_ROWS_MIN (sets all four 8-row thresholds) / _NODE / _HOIST, PFDYN_RG2P_ROWS_MIN, PFDYN_L0_RGA / PFDYN_L0_RGP (rows-per-
-//   wave factor of the full-chain / hoisted items of a compact layer-0 launch), PFDYN_RG_SPLIT_MAX (all three) / _NODE / _HEAD,
-//   PFDYN_COOP_EDGE_MAX, PFDYN_COOP2_EDGE_MAX, PFDYN_COOP_NODE_MAX.  Forcing a row-group form switches the n16 form off
-//   unless PFDYN_N16 is given.  Feature switches (not thresholds) are read in pf_handle::init_tuning.
+//   PFDYN_N16 (bit 0: conv layers >= 1, bit 1: conv layer 0, bit 2: conv layer 0's node update fused into the last layer's edge launch when
+//   n_convs = 2, bit 3: the tail launch of a denoising step -- last node update + noise head + sampler update + edge build, one workgroup per
+//   graph: off unless asked for; default 7), PFDYN_TAIL_GRAPHS_MAX, PFDYN_TAIL_FORM (rg | n16), PFDYN_N16_ROWS_MAX (sets both n16 thresholds),
+//   PFDYN_N16_FUSE_ROWS_MAX, PFDYN_RG_ROWS_MAX, PFDYN_RG2_ROWS_MIN (sets all four 8-row thresholds) / _NODE / _HOIST, PFDYN_RG2P_ROWS_MIN,
+//   PFDYN_L0_RGA / PFDYN_L0_RGP (rows-per-wave factor of the full-chain / hoisted items of a compact layer-0 launch), PFDYN_RG_SPLIT_MAX (all
+//   three) / _NODE / _HEAD, PFDYN_COOP_EDGE_MAX, PFDYN_COOP2_EDGE_MAX, PFDYN_COOP_NODE_MAX.  Forcing a row-group form switches the n16 form
+//   off unless PFDYN_N16 is given.  Feature switches (not thresholds) are read in pf_handle::init_tuning.
 // ------------------------------------------------------------------------------------------------------------------
 struct LaunchPolicy {
     static constexpr int kCUs = 256, kSIMDs = 4 * kCUs;
@@ -1013,6 +1015,8 @@ struct ProfScope {
 };
 
 static bool l0_hoist_ok(pf_handle* h);
+// the conv layer restricted to active atoms (receptive-field pruning of the second-to-last layer); -1: none
+static int prune_layer(const pf_handle* h) { return (h->prune && h->cfg.n_convs >= 2) ? h->cfg.n_convs - 2 : -1; }
 // pocket sharing applies to inference calls at one common t whose conv layer 0 is the pruned layer under the static hoist
 static bool share_now(pf_handle* h) {
     const pf_config& c = h->cfg;
@@ -1023,6 +1027,10 @@ static bool share_now(pf_handle* h) {
     if (h->share_check == 2) return false;           // (run_dynamics fails the call: a false claim is the caller's bug, not a mode)
     return !h->wide && h->share_ok && !h->share_disable && h->prune && c.n_convs == 2 && h->rg_compact && l0_hoist_ok(h);
 }
+// what the next denoising step's dynamics call will ask for (the mode its edges are built in)
+static bool share_next(pf_handle* h) { return (h->prune && h->cfg.n_convs == 2) && share_now(h); }
+// the fast update + build's shape (one atom per thread, the latency-optimised kernel): kNN pf edges, pockets of at most 512 atoms
+static bool step_build_fast_ok(const pf_handle* h) { return h->cfg.pf_k > 0 && h->max_np <= 512 && h->cfg.pharm_nf <= 16 && h->step_build_fast; }
 // a build with these parameters has been enqueued: its stamp is what the next shared edge launch looks for
 static void build_done(pf_handle* h, bool share, bool with_records = false) {
     h->rec_valid = with_records;
@@ -1040,20 +1048,107 @@ static BuildParams build_params(pf_handle* h, bool share = false) {
     bp.r2_ff = c.cutoff_ff * c.cutoff_ff; bp.r2_pf = c.cutoff_pf * c.cutoff_pf;
     bp.gnorm = h->d_gnorm; bp.pp_cnt = h->d_pp_cnt; bp.pfq_cnt = h->d_pfq_cnt; bp.norm_mode = c.message_norm_mode;
     if (h->pa_spec && h->sampling && h->d_pa_stamp && !share) { bp.pa_stamp = h->d_pa_stamp; bp.step_id = h->step_id; bp.pa_same = h->d_pa_same; }
-    const int prune_layer = (h->prune && c.n_convs >= 2) ? c.n_convs - 2 : -1;
-    bp.act_ids = prune_layer >= 0 ? h->d_act_ids : nullptr; bp.reg_act = h->d_reg_act;
+    bp.act_ids = prune_layer(h) >= 0 ? h->d_act_ids : nullptr; bp.reg_act = h->d_reg_act;
     bp.eorig = h->d_eorig;
     bp.pa_static = share ? h->d_pa_static : nullptr;
     if (share) { bp.rep_base = h->d_rep_base; bp.need = h->d_need; bp.need_stamp = h->need_stamp + 1; }   // committed by build_done()
     return bp;
 }
+// ---- one builder per parameter struct (what does not depend on the call's mode; callers add the rest), one predicate per gate ----
+// RBF centres (torch.linspace(0, dmax, dim)) and width of the edge distance embedding; returns sigma
+static float rbf_params(const pf_config& c, float* mu, float* inv_sigma) {
+    linspace_f32(0.f, c.rbf_dmax, c.rbf_dim, mu);
+    const float sigma = (c.rbf_dmax - 0.f) / (float)c.rbf_dim;
+    if (inv_sigma) *inv_sigma = 1.0f / sigma;
+    return sigma;
+}
+static EncodeParams encode_params(const pf_handle* h, const float* t_scalar, float* h_out) {
+    const pf_config& c = h->cfg;
+    EncodeParams ep{};
+    ep.Np = h->Np; ep.Nf = h->Nf; ep.rec_nf = c.rec_nf; ep.pharm_nf = c.pharm_nf;
+    ep.prot_h0 = h->d_prot_h0; ep.pharm_h = h->d_pharm_h; ep.gid = h->d_gid; ep.h_out = h_out;
+    ep.t = t_scalar ? nullptr : h->d_t; ep.t_scalar = t_scalar ? *t_scalar : 0.f;
+    for (int nt = 0; nt < 2; ++nt) {
+        ep.w[nt] = h->d_w + h->enc_w[nt]; ep.b[nt] = h->d_w + h->enc_b[nt];
+        ep.ln_w[nt] = h->d_w + h->enc_lw[nt]; ep.ln_b[nt] = h->d_w + h->enc_lb[nt];
+    }
+    return ep;
+}
+// the noise head; h / v (a launch of its own reads the last layer's output) and the exchange words (merged launch) are the caller's
+static HeadParams head_params(const pf_handle* h, float* eps_h, float* eps_x) {
+    const pf_config& c = h->cfg;
+    HeadParams hp{};
+    hp.tiles = h->d_head_tiles; hp.ntiles = h->n_head_tiles; hp.node_base = h->Np;
+    hp.gvps = h->d_gvp + h->head_base(); hp.n_gvps = c.n_noise_gvps;
+    hp.a_out = h->d_w + h->out_a; hp.b_out = h->d_w + h->out_b; hp.pharm_nf = c.pharm_nf; hp.eps_h = eps_h; hp.eps_x = eps_x;
+    return hp;
+}
+// edge messages of a conv layer: tiles, geometry, GVP table, RBF, the row-group streams.  The caller's: h / v / msg rows, regions,
+// the hoist's and the n16 form's fields, the two-wave streams (rgs: pf_debug_conv_layer passes none)
+static EdgeParams edge_params_base(const pf_handle* h, int layer, bool last, bool pruned) {
+    const pf_config& c = h->cfg;
+    EdgeParams e{};
+    e.tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
+    e.ntiles = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles); e.dyn_cnt = h->d_dyn_cnt;
+    e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
+    e.w = h->d_gvp + h->msg_base(layer, 0); e.n_gvps = c.n_message_gvps;
+    rbf_params(c, e.rbf_mu, &e.rbf_inv_sigma);
+    for (int et = 0; et < 4; ++et) e.rg[et] = h->d_w + h->rg_msg[(size_t)layer * 4 + et];
+    return e;
+}
+// node update of a conv layer.  The caller's: msg rows, h / v in and out, grp / grp_pa, pp_slot 3 of a shared launch, the two-wave streams
+static NodeParams node_params_base(const pf_handle* h, int layer, bool last, bool pruned) {
+    const pf_config& c = h->cfg;
+    NodeParams n{};
+    n.tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
+    n.ntiles = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
+    n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N;
+    n.pp_slot = pruned ? 2 : 1; n.row_ids = h->d_act_ids; n.dyn_cnt = h->d_dyn_cnt; n.zero_row = h->zero_row;
+    n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
+    n.n_upd = c.n_update_gvps;
+    for (int nt = 0; nt < 2; ++nt) {
+        const size_t* lo = &h->ln_off[(size_t)(layer * 2 + nt) * 4];
+        n.w[nt].ln1_w = h->d_w + lo[0]; n.w[nt].ln1_b = h->d_w + lo[1];
+        n.w[nt].ln2_w = h->d_w + lo[2]; n.w[nt].ln2_b = h->d_w + lo[3];
+        n.w[nt].upd = h->d_gvp + h->upd_base(layer, nt);
+        n.rg_upd[nt] = h->d_w + h->rg_upd[(size_t)layer * 2 + nt];
+    }
+    return n;
+}
+// the "pa" rows of this conv-layer-0 launch may be computed ahead (k_n16_pa_spec): one contract for the side that saves the launch's
+// parameters for the speculative items and the side that skips the regions they filled
+static bool pa_ahead_ok(const pf_handle* h, const EdgeParams& e, bool shared) { return h->pa_spec && !shared && h->B <= 64 && !e.need; }
+// the timestep behind t in the announced plan (searched from plan_pos on); NaN when nothing follows.  index (optional): where t was found
+static float planned_next_t(const pf_handle* h, float t, size_t* index) {
+    const size_t n = h->t_plan.size();
+    for (size_t k = 0; k < n; ++k) {
+        const size_t i = (h->plan_pos + k) % n;
+        if (h->t_plan[i] != t) continue;
+        if (index) *index = i;
+        return i + 1 < n ? h->t_plan[i + 1] : NAN;
+    }
+    return NAN;
+}
+// every graph has regions of one capacity at a fixed stride, for each of the first n_et edge types: the item map of a launch
+// can be arithmetic.  The strides fit 16 bits (both users pack them so); what the capacities must fit is the caller's
+static bool uniform_regions(const pf_handle* h, int n_et, int* stride, int* cap) {
+    for (int et = 0; et < n_et; ++et) {
+        const size_t o = (size_t)et * h->B;
+        stride[et] = h->B > 1 ? h->h_reg[o + 1] - h->h_reg[o] : 0; cap[et] = h->h_cap[o];
+        for (int g = 0; g < h->B; ++g)
+            if (h->h_cap[o + g] != cap[et] || h->h_reg[o + g] != h->h_reg[o] + g * stride[et]) return false;
+        if (stride[et] < 0 || stride[et] >= 65536) return false;
+    }
+    return true;
+}
+// profile class of an edge launch on the latency-regime forms: the last of several conv layers is timed apart
+static int edge_prof_class(bool last, int n_convs) { return (last && n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP; }
 // conv layer 0 of an inference call runs on the row-group kernels: they encode the rows they read on the fly, so the
 // call's first launch is the edge build alone -- which the previous denoising step's update launch can do as well
 static bool encoders_on_the_fly(const pf_handle* h) {
     if (h->wide) return false;          // (the width-generic family launches its encoders; pf_denoise_step: the update alone)
     const pf_config& c = h->cfg;
-    const int prune_layer = (h->prune && c.n_convs >= 2) ? c.n_convs - 2 : -1;
-    const int nt0 = c.n_convs == 1 ? h->n_edge_tiles_last : (prune_layer == 0 ? h->n_edge_tiles_act : h->n_edge_tiles);
+    const int nt0 = c.n_convs == 1 ? h->n_edge_tiles_last : (prune_layer(h) == 0 ? h->n_edge_tiles_act : h->n_edge_tiles);
     return h->enc_on_the_fly && h->pol.rg_mode(nt0) != 0;
 }
 
@@ -1079,9 +1174,8 @@ static L0HoistParams l0_params(pf_handle* h) {
     lp.src = h->d_w + h->l0h_off; lp.l0c = h->d_l0c;
     lp.esrc = h->d_esrc; lp.edst = h->d_edst; lp.xn = h->d_xn; lp.Epp = (int)h->Epp; lp.zs = h->d_zs;
     float mu[PF_R];
-    linspace_f32(0.f, c.rbf_dmax, c.rbf_dim, mu);
+    rbf_params(c, mu, &lp.rbf_inv_sigma);
     lp.rbf_mu0 = mu[0]; lp.rbf_mu_step = (mu[PF_R - 1] - mu[0]) * (1.0f / (float)(PF_R - 1));
-    lp.rbf_inv_sigma = 1.0f / ((c.rbf_dmax - 0.f) / (float)c.rbf_dim);
     lp.enc_w = h->d_w + h->enc_w[0]; lp.enc_b = h->d_w + h->enc_b[0];
     lp.enc_lw = h->d_w + h->enc_lw[0]; lp.enc_lb = h->d_w + h->enc_lb[0];
     lp.rec_nf = c.rec_nf;
@@ -1117,9 +1211,6 @@ static void l0_prepare_t(pf_handle* h, const float* tv, int n, hipStream_t s) {
     }
 }
 
-// sequence one dynamics call on the handle's state (xn, pharm_h, d_t).  train: keep every layer's input and message
-// rows (h->t_*), compute every tile (gradients need the full graph only where they are non-zero, but the first
-// version of the backward pass walks the dense tile lists) and apply dropout in the node update.
 // the n16 streams after pf_set_flat_params left them behind (see pf_handle::n16_begin)
 static void n16_refresh(pf_handle* h, hipStream_t s) {
     if (!h->n16_stale) return;
@@ -1156,11 +1247,10 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         { ProfScope ps(h, pf_handle::K_BUILD, s); pfk_build_edges(&bp, s); }
         build_done(h, false);
     }
-    const int prune_layer = (h->prune && c.n_convs >= 2) ? c.n_convs - 2 : -1;
     h->last_family.assign(c.n_convs, 64);
     int cur = 0;
     for (int l = 0; l < c.n_convs; ++l) {
-        const bool last = l == c.n_convs - 1, pruned = l == prune_layer;
+        const bool last = l == c.n_convs - 1, pruned = l == prune_layer(h);
         WideEdgeParams e{};
         e.tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
         e.ntiles = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles);
@@ -1168,8 +1258,7 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         e.h = h->d_h[cur]; e.v = h->d_v[cur]; e.layer0 = l == 0;
         e.msg_s = h->d_msg_s; e.msg_v = h->d_msg_v;
         e.w = h->d_wgvp + h->msg_base(l, 0); e.n_gvps = c.n_message_gvps; e.S = S; e.V = V;
-        linspace_f32(0.f, c.rbf_dmax, c.rbf_dim, e.rbf_mu);
-        e.rbf_sigma = (c.rbf_dmax - 0.f) / (float)c.rbf_dim;
+        e.rbf_sigma = rbf_params(c, e.rbf_mu, nullptr);
         { ProfScope ps(h, pf_handle::K_EDGE, s); pfk_wide_edge(&e, s); }
         WideNodeParams n{};
         n.tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
@@ -1201,469 +1290,394 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
     return PF_OK;
 }
 
-// step: this call is the dynamics call of a denoising step (pf_denoise_step) -- when the tail launch applies, the step's
-// sampler update and edge build run behind the noise head in the same launch and h->tail_done tells the caller
-static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s, const float* t_scalar = nullptr,
-                        bool train = false, const StepParams* step = nullptr) {
-    if (h->wide && !train) return run_dynamics_wide(h, eps_h, eps_x, s, t_scalar);
-    const pf_config& c = h->cfg;
-    h->tail_done = false; h->last_tail = 0;
-    // center hoist: the previous denoising step left h_c and P_ff / P_fp of every center for THIS call's timestep
-    const bool cen_have = !train && h->cen_valid && h->edges_built && t_scalar != nullptr && *t_scalar == h->cen_t && h->cen_wver == h->w_version;
-    h->cen_valid = false; h->last_cen = false;
-    // rows computed ahead for this call's "pa" regions (the speculative items of the previous step's merged launch)
-    const bool spec_have = !train && h->spec_valid && h->edges_built && t_scalar != nullptr && *t_scalar == h->spec_t && h->spec_wver == h->w_version;
-    h->spec_valid = false; h->last_spec = 0; h->e0_saved = false;
-    if (!train) n16_refresh(h, s);
-    EncodeParams ep{};
-    ep.Np = h->Np; ep.Nf = h->Nf;
-    ep.prot_h0 = h->d_prot_h0; ep.pharm_h = h->d_pharm_h; ep.t = t_scalar ? nullptr : h->d_t; ep.gid = h->d_gid;
-    ep.t_scalar = t_scalar ? *t_scalar : 0.f;
-    ep.rec_nf = c.rec_nf; ep.pharm_nf = c.pharm_nf;
-    for (int nt = 0; nt < 2; ++nt) {
-        ep.w[nt] = h->d_w + h->enc_w[nt]; ep.b[nt] = h->d_w + h->enc_b[nt];
-        ep.ln_w[nt] = h->d_w + h->enc_lw[nt]; ep.ln_b[nt] = h->d_w + h->enc_lb[nt];
+// ---- one dynamics call on the specialised kernels: the sequencer ------------------------------------------------------
+// What is computed once per call and read by every piece below (a plain struct on run_dynamics' stack), and what one conv
+// layer's edge launch hands to its node launch
+struct DynCall {
+    pf_handle* h; hipStream_t s; float *eps_h, *eps_x;
+    const float* t_scalar; bool train; const StepParams* step;
+    bool cen_have, spec_have;               // the previous step left the center hoist's tables / the "pa" rows for THIS call's timestep
+    bool enc_fly, share, pre_ready, hoist, n16_batch, n16_l0, fuse_l0node;
+    const float* l0_ptab; int l0_gstride, cur; bool head_done; EncodeParams ep; FusedParams fz;
+    EdgeParams e; bool last, pruned, shared; int rg, rgp;       // the conv layer in flight
+};
+// capacity of the regions [r0, r1) in groups of gs slots (a shared kind-3 region is cut on absolute multiples of gs)
+static int region_groups(const pf_handle* h, bool shared, int r0, int r1, int gs) {
+    int n = 0;
+    for (int r = r0; r < r1; ++r) {
+        if (shared && r >= 3 * h->B) {
+            const int st = h->h_share_start[r - 3 * h->B], cn = h->h_share_cnt[r - 3 * h->B];
+            n += cn > 0 ? (st + cn - 1) / gs - st / gs + 1 : 0;
+        } else n += (h->h_cap[r] + gs - 1) / gs;
     }
-    ep.h_out = train ? h->t_H[0] : h->d_h[0];
-
-    const int prune_layer = (h->prune && c.n_convs >= 2) ? c.n_convs - 2 : -1;    // the layer restricted to active atoms
+    return n;
+}
+// the prologue: encoders, edge build and the pp precompute of a dense conv layer 0, whichever of them this call needs
+static int dyn_prologue(DynCall& dc) {
+    pf_handle* h = dc.h; hipStream_t s = dc.s; const pf_config& c = h->cfg;
     // conv layer 0 on the row-group kernels: they encode the rows they read on the fly, only the edge build is launched
     // -- unless the previous denoising step's update launch has built the edges of these coordinates already
-    const bool enc_fly = !train && encoders_on_the_fly(h);
+    dc.enc_fly = !dc.train && encoders_on_the_fly(h);
     // pocket sharing: copies of a pocket read one set of layer-0 pp messages (calls at one common t only)
     if (h->share_ok && h->share_check == 0) (void)share_now(h);                    // a claim about device rows: its verdict, whatever this call shares
-    const bool share = enc_fly && t_scalar != nullptr && prune_layer == 0 && share_now(h);
+    dc.share = dc.enc_fly && dc.t_scalar != nullptr && prune_layer(h) == 0 && share_now(h);
     if (h->share_check == 2)
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: the claim made for this batch is false -- a graph differs from its representative in "
                                "coordinates or features (compared on the device); bind the batch again without the claim");
-    if (h->edges_built && h->edges_share != share) h->edges_built = false;       // built for the other mode: rebuild
-    BuildParams bp = build_params(h, share);
-    bool pre_ready = false;
-    if (enc_fly) {
-        if (!h->edges_built) { ProfScope ps(h, pf_handle::K_BUILD, s); pfk_build_edges(&bp, s); build_done(h, share); }
-    }
+    if (h->edges_built && h->edges_share != dc.share) h->edges_built = false;    // built for the other mode: rebuild
+    const BuildParams bp = build_params(h, dc.share);
+    if (dc.enc_fly) { if (!h->edges_built) { ProfScope ps(h, pf_handle::K_BUILD, s); pfk_build_edges(&bp, s); build_done(h, dc.share); } }
     else if (h->prof_mask & 3u) {     // timing the two halves separately needs separate launches
-        { ProfScope ps(h, pf_handle::K_ENCODE, s); pfk_encode(&ep, s); }
+        { ProfScope ps(h, pf_handle::K_ENCODE, s); pfk_encode(&dc.ep, s); }
         { ProfScope ps(h, pf_handle::K_BUILD, s); pfk_build_edges(&bp, s); }
-    } else if (h->use_pre && h->Np > 0 && prune_layer != 0) {      // layer 0 is dense: precompute P for its pp messages
+    } else if (h->use_pre && h->Np > 0 && prune_layer(h) != 0) {      // layer 0 is dense: precompute P for its pp messages
         PreParams pp{};
         pp.Np = h->Np; pp.rec_nf = c.rec_nf; pp.nke = (c.rec_nf + 2) / 2;
-        pp.prot_h0 = h->d_prot_h0; pp.t = ep.t; pp.t_scalar = ep.t_scalar; pp.gid = h->d_gid;
-        pp.a_enc = h->d_w + h->enc_a; pp.b_enc = h->d_w + h->enc_bf;
-        pp.ln_w = h->d_w + h->enc_lw[0]; pp.ln_b = h->d_w + h->enc_lb[0];
+        pp.prot_h0 = h->d_prot_h0; pp.t = dc.ep.t; pp.t_scalar = dc.ep.t_scalar; pp.gid = h->d_gid;
+        pp.a_enc = h->d_w + h->enc_a; pp.b_enc = h->d_w + h->enc_bf; pp.ln_w = h->d_w + h->enc_lw[0]; pp.ln_b = h->d_w + h->enc_lb[0];
         pp.pre_w = h->h_gvp[h->msg_base(0, ET_PP)]; pp.pre_nks = 64 + c.rbf_dim / 2 + 9;
-        pp.h_out = ep.h_out; pp.pre_out = h->d_pre;
-        pfk_encode_build_pre(&ep, &bp, &pp, s);
-        pre_ready = true;
-    } else pfk_encode_build(&ep, &bp, s);
-
-    // conv layer 0: static hoist of the pp messages (trajectory constants + per-timestep type table)
-    const bool hoist = !train && enc_fly && l0_hoist_ok(h);
-    const float* l0_ptab = nullptr;
-    int l0_gstride = 0;
+        pp.h_out = dc.ep.h_out; pp.pre_out = h->d_pre;
+        pfk_encode_build_pre(&dc.ep, &bp, &pp, s); dc.pre_ready = true;
+    } else pfk_encode_build(&dc.ep, &bp, s);
+    return PF_OK;
+}
+// conv layer 0: static hoist of the pp messages (trajectory constants + per-timestep type table)
+static void dyn_hoist_prepare(DynCall& dc) {
+    pf_handle* h = dc.h; hipStream_t s = dc.s; const pf_config& c = h->cfg;
+    dc.hoist = !dc.train && dc.enc_fly && l0_hoist_ok(h);
     // the n16 form serves the latency regime: batches whose pruned conv-layer launch has few items per compute unit
-    const bool n16_batch = (long)(prune_layer >= 0 ? h->n_edge_tiles_act : h->n_edge_tiles) * 32 <= h->pol.n16_rows_max && !h->n16_msg.empty();
-    const bool n16_l0 = hoist && (h->pol.n16_mask & 2) && n16_batch;      // layer 0 on the n16 kernels: no zs
-    if (hoist) {
-        if (!n16_l0) l0_ensure_static(h, s);
-        if (t_scalar) {
-            l0_prepare_t(h, t_scalar, 1, s);
-            uint32_t bits; memcpy(&bits, t_scalar, 4);
-            l0_ptab = h->d_ptab + (size_t)h->ptab_slot[bits] * L0_NTAB * c.rec_nf * PF_S;
+    dc.n16_batch = (long)(prune_layer(h) >= 0 ? h->n_edge_tiles_act : h->n_edge_tiles) * 32 <= h->pol.n16_rows_max && !h->n16_msg.empty();
+    dc.n16_l0 = dc.hoist && (h->pol.n16_mask & 2) && dc.n16_batch;      // layer 0 on the n16 kernels: no zs
+    if (!dc.hoist) return;
+    if (!dc.n16_l0) l0_ensure_static(h, s);
+    if (dc.t_scalar) {
+        l0_prepare_t(h, dc.t_scalar, 1, s);
+        uint32_t bits; memcpy(&bits, dc.t_scalar, 4);
+        dc.l0_ptab = h->d_ptab + (size_t)h->ptab_slot[bits] * L0_NTAB * c.rec_nf * PF_S;
+    } else {
+        L0HoistParams lp = l0_params(h);
+        lp.nt = h->B; lp.t_dev = h->d_t; lp.ptab = h->d_ptab_pg;
+        pfk_l0_hoist(&lp, 1, s);
+        dc.l0_ptab = h->d_ptab_pg; dc.l0_gstride = L0_NTAB * c.rec_nf * PF_S;
+    }
+}
+// n16 form (pf_n16.hip): 16-row items on four waves.  Conv layers >= 1 read h / v of the sources from memory; conv
+// layer 0 needs the static hoist's type tables (protein sources) and encodes the centers on the fly
+static void edge_n16_form(DynCall& dc, int l) {
+    pf_handle* h = dc.h; EdgeParams& e = dc.e; const pf_config& c = h->cfg; const bool shared = dc.shared;
+    for (int et = 0; et < 4; ++et) {
+        e.n16[et] = h->d_w + (l > 0 ? h->n16_msg[(size_t)l * 4 + et] : h->n16_l0[et]);
+        e.n16_stride[et] = (int)(l > 0 ? h->n16_msg_stride : h->n16_l0_stride[et]);
+        e.ptab16_off[et] = et == ET_PP ? c.rec_nf * PF_S : (et == ET_PF ? 2 * c.rec_nf * PF_S : -1);
+    }
+    if (l == 0) { e.zs = nullptr; dc.rgp = 4; h->last_hoist = 16; }      // (ptab / ptype / l0_gid were set by edge_launch)
+    if (l == 0 && dc.step != nullptr && h->sampling && !h->coords_custom) {
+        // a sampling run: pp geometry from the original coordinates (the same bits in every step, with or without the rows
+        // computed ahead; no race with the build that shifts xn under the speculative items)
+        e.x0_static = h->d_prot_x0;
+        // "pa" regions whose rows were computed ahead (k_n16_pa_spec) and still apply are skipped
+        if (dc.spec_have && pa_ahead_ok(h, e, shared)) { e.pa_skip = h->d_pa_same; h->last_spec = 1; }
+    }
+    if (l == 0 && dc.cen_have && h->n16_l0h[ET_FF] != 0) {              // ff / fp items start from the center hoist's tables (kind M0H)
+        for (int et : {(int)ET_FF, (int)ET_FP}) { e.n16[et] = h->d_w + h->n16_l0h[et]; e.n16_stride[et] = (int)h->n16_l0h_stride[et]; }
+        e.pcen = h->d_cen_p; e.pcen_nf = h->Nf; h->last_cen = true;
+    }
+    e.ngroups_sel = region_groups(h, shared, 0, e.nreg, 16);
+    // conv layer 0, every graph with ff / pf / fp regions of one capacity: their items are mapped by arithmetic (k_n16_edge_u)
+    int stride[3], cap[3], grp[3] = {0, 0, 0};
+    bool uni = l == 0 && h->pol.fused_uni && !shared && e.reg == h->d_reg && e.nreg == 4 * h->B && h->B <= 64 && !e.pa_abs && !e.need &&
+               uniform_regions(h, 3, stride, cap);
+    for (int et = 0; et < 3 && uni; ++et) { grp[et] = (cap[et] + 15) / 16; uni = grp[et] > 0 && grp[et] < 8; }      // (three bits each)
+    if (uni) {
+        for (int et = 0; et < 3; ++et) e.uni_base[et] = h->h_reg[(size_t)et * h->B];
+        e.uni_s01 = stride[0] | (stride[1] << 16);
+        e.uni_s2g = stride[2] | (grp[0] << 16) | (grp[1] << 19) | (grp[2] << 22) | ((h->B - 1) << 25);
+        e.uni_pa_groups = region_groups(h, shared, 3 * h->B, 4 * h->B, 16);
+    }
+    dc.rg = 4;                               // 16 slots per partial-row group
+    if (l == 0 && e.x0_static && pa_ahead_ok(h, e, shared)) {      // what k_n16_pa_spec needs of this launch (the regions, streams and tables of conv layer 0)
+        e.cnt_snap = h->d_pa_cnt;                // (this launch leaves the kind-3 counts it consumed there: the speculative items' map)
+        h->e0 = e; h->ep0 = dc.ep; h->e0_saved = true;
+        h->e0_groups = region_groups(h, shared, 3 * h->B, 4 * h->B, 16);
+    }
+}
+// the edge messages of conv layer l: form choice (LaunchPolicy) + launch
+static void edge_launch(DynCall& dc, int l) {
+    pf_handle* h = dc.h; hipStream_t s = dc.s; const pf_config& c = h->cfg; const bool train = dc.train;
+    const bool last = dc.last = (l == c.n_convs - 1), pruned = dc.pruned = (l == prune_layer(h));
+    EdgeParams& e = dc.e; int &rg = dc.rg, &rgp = dc.rgp;
+    e = edge_params_base(h, l, last, pruned);
+    e.h = train ? h->t_H[l] : h->d_h[dc.cur]; e.v = train ? h->t_V[l] : h->d_v[dc.cur];
+    e.msg_s = train ? h->t_msg_s[l] : h->d_msg_s; e.msg_v = train ? h->t_msg_v[l] : h->d_msg_v;
+    if (dc.fuse_l0node && l == 1) { e.msg_s = h->d_msg_s2; e.msg_v = h->d_msg_v2; }
+    e.pre = (l == 0 && dc.pre_ready) ? h->d_pre : nullptr;
+    if (train) { e.sv_z = h->t_sv_z[l]; e.sv_g = h->t_sv_g[l]; e.sv_v = h->t_sv_v[l]; e.sv_stride = (size_t)std::max<int64_t>(h->Ecap, 1); }
+    // every edge of this launch lives in a dynamic region (each wave scans the region lengths: up to 1024 regions = 64 * RG_CPASS)
+    const bool shared = dc.shared = dc.share && pruned && l == 0;       // pocket sharing: kind-3 regions = static ranges of the representatives
+    if ((last || pruned) && h->rg_compact && (last ? 2 : 4) * h->B <= 1024) {
+        e.reg = shared ? h->d_reg_share : h->d_reg; e.regB = h->B; e.nreg = (last ? 2 : 4) * h->B; e.pa_abs = shared ? 1 : 0;
+        if (shared) { e.need = h->d_need; e.need_stamp = h->edges_stamp; }
+        e.ngroups4 = region_groups(h, shared, 0, e.nreg, 4); e.ngroups8 = region_groups(h, shared, 0, e.nreg, 8);
+    }
+    // (bf16 leg: the message chains run on the 32-slot tile kernel, whose to_feats_out / gate products have a bf16 form)
+    if (train && h->train_bf16) e.bf16 = 1;
+    rg = train ? ((h->train_rg_edge && h->train_rg_node && !h->train_bf16) ? h->pol.rg_mode(e.ntiles) : 0)
+               : h->pol.rg_mode(shared ? (int)((h->share_rows + 31) / 32) : e.ntiles);           // the node launch of this layer follows (partial-row grouping)
+    // static hoist: the hoisted ("pa") items of a compact layer-0 launch run a two-block chain and may take 8 rows
+    // per wave while the full-chain items (ff, pf, fp) take 4
+    rgp = 0;
+    if (dc.hoist && l == 0 && rg) {
+        e.zs = h->d_zs; e.ptab = dc.l0_ptab; e.ptab_gstride = dc.l0_gstride; e.ptype = h->d_ptype; e.eorig = h->d_eorig; e.l0_gid = h->d_gid; e.l0c = h->d_l0c;
+        rgp = rg;
+        if (e.nreg > 0 && pruned) {
+            // (a shared launch: most of the representatives' groups return at once, what runs scales with the batch like the dynamic regions
+            // do -- the general threshold applies; measured at 4-5 pockets x 30 copies: 1.21 M sample-steps/s end to end at 4 rows per wave, 1.26 M at 8)
+            // (one pocket x 128 copies: few shared rows, but 128 graphs' worth of ff / pf / fp items -- 8 rows per wave is 8 % ahead)
+            rg = shared ? ((h->share_rows >= h->pol.rg2_rows_min || (long)e.ntiles * 32 >= h->pol.rg2_rows_min_hoist) ? 2 : 1)
+                        : ((long)e.ntiles * 32 >= h->pol.rg2_rows_min_hoist ? 2 : 1);
+            const int rgp_pol = shared ? rg : ((long)e.ntiles * 32 >= h->pol.rg2p_rows_min ? 2 : 1);
+            if (h->pol.l0_rga) rg = h->pol.l0_rga;
+            rgp = h->pol.l0_rgp ? h->pol.l0_rgp : std::max(rg, rgp_pol);
+            if (rg == 2) rgp = 2;
+            e.ngroups_sel = region_groups(h, shared, 0, 3 * h->B, 4 * rg) + region_groups(h, shared, 3 * h->B, e.nreg, 4 * rgp);     // (a pruned layer: nreg = 4 B)
+        }
+        h->last_hoist = 4 * rgp;
+    }
+    const bool n16e = !train && rg && dc.n16_batch && (l > 0 ? (h->pol.n16_mask & 1) != 0 : dc.n16_l0);
+    if (n16e) edge_n16_form(dc, l);
+    h->last_family.resize(c.n_convs);
+    h->last_family[l] = rg ? 4 * rg : ((!train && e.ntiles <= ((last || pruned) ? std::max(h->pol.coop_edge_max, h->pol.coop2_edge_max) : std::max(h->pol.coop_edge_max, h->pol.coop2_dense_max))) ? 128 : 32);
+    for (int et = 0; et < 4; ++et) { e.rgs[et] = h->d_w + h->rgs_msg[(size_t)l * 4 + et]; e.rgs_stride = (int)h->rgs_msg_stride; }
+    const int esplit = (rg == 1 && e.ntiles * 8 <= h->pol.rg_split_max && !e.zs) ? 1 : 0;    // fewer groups than SIMDs: latency-bound
+    const int pc = edge_prof_class(last, c.n_convs);
+    if (n16e && dc.fuse_l0node && l == 1) {         // the fused launch: what conv layer 0's node update left in fz (fused_take_node) + its own fields
+        FusedParams& fz = dc.fz;
+        fz.chain[ET_FF] = h->d_w + h->n16_fused[0]; fz.chain_stride[ET_FF] = (int)h->n16_fused_stride[0];
+        fz.chain[ET_PF] = h->d_w + h->n16_fused[1]; fz.chain_stride[ET_PF] = (int)h->n16_fused_stride[1];
+        fz.upd_pharm = h->d_w + h->n16_upd[(size_t)0 * 2 + 1]; fz.upd_pharm_stride = (int)h->n16_upd_stride;
+        fz.htab = dc.l0_ptab + (size_t)3 * c.rec_nf * PF_S; fz.htab_gstride = dc.l0_gstride; fz.ptype = h->d_ptype; fz.hcen = h->last_cen ? h->d_cen_h : nullptr;
+        fz.h_out = h->d_h[dc.cur]; fz.v_out = h->d_v[dc.cur];          // (cur was flipped behind conv layer 0: its output side)
+        fz.pharm_ptr = h->d_pharm_ptr; fz.Np = h->Np; fz.n_edge_items = e.ngroups_sel;
+        fz.nff_cap = region_groups(h, shared, 0, std::min(h->B, e.nreg), 16); fz.npf_cap = region_groups(h, shared, h->B, e.nreg, 16);
+        fz.xcd_split = ((h->pol.xcd_split & 1) && 2 * h->B <= 64 && h->max_nf <= 16) ? 1 : 0;
+        // every graph with regions of one capacity (the same number of centers everywhere): the regions of an etype sit at a fixed
+        // stride and the item map is arithmetic (k_n16_fused_u); PFDYN_FUSED_UNI=0: the work-list form
+        int stride[2], cap[2];
+        bool uni = fz.xcd_split && h->pol.fused_uni && e.reg == h->d_reg && e.nreg == 2 * h->B && uniform_regions(h, 2, stride, cap);
+        for (int et = 0; et < 2 && uni; ++et) uni = cap[et] > 0 && (cap[et] + 15) / 16 < 256;      // (eight bits each)
+        if (uni) {
+            fz.uni_ff_base = h->h_reg[0]; fz.uni_pf_base = h->h_reg[(size_t)h->B];
+            fz.uni_strides = stride[0] | (stride[1] << 16); fz.uni_groups = ((cap[0] + 15) / 16) | (((cap[1] + 15) / 16) << 8);
+        }
+        h->last_family[l] = 17;                      // pf_debug_kernel_family: 16-row items with conv layer 0's node update in front
+        { ProfScope ps(h, pf_handle::K_EDGE_LAST, s); pfk_n16_fused(&e, &fz, &dc.ep, s); }
+    }
+    else if (n16e) {
+        // PFDYN_PA_CHECK: the kept groups of the rows computed ahead must carry the serial of the launch that computed them (before this
+        // launch overwrites the count snapshot the check compares with)
+        if (l == 0 && e.pa_skip && h->d_pa_gstamp && h->d_pa_chk)
+            pfk_pa_check(h->d_dyn_cnt, h->d_pa_cnt, e.reg, e.pa_skip, h->d_pa_gstamp, h->spec_serial, h->B, h->d_pa_chk, s);
+        ProfScope ps(h, pc, s); pfk_n16_edge(&e, &dc.ep, l == 0, s);
+    }
+    else if (rg) { ProfScope ps(h, pc, s); pfk_rg_edge(&e, dc.enc_fly ? &dc.ep : nullptr, l == 0, rg, esplit, rgp, s); }
+    // few tiles (last layer): 4 waves per tile to cut the serial latency; otherwise one wave per tile
+    else if (e.ntiles <= h->pol.coop_edge_max && !train) { ProfScope ps(h, pc, s); pfk_edge_msg_coop(&e, l == 0, s); }
+    else if (e.ntiles <= ((last || pruned) ? h->pol.coop2_edge_max : h->pol.coop2_dense_max) && !train) { ProfScope ps(h, pc, s); pfk_edge_msg_coop2(&e, l == 0, s); }
+    else { ProfScope ps(h, pf_handle::K_EDGE, s); pfk_edge_msg(&e, l == 0, s); }
+}
+// the fused launch takes conv layer 0's node update: no node launch, the last layer's edge items (and its store items) compute these rows
+static void fused_take_node(DynCall& dc, const NodeParams& n) {
+    pf_handle* h = dc.h; FusedParams& fz = dc.fz;
+    fz.in_start = n.in_start; fz.in_cnt = n.in_cnt; fz.N = n.N; fz.pp_slot = n.pp_slot;
+    // (records describe the sources' in-edges as the update + build left them: the "pa" region as an atom's second segment)
+    fz.rec = (h->rec_valid && h->d_rec && n.pp_slot == 2 && !dc.shared) ? h->d_rec : nullptr;
+    fz.msg_s = n.msg_s; fz.msg_v = n.msg_v; fz.zero_row = n.zero_row; fz.grp = n.grp; fz.grp_pa = n.grp_pa;
+    fz.gid = n.gid; fz.gnorm = n.gnorm; fz.B = n.B; fz.norm_mode = n.norm_mode; fz.norm_value = n.norm_value; fz.n_upd = n.n_upd;
+    for (int nt = 0; nt < 2; ++nt) { fz.ln1_w[nt] = n.w[nt].ln1_w; fz.ln1_b[nt] = n.w[nt].ln1_b; fz.ln2_w[nt] = n.w[nt].ln2_w; fz.ln2_b[nt] = n.w[nt].ln2_b; }
+}
+static void node_save_levels(pf_handle* h, int l, NodeParams& n) {     // training forward: the update chains' levels stay for k_bwd_node
+    n.sv_z = h->t_nsv_z[l]; n.sv_g = h->t_nsv_g[l]; n.sv_v = h->t_nsv_v[l]; n.sv_stride = (size_t)2 * h->N;
+    h->t_node_saved[l] = 1;
+}
+// the tail launch: one workgroup per graph does the centers' node update, the head, the sampler update and the edge build.
+// form 4: the row-group form (the fused node + head item, two per workgroup), 16: the n16 form
+static void tail_launch(DynCall& dc, const NodeParams& n, int form) {
+    pf_handle* h = dc.h; hipStream_t s = dc.s; const pf_config& c = h->cfg;
+    const HeadParams hp = head_params(h, dc.eps_h, dc.eps_x); TailParams tp{};
+    if (form == 16) {
+        tp.in_start = n.in_start; tp.in_cnt = n.in_cnt; tp.N = n.N; tp.h_in = n.h_in; tp.v_in = n.v_in;
+        tp.msg_s = n.msg_s; tp.msg_v = n.msg_v; tp.zero_row = n.zero_row; tp.grp = n.grp;
+        tp.gid = n.gid; tp.gnorm = n.gnorm; tp.B = n.B; tp.norm_mode = n.norm_mode; tp.norm_value = n.norm_value;
+        tp.ln1_w = n.w[1].ln1_w; tp.ln1_b = n.w[1].ln1_b; tp.ln2_w = n.w[1].ln2_w; tp.ln2_b = n.w[1].ln2_b;
+        tp.n_upd = n.n_upd; tp.n_head = c.n_noise_gvps; tp.chain = h->d_w + h->n16_tail; tp.chain_stride = (int)h->n16_tail_stride;
+        tp.pharm_nf = c.pharm_nf; tp.eps_h = dc.eps_h; tp.eps_x = dc.eps_x;
+    }
+    const bool sn = share_next(h);
+    const BuildParams bpn = build_params(h, sn);
+    { ProfScope ps(h, pf_handle::K_HEAD, s); if (form == 16) pfk_n16_tail(&tp, dc.step, &bpn, s); else pfk_rg_tail(&n, &hp, dc.step, &bpn, s); }
+    build_done(h, sn);
+    h->tail_done = true; h->last_tail = form; dc.head_done = true;
+}
+// center hoist for the NEXT call: its timestep from the announced plan (the entry behind this step's t); the tables
+// serve a call that runs conv layer 0 on the n16 kernels with the type tables (as this one did); this step's
+// features before the update must be in a snapshot (pf_sample_begin / the previous step left it).  NaN: no hoist
+static float cen_hoist_plan(DynCall& dc) {
+    pf_handle* h = dc.h;
+    if (!(h->cen_hoist && dc.t_scalar && !h->t_plan.empty() && h->last_hoist == 16 && h->l0c_off != 0 && h->n16_l0h[ET_FF] != 0 &&
+          h->snap_cur >= 0 && dc.step->h_snap_out != nullptr && h->d_xchg2 && dc.fuse_l0node)) return NAN;
+    return planned_next_t(h, *dc.t_scalar, &h->plan_pos);
+}
+// ... and its workgroups' parameters
+static void cen_hoist_params(DynCall& dc, float t_next, CenHoistParams& cp, HeadParams& hp) {
+    pf_handle* h = dc.h; const StepParams* step = dc.step;
+    cp.on = 1; cp.Nf = h->Nf; cp.nf = h->cfg.pharm_nf; cp.t_next = t_next; cp.pharm_h = h->d_snap[h->snap_cur]; cp.noise = step->noise;
+    cp.a_ts = step->a_ts; cp.var = step->var; cp.sigma = step->sigma; cp.ep_zt = step->ep_zt; cp.ep_pred = step->ep_pred; cp.ep_feat = step->ep_feat;
+    cp.enc_w = h->d_w + h->enc_w[1]; cp.enc_b = h->d_w + h->enc_b[1]; cp.enc_lw = h->d_w + h->enc_lw[1]; cp.enc_lb = h->d_w + h->enc_lb[1];
+    cp.blk = h->d_w + h->l0c_off; cp.cen_h = h->d_cen_h; cp.cen_p = h->d_cen_p; cp.xchg2 = hp.xchg2 = h->d_xchg2;
+    h->cen_valid = true; h->cen_t = t_next; h->cen_wver = h->w_version;
+}
+// the NEXT call's "pa" messages, ahead of time, as workgroups of the merged launch (BuildParams::pa_same): conv layer 0's rows of this call have been
+// consumed by the fused launch, the next timestep's type tables exist (or are made now).  Returns the number of speculative groups (0: none)
+static int pa_ahead_plan(DynCall& dc, EdgeParams& es, EncodeParams& ees) {
+    pf_handle* h = dc.h; const pf_config& c = h->cfg;
+    if (!(h->e0_saved && h->pa_spec && !h->t_plan.empty() && dc.t_scalar && h->d_pa_stamp && !share_next(h))) return 0;
+    float tn = planned_next_t(h, *dc.t_scalar, nullptr);
+    if (tn != tn) return 0;
+    l0_prepare_t(h, &tn, 1, dc.s);                  // (a no-op when the plan was announced)
+    uint32_t bits; memcpy(&bits, &tn, 4);
+    es = h->e0; es.pa_skip = nullptr; es.pcen = nullptr;
+    es.ptab = h->d_ptab + (size_t)h->ptab_slot[bits] * L0_NTAB * c.rec_nf * PF_S;
+    for (int et = 0; et < 4; ++et) { es.n16[et] = h->d_w + h->n16_l0[et]; es.n16_stride[et] = (int)h->n16_l0_stride[et]; }
+    ees = h->ep0; ees.t_scalar = tn;
+    h->spec_valid = true; h->spec_t = tn; h->spec_wver = h->w_version;
+    es.pa_serial = h->spec_serial = ++h->pa_serial; es.pa_gstamp = h->d_pa_gstamp;
+    return h->e0_groups;
+}
+// the merged last launch of a denoising step of a small batch: the step's update + build joins the node + head launch as
+// workgroups of its own (k_rg_node_hs_build), with the work done ahead for the next call
+static void merged_step_launch(DynCall& dc, const NodeParams& n, HeadParams& hp) {
+    pf_handle* h = dc.h; hipStream_t s = dc.s; const pf_config& c = h->cfg;
+    hp.xchg = h->d_xchg; hp.xchg_fault = h->xchg_fault;
+    CenHoistParams cp{}; EdgeParams es{}; EncodeParams ees{};
+    const float t_next = cen_hoist_plan(dc);
+    const int spec_groups = pa_ahead_plan(dc, es, ees);
+    if (t_next == t_next) cen_hoist_params(dc, t_next, cp, hp);
+    const bool sn = share_next(h);
+    BuildParams bpn = build_params(h, sn);
+    // edge records for the next call's fused launch: radius ff edges, compact "pa" regions, the static hoist's element types
+    const bool with_rec = h->d_rec && !sn && c.ff_k == 0 && bpn.act_ids && !bpn.pa_static && h->last_hoist == 16 && dc.fuse_l0node;
+    if (with_rec) { bpn.rec = h->d_rec; bpn.ptype = h->d_ptype; }
+    // PFDYN_PA_SPEC_SPLIT (test knob): no speculative slots in the merged launch; items w < k run just before it (the kind-3
+    // counts before the build), w >= k just after it (the counts after the build).  "mid" / "step": k is half / a per-step
+    // fraction of the non-empty groups, fixed by the launch in front (k_pa_spec)
+    const bool split = spec_groups > 0 && h->pa_spec_split != 0;
+    if (split) {
+        const int frac = h->pa_spec_split == -1 ? 128 : (h->pa_spec_split == -2 ? (int)((((uint32_t)h->pa_serial * 2654435761u) >> 16) & 255) + 1 : 0);
+        pfk_pa_spec(&es, &ees, spec_groups, 0, std::max(h->pa_spec_split, 0), frac, h->d_pa_cnt + h->B, s);
+    }
+    { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_node_hs_build(&n, &hp, dc.step, &bpn, h->d_xstat, h->pol.xchg_sleep, h->pol.hsb_avoid, h->xchg_poll_max, &cp, &es, &ees, split ? 0 : spec_groups, s); }
+    if (split) pfk_pa_spec(&es, &ees, spec_groups, 1, 0, 0, h->d_pa_cnt + h->B, s);
+    build_done(h, sn, with_rec);
+    h->tail_done = true; h->last_tail = 2;
+}
+// the node update of conv layer l on the partial rows its edge launch left: form choice (LaunchPolicy) + launch
+static void node_launch(DynCall& dc, int l) {
+    pf_handle* h = dc.h; hipStream_t s = dc.s; const pf_config& c = h->cfg; const bool train = dc.train;
+    NodeParams n = node_params_base(h, l, dc.last, dc.pruned);
+    if (dc.shared) n.pp_slot = 3;
+    n.msg_s = dc.e.msg_s; n.msg_v = dc.e.msg_v; n.h_in = dc.e.h; n.v_in = dc.e.v;
+    n.h_out = train ? h->t_H[l + 1] : h->d_h[dc.cur ^ 1]; n.v_out = train ? h->t_V[l + 1] : h->d_v[dc.cur ^ 1];
+    if (train) { n.drop_thr = h->t_common.drop_thr; n.drop_scale = h->t_common.drop_scale; n.seed = h->t_common.seed; n.layer = l; n.mask_override = h->t_common.mask_override; }
+    n.grp = dc.rg ? 4 * dc.rg : 32; n.grp_pa = dc.rgp ? 4 * dc.rgp : n.grp;
+    if (train) { h->t_grp.resize(c.n_convs); h->t_grp[l] = n.grp; h->t_node_saved.resize(c.n_convs); h->t_node_saved[l] = 0; }
+    for (int nt = 0; nt < 2; ++nt) { n.rgs_upd[nt] = h->d_w + h->rgs_upd[(size_t)l * 2 + nt]; n.rgs_stride[nt] = (int)h->rgs_upd_stride[(size_t)l * 2 + nt]; }
+    const EncodeParams* enc = dc.enc_fly ? &dc.ep : nullptr;
+    if (dc.fuse_l0node && l == 0) fused_take_node(dc, n);
+    else if (dc.rg) {
+        const int rgn = (long)n.ntiles * 32 >= h->pol.rg2_rows_min_node ? 2 : 1;
+        const bool fuse = dc.last && !train && h->fuse_head && h->n_head_tiles == n.ntiles;
+        const int nsplit = (!train && rgn == 1 && n.ntiles * 8 <= (fuse ? h->pol.rg_split_max_head : h->pol.rg_split_max_node)) ? 1 : 0;
+        const bool tail = fuse && dc.step != nullptr && l > 0 && (h->pol.n16_mask & 8) && h->B <= h->pol.tail_graphs_max && dc.enc_fly && step_build_fast_ok(h);
+        if (tail) tail_launch(dc, n, (h->pol.tail_form == 16 && h->n16_tail != 0) ? 16 : 4);
+        else if (fuse) {
+            // few two-wave items: confined to node_xcds XCDs when they fit one per compute unit there (32 CUs per XCD)
+            if (nsplit && h->pol.node_xcds > 0 && n.ntiles * 8 <= 32 * h->pol.node_xcds) n.xcd_n = h->pol.node_xcds;
+            if (nsplit && l > 0 && h->pol.node_static) { n.st_n0 = h->Np; n.st_n = h->Nf; }      // (the last layer's node tiles ARE the static tiling of the centers)
+            HeadParams hp = head_params(h, dc.eps_h, dc.eps_x);
+            // a denoising step of a small batch: the step's update + build joins this launch; timing the two separately needs the separate launches
+            const bool hsb = n.st_n > 0 && dc.step != nullptr && h->pol.hs_build && dc.enc_fly && step_build_fast_ok(h) &&
+                             h->B <= 256 && !(h->prof_mask & (1u << pf_handle::K_STEP)) && h->d_xchg && h->d_xstat;
+            if (hsb) merged_step_launch(dc, n, hp);
+            else { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_node(&n, &hp, enc, l == 0, rgn, nsplit, s); }
+            dc.head_done = true;
         } else {
-            L0HoistParams lp = l0_params(h);
-            lp.nt = h->B; lp.t_dev = h->d_t; lp.ptab = h->d_ptab_pg;
-            pfk_l0_hoist(&lp, 1, s);
-            l0_ptab = h->d_ptab_pg; l0_gstride = L0_NTAB * c.rec_nf * PF_S;
+            if (train && h->train_node_save) node_save_levels(h, l, n);
+            ProfScope ps(h, pf_handle::K_NODE_COOP, s); pfk_rg_node(&n, nullptr, enc, l == 0, rgn, nsplit, s);
         }
     }
-    h->last_hoist = 0;
-    int cur = 0;
-    bool head_done = false;
-    // fused launch (pf_n16.hip: k_n16_fused): with two conv layers, receptive-field pruning and kNN pf edges the rows conv
-    // layer 0's node update produces are exactly the sources of the last layer's edges (+ the centers): every edge item of
-    // the last layer updates its own source rows first, and the node launch of conv layer 0 disappears
-    const bool fuse_l0node = !train && n16_batch && (long)h->n_edge_tiles_act * 32 <= h->pol.n16_fuse_rows_max && (h->pol.n16_mask & 4) && (h->pol.n16_mask & 1) && hoist && c.n_convs == 2 && prune_layer == 0 && c.pf_k > 0 &&
-                             c.n_update_gvps >= 1 && h->rg_compact && 2 * h->B <= 1024 && h->d_msg_s2 != nullptr && h->n16_fused[0] != 0;
-    FusedParams fz{};
-    for (int l = 0; l < c.n_convs; ++l) {
-        EdgeParams e{};
-        const bool last = (l == c.n_convs - 1), pruned = (l == prune_layer);
-        e.tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
-        e.ntiles = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles); e.dyn_cnt = h->d_dyn_cnt;
-        e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
-        e.h = train ? h->t_H[l] : h->d_h[cur]; e.v = train ? h->t_V[l] : h->d_v[cur];
-        e.msg_s = train ? h->t_msg_s[l] : h->d_msg_s; e.msg_v = train ? h->t_msg_v[l] : h->d_msg_v;
-        if (fuse_l0node && l == 1) { e.msg_s = h->d_msg_s2; e.msg_v = h->d_msg_v2; }
-        e.w = h->d_gvp + h->msg_base(l, 0); e.n_gvps = c.n_message_gvps;
-        e.pre = (l == 0 && pre_ready) ? h->d_pre : nullptr;
-        linspace_f32(0.f, c.rbf_dmax, c.rbf_dim, e.rbf_mu);
-        e.rbf_inv_sigma = 1.0f / ((c.rbf_dmax - 0.f) / (float)c.rbf_dim);
-        // few tiles (last layer): 4 waves per tile to cut the serial latency; otherwise one wave per tile
-        if (train) {
-            e.sv_z = h->t_sv_z[l]; e.sv_g = h->t_sv_g[l]; e.sv_v = h->t_sv_v[l];
-            e.sv_stride = (size_t)std::max<int64_t>(h->Ecap, 1);
-        }
-        for (int et = 0; et < 4; ++et) e.rg[et] = h->d_w + h->rg_msg[(size_t)l * 4 + et];
-        // every edge of this launch lives in a dynamic region (each wave scans the region lengths: up to 1024 regions = 64 * RG_CPASS)
-        const bool shared = share && pruned && l == 0;       // pocket sharing: kind-3 regions = static ranges of the representatives
-        // capacity of region r in groups of gs slots (a shared kind-3 region is cut on absolute multiples of gs)
-        auto region_groups = [&](int r, int gs) {
-            if (shared && r >= 3 * h->B) {
-                const int st = h->h_share_start[r - 3 * h->B], cn = h->h_share_cnt[r - 3 * h->B];
-                return cn > 0 ? (st + cn - 1) / gs - st / gs + 1 : 0;
-            }
-            return (h->h_cap[r] + gs - 1) / gs;
-        };
-        if ((last || pruned) && h->rg_compact && (last ? 2 : 4) * h->B <= 1024) {
-            e.reg = shared ? h->d_reg_share : h->d_reg; e.regB = h->B; e.nreg = (last ? 2 : 4) * h->B;
-            e.pa_abs = shared ? 1 : 0;
-            if (shared) { e.need = h->d_need; e.need_stamp = h->edges_stamp; }
-            for (int r = 0; r < e.nreg; ++r) { e.ngroups4 += region_groups(r, 4); e.ngroups8 += region_groups(r, 8); }
-        }
-        // (bf16 leg: the message chains run on the 32-slot tile kernel, whose to_feats_out / gate products have a bf16 form)
-        if (train && h->train_bf16) e.bf16 = 1;
-        int rg = train ? ((h->train_rg_edge && h->train_rg_node && !h->train_bf16) ? h->pol.rg_mode(e.ntiles) : 0)
-                       : h->pol.rg_mode(shared ? (int)((h->share_rows + 31) / 32) : e.ntiles);           // the node launch of this layer follows (partial-row grouping)
-        // static hoist: the hoisted ("pa") items of a compact layer-0 launch run a two-block chain and may take 8 rows
-        // per wave while the full-chain items (ff, pf, fp) take 4
-        int rgp = 0;
-        if (hoist && l == 0 && rg) {
-            e.zs = h->d_zs; e.ptab = l0_ptab; e.ptab_gstride = l0_gstride; e.ptype = h->d_ptype; e.eorig = h->d_eorig;
-            e.l0_gid = h->d_gid; e.l0c = h->d_l0c;
-            rgp = rg;
-            if (e.nreg > 0 && pruned) {
-                // (a shared launch: most of the representatives' groups return at once, what runs scales with the batch
-                // like the dynamic regions do -- the general threshold applies; measured at 4-5 pockets x 30 copies:
-                // 1.21 M sample-steps/s end to end at 4 rows per wave, 1.26 M at 8)
-                // (one pocket x 128 copies: few shared rows, but 128 graphs' worth of ff / pf / fp items -- 8 rows per wave is 8 % ahead)
-                rg = shared ? ((h->share_rows >= h->pol.rg2_rows_min || (long)e.ntiles * 32 >= h->pol.rg2_rows_min_hoist) ? 2 : 1)
-                            : ((long)e.ntiles * 32 >= h->pol.rg2_rows_min_hoist ? 2 : 1);
-                const int rgp_pol = shared ? rg : ((long)e.ntiles * 32 >= h->pol.rg2p_rows_min ? 2 : 1);
-                if (h->pol.l0_rga) rg = h->pol.l0_rga;
-                rgp = h->pol.l0_rgp ? h->pol.l0_rgp : std::max(rg, rgp_pol);
-                if (rg == 2) rgp = 2;
-                for (int r = 0; r < e.nreg; ++r) e.ngroups_sel += region_groups(r, 4 * (r >= 3 * h->B ? rgp : rg));
-            }
-            h->last_hoist = 4 * rgp;
-        }
-        // n16 form (pf_n16.hip): 16-row items on four waves.  Conv layers >= 1 read h / v of the sources from memory; conv
-        // layer 0 needs the static hoist's type tables (protein sources) and encodes the centers on the fly
-        const bool n16e = !train && rg && n16_batch && (l > 0 ? (h->pol.n16_mask & 1) != 0 : n16_l0);
-        if (n16e) {
-            for (int et = 0; et < 4; ++et) {
-                e.n16[et] = h->d_w + (l > 0 ? h->n16_msg[(size_t)l * 4 + et] : h->n16_l0[et]);
-                e.n16_stride[et] = (int)(l > 0 ? h->n16_msg_stride : h->n16_l0_stride[et]);
-                e.ptab16_off[et] = et == ET_PP ? c.rec_nf * PF_S : (et == ET_PF ? 2 * c.rec_nf * PF_S : -1);
-            }
-            if (l == 0) { e.zs = nullptr; rgp = 4; h->last_hoist = 16; }      // (ptab / ptype / l0_gid were set above)
-            if (l == 0 && step != nullptr && h->sampling && !h->coords_custom) {
-                // a sampling run: pp geometry from the original coordinates (the same bits in every step, with or without the rows
-                // computed ahead; no race with the build that shifts xn under the speculative items)
-                e.x0_static = h->d_prot_x0;
-                // "pa" regions whose rows were computed ahead (k_n16_pa_spec) and still apply are skipped
-                if (spec_have && h->pa_spec && !shared && h->B <= 64 && !e.need) { e.pa_skip = h->d_pa_same; h->last_spec = 1; }
-            }
-            if (l == 0 && cen_have && h->n16_l0h[ET_FF] != 0) {              // ff / fp items start from the center hoist's tables (kind M0H)
-                for (int et : {(int)ET_FF, (int)ET_FP}) { e.n16[et] = h->d_w + h->n16_l0h[et]; e.n16_stride[et] = (int)h->n16_l0h_stride[et]; }
-                e.pcen = h->d_cen_p; e.pcen_nf = h->Nf;
-                h->last_cen = true;
-            }
-            e.ngroups_sel = 0;
-            for (int r = 0; r < e.nreg; ++r) e.ngroups_sel += region_groups(r, 16);
-            // conv layer 0, every graph with ff / pf / fp regions of one capacity: their items are mapped by arithmetic (k_n16_edge_u)
-            if (l == 0 && h->pol.fused_uni && !shared && e.reg == h->d_reg && e.nreg == 4 * h->B && h->B <= 64 && !e.pa_abs && !e.need) {
-                bool uni = true;
-                int stride[3] = {0, 0, 0}, grp[3] = {0, 0, 0};
-                for (int et = 0; et < 3 && uni; ++et) {
-                    const size_t o = (size_t)et * h->B;
-                    if (h->B > 1) stride[et] = h->h_reg[o + 1] - h->h_reg[o];
-                    for (int g = 0; g < h->B && uni; ++g)
-                        uni = h->h_cap[o + g] == h->h_cap[o] && h->h_reg[o + g] == h->h_reg[o] + g * stride[et];
-                    grp[et] = (h->h_cap[o] + 15) / 16;
-                    uni = uni && stride[et] >= 0 && stride[et] < 65536 && grp[et] > 0 && grp[et] < 8;
-                }
-                if (uni) {
-                    for (int et = 0; et < 3; ++et) e.uni_base[et] = h->h_reg[(size_t)et * h->B];
-                    e.uni_s01 = stride[0] | (stride[1] << 16);
-                    e.uni_s2g = stride[2] | (grp[0] << 16) | (grp[1] << 19) | (grp[2] << 22) | ((h->B - 1) << 25);
-                    e.uni_pa_groups = 0;
-                    for (int g = 0; g < h->B; ++g) e.uni_pa_groups += region_groups(3 * h->B + g, 16);
-                }
-            }
-            rg = 4;                                  // 16 slots per partial-row group
-            if (l == 0 && e.x0_static && h->pa_spec && !shared && h->B <= 64 && !e.need) {      // what k_n16_pa_spec needs of this launch (the regions, streams and tables of conv layer 0)
-                e.cnt_snap = h->d_pa_cnt;                // (this launch leaves the kind-3 counts it consumed there: the speculative items' map)
-                h->e0 = e; h->ep0 = ep; h->e0_saved = true;
-                h->e0_groups = 0;
-                for (int g = 0; g < h->B; ++g) h->e0_groups += region_groups(3 * h->B + g, 16);
-            }
-        }
-        h->last_family.resize(c.n_convs);
-        h->last_family[l] = rg ? 4 * rg : ((!train && e.ntiles <= ((last || pruned) ? std::max(h->pol.coop_edge_max, h->pol.coop2_edge_max) : std::max(h->pol.coop_edge_max, h->pol.coop2_dense_max))) ? 128 : 32);
-        for (int et = 0; et < 4; ++et) e.rgs[et] = h->d_w + h->rgs_msg[(size_t)l * 4 + et];
-        e.rgs_stride = (int)h->rgs_msg_stride;
-        const int esplit = (rg == 1 && e.ntiles * 8 <= h->pol.rg_split_max && !e.zs) ? 1 : 0;    // fewer groups than SIMDs: latency-bound
-        if (n16e && fuse_l0node && l == 1) {
-            fz.chain[ET_FF] = h->d_w + h->n16_fused[0]; fz.chain_stride[ET_FF] = (int)h->n16_fused_stride[0];
-            fz.chain[ET_PF] = h->d_w + h->n16_fused[1]; fz.chain_stride[ET_PF] = (int)h->n16_fused_stride[1];
-            fz.upd_pharm = h->d_w + h->n16_upd[(size_t)0 * 2 + 1]; fz.upd_pharm_stride = (int)h->n16_upd_stride;
-            fz.htab = l0_ptab + (size_t)3 * c.rec_nf * PF_S; fz.htab_gstride = l0_gstride; fz.ptype = h->d_ptype;
-            fz.hcen = h->last_cen ? h->d_cen_h : nullptr;
-            fz.h_out = h->d_h[cur]; fz.v_out = h->d_v[cur];          // (cur was flipped behind conv layer 0: its output side)
-            fz.pharm_ptr = h->d_pharm_ptr; fz.Np = h->Np; fz.n_edge_items = e.ngroups_sel;
-            for (int r = 0; r < e.nreg; ++r) (r < h->B ? fz.nff_cap : fz.npf_cap) += region_groups(r, 16);
-            fz.xcd_split = ((h->pol.xcd_split & 1) && 2 * h->B <= 64 && h->max_nf <= 16) ? 1 : 0;
-            // every graph with regions of one capacity (the same number of centers everywhere): the regions of an etype sit at a fixed
-            // stride and the item map is arithmetic (k_n16_fused_u); PFDYN_FUSED_UNI=0: the work-list form
-            if (fz.xcd_split && h->pol.fused_uni && e.reg == h->d_reg && e.nreg == 2 * h->B) {
-                bool uni = true;
-                int stride[2] = {0, 0};
-                for (int et = 0; et < 2 && uni; ++et) {
-                    const size_t o = (size_t)et * h->B;
-                    if (h->B > 1) stride[et] = h->h_reg[o + 1] - h->h_reg[o];
-                    for (int g = 0; g < h->B && uni; ++g)
-                        uni = h->h_cap[o + g] == h->h_cap[o] && h->h_reg[o + g] == h->h_reg[o] + g * stride[et];
-                    uni = uni && stride[et] >= 0 && stride[et] < 65536 && (h->h_cap[o] + 15) / 16 < 256 && h->h_cap[o] > 0;
-                }
-                if (uni) {
-                    fz.uni_ff_base = h->h_reg[0]; fz.uni_pf_base = h->h_reg[(size_t)h->B];
-                    fz.uni_strides = stride[0] | (stride[1] << 16);
-                    fz.uni_groups = ((h->h_cap[0] + 15) / 16) | (((h->h_cap[(size_t)h->B] + 15) / 16) << 8);
-                }
-            }
-            h->last_family[l] = 17;                      // pf_debug_kernel_family: 16-row items with conv layer 0's node update in front
-            { ProfScope ps(h, pf_handle::K_EDGE_LAST, s); pfk_n16_fused(&e, &fz, &ep, s); }
-        }
-        else if (n16e) {
-            // PFDYN_PA_CHECK: the kept groups of the rows computed ahead must carry the serial of the launch that computed them (before this
-            // launch overwrites the count snapshot the check compares with)
-            if (l == 0 && e.pa_skip && h->d_pa_gstamp && h->d_pa_chk)
-                pfk_pa_check(h->d_dyn_cnt, h->d_pa_cnt, e.reg, e.pa_skip, h->d_pa_gstamp, h->spec_serial, h->B, h->d_pa_chk, s);
-            ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_n16_edge(&e, &ep, l == 0, s);
-        }
-        else if (rg) { ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_rg_edge(&e, enc_fly ? &ep : nullptr, l == 0, rg, esplit, rgp, s); }
-        else if (e.ntiles <= h->pol.coop_edge_max && !train) { ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_edge_msg_coop(&e, l == 0, s); }
-        else if (e.ntiles <= ((last || pruned) ? h->pol.coop2_edge_max : h->pol.coop2_dense_max) && !train) { ProfScope ps(h, (last && c.n_convs > 1) ? pf_handle::K_EDGE_LAST : pf_handle::K_EDGE_COOP, s); pfk_edge_msg_coop2(&e, l == 0, s); }
-        else { ProfScope ps(h, pf_handle::K_EDGE, s); pfk_edge_msg(&e, l == 0, s); }
-
-        NodeParams n{};
-        n.tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
-        n.ntiles = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
-        n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N;
-        n.pp_slot = pruned ? (shared ? 3 : 2) : 1; n.row_ids = h->d_act_ids; n.dyn_cnt = h->d_dyn_cnt;
-        n.msg_s = e.msg_s; n.msg_v = e.msg_v; n.zero_row = h->zero_row;
-        n.h_in = e.h; n.v_in = e.v;
-        n.h_out = train ? h->t_H[l + 1] : h->d_h[cur ^ 1]; n.v_out = train ? h->t_V[l + 1] : h->d_v[cur ^ 1];
-        if (train) { n.drop_thr = h->t_common.drop_thr; n.drop_scale = h->t_common.drop_scale; n.seed = h->t_common.seed; n.layer = l; n.mask_override = h->t_common.mask_override; }
-        n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B;
-        n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
-        for (int nt = 0; nt < 2; ++nt) {
-            const size_t* lo = &h->ln_off[(size_t)(l * 2 + nt) * 4];
-            n.w[nt].ln1_w = h->d_w + lo[0]; n.w[nt].ln1_b = h->d_w + lo[1];
-            n.w[nt].ln2_w = h->d_w + lo[2]; n.w[nt].ln2_b = h->d_w + lo[3];
-            n.w[nt].upd = h->d_gvp + h->upd_base(l, nt);
-        }
-        n.n_upd = c.n_update_gvps;
-        n.grp = rg ? 4 * rg : 32;
-        n.grp_pa = rgp ? 4 * rgp : n.grp;
-        if (train) {
-            h->t_grp.resize(c.n_convs); h->t_grp[l] = n.grp;
-            h->t_node_saved.resize(c.n_convs); h->t_node_saved[l] = 0;
-        }
-        for (int nt = 0; nt < 2; ++nt) n.rg_upd[nt] = h->d_w + h->rg_upd[(size_t)l * 2 + nt];
-        for (int nt = 0; nt < 2; ++nt) {
-            n.rgs_upd[nt] = h->d_w + h->rgs_upd[(size_t)l * 2 + nt];
-            n.rgs_stride[nt] = (int)h->rgs_upd_stride[(size_t)l * 2 + nt];
-        }
-        if (fuse_l0node && l == 0) {       // no node launch: the last layer's edge items (and its store items) compute these rows
-            fz.in_start = n.in_start; fz.in_cnt = n.in_cnt; fz.N = n.N; fz.pp_slot = n.pp_slot;
-            // (records describe the sources' in-edges as the update + build left them: the "pa" region as an atom's second segment)
-            fz.rec = (h->rec_valid && h->d_rec && n.pp_slot == 2 && !shared) ? h->d_rec : nullptr;
-            fz.msg_s = n.msg_s; fz.msg_v = n.msg_v; fz.zero_row = n.zero_row; fz.grp = n.grp; fz.grp_pa = n.grp_pa;
-            fz.gid = n.gid; fz.gnorm = n.gnorm; fz.B = n.B; fz.norm_mode = n.norm_mode; fz.norm_value = n.norm_value;
-            for (int nt = 0; nt < 2; ++nt) {
-                fz.ln1_w[nt] = n.w[nt].ln1_w; fz.ln1_b[nt] = n.w[nt].ln1_b; fz.ln2_w[nt] = n.w[nt].ln2_w; fz.ln2_b[nt] = n.w[nt].ln2_b;
-            }
-            fz.n_upd = n.n_upd;
-            cur ^= 1;
-            continue;
-        }
-        if (rg) {
-            const int rgn = (long)n.ntiles * 32 >= h->pol.rg2_rows_min_node ? 2 : 1;
-            const bool fuse = last && !train && h->fuse_head && h->n_head_tiles == n.ntiles;
-            const int nsplit = (!train && rgn == 1 && n.ntiles * 8 <= (fuse ? h->pol.rg_split_max_head : h->pol.rg_split_max_node)) ? 1 : 0;
-            // the tail launch: one workgroup per graph does the centers' node update, the head, the sampler update and the
-            // edge build (the fast build's shape: kNN pf edges, pockets of at most 512 atoms)
-            const bool tail = fuse && step != nullptr && l > 0 && (h->pol.n16_mask & 8) && h->B <= h->pol.tail_graphs_max &&
-                              enc_fly && c.pf_k > 0 && h->max_np <= 512 && c.pharm_nf <= 16 && h->step_build_fast;
-            const bool tail16 = tail && h->pol.tail_form == 16 && h->n16_tail != 0;
-            if (tail && !tail16) {                      // row-group form: the fused node + head item, two per workgroup
-                HeadParams hp{};
-                hp.tiles = h->d_head_tiles; hp.ntiles = h->n_head_tiles; hp.node_base = h->Np;
-                hp.gvps = h->d_gvp + h->head_base(); hp.n_gvps = c.n_noise_gvps;
-                hp.a_out = h->d_w + h->out_a; hp.b_out = h->d_w + h->out_b; hp.pharm_nf = c.pharm_nf;
-                hp.eps_h = eps_h; hp.eps_x = eps_x;
-                const bool share_next = (h->prune && c.n_convs == 2) && share_now(h);     // what the next denoising step's dynamics call will ask for
-                const BuildParams bpn = build_params(h, share_next);
-                { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_tail(&n, &hp, step, &bpn, s); }
-                build_done(h, share_next);
-                h->tail_done = true; h->last_tail = 4;
-                head_done = true;
-            } else if (tail16) {
-                TailParams tp{};
-                tp.in_start = n.in_start; tp.in_cnt = n.in_cnt; tp.N = n.N;
-                tp.msg_s = n.msg_s; tp.msg_v = n.msg_v; tp.zero_row = n.zero_row; tp.grp = n.grp;
-                tp.h_in = n.h_in; tp.v_in = n.v_in;
-                tp.gid = n.gid; tp.gnorm = n.gnorm; tp.B = n.B; tp.norm_mode = n.norm_mode; tp.norm_value = n.norm_value;
-                tp.ln1_w = n.w[1].ln1_w; tp.ln1_b = n.w[1].ln1_b; tp.ln2_w = n.w[1].ln2_w; tp.ln2_b = n.w[1].ln2_b;
-                tp.n_upd = n.n_upd; tp.n_head = c.n_noise_gvps;
-                tp.chain = h->d_w + h->n16_tail; tp.chain_stride = (int)h->n16_tail_stride;
-                tp.pharm_nf = c.pharm_nf; tp.eps_h = eps_h; tp.eps_x = eps_x;
-                const bool share_next = (h->prune && c.n_convs == 2) && share_now(h);     // what the next denoising step's dynamics call will ask for
-                const BuildParams bpn = build_params(h, share_next);
-                { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_n16_tail(&tp, step, &bpn, s); }
-                build_done(h, share_next);
-                h->tail_done = true; h->last_tail = 16;
-                head_done = true;
-            } else if (fuse) {
-                // few two-wave items: confined to node_xcds XCDs when they fit one per compute unit there (32 CUs per XCD)
-                if (nsplit && h->pol.node_xcds > 0 && n.ntiles * 8 <= 32 * h->pol.node_xcds) n.xcd_n = h->pol.node_xcds;
-                if (nsplit && l > 0 && h->pol.node_static) { n.st_n0 = h->Np; n.st_n = h->Nf; }      // (the last layer's node tiles ARE the static tiling of the centers)
-                HeadParams hp{};
-                hp.tiles = h->d_head_tiles; hp.ntiles = h->n_head_tiles; hp.node_base = h->Np;
-                hp.gvps = h->d_gvp + h->head_base(); hp.n_gvps = c.n_noise_gvps;
-                hp.a_out = h->d_w + h->out_a; hp.b_out = h->d_w + h->out_b; hp.pharm_nf = c.pharm_nf;
-                hp.eps_h = eps_h; hp.eps_x = eps_x;
-                // a denoising step of a small batch: the step's update + build joins this launch as workgroups of its own (the fast
-                // build's shape: kNN pf edges, pockets of at most 512 atoms); timing the two separately needs the separate launches
-                const bool hsb = n.st_n > 0 && step != nullptr && h->pol.hs_build && enc_fly && c.pf_k > 0 && h->max_np <= 512 && c.pharm_nf <= 16 &&
-                                 h->step_build_fast && h->B <= 256 && !(h->prof_mask & (1u << pf_handle::K_STEP)) && h->d_xchg && h->d_xstat;
-                if (hsb) {
-                    hp.xchg = h->d_xchg; hp.xchg_fault = h->xchg_fault;
-                    // center hoist for the NEXT call: its timestep from the announced plan (the entry behind this step's t); the tables
-                    // serve a call that runs conv layer 0 on the n16 kernels with the type tables (as this one did); this step's
-                    // features before the update must be in a snapshot (pf_sample_begin / the previous step left it)
-                    CenHoistParams cp{};
-                    float t_next = NAN;
-                    if (h->cen_hoist && t_scalar && !h->t_plan.empty() && h->last_hoist == 16 && h->l0c_off != 0 && h->n16_l0h[ET_FF] != 0 &&
-                        h->snap_cur >= 0 && step->h_snap_out != nullptr && h->d_xchg2 && fuse_l0node) {
-                        const size_t n = h->t_plan.size();
-                        for (size_t k = 0; k < n; ++k) {
-                            const size_t i = (h->plan_pos + k) % n;
-                            if (h->t_plan[i] == *t_scalar) { h->plan_pos = i; if (i + 1 < n) t_next = h->t_plan[i + 1]; break; }
-                        }
-                    }
-                    // ---- the NEXT call's "pa" messages, ahead of time, as workgroups of this launch (BuildParams::pa_same): conv layer 0's rows
-                    // of this call have been consumed by the fused launch, the next timestep's type tables exist (or are made now)
-                    EdgeParams es{};
-                    EncodeParams ees{};
-                    int spec_groups = 0;
-                    if (h->e0_saved && h->pa_spec && !h->t_plan.empty() && t_scalar && h->d_pa_stamp && !(h->prune && c.n_convs == 2 && share_now(h))) {
-                        float tn = NAN;
-                        const size_t n = h->t_plan.size();
-                        for (size_t k = 0; k < n; ++k) {
-                            const size_t i = (h->plan_pos + k) % n;
-                            if (h->t_plan[i] == *t_scalar) { if (i + 1 < n) tn = h->t_plan[i + 1]; break; }
-                        }
-                        if (tn == tn) {
-                            l0_prepare_t(h, &tn, 1, s);                  // (a no-op when the plan was announced)
-                            uint32_t bits; memcpy(&bits, &tn, 4);
-                            es = h->e0;
-                            es.ptab = h->d_ptab + (size_t)h->ptab_slot[bits] * L0_NTAB * c.rec_nf * PF_S;
-                            es.pa_skip = nullptr; es.pcen = nullptr;
-                            for (int et = 0; et < 4; ++et) { es.n16[et] = h->d_w + h->n16_l0[et]; es.n16_stride[et] = (int)h->n16_l0_stride[et]; }
-                            ees = h->ep0; ees.t_scalar = tn;
-                            spec_groups = h->e0_groups;
-                            h->spec_valid = true; h->spec_t = tn; h->spec_wver = h->w_version;
-                            es.pa_serial = h->spec_serial = ++h->pa_serial;
-                            es.pa_gstamp = h->d_pa_gstamp;
-                        }
-                    }
-                    if (t_next == t_next) {
-                        cp.on = 1; cp.Nf = h->Nf; cp.nf = c.pharm_nf; cp.t_next = t_next;
-                        cp.pharm_h = h->d_snap[h->snap_cur]; cp.noise = step->noise;
-                        cp.a_ts = step->a_ts; cp.var = step->var; cp.sigma = step->sigma; cp.ep_zt = step->ep_zt; cp.ep_pred = step->ep_pred;
-                        cp.ep_feat = step->ep_feat;
-                        cp.enc_w = h->d_w + h->enc_w[1]; cp.enc_b = h->d_w + h->enc_b[1];
-                        cp.enc_lw = h->d_w + h->enc_lw[1]; cp.enc_lb = h->d_w + h->enc_lb[1];
-                        cp.blk = h->d_w + h->l0c_off; cp.cen_h = h->d_cen_h; cp.cen_p = h->d_cen_p; cp.xchg2 = h->d_xchg2;
-                        hp.xchg2 = h->d_xchg2;
-                        h->cen_valid = true; h->cen_t = t_next; h->cen_wver = h->w_version;
-                    }
-                    const bool share_next = (h->prune && c.n_convs == 2) && share_now(h);     // what the next denoising step's dynamics call will ask for
-                    BuildParams bpn = build_params(h, share_next);
-                    // edge records for the next call's fused launch: radius ff edges, compact "pa" regions, the static hoist's element types
-                    const bool with_rec = h->d_rec && !share_next && c.ff_k == 0 && bpn.act_ids && !bpn.pa_static && h->last_hoist == 16 && fuse_l0node;
-                    if (with_rec) { bpn.rec = h->d_rec; bpn.ptype = h->d_ptype; }
-                    // PFDYN_PA_SPEC_SPLIT (test knob): no speculative slots in the merged launch; items w < k run just before it (the kind-3
-                    // counts before the build), w >= k just after it (the counts after the build).  "mid" / "step": k is half / a per-step
-                    // fraction of the non-empty groups, fixed by the launch in front (k_pa_spec)
-                    const bool split = spec_groups > 0 && h->pa_spec_split != 0;
-                    if (split) {
-                        const int frac = h->pa_spec_split == -1 ? 128 : (h->pa_spec_split == -2 ? (int)((((uint32_t)h->pa_serial * 2654435761u) >> 16) & 255) + 1 : 0);
-                        pfk_pa_spec(&es, &ees, spec_groups, 0, std::max(h->pa_spec_split, 0), frac, h->d_pa_cnt + h->B, s);
-                    }
-                    { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_node_hs_build(&n, &hp, step, &bpn, h->d_xstat, h->pol.xchg_sleep, h->pol.hsb_avoid, h->xchg_poll_max, &cp, &es, &ees, split ? 0 : spec_groups, s); }
-                    if (split) pfk_pa_spec(&es, &ees, spec_groups, 1, 0, 0, h->d_pa_cnt + h->B, s);
-                    build_done(h, share_next, with_rec);
-                    h->tail_done = true; h->last_tail = 2;
-                } else { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_node(&n, &hp, enc_fly ? &ep : nullptr, l == 0, rgn, nsplit, s); }
-                head_done = true;
-            } else {
-                if (train && h->train_node_save) {
-                    n.sv_z = h->t_nsv_z[l]; n.sv_g = h->t_nsv_g[l]; n.sv_v = h->t_nsv_v[l]; n.sv_stride = (size_t)2 * h->N;
-                    h->t_node_saved[l] = 1;
-                }
-                ProfScope ps(h, pf_handle::K_NODE_COOP, s); pfk_rg_node(&n, nullptr, enc_fly ? &ep : nullptr, l == 0, rgn, nsplit, s);
-            }
-        }
-        else if (last && !train && h->fuse_head && n.ntiles <= h->pol.coop_node_max && h->n_head_tiles == n.ntiles) {
-            // last layer (pharm tiles only) + noise head in one launch: the layer output stays in registers
-            HeadParams hp{};
-            hp.tiles = h->d_head_tiles; hp.ntiles = h->n_head_tiles; hp.node_base = h->Np;
-            hp.gvps = h->d_gvp + h->head_base(); hp.n_gvps = c.n_noise_gvps;
-            hp.a_out = h->d_w + h->out_a; hp.b_out = h->d_w + h->out_b; hp.pharm_nf = c.pharm_nf;
-            hp.eps_h = eps_h; hp.eps_x = eps_x;
-            { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_node_head_coop(&n, &hp, l == 0, s); }
-            head_done = true;
-        }
-        else if (train && h->train_rg_node && h->pol.rg_mode(n.ntiles) > 0) {
-            // training forward: the row-group node kernel (with the two GVPDropout sites) on the tile edge kernels' partial rows
-            // (one per 32-slot tile and destination: grp = 32); the layer input comes from memory, as the backward kernels read it
-            n.grp = 32; n.grp_pa = 32;
-            if (h->train_node_save) {
-                n.sv_z = h->t_nsv_z[l]; n.sv_g = h->t_nsv_g[l]; n.sv_v = h->t_nsv_v[l]; n.sv_stride = (size_t)2 * h->N;
-                h->t_node_saved[l] = 1;
-            }
-            ProfScope ps(h, pf_handle::K_NODE_COOP, s);
-            pfk_rg_node(&n, nullptr, nullptr, l == 0, h->pol.rg_mode(n.ntiles), 0, s);
-        }
-        else if (n.ntiles <= h->pol.coop_node_max && !train) { ProfScope ps(h, pf_handle::K_NODE_COOP, s); pfk_node_update_coop(&n, l == 0, s); }
-        else { ProfScope ps(h, pf_handle::K_NODE, s); pfk_node_update(&n, l == 0, s); }
-        cur ^= 1;
+    else if (dc.last && !train && h->fuse_head && n.ntiles <= h->pol.coop_node_max && h->n_head_tiles == n.ntiles) {
+        // last layer (pharm tiles only) + noise head in one launch: the layer output stays in registers
+        const HeadParams hp = head_params(h, dc.eps_h, dc.eps_x);
+        { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_node_head_coop(&n, &hp, l == 0, s); }
+        dc.head_done = true;
     }
-    HeadParams hp{};
-    hp.tiles = h->d_head_tiles; hp.ntiles = h->n_head_tiles; hp.node_base = h->Np;
-    hp.h = train ? h->t_H[c.n_convs] : h->d_h[cur]; hp.v = train ? h->t_V[c.n_convs] : h->d_v[cur];
-    hp.gvps = h->d_gvp + h->head_base(); hp.n_gvps = c.n_noise_gvps;
-    hp.a_out = h->d_w + h->out_a; hp.b_out = h->d_w + h->out_b; hp.pharm_nf = c.pharm_nf;
-    hp.eps_h = eps_h; hp.eps_x = eps_x;
+    else if (train && h->train_rg_node && h->pol.rg_mode(n.ntiles) > 0) {
+        // training forward: the row-group node kernel (with the two GVPDropout sites) on the tile edge kernels' partial rows
+        // (one per 32-slot tile and destination: grp = 32); the layer input comes from memory, as the backward kernels read it
+        n.grp = 32; n.grp_pa = 32;
+        if (h->train_node_save) node_save_levels(h, l, n);
+        ProfScope ps(h, pf_handle::K_NODE_COOP, s); pfk_rg_node(&n, nullptr, nullptr, l == 0, h->pol.rg_mode(n.ntiles), 0, s);
+    }
+    else if (n.ntiles <= h->pol.coop_node_max && !train) { ProfScope ps(h, pf_handle::K_NODE_COOP, s); pfk_node_update_coop(&n, l == 0, s); }
+    else { ProfScope ps(h, pf_handle::K_NODE, s); pfk_node_update(&n, l == 0, s); }
+}
+// the noise head as a launch of its own, when no node launch carried it
+static void head_launch(DynCall& dc) {
+    pf_handle* h = dc.h; hipStream_t s = dc.s; const pf_config& c = h->cfg; const bool train = dc.train;
+    HeadParams hp = head_params(h, dc.eps_h, dc.eps_x);
+    hp.h = train ? h->t_H[c.n_convs] : h->d_h[dc.cur]; hp.v = train ? h->t_V[c.n_convs] : h->d_v[dc.cur];
     if (train) h->t_head_saved = false;
-    if (!head_done && train && h->train_rg_head && !h->rg_msg.empty() && h->Nf > 0) {
+    if (!dc.head_done && train && h->train_rg_head && !h->rg_msg.empty() && h->Nf > 0) {
         // training forward: the head chain on the row-group code (4 rows per wave), which also leaves every level's pre-activations,
         // gate pre-activations and gated vectors for k_bwd_head (pharm rows are the contiguous rows [Np, Np + Nf))
         UnitParams up{};
-        up.s_in = hp.h + (size_t)h->Np * PF_S; up.v_in = hp.v + (size_t)h->Np * 48; up.s_out = eps_h; up.v_out = eps_x;
+        up.s_in = hp.h + (size_t)h->Np * PF_S; up.v_in = hp.v + (size_t)h->Np * 48; up.s_out = dc.eps_h; up.v_out = dc.eps_x;
         up.n = h->Nf; up.kind = 3; up.n_gvps = c.n_noise_gvps; up.pharm_nf = c.pharm_nf;
         up.stream = h->d_w + h->rg_upd[(size_t)(c.n_convs - 1) * 2 + 1]; up.skip_gvps = c.n_update_gvps;
         up.sv_z = h->t_hsv_z; up.sv_g = h->t_hsv_g; up.sv_v = h->t_hsv_v; up.sv_stride = (size_t)h->Nf;
         { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_unit(&up, s); }
-        h->t_head_saved = true;
-        head_done = true;
+        h->t_head_saved = true; dc.head_done = true;
     }
-    if (!head_done) { ProfScope ps(h, pf_handle::K_HEAD, s); if (hp.ntiles <= h->pol.coop_node_max) pfk_noise_head_coop(&hp, s); else pfk_noise_head(&hp, s); }
-    h->edges_built = h->tail_done;          // whoever moves the coordinates next decides (pf_denoise_step rebuilds; the tail launch has)
+    if (!dc.head_done) { ProfScope ps(h, pf_handle::K_HEAD, s); if (hp.ntiles <= h->pol.coop_node_max) pfk_noise_head_coop(&hp, s); else pfk_noise_head(&hp, s); }
+}
+// sequence one dynamics call on the handle's state (xn, pharm_h, d_t).  train: keep every layer's input and message rows (h->t_*), compute every
+// tile (gradients need the full graph only where they are non-zero, but the first version of the backward pass walks the dense tile lists) and
+// apply dropout in the node update.  step: this call is the dynamics call of a denoising step (pf_denoise_step) -- when the tail launch or the
+// merged launch applies, the step's sampler update and edge build run behind the noise head in the same launch and h->tail_done tells the caller
+static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s, const float* t_scalar = nullptr, bool train = false, const StepParams* step = nullptr) {
+    if (h->wide && !train) return run_dynamics_wide(h, eps_h, eps_x, s, t_scalar);
+    const pf_config& c = h->cfg;
+    h->tail_done = false; h->last_tail = 0;
+    DynCall dc{};
+    dc.h = h; dc.s = s; dc.eps_h = eps_h; dc.eps_x = eps_x; dc.t_scalar = t_scalar; dc.train = train; dc.step = step;
+    // center hoist: the previous denoising step left h_c and P_ff / P_fp of every center for THIS call's timestep
+    dc.cen_have = !train && h->cen_valid && h->edges_built && t_scalar != nullptr && *t_scalar == h->cen_t && h->cen_wver == h->w_version;
+    h->cen_valid = false; h->last_cen = false;
+    // rows computed ahead for this call's "pa" regions (the speculative items of the previous step's merged launch)
+    dc.spec_have = !train && h->spec_valid && h->edges_built && t_scalar != nullptr && *t_scalar == h->spec_t && h->spec_wver == h->w_version;
+    h->spec_valid = false; h->last_spec = 0; h->e0_saved = false;
+    if (!train) n16_refresh(h, s);
+    dc.ep = encode_params(h, t_scalar, train ? h->t_H[0] : h->d_h[0]);
+    if (const int rc = dyn_prologue(dc)) return rc;
+    dyn_hoist_prepare(dc);
+    h->last_hoist = 0;
+    // fused launch (pf_n16.hip: k_n16_fused): with two conv layers, receptive-field pruning and kNN pf edges the rows conv layer 0's node update produces are
+    // exactly the sources of the last layer's edges (+ the centers): every edge item of the last layer updates its own source rows first, and the node launch of conv layer 0 disappears
+    dc.fuse_l0node = !train && dc.n16_batch && (long)h->n_edge_tiles_act * 32 <= h->pol.n16_fuse_rows_max && (h->pol.n16_mask & 4) && (h->pol.n16_mask & 1) && dc.hoist && c.n_convs == 2 && prune_layer(h) == 0 && c.pf_k > 0 &&
+                     c.n_update_gvps >= 1 && h->rg_compact && 2 * h->B <= 1024 && h->d_msg_s2 != nullptr && h->n16_fused[0] != 0;
+    for (int l = 0; l < c.n_convs; ++l, dc.cur ^= 1) { edge_launch(dc, l); node_launch(dc, l); }
+    head_launch(dc);
+    h->edges_built = h->tail_done;          // whoever moves the coordinates next decides (pf_denoise_step rebuilds; the tail and merged launches have)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return PF_OK;
@@ -2879,12 +2893,9 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
     if (h->snap_cur < 0) h->cen_valid = false;
     if (h->tail_done) return PF_OK;         // the tail launch did the update and built the next call's edges
     if (encoders_on_the_fly(h)) {           // update + the edges of the next dynamics call in one launch
-        const pf_config& cc = h->cfg;
-        const bool share = (h->prune && cc.n_convs == 2) && share_now(h);     // what the next denoising step's dynamics call will ask for
+        const bool share = share_next(h);
         const BuildParams bp = build_params(h, share);
-        // kNN pf edges and pockets of at most 512 atoms: the latency-optimised kernel (one atom per thread)
-        const int fast = (h->cfg.pf_k > 0 && h->max_np <= 512 && h->cfg.pharm_nf <= 16 && h->step_build_fast) ? 1 : 0;
-        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_build(&sp, &bp, fast, s); }
+        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_build(&sp, &bp, step_build_fast_ok(h) ? 1 : 0, s); }
         build_done(h, share);
         h->edges_built = true;
     } else { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update(&sp, s); }
@@ -3022,7 +3033,7 @@ int pf_debug_conv_layer(pf_handle* h, int32_t layer, const float* dev_prot_x, co
     pfk_copy(hf_, h->d_h[0] + Np * PF_S, Nf * PF_S, s);
     pfk_copy(vp_, h->d_v[0], Np * 48, s);
     pfk_copy(vf_, h->d_v[0] + Np * 48, Nf * 48, s);
-    BuildParams bp{};
+    BuildParams bp{};       // (not build_params(): it would add eorig, act_ids of a pruned model and, in a sampling run, pa_stamp)
     bp.B = h->B; bp.Np_tot = h->Np; bp.prot_ptr = h->d_prot_ptr; bp.pharm_ptr = h->d_pharm_ptr; bp.xn = h->d_xn;
     bp.reg = h->d_reg; bp.dyn_cnt = h->d_dyn_cnt; bp.esrc = h->d_esrc; bp.edst = h->d_edst;
     bp.in_start = h->d_in_start; bp.in_cnt = h->d_in_cnt; bp.N = h->N; bp.ff_k = c.ff_k; bp.pf_k = c.pf_k;
@@ -3030,30 +3041,14 @@ int pf_debug_conv_layer(pf_handle* h, int32_t layer, const float* dev_prot_x, co
     bp.gnorm = h->d_gnorm; bp.pp_cnt = h->d_pp_cnt; bp.pfq_cnt = h->d_pfq_cnt; bp.norm_mode = c.message_norm_mode;
     bp.act_ids = nullptr; bp.reg_act = h->d_reg_act;
     pfk_build_edges(&bp, s);
-    EdgeParams e{};
-    e.tiles = h->d_edge_tiles; e.ntiles = h->n_edge_tiles; e.dyn_cnt = h->d_dyn_cnt; e.esrc = h->d_esrc; e.edst = h->d_edst;
-    e.xn = h->d_xn; e.h = h->d_h[0]; e.v = h->d_v[0]; e.msg_s = h->d_msg_s; e.msg_v = h->d_msg_v;
-    e.w = h->d_gvp + h->msg_base(layer, 0); e.n_gvps = c.n_message_gvps;
-    linspace_f32(0.f, c.rbf_dmax, c.rbf_dim, e.rbf_mu);
-    e.rbf_inv_sigma = 1.0f / (c.rbf_dmax / (float)c.rbf_dim);
-    for (int et = 0; et < 4; ++et) e.rg[et] = h->d_w + h->rg_msg[(size_t)layer * 4 + et];
+    EdgeParams e = edge_params_base(h, layer, false, false);      // the dense tile lists, whichever layer
+    e.h = h->d_h[0]; e.v = h->d_v[0]; e.msg_s = h->d_msg_s; e.msg_v = h->d_msg_v;
     const int rg = h->pol.rg_mode(e.ntiles);                  // same choice as run_dynamics
     if (rg) pfk_rg_edge(&e, nullptr, 0, rg, 0, 0, s);
     else if (e.ntiles <= h->pol.coop_edge_max) pfk_edge_msg_coop(&e, 0, s); else pfk_edge_msg(&e, 0, s);
-    NodeParams n{};
-    n.tiles = h->d_node_tiles; n.ntiles = h->n_node_tiles; n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N;
-    n.pp_slot = 1; n.row_ids = h->d_act_ids; n.dyn_cnt = h->d_dyn_cnt;
-    n.msg_s = h->d_msg_s; n.msg_v = h->d_msg_v; n.zero_row = h->zero_row; n.h_in = h->d_h[0]; n.v_in = h->d_v[0]; n.h_out = h->d_h[1]; n.v_out = h->d_v[1];
-    n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
-    for (int nt = 0; nt < 2; ++nt) {
-        const size_t* lo = &h->ln_off[(size_t)(layer * 2 + nt) * 4];
-        n.w[nt].ln1_w = h->d_w + lo[0]; n.w[nt].ln1_b = h->d_w + lo[1]; n.w[nt].ln2_w = h->d_w + lo[2]; n.w[nt].ln2_b = h->d_w + lo[3];
-        n.w[nt].upd = h->d_gvp + h->upd_base(layer, nt);
-    }
-    n.n_upd = c.n_update_gvps;
-    n.grp = rg ? 4 * rg : 32;
-    n.grp_pa = n.grp;
-    for (int nt = 0; nt < 2; ++nt) n.rg_upd[nt] = h->d_w + h->rg_upd[(size_t)layer * 2 + nt];
+    NodeParams n = node_params_base(h, layer, false, false);
+    n.msg_s = h->d_msg_s; n.msg_v = h->d_msg_v; n.h_in = h->d_h[0]; n.v_in = h->d_v[0]; n.h_out = h->d_h[1]; n.v_out = h->d_v[1];
+    n.grp = n.grp_pa = rg ? 4 * rg : 32;
     if (rg) pfk_rg_node(&n, nullptr, nullptr, 0, std::max(1, h->pol.rg_mode(n.ntiles)), 0, s);
     else if (n.ntiles <= h->pol.coop_node_max) pfk_node_update_coop(&n, 0, s); else pfk_node_update(&n, 0, s);
     pfk_copy(h->d_h[1], ohp, Np * PF_S, s);
@@ -3496,8 +3491,7 @@ int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g
         e.sv_stride = (size_t)std::max<int64_t>(h->Ecap, 1);
         e.gs_buf = h->t_gs_buf; e.gv_buf = h->t_gv_buf;
         e.g = h->d_gvpt + h->msg_base(l, 0); e.n_gvps = c.n_message_gvps;
-        linspace_f32(0.f, c.rbf_dmax, c.rbf_dim, e.rbf_mu);
-        e.rbf_inv_sigma = 1.0f / ((c.rbf_dmax - 0.f) / (float)c.rbf_dim);
+        rbf_params(c, e.rbf_mu, &e.rbf_inv_sigma);
         e.l0 = l == 0;
         e.A_h = h->t_A_h; e.A_v = h->t_A_v; e.fix = h->t_fix;
         e.wpack = h->d_wpack + (size_t)h->msg_base(l, 0) * PFT_WPACK_FLOATS;
@@ -3809,19 +3803,19 @@ int pf_debug_work(pf_handle* h, double* flops, double* bytes, int64_t* n_edges, 
     if (n_edges) for (int i = 0; i < 4; ++i) n_edges[i] = ne[i];
     // what the kernels actually compute: the last layer only feeds pharm nodes; the layer before it (when pruning
     // is on) only the active atoms
-    const int prune_layer = (h->prune && c.n_convs >= 2) ? c.n_convs - 2 : -1;
+    const int pl = prune_layer(h);
     double ex = (double)h->Nf * head + enc;
     for (int l = 0; l < c.n_convs; ++l) {
         double el, nl;
         if (l == c.n_convs - 1) { el = (double)(ne[0] + ne[1]); nl = (double)h->Nf; }
-        else if (l == prune_layer) { el = (double)(ne[0] + ne[1] + ne[2] + n_pa); nl = (double)(h->Nf + n_act); }
+        else if (l == pl) { el = (double)(ne[0] + ne[1] + ne[2] + n_pa); nl = (double)(h->Nf + n_act); }
         else { el = E; nl = (double)h->N; }
         ex += el * per_edge + nl * per_node;
         // static hoist (last call): the pp edges of layer 0 skip their first message GVP but for its gates
         // (n16 form, last_hoist == 16: the pp AND pf edges skip the h_src block of the first scalar Linear and the Vh matrix product
         // -- a type-table row and 17 x 3 multiplications instead)
-        if (l == 0 && h->last_hoist == 16) ex -= (double)((l == prune_layer ? n_pa : (l == c.n_convs - 1 ? 0 : ne[3])) + ne[1] + (h->last_cen ? ne[0] + ne[2] : 0)) * (2.0 * 128 * 128 + 2.0 * 16 * 17 * 3);
-        else if (l == 0 && h->last_hoist) ex -= (double)(l == prune_layer ? n_pa : (l == c.n_convs - 1 ? 0 : ne[3])) * (g0 - 2.0 * 128 * 16);
+        if (l == 0 && h->last_hoist == 16) ex -= (double)((l == pl ? n_pa : (l == c.n_convs - 1 ? 0 : ne[3])) + ne[1] + (h->last_cen ? ne[0] + ne[2] : 0)) * (2.0 * 128 * 128 + 2.0 * 16 * 17 * 3);
+        else if (l == 0 && h->last_hoist) ex -= (double)(l == pl ? n_pa : (l == c.n_convs - 1 ? 0 : ne[3])) * (g0 - 2.0 * 128 * 16);
         if (executed_edges) executed_edges[l] = (int64_t)el;
     }
     if (executed_flops) *executed_flops = ex;
