@@ -214,8 +214,9 @@ int pf_train_forward(pf_handle* h, const float* dev_prot_x /*[Np,3] or NULL*/, c
                      float* dev_eps_h, float* dev_eps_x, pf_stream stream);
 int pf_train_backward(pf_handle* h, const float* dev_g_eps_h /*[Nf,pharm_nf]*/, const float* dev_g_eps_x /*[Nf,3]*/,
                       float* dev_grad /*[n_params]*/, pf_stream stream);
-/* The loss around the dynamics, fused (PharmacophoreDiff.forward, pharmacodiff.py:162-243, with the noise parameterisation
- * of both outputs -- endpoint_param_feat / endpoint_param_coord false): per graph the COM of the clean centers is taken
+/* The loss around the dynamics, fused (PharmacophoreDiff.forward, pharmacodiff.py:162-243; pf_train_loss_forward: the noise
+ * parameterisation of both outputs, pf_train_loss_forward_ep: every combination of endpoint_param_coord /
+ * endpoint_param_feat, see below): per graph the COM of the clean centers is taken
  * off the centers and the bound pocket (:176-183), z_t = alpha_t x0 + sigma_t eps with alpha / sigma read from the caller's
  * tables at t_int (:186-197: dev_alpha[k] = alpha(gamma(k / T)), likewise sigma), the COM of the noised centers is removed
  * when remove_com (:199-205), the dynamics run in train() mode (pf_train_forward), and dev_out receives
@@ -224,6 +225,17 @@ int pf_train_backward(pf_handle* h, const float* dev_g_eps_h /*[Nf,pharm_nf]*/, 
  *   [6] total loss = [0] + [1]  [7] total error = [2] + 1 - [4]  [8] weighted total error = [3] + 1 - [5]  (what
  *       training_step / validation_step derive, :274-277, :303-306).
  * dev_pharm_h0 are the raw feature one-hots (divided by feat_norm inside).  The protein coordinates are the bound ones.
+ * pf_train_loss_forward_ep takes the two parameterisation flags of the reference's configuration (independent of each
+ * other; pf_train_loss_forward is its (0, 0) call and computes the same bits).  With wl = 1 - t when weighted_loss, else 1,
+ * per center f of graph g the four forms are
+ *   endpoint_param_coord 0  pos loss term |eps_x - dyn_x|^2 (:217); position error |(x_t - sigma_t dyn_x) / alpha_t - x0|^2 (:219)
+ *   endpoint_param_coord 1  the dynamics predict the clean center: x_pred = dyn_x + COM taken off the noised centers (added
+ *                           only when remove_com), pos loss term |x_pred - x0|^2 (:210-215), which is also the position error
+ *   endpoint_param_feat 0   feat loss term |eps_h - dyn_h|^2 (:208); predicted type argmax (h_t - sigma_t dyn_h) / alpha_t (:209)
+ *   endpoint_param_feat 1   the dynamics predict the type logits: feat loss term cross_entropy(dyn_h, argmax h0) (:204-206),
+ *                           predicted type argmax dyn_h
+ * with x0 the COM-removed clean center; the terms times wl are summed and divided by eps.numel() (:226-232: Nf * 3 and
+ * Nf * pharm_nf, the cross-entropy's too), the metrics are as above (:234-241).  The backward calls serve every form.
  * pf_train_loss_backward(g_pos, g_feat) = d(g_pos * pos loss + g_feat * feat loss)/d(parameters), the two upstream
  * scalars read from device memory; it consumes the state of the forward (one backward per forward).
  * pf_train_loss_backward_out takes the upstream gradient of all nine outputs instead (what autograd hands the node that
@@ -233,6 +245,11 @@ int pf_train_loss_forward(pf_handle* h, const float* dev_pharm_x0 /*[Nf,3]*/, co
                           const float* dev_alpha /*[>= max t_int + 1]*/, const float* dev_sigma, int32_t n_timesteps, float feat_norm,
                           int32_t remove_com, int32_t weighted_loss, float dropout_p, uint32_t seed, float* dev_out /*[9]*/,
                           pf_stream stream);
+int pf_train_loss_forward_ep(pf_handle* h, const float* dev_pharm_x0 /*[Nf,3]*/, const float* dev_pharm_h0 /*[Nf,pharm_nf]*/,
+                             const int32_t* dev_t_int /*[B]*/, const float* dev_eps_x /*[Nf,3]*/, const float* dev_eps_h /*[Nf,pharm_nf]*/,
+                             const float* dev_alpha /*[>= max t_int + 1]*/, const float* dev_sigma, int32_t n_timesteps, float feat_norm,
+                             int32_t remove_com, int32_t weighted_loss, int32_t endpoint_param_coord, int32_t endpoint_param_feat,
+                             float dropout_p, uint32_t seed, float* dev_out /*[9]*/, pf_stream stream);
 int pf_train_loss_backward(pf_handle* h, const float* dev_g_pos /*[1]*/, const float* dev_g_feat /*[1]*/,
                            float* dev_grad /*[n_params]*/, pf_stream stream);
 int pf_train_loss_backward_out(pf_handle* h, const float* dev_g_out /*[9]*/, float* dev_grad /*[n_params]*/, pf_stream stream);

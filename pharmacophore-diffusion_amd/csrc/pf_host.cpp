@@ -78,7 +78,7 @@ void pfk_gather_weights(const float* flat, const int* map, size_t n, float* pack
 void pfk_n16_split_words(const float* flat, const int4* tab, size_t n, float* packed, hipStream_t s);
 void pfk_pack_gvp(const float* W, const GvpT* g, int n_gvps, float* out_b, float* out_f, const ScaleArgs* sa, hipStream_t s);
 void pfk_loss_prepare(const LossParams* p, hipStream_t s);
-void pfk_loss_eval(const LossParams* p, hipStream_t s);
+void pfk_loss_eval(const LossParams* p, int ep_coord, int ep_feat, hipStream_t s);
 void pfk_scale_loss(float* gx, int nx, const float* a, const float* a2, float* gh, int nh, const float* b, const float* b2, hipStream_t s);
 void pfk_compact_node_rows(const NodeTile* tiles, int ntiles, const int* dyn_cnt, const int* row_ids, int N, int* list, int cap, int* ucnt,
                            hipStream_t s);
@@ -477,7 +477,7 @@ struct pf_handle {
     int n_gvpt = 0;                         // entries of d_gvpt (message, update, head GVPs)
     float* d_wpack = nullptr;               // k_pack_gvp tables of every GVP (input-gradient fragments, then forward fragments); valid for w_version == wpack_version
     uint64_t wpack_version = ~0ull;
-    float *t_lx0c = nullptr, *t_lag = nullptr, *t_lsg = nullptr, *t_lgx = nullptr, *t_lgh = nullptr, *t_lout = nullptr;   // pf_train_loss_forward
+    float *t_lx0c = nullptr, *t_lag = nullptr, *t_lsg = nullptr, *t_lcom2 = nullptr, *t_lgx = nullptr, *t_lgh = nullptr, *t_lout = nullptr;   // pf_train_loss_forward
     bool t_have_loss = false;
     float* t_Gg = nullptr;                  // encoder backward: upstream gradient summed per (graph, element)
     int* t_ulist = nullptr;                 // dense per-type row list of the layer being differentiated (k_compact_node_rows; counts: t_ccnt[97], [98])
@@ -3086,7 +3086,7 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
     need((size_t)PFT_ENC_BLOCKS * std::max(h->enc_n, 1));
     need((size_t)2 * std::max(h->n_node_tiles, h->n_node_tiles_act) + 64);
     need((size_t)h->B * c.rec_nf * PF_S);
-    need((size_t)h->Nf * 3); need((size_t)h->B); need((size_t)h->B); need((size_t)h->Nf * 3); need((size_t)h->Nf * c.pharm_nf); need(64);   // loss buffers
+    need((size_t)h->Nf * 3); need((size_t)h->B); need((size_t)h->B); need((size_t)h->B * 3); need((size_t)h->Nf * 3); need((size_t)h->Nf * c.pharm_nf); need(64);   // loss buffers
     for (int l = 0; l < L; ++l) { need((size_t)c.n_update_gvps * 2 * N * PF_S); need((size_t)c.n_update_gvps * 2 * N * 16); need((size_t)c.n_update_gvps * 2 * N * 48); }
     need((size_t)c.n_noise_gvps * std::max(h->Nf, 1) * PF_S); need((size_t)c.n_noise_gvps * std::max(h->Nf, 1) * 16);
     need((size_t)c.n_noise_gvps * std::max(h->Nf, 1) * 48);
@@ -3136,6 +3136,7 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
     h->t_ulist = carve<int>(cur, h->t_ulist_cap * L);                          // per conv layer: [2 types][t_ucap] x (node id, saved-level row)
     h->t_Gg = carve<float>(cur, (size_t)h->B * c.rec_nf * PF_S);
     h->t_lx0c = carve<float>(cur, (size_t)h->Nf * 3); h->t_lag = carve<float>(cur, (size_t)h->B); h->t_lsg = carve<float>(cur, (size_t)h->B);
+    h->t_lcom2 = carve<float>(cur, (size_t)h->B * 3);
     h->t_lgx = carve<float>(cur, (size_t)h->Nf * 3); h->t_lgh = carve<float>(cur, (size_t)h->Nf * c.pharm_nf); h->t_lout = carve<float>(cur, 64);
     h->t_nsv_z.assign(L, nullptr); h->t_nsv_g.assign(L, nullptr); h->t_nsv_v.assign(L, nullptr);
     for (int l = 0; l < L; ++l) {
@@ -3260,19 +3261,20 @@ int pf_train_forward(pf_handle* h, const float* dev_prot_x, const float* dev_pha
     return rc;
 }
 
-int pf_train_loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* dev_pharm_h0, const int32_t* dev_t_int,
-                          const float* dev_eps_x, const float* dev_eps_h, const float* dev_alpha, const float* dev_sigma,
-                          int32_t n_timesteps, float feat_norm, int32_t remove_com, int32_t weighted_loss, float dropout_p,
-                          uint32_t seed, float* dev_out, pf_stream stream) {
+// who: the entry the caller used, for the messages (pf_train_loss_forward is the (0, 0) call of pf_train_loss_forward_ep)
+static int loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* dev_pharm_h0, const int32_t* dev_t_int,
+                        const float* dev_eps_x, const float* dev_eps_h, const float* dev_alpha, const float* dev_sigma,
+                        int32_t n_timesteps, float feat_norm, int32_t remove_com, int32_t weighted_loss, int32_t endpoint_param_coord,
+                        int32_t endpoint_param_feat, float dropout_p, uint32_t seed, float* dev_out, pf_stream stream, const char* who) {
     if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
-                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
+                                "the width-generic family is inference only)", who, h->cfg.n_hidden_scalars, h->cfg.vector_size);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_pharm_x0 || !dev_pharm_h0 || !dev_t_int || !dev_eps_x || !dev_eps_h || !dev_alpha || !dev_sigma || !dev_out)
-        PF_FAIL(h, PF_ERR_ARG, "pf_train_loss_forward: null argument");
-    if (n_timesteps < 1 || !(feat_norm > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_train_loss_forward: bad n_timesteps / feat_norm");
-    if (!(dropout_p >= 0.f && dropout_p < 1.f)) PF_FAIL(h, PF_ERR_ARG, "pf_train_loss_forward: dropout must be in [0, 1)");
-    if (h->Nf == 0) PF_FAIL(h, PF_ERR_ARG, "pf_train_loss_forward: the batch has no pharmacophore centers (the losses are means over them)");
+        PF_FAIL(h, PF_ERR_ARG, "%s: null argument", who);
+    if (n_timesteps < 1 || !(feat_norm > 0.f)) PF_FAIL(h, PF_ERR_ARG, "%s: bad n_timesteps / feat_norm", who);
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) PF_FAIL(h, PF_ERR_ARG, "%s: dropout must be in [0, 1)", who);
+    if (h->Nf == 0) PF_FAIL(h, PF_ERR_ARG, "%s: the batch has no pharmacophore centers (the losses are means over them)", who);
     hipStream_t s = (hipStream_t)stream;
     rc = ensure_train_ws(h, s);
     if (rc) return rc;
@@ -3295,7 +3297,7 @@ int pf_train_loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* 
     lp.x0 = dev_pharm_x0; lp.h0 = dev_pharm_h0; lp.t_int = dev_t_int; lp.eps_x = dev_eps_x; lp.eps_h = dev_eps_h;
     lp.alpha_tab = dev_alpha; lp.sigma_tab = dev_sigma;
     lp.xn = h->d_xn; lp.pharm_h = h->d_pharm_h; lp.t = h->d_t;
-    lp.x0c = h->t_lx0c; lp.alpha_g = h->t_lag; lp.sigma_g = h->t_lsg;
+    lp.x0c = h->t_lx0c; lp.alpha_g = h->t_lag; lp.sigma_g = h->t_lsg; lp.com2 = h->t_lcom2;
     lp.dyn_h = h->d_eps_h; lp.dyn_x = h->d_eps_x; lp.g_x = h->t_lgx; lp.g_h = h->t_lgh; lp.out = dev_out;
     h->edges_built = false; h->rec_valid = false;
     h->coords_custom = true;                     // the pocket moved with the centers' COM: trajectory constants of the bound coordinates do not apply
@@ -3303,11 +3305,28 @@ int pf_train_loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* 
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, nullptr, true);
     h->t_have_fwd = rc == PF_OK;
     if (rc) return rc;
-    pfk_loss_eval(&lp, s);
+    pfk_loss_eval(&lp, endpoint_param_coord != 0, endpoint_param_feat != 0, s);
     h->t_have_loss = true;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return PF_OK;
+}
+
+int pf_train_loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* dev_pharm_h0, const int32_t* dev_t_int,
+                          const float* dev_eps_x, const float* dev_eps_h, const float* dev_alpha, const float* dev_sigma,
+                          int32_t n_timesteps, float feat_norm, int32_t remove_com, int32_t weighted_loss, float dropout_p,
+                          uint32_t seed, float* dev_out, pf_stream stream) {
+    return loss_forward(h, dev_pharm_x0, dev_pharm_h0, dev_t_int, dev_eps_x, dev_eps_h, dev_alpha, dev_sigma, n_timesteps, feat_norm,
+                        remove_com, weighted_loss, 0, 0, dropout_p, seed, dev_out, stream, __func__);
+}
+
+int pf_train_loss_forward_ep(pf_handle* h, const float* dev_pharm_x0, const float* dev_pharm_h0, const int32_t* dev_t_int,
+                             const float* dev_eps_x, const float* dev_eps_h, const float* dev_alpha, const float* dev_sigma,
+                             int32_t n_timesteps, float feat_norm, int32_t remove_com, int32_t weighted_loss,
+                             int32_t endpoint_param_coord, int32_t endpoint_param_feat, float dropout_p, uint32_t seed,
+                             float* dev_out, pf_stream stream) {
+    return loss_forward(h, dev_pharm_x0, dev_pharm_h0, dev_t_int, dev_eps_x, dev_eps_h, dev_alpha, dev_sigma, n_timesteps, feat_norm,
+                        remove_com, weighted_loss, endpoint_param_coord, endpoint_param_feat, dropout_p, seed, dev_out, stream, __func__);
 }
 
 static int loss_backward(pf_handle* h, const float* g_pos, const float* g_pos2, const float* g_feat, const float* g_feat2,

@@ -171,7 +171,7 @@ struct BwdEncodeParams {
     const int* onehot_flag;                  // device: 0 iff every protein feature row is an element one-hot (k_l0_types at bind time)
 };
 
-// the loss around the dynamics (k_loss_prepare / k_loss_eval, pf_train_loss_forward)
+// the loss around the dynamics (k_loss_prepare / k_loss_eval, pf_train_loss_forward / _ep)
 // the loss's unit gradients (gx [nx], gh [nh]) times their upstream scalars a (+ a2), b (+ b2): device scalars, a2 / b2 may be null
 struct ScaleArgs { float* gx; int nx; const float* a; const float* a2; float* gh; int nh; const float* b; const float* b2; };
 
@@ -185,6 +185,7 @@ struct LossParams {
     const float* alpha_tab; const float* sigma_tab;
     float4* xn; float* pharm_h; float* t;    // the dynamics' input state
     float* x0c; float* alpha_g; float* sigma_g;
+    float* com2;                             // [B][3] COM of the noised centers that remove_com took off (zeros without it)
     const float* dyn_h; const float* dyn_x;  // the dynamics' outputs
     float* g_x; float* g_h; float* out;      // unit upstream gradients, [6] losses and metrics
     float* part; int* ticket;                // k_loss_eval: [blocks][8] partial sums; arrival counter (zero between launches)

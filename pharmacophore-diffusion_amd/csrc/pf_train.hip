@@ -2202,6 +2202,10 @@ __global__ void k_adam(float* p, const float* g, float* m, float* v, const size_
 //     dynamics' input state (xn, pharm_h, t) in place
 //   k_loss_eval (one block, fixed reduction order): the two losses (:208-232), the four metrics (:234-241) and the unit
 //     upstream gradients d(pos loss)/d(eps_x), d(feat loss)/d(eps_h) for pf_train_loss_backward
+//   k_loss_eval<EPC, EPF>: the endpoint parameterisations (pf_train_loss_forward_ep), each output on its own -- the dynamics'
+//     coordinate output is the clean center itself (:210-215; the COM that k_loss_prepare took off the noised centers, kept in
+//     com2, is added back), its feature output the logits of a cross-entropy against the clean type (:204-206);
+//     <false, false> is the noise parameterisation
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_loss_prepare(const LossParams p) {
     __shared__ float s_sh[8];
@@ -2235,6 +2239,7 @@ __global__ __launch_bounds__(256) void k_loss_prepare(const LossParams p) {
             s_sh[0] = cx; s_sh[1] = cy; s_sh[2] = cz; s_sh[3] = mx; s_sh[4] = my; s_sh[5] = mz;
             p.t[g] = (float)ti / (float)p.T;
             p.alpha_g[g] = a; p.sigma_g[g] = sg;
+            p.com2[3 * g] = mx; p.com2[3 * g + 1] = my; p.com2[3 * g + 2] = mz;      // zeros without remove_com
         }
     }
     __syncthreads();
@@ -2245,6 +2250,7 @@ __global__ __launch_bounds__(256) void k_loss_prepare(const LossParams p) {
 // one center per thread, 64 centers per block (a single block spent its time issuing ~30 strided loads per center from one compute
 // unit: 18 us at 1,536 centers); every block leaves its six partial sums, the block that draws the last ticket adds them in block
 // order -- the result does not depend on which block that is -- and re-arms the ticket
+template <bool EPC, bool EPF>
 __global__ __launch_bounds__(64) void k_loss_eval(const LossParams p) {
     const int lane = threadIdx.x;
     const int f = blockIdx.x * 64 + lane;
@@ -2267,26 +2273,61 @@ __global__ __launch_bounds__(64) void k_loss_eval(const LossParams p) {
         const float a = p.alpha_g[g], sg = p.sigma_g[g], wm = 1.0f - p.t[g], wl = p.weighted ? wm : 1.0f;
         const float xtv[3] = {xt.x, xt.y, xt.z};
         float xl = 0.f, err = 0.f;
+        if constexpr (EPC) {
+            // the prediction is the clean center in the frame before the second COM removal; the position error is the loss term
+            const float* m = p.com2 + 3 * g;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float d = ex[c] - dx[c];
-            xl += d * d;
-            p.g_x[3 * f + c] = -2.0f * wl * d * inv_x;
-            const float e = (xtv[c] - sg * dx[c]) / a - xc[c];
-            err += e * e;
+            for (int c = 0; c < 3; ++c) {
+                const float d = (dx[c] + m[c]) - xc[c];
+                xl += d * d;
+                p.g_x[3 * f + c] = 2.0f * wl * d * inv_x;
+            }
+            err = xl;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float d = ex[c] - dx[c];
+                xl += d * d;
+                p.g_x[3 * f + c] = -2.0f * wl * d * inv_x;
+                const float e = (xtv[c] - sg * dx[c]) / a - xc[c];
+                err += e * e;
+            }
         }
         float hl = 0.f, bp = 0.f, bt = 0.f;
         int ip = 0, it = 0;
+        if constexpr (EPF) {
+            // cross-entropy of the logits against the clean type: first maxima like argmax, the row maximum taken off before expf
 #pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (k < p.nf) {
-                const float d = eh[k] - dh[k];
-                hl += d * d;
-                p.g_h[(size_t)f * p.nf + k] = -2.0f * wl * d * inv_h;
-                const float hp = (ph[k] - sg * dh[k]) / a, ht = h0v[k];
-                if (k == 0 || hp > bp) { bp = hp; ip = k; }                  // first maximum, like argmax
-                if (k == 0 || ht > bt) { bt = ht; it = k; }
-            }
+            for (int k = 0; k < 8; ++k)
+                if (k < p.nf) {
+                    if (k == 0 || dh[k] > bp) { bp = dh[k]; ip = k; }
+                    if (k == 0 || h0v[k] > bt) { bt = h0v[k]; it = k; }
+                }
+            float se = 0.f, lt = 0.f, ek[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k < p.nf) {
+                    ek[k] = expf(dh[k] - bp);
+                    se += ek[k];
+                    if (k == it) lt = dh[k];
+                } else ek[k] = 0.f;
+            hl = logf(se) + bp - lt;
+            const float rs = 1.0f / se;
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k < p.nf) p.g_h[(size_t)f * p.nf + k] = wl * (ek[k] * rs - (k == it ? 1.0f : 0.f)) * inv_h;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k < p.nf) {
+                    const float d = eh[k] - dh[k];
+                    hl += d * d;
+                    p.g_h[(size_t)f * p.nf + k] = -2.0f * wl * d * inv_h;
+                    const float hp = (ph[k] - sg * dh[k]) / a, ht = h0v[k];
+                    if (k == 0 || hp > bp) { bp = hp; ip = k; }                  // first maximum, like argmax
+                    if (k == 0 || ht > bt) { bt = ht; it = k; }
+                }
+        }
         const float hit = ip == it ? 1.0f : 0.f;
         acc[0] = xl * wl; acc[1] = hl * wl; acc[2] = err; acc[3] = wm * err; acc[4] = hit; acc[5] = wm * hit;
     }
@@ -2376,7 +2417,11 @@ void pfk_compact_rows(const EdgeTile* tiles, const int* et_tile0, int n_et, cons
     hipLaunchKernelGGL(k_compact_rows, dim3(n_et), dim3(1024), 0, s, tiles, cp, dyn_cnt, rlist, ccnt);
 }
 void pfk_loss_prepare(const LossParams* p, hipStream_t s) { hipLaunchKernelGGL(k_loss_prepare, dim3(p->B), dim3(256), 0, s, *p); }
-void pfk_loss_eval(const LossParams* p, hipStream_t s) { hipLaunchKernelGGL(k_loss_eval, dim3((p->Nf + 63) / 64), dim3(64), 0, s, *p); }
+void pfk_loss_eval(const LossParams* p, int ep_coord, int ep_feat, hipStream_t s) {
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((p->Nf + 63) / 64), dim3(64), 0, s, *p); };
+    if (ep_coord) { if (ep_feat) go(k_loss_eval<true, true>); else go(k_loss_eval<true, false>); }
+    else { if (ep_feat) go(k_loss_eval<false, true>); else go(k_loss_eval<false, false>); }
+}
 void pfk_scale_loss(float* gx, int nx, const float* a, const float* a2, float* gh, int nh, const float* b, const float* b2, hipStream_t s) {
     if (nx + nh > 0) hipLaunchKernelGGL(k_scale_loss, dim3((nx + nh + 255) / 256), dim3(256), 0, s, gx, nx, a, a2, gh, nh, b, b2);
 }

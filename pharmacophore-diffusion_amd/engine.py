@@ -209,21 +209,23 @@ class PfEngine:
         return grad
 
     def train_loss_forward(self, pharm_x0, pharm_h0, t_int, eps_x, eps_h, alpha_tab, sigma_tab, n_timesteps, feat_norm,
-                           remove_com=True, weighted_loss=False, dropout=0.0, seed=0):
-        """PharmacophoreDiff.forward (pharmacodiff.py:162-243, noise parameterisation) around the bound batch as one call:
-        COM removal, noising, the train-mode dynamics, losses and metrics.  Returns a device tensor [9]: pos loss, feat
-        loss, position error, weighted position error, accuracy, weighted accuracy, then what a step derives from them --
-        total loss, total error, weighted total error."""
+                           remove_com=True, weighted_loss=False, dropout=0.0, seed=0, ep_coord=False, ep_feat=False):
+        """PharmacophoreDiff.forward (pharmacodiff.py:162-243) around the bound batch as one call: COM removal, noising, the
+        train-mode dynamics, losses and metrics.  ep_coord / ep_feat: the reference's endpoint_param_coord / endpoint_param_feat
+        (the dynamics predict the clean coordinates / the type logits instead of the noise).  Returns a device tensor [9]:
+        pos loss, feat loss, position error, weighted position error, accuracy, weighted accuracy, then what a step derives
+        from them -- total loss, total error, weighted total error."""
         x0, h0 = _f32(pharm_x0, self.device), _f32(pharm_h0, self.device)
         ex, eh = _f32(eps_x, self.device), _f32(eps_h, self.device)
         ti = t_int.to(self.device, torch.int32).contiguous()
         al, sg = _f32(alpha_tab, self.device), _f32(sigma_tab, self.device)
         out = torch.empty(9, device=self.device)
         with torch.cuda.device(self.device):
-            self._ck(self.lib.pf_train_loss_forward(self._h, _dptr(x0), _dptr(h0), _dptr(ti), _dptr(ex), _dptr(eh), _dptr(al),
-                                                    _dptr(sg), int(n_timesteps), float(feat_norm), int(bool(remove_com)),
-                                                    int(bool(weighted_loss)), float(dropout), int(seed) & 0xFFFFFFFF,
-                                                    _dptr(out), _stream_ptr()), "pf_train_loss_forward")
+            self._ck(self.lib.pf_train_loss_forward_ep(self._h, _dptr(x0), _dptr(h0), _dptr(ti), _dptr(ex), _dptr(eh), _dptr(al),
+                                                       _dptr(sg), int(n_timesteps), float(feat_norm), int(bool(remove_com)),
+                                                       int(bool(weighted_loss)), int(bool(ep_coord)), int(bool(ep_feat)),
+                                                       float(dropout), int(seed) & 0xFFFFFFFF, _dptr(out), _stream_ptr()),
+                     "pf_train_loss_forward_ep")
         return out
 
     def _grad_out(self, out):

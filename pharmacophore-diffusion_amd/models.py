@@ -162,15 +162,16 @@ class _DynamicsFn(torch.autograd.Function):
 
 
 class _LossFn(torch.autograd.Function):
-    """PharmacophoreDiff.forward's loss (pharmacodiff.py:162-243, noise parameterisation) as one autograd node: forward =
-    pf_train_loss_forward (COM removal, noising, train-mode dynamics, losses and metrics on the device), backward =
+    """PharmacophoreDiff.forward's loss (pharmacodiff.py:162-243, either parameterisation of either output) as one autograd node:
+    forward = pf_train_loss_forward_ep (COM removal, noising, train-mode dynamics, losses and metrics on the device), backward =
     pf_train_loss_backward_out with the upstream gradient of the output vector.  Output: [pos loss, feat loss, four metrics,
     total loss, total error, weighted total error]."""
 
     @staticmethod
-    def forward(ctx, mod, eng, x0, h0, t_int, eps_x, eps_h, tabs, T, feat_norm, remove_com, weighted, dropout, seed, flat_leaf):
+    def forward(ctx, mod, eng, x0, h0, t_int, eps_x, eps_h, tabs, T, feat_norm, remove_com, weighted, dropout, seed, ep_coord,
+                ep_feat, flat_leaf):
         out = eng.train_loss_forward(x0, h0, t_int, eps_x, eps_h, tabs[0], tabs[1], T, feat_norm, remove_com, weighted,
-                                     dropout=dropout, seed=seed)
+                                     dropout=dropout, seed=seed, ep_coord=ep_coord, ep_feat=ep_feat)
         mod._fwd_token += 1
         ctx.mod, ctx.eng, ctx.token = mod, eng, mod._fwd_token
         ctx.set_materialize_grads(False)
@@ -186,7 +187,7 @@ class _LossFn(torch.autograd.Function):
             raise RuntimeError("backward of a loss forward that is not the most recent training forward: the engine keeps "
                                "the activations of one forward at a time")
         if g_out is None and g_total is None:
-            return (None,) * 15
+            return (None,) * 17
         leaf = mod.__dict__.get("_flat_leaf")
         # FlatAdam.zero_grad(lazy=True) left the clear to this backward: the gradient kernels STORE every element, so writing
         # into the bound flat gradient is the clear and the accumulation at once (no fill, no add: two 3 MB launches per step);
@@ -202,8 +203,8 @@ class _LossFn(torch.autograd.Function):
         if into is not None:
             mod.__dict__["_grad_lazy_zero"] = False
             mod._last_flat_grad = into
-            return (None,) * 15
-        return (None,) * 14 + (g,)
+            return (None,) * 17
+        return (None,) * 16 + (g,)
 
 
 class PharmRecDynamicsGVP(nn.Module):
@@ -911,7 +912,7 @@ class PharmacophoreDiff(_Base):
         g = as_pocket_graph(g)
         dev = self.device
         self.__dict__["_fused_sums"] = None
-        if self.fused_loss and dev.type == "cuda" and not self.endpoint_param_feat and not self.endpoint_param_coord:
+        if self.fused_loss and dev.type == "cuda":
             return self._forward_fused(g, phase, t_int, eps)
         bidx = get_batch_idxs(g)
         bp, br = bidx['pharm'].to(dev), bidx['prot'].to(dev)
@@ -978,7 +979,7 @@ class PharmacophoreDiff(_Base):
 
     sample_lanes = None    # batches that sample() keeps in flight at once (HIP streams / handles); None: 2, or 4 for batches of <= 32
                            # graphs; 1: strictly one after the other
-    fused_loss = True      # noise-parameterised losses run as one C-ABI call (pf_train_loss_forward); False: the framework-op restatement above
+    fused_loss = True      # the losses run as one C-ABI call (pf_train_loss_forward_ep, every parameterisation); False: the framework-op restatement above
 
     def _loss_tables(self):
         """alpha(gamma(k / T)), sigma(gamma(k / T)) for k = 0..T with the reference's own fp32 expressions (pharmacodiff.py:186-190,
@@ -992,7 +993,7 @@ class PharmacophoreDiff(_Base):
         return tabs
 
     def _forward_fused(self, g, phase, t_int, eps):
-        """forward() for the noise parameterisation through pf_train_loss_forward: same draws (t_int, eps), same losses and
+        """forward() through pf_train_loss_forward_ep (endpoint_param_coord / endpoint_param_feat as configured): same draws (t_int, eps), same losses and
         metrics; the pocket's coordinates are the ones bound to the engine (bind_graph), nothing else is uploaded but the
         clean centers."""
         dev = self.device
@@ -1010,12 +1011,13 @@ class PharmacophoreDiff(_Base):
         p_drop = float(dyn.dropout_rate) if dyn.training else 0.0
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0 else 0
         args = (x0, h0, t_int, eps['x'], eps['h'], self._loss_tables(), self.n_timesteps, float(self.pharm_feat_norm_constant),
-                bool(self.remove_com), bool(self.weighted_loss), p_drop, seed)
+                bool(self.remove_com), bool(self.weighted_loss), p_drop, seed, bool(self.endpoint_param_coord),
+                bool(self.endpoint_param_feat))
         if need_grad:
             out, total = _LossFn.apply(dyn, eng, *args, dyn.__dict__["_flat_leaf"])
         else:
             out = eng.train_loss_forward(args[0], args[1], args[2], args[3], args[4], args[5][0], args[5][1], *args[6:10],
-                                         dropout=p_drop, seed=seed)
+                                         dropout=p_drop, seed=seed, ep_coord=args[12], ep_feat=args[13])
             total = out[6]
         losses = {phase + ' pos loss': out[0], phase + ' feat loss': out[1]}
         m = out.detach()
