@@ -32,6 +32,8 @@ _FLAGS = [
     ('--seed', dict(type=int, default=42, help='torch seed of the run')),
     ('--use_ref_lig_com', dict(action='store_true', help='start the centers at the ligand\'s mean position instead of the pocket\'s')),
     ('--visualize_trajectory', dict(action='store_true', help='write every denoising frame, one xyz file per sample')),
+    ('--pinned_centers', dict(type=Path, default=None, help='one xyz frame in the pharms.xyz format (elements P S F N O C): centers every sample must contain; the model places the others around them')),
+    ('--pin_what', dict(choices=['both', 'position', 'type'], default='both', help='what of the pinned centers is fixed')),
     ('--metrics', dict(action='store_true', help='print the validity of the samples against receptor pharmacophore features')),
 ]
 
@@ -48,11 +50,28 @@ def parse_arguments(argv=None):
         problems.append(f'--pharm_sizes lists {len(a.pharm_sizes)} sizes for --samples_per_pocket {a.samples_per_pocket}')
     if a.ref_ligand_file is None and not a.residue_list:
         problems.append('the pocket is undefined: pass --ref_ligand_file or --residue_list')
+    a.pinned = None
+    if a.pinned_centers is not None:
+        from pharmacoforge_amd.analysis import read_pinned_centers
+        a.pinned = read_pinned_centers(a.pinned_centers)
+        k = len(a.pinned[1])
+        small = [n for n in a.pharm_sizes if n < k]
+        if small:
+            problems.append(f'--pharm_sizes {small} below the {k} centers of --pinned_centers')
     if problems:
         raise ValueError('; '.join(problems))
     if a.ref_ligand_file is not None and a.residue_list:
         print('note: --residue_list is ignored because --ref_ligand_file defines the pocket', file=sys.stderr)
     return a
+
+
+def pinned_sizes(sizes, k):
+    """Sizes drawn uniformly may fall below the k pinned centers: those are raised to k, with a note."""
+    sizes = [int(n) for n in sizes]
+    raised = sum(n < k for n in sizes)
+    if raised:
+        print(f'note: {raised} drawn size(s) below the {k} pinned centers raised to {k}', file=sys.stderr)
+    return [max(n, k) for n in sizes]
 
 
 def locate_run(args):
@@ -101,11 +120,23 @@ def main(argv=None):
                                        graph_cutoffs=config['graph']['graph_cutoffs'],
                                        pocket_cutoff=config['dataset']['pocket_cutoff'], remove_hydrogen=True).to(device)
 
+    k_pin = 0
+    if args.pinned is not None:              # the pinned centers ride on the pocket graph: the first k centers of every copy
+        import dataclasses
+        pin_x, pin_types = args.pinned
+        k_pin = len(pin_types)
+        flag = {'both': 3, 'position': 1, 'type': 2}[args.pin_what]
+        pocket = dataclasses.replace(pocket, pharm_pin=torch.full((k_pin,), flag, dtype=torch.int32, device=device),
+                                     pharm_pin_x=pin_x.to(device),
+                                     pharm_pin_h=torch.nn.functional.one_hot(pin_types, model.n_pharm_feats).float().to(device))
+
     t0 = time.time()
     pharms = []
     while len(pharms) < args.samples_per_pocket:
         n = min(args.samples_per_pocket - len(pharms), args.max_batch_size)
         sizes = args.pharm_sizes or model.pharm_size_dist.sample_uniformly(args.samples_per_pocket)
+        if k_pin and not args.pharm_sizes:
+            sizes = pinned_sizes(sizes, k_pin)
         # like the reference (:329-333, utils/unorganized_utils.py:48) every chunk reads the size list from its start
         copies = pfa.batch(pfa.copy_graph(pocket, n, pharm_feats_per_copy=sizes))
         com = pocket.pharm_x0.repeat(n, 1) if args.use_ref_lig_com else None

@@ -90,6 +90,10 @@ typedef struct pf_step_coef {
     float ep_pred;              /* endpoint param: alpha_s*sigma2_t_given_s/sigma_t^2     (:414) */
 } pf_step_coef;
 
+/* per-step scalars of a pinned run (pf_denoise_step_pinned): the noise level of z_s, alpha(gamma(s/T)) and sigma(gamma(s/T))
+ * (pharmacodiff.py:140-146), fp32, computed by the host */
+typedef struct pf_pin_coef { float alpha_s; float sigma_s; } pf_pin_coef;
+
 const char* pf_version(void);
 const char* pf_last_error(const pf_handle* h);     /* h may be NULL: last error of pf_create */
 
@@ -195,6 +199,37 @@ int pf_sample(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, cons
               const float* dev_init_pharm_com, int32_t endpoint_param_coord, int32_t endpoint_param_feat,
               float feat_norm_constant, float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h,
               pf_stream stream);
+
+/* -- pinned centers: complete a pharmacophore around given points (replacement conditioning; no reference counterpart) ----------
+ * Every center carries a 2-bit flag: bit 0 = its position is given, bit 1 = its feature row is given (0 = free, 3 = both).
+ * dev_pin_x are positions in the CALLER's frame (the frame of the pocket coordinates bound with pf_set_pocket_batch);
+ * dev_pin_h are the raw rows the caller wants back (normally type one-hots; the run divides them by feat_norm_constant).  Rows of
+ * free centers are ignored.  A pinned run is pf_sample with one change per step: iteration i handles s = T-1-i, and after the
+ * usual p(z_s | z_t) values, for every graph g and center f of it
+ *     c_cur[g] = mean of the graph's current protein rows (before this step's shift)
+ *     D[g]     = c_init[g] - c_cur[g]        c_init = mean of the original protein coordinates; caller's frame = sampler frame + D
+ *     bit 0:  x_s[f] = alpha_s * (pin_x[f] - D[g]) + sigma_s * noise_x[f]
+ *     bit 1:  h_s[f] = alpha_s * (pin_h[f] / feat_norm_constant) + sigma_s * noise_h[f]
+ * with this step's own noise draw of the center (one rounding per operation); then the COM of ALL centers of the graph is removed
+ * from centers and protein as in pf_denoise_step.  The initial draw is not touched.  pf_sample_end (and the last trajectory
+ * frame of pf_sample_pinned) returns the given values bit for bit; earlier frames show the noised state.
+ * pf_sample_begin_pinned = pf_sample_begin + the handle's own copy of the three pin arrays (stream-ordered; the allocation is kept
+ * and reused, and grows -- with a stream synchronisation -- only when a batch has more centers).  The run is pinned until the next
+ * pf_sample_begin / pf_sample_begin_pinned / pf_set_pocket_batch: inside it pf_denoise_step returns PF_ERR_STATE, and so does
+ * pf_denoise_step_pinned outside it.  A pinned step never takes the tail or merged launches of pf_denoise_step: its dynamics call
+ * is followed by one launch of its own (k_step_build_pinned: the update above + the generic edge build; k_step_update_pinned for the
+ * width-generic family), so it costs one launch per step more than the default path, and pf_debug_kernel_family(h, n_convs)
+ * reports 0 after it.  Unpinned runs are not affected.
+ * pf_sample_pinned: pf_sample's arguments + host_pin_coef[n_steps] (entry i: s = T-1-i) + the three pin arrays. */
+int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com /*[B,3] or NULL*/, const float* dev_noise0 /*[Nf,3+pharm_nf]*/,
+                           const int32_t* dev_pin_flags /*[Nf], 0..3*/, const float* dev_pin_x /*[Nf,3]*/,
+                           const float* dev_pin_h /*[Nf,pharm_nf]*/, float feat_norm_constant, pf_stream stream);
+int pf_denoise_step_pinned(pf_handle* h, const pf_step_coef* coef, const pf_pin_coef* pin_coef, const float* dev_noise /*[Nf,3+pharm_nf]*/,
+                           int32_t endpoint_param_coord, int32_t endpoint_param_feat, pf_stream stream);
+int pf_sample_pinned(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef,
+                     const float* dev_noise, const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x,
+                     const float* dev_pin_h, int32_t endpoint_param_coord, int32_t endpoint_param_feat, float feat_norm_constant,
+                     float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream);
 
 /* -- training step: gradients of the dynamics (autograd through PharmRecDynamicsGVP.forward, ------
  *    dynamics_gvp.py:131-185, as used by PharmacophoreDiff.forward / training_step, pharmacodiff.py:162-276)

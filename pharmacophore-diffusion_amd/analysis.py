@@ -23,6 +23,31 @@ def _xyz_block(elements, coords) -> str:
     return f"{len(rows)}\n" + body
 
 
+def read_pinned_centers(filename):
+    """One xyz frame in the pharms.xyz format (the center count, then `element x y z` per center, elements P S F N O C)
+    -> (positions [k,3] fp32, type indices [k]): centers a user cut from an earlier output, to be pinned."""
+    lines = [ln.strip() for ln in Path(filename).read_text().splitlines() if ln.strip()]
+    if not lines:
+        raise ValueError(f"{filename}: empty file")
+    try:
+        k = int(lines[0])
+    except ValueError:
+        raise ValueError(f"{filename}: the first line must be the center count, got {lines[0]!r}") from None
+    if k < 1 or len(lines) != k + 1:
+        raise ValueError(f"{filename}: one frame of {k} center lines expected, found {len(lines) - 1} lines")
+    pos, types = [], []
+    for ln in lines[1:]:
+        tok = ln.split()
+        if len(tok) != 4 or tok[0] not in _XYZ_ELEMENTS:
+            raise ValueError(f"{filename}: bad center line {ln!r} (element x y z, elements {' '.join(_XYZ_ELEMENTS)})")
+        try:
+            pos.append([float(v) for v in tok[1:]])
+        except ValueError:
+            raise ValueError(f"{filename}: bad coordinates in {ln!r}") from None
+        types.append(_XYZ_ELEMENTS.index(tok[0]))
+    return torch.tensor(pos, dtype=torch.float32), torch.tensor(types, dtype=torch.int64)
+
+
 def _emit(text: str, filename):
     """Return the text, or write it when a file name is given (the reference's writers do the same)."""
     if filename is None:
@@ -48,6 +73,9 @@ class SampledPharmacophore:
         self.ph_feats_idxs = torch.argmax(g.pharm_h0, dim=1)
         self.ph_types = self._names(self.ph_feats_idxs)
         self.n_ph_centers = int(self.ph_coords.shape[0])
+        # the 2-bit pin flag of every center (bit 0: its position was given, bit 1: its type); all zero for an unpinned sample
+        pin = getattr(g, "pharm_pin", None)
+        self.pinned = torch.zeros(self.n_ph_centers, dtype=torch.int32) if pin is None else pin.to("cpu", torch.int32)
         self.pos_frames, self.feat_frames = traj_frames if traj_frames is not None else (None, None)
 
     def _names(self, type_indices) -> List[str]:

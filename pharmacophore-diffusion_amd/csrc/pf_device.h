@@ -527,6 +527,14 @@ struct StepParams {
     // features as they were before that step's update, while its update + build overwrites pharm_h), or NULL
     float* h_snap_out;
 };
+// pinned centers (pf_denoise_step_pinned): what the replacement selects in front of the update's stores read
+struct PinParams {
+    const int* flags;          // [Nf]  bit 0: position given, bit 1: feature row given
+    const float* pin_x;        // [Nf][3]   given positions, caller's frame
+    const float* pin_h;        // [Nf][nf]  given feature rows, raw (divided by feat_norm here)
+    const float* com_init;     // [B][3]    mean of the original protein coordinates (pf_sample_begin)
+    float alpha_s, sigma_s, feat_norm;
+};
 #ifdef __HIPCC__
 // The p(z_s | z_t) update of sample_p_zs_given_zt (pharmacodiff.py:397-426) for ONE value -- coordinate or feature -- and the only place
 // it is written: the generic update, the latency-optimised one (center threads / feature lanes) and the center hoist's copy all call

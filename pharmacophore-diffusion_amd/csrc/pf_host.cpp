@@ -60,6 +60,9 @@ void pfk_scale_copy(const float* src, float* dst, size_t n, float sc, hipStream_
 void pfk_segment_mean(const float4* xn, const int* ptr, int base, int B, float* out, hipStream_t s);
 void pfk_step_update(const StepParams* p, hipStream_t s);
 void pfk_step_build(const StepParams* sp, const BuildParams* bp, int fast, hipStream_t s);
+void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const BuildParams* bp, hipStream_t s);
+void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s);
+void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s);
 void pfk_bwd_head(const BwdHeadParams* p, int nblocks, hipStream_t s);
@@ -372,6 +375,12 @@ struct pf_handle {
     std::vector<char> t_node_saved;         // ... by the last pf_train_forward
     std::vector<int> t_grp;                 // per conv layer: slots per message partial-row group of the last training forward
     bool sampling = false;
+    // pinned centers (pf_sample_begin_pinned): the run in progress replaces the flagged centers every step; the handle's own copy of
+    // the caller's arrays (one allocation, kept and reused: flags [Nf], positions [Nf][3], feature rows [Nf][pharm_nf])
+    bool pinned = false;
+    void* d_pin = nullptr; size_t pin_capacity = 0;
+    int* d_pin_flags = nullptr; float *d_pin_x = nullptr, *d_pin_h = nullptr;
+    float pin_feat_norm = 1.f;
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
@@ -1765,6 +1774,7 @@ void pf_destroy(pf_handle* h) {
     if (h->d_split_tab) (void)hipFree(h->d_split_tab);
     if (h->d_l0c) (void)hipFree(h->d_l0c);
     if (h->d_ptab) (void)hipFree(h->d_ptab);
+    if (h->d_pin) (void)hipFree(h->d_pin);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
     for (int k = 0; k < 2; ++k) {
         if (h->d_tab[k]) (void)hipFree(h->d_tab[k]);
@@ -2737,7 +2747,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     if (host_onehot >= 0) { h->l0_state = host_onehot ? 1 : 2; h->l0_onehot = host_onehot == 1; }
     h->zs_version = 0; h->zs_batch_coords = false; h->coords_custom = false;
     h->have_batch = true;
-    h->sampling = false;
+    h->sampling = false; h->pinned = false;
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
 }
@@ -2864,9 +2874,20 @@ int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* 
         h->snap_cur = 0;
     }
     h->coords_custom = false;               // a rigid translate of the batch's own coordinates from here on
-    h->sampling = true;
+    h->sampling = true; h->pinned = false;
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
+}
+
+// the p(z_s | z_t) update's parameters of one denoising step (h_snap_out is the caller's)
+static StepParams step_params(const pf_handle* h, const pf_step_coef* coef, const float* dev_noise, int32_t ep_coord, int32_t ep_feat) {
+    StepParams sp{};
+    sp.B = h->B; sp.Np_tot = h->Np; sp.prot_ptr = h->d_prot_ptr; sp.pharm_ptr = h->d_pharm_ptr;
+    sp.xn = h->d_xn; sp.pharm_h = h->d_pharm_h; sp.eps_h = h->d_eps_h; sp.eps_x = h->d_eps_x; sp.noise = dev_noise;
+    sp.nf = h->cfg.pharm_nf;
+    sp.a_ts = coef->alpha_t_given_s; sp.var = coef->var_terms; sp.sigma = coef->sigma;
+    sp.ep_zt = coef->ep_zt; sp.ep_pred = coef->ep_pred; sp.ep_coord = ep_coord; sp.ep_feat = ep_feat;
+    return sp;
 }
 
 int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noise, int32_t ep_coord, int32_t ep_feat,
@@ -2875,13 +2896,9 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
     if (rc) return rc;
     if (!coef || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step: null argument");
     if (!h->sampling) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step before pf_sample_begin");
+    if (h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step inside a pinned run (pf_sample_begin_pinned): use pf_denoise_step_pinned");
     hipStream_t s = (hipStream_t)stream;
-    StepParams sp{};
-    sp.B = h->B; sp.Np_tot = h->Np; sp.prot_ptr = h->d_prot_ptr; sp.pharm_ptr = h->d_pharm_ptr;
-    sp.xn = h->d_xn; sp.pharm_h = h->d_pharm_h; sp.eps_h = h->d_eps_h; sp.eps_x = h->d_eps_x; sp.noise = dev_noise;
-    sp.nf = h->cfg.pharm_nf;
-    sp.a_ts = coef->alpha_t_given_s; sp.var = coef->var_terms; sp.sigma = coef->sigma;
-    sp.ep_zt = coef->ep_zt; sp.ep_pred = coef->ep_pred; sp.ep_coord = ep_coord; sp.ep_feat = ep_feat;
+    StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
     // center hoist: the updated features also go to the snapshot the NEXT step's hoist workgroups read (they must not race with that
     // step's update of pharm_h); only the paths through pf_stepbuild.h write it
     ++h->step_id;
@@ -2899,6 +2916,60 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
         build_done(h, share);
         h->edges_built = true;
     } else { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update(&sp, s); }
+    return PF_OK;
+}
+
+// Pinned centers: pf_sample_begin, then the handle's own copy of the caller's pin arrays (stream-ordered; the caller may free its
+// arrays once the stream has passed this call).  The run is pinned until the next pf_sample_begin / _pinned or bind
+int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
+                           const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, pf_stream stream) {
+    if (h && (!dev_pin_flags || !dev_pin_x || !dev_pin_h)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_pinned: null pin array");
+    if (h && !(feat_norm_constant > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_pinned: feat_norm_constant must be positive");
+    int rc = pf_sample_begin(h, dev_init_pharm_com, dev_noise0, stream);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nf = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
+    const size_t bytes = nf * 4 * (1 + 3 + nh);
+    if (bytes > h->pin_capacity) {
+        if (h->d_pin) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(h->d_pin)); h->d_pin = nullptr; h->pin_capacity = 0; }
+        PF_HIP(h, hipMalloc(&h->d_pin, bytes));
+        h->pin_capacity = bytes;
+    }
+    h->d_pin_flags = (int*)h->d_pin; h->d_pin_x = (float*)h->d_pin + nf; h->d_pin_h = h->d_pin_x + nf * 3;
+    if (h->Nf > 0) {
+        PF_HIP(h, hipMemcpyAsync(h->d_pin_flags, dev_pin_flags, (size_t)h->Nf * 4, hipMemcpyDeviceToDevice, s));
+        PF_HIP(h, hipMemcpyAsync(h->d_pin_x, dev_pin_x, (size_t)h->Nf * 3 * 4, hipMemcpyDeviceToDevice, s));
+        PF_HIP(h, hipMemcpyAsync(h->d_pin_h, dev_pin_h, (size_t)h->Nf * nh * 4, hipMemcpyDeviceToDevice, s));
+    }
+    h->pin_feat_norm = feat_norm_constant;
+    h->pinned = true;
+    return PF_OK;
+}
+
+// One denoising step of a pinned run.  The dynamics call is sequenced WITHOUT a step (no tail, fused-tail or merged launch); the
+// step ends with one launch of its own: the pinned update and, with the encoders on the fly, the generic edge build
+int pf_denoise_step_pinned(pf_handle* h, const pf_step_coef* coef, const pf_pin_coef* pin, const float* dev_noise, int32_t ep_coord,
+                           int32_t ep_feat, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!coef || !pin || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_pinned: null argument");
+    if (!h->sampling || !h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_pinned outside a pinned run (pf_sample_begin_pinned)");
+    hipStream_t s = (hipStream_t)stream;
+    const StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
+    PinParams q{};
+    q.flags = h->d_pin_flags; q.pin_x = h->d_pin_x; q.pin_h = h->d_pin_h; q.com_init = h->d_com_init;
+    q.alpha_s = pin->alpha_s; q.sigma_s = pin->sigma_s; q.feat_norm = h->pin_feat_norm;
+    ++h->step_id;
+    rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, nullptr);
+    if (rc) return rc;
+    if (encoders_on_the_fly(h)) {           // update + the edges of the next dynamics call in one launch
+        const bool share = share_next(h);
+        const BuildParams bp = build_params(h, share);
+        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_build_pinned(&sp, &q, &bp, s); }
+        build_done(h, share);
+        h->edges_built = true;
+    } else { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update_pinned(&sp, &q, s); }
+    h->snap_cur = -1; h->cen_valid = false; h->spec_valid = false;
     return PF_OK;
 }
 
@@ -2926,6 +2997,8 @@ int pf_sample_frame(pf_handle* h, float feat_norm_constant, float* dev_x, float*
 int pf_sample_end(pf_handle* h, float feat_norm_constant, float* dev_x0, float* dev_h0, pf_stream stream) {
     // x_0 = x_t - protein COM + initial protein COM ; h_0 = h_t * norm constant  (pharmacodiff.py:480-488)
     int rc = pf_sample_frame(h, feat_norm_constant, dev_x0, dev_h0, stream);
+    // a pinned run returns the given values bit for bit
+    if (rc == PF_OK && h->pinned) pfk_pin_restore(h->d_pin_flags, h->d_pin_x, h->d_pin_h, h->Nf, h->cfg.pharm_nf, dev_x0, dev_h0, (hipStream_t)stream);
     // the exchange's cumulative time-out count travels with the results: once the caller has waited for x_0 / h_0 it is on
     // the host too, and pf_sample_status judges THIS run without touching the device
     if (rc == PF_OK && h->d_xstat)
@@ -2955,15 +3028,20 @@ int pf_debug_xchg_fault(pf_handle* h, int32_t drop_word, int32_t poll_max) {
     return PF_OK;
 }
 
-int pf_sample(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const float* dev_noise,
-              const float* dev_init_pharm_com, int32_t ep_coord, int32_t ep_feat, float feat_norm_constant,
-              float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
+// the whole loop of pf_sample / pf_sample_pinned (host_pin_coef != NULL: a pinned run with the three pin arrays)
+static int sample_loop(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef, const float* dev_noise,
+                       const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h,
+                       int32_t ep_coord, int32_t ep_feat, float feat_norm_constant,
+                       float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (n_steps < 0 || (n_steps && !host_coef) || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_sample: bad argument");
+    const bool pinned = dev_pin_flags != nullptr;
+    if (pinned && n_steps && !host_pin_coef) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null host_pin_coef");
     const size_t row = (size_t)h->Nf * (3 + h->cfg.pharm_nf);
     const size_t fx = (size_t)h->Nf * 3, fh = (size_t)h->Nf * h->cfg.pharm_nf;
-    rc = pf_sample_begin(h, dev_init_pharm_com, dev_noise, stream);
+    rc = pinned ? pf_sample_begin_pinned(h, dev_init_pharm_com, dev_noise, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, stream)
+                : pf_sample_begin(h, dev_init_pharm_com, dev_noise, stream);
     if (rc) return rc;
     if (dev_traj_x || dev_traj_h) {
         rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x, dev_traj_h, stream);
@@ -2976,7 +3054,8 @@ int pf_sample(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, cons
         if (rc) return rc;
     }
     for (int i = 0; i < n_steps; ++i) {
-        rc = pf_denoise_step(h, host_coef + i, dev_noise + (size_t)(i + 1) * row, ep_coord, ep_feat, stream);
+        rc = pinned ? pf_denoise_step_pinned(h, host_coef + i, host_pin_coef + i, dev_noise + (size_t)(i + 1) * row, ep_coord, ep_feat, stream)
+                    : pf_denoise_step(h, host_coef + i, dev_noise + (size_t)(i + 1) * row, ep_coord, ep_feat, stream);
         if (rc) return rc;
         if (dev_traj_x || dev_traj_h) {
             rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x ? dev_traj_x + (size_t)(i + 1) * fx : nullptr,
@@ -2984,7 +3063,26 @@ int pf_sample(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, cons
             if (rc) return rc;
         }
     }
+    // the last frame of a pinned run carries the given values like x_0 / h_0 do (frame n_steps == x_0 / h_0, as in unpinned runs)
+    if (pinned) pfk_pin_restore(h->d_pin_flags, h->d_pin_x, h->d_pin_h, h->Nf, h->cfg.pharm_nf, dev_traj_x ? dev_traj_x + (size_t)n_steps * fx : nullptr,
+                                dev_traj_h ? dev_traj_h + (size_t)n_steps * fh : nullptr, (hipStream_t)stream);
     return pf_sample_end(h, feat_norm_constant, dev_x0, dev_h0, stream);
+}
+
+int pf_sample(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const float* dev_noise,
+              const float* dev_init_pharm_com, int32_t ep_coord, int32_t ep_feat, float feat_norm_constant,
+              float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
+    return sample_loop(h, n_steps, host_coef, nullptr, dev_noise, dev_init_pharm_com, nullptr, nullptr, nullptr, ep_coord, ep_feat,
+                       feat_norm_constant, dev_x0, dev_h0, dev_traj_x, dev_traj_h, stream);
+}
+
+int pf_sample_pinned(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef, const float* dev_noise,
+                     const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h,
+                     int32_t ep_coord, int32_t ep_feat, float feat_norm_constant, float* dev_x0, float* dev_h0,
+                     float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
+    if (h && (!dev_pin_flags || !dev_pin_x || !dev_pin_h)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null pin array");
+    return sample_loop(h, n_steps, host_coef, host_pin_coef, dev_noise, dev_init_pharm_com, dev_pin_flags, dev_pin_x, dev_pin_h, ep_coord, ep_feat,
+                       feat_norm_constant, dev_x0, dev_h0, dev_traj_x, dev_traj_h, stream);
 }
 
 int64_t pf_debug_get_edges(pf_handle* h, int32_t etype, int32_t* host_src, int32_t* host_dst, int64_t capacity,

@@ -1856,6 +1856,97 @@ __global__ __launch_bounds__(256) void k_step_build(const StepParams sp, const B
     build_body(bp, blockIdx.x);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Pinned centers (replacement conditioning, pf_denoise_step_pinned): step_update_body with two selects in front of its
+// stores.  A center whose position is given (flag bit 0) becomes the given position noised to this step's level,
+// z_s = alpha_s * given + sigma_s * noise, with the step's own noise draw (its posterior sample is discarded); likewise a
+// center whose feature row is given (bit 1).  Given positions are in the caller's frame: sampler frame = caller's frame - D,
+// D = mean of the original protein coordinates - mean of the graph's CURRENT protein rows (pf_sample_frame's rule), so the
+// workgroup first reduces the current mean -- wave 0, in k_segment_mean's order.  Free centers take pf_feat_update as in
+// step_update_body and the COM sum keeps its reduction order.  One rounding per operation, as in pf_feat_update.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float pf_pin_value(const float given, const float nz, const float alpha_s, const float sigma_s) {
+#pragma clang fp contract(off)
+    const float a = alpha_s * given, n = sigma_s * nz;
+    return a + n;
+}
+__device__ __forceinline__ void pinned_update_body(const StepParams& p, const PinParams& q, const int g) {
+    __shared__ float com[3];
+    __shared__ float red[4][3];
+    __shared__ float dfr[3];                            // D[g]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
+    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
+    if (wave == 0) {
+        float ax = 0.f, ay = 0.f, az = 0.f;
+        for (int i = p0 + lane; i < p1; i += 64) { const float4 x = p.xn[i]; ax += x.x; ay += x.y; az += x.z; }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o); }
+        if (lane == 0) {
+            const float n = (float)max(p1 - p0, 1);
+            dfr[0] = q.com_init[3 * g] - ax / n; dfr[1] = q.com_init[3 * g + 1] - ay / n; dfr[2] = q.com_init[3 * g + 2] - az / n;
+        }
+    }
+    __syncthreads();                                    // (the protein rows are not written before the second barrier below)
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int f = f0 + tid; f < f1; f += 256) {
+        const float4 x = p.xn[p.Np_tot + f];
+        const float* nz = p.noise + (size_t)f * (3 + p.nf);
+        const int flag = q.flags[f];
+        float m[3];
+        const float xi[3] = {x.x, x.y, x.z};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float e = p.eps_x[(size_t)f * 3 + c];
+            m[c] = (flag & 1) ? pf_pin_value(q.pin_x[(size_t)f * 3 + c] - dfr[c], nz[c], q.alpha_s, q.sigma_s)
+                              : pf_feat_update(xi[c], e, nz[c], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_coord);
+        }
+        p.xn[p.Np_tot + f] = make_float4(m[0], m[1], m[2], 0.f);
+        sx += m[0]; sy += m[1]; sz += m[2];
+        for (int k = 0; k < p.nf; ++k) {
+            const float hv = p.pharm_h[(size_t)f * p.nf + k];
+            const float e = p.eps_h[(size_t)f * p.nf + k];
+            p.pharm_h[(size_t)f * p.nf + k] = (flag & 2) ? pf_pin_value(q.pin_h[(size_t)f * p.nf + k] / q.feat_norm, nz[3 + k], q.alpha_s, q.sigma_s)
+                                                         : pf_feat_update(hv, e, nz[3 + k], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_feat);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
+    __syncthreads();
+    if (tid == 0) {
+        const float n = (float)max(f1 - f0, 1);
+        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
+    }
+    __syncthreads();
+    const float cx = com[0], cy = com[1], cz = com[2];
+    for (int f = f0 + tid; f < f1; f += 256) {
+        float4 x = p.xn[p.Np_tot + f];
+        x.x -= cx; x.y -= cy; x.z -= cz;
+        p.xn[p.Np_tot + f] = x;
+    }
+    for (int i = p0 + tid; i < p1; i += 256) {
+        float4 x = p.xn[i];
+        x.x -= cx; x.y -= cy; x.z -= cz;
+        p.xn[i] = x;
+    }
+}
+__global__ __launch_bounds__(256) void k_step_update_pinned(const StepParams p, const PinParams q) { pinned_update_body(p, q, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_step_build_pinned(const StepParams sp, const PinParams q, const BuildParams bp) {
+    pinned_update_body(sp, q, blockIdx.x);
+    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
+    build_body(bp, blockIdx.x);
+}
+// the given values back, bit for bit (pf_sample_end and the last trajectory frame of a pinned run); out_x / out_h may be NULL
+__global__ void k_pin_restore(const int* __restrict__ flags, const float* __restrict__ pin_x, const float* __restrict__ pin_h,
+                              const int n, const int nf, float* __restrict__ out_x, float* __restrict__ out_h) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int flag = flags[i];
+    if (out_x && (flag & 1)) for (int c = 0; c < 3; ++c) out_x[(size_t)i * 3 + c] = pin_x[(size_t)i * 3 + c];
+    if (out_h && (flag & 2)) for (int k = 0; k < nf; ++k) out_h[(size_t)i * nf + k] = pin_h[(size_t)i * nf + k];
+}
+
 // out[i] = xn[base+i] + (add[g] - sub[g]) ; used for the final frame of reference
 __global__ void k_export_coords(const float4* xn, const int base, const int n, const int* gid, const float* add,
                                 const float* sub, float* out) {
@@ -2015,6 +2106,18 @@ void pfk_step_build(const StepParams* sp, const BuildParams* bp, int fast, hipSt
 void pfk_step_update(const StepParams* p, hipStream_t s) {
     if (p->B == 0) return;
     hipLaunchKernelGGL(k_step_update, dim3(p->B), dim3(256), 0, s, *p);
+}
+void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const BuildParams* bp, hipStream_t s) {
+    if (sp->B == 0) return;
+    hipLaunchKernelGGL(k_step_build_pinned, dim3(sp->B), dim3(256), 0, s, *sp, *q, *bp);
+}
+void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s) {
+    if (p->B == 0) return;
+    hipLaunchKernelGGL(k_step_update_pinned, dim3(p->B), dim3(256), 0, s, *p, *q);
+}
+void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s) {
+    if (n == 0 || (!out_x && !out_h)) return;
+    hipLaunchKernelGGL(k_pin_restore, dim3((n + 255) / 256), dim3(256), 0, s, flags, pin_x, pin_h, n, nf, out_x, out_h);
 }
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s) {

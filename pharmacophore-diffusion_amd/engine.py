@@ -319,11 +319,36 @@ class PfEngine:
                                   float(coef["sigma"][s]), float(coef["ep_zt"][s]), float(coef["ep_pred"][s]))
         return arr
 
-    def sample_begin(self, noise0, init_pharm_com=None):
+    @staticmethod
+    def pin_coef_array(pin_coef: Dict[str, torch.Tensor], order):
+        """pin_coef: per-s tensors (schedule.pin_coefficients); order: iterable of s (the same as coef_array's)."""
+        order = list(order)
+        arr = (L.PfPinCoef * max(len(order), 1))()
+        for i, s in enumerate(order):
+            arr[i] = L.PfPinCoef(float(pin_coef["alpha_s"][s]), float(pin_coef["sigma_s"][s]))
+        return arr
+
+    def _pins(self, pins):
+        """(flags [Nf] 0..3, positions [Nf,3] in the caller's frame, feature rows [Nf,pharm_nf]) as device tensors."""
+        flags, px, ph = pins
+        flags = flags.detach().to(self.device, torch.int32).contiguous()
+        px, ph = _f32(px, self.device), _f32(ph, self.device)
+        if flags.shape != (self.Nf,) or px.shape != (self.Nf, 3) or ph.shape != (self.Nf, self.pharm_nf):
+            raise ValueError(f"pins must be (flags [{self.Nf}], positions [{self.Nf}, 3], feature rows [{self.Nf}, {self.pharm_nf}])")
+        return flags, px, ph
+
+    def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0):
+        """pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
+        denoise_step(..., pin_coef=...); feat_norm_constant is what the given feature rows are divided by."""
         nz = _f32(noise0, self.device)
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         self._keep = [nz, com]
         with torch.cuda.device(self.device):
+            if pins is not None:
+                fl, px, ph = self._pins(pins)
+                self._ck(self.lib.pf_sample_begin_pinned(self._h, _dptr(com), _dptr(nz), _dptr(fl), _dptr(px), _dptr(ph),
+                                                         float(feat_norm_constant), _stream_ptr()), "pf_sample_begin_pinned")
+                return
             self._ck(self.lib.pf_sample_begin(self._h, _dptr(com), _dptr(nz), _stream_ptr()), "pf_sample_begin")
 
     def prepare_timesteps(self, coef_arr, n=None):
@@ -333,11 +358,25 @@ class PfEngine:
         with torch.cuda.device(self.device):
             self._ck(self.lib.pf_prepare_timesteps(self._h, tv, n, _stream_ptr()), "pf_prepare_timesteps")
 
-    def denoise_step(self, coef_struct, noise, ep_coord=False, ep_feat=False):
+    def denoise_step(self, coef_struct, noise, ep_coord=False, ep_feat=False, pin_coef=None):
+        """pin_coef (a PfPinCoef, the entry of pin_coef_array for this step): a step of a pinned run."""
         nz = _f32(noise, self.device)
         with torch.cuda.device(self.device):
+            if pin_coef is not None:
+                self._ck(self.lib.pf_denoise_step_pinned(self._h, ctypes.byref(coef_struct), ctypes.byref(pin_coef), _dptr(nz),
+                                                         int(ep_coord), int(ep_feat), _stream_ptr()), "pf_denoise_step_pinned")
+                return
             self._ck(self.lib.pf_denoise_step(self._h, ctypes.byref(coef_struct), _dptr(nz), int(ep_coord), int(ep_feat),
                                               _stream_ptr()), "pf_denoise_step")
+
+    def sample_end(self, feat_norm_constant=1.0):
+        """x_0 / h_0 of the run in progress (pf_sample_end); a pinned run returns its given values bit for bit."""
+        x = torch.empty(self.Nf, 3, device=self.device)
+        hh = torch.empty(self.Nf, self.pharm_nf, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_sample_end(self._h, float(feat_norm_constant), _dptr(x), _dptr(hh), _stream_ptr()),
+                     "pf_sample_end")
+        return x, hh
 
     def sample_frame(self, feat_norm_constant=1.0):
         x = torch.empty(self.Nf, 3, device=self.device)
@@ -348,7 +387,8 @@ class PfEngine:
         return x, hh
 
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
-               feat_norm_constant=1.0, trajectory=False):
+               feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None):
+        """pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned."""
         nz = _f32(noise, self.device)
         assert nz.shape[0] >= n_steps + 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
@@ -358,6 +398,15 @@ class PfEngine:
         if trajectory:
             tx = torch.empty(n_steps + 1, self.Nf, 3, device=self.device)
             th = torch.empty(n_steps + 1, self.Nf, self.pharm_nf, device=self.device)
+        if pins is not None:
+            if pin_coef_arr is None:
+                raise ValueError("a pinned run needs pin_coef_arr (PfEngine.pin_coef_array)")
+            fl, px, ph = self._pins(pins)
+            with torch.cuda.device(self.device):
+                self._ck(self.lib.pf_sample_pinned(self._h, n_steps, coef_arr, pin_coef_arr, _dptr(nz), _dptr(com), _dptr(fl),
+                                                   _dptr(px), _dptr(ph), int(ep_coord), int(ep_feat), float(feat_norm_constant),
+                                                   _dptr(x0), _dptr(h0), _dptr(tx), _dptr(th), _stream_ptr()), "pf_sample_pinned")
+            return (x0, h0, tx, th) if trajectory else (x0, h0)
         with torch.cuda.device(self.device):
             self._ck(self.lib.pf_sample(self._h, n_steps, coef_arr, _dptr(nz), _dptr(com), int(ep_coord), int(ep_feat),
                                         float(feat_norm_constant), _dptr(x0), _dptr(h0), _dptr(tx), _dptr(th),

@@ -47,6 +47,10 @@ class PocketGraph:
     pocket_uid: Optional[torch.Tensor] = None  # [B] int64 (host): graphs with the same value are COPIES of one pocket (same
                                                # atoms, features, coordinates, pp edges) -- stamped by copy_graph, carried
                                                # through batch / unbatch / to; the engine lets such copies share work
+    # pinned centers (optional; all three or none): sampling completes the pharmacophore around them (pf_sample_pinned)
+    pharm_pin: Optional[torch.Tensor] = None   # [Nf] int, 2-bit flag per center: bit 0 position given, bit 1 feature row given
+    pharm_pin_x: Optional[torch.Tensor] = None # [Nf,3]  given positions, in the frame of prot_x (rows of free centers: ignored)
+    pharm_pin_h: Optional[torch.Tensor] = None # [Nf,pharm_nf]  given feature rows, raw (normally type one-hots)
 
     # -- DGL-like accessors used by the reference's drivers --------------------------------
     @property
@@ -78,7 +82,8 @@ class PocketGraph:
             return None if t is None else t.to(device)
         out = replace(self, prot_x=mv(self.prot_x), prot_h=mv(self.prot_h), pharm_x0=mv(self.pharm_x0),
                       pharm_h0=mv(self.pharm_h0), prot_ph_x=mv(self.prot_ph_x), prot_ph_h=mv(self.prot_ph_h),
-                      x_t=mv(self.x_t), h_t=mv(self.h_t))
+                      x_t=mv(self.x_t), h_t=mv(self.h_t), pharm_pin=mv(self.pharm_pin), pharm_pin_x=mv(self.pharm_pin_x),
+                      pharm_pin_h=mv(self.pharm_pin_h))
         if "_i32_cache" in self.__dict__:          # the index tensors are shared with the copy
             out.__dict__["_i32_cache"] = self.__dict__["_i32_cache"]
         return out
@@ -126,6 +131,24 @@ def get_batch_info(g: PocketGraph):
     return nodes, edges
 
 
+def _cat_pins(graphs: List[PocketGraph]):
+    """The pin fields of a batch: None when no graph has any; graphs without pins contribute free centers (flag 0)."""
+    have = [g for g in graphs if g.pharm_pin is not None]
+    if not have:
+        return None, None, None
+    like, nf = have[0], int(have[0].pharm_pin_h.shape[1])
+    flags, xs, hs = [], [], []
+    for g in graphs:
+        n = g.num_nodes("pharm")
+        if g.pharm_pin is not None:
+            flags.append(g.pharm_pin); xs.append(g.pharm_pin_x); hs.append(g.pharm_pin_h)
+        else:
+            flags.append(torch.zeros(n, dtype=like.pharm_pin.dtype, device=like.pharm_pin.device))
+            xs.append(torch.zeros(n, 3, dtype=like.pharm_pin_x.dtype, device=like.pharm_pin_x.device))
+            hs.append(torch.zeros(n, nf, dtype=like.pharm_pin_h.dtype, device=like.pharm_pin_h.device))
+    return torch.cat(flags), torch.cat(xs), torch.cat(hs)
+
+
 def batch(graphs: List[PocketGraph]) -> PocketGraph:
     """dgl.batch for PocketGraphs (collate_fn, dataset/protein_pharm_dataset.py:268-271)."""
     def cat(name):
@@ -151,7 +174,7 @@ def batch(graphs: List[PocketGraph]) -> PocketGraph:
                          for g in graphs])
     out = PocketGraph(cat("prot_x"), cat("prot_h"), _ptr(prot_counts), _ptr(pharm_counts), torch.cat(srcs), torch.cat(dsts),
                       cat("pharm_x0"), cat("pharm_h0"), cat("prot_ph_x"), cat("prot_ph_h"), _ptr(ph_counts),
-                      cat("x_t"), cat("h_t"), pp_ptr, uid)
+                      cat("x_t"), cat("h_t"), pp_ptr, uid, *_cat_pins(graphs))
     out.index_arrays_i32()          # the engine's int32 view of the index arrays, made here (collate time)
     return out
 
@@ -188,7 +211,9 @@ def unbatch(g: PocketGraph) -> List[PocketGraph]:
                                sl(g.pharm_x0, f0, f1), sl(g.pharm_h0, f0, f1),
                                sl(g.prot_ph_x, q0, q1), sl(g.prot_ph_h, q0, q1), _ptr1(q1 - q0),
                                sl(g.x_t, f0, f1), sl(g.h_t, f0, f1),
-                               pocket_uid=None if g.pocket_uid is None else g.pocket_uid[b:b + 1]))
+                               pocket_uid=None if g.pocket_uid is None else g.pocket_uid[b:b + 1],
+                               pharm_pin=sl(g.pharm_pin, f0, f1), pharm_pin_x=sl(g.pharm_pin_x, f0, f1),
+                               pharm_pin_h=sl(g.pharm_pin_h, f0, f1)))
     return out
 
 
@@ -210,8 +235,15 @@ def copy_graph(g: PocketGraph, n_copies: int, pharm_feats_per_copy=None, batched
             c.pharm_x0 = torch.zeros(n, 3, device=g.device)
             c.pharm_h0 = torch.zeros(n, nf, device=g.device)
             c.x_t = c.h_t = None
+            if g.pharm_pin is not None:          # the k given centers are the FIRST k of every copy; the rest are free
+                k = int(g.pharm_pin.shape[0])
+                if n < k:
+                    raise ValueError(f"copy {i} has {n} centers but {k} are pinned")
+                c.pharm_pin = torch.cat([g.pharm_pin, g.pharm_pin.new_zeros(n - k)])
+                c.pharm_pin_x = torch.cat([g.pharm_pin_x, g.pharm_pin_x.new_zeros(n - k, 3)])
+                c.pharm_pin_h = torch.cat([g.pharm_pin_h, g.pharm_pin_h.new_zeros(n - k, g.pharm_pin_h.shape[1])])
         else:
-            for name in ("pharm_x0", "pharm_h0", "x_t", "h_t"):
+            for name in ("pharm_x0", "pharm_h0", "x_t", "h_t", "pharm_pin", "pharm_pin_x", "pharm_pin_h"):
                 v = getattr(g, name)
                 setattr(c, name, None if v is None else v.detach().clone())
         copies.append(c)

@@ -14,6 +14,7 @@ eager / CPU fallback -- without the HIP library and a GPU the calls raise.
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from math import ceil
 from pathlib import Path
@@ -27,7 +28,8 @@ import torch.nn.functional as F
 from .analysis import SampleAnalyzer, SampledPharmacophore
 from .engine import PfEngine
 from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_graph, get_batch_idxs, unbatch
-from .schedule import PredefinedNoiseSchedule, alpha as _alpha, sigma as _sigma, sigma_and_alpha_t_given_s, step_coefficients
+from .schedule import (PredefinedNoiseSchedule, alpha as _alpha, pin_coefficients, sigma as _sigma, sigma_and_alpha_t_given_s,
+                       step_coefficients)
 
 try:  # subclass LightningModule when Lightning is importable (drop-in for train.py / load_from_checkpoint)
     import pytorch_lightning as pl
@@ -736,7 +738,11 @@ class PharmacophoreDiff(_Base):
         columns before h columns -- the reference's draw order, pharmacodiff.py:455-456, 423-424): replaying a
         reference run means passing its draws here.  When omitted all T+1 draws come from ONE torch.randn call on the
         model's device (same distribution, reproducible under torch.manual_seed; the reference's 2(T+1) separate calls
-        would cost a thousand launches per batch and cannot reproduce a CUDA generator's stream on ROCm anyway)."""
+        would cost a thousand launches per batch and cannot reproduce a CUDA generator's stream on ROCm anyway).
+
+        Pinned centers: when the graph carries ``pharm_pin`` / ``pharm_pin_x`` / ``pharm_pin_h`` with a non-zero flag, the
+        run is pf_sample_pinned -- the flagged centers are replaced by the given values at every step's noise level and
+        come back bit for bit; the free centers are placed around them."""
         return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, init_pharm_com, visualize_trajectory, noise)))
 
     def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0):
@@ -756,13 +762,18 @@ class PharmacophoreDiff(_Base):
         if getattr(self, "_coef_arr", None) is None or self._coef_arr[0] != T:      # 500-1000 ctypes structs: built once
             self._coef_arr = (T, eng.coef_array(coef, reversed(range(T))))
         arr = self._coef_arr[1]
+        pin_kw = {}
+        if g.pharm_pin is not None and bool((g.pharm_pin != 0).any()):
+            if getattr(self, "_pin_arr", None) is None or self._pin_arr[0] != T:
+                self._pin_arr = (T, eng.pin_coef_array(pin_coefficients(self.gamma.gamma, T), reversed(range(T))))
+            pin_kw = {"pins": (g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h), "pin_coef_arr": self._pin_arr[1]}
         com = None
         if init_pharm_com is not None:
             com = init_pharm_com if init_pharm_com.is_cuda else init_pharm_com.float().pin_memory().to(dev, non_blocking=True)
         res = eng.sample(arr, T, noise if noise.is_cuda else noise.float().pin_memory().to(dev, non_blocking=True),
                          init_pharm_com=com, ep_coord=self.endpoint_param_coord,
                          ep_feat=self.endpoint_param_feat, feat_norm_constant=float(self.pharm_feat_norm_constant),
-                         trajectory=visualize_trajectory)
+                         trajectory=visualize_trajectory, **pin_kw)
         # results go to pinned host memory with copies enqueued right behind the batch's kernels, and an event marks their
         # completion: whatever is enqueued afterwards (the next batch) does not delay the fetch of this one
         host = tuple(None if r is None else torch.empty(r.shape, dtype=r.dtype, pin_memory=True).copy_(r, non_blocking=True)
@@ -796,9 +807,38 @@ class PharmacophoreDiff(_Base):
             out.append(SampledPharmacophore(**kwargs))
         return out
 
+    def _with_pins(self, ref_graphs, n_pharms, pinned):
+        """sample(pinned=...): per pocket None or (x [k,3] in the pocket's frame, types [k] type indices, flags [k] or None =
+        pin both).  The k given centers become the FIRST k centers of every copy of that pocket (copy_graph pads the rest
+        with free centers); a requested size below k is refused here, before any device work."""
+        if len(pinned) != len(ref_graphs):
+            raise ValueError(f"pinned lists {len(pinned)} entries for {len(ref_graphs)} pockets")
+        out = []
+        for r, (g, pin) in enumerate(zip(ref_graphs, pinned)):
+            if pin is None:
+                out.append(g)
+                continue
+            x, types, flags = pin
+            x = torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3)
+            types = torch.as_tensor(types, dtype=torch.int64).reshape(-1)
+            k = int(x.shape[0])
+            flags = torch.full((k,), 3, dtype=torch.int32) if flags is None else torch.as_tensor(flags, dtype=torch.int32).reshape(-1)
+            if types.numel() != k or flags.numel() != k:
+                raise ValueError(f"pocket {r}: {k} pinned positions, {types.numel()} types, {flags.numel()} flags")
+            if k and (int(types.min()) < 0 or int(types.max()) >= self.n_pharm_feats or int(flags.min()) < 0 or int(flags.max()) > 3):
+                raise ValueError(f"pocket {r}: pinned types must be in 0..{self.n_pharm_feats - 1} and flags in 0..3")
+            small = [int(n) for n in n_pharms[r] if int(n) < k]
+            if small:
+                raise ValueError(f"pocket {r}: {k} centers are pinned but sizes {small} were requested")
+            dev = g.prot_x.device
+            out.append(dataclasses.replace(g, pharm_pin=flags.to(dev), pharm_pin_x=x.to(dev),
+                                           pharm_pin_h=F.one_hot(types, self.n_pharm_feats).float().to(dev)))
+        return out
+
     def sample(self, ref_graphs: List[PocketGraph], n_pharms: List[List[int]], max_batch_size: int = 32,
                init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
-               rank: int = 0, world_size: int = 1, noise=None, lanes: int = None) -> List[List[SampledPharmacophore]]:
+               rank: int = 0, world_size: int = 1, noise=None, lanes: int = None,
+               pinned=None) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -812,6 +852,10 @@ class PharmacophoreDiff(_Base):
         rank / world_size when the ranks share the seed; or a list with one such tensor per batch (replaying a
         reference run: tests/golden/sample_multi.npz).
 
+        ``pinned``: None, or one entry per pocket -- None or (x [k,3], types [k], flags [k] or None): every pharmacophore
+        of that pocket is completed around these k centers, which are its first k (flag bit 0: position given, bit 1: type
+        given; None = both).  Raises ValueError when a requested size is below k.
+
         ``lanes`` (default ``self.sample_lanes``; None = 2, or 4 when the batches hold at most 32 graphs): batches in flight at
         once, each on its own HIP stream and handle.  Four of
         the five launches of a batched step occupy part of the chip, so independent batches overlap (2 lanes: +16 % at
@@ -821,6 +865,8 @@ class PharmacophoreDiff(_Base):
         n_receptors = len(ref_graphs)
         if n_receptors == 0:
             return []
+        if pinned is not None:
+            ref_graphs = self._with_pins(ref_graphs, n_pharms, pinned)
         if init_pharm_com is None:
             init_pharm_com = torch.stack([g.prot_x.mean(dim=0) for g in ref_graphs], dim=0)
         # the requested graphs in pocket order: (pocket, number of centers); the copies themselves are made batch by batch

@@ -86,3 +86,13 @@ def step_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, to
     sig_s, sig_t = sigma(g_s), sigma(g_t)
     return {"t": t, "s": s, "alpha_t_given_s": a_ts, "var_terms": s2_ts / a_ts / sig_t, "sigma": s_ts * sig_s / sig_t,
             "ep_zt": a_ts * (sig_s ** 2) / (sig_t ** 2), "ep_pred": a_s * s2_ts / (sig_t ** 2)}
+
+
+def pin_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, torch.Tensor]:
+    """Noise level of z_s for all s at once (index = s), fp32 on the host: alpha_s = alpha(gamma(s / T)) and
+    sigma_s = sigma(gamma(s / T)) -- what a pinned run noises its given centers with (pf_denoise_step_pinned)."""
+    g = gamma_table.detach().float().cpu()
+    s_int = torch.arange(timesteps)
+    s = s_int.float() / timesteps
+    g_s = g[torch.round(s * timesteps).long()]
+    return {"alpha_s": alpha(g_s), "sigma_s": sigma(g_s)}
