@@ -103,7 +103,7 @@ def norm_no_nan(x, axis=-1, keepdims=False, eps=1e-8, sqrt=True):
 
 def rbf(D, D_min=0.0, D_max=20.0, D_count=16):
     """gvp.py:26-41."""
-    D_mu = torch.linspace(D_min, D_max, D_count).view(1, -1)
+    D_mu = torch.linspace(D_min, D_max, D_count, dtype=D.dtype).view(1, -1)
     D_sigma = (D_max - D_min) / D_count
     return torch.exp(-((D.unsqueeze(-1) - D_mu) / D_sigma) ** 2)
 
@@ -115,10 +115,10 @@ def gvp_forward(sd: Dict[str, torch.Tensor], prefix: str, feats, vectors, vec_ac
     in the reference state-dict key layout."""
     Wh = sd[prefix + "Wh"]
     Wu = sd[prefix + "Wu"]
-    Vh = torch.einsum("bvc,vh->bhc", vectors.float(), Wh)
+    Vh = torch.einsum("bvc,vh->bhc", vectors, Wh)
     Vu = torch.einsum("bhc,hu->buc", Vh, Wu)
     sh = norm_no_nan(Vh)
-    s = torch.cat((feats.float(), sh), dim=1)
+    s = torch.cat((feats, sh), dim=1)
     feats_out = F.silu(F.linear(s, sd[prefix + "to_feats_out.0.weight"], sd[prefix + "to_feats_out.0.bias"]))
     gating = F.linear(feats_out, sd[prefix + "scalar_to_vector_gates.weight"],
                       sd[prefix + "scalar_to_vector_gates.bias"]).unsqueeze(-1)
@@ -328,8 +328,8 @@ def conv_layer(sd, prefix: str, cfg: DynamicsConfig, node_feats, edges, batch: P
             # gvp.py:504-507: per-graph (edges into ntype)/(nodes of ntype) + 1
             assert edge_counts is not None
             ptr = batch.pharm_ptr if nt == "pharm" else batch.prot_ptr
-            n_nodes = (ptr[1:] - ptr[:-1]).to(torch.float32)
-            tot = sum(edge_counts[et] for et in ETYPES if CANONICAL[et][2] == nt).to(torch.float32)
+            n_nodes = (ptr[1:] - ptr[:-1]).to(h.dtype)
+            tot = sum(edge_counts[et] for et in ETYPES if CANONICAL[et][2] == nt).to(h.dtype)
             norm_value = (tot / n_nodes + 1)[bidx[nt]].unsqueeze(1)
         else:
             norm_value = cfg.message_norm
@@ -411,21 +411,25 @@ def dynamic_edge_counts(cfg: DynamicsConfig, batch: PocketBatch, edges):
 
 
 def dynamics_forward(sd, cfg: DynamicsConfig, batch: PocketBatch, prot_x, pharm_x, pharm_h, t,
-                     prefix: str = "dynamics.", return_edges: bool = False, dropout=None):
+                     prefix: str = "dynamics.", return_edges: bool = False, dropout=None, edges=None):
     """PharmRecDynamicsGVP.forward, dynamics_gvp.py:131-185.
 
     prot_x: current (COM-shifted) protein coordinates [Np,3]; pharm_x/pharm_h: x_t, h_t;
     t: [B] fp32.  Returns (eps_h [Nf,pharm_nf], eps_x [Nf,3]).  dropout: None or one
-    conv_layer mask dict per layer (training mode)."""
+    conv_layer mask dict per layer (training mode).  The arithmetic runs in the dtype of the
+    inputs (fp32, or fp64 with every tensor and weight cast: dynamics_forward64).  edges: None
+    (built here from the coordinates given) or the dynamic {etype: (src, dst)} of an earlier
+    build_dynamic_edges -- an fp64 evaluation runs on the edge set decided in fp32."""
     bidx = batch.batch_idxs()
     hp = encode(sd, prefix + "pharm_encoder.", pharm_h, t[bidx["pharm"]])
     hr = encode(sd, prefix + "prot_encoder.", batch.prot_h, t[bidx["prot"]])
     V = cfg.vector_size
     node = {
-        "pharm": (hp, pharm_x, torch.zeros(hp.shape[0], V, 3)),
-        "prot": (hr, prot_x, torch.zeros(hr.shape[0], V, 3)),
+        "pharm": (hp, pharm_x, torch.zeros(hp.shape[0], V, 3, dtype=hp.dtype)),
+        "prot": (hr, prot_x, torch.zeros(hr.shape[0], V, 3, dtype=hr.dtype)),
     }
-    edges = build_dynamic_edges(cfg, batch, prot_x, pharm_x)
+    # (the edge set is decided in fp32 whatever the dtype of the arithmetic: .float() is the identity on fp32 inputs)
+    edges = build_dynamic_edges(cfg, batch, prot_x.float(), pharm_x.float()) if edges is None else dict(edges)
     edges["pp"] = (batch.pp_src, batch.pp_dst)
     edge_counts = None
     if cfg.message_norm == 0 and cfg.message_norm != "mean":
@@ -440,6 +444,38 @@ def dynamics_forward(sd, cfg: DynamicsConfig, batch: PocketBatch, prot_x, pharm_
     if return_edges:
         return eps_h, eps_x, edges
     return eps_h, eps_x
+
+
+def batch64(batch: PocketBatch) -> PocketBatch:
+    """The same batch with its floating-point tensors in fp64."""
+    return PocketBatch(batch.prot_x.double(), batch.prot_h.double(), batch.prot_ptr, batch.pharm_ptr,
+                       batch.pp_src, batch.pp_dst)
+
+
+def state_dict64(sd):
+    return {k: v.double() for k, v in sd.items()}
+
+
+def dynamics_forward64(sd, cfg: DynamicsConfig, batch: PocketBatch, prot_x, x, h, t, dropout=None,
+                       return_edges: bool = False):
+    """dynamics_forward evaluated in fp64 on the fp32 inputs and weights given: the dynamic edges
+    are built in fp32 (the product's rule and the reference's), everything else is cast to double.
+    The yardstick an fp32 evaluation's rounding noise is measured against.  Returns doubles."""
+    edges = build_dynamic_edges(cfg, batch, prot_x.float(), x.float())
+    if dropout is not None:
+        dropout = [{nt: tuple(m.double() for m in d[nt]) for nt in d} for d in dropout]
+    eh, ex = dynamics_forward(state_dict64(sd), cfg, batch64(batch), prot_x.double(), x.double(), h.double(),
+                              t.double(), dropout=dropout, edges=edges)
+    if return_edges:
+        return eh, ex, edges
+    return eh, ex
+
+
+def sample_given_receptor64(sd, cfg, batch: PocketBatch, n_timesteps: int, precision: float, noise, **kw):
+    """sample_given_receptor in fp64 on the fp32 weights, batch and noise given.  The step coefficients stay the
+    fp32 table (the product uses the same fp32 coefficients) and promote; every step's edges are decided in fp32
+    on the rounded coordinates."""
+    return sample_given_receptor(state_dict64(sd), cfg, batch64(batch), n_timesteps, precision, noise.double(), **kw)
 
 
 # --------------------------------------------------------------------------------------

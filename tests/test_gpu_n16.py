@@ -7,8 +7,8 @@ import pytest
 import torch
 
 from oracle import pf_oracle as O
-from helpers import DYN_CASES, batch_from, load
-from test_gpu_parity import UNIT_TOL, close, engine_for, set_batch
+from helpers import DYN_CASES, batch_from, check_live, live_reference, load, with_head
+from test_gpu_parity import ATOL, RTOL, UNIT_TOL, check_eps, close, engine_for, golden_case, set_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -56,8 +56,8 @@ def test_n16_every_chain_vs_oracle(arch):
 
 @pytest.mark.parametrize("mask", [1, 2, 3, 5, 7])
 @pytest.mark.parametrize("variant", ["compact", "tile_lists", "dense"])
-@pytest.mark.parametrize("name", list(DYN_CASES))
-def test_n16_edge_kernels_on_goldens(name, variant, mask, monkeypatch):
+@pytest.mark.parametrize("name,head", with_head(DYN_CASES))
+def test_n16_edge_kernels_on_goldens(name, head, variant, mask, monkeypatch):
     """The n16 edge kernel forced onto every dynamics golden (PFDYN_N16 bit 0: conv layers >= 1, first message GVP reads
     h / v from memory; bit 1: conv layer 0, protein sources from the static hoist's type tables, centers encoded on the
     fly; bit 2: with two conv layers, conv layer 0's node update fused into the last layer's edge launch), on compact work lists, on tile lists and on the dense (unpruned) lists; the node kernels read its 16-slot
@@ -68,9 +68,8 @@ def test_n16_edge_kernels_on_goldens(name, variant, mask, monkeypatch):
         monkeypatch.setenv("PFDYN_NO_COMPACT", "1")
     if variant == "dense":
         monkeypatch.setenv("PFDYN_NO_PRUNE", "1")
-    z, cfg = load(name), DYN_CASES[name]
-    batch = batch_from(z)
-    eng = engine_for(cfg, O.make_state_dict(cfg, int(z["wseed"])))
+    z, cfg, batch, sd, live = golden_case(name, head)
+    eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
     fusable = cfg.n_convs == 2 and cfg.pf_k > 0 and variant == "compact"      # bit 2: conv layer 0's node update inside the last layer's edge launch
@@ -78,7 +77,7 @@ def test_n16_edge_kernels_on_goldens(name, variant, mask, monkeypatch):
         assert eng.kernel_family(cfg.n_convs - 1) == (17 if (mask & 4) and fusable else 16)
     if mask & 2:
         assert eng.kernel_family(0) == 16 and eng.l0_hoist() == 16
-    close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
+    check_eps(eps_h, eps_x, z, live, f"n16 mask {mask} {variant} {name}")
 
 
 def test_n16_with_pocket_sharing(monkeypatch):
@@ -110,8 +109,8 @@ def test_n16_with_pocket_sharing(monkeypatch):
     assert work["n16_shared"]["executed_edges_per_layer"][0] < 0.9 * work["n16"]["executed_edges_per_layer"][0]
 
 
-@pytest.mark.parametrize("norm", ["mean", 0, 4.0])
-def test_n16_default_policy_on_random_ragged_batches_vs_oracle(norm):
+@pytest.mark.parametrize("norm,head", with_head(["mean", 0, 4.0]))
+def test_n16_default_policy_on_random_ragged_batches_vs_oracle(norm, head):
     """The default launch policy (n16 edge kernels, fused launch) on seeded random ragged batches against the oracle: 1-12
     graphs, pockets of 3-70 atoms (some smaller than k), 1-10 centers (a single center has no ff edges: its graph's store
     item is the only writer of that center's conv-layer-0 update), both calling conventions (one common t, per-graph t),
@@ -132,8 +131,15 @@ def test_n16_default_policy_on_random_ragged_batches_vs_oracle(norm):
         x_t, h_t = spread * torch.randn(Nf, 3, generator=gen), torch.randn(Nf, 6, generator=gen)
         set_batch(eng, batch)
         for t in (torch.full((B,), 0.37), torch.rand(B, generator=gen)):
+            if head == "live":                                              # (k per call, from the oracle's eps_x on the seeded weights)
+                live = live_reference(sd, cfg, batch, batch.prot_x, x_t, h_t, t)
+                eng = engine_for(cfg, live.sd)
+                set_batch(eng, batch)
             eps_h, eps_x = eng.dynamics(x_t, h_t, t)
             assert eng.kernel_family(0) == 16 and eng.kernel_family(1) == 17, (trial, eng.kernel_family(0), eng.kernel_family(1))
+            if head == "live":
+                check_live(eps_h, eps_x, live, f"n16 default policy norm {norm} trial {trial}", RTOL, ATOL)
+                continue
             oh, ox = O.dynamics_forward(sd, cfg, batch, batch.prot_x, x_t, h_t, t)
             close(eps_h, oh); close(eps_x, ox)
 

@@ -5,12 +5,23 @@ Tolerances (fp32 arithmetic on both sides; the HIP kernels accumulate dot produc
 k-order, the oracle in BLAS order):
     single dynamics call / conv layer :  |err| <= 2e-4 + 2e-4*|ref|
     T-step stochastic trajectory       :  |err| <= 5e-3 + 5e-3*|ref|   (rounding compounds over T steps)
-Edge sets must match exactly (bit-exact integer work)."""
+Edge sets must match exactly (bit-exact integer work).
+
+Two heads.  With the seeded random weights every test here uses, eps_x -- the coordinate half of the noise prediction, the only
+path from the head's vector output into the sampler update -- is ~4e-5: below the absolute part of those tolerances, so the
+`recorded` leg of a test (the weights as make_state_dict gives them, the reference's recorded outputs) proves eps_h, the edge
+sets and the x_t / a_ts + sigma * noise part of a step, and would pass a kernel that writes eps_x = 0.  The `live` leg runs the
+same call with the last head GVP's Wu times 2**k (helpers.live_head): eps_x scales by 2**k EXACTLY, so the reference's output
+for those weights is its recorded eps_x * 2**k, of order one, and the same tolerances now bite on eps_x and on the eps_x term of
+the sampler update (test_live_head_*).  On top, the live legs hold both outputs to an error budget against an fp64 evaluation of
+the oracle (helpers.within_budget): at most 8 x the rounding noise of one fp32 evaluation of the same graph, measured in the
+test.  The measured ratios per kernel family are in DESIGN.md section 2, "error against fp64"."""
 import pytest
 import torch
 
 from oracle import pf_oracle as O
-from helpers import DYN_CASES, batch_from, edge_set, load
+from helpers import (DYN_CASES, HEADS, batch_from, check_live, edge_set, frames_within_budget, golden_live, live_head, live_reference, load,
+                     sampler_live_head, with_head, within_budget)
 
 pytestmark = pytest.mark.gpu
 
@@ -36,11 +47,23 @@ def close(a, b, rtol=RTOL, atol=ATOL):
     torch.testing.assert_close(a.cpu(), b, rtol=rtol, atol=atol)
 
 
-@pytest.mark.parametrize("name", list(DYN_CASES))
-def test_dynamics_vs_golden_and_oracle(name):
+def golden_case(name, head):
+    """(z, cfg, batch, sd, live) of a dynamics golden: the recorded weights (live = None), or the live head's with its references"""
     z, cfg = load(name), DYN_CASES[name]
-    batch = batch_from(z)
-    sd = O.make_state_dict(cfg, int(z["wseed"]))
+    live = golden_live(name) if head == "live" else None
+    return z, cfg, batch_from(z), (O.make_state_dict(cfg, int(z["wseed"])) if live is None else live.sd), live
+
+
+def check_eps(eps_h, eps_x, z, live, what):
+    if live is None:
+        close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
+    else:
+        check_live(eps_h, eps_x, live, what, RTOL, ATOL, z=z)
+
+
+@pytest.mark.parametrize("name,head", with_head(DYN_CASES))
+def test_dynamics_vs_golden_and_oracle(name, head):
+    z, cfg, batch, sd, live = golden_case(name, head)
     eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
@@ -49,9 +72,10 @@ def test_dynamics_vs_golden_and_oracle(name):
         s, d = eng.get_edges(i)
         assert edge_set(s, d) == edge_set(z[f"e_{et}_src"].long(), z[f"e_{et}_dst"].long()), et
         assert s.numel() == z[f"e_{et}_src"].numel()
-    close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
-    oh, ox = O.dynamics_forward(sd, cfg, batch, z["prot_x"], z["x_t"], z["h_t"], z["t"])
-    close(eps_h, oh); close(eps_x, ox)
+    check_eps(eps_h, eps_x, z, live, f"default {name}")
+    if live is None:
+        oh, ox = O.dynamics_forward(sd, cfg, batch, z["prot_x"], z["x_t"], z["h_t"], z["t"])
+        close(eps_h, oh); close(eps_x, ox)
 
 
 @pytest.mark.parametrize("name", list(DYN_CASES))
@@ -144,6 +168,80 @@ def test_bounded_T500_trajectory_every_frame_absolute(tail, monkeypatch):
     assert worst < 2e-2, worst
 
 
+def _live_T500(monkeypatch, form):
+    """The body of the live-head T = 500 tests.  tests/golden/traj_live_c1_T500.npz (make_golden_live.py) holds the fp64 oracle's
+    501 frames of the bounded trajectory under a head scaled by 2**k, and e32_*: the fp32 oracle's worst deviation from them.  The
+    eps_x term moves x_0 by ~1 A here, so a wrong sign, coefficient or index on it in a sampler update cannot hide; the generator
+    asserted that no edge decision of the run is within 1e-3 of flipping, so every fp32 implementation builds the same edges."""
+    fx, zb = load("traj_live_c1_T500.npz"), load("traj_c1_T500_bounded.npz")
+    cfg = O.DynamicsConfig()
+    batch = batch_from(zb)
+    T, prec = int(fx["T"]), float(fx["precision"])
+    sd, k = sampler_live_head(O.make_state_dict(cfg, int(fx["wseed"])), cfg, batch, T, prec, zb["noise"])
+    assert k == int(fx["k"]) and T == 500
+    eng = engine_for(cfg, sd)
+    set_batch(eng, batch)
+    coef = O.step_coefficients(O.gamma_table(T, prec), T)
+    res = eng.sample(eng.coef_array(coef, reversed(range(T))), T, fx["noise"], trajectory=True)
+    if form == "wide":
+        assert all(eng.kernel_family(layer) == 64 for layer in range(cfg.n_convs))
+    else:
+        assert eng.kernel_family(cfg.n_convs) == TAIL_FORMS[form]
+    assert eng.xchg_timeouts() == 0
+    eng.sample_status()
+    # the test itself: the live head decided the result (against the recorded head on the same noise, and the bounded golden)
+    assert float((res[0].cpu() - fx["x0_recorded_head"]).abs().max()) > 0.5
+    assert float((res[0].cpu() - zb["x0"]).abs().max()) > 0.5
+    frames_within_budget(res[2], fx["pos_frames"], fx["e32_pos"], f"T500 live {form} pos")
+    frames_within_budget(res[3], fx["feat_frames"], fx["e32_feat"], f"T500 live {form} feat")
+    frames_within_budget(res[0][None], fx["x0"][None], fx["e32_pos"], f"T500 live {form} x0")
+    frames_within_budget(res[1][None], fx["h0"][None], fx["e32_feat"], f"T500 live {form} h0")
+    Nf = int(batch.pharm_ptr[-1])
+    ne = eng.work()[2]
+    assert ne[0] == Nf * (Nf - 1) and ne[1] == 5 * Nf and ne[2] == ne[1]
+
+
+@pytest.mark.parametrize("tail", list(TAIL_FORMS))
+def test_live_head_T500_trajectory(tail, monkeypatch):
+    """Every form of a step's end over the whole bounded T = 500 reverse process with a live head: all 501 frames within
+    8 * max(e32, 2**-22 * max|frame|) of the fp64 oracle's (_live_T500)."""
+    set_tail(monkeypatch, tail)
+    _live_T500(monkeypatch, tail)
+
+
+def test_live_head_T500_trajectory_wide_family(monkeypatch):
+    """The same run through the width-generic family forced onto (128, 16)."""
+    monkeypatch.setenv("PFDYN_WIDE", "1")
+    _live_T500(monkeypatch, "wide")
+
+
+@pytest.mark.parametrize("name,ep", [("traj_endpoint.npz", True), ("traj_ragged.npz", False)])
+def test_live_head_T50_trajectories_vs_fp32_and_fp64_oracle(name, ep):
+    """T = 50 with a live head on the batches of the endpoint-parameterisation golden (mu = ep_zt * x_t + ep_pred * eps_x) and the
+    ragged golden: every frame against the fp32 oracle at the trajectory tolerance and inside the fp64 budget, both oracles run here."""
+    z = load(name)
+    cfg = O.DynamicsConfig()
+    batch = batch_from(z)
+    T = 50                                                           # (the batch and weights of the golden; T and the draws are this test's)
+    noise = torch.randn(T + 1, int(batch.pharm_ptr[-1]), 9, generator=torch.Generator().manual_seed(50))
+    z = {"noise": noise, "wseed": z["wseed"]}
+    sd, k = sampler_live_head(O.make_state_dict(cfg, int(z["wseed"])), cfg, batch, T, 1e-5, z["noise"])
+    eng = engine_for(cfg, sd)
+    set_batch(eng, batch)
+    coef = O.step_coefficients(O.gamma_table(T, 1e-5), T)
+    res = eng.sample(eng.coef_array(coef, reversed(range(T))), T, z["noise"], trajectory=True, ep_coord=ep, ep_feat=ep)
+    assert eng.xchg_timeouts() == 0
+    kw = dict(return_traj=True, endpoint_param_coord=ep, endpoint_param_feat=ep)
+    x32, h32, f32 = O.sample_given_receptor(sd, cfg, batch, T, 1e-5, z["noise"], **kw)
+    x64, h64, f64 = O.sample_given_receptor64(sd, cfg, batch, T, 1e-5, z["noise"], **kw)
+    p32, q32 = torch.stack([p for p, _ in f32]), torch.stack([h for _, h in f32])
+    p64, q64 = torch.stack([p for p, _ in f64]), torch.stack([h for _, h in f64])
+    close(res[0], x32, 5e-3, 5e-3); close(res[1], h32, 5e-3, 5e-3)
+    close(res[2], p32, 5e-3, 5e-3); close(res[3], q32, 5e-3, 5e-3)
+    frames_within_budget(res[2], p64, float((p32.double() - p64).abs().max()), f"T50 live {name} pos")
+    frames_within_budget(res[3], q64, float((q32.double() - q64).abs().max()), f"T50 live {name} feat")
+
+
 UNIT_TOL = 5e-5
 
 
@@ -165,6 +263,12 @@ def test_chain_units_vs_reference_modules():
     assert torch.all(vo[5] == 0) and torch.isfinite(vo).all()
     eh, ex = eng.debug_chain(3, 0, 0, z["head_s"], z["head_v"])              # noise_predictor: 4 GVPs + to_scalar_output
     close(eh, z["head_eh"], UNIT_TOL, UNIT_TOL); close(ex, z["head_ex"], UNIT_TOL, UNIT_TOL)
+    # the head's vector output is 4e-4 at most here, below 10 x UNIT_TOL: the same rows through a live head (Wu of the last GVP times
+    # 2**k; the reference module's output for it is head_ex * 2**k exactly)
+    sd_live, k = live_head(O.make_state_dict(cfg, 0), cfg, z["head_ex"])
+    assert float(z["head_ex"].abs().max()) < 10 * UNIT_TOL <= 0.5
+    eh, ex = engine_for(cfg, sd_live).debug_chain(3, 0, 0, z["head_s"], z["head_v"])
+    close(eh, z["head_eh"], UNIT_TOL, UNIT_TOL); close(ex, z["head_ex"] * 2.0 ** k, UNIT_TOL, UNIT_TOL)
 
 
 @pytest.mark.parametrize("arch", ["dev", "deep"])
@@ -199,6 +303,11 @@ def test_chain_units_every_chain_vs_oracle(arch):
     eh, ex = eng.debug_chain(3, 0, 0, s, v)
     rh, rx = O.noise_head(sd, "dynamics.noise_predictor.noise_predictor.", cfg, s, v)
     close(eh, rh, UNIT_TOL, UNIT_TOL); close(ex, rx, UNIT_TOL, UNIT_TOL)
+    sd_live, k = live_head(sd, cfg, rx)                                   # (dev: max|rx| = 1e-4, below 10 x UNIT_TOL)
+    eh, ex = engine_for(cfg, sd_live).debug_chain(3, 0, 0, s, v)
+    lh, lx = O.noise_head(sd_live, "dynamics.noise_predictor.noise_predictor.", cfg, s, v)
+    assert torch.equal(lx, rx * 2.0 ** k) and float(lx.abs().max()) >= 0.5
+    close(eh, lh, UNIT_TOL, UNIT_TOL); close(ex, lx, UNIT_TOL, UNIT_TOL)
 
 
 def test_pp_edges_as_the_reference_dataset_code_emits_them():
@@ -353,9 +462,9 @@ def test_dead_work_elimination_matches_dense_computation(name, monkeypatch):
     assert w1["executed_edges_per_layer"][0] == sum(w1["edges"])           # dense: every edge of layer 0
 
 
-@pytest.mark.parametrize("name", ["dynamics_ragged.npz", "dynamics_radius.npz", "dynamics_knnff.npz",
-                                  "dynamics_gnorm_radius.npz", "dynamics_gnorm_knn.npz"])
-def test_one_wave_per_tile_kernels(name, monkeypatch):
+@pytest.mark.parametrize("name,head", with_head(["dynamics_ragged.npz", "dynamics_radius.npz", "dynamics_knnff.npz",
+                                  "dynamics_gnorm_radius.npz", "dynamics_gnorm_knn.npz"]))
+def test_one_wave_per_tile_kernels(name, head, monkeypatch):
     """The kernels used for launches with MANY tiles (k_edge_msg / k_node_update / k_noise_head: one wave per
     32 rows, dense layers, per-source precompute) are forced here on the small golden cases, so that both
     kernel families are checked against the reference goldens."""
@@ -364,13 +473,11 @@ def test_one_wave_per_tile_kernels(name, monkeypatch):
     monkeypatch.setenv("PFDYN_COOP2_EDGE_MAX", "0")
     monkeypatch.setenv("PFDYN_COOP_NODE_MAX", "0")
     monkeypatch.setenv("PFDYN_NO_PRUNE", "1")
-    z, cfg = load(name), DYN_CASES[name]
-    batch = batch_from(z)
-    sd = O.make_state_dict(cfg, int(z["wseed"]))
+    z, cfg, batch, sd, live = golden_case(name, head)
     eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
-    close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
+    check_eps(eps_h, eps_x, z, live, f"one wave per tile {name}")
     li = int(z["conv_layer_index"])
     hp, vp, hf, vf = eng.conv_layer(li, z["prot_x"], z["x_t"], z["conv_in_h_prot"], z["conv_in_v_prot"],
                                     z["conv_in_h_pharm"], z["conv_in_v_pharm"])
@@ -378,9 +485,9 @@ def test_one_wave_per_tile_kernels(name, monkeypatch):
     close(hf, z["conv_out_h_pharm"]); close(vf, z["conv_out_v_pharm"])
 
 
-@pytest.mark.parametrize("name", ["dynamics_ragged.npz", "dynamics_radius.npz"])
+@pytest.mark.parametrize("name,head", with_head(["dynamics_ragged.npz", "dynamics_radius.npz"]))
 @pytest.mark.parametrize("dense", [False, True])
-def test_two_workgroups_per_cu_edge_kernel(name, dense, monkeypatch):
+def test_two_workgroups_per_cu_edge_kernel(name, head, dense, monkeypatch):
     """k_edge_msg_coop2 (the 4-wave kernel without weight prefetch, two workgroups per CU: launches with more tiles
     than CUs) forced on the small golden cases, on the pruned and on the dense tile lists."""
     monkeypatch.setenv("PFDYN_RG_ROWS_MAX", "0")
@@ -388,30 +495,26 @@ def test_two_workgroups_per_cu_edge_kernel(name, dense, monkeypatch):
     monkeypatch.setenv("PFDYN_COOP2_EDGE_MAX", "1000000")
     if dense:
         monkeypatch.setenv("PFDYN_NO_PRUNE", "1")
-    z, cfg = load(name), DYN_CASES[name]
-    batch = batch_from(z)
-    sd = O.make_state_dict(cfg, int(z["wseed"]))
+    z, cfg, batch, sd, live = golden_case(name, head)
     eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
-    close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
+    check_eps(eps_h, eps_x, z, live, f"two workgroups per CU {name} dense {dense}")
 
 
-@pytest.mark.parametrize("name", ["dynamics_c1.npz", "dynamics_ragged.npz", "dynamics_radius.npz", "dynamics_knnff.npz",
-                                  "dynamics_gnorm_radius.npz", "dynamics_gnorm_knn.npz"])
+@pytest.mark.parametrize("name,head", with_head(DYN_CASES))
 @pytest.mark.parametrize("dense", [False, True])
-def test_four_waves_per_tile_kernels(name, dense, monkeypatch):
+def test_four_waves_per_tile_kernels(name, head, dense, monkeypatch):
     """The 4-wave cooperative kernels (k_edge_msg_coop / k_node_update_coop / k_node_head_coop: one 32-row tile per
     workgroup; launches between the row-group and the one-wave regimes) forced on the golden cases."""
     monkeypatch.setenv("PFDYN_RG_ROWS_MAX", "0")
     if dense:
         monkeypatch.setenv("PFDYN_NO_PRUNE", "1")
-    z, cfg = load(name), DYN_CASES[name]
-    batch = batch_from(z)
-    eng = engine_for(cfg, O.make_state_dict(cfg, int(z["wseed"])))
+    z, cfg, batch, sd, live = golden_case(name, head)
+    eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
-    close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
+    check_eps(eps_h, eps_x, z, live, f"four waves per tile {name} dense {dense}")
     li = int(z["conv_layer_index"])
     hp, vp, hf, vf = eng.conv_layer(li, z["prot_x"], z["x_t"], z["conv_in_h_prot"], z["conv_in_v_prot"],
                                     z["conv_in_h_pharm"], z["conv_in_v_pharm"])
@@ -419,11 +522,10 @@ def test_four_waves_per_tile_kernels(name, dense, monkeypatch):
     close(hf, z["conv_out_h_pharm"]); close(vf, z["conv_out_v_pharm"])
 
 
-@pytest.mark.parametrize("name", ["dynamics_c1.npz", "dynamics_ragged.npz", "dynamics_radius.npz", "dynamics_knnff.npz",
-                                  "dynamics_gnorm_radius.npz", "dynamics_gnorm_knn.npz"])
+@pytest.mark.parametrize("name,head", with_head(DYN_CASES))
 @pytest.mark.parametrize("rows_per_wave", [4, 8, "4 on two waves"])
 @pytest.mark.parametrize("dense", [False, True])
-def test_row_group_kernels(name, rows_per_wave, dense, monkeypatch):
+def test_row_group_kernels(name, head, rows_per_wave, dense, monkeypatch):
     """The row-group kernels (pf_rg.hip: k_rg_edge / k_rg_node, 4 or 8 rows per wave on the 4x4x1 MFMA) forced on
     the golden cases at both widths and in the two-wave form (a 4-row group on two waves, each owning 64 of the 128
     outputs), on the pruned and on the dense tile lists, fused and separate head, plus one whole conv layer with
@@ -434,12 +536,11 @@ def test_row_group_kernels(name, rows_per_wave, dense, monkeypatch):
     if dense:
         monkeypatch.setenv("PFDYN_NO_PRUNE", "1")
         monkeypatch.setenv("PFDYN_NO_FUSE_HEAD", "1")
-    z, cfg = load(name), DYN_CASES[name]
-    batch = batch_from(z)
-    eng = engine_for(cfg, O.make_state_dict(cfg, int(z["wseed"])))
+    z, cfg, batch, sd, live = golden_case(name, head)
+    eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
-    close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
+    check_eps(eps_h, eps_x, z, live, f"row groups {rows_per_wave} {name} dense {dense}")
     li = int(z["conv_layer_index"])
     hp, vp, hf, vf = eng.conv_layer(li, z["prot_x"], z["x_t"], z["conv_in_h_prot"], z["conv_in_v_prot"],
                                     z["conv_in_h_pharm"], z["conv_in_v_pharm"])
@@ -447,17 +548,16 @@ def test_row_group_kernels(name, rows_per_wave, dense, monkeypatch):
     close(hf, z["conv_out_h_pharm"]); close(vf, z["conv_out_v_pharm"])
 
 
-@pytest.mark.parametrize("name", ["dynamics_c1.npz", "dynamics_radius.npz"])
-def test_separate_head_launch(name, monkeypatch):
+@pytest.mark.parametrize("name,head", with_head(["dynamics_c1.npz", "dynamics_radius.npz"]))
+def test_separate_head_launch(name, head, monkeypatch):
     """By default the last layer's node update and the noise head share one launch (k_node_head_coop); with
     PFDYN_NO_FUSE_HEAD=1 the head runs as its own kernel -- same goldens."""
     monkeypatch.setenv("PFDYN_NO_FUSE_HEAD", "1")
-    z, cfg = load(name), DYN_CASES[name]
-    batch = batch_from(z)
-    eng = engine_for(cfg, O.make_state_dict(cfg, int(z["wseed"])))
+    z, cfg, batch, sd, live = golden_case(name, head)
+    eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
-    close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
+    check_eps(eps_h, eps_x, z, live, f"separate head launch {name}")
 
 
 def _rand_inputs(batch, seed, pharm_nf=6, scale=3.0):
@@ -487,37 +587,57 @@ def test_large_graphs_high_degree_many_centers():
     close(eh, oh, 5e-4, 5e-4); close(ex, ox, 5e-4, 5e-4)
 
 
-@pytest.mark.parametrize("pf_k", [5, 0])
-def test_per_graph_message_norm(pf_k):
+@pytest.mark.parametrize("pf_k,head", with_head([5, 0]))
+def test_per_graph_message_norm(pf_k, head):
     """message_norm = 0: sum reducer divided by (edges into the node type)/(nodes of the type) + 1 per graph
     (gvp.py:504-507), counted by the true graph of each edge."""
     cfg = O.DynamicsConfig(message_norm=0, pf_k=pf_k)
     sd = O.make_state_dict(cfg, 4)
     batch = O.synthetic_batch([41, 42, 43], 64, [4, 6, 3], cfg)
     x_t, h_t, t = _rand_inputs(batch, 6)
-    eng = engine_for(cfg, sd)
+    live = live_reference(sd, cfg, batch, batch.prot_x, x_t, h_t, t) if head == "live" else None
+    eng = engine_for(cfg, sd if live is None else live.sd)
     set_batch(eng, batch)
     eh, ex = eng.dynamics(x_t, h_t, t)
+    if live is not None:
+        check_live(eh, ex, live, f"per-graph norm pf_k {pf_k}", RTOL, ATOL)
+        return
     oh, ox = O.dynamics_forward(sd, cfg, batch, batch.prot_x, x_t, h_t, t)
     close(eh, oh); close(ex, ox)
 
 
-def test_endpoint_parameterisation_step():
-    """sample_p_zs_given_zt with endpoint_param_coord / endpoint_param_feat (pharmacodiff.py:413-420)."""
+def _endpoint_step(head):
     cfg = O.DynamicsConfig()
     sd = O.make_state_dict(cfg, 0)
     batch = O.synthetic_batch([51, 52], 64, [4, 5], cfg)
     T = 50
     gen = torch.Generator().manual_seed(8)
     noise = torch.randn(3, int(batch.pharm_ptr[-1]), 9, generator=gen)
+    if head == "live":
+        sd, _ = sampler_live_head(sd, cfg, batch, T, 1e-5, noise)
     eng = engine_for(cfg, sd)
     set_batch(eng, batch)
     coef = O.step_coefficients(O.gamma_table(T, 1e-5), T)
     arr = eng.coef_array(coef, reversed(range(T)))
     x0, h0 = eng.sample(arr, 2, noise, ep_coord=True, ep_feat=True)
-    ox, oh = O.sample_given_receptor(sd, cfg, batch, T, 1e-5, noise, n_steps=2, endpoint_param_coord=True,
-                                     endpoint_param_feat=True)
+    kw = dict(n_steps=2, endpoint_param_coord=True, endpoint_param_feat=True)
+    ox, oh = O.sample_given_receptor(sd, cfg, batch, T, 1e-5, noise, **kw)
     close(x0, ox, 1e-3, 1e-3); close(h0, oh, 1e-3, 1e-3)
+    if head == "live":
+        x64, h64 = O.sample_given_receptor64(sd, cfg, batch, T, 1e-5, noise, **kw)
+        within_budget(x0, ox, x64, "endpoint step x0")
+        within_budget(h0, oh, h64, "endpoint step h0")
+
+
+def test_endpoint_parameterisation_step():
+    """sample_p_zs_given_zt with endpoint_param_coord / endpoint_param_feat (pharmacodiff.py:413-420)."""
+    _endpoint_step("recorded")
+
+
+def test_endpoint_parameterisation_step_live_head():
+    """The same two steps with a live head (mu = ep_zt * x_t + ep_pred * eps_x with eps_x of order one), also inside the fp64
+    error budget."""
+    _endpoint_step("live")
 
 
 @pytest.mark.parametrize("case", ["knn_pf", "knn_ff", "graph_norm", "endpoint", "near_ties", "near_ties_k16"])
@@ -661,21 +781,19 @@ HOIST_VARIANTS = {
 
 
 @pytest.mark.parametrize("variant", list(HOIST_VARIANTS))
-@pytest.mark.parametrize("name", list(DYN_CASES))
-def test_static_hoist_vs_golden_and_full_chain(name, variant, monkeypatch):
+@pytest.mark.parametrize("name,head", with_head(DYN_CASES))
+def test_static_hoist_vs_golden_and_full_chain(name, head, variant, monkeypatch):
     """Conv layer 0 with the pp messages' first GVP hoisted (trajectory constants + per-timestep type table) against
     the reference goldens, and against the same launch shapes computing the full chain (PFDYN_NO_L0_HOIST=1).  Every
     work-list form of the layer-0 edge launch is forced: mixed 4 / 8 rows per wave, tile lists, the dense layer."""
-    z, cfg = load(name), DYN_CASES[name]
-    batch = batch_from(z)
-    sd = O.make_state_dict(cfg, int(z["wseed"]))
+    z, cfg, batch, sd, live = golden_case(name, head)
     for k, v in HOIST_VARIANTS[variant].items():
         monkeypatch.setenv(k, v)
     eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
     assert eng.l0_hoist() in (4, 8, 16), "the static hoist did not run"
-    close(eps_h, z["eps_h"]); close(eps_x, z["eps_x"])
+    check_eps(eps_h, eps_x, z, live, f"static hoist {variant} {name}")
     monkeypatch.setenv("PFDYN_NO_L0_HOIST", "1")
     ref = engine_for(cfg, sd)
     set_batch(ref, batch, z["prot_x"])

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import pf_oracle as O
-from helpers import GRAD_CASES, batch_from, load
+from helpers import GRAD_CASES, batch_from, live_head, load
 
 pytestmark = pytest.mark.gpu
 
@@ -116,10 +116,10 @@ EXTRA_CASES = {
 }
 
 
-@pytest.mark.parametrize("name", sorted(EXTRA_CASES) + ["soft_features"])
+@pytest.mark.parametrize("name", sorted(EXTRA_CASES) + ["soft_features", "live_head"])
 def test_gradients_vs_oracle_more_configs(name):
-    soft = name == "soft_features"
-    cfg, seeds, n_prot, n_pharm = EXTRA_CASES["large_radius" if soft else name]
+    soft, live = name == "soft_features", name == "live_head"
+    cfg, seeds, n_prot, n_pharm = EXTRA_CASES["large_radius" if soft or live else name]
     batch = O.synthetic_batch(seeds, n_prot, n_pharm, cfg)
     if soft:
         # protein feature rows that are NOT element one-hots: the encoder backward then differentiates every atom on its own
@@ -128,7 +128,6 @@ def test_gradients_vs_oracle_more_configs(name):
         batch = O.PocketBatch(batch.prot_x, batch.prot_h + 0.25 * torch.rand(batch.prot_h.shape, generator=g0), batch.prot_ptr,
                               batch.pharm_ptr, batch.pp_src, batch.pp_dst)
     sd = O.make_state_dict(cfg, 3)
-    eng = make_engine(cfg, sd, batch)
     Np, Nf, B = int(batch.prot_ptr[-1]), int(batch.pharm_ptr[-1]), batch.batch_size
     gen = torch.Generator().manual_seed(11)
     bidx = batch.batch_idxs()
@@ -137,6 +136,11 @@ def test_gradients_vs_oracle_more_configs(name):
     x_t = 2.5 * torch.randn(Nf, 3, generator=gen)
     h_t = torch.randn(Nf, cfg.pharm_nf, generator=gen)
     t = torch.rand(B, generator=gen)
+    if live:
+        # the head's last Wu scaled by 2**k (k from the oracle's forward, eval mode): eps_x of order one, so the gradient that reaches
+        # the conv stack through the VECTOR head is no longer 1e-5 of the one through eps_h
+        sd, _ = live_head(sd, cfg, O.dynamics_forward(sd, cfg, batch, prot_x, x_t, h_t, t)[1])
+    eng = make_engine(cfg, sd, batch)
     w_h, w_x = torch.randn(Nf, cfg.pharm_nf, generator=gen), torch.randn(Nf, 3, generator=gen)
     p_drop, seed = 0.2, 99
     eps_h, eps_x = eng.train_forward(x_t, h_t, t, prot_x=prot_x, dropout=p_drop, seed=seed)

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import pf_oracle as O
-from helpers import DYN_CASES, batch_from, edge_set, load
+from helpers import DYN_CASES, batch_from, check_live, edge_set, golden_live, live_reference, load, with_head
 from test_oracle_width import WIDTH_DYN_CASES, WIDTH_TRAJ_CASES
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 SPEC_FAMILIES = {4, 8, 16, 17, 32, 128}     # pf_debug_kernel_family values of the specialised kernels
 
 RTOL, ATOL = 2e-4, 2e-4
-PAIRS = [(64, 16), (160, 16), (256, 16), (64, 32), (160, 32), (256, 32), (128, 32)]
+PAIRS = [(64, 16), (160, 16), (256, 16), (64, 32), (160, 32), (256, 32), (128, 32), (96, 16), (224, 32)]
 CASES = {   # name -> (config fields, protein atoms per graph, centers per graph)
     "knn_mean_c2": (dict(), [64, 64], [4, 3]),
     "radius_value_c3": (dict(n_convs=3, n_noise_gvps=3, message_norm=10, pf_k=0, ff_k=0), [48, 64], [3, 5]),
@@ -66,6 +66,15 @@ def check_call(cfg, batch, seed=0, wseed=3):
     torch.testing.assert_close(eps_x.cpu(), ox, rtol=RTOL, atol=ATOL)
     for layer in range(cfg.n_convs):
         assert eng.kernel_family(layer) == 64
+    # the live leg: the same call with the head scaled by 2**k (k from the oracle's fp32 eps_x above), eps_x of order one
+    live = live_reference(sd, cfg, batch, batch.prot_x, x_t, h_t, t, eps_x_ref=ox)
+    eng_live = engine_for(cfg, live.sd)
+    set_batch(eng_live, batch)
+    eps_h, eps_x = eng_live.dynamics(x_t, h_t, t)
+    for layer in range(cfg.n_convs):
+        assert eng_live.kernel_family(layer) == 64
+    check_live(eps_h, eps_x, live, f"wide {cfg.n_hidden_scalars}/{cfg.vector_size} convs {cfg.n_convs} norm {cfg.message_norm} "
+               f"pf_k {cfg.pf_k} ff_k {cfg.ff_k} atoms {int(batch.prot_ptr[-1])}", RTOL, ATOL)
     return eng
 
 
@@ -78,12 +87,17 @@ def test_dynamics_vs_oracle(S, V, case):
     check_call(cfg, batch)
 
 
-@pytest.mark.parametrize("name", list(WIDTH_DYN_CASES))
-def test_dynamics_vs_reference_fixtures(name):
-    """the reference model's own outputs at (256, 16) and (64, 32) (tests/golden/make_golden_width.py) and the oracle"""
+@pytest.mark.parametrize("name,head", with_head(WIDTH_DYN_CASES))
+def test_dynamics_vs_reference_fixtures(name, head):
+    """the reference model's own outputs at (256, 16) and (64, 32) (tests/golden/make_golden_width.py) and the oracle; with the
+    recorded head and with a live one (the recorded eps_x times 2**k is the reference's output for it)"""
     z, cfg = load(name), WIDTH_DYN_CASES[name]
     batch = batch_from(z)
     sd = O.make_state_dict(cfg, int(z["wseed"]))
+    live = None
+    if head == "live":
+        live = live_reference(sd, cfg, batch, z["prot_x"], z["x_t"], z["h_t"], z["t"], eps_x_ref=z["eps_x"])
+        sd = live.sd
     eng = engine_for(cfg, sd)
     set_batch(eng, batch, z["prot_x"])
     eps_h, eps_x = eng.dynamics(z["x_t"], z["h_t"], z["t"])
@@ -91,6 +105,11 @@ def test_dynamics_vs_reference_fixtures(name):
         s, d = eng.get_edges(i)
         assert edge_set(s, d) == edge_set(z[f"e_{et}_src"].long(), z[f"e_{et}_dst"].long()), et
         assert s.numel() == z[f"e_{et}_src"].numel()
+    for layer in range(cfg.n_convs):
+        assert eng.kernel_family(layer) == 64
+    if live is not None:
+        check_live(eps_h, eps_x, live, f"wide fixture {name}", RTOL, ATOL, z=z)
+        return
     torch.testing.assert_close(eps_h.cpu(), z["eps_h"], rtol=RTOL, atol=ATOL)
     torch.testing.assert_close(eps_x.cpu(), z["eps_x"], rtol=RTOL, atol=ATOL)
     oh, ox = O.dynamics_forward(sd, cfg, batch, z["prot_x"], z["x_t"], z["h_t"], z["t"])
@@ -128,11 +147,12 @@ def test_pocket_above_512_atoms(S, V):
     check_call(cfg, batch)
 
 
-@pytest.mark.parametrize("name", list(DYN_CASES))
-def test_forced_wide_128_16_vs_goldens_and_specialised(name, monkeypatch):
+@pytest.mark.parametrize("name,head", with_head(DYN_CASES))
+def test_forced_wide_128_16_vs_goldens_and_specialised(name, head, monkeypatch):
     z, cfg = load(name), DYN_CASES[name]
     batch = batch_from(z)
-    sd = O.make_state_dict(cfg, int(z["wseed"]))
+    live = golden_live(name) if head == "live" else None
+    sd = O.make_state_dict(cfg, int(z["wseed"])) if live is None else live.sd
     spec = engine_for(cfg, sd)
     set_batch(spec, batch, z["prot_x"])
     sh, sx = spec.dynamics(z["x_t"], z["h_t"], z["t"])
@@ -147,8 +167,11 @@ def test_forced_wide_128_16_vs_goldens_and_specialised(name, monkeypatch):
     for i, et in enumerate(O.ETYPES):
         s, d = eng.get_edges(i)
         assert edge_set(s, d) == edge_set(z[f"e_{et}_src"].long(), z[f"e_{et}_dst"].long()), et
-    torch.testing.assert_close(eps_h.cpu(), z["eps_h"], rtol=RTOL, atol=ATOL)
-    torch.testing.assert_close(eps_x.cpu(), z["eps_x"], rtol=RTOL, atol=ATOL)
+    if live is None:
+        torch.testing.assert_close(eps_h.cpu(), z["eps_h"], rtol=RTOL, atol=ATOL)
+        torch.testing.assert_close(eps_x.cpu(), z["eps_x"], rtol=RTOL, atol=ATOL)
+    else:
+        check_live(eps_h, eps_x, live, f"forced wide 128/16 {name}", RTOL, ATOL, z=z)
     torch.testing.assert_close(eps_h, sh, rtol=2e-5, atol=2e-5)
     torch.testing.assert_close(eps_x, sx, rtol=2e-5, atol=2e-5)
     # without the variable a new handle is back on the specialised kernels, with the very families of the first one
