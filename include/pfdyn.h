@@ -309,8 +309,25 @@ int pf_adam_step(pf_handle* h, float* dev_params, const float* dev_grad, float* 
 #define PF_TRAIN_BF16 1
 int pf_train_set_precision(pf_handle* h, int32_t precision);
 int pf_train_get_precision(pf_handle* h, int32_t* precision);
+/* Kernel family of the training step.  PF_TRAIN_FAMILY_TUNED -- the default -- is the gradient path specialised to
+ * n_hidden_scalars 128 / vector_size 16; at other widths every pf_train_* entry is refused.  PF_TRAIN_FAMILY_WIDE runs
+ * pf_train_forward / _backward, pf_train_loss_forward / _forward_ep and pf_train_loss_backward / _backward_out on the
+ * width-generic kernels (training form of the wide forward, gradient kernels of their own) at every width pair pf_create accepts,
+ * fp32 only: together with PF_TRAIN_BF16 it is PF_ERR_ARG, in either order.  A 128 / 16 handle takes it like any other (the A/B
+ * against the tuned gradients): its inference stays on the tuned kernels, and the packing the wide forward needs is made from
+ * the flat parameter vector on first use and whenever the weights changed.  The leg that is switched away from gives its training
+ * workspace back.  The
+ * limits of the gradient path hold for both families (at most 4 GVPs per chain, 3 update GVPs, pharm_nf <= 8, rec_nf <= 16,
+ * n_convs <= 4).  Under the wide family the dropout multipliers have n_hidden_scalars + vector_size columns per node instead of
+ * 144 (pf_debug_set_dropout_masks, pf_debug_dropout_mask).  Switching drops a kept forward: a backward then is PF_ERR_STATE.
+ * Inference is untouched by the switch. */
+#define PF_TRAIN_FAMILY_TUNED 0
+#define PF_TRAIN_FAMILY_WIDE 1
+int pf_train_set_family(pf_handle* h, int32_t family);
+int pf_train_get_family(pf_handle* h, int32_t* family);
 /* tests: make the following pf_train_forward / pf_train_backward calls on this batch use the given multipliers
- * [n_convs][2][N][144] (layout of pf_debug_dropout_mask) instead of the built-in generator; NULL restores it.  The
+ * [n_convs][2][N][144] -- under PF_TRAIN_FAMILY_WIDE [n_convs][2][N][n_hidden_scalars + vector_size] -- (layout of
+ * pf_debug_dropout_mask) instead of the built-in generator; NULL restores it.  The library cannot see the buffer's size.  The
  * buffer must stay alive until the backward call has finished. */
 int pf_debug_set_dropout_masks(pf_handle* h, const float* dev_masks);
 /* the {0, 1/(1-p)} multipliers pf_train_forward applies in conv layer `layer` (which: 0 message dropout, gvp.py:518;

@@ -570,6 +570,9 @@ struct WideGvp {           // one GVP (device pointers into the packed weights)
     pf_gcf bg;             // [vo]
     int vi, vo, si, so;
 };
+struct WidePackJob {       // one Linear W [n_out][K] at flat[src] into fragment order at out[dst] (k_wide_pack)
+    int src, n_out, K, dst;
+};
 struct WideEncParams {     // Linear(nf + 1 -> S) + SiLU + LayerNorm of every node (dynamics_gvp.py:107-117, 143-151)
     int Np, Nf, S, rec_nf, pharm_nf;
     const float* prot_h0; const float* pharm_h;
@@ -586,6 +589,9 @@ struct WideEdgeParams {    // the messages of one conv layer along the edge slot
     const WideGvp* w;                   // [4 etypes][n_gvps]
     int n_gvps, S, V;
     float rbf_mu[PF_R]; float rbf_sigma;
+    // training form (k_wide_edge<true>): the input of every chain level per edge slot, level j's rows behind j * sv_rows --
+    // scalars [S + PF_R] (level 0: [h_src, rbf]; later levels use S of them), vectors [V + 1][3] (later levels: V)
+    float* sv_s; float* sv_v; size_t sv_rows;
 };
 struct WideNodeParams {    // aggregation + node update of one conv layer (gvp.py:488-532); the last one also runs the noise head
     const NodeTile* tiles; int ntiles;
@@ -602,6 +608,14 @@ struct WideNodeParams {    // aggregation + node update of one conv layer (gvp.p
     const WideGvp* head; int n_head;
     pf_gcf w_out; pf_gcf b_out; int pharm_nf, node_base;   // to_scalar_output as stored: [pharm_nf][64]
     float* eps_h; float* eps_x;
+    // training form (k_wide_node<true>): the two GVPDropout points (gvp.py:518, 529) and what the gradient kernels read again,
+    // all per node id: the rows before either GVPLayerNorm (x1, x2: [N][S], [N][V][3]), the input of every update-chain level
+    // (level j behind j * sv_rows rows), and for the centers the input of every head level (row = node - node_base, level j
+    // behind j * hsv_rows) and the head's 64 output scalars
+    uint32_t drop_thr, seed; float drop_scale; const float* mask_override; int layer;
+    float* x1_s; float* x1_v; float* x2_s; float* x2_v;
+    float* sv_s; float* sv_v; size_t sv_rows;
+    float* hsv_s; float* hsv_v; size_t hsv_rows; float* h64;
 };
 
 struct PreParams {         // protein encoder + pp precompute (encode_pre_tile)

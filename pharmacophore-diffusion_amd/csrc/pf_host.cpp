@@ -93,8 +93,15 @@ void pfk_pp_radius(const float4* xn, const int* prot_ptr, int B, float r2, int m
                    int* src, int* dst, int pass, hipStream_t s);
 // width-generic family (pf_wide.hip)
 void pfk_wide_encode(const WideEncParams* p, hipStream_t s);
-void pfk_wide_edge(const WideEdgeParams* p, hipStream_t s);
-void pfk_wide_node(const WideNodeParams* p, hipStream_t s);
+void pfk_wide_pack(const float* flat, const WidePackJob* jobs, int n_jobs, float* out, hipStream_t s);
+void pfk_wide_edge(const WideEdgeParams* p, int train, hipStream_t s);
+void pfk_wide_node(const WideNodeParams* p, int train, hipStream_t s);
+// its gradient kernels (pf_wide_train.hip)
+void pfk_wt_chain(const WtChainParams* p, int edge, hipStream_t s);
+void pfk_wt_norm(const WtNormParams* p, hipStream_t s);
+void pfk_wt_head_out(const WtHeadOutParams* p, hipStream_t s);
+void pfk_wt_encode(const WtEncParams* p, hipStream_t s);
+void pfk_wt_reduce(const float* gpart, int gstride, float* grad, int nparams, hipStream_t s);
 }
 
 namespace {
@@ -499,6 +506,30 @@ struct pf_handle {
     const float* t_mask_override = nullptr; // pf_debug_set_dropout_masks
     bool t_have_fwd = false;
     bool t_ws_ready = false;                // d_tws is carved (and its zero rows set) for the current batch
+    // pf_train_set_family: the width-generic training leg (pf_wide.hip's training form, pf_wide_train.hip) and its workspace --
+    // like d_tws one allocation that outlives the batch, carved again for every new batch (ensure_wide_train_ws)
+    bool train_wide = false;
+    // a handle of the specialised widths carries no width-generic packing (inference stays on the tuned kernels): its wide training
+    // leg builds the WideGvp table on first use (ensure_wide_pack) -- Wh, Wu and the biases read from d_flat as stored, to_feats_out
+    // and the gate Linear packed on the device into d_wpk whenever w_version moved
+    float* d_wpk = nullptr; WidePackJob* d_wpk_jobs = nullptr; int n_wpk_jobs = 0; uint64_t wpk_version = ~0ull;
+    void* d_wtws = nullptr; size_t wtws_capacity = 0; bool wt_ready = false;
+    void* d_wtA = nullptr; size_t wtA_capacity = 0;      // the fixed-point accumulators [N][S], [N][V][3] (int64), zero between passes
+    struct WtWs {
+        float *esv_s, *esv_v;               // per conv layer [n_message_gvps][Ecap] level inputs of the message chains
+        float *x1_s, *x1_v, *x2_s, *x2_v;   // per conv layer [N] rows in front of the two GVPLayerNorms
+        float *usv_s, *usv_v;               // per conv layer [n_update_gvps][N] level inputs of the update chains
+        float *hsv_s, *hsv_v, *h64;         // [n_noise_gvps][Nf] level inputs of the head, its 64 output scalars [Nf]
+        float *G_s[2], *G_v[2];             // dL/d(layer output / input), ping-pong [N]
+        float *gch_s, *gch_v, *gres_s, *gres_v, *gagg_s, *gagg_v;   // per node: chain gradient, residual branch, aggregate
+        float *ges, *gev;                   // per edge slot: gradient between two message-chain levels
+        float *gpart, *fix;
+        float *st_h[2], *st_v[2], *msg_s, *msg_v;   // the training forward's own layer states [N] and message rows [Ecap]: the
+                                                    // inference buffers (and what the tuned kernels expect in them) stay untouched
+        long long *A_h, *A_v;
+        size_t Es;
+    } wt{};
+    WtCommon wt_common{};
     TrainCommon t_common{};
     // (looked up ~26 times per backward pass: an index over the 244 names, rebuilt when the layout is -- a linear search with string
     // compares was 50-100 us of a training step's host time, and that step is host-bound with a new batch every step)
@@ -990,7 +1021,10 @@ static void free_ws(pf_handle* h, bool keep_ws = false) {
     if (h->d_ws && !keep_ws) { (void)hipFree(h->d_ws); h->d_ws = nullptr; h->ws_capacity = 0; h->d_xchg = nullptr; h->d_lpart = nullptr; h->d_xchg2 = nullptr; h->d_cen_h = h->d_cen_p = nullptr; h->d_snap[0] = h->d_snap[1] = nullptr; h->d_pa_stamp = h->d_pa_same = nullptr; h->d_pa_cnt = h->d_pa_gstamp = nullptr; }
     if (h->d_tws && !keep_ws) { (void)hipFree(h->d_tws); h->d_tws = nullptr; h->tws_capacity = 0; }
     if (h->d_tA && !keep_ws) { (void)hipFree(h->d_tA); h->d_tA = nullptr; h->tA_capacity = 0; }
+    if (h->d_wtws && !keep_ws) { (void)hipFree(h->d_wtws); h->d_wtws = nullptr; h->wtws_capacity = 0; }
+    if (h->d_wtA && !keep_ws) { (void)hipFree(h->d_wtA); h->d_wtA = nullptr; h->wtA_capacity = 0; }
     h->t_ws_ready = false;
+    h->wt_ready = false;
     h->t_have_fwd = false;
     h->t_mask_override = nullptr;
     h->have_batch = false;
@@ -1231,13 +1265,14 @@ static void n16_refresh(pf_handle* h, hipStream_t s) {
 // One dynamics call on the width-generic family (pf_wide.hip): encoders, the edge build, per conv layer one message launch and
 // one node launch (the last one with the noise head).  The same tile lists as the specialised path: the last layer computes the
 // ff / pf messages and the centers only, the layer before it (receptive-field pruning) the active atoms and the centers.
-static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s, const float* t_scalar) {
+// train: the training form (pf_train_set_family) -- dropout, and what the gradient kernels read again goes to h->wt
+static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s, const float* t_scalar, bool train = false) {
     const pf_config& c = h->cfg;
     h->tail_done = false; h->last_tail = 0; h->last_hoist = 0;
     h->cen_valid = false; h->last_cen = false; h->spec_valid = false; h->last_spec = 0; h->e0_saved = false;
     // a pocket-group claim is verified as on the specialised path; the family then computes every graph itself
-    if (h->share_ok && h->share_check == 0) (void)share_now(h);
-    if (h->share_check == 2)
+    if (!train && h->share_ok && h->share_check == 0) (void)share_now(h);
+    if (!train && h->share_check == 2)
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: the claim made for this batch is false -- a graph differs from its representative in "
                                "coordinates or features (compared on the device); bind the batch again without the claim");
     const int S = c.n_hidden_scalars, V = c.vector_size;
@@ -1249,7 +1284,9 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         ep.w[nt] = h->d_w + h->enc_w[nt]; ep.b[nt] = h->d_w + h->enc_b[nt];
         ep.ln_w[nt] = h->d_w + h->enc_lw[nt]; ep.ln_b[nt] = h->d_w + h->enc_lb[nt];
     }
-    ep.h_out = h->d_h[0];
+    float* const* st_h = train ? h->wt.st_h : h->d_h;
+    float* const* st_v = train ? h->wt.st_v : h->d_v;
+    ep.h_out = st_h[0];
     { ProfScope ps(h, pf_handle::K_ENCODE, s); pfk_wide_encode(&ep, s); }
     if (!h->edges_built) {
         const BuildParams bp = build_params(h, false);
@@ -1264,11 +1301,17 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         e.tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
         e.ntiles = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles);
         e.dyn_cnt = h->d_dyn_cnt; e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
-        e.h = h->d_h[cur]; e.v = h->d_v[cur]; e.layer0 = l == 0;
-        e.msg_s = h->d_msg_s; e.msg_v = h->d_msg_v;
+        e.h = st_h[cur]; e.v = st_v[cur]; e.layer0 = l == 0;
+        e.msg_s = train ? h->wt.msg_s : h->d_msg_s; e.msg_v = train ? h->wt.msg_v : h->d_msg_v;
         e.w = h->d_wgvp + h->msg_base(l, 0); e.n_gvps = c.n_message_gvps; e.S = S; e.V = V;
         e.rbf_sigma = rbf_params(c, e.rbf_mu, nullptr);
-        { ProfScope ps(h, pf_handle::K_EDGE, s); pfk_wide_edge(&e, s); }
+        const size_t N_ = (size_t)h->N, V3_ = (size_t)3 * V;
+        if (train) {
+            const size_t nm = (size_t)c.n_message_gvps;
+            e.sv_rows = h->wt.Es;
+            e.sv_s = h->wt.esv_s + (size_t)l * nm * h->wt.Es * (S + PF_R); e.sv_v = h->wt.esv_v + (size_t)l * nm * h->wt.Es * 3 * (V + 1);
+        }
+        { ProfScope ps(h, pf_handle::K_EDGE, s); pfk_wide_edge(&e, train ? 1 : 0, s); }
         WideNodeParams n{};
         n.tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
         n.ntiles = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
@@ -1276,7 +1319,7 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N; n.pp_slot = pruned ? 2 : 1;
         n.msg_s = e.msg_s; n.msg_v = e.msg_v;
         n.h_in = e.h; n.v_in = e.v; n.layer0 = e.layer0;
-        n.h_out = h->d_h[cur ^ 1]; n.v_out = h->d_v[cur ^ 1];
+        n.h_out = st_h[cur ^ 1]; n.v_out = st_v[cur ^ 1];
         n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
         for (int nt = 0; nt < 2; ++nt) {
             const size_t* lo = &h->ln_off[(size_t)(l * 2 + nt) * 4];
@@ -1285,12 +1328,26 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
             n.upd[nt] = h->d_wgvp + h->upd_base(l, nt);
         }
         n.n_upd = c.n_update_gvps; n.S = S; n.V = V;
+        if (train) {
+            const WtCommon& wc = h->wt_common;
+            n.drop_thr = wc.drop_thr; n.seed = wc.seed; n.drop_scale = wc.drop_scale; n.mask_override = wc.mask_override; n.layer = l;
+            n.x1_s = h->wt.x1_s + l * N_ * S; n.x1_v = h->wt.x1_v + l * N_ * V3_;
+            n.x2_s = h->wt.x2_s + l * N_ * S; n.x2_v = h->wt.x2_v + l * N_ * V3_;
+            n.sv_rows = N_;
+            n.sv_s = h->wt.usv_s + l * c.n_update_gvps * N_ * S; n.sv_v = h->wt.usv_v + l * c.n_update_gvps * N_ * V3_;
+            n.hsv_rows = (size_t)std::max(h->Nf, 1); n.hsv_s = h->wt.hsv_s; n.hsv_v = h->wt.hsv_v; n.h64 = h->wt.h64;
+        }
         if (last) {             // the last layer's node tiles are the centers: the noise head follows in the same launch
             n.head = h->d_wgvp + h->head_base(); n.n_head = c.n_noise_gvps;
-            n.w_out = h->d_w + h->wide_out_w; n.b_out = h->d_w + h->wide_out_b; n.pharm_nf = c.pharm_nf; n.node_base = h->Np;
+            if (h->wide) { n.w_out = h->d_w + h->wide_out_w; n.b_out = h->d_w + h->wide_out_b; }
+            else {              // (a handle of the specialised widths on the wide training leg: to_scalar_output as the flat vector stores it)
+                n.w_out = h->d_flat + h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.weight");
+                n.b_out = h->d_flat + h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.bias");
+            }
+            n.pharm_nf = c.pharm_nf; n.node_base = h->Np;
             n.eps_h = eps_h; n.eps_x = eps_x;
-            ProfScope ps(h, pf_handle::K_HEAD, s); pfk_wide_node(&n, s);
-        } else { ProfScope ps(h, pf_handle::K_NODE, s); pfk_wide_node(&n, s); }
+            ProfScope ps(h, pf_handle::K_HEAD, s); pfk_wide_node(&n, train ? 1 : 0, s);
+        } else { ProfScope ps(h, pf_handle::K_NODE, s); pfk_wide_node(&n, train ? 1 : 0, s); }
         cur ^= 1;
     }
     h->edges_built = false;                 // whoever moves the coordinates next rebuilds
@@ -1664,7 +1721,7 @@ static void head_launch(DynCall& dc) {
 // apply dropout in the node update.  step: this call is the dynamics call of a denoising step (pf_denoise_step) -- when the tail launch or the
 // merged launch applies, the step's sampler update and edge build run behind the noise head in the same launch and h->tail_done tells the caller
 static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s, const float* t_scalar = nullptr, bool train = false, const StepParams* step = nullptr) {
-    if (h->wide && !train) return run_dynamics_wide(h, eps_h, eps_x, s, t_scalar);
+    if (train ? h->train_wide : h->wide) return run_dynamics_wide(h, eps_h, eps_x, s, t_scalar, train);
     const pf_config& c = h->cfg;
     h->tail_done = false; h->last_tail = 0;
     DynCall dc{};
@@ -1763,6 +1820,8 @@ void pf_destroy(pf_handle* h) {
     if (h->d_w) (void)hipFree(h->d_w);
     if (h->d_gvp) (void)hipFree(h->d_gvp);
     if (h->d_wgvp) (void)hipFree(h->d_wgvp);
+    if (h->d_wpk) (void)hipFree(h->d_wpk);
+    if (h->d_wpk_jobs) (void)hipFree(h->d_wpk_jobs);
     if (h->d_flat) (void)hipFree(h->d_flat);
     if (h->d_wpack) (void)hipFree(h->d_wpack);
     if (h->d_xstat) (void)hipFree(h->d_xstat);
@@ -2117,6 +2176,8 @@ int pf_commit_weights(pf_handle* h) {
         PF_HIP(h, hipMemcpy(h->d_gvp, h->h_gvp.data(), h->h_gvp.size() * sizeof(GvpW), hipMemcpyHostToDevice));
     }
     if (h->d_wgvp) { (void)hipFree(h->d_wgvp); h->d_wgvp = nullptr; }
+    if (h->d_wpk) { (void)hipFree(h->d_wpk); h->d_wpk = nullptr; }          // (ensure_wide_pack builds both again on the new d_flat)
+    if (h->d_wpk_jobs) { (void)hipFree(h->d_wpk_jobs); h->d_wpk_jobs = nullptr; }
     if (h->wide) {
         std::vector<WideGvp> tab;
         size_t i = 0;
@@ -3204,6 +3265,7 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
         fresh = true;
     }
     char* cur = reinterpret_cast<char*>(h->d_tws);
+    h->wt_ready = false;                         // (the loss buffers t_l* below are shared with the width-generic leg's carve)
     h->t_H.assign(L + 1, nullptr); h->t_V.assign(L + 1, nullptr); h->t_msg_s.assign(L, nullptr); h->t_msg_v.assign(L, nullptr);
     for (int l = 0; l <= L; ++l) { h->t_H[l] = carve<float>(cur, (size_t)N * PF_S); h->t_V[l] = carve<float>(cur, (size_t)N * 48); }
     for (int l = 0; l < L; ++l) { h->t_msg_s[l] = carve<float>(cur, E1 * PF_S); h->t_msg_v[l] = carve<float>(cur, E1 * 48); }
@@ -3272,6 +3334,139 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
     return PF_OK;
 }
 
+
+// workspace of the width-generic training leg (pf_train_set_family): what k_wide_edge<true> / k_wide_node<true> keep, the gradient
+// buffers of pf_wide_train.hip, the gradient copies and the loss buffers
+static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
+    if (h->d_wtws && h->wt_ready) return PF_OK;
+    const pf_config& c = h->cfg;
+    if (c.n_message_gvps > PFT_MAX_CHAIN || c.n_noise_gvps > PFT_MAX_CHAIN || c.n_update_gvps > 3)
+        PF_FAIL(h, PF_ERR_ARG, "training supports at most %d message / noise GVPs and 3 update GVPs per chain", PFT_MAX_CHAIN);
+    if (c.pharm_nf > 8 || c.rec_nf + 1 > 17 || c.pharm_nf + 1 > 17)
+        PF_FAIL(h, PF_ERR_ARG, "training supports pharm_nf <= 8 and rec_nf <= 16");
+    const size_t L = c.n_convs, N = h->N, S = c.n_hidden_scalars, V3 = (size_t)3 * c.vector_size;
+    const size_t ES = S + PF_R, EV = V3 + 3, Es = (size_t)std::max<int64_t>(h->Ecap, 1), Nf1 = (size_t)std::max(h->Nf, 1);
+    const size_t nm = c.n_message_gvps, nu = c.n_update_gvps, nh = c.n_noise_gvps;
+    const size_t gstride = (h->nparams + 63) / 64 * 64;
+    pf_handle::WtWs& w = h->wt;
+    // two passes over one list: sizes, then pointers
+    for (int pass = 0; pass < 2; ++pass) {
+        char* const base = pass ? reinterpret_cast<char*>(h->d_wtws) : reinterpret_cast<char*>(uintptr_t(256));
+        char* cur = base;
+        auto take = [&](float*& dst, size_t n) { float* q = carve<float>(cur, n); if (pass) dst = q; };
+        take(w.esv_s, L * nm * Es * ES); take(w.esv_v, L * nm * Es * EV);
+        take(w.x1_s, L * N * S); take(w.x1_v, L * N * V3); take(w.x2_s, L * N * S); take(w.x2_v, L * N * V3);
+        take(w.usv_s, L * nu * N * S); take(w.usv_v, L * nu * N * V3);
+        take(w.hsv_s, nh * Nf1 * S); take(w.hsv_v, nh * Nf1 * V3); take(w.h64, Nf1 * 64);
+        for (int a = 0; a < 2; ++a) { take(w.G_s[a], N * S); take(w.G_v[a], N * V3); }
+        take(w.gch_s, N * S); take(w.gch_v, N * V3); take(w.gres_s, N * S); take(w.gres_v, N * V3);
+        take(w.gagg_s, N * S); take(w.gagg_v, N * V3);
+        take(w.ges, Es * ES); take(w.gev, Es * EV);
+        take(w.gpart, (size_t)PFWT_NB * gstride); take(w.fix, 64);
+        for (int a = 0; a < 2; ++a) { take(w.st_h[a], N * S); take(w.st_v[a], N * V3); }
+        take(w.msg_s, Es * S); take(w.msg_v, Es * V3);
+        take(h->t_lx0c, (size_t)h->Nf * 3); take(h->t_lag, (size_t)h->B); take(h->t_lsg, (size_t)h->B); take(h->t_lcom2, (size_t)h->B * 3);
+        take(h->t_lgx, (size_t)h->Nf * 3); take(h->t_lgh, (size_t)h->Nf * c.pharm_nf); take(h->t_lout, 64);
+        if (pass == 0) {
+            const size_t bytes = (size_t)(cur - base);
+            if (h->wtws_capacity < bytes + 4096) {
+                PF_HIP(h, hipDeviceSynchronize());
+                if (h->d_wtws) { (void)hipFree(h->d_wtws); h->d_wtws = nullptr; h->wtws_capacity = 0; }
+                const size_t want = bytes + bytes / 8 + 4096;
+                PF_HIP(h, hipMalloc(&h->d_wtws, want));
+                h->wtws_capacity = want;
+            }
+        }
+    }
+    w.Es = Es;
+    const size_t a_bytes = (N * S * 8 + 255) / 256 * 256, need_a = a_bytes + N * V3 * 8;
+    if (h->wtA_capacity < need_a) {
+        PF_HIP(h, hipDeviceSynchronize());
+        if (h->d_wtA) { (void)hipFree(h->d_wtA); h->d_wtA = nullptr; h->wtA_capacity = 0; }
+        PF_HIP(h, hipMalloc(&h->d_wtA, need_a + need_a / 8));
+        h->wtA_capacity = need_a + need_a / 8;
+    }
+    PF_HIP(h, hipMemsetAsync(h->d_wtA, 0, h->wtA_capacity, s));
+    w.A_h = reinterpret_cast<long long*>(h->d_wtA);
+    w.A_v = reinterpret_cast<long long*>(reinterpret_cast<char*>(h->d_wtA) + a_bytes);
+    h->t_ws_ready = false;                       // (the specialised leg's carve owns the same loss-buffer fields)
+    h->wt_ready = true;
+    return PF_OK;
+}
+
+
+// The WideGvp table of a handle that was not created on the width-generic family (the specialised widths without PFDYN_WIDE), for
+// its wide training leg: built on first use after a commit, its two packed Linears per GVP refreshed from d_flat when the weights
+// moved.  A handle of the family itself has the table from pf_commit_weights and the gather map keeps it fresh.
+static int ensure_wide_pack(pf_handle* h, hipStream_t s) {
+    if (h->wide) return PF_OK;
+    const pf_config& c = h->cfg;
+    if (!h->d_wgvp) {
+        std::vector<WideGvp> tab;
+        std::vector<WidePackJob> jobs;
+        std::vector<size_t> dst;            // per GVP: wm, wg
+        size_t total = 0;
+        auto frag = [](int n_out, int K) { return (size_t)((n_out + 15) / 16) * ((K + 3) / 4) * 64; };
+        std::vector<GvpSpec> specs;
+        for (int l = 0; l < c.n_convs; ++l)
+            for (int et = 0; et < 4; ++et)
+                for (int j = 0; j < c.n_message_gvps; ++j) specs.push_back(msg_spec(c, l, et, j));
+        for (int l = 0; l < c.n_convs; ++l)
+            for (int nt = 0; nt < 2; ++nt)
+                for (int j = 0; j < c.n_update_gvps; ++j) specs.push_back(upd_spec(c, l, nt, j));
+        for (int k = 0; k < c.n_noise_gvps; ++k) specs.push_back(head_spec(c, k));
+        for (const GvpSpec& g : specs) {
+            const int H = std::max(g.vi, g.vo);
+            const int o_wm = (int)h->flat_offset(g.prefix + "to_feats_out.0.weight"), o_wg = (int)h->flat_offset(g.prefix + "scalar_to_vector_gates.weight");
+            jobs.push_back({o_wm, g.so, g.si + H, (int)total}); dst.push_back(total); total += frag(g.so, g.si + H);
+            jobs.push_back({o_wg, g.vo, g.so, (int)total}); dst.push_back(total); total += frag(g.vo, g.so);
+        }
+        if (total >= (size_t)1 << 31) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_family: the model is too large for the width-generic packing");
+        if (h->d_wpk) { (void)hipFree(h->d_wpk); h->d_wpk = nullptr; }
+        if (h->d_wpk_jobs) { (void)hipFree(h->d_wpk_jobs); h->d_wpk_jobs = nullptr; }
+        PF_HIP(h, hipMalloc((void**)&h->d_wpk, std::max<size_t>(total, 1) * sizeof(float)));
+        PF_HIP(h, hipMalloc((void**)&h->d_wpk_jobs, jobs.size() * sizeof(WidePackJob)));
+        PF_HIP(h, hipMemcpy(h->d_wpk_jobs, jobs.data(), jobs.size() * sizeof(WidePackJob), hipMemcpyHostToDevice));
+        h->n_wpk_jobs = (int)jobs.size();
+        for (size_t i = 0; i < specs.size(); ++i) {
+            const GvpSpec& g = specs[i];
+            WideGvp w;
+            w.wh = h->d_flat + h->flat_offset(g.prefix + "Wh"); w.wu = h->d_flat + h->flat_offset(g.prefix + "Wu");
+            w.wm = h->d_wpk + dst[2 * i]; w.bm = h->d_flat + h->flat_offset(g.prefix + "to_feats_out.0.bias");
+            w.wg = h->d_wpk + dst[2 * i + 1]; w.bg = h->d_flat + h->flat_offset(g.prefix + "scalar_to_vector_gates.bias");
+            w.vi = g.vi; w.vo = g.vo; w.si = g.si; w.so = g.so;
+            tab.push_back(w);
+        }
+        PF_HIP(h, hipMalloc((void**)&h->d_wgvp, tab.size() * sizeof(WideGvp)));
+        PF_HIP(h, hipMemcpy(h->d_wgvp, tab.data(), tab.size() * sizeof(WideGvp), hipMemcpyHostToDevice));
+        h->wpk_version = ~0ull;
+    }
+    if (h->wpk_version != h->w_version) {
+        pfk_wide_pack(h->d_flat, h->d_wpk_jobs, h->n_wpk_jobs, h->d_wpk, s);
+        h->wpk_version = h->w_version;
+    }
+    return PF_OK;
+}
+
+// dropout and parameter view of one training step of the width-generic leg
+static void wide_train_common(pf_handle* h, float dropout_p, uint32_t seed) {
+    WtCommon& wc = h->wt_common;
+    wc = WtCommon{};
+    wc.W = h->d_flat; wc.gpart = h->wt.gpart; wc.gstride = (int)((h->nparams + 63) / 64 * 64);
+    wc.S = h->cfg.n_hidden_scalars; wc.V = h->cfg.vector_size; wc.N = h->N;
+    wc.drop_thr = dropout_p > 0.f ? (uint32_t)std::min(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
+    wc.drop_scale = 1.0f / (1.0f - dropout_p);
+    wc.seed = seed;
+    wc.mask_override = h->t_mask_override;
+}
+
+// every training entry: the specialised gradient path serves 128 / 16 only; other widths need the width-generic leg
+#define PF_TRAIN_WIDTH_GUARD(h, who)                                                                                              \
+    if ((h) && !(h)->spec && !(h)->train_wide)                                                                                    \
+        PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "     \
+                               "pf_train_set_family(PF_TRAIN_FAMILY_WIDE) selects the width-generic training leg)", who,          \
+                (h)->cfg.n_hidden_scalars, (h)->cfg.vector_size)
+
 int pf_param_count(pf_handle* h, int64_t* n_params, int32_t* n_tensors) {
     int rc = check_ready(h, false);
     if (rc) return rc;
@@ -3332,15 +3527,19 @@ int pf_get_flat_params(pf_handle* h, float* dev_flat, pf_stream stream) {
 
 int pf_train_forward(pf_handle* h, const float* dev_prot_x, const float* dev_pharm_x, const float* dev_pharm_h,
                      const float* dev_t, float dropout_p, uint32_t seed, float* dev_eps_h, float* dev_eps_x, pf_stream stream) {
-    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
-                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
+    PF_TRAIN_WIDTH_GUARD(h, __func__);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_pharm_x || !dev_pharm_h || !dev_t || !dev_eps_h || !dev_eps_x) PF_FAIL(h, PF_ERR_ARG, "pf_train_forward: null argument");
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) PF_FAIL(h, PF_ERR_ARG, "pf_train_forward: dropout must be in [0, 1)");
     hipStream_t s = (hipStream_t)stream;
-    rc = ensure_train_ws(h, s);
+    rc = h->train_wide ? ensure_wide_train_ws(h, s) : ensure_train_ws(h, s);
     if (rc) return rc;
+    if (h->train_wide) {
+        rc = ensure_wide_pack(h, s);
+        if (rc) return rc;
+        wide_train_common(h, dropout_p, seed);
+    }
     h->t_common = TrainCommon{};
     h->t_common.W = h->d_flat; h->t_common.gpart = h->t_gpart; h->t_common.nparams = (int)h->nparams;
     h->t_common.gstride = (int)((h->nparams + 63) / 64 * 64);
@@ -3364,8 +3563,7 @@ static int loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* de
                         const float* dev_eps_x, const float* dev_eps_h, const float* dev_alpha, const float* dev_sigma,
                         int32_t n_timesteps, float feat_norm, int32_t remove_com, int32_t weighted_loss, int32_t endpoint_param_coord,
                         int32_t endpoint_param_feat, float dropout_p, uint32_t seed, float* dev_out, pf_stream stream, const char* who) {
-    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
-                                "the width-generic family is inference only)", who, h->cfg.n_hidden_scalars, h->cfg.vector_size);
+    PF_TRAIN_WIDTH_GUARD(h, who);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_pharm_x0 || !dev_pharm_h0 || !dev_t_int || !dev_eps_x || !dev_eps_h || !dev_alpha || !dev_sigma || !dev_out)
@@ -3374,8 +3572,13 @@ static int loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* de
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) PF_FAIL(h, PF_ERR_ARG, "%s: dropout must be in [0, 1)", who);
     if (h->Nf == 0) PF_FAIL(h, PF_ERR_ARG, "%s: the batch has no pharmacophore centers (the losses are means over them)", who);
     hipStream_t s = (hipStream_t)stream;
-    rc = ensure_train_ws(h, s);
+    rc = h->train_wide ? ensure_wide_train_ws(h, s) : ensure_train_ws(h, s);
     if (rc) return rc;
+    if (h->train_wide) {
+        rc = ensure_wide_pack(h, s);
+        if (rc) return rc;
+        wide_train_common(h, dropout_p, seed);
+    }
     h->t_have_loss = false;
     h->t_common = TrainCommon{};
     h->t_common.W = h->d_flat; h->t_common.gpart = h->t_gpart; h->t_common.nparams = (int)h->nparams;
@@ -3444,28 +3647,145 @@ static int loss_backward(pf_handle* h, const float* g_pos, const float* g_pos2, 
 }
 
 int pf_train_loss_backward(pf_handle* h, const float* dev_g_pos, const float* dev_g_feat, float* dev_grad, pf_stream stream) {
-    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
-                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
+    PF_TRAIN_WIDTH_GUARD(h, __func__);
     return loss_backward(h, dev_g_pos, nullptr, dev_g_feat, nullptr, dev_grad, stream, "pf_train_loss_backward");
 }
 
 int pf_train_loss_backward_out(pf_handle* h, const float* dev_g_out, float* dev_grad, pf_stream stream) {
-    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
-                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
+    PF_TRAIN_WIDTH_GUARD(h, __func__);
     if (h && !dev_g_out) PF_FAIL(h, PF_ERR_ARG, "pf_train_loss_backward_out: null argument");
     // upstream gradients of the nine outputs: [0] and [1] of the two losses, [6] of their sum; the metrics carry none
     return loss_backward(h, dev_g_out, dev_g_out ? dev_g_out + 6 : nullptr, dev_g_out ? dev_g_out + 1 : nullptr,
                          dev_g_out ? dev_g_out + 6 : nullptr, dev_grad, stream, "pf_train_loss_backward_out");
 }
 
+
+// the backward pass of the width-generic leg: the reverse of run_dynamics_wide (pf_wide_train.hip lists the launches)
+static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* g_eps_x, float* dev_grad, hipStream_t s) {
+    const pf_config& c = h->cfg;
+    const int L = c.n_convs, N = h->N, S = c.n_hidden_scalars, V = c.vector_size, V3 = 3 * V, ES = S + PF_R, EV = V3 + 3;
+    pf_handle::WtWs& w = h->wt;
+    const WtCommon wc = h->wt_common;
+    if (h->has_pend_scale) {
+        const ScaleArgs& a = h->pend_scale;
+        pfk_scale_loss(a.gx, a.nx, a.a, a.a2, a.gh, a.nh, a.b, a.b2, s);
+        h->has_pend_scale = false;
+    }
+    PF_HIP(h, hipMemsetAsync(w.gpart, 0, (size_t)PFWT_NB * wc.gstride * sizeof(float), s));
+    PF_HIP(h, hipMemsetAsync(h->d_wtA, 0, h->wtA_capacity, s));
+    pfk_fix_scale(g_eps_h, h->Nf * c.pharm_nf, g_eps_x, h->Nf * 3, w.fix, s);
+    int a = 0;
+    {   // head: to_scalar_output, then its levels; the first level's input gradient is dL/d(last layer output) of the centers
+        WtHeadOutParams p{};
+        p.c = wc; p.Np = h->Np; p.Nf = h->Nf; p.pharm_nf = c.pharm_nf; p.g_eps_h = g_eps_h; p.g_eps_x = g_eps_x; p.h64 = w.h64;
+        p.o_Wout = (int)h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.weight");
+        p.o_bout = (int)h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.bias");
+        p.up_s = w.gch_s; p.up_v = w.gch_v; p.up_ls = S; p.up_lv = V3;
+        pfk_wt_head_out(&p, s);
+        const size_t Nf1 = (size_t)std::max(h->Nf, 1);
+        for (int lv = c.n_noise_gvps - 1; lv >= 0; --lv) {
+            WtChainParams q{};
+            q.c = wc; q.ntiles = h->d_node_tiles; q.n_tiles = h->n_node_tiles_last; q.dyn_cnt = h->d_dyn_cnt; q.row_ids = h->d_act_ids;
+            q.g = h->d_gvpt + h->head_base(); q.g_stride = 0; q.level = lv; q.last = lv == c.n_noise_gvps - 1;
+            q.sv_s = w.hsv_s + (size_t)lv * Nf1 * S; q.sv_v = w.hsv_v + (size_t)lv * Nf1 * V3; q.sv_ls = S; q.sv_lv = V3; q.sv_base = h->Np;
+            q.up_s = w.gch_s; q.up_v = w.gch_v; q.up_ls = S; q.up_lv = V3;
+            q.out_s = lv == 0 ? w.G_s[a] : w.gch_s; q.out_v = lv == 0 ? w.G_v[a] : w.gch_v; q.out_ls = S; q.out_lv = V3;
+            ProfScope ps(h, pf_handle::K_BWD_HEAD, s);
+            pfk_wt_chain(&q, 0, s);
+        }
+    }
+    for (int l = L - 1; l >= 0; --l) {
+        // the tile lists of the forward (run_dynamics_wide): rows it did not compute have no backward
+        const bool last = l == L - 1, pruned = l == prune_layer(h);
+        const NodeTile* ntiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
+        const int n_nt = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
+        const EdgeTile* etiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
+        const int n_et = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles);
+        const size_t lN = (size_t)l * N;
+        PF_HIP(h, hipMemsetAsync(w.G_s[a ^ 1], 0, (size_t)N * S * sizeof(float), s));
+        PF_HIP(h, hipMemsetAsync(w.G_v[a ^ 1], 0, (size_t)N * V3 * sizeof(float), s));
+        WtNormParams n{};
+        n.c = wc; n.tiles = ntiles; n.n_tiles = n_nt; n.dyn_cnt = h->d_dyn_cnt; n.row_ids = h->d_act_ids;
+        n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
+        auto ln_offsets = [&](const char* which) {
+            for (int nt = 0; nt < 2; ++nt) {
+                const std::string pre = conv_prefix(l) + which + "." + kNtKey[nt] + ".feat_norm.";
+                n.o_lw[nt] = (int)h->flat_offset(pre + "weight"); n.o_lb[nt] = (int)h->flat_offset(pre + "bias");
+            }
+        };
+        {   // LayerNorm 2 and the residual dropout
+            ln_offsets("update_layer_norms");
+            n.dyA_s = w.G_s[a]; n.dyA_v = w.G_v[a]; n.dyB_s = nullptr; n.dyB_v = nullptr;
+            n.x_s = w.x2_s + lN * S; n.x_v = w.x2_v + lN * V3;
+            n.out1_s = w.gres_s; n.out1_v = w.gres_v; n.out2_s = w.gch_s; n.out2_v = w.gch_v;
+            n.stream = l * 2 + 1; n.use_norm = 0;
+            ProfScope ps(h, pf_handle::K_BWD_NODE, s);
+            pfk_wt_norm(&n, s);
+        }
+        for (int lv = c.n_update_gvps - 1; lv >= 0; --lv) {
+            WtChainParams q{};
+            q.c = wc; q.ntiles = ntiles; q.n_tiles = n_nt; q.dyn_cnt = h->d_dyn_cnt; q.row_ids = h->d_act_ids;
+            q.g = h->d_gvpt + h->upd_base(l, 0); q.g_stride = c.n_update_gvps; q.level = lv; q.last = lv == c.n_update_gvps - 1;
+            q.sv_s = w.usv_s + ((size_t)l * c.n_update_gvps + lv) * N * S; q.sv_v = w.usv_v + ((size_t)l * c.n_update_gvps + lv) * N * V3;
+            q.sv_ls = S; q.sv_lv = V3; q.sv_base = 0;
+            q.up_s = w.gch_s; q.up_v = w.gch_v; q.up_ls = S; q.up_lv = V3;
+            q.out_s = w.gch_s; q.out_v = w.gch_v; q.out_ls = S; q.out_lv = V3;
+            ProfScope ps(h, pf_handle::K_BWD_NODE, s);
+            pfk_wt_chain(&q, 0, s);
+        }
+        {   // the residual joins, LayerNorm 1, the message dropout and norm: dL/d(layer input) (residual path), dL/d(aggregate)
+            ln_offsets("message_layer_norms");
+            n.dyA_s = w.gch_s; n.dyA_v = w.gch_v; n.dyB_s = w.gres_s; n.dyB_v = w.gres_v;
+            n.x_s = w.x1_s + lN * S; n.x_v = w.x1_v + lN * V3;
+            n.out1_s = w.G_s[a ^ 1]; n.out1_v = w.G_v[a ^ 1]; n.out2_s = w.gagg_s; n.out2_v = w.gagg_v;
+            n.stream = l * 2; n.use_norm = 1;
+            ProfScope ps(h, pf_handle::K_BWD_NODE, s);
+            pfk_wt_norm(&n, s);
+        }
+        for (int lv = c.n_message_gvps - 1; lv >= 0; --lv) {
+            WtChainParams q{};
+            q.c = wc; q.etiles = etiles; q.n_tiles = n_et; q.dyn_cnt = h->d_dyn_cnt;
+            q.g = h->d_gvpt + h->msg_base(l, 0); q.g_stride = c.n_message_gvps; q.level = lv; q.last = lv == c.n_message_gvps - 1;
+            q.sv_s = w.esv_s + ((size_t)l * c.n_message_gvps + lv) * w.Es * ES; q.sv_v = w.esv_v + ((size_t)l * c.n_message_gvps + lv) * w.Es * EV;
+            q.sv_ls = ES; q.sv_lv = EV; q.sv_base = 0;
+            q.up_s = w.ges; q.up_v = w.gev; q.up_ls = ES; q.up_lv = EV;
+            q.out_s = w.ges; q.out_v = w.gev; q.out_ls = ES; q.out_lv = EV;
+            q.esrc = h->d_esrc; q.edst = h->d_edst; q.gagg_s = w.gagg_s; q.gagg_v = w.gagg_v;
+            q.in_cnt = h->d_in_cnt; q.pp_slot = pruned ? 2 : 1; q.norm_mode = c.message_norm_mode; q.l0 = l == 0;
+            q.A_h = w.A_h; q.A_v = w.A_v; q.fix = w.fix;
+            ProfScope ps(h, pf_handle::K_BWD_EDGE_LEVEL, s);
+            pfk_wt_chain(&q, 1, s);
+        }
+        pfk_fix_apply(w.A_h, w.G_s[a ^ 1], (size_t)N * S, w.fix, s);
+        if (l != 0) pfk_fix_apply(w.A_v, w.G_v[a ^ 1], (size_t)N * V3, w.fix, s);      // conv layer 0 has no vector input
+        a ^= 1;
+    }
+    {
+        WtEncParams p{};
+        p.c = wc; p.Np = h->Np; p.Nf = h->Nf; p.rec_nf = c.rec_nf; p.pharm_nf = c.pharm_nf;
+        p.prot_h0 = h->d_prot_h0; p.pharm_h = h->d_pharm_h; p.t = h->d_t; p.gid = h->d_gid;
+        for (int nt = 0; nt < 2; ++nt) {
+            const std::string pre = std::string("dynamics.") + kNtKey[nt] + "_encoder.";
+            p.o_w[nt] = (int)h->flat_offset(pre + "0.weight"); p.o_b[nt] = (int)h->flat_offset(pre + "0.bias");
+            p.o_lw[nt] = (int)h->flat_offset(pre + "2.weight"); p.o_lb[nt] = (int)h->flat_offset(pre + "2.bias");
+        }
+        p.G_h = w.G_s[a];
+        pfk_wt_encode(&p, s);
+    }
+    pfk_wt_reduce(w.gpart, wc.gstride, dev_grad, (int)h->nparams, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
 int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, pf_stream stream) {
-    if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: training is specialised to n_hidden_scalars 128 / vector_size 16 (this handle: %d / %d; "
-                                "the width-generic family is inference only)", __func__, h->cfg.n_hidden_scalars, h->cfg.vector_size);
+    PF_TRAIN_WIDTH_GUARD(h, __func__);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!h->t_have_fwd) PF_FAIL(h, PF_ERR_STATE, "pf_train_backward: no pf_train_forward on this batch");
     if (!dev_g_eps_h || !dev_g_eps_x || !dev_grad) PF_FAIL(h, PF_ERR_ARG, "pf_train_backward: null argument");
     if (h->n_tseg < 0) PF_FAIL(h, PF_ERR_ARG, "pf_train_backward: the gradient path supports n_convs <= 4");
+    if (h->train_wide) return wide_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, (hipStream_t)stream);
     hipStream_t s = (hipStream_t)stream;
     const pf_config& c = h->cfg;
     const int L = c.n_convs, N = h->N, nb = h->t_nblk;
@@ -3690,6 +4010,7 @@ int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g
 int pf_train_set_precision(pf_handle* h, int32_t precision) {
     if (!h) return PF_ERR_ARG;
     if (precision != PF_TRAIN_F32 && precision != PF_TRAIN_BF16) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_precision: precision must be PF_TRAIN_F32 or PF_TRAIN_BF16");
+    if (precision == PF_TRAIN_BF16 && h->train_wide) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_precision: the width-generic training leg (pf_train_set_family) is fp32 only");
     h->train_bf16 = precision == PF_TRAIN_BF16;
     h->t_have_fwd = false;                       // a forward of the other precision is not this backward's
     h->t_have_loss = false;
@@ -3699,6 +4020,36 @@ int pf_train_set_precision(pf_handle* h, int32_t precision) {
 int pf_train_get_precision(pf_handle* h, int32_t* precision) {
     if (!h || !precision) return PF_ERR_ARG;
     *precision = h->train_bf16 ? PF_TRAIN_BF16 : PF_TRAIN_F32;
+    return PF_OK;
+}
+
+int pf_train_set_family(pf_handle* h, int32_t family) {
+    if (!h) return PF_ERR_ARG;
+    if (family != PF_TRAIN_FAMILY_TUNED && family != PF_TRAIN_FAMILY_WIDE) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_family: family must be PF_TRAIN_FAMILY_TUNED or PF_TRAIN_FAMILY_WIDE");
+    if (family == PF_TRAIN_FAMILY_WIDE) {
+        if (h->train_bf16) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_family: the width-generic training leg is fp32 only (pf_train_set_precision: PF_TRAIN_BF16 is set)");
+    }
+    if (h->train_wide != (family == PF_TRAIN_FAMILY_WIDE)) {
+        // the leg that is left gives its workspace back (several GB at a training batch); it is allocated again on that leg's next use
+        (void)hipDeviceSynchronize();
+        if (family == PF_TRAIN_FAMILY_WIDE) {
+            if (h->d_tws) { (void)hipFree(h->d_tws); h->d_tws = nullptr; h->tws_capacity = 0; }
+            if (h->d_tA) { (void)hipFree(h->d_tA); h->d_tA = nullptr; h->tA_capacity = 0; }
+        } else {
+            if (h->d_wtws) { (void)hipFree(h->d_wtws); h->d_wtws = nullptr; h->wtws_capacity = 0; }
+            if (h->d_wtA) { (void)hipFree(h->d_wtA); h->d_wtA = nullptr; h->wtA_capacity = 0; }
+        }
+    }
+    h->train_wide = family == PF_TRAIN_FAMILY_WIDE;
+    h->t_have_fwd = false;                       // a forward of the other family is not this backward's
+    h->t_have_loss = false;
+    h->t_ws_ready = false; h->wt_ready = false;  // (the two legs' workspaces share the loss-buffer fields: whoever runs next carves again)
+    return PF_OK;
+}
+
+int pf_train_get_family(pf_handle* h, int32_t* family) {
+    if (!h || !family) return PF_ERR_ARG;
+    *family = h->train_wide ? PF_TRAIN_FAMILY_WIDE : PF_TRAIN_FAMILY_TUNED;
     return PF_OK;
 }
 
@@ -3716,7 +4067,9 @@ int pf_debug_dropout_mask(pf_handle* h, int32_t layer, int32_t which, float drop
     tc.drop_thr = dropout_p > 0.f ? (uint32_t)std::min(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
     tc.drop_scale = 1.0f / (1.0f - dropout_p);
     tc.seed = seed;
-    pfk_drop_masks(&tc, (uint32_t)layer * 2u + (uint32_t)which, h->N * 144, dev_out, (hipStream_t)stream);
+    // element = node * columns + column: 144 columns on the specialised leg, n_hidden_scalars + vector_size on the width-generic one
+    const int cols = h->train_wide ? h->cfg.n_hidden_scalars + h->cfg.vector_size : 144;
+    pfk_drop_masks(&tc, (uint32_t)layer * 2u + (uint32_t)which, h->N * cols, dev_out, (hipStream_t)stream);
     return PF_OK;
 }
 

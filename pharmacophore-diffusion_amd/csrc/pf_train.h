@@ -204,3 +204,61 @@ uint32_t pf_drop_hash(uint32_t seed, uint32_t stream, uint32_t elem) {
     x += elem; x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12; x *= 0x297A2D39u; x ^= x >> 15;
     return x;
 }
+
+// ---- gradient kernels of the width-generic family (pf_wide_train.hip; the forward is k_wide_edge<true> / k_wide_node<true>) ----
+// One launch differentiates ONE GVP level of every chain of a tile list (message chains of a conv layer, its update chains, the
+// noise head), last level first, reading that level's input rows as the training forward kept them and recomputing the level from
+// them.  Upstream and downstream gradients of a level travel through per-row buffers in HBM.  Sub-tiles of PFWT_ROWS rows.
+// Weight gradients: a launch's workgroups walk the tile list with a stride and add into their own copy of the gradient vector
+// (gpart[workgroup][gstride], plain read-modify-write by the owning lane); pfk_wt_reduce sums the PFWT_NB copies in index order.
+#define PFWT_ROWS 16
+#define PFWT_NB 64           // gradient copies = largest grid of a gradient launch
+struct WtCommon {
+    const float* W;          // flat parameters
+    float* gpart; int gstride;
+    int S, V, N;
+    uint32_t drop_thr, seed; float drop_scale;
+    const float* mask_override;   // tests: multipliers [n_convs * 2 streams][N * (S + V)] instead of the hash, or NULL
+};
+struct WtChainParams {
+    WtCommon c;
+    const EdgeTile* etiles; const NodeTile* ntiles; int n_tiles;   // one of the two tile tables (k_wt_chain<EDGE>)
+    const int* dyn_cnt; const int* row_ids;
+    const GvpT* g; int g_stride;             // this level's GVP of tile type ty (etype / node type): g[ty * g_stride + level]
+    int level, last;                         // last: the chain's last level (edges: the upstream is the destination's aggregate)
+    const float* sv_s; const float* sv_v;    // the level's input rows (already offset to the level): row (id - sv_base), strides sv_ls / sv_lv
+    int sv_ls, sv_lv, sv_base;
+    const float* up_s; const float* up_v; int up_ls, up_lv;   // dL/d(level output), row id
+    float* out_s; float* out_v; int out_ls, out_lv;           // dL/d(level input), row id (may alias up_*)
+    // message chains: row id = edge slot
+    const int* esrc; const int* edst;
+    const float* gagg_s; const float* gagg_v;   // dL/d(aggregated message) per node [N][S], [N][V][3]
+    const int* in_cnt; int pp_slot, norm_mode, l0;
+    long long* A_h; long long* A_v;          // level 0: fixed-point sums of dL/d(h_src, v_src) per source node [N][S], [N][V][3]
+    const float* fix;                        // pfk_fix_scale
+};
+struct WtNormParams {        // backward of one GVPLayerNorm of a conv layer and of the GVPDropout in front of / behind it
+    WtCommon c;
+    const NodeTile* tiles; int n_tiles; const int* dyn_cnt; const int* row_ids;
+    const float* dyA_s; const float* dyA_v; const float* dyB_s; const float* dyB_v;   // dL/d(output) = A (+ B when not NULL)
+    const float* x_s; const float* x_v;      // the rows the forward normalised
+    int o_lw[2], o_lb[2];                    // the norm's weight / bias per node type
+    float* out1_s; float* out1_v;            // dL/d(x)
+    float* out2_s; float* out2_v;            // the same times the dropout multipliers of `stream` (and over the message norm: use_norm)
+    int stream, use_norm;
+    const int* gid; const float* gnorm; int B, norm_mode; float norm_value;
+};
+struct WtHeadOutParams {     // to_scalar_output and the head's vector output
+    WtCommon c;
+    int Np, Nf, pharm_nf;
+    const float* g_eps_h; const float* g_eps_x; const float* h64;
+    int o_Wout, o_bout;
+    float* up_s; float* up_v; int up_ls, up_lv;
+};
+struct WtEncParams {
+    WtCommon c;
+    int Np, Nf, rec_nf, pharm_nf;
+    const float* prot_h0; const float* pharm_h; const float* t; const int* gid;
+    int o_w[2], o_b[2], o_lw[2], o_lb[2];    // 0 prot, 1 pharm
+    const float* G_h;                        // dL/d(encoder output) [N][S]
+};

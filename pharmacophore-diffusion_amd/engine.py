@@ -294,15 +294,38 @@ class PfEngine:
         self._ck(self.lib.pf_train_get_precision(self._h, ctypes.byref(out)), "pf_train_get_precision")
         return "bf16" if out.value == 1 else "f32"
 
+    def set_train_family(self, family):
+        """'tuned' (default: the gradient path specialised to n_hidden_scalars 128 / vector_size 16; other widths are refused) or
+        'wide' (the labelled width-generic leg: training forward and gradient kernels at every supported width pair, 128 / 16
+        included, fp32 only).  Inference is unaffected."""
+        code = {"tuned": 0, "wide": 1}.get(str(family).lower())
+        if code is None:
+            raise ValueError(f"train family must be 'tuned' or 'wide', got {family!r}")
+        self._ck(self.lib.pf_train_set_family(self._h, code), "pf_train_set_family")
+
+    def train_family(self):
+        out = ctypes.c_int32(0)
+        self._ck(self.lib.pf_train_get_family(self._h, ctypes.byref(out)), "pf_train_get_family")
+        return "wide" if out.value == 1 else "tuned"
+
+    def mask_columns(self):
+        """columns of a dropout-mask row: n_hidden_scalars + vector_size on the wide training leg, 144 on the tuned one"""
+        return self.cfg.n_hidden_scalars + self.cfg.vector_size if self.train_family() == "wide" else 144
+
     def set_dropout_masks(self, masks):
-        """tests: [n_convs, 2, N, 144] multipliers used instead of the built-in generator (None restores it)."""
+        """tests: [n_convs, 2, N, S + V] multipliers used instead of the built-in generator (None restores it); S + V = 144 on
+        the tuned training leg, n_hidden_scalars + vector_size on the wide one."""
+        if masks is not None:
+            want = (self.cfg.n_convs, 2, self.Np + self.Nf, self.mask_columns())
+            if tuple(masks.shape) != want:
+                raise ValueError(f"dropout masks must have shape {want} on the {self.train_family()} training leg, got {tuple(masks.shape)}")
         self._mask_keepalive = None if masks is None else _f32(masks, self.device)
         self._ck(self.lib.pf_debug_set_dropout_masks(self._h, _dptr(self._mask_keepalive)), "pf_debug_set_dropout_masks")
 
     def dropout_mask(self, layer, which, dropout, seed):
-        """[N, 144] multipliers of conv layer ``layer`` (which: 0 message, 1 residual dropout); rows are global node
-        ids (protein atoms first), columns 128 scalar features then 16 vector channels."""
-        out = torch.empty(self.Np + self.Nf, 144, device=self.device)
+        """[N, S + V] multipliers of conv layer ``layer`` (which: 0 message, 1 residual dropout); rows are global node
+        ids (protein atoms first), columns the S scalar features then the V vector channels (128 + 16 on the tuned leg)."""
+        out = torch.empty(self.Np + self.Nf, self.mask_columns(), device=self.device)
         with torch.cuda.device(self.device):
             self._ck(self.lib.pf_debug_dropout_mask(self._h, layer, which, float(dropout), int(seed) & 0xFFFFFFFF,
                                                     _dptr(out), _stream_ptr()), "pf_debug_dropout_mask")

@@ -251,6 +251,7 @@ class PharmRecDynamicsGVP(nn.Module):
         if self._engine is None or self._engine.device != dev:
             self._engine = PfEngine(device=dev, **self._arch)
             self._engine.set_train_precision(getattr(self, "train_precision", "f32"))
+            self._engine.set_train_family(getattr(self, "train_family", "tuned"))
             self._join_prefetch()
             self.__dict__["_twin"] = None           # (prefetch_graph makes a new one on this device)
             self._weights_stamp = None
@@ -282,6 +283,19 @@ class PharmRecDynamicsGVP(nn.Module):
         if twin is not None:
             self._join_prefetch()
             twin.set_train_precision(self.train_precision)
+
+    def set_train_family(self, family: str):
+        """'tuned' (default: the gradient kernels specialised to n_hidden_scalars 128 / vector_size 16) or 'wide' -- the labelled
+        width-generic training leg (fp32 only), which trains at every supported width pair.  Inference is unaffected."""
+        if str(family).lower() not in ("tuned", "wide"):
+            raise ValueError(f"train family must be 'tuned' or 'wide', got {family!r}")
+        self.train_family = str(family).lower()
+        if self._engine is not None:
+            self._engine.set_train_family(self.train_family)
+        twin = self.__dict__.get("_twin")
+        if twin is not None:
+            self._join_prefetch()
+            twin.set_train_family(self.train_family)
 
     def lane_engine(self, lane: int) -> PfEngine:
         """Engine of sampling lane ``lane``: lane 0 is engine(); further lanes are extra handles (own workspace) that carry
@@ -458,6 +472,7 @@ class PharmRecDynamicsGVP(nn.Module):
             twin = PfEngine(device=self._engine.device, **self._arch)
             twin.load_state_dict({k: v for k, v in self.state_dict().items()}, prefix="")
             twin.set_train_precision(getattr(self, "train_precision", "f32"))
+            twin.set_train_family(getattr(self, "train_family", "tuned"))
             self.__dict__["_twin"] = twin
         stream = torch.cuda.current_stream(twin.device)
         pf = {"key": key, "static": static, "err": None}

@@ -49,7 +49,16 @@ def main():
     p.add_argument('--train_precision', choices=['f32', 'bf16'], default='f32',
                    help="arithmetic of the dense Linears in the training step: f32 (the reference's) or the bf16 leg (bf16 matrix "
                         "instructions, fp32 accumulation, fp32 master weights and optimiser)")
+    p.add_argument('--train_family', choices=['auto', 'tuned', 'wide'], default='auto',
+                   help="gradient kernels: tuned (n_hidden_scalars 128 / vector_size 16 only), wide (the width-generic fp32 leg, every "
+                        "supported width pair) or auto: wide iff the config's widths are not 128 / 16")
     args = p.parse_args()
+    with open(args.config) as f:
+        _dyn = (yaml.load(f, Loader=yaml.FullLoader).get('dynamics') or {})
+    widths = (int(_dyn.get('n_hidden_scalars', 128)), int(_dyn.get('vector_size', 16)))
+    family = args.train_family if args.train_family != 'auto' else ('tuned' if widths == (128, 16) else 'wide')
+    if family == 'wide' and args.train_precision == 'bf16':
+        p.error('--train_precision bf16 is not available on the wide training leg (fp32 only)')
     import pharmacoforge_amd as pfa
     from pharmacoforge_amd.dataset import data_module_from_config
 
@@ -80,6 +89,9 @@ def main():
         torch.manual_seed(args.seed)
     model = pfa.model_from_config(config).to(dev)
     model.dynamics.set_train_precision(args.train_precision)
+    model.dynamics.set_train_family(family)
+    print(f"training leg: {family} ({'width-generic fp32 kernels' if family == 'wide' else 'kernels specialised to 128 / 16'}; "
+          f"n_hidden_scalars {widths[0]}, vector_size {widths[1]})", flush=True)
     lr_cfg = config['lr_scheduler']
     opt = pfa.FlatAdam(model.dynamics, lr=lr_cfg['base_lr'], weight_decay=lr_cfg.get('weight_decay', 0.0))
     plateau = dict(lr_cfg.get('reducelronplateau', {}))
