@@ -21,7 +21,7 @@
 //   u(t,hl) = (t&3) + 8*(t>>2) + 4*hl sits in register t (0..7) of lane half hl, one register
 //   array per coordinate -- rows 0..15 of a C/D fragment -- so the vector channel (Wh, Wu) runs
 //   on the matrix cores too and the two lanes of a row never exchange data explicitly.
-//   Weights are pre-packed on the host in A-operand fragment order (pf_host.cpp: pack_linear).
+//   Weights are pre-packed on the host in A-operand fragment order (pf_pack.cpp: pack_gvp).
 #pragma once
 #include <stdint.h>
 
@@ -397,7 +397,7 @@ struct TailParams {
     pf_gcf ln1_w, ln1_b, ln2_w, ln2_b;               // message / update layer norms of the centers
     int n_upd, n_head;
     // wave 0's quad stream: [update chain][head GVPs 0 .. n_head - 2][the head's last GVP, zero-padded to 128 + 16 outputs, with
-    // to_scalar_output in gate rows 1 .. pharm_nf (pf_host.cpp: pack_n16_head_last)]; wave w's chain_stride floats further
+    // to_scalar_output in gate rows 1 .. pharm_nf (pf_pack.cpp: pack_n16_head_last)]; wave w's chain_stride floats further
     pf_gcf chain; int chain_stride;
     int pharm_nf;
     float* eps_h; float* eps_x;                      // [Nf][pharm_nf], [Nf][3]: also written to memory (debug / profiling readers)

@@ -1,4 +1,4 @@
-// pf_host.cpp -- C ABI of libpfdyn.so (include/pfdyn.h): handle, weight packing, workspace,
+// pf_host.cpp -- C ABI of libpfdyn.so (include/pfdyn.h): handle, weight commit (the packer itself: pf_pack.cpp), workspace,
 // launch sequencing.  No compute happens on the host; without a HIP device every compute entry
 // point fails (there is no CPU fallback).
 #include <hip/hip_runtime.h>
@@ -17,7 +17,10 @@
 
 #include "../../include/pfdyn.h"
 #include "pf_device.h"
+#include "pf_pack.h"
 #include "pf_train.h"
+
+using namespace pfpack;
 
 #define L0_PTAB_SLOTS 2048        // timesteps whose layer-0 type tables stay resident (pf_prepare_timesteps)
 
@@ -107,16 +110,6 @@ void pfk_wt_reduce(const float* gpart, int gstride, float* grad, int nparams, hi
 namespace {
 
 static std::string g_create_error;
-
-struct RawTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
-
-static const char* kEtKey[4] = {"pharm_ff_pharm", "prot_pf_pharm", "pharm_fp_prot", "prot_pp_prot"};
-static const char* kNtKey[2] = {"prot", "pharm"};
-
-inline int rho(int r, int hl) { return (r & 3) + 8 * (r >> 2) + 4 * hl; }
 
 // torch.linspace(start, end, steps) in fp32 (symmetric evaluation like ATen)
 static void linspace_f32(float start, float end, int steps, float* out) {
@@ -237,16 +230,14 @@ struct pf_handle {
     // a (128, 16) handle created under PFDYN_WIDE=1.  spec: the widths of the specialised kernels -- their weights are packed and
     // training is available; wide: inference goes to run_dynamics_wide
     bool spec = true, wide = false;
-    std::vector<size_t> wide_off;           // per GVP (the GvpW table's order) the offsets of wh, wu, wm, bm, wg, bg in d_w
     WideGvp* d_wgvp = nullptr;              // device table of the width-generic GVPs (same indexing as d_gvp)
-    size_t wide_out_w = 0, wide_out_b = 0;  // to_scalar_output as stored ([pharm_nf][64], [pharm_nf])
     std::string err;
     std::map<std::string, RawTensor> raw;
     bool committed = false;
 
     // ---- packed weights (one device allocation)
     float* d_w = nullptr;
-    std::vector<float> h_w;                 // staging
+    PackLayout pk;                          // where everything sits in d_w (pf_pack.h): offsets and strides in floats
     GvpW* d_gvp = nullptr;                  // table of all GvpW
     std::vector<GvpW> h_gvp;
     // indices into the GvpW table
@@ -254,11 +245,6 @@ struct pf_handle {
     int upd_base(int layer, int nt) const { return n_msg_tot + (layer * 2 + nt) * cfg.n_update_gvps; }
     int head_base() const { return n_msg_tot + n_upd_tot; }
     int n_msg_tot = 0, n_upd_tot = 0;
-    // raw (unpacked) device weights: offsets into d_w
-    size_t enc_w[2]{}, enc_b[2]{}, enc_lw[2]{}, enc_lb[2]{};
-    std::vector<size_t> ln_off;             // [layer][nt][4]: ln1_w ln1_b ln2_w ln2_b
-    size_t out_a = 0, out_b = 0;
-    size_t enc_a = 0, enc_bf = 0;           // protein encoder as A fragments / F-layout bias (encode_pre_tile)
     bool use_pre = true;
 
     // ---- batch / workspace
@@ -340,11 +326,9 @@ struct pf_handle {
     int* xstat_host = nullptr;              // pinned; an async copy of d_xstat follows every sampling run (pf_sample_end)
     int xstat_ack = 0;                      // the count already reported (pf_sample_status / pf_sample_begin / pf_debug_xchg_timeouts)
     int xchg_fault = 0, xchg_poll_max = 0;  // diagnostics (pf_debug_xchg_fault)
-    // center hoist (CenHoistParams; pf_cenhoist.h): M0H streams of conv layer 0's chains for EVERY etype, the L0C block, the per-batch
+    // center hoist (CenHoistParams; pf_cenhoist.h; its streams and L0C block: pk.n16_l0h, pk.l0c_off): the per-batch
     // tables and exchange copy, two alternating snapshots of the centers' features, the announced timestep plan (pf_prepare_timesteps)
     // that tells a denoising step the NEXT call's t, and what the tables currently hold
-    size_t n16_l0h[4] = {0, 0, 0, 0}, n16_l0h_stride[4] = {0, 0, 0, 0};
-    size_t l0c_off = 0;
     bool cen_hoist = true;                  // PFDYN_NO_CENTER_HOIST=1: off
     float *d_cen_h = nullptr, *d_cen_p = nullptr, *d_snap[2] = {nullptr, nullptr};
     unsigned int* d_xchg2 = nullptr;
@@ -391,33 +375,14 @@ struct pf_handle {
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
-    // row-group kernels (pf_rg.hip): quad streams of the message chains [layer][etype] and update chains [layer][ntype]
-    // (offsets into d_w); which form a launch takes: LaunchPolicy above
-    std::vector<size_t> rg_msg, rg_upd;
-    std::vector<size_t> rgs_msg, rgs_upd, rgs_upd_stride;   // two-wave form: wave 0's stream; wave 1's follows *_stride floats later
-    size_t rgs_msg_stride = 0;
-    // n16 kernels (pf_n16.hip): per chain the four waves' quad streams, wave w's *_stride floats after wave w - 1's.
-    // n16_msg: every message chain with a full first GVP (M0F: what conv layers >= 1 run, and what pf_debug_chain tests)
-    std::vector<size_t> n16_msg, n16_upd;
-    size_t n16_msg_stride = 0, n16_upd_stride = 0;
-    // packed elements [n16_begin, n_packed) are the n16 streams: no training kernel reads them, so pf_set_flat_params (called
+    // which form a launch takes (row-group quad streams, n16 streams: pk.rg_*, pk.n16_*): LaunchPolicy above
+    // packed elements [pk.n16_begin, n_packed) are the n16 streams: no training kernel reads them, so pf_set_flat_params (called
     // after every optimiser step) refreshes only what precedes them and marks them stale; the first inference call afterwards
     // (run_dynamics without train, pf_debug_chain) gathers them (n16_refresh)
-    size_t n16_begin = 0;
     bool n16_stale = false;
-    // -DN16_SPLIT builds: the main quads of the n16 streams hold bf16 planes, two weights per 32-bit word -- not a gather.  While the
-    // index-valued packing pass runs (split_record) pack_n16_raw notes (word position, flat index a, flat index b, plane) per word;
-    // n16_refresh re-derives those words from the flat vector behind the gather (k_n16_split_words)
-    bool split_record = false;
-    std::vector<int4> split_pending, split_tab;     // positions relative to the stream being packed / to h_w
+    // -DN16_SPLIT builds: the main quads of the n16 streams hold bf16 planes, two weights per 32-bit word -- not a gather (PackedModel::
+    // split_tab); n16_refresh re-derives those words from the flat vector behind the gather (k_n16_split_words)
     int4* d_split_tab = nullptr; size_t n_split_tab = 0;
-    // conv layer 0's message chains in their own forms: protein sources (pf, pp) start from a type-table row (M0H),
-    // centers (ff, fp) have zero node vectors (M0Z)
-    size_t n16_l0[4] = {0, 0, 0, 0}, n16_l0_stride[4] = {0, 0, 0, 0};
-    // fused launch (n_convs = 2): per etype of the last layer (ff, pf) [update chain of conv layer 0 for the source type][message chain]
-    size_t n16_fused[2] = {0, 0}, n16_fused_stride[2] = {0, 0};
-    // tail launch (pf_n16.hip: k_n16_tail): [update chain of the centers in the last conv layer][noise head; its last GVP padded, with to_scalar_output]
-    size_t n16_tail = 0, n16_tail_stride = 0;
     bool tail_done = false;                 // the last run_dynamics call of a denoising step also did the step's update + build
     int last_tail = 0;                      // pf_debug_kernel_family(layer = n_convs): 0 / 4 (k_rg_tail) / 16 (k_n16_tail)
     float *d_msg_s2 = nullptr, *d_msg_v2 = nullptr;   // the last conv layer's message rows when conv layer 0's are still being read (fused launch)
@@ -426,7 +391,6 @@ struct pf_handle {
     // ---- static hoist of conv layer 0's pp messages (pf_rg.hip, EdgeParams::zs).  Everything derived from the weights
     // carries the version of the weights it was computed from (commit / pf_set_flat_params bump w_version).
     bool l0_hoist = true;                   // PFDYN_NO_L0_HOIST=1: off
-    size_t l0h_off = 0;                     // L0H_* block in d_w
     uint64_t w_version = 1, zs_version = 0, ptab_version = 0;
     bool l0_onehot = false;                 // every protein feature row of the batch is an element one-hot
     bool coords_custom = false;             // protein coordinates came from the caller of this call (not the batch's own)
@@ -471,8 +435,7 @@ struct pf_handle {
     size_t nparams = 0;
     std::vector<std::pair<std::string, std::pair<size_t, size_t>>> flat_layout;   // name -> (offset, numel), state-dict order
     GvpT* d_gvpt = nullptr;                 // same indexing as the GvpW table
-    std::vector<int> h_map;                 // packed element -> flat parameter index (-1: zero), see pf_commit_weights
-    int* d_map = nullptr;
+    int* d_map = nullptr;                   // packed element -> flat parameter index (-1: zero): PackedModel::map
     size_t n_packed = 0;
     void* d_tws = nullptr;                  // training workspace of the current batch (allocated on first use)
     std::vector<float*> t_H, t_V, t_msg_s, t_msg_v;
@@ -571,448 +534,13 @@ namespace {
         if (_e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
     } while (0)
 
-// ------------------------------------------------------------------------------------------------
-// expected state-dict layout (mirrors the reference's module tree)
-// ------------------------------------------------------------------------------------------------
-struct GvpSpec { std::string prefix; int vi, vo, si, so; };
-
-static void gvp_names(const GvpSpec& g, std::vector<std::pair<std::string, std::vector<int64_t>>>& out) {
-    const int h = std::max(g.vi, g.vo);
-    out.push_back({g.prefix + "Wh", {g.vi, h}});
-    out.push_back({g.prefix + "Wu", {h, g.vo}});
-    out.push_back({g.prefix + "to_feats_out.0.weight", {g.so, h + g.si}});
-    out.push_back({g.prefix + "to_feats_out.0.bias", {g.so}});
-    out.push_back({g.prefix + "scalar_to_vector_gates.weight", {g.vo, g.so}});
-    out.push_back({g.prefix + "scalar_to_vector_gates.bias", {g.vo}});
-}
-
-static std::string conv_prefix(int layer) {
-    return "dynamics.noise_predictor.conv_layers." + std::to_string(layer) + ".";
-}
-static GvpSpec msg_spec(const pf_config& c, int layer, int et, int j) {
-    GvpSpec g;
-    g.prefix = conv_prefix(layer) + "edge_message_fns." + kEtKey[et] + "." + std::to_string(j) + ".";
-    g.vi = c.vector_size + (j == 0 ? 1 : 0);
-    g.vo = c.vector_size;
-    g.si = c.n_hidden_scalars + (j == 0 ? c.rbf_dim : 0);
-    g.so = c.n_hidden_scalars;
-    return g;
-}
-static GvpSpec upd_spec(const pf_config& c, int layer, int nt, int j) {
-    GvpSpec g;
-    g.prefix = conv_prefix(layer) + "node_update_fns." + kNtKey[nt] + "." + std::to_string(j) + ".";
-    g.vi = g.vo = c.vector_size;
-    g.si = g.so = c.n_hidden_scalars;
-    return g;
-}
-static GvpSpec head_spec(const pf_config& c, int k) {
-    GvpSpec g;
-    g.prefix = "dynamics.noise_predictor.noise_predictor.gvps." + std::to_string(k) + ".";
-    g.vi = c.vector_size;
-    g.si = c.n_hidden_scalars;
-    const bool last = k == c.n_noise_gvps - 1;
-    g.vo = last ? 1 : c.vector_size;
-    g.so = last ? 64 : c.n_hidden_scalars;
-    return g;
-}
-
-static std::vector<std::pair<std::string, std::vector<int64_t>>> expected_tensors(const pf_config& c) {
-    std::vector<std::pair<std::string, std::vector<int64_t>>> v;
-    const int S = c.n_hidden_scalars;
-    for (int nt = 0; nt < 2; ++nt) {
-        const std::string p = std::string("dynamics.") + kNtKey[nt] + "_encoder.";
-        const int nf = nt ? c.pharm_nf : c.rec_nf;
-        v.push_back({p + "0.weight", {S, nf + 1}});
-        v.push_back({p + "0.bias", {S}});
-        v.push_back({p + "2.weight", {S}});
-        v.push_back({p + "2.bias", {S}});
-    }
-    for (int l = 0; l < c.n_convs; ++l) {
-        for (int et = 0; et < 4; ++et)
-            for (int j = 0; j < c.n_message_gvps; ++j) gvp_names(msg_spec(c, l, et, j), v);
-        for (int nt = 0; nt < 2; ++nt) {
-            for (int j = 0; j < c.n_update_gvps; ++j) gvp_names(upd_spec(c, l, nt, j), v);
-            for (const char* which : {"message_layer_norms", "update_layer_norms"}) {
-                const std::string p = conv_prefix(l) + which + "." + kNtKey[nt] + ".feat_norm.";
-                v.push_back({p + "weight", {S}});
-                v.push_back({p + "bias", {S}});
-            }
-        }
-    }
-    for (int k = 0; k < c.n_noise_gvps; ++k) gvp_names(head_spec(c, k), v);
-    v.push_back({"dynamics.noise_predictor.noise_predictor.to_scalar_output.weight", {c.pharm_nf, 64}});
-    v.push_back({"dynamics.noise_predictor.noise_predictor.to_scalar_output.bias", {c.pharm_nf}});
-    return v;
-}
-
-// ------------------------------------------------------------------------------------------------
-// packing into MFMA A-operand fragment order (see pf_device.h "F-layout")
-// ------------------------------------------------------------------------------------------------
-static size_t push(std::vector<float>& w, const std::vector<float>& v) {
-    while (w.size() % 64) w.push_back(0.f);     // 256-byte alignment of every block
-    const size_t off = w.size();
-    w.insert(w.end(), v.begin(), v.end());
-    return off;
-}
-
-struct GvpOff { size_t wh, wu, wh_c, wu_c, a_main, a_main_c, b_main, a_gate, a_gate_c, b_gate; };
-
-// width-generic family: a Linear W [n_out][K] as the B operand of v_mfma_f32_16x16x4_f32, [tile of 16 outputs][k-step][64 lanes],
-// lane l <-> W[16 t + (l & 15)][4 ks + (l >> 4)] (pf_device.h: WideGvp); zero outside the matrix
-static std::vector<float> pack_wide_linear(const std::vector<float>& W, int n_out, int K) {
-    const int KS = (K + 3) / 4, NT = (n_out + 15) / 16;
-    std::vector<float> a((size_t)NT * KS * 64, 0.f);
-    for (int t = 0; t < NT; ++t)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int l = 0; l < 64; ++l) {
-                const int n = 16 * t + (l & 15), k = 4 * ks + (l >> 4);
-                if (n < n_out && k < K) a[((size_t)t * KS + ks) * 64 + l] = W[(size_t)n * K + k];
-            }
-    return a;
-}
-// the six pieces of one GVP; appends their offsets (wh, wu, wm, bm, wg, bg) to off
-static void pack_wide_gvp(pf_handle* h, const GvpSpec& g, std::vector<size_t>& off) {
-    const int H = std::max(g.vi, g.vo);
-    off.push_back(push(h->h_w, h->raw[g.prefix + "Wh"].data));
-    off.push_back(push(h->h_w, h->raw[g.prefix + "Wu"].data));
-    off.push_back(push(h->h_w, pack_wide_linear(h->raw[g.prefix + "to_feats_out.0.weight"].data, g.so, g.si + H)));
-    off.push_back(push(h->h_w, h->raw[g.prefix + "to_feats_out.0.bias"].data));
-    off.push_back(push(h->h_w, pack_wide_linear(h->raw[g.prefix + "scalar_to_vector_gates.weight"].data, g.vo, g.so)));
-    off.push_back(push(h->h_w, h->raw[g.prefix + "scalar_to_vector_gates.bias"].data));
-}
-
-static GvpOff pack_gvp(pf_handle* h, const GvpSpec& g) {
-    const int H = std::max(g.vi, g.vo);
-    const int nextra = g.si - h->cfg.n_hidden_scalars;     // 16 (rbf) for the first message GVP
-    const int NMO = g.so / 32;
-    const int NSH = 8 + (g.vi == 17 ? 1 : 0);
-    const int NKS = 64 + nextra / 2 + NSH;
-    const int Kin = H + g.si;
-    const RawTensor& W = h->raw[g.prefix + "to_feats_out.0.weight"];   // [so][si + H]
-    const RawTensor& Bv = h->raw[g.prefix + "to_feats_out.0.bias"];
-    const RawTensor& G = h->raw[g.prefix + "scalar_to_vector_gates.weight"];   // [vo][so]
-    GvpOff o;
-    {   // vector channel as A fragments.  k-step t < 8: lane half hl carries input channel u(t,hl) = rho(t,hl)
-        // (for a 17-channel input that is Wh row 1 + u: row 0 is the unit x_diff, fed at k-step 8 by half 0).
-        const std::vector<float>& wh = h->raw[g.prefix + "Wh"].data;      // [vi][H]
-        const std::vector<float>& wu = h->raw[g.prefix + "Wu"].data;      // [H][vo]
-        const bool X = g.vi == 17;
-        const int NVK = 8 + (X ? 1 : 0);
-        std::vector<float> awh((size_t)NVK * 64, 0.f), awu((size_t)NVK * 64, 0.f);
-        for (int t = 0; t < NVK; ++t)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int i = lane & 31, hl = lane >> 5;
-                int vin, hin;                      // input channel of Wh / of Wu at this k-step for this half
-                if (t < 8) { vin = (X ? 1 : 0) + rho(t, hl); hin = rho(t, hl); }
-                else { vin = hl == 0 ? 0 : -1; hin = hl == 0 ? 16 : -1; }
-                awh[(size_t)t * 64 + lane] = (i < H && vin >= 0) ? wh[(size_t)vin * H + i] : 0.f;
-                awu[(size_t)t * 64 + lane] = (i < g.vo && hin >= 0 && hin < H) ? wu[(size_t)hin * g.vo + i] : 0.f;
-            }
-        o.wh = push(h->h_w, awh);
-        o.wu = push(h->h_w, awu);
-        // four k-steps per lane for the 4-wave kernels: [t/4][lane][t%4]
-        std::vector<float> c1((size_t)3 * 64 * 4, 0.f), c2((size_t)3 * 64 * 4, 0.f);
-        for (int t = 0; t < NVK; ++t)
-            for (int lane = 0; lane < 64; ++lane) {
-                c1[((size_t)(t / 4) * 64 + lane) * 4 + t % 4] = awh[(size_t)t * 64 + lane];
-                c2[((size_t)(t / 4) * 64 + lane) * 4 + t % 4] = awu[(size_t)t * 64 + lane];
-            }
-        o.wh_c = push(h->h_w, c1);
-        o.wu_c = push(h->h_w, c2);
-    }
-    std::vector<float> a((size_t)NKS * 64 * NMO, 0.f);
-    for (int ks = 0; ks < NKS; ++ks)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int i = lane & 31, hl = lane >> 5;
-            int col;
-            if (ks < 64) col = 32 * (ks / 16) + rho(ks % 16, hl);
-            else if (ks < 64 + nextra / 2) col = 128 + 2 * (ks - 64) + hl;
-            else {                                   // sh block: k-step t carries sh[u(t,hl)]; t == 8: sh[16] on half 0
-                const int t = ks - 64 - nextra / 2;
-                const int idx = t < 8 ? rho(t, hl) : (hl == 0 ? 16 : -1);
-                col = (idx >= 0 && idx < H) ? 128 + nextra + idx : -1;
-            }
-            for (int mo = 0; mo < NMO; ++mo) {
-                const int row = 32 * mo + i;
-                a[((size_t)ks * 64 + lane) * NMO + mo] = col >= 0 ? W.data[(size_t)row * Kin + col] : 0.f;
-            }
-        }
-    o.a_main = push(h->h_w, a);
-    {   // the same fragments per output tile, four k-steps per lane: [mo][ks/4][lane][ks%4]
-        const int NKS4 = (NKS + 3) / 4;
-        std::vector<float> ac((size_t)NMO * NKS4 * 64 * 4, 0.f);
-        for (int ks = 0; ks < NKS; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int mo = 0; mo < NMO; ++mo)
-                    ac[(((size_t)mo * NKS4 + ks / 4) * 64 + lane) * 4 + ks % 4] = a[((size_t)ks * 64 + lane) * NMO + mo];
-        o.a_main_c = push(h->h_w, ac);
-    }
-    std::vector<float> b((size_t)2 * NMO * 16);
-    for (int hl = 0; hl < 2; ++hl)
-        for (int mo = 0; mo < NMO; ++mo)
-            for (int r = 0; r < 16; ++r) b[(size_t)hl * NMO * 16 + mo * 16 + r] = Bv.data[32 * mo + rho(r, hl)];
-    o.b_main = push(h->h_w, b);
-    std::vector<float> ag((size_t)NMO * 16 * 64, 0.f);
-    for (int ks = 0; ks < NMO * 16; ++ks)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int i = lane & 31, hl = lane >> 5;
-            const int k = 32 * (ks / 16) + rho(ks % 16, hl);
-            ag[(size_t)ks * 64 + lane] = i < g.vo ? G.data[(size_t)i * g.so + k] : 0.f;      // rows 0..vo-1 = gates
-        }
-    o.a_gate = push(h->h_w, ag);
-    {   // gate fragments of the wave owning output tile mo: k-steps 16*mo .. 16*mo+15 as [mo][r/4][lane][r%4]
-        std::vector<float> agc((size_t)NMO * 4 * 64 * 4, 0.f);
-        for (int mo = 0; mo < NMO; ++mo)
-            for (int r = 0; r < 16; ++r)
-                for (int lane = 0; lane < 64; ++lane)
-                    agc[(((size_t)mo * 4 + r / 4) * 64 + lane) * 4 + r % 4] = ag[(size_t)(mo * 16 + r) * 64 + lane];
-        o.a_gate_c = push(h->h_w, agc);
-    }
-    {   // gate bias in R-layout: half hl, register t <-> gate rho(t,hl)
-        const std::vector<float>& bgv = h->raw[g.prefix + "scalar_to_vector_gates.bias"].data;
-        std::vector<float> bg(16, 0.f);
-        for (int hl = 0; hl < 2; ++hl)
-            for (int t = 0; t < 8; ++t) bg[(size_t)hl * 8 + t] = rho(t, hl) < g.vo ? bgv[rho(t, hl)] : 0.f;
-        o.b_gate = push(h->h_w, bg);
-    }
-    return o;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Quad stream of one GVP for the row-group kernels (pf_rg.hip; schedule: rg_sched in pf_device.h).  A quad is
-// [64 lanes][4 images]; an image is what one lane holds of a B operand: lane f <-> output feature f (scalar Linear),
-// lane 16g + u <-> output channel u of coordinate group g (vector products, gates; g = 3 unused -> 0).
-// ------------------------------------------------------------------------------------------------
-// the 8 gate quads of a GVP (or to_scalar_output): K split over the lane groups, quad m, image j <-> features
-// 8 (4g + j) + m of lane group g (the A block (g, j) of the SA layout)
-static void pack_gate_quads_rg(const std::vector<float>& Wg, int vo, int so, std::vector<float>& out, size_t base, int q0) {
-    for (int lane = 0; lane < 64; ++lane) {
-        const int gq = lane >> 4, u = lane & 15;
-        for (int m = 0; m < 8; ++m)
-            for (int j = 0; j < 4; ++j) {
-                const int feat = 8 * (4 * gq + j) + m;
-                out[base + ((size_t)(q0 + m) * 64 + lane) * 4 + j] = (u < vo && feat < so) ? Wg[(size_t)u * so + feat] : 0.f;
-            }
-    }
-}
-// one block of a chain: GVP g, plus the gate quads of the GVP before it (prev) when there is one
-// half >= 0: the block of wave `half` of the two-wave form (outputs 64 half .. 64 half + 63 of a 128-output scalar
-// Linear; a 64-output GVP is the same block for both waves)
-static void pack_gvp_rg(pf_handle* h, const GvpSpec& g, const GvpSpec* prev, std::vector<float>& out, int half = -1) {
-    const int S = h->cfg.n_hidden_scalars;
-    const int H = std::max(g.vi, g.vo);
-    const int nextra = g.si - S;
-    const bool split = half >= 0 && g.so == 128;
-    const int NH = split ? 1 : g.so / 64;             // halves of 64 outputs in this block
-    const int f0 = split ? 64 * half : 0;             // first output feature of the block
-    const int so_end = split ? f0 + 64 : g.so;
-    const bool X17 = g.vi == 17;
-    const RgSched q = rg_sched(g.vi, nextra, NH, prev != nullptr);
-    const int Kin = H + g.si;
-    const std::vector<float>& W = h->raw[g.prefix + "to_feats_out.0.weight"].data;            // [so][si + H]
-    const std::vector<float>& Bv = h->raw[g.prefix + "to_feats_out.0.bias"].data;
-    const std::vector<float>& bg = h->raw[g.prefix + "scalar_to_vector_gates.bias"].data;
-    const std::vector<float>& wh = h->raw[g.prefix + "Wh"].data;                              // [vi][H]
-    const std::vector<float>& wu = h->raw[g.prefix + "Wu"].data;                              // [H][vo]
-    const size_t base = out.size();
-    out.resize(base + (size_t)q.nq * 256, 0.f);
-    auto at = [&](int quad, int lane, int j) -> float& { return out[base + ((size_t)quad * 64 + lane) * 4 + j]; };
-    const int v0 = X17 ? 1 : 0;                      // Wh row of node-vector channel 0 (row 0 is the unit x_diff)
-    for (int lane = 0; lane < 64; ++lane) {
-        const int gq = lane >> 4, u = lane & 15, qq = (lane >> 2) & 3;
-        // constants: scalar bias (two halves), gate bias, Wh[0][16] on the lanes that carry xhat
-        at(q.q_c, lane, 0) = f0 + lane < so_end ? Bv[f0 + lane] : 0.f;
-        at(q.q_c, lane, 1) = f0 + 64 + lane < so_end ? Bv[f0 + 64 + lane] : 0.f;
-        at(q.q_c, lane, 2) = u < g.vo ? bg[u] : 0.f;
-        at(q.q_c, lane, 3) = (X17 && qq == 0 && gq < 3) ? wh[(size_t)0 * H + 16] : 0.f;
-        if (X17) {
-            at(q.q_xh, lane, 0) = gq < 3 ? wh[(size_t)0 * H + u] : 0.f;                              // xhat k-step of Vh
-            at(q.q_xh, lane, 1) = (gq < 3 && u < g.vo) ? wu[(size_t)16 * g.vo + u] : 0.f;           // Vh[16] k-step of Vu
-            at(q.q_xh, lane, 2) = f0 + lane < so_end ? W[(size_t)(f0 + lane) * Kin + g.si + 16] : 0.f;           // sh[16] column
-            at(q.q_xh, lane, 3) = f0 + 64 + lane < so_end ? W[(size_t)(f0 + 64 + lane) * Kin + g.si + 16] : 0.f;
-            for (int t = 0; t < 4; ++t) at(q.q_xh + 1, lane, t) = gq < 3 ? wh[(size_t)(1 + 4 * t + qq) * H + 16] : 0.f;
-        }
-        for (int t = 0; t < 4; ++t)
-            for (int j = 0; j < 4; ++j) {
-                at(q.q_vh + t, lane, j) = gq < 3 ? wh[(size_t)(v0 + 4 * t + j) * H + u] : 0.f;
-                at(q.q_vu + t, lane, j) = (gq < 3 && u < g.vo) ? wu[(size_t)(4 * t + j) * g.vo + u] : 0.f;
-            }
-        for (int hh = 0; hh < NH; ++hh) {
-            const int f = f0 + hh * 64 + lane;
-            for (int m = 0; m < 8; ++m)
-                for (int aq = 0; aq < 4; ++aq)
-                    for (int j = 0; j < 4; ++j)
-                        at(rg_main_quad(q, NH, (m * 4 + aq) * NH + hh), lane, j) = W[(size_t)f * Kin + 8 * (4 * aq + j) + m];
-            for (int aq = 0; aq < 4; ++aq)
-                for (int j = 0; j < 4; ++j) {
-                    if (nextra) at(q.q_rbf + aq * NH + hh, lane, j) = W[(size_t)f * Kin + S + 4 * aq + j];
-                    at(q.q_sh + aq * NH + hh, lane, j) = W[(size_t)f * Kin + g.si + 4 * aq + j];
-                }
-        }
-    }
-    if (prev) pack_gate_quads_rg(h->raw[prev->prefix + "scalar_to_vector_gates.weight"].data, prev->vo, prev->so, out, base, q.q_gate);
-}
-// end of a chain: the gate quads of its last GVP
-static void pack_flush_rg(pf_handle* h, const GvpSpec& g, std::vector<float>& out) {
-    const size_t base = out.size();
-    out.resize(base + (size_t)RG_NQ_FLUSH * 256, 0.f);
-    pack_gate_quads_rg(h->raw[g.prefix + "scalar_to_vector_gates.weight"].data, g.vo, g.so, out, base, 0);
-}
-// to_scalar_output (Linear 64 -> pharm_nf) as a gate-like product: [const] [8 quads] [pad]
-static void pack_out_rg(pf_handle* h, std::vector<float>& out) {
-    const RawTensor& W = h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.weight"];   // [pharm_nf][64]
-    const RawTensor& Bv = h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.bias"];
-    const int nf = h->cfg.pharm_nf;
-    const size_t base = out.size();
-    out.resize(base + (size_t)RG_NQ_OUT * 256, 0.f);
-    auto at = [&](int quad, int lane, int j) -> float& { return out[base + ((size_t)quad * 64 + lane) * 4 + j]; };
-    for (int lane = 0; lane < 64; ++lane) {
-        const int gq = lane >> 4, u = lane & 15;
-        at(0, lane, 0) = u < nf ? Bv.data[u] : 0.f;
-        for (int m = 0; m < 8; ++m)
-            for (int j = 0; j < 4; ++j) {
-                const int feat = 8 * (4 * gq + j) + m;
-                at(1 + m, lane, j) = (u < nf && feat < 64) ? W.data[(size_t)u * 64 + feat] : 0.f;
-            }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// n16 kernels (pf_n16.hip; schedules: n16_sched in pf_device.h): wave w's block of GVP g.  An image is one lane's share
-// of an A operand of v_mfma_f32_16x16x4_f32: lane 16 gq + i <-> output row i of the tile, k = gq of the k-step.
-// Scalar k-step ks <-> input feature 16 (ks >> 2) + 4 gq + (ks & 3); vector / rbf / sh k-step r <-> channel 4 gq + r.
-// ------------------------------------------------------------------------------------------------
-struct N16Raw {                                  // the six tensors of a GVP with 128 scalar and 16 vector outputs (g: its dimensions)
-    const std::vector<float>&W, &Bv, &Wg, &bg, &wh, &wu;
-    GvpSpec g;
-};
-// plane p (0..2) of x = p0 + p1 + p2 as a bf16 bit pattern: round-to-nearest-even of what the earlier planes left (the device's
-// n16_split8 / k_n16_split_words do the same arithmetic)
-[[maybe_unused]] static uint32_t n16_bf16_plane(float x, int p) {
-    uint32_t bits = 0;
-    for (int k = 0; k <= p; ++k) {
-        uint32_t u; memcpy(&u, &x, 4);
-        bits = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-        const uint32_t hi = bits << 16;
-        float back; memcpy(&back, &hi, 4);
-        x -= back;
-    }
-    return bits & 0xffffu;
-}
-static void pack_n16_raw(const N16Raw& rw, int kind, int w, std::vector<float>& out, std::vector<int4>* split_rec = nullptr) {
-    const GvpSpec& g = rw.g;
-    const N16Sched q = n16_sched(kind);
-    const int H = std::max(g.vi, g.vo), Kin = H + g.si;
-    const bool m0 = kind != N16_GEN, vz = kind == N16_M0Z || kind == N16_M0H;
-    const int v0 = g.vi == 17 ? 1 : 0;
-    const std::vector<float>& W = rw.W;             // [so][si + H]
-    const std::vector<float>& Bv = rw.Bv;
-    const std::vector<float>& Wg = rw.Wg;           // [vo][so]
-    const std::vector<float>& bg = rw.bg;
-    const std::vector<float>& wh = rw.wh;           // [vi][H]
-    const std::vector<float>& wu = rw.wu;           // [H][vo]
-    const size_t base = out.size();
-    out.resize(base + (size_t)q.nq * 256, 0.f);
-    auto at = [&](int quad, int lane, int j) -> float& { return out[base + ((size_t)quad * 64 + lane) * 4 + j]; };
-    for (int lane = 0; lane < 64; ++lane) {
-        const int gq = lane >> 4, i = lane & 15;
-        const int f0 = 32 * w + i, f1 = 32 * w + 16 + i;             // this lane's output rows of tile 0 / tile 1
-        if (m0) {
-            at(q.q_x1, lane, 0) = gq == 0 ? W[(size_t)f0 * Kin + g.si + 16] : 0.f;
-            at(q.q_x1, lane, 1) = gq == 0 ? W[(size_t)f1 * Kin + g.si + 16] : 0.f;
-            at(q.q_x1, lane, 2) = (gq == 0 && w < 3) ? wu[(size_t)16 * g.vo + i] : 0.f;
-            at(q.q_x1, lane, 3) = gq == 0 ? wh[(size_t)0 * H + i] : (lane == 16 ? wh[(size_t)0 * H + 16] : 0.f);
-        }
-        for (int r = 0; r < 4; ++r) {
-            if (vz) at(q.q_vh, lane, r) = wh[(size_t)0 * H + 4 * gq + r];                     // Vh = Wh[0] (x) xhat
-            else if (w < 3) at(q.q_vh, lane, r) = wh[(size_t)(v0 + 4 * gq + r) * H + i];
-            if (q.q_w16 >= 0 && w < 3) at(q.q_w16, lane, r) = wh[(size_t)(v0 + 4 * gq + r) * H + 16];
-            at(q.q_vu, lane, r) = w < 3 ? wu[(size_t)(4 * gq + r) * g.vo + i] : bg[4 * gq + r];
-        }
-#if N16_SPLIT
-        // main quad m = plane m % 3 of the weights of output tile (m / 3) % 2 over K chunk m / 6; a 32-bit word = elements 2 d, 2 d + 1
-        if (q.q_main >= 0)
-            for (int qm = 0; qm < N16_NQM; ++qm) {
-                const int cch = qm / 6, tt = (qm / 3) % 2, pl = qm % 3;
-                const int frow = tt ? f1 : f0;
-                for (int d = 0; d < 4; ++d) {
-                    float v[2];
-                    for (int k = 0; k < 2; ++k) {
-                        const int e = 2 * d + k;
-                        v[k] = W[(size_t)frow * Kin + 16 * (2 * cch + e / 4) + 4 * gq + e % 4];
-                    }
-                    float& word = at(q.main_pos(qm), lane, d);
-                    if (split_rec) {                 // index-valued pass: v = flat index + 1 (0: a padded row)
-                        word = 0.f;
-                        split_rec->push_back(make_int4((int)(&word - out.data()), (int)v[0] - 1, (int)v[1] - 1, pl));
-                    } else {
-                        const uint32_t bits = n16_bf16_plane(v[0], pl) | (n16_bf16_plane(v[1], pl) << 16);
-                        memcpy(&word, &bits, 4);
-                    }
-                }
-            }
-#else
-        if (q.q_main >= 0)
-            for (int qm = 0; qm < 16; ++qm)
-                for (int half = 0; half < 2; ++half) {
-                    const int ks = 2 * qm + half, f = 16 * (ks >> 2) + 4 * gq + (ks & 3);
-                    at(q.main_pos(qm), lane, 2 * half) = W[(size_t)f0 * Kin + f];
-                    at(q.main_pos(qm), lane, 2 * half + 1) = W[(size_t)f1 * Kin + f];
-                }
-#endif
-        for (int qq = 0; qq < 2; ++qq)
-            for (int half = 0; half < 2; ++half) {
-                const int r = 2 * qq + half;
-                if (m0) {
-                    at(q.q_rbf + qq, lane, 2 * half) = W[(size_t)f0 * Kin + PF_S + 4 * gq + r];
-                    at(q.q_rbf + qq, lane, 2 * half + 1) = W[(size_t)f1 * Kin + PF_S + 4 * gq + r];
-                }
-                at(q.q_sh + qq, lane, 2 * half) = W[(size_t)f0 * Kin + g.si + 4 * gq + r];
-                at(q.q_sh + qq, lane, 2 * half + 1) = W[(size_t)f1 * Kin + g.si + 4 * gq + r];
-            }
-        if (q.q_b >= 0)
-            for (int r = 0; r < 4; ++r) {
-                at(q.q_b, lane, r) = Bv[32 * w + 4 * gq + r];
-                at(q.q_b + 1, lane, r) = Bv[32 * w + 16 + 4 * gq + r];
-            }
-        for (int t = 0; t < 2; ++t)
-            for (int r = 0; r < 4; ++r) at(q.q_gate + t, lane, r) = Wg[(size_t)i * g.so + 32 * w + 16 * t + 4 * gq + r];
-    }
-}
-static void pack_n16(pf_handle* h, const GvpSpec& g, int kind, int w, std::vector<float>& out) {
-    const N16Raw rw{h->raw[g.prefix + "to_feats_out.0.weight"].data, h->raw[g.prefix + "to_feats_out.0.bias"].data,
-                    h->raw[g.prefix + "scalar_to_vector_gates.weight"].data, h->raw[g.prefix + "scalar_to_vector_gates.bias"].data,
-                    h->raw[g.prefix + "Wh"].data, h->raw[g.prefix + "Wu"].data, g};
-    pack_n16_raw(rw, kind, w, out, h->split_record ? &h->split_pending : nullptr);
-}
-// The noise head's last GVP (dynamics_gvp.py:17-20: 16 vectors -> 1, 128 scalars -> 64, identity vector gate) followed by
-// to_scalar_output (Linear 64 -> pharm_nf, :35,39) as ONE GEN block of the tail kernel: the GVP zero-padded to 128 scalar
-// and 16 vector outputs (SiLU(0) = 0: the padded scalars feed nothing), and to_scalar_output -- a Linear on the same SiLU
-// output as the gate Linear -- in the unused gate rows 1 .. pharm_nf (bias in the gate bias).  Pure data movement, like
-// every packing here (the gather map of pf_set_flat_params covers it).  Needs pharm_nf <= 15.
-static void pack_n16_head_last(pf_handle* h, const GvpSpec& g, int w, std::vector<float>& out) {
-    const int nf = h->cfg.pharm_nf, H = std::max(g.vi, g.vo), Kin = H + g.si;
-    const std::vector<float>& W = h->raw[g.prefix + "to_feats_out.0.weight"].data;            // [64][128 + 16]
-    const std::vector<float>& Bv = h->raw[g.prefix + "to_feats_out.0.bias"].data;
-    const std::vector<float>& Wg = h->raw[g.prefix + "scalar_to_vector_gates.weight"].data;   // [1][64]
-    const std::vector<float>& bg = h->raw[g.prefix + "scalar_to_vector_gates.bias"].data;
-    const std::vector<float>& wu = h->raw[g.prefix + "Wu"].data;                              // [16][1]
-    const std::vector<float>& Wo = h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.weight"].data;   // [nf][64]
-    const std::vector<float>& bo = h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.bias"].data;
-    std::vector<float> W2((size_t)PF_S * Kin, 0.f), B2(PF_S, 0.f), G2((size_t)16 * PF_S, 0.f), bg2(16, 0.f), U2((size_t)H * 16, 0.f);
-    for (int f = 0; f < g.so; ++f) {
-        for (int k = 0; k < Kin; ++k) W2[(size_t)f * Kin + k] = W[(size_t)f * Kin + k];
-        B2[f] = Bv[f];
-        G2[f] = Wg[f];                                                                         // gate row 0
-        for (int k = 0; k < nf; ++k) G2[(size_t)(1 + k) * PF_S + f] = Wo[(size_t)k * g.so + f];
-    }
-    bg2[0] = bg[0];
-    for (int k = 0; k < nf; ++k) bg2[1 + k] = bo[k];
-    for (int c = 0; c < H; ++c) U2[(size_t)c * 16] = wu[(size_t)c * g.vo];
-    GvpSpec g2 = g;
-    g2.vo = 16; g2.so = PF_S;
-    const N16Raw rw{W2, B2, G2, bg2, h->raw[g.prefix + "Wh"].data, U2, g2};
-    pack_n16_raw(rw, N16_GEN, w, out, h->split_record ? &h->split_pending : nullptr);
+// Replaces the device buffer behind *slot with a copy of v (an empty v leaves the slot null).
+template <typename T>
+static hipError_t upload(T** slot, const std::vector<T>& v) {
+    if (*slot) { (void)hipFree(*slot); *slot = nullptr; }
+    if (v.empty()) return hipSuccess;
+    const hipError_t e = hipMalloc((void**)slot, v.size() * sizeof(T));
+    return e != hipSuccess ? e : hipMemcpy(*slot, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 // keep_ws: the inference workspace stays allocated (pf_set_pocket_batch re-carves it when the next batch fits: a
@@ -1112,8 +640,8 @@ static EncodeParams encode_params(const pf_handle* h, const float* t_scalar, flo
     ep.prot_h0 = h->d_prot_h0; ep.pharm_h = h->d_pharm_h; ep.gid = h->d_gid; ep.h_out = h_out;
     ep.t = t_scalar ? nullptr : h->d_t; ep.t_scalar = t_scalar ? *t_scalar : 0.f;
     for (int nt = 0; nt < 2; ++nt) {
-        ep.w[nt] = h->d_w + h->enc_w[nt]; ep.b[nt] = h->d_w + h->enc_b[nt];
-        ep.ln_w[nt] = h->d_w + h->enc_lw[nt]; ep.ln_b[nt] = h->d_w + h->enc_lb[nt];
+        ep.w[nt] = h->d_w + h->pk.enc_w[nt]; ep.b[nt] = h->d_w + h->pk.enc_b[nt];
+        ep.ln_w[nt] = h->d_w + h->pk.enc_lw[nt]; ep.ln_b[nt] = h->d_w + h->pk.enc_lb[nt];
     }
     return ep;
 }
@@ -1123,7 +651,7 @@ static HeadParams head_params(const pf_handle* h, float* eps_h, float* eps_x) {
     HeadParams hp{};
     hp.tiles = h->d_head_tiles; hp.ntiles = h->n_head_tiles; hp.node_base = h->Np;
     hp.gvps = h->d_gvp + h->head_base(); hp.n_gvps = c.n_noise_gvps;
-    hp.a_out = h->d_w + h->out_a; hp.b_out = h->d_w + h->out_b; hp.pharm_nf = c.pharm_nf; hp.eps_h = eps_h; hp.eps_x = eps_x;
+    hp.a_out = h->d_w + h->pk.out_a; hp.b_out = h->d_w + h->pk.out_b; hp.pharm_nf = c.pharm_nf; hp.eps_h = eps_h; hp.eps_x = eps_x;
     return hp;
 }
 // edge messages of a conv layer: tiles, geometry, GVP table, RBF, the row-group streams.  The caller's: h / v / msg rows, regions,
@@ -1136,7 +664,7 @@ static EdgeParams edge_params_base(const pf_handle* h, int layer, bool last, boo
     e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
     e.w = h->d_gvp + h->msg_base(layer, 0); e.n_gvps = c.n_message_gvps;
     rbf_params(c, e.rbf_mu, &e.rbf_inv_sigma);
-    for (int et = 0; et < 4; ++et) e.rg[et] = h->d_w + h->rg_msg[(size_t)layer * 4 + et];
+    for (int et = 0; et < 4; ++et) e.rg[et] = h->d_w + h->pk.rg_msg[(size_t)layer * 4 + et];
     return e;
 }
 // node update of a conv layer.  The caller's: msg rows, h / v in and out, grp / grp_pa, pp_slot 3 of a shared launch, the two-wave streams
@@ -1150,11 +678,11 @@ static NodeParams node_params_base(const pf_handle* h, int layer, bool last, boo
     n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
     n.n_upd = c.n_update_gvps;
     for (int nt = 0; nt < 2; ++nt) {
-        const size_t* lo = &h->ln_off[(size_t)(layer * 2 + nt) * 4];
+        const size_t* lo = &h->pk.ln_off[(size_t)(layer * 2 + nt) * 4];
         n.w[nt].ln1_w = h->d_w + lo[0]; n.w[nt].ln1_b = h->d_w + lo[1];
         n.w[nt].ln2_w = h->d_w + lo[2]; n.w[nt].ln2_b = h->d_w + lo[3];
         n.w[nt].upd = h->d_gvp + h->upd_base(layer, nt);
-        n.rg_upd[nt] = h->d_w + h->rg_upd[(size_t)layer * 2 + nt];
+        n.rg_upd[nt] = h->d_w + h->pk.rg_upd[(size_t)layer * 2 + nt];
     }
     return n;
 }
@@ -1214,13 +742,13 @@ static bool l0_hoist_ok(pf_handle* h) {
 static L0HoistParams l0_params(pf_handle* h) {
     const pf_config& c = h->cfg;
     L0HoistParams lp{};
-    lp.src = h->d_w + h->l0h_off; lp.l0c = h->d_l0c;
+    lp.src = h->d_w + h->pk.l0h_off; lp.l0c = h->d_l0c;
     lp.esrc = h->d_esrc; lp.edst = h->d_edst; lp.xn = h->d_xn; lp.Epp = (int)h->Epp; lp.zs = h->d_zs;
     float mu[PF_R];
     rbf_params(c, mu, &lp.rbf_inv_sigma);
     lp.rbf_mu0 = mu[0]; lp.rbf_mu_step = (mu[PF_R - 1] - mu[0]) * (1.0f / (float)(PF_R - 1));
-    lp.enc_w = h->d_w + h->enc_w[0]; lp.enc_b = h->d_w + h->enc_b[0];
-    lp.enc_lw = h->d_w + h->enc_lw[0]; lp.enc_lb = h->d_w + h->enc_lb[0];
+    lp.enc_w = h->d_w + h->pk.enc_w[0]; lp.enc_b = h->d_w + h->pk.enc_b[0];
+    lp.enc_lw = h->d_w + h->pk.enc_lw[0]; lp.enc_lb = h->d_w + h->pk.enc_lb[0];
     lp.rec_nf = c.rec_nf;
     return lp;
 }
@@ -1257,9 +785,49 @@ static void l0_prepare_t(pf_handle* h, const float* tv, int n, hipStream_t s) {
 // the n16 streams after pf_set_flat_params left them behind (see pf_handle::n16_begin)
 static void n16_refresh(pf_handle* h, hipStream_t s) {
     if (!h->n16_stale) return;
-    pfk_gather_weights(h->d_flat, h->d_map + h->n16_begin, h->n_packed - h->n16_begin, h->d_w + h->n16_begin, s);
+    pfk_gather_weights(h->d_flat, h->d_map + h->pk.n16_begin, h->n_packed - h->pk.n16_begin, h->d_w + h->pk.n16_begin, s);
     if (h->n_split_tab) pfk_n16_split_words(h->d_flat, h->d_split_tab, h->n_split_tab, h->d_w, s);     // (-DN16_SPLIT: the bf16-plane words)
     h->n16_stale = false;
+}
+
+// The WideGvp table of a handle that was not created on the width-generic family (the specialised widths without PFDYN_WIDE), for
+// its wide training leg: Wh, Wu and the biases point into the flat parameter vector, which stores them in the layout the kernels
+// read; to_feats_out and the gate Linear of every GVP sit in fragment order in d_wpk, written from the flat vector by k_wide_pack
+// (ensure_wide_pack).  A handle of the family itself has the table from pf_commit_weights and the gather map keeps it fresh.
+static int ensure_wide_pack(pf_handle* h, hipStream_t s) {
+    if (h->wide) return PF_OK;
+    const pf_config& c = h->cfg;
+    if (!h->d_wgvp) {
+        std::vector<WideGvp> tab;
+        std::vector<WidePackJob> jobs;
+        size_t total = 0;
+        auto frag = [](int n_out, int K) { return (size_t)((n_out + 15) / 16) * ((K + 3) / 4) * 64; };
+        for_each_gvp(c, [&](const GvpSpec& g) {
+            const int H = std::max(g.vi, g.vo);
+            WideGvp w{};                    // (wm, wg: below, once d_wpk exists)
+            w.wh = h->d_flat + h->flat_offset(g.prefix + "Wh"); w.wu = h->d_flat + h->flat_offset(g.prefix + "Wu");
+            w.bm = h->d_flat + h->flat_offset(g.prefix + "to_feats_out.0.bias"); w.bg = h->d_flat + h->flat_offset(g.prefix + "scalar_to_vector_gates.bias");
+            w.vi = g.vi; w.vo = g.vo; w.si = g.si; w.so = g.so;
+            jobs.push_back({(int)h->flat_offset(g.prefix + "to_feats_out.0.weight"), g.so, g.si + H, (int)total});
+            total += frag(g.so, g.si + H);
+            jobs.push_back({(int)h->flat_offset(g.prefix + "scalar_to_vector_gates.weight"), g.vo, g.so, (int)total});
+            total += frag(g.vo, g.so);
+            tab.push_back(w);
+        });
+        if (total >= (size_t)1 << 31) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_family: the model is too large for the width-generic packing");
+        if (h->d_wpk) { (void)hipFree(h->d_wpk); h->d_wpk = nullptr; }
+        PF_HIP(h, hipMalloc((void**)&h->d_wpk, std::max<size_t>(total, 1) * sizeof(float)));
+        PF_HIP(h, upload(&h->d_wpk_jobs, jobs));
+        h->n_wpk_jobs = (int)jobs.size();
+        for (size_t i = 0; i < tab.size(); ++i) { tab[i].wm = h->d_wpk + jobs[2 * i].dst; tab[i].wg = h->d_wpk + jobs[2 * i + 1].dst; }
+        PF_HIP(h, upload(&h->d_wgvp, tab));
+        h->wpk_version = ~0ull;
+    }
+    if (h->wpk_version != h->w_version) {
+        pfk_wide_pack(h->d_flat, h->d_wpk_jobs, h->n_wpk_jobs, h->d_wpk, s);
+        h->wpk_version = h->w_version;
+    }
+    return PF_OK;
 }
 
 // One dynamics call on the width-generic family (pf_wide.hip): encoders, the edge build, per conv layer one message launch and
@@ -1275,14 +843,16 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
     if (!train && h->share_check == 2)
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: the claim made for this batch is false -- a graph differs from its representative in "
                                "coordinates or features (compared on the device); bind the batch again without the claim");
+    const int rc = ensure_wide_pack(h, s);
+    if (rc) return rc;
     const int S = c.n_hidden_scalars, V = c.vector_size;
     WideEncParams ep{};
     ep.Np = h->Np; ep.Nf = h->Nf; ep.S = S; ep.rec_nf = c.rec_nf; ep.pharm_nf = c.pharm_nf;
     ep.prot_h0 = h->d_prot_h0; ep.pharm_h = h->d_pharm_h;
     ep.t = t_scalar ? nullptr : h->d_t; ep.t_scalar = t_scalar ? *t_scalar : 0.f; ep.gid = h->d_gid;
     for (int nt = 0; nt < 2; ++nt) {
-        ep.w[nt] = h->d_w + h->enc_w[nt]; ep.b[nt] = h->d_w + h->enc_b[nt];
-        ep.ln_w[nt] = h->d_w + h->enc_lw[nt]; ep.ln_b[nt] = h->d_w + h->enc_lb[nt];
+        ep.w[nt] = h->d_w + h->pk.enc_w[nt]; ep.b[nt] = h->d_w + h->pk.enc_b[nt];
+        ep.ln_w[nt] = h->d_w + h->pk.enc_lw[nt]; ep.ln_b[nt] = h->d_w + h->pk.enc_lb[nt];
     }
     float* const* st_h = train ? h->wt.st_h : h->d_h;
     float* const* st_v = train ? h->wt.st_v : h->d_v;
@@ -1322,7 +892,7 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         n.h_out = st_h[cur ^ 1]; n.v_out = st_v[cur ^ 1];
         n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
         for (int nt = 0; nt < 2; ++nt) {
-            const size_t* lo = &h->ln_off[(size_t)(l * 2 + nt) * 4];
+            const size_t* lo = &h->pk.ln_off[(size_t)(l * 2 + nt) * 4];
             n.ln1_w[nt] = h->d_w + lo[0]; n.ln1_b[nt] = h->d_w + lo[1];
             n.ln2_w[nt] = h->d_w + lo[2]; n.ln2_b[nt] = h->d_w + lo[3];
             n.upd[nt] = h->d_wgvp + h->upd_base(l, nt);
@@ -1339,11 +909,9 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         }
         if (last) {             // the last layer's node tiles are the centers: the noise head follows in the same launch
             n.head = h->d_wgvp + h->head_base(); n.n_head = c.n_noise_gvps;
-            if (h->wide) { n.w_out = h->d_w + h->wide_out_w; n.b_out = h->d_w + h->wide_out_b; }
-            else {              // (a handle of the specialised widths on the wide training leg: to_scalar_output as the flat vector stores it)
-                n.w_out = h->d_flat + h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.weight");
-                n.b_out = h->d_flat + h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.bias");
-            }
+            // (a handle of the specialised widths on the wide training leg: to_scalar_output as the flat vector stores it)
+            n.w_out = h->wide ? h->d_w + h->pk.wide_out_w : h->d_flat + h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.weight");
+            n.b_out = h->wide ? h->d_w + h->pk.wide_out_b : h->d_flat + h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.bias");
             n.pharm_nf = c.pharm_nf; n.node_base = h->Np;
             n.eps_h = eps_h; n.eps_x = eps_x;
             ProfScope ps(h, pf_handle::K_HEAD, s); pfk_wide_node(&n, train ? 1 : 0, s);
@@ -1400,7 +968,7 @@ static int dyn_prologue(DynCall& dc) {
         PreParams pp{};
         pp.Np = h->Np; pp.rec_nf = c.rec_nf; pp.nke = (c.rec_nf + 2) / 2;
         pp.prot_h0 = h->d_prot_h0; pp.t = dc.ep.t; pp.t_scalar = dc.ep.t_scalar; pp.gid = h->d_gid;
-        pp.a_enc = h->d_w + h->enc_a; pp.b_enc = h->d_w + h->enc_bf; pp.ln_w = h->d_w + h->enc_lw[0]; pp.ln_b = h->d_w + h->enc_lb[0];
+        pp.a_enc = h->d_w + h->pk.enc_a; pp.b_enc = h->d_w + h->pk.enc_bf; pp.ln_w = h->d_w + h->pk.enc_lw[0]; pp.ln_b = h->d_w + h->pk.enc_lb[0];
         pp.pre_w = h->h_gvp[h->msg_base(0, ET_PP)]; pp.pre_nks = 64 + c.rbf_dim / 2 + 9;
         pp.h_out = dc.ep.h_out; pp.pre_out = h->d_pre;
         pfk_encode_build_pre(&dc.ep, &bp, &pp, s); dc.pre_ready = true;
@@ -1412,7 +980,7 @@ static void dyn_hoist_prepare(DynCall& dc) {
     pf_handle* h = dc.h; hipStream_t s = dc.s; const pf_config& c = h->cfg;
     dc.hoist = !dc.train && dc.enc_fly && l0_hoist_ok(h);
     // the n16 form serves the latency regime: batches whose pruned conv-layer launch has few items per compute unit
-    dc.n16_batch = (long)(prune_layer(h) >= 0 ? h->n_edge_tiles_act : h->n_edge_tiles) * 32 <= h->pol.n16_rows_max && !h->n16_msg.empty();
+    dc.n16_batch = (long)(prune_layer(h) >= 0 ? h->n_edge_tiles_act : h->n_edge_tiles) * 32 <= h->pol.n16_rows_max && !h->pk.n16_msg.empty();
     dc.n16_l0 = dc.hoist && (h->pol.n16_mask & 2) && dc.n16_batch;      // layer 0 on the n16 kernels: no zs
     if (!dc.hoist) return;
     if (!dc.n16_l0) l0_ensure_static(h, s);
@@ -1432,8 +1000,8 @@ static void dyn_hoist_prepare(DynCall& dc) {
 static void edge_n16_form(DynCall& dc, int l) {
     pf_handle* h = dc.h; EdgeParams& e = dc.e; const pf_config& c = h->cfg; const bool shared = dc.shared;
     for (int et = 0; et < 4; ++et) {
-        e.n16[et] = h->d_w + (l > 0 ? h->n16_msg[(size_t)l * 4 + et] : h->n16_l0[et]);
-        e.n16_stride[et] = (int)(l > 0 ? h->n16_msg_stride : h->n16_l0_stride[et]);
+        e.n16[et] = h->d_w + (l > 0 ? h->pk.n16_msg[(size_t)l * 4 + et] : h->pk.n16_l0[et]);
+        e.n16_stride[et] = (int)(l > 0 ? h->pk.n16_msg_stride : h->pk.n16_l0_stride[et]);
         e.ptab16_off[et] = et == ET_PP ? c.rec_nf * PF_S : (et == ET_PF ? 2 * c.rec_nf * PF_S : -1);
     }
     if (l == 0) { e.zs = nullptr; dc.rgp = 4; h->last_hoist = 16; }      // (ptab / ptype / l0_gid were set by edge_launch)
@@ -1444,8 +1012,8 @@ static void edge_n16_form(DynCall& dc, int l) {
         // "pa" regions whose rows were computed ahead (k_n16_pa_spec) and still apply are skipped
         if (dc.spec_have && pa_ahead_ok(h, e, shared)) { e.pa_skip = h->d_pa_same; h->last_spec = 1; }
     }
-    if (l == 0 && dc.cen_have && h->n16_l0h[ET_FF] != 0) {              // ff / fp items start from the center hoist's tables (kind M0H)
-        for (int et : {(int)ET_FF, (int)ET_FP}) { e.n16[et] = h->d_w + h->n16_l0h[et]; e.n16_stride[et] = (int)h->n16_l0h_stride[et]; }
+    if (l == 0 && dc.cen_have && h->pk.n16_l0h[ET_FF] != 0) {              // ff / fp items start from the center hoist's tables (kind M0H)
+        for (int et : {(int)ET_FF, (int)ET_FP}) { e.n16[et] = h->d_w + h->pk.n16_l0h[et]; e.n16_stride[et] = (int)h->pk.n16_l0h_stride[et]; }
         e.pcen = h->d_cen_p; e.pcen_nf = h->Nf; h->last_cen = true;
     }
     e.ngroups_sel = region_groups(h, shared, 0, e.nreg, 16);
@@ -1513,14 +1081,14 @@ static void edge_launch(DynCall& dc, int l) {
     if (n16e) edge_n16_form(dc, l);
     h->last_family.resize(c.n_convs);
     h->last_family[l] = rg ? 4 * rg : ((!train && e.ntiles <= ((last || pruned) ? std::max(h->pol.coop_edge_max, h->pol.coop2_edge_max) : std::max(h->pol.coop_edge_max, h->pol.coop2_dense_max))) ? 128 : 32);
-    for (int et = 0; et < 4; ++et) { e.rgs[et] = h->d_w + h->rgs_msg[(size_t)l * 4 + et]; e.rgs_stride = (int)h->rgs_msg_stride; }
+    for (int et = 0; et < 4; ++et) { e.rgs[et] = h->d_w + h->pk.rgs_msg[(size_t)l * 4 + et]; e.rgs_stride = (int)h->pk.rgs_msg_stride; }
     const int esplit = (rg == 1 && e.ntiles * 8 <= h->pol.rg_split_max && !e.zs) ? 1 : 0;    // fewer groups than SIMDs: latency-bound
     const int pc = edge_prof_class(last, c.n_convs);
     if (n16e && dc.fuse_l0node && l == 1) {         // the fused launch: what conv layer 0's node update left in fz (fused_take_node) + its own fields
         FusedParams& fz = dc.fz;
-        fz.chain[ET_FF] = h->d_w + h->n16_fused[0]; fz.chain_stride[ET_FF] = (int)h->n16_fused_stride[0];
-        fz.chain[ET_PF] = h->d_w + h->n16_fused[1]; fz.chain_stride[ET_PF] = (int)h->n16_fused_stride[1];
-        fz.upd_pharm = h->d_w + h->n16_upd[(size_t)0 * 2 + 1]; fz.upd_pharm_stride = (int)h->n16_upd_stride;
+        fz.chain[ET_FF] = h->d_w + h->pk.n16_fused[0]; fz.chain_stride[ET_FF] = (int)h->pk.n16_fused_stride[0];
+        fz.chain[ET_PF] = h->d_w + h->pk.n16_fused[1]; fz.chain_stride[ET_PF] = (int)h->pk.n16_fused_stride[1];
+        fz.upd_pharm = h->d_w + h->pk.n16_upd[(size_t)0 * 2 + 1]; fz.upd_pharm_stride = (int)h->pk.n16_upd_stride;
         fz.htab = dc.l0_ptab + (size_t)3 * c.rec_nf * PF_S; fz.htab_gstride = dc.l0_gstride; fz.ptype = h->d_ptype; fz.hcen = h->last_cen ? h->d_cen_h : nullptr;
         fz.h_out = h->d_h[dc.cur]; fz.v_out = h->d_v[dc.cur];          // (cur was flipped behind conv layer 0: its output side)
         fz.pharm_ptr = h->d_pharm_ptr; fz.Np = h->Np; fz.n_edge_items = e.ngroups_sel;
@@ -1575,7 +1143,7 @@ static void tail_launch(DynCall& dc, const NodeParams& n, int form) {
         tp.msg_s = n.msg_s; tp.msg_v = n.msg_v; tp.zero_row = n.zero_row; tp.grp = n.grp;
         tp.gid = n.gid; tp.gnorm = n.gnorm; tp.B = n.B; tp.norm_mode = n.norm_mode; tp.norm_value = n.norm_value;
         tp.ln1_w = n.w[1].ln1_w; tp.ln1_b = n.w[1].ln1_b; tp.ln2_w = n.w[1].ln2_w; tp.ln2_b = n.w[1].ln2_b;
-        tp.n_upd = n.n_upd; tp.n_head = c.n_noise_gvps; tp.chain = h->d_w + h->n16_tail; tp.chain_stride = (int)h->n16_tail_stride;
+        tp.n_upd = n.n_upd; tp.n_head = c.n_noise_gvps; tp.chain = h->d_w + h->pk.n16_tail; tp.chain_stride = (int)h->pk.n16_tail_stride;
         tp.pharm_nf = c.pharm_nf; tp.eps_h = dc.eps_h; tp.eps_x = dc.eps_x;
     }
     const bool sn = share_next(h);
@@ -1589,7 +1157,7 @@ static void tail_launch(DynCall& dc, const NodeParams& n, int form) {
 // features before the update must be in a snapshot (pf_sample_begin / the previous step left it).  NaN: no hoist
 static float cen_hoist_plan(DynCall& dc) {
     pf_handle* h = dc.h;
-    if (!(h->cen_hoist && dc.t_scalar && !h->t_plan.empty() && h->last_hoist == 16 && h->l0c_off != 0 && h->n16_l0h[ET_FF] != 0 &&
+    if (!(h->cen_hoist && dc.t_scalar && !h->t_plan.empty() && h->last_hoist == 16 && h->pk.l0c_off != 0 && h->pk.n16_l0h[ET_FF] != 0 &&
           h->snap_cur >= 0 && dc.step->h_snap_out != nullptr && h->d_xchg2 && dc.fuse_l0node)) return NAN;
     return planned_next_t(h, *dc.t_scalar, &h->plan_pos);
 }
@@ -1598,8 +1166,8 @@ static void cen_hoist_params(DynCall& dc, float t_next, CenHoistParams& cp, Head
     pf_handle* h = dc.h; const StepParams* step = dc.step;
     cp.on = 1; cp.Nf = h->Nf; cp.nf = h->cfg.pharm_nf; cp.t_next = t_next; cp.pharm_h = h->d_snap[h->snap_cur]; cp.noise = step->noise;
     cp.a_ts = step->a_ts; cp.var = step->var; cp.sigma = step->sigma; cp.ep_zt = step->ep_zt; cp.ep_pred = step->ep_pred; cp.ep_feat = step->ep_feat;
-    cp.enc_w = h->d_w + h->enc_w[1]; cp.enc_b = h->d_w + h->enc_b[1]; cp.enc_lw = h->d_w + h->enc_lw[1]; cp.enc_lb = h->d_w + h->enc_lb[1];
-    cp.blk = h->d_w + h->l0c_off; cp.cen_h = h->d_cen_h; cp.cen_p = h->d_cen_p; cp.xchg2 = hp.xchg2 = h->d_xchg2;
+    cp.enc_w = h->d_w + h->pk.enc_w[1]; cp.enc_b = h->d_w + h->pk.enc_b[1]; cp.enc_lw = h->d_w + h->pk.enc_lw[1]; cp.enc_lb = h->d_w + h->pk.enc_lb[1];
+    cp.blk = h->d_w + h->pk.l0c_off; cp.cen_h = h->d_cen_h; cp.cen_p = h->d_cen_p; cp.xchg2 = hp.xchg2 = h->d_xchg2;
     h->cen_valid = true; h->cen_t = t_next; h->cen_wver = h->w_version;
 }
 // the NEXT call's "pa" messages, ahead of time, as workgroups of the merged launch (BuildParams::pa_same): conv layer 0's rows of this call have been
@@ -1613,7 +1181,7 @@ static int pa_ahead_plan(DynCall& dc, EdgeParams& es, EncodeParams& ees) {
     uint32_t bits; memcpy(&bits, &tn, 4);
     es = h->e0; es.pa_skip = nullptr; es.pcen = nullptr;
     es.ptab = h->d_ptab + (size_t)h->ptab_slot[bits] * L0_NTAB * c.rec_nf * PF_S;
-    for (int et = 0; et < 4; ++et) { es.n16[et] = h->d_w + h->n16_l0[et]; es.n16_stride[et] = (int)h->n16_l0_stride[et]; }
+    for (int et = 0; et < 4; ++et) { es.n16[et] = h->d_w + h->pk.n16_l0[et]; es.n16_stride[et] = (int)h->pk.n16_l0_stride[et]; }
     ees = h->ep0; ees.t_scalar = tn;
     h->spec_valid = true; h->spec_t = tn; h->spec_wver = h->w_version;
     es.pa_serial = h->spec_serial = ++h->pa_serial; es.pa_gstamp = h->d_pa_gstamp;
@@ -1656,7 +1224,7 @@ static void node_launch(DynCall& dc, int l) {
     if (train) { n.drop_thr = h->t_common.drop_thr; n.drop_scale = h->t_common.drop_scale; n.seed = h->t_common.seed; n.layer = l; n.mask_override = h->t_common.mask_override; }
     n.grp = dc.rg ? 4 * dc.rg : 32; n.grp_pa = dc.rgp ? 4 * dc.rgp : n.grp;
     if (train) { h->t_grp.resize(c.n_convs); h->t_grp[l] = n.grp; h->t_node_saved.resize(c.n_convs); h->t_node_saved[l] = 0; }
-    for (int nt = 0; nt < 2; ++nt) { n.rgs_upd[nt] = h->d_w + h->rgs_upd[(size_t)l * 2 + nt]; n.rgs_stride[nt] = (int)h->rgs_upd_stride[(size_t)l * 2 + nt]; }
+    for (int nt = 0; nt < 2; ++nt) { n.rgs_upd[nt] = h->d_w + h->pk.rgs_upd[(size_t)l * 2 + nt]; n.rgs_stride[nt] = (int)h->pk.rgs_upd_stride[(size_t)l * 2 + nt]; }
     const EncodeParams* enc = dc.enc_fly ? &dc.ep : nullptr;
     if (dc.fuse_l0node && l == 0) fused_take_node(dc, n);
     else if (dc.rg) {
@@ -1664,7 +1232,7 @@ static void node_launch(DynCall& dc, int l) {
         const bool fuse = dc.last && !train && h->fuse_head && h->n_head_tiles == n.ntiles;
         const int nsplit = (!train && rgn == 1 && n.ntiles * 8 <= (fuse ? h->pol.rg_split_max_head : h->pol.rg_split_max_node)) ? 1 : 0;
         const bool tail = fuse && dc.step != nullptr && l > 0 && (h->pol.n16_mask & 8) && h->B <= h->pol.tail_graphs_max && dc.enc_fly && step_build_fast_ok(h);
-        if (tail) tail_launch(dc, n, (h->pol.tail_form == 16 && h->n16_tail != 0) ? 16 : 4);
+        if (tail) tail_launch(dc, n, (h->pol.tail_form == 16 && h->pk.n16_tail != 0) ? 16 : 4);
         else if (fuse) {
             // few two-wave items: confined to node_xcds XCDs when they fit one per compute unit there (32 CUs per XCD)
             if (nsplit && h->pol.node_xcds > 0 && n.ntiles * 8 <= 32 * h->pol.node_xcds) n.xcd_n = h->pol.node_xcds;
@@ -1703,13 +1271,13 @@ static void head_launch(DynCall& dc) {
     HeadParams hp = head_params(h, dc.eps_h, dc.eps_x);
     hp.h = train ? h->t_H[c.n_convs] : h->d_h[dc.cur]; hp.v = train ? h->t_V[c.n_convs] : h->d_v[dc.cur];
     if (train) h->t_head_saved = false;
-    if (!dc.head_done && train && h->train_rg_head && !h->rg_msg.empty() && h->Nf > 0) {
+    if (!dc.head_done && train && h->train_rg_head && !h->pk.rg_msg.empty() && h->Nf > 0) {
         // training forward: the head chain on the row-group code (4 rows per wave), which also leaves every level's pre-activations,
         // gate pre-activations and gated vectors for k_bwd_head (pharm rows are the contiguous rows [Np, Np + Nf))
         UnitParams up{};
         up.s_in = hp.h + (size_t)h->Np * PF_S; up.v_in = hp.v + (size_t)h->Np * 48; up.s_out = dc.eps_h; up.v_out = dc.eps_x;
         up.n = h->Nf; up.kind = 3; up.n_gvps = c.n_noise_gvps; up.pharm_nf = c.pharm_nf;
-        up.stream = h->d_w + h->rg_upd[(size_t)(c.n_convs - 1) * 2 + 1]; up.skip_gvps = c.n_update_gvps;
+        up.stream = h->d_w + h->pk.rg_upd[(size_t)(c.n_convs - 1) * 2 + 1]; up.skip_gvps = c.n_update_gvps;
         up.sv_z = h->t_hsv_z; up.sv_g = h->t_hsv_g; up.sv_v = h->t_hsv_v; up.sv_stride = (size_t)h->Nf;
         { ProfScope ps(h, pf_handle::K_HEAD, s); pfk_rg_unit(&up, s); }
         h->t_head_saved = true; dc.head_done = true;
@@ -1740,7 +1308,7 @@ static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s,
     // fused launch (pf_n16.hip: k_n16_fused): with two conv layers, receptive-field pruning and kNN pf edges the rows conv layer 0's node update produces are
     // exactly the sources of the last layer's edges (+ the centers): every edge item of the last layer updates its own source rows first, and the node launch of conv layer 0 disappears
     dc.fuse_l0node = !train && dc.n16_batch && (long)h->n_edge_tiles_act * 32 <= h->pol.n16_fuse_rows_max && (h->pol.n16_mask & 4) && (h->pol.n16_mask & 1) && dc.hoist && c.n_convs == 2 && prune_layer(h) == 0 && c.pf_k > 0 &&
-                     c.n_update_gvps >= 1 && h->rg_compact && 2 * h->B <= 1024 && h->d_msg_s2 != nullptr && h->n16_fused[0] != 0;
+                     c.n_update_gvps >= 1 && h->rg_compact && 2 * h->B <= 1024 && h->d_msg_s2 != nullptr && h->pk.n16_fused[0] != 0;
     for (int l = 0; l < c.n_convs; ++l, dc.cur ^= 1) { edge_launch(dc, l); node_launch(dc, l); }
     head_launch(dc);
     h->edges_built = h->tail_done;          // whoever moves the coordinates next decides (pf_denoise_step rebuilds; the tail and merged launches have)
@@ -1772,6 +1340,43 @@ static int check_ready(pf_handle* h, bool need_batch) {
 }  // namespace
 
 // =================================================================================================
+// class of every parameter tensor: the kernel that differentiates it.  The gradient path numbers its classes for n_convs <= 4:
+// the list ends in front of the first tensor of a fifth conv layer (pf_commit_weights: n_tseg = -1, no gradient path)
+typedef std::vector<std::pair<std::string, std::pair<size_t, size_t>>> FlatLayout;     // name -> (offset, numel)
+static int tensor_classes(pf_handle* h, const FlatLayout& layout, std::vector<TensorSeg>& segs) {
+    const pf_config& c = h->cfg;
+    for (const auto& kv : layout) {
+        const std::string& k = kv.first;
+        TensorSeg sg{(int)kv.second.first, (int)(kv.second.first + kv.second.second), PFT_CLS_NONE, 0};
+        if (kv.second.second == 0) sg.cls = PFT_CLS_NONE;
+        else if (k.find("_encoder.") != std::string::npos) sg.cls = PFT_CLS_ENC;
+        else if (k.find("noise_predictor.noise_predictor.") != std::string::npos) sg.cls = PFT_CLS_HEAD;
+        else {
+            int layer = -1;
+            for (int l = 0; l < c.n_convs; ++l)
+                if (k.compare(0, conv_prefix(l).size(), conv_prefix(l)) == 0) layer = l;
+            if (layer < 0) PF_FAIL(h, PF_ERR_STATE, "internal: parameter %s has no gradient class", k.c_str());
+            if (layer >= 4) break;
+            sg.cls = PFT_CLS_NODE + layer;
+            for (int et = 0; et < 4; ++et)
+                if (k.find(std::string("edge_message_fns.") + kEtKey[et] + ".") != std::string::npos) sg.cls = PFT_CLS_MSG + layer * 4 + et;
+        }
+        segs.push_back(sg);
+    }
+    return PF_OK;
+}
+
+// flat range of the encoders' parameters: one contiguous run (the first tensors of the state dict)
+static int encoder_range(pf_handle* h, const std::vector<TensorSeg>& segs, int& begin, int& n) {
+    int lo = 0x7fffffff, hi = 0, tot = 0;
+    for (const TensorSeg& sg : segs)
+        if (sg.cls == PFT_CLS_ENC) { lo = std::min(lo, sg.begin); hi = std::max(hi, sg.end); tot += sg.end - sg.begin; }
+    if (tot == 0) { lo = hi = 0; }
+    if (hi - lo != tot) PF_FAIL(h, PF_ERR_STATE, "internal: the encoders' parameters are not contiguous in the flat layout");
+    begin = lo; n = hi - lo;
+    return PF_OK;
+}
+
 extern "C" {
 
 const char* pf_version(void) { return "libpfdyn 0.1 (gfx950, fp32 MFMA)"; }
@@ -1817,20 +1422,12 @@ int pf_create(const pf_config* cfg, pf_handle** out) {
 void pf_destroy(pf_handle* h) {
     if (!h) return;
     free_ws(h);
-    if (h->d_w) (void)hipFree(h->d_w);
-    if (h->d_gvp) (void)hipFree(h->d_gvp);
-    if (h->d_wgvp) (void)hipFree(h->d_wgvp);
-    if (h->d_wpk) (void)hipFree(h->d_wpk);
-    if (h->d_wpk_jobs) (void)hipFree(h->d_wpk_jobs);
-    if (h->d_flat) (void)hipFree(h->d_flat);
-    if (h->d_wpack) (void)hipFree(h->d_wpack);
+    for (void* p : {(void*)h->d_w, (void*)h->d_gvp, (void*)h->d_wgvp, (void*)h->d_wpk, (void*)h->d_wpk_jobs, (void*)h->d_flat, (void*)h->d_wpack,
+                    (void*)h->d_tseg, (void*)h->d_gvpt, (void*)h->d_map, (void*)h->d_split_tab})
+        if (p) (void)hipFree(p);             // what pf_commit_weights and ensure_wide_pack allocated
     if (h->d_xstat) (void)hipFree(h->d_xstat);
     if (h->d_pa_chk) (void)hipFree(h->d_pa_chk);
     if (h->xstat_host) (void)hipHostFree(h->xstat_host);
-    if (h->d_tseg) (void)hipFree(h->d_tseg);
-    if (h->d_gvpt) (void)hipFree(h->d_gvpt);
-    if (h->d_map) (void)hipFree(h->d_map);
-    if (h->d_split_tab) (void)hipFree(h->d_split_tab);
     if (h->d_l0c) (void)hipFree(h->d_l0c);
     if (h->d_ptab) (void)hipFree(h->d_ptab);
     if (h->d_pin) (void)hipFree(h->d_pin);
@@ -1866,417 +1463,83 @@ int pf_set_weight(pf_handle* h, const char* name, const float* host_data, int32_
 int pf_commit_weights(pf_handle* h) {
     if (!h) return PF_ERR_ARG;
     const pf_config& c = h->cfg;
-    const auto exp = expected_tensors(c);
-    for (const auto& kv : exp) {
-        auto it = h->raw.find(kv.first);
-        if (it == h->raw.end()) PF_FAIL(h, PF_ERR_WEIGHT, "missing weight tensor %s", kv.first.c_str());
-        if (it->second.shape != kv.second) PF_FAIL(h, PF_ERR_WEIGHT, "wrong shape for %s", kv.first.c_str());
+    // ---- on the host: everything that can fail without the device runs before the first old buffer is freed
+    PackedModel pm;
+    int rc = pack_model(c, h->raw, h->spec, h->wide, pm, h->err);
+    if (rc) return rc;
+    // gradient path: the parameters once more as one flat vector in state-dict order
+    std::vector<float> flat;
+    FlatLayout layout;
+    for (const auto& kv : expected_tensors(c)) {
+        const RawTensor& t = h->raw[kv.first];
+        layout.push_back({kv.first, {flat.size(), t.data.size()}});
+        flat.insert(flat.end(), t.data.begin(), t.data.end());
     }
-    if (h->raw.size() != exp.size()) {
-        for (const auto& kv : h->raw) {
-            bool found = false;
-            for (const auto& e : exp) if (e.first == kv.first) { found = true; break; }
-            if (!found) PF_FAIL(h, PF_ERR_WEIGHT, "unexpected weight tensor %s", kv.first.c_str());
-        }
-    }
+    std::vector<TensorSeg> segs;
+    int enc_begin = 0, enc_n = 0;
+    if ((rc = tensor_classes(h, layout, segs)) != PF_OK || (rc = encoder_range(h, segs, enc_begin, enc_n)) != PF_OK) return rc;
+    // ---- the handle changes from here on.  A HIP call that fails leaves it uncommitted: some of its tables are then replaced, others not
+    h->committed = false;
+    h->flat_layout.swap(layout);
+    h->flat_index.clear(); h->flat_index_ok = false; h->edge_fx.clear();
+    h->enc_begin = enc_begin; h->enc_n = enc_n;
+    h->pk = std::move(pm.lay);
+    h->n_msg_tot = c.n_convs * 4 * c.n_message_gvps;
+    h->n_upd_tot = c.n_convs * 2 * c.n_update_gvps;
+    h->n_packed = pm.w.size();
+    h->n_split_tab = pm.split_tab.size();
+    PF_HIP(h, upload(&h->d_w, pm.w));
+    PF_HIP(h, upload(&h->d_map, pm.map));
+    PF_HIP(h, upload(&h->d_split_tab, pm.split_tab));
     h->h_gvp.clear();
-    std::vector<GvpOff> offs;
-    // the packing is pure data movement (copies and zero padding), so running it a second time on tensors whose VALUES
-    // are their own flat index + 1 yields, per packed element, where it comes from: the gather map that lets
-    // pf_set_flat_params refresh the packed weights on the device after an optimiser step
-    auto pack_all = [&]() {
-        h->h_w.clear();
-        offs.clear();
-        h->wide_off.clear();
-        h->n_msg_tot = c.n_convs * 4 * c.n_message_gvps;
-        h->n_upd_tot = c.n_convs * 2 * c.n_update_gvps;
-        // every GVP in the GvpW table's order (message, update, head), the kernels' view of each
-        auto each_gvp = [&](auto fn) {
-            for (int l = 0; l < c.n_convs; ++l)
-                for (int et = 0; et < 4; ++et)
-                    for (int j = 0; j < c.n_message_gvps; ++j) fn(msg_spec(c, l, et, j));
-            for (int l = 0; l < c.n_convs; ++l)
-                for (int nt = 0; nt < 2; ++nt)
-                    for (int j = 0; j < c.n_update_gvps; ++j) fn(upd_spec(c, l, nt, j));
-            for (int k = 0; k < c.n_noise_gvps; ++k) fn(head_spec(c, k));
-        };
-        if (h->wide) {          // width-generic family: its GVPs and to_scalar_output as stored
-            each_gvp([&](const GvpSpec& g) { pack_wide_gvp(h, g, h->wide_off); });
-            h->wide_out_w = push(h->h_w, h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.weight"].data);
-            h->wide_out_b = push(h->h_w, h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.bias"].data);
-        }
-        if (h->spec) each_gvp([&](const GvpSpec& g) { offs.push_back(pack_gvp(h, g)); });
-        for (int nt = 0; nt < 2; ++nt) {
-            const std::string p = std::string("dynamics.") + kNtKey[nt] + "_encoder.";
-            {   // encoder weight transposed to [nf+1][128]: coalesced loads of one input's column
-                const RawTensor& W = h->raw[p + "0.weight"];
-                const int K = (int)W.shape[1], S = (int)W.shape[0];
-                std::vector<float> wt((size_t)K * S);
-                for (int f = 0; f < S; ++f) for (int k = 0; k < K; ++k) wt[(size_t)k * S + f] = W.data[(size_t)f * K + k];
-                h->enc_w[nt] = push(h->h_w, wt);
-            }
-            h->enc_b[nt] = push(h->h_w, h->raw[p + "0.bias"].data);
-            h->enc_lw[nt] = push(h->h_w, h->raw[p + "2.weight"].data);
-            h->enc_lb[nt] = push(h->h_w, h->raw[p + "2.bias"].data);
-        }
-        if (h->spec) {   // protein encoder Linear [128][rec_nf+1] as A fragments [tile][k-step][lane]; k-step t, half hl <-> input 2t+hl
-            const RawTensor& W = h->raw["dynamics.prot_encoder.0.weight"];
-            const RawTensor& Bv = h->raw["dynamics.prot_encoder.0.bias"];
-            const int K = c.rec_nf + 1, nke = (K + 1) / 2;
-            std::vector<float> a((size_t)4 * nke * 64, 0.f), bf(128);
-            for (int mo = 0; mo < 4; ++mo)
-                for (int t = 0; t < nke; ++t)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int i = lane & 31, hl = lane >> 5, k = 2 * t + hl;
-                        a[((size_t)mo * nke + t) * 64 + lane] = k < K ? W.data[(size_t)(32 * mo + i) * K + k] : 0.f;
-                    }
-            for (int hl = 0; hl < 2; ++hl)
-                for (int mo = 0; mo < 4; ++mo)
-                    for (int r = 0; r < 16; ++r) bf[(size_t)hl * 64 + mo * 16 + r] = Bv.data[32 * mo + rho(r, hl)];
-            h->enc_a = push(h->h_w, a);
-            h->enc_bf = push(h->h_w, bf);
-        }
-        h->ln_off.assign((size_t)c.n_convs * 2 * 4, 0);
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int nt = 0; nt < 2; ++nt) {
-                size_t* lo = &h->ln_off[(size_t)(l * 2 + nt) * 4];
-                const std::string p1 = conv_prefix(l) + "message_layer_norms." + kNtKey[nt] + ".feat_norm.";
-                const std::string p2 = conv_prefix(l) + "update_layer_norms." + kNtKey[nt] + ".feat_norm.";
-                lo[0] = push(h->h_w, h->raw[p1 + "weight"].data);
-                lo[1] = push(h->h_w, h->raw[p1 + "bias"].data);
-                lo[2] = push(h->h_w, h->raw[p2 + "weight"].data);
-                lo[3] = push(h->h_w, h->raw[p2 + "bias"].data);
-            }
-        if (h->spec) {   // to_scalar_output as A fragments: K = 64 (32 k-steps), rows = outputs
-            const RawTensor& W = h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.weight"];
-            std::vector<float> a((size_t)32 * 64, 0.f);
-            for (int ks = 0; ks < 32; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int i = lane & 31, hl = lane >> 5;
-                    const int k = 32 * (ks / 16) + rho(ks % 16, hl);
-                    a[(size_t)ks * 64 + lane] = i < c.pharm_nf ? W.data[(size_t)i * 64 + k] : 0.f;
-                }
-            h->out_a = push(h->h_w, a);
-            h->out_b = push(h->h_w, h->raw["dynamics.noise_predictor.noise_predictor.to_scalar_output.bias"].data);
-        }
-        h->l0c_off = 0;
-        if (h->spec) {   // static hoist of conv layer 0 (pf_device.h L0H_*): pure copies of the first pp message GVP's pieces
-            const GvpSpec g = msg_spec(c, 0, ET_PP, 0);
-            const std::vector<float>& W = h->raw[g.prefix + "to_feats_out.0.weight"].data;        // [128][144 + 17]
-            const std::vector<float>& wh = h->raw[g.prefix + "Wh"].data;                          // [17][17]
-            const std::vector<float>& wu = h->raw[g.prefix + "Wu"].data;                          // [17][16]
-            std::vector<float> blk(L0H_SIZE, 0.f);
-            if (g.vi == 17 && g.so == PF_S && g.si == PF_S + PF_R && g.vo == 16) {
-                const int Kin = g.si + 17;
-                for (int f = 0; f < PF_S; ++f) {
-                    for (int k = 0; k < PF_R; ++k) blk[L0H_WR + (size_t)k * PF_S + f] = W[(size_t)f * Kin + PF_S + k];
-                    for (int k = 0; k < 17; ++k) blk[L0H_WSH + (size_t)k * PF_S + f] = W[(size_t)f * Kin + g.si + k];
-                    for (int k = 0; k < PF_S; ++k) blk[L0H_WHT + (size_t)k * PF_S + f] = W[(size_t)f * Kin + k];
-                    blk[L0H_B + f] = h->raw[g.prefix + "to_feats_out.0.bias"].data[f];
-                }
-                for (int k = 0; k < 17; ++k) blk[L0H_WH0 + k] = wh[(size_t)0 * 17 + k];
-                for (int k = 0; k < 17 * 16; ++k) blk[L0H_WU + k] = wu[k];
-                for (int k = 0; k < 16; ++k) blk[L0H_BG + k] = h->raw[g.prefix + "scalar_to_vector_gates.bias"].data[k];
-                const GvpSpec gp = msg_spec(c, 0, ET_PF, 0);                  // the pf etype's type table (n16 kernels)
-                const std::vector<float>& Wp = h->raw[gp.prefix + "to_feats_out.0.weight"].data;
-                for (int f = 0; f < PF_S; ++f) {
-                    for (int k = 0; k < PF_S; ++k) blk[L0H_WHT_PF + (size_t)k * PF_S + f] = Wp[(size_t)f * Kin + k];
-                    blk[L0H_B_PF + f] = h->raw[gp.prefix + "to_feats_out.0.bias"].data[f];
-                }
-            }
-            h->l0h_off = push(h->h_w, blk);
-            // center hoist (pf_cenhoist.h): the h_src blocks and biases of the ff / fp etypes' first message GVP, k-major
-            h->l0c_off = 0;
-            if (g.vi == 17 && g.so == PF_S && g.si == PF_S + PF_R && g.vo == 16) {
-                std::vector<float> cb(L0C_SIZE, 0.f);
-                const int Kin = g.si + 17;
-                for (int k2 = 0; k2 < 2; ++k2) {
-                    const GvpSpec gc = msg_spec(c, 0, k2 == 0 ? ET_FF : ET_FP, 0);
-                    const std::vector<float>& Wc = h->raw[gc.prefix + "to_feats_out.0.weight"].data;
-                    const std::vector<float>& bc = h->raw[gc.prefix + "to_feats_out.0.bias"].data;
-                    const size_t wo = k2 == 0 ? L0C_WHT_FF : L0C_WHT_FP, bo = k2 == 0 ? L0C_B_FF : L0C_B_FP;
-                    for (int f = 0; f < PF_S; ++f) {
-                        for (int k = 0; k < PF_S; ++k) cb[wo + (size_t)k * PF_S + f] = Wc[(size_t)f * Kin + k];
-                        cb[bo + f] = bc[f];
-                    }
-                }
-                h->l0c_off = push(h->h_w, cb);
-            }
-        }
-        if (h->spec) {   // row-group quad streams, one contiguous stream per chain.  The pharm update chain of the last conv layer
-            // comes last and is followed by the noise head's chain and to_scalar_output: the fused node + head kernel
-            // streams straight through.  RG_TAIL_PAD quads of padding: the prefetch ring reads ahead of the last quad used.
-            h->rg_msg.assign((size_t)c.n_convs * 4, 0);
-            h->rg_upd.assign((size_t)c.n_convs * 2, 0);
-            std::vector<float> st;
-            auto flush = [&]() { const size_t off = push(h->h_w, st); st.clear(); return off; };
-            auto chain = [&](auto spec_of, int n, int half = -1) {   // blocks of a chain: GVP j carries the gates of GVP j - 1
-                GvpSpec prev;
-                for (int j = 0; j < n; ++j) {
-                    const GvpSpec g = spec_of(j);
-                    pack_gvp_rg(h, g, j ? &prev : nullptr, st, half);
-                    prev = g;
-                }
-                pack_flush_rg(h, prev, st);
-            };
-            for (int l = 0; l < c.n_convs; ++l)
-                for (int et = 0; et < 4; ++et) {
-                    chain([&](int j) { return msg_spec(c, l, et, j); }, c.n_message_gvps);
-                    h->rg_msg[(size_t)l * 4 + et] = flush();
-                }
-            for (int l = 0; l < c.n_convs; ++l)
-                for (int nt = 0; nt < 2; ++nt) {
-                    if (l == c.n_convs - 1 && nt == 1) continue;
-                    chain([&](int j) { return upd_spec(c, l, nt, j); }, c.n_update_gvps);
-                    h->rg_upd[(size_t)l * 2 + nt] = flush();
-                }
-            chain([&](int j) { return upd_spec(c, c.n_convs - 1, 1, j); }, c.n_update_gvps);
-            chain([&](int k) { return head_spec(c, k); }, c.n_noise_gvps);
-            pack_out_rg(h, st);
-            st.resize(st.size() + (size_t)RG_TAIL_PAD * 256, 0.f);
-            h->rg_upd[(size_t)(c.n_convs - 1) * 2 + 1] = flush();
-            // the same chains for the two-wave form: per chain wave 0's stream, then wave 1's
-            h->rgs_msg.assign((size_t)c.n_convs * 4, 0);
-            h->rgs_upd.assign((size_t)c.n_convs * 2, 0);
-            h->rgs_upd_stride.assign((size_t)c.n_convs * 2, 0);
-            for (int l = 0; l < c.n_convs; ++l)
-                for (int et = 0; et < 4; ++et) {
-                    for (int half = 0; half < 2; ++half) {
-                        chain([&](int j) { return msg_spec(c, l, et, j); }, c.n_message_gvps, half);
-                        if (half == 0) h->rgs_msg_stride = st.size();
-                    }
-                    h->rgs_msg[(size_t)l * 4 + et] = flush();
-                }
-            for (int l = 0; l < c.n_convs; ++l)
-                for (int nt = 0; nt < 2; ++nt) {
-                    const bool tail = l == c.n_convs - 1 && nt == 1;
-                    for (int half = 0; half < 2; ++half) {
-                        chain([&](int j) { return upd_spec(c, l, nt, j); }, c.n_update_gvps, half);
-                        if (tail) {
-                            chain([&](int k) { return head_spec(c, k); }, c.n_noise_gvps, half);
-                            pack_out_rg(h, st);
-                        }
-                        if (half == 0) h->rgs_upd_stride[(size_t)l * 2 + nt] = st.size();
-                    }
-                    if (!tail) h->rgs_upd[(size_t)l * 2 + nt] = flush();
-                }
-            st.resize(st.size() + (size_t)RG_TAIL_PAD * 256, 0.f);
-            h->rgs_upd[(size_t)(c.n_convs - 1) * 2 + 1] = flush();
-        }
-        h->n16_begin = h->spec ? h->h_w.size() : 0;     // everything packed from here on serves the n16 (inference-only) kernels
-        if (h->spec && c.n_message_gvps >= 2 && c.n_update_gvps >= 1) {   // n16 quad streams: per chain wave 0's stream, then waves 1..3
-            h->n16_msg.assign((size_t)c.n_convs * 4, 0);
-            h->n16_upd.assign((size_t)c.n_convs * 2, 0);
-            std::vector<float> st;
-            // (m0_at: index of the block that is a first message GVP in the full form, M0F; -1: block 0 has kind0)
-            auto chain16 = [&](auto spec_of, int n, int kind0, size_t& stride, int m0_at = -1) {
-                for (int w = 0; w < 4; ++w) {
-                    const size_t b0 = st.size();
-                    for (int j = 0; j < n; ++j) pack_n16(h, spec_of(j), j == m0_at ? N16_M0F : (j == 0 ? kind0 : N16_GEN), w, st);
-                    st.resize(st.size() + (size_t)N16_TAIL_PAD * 256, 0.f);
-                    stride = st.size() - b0;
-                }
-                const size_t off = push(h->h_w, st);
-                for (int4 r : h->split_pending) { r.x += (int)off; h->split_tab.push_back(r); }
-                h->split_pending.clear();
-                st.clear();
-                return off;
-            };
-            for (int l = 0; l < c.n_convs; ++l)
-                for (int et = 0; et < 4; ++et)
-                    h->n16_msg[(size_t)l * 4 + et] = chain16([&](int j) { return msg_spec(c, l, et, j); }, c.n_message_gvps, N16_M0F, h->n16_msg_stride);
-            for (int et = 0; et < 4; ++et)
-                h->n16_l0[et] = chain16([&](int j) { return msg_spec(c, 0, et, j); }, c.n_message_gvps,
-                                        (et == ET_PP || et == ET_PF) ? N16_M0H : N16_M0Z, h->n16_l0_stride[et]);
-            for (int et = 0; et < 4; ++et)      // center hoist: every etype's chain with a hoisted first block (ff / fp start from P_et rows)
-                h->n16_l0h[et] = chain16([&](int j) { return msg_spec(c, 0, et, j); }, c.n_message_gvps, N16_M0H, h->n16_l0h_stride[et]);
-            if (c.n_convs == 2)          // fused launch: conv layer 0's update chain of the source type, then the last layer's message chain
-                for (int k = 0; k < 2; ++k) {
-                    const int et = k == 0 ? ET_FF : ET_PF, nt = k == 0 ? 1 : 0;
-                    h->n16_fused[k] = chain16([&](int j) { return j < c.n_update_gvps ? upd_spec(c, 0, nt, j) : msg_spec(c, 1, et, j - c.n_update_gvps); },
-                                              c.n_update_gvps + c.n_message_gvps, N16_GEN, h->n16_fused_stride[k], c.n_update_gvps);
-                }
-            for (int l = 0; l < c.n_convs; ++l)
-                for (int nt = 0; nt < 2; ++nt)
-                    h->n16_upd[(size_t)l * 2 + nt] = chain16([&](int j) { return upd_spec(c, l, nt, j); }, c.n_update_gvps, N16_GEN, h->n16_upd_stride);
-            {   // tail launch: the centers' update chain of the last conv layer, then the noise head (its last GVP padded, with to_scalar_output)
-                const GvpSpec hl = head_spec(c, c.n_noise_gvps - 1);
-                h->n16_tail = 0;
-                if (c.pharm_nf <= 15 && c.n_noise_gvps >= 1 && hl.vi == 16 && hl.vo == 1 && hl.si == PF_S && hl.so == 64) {
-                    for (int w = 0; w < 4; ++w) {
-                        const size_t b0 = st.size();
-                        for (int j = 0; j < c.n_update_gvps; ++j) pack_n16(h, upd_spec(c, c.n_convs - 1, 1, j), N16_GEN, w, st);
-                        for (int k = 0; k + 1 < c.n_noise_gvps; ++k) pack_n16(h, head_spec(c, k), N16_GEN, w, st);
-                        pack_n16_head_last(h, hl, w, st);
-                        st.resize(st.size() + (size_t)N16_TAIL_PAD * 256, 0.f);
-                        h->n16_tail_stride = st.size() - b0;
-                    }
-                    h->n16_tail = push(h->h_w, st);
-                    for (int4 r : h->split_pending) { r.x += (int)h->n16_tail; h->split_tab.push_back(r); }
-                    h->split_pending.clear();
-                    st.clear();
-                }
-            }
-        } else { h->n16_msg.clear(); h->n16_upd.clear(); h->n16_tail = 0; for (int et = 0; et < 4; ++et) h->n16_l0h[et] = 0; }
-        while (h->h_w.size() % 64) h->h_w.push_back(0.f);
-    };
-    {
-        std::map<std::string, RawTensor> keep;
-        keep.swap(h->raw);
-        size_t off = 0;
-        for (const auto& kv : exp) {
-            RawTensor t;
-            t.shape = keep[kv.first].shape;
-            t.data.resize(keep[kv.first].data.size());
-            for (size_t i = 0; i < t.data.size(); ++i) t.data[i] = (float)(off + i + 1);
-            off += t.data.size();
-            h->raw[kv.first] = std::move(t);
-        }
-        h->h_map.clear();
-        h->split_tab.clear(); h->split_pending.clear();
-        if (off < (size_t(1) << 24)) {           // indices are exact in fp32
-            h->split_record = N16_SPLIT != 0;
-            pack_all();
-            h->split_record = false;
-            h->h_map.resize(h->h_w.size());
-            for (size_t i = 0; i < h->h_w.size(); ++i) h->h_map[i] = (int)h->h_w[i] - 1;      // -1: zero padding
-        }
-        h->raw.swap(keep);
-    }
-    pack_all();
-    if (h->d_w) { (void)hipFree(h->d_w); h->d_w = nullptr; }
-    if (h->d_gvp) { (void)hipFree(h->d_gvp); h->d_gvp = nullptr; }
-    PF_HIP(h, hipMalloc((void**)&h->d_w, h->h_w.size() * sizeof(float)));
-    PF_HIP(h, hipMemcpy(h->d_w, h->h_w.data(), h->h_w.size() * sizeof(float), hipMemcpyHostToDevice));
-    h->n_packed = h->h_w.size();
-    if (h->d_map) { (void)hipFree(h->d_map); h->d_map = nullptr; }
-    if (!h->h_map.empty()) {
-        if (h->h_map.size() != h->h_w.size()) PF_FAIL(h, PF_ERR_STATE, "internal: gather map does not match the packed weights");
-        PF_HIP(h, hipMalloc((void**)&h->d_map, h->h_map.size() * sizeof(int)));
-        PF_HIP(h, hipMemcpy(h->d_map, h->h_map.data(), h->h_map.size() * sizeof(int), hipMemcpyHostToDevice));
-        h->h_map.clear();
-        h->h_map.shrink_to_fit();
-    }
-    if (h->d_split_tab) { (void)hipFree(h->d_split_tab); h->d_split_tab = nullptr; }
-    h->n_split_tab = h->split_tab.size();
-    if (h->n_split_tab) {
-        PF_HIP(h, hipMalloc((void**)&h->d_split_tab, h->n_split_tab * sizeof(int4)));
-        PF_HIP(h, hipMemcpy(h->d_split_tab, h->split_tab.data(), h->n_split_tab * sizeof(int4), hipMemcpyHostToDevice));
-        h->split_tab.clear(); h->split_tab.shrink_to_fit();
-    }
-    for (const GvpOff& o : offs) {
+    for (const GvpOff& o : pm.gvp) {
         GvpW g;
         g.a_wh = h->d_w + o.wh; g.a_wu = h->d_w + o.wu; g.a_main = h->d_w + o.a_main; g.a_main_c = h->d_w + o.a_main_c; g.b_main = h->d_w + o.b_main;
         g.a_gate_c = h->d_w + o.a_gate_c; g.a_wh_c = h->d_w + o.wh_c; g.a_wu_c = h->d_w + o.wu_c;
         g.a_gate = h->d_w + o.a_gate; g.b_gate = h->d_w + o.b_gate;
         h->h_gvp.push_back(g);
     }
-    if (!h->h_gvp.empty()) {
-        PF_HIP(h, hipMalloc((void**)&h->d_gvp, h->h_gvp.size() * sizeof(GvpW)));
-        PF_HIP(h, hipMemcpy(h->d_gvp, h->h_gvp.data(), h->h_gvp.size() * sizeof(GvpW), hipMemcpyHostToDevice));
-    }
+    PF_HIP(h, upload(&h->d_gvp, h->h_gvp));
+    h->nparams = flat.size();
+    PF_HIP(h, upload(&h->d_flat, flat));
+    h->n_tseg = c.n_convs <= 4 ? (int)segs.size() : -1;
+    PF_HIP(h, upload(&h->d_tseg, segs));
+    std::vector<GvpT> tab;              // where each GVP's tensors sit in the flat vector
+    for_each_gvp(c, [&](const GvpSpec& g) {
+        GvpT t;
+        t.o_Wh = (int)h->flat_offset(g.prefix + "Wh"); t.o_Wu = (int)h->flat_offset(g.prefix + "Wu");
+        t.o_Wm = (int)h->flat_offset(g.prefix + "to_feats_out.0.weight"); t.o_bm = (int)h->flat_offset(g.prefix + "to_feats_out.0.bias");
+        t.o_Wg = (int)h->flat_offset(g.prefix + "scalar_to_vector_gates.weight"); t.o_bg = (int)h->flat_offset(g.prefix + "scalar_to_vector_gates.bias");
+        t.vi = g.vi; t.vo = g.vo; t.h = std::max(g.vi, g.vo); t.si = g.si; t.so = g.so; t.sig = 1;
+        t.pk = (int)tab.size();
+        tab.push_back(t);
+    });
+    tab.back().sig = 0;                 // the walk ends with the noise head's last GVP (pf_create: n_noise_gvps >= 1): no sigmoid on its vector gate
+    h->n_gvpt = (int)tab.size();
+    PF_HIP(h, upload(&h->d_gvpt, tab));
+    // per-handle allocations; what was derived from the old weights goes (ensure_wide_pack / the backward build theirs again on the new d_flat)
+    if (h->d_wpack) { (void)hipFree(h->d_wpack); h->d_wpack = nullptr; }
+    h->wpack_version = ~0ull;
     if (h->d_wgvp) { (void)hipFree(h->d_wgvp); h->d_wgvp = nullptr; }
-    if (h->d_wpk) { (void)hipFree(h->d_wpk); h->d_wpk = nullptr; }          // (ensure_wide_pack builds both again on the new d_flat)
+    if (h->d_wpk) { (void)hipFree(h->d_wpk); h->d_wpk = nullptr; }
     if (h->d_wpk_jobs) { (void)hipFree(h->d_wpk_jobs); h->d_wpk_jobs = nullptr; }
-    if (h->wide) {
-        std::vector<WideGvp> tab;
-        size_t i = 0;
-        auto add = [&](const GvpSpec& g) {
+    if (h->wide) {          // a handle of the family: its table points into d_w, and the gather map keeps that fresh
+        std::vector<WideGvp> wtab;
+        for_each_gvp(c, [&](const GvpSpec& g) {
+            const size_t* o = &h->pk.wide_off[6 * wtab.size()];
             WideGvp w;
-            const size_t* o = &h->wide_off[i];
             w.wh = h->d_w + o[0]; w.wu = h->d_w + o[1]; w.wm = h->d_w + o[2]; w.bm = h->d_w + o[3]; w.wg = h->d_w + o[4]; w.bg = h->d_w + o[5];
             w.vi = g.vi; w.vo = g.vo; w.si = g.si; w.so = g.so;
-            tab.push_back(w);
-            i += 6;
-        };
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int et = 0; et < 4; ++et)
-                for (int j = 0; j < c.n_message_gvps; ++j) add(msg_spec(c, l, et, j));
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int nt = 0; nt < 2; ++nt)
-                for (int j = 0; j < c.n_update_gvps; ++j) add(upd_spec(c, l, nt, j));
-        for (int k = 0; k < c.n_noise_gvps; ++k) add(head_spec(c, k));
-        PF_HIP(h, hipMalloc((void**)&h->d_wgvp, tab.size() * sizeof(WideGvp)));
-        PF_HIP(h, hipMemcpy(h->d_wgvp, tab.data(), tab.size() * sizeof(WideGvp), hipMemcpyHostToDevice));
+            wtab.push_back(w);
+        });
+        PF_HIP(h, upload(&h->d_wgvp, wtab));
     }
-    h->h_w.clear();
-    h->h_w.shrink_to_fit();
-    {   // gradient path: the parameters once more as one flat vector in state-dict order, and where each GVP's tensors sit
-        std::vector<float> flat;
-        h->flat_layout.clear();
-        h->flat_index.clear(); h->flat_index_ok = false; h->edge_fx.clear();
-        for (const auto& kv : exp) {
-            const RawTensor& t = h->raw[kv.first];
-            h->flat_layout.push_back({kv.first, {flat.size(), t.data.size()}});
-            flat.insert(flat.end(), t.data.begin(), t.data.end());
-        }
-        h->nparams = flat.size();
-        {   // class of every tensor: the kernel that differentiates it
-            std::vector<TensorSeg> segs;
-            for (const auto& kv : h->flat_layout) {
-                const std::string& k = kv.first;
-                TensorSeg sg{(int)kv.second.first, (int)(kv.second.first + kv.second.second), PFT_CLS_NONE, 0};
-                if (kv.second.second == 0) sg.cls = PFT_CLS_NONE;
-                else if (k.find("_encoder.") != std::string::npos) sg.cls = PFT_CLS_ENC;
-                else if (k.find("noise_predictor.noise_predictor.") != std::string::npos) sg.cls = PFT_CLS_HEAD;
-                else {
-                    int layer = -1;
-                    for (int l = 0; l < c.n_convs; ++l)
-                        if (k.compare(0, conv_prefix(l).size(), conv_prefix(l)) == 0) layer = l;
-                    if (layer < 0) PF_FAIL(h, PF_ERR_STATE, "internal: parameter %s has no gradient class", k.c_str());
-                    if (layer >= 4) { h->n_tseg = -1; break; }           // the gradient path numbers its classes for n_convs <= 4
-                    sg.cls = PFT_CLS_NODE + layer;
-                    for (int et = 0; et < 4; ++et)
-                        if (k.find(std::string("edge_message_fns.") + kEtKey[et] + ".") != std::string::npos) sg.cls = PFT_CLS_MSG + layer * 4 + et;
-                }
-                segs.push_back(sg);
-            }
-            {
-                int lo = 0x7fffffff, hi = 0, tot = 0;
-                for (const TensorSeg& sg : segs)
-                    if (sg.cls == PFT_CLS_ENC) { lo = std::min(lo, sg.begin); hi = std::max(hi, sg.end); tot += sg.end - sg.begin; }
-                if (tot == 0) { lo = hi = 0; }
-                if (hi - lo != tot) PF_FAIL(h, PF_ERR_STATE, "internal: the encoders' parameters are not contiguous in the flat layout");
-                h->enc_begin = lo; h->enc_n = hi - lo;
-            }
-            if (h->d_tseg) { (void)hipFree(h->d_tseg); h->d_tseg = nullptr; }
-            h->n_tseg = c.n_convs <= 4 ? (int)segs.size() : -1;
-            PF_HIP(h, hipMalloc((void**)&h->d_tseg, std::max<size_t>(segs.size(), 1) * sizeof(TensorSeg)));
-            PF_HIP(h, hipMemcpy(h->d_tseg, segs.data(), segs.size() * sizeof(TensorSeg), hipMemcpyHostToDevice));
-        }
-        std::vector<GvpT> tab;
-        auto mk = [&](const GvpSpec& g, bool sig) {
-            GvpT t;
-            t.o_Wh = (int)h->flat_offset(g.prefix + "Wh"); t.o_Wu = (int)h->flat_offset(g.prefix + "Wu");
-            t.o_Wm = (int)h->flat_offset(g.prefix + "to_feats_out.0.weight"); t.o_bm = (int)h->flat_offset(g.prefix + "to_feats_out.0.bias");
-            t.o_Wg = (int)h->flat_offset(g.prefix + "scalar_to_vector_gates.weight"); t.o_bg = (int)h->flat_offset(g.prefix + "scalar_to_vector_gates.bias");
-            t.vi = g.vi; t.vo = g.vo; t.h = std::max(g.vi, g.vo); t.si = g.si; t.so = g.so; t.sig = sig ? 1 : 0;
-            t.pk = (int)tab.size();
-            return t;
-        };
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int et = 0; et < 4; ++et)
-                for (int j = 0; j < c.n_message_gvps; ++j) tab.push_back(mk(msg_spec(c, l, et, j), true));
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int nt = 0; nt < 2; ++nt)
-                for (int j = 0; j < c.n_update_gvps; ++j) tab.push_back(mk(upd_spec(c, l, nt, j), true));
-        for (int k = 0; k < c.n_noise_gvps; ++k) tab.push_back(mk(head_spec(c, k), k != c.n_noise_gvps - 1));
-        if (h->d_flat) { (void)hipFree(h->d_flat); h->d_flat = nullptr; }
-        if (h->d_gvpt) { (void)hipFree(h->d_gvpt); h->d_gvpt = nullptr; }
-        if (h->d_wpack) { (void)hipFree(h->d_wpack); h->d_wpack = nullptr; }
-        h->wpack_version = ~0ull;
-        PF_HIP(h, hipMalloc((void**)&h->d_flat, std::max<size_t>(flat.size(), 1) * sizeof(float)));
-        PF_HIP(h, hipMemcpy(h->d_flat, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice));
-        h->n_gvpt = (int)tab.size();
-        PF_HIP(h, hipMalloc((void**)&h->d_gvpt, tab.size() * sizeof(GvpT)));
-        PF_HIP(h, hipMemcpy(h->d_gvpt, tab.data(), tab.size() * sizeof(GvpT), hipMemcpyHostToDevice));
-    }
-    h->t_have_fwd = false;
-    h->committed = true;
-    ++h->w_version;
     if (!h->d_l0c) PF_HIP(h, hipMalloc((void**)&h->d_l0c, 32 * sizeof(float)));
     if (h->d_ptab) { (void)hipFree(h->d_ptab); h->d_ptab = nullptr; }
     if (h->spec) PF_HIP(h, hipMalloc((void**)&h->d_ptab, (size_t)L0_PTAB_SLOTS * L0_NTAB * c.rec_nf * PF_S * sizeof(float)));
+    h->t_have_fwd = false;
+    ++h->w_version;
+    h->committed = true;
     return PF_OK;
 }
 
@@ -2930,7 +2193,7 @@ int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* 
     pfk_load_noise0(dev_noise0, h->d_xn + h->Np, h->d_pharm_h, h->Nf, h->cfg.pharm_nf, s);  // :455-456
     h->cen_valid = false; h->snap_cur = -1;
     h->spec_valid = false; h->step_id += 2;      // (a gap: no stamp of the run before reads as "the previous step")
-    if (h->cen_hoist && h->d_snap[0] && h->l0c_off != 0) {      // center hoist: the features as they are, for the first step's hoist workgroups
+    if (h->cen_hoist && h->d_snap[0] && h->pk.l0c_off != 0) {      // center hoist: the features as they are, for the first step's hoist workgroups
         pfk_copy(h->d_pharm_h, h->d_snap[0], (size_t)h->Nf * h->cfg.pharm_nf, s);
         h->snap_cur = 0;
     }
@@ -2964,7 +2227,7 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
     // step's update of pharm_h); only the paths through pf_stepbuild.h write it
     ++h->step_id;
     const int snap_next = h->snap_cur < 0 ? 0 : (h->snap_cur ^ 1);
-    sp.h_snap_out = (h->cen_hoist && h->d_snap[0] && h->l0c_off != 0) ? h->d_snap[snap_next] : nullptr;
+    sp.h_snap_out = (h->cen_hoist && h->d_snap[0] && h->pk.l0c_off != 0) ? h->d_snap[snap_next] : nullptr;
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, &sp);      // every graph of the batch is at the same t
     if (rc) return rc;
     h->snap_cur = (sp.h_snap_out && h->tail_done && h->last_tail == 2) ? snap_next : -1;
@@ -3395,59 +2658,6 @@ static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
 }
 
 
-// The WideGvp table of a handle that was not created on the width-generic family (the specialised widths without PFDYN_WIDE), for
-// its wide training leg: built on first use after a commit, its two packed Linears per GVP refreshed from d_flat when the weights
-// moved.  A handle of the family itself has the table from pf_commit_weights and the gather map keeps it fresh.
-static int ensure_wide_pack(pf_handle* h, hipStream_t s) {
-    if (h->wide) return PF_OK;
-    const pf_config& c = h->cfg;
-    if (!h->d_wgvp) {
-        std::vector<WideGvp> tab;
-        std::vector<WidePackJob> jobs;
-        std::vector<size_t> dst;            // per GVP: wm, wg
-        size_t total = 0;
-        auto frag = [](int n_out, int K) { return (size_t)((n_out + 15) / 16) * ((K + 3) / 4) * 64; };
-        std::vector<GvpSpec> specs;
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int et = 0; et < 4; ++et)
-                for (int j = 0; j < c.n_message_gvps; ++j) specs.push_back(msg_spec(c, l, et, j));
-        for (int l = 0; l < c.n_convs; ++l)
-            for (int nt = 0; nt < 2; ++nt)
-                for (int j = 0; j < c.n_update_gvps; ++j) specs.push_back(upd_spec(c, l, nt, j));
-        for (int k = 0; k < c.n_noise_gvps; ++k) specs.push_back(head_spec(c, k));
-        for (const GvpSpec& g : specs) {
-            const int H = std::max(g.vi, g.vo);
-            const int o_wm = (int)h->flat_offset(g.prefix + "to_feats_out.0.weight"), o_wg = (int)h->flat_offset(g.prefix + "scalar_to_vector_gates.weight");
-            jobs.push_back({o_wm, g.so, g.si + H, (int)total}); dst.push_back(total); total += frag(g.so, g.si + H);
-            jobs.push_back({o_wg, g.vo, g.so, (int)total}); dst.push_back(total); total += frag(g.vo, g.so);
-        }
-        if (total >= (size_t)1 << 31) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_family: the model is too large for the width-generic packing");
-        if (h->d_wpk) { (void)hipFree(h->d_wpk); h->d_wpk = nullptr; }
-        if (h->d_wpk_jobs) { (void)hipFree(h->d_wpk_jobs); h->d_wpk_jobs = nullptr; }
-        PF_HIP(h, hipMalloc((void**)&h->d_wpk, std::max<size_t>(total, 1) * sizeof(float)));
-        PF_HIP(h, hipMalloc((void**)&h->d_wpk_jobs, jobs.size() * sizeof(WidePackJob)));
-        PF_HIP(h, hipMemcpy(h->d_wpk_jobs, jobs.data(), jobs.size() * sizeof(WidePackJob), hipMemcpyHostToDevice));
-        h->n_wpk_jobs = (int)jobs.size();
-        for (size_t i = 0; i < specs.size(); ++i) {
-            const GvpSpec& g = specs[i];
-            WideGvp w;
-            w.wh = h->d_flat + h->flat_offset(g.prefix + "Wh"); w.wu = h->d_flat + h->flat_offset(g.prefix + "Wu");
-            w.wm = h->d_wpk + dst[2 * i]; w.bm = h->d_flat + h->flat_offset(g.prefix + "to_feats_out.0.bias");
-            w.wg = h->d_wpk + dst[2 * i + 1]; w.bg = h->d_flat + h->flat_offset(g.prefix + "scalar_to_vector_gates.bias");
-            w.vi = g.vi; w.vo = g.vo; w.si = g.si; w.so = g.so;
-            tab.push_back(w);
-        }
-        PF_HIP(h, hipMalloc((void**)&h->d_wgvp, tab.size() * sizeof(WideGvp)));
-        PF_HIP(h, hipMemcpy(h->d_wgvp, tab.data(), tab.size() * sizeof(WideGvp), hipMemcpyHostToDevice));
-        h->wpk_version = ~0ull;
-    }
-    if (h->wpk_version != h->w_version) {
-        pfk_wide_pack(h->d_flat, h->d_wpk_jobs, h->n_wpk_jobs, h->d_wpk, s);
-        h->wpk_version = h->w_version;
-    }
-    return PF_OK;
-}
-
 // dropout and parameter view of one training step of the width-generic leg
 static void wide_train_common(pf_handle* h, float dropout_p, uint32_t seed) {
     WtCommon& wc = h->wt_common;
@@ -3494,7 +2704,7 @@ static int set_flat_params_impl(pf_handle* h, const float* dev_flat, pf_stream s
     if (!h->d_map) PF_FAIL(h, PF_ERR_STATE, "pf_set_flat_params: no gather map (more than 2^24 parameters)");
     hipStream_t s = (hipStream_t)stream;
     if (!copied) PF_HIP(h, hipMemcpyAsync(h->d_flat, dev_flat, h->nparams * sizeof(float), hipMemcpyDeviceToDevice, s));
-    const size_t n_now = (h->n16_begin > 0 && h->n16_begin < h->n_packed) ? h->n16_begin : h->n_packed;
+    const size_t n_now = (h->pk.n16_begin > 0 && h->pk.n16_begin < h->n_packed) ? h->pk.n16_begin : h->n_packed;
     pfk_gather_weights(h->d_flat, h->d_map, n_now, h->d_w, s);
     h->n16_stale = n_now < h->n_packed;
     ++h->w_version;
@@ -3535,11 +2745,7 @@ int pf_train_forward(pf_handle* h, const float* dev_prot_x, const float* dev_pha
     hipStream_t s = (hipStream_t)stream;
     rc = h->train_wide ? ensure_wide_train_ws(h, s) : ensure_train_ws(h, s);
     if (rc) return rc;
-    if (h->train_wide) {
-        rc = ensure_wide_pack(h, s);
-        if (rc) return rc;
-        wide_train_common(h, dropout_p, seed);
-    }
+    if (h->train_wide) wide_train_common(h, dropout_p, seed);
     h->t_common = TrainCommon{};
     h->t_common.W = h->d_flat; h->t_common.gpart = h->t_gpart; h->t_common.nparams = (int)h->nparams;
     h->t_common.gstride = (int)((h->nparams + 63) / 64 * 64);
@@ -3574,11 +2780,7 @@ static int loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* de
     hipStream_t s = (hipStream_t)stream;
     rc = h->train_wide ? ensure_wide_train_ws(h, s) : ensure_train_ws(h, s);
     if (rc) return rc;
-    if (h->train_wide) {
-        rc = ensure_wide_pack(h, s);
-        if (rc) return rc;
-        wide_train_common(h, dropout_p, seed);
-    }
+    if (h->train_wide) wide_train_common(h, dropout_p, seed);
     h->t_have_loss = false;
     h->t_common = TrainCommon{};
     h->t_common.W = h->d_flat; h->t_common.gpart = h->t_gpart; h->t_common.nparams = (int)h->nparams;
@@ -4155,12 +3357,12 @@ int pf_debug_chain(pf_handle* h, int32_t kind, int32_t layer, int32_t sub, int32
         n16_refresh(h, (hipStream_t)stream);
         if (n_rows < 0 || !dev_s_in || !dev_v_in || !dev_s_out || !dev_v_out) PF_FAIL(h, PF_ERR_ARG, "pf_debug_chain: bad argument");
         if (layer < 0 || layer >= c.n_convs || sub < 0 || sub > (kind == 16 ? 3 : 1)) PF_FAIL(h, PF_ERR_ARG, "pf_debug_chain: bad layer / sub index");
-        if (h->n16_msg.empty()) PF_FAIL(h, PF_ERR_STATE, "pf_debug_chain: this architecture has no n16 streams (needs n_message_gvps >= 2)");
+        if (h->pk.n16_msg.empty()) PF_FAIL(h, PF_ERR_STATE, "pf_debug_chain: this architecture has no n16 streams (needs n_message_gvps >= 2)");
         UnitParams p{};
         p.s_in = dev_s_in; p.v_in = dev_v_in; p.s_out = dev_s_out; p.v_out = dev_v_out;
         p.n = n_rows; p.kind = kind;
-        if (kind == 16) { p.stream = h->d_w + h->n16_msg[(size_t)layer * 4 + sub]; p.n_gvps = c.n_message_gvps; p.n16_stride = (int)h->n16_msg_stride; }
-        else { p.stream = h->d_w + h->n16_upd[(size_t)layer * 2 + sub]; p.n_gvps = c.n_update_gvps; p.n16_stride = (int)h->n16_upd_stride; }
+        if (kind == 16) { p.stream = h->d_w + h->pk.n16_msg[(size_t)layer * 4 + sub]; p.n_gvps = c.n_message_gvps; p.n16_stride = (int)h->pk.n16_msg_stride; }
+        else { p.stream = h->d_w + h->pk.n16_upd[(size_t)layer * 2 + sub]; p.n_gvps = c.n_update_gvps; p.n16_stride = (int)h->pk.n16_upd_stride; }
         pfk_n16_unit(&p, (hipStream_t)stream);
         hipError_t e16 = hipGetLastError();
         if (e16 != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e16));
@@ -4169,19 +3371,19 @@ int pf_debug_chain(pf_handle* h, int32_t kind, int32_t layer, int32_t sub, int32
     if (kind < 0 || kind > 3 || n_rows < 0 || !dev_s_in || !dev_v_in || !dev_s_out || !dev_v_out) PF_FAIL(h, PF_ERR_ARG, "pf_debug_chain: bad argument");
     if (kind != 3 && (layer < 0 || layer >= c.n_convs)) PF_FAIL(h, PF_ERR_ARG, "pf_debug_chain: bad layer");
     if ((kind == 0 && (sub < 0 || sub > 3)) || ((kind == 1 || kind == 2) && (sub < 0 || sub > 3))) PF_FAIL(h, PF_ERR_ARG, "pf_debug_chain: bad sub index");
-    if (h->rg_msg.empty()) PF_FAIL(h, PF_ERR_STATE, "pf_debug_chain: no row-group streams (weights not committed)");
+    if (h->pk.rg_msg.empty()) PF_FAIL(h, PF_ERR_STATE, "pf_debug_chain: no row-group streams (weights not committed)");
     UnitParams p{};
     p.s_in = dev_s_in; p.v_in = dev_v_in; p.s_out = dev_s_out; p.v_out = dev_v_out;
     p.n = n_rows; p.kind = kind; p.pharm_nf = c.pharm_nf;
-    if (kind == 0) { p.stream = h->d_w + h->rg_msg[(size_t)layer * 4 + sub]; p.n_gvps = c.n_message_gvps; }
+    if (kind == 0) { p.stream = h->d_w + h->pk.rg_msg[(size_t)layer * 4 + sub]; p.n_gvps = c.n_message_gvps; }
     else if (kind == 1) {
         if (sub > 1) PF_FAIL(h, PF_ERR_ARG, "pf_debug_chain: node type 0 (prot) or 1 (pharm)");
-        p.stream = h->d_w + h->rg_upd[(size_t)layer * 2 + sub]; p.n_gvps = c.n_update_gvps;
+        p.stream = h->d_w + h->pk.rg_upd[(size_t)layer * 2 + sub]; p.n_gvps = c.n_update_gvps;
     } else if (kind == 2) {           // sub: 2 * node type + (0: message_layer_norms, 1: update_layer_norms)
-        const size_t* lo = &h->ln_off[(size_t)(layer * 2 + (sub >> 1)) * 4];
+        const size_t* lo = &h->pk.ln_off[(size_t)(layer * 2 + (sub >> 1)) * 4];
         p.ln_w = h->d_w + lo[(sub & 1) * 2]; p.ln_b = h->d_w + lo[(sub & 1) * 2 + 1];
     } else {
-        p.stream = h->d_w + h->rg_upd[(size_t)(c.n_convs - 1) * 2 + 1]; p.n_gvps = c.n_noise_gvps; p.skip_gvps = c.n_update_gvps;
+        p.stream = h->d_w + h->pk.rg_upd[(size_t)(c.n_convs - 1) * 2 + 1]; p.n_gvps = c.n_noise_gvps; p.skip_gvps = c.n_update_gvps;
     }
     pfk_rg_unit(&p, (hipStream_t)stream);
     hipError_t e = hipGetLastError();

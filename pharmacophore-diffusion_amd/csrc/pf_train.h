@@ -6,7 +6,7 @@
 // through PharmRecDynamicsGVP.forward, dynamics_gvp.py:131-185, and GVPMultiEdgeConv, gvp.py:459-551).
 //
 // Parameters and gradients live in ONE flat fp32 vector in the reference's state-dict order
-// (pf_host.cpp: expected_tensors); a GvpT addresses one GVP's six tensors by offset into that vector, so the
+// (pf_pack.cpp: expected_tensors); a GvpT addresses one GVP's six tensors by offset into that vector, so the
 // gradient of a tensor sits at the same offset of the gradient vector.  Every thread block of a backward kernel
 // accumulates into its own private copy of the gradient vector (gpart[block][nparams], plain read-modify-write by
 // the owning lane, no atomics) and pfk_train_reduce sums the copies in a fixed order.  The scatter of dL/d(h_src, v_src)

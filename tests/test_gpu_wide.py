@@ -233,6 +233,33 @@ def test_trajectory_vs_oracle_and_repeatable(S, V):
     assert torch.equal(x0, x1) and torch.equal(h0, h1)
 
 
+def test_set_flat_params_reaches_the_packed_linears():
+    """The family's packed Linears follow the flat parameter vector (the gather map of its packing, pf_pack.cpp): after
+    pf_set_flat_params a (64, 32) handle computes, bit for bit, what a fresh handle committed with those weights computes -- and
+    the first result again after the first weights come back."""
+    fields, n_prot, n_pharm = CASES["knnff_c1"]
+    cfg = O.DynamicsConfig(n_hidden_scalars=64, vector_size=32, **fields)
+    batch = O.synthetic_batch(range(len(n_prot)), n_prot, n_pharm, cfg)
+    x_t, h_t, t = inputs(cfg, batch, 0)
+    sd1, sd2 = O.make_state_dict(cfg, 3), O.make_state_dict(cfg, 4)
+    eng = engine_for(cfg, sd1)
+    set_batch(eng, batch)
+    h1, x1 = eng.dynamics(x_t, h_t, t)
+
+    def flat(sd):
+        return torch.cat([sd[n].reshape(-1) for n, _, _ in eng.param_layout()])
+    eng.set_flat_params(flat(sd2))                  # as after an optimiser step
+    h2, x2 = eng.dynamics(x_t, h_t, t)
+    fresh = engine_for(cfg, sd2)
+    set_batch(fresh, batch)
+    fh, fx = fresh.dynamics(x_t, h_t, t)
+    assert torch.equal(h2, fh) and torch.equal(x2, fx)
+    assert not torch.equal(h2, h1)
+    eng.set_flat_params(flat(sd1))
+    h3, x3 = eng.dynamics(x_t, h_t, t)
+    assert torch.equal(h3, h1) and torch.equal(x3, x1)
+
+
 def test_pocket_groups_accepted_at_other_widths():
     cfg = O.DynamicsConfig(n_hidden_scalars=256, vector_size=16)
     pocket = O.synthetic_batch([4], [64], [3], cfg)

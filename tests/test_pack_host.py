@@ -1,0 +1,32 @@
+"""The weight packer on the CPU (csrc/pf_pack.cpp): tests/pack_check.cpp packs seeded tensors for seven configurations and checks
+every packed element against the gather map, the split table, the layout's offsets and extents -- compiled host-only under the
+address and undefined-behaviour sanitizers and run as a program of its own, once as the default build and once with -DN16_SPLIT=1."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "pharmacophore-diffusion_amd", "csrc")
+SAN = "-fsanitize=address,undefined -fno-sanitize-recover"
+
+
+@pytest.mark.parametrize("split", [0, 1], ids=["default", "n16_split"])
+def test_pack_check(tmp_path, split):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.fail("hipcc not found: the packer check needs the compiler the library is built with")
+    exe = str(tmp_path / "pack_check")
+    cmd = [hipcc, "-x", "c++", "-O1", "-g", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + CSRC]
+    cmd += ["-Xarch_host", SAN.split()[0], "-Xarch_host", SAN.split()[1]]
+    if split:
+        cmd.append("-DN16_SPLIT=1")
+    cmd += [os.path.join(ROOT, "tests", "pack_check.cpp"), os.path.join(CSRC, "pf_pack.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    assert b.returncode == 0, b.stdout + b.stderr
+    r = subprocess.run([exe], capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+    assert "pack_check: all checks passed" in r.stdout
