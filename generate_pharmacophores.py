@@ -34,6 +34,8 @@ _FLAGS = [
     ('--visualize_trajectory', dict(action='store_true', help='write every denoising frame, one xyz file per sample')),
     ('--pinned_centers', dict(type=Path, default=None, help='one xyz frame in the pharms.xyz format (elements P S F N O C): centers every sample must contain; the model places the others around them')),
     ('--pin_what', dict(choices=['both', 'position', 'type'], default='both', help='what of the pinned centers is fixed')),
+    ('--pin_resamples', dict(type=int, default=None, help='with --pinned_centers: denoise every stretch of --pin_jump levels this many times, re-noising it in between, so that the free centers can react to the pinned ones (default 1: no resampling; a run costs about this many times the steps)')),
+    ('--pin_jump', dict(type=int, default=None, help='with --pinned_centers: levels per resampled stretch (default 10)')),
     ('--metrics', dict(action='store_true', help='print the validity of the samples against receptor pharmacophore features')),
 ]
 
@@ -43,6 +45,14 @@ def parse_arguments(argv=None):
     for flag, kw in _FLAGS:
         parser.add_argument(flag, **kw)
     a = parser.parse_args(argv)
+    for flag in ('pin_resamples', 'pin_jump'):
+        v = getattr(a, flag)
+        if v is not None and a.pinned_centers is None:
+            parser.error(f'--{flag} needs --pinned_centers')
+        if v is not None and v < 1:
+            parser.error(f'--{flag} must be at least 1, got {v}')
+    a.pin_resamples = 1 if a.pin_resamples is None else a.pin_resamples
+    a.pin_jump = 10 if a.pin_jump is None else a.pin_jump
     problems = []
     if (a.ckpt is None) == (a.model_dir is None):
         problems.append('give exactly one of --ckpt and --model_dir')
@@ -141,7 +151,8 @@ def main(argv=None):
         copies = pfa.batch(pfa.copy_graph(pocket, n, pharm_feats_per_copy=sizes))
         com = pocket.pharm_x0.repeat(n, 1) if args.use_ref_lig_com else None
         with torch.no_grad():
-            pharms += model.sample_given_receptor(copies, init_pharm_com=com, visualize_trajectory=args.visualize_trajectory)
+            pharms += model.sample_given_receptor(copies, init_pharm_com=com, visualize_trajectory=args.visualize_trajectory,
+                                                  pin_resamples=args.pin_resamples, pin_jump=args.pin_jump)
     elapsed = time.time() - t0
 
     (pocket_dir / 'sample_time.txt').write_text(f'{elapsed:.2f}')

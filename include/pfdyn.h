@@ -94,6 +94,10 @@ typedef struct pf_step_coef {
  * (pharmacodiff.py:140-146), fp32, computed by the host */
 typedef struct pf_pin_coef { float alpha_s; float sigma_s; } pf_pin_coef;
 
+/* scalars of one resampling jump b -> a of a pinned run (pf_renoise_step): alpha_{a|b} and sigma_{a|b} of
+ * sigma_and_alpha_t_given_s(gamma(a/T), gamma(b/T)) (pharmacodiff.py:148-160), fp32, computed by the host */
+typedef struct pf_renoise_coef { float alpha_t_given_s; float sigma_t_given_s; } pf_renoise_coef;
+
 const char* pf_version(void);
 const char* pf_last_error(const pf_handle* h);     /* h may be NULL: last error of pf_create */
 
@@ -230,6 +234,40 @@ int pf_sample_pinned(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coe
                      const float* dev_noise, const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x,
                      const float* dev_pin_h, int32_t endpoint_param_coord, int32_t endpoint_param_feat, float feat_norm_constant,
                      float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream);
+
+/* -- pinned runs with resampling jumps (RePaint, Lugmayr et al. 2022; no reference counterpart) --------------------------------
+ * In a pinned run the given centers are drawn at every step independently of what the free centers just became.  Resampling lets
+ * the free centers react: after a stretch of reverse steps the whole state is diffused forward again to the stretch's upper noise
+ * level and the stretch is denoised again.  Let T be the number of timesteps, `jump` j >= 1 and `resamples` r >= 1.
+ * Levels run T -> 0.  Segment tops are a_0 = T and a_(k+1) = max(a_k - j, 0), until 0.  A segment is (a, b) with a > b; its length
+ * is j, except possibly the last one.  D(s) is the pinned denoise step with coefficient index s (t = s+1 -> s,
+ * pf_denoise_step_pinned); R(b->a) is the re-noise op (pf_renoise_step).  The plan of a run is, segment after segment from the top:
+ *     D(a-1) ... D(b),   then (r - 1) times:  R(b->a), D(a-1) ... D(b)
+ * The last segment, which ends at level 0, is resampled like the others.  r = 1 gives exactly D(T-1) ... D(0).
+ * Example, T = 7, j = 3, r = 2:   D6 D5 D4 R(4->7) D6 D5 D4 | D3 D2 D1 R(1->4) D3 D2 D1 | D0 R(0->1) D0   -- 17 ops.
+ * R(b->a) acts on every graph g and every center f of it, pinned and free centers alike, coordinates and feature rows alike:
+ *     z_a[f] = alpha_{a|b} * z_b[f] + sigma_{a|b} * noise[f]                     (one rounding per operation, no contraction)
+ * then the COM of all centers of the graph is removed from centers and protein (the reduction order of pf_denoise_step's update),
+ * and the dynamic edges of the next dynamics call are built on the new coordinates.  alpha_{a|b} and sigma_{a|b} come from
+ * sigma_and_alpha_t_given_s(gamma(a/T), gamma(b/T)), in fp32 on the host.  One forward jump over the whole segment is used, not j
+ * single steps: it has the same distribution and costs one launch.  No frame offset D[g] is needed, because nothing of the
+ * caller's frame enters.  A pinned center needs no special case: at level b it holds the given value noised to level b, the forward
+ * move gives it the right marginal at level a, and the following D op replaces it anyway.
+ * pf_renoise_step is valid only inside a pinned run (outside one: PF_ERR_STATE; a caller who wants resampling without pins begins a
+ * pinned run with all flags zero); a null argument is PF_ERR_ARG.  It makes no dynamics call: one launch (k_step_build_renoise: the
+ * move + the generic edge build; k_step_update_renoise for the width-generic family and every configuration whose next dynamics call
+ * builds its own edges), on the caller's stream, no host synchronisation.  pf_debug_kernel_family(h, n_convs) reports 0 after it.
+ * pf_sample_pinned_resampled: pf_sample_pinned's arguments with n_ops in place of n_steps, plus host_op[n_ops] (0 denoise, 1 renoise;
+ * anything else: PF_ERR_ARG before anything is enqueued) and host_renoise[n_ops].  host_coef[i] and host_pin_coef[i] are read for op
+ * kind 0, host_renoise[i] for kind 1; the other entries are ignored.  dev_noise is [n_ops + 1, Nf, 3 + pharm_nf]: row 0 is the
+ * initial draw and row 1 + i belongs to op i, whatever its kind.  A trajectory has n_ops + 1 frames; the last frame and x_0 / h_0
+ * carry the given values bit for bit.  Unpinned runs, and pinned runs without resampling, are not affected. */
+int pf_renoise_step(pf_handle* h, const pf_renoise_coef* coef, const float* dev_noise /*[Nf,3+pharm_nf]*/, pf_stream stream);
+int pf_sample_pinned_resampled(pf_handle* h, int32_t n_ops, const int32_t* host_op /*[n_ops]: 0 denoise, 1 renoise*/,
+                               const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef, const pf_renoise_coef* host_renoise /*[n_ops]*/,
+                               const float* dev_noise, const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x,
+                               const float* dev_pin_h, int32_t endpoint_param_coord, int32_t endpoint_param_feat, float feat_norm_constant,
+                               float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream);
 
 /* -- training step: gradients of the dynamics (autograd through PharmRecDynamicsGVP.forward, ------
  *    dynamics_gvp.py:131-185, as used by PharmacophoreDiff.forward / training_step, pharmacodiff.py:162-276)

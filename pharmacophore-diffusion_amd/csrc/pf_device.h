@@ -535,6 +535,11 @@ struct PinParams {
     const float* com_init;     // [B][3]    mean of the original protein coordinates (pf_sample_begin)
     float alpha_s, sigma_s, feat_norm;
 };
+// resampling jump of a pinned run (pf_renoise_step): z_a = alpha_ts * z_b + sigma_ts * noise; of StepParams it reads the graph
+// pointers, xn, pharm_h, noise and nf only
+struct RenoiseParams {
+    float alpha_ts, sigma_ts;  // alpha_{a|b}, sigma_{a|b} (pf_renoise_coef)
+};
 #ifdef __HIPCC__
 // The p(z_s | z_t) update of sample_p_zs_given_zt (pharmacodiff.py:397-426) for ONE value -- coordinate or feature -- and the only place
 // it is written: the generic update, the latency-optimised one (center threads / feature lanes) and the center hoist's copy all call

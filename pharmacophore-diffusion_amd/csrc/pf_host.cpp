@@ -65,6 +65,8 @@ void pfk_step_update(const StepParams* p, hipStream_t s);
 void pfk_step_build(const StepParams* sp, const BuildParams* bp, int fast, hipStream_t s);
 void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const BuildParams* bp, hipStream_t s);
 void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s);
+void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s);
+void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s);
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s);
@@ -2297,6 +2299,37 @@ int pf_denoise_step_pinned(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     return PF_OK;
 }
 
+// Resampling jump of a pinned run: the whole state goes from level b back up to level a with one launch and no dynamics call
+// (k_step_build_renoise: the forward move + the generic edge build; k_step_update_renoise where the next dynamics call builds its own edges)
+int pf_renoise_step(pf_handle* h, const pf_renoise_coef* coef, const float* dev_noise, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!coef || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_renoise_step: null argument");
+    if (!h->sampling || !h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_renoise_step outside a pinned run (pf_sample_begin_pinned)");
+    hipStream_t s = (hipStream_t)stream;
+    StepParams sp{};
+    sp.B = h->B; sp.Np_tot = h->Np; sp.prot_ptr = h->d_prot_ptr; sp.pharm_ptr = h->d_pharm_ptr;
+    sp.xn = h->d_xn; sp.pharm_h = h->d_pharm_h; sp.noise = dev_noise; sp.nf = h->cfg.pharm_nf;
+    RenoiseParams r{};
+    r.alpha_ts = coef->alpha_t_given_s; r.sigma_ts = coef->sigma_t_given_s;
+    ++h->step_id;
+    if (encoders_on_the_fly(h)) {           // forward move + the edges of the next dynamics call in one launch
+        const bool share = share_next(h);
+        const BuildParams bp = build_params(h, share);
+        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_build_renoise(&sp, &r, &bp, s); }
+        build_done(h, share);
+        h->edges_built = true;
+    } else {
+        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update_renoise(&sp, &r, s); }
+        h->edges_built = false; h->rec_valid = false;      // the centers moved: the next dynamics call builds
+    }
+    h->tail_done = false; h->last_tail = 0;
+    h->snap_cur = -1; h->cen_valid = false; h->spec_valid = false;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
 int pf_prepare_timesteps(pf_handle* h, const float* host_t, int32_t n, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
@@ -2352,16 +2385,22 @@ int pf_debug_xchg_fault(pf_handle* h, int32_t drop_word, int32_t poll_max) {
     return PF_OK;
 }
 
-// the whole loop of pf_sample / pf_sample_pinned (host_pin_coef != NULL: a pinned run with the three pin arrays)
+// the whole loop of pf_sample / pf_sample_pinned (host_pin_coef != NULL: a pinned run with the three pin arrays) /
+// pf_sample_pinned_resampled (host_op != NULL: op i is a denoising step, 0, or a resampling jump, 1; NULL: every op is a step)
 static int sample_loop(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef, const float* dev_noise,
                        const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h,
                        int32_t ep_coord, int32_t ep_feat, float feat_norm_constant,
-                       float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
+                       float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream,
+                       const int32_t* host_op = nullptr, const pf_renoise_coef* host_renoise = nullptr) {
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (n_steps < 0 || (n_steps && !host_coef) || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_sample: bad argument");
     const bool pinned = dev_pin_flags != nullptr;
     if (pinned && n_steps && !host_pin_coef) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null host_pin_coef");
+    for (int i = 0; host_op && i < n_steps; ++i) {
+        if (host_op[i] != 0 && host_op[i] != 1) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: op %d has kind %d (0 denoise, 1 renoise)", i, (int)host_op[i]);
+        if (host_op[i] == 1 && !host_renoise) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: null host_renoise");
+    }
     const size_t row = (size_t)h->Nf * (3 + h->cfg.pharm_nf);
     const size_t fx = (size_t)h->Nf * 3, fh = (size_t)h->Nf * h->cfg.pharm_nf;
     rc = pinned ? pf_sample_begin_pinned(h, dev_init_pharm_com, dev_noise, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, stream)
@@ -2372,14 +2411,17 @@ static int sample_loop(pf_handle* h, int32_t n_steps, const pf_step_coef* host_c
         if (rc) return rc;
     }
     {
-        std::vector<float> tv(n_steps);
-        for (int i = 0; i < n_steps; ++i) tv[i] = host_coef[i].t;
-        rc = pf_prepare_timesteps(h, tv.data(), n_steps, stream);
+        std::vector<float> tv;                  // the denoising steps' timesteps in op order
+        tv.reserve(n_steps);
+        for (int i = 0; i < n_steps; ++i) if (!host_op || host_op[i] == 0) tv.push_back(host_coef[i].t);
+        rc = pf_prepare_timesteps(h, tv.data(), (int32_t)tv.size(), stream);
         if (rc) return rc;
     }
     for (int i = 0; i < n_steps; ++i) {
-        rc = pinned ? pf_denoise_step_pinned(h, host_coef + i, host_pin_coef + i, dev_noise + (size_t)(i + 1) * row, ep_coord, ep_feat, stream)
-                    : pf_denoise_step(h, host_coef + i, dev_noise + (size_t)(i + 1) * row, ep_coord, ep_feat, stream);
+        const float* nz = dev_noise + (size_t)(i + 1) * row;
+        if (host_op && host_op[i] == 1) rc = pf_renoise_step(h, host_renoise + i, nz, stream);
+        else rc = pinned ? pf_denoise_step_pinned(h, host_coef + i, host_pin_coef + i, nz, ep_coord, ep_feat, stream)
+                         : pf_denoise_step(h, host_coef + i, nz, ep_coord, ep_feat, stream);
         if (rc) return rc;
         if (dev_traj_x || dev_traj_h) {
             rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x ? dev_traj_x + (size_t)(i + 1) * fx : nullptr,
@@ -2407,6 +2449,16 @@ int pf_sample_pinned(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coe
     if (h && (!dev_pin_flags || !dev_pin_x || !dev_pin_h)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null pin array");
     return sample_loop(h, n_steps, host_coef, host_pin_coef, dev_noise, dev_init_pharm_com, dev_pin_flags, dev_pin_x, dev_pin_h, ep_coord, ep_feat,
                        feat_norm_constant, dev_x0, dev_h0, dev_traj_x, dev_traj_h, stream);
+}
+
+int pf_sample_pinned_resampled(pf_handle* h, int32_t n_ops, const int32_t* host_op, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef,
+                               const pf_renoise_coef* host_renoise, const float* dev_noise, const float* dev_init_pharm_com,
+                               const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h, int32_t ep_coord, int32_t ep_feat,
+                               float feat_norm_constant, float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
+    if (h && (!dev_pin_flags || !dev_pin_x || !dev_pin_h)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: null pin array");
+    if (h && n_ops > 0 && !host_op) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: null host_op");
+    return sample_loop(h, n_ops, host_coef, host_pin_coef, dev_noise, dev_init_pharm_com, dev_pin_flags, dev_pin_x, dev_pin_h, ep_coord, ep_feat,
+                       feat_norm_constant, dev_x0, dev_h0, dev_traj_x, dev_traj_h, stream, host_op, host_renoise);
 }
 
 int64_t pf_debug_get_edges(pf_handle* h, int32_t etype, int32_t* host_src, int32_t* host_dst, int64_t capacity,

@@ -1937,6 +1937,97 @@ __global__ __launch_bounds__(256) void k_step_build_pinned(const StepParams sp, 
     __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
     build_body(bp, blockIdx.x);
 }
+// ---------------------------------------------------------------------------------------------
+// Resampling jump of a pinned run (pf_renoise_step): the whole state of graph g goes from level b back up to level a > b,
+// z_a = alpha_{a|b} * z_b + sigma_{a|b} * noise, for every center -- pinned or free -- and for coordinates and feature rows
+// alike; then the COM of all centers is removed from centers and protein in step_update_body's reduction order.  Nothing of the
+// caller's frame enters, so no protein mean is reduced in front.  A launch starts with cold caches and a dependent global round
+// trip is its unit of cost: after the graph's four pointers every row the thread needs -- its center's state and noise, its
+// first protein row -- is requested before the first barrier, and the updated coordinates stay in registers between the two
+// passes (only a graph of more than 256 centers reads the rows beyond the thread's first back, its own stores).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float pf_renoise_value(const float z, const float nz, const float alpha_ts, const float sigma_ts) {
+#pragma clang fp contract(off)
+    const float a = alpha_ts * z, n = sigma_ts * nz;
+    return a + n;
+}
+__device__ __forceinline__ void renoise_body(const StepParams& p, const RenoiseParams& r, const int g) {
+    __shared__ float com[3];
+    __shared__ float red[4][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
+    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
+    const int fa = f0 + tid, ia = p0 + tid;            // the thread's first center and first atom
+    const bool own_f = fa < f1, own_i = ia < p1;
+    float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (own_i) pa = p.xn[ia];                           // shifted behind the second barrier
+    float m[3] = {0.f, 0.f, 0.f};
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    if (own_f) {
+        const float* __restrict__ nz = p.noise + (size_t)fa * (3 + p.nf);
+        float* __restrict__ hr = p.pharm_h + (size_t)fa * p.nf;
+        const float4 xa = p.xn[p.Np_tot + fa];
+        const float nx[3] = {nz[0], nz[1], nz[2]};
+        float hv[8], nv[8];                             // the first eight features (pharm_nf is 6 in every shipped configuration)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const bool in = j < p.nf;
+            hv[j] = in ? hr[j] : 0.f; nv[j] = in ? nz[3 + j] : 0.f;
+        }
+        {   // every row is requested before the first wait (an empty asm the compiler cannot move the loads across, as in pf_stepbuild.h)
+            float pin = ((xa.x + xa.y) + (xa.z + nx[0])) + (nx[1] + nx[2]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pin += hv[j] + nv[j];
+            asm volatile("" :: "v"(pin), "v"(pa.x) : "memory");
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) if (j < p.nf) hr[j] = pf_renoise_value(hv[j], nv[j], r.alpha_ts, r.sigma_ts);
+        for (int k = 8; k < p.nf; ++k) hr[k] = pf_renoise_value(hr[k], nz[3 + k], r.alpha_ts, r.sigma_ts);
+        m[0] = pf_renoise_value(xa.x, nx[0], r.alpha_ts, r.sigma_ts);
+        m[1] = pf_renoise_value(xa.y, nx[1], r.alpha_ts, r.sigma_ts);
+        m[2] = pf_renoise_value(xa.z, nx[2], r.alpha_ts, r.sigma_ts);
+        sx += m[0]; sy += m[1]; sz += m[2];
+    }
+    for (int f = fa + 256; f < f1; f += 256) {          // more than 256 centers in the graph: through memory, as step_update_body does
+        const float4 x = p.xn[p.Np_tot + f];
+        const float* nz = p.noise + (size_t)f * (3 + p.nf);
+        const float q0 = pf_renoise_value(x.x, nz[0], r.alpha_ts, r.sigma_ts);
+        const float q1 = pf_renoise_value(x.y, nz[1], r.alpha_ts, r.sigma_ts);
+        const float q2 = pf_renoise_value(x.z, nz[2], r.alpha_ts, r.sigma_ts);
+        p.xn[p.Np_tot + f] = make_float4(q0, q1, q2, 0.f);
+        sx += q0; sy += q1; sz += q2;
+        for (int k = 0; k < p.nf; ++k)
+            p.pharm_h[(size_t)f * p.nf + k] = pf_renoise_value(p.pharm_h[(size_t)f * p.nf + k], nz[3 + k], r.alpha_ts, r.sigma_ts);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
+    __syncthreads();
+    if (tid == 0) {
+        const float n = (float)max(f1 - f0, 1);
+        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
+    }
+    __syncthreads();
+    const float cx = com[0], cy = com[1], cz = com[2];
+    if (own_f) p.xn[p.Np_tot + fa] = make_float4(m[0] - cx, m[1] - cy, m[2] - cz, 0.f);
+    for (int f = fa + 256; f < f1; f += 256) {
+        float4 x = p.xn[p.Np_tot + f];
+        x.x -= cx; x.y -= cy; x.z -= cz;
+        p.xn[p.Np_tot + f] = x;
+    }
+    if (own_i) { pa.x -= cx; pa.y -= cy; pa.z -= cz; p.xn[ia] = pa; }
+    for (int i = ia + 256; i < p1; i += 256) {
+        float4 x = p.xn[i];
+        x.x -= cx; x.y -= cy; x.z -= cz;
+        p.xn[i] = x;
+    }
+}
+__global__ __launch_bounds__(256) void k_step_update_renoise(const StepParams p, const RenoiseParams r) { renoise_body(p, r, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_step_build_renoise(const StepParams sp, const RenoiseParams r, const BuildParams bp) {
+    renoise_body(sp, r, blockIdx.x);
+    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
+    build_body(bp, blockIdx.x);
+}
 // the given values back, bit for bit (pf_sample_end and the last trajectory frame of a pinned run); out_x / out_h may be NULL
 __global__ void k_pin_restore(const int* __restrict__ flags, const float* __restrict__ pin_x, const float* __restrict__ pin_h,
                               const int n, const int nf, float* __restrict__ out_x, float* __restrict__ out_h) {
@@ -2114,6 +2205,14 @@ void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const Build
 void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s) {
     if (p->B == 0) return;
     hipLaunchKernelGGL(k_step_update_pinned, dim3(p->B), dim3(256), 0, s, *p, *q);
+}
+void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s) {
+    if (sp->B == 0) return;
+    hipLaunchKernelGGL(k_step_build_renoise, dim3(sp->B), dim3(256), 0, s, *sp, *r, *bp);
+}
+void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s) {
+    if (p->B == 0) return;
+    hipLaunchKernelGGL(k_step_update_renoise, dim3(p->B), dim3(256), 0, s, *p, *r);
 }
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s) {
     if (n == 0 || (!out_x && !out_h)) return;

@@ -351,6 +351,39 @@ class PfEngine:
             arr[i] = L.PfPinCoef(float(pin_coef["alpha_s"][s]), float(pin_coef["sigma_s"][s]))
         return arr
 
+    @staticmethod
+    def renoise_coef_array(renoise_coef: Dict[str, torch.Tensor], n=None):
+        """renoise_coef: per-pair tensors (schedule.renoise_coefficients); entry i of the array is pair i."""
+        n = len(renoise_coef["alpha_t_given_s"]) if n is None else n
+        arr = (L.PfRenoiseCoef * max(n, 1))()
+        for i in range(n):
+            arr[i] = L.PfRenoiseCoef(float(renoise_coef["alpha_t_given_s"][i]), float(renoise_coef["sigma_t_given_s"][i]))
+        return arr
+
+    @staticmethod
+    def plan_arrays(plan, coef, pin_coef, renoise_coef):
+        """The four host arrays of pf_sample_pinned_resampled for ``plan`` (schedule.resample_plan): (coef_arr, pin_coef_arr,
+        op_arr, renoise_arr), each with one entry per op.  coef / pin_coef: per-s tensors (coef_array / pin_coef_array);
+        renoise_coef: schedule.renoise_coefficients of the plan's renoise ops in plan order.  The entries an op's kind does
+        not read are zero."""
+        n = len(plan)
+        coef_arr, pin_arr = (L.PfStepCoef * max(n, 1))(), (L.PfPinCoef * max(n, 1))()
+        op_arr, re_arr = (ctypes.c_int32 * max(n, 1))(), (L.PfRenoiseCoef * max(n, 1))()
+        k = 0
+        for i, op in enumerate(plan):
+            if op[0] == "denoise":
+                s = op[1]
+                coef_arr[i] = L.PfStepCoef(float(coef["t"][s]), float(coef["alpha_t_given_s"][s]), float(coef["var_terms"][s]),
+                                           float(coef["sigma"][s]), float(coef["ep_zt"][s]), float(coef["ep_pred"][s]))
+                pin_arr[i] = L.PfPinCoef(float(pin_coef["alpha_s"][s]), float(pin_coef["sigma_s"][s]))
+            elif op[0] == "renoise":
+                op_arr[i] = 1
+                re_arr[i] = L.PfRenoiseCoef(float(renoise_coef["alpha_t_given_s"][k]), float(renoise_coef["sigma_t_given_s"][k]))
+                k += 1
+            else:
+                raise ValueError(f"op {i} of the plan is {op!r}: expected ('denoise', s) or ('renoise', b, a)")
+        return coef_arr, pin_arr, op_arr, re_arr
+
     def _pins(self, pins):
         """(flags [Nf] 0..3, positions [Nf,3] in the caller's frame, feature rows [Nf,pharm_nf]) as device tensors."""
         flags, px, ph = pins
@@ -392,6 +425,12 @@ class PfEngine:
             self._ck(self.lib.pf_denoise_step(self._h, ctypes.byref(coef_struct), _dptr(nz), int(ep_coord), int(ep_feat),
                                               _stream_ptr()), "pf_denoise_step")
 
+    def renoise_step(self, coef, noise):
+        """One resampling jump of a pinned run (pf_renoise_step): coef is a PfRenoiseCoef (an entry of renoise_coef_array)."""
+        nz = _f32(noise, self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_renoise_step(self._h, ctypes.byref(coef), _dptr(nz), _stream_ptr()), "pf_renoise_step")
+
     def sample_end(self, feat_norm_constant=1.0):
         """x_0 / h_0 of the run in progress (pf_sample_end); a pinned run returns its given values bit for bit."""
         x = torch.empty(self.Nf, 3, device=self.device)
@@ -410,8 +449,12 @@ class PfEngine:
         return x, hh
 
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
-               feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None):
-        """pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned."""
+               feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None):
+        """pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned.
+        plan = (op_arr, renoise_arr) (plan_arrays; n_steps is then the number of ops and coef_arr / pin_coef_arr have one entry
+        per op): pf_sample_pinned_resampled."""
+        if plan is not None and pins is None:
+            raise ValueError("a plan needs pins: resampling runs inside a pinned run (all flags zero pins nothing)")
         nz = _f32(noise, self.device)
         assert nz.shape[0] >= n_steps + 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
@@ -425,6 +468,16 @@ class PfEngine:
             if pin_coef_arr is None:
                 raise ValueError("a pinned run needs pin_coef_arr (PfEngine.pin_coef_array)")
             fl, px, ph = self._pins(pins)
+            if plan is not None:
+                op_arr, re_arr = plan
+                if len(op_arr) < n_steps or len(re_arr) < n_steps or len(coef_arr) < n_steps or len(pin_coef_arr) < n_steps:
+                    raise ValueError(f"a plan of {n_steps} ops needs {n_steps} entries in each of its four arrays")
+                with torch.cuda.device(self.device):
+                    self._ck(self.lib.pf_sample_pinned_resampled(self._h, n_steps, op_arr, coef_arr, pin_coef_arr, re_arr, _dptr(nz),
+                                                                 _dptr(com), _dptr(fl), _dptr(px), _dptr(ph), int(ep_coord), int(ep_feat),
+                                                                 float(feat_norm_constant), _dptr(x0), _dptr(h0), _dptr(tx), _dptr(th),
+                                                                 _stream_ptr()), "pf_sample_pinned_resampled")
+                return (x0, h0, tx, th) if trajectory else (x0, h0)
             with torch.cuda.device(self.device):
                 self._ck(self.lib.pf_sample_pinned(self._h, n_steps, coef_arr, pin_coef_arr, _dptr(nz), _dptr(com), _dptr(fl),
                                                    _dptr(px), _dptr(ph), int(ep_coord), int(ep_feat), float(feat_norm_constant),

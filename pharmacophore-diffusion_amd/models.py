@@ -28,8 +28,8 @@ import torch.nn.functional as F
 from .analysis import SampleAnalyzer, SampledPharmacophore
 from .engine import PfEngine
 from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_graph, get_batch_idxs, unbatch
-from .schedule import (PredefinedNoiseSchedule, alpha as _alpha, pin_coefficients, sigma as _sigma, sigma_and_alpha_t_given_s,
-                       step_coefficients)
+from .schedule import (PredefinedNoiseSchedule, alpha as _alpha, pin_coefficients, renoise_coefficients, resample_plan,
+                       sigma as _sigma, sigma_and_alpha_t_given_s, step_coefficients)
 
 try:  # subclass LightningModule when Lightning is importable (drop-in for train.py / load_from_checkpoint)
     import pytorch_lightning as pl
@@ -745,7 +745,7 @@ class PharmacophoreDiff(_Base):
     # -- sampling (pharmacodiff.py:433-514) ------------------------------------------------------
     @torch.no_grad()
     def sample_given_receptor(self, g, init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
-                              noise: torch.Tensor = None) -> List[SampledPharmacophore]:
+                              noise: torch.Tensor = None, pin_resamples: int = 1, pin_jump: int = 10) -> List[SampledPharmacophore]:
         """Reverse diffusion for a batch of pocket graphs; the whole T-step loop is enqueued on the
         current HIP stream by pf_sample (no host synchronisation inside the loop).
 
@@ -757,15 +757,38 @@ class PharmacophoreDiff(_Base):
 
         Pinned centers: when the graph carries ``pharm_pin`` / ``pharm_pin_x`` / ``pharm_pin_h`` with a non-zero flag, the
         run is pf_sample_pinned -- the flagged centers are replaced by the given values at every step's noise level and
-        come back bit for bit; the free centers are placed around them."""
-        return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, init_pharm_com, visualize_trajectory, noise)))
+        come back bit for bit; the free centers are placed around them.  With ``pin_resamples`` r > 1 such a run is
+        pf_sample_pinned_resampled: every stretch of ``pin_jump`` levels is re-noised to its upper level and denoised again,
+        r times in all (schedule.resample_plan), so that the free centers can react to the given ones; it has n_ops ~ r T ops
+        and ``noise`` must then have n_ops + 1 rows.  A graph batch without a flag set ignores both."""
+        return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, init_pharm_com, visualize_trajectory, noise,
+                                                                           pin_resamples=pin_resamples, pin_jump=pin_jump)))
 
-    def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0):
+    def _plan_arrays(self, jump: int, resamples: int):
+        """(n_ops, coef_arr, pin_coef_arr, op_arr, renoise_arr) of a resampled pinned run at this model's T: a few thousand
+        ctypes structs, built once per (T, jump, resamples)."""
+        key = (self.n_timesteps, int(jump), int(resamples))
+        if getattr(self, "_plan_arr", None) is None or self._plan_arr[0] != key:
+            T = self.n_timesteps
+            plan = resample_plan(T, jump, resamples)
+            pairs = [(op[1], op[2]) for op in plan if op[0] == "renoise"]
+            arrs = PfEngine.plan_arrays(plan, self.step_coefficients(), pin_coefficients(self.gamma.gamma, T),
+                                        renoise_coefficients(self.gamma.gamma, T, pairs))
+            self._plan_arr = (key, (len(plan),) + tuple(arrs))
+        return self._plan_arr[1]
+
+    def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0,
+                        pin_resamples: int = 1, pin_jump: int = 10):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
         current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine)."""
         g = as_pocket_graph(g)
         dev = self.device
         T, Nf, nf = self.n_timesteps, g.num_nodes("pharm"), self.n_pharm_feats
+        if pin_resamples < 1 or pin_jump < 1:
+            raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
+        has_pins = g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
+        if has_pins and pin_resamples > 1:
+            return self._sample_enqueue_resampled(g, init_pharm_com, visualize_trajectory, noise, lane, pin_resamples, pin_jump)
         if noise is None:
             noise = torch.randn(T + 1, Nf, 3 + nf, device=dev)
         if lane == 0:
@@ -791,6 +814,35 @@ class PharmacophoreDiff(_Base):
                          trajectory=visualize_trajectory, **pin_kw)
         # results go to pinned host memory with copies enqueued right behind the batch's kernels, and an event marks their
         # completion: whatever is enqueued afterwards (the next batch) does not delay the fetch of this one
+        host = tuple(None if r is None else torch.empty(r.shape, dtype=r.dtype, pin_memory=True).copy_(r, non_blocking=True)
+                     for r in res)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        return g, host, visualize_trajectory, done, eng
+
+    def _sample_enqueue_resampled(self, g, init_pharm_com, visualize_trajectory, noise, lane, pin_resamples, pin_jump):
+        """_sample_enqueue for a batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled."""
+        dev = self.device
+        Nf, nf = g.num_nodes("pharm"), self.n_pharm_feats
+        n_ops, arr, parr, op_arr, re_arr = self._plan_arrays(pin_jump, pin_resamples)
+        if noise is None:
+            noise = torch.randn(n_ops + 1, Nf, 3 + nf, device=dev)
+        elif noise.shape[0] != n_ops + 1:
+            raise ValueError(f"a resampled pinned run of {n_ops} ops (T = {self.n_timesteps}, jump {pin_jump}, resamples {pin_resamples}) "
+                             f"needs {n_ops + 1} noise rows, got {noise.shape[0]}")
+        if lane == 0:
+            eng = self.dynamics.bind_graph(g)
+        else:
+            eng = self.dynamics.lane_engine(lane)
+            eng.set_batch(g.prot_x, g.prot_h, g.prot_ptr, g.pharm_ptr, g.pp_src, g.pp_dst, pocket_uid=g.pocket_uid)
+        com = None
+        if init_pharm_com is not None:
+            com = init_pharm_com if init_pharm_com.is_cuda else init_pharm_com.float().pin_memory().to(dev, non_blocking=True)
+        res = eng.sample(arr, n_ops, noise if noise.is_cuda else noise.float().pin_memory().to(dev, non_blocking=True),
+                         init_pharm_com=com, ep_coord=self.endpoint_param_coord,
+                         ep_feat=self.endpoint_param_feat, feat_norm_constant=float(self.pharm_feat_norm_constant),
+                         trajectory=visualize_trajectory, pins=(g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h), pin_coef_arr=parr,
+                         plan=(op_arr, re_arr))
         host = tuple(None if r is None else torch.empty(r.shape, dtype=r.dtype, pin_memory=True).copy_(r, non_blocking=True)
                      for r in res)
         done = torch.cuda.Event()
@@ -853,7 +905,7 @@ class PharmacophoreDiff(_Base):
     def sample(self, ref_graphs: List[PocketGraph], n_pharms: List[List[int]], max_batch_size: int = 32,
                init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
                rank: int = 0, world_size: int = 1, noise=None, lanes: int = None,
-               pinned=None) -> List[List[SampledPharmacophore]]:
+               pinned=None, pin_resamples: int = 1, pin_jump: int = 10) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -871,6 +923,11 @@ class PharmacophoreDiff(_Base):
         of that pocket is completed around these k centers, which are its first k (flag bit 0: position given, bit 1: type
         given; None = both).  Raises ValueError when a requested size is below k.
 
+        ``pin_resamples`` r, ``pin_jump`` j: with r > 1 every batch holding a pinned graph runs with resampling jumps
+        (schedule.resample_plan(T, j, r): n_ops ~ r T ops instead of T, i.e. about r times the work of a pinned run), so that the
+        free centers can react to the given ones; its noise has n_ops + 1 rows.  Batches of free graphs run the default path with
+        T + 1 rows, as without them.
+
         ``lanes`` (default ``self.sample_lanes``; None = 2, or 4 when the batches hold at most 32 graphs): batches in flight at
         once, each on its own HIP stream and handle.  Four of
         the five launches of a batched step occupy part of the chip, so independent batches overlap (2 lanes: +16 % at
@@ -880,6 +937,8 @@ class PharmacophoreDiff(_Base):
         n_receptors = len(ref_graphs)
         if n_receptors == 0:
             return []
+        if pin_resamples < 1 or pin_jump < 1:
+            raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
         if pinned is not None:
             ref_graphs = self._with_pins(ref_graphs, n_pharms, pinned)
         if init_pharm_com is None:
@@ -936,13 +995,17 @@ class PharmacophoreDiff(_Base):
             init_coms = coms_dev[idx[0]:idx[-1] + 1]
             lane = k % n_lanes
             with torch.cuda.stream(streams[lane]):
+                rows = T + 1
+                if pin_resamples > 1 and batch_g.pharm_pin is not None and bool((batch_g.pharm_pin != 0).any()):
+                    rows = self._plan_arrays(pin_jump, pin_resamples)[0] + 1
                 if noise is None:
                     gen = torch.Generator(device=self.device).manual_seed(base_seed + bi)
-                    nz = torch.randn(T + 1, batch_g.num_nodes("pharm"), 3 + nf, device=self.device, generator=gen)
+                    nz = torch.randn(rows, batch_g.num_nodes("pharm"), 3 + nf, device=self.device, generator=gen)
                 else:
                     nz = noise[bi]
                 # the bind is asynchronous (stream-ordered behind the lane's previous batch), nothing here waits for the device
-                enq = self._sample_enqueue(batch_g, init_coms, visualize_trajectory, nz, lane=lane)
+                enq = self._sample_enqueue(batch_g, init_coms, visualize_trajectory, nz, lane=lane,
+                                           pin_resamples=pin_resamples, pin_jump=pin_jump)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on

@@ -96,3 +96,41 @@ def pin_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, tor
     s = s_int.float() / timesteps
     g_s = g[torch.round(s * timesteps).long()]
     return {"alpha_s": alpha(g_s), "sigma_s": sigma(g_s)}
+
+
+def resample_plan(timesteps: int, jump: int, resamples: int):
+    """The op list of a pinned run with resampling jumps (include/pfdyn.h, "pinned runs with resampling jumps"): levels run
+    T -> 0 in segments (a, b) of length ``jump`` (the last one possibly shorter); every segment is denoised, D(a-1) ... D(b), and
+    then ``resamples`` - 1 times re-noised from b back up to a and denoised again.  Returns ("denoise", s) and
+    ("renoise", b, a) tuples; resamples = 1 gives D(T-1) ... D(0)."""
+    if jump < 1:
+        raise ValueError(f"jump must be at least 1, got {jump}")
+    if resamples < 1:
+        raise ValueError(f"resamples must be at least 1, got {resamples}")
+    plan, a = [], int(timesteps)
+    while a > 0:
+        b = max(a - int(jump), 0)
+        down = [("denoise", s) for s in range(a - 1, b - 1, -1)]
+        plan += down
+        for _ in range(int(resamples) - 1):
+            plan.append(("renoise", b, a))
+            plan += down
+        a = b
+    return plan
+
+
+def renoise_coefficients(gamma_table: torch.Tensor, timesteps: int, pairs) -> Dict[str, torch.Tensor]:
+    """alpha_{a|b} and sigma_{a|b} of the forward jump from level b up to level a > b, for every (b, a) of ``pairs`` (index =
+    position in pairs), fp32 on the host: sigma_and_alpha_t_given_s(gamma(a / T), gamma(b / T)) -- what pf_renoise_step moves the
+    whole state with, z_a = alpha_{a|b} z_b + sigma_{a|b} noise."""
+    g = gamma_table.detach().float().cpu()
+    pairs = [(int(b), int(a)) for b, a in pairs]
+    for b, a in pairs:
+        if not 0 <= b < a <= timesteps:
+            raise ValueError(f"a re-noise pair must satisfy 0 <= b < a <= {timesteps}, got ({b}, {a})")
+    b_int = torch.tensor([p[0] for p in pairs], dtype=torch.long)
+    a_int = torch.tensor([p[1] for p in pairs], dtype=torch.long)
+    g_b = g[torch.round(b_int.float() / timesteps * timesteps).long()]
+    g_a = g[torch.round(a_int.float() / timesteps * timesteps).long()]
+    _, s_ab, a_ab, _ = sigma_and_alpha_t_given_s(g_a, g_b)
+    return {"alpha_t_given_s": a_ab, "sigma_t_given_s": s_ab}
