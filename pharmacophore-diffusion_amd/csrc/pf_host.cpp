@@ -17,6 +17,7 @@
 
 #include "../../include/pfdyn.h"
 #include "pf_device.h"
+#include "pf_bind.h"
 #include "pf_pack.h"
 #include "pf_train.h"
 
@@ -254,8 +255,8 @@ struct pf_handle {
     int B = 0, Np = 0, Nf = 0, N = 0;
     int64_t Epp = 0, Ecap = 0;
     std::vector<int> h_prot_ptr, h_pharm_ptr;
-    std::vector<int> h_reg;                 // [3][B]
-    std::vector<int> h_cap;                 // [3][B]
+    std::vector<int> h_reg;                 // [4][B] first slot of the ff, pf, fp and pa regions
+    std::vector<int> h_cap;                 // [4][B] ... and their capacities
     int n_edge_tiles = 0, n_node_tiles = 0, n_head_tiles = 0;
     int zero_row = 0;
     int n_edge_tiles_last = 0, n_node_tiles_last = 0;
@@ -567,6 +568,32 @@ static T* carve(char*& cur, size_t count) {
     bytes = (bytes + 255) & ~size_t(255);
     cur += bytes;
     return p;
+}
+
+// One list for sizes and pointers: a workspace's buffers are one sequence of take() calls that runs twice -- first over a
+// dummy base, which only counts the bytes, then over the allocation, which hands the pointers out
+struct Carver {
+    char* const base;
+    char* cur;
+    const bool assign;
+    explicit Carver(void* allocation) : base(allocation ? static_cast<char*>(allocation) : reinterpret_cast<char*>(uintptr_t(256))), cur(base), assign(allocation != nullptr) {}
+    template <typename T>
+    void take(T*& dst, size_t n) { T* q = carve<T>(cur, n); if (assign) dst = q; }
+    size_t bytes() const { return (size_t)(cur - base); }
+};
+
+// An allocation that outlives the batches (a hipFree / hipMalloc pair of a few hundred MB per batch costs milliseconds, and
+// a training loop binds a new batch every step): kept while *cap >= need, else replaced by one of `want` bytes -- the head
+// room that lets the next batch of similar size fit.  Launches of earlier batches may still read a device buffer, so
+// replacing one waits for the device; a pinned host buffer's reader is the caller's to wait for.  *grew: the contents are gone.
+static int grow_buffer(pf_handle* h, void** buf, size_t* cap, size_t need, size_t want, bool pinned, bool* grew = nullptr) {
+    if (*cap >= need) return PF_OK;
+    if (!pinned) PF_HIP(h, hipDeviceSynchronize());
+    if (*buf) { (void)(pinned ? hipHostFree(*buf) : hipFree(*buf)); *buf = nullptr; *cap = 0; }
+    PF_HIP(h, pinned ? hipHostMalloc(buf, want, hipHostMallocDefault) : hipMalloc(buf, want));
+    *cap = want;
+    if (grew) *grew = true;
+    return PF_OK;
 }
 
 struct ProfScope {
@@ -1545,292 +1572,115 @@ int pf_commit_weights(pf_handle* h) {
     return PF_OK;
 }
 
-// prot_x / prot_h come either as device pointers (copied on the stream) or as host pointers (staged with the tables)
-// pf_set_pocket_batch's pass over the pp edges for the common case -- destination-sorted, every edge inside its graph -- with
-// 8 edges per instruction (a training loop binds a new batch every step: 0.65 M edges at 256 pockets, and the bind is on the
-// step's host-side critical path).  Returns false when anything is unusual (unsorted, out of range, an edge across graphs):
-// the scalar pass then runs and reports.  On success start[d] (d = 0 .. Np) = index of the first edge whose destination
-// is >= d, i.e. the in-edge ranges of a destination-sorted list.
-#if defined(__x86_64__)
-#include <immintrin.h>
-__attribute__((target("avx2"))) static bool pp_edges_fast_avx2(const int* src, const int* dst, int64_t n, const int* prot_ptr, int B, int Np,
-                                                                int* start) {
-    if (n <= 0 || dst[0] < 0 || dst[n - 1] >= Np) return false;
-    // sortedness + boundaries in one sweep: a boundary after edge e (dst[e] < dst[e + 1]) starts the ranges of nodes dst[e] + 1 .. dst[e + 1]
-    for (int d = 0; d <= dst[0]; ++d) start[d] = 0;
-    int64_t e = 0;
-    for (; e + 8 < n; e += 8) {
-        const __m256i a = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(dst + e));
-        const __m256i b = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(dst + e + 1));
-        if (_mm256_movemask_epi8(_mm256_cmpgt_epi32(a, b))) return false;                       // descending somewhere
-        unsigned m = (unsigned)_mm256_movemask_ps(_mm256_castsi256_ps(_mm256_cmpgt_epi32(b, a)));
-        while (m) {
-            const int k = __builtin_ctz(m);
-            m &= m - 1;
-            const int lo = dst[e + k], hi = dst[e + k + 1];
-            for (int d = lo + 1; d <= hi; ++d) start[d] = (int)(e + k + 1);
-        }
-    }
-    for (; e + 1 < n; ++e) {
-        if (dst[e] > dst[e + 1]) return false;
-        for (int d = dst[e] + 1; d <= dst[e + 1]; ++d) start[d] = (int)(e + 1);
-    }
-    for (int d = dst[n - 1] + 1; d <= Np; ++d) start[d] = (int)n;
-    // every source inside the atom range of its destination's graph (the destinations of graph g are the edges start[p0] .. start[p1])
-    for (int g = 0; g < B; ++g) {
-        const int lo = prot_ptr[g], hi = prot_ptr[g + 1];
-        const int64_t a = start[lo], b = start[hi];
-        const __m256i vlo = _mm256_set1_epi32(lo), vhi = _mm256_set1_epi32(hi);
-        __m256i bad = _mm256_setzero_si256();
-        int64_t i = a;
-        for (; i + 8 <= b; i += 8) {
-            const __m256i x = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(src + i));
-            bad = _mm256_or_si256(bad, _mm256_or_si256(_mm256_cmpgt_epi32(vlo, x), _mm256_cmpgt_epi32(x, _mm256_sub_epi32(vhi, _mm256_set1_epi32(1)))));
-        }
-        if (_mm256_movemask_epi8(bad)) return false;
-        for (; i < b; ++i) if (src[i] < lo || src[i] >= hi) return false;
-    }
-    return true;
+// The bind's point of no return: the handle's fields take the plan's values, all in this one place.  The previous batch is gone
+// (its training workspaces stay allocated and are carved again), and have_batch stays false until the bind has enqueued everything.
+static void adopt_plan(pf_handle* h, const pfbind::BindPlan& p, const pfbind::BindInputs& in) {
+    const int B = p.B;
+    h->have_batch = false;
+    free_ws(h, true);
+    h->B = B; h->Np = p.Np; h->Nf = p.Nf; h->N = p.N; h->Epp = p.n_pp; h->Ecap = p.Ecap;
+    h->h_prot_ptr.assign(in.prot_ptr, in.prot_ptr + B + 1);
+    h->h_pharm_ptr.assign(in.pharm_ptr, in.pharm_ptr + B + 1);
+    h->max_np = p.max_np; h->max_nf = p.max_nf;
+    h->h_reg = p.h_reg; h->h_cap = p.h_cap;
+    std::copy(p.et_tile0, p.et_tile0 + 5, h->et_tile0);
+    std::copy(p.et_tile0_act, p.et_tile0_act + 5, h->et_tile0_act);
+    h->n_edge_tiles = p.n_edge_tiles; h->n_node_tiles = p.n_node_tiles; h->n_head_tiles = p.n_head_tiles;
+    h->n_edge_tiles_last = p.n_edge_tiles_last; h->n_node_tiles_last = p.n_node_tiles_last;
+    h->n_edge_tiles_act = p.n_edge_tiles_act; h->n_node_tiles_act = p.n_node_tiles_act;
+    h->share_ok = false; h->share_rows = 0;
+    h->h_share_start.assign(B, 0); h->h_share_cnt.assign(B, 0);
 }
-static bool pp_edges_fast(const int* src, const int* dst, int64_t n, const int* prot_ptr, int B, int Np, int* start) {
-    static const bool ok = __builtin_cpu_supports("avx2") && getenv("PFDYN_NO_AVX2") == nullptr;
-    return ok && pp_edges_fast_avx2(src, dst, n, prot_ptr, B, Np, start);
-}
-#else
-static bool pp_edges_fast(const int*, const int*, int64_t, const int*, int, int, int*) { return false; }
-#endif
 
+// Every per-batch device pointer of the handle, from the plan's offsets: table section (tbase: the table buffer of this bind), zero
+// section and scratch (base: the workspace); with them the flags that say what those buffers hold -- nothing yet.
+static void set_batch_pointers(pf_handle* h, const pfbind::BindPlan& p, char* base, char* tbase) {
+    const pf_config& c = h->cfg;
+    const int Nf = p.Nf;
+    auto at = [&](size_t o) { return base + o; };
+    auto tat = [&](size_t o) { return tbase + o; };
+    const pfbind::TableOff& ot = p.t;
+    const pfbind::ZeroOff& oz = p.z;
+    const pfbind::ScratchOff& os = p.s;
+    h->d_prot_ptr = (int*)tat(ot.pptr); h->d_pharm_ptr = (int*)tat(ot.fptr); h->d_gid = (int*)tat(ot.gid); h->d_reg = (int*)tat(ot.reg);
+    h->d_reg_act = (int*)tat(ot.regact); h->d_edge_tiles_act = (EdgeTile*)tat(ot.eta); h->d_node_tiles_act = (NodeTile*)tat(ot.nta);
+    h->d_esrc = (int*)tat(ot.esrc); h->d_edst = (int*)tat(ot.edst); h->d_in_start = (int*)tat(ot.ins); h->d_in_cnt = (int*)tat(ot.inc);
+    h->d_pp_cnt = (int*)tat(ot.ppc); h->d_edge_tiles = (EdgeTile*)tat(ot.et); h->d_node_tiles = (NodeTile*)tat(ot.nt);
+    h->d_head_tiles = (NodeTile*)tat(ot.ht); h->d_pfq_cnt = p.pfq.empty() ? nullptr : (int*)tat(ot.pfq);
+    h->d_reg_share = (int*)tat(ot.regs); h->d_pa_static = (int*)tat(ot.pas); h->d_rep_base = (int*)tat(ot.repb); h->d_need = (int*)at(oz.need);
+    h->need_stamp = 0; h->edges_stamp = 0;
+    h->d_dyn_cnt = (int*)at(oz.dyn); h->d_act_ids = (int*)at(oz.act); h->d_l0flag = (int*)at(oz.flag); h->d_gnorm = (float*)at(oz.gnorm);
+    h->d_xn = (float4*)at(os.xn); h->d_prot_x0 = (float*)tat(ot.px0); h->d_prot_h0 = (float*)tat(ot.ph0); h->d_pharm_h = (float*)at(os.fh);
+    h->d_t = (float*)at(os.t); h->d_h[0] = (float*)at(os.h0); h->d_h[1] = (float*)at(os.h1); h->d_v[0] = (float*)at(os.v0); h->d_v[1] = (float*)at(os.v1);
+    h->d_msg_s2 = p.msg2 ? (float*)at(os.ms2) : nullptr; h->d_msg_v2 = p.msg2 ? (float*)at(os.mv2) : nullptr;
+    h->d_msg_s = (float*)at(os.ms); h->d_msg_v = (float*)at(os.mv); h->d_eps_h = (float*)at(os.eh); h->d_eps_x = (float*)at(os.ex);
+    h->d_com_init = (float*)at(os.c0); h->d_com_tmp = (float*)at(os.c1); h->d_pre = (float*)at(os.pre); h->d_eorig = (int*)at(os.eorig);
+    h->d_ptype = (int*)at(os.ptype); h->d_zs = (float*)at(os.zs); h->d_ptab_pg = (float*)at(os.ptpg);
+    h->d_rec = (h->pol.edge_rec && p.rec_slots > 0) ? (int4*)at(os.rec) : nullptr; h->rec_valid = false;
+    h->d_xchg = (unsigned int*)at(os.xchg); h->d_lpart = (float*)at(oz.lpart);
+    h->d_xchg2 = h->d_xchg + (size_t)std::max(Nf, 1) * PF_XCHG_STRIDE;
+    h->d_cen_h = (float*)at(os.cenh); h->d_cen_p = (float*)at(os.cenp);
+    h->d_snap[0] = (float*)at(os.snap); h->d_snap[1] = h->d_snap[0] + (size_t)std::max(Nf, 1) * c.pharm_nf + 4;
+    h->cen_valid = false; h->snap_cur = -1;
+    h->d_pa_stamp = (int*)at(oz.pastamp); h->d_pa_same = (int*)at(oz.pasame); h->spec_valid = false; h->e0_saved = false;
+    h->d_pa_cnt = (int*)at(oz.pacnt); h->d_pa_gstamp = h->pa_check ? (int*)at(oz.pagst) : nullptr;
+}
+
+// prot_x / prot_h come either as device pointers (copied on the stream) or as host pointers (staged with the tables).
+// The arithmetic is pf_bind.cpp's (host only, checked on the CPU by tests/bind_check.cpp); this function owns the handle,
+// the HIP resources and the enqueueing.
 static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_ptr, const int32_t* pharm_ptr,
                                  const float* dev_prot_x, const float* dev_prot_h, const float* host_prot_x, const float* host_prot_h,
                                  int64_t n_pp, const int32_t* pp_src, const int32_t* pp_dst, pf_stream stream) {
-    // the pocket-group claim (pf_set_pocket_groups) belongs to THIS bind: it is taken off the handle before anything can
-    // fail, so that a rejected bind never leaves it behind for the next, unrelated batch
-    std::vector<int> rep_claim;
-    if (h) rep_claim.swap(h->pending_rep);
+    // ---- 1. the pocket-group claim (pf_set_pocket_groups) belongs to THIS bind: it is taken off the handle before anything
+    // can fail, so that a rejected bind never leaves it behind for the next, unrelated batch
+    pfbind::BindInputs in;
+    if (h) in.rep.swap(h->pending_rep);
     int rc = check_ready(h, false);
     if (rc) return rc;
     const bool from_host = host_prot_x != nullptr;
-    if (B < 1 || !prot_ptr || !pharm_ptr || (from_host ? !host_prot_h : (!dev_prot_x || !dev_prot_h)) || n_pp < 0 ||
-        (n_pp && (!pp_src || !pp_dst)))
-        PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch: bad argument");
+    if (from_host ? !host_prot_h : (!dev_prot_x || !dev_prot_h)) PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch: bad argument");
     hipStream_t s = (hipStream_t)stream;
     const pf_config& c = h->cfg;
-    if (prot_ptr[0] != 0 || pharm_ptr[0] != 0) PF_FAIL(h, PF_ERR_ARG, "ptr arrays must start at 0");
-    for (int g = 0; g < B; ++g) {
-        if (prot_ptr[g + 1] < prot_ptr[g] || pharm_ptr[g + 1] < pharm_ptr[g]) PF_FAIL(h, PF_ERR_ARG, "ptr arrays must be non-decreasing");
-        if (pharm_ptr[g + 1] - pharm_ptr[g] > PF_MAXF)
-            PF_FAIL(h, PF_ERR_ARG, "graph %d has %d pharmacophore centers (limit %d)", g, pharm_ptr[g + 1] - pharm_ptr[g], PF_MAXF);
-    }
     static const bool timing = getenv("PFDYN_TIMING") != nullptr;
     double tm[8] = {0}; int tmi = 0;
     auto now = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     auto mark = [&] { if (timing && tmi < 8) tm[tmi++] = now(); };
     mark();
-    const int Np = prot_ptr[B], Nf = pharm_ptr[B], N = Np + Nf;
-    // ---- host-side tables
-    std::vector<int> gid(N);
-    int max_np = 0, max_nf = 0;
-    for (int g = 0; g < B; ++g) {
-        max_np = std::max(max_np, prot_ptr[g + 1] - prot_ptr[g]);
-        max_nf = std::max(max_nf, pharm_ptr[g + 1] - pharm_ptr[g]);
-        for (int i = prot_ptr[g]; i < prot_ptr[g + 1]; ++i) gid[i] = g;
-        for (int i = pharm_ptr[g]; i < pharm_ptr[g + 1]; ++i) gid[Np + i] = g;
+    // ---- 2. the plan: every argument check runs before the previous batch's state is touched -- a rejected bind leaves the
+    // handle as it was
+    in.cfg = c; in.B = B; in.prot_ptr = prot_ptr; in.pharm_ptr = pharm_ptr; in.n_pp = n_pp; in.pp_src = pp_src; in.pp_dst = pp_dst;
+    in.host_rows = from_host; in.host_prot_x = host_prot_x; in.host_prot_h = host_prot_h;
+    in.spec = h->spec; in.wide = h->wide; in.pa_check = h->pa_check; in.edge_rec = h->pol.edge_rec; in.n16_rows_max = h->pol.n16_rows_max;
+#if defined(__x86_64__)
+    static const bool avx2 = __builtin_cpu_supports("avx2") && getenv("PFDYN_NO_AVX2") == nullptr;
+    in.allow_avx2 = avx2;
+#endif
+    pfbind::BindPlan p;
+    pfbind::BindError berr;
+    rc = pfbind::plan_batch(in, p, berr);
+    if (rc) {
+        if (berr.batch_lost) free_ws(h, true);         // (a batch too large for the edge slots' indices: the one rejection that drops the previous batch)
+        h->err = berr.msg;
+        return rc;
     }
-    // every argument check runs before the previous batch's state is touched: a rejected bind leaves the handle as it was.
-    // One pass over the pp edges checks them and counts the in-degrees (a training loop binds a new batch every step and
-    // this function is most of that step's host time): the graph of an edge is looked up only when the destination leaves
-    // the atom range of the previous edge's graph -- edge lists come grouped by destination.
-    std::vector<int> deg(Np + 1, 0);
-    bool dst_sorted = true;                    // radius_graph and pf_build_pp_edges emit the edges grouped by destination, ascending:
-    const bool deg_is_prefix = pp_edges_fast(pp_src, pp_dst, n_pp, prot_ptr, B, Np, deg.data());     // (the common case, 8 edges at a time)
-    if (!deg_is_prefix) {                      // the stable sort below is then the identity and is skipped
-        std::fill(deg.begin(), deg.end(), 0);
-        // (per-edge increments, no branch on a change of destination: counting per run of equal destinations costs a
-        // mispredicted branch per atom and measured 0.3 ms slower at 256 pockets)
-        int prev_dst = -1, lo = 0, hi = 0;
-        for (int64_t e = 0; e < n_pp; ++e) {
-            const int sn = pp_src[e], dn = pp_dst[e];
-            if ((unsigned)sn >= (unsigned)Np || (unsigned)dn >= (unsigned)Np) PF_FAIL(h, PF_ERR_ARG, "pp edge %lld out of range", (long long)e);
-            if (dn < lo || dn >= hi) { const int g = gid[dn]; lo = prot_ptr[g]; hi = prot_ptr[g + 1]; }
-            if (sn < lo || sn >= hi) PF_FAIL(h, PF_ERR_ARG, "pp edge %lld crosses graphs", (long long)e);
-            dst_sorted &= dn >= prev_dst;
-            prev_dst = dn;
-            deg[dn + 1]++;
-        }
-    }
-    if (c.message_norm_mode == PF_NORM_GRAPH && c.pf_k > 0)
-        for (int g = 0; g < B; ++g)
-            if (std::min(c.pf_k, prot_ptr[g + 1] - prot_ptr[g]) > 0 && pharm_ptr[g + 1] > pharm_ptr[g] && pharm_ptr[g + 1] - 1 >= Np)
-                PF_FAIL(h, PF_ERR_ARG, "message_norm 0 with kNN pf edges: center index %d >= %d protein atoms "
-                        "(the reference indexes the protein batch vector with it, dynamics_gvp.py:220)", pharm_ptr[g + 1] - 1, Np);
-    if (!rep_claim.empty() && (int)rep_claim.size() != B)
-        PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups named %d graphs, this batch has %d", (int)rep_claim.size(), B);
-    // from here on the handle describes the new batch (a failure below -- a false pocket-group claim, a failing HIP call --
-    // leaves it without a batch: loud, never the previous one's tables under the new sizes)
-    h->have_batch = false;
-    free_ws(h, true);
-    h->B = B; h->Np = Np; h->Nf = Nf; h->N = N; h->Epp = n_pp;
-    h->h_prot_ptr.assign(prot_ptr, prot_ptr + B + 1);
-    h->h_pharm_ptr.assign(pharm_ptr, pharm_ptr + B + 1);
-    h->max_np = max_np; h->max_nf = max_nf;
-    if (!deg_is_prefix)
-        for (int i = 0; i < Np; ++i) deg[i + 1] += deg[i];
-    std::vector<int> pp_cnt(B, 0);
-    // message_norm == 0 with kNN pf edges: the reference derives the per-graph pf / fp edge counts by looking the
-    // pharmacophore-CENTER index of every edge up in the PROTEIN batch vector (dynamics_gvp.py:220), i.e. the min(k, Np_g)
-    // edges of center j are booked on the graph that owns protein atom j.  gvp.py:506 normalises with those counts, so
-    // they are reproduced (a pure function of the ptr arrays); the reference raises an IndexError when j >= Np_tot.
-    std::vector<int> pfq;
-    if (c.message_norm_mode == PF_NORM_GRAPH && c.pf_k > 0) {
-        pfq.assign(B, 0);
-        for (int g = 0; g < B; ++g) {
-            const int kg = std::min(c.pf_k, prot_ptr[g + 1] - prot_ptr[g]);
-            for (int j = pharm_ptr[g]; j < pharm_ptr[g + 1] && kg > 0; ++j) {
-                if (j >= Np) PF_FAIL(h, PF_ERR_ARG, "message_norm 0 with kNN pf edges: center index %d >= %d protein atoms "
-                                     "(the reference indexes the protein batch vector with it, dynamics_gvp.py:220)", j, Np);
-                pfq[gid[j]] += kg;
-            }
-        }
-    }
-    // capacity of dynamic regions: ff, pf, fp and "pa" = compact copy of the pp edges into the active atoms
-    h->h_reg.assign((size_t)4 * B, 0);
-    h->h_cap.assign((size_t)4 * B, 0);
-    std::vector<int> reg_act(B, 0), cap_act(B, 0), maxdeg(B, 0), epp_g(B, 0);
-    for (int i = 0; i < Np; ++i) {
-        maxdeg[gid[i]] = std::max(maxdeg[gid[i]], deg[i + 1] - deg[i]);
-        epp_g[gid[i]] += deg[i + 1] - deg[i];
-    }
-    int64_t cursor = n_pp;
-    int act_total = 0;
-    for (int et = 0; et < 4; ++et)
-        for (int g = 0; g < B; ++g) {
-            const int np = prot_ptr[g + 1] - prot_ptr[g], nf = pharm_ptr[g + 1] - pharm_ptr[g];
-            const int nact = c.pf_k > 0 ? std::min(np, nf * std::min(c.pf_k, np)) : (nf > 0 ? np : 0);
-            int cap;
-            if (et == ET_FF) cap = c.ff_k > 0 ? nf * std::min(c.ff_k, std::max(nf - 1, 0)) : nf * std::max(nf - 1, 0);
-            else if (et < 3) cap = c.pf_k > 0 ? nf * std::min(c.pf_k, np) : nf * np;
-            else {
-                cap = (int)std::min<int64_t>(epp_g[g], (int64_t)nact * maxdeg[g]);
-                reg_act[g] = act_total; cap_act[g] = nact; act_total += nact;
-            }
-            cursor = (cursor + 31) & ~int64_t(31);     // tiles are aligned to multiples of 32 slots (seg_tail in the kernels)
-            h->h_reg[(size_t)et * B + g] = (int)cursor;
-            h->h_cap[(size_t)et * B + g] = cap;
-            cursor += cap;
-        }
-    if (cursor > 0x7fffffffLL / 128) PF_FAIL(h, PF_ERR_ARG, "edge capacity too large");
-    h->Ecap = cursor;
-    const int64_t Ecap = std::max<int64_t>(cursor, 1);
-    // tiles: dynamic etypes first (they feed the short pharm-side chain), then pp
-    std::vector<EdgeTile> et_tiles;
-    et_tiles.reserve((size_t)n_pp / 32 + (size_t)(Ecap - n_pp) / 8 + 64);
-    for (int et = 0; et < 3; ++et) {
-        h->et_tile0[et] = (int)et_tiles.size();
-        for (int g = 0; g < B; ++g) {
-            const int cap = h->h_cap[(size_t)et * B + g], reg = h->h_reg[(size_t)et * B + g];
-            for (int o = 0; o < cap; o += 32) et_tiles.push_back({reg + o, std::min(32, cap - o), et, et * B + g, o});
-        }
-        // The output of the last conv layer is consumed only on the pharm nodes (dynamics_gvp.py:91), so in
-        // that layer only the etypes with a pharm destination (ff, pf: the first tiles) and only the pharm node
-        // tiles are computed; the reference computes and discards the protein side.
-        if (et == ET_PF) h->n_edge_tiles_last = (int)et_tiles.size();
-    }
-    h->et_tile0[3] = (int)et_tiles.size();
-    for (int64_t o = 0; o < n_pp; o += 32) et_tiles.push_back({(int)o, (int)std::min<int64_t>(32, n_pp - o), ET_PP, -1, 0});
-    h->et_tile0[4] = (int)et_tiles.size();
-    std::vector<NodeTile> n_tiles, h_tiles;
-    n_tiles.reserve((size_t)N / 32 + 8);
-    for (int o = 0; o < Nf; o += 32) {
-        n_tiles.push_back({Np + o, std::min(32, Nf - o), 1, -1, 0, 0});
-        h_tiles.push_back({Np + o, std::min(32, Nf - o), 1, -1, 0, 0});
-    }
-    for (int o = 0; o < Np; o += 32) n_tiles.push_back({o, std::min(32, Np - o), 0, -1, 0, 0});
-    h->n_edge_tiles = (int)et_tiles.size();
-    h->n_node_tiles = (int)n_tiles.size();
-    h->n_head_tiles = (int)h_tiles.size();
-    h->n_node_tiles_last = (int)h_tiles.size();          // pharm tiles come first in n_tiles
-    // pruned layer: ff, pf, fp tiles + pa tiles; pharm node tiles + tiles over the active-atom lists
-    std::vector<EdgeTile> et_act;
-    for (int et = 0; et < 4; ++et) {
-        h->et_tile0_act[et] = (int)et_act.size();
-        for (int g = 0; g < B; ++g) {
-            const int cap = h->h_cap[(size_t)et * B + g], reg = h->h_reg[(size_t)et * B + g];
-            for (int o = 0; o < cap; o += 32) et_act.push_back({reg + o, std::min(32, cap - o), et == 3 ? (int)ET_PP : et, et * B + g, o});
-        }
-    }
-    h->et_tile0_act[4] = (int)et_act.size();
-    std::vector<NodeTile> n_act(h_tiles);
-    for (int g = 0; g < B; ++g)
-        for (int o = 0; o < cap_act[g]; o += 32) n_act.push_back({reg_act[g] + o, std::min(32, cap_act[g] - o), 0, 4 * B + g, o, 1});
-    h->n_edge_tiles_act = (int)et_act.size();
-    h->n_node_tiles_act = (int)n_act.size();
+    // ---- 3. the point of no return: from here on the handle describes the new batch (a failure below -- a false pocket-group
+    // claim, a failing HIP call -- leaves it without a batch: loud, never the previous one's tables under the new sizes)
+    adopt_plan(h, p, in);
+    const int Np = p.Np, N = p.N;
+    const int64_t Ecap = std::max<int64_t>(p.Ecap, 1);
+    const size_t S = (size_t)c.n_hidden_scalars, V3 = (size_t)3 * c.vector_size;
     mark();      // 1: host tables built
-    // ---- workspace layout: [table section: host-built, uploaded with one copy][zero section][scratch]
-    const size_t n_eta = et_act.size() + 16, n_nta = n_act.size() + 16, n_et = et_tiles.size() + 16, n_nt = n_tiles.size() + 16,
-                 n_ht = h_tiles.size() + 16;
-    auto rnd = [](size_t b) { return (b + 255) & ~size_t(255); };
-    size_t off = 0;
-    auto place = [&](size_t b) { const size_t o = off; off += rnd(b); return o; };
-    // table section (a buffer of its own: offsets relative to d_tab[w])
-    const size_t o_pptr = place((B + 1) * 4), o_fptr = place((B + 1) * 4), o_gid = place((size_t)N * 4), o_reg = place((size_t)4 * B * 4),
-                 o_regact = place((size_t)B * 4), o_eta = place(n_eta * sizeof(EdgeTile)), o_nta = place(n_nta * sizeof(NodeTile)),
-                 o_esrc = place(Ecap * 4), o_edst = place(Ecap * 4), o_ins = place((size_t)4 * N * 4), o_inc = place((size_t)4 * N * 4),
-                 o_ppc = place((size_t)B * 4), o_et = place(n_et * sizeof(EdgeTile)), o_nt = place(n_nt * sizeof(NodeTile)),
-                 o_ht = place(n_ht * sizeof(NodeTile)), o_pfq = place((size_t)B * 4),
-                 o_regs = place((size_t)4 * B * 4), o_pas = place((size_t)B * 4), o_repb = place((size_t)B * 4);
-    const size_t index_bytes = off;
-    const size_t o_px0 = place((size_t)Np * 3 * 4 + 16), o_ph0 = place((size_t)Np * c.rec_nf * 4 + 16);
-    const size_t table_bytes = from_host ? off : index_bytes;      // what the single upload covers
-    const size_t table_total = off;
-    off = 0;                                                       // the workspace proper starts with the zero section
-    // zero section (cleared with one launch per bind)
-    const size_t o_dyn = place((size_t)5 * B * 4), o_act = place((size_t)(act_total + 1) * 4), o_flag = place(256), o_gnorm = place((size_t)2 * B * 4),
-                 o_need = place((size_t)std::max(Np, 1) * 4),
-                 o_lpart = place(64 + (size_t)((Nf + 63) / 64) * 8 * sizeof(float)),       // k_loss_eval's ticket (re-armed by its last block) + partial sums
-                 o_pastamp = place((size_t)std::max(Np, 1) * 4), o_pasame = place((size_t)B * 4),      // speculative "pa" messages: per-atom step stamps, per-graph verdicts
-                 o_pacnt = place((size_t)(B + 1) * 4),                                                 // ... the kind-3 counts they are mapped on (+ PFDYN_PA_SPEC_SPLIT's k)
-                 o_pagst = place(h->pa_check ? (size_t)(std::max<int64_t>(Ecap, 1) / 16 + 1) * 4 : 16);      // PFDYN_PA_CHECK: per-group stamps
-    const size_t zero_bytes = off;
-    // scratch
-    // (a second set of message rows for the last conv layer: the fused launch of small n_convs = 2 batches writes them while conv
-    // layer 0's are still being read)
-    const bool msg2 = !h->wide && c.n_convs == 2 && (long)h->n_edge_tiles_act * 32 <= h->pol.n16_rows_max;
-    // node state and message rows at the handle's widths; the tables of the specialised path's hoists only where it runs
-    const size_t S = (size_t)c.n_hidden_scalars, V3 = (size_t)3 * c.vector_size, SP = PF_S;
-    auto spec_only = [&](size_t b) { return h->spec ? b : (size_t)16; };
-    const int64_t rec_slots = B <= 64 ? Ecap : 0;      // edge records: small batches only (the n16 fused launch)
-    const size_t o_xn = place((size_t)N * 16),
-                 o_fh = place((size_t)Nf * c.pharm_nf * 4 + 16), o_t = place((size_t)B * 4),
-                 o_h0 = place((size_t)N * S * 4), o_h1 = place((size_t)N * S * 4), o_v0 = place((size_t)N * V3 * 4), o_v1 = place((size_t)N * V3 * 4),
-                 o_ms = place((size_t)(Ecap + 1) * S * 4), o_mv = place((size_t)(Ecap + 1) * V3 * 4),
-                 o_ms2 = place(msg2 ? (size_t)(Ecap + 1) * PF_S * 4 : 16), o_mv2 = place(msg2 ? (size_t)(Ecap + 1) * 48 * 4 : 16),
-                 o_eh = place((size_t)Nf * c.pharm_nf * 4 + 16), o_ex = place((size_t)Nf * 3 * 4 + 16), o_c0 = place((size_t)B * 3 * 4), o_c1 = place((size_t)B * 3 * 4),
-                 o_pre = place(spec_only((size_t)std::max(Np, 1) * SP * 4)), o_eorig = place(Ecap * 4), o_ptype = place((size_t)std::max(Np, 1) * 4),
-                 o_rec = place((size_t)(h->pol.edge_rec ? 3 * rec_slots : 0) * 16 + 16),
-                 o_zs = place(spec_only((size_t)std::max<int64_t>(n_pp, 1) * SP * 4)), o_ptpg = place(spec_only((size_t)B * L0_NTAB * c.rec_nf * SP * 4)),
-                 o_xchg = place((size_t)2 * std::max(Nf, 1) * PF_XCHG_STRIDE * sizeof(unsigned int)),      // (+ the center hoist's copy)
-                 o_cenh = place(spec_only((size_t)std::max(Nf, 1) * SP * 4)), o_cenp = place(spec_only((size_t)2 * std::max(Nf, 1) * SP * 4)),
-                 o_snap = place((size_t)2 * (std::max(Nf, 1) * c.pharm_nf + 4) * 4);
-    const size_t bytes = off;
-    bool fresh = false;
-    if (h->ws_capacity < bytes + 4096) {
-        // launches of the previous batch may still read the old workspace
-        PF_HIP(h, hipDeviceSynchronize());
-        if (h->d_ws) { (void)hipFree(h->d_ws); h->d_ws = nullptr; h->ws_capacity = 0; }
-        const size_t want = bytes + bytes / 8 + 4096;           // head room: the next batch of similar size fits without a realloc
-        PF_HIP(h, hipMalloc(&h->d_ws, want));
-        h->ws_capacity = want;
-        fresh = true;
-    }
-    char* const base = reinterpret_cast<char*>(h->d_ws);
-    auto at = [&](size_t o) { return base + o; };
+    // ---- 4. the workspace, the table buffer of this bind and the staging buffer
+    bool fresh = false;           // (launches of the previous batch may still read the old workspace: grow_buffer waits for them)
+    rc = grow_buffer(h, &h->d_ws, &h->ws_capacity, p.ws_bytes + 4096, p.ws_bytes + p.ws_bytes / 8 + 4096, false, &fresh);
+    if (rc) return rc;
     if (!h->d_xstat) {                                           // once per handle: the exchange's time-out counter and its pinned mirror
         PF_HIP(h, hipMalloc((void**)&h->d_xstat, 64));
         PF_HIP(h, hipMemset(h->d_xstat, 0, 64));
         PF_HIP(h, hipHostMalloc((void**)&h->xstat_host, 64, hipHostMallocDefault));
         *h->xstat_host = 0; h->xstat_ack = 0;
     }
-    // the table buffer of this bind
     const int tw = h->tab_next;
     h->tab_next ^= 1;
     if (!h->s_copy) PF_HIP(h, hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking));
@@ -1838,192 +1688,55 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
         if (!h->tab_guard[k]) PF_HIP(h, hipEventCreateWithFlags(&h->tab_guard[k], hipEventDisableTiming));
         if (!h->tab_up[k]) PF_HIP(h, hipEventCreateWithFlags(&h->tab_up[k], hipEventDisableTiming));
     }
-    if (h->tab_cap[tw] < table_total + 4096) {
-        PF_HIP(h, hipDeviceSynchronize());                       // launches of two binds ago may still read the old buffer
-        if (h->d_tab[tw]) { (void)hipFree(h->d_tab[tw]); h->d_tab[tw] = nullptr; h->tab_cap[tw] = 0; }
-        const size_t want = table_total + table_total / 8 + 4096;
-        PF_HIP(h, hipMalloc(&h->d_tab[tw], want));
-        h->tab_cap[tw] = want;
-        h->tab_guard_set[tw] = false;
-    }
+    bool tab_grew = false;        // (launches of two binds ago may still read the old buffer)
+    rc = grow_buffer(h, &h->d_tab[tw], &h->tab_cap[tw], p.table_total + 4096, p.table_total + p.table_total / 8 + 4096, false, &tab_grew);
+    if (rc) return rc;
+    if (tab_grew) h->tab_guard_set[tw] = false;
+    // ---- 5. the pointers, from the plan's offsets
+    char* const base = reinterpret_cast<char*>(h->d_ws);
     char* const tbase = reinterpret_cast<char*>(h->d_tab[tw]);
-    auto tat = [&](size_t o) { return tbase + o; };
-    h->d_prot_ptr = (int*)tat(o_pptr); h->d_pharm_ptr = (int*)tat(o_fptr); h->d_gid = (int*)tat(o_gid); h->d_reg = (int*)tat(o_reg);
-    h->d_reg_act = (int*)tat(o_regact); h->d_edge_tiles_act = (EdgeTile*)tat(o_eta); h->d_node_tiles_act = (NodeTile*)tat(o_nta);
-    h->d_esrc = (int*)tat(o_esrc); h->d_edst = (int*)tat(o_edst); h->d_in_start = (int*)tat(o_ins); h->d_in_cnt = (int*)tat(o_inc);
-    h->d_pp_cnt = (int*)tat(o_ppc); h->d_edge_tiles = (EdgeTile*)tat(o_et); h->d_node_tiles = (NodeTile*)tat(o_nt);
-    h->d_head_tiles = (NodeTile*)tat(o_ht); h->d_pfq_cnt = pfq.empty() ? nullptr : (int*)tat(o_pfq);
-    h->d_reg_share = (int*)tat(o_regs); h->d_pa_static = (int*)tat(o_pas); h->d_rep_base = (int*)tat(o_repb); h->d_need = (int*)at(o_need);
-    h->need_stamp = 0; h->edges_stamp = 0;
-    h->d_dyn_cnt = (int*)at(o_dyn); h->d_act_ids = (int*)at(o_act); h->d_l0flag = (int*)at(o_flag); h->d_gnorm = (float*)at(o_gnorm);
-    h->d_xn = (float4*)at(o_xn); h->d_prot_x0 = (float*)tat(o_px0); h->d_prot_h0 = (float*)tat(o_ph0); h->d_pharm_h = (float*)at(o_fh);
-    h->d_t = (float*)at(o_t); h->d_h[0] = (float*)at(o_h0); h->d_h[1] = (float*)at(o_h1); h->d_v[0] = (float*)at(o_v0); h->d_v[1] = (float*)at(o_v1);
-    h->d_msg_s2 = msg2 ? (float*)at(o_ms2) : nullptr; h->d_msg_v2 = msg2 ? (float*)at(o_mv2) : nullptr;
-    h->d_msg_s = (float*)at(o_ms); h->d_msg_v = (float*)at(o_mv); h->d_eps_h = (float*)at(o_eh); h->d_eps_x = (float*)at(o_ex);
-    h->d_com_init = (float*)at(o_c0); h->d_com_tmp = (float*)at(o_c1); h->d_pre = (float*)at(o_pre); h->d_eorig = (int*)at(o_eorig);
-    h->d_ptype = (int*)at(o_ptype); h->d_zs = (float*)at(o_zs); h->d_ptab_pg = (float*)at(o_ptpg);
-    h->d_rec = (h->pol.edge_rec && rec_slots > 0) ? (int4*)at(o_rec) : nullptr; h->rec_valid = false;
-    h->d_xchg = (unsigned int*)at(o_xchg); h->d_lpart = (float*)at(o_lpart);
-    h->d_xchg2 = h->d_xchg + (size_t)std::max(Nf, 1) * PF_XCHG_STRIDE;
-    h->d_cen_h = (float*)at(o_cenh); h->d_cen_p = (float*)at(o_cenp);
-    h->d_snap[0] = (float*)at(o_snap); h->d_snap[1] = h->d_snap[0] + (size_t)std::max(Nf, 1) * c.pharm_nf + 4;
-    h->cen_valid = false; h->snap_cur = -1;
-    h->d_pa_stamp = (int*)at(o_pastamp); h->d_pa_same = (int*)at(o_pasame); h->spec_valid = false; h->e0_saved = false;
-    h->d_pa_cnt = (int*)at(o_pacnt); h->d_pa_gstamp = h->pa_check ? (int*)at(o_pagst) : nullptr;
+    set_batch_pointers(h, p, base, tbase);
     if (h->pa_check && !h->d_pa_chk) {                           // once per handle: the check's counters
         PF_HIP(h, hipMalloc((void**)&h->d_pa_chk, 3 * sizeof(unsigned long long)));
         PF_HIP(h, hipMemset(h->d_pa_chk, 0, 3 * sizeof(unsigned long long)));
     }
     mark();      // 2: workspace ready
-    // ---- stage the tables in pinned memory and upload them with one asynchronous copy
+    // the tables are staged in pinned memory and uploaded with one asynchronous copy
     const int sb = h->stage_next;
     h->stage_next ^= 1;
     if (!h->stage_ev[sb]) PF_HIP(h, hipEventCreateWithFlags(&h->stage_ev[sb], hipEventDisableTiming));
     else PF_HIP(h, hipEventSynchronize(h->stage_ev[sb]));       // the copy that last read this buffer (two binds ago) is done
-    if (h->stage_cap[sb] < table_bytes) {
-        if (h->stage[sb]) (void)hipHostFree(h->stage[sb]);
-        h->stage[sb] = nullptr; h->stage_cap[sb] = 0;
-        PF_HIP(h, hipHostMalloc(&h->stage[sb], table_bytes + table_bytes / 4 + 4096, hipHostMallocDefault));
-        h->stage_cap[sb] = table_bytes + table_bytes / 4 + 4096;
-    }
+    rc = grow_buffer(h, &h->stage[sb], &h->stage_cap[sb], p.table_bytes, p.table_bytes + p.table_bytes / 4 + 4096, true);
+    if (rc) return rc;
     mark();      // 3: staging buffer ready
+    // ---- 6. the table section, built in the staging buffer itself; a false pocket-group claim is rejected here
     char* const st = reinterpret_cast<char*>(h->stage[sb]);
-    // pp edges sorted by destination (stable counting sort): CSR-by-dst.  The big index arrays are built in the staging
-    // buffer itself (5 MB of edges and 2 MB of in-edge ranges at 256 pockets: no intermediate copies)
-    int* const esrc = reinterpret_cast<int*>(st + o_esrc);
-    int* const edst = reinterpret_cast<int*>(st + o_edst);
-    int* const in_start = reinterpret_cast<int*>(st + o_ins);      // [4 slots][N]: BuildParams::in_start
-    int* const in_cnt = reinterpret_cast<int*>(st + o_inc);
-    memset(esrc + n_pp, 0, (size_t)(Ecap - n_pp) * 4);
-    memset(edst + n_pp, 0, (size_t)(Ecap - n_pp) * 4);
-    memset(in_start, 0, (size_t)4 * N * 4);
-    memset(in_cnt, 0, (size_t)4 * N * 4);
-    {
-        if (dst_sorted) {
-            if (n_pp > 0) { memcpy(esrc, pp_src, (size_t)n_pp * 4); memcpy(edst, pp_dst, (size_t)n_pp * 4); }
-            for (int g = 0; g < B; ++g) pp_cnt[g] = deg[prot_ptr[g + 1]] - deg[prot_ptr[g]];
-        } else {
-            std::vector<int> fill(deg.begin(), deg.end() - 1);
-            for (int64_t e = 0; e < n_pp; ++e) {
-                const int pos = fill[pp_dst[e]]++;
-                esrc[pos] = pp_src[e];
-                edst[pos] = pp_dst[e];
-                pp_cnt[gid[pp_dst[e]]]++;
-            }
-        }
-        for (int i = 0; i < Np; ++i) { in_start[(size_t)N + i] = deg[i]; in_cnt[(size_t)N + i] = deg[i + 1] - deg[i]; }
-    }
-    // ---- pocket sharing (pf_set_pocket_groups): verify the caller's claim and prepare the tables of the sharing mode
-    bool share = false;
-    std::vector<int> rep_base(B, 0);
-    h->share_ok = false; h->share_rows = 0;
-    h->h_share_start.assign(B, 0); h->h_share_cnt.assign(B, 0);
-    if (!rep_claim.empty()) {
-        std::vector<int> rep;
-        rep.swap(rep_claim);
-        if ((int)rep.size() != B) PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups named %d graphs, this batch has %d", (int)rep.size(), B);
-        long dense = 0, percopy = 0;
-        int nrep = 0;
-        for (int g = 0; g < B; ++g) {
-            const int r = rep[g];
-            if (r < 0 || r >= B || rep[r] != r) PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: graph %d names %d, which is not a representative", g, r);
-            const int np = prot_ptr[g + 1] - prot_ptr[g];
-            if (np != prot_ptr[r + 1] - prot_ptr[r] || epp_g[g] != epp_g[r])
-                PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: graph %d is not a copy of graph %d (%d vs %d atoms, %d vs %d pp edges)",
-                        g, r, np, prot_ptr[r + 1] - prot_ptr[r], epp_g[g], epp_g[r]);
-            if (r != g) {
-                // same static graph: in-degrees and (destination-sorted) sources, pocket-local
-                const int p0g = prot_ptr[g], p0r = prot_ptr[r];
-                for (int i = 0; i < np; ++i)
-                    if (deg[p0g + i + 1] - deg[p0g + i] != deg[p0r + i + 1] - deg[p0r + i])
-                        PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: graph %d is not a copy of graph %d (pp in-degree of atom %d)", g, r, i);
-                const int eg = deg[p0g], er = deg[p0r];
-                for (int k = 0; k < epp_g[g]; ++k)
-                    if (esrc[eg + k] - p0g != esrc[er + k] - p0r)
-                        PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: graph %d is not a copy of graph %d (pp edge %d)", g, r, k);
-                if (from_host && (memcmp(host_prot_x + (size_t)p0g * 3, host_prot_x + (size_t)p0r * 3, (size_t)np * 12) ||
-                                  memcmp(host_prot_h + (size_t)p0g * c.rec_nf, host_prot_h + (size_t)p0r * c.rec_nf, (size_t)np * c.rec_nf * 4)))
-                    PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: graph %d is not a copy of graph %d (coordinates / features differ)", g, r);
-            } else { dense += epp_g[g]; ++nrep; }
-            {   // what the per-copy form computes for this graph: the pp in-edges of its active atoms -- at most nf k
-                // of them, about 60 % of that once the centers' neighbour sets overlap -- at the pocket's mean in-degree
-                const int nf = pharm_ptr[g + 1] - pharm_ptr[g];
-                const int nact = c.pf_k > 0 ? std::min(np, nf * std::min(c.pf_k, np)) : (nf > 0 ? np : 0);
-                percopy += np > 0 ? (long)(0.6 * nact * (double)epp_g[g] / np) : 0;
-            }
-        }
-        // worth it when the representatives' static edges are clearly fewer than the per-copy edges they replace (about
-        // half of them at 30 copies of a 256-atom pocket); the compact work list must cover 4 B regions
-        // (with the per-step need stamps only the union of the copies' active atoms is computed, so what a
-        // representative costs beyond that is launching the idle groups of its static range)
-        share = nrep < B && 4 * B <= 1024 && (dense * 4 <= percopy * 3 || nrep * 4 <= B);
-        if (share) {
-            for (int g = 0; g < B; ++g) {
-                const int r = rep[g], p0g = prot_ptr[g], p0r = prot_ptr[r], np = prot_ptr[g + 1] - p0g;
-                for (int i = 0; i < np; ++i) {         // slot 3: the representative's static in-edge range of the same atom
-                    in_start[(size_t)3 * N + p0g + i] = deg[p0r + i];
-                    in_cnt[(size_t)3 * N + p0g + i] = deg[p0r + i + 1] - deg[p0r + i];
-                }
-                rep_base[g] = p0r;
-                if (r == g) { h->h_share_start[g] = deg[p0g]; h->h_share_cnt[g] = epp_g[g]; }
-            }
-            h->share_rows = dense;
-            for (int et = 0; et < 3; ++et) for (int g = 0; g < B; ++g) h->share_rows += h->h_cap[(size_t)et * B + g];
-            h->share_ok = true;
-        }
-    }
-    memcpy(st + o_pptr, prot_ptr, (size_t)(B + 1) * 4);
-    memcpy(st + o_fptr, pharm_ptr, (size_t)(B + 1) * 4);
-    memcpy(st + o_gid, gid.data(), (size_t)N * 4);
-    memcpy(st + o_reg, h->h_reg.data(), (size_t)4 * B * 4);
-    memcpy(st + o_regact, reg_act.data(), (size_t)B * 4);
-    if (!et_act.empty()) memcpy(st + o_eta, et_act.data(), et_act.size() * sizeof(EdgeTile));
-    if (!n_act.empty()) memcpy(st + o_nta, n_act.data(), n_act.size() * sizeof(NodeTile));
-    memcpy(st + o_ppc, pp_cnt.data(), (size_t)B * 4);
-    if (!et_tiles.empty()) memcpy(st + o_et, et_tiles.data(), et_tiles.size() * sizeof(EdgeTile));
-    if (!n_tiles.empty()) memcpy(st + o_nt, n_tiles.data(), n_tiles.size() * sizeof(NodeTile));
-    if (!h_tiles.empty()) memcpy(st + o_ht, h_tiles.data(), h_tiles.size() * sizeof(NodeTile));
-    if (!pfq.empty()) memcpy(st + o_pfq, pfq.data(), (size_t)B * 4);
-    {
-        std::vector<int> regs(h->h_reg);
-        for (int g = 0; g < B && share; ++g) regs[(size_t)3 * B + g] = h->h_share_start[g];
-        memcpy(st + o_regs, regs.data(), (size_t)4 * B * 4);
-        if (share) memcpy(st + o_pas, h->h_share_cnt.data(), (size_t)B * 4); else memset(st + o_pas, 0, (size_t)B * 4);
-        memcpy(st + o_repb, rep_base.data(), (size_t)B * 4);
-    }
-    int host_onehot = -1;
-    if (from_host) {
-        memcpy(st + o_px0, host_prot_x, (size_t)Np * 3 * 4);
-        memcpy(st + o_ph0, host_prot_h, (size_t)Np * c.rec_nf * 4);
-        // the one-hot verdict (static hoist) on the host copy: nobody will wait for the device-side check
-        host_onehot = Np > 0 ? 1 : 0;
-        for (int i = 0; i < Np && host_onehot; ++i) {
-            int ones = 0;
-            for (int k = 0; k < c.rec_nf; ++k) {
-                const float x = host_prot_h[(size_t)i * c.rec_nf + k];
-                if (x == 1.0f) ++ones; else if (x != 0.0f) host_onehot = 0;
-            }
-            if (ones != 1) host_onehot = 0;
-        }
+    pfbind::FillResult fr;
+    rc = pfbind::fill_tables(p, in, st, fr, berr);
+    if (rc) { h->err = berr.msg; return rc; }
+    if (fr.share) {
+        h->h_share_start.swap(fr.h_share_start); h->h_share_cnt.swap(fr.h_share_cnt);
+        h->share_rows = fr.share_rows;
+        h->share_ok = true;
     }
     mark();      // 4: staged
-    // the upload: on the copy stream, once everything that read this table buffer (the bind before the previous one and its
-    // steps) has finished; the caller's stream continues when it has arrived.  The guard of the OTHER buffer is recorded now:
-    // what is enqueued on the caller's stream at this point is everything that reads it.
+    // ---- 7. the upload: on the copy stream, once everything that read this table buffer (the bind before the previous one and
+    // its steps) has finished; the caller's stream continues when it has arrived.  The guard of the OTHER buffer is recorded
+    // now: what is enqueued on the caller's stream at this point is everything that reads it.
     if (h->tab_guard_set[tw]) PF_HIP(h, hipStreamWaitEvent(h->s_copy, h->tab_guard[tw], 0));
     PF_HIP(h, hipEventRecord(h->tab_guard[tw ^ 1], s));
     h->tab_guard_set[tw ^ 1] = true;
-    PF_HIP(h, hipMemcpyAsync(tbase, st, table_bytes, hipMemcpyHostToDevice, h->s_copy));
+    PF_HIP(h, hipMemcpyAsync(tbase, st, p.table_bytes, hipMemcpyHostToDevice, h->s_copy));
     PF_HIP(h, hipEventRecord(h->stage_ev[sb], h->s_copy));
     PF_HIP(h, hipEventRecord(h->tab_up[tw], h->s_copy));
     PF_HIP(h, hipStreamWaitEvent(s, h->tab_up[tw], 0));
     mark();      // 5: upload enqueued
-    // Message rows: the node kernels read only rows the edge kernels of the same layer wrote (the last slot of every
-    // aligned group a destination's segment touches) and the all-zero row Ecap, so a reused workspace needs only that row
-    // cleared; a fresh allocation is cleared once in full
+    // ---- 8. the clears and the four launches.  Message rows: the node kernels read only rows the edge kernels of the same
+    // layer wrote (the last slot of every aligned group a destination's segment touches) and the all-zero row Ecap, so a
+    // reused workspace needs only that row cleared; a fresh allocation is cleared once in full
     {
         ZeroBatch zb(s);
-        zb.add(base, zero_bytes);
+        zb.add(base, p.zero_bytes);
         zb.add(h->d_v[0], (size_t)N * V3 * 4);
         if (fresh) {
             zb.add(h->d_msg_s, (size_t)(Ecap + 1) * S * 4);
@@ -2059,7 +1772,8 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
         lp.zs = reinterpret_cast<float*>(h->d_eorig); lp.Epp = (int)Ecap;      // static slot of every edge slot: the identity
         pfk_l0_hoist(&lp, 2, s);
     }
-    // the one-hot verdict of k_l0_types comes back through pinned memory; nobody waits for it here (l0_resolve_onehot)
+    // ---- 9. the read-back: the one-hot verdict of k_l0_types comes back through pinned memory; nobody waits for it here
+    // (l0_resolve_onehot)
     if (!h->l0flag_host) PF_HIP(h, hipHostMalloc((void**)&h->l0flag_host, 64, hipHostMallocDefault));
     if (!h->l0flag_ev) PF_HIP(h, hipEventCreateWithFlags(&h->l0flag_ev, hipEventDisableTiming));
     else PF_HIP(h, hipEventSynchronize(h->l0flag_ev));           // the previous bind's read-back (long done) before its target is reused
@@ -2068,9 +1782,10 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     PF_HIP(h, hipEventRecord(h->l0flag_ev, s));
     mark();      // 6: everything enqueued
     if (timing) fprintf(stderr, "[pf_set_pocket_batch] B=%d checks+tables %.2f ws %.2f stage-wait %.2f index arrays (in staging) %.2f upload %.2f launches+waits %.2f ms (fresh %d, %zu MB)\n",
-                        B, tm[1] - tm[0], tm[2] - tm[1], tm[3] - tm[2], tm[4] - tm[3], tm[5] - tm[4], tm[6] - tm[5], (int)fresh, bytes >> 20);
+                        B, tm[1] - tm[0], tm[2] - tm[1], tm[3] - tm[2], tm[4] - tm[3], tm[5] - tm[4], tm[6] - tm[5], (int)fresh, p.ws_bytes >> 20);
+    // ---- 10. the per-batch flags
     h->l0_state = 0; h->l0_onehot = false;
-    if (host_onehot >= 0) { h->l0_state = host_onehot ? 1 : 2; h->l0_onehot = host_onehot == 1; }
+    if (fr.host_onehot >= 0) { h->l0_state = fr.host_onehot ? 1 : 2; h->l0_onehot = fr.host_onehot == 1; }
     h->zs_version = 0; h->zs_batch_coords = false; h->coords_custom = false;
     h->have_batch = true;
     h->sampling = false; h->pinned = false;
@@ -2547,88 +2262,56 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
     if (c.pharm_nf > 8 || c.rec_nf + 1 > 17 || c.pharm_nf + 1 > 17)
         PF_FAIL(h, PF_ERR_ARG, "training supports pharm_nf <= 8 and rec_nf <= 16");
     const int L = c.n_convs, N = h->N;
-    const size_t E1 = (size_t)h->Ecap + 1;
+    const size_t E1 = (size_t)h->Ecap + 1, Es = (size_t)std::max<int64_t>(h->Ecap, 1), Nf1 = (size_t)std::max(h->Nf, 1);
+    const size_t ng = (size_t)c.n_message_gvps, nu = (size_t)c.n_update_gvps, nh = (size_t)c.n_noise_gvps;
     h->t_nblk = std::max(8, std::min(256, h->n_edge_tiles));
-    size_t bytes = 0;
-    auto need = [&](size_t n_floats) { bytes += (n_floats * 4 + 255) & ~size_t(255); };
-    for (int l = 0; l <= L; ++l) { need((size_t)N * PF_S); need((size_t)N * 48); }
-    for (int l = 0; l < L; ++l) { need(E1 * PF_S); need(E1 * 48); }
-    for (int a = 0; a < 2; ++a) { need((size_t)N * PF_S); need((size_t)N * 48); }
-    need((size_t)N * PF_S); need((size_t)N * 48);
-    need(64);
-    need(64); need((size_t)std::max(h->n_edge_tiles, h->n_edge_tiles_act) + 64);      // compact tile list and its counts
-    need((size_t)PFT_ENC_BLOCKS * std::max(h->enc_n, 1));
-    need((size_t)2 * std::max(h->n_node_tiles, h->n_node_tiles_act) + 64);
-    need((size_t)h->B * c.rec_nf * PF_S);
-    need((size_t)h->Nf * 3); need((size_t)h->B); need((size_t)h->B); need((size_t)h->B * 3); need((size_t)h->Nf * 3); need((size_t)h->Nf * c.pharm_nf); need(64);   // loss buffers
-    for (int l = 0; l < L; ++l) { need((size_t)c.n_update_gvps * 2 * N * PF_S); need((size_t)c.n_update_gvps * 2 * N * 16); need((size_t)c.n_update_gvps * 2 * N * 48); }
-    need((size_t)c.n_noise_gvps * std::max(h->Nf, 1) * PF_S); need((size_t)c.n_noise_gvps * std::max(h->Nf, 1) * 16);
-    need((size_t)c.n_noise_gvps * std::max(h->Nf, 1) * 48);
-    need((size_t)h->t_nblk * ((h->nparams + 63) / 64 * 64));
-    const size_t Es = (size_t)std::max<int64_t>(h->Ecap, 1), ng = (size_t)c.n_message_gvps;
-    for (int l = 0; l < L; ++l) { need(ng * Es * PF_S); need(ng * Es * 16); need(ng * Es * 48); }
-    need(Es * PF_S); need(Es * 48);
-    // like d_ws the allocation outlives the batch: a training loop binds a new batch every step, and a hipFree / hipMalloc
-    // pair of a few GB (plus clearing it) per step cost two orders of magnitude more than the step itself
-    bool fresh = false;
-    if (h->tws_capacity < bytes + 4096) {
-        PF_HIP(h, hipDeviceSynchronize());
-        if (h->d_tws) { (void)hipFree(h->d_tws); h->d_tws = nullptr; h->tws_capacity = 0; }
-        const size_t want = bytes + bytes / 8 + 4096;
-        PF_HIP(h, hipMalloc(&h->d_tws, want));
-        h->tws_capacity = want;
-        fresh = true;
-    }
-    char* cur = reinterpret_cast<char*>(h->d_tws);
+    h->t_clist_cap = (size_t)std::max(h->n_edge_tiles, h->n_edge_tiles_act) * 32 + 64;
+    h->t_ucap = 32 * std::max(h->n_node_tiles, h->n_node_tiles_act) + 16;      // rows per node type in the dense unit list
+    h->t_ulist_cap = (size_t)2 * 2 * h->t_ucap + 64;
     h->wt_ready = false;                         // (the loss buffers t_l* below are shared with the width-generic leg's carve)
     h->t_H.assign(L + 1, nullptr); h->t_V.assign(L + 1, nullptr); h->t_msg_s.assign(L, nullptr); h->t_msg_v.assign(L, nullptr);
-    for (int l = 0; l <= L; ++l) { h->t_H[l] = carve<float>(cur, (size_t)N * PF_S); h->t_V[l] = carve<float>(cur, (size_t)N * 48); }
-    for (int l = 0; l < L; ++l) { h->t_msg_s[l] = carve<float>(cur, E1 * PF_S); h->t_msg_v[l] = carve<float>(cur, E1 * 48); }
-    for (int a = 0; a < 2; ++a) { h->t_G_h[a] = carve<float>(cur, (size_t)N * PF_S); h->t_G_v[a] = carve<float>(cur, (size_t)N * 48); }
-    h->t_gagg_s = carve<float>(cur, (size_t)N * PF_S); h->t_gagg_v = carve<float>(cur, (size_t)N * 48);
+    h->t_nsv_z.assign(L, nullptr); h->t_nsv_g.assign(L, nullptr); h->t_nsv_v.assign(L, nullptr);
+    h->t_sv_z.assign(L, nullptr); h->t_sv_g.assign(L, nullptr); h->t_sv_v.assign(L, nullptr);
+    // two passes over one list: sizes, then pointers
+    bool fresh = false;
+    size_t bytes = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver w(pass ? h->d_tws : nullptr);
+        for (int l = 0; l <= L; ++l) { w.take(h->t_H[l], (size_t)N * PF_S); w.take(h->t_V[l], (size_t)N * 48); }
+        for (int l = 0; l < L; ++l) { w.take(h->t_msg_s[l], E1 * PF_S); w.take(h->t_msg_v[l], E1 * 48); }
+        for (int a = 0; a < 2; ++a) { w.take(h->t_G_h[a], (size_t)N * PF_S); w.take(h->t_G_v[a], (size_t)N * 48); }
+        w.take(h->t_gagg_s, (size_t)N * PF_S); w.take(h->t_gagg_v, (size_t)N * 48);
+        w.take(h->t_fix, 64);
+        w.take(h->t_ccnt, 128);                                 // [layer][16]: passes per etype, rows per etype at + 8; node units at [96]
+        w.take(h->t_clist, h->t_clist_cap * L);                 // dense row lists, one per conv layer
+        w.take(h->t_gpart_enc, (size_t)PFT_ENC_BLOCKS * std::max(h->enc_n, 1));
+        w.take(h->t_ulist, h->t_ulist_cap * L);                 // per conv layer: [2 types][t_ucap] x (node id, saved-level row)
+        w.take(h->t_Gg, (size_t)h->B * c.rec_nf * PF_S);
+        w.take(h->t_lx0c, (size_t)h->Nf * 3); w.take(h->t_lag, (size_t)h->B); w.take(h->t_lsg, (size_t)h->B); w.take(h->t_lcom2, (size_t)h->B * 3);
+        w.take(h->t_lgx, (size_t)h->Nf * 3); w.take(h->t_lgh, (size_t)h->Nf * c.pharm_nf); w.take(h->t_lout, 64);      // loss buffers
+        for (int l = 0; l < L; ++l) { w.take(h->t_nsv_z[l], nu * 2 * N * PF_S); w.take(h->t_nsv_g[l], nu * 2 * N * 16); w.take(h->t_nsv_v[l], nu * 2 * N * 48); }
+        w.take(h->t_hsv_z, nh * Nf1 * PF_S); w.take(h->t_hsv_g, nh * Nf1 * 16); w.take(h->t_hsv_v, nh * Nf1 * 48);
+        w.take(h->t_gpart, (size_t)h->t_nblk * ((h->nparams + 63) / 64 * 64));
+        for (int l = 0; l < L; ++l) { w.take(h->t_sv_z[l], ng * Es * PF_S); w.take(h->t_sv_g[l], ng * Es * 16); w.take(h->t_sv_v[l], ng * Es * 48); }
+        w.take(h->t_gs_buf, Es * PF_S); w.take(h->t_gv_buf, Es * 48);
+        if (pass == 0) {
+            // like d_ws the allocation outlives the batch: a training loop binds a new batch every step, and a hipFree / hipMalloc
+            // pair of a few GB (plus clearing it) per step cost two orders of magnitude more than the step itself
+            bytes = w.bytes();
+            const int rc = grow_buffer(h, &h->d_tws, &h->tws_capacity, bytes + 4096, bytes + bytes / 8 + 4096, false, &fresh);
+            if (rc) return rc;
+        } else if (w.bytes() != bytes)
+            PF_FAIL(h, PF_ERR_STATE, "training workspace: carved %zu bytes, counted %zu", w.bytes(), bytes);
+    }
     {
         // int64 accumulators [N][128] and [N][48]: cleared when allocated, pfk_fix_apply leaves every element it read at zero
         const size_t a_bytes = ((size_t)N * PF_S * 8 + 255) / 256 * 256, need_a = a_bytes + (size_t)N * 48 * 8;
-        if (h->tA_capacity < need_a) {
-            PF_HIP(h, hipDeviceSynchronize());
-            if (h->d_tA) { (void)hipFree(h->d_tA); h->d_tA = nullptr; h->tA_capacity = 0; }
-            const size_t want = need_a + need_a / 8;
-            PF_HIP(h, hipMalloc(&h->d_tA, want));
-            h->tA_capacity = want;
-            h->tA_dirty = true;
-        }
+        const int rc = grow_buffer(h, &h->d_tA, &h->tA_capacity, need_a, need_a + need_a / 8, false, &h->tA_dirty);
+        if (rc) return rc;
         if (h->tA_dirty) { PF_HIP(h, hipMemsetAsync(h->d_tA, 0, h->tA_capacity, s)); h->tA_dirty = false; }
         h->t_A_h = reinterpret_cast<long long*>(h->d_tA);
         h->t_A_v = reinterpret_cast<long long*>(reinterpret_cast<char*>(h->d_tA) + a_bytes);
     }
-    h->t_fix = carve<float>(cur, 64);
-    h->t_ccnt = carve<int>(cur, 128);            // [layer][16]: passes per etype, rows per etype at + 8; node units at [96]
-    h->t_clist_cap = (size_t)std::max(h->n_edge_tiles, h->n_edge_tiles_act) * 32 + 64;
-    h->t_clist = carve<int>(cur, h->t_clist_cap * L);                          // dense row lists, one per conv layer
-    h->t_gpart_enc = carve<float>(cur, (size_t)PFT_ENC_BLOCKS * std::max(h->enc_n, 1));
-    h->t_ucap = 32 * std::max(h->n_node_tiles, h->n_node_tiles_act) + 16;      // rows per node type in the dense unit list
-    h->t_ulist_cap = (size_t)2 * 2 * h->t_ucap + 64;
-    h->t_ulist = carve<int>(cur, h->t_ulist_cap * L);                          // per conv layer: [2 types][t_ucap] x (node id, saved-level row)
-    h->t_Gg = carve<float>(cur, (size_t)h->B * c.rec_nf * PF_S);
-    h->t_lx0c = carve<float>(cur, (size_t)h->Nf * 3); h->t_lag = carve<float>(cur, (size_t)h->B); h->t_lsg = carve<float>(cur, (size_t)h->B);
-    h->t_lcom2 = carve<float>(cur, (size_t)h->B * 3);
-    h->t_lgx = carve<float>(cur, (size_t)h->Nf * 3); h->t_lgh = carve<float>(cur, (size_t)h->Nf * c.pharm_nf); h->t_lout = carve<float>(cur, 64);
-    h->t_nsv_z.assign(L, nullptr); h->t_nsv_g.assign(L, nullptr); h->t_nsv_v.assign(L, nullptr);
-    for (int l = 0; l < L; ++l) {
-        h->t_nsv_z[l] = carve<float>(cur, (size_t)c.n_update_gvps * 2 * N * PF_S);
-        h->t_nsv_g[l] = carve<float>(cur, (size_t)c.n_update_gvps * 2 * N * 16);
-        h->t_nsv_v[l] = carve<float>(cur, (size_t)c.n_update_gvps * 2 * N * 48);
-    }
-    h->t_hsv_z = carve<float>(cur, (size_t)c.n_noise_gvps * std::max(h->Nf, 1) * PF_S);
-    h->t_hsv_g = carve<float>(cur, (size_t)c.n_noise_gvps * std::max(h->Nf, 1) * 16);
-    h->t_hsv_v = carve<float>(cur, (size_t)c.n_noise_gvps * std::max(h->Nf, 1) * 48);
-    h->t_gpart = carve<float>(cur, (size_t)h->t_nblk * ((h->nparams + 63) / 64 * 64));
-    h->t_sv_z.assign(L, nullptr); h->t_sv_g.assign(L, nullptr); h->t_sv_v.assign(L, nullptr);
-    for (int l = 0; l < L; ++l) {
-        h->t_sv_z[l] = carve<float>(cur, ng * Es * PF_S); h->t_sv_g[l] = carve<float>(cur, ng * Es * 16);
-        h->t_sv_v[l] = carve<float>(cur, ng * Es * 48);
-    }
-    h->t_gs_buf = carve<float>(cur, Es * PF_S); h->t_gv_buf = carve<float>(cur, Es * 48);
     // message buffers: the zero row (index Ecap) must read as zeros; V[0] is the all-zero initial vector state
     // (only rows written by the same forward and the zero row are ever read: a reused allocation needs just that row)
     {
@@ -2665,10 +2348,10 @@ static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
     const size_t gstride = (h->nparams + 63) / 64 * 64;
     pf_handle::WtWs& w = h->wt;
     // two passes over one list: sizes, then pointers
+    size_t bytes = 0;
     for (int pass = 0; pass < 2; ++pass) {
-        char* const base = pass ? reinterpret_cast<char*>(h->d_wtws) : reinterpret_cast<char*>(uintptr_t(256));
-        char* cur = base;
-        auto take = [&](float*& dst, size_t n) { float* q = carve<float>(cur, n); if (pass) dst = q; };
+        Carver cv(pass ? h->d_wtws : nullptr);
+        auto take = [&](float*& dst, size_t n) { cv.take(dst, n); };
         take(w.esv_s, L * nm * Es * ES); take(w.esv_v, L * nm * Es * EV);
         take(w.x1_s, L * N * S); take(w.x1_v, L * N * V3); take(w.x2_s, L * N * S); take(w.x2_v, L * N * V3);
         take(w.usv_s, L * nu * N * S); take(w.usv_v, L * nu * N * V3);
@@ -2683,24 +2366,16 @@ static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
         take(h->t_lx0c, (size_t)h->Nf * 3); take(h->t_lag, (size_t)h->B); take(h->t_lsg, (size_t)h->B); take(h->t_lcom2, (size_t)h->B * 3);
         take(h->t_lgx, (size_t)h->Nf * 3); take(h->t_lgh, (size_t)h->Nf * c.pharm_nf); take(h->t_lout, 64);
         if (pass == 0) {
-            const size_t bytes = (size_t)(cur - base);
-            if (h->wtws_capacity < bytes + 4096) {
-                PF_HIP(h, hipDeviceSynchronize());
-                if (h->d_wtws) { (void)hipFree(h->d_wtws); h->d_wtws = nullptr; h->wtws_capacity = 0; }
-                const size_t want = bytes + bytes / 8 + 4096;
-                PF_HIP(h, hipMalloc(&h->d_wtws, want));
-                h->wtws_capacity = want;
-            }
-        }
+            bytes = cv.bytes();
+            const int rc = grow_buffer(h, &h->d_wtws, &h->wtws_capacity, bytes + 4096, bytes + bytes / 8 + 4096, false);
+            if (rc) return rc;
+        } else if (cv.bytes() != bytes)
+            PF_FAIL(h, PF_ERR_STATE, "width-generic training workspace: carved %zu bytes, counted %zu", cv.bytes(), bytes);
     }
     w.Es = Es;
     const size_t a_bytes = (N * S * 8 + 255) / 256 * 256, need_a = a_bytes + N * V3 * 8;
-    if (h->wtA_capacity < need_a) {
-        PF_HIP(h, hipDeviceSynchronize());
-        if (h->d_wtA) { (void)hipFree(h->d_wtA); h->d_wtA = nullptr; h->wtA_capacity = 0; }
-        PF_HIP(h, hipMalloc(&h->d_wtA, need_a + need_a / 8));
-        h->wtA_capacity = need_a + need_a / 8;
-    }
+    const int rc_a = grow_buffer(h, &h->d_wtA, &h->wtA_capacity, need_a, need_a + need_a / 8, false);
+    if (rc_a) return rc_a;
     PF_HIP(h, hipMemsetAsync(h->d_wtA, 0, h->wtA_capacity, s));
     w.A_h = reinterpret_cast<long long*>(h->d_wtA);
     w.A_v = reinterpret_cast<long long*>(reinterpret_cast<char*>(h->d_wtA) + a_bytes);

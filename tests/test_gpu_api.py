@@ -990,6 +990,36 @@ def test_pocket_claims_device_resident_batches_and_failed_binds():
         m.forward(g, 'val', t_int=bad_t, eps={'h': z["eps_h"], 'x': z["eps_x"]})
 
 
+def test_a_false_claim_leaves_the_handle_without_a_batch():
+    """A pocket-group claim is verified after the bind's point of no return (the plan is adopted, then the tables are filled): a
+    claim that fails there -- same atoms, in-degrees and edge count, one pp source of a copy redirected inside its graph -- leaves
+    the handle without a batch, loudly, never with the previous one's tables; binding the true batch again gives bitwise what it
+    gave before."""
+    cfg = O.DynamicsConfig()
+    sd = O.make_state_dict(cfg, 0)
+    from test_gpu_fullsize import _copies_batch, _engine
+    batch, uid = _copies_batch(cfg, [(621, 48), (622, 40)], [[3, 5], [4, 3]])
+    eng = _engine(cfg, sd)
+    args = (batch.prot_x, batch.prot_h, batch.prot_ptr, batch.pharm_ptr)            # host rows
+    eng.set_batch(*args, batch.pp_src, batch.pp_dst, pocket_uid=uid)
+    gen = torch.Generator().manual_seed(6)
+    Nf = int(batch.pharm_ptr[-1])
+    x_t, h_t, t = torch.randn(Nf, 3, generator=gen), torch.randn(Nf, 6, generator=gen), torch.full((4,), 0.4)
+    ref = [v.cpu() for v in eng.dynamics(x_t, h_t, t)]
+    p1, p2 = int(batch.prot_ptr[1]), int(batch.prot_ptr[2])
+    e = int((batch.pp_dst >= p1).nonzero()[0])                                      # the first pp edge of the first pocket's second copy
+    bad_src = batch.pp_src.clone()
+    bad_src[e] = p1 + (int(bad_src[e]) - p1 + 1) % (p2 - p1)
+    assert bad_src[e] != batch.pp_src[e] and p1 <= int(bad_src[e]) < p2
+    with pytest.raises(pfa.PfError, match="not a copy of graph"):
+        eng.set_batch(*args, bad_src, batch.pp_dst, pocket_uid=uid)
+    with pytest.raises(pfa.PfError, match="no pocket batch set"):
+        eng.dynamics(x_t, h_t, t)
+    eng.set_batch(*args, batch.pp_src, batch.pp_dst, pocket_uid=uid)
+    again = [v.cpu() for v in eng.dynamics(x_t, h_t, t)]
+    assert torch.equal(again[0], ref[0]) and torch.equal(again[1], ref[1])
+
+
 def test_c_abi_verifies_a_pocket_claim_made_for_device_rows():
     """pf_set_pocket_groups + pf_set_pocket_batch with DEVICE coordinates / features, straight through the C ABI (the Python
     engine's own comparison bypassed): the bind compares every copy with its representative on the device, and the first call

@@ -4,7 +4,7 @@ compute unit (HW_ID, XCC_ID) and the item kind of every workgroup of one launch.
 
     cd pharmacophore-diffusion_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form=1 \
         -DN16_TRACE -c pf_n16.hip -o variants/n16_trace.o && hipcc -shared -fPIC --offload-arch=gfx950 pf_kernels.o pf_train.o \
-        pf_rg.o pf_wide.o pf_wide_train.o variants/n16_trace.o pf_host.o pf_pack.o -o variants/libpfdyn_n16trace.so
+        pf_rg.o pf_wide.o pf_wide_train.o variants/n16_trace.o pf_host.o pf_bind.o pf_pack.o -o variants/libpfdyn_n16trace.so
     PFDYN_N16=2 PFDYN_LIB=$PWD/pharmacophore-diffusion_amd/csrc/variants/libpfdyn_n16trace.so B=32 python tools/n16_trace.py
 """
 import collections
