@@ -159,3 +159,200 @@ def sampler_live_head(sd, cfg, batch, T, precision, noise):
     nf = cfg.pharm_nf
     _, ex = O.dynamics_forward(sd, cfg, batch, prot_x, noise[0][:, :3], noise[0][:, 3:3 + nf], t)
     return live_head(sd, cfg, ex)
+
+
+# ---- the 1e-8 norm floor (oracle.pf_oracle.norm_no_nan): inputs that put it to work, and a census of where it acts --------------
+NORM_EPS = 1e-8
+
+
+def floor_weights(sd, down=20, up=10):
+    """A copy of ``sd`` in which every GVP (every key ending in ``.Wh``, at any width) has the odd columns of Wh multiplied by
+    2**-down and the matching ``sh`` columns of its to_feats_out.0.weight -- the last Wh.shape[1] columns: s = [feats, sh],
+    gvp.py:103 -- multiplied by 2**up.  The hidden vectors of the odd channels then have squared norms far below 1e-8, so
+    sh = |Vh| sits on the floor of norm_no_nan for about half of all (row, channel) entries, and the 2**up makes that sh count
+    in the scalar path.  Powers of two: every scaled product is exact, as with live_head."""
+    out = dict(sd)
+    for key, wh in sd.items():
+        if not key.endswith(".Wh"):
+            continue
+        h = wh.shape[1]
+        wh = wh.clone()
+        wh[:, 1::2] *= 2.0 ** -down
+        out[key] = wh
+        wkey = key[:-2] + "to_feats_out.0.weight"
+        w = sd[wkey].clone()
+        first = w.shape[1] - h
+        w[:, first + 1::2] *= 2.0 ** up
+        out[wkey] = w
+    return out
+
+
+def _norm_site():
+    """The call site of the norm_no_nan call being spied on: the weight prefix of the GVP or GVPLayerNorm that called it, or
+    ``<conv layer prefix>distance.<edge type>`` for the edge geometry."""
+    import sys
+    f = sys._getframe(2)
+    while f is not None:
+        name, loc = f.f_code.co_name, f.f_locals
+        if name == "gvp_forward":
+            return loc["prefix"] + "sh"
+        if name == "gvp_layernorm":
+            return loc["prefix"] + "vn"
+        if name == "conv_layer":
+            return loc["prefix"] + "distance." + loc["et"]
+        f = f.f_back
+    return "?"
+
+
+def site_family(site):
+    """The chain family of a norm site: ``msg<layer>`` (the message chains of a conv layer), ``upd.prot`` / ``upd.pharm`` (the
+    update chains of a node type), ``head``, ``norm`` (a GVPLayerNorm) or ``distance``."""
+    if site.endswith(".vn"):
+        return "norm"
+    if ".distance." in site:
+        return "distance"
+    if ".edge_message_fns." in site:
+        return "msg" + site.split("conv_layers.")[1].split(".")[0]
+    if ".node_update_fns." in site:
+        return "upd." + site.split(".node_update_fns.")[1].split(".")[0]
+    return "head"
+
+
+class NormCensus:
+    """What norm_census recorded: ``sites`` maps a call site (in call order) to the list of squared-norm tensors it saw, one per
+    call; ``result`` is what ``fn`` returned."""
+
+    def __init__(self):
+        self.sites, self.result = {}, None
+
+    def squared(self, site):
+        return torch.cat([t.reshape(-1).double() for t in self.sites[site]])
+
+    def clamped_share(self, site=None):
+        ss = torch.cat([self.squared(s) for s in self.sites]) if site is None else self.squared(site)
+        return float((ss < NORM_EPS).double().mean())
+
+    def sides(self):
+        """one bool tensor over every entry of every site, in call order: True where the floor acts"""
+        return torch.cat([self.squared(s) < NORM_EPS for s in self.sites])
+
+    def nearest_to_threshold(self):
+        """min over all entries of |ss / 1e-8 - 1|"""
+        return min(float((self.squared(s) / NORM_EPS - 1.0).abs().min()) for s in self.sites)
+
+
+class norm_census:
+    """Context manager that spies on O.norm_no_nan: every call's squared norms (the sum of squares before the clamp) are recorded
+    under its call site, the original computes the result, and the original is restored on exit.  With ``fn``, fn() runs inside
+    the context as it is entered and its return value is kept in ``.result``:
+
+        with norm_census(lambda: O.dynamics_forward(...)) as c: ...        # c.sites, c.result
+        with norm_census() as c: O.dynamics_forward(...)"""
+
+    def __init__(self, fn=None):
+        self.fn = fn
+
+    def __enter__(self):
+        census, orig = NormCensus(), O.norm_no_nan
+        self._orig = orig
+
+        def spy(x, axis=-1, keepdims=False, eps=1e-8, sqrt=True):
+            census.sites.setdefault(_norm_site(), []).append(torch.sum(torch.square(x.detach()), axis, keepdims))
+            return orig(x, axis, keepdims, eps, sqrt)
+
+        O.norm_no_nan = spy
+        try:
+            if self.fn is not None:
+                census.result = self.fn()
+        except BaseException:
+            O.norm_no_nan = orig
+            raise
+        return census
+
+    def __exit__(self, *exc):
+        O.norm_no_nan = self._orig
+        return False
+
+
+def twin_inputs(batch, x_t, cfg=None):
+    """(batch', x_t', planted): coincident and near-coincident nodes for the distance floor of the edge geometry,
+    d = sqrt(max(|x_src - x_dst|^2, 1e-8)) + 1e-8 (gvp.py:478).  Protein and center coordinates are rounded to multiples of
+    2**-12 (the small offsets below are then exact in fp32 and so is every coordinate difference between the planted nodes),
+    the pp edges are rebuilt from the rounded atoms, and four things are planted across the first two graphs with at least three
+    centers (x_t is in the frame of batch.prot_x: pass prot_x = batch'.prot_x to the dynamics call):
+      graph A: centers 0, 1 an exact twin pair (both on the rounded position of center 0); center 2 exactly on protein atom 0;
+      graph B: center 1 at center 0 + (2**-15, 0, 2**-14), 6.8e-5 A away: the unit vector becomes a 0.68-length vector;
+               its last center at protein atom 1 + (0, -2**-14, 2**-16).
+    ``planted`` names them: {what: (center index, partner index)} in batch-global ids."""
+    cfg = O.DynamicsConfig() if cfg is None else cfg
+    q = 2.0 ** 12
+    px = torch.round(batch.prot_x * q) / q
+    x = torch.round(x_t * q) / q
+    sizes = (batch.pharm_ptr[1:] - batch.pharm_ptr[:-1]).tolist()
+    big = [g for g, n in enumerate(sizes) if n >= 3]
+    assert len(big) >= 2, "twin_inputs needs two graphs with at least three centers"
+    ga, gb = big[0], big[1]
+    fa, fb = int(batch.pharm_ptr[ga]), int(batch.pharm_ptr[gb])
+    pa, pb = int(batch.prot_ptr[ga]), int(batch.prot_ptr[gb])
+    planted = {}
+    x[fa + 1] = x[fa]
+    planted["exact twin"] = (fa + 1, fa)
+    x[fa + 2] = px[pa]
+    planted["on atom"] = (fa + 2, pa)
+    x[fb + 1] = x[fb] + torch.tensor([2.0 ** -15, 0.0, 2.0 ** -14])
+    planted["near twin"] = (fb + 1, fb)
+    last = fb + sizes[gb] - 1
+    x[last] = px[pb + 1] + torch.tensor([0.0, -2.0 ** -14, 2.0 ** -16])
+    planted["near atom"] = (last, pb + 1)
+    assert torch.equal(x[fb + 1] - x[fb], torch.tensor([2.0 ** -15, 0.0, 2.0 ** -14]))
+    assert torch.equal(x[last] - px[pb + 1], torch.tensor([0.0, -2.0 ** -14, 2.0 ** -16]))
+    src, dst = O.build_pp_edges(px, batch.prot_ptr, cfg.cutoff_pp, 100)
+    return O.PocketBatch(px, batch.prot_h, batch.prot_ptr, batch.pharm_ptr, src, dst), x, planted
+
+
+class _NormThroughClamp(torch.autograd.Function):
+    """norm_no_nan whose backward omits the indicator ss > eps: it differentiates sqrt(ss) (or ss) as if the clamp were not
+    there, with the clamped value in the denominator.  Same forward values."""
+
+    @staticmethod
+    def forward(ctx, x, axis, keepdims, eps, sqrt):
+        ss = torch.clamp(torch.sum(torch.square(x), axis, True), min=eps)
+        out = torch.sqrt(ss) if sqrt else ss
+        ctx.save_for_backward(x, out)
+        ctx.meta = (axis, keepdims, sqrt)
+        return out if keepdims else out.squeeze(axis)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, out = ctx.saved_tensors
+        axis, keepdims, sqrt = ctx.meta
+        g = g if keepdims else g.unsqueeze(axis)
+        return (g * x / out if sqrt else 2.0 * g * x), None, None, None, None
+
+
+NORM_MUTANTS = {
+    # no floor at all: sqrt(ss)
+    "sqrt": lambda x, axis=-1, keepdims=False, eps=1e-8, sqrt=True:
+        (torch.sqrt if sqrt else (lambda v: v))(torch.sum(torch.square(x), axis, keepdims)),
+    # the floor applied after the square root: max(sqrt(ss), 1e-8)
+    "floor_after_sqrt": lambda x, axis=-1, keepdims=False, eps=1e-8, sqrt=True:
+        (torch.clamp(torch.sqrt(torch.sum(torch.square(x), axis, keepdims)), min=eps) if sqrt
+         else torch.clamp(torch.sum(torch.square(x), axis, keepdims), min=eps)),
+    # the right forward, a backward without the indicator
+    "no_indicator": lambda x, axis=-1, keepdims=False, eps=1e-8, sqrt=True: _NormThroughClamp.apply(x, axis, keepdims, eps, sqrt),
+}
+
+
+class norm_mutant:
+    """Context manager: O.norm_no_nan replaced by one of NORM_MUTANTS (a wrong kernel's arithmetic, restated), restored on exit."""
+
+    def __init__(self, kind):
+        self.impl = NORM_MUTANTS[kind]
+
+    def __enter__(self):
+        self._orig, O.norm_no_nan = O.norm_no_nan, self.impl
+        return self
+
+    def __exit__(self, *exc):
+        O.norm_no_nan = self._orig
+        return False
