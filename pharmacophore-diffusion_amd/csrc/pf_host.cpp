@@ -436,7 +436,7 @@ struct pf_handle {
     // ---- gradient path (pf_train_*): flat parameter vector in state-dict order, GvpT tables, per-layer activations
     float* d_flat = nullptr;
     size_t nparams = 0;
-    std::vector<std::pair<std::string, std::pair<size_t, size_t>>> flat_layout;   // name -> (offset, numel), state-dict order
+    FlatLayout flat_layout;                 // name -> (offset, numel), state-dict order
     GvpT* d_gvpt = nullptr;                 // same indexing as the GvpW table
     int* d_map = nullptr;                   // packed element -> flat parameter index (-1: zero): PackedModel::map
     size_t n_packed = 0;
@@ -497,20 +497,9 @@ struct pf_handle {
     } wt{};
     WtCommon wt_common{};
     TrainCommon t_common{};
-    // (looked up ~26 times per backward pass: an index over the 244 names, rebuilt when the layout is -- a linear search with string
-    // compares was 50-100 us of a training step's host time, and that step is host-bound with a new batch every step)
-    mutable std::unordered_map<std::string, size_t> flat_index;
-    mutable bool flat_index_ok = false;
-    size_t flat_offset(const std::string& name) const {
-        if (!flat_index_ok) {
-            flat_index.clear();
-            for (const auto& kv : flat_layout) flat_index.emplace(kv.first, kv.second.first);
-            flat_index_ok = true;
-        }
-        const auto it = flat_index.find(name);
-        return it == flat_index.end() ? (size_t)-1 : it->second;
-    }
-    std::vector<int> edge_fx;               // [conv layer][message GVP level]: k_bwd_edge_level's shape class (msg_spec is string-building host work)
+    // offsets into the flat vector that every training call reads, resolved by name once per commit (pf_pack.h: param_offsets) --
+    // the training step is host-bound with a new batch every step, and looking ~26 names up per backward pass was 50-100 us of it
+    ParamOffsets po;
 
     // ---- optional per-kernel timing with HIP events on the caller's stream (pf_profile_*)
     // classes 0..8: pf_profile_read (inference path); 9..12: pf_profile_read_train (gradient kernels)
@@ -617,6 +606,27 @@ struct ProfScope {
 static bool l0_hoist_ok(pf_handle* h);
 // the conv layer restricted to active atoms (receptive-field pruning of the second-to-last layer); -1: none
 static int prune_layer(const pf_handle* h) { return (h->prune && h->cfg.n_convs >= 2) ? h->cfg.n_convs - 2 : -1; }
+// Which tiles a conv layer walks, forward and backward.  The last layer's output is read on the centers only: their node tiles
+// and the ff / pf edge tiles (the head of either table).  The pruned layer walks the active atoms' tables.  Every other layer,
+// everything.
+struct LayerTiles {
+    const EdgeTile* etiles; int n_etiles;
+    const int* et_tile0; int n_et;          // etype segments of the edge table [5]; etypes [0, n_et) take part in the gradient
+    const NodeTile* ntiles; int n_ntiles;
+    int pp_slot;                            // in_cnt slot of the pp edges (2: the active atoms' compact copy)
+};
+static LayerTiles layer_tiles(const pf_handle* h, bool last, bool pruned) {
+    LayerTiles t;
+    t.etiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
+    t.n_etiles = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles);
+    t.et_tile0 = pruned ? h->et_tile0_act : h->et_tile0;
+    t.n_et = last ? 2 : 4;                  // the last layer's fp / pp messages reach no output
+    t.ntiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
+    t.n_ntiles = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
+    t.pp_slot = pruned ? 2 : 1;
+    return t;
+}
+static LayerTiles layer_tiles(const pf_handle* h, int l) { return layer_tiles(h, l == h->cfg.n_convs - 1, l == prune_layer(h)); }
 // pocket sharing applies to inference calls at one common t whose conv layer 0 is the pruned layer under the static hoist
 static bool share_now(pf_handle* h) {
     const pf_config& c = h->cfg;
@@ -687,9 +697,9 @@ static HeadParams head_params(const pf_handle* h, float* eps_h, float* eps_x) {
 // the hoist's and the n16 form's fields, the two-wave streams (rgs: pf_debug_conv_layer passes none)
 static EdgeParams edge_params_base(const pf_handle* h, int layer, bool last, bool pruned) {
     const pf_config& c = h->cfg;
+    const LayerTiles lt = layer_tiles(h, last, pruned);
     EdgeParams e{};
-    e.tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
-    e.ntiles = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles); e.dyn_cnt = h->d_dyn_cnt;
+    e.tiles = lt.etiles; e.ntiles = lt.n_etiles; e.dyn_cnt = h->d_dyn_cnt;
     e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
     e.w = h->d_gvp + h->msg_base(layer, 0); e.n_gvps = c.n_message_gvps;
     rbf_params(c, e.rbf_mu, &e.rbf_inv_sigma);
@@ -699,11 +709,11 @@ static EdgeParams edge_params_base(const pf_handle* h, int layer, bool last, boo
 // node update of a conv layer.  The caller's: msg rows, h / v in and out, grp / grp_pa, pp_slot 3 of a shared launch, the two-wave streams
 static NodeParams node_params_base(const pf_handle* h, int layer, bool last, bool pruned) {
     const pf_config& c = h->cfg;
+    const LayerTiles lt = layer_tiles(h, last, pruned);
     NodeParams n{};
-    n.tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
-    n.ntiles = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
+    n.tiles = lt.ntiles; n.ntiles = lt.n_ntiles;
     n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N;
-    n.pp_slot = pruned ? 2 : 1; n.row_ids = h->d_act_ids; n.dyn_cnt = h->d_dyn_cnt; n.zero_row = h->zero_row;
+    n.pp_slot = lt.pp_slot; n.row_ids = h->d_act_ids; n.dyn_cnt = h->d_dyn_cnt; n.zero_row = h->zero_row;
     n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
     n.n_upd = c.n_update_gvps;
     for (int nt = 0; nt < 2; ++nt) {
@@ -833,13 +843,13 @@ static int ensure_wide_pack(pf_handle* h, hipStream_t s) {
         auto frag = [](int n_out, int K) { return (size_t)((n_out + 15) / 16) * ((K + 3) / 4) * 64; };
         for_each_gvp(c, [&](const GvpSpec& g) {
             const int H = std::max(g.vi, g.vo);
+            const int* o = &h->po.gvp[6 * tab.size()];     // Wh Wu Wm bm Wg bg
             WideGvp w{};                    // (wm, wg: below, once d_wpk exists)
-            w.wh = h->d_flat + h->flat_offset(g.prefix + "Wh"); w.wu = h->d_flat + h->flat_offset(g.prefix + "Wu");
-            w.bm = h->d_flat + h->flat_offset(g.prefix + "to_feats_out.0.bias"); w.bg = h->d_flat + h->flat_offset(g.prefix + "scalar_to_vector_gates.bias");
+            w.wh = h->d_flat + o[0]; w.wu = h->d_flat + o[1]; w.bm = h->d_flat + o[3]; w.bg = h->d_flat + o[5];
             w.vi = g.vi; w.vo = g.vo; w.si = g.si; w.so = g.so;
-            jobs.push_back({(int)h->flat_offset(g.prefix + "to_feats_out.0.weight"), g.so, g.si + H, (int)total});
+            jobs.push_back({o[2], g.so, g.si + H, (int)total});
             total += frag(g.so, g.si + H);
-            jobs.push_back({(int)h->flat_offset(g.prefix + "scalar_to_vector_gates.weight"), g.vo, g.so, (int)total});
+            jobs.push_back({o[4], g.vo, g.so, (int)total});
             total += frag(g.vo, g.so);
             tab.push_back(w);
         });
@@ -895,10 +905,10 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
     h->last_family.assign(c.n_convs, 64);
     int cur = 0;
     for (int l = 0; l < c.n_convs; ++l) {
-        const bool last = l == c.n_convs - 1, pruned = l == prune_layer(h);
+        const bool last = l == c.n_convs - 1;
+        const LayerTiles lt = layer_tiles(h, l);
         WideEdgeParams e{};
-        e.tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
-        e.ntiles = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles);
+        e.tiles = lt.etiles; e.ntiles = lt.n_etiles;
         e.dyn_cnt = h->d_dyn_cnt; e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
         e.h = st_h[cur]; e.v = st_v[cur]; e.layer0 = l == 0;
         e.msg_s = train ? h->wt.msg_s : h->d_msg_s; e.msg_v = train ? h->wt.msg_v : h->d_msg_v;
@@ -912,10 +922,9 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         }
         { ProfScope ps(h, pf_handle::K_EDGE, s); pfk_wide_edge(&e, train ? 1 : 0, s); }
         WideNodeParams n{};
-        n.tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
-        n.ntiles = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
+        n.tiles = lt.ntiles; n.ntiles = lt.n_ntiles;
         n.dyn_cnt = h->d_dyn_cnt; n.row_ids = h->d_act_ids;
-        n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N; n.pp_slot = pruned ? 2 : 1;
+        n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N; n.pp_slot = lt.pp_slot;
         n.msg_s = e.msg_s; n.msg_v = e.msg_v;
         n.h_in = e.h; n.v_in = e.v; n.layer0 = e.layer0;
         n.h_out = st_h[cur ^ 1]; n.v_out = st_v[cur ^ 1];
@@ -939,8 +948,8 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         if (last) {             // the last layer's node tiles are the centers: the noise head follows in the same launch
             n.head = h->d_wgvp + h->head_base(); n.n_head = c.n_noise_gvps;
             // (a handle of the specialised widths on the wide training leg: to_scalar_output as the flat vector stores it)
-            n.w_out = h->wide ? h->d_w + h->pk.wide_out_w : h->d_flat + h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.weight");
-            n.b_out = h->wide ? h->d_w + h->pk.wide_out_b : h->d_flat + h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.bias");
+            n.w_out = h->wide ? h->d_w + h->pk.wide_out_w : h->d_flat + h->po.out_w;
+            n.b_out = h->wide ? h->d_w + h->pk.wide_out_b : h->d_flat + h->po.out_b;
             n.pharm_nf = c.pharm_nf; n.node_base = h->Np;
             n.eps_h = eps_h; n.eps_x = eps_x;
             ProfScope ps(h, pf_handle::K_HEAD, s); pfk_wide_node(&n, train ? 1 : 0, s);
@@ -1371,7 +1380,6 @@ static int check_ready(pf_handle* h, bool need_batch) {
 // =================================================================================================
 // class of every parameter tensor: the kernel that differentiates it.  The gradient path numbers its classes for n_convs <= 4:
 // the list ends in front of the first tensor of a fifth conv layer (pf_commit_weights: n_tseg = -1, no gradient path)
-typedef std::vector<std::pair<std::string, std::pair<size_t, size_t>>> FlatLayout;     // name -> (offset, numel)
 static int tensor_classes(pf_handle* h, const FlatLayout& layout, std::vector<TensorSeg>& segs) {
     const pf_config& c = h->cfg;
     for (const auto& kv : layout) {
@@ -1497,11 +1505,12 @@ int pf_commit_weights(pf_handle* h) {
     int rc = pack_model(c, h->raw, h->spec, h->wide, pm, h->err);
     if (rc) return rc;
     // gradient path: the parameters once more as one flat vector in state-dict order
-    std::vector<float> flat;
     FlatLayout layout;
-    for (const auto& kv : expected_tensors(c)) {
+    ParamOffsets po;
+    if ((rc = param_offsets(c, expected_tensors(c), layout, po, h->err)) != PF_OK) return rc;
+    std::vector<float> flat;
+    for (const auto& kv : layout) {
         const RawTensor& t = h->raw[kv.first];
-        layout.push_back({kv.first, {flat.size(), t.data.size()}});
         flat.insert(flat.end(), t.data.begin(), t.data.end());
     }
     std::vector<TensorSeg> segs;
@@ -1510,7 +1519,7 @@ int pf_commit_weights(pf_handle* h) {
     // ---- the handle changes from here on.  A HIP call that fails leaves it uncommitted: some of its tables are then replaced, others not
     h->committed = false;
     h->flat_layout.swap(layout);
-    h->flat_index.clear(); h->flat_index_ok = false; h->edge_fx.clear();
+    h->po = std::move(po);
     h->enc_begin = enc_begin; h->enc_n = enc_n;
     h->pk = std::move(pm.lay);
     h->n_msg_tot = c.n_convs * 4 * c.n_message_gvps;
@@ -1535,10 +1544,9 @@ int pf_commit_weights(pf_handle* h) {
     PF_HIP(h, upload(&h->d_tseg, segs));
     std::vector<GvpT> tab;              // where each GVP's tensors sit in the flat vector
     for_each_gvp(c, [&](const GvpSpec& g) {
+        const int* o = &h->po.gvp[6 * tab.size()];
         GvpT t;
-        t.o_Wh = (int)h->flat_offset(g.prefix + "Wh"); t.o_Wu = (int)h->flat_offset(g.prefix + "Wu");
-        t.o_Wm = (int)h->flat_offset(g.prefix + "to_feats_out.0.weight"); t.o_bm = (int)h->flat_offset(g.prefix + "to_feats_out.0.bias");
-        t.o_Wg = (int)h->flat_offset(g.prefix + "scalar_to_vector_gates.weight"); t.o_bg = (int)h->flat_offset(g.prefix + "scalar_to_vector_gates.bias");
+        t.o_Wh = o[0]; t.o_Wu = o[1]; t.o_Wm = o[2]; t.o_bm = o[3]; t.o_Wg = o[4]; t.o_bg = o[5];
         t.vi = g.vi; t.vo = g.vo; t.h = std::max(g.vi, g.vo); t.si = g.si; t.so = g.so; t.sig = 1;
         t.pk = (int)tab.size();
         tab.push_back(t);
@@ -2254,13 +2262,25 @@ int pf_debug_conv_layer(pf_handle* h, int32_t layer, const float* dev_prot_x, co
 // ------------------------------------------------------------------------------------------------
 // gradient path (training step): forward that keeps the per-layer state, backward, parameter layout
 // ------------------------------------------------------------------------------------------------
-static int ensure_train_ws(pf_handle* h, hipStream_t s) {
-    if (h->d_tws && h->t_ws_ready) return PF_OK;
+// what the gradient kernels of both legs are built for: PF_OK, or the error
+static int train_limits_ok(pf_handle* h) {
     const pf_config& c = h->cfg;
     if (c.n_message_gvps > PFT_MAX_CHAIN || c.n_noise_gvps > PFT_MAX_CHAIN || c.n_update_gvps > 3)
         PF_FAIL(h, PF_ERR_ARG, "training supports at most %d message / noise GVPs and 3 update GVPs per chain", PFT_MAX_CHAIN);
     if (c.pharm_nf > 8 || c.rec_nf + 1 > 17 || c.pharm_nf + 1 > 17)
         PF_FAIL(h, PF_ERR_ARG, "training supports pharm_nf <= 8 and rec_nf <= 16");
+    return PF_OK;
+}
+// floats between two gradient copies: the parameter count rounded up to a multiple of 64 (16-byte aligned rows)
+static size_t grad_stride(const pf_handle* h) { return (h->nparams + 63) / 64 * 64; }
+// an element is dropped iff its hash is below p * 2^32 (pf_drop_hash; 0: no dropout)
+static bool dropout_ok(float p) { return p >= 0.f && p < 1.f; }
+static uint32_t drop_threshold(float p) { return p > 0.f ? (uint32_t)std::min(4294967295.0, (double)p * 4294967296.0) : 0u; }
+
+static int ensure_train_ws(pf_handle* h, hipStream_t s) {
+    if (h->d_tws && h->t_ws_ready) return PF_OK;
+    const pf_config& c = h->cfg;
+    if (const int rc = train_limits_ok(h)) return rc;
     const int L = c.n_convs, N = h->N;
     const size_t E1 = (size_t)h->Ecap + 1, Es = (size_t)std::max<int64_t>(h->Ecap, 1), Nf1 = (size_t)std::max(h->Nf, 1);
     const size_t ng = (size_t)c.n_message_gvps, nu = (size_t)c.n_update_gvps, nh = (size_t)c.n_noise_gvps;
@@ -2291,7 +2311,7 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
         w.take(h->t_lgx, (size_t)h->Nf * 3); w.take(h->t_lgh, (size_t)h->Nf * c.pharm_nf); w.take(h->t_lout, 64);      // loss buffers
         for (int l = 0; l < L; ++l) { w.take(h->t_nsv_z[l], nu * 2 * N * PF_S); w.take(h->t_nsv_g[l], nu * 2 * N * 16); w.take(h->t_nsv_v[l], nu * 2 * N * 48); }
         w.take(h->t_hsv_z, nh * Nf1 * PF_S); w.take(h->t_hsv_g, nh * Nf1 * 16); w.take(h->t_hsv_v, nh * Nf1 * 48);
-        w.take(h->t_gpart, (size_t)h->t_nblk * ((h->nparams + 63) / 64 * 64));
+        w.take(h->t_gpart, (size_t)h->t_nblk * grad_stride(h));
         for (int l = 0; l < L; ++l) { w.take(h->t_sv_z[l], ng * Es * PF_S); w.take(h->t_sv_g[l], ng * Es * 16); w.take(h->t_sv_v[l], ng * Es * 48); }
         w.take(h->t_gs_buf, Es * PF_S); w.take(h->t_gv_buf, Es * 48);
         if (pass == 0) {
@@ -2338,14 +2358,11 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
 static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
     if (h->d_wtws && h->wt_ready) return PF_OK;
     const pf_config& c = h->cfg;
-    if (c.n_message_gvps > PFT_MAX_CHAIN || c.n_noise_gvps > PFT_MAX_CHAIN || c.n_update_gvps > 3)
-        PF_FAIL(h, PF_ERR_ARG, "training supports at most %d message / noise GVPs and 3 update GVPs per chain", PFT_MAX_CHAIN);
-    if (c.pharm_nf > 8 || c.rec_nf + 1 > 17 || c.pharm_nf + 1 > 17)
-        PF_FAIL(h, PF_ERR_ARG, "training supports pharm_nf <= 8 and rec_nf <= 16");
+    if (const int rc = train_limits_ok(h)) return rc;
     const size_t L = c.n_convs, N = h->N, S = c.n_hidden_scalars, V3 = (size_t)3 * c.vector_size;
     const size_t ES = S + PF_R, EV = V3 + 3, Es = (size_t)std::max<int64_t>(h->Ecap, 1), Nf1 = (size_t)std::max(h->Nf, 1);
     const size_t nm = c.n_message_gvps, nu = c.n_update_gvps, nh = c.n_noise_gvps;
-    const size_t gstride = (h->nparams + 63) / 64 * 64;
+    const size_t gstride = grad_stride(h);
     pf_handle::WtWs& w = h->wt;
     // two passes over one list: sizes, then pointers
     size_t bytes = 0;
@@ -2389,12 +2406,31 @@ static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
 static void wide_train_common(pf_handle* h, float dropout_p, uint32_t seed) {
     WtCommon& wc = h->wt_common;
     wc = WtCommon{};
-    wc.W = h->d_flat; wc.gpart = h->wt.gpart; wc.gstride = (int)((h->nparams + 63) / 64 * 64);
+    wc.W = h->d_flat; wc.gpart = h->wt.gpart; wc.gstride = (int)grad_stride(h);
     wc.S = h->cfg.n_hidden_scalars; wc.V = h->cfg.vector_size; wc.N = h->N;
-    wc.drop_thr = dropout_p > 0.f ? (uint32_t)std::min(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
+    wc.drop_thr = drop_threshold(dropout_p);
     wc.drop_scale = 1.0f / (1.0f - dropout_p);
     wc.seed = seed;
     wc.mask_override = h->t_mask_override;
+}
+
+// What pf_train_forward and the loss entries do once their own arguments are checked: the dropout range, the workspace of the
+// selected leg, and the parameters every kernel of this step shares (h->t_common; the wide leg's h->wt_common).  who: the entry
+static int train_begin(pf_handle* h, float dropout_p, uint32_t seed, hipStream_t s, const char* who) {
+    if (!dropout_ok(dropout_p)) PF_FAIL(h, PF_ERR_ARG, "%s: dropout must be in [0, 1)", who);
+    const int rc = h->train_wide ? ensure_wide_train_ws(h, s) : ensure_train_ws(h, s);
+    if (rc) return rc;
+    if (h->train_wide) wide_train_common(h, dropout_p, seed);
+    TrainCommon& tc = h->t_common;
+    tc = TrainCommon{};
+    tc.W = h->d_flat; tc.gpart = h->t_gpart; tc.nparams = (int)h->nparams; tc.gstride = (int)grad_stride(h);
+    tc.tseg = h->d_tseg; tc.ntens = h->n_tseg;
+    tc.gpart_enc = h->t_gpart_enc; tc.enc_begin = h->enc_begin; tc.enc_n = h->enc_n;
+    tc.drop_thr = drop_threshold(dropout_p); tc.drop_scale = 1.0f / (1.0f - dropout_p); tc.seed = seed;
+    tc.mask_override = h->t_mask_override; tc.mask_N = h->N;
+    tc.bf16 = h->train_bf16 ? 1 : 0;
+    h->t_have_loss = false;                      // a new forward: the unit gradients of an earlier loss are void
+    return PF_OK;
 }
 
 // every training entry: the specialised gradient path serves 128 / 16 only; other widths need the width-generic leg
@@ -2468,22 +2504,8 @@ int pf_train_forward(pf_handle* h, const float* dev_prot_x, const float* dev_pha
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_pharm_x || !dev_pharm_h || !dev_t || !dev_eps_h || !dev_eps_x) PF_FAIL(h, PF_ERR_ARG, "pf_train_forward: null argument");
-    if (!(dropout_p >= 0.f && dropout_p < 1.f)) PF_FAIL(h, PF_ERR_ARG, "pf_train_forward: dropout must be in [0, 1)");
     hipStream_t s = (hipStream_t)stream;
-    rc = h->train_wide ? ensure_wide_train_ws(h, s) : ensure_train_ws(h, s);
-    if (rc) return rc;
-    if (h->train_wide) wide_train_common(h, dropout_p, seed);
-    h->t_common = TrainCommon{};
-    h->t_common.W = h->d_flat; h->t_common.gpart = h->t_gpart; h->t_common.nparams = (int)h->nparams;
-    h->t_common.gstride = (int)((h->nparams + 63) / 64 * 64);
-    h->t_common.tseg = h->d_tseg; h->t_common.ntens = h->n_tseg;
-    h->t_common.gpart_enc = h->t_gpart_enc; h->t_common.enc_begin = h->enc_begin; h->t_common.enc_n = h->enc_n;
-    h->t_common.drop_thr = dropout_p > 0.f ? (uint32_t)std::min(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
-    h->t_common.drop_scale = 1.0f / (1.0f - dropout_p);
-    h->t_common.seed = seed;
-    h->t_common.mask_override = h->t_mask_override; h->t_common.mask_N = h->N;
-    h->t_common.bf16 = h->train_bf16 ? 1 : 0;
-    h->t_have_loss = false;
+    if ((rc = train_begin(h, dropout_p, seed, s, __func__)) != PF_OK) return rc;
     load_state(h, dev_prot_x, dev_pharm_x, dev_pharm_h, s);
     pfk_copy(dev_t, h->d_t, (size_t)h->B, s);
     rc = run_dynamics(h, dev_eps_h, dev_eps_x, s, nullptr, true);
@@ -2502,23 +2524,10 @@ static int loss_forward(pf_handle* h, const float* dev_pharm_x0, const float* de
     if (!dev_pharm_x0 || !dev_pharm_h0 || !dev_t_int || !dev_eps_x || !dev_eps_h || !dev_alpha || !dev_sigma || !dev_out)
         PF_FAIL(h, PF_ERR_ARG, "%s: null argument", who);
     if (n_timesteps < 1 || !(feat_norm > 0.f)) PF_FAIL(h, PF_ERR_ARG, "%s: bad n_timesteps / feat_norm", who);
-    if (!(dropout_p >= 0.f && dropout_p < 1.f)) PF_FAIL(h, PF_ERR_ARG, "%s: dropout must be in [0, 1)", who);
-    if (h->Nf == 0) PF_FAIL(h, PF_ERR_ARG, "%s: the batch has no pharmacophore centers (the losses are means over them)", who);
+    // (a dropout_p out of range is reported first, by train_begin: the order of the entry's checks)
+    if (dropout_ok(dropout_p) && h->Nf == 0) PF_FAIL(h, PF_ERR_ARG, "%s: the batch has no pharmacophore centers (the losses are means over them)", who);
     hipStream_t s = (hipStream_t)stream;
-    rc = h->train_wide ? ensure_wide_train_ws(h, s) : ensure_train_ws(h, s);
-    if (rc) return rc;
-    if (h->train_wide) wide_train_common(h, dropout_p, seed);
-    h->t_have_loss = false;
-    h->t_common = TrainCommon{};
-    h->t_common.W = h->d_flat; h->t_common.gpart = h->t_gpart; h->t_common.nparams = (int)h->nparams;
-    h->t_common.gstride = (int)((h->nparams + 63) / 64 * 64);
-    h->t_common.tseg = h->d_tseg; h->t_common.ntens = h->n_tseg;
-    h->t_common.gpart_enc = h->t_gpart_enc; h->t_common.enc_begin = h->enc_begin; h->t_common.enc_n = h->enc_n;
-    h->t_common.drop_thr = dropout_p > 0.f ? (uint32_t)std::min(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
-    h->t_common.drop_scale = 1.0f / (1.0f - dropout_p);
-    h->t_common.seed = seed;
-    h->t_common.mask_override = h->t_mask_override; h->t_common.mask_N = h->N;
-    h->t_common.bf16 = h->train_bf16 ? 1 : 0;
+    if ((rc = train_begin(h, dropout_p, seed, s, who)) != PF_OK) return rc;
     LossParams lp{};
     lp.part = h->d_lpart + 16; lp.ticket = reinterpret_cast<int*>(h->d_lpart);
     lp.B = h->B; lp.Np = h->Np; lp.Nf = h->Nf; lp.nf = h->cfg.pharm_nf; lp.T = n_timesteps; lp.remove_com = remove_com; lp.weighted = weighted_loss;
@@ -2589,12 +2598,42 @@ int pf_train_loss_backward_out(pf_handle* h, const float* dev_g_out, float* dev_
 }
 
 
-// the backward pass of the width-generic leg: the reverse of run_dynamics_wide (pf_wide_train.hip lists the launches)
+// ---- the backward pass of the width-generic leg: the reverse of run_dynamics_wide (pf_wide_train.hip lists the launches) ----
+// One level of a chain (the message chains of a conv layer, its update chains, the noise head): the GVP table and level, the
+// level's input rows (already at the level) and buf_s / buf_v as upstream and output gradient alike, all rows of one shape.
+// The caller's: the tile table, sv_base, the head's output of level 0, what only the message chains read
+static WtChainParams wt_chain_params(const pf_handle* h, const GvpT* g, int g_stride, int n_levels, int lv, const float* sv_s,
+                                     const float* sv_v, float* buf_s, float* buf_v, int ls, int lvw) {
+    WtChainParams q{};
+    q.c = h->wt_common; q.dyn_cnt = h->d_dyn_cnt;
+    q.g = g; q.g_stride = g_stride; q.level = lv; q.last = lv == n_levels - 1;
+    q.sv_s = sv_s; q.sv_v = sv_v; q.sv_ls = ls; q.sv_lv = lvw;
+    q.up_s = buf_s; q.up_v = buf_v; q.up_ls = ls; q.up_lv = lvw;
+    q.out_s = buf_s; q.out_v = buf_v; q.out_ls = ls; q.out_lv = lvw;
+    return q;
+}
+// One of conv layer l's two GVPLayerNorms with the GVPDropout next to it (which: 0 message_layer_norms, 1 update_layer_norms):
+// tiles, the rows the forward normalised, the norm's parameters, the dropout stream.  The caller's: dyA / dyB, out1 / out2
+static WtNormParams wt_norm_params(const pf_handle* h, const LayerTiles& lt, int l, int which) {
+    const pf_config& c = h->cfg;
+    const size_t row0 = (size_t)l * h->N, S = c.n_hidden_scalars, V3 = (size_t)3 * c.vector_size;
+    WtNormParams n{};
+    n.c = h->wt_common; n.tiles = lt.ntiles; n.n_tiles = lt.n_ntiles; n.dyn_cnt = h->d_dyn_cnt; n.row_ids = h->d_act_ids;
+    n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
+    for (int nt = 0; nt < 2; ++nt) {
+        const int* o = &h->po.ln[(size_t)(l * 2 + nt) * 4 + 2 * which];
+        n.o_lw[nt] = o[0]; n.o_lb[nt] = o[1];
+    }
+    n.x_s = (which ? h->wt.x2_s : h->wt.x1_s) + row0 * S; n.x_v = (which ? h->wt.x2_v : h->wt.x1_v) + row0 * V3;
+    n.stream = l * 2 + which; n.use_norm = which ? 0 : 1;
+    return n;
+}
 static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* g_eps_x, float* dev_grad, hipStream_t s) {
     const pf_config& c = h->cfg;
     const int L = c.n_convs, N = h->N, S = c.n_hidden_scalars, V = c.vector_size, V3 = 3 * V, ES = S + PF_R, EV = V3 + 3;
+    const int nm = c.n_message_gvps, nu = c.n_update_gvps, nh = c.n_noise_gvps;
     pf_handle::WtWs& w = h->wt;
-    const WtCommon wc = h->wt_common;
+    const WtCommon& wc = h->wt_common;
     if (h->has_pend_scale) {
         const ScaleArgs& a = h->pend_scale;
         pfk_scale_loss(a.gx, a.nx, a.a, a.a2, a.gh, a.nh, a.b, a.b2, s);
@@ -2607,80 +2646,52 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
     {   // head: to_scalar_output, then its levels; the first level's input gradient is dL/d(last layer output) of the centers
         WtHeadOutParams p{};
         p.c = wc; p.Np = h->Np; p.Nf = h->Nf; p.pharm_nf = c.pharm_nf; p.g_eps_h = g_eps_h; p.g_eps_x = g_eps_x; p.h64 = w.h64;
-        p.o_Wout = (int)h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.weight");
-        p.o_bout = (int)h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.bias");
+        p.o_Wout = h->po.out_w; p.o_bout = h->po.out_b;
         p.up_s = w.gch_s; p.up_v = w.gch_v; p.up_ls = S; p.up_lv = V3;
         pfk_wt_head_out(&p, s);
         const size_t Nf1 = (size_t)std::max(h->Nf, 1);
-        for (int lv = c.n_noise_gvps - 1; lv >= 0; --lv) {
-            WtChainParams q{};
-            q.c = wc; q.ntiles = h->d_node_tiles; q.n_tiles = h->n_node_tiles_last; q.dyn_cnt = h->d_dyn_cnt; q.row_ids = h->d_act_ids;
-            q.g = h->d_gvpt + h->head_base(); q.g_stride = 0; q.level = lv; q.last = lv == c.n_noise_gvps - 1;
-            q.sv_s = w.hsv_s + (size_t)lv * Nf1 * S; q.sv_v = w.hsv_v + (size_t)lv * Nf1 * V3; q.sv_ls = S; q.sv_lv = V3; q.sv_base = h->Np;
-            q.up_s = w.gch_s; q.up_v = w.gch_v; q.up_ls = S; q.up_lv = V3;
-            q.out_s = lv == 0 ? w.G_s[a] : w.gch_s; q.out_v = lv == 0 ? w.G_v[a] : w.gch_v; q.out_ls = S; q.out_lv = V3;
+        for (int lv = nh - 1; lv >= 0; --lv) {
+            WtChainParams q = wt_chain_params(h, h->d_gvpt + h->head_base(), 0, nh, lv, w.hsv_s + (size_t)lv * Nf1 * S,
+                                              w.hsv_v + (size_t)lv * Nf1 * V3, w.gch_s, w.gch_v, S, V3);
+            q.ntiles = h->d_node_tiles; q.n_tiles = h->n_node_tiles_last; q.row_ids = h->d_act_ids; q.sv_base = h->Np;
+            if (lv == 0) { q.out_s = w.G_s[a]; q.out_v = w.G_v[a]; }
             ProfScope ps(h, pf_handle::K_BWD_HEAD, s);
             pfk_wt_chain(&q, 0, s);
         }
     }
     for (int l = L - 1; l >= 0; --l) {
-        // the tile lists of the forward (run_dynamics_wide): rows it did not compute have no backward
-        const bool last = l == L - 1, pruned = l == prune_layer(h);
-        const NodeTile* ntiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
-        const int n_nt = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
-        const EdgeTile* etiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
-        const int n_et = last ? h->n_edge_tiles_last : (pruned ? h->n_edge_tiles_act : h->n_edge_tiles);
-        const size_t lN = (size_t)l * N;
+        const LayerTiles lt = layer_tiles(h, l);    // the forward's tile lists: rows it did not compute have no backward
         PF_HIP(h, hipMemsetAsync(w.G_s[a ^ 1], 0, (size_t)N * S * sizeof(float), s));
         PF_HIP(h, hipMemsetAsync(w.G_v[a ^ 1], 0, (size_t)N * V3 * sizeof(float), s));
-        WtNormParams n{};
-        n.c = wc; n.tiles = ntiles; n.n_tiles = n_nt; n.dyn_cnt = h->d_dyn_cnt; n.row_ids = h->d_act_ids;
-        n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B; n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
-        auto ln_offsets = [&](const char* which) {
-            for (int nt = 0; nt < 2; ++nt) {
-                const std::string pre = conv_prefix(l) + which + "." + kNtKey[nt] + ".feat_norm.";
-                n.o_lw[nt] = (int)h->flat_offset(pre + "weight"); n.o_lb[nt] = (int)h->flat_offset(pre + "bias");
-            }
-        };
         {   // LayerNorm 2 and the residual dropout
-            ln_offsets("update_layer_norms");
-            n.dyA_s = w.G_s[a]; n.dyA_v = w.G_v[a]; n.dyB_s = nullptr; n.dyB_v = nullptr;
-            n.x_s = w.x2_s + lN * S; n.x_v = w.x2_v + lN * V3;
+            WtNormParams n = wt_norm_params(h, lt, l, 1);
+            n.dyA_s = w.G_s[a]; n.dyA_v = w.G_v[a];
             n.out1_s = w.gres_s; n.out1_v = w.gres_v; n.out2_s = w.gch_s; n.out2_v = w.gch_v;
-            n.stream = l * 2 + 1; n.use_norm = 0;
             ProfScope ps(h, pf_handle::K_BWD_NODE, s);
             pfk_wt_norm(&n, s);
         }
-        for (int lv = c.n_update_gvps - 1; lv >= 0; --lv) {
-            WtChainParams q{};
-            q.c = wc; q.ntiles = ntiles; q.n_tiles = n_nt; q.dyn_cnt = h->d_dyn_cnt; q.row_ids = h->d_act_ids;
-            q.g = h->d_gvpt + h->upd_base(l, 0); q.g_stride = c.n_update_gvps; q.level = lv; q.last = lv == c.n_update_gvps - 1;
-            q.sv_s = w.usv_s + ((size_t)l * c.n_update_gvps + lv) * N * S; q.sv_v = w.usv_v + ((size_t)l * c.n_update_gvps + lv) * N * V3;
-            q.sv_ls = S; q.sv_lv = V3; q.sv_base = 0;
-            q.up_s = w.gch_s; q.up_v = w.gch_v; q.up_ls = S; q.up_lv = V3;
-            q.out_s = w.gch_s; q.out_v = w.gch_v; q.out_ls = S; q.out_lv = V3;
+        for (int lv = nu - 1; lv >= 0; --lv) {
+            const size_t row0 = ((size_t)l * nu + lv) * N;
+            WtChainParams q = wt_chain_params(h, h->d_gvpt + h->upd_base(l, 0), nu, nu, lv, w.usv_s + row0 * S, w.usv_v + row0 * V3,
+                                              w.gch_s, w.gch_v, S, V3);
+            q.ntiles = lt.ntiles; q.n_tiles = lt.n_ntiles; q.row_ids = h->d_act_ids;
             ProfScope ps(h, pf_handle::K_BWD_NODE, s);
             pfk_wt_chain(&q, 0, s);
         }
         {   // the residual joins, LayerNorm 1, the message dropout and norm: dL/d(layer input) (residual path), dL/d(aggregate)
-            ln_offsets("message_layer_norms");
+            WtNormParams n = wt_norm_params(h, lt, l, 0);
             n.dyA_s = w.gch_s; n.dyA_v = w.gch_v; n.dyB_s = w.gres_s; n.dyB_v = w.gres_v;
-            n.x_s = w.x1_s + lN * S; n.x_v = w.x1_v + lN * V3;
             n.out1_s = w.G_s[a ^ 1]; n.out1_v = w.G_v[a ^ 1]; n.out2_s = w.gagg_s; n.out2_v = w.gagg_v;
-            n.stream = l * 2; n.use_norm = 1;
             ProfScope ps(h, pf_handle::K_BWD_NODE, s);
             pfk_wt_norm(&n, s);
         }
-        for (int lv = c.n_message_gvps - 1; lv >= 0; --lv) {
-            WtChainParams q{};
-            q.c = wc; q.etiles = etiles; q.n_tiles = n_et; q.dyn_cnt = h->d_dyn_cnt;
-            q.g = h->d_gvpt + h->msg_base(l, 0); q.g_stride = c.n_message_gvps; q.level = lv; q.last = lv == c.n_message_gvps - 1;
-            q.sv_s = w.esv_s + ((size_t)l * c.n_message_gvps + lv) * w.Es * ES; q.sv_v = w.esv_v + ((size_t)l * c.n_message_gvps + lv) * w.Es * EV;
-            q.sv_ls = ES; q.sv_lv = EV; q.sv_base = 0;
-            q.up_s = w.ges; q.up_v = w.gev; q.up_ls = ES; q.up_lv = EV;
-            q.out_s = w.ges; q.out_v = w.gev; q.out_ls = ES; q.out_lv = EV;
+        for (int lv = nm - 1; lv >= 0; --lv) {
+            const size_t row0 = ((size_t)l * nm + lv) * w.Es;
+            WtChainParams q = wt_chain_params(h, h->d_gvpt + h->msg_base(l, 0), nm, nm, lv, w.esv_s + row0 * ES, w.esv_v + row0 * EV,
+                                              w.ges, w.gev, ES, EV);
+            q.etiles = lt.etiles; q.n_tiles = lt.n_etiles;
             q.esrc = h->d_esrc; q.edst = h->d_edst; q.gagg_s = w.gagg_s; q.gagg_v = w.gagg_v;
-            q.in_cnt = h->d_in_cnt; q.pp_slot = pruned ? 2 : 1; q.norm_mode = c.message_norm_mode; q.l0 = l == 0;
+            q.in_cnt = h->d_in_cnt; q.pp_slot = lt.pp_slot; q.norm_mode = c.message_norm_mode; q.l0 = l == 0;
             q.A_h = w.A_h; q.A_v = w.A_v; q.fix = w.fix;
             ProfScope ps(h, pf_handle::K_BWD_EDGE_LEVEL, s);
             pfk_wt_chain(&q, 1, s);
@@ -2693,11 +2704,7 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
         WtEncParams p{};
         p.c = wc; p.Np = h->Np; p.Nf = h->Nf; p.rec_nf = c.rec_nf; p.pharm_nf = c.pharm_nf;
         p.prot_h0 = h->d_prot_h0; p.pharm_h = h->d_pharm_h; p.t = h->d_t; p.gid = h->d_gid;
-        for (int nt = 0; nt < 2; ++nt) {
-            const std::string pre = std::string("dynamics.") + kNtKey[nt] + "_encoder.";
-            p.o_w[nt] = (int)h->flat_offset(pre + "0.weight"); p.o_b[nt] = (int)h->flat_offset(pre + "0.bias");
-            p.o_lw[nt] = (int)h->flat_offset(pre + "2.weight"); p.o_lb[nt] = (int)h->flat_offset(pre + "2.bias");
-        }
+        for (int nt = 0; nt < 2; ++nt) { p.o_w[nt] = h->po.enc[nt][0]; p.o_b[nt] = h->po.enc[nt][1]; p.o_lw[nt] = h->po.enc[nt][2]; p.o_lb[nt] = h->po.enc[nt][3]; }
         p.G_h = w.G_s[a];
         pfk_wt_encode(&p, s);
     }
@@ -2705,6 +2712,241 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return PF_OK;
+}
+
+// ---- the backward pass of the specialised gradient kernels: a sequencer like run_dynamics --------------------------------------
+// What one pf_train_backward call computes once and its pieces share (a plain struct on the entry's stack).  The rule: a piece is
+// named for what it launches, every parameter struct has one builder, and which tiles a layer walks is layer_tiles' to say.
+struct BwdCall {
+    pf_handle* h; hipStream_t s; const float *g_eps_h, *g_eps_x;
+    bool side_on;                           // the side stream is another stream than the caller's (always, unless the caller passes it)
+    TrainCommon tc;                         // h->t_common with this call's k_pack_gvp tables
+    ReduceParams rp;                        // the final reduce; the early one is a copy with its own class mask
+    int a;                                  // t_G_*[a]: dL/d(output) of the layer being differentiated, [a ^ 1]: dL/d(its input)
+    bool first_clear_done;                  // the side stream cleared the last layer's input gradients
+    bool enc_grouped_done;                  // conv layer 0's join grouped the protein rows for the encoders (k_fix_enc_group)
+    unsigned early_mask;                    // classes the early reduce summed
+};
+static int bwd_grid(int nb, int ntiles) { return ntiles > 0 ? std::max(1, std::min(nb, 2 * ntiles)) : 0; }
+// (the encoders' backward differentiates the protein rows grouped by (graph, element) when the features can be one-hots)
+static bool enc_grouped(const pf_handle* h) { return h->cfg.rec_nf <= 16 && h->Np > 0; }
+// which gradient copies hold what: the grid of every launch of the pass, known before the first one
+static ReduceParams reduce_params(const pf_handle* h, float* dev_grad) {
+    ReduceParams rp{};
+    rp.gpart = h->t_gpart; rp.nparams = (int)h->nparams; rp.gstride = (int)grad_stride(h); rp.grad = dev_grad;
+    rp.tseg = h->d_tseg; rp.ntens = h->n_tseg; rp.NB = h->t_nblk; rp.ccnt = h->t_ccnt;
+    rp.gpart_enc = h->t_gpart_enc; rp.enc_begin = h->enc_begin; rp.enc_n = h->enc_n;
+    rp.head_grid = bwd_grid(h->t_nblk, h->n_head_tiles);
+    for (int l = 0; l < h->cfg.n_convs; ++l) {
+        const LayerTiles lt = layer_tiles(h, l);
+        rp.node_grid[l] = bwd_grid(h->t_nblk, lt.n_ntiles); rp.n_et[l] = lt.n_et;
+    }
+    rp.enc_grid = std::max(1, std::min(PFT_ENC_BLOCKS, (h->Np + PFT_ROWS - 1) / PFT_ROWS + (h->Nf + PFT_ROWS - 1) / PFT_ROWS));
+    return rp;
+}
+// the fragment tables of k_bwd_edge_level (re-packed when the weights moved), the loss's unit gradients times their upstream
+// scalars (extra blocks of the re-pack when there is one, else a launch of their own), the accumulators an aborted pass left dirty
+static int bwd_prologue(BwdCall& bc, float* dev_grad) {
+    pf_handle* h = bc.h;
+    const bool scale_now = h->has_pend_scale;
+    h->has_pend_scale = false;
+    if (h->wpack_version != h->w_version) {
+        const int ng = h->n_gvpt;
+        if (!h->d_wpack) PF_HIP(h, hipMalloc((void**)&h->d_wpack, (size_t)2 * std::max(ng, 1) * PFT_WPACK_FLOATS * sizeof(float)));
+        pfk_pack_gvp(h->d_flat, h->d_gvpt, ng, h->d_wpack, h->d_wpack + (size_t)ng * PFT_WPACK_FLOATS, scale_now ? &h->pend_scale : nullptr, bc.s);
+        h->wpack_version = h->w_version;
+    } else if (scale_now) {
+        const ScaleArgs& a = h->pend_scale;
+        pfk_scale_loss(a.gx, a.nx, a.a, a.a2, a.gh, a.nh, a.b, a.b2, bc.s);
+    }
+    h->t_common.wpack_b = h->d_wpack; h->t_common.wpack_f = h->d_wpack + (size_t)h->n_gvpt * PFT_WPACK_FLOATS;
+    bc.tc = h->t_common;
+    bc.rp = reduce_params(h, dev_grad);
+    if (h->tA_dirty) PF_HIP(h, hipMemsetAsync(h->d_tA, 0, h->tA_capacity, bc.s));      // an earlier pass stopped half way
+    h->tA_dirty = true;
+    return PF_OK;
+}
+// the dense work lists of conv layer l (k_compact_node_rows, k_compact_rows: one or two workgroups each, 10-20 us)
+static void bwd_work_lists(BwdCall& bc, int l, hipStream_t on) {
+    pf_handle* h = bc.h;
+    const LayerTiles lt = layer_tiles(h, l);
+    pfk_compact_node_rows(lt.ntiles, lt.n_ntiles, h->d_dyn_cnt, h->d_act_ids, h->N, h->t_ulist + h->t_ulist_cap * l, h->t_ucap, h->t_ccnt + 96 + 4 * l, on);
+    pfk_compact_rows(lt.etiles, lt.et_tile0, lt.n_et, h->d_dyn_cnt, h->t_clist + h->t_clist_cap * l, h->t_ccnt + 16 * l, on);
+}
+// The work lists depend on the forward's edge counts only: they are built on the side stream while the head's backward runs on
+// the caller's.  Two groups: what the first layer of the loop needs at once (its work lists, its cleared input gradients: cmp_ev[1]),
+// then the rest (the fixed-point scale, first read by that layer's edge kernels; the other layers' lists: cmp_ev[2], waited for
+// behind that layer's node kernel) -- as one group the side stream outlasted the head's backward by 28 us once that took 59
+static int bwd_side_lists(BwdCall& bc) {
+    pf_handle* h = bc.h;
+    const int L = h->cfg.n_convs;
+    for (int k = 0; k < 3; ++k)
+        if (!h->cmp_ev[k]) PF_HIP(h, hipEventCreateWithFlags(&h->cmp_ev[k], hipEventDisableTiming));
+    if (!h->s_side) PF_HIP(h, hipStreamCreateWithFlags(&h->s_side, hipStreamNonBlocking));
+    hipStream_t side = h->s_side;
+    bc.side_on = side != bc.s;
+    if (bc.side_on) { PF_HIP(h, hipEventRecord(h->cmp_ev[0], bc.s)); PF_HIP(h, hipStreamWaitEvent(side, h->cmp_ev[0], 0)); }
+    bwd_work_lists(bc, L - 1, side);
+    if (bc.side_on) {
+        // the first layer of the loop receives its input gradients in G[1]: cleared here, under the head's backward
+        ZeroBatch zb(side);
+        zb.add(h->t_G_h[1], (size_t)h->N * PF_S * 4);
+        if (L - 1 != 0) zb.add(h->t_G_v[1], (size_t)h->N * 48 * 4);
+        zb.flush();
+        bc.first_clear_done = true;
+        PF_HIP(h, hipEventRecord(h->cmp_ev[1], side));
+    }
+    pfk_fix_scale(bc.g_eps_h, h->Nf * h->cfg.pharm_nf, bc.g_eps_x, h->Nf * 3, h->t_fix, side);
+    for (int l = L - 2; l >= 0; --l) bwd_work_lists(bc, l, side);
+    if (bc.side_on) PF_HIP(h, hipEventRecord(h->cmp_ev[2], side));
+    return PF_OK;
+}
+// (the head kernel stores dL/d(last layer output) for every pharm row, and the last layer's node kernel reads those rows
+// only: no clearing of t_G_*[0] in front of it)
+static void bwd_head_launch(BwdCall& bc) {
+    pf_handle* h = bc.h;
+    const pf_config& c = h->cfg;
+    BwdHeadParams p{};
+    p.c = bc.tc; p.tiles = h->d_head_tiles; p.ntiles = h->n_head_tiles; p.node_base = h->Np;
+    p.h = h->t_H[c.n_convs]; p.v = h->t_V[c.n_convs];
+    p.g = h->d_gvpt + h->head_base(); p.n_gvps = c.n_noise_gvps;
+    p.o_Wout = h->po.out_w; p.o_bout = h->po.out_b;
+    p.pharm_nf = c.pharm_nf; p.g_eps_h = bc.g_eps_h; p.g_eps_x = bc.g_eps_x;
+    p.G_h = h->t_G_h[0]; p.G_v = h->t_G_v[0];
+    if (h->t_head_saved) { p.sv_z = h->t_hsv_z; p.sv_g = h->t_hsv_g; p.sv_v = h->t_hsv_v; p.sv_stride = (size_t)h->Nf; }
+    ProfScope ps(h, pf_handle::K_BWD_HEAD, bc.s);
+    pfk_bwd_head(&p, bc.rp.head_grid, bc.s);
+}
+static BwdNodeParams bwd_node_params(const BwdCall& bc, int l) {
+    const pf_handle* h = bc.h;
+    const pf_config& c = h->cfg;
+    const LayerTiles lt = layer_tiles(h, l);
+    const int a = bc.a;
+    BwdNodeParams n{};
+    n.c = bc.tc; n.tiles = lt.ntiles; n.ntiles = lt.n_ntiles;
+    n.pp_slot = lt.pp_slot; n.row_ids = h->d_act_ids; n.dyn_cnt = h->d_dyn_cnt;
+    n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = h->N;
+    n.msg_s = h->t_msg_s[l]; n.msg_v = h->t_msg_v[l]; n.zero_row = h->zero_row;
+    n.h_in = h->t_H[l]; n.v_in = h->t_V[l];
+    n.G_h_out = h->t_G_h[a]; n.G_v_out = h->t_G_v[a]; n.G_h_in = h->t_G_h[a ^ 1]; n.G_v_in = h->t_G_v[a ^ 1];
+    n.gagg_s = h->t_gagg_s; n.gagg_v = h->t_gagg_v;
+    n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B;
+    n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
+    n.upd = h->d_gvpt + h->upd_base(l, 0); n.n_upd = c.n_update_gvps;
+    for (int nt = 0; nt < 2; ++nt)
+        for (int k = 0; k < 4; ++k) n.o_ln[nt][k] = h->po.ln[(size_t)(l * 2 + nt) * 4 + k];
+    n.layer = l; n.l0 = l == 0;
+    n.grp = (int)h->t_grp.size() > l ? h->t_grp[l] : 32;
+    if ((int)h->t_node_saved.size() > l && h->t_node_saved[l]) {
+        n.sv_z = h->t_nsv_z[l]; n.sv_g = h->t_nsv_g[l]; n.sv_v = h->t_nsv_v[l]; n.sv_stride = (size_t)2 * h->N;
+    }
+    n.ulist = h->t_ulist + h->t_ulist_cap * l; n.ucnt = h->t_ccnt + 96 + 4 * l; n.ucap = h->t_ucap;
+    return n;
+}
+// The node kernel stores dL/d(layer input) for the rows it walks and the edge kernels add to it: cleared first, unless the side
+// stream has (the last layer's)
+static void bwd_node_launch(BwdCall& bc, int l) {
+    pf_handle* h = bc.h;
+    const bool last = l == h->cfg.n_convs - 1;
+    if (!(last && bc.first_clear_done)) {
+        ZeroBatch zb(bc.s);
+        zb.add(h->t_G_h[bc.a ^ 1], (size_t)h->N * PF_S * 4);
+        if (l != 0) zb.add(h->t_G_v[bc.a ^ 1], (size_t)h->N * 48 * 4);      // (conv layer 0 has no vector input: nobody writes or reads that gradient)
+        zb.flush();
+    }
+    const BwdNodeParams n = bwd_node_params(bc, l);
+    ProfScope ps(h, pf_handle::K_BWD_NODE, bc.s);
+    pfk_bwd_node(&n, bc.rp.node_grid[l], bc.s);
+}
+// the message chains of conv layer l; level and fx are set per launch
+static BwdEdgeLevelParams bwd_edge_params(const BwdCall& bc, int l) {
+    const pf_handle* h = bc.h;
+    const pf_config& c = h->cfg;
+    const LayerTiles lt = layer_tiles(h, l);
+    BwdEdgeLevelParams e{};
+    e.c = bc.tc; e.tiles = lt.etiles; e.dyn_cnt = h->d_dyn_cnt;
+    e.pp_slot = lt.pp_slot;
+    for (int et = 0; et <= 4; ++et) e.et_tile0[et] = lt.et_tile0[et];
+    e.n_et = lt.n_et;
+    e.clist = h->t_clist + h->t_clist_cap * l; e.ccnt = h->t_ccnt + 16 * l;
+    e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
+    e.h = h->t_H[l]; e.v = h->t_V[l];
+    e.gagg_s = h->t_gagg_s; e.gagg_v = h->t_gagg_v; e.in_cnt = h->d_in_cnt; e.N = h->N;
+    e.norm_mode = c.message_norm_mode;
+    e.G_h_in = h->t_G_h[bc.a ^ 1]; e.G_v_in = h->t_G_v[bc.a ^ 1];
+    e.sv_z = h->t_sv_z[l]; e.sv_g = h->t_sv_g[l]; e.sv_v = h->t_sv_v[l];
+    e.sv_stride = (size_t)std::max<int64_t>(h->Ecap, 1);
+    e.gs_buf = h->t_gs_buf; e.gv_buf = h->t_gv_buf;
+    e.g = h->d_gvpt + h->msg_base(l, 0); e.n_gvps = c.n_message_gvps;
+    rbf_params(c, e.rbf_mu, &e.rbf_inv_sigma);
+    e.l0 = l == 0;
+    e.A_h = h->t_A_h; e.A_v = h->t_A_v; e.fix = h->t_fix;
+    e.wpack = h->d_wpack + (size_t)h->msg_base(l, 0) * PFT_WPACK_FLOATS;
+    return e;
+}
+static void bwd_edge_levels(BwdCall& bc, int l) {
+    pf_handle* h = bc.h;
+    const int nm = h->cfg.n_message_gvps;
+    BwdEdgeLevelParams e = bwd_edge_params(bc, l);
+    for (int lv = nm - 1; lv >= 0; --lv) {
+        e.level = lv;
+        e.fx = h->no_fixed_shapes ? 0 : h->po.edge_fx[(size_t)l * nm + lv];
+        ProfScope ps(h, pf_handle::K_BWD_EDGE_LEVEL, bc.s);
+        pfk_bwd_edge_level(&e, h->t_nblk, bc.s);
+    }
+}
+// How conv layer l's fixed-point sums (the level-0 scatter to the source nodes) join dL/d(layer input):
+//   JOIN_ACTIVE_ROWS  the last layer's ff / pf edges scatter into pharm rows and active protein atoms only: the pruned layout's node tiles
+//   JOIN_ENC_GROUP    conv layer 0: in the pass that also groups the protein rows by (graph, element) for the encoders
+//   JOIN_ALL_ROWS     every row (and, above conv layer 0, every vector row)
+enum FixJoin { JOIN_ACTIVE_ROWS, JOIN_ENC_GROUP, JOIN_ALL_ROWS };
+static FixJoin fix_join_form(const pf_handle* h, int l) {
+    const bool last = l == h->cfg.n_convs - 1;
+    if (last && l != 0 && prune_layer(h) >= 0 && h->d_act_ids != nullptr && h->n_node_tiles_act > 0) return JOIN_ACTIVE_ROWS;
+    if (l == 0 && enc_grouped(h) && !h->no_fix_fuse) return JOIN_ENC_GROUP;
+    return JOIN_ALL_ROWS;
+}
+static void bwd_fix_join(BwdCall& bc, int l) {
+    pf_handle* h = bc.h;
+    float *G_h_in = h->t_G_h[bc.a ^ 1], *G_v_in = h->t_G_v[bc.a ^ 1];
+    const FixJoin form = fix_join_form(h, l);
+    if (form == JOIN_ACTIVE_ROWS)
+        pfk_fix_apply_rows(h->d_node_tiles_act, h->n_node_tiles_act, h->d_dyn_cnt, h->d_act_ids, h->t_A_h, G_h_in, h->t_A_v, G_v_in, h->t_fix, bc.s);
+    else if (form == JOIN_ENC_GROUP) {
+        pfk_fix_enc_group(h->t_A_h, G_h_in, h->t_fix, h->d_prot_ptr, h->d_ptype, h->B, h->cfg.rec_nf, h->t_Gg, h->Np, h->Nf, h->d_l0flag, bc.s);
+        bc.enc_grouped_done = true;
+    } else {
+        pfk_fix_apply(h->t_A_h, G_h_in, (size_t)h->N * PF_S, h->t_fix, bc.s);
+        if (l != 0) pfk_fix_apply(h->t_A_v, G_v_in, (size_t)h->N * 48, h->t_fix, bc.s);      // conv layer 0 has no vector input
+    }
+}
+// The head's and the last layer's node and message classes are complete: with more layers to go, their gradient copies are
+// summed on the side stream now (bandwidth-bound, ~140 MB) under the next layer's kernels
+static int bwd_early_reduce(BwdCall& bc, int l) {
+    pf_handle* h = bc.h;
+    ReduceParams early = bc.rp;
+    early.cls_mask = (1u << PFT_CLS_HEAD) | (1u << (PFT_CLS_NODE + l));
+    for (int et = 0; et < 4; ++et) early.cls_mask |= 1u << (PFT_CLS_MSG + l * 4 + et);
+    PF_HIP(h, hipEventRecord(h->cmp_ev[0], bc.s));
+    PF_HIP(h, hipStreamWaitEvent(h->s_side, h->cmp_ev[0], 0));
+    pfk_train_reduce(&early, h->s_side);
+    PF_HIP(h, hipEventRecord(h->cmp_ev[1], h->s_side));
+    bc.early_mask = early.cls_mask;
+    return PF_OK;
+}
+static void bwd_encoders(BwdCall& bc) {
+    pf_handle* h = bc.h;
+    const pf_config& c = h->cfg;
+    BwdEncodeParams p{};
+    p.c = bc.tc; p.Np = h->Np; p.Nf = h->Nf;
+    p.prot_h0 = h->d_prot_h0; p.pharm_h = h->d_pharm_h; p.t = h->d_t; p.gid = h->d_gid;
+    p.rec_nf = c.rec_nf; p.pharm_nf = c.pharm_nf;
+    for (int nt = 0; nt < 2; ++nt) { p.o_w[nt] = h->po.enc[nt][0]; p.o_b[nt] = h->po.enc[nt][1]; p.o_lw[nt] = h->po.enc[nt][2]; p.o_lb[nt] = h->po.enc[nt][3]; }
+    p.G_h = h->t_G_h[bc.a];
+    p.B = h->B; p.onehot_flag = h->d_l0flag;
+    p.Gg = enc_grouped(h) ? h->t_Gg : nullptr;
+    if (p.Gg && !bc.enc_grouped_done) pfk_enc_group(p.G_h, h->d_prot_ptr, h->d_ptype, h->B, c.rec_nf, h->t_Gg, bc.s);
+    pfk_bwd_encode(&p, bc.rp.enc_grid, bc.s);
 }
 
 int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, pf_stream stream) {
@@ -2715,221 +2957,26 @@ int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g
     if (!dev_g_eps_h || !dev_g_eps_x || !dev_grad) PF_FAIL(h, PF_ERR_ARG, "pf_train_backward: null argument");
     if (h->n_tseg < 0) PF_FAIL(h, PF_ERR_ARG, "pf_train_backward: the gradient path supports n_convs <= 4");
     if (h->train_wide) return wide_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, (hipStream_t)stream);
-    hipStream_t s = (hipStream_t)stream;
-    const pf_config& c = h->cfg;
-    const int L = c.n_convs, N = h->N, nb = h->t_nblk;
-    const bool scale_now = h->has_pend_scale;
-    h->has_pend_scale = false;
-    if (h->wpack_version != h->w_version) {         // packed to_feats_out fragments of the message GVPs for k_bwd_edge_level
-        const int ng = h->n_gvpt;
-        if (!h->d_wpack) PF_HIP(h, hipMalloc((void**)&h->d_wpack, (size_t)2 * std::max(ng, 1) * PFT_WPACK_FLOATS * sizeof(float)));
-        pfk_pack_gvp(h->d_flat, h->d_gvpt, ng, h->d_wpack, h->d_wpack + (size_t)ng * PFT_WPACK_FLOATS, scale_now ? &h->pend_scale : nullptr, s);
-        h->wpack_version = h->w_version;
-    } else if (scale_now) {
-        const ScaleArgs& a = h->pend_scale;
-        pfk_scale_loss(a.gx, a.nx, a.a, a.a2, a.gh, a.nh, a.b, a.b2, s);
-    }
-    h->t_common.wpack_b = h->d_wpack; h->t_common.wpack_f = h->d_wpack + (size_t)h->n_gvpt * PFT_WPACK_FLOATS;
-    const TrainCommon tc = h->t_common;
-    ReduceParams rp{};
-    rp.gpart = h->t_gpart; rp.nparams = (int)h->nparams; rp.gstride = (int)((h->nparams + 63) / 64 * 64); rp.grad = dev_grad; rp.tseg = h->d_tseg; rp.ntens = h->n_tseg;
-    rp.NB = nb; rp.ccnt = h->t_ccnt;
-    rp.gpart_enc = h->t_gpart_enc; rp.enc_begin = h->enc_begin; rp.enc_n = h->enc_n;
-    if (h->tA_dirty) PF_HIP(h, hipMemsetAsync(h->d_tA, 0, h->tA_capacity, s));      // an earlier pass stopped half way
-    h->tA_dirty = true;
-    // The dense work lists of every conv layer (k_compact_rows, k_compact_node_rows: one or two workgroups each, 10-20 us) depend
-    // on the forward's edge counts only: they are built on the side stream while the head's backward runs here.
-    bool first_clear_done = false;
-    auto layer_tables = [&](int l, const NodeTile*& nt_tiles, int& nt_n, const EdgeTile*& e_tiles, const int*& et0, int& n_et) {
-        const bool last = l == L - 1, pruned = h->prune && L >= 2 && l == L - 2;
-        nt_tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
-        nt_n = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
-        e_tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles;
-        et0 = pruned ? h->et_tile0_act : h->et_tile0;
-        n_et = last ? 2 : 4;                         // the last layer's fp / pp messages reach no output
-    };
-    {
-        for (int k = 0; k < 3; ++k)
-            if (!h->cmp_ev[k]) PF_HIP(h, hipEventCreateWithFlags(&h->cmp_ev[k], hipEventDisableTiming));
-        if (!h->s_side) PF_HIP(h, hipStreamCreateWithFlags(&h->s_side, hipStreamNonBlocking));
-        hipStream_t side = h->s_side;
-        if (side != s) { PF_HIP(h, hipEventRecord(h->cmp_ev[0], s)); PF_HIP(h, hipStreamWaitEvent(side, h->cmp_ev[0], 0)); }
-        // two groups: what the first layer of the loop below needs at once (its work lists, its cleared input gradients: cmp_ev[1]),
-        // then the rest (the fixed-point scale, first read by that layer's edge kernels; the other layers' lists: cmp_ev[2], waited
-        // for behind that layer's node kernel) -- as one group the side stream outlasted the head's backward by 28 us once that took 59
-        auto lists = [&](int l) {
-            const NodeTile* ntt; const EdgeTile* ett; const int* et0; int ntn, n_et;
-            layer_tables(l, ntt, ntn, ett, et0, n_et);
-            pfk_compact_node_rows(ntt, ntn, h->d_dyn_cnt, h->d_act_ids, N, h->t_ulist + h->t_ulist_cap * l, h->t_ucap, h->t_ccnt + 96 + 4 * l, side);
-            pfk_compact_rows(ett, et0, n_et, h->d_dyn_cnt, h->t_clist + h->t_clist_cap * l, h->t_ccnt + 16 * l, side);
-        };
-        lists(L - 1);
-        if (side != s) {
-            // the first layer of the loop below receives its input gradients in G[1]: cleared here, under the head's backward
-            ZeroBatch zb(side);
-            zb.add(h->t_G_h[1], (size_t)N * PF_S * 4);
-            if (L - 1 != 0) zb.add(h->t_G_v[1], (size_t)N * 48 * 4);
-            zb.flush();
-            first_clear_done = true;
-            PF_HIP(h, hipEventRecord(h->cmp_ev[1], side));
-        }
-        pfk_fix_scale(dev_g_eps_h, h->Nf * c.pharm_nf, dev_g_eps_x, h->Nf * 3, h->t_fix, side);      // (first read by the last layer's edge kernels)
-        for (int l = L - 2; l >= 0; --l) lists(l);
-        if (side != s) PF_HIP(h, hipEventRecord(h->cmp_ev[2], side));
-    }
-    // (the head kernel stores dL/d(last layer output) for every pharm row, and the last layer's node kernel reads those rows
-    // only: no clearing of t_G_*[0] here)
-    {
-        BwdHeadParams p{};
-        p.c = tc; p.tiles = h->d_head_tiles; p.ntiles = h->n_head_tiles; p.node_base = h->Np;
-        p.h = h->t_H[L]; p.v = h->t_V[L];
-        p.g = h->d_gvpt + h->head_base(); p.n_gvps = c.n_noise_gvps;
-        p.o_Wout = (int)h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.weight");
-        p.o_bout = (int)h->flat_offset("dynamics.noise_predictor.noise_predictor.to_scalar_output.bias");
-        p.pharm_nf = c.pharm_nf; p.g_eps_h = dev_g_eps_h; p.g_eps_x = dev_g_eps_x;
-        p.G_h = h->t_G_h[0]; p.G_v = h->t_G_v[0];
-        if (h->t_head_saved) { p.sv_z = h->t_hsv_z; p.sv_g = h->t_hsv_g; p.sv_v = h->t_hsv_v; p.sv_stride = (size_t)h->Nf; }
-        rp.head_grid = p.ntiles > 0 ? std::max(1, std::min(nb, 2 * p.ntiles)) : 0;
-        { ProfScope ps(h, pf_handle::K_BWD_HEAD, s); pfk_bwd_head(&p, rp.head_grid, s); }
-    }
-    if (h->s_side != s) PF_HIP(h, hipStreamWaitEvent(s, h->cmp_ev[1], 0));
-    int a = 0;
-    unsigned early_mask = 0;
-    // (the encoders' backward differentiates the protein rows grouped by (graph, element) when the features can be one-hots)
-    const bool enc_grouped = c.rec_nf <= 16 && h->Np > 0;
-    bool enc_grouped_done = false;
-    for (int l = L - 1; l >= 0; --l) {
-        // The last conv layer's output is read on the pharm nodes only (dynamics_gvp.py:91): its protein rows have a
-        // zero gradient, so -- as in the forward -- only the pharm node tiles and the ff / pf edge tiles do any work
-        // there.  The node kernel stores dL/d(layer input) for the rows it walks, the edge kernels add to it: clear first.
+    const int L = h->cfg.n_convs;
+    BwdCall bc{};
+    bc.h = h; bc.s = (hipStream_t)stream; bc.g_eps_h = dev_g_eps_h; bc.g_eps_x = dev_g_eps_x;
+    if ((rc = bwd_prologue(bc, dev_grad)) != PF_OK || (rc = bwd_side_lists(bc)) != PF_OK) return rc;
+    bwd_head_launch(bc);
+    if (bc.side_on) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[1], 0));       // the side stream's first group
+    // The last conv layer's output is read on the pharm nodes only (dynamics_gvp.py:91), the layer before it only where the last
+    // one reads it (the pharm nodes and the active atoms): every other row has a zero gradient and, as in the forward, no work
+    for (int l = L - 1; l >= 0; --l, bc.a ^= 1) {
         const bool last = l == L - 1;
-        // The layer before it is needed only where the last layer reads it: the pharm nodes and the protein atoms that
-        // are the source of a pf edge (the active atoms); every other row of its output has a zero gradient.  Same
-        // tile lists as the pruned forward.
-        const bool pruned = h->prune && L >= 2 && l == L - 2;
-        if (!(last && first_clear_done)) {
-            ZeroBatch zb(s);
-            zb.add(h->t_G_h[a ^ 1], (size_t)N * PF_S * 4);
-            if (l != 0) zb.add(h->t_G_v[a ^ 1], (size_t)N * 48 * 4);      // (conv layer 0 has no vector input: nobody writes or reads that gradient)
-            zb.flush();
-        }
-        BwdNodeParams n{};
-        n.c = tc; n.tiles = pruned ? h->d_node_tiles_act : h->d_node_tiles;
-        n.ntiles = last ? h->n_node_tiles_last : (pruned ? h->n_node_tiles_act : h->n_node_tiles);
-        n.pp_slot = pruned ? 2 : 1; n.row_ids = h->d_act_ids; n.dyn_cnt = h->d_dyn_cnt;
-        n.in_start = h->d_in_start; n.in_cnt = h->d_in_cnt; n.N = N;
-        n.msg_s = h->t_msg_s[l]; n.msg_v = h->t_msg_v[l]; n.zero_row = h->zero_row;
-        n.h_in = h->t_H[l]; n.v_in = h->t_V[l];
-        n.G_h_out = h->t_G_h[a]; n.G_v_out = h->t_G_v[a]; n.G_h_in = h->t_G_h[a ^ 1]; n.G_v_in = h->t_G_v[a ^ 1];
-        n.gagg_s = h->t_gagg_s; n.gagg_v = h->t_gagg_v;
-        n.gid = h->d_gid; n.gnorm = h->d_gnorm; n.B = h->B;
-        n.norm_mode = c.message_norm_mode; n.norm_value = c.message_norm_value;
-        n.upd = h->d_gvpt + h->upd_base(l, 0); n.n_upd = c.n_update_gvps;
-        for (int nt = 0; nt < 2; ++nt) {
-            const std::string p1 = conv_prefix(l) + "message_layer_norms." + kNtKey[nt] + ".feat_norm.";
-            const std::string p2 = conv_prefix(l) + "update_layer_norms." + kNtKey[nt] + ".feat_norm.";
-            n.o_ln[nt][0] = (int)h->flat_offset(p1 + "weight"); n.o_ln[nt][1] = (int)h->flat_offset(p1 + "bias");
-            n.o_ln[nt][2] = (int)h->flat_offset(p2 + "weight"); n.o_ln[nt][3] = (int)h->flat_offset(p2 + "bias");
-        }
-        n.layer = l; n.l0 = l == 0;
-        n.grp = (int)h->t_grp.size() > l ? h->t_grp[l] : 32;
-        if ((int)h->t_node_saved.size() > l && h->t_node_saved[l]) {
-            n.sv_z = h->t_nsv_z[l]; n.sv_g = h->t_nsv_g[l]; n.sv_v = h->t_nsv_v[l]; n.sv_stride = (size_t)2 * h->N;
-        }
-        n.ulist = h->t_ulist + h->t_ulist_cap * l; n.ucnt = h->t_ccnt + 96 + 4 * l; n.ucap = h->t_ucap;
-        rp.node_grid[l] = n.ntiles > 0 ? std::max(1, std::min(nb, 2 * n.ntiles)) : 0;
-        { ProfScope ps(h, pf_handle::K_BWD_NODE, s); pfk_bwd_node(&n, rp.node_grid[l], s); }
-        if (last && h->s_side != s) PF_HIP(h, hipStreamWaitEvent(s, h->cmp_ev[2], 0));      // the side stream's second group (above)
-        BwdEdgeLevelParams e{};
-        e.c = tc; e.tiles = pruned ? h->d_edge_tiles_act : h->d_edge_tiles; e.dyn_cnt = h->d_dyn_cnt;
-        e.pp_slot = pruned ? 2 : 1;
-        const int* et0 = pruned ? h->et_tile0_act : h->et_tile0;
-        for (int et = 0; et <= 4; ++et) e.et_tile0[et] = et0[et];
-        e.n_et = last ? 2 : 4;                       // the last layer's fp / pp messages reach no output
-        e.clist = h->t_clist + h->t_clist_cap * l; e.ccnt = h->t_ccnt + 16 * l;
-        rp.n_et[l] = e.n_et;
-        e.esrc = h->d_esrc; e.edst = h->d_edst; e.xn = h->d_xn;
-        e.h = h->t_H[l]; e.v = h->t_V[l];
-        e.gagg_s = h->t_gagg_s; e.gagg_v = h->t_gagg_v; e.in_cnt = h->d_in_cnt; e.N = N;
-        e.norm_mode = c.message_norm_mode;
-        e.G_h_in = h->t_G_h[a ^ 1]; e.G_v_in = h->t_G_v[a ^ 1];
-        e.sv_z = h->t_sv_z[l]; e.sv_g = h->t_sv_g[l]; e.sv_v = h->t_sv_v[l];
-        e.sv_stride = (size_t)std::max<int64_t>(h->Ecap, 1);
-        e.gs_buf = h->t_gs_buf; e.gv_buf = h->t_gv_buf;
-        e.g = h->d_gvpt + h->msg_base(l, 0); e.n_gvps = c.n_message_gvps;
-        rbf_params(c, e.rbf_mu, &e.rbf_inv_sigma);
-        e.l0 = l == 0;
-        e.A_h = h->t_A_h; e.A_v = h->t_A_v; e.fix = h->t_fix;
-        e.wpack = h->d_wpack + (size_t)h->msg_base(l, 0) * PFT_WPACK_FLOATS;
-        for (int lv = c.n_message_gvps - 1; lv >= 0; --lv) {
-            e.level = lv;
-            e.fx = 0;
-            if (!h->no_fixed_shapes) {
-                if (h->edge_fx.empty()) {
-                    h->edge_fx.assign((size_t)L * c.n_message_gvps, 0);
-                    for (int ll = 0; ll < L; ++ll)
-                        for (int j = 0; j < c.n_message_gvps; ++j) {
-                            bool f1 = true, f2 = true;
-                            for (int et = 0; et < 4; ++et) {
-                                const GvpSpec gs = msg_spec(c, ll, et, j);
-                                f1 = f1 && gs.vi == 16 && gs.vo == 16 && gs.si == 128 && gs.so == 128;
-                                f2 = f2 && gs.vi == 17 && gs.vo == 16 && gs.si == 144 && gs.so == 128;
-                            }
-                            h->edge_fx[(size_t)ll * c.n_message_gvps + j] = f1 ? 1 : (f2 ? 2 : 0);
-                        }
-                }
-                e.fx = h->edge_fx[(size_t)l * c.n_message_gvps + lv];
-            }
-            ProfScope ps(h, pf_handle::K_BWD_EDGE_LEVEL, s);
-            pfk_bwd_edge_level(&e, nb, s);
-        }
-        // the last layer's ff / pf edges scatter into pharm rows and active protein atoms only (the pruned layout's node tiles)
-        if (last && l != 0 && h->prune && L >= 2 && h->d_act_ids != nullptr && h->n_node_tiles_act > 0)
-            pfk_fix_apply_rows(h->d_node_tiles_act, h->n_node_tiles_act, h->d_dyn_cnt, h->d_act_ids, h->t_A_h, e.G_h_in, h->t_A_v, e.G_v_in,
-                               h->t_fix, s);
-        else if (l == 0 && enc_grouped && !h->no_fix_fuse) {
-            // conv layer 0: the scalar sums join G_h in the same pass that groups the protein rows by (graph, element) for the encoders
-            pfk_fix_enc_group(h->t_A_h, e.G_h_in, h->t_fix, h->d_prot_ptr, h->d_ptype, h->B, c.rec_nf, h->t_Gg, h->Np, h->Nf, h->d_l0flag, s);
-            enc_grouped_done = true;
-        } else {
-            pfk_fix_apply(h->t_A_h, e.G_h_in, (size_t)N * PF_S, h->t_fix, s);
-            if (l != 0) pfk_fix_apply(h->t_A_v, e.G_v_in, (size_t)N * 48, h->t_fix, s);       // conv layer 0 has no vector input
-        }
-        a ^= 1;
-        // the head's, this layer's node and message classes are complete: with more layers to go, their gradient copies are
-        // summed on the side stream now (bandwidth-bound, ~140 MB) under the next layer's kernels
-        if (last && L >= 2 && h->s_side != s) {
-            ReduceParams early = rp;
-            early.cls_mask = (1u << PFT_CLS_HEAD) | (1u << (PFT_CLS_NODE + l));
-            for (int et = 0; et < 4; ++et) early.cls_mask |= 1u << (PFT_CLS_MSG + l * 4 + et);
-            PF_HIP(h, hipEventRecord(h->cmp_ev[0], s));
-            PF_HIP(h, hipStreamWaitEvent(h->s_side, h->cmp_ev[0], 0));
-            pfk_train_reduce(&early, h->s_side);
-            PF_HIP(h, hipEventRecord(h->cmp_ev[1], h->s_side));
-            early_mask = early.cls_mask;
-        }
+        bwd_node_launch(bc, l);
+        if (last && bc.side_on) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[2], 0));      // the side stream's second group
+        bwd_edge_levels(bc, l);
+        bwd_fix_join(bc, l);
+        if (last && L >= 2 && bc.side_on && (rc = bwd_early_reduce(bc, l)) != PF_OK) return rc;
     }
-    {
-        BwdEncodeParams p{};
-        p.c = tc; p.Np = h->Np; p.Nf = h->Nf;
-        p.prot_h0 = h->d_prot_h0; p.pharm_h = h->d_pharm_h; p.t = h->d_t; p.gid = h->d_gid;
-        p.rec_nf = c.rec_nf; p.pharm_nf = c.pharm_nf;
-        for (int nt = 0; nt < 2; ++nt) {
-            const std::string pre = std::string("dynamics.") + kNtKey[nt] + "_encoder.";
-            p.o_w[nt] = (int)h->flat_offset(pre + "0.weight"); p.o_b[nt] = (int)h->flat_offset(pre + "0.bias");
-            p.o_lw[nt] = (int)h->flat_offset(pre + "2.weight"); p.o_lb[nt] = (int)h->flat_offset(pre + "2.bias");
-        }
-        p.G_h = h->t_G_h[a];
-        p.B = h->B; p.onehot_flag = h->d_l0flag;
-        p.Gg = (c.rec_nf <= 16 && h->Np > 0) ? h->t_Gg : nullptr;
-        if (p.Gg && !enc_grouped_done) pfk_enc_group(p.G_h, h->d_prot_ptr, h->d_ptype, h->B, c.rec_nf, h->t_Gg, s);
-        const int tiles = (h->Np + PFT_ROWS - 1) / PFT_ROWS + (h->Nf + PFT_ROWS - 1) / PFT_ROWS;
-        rp.enc_grid = std::max(1, std::min(PFT_ENC_BLOCKS, tiles));
-        pfk_bwd_encode(&p, rp.enc_grid, s);
-    }
-    rp.cls_mask = ~early_mask;
-    pfk_train_reduce(&rp, s);
-    if (early_mask) PF_HIP(h, hipStreamWaitEvent(s, h->cmp_ev[1], 0));       // the gradient is complete on the caller's stream
+    bwd_encoders(bc);
+    bc.rp.cls_mask = ~bc.early_mask;
+    pfk_train_reduce(&bc.rp, bc.s);
+    if (bc.early_mask) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[1], 0));       // the gradient is complete on the caller's stream
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     h->tA_dirty = false;

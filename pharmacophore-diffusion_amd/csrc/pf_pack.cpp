@@ -82,6 +82,57 @@ TensorList expected_tensors(const pf_config& c) {
     return v;
 }
 
+int param_offsets(const pf_config& c, const TensorList& tensors, FlatLayout& layout, ParamOffsets& out, std::string& err) {
+    layout.clear();
+    out = ParamOffsets{};
+    std::map<std::string, size_t> at;
+    size_t total = 0;
+    for (const auto& kv : tensors) {
+        size_t numel = 1;
+        for (int64_t d : kv.second) numel *= (size_t)d;
+        layout.push_back({kv.first, {total, numel}});
+        at[kv.first] = total;
+        total += numel;
+    }
+    bool ok = true;
+    auto off = [&](const std::string& name) {
+        const auto it = at.find(name);
+        if (it != at.end()) return (int)it->second;
+        if (ok) err = "internal: parameter " + name + " is not in the flat layout";
+        ok = false;
+        return 0;
+    };
+    const std::string head = "dynamics.noise_predictor.noise_predictor.to_scalar_output.";
+    out.out_w = off(head + "weight"); out.out_b = off(head + "bias");
+    for (int nt = 0; nt < 2; ++nt) {
+        const std::string p = std::string("dynamics.") + kNtKey[nt] + "_encoder.";
+        int k = 0;
+        for (const char* t : {"0.weight", "0.bias", "2.weight", "2.bias"}) out.enc[nt][k++] = off(p + t);
+    }
+    for (int l = 0; l < c.n_convs; ++l)
+        for (int nt = 0; nt < 2; ++nt)
+            for (const char* which : {"message_layer_norms", "update_layer_norms"}) {
+                const std::string p = conv_prefix(l) + which + "." + kNtKey[nt] + ".feat_norm.";
+                out.ln.push_back(off(p + "weight")); out.ln.push_back(off(p + "bias"));
+            }
+    for_each_gvp(c, [&](const GvpSpec& g) {
+        for (const char* t : {"Wh", "Wu", "to_feats_out.0.weight", "to_feats_out.0.bias", "scalar_to_vector_gates.weight", "scalar_to_vector_gates.bias"})
+            out.gvp.push_back(off(g.prefix + t));
+    });
+    // the two message-GVP shapes k_bwd_edge_level is instantiated for: a level whose four etypes all have one of them
+    for (int l = 0; l < c.n_convs; ++l)
+        for (int j = 0; j < c.n_message_gvps; ++j) {
+            bool f1 = true, f2 = true;
+            for (int et = 0; et < 4; ++et) {
+                const GvpSpec gs = msg_spec(c, l, et, j);
+                f1 = f1 && gs.vi == 16 && gs.vo == 16 && gs.si == 128 && gs.so == 128;
+                f2 = f2 && gs.vi == 17 && gs.vo == 16 && gs.si == 144 && gs.so == 128;
+            }
+            out.edge_fx.push_back(f1 ? 1 : (f2 ? 2 : 0));
+        }
+    return ok ? PF_OK : PF_ERR_STATE;
+}
+
 // ------------------------------------------------------------------------------------------------
 // packing into MFMA A-operand fragment order (see pf_device.h "F-layout")
 // ------------------------------------------------------------------------------------------------

@@ -34,6 +34,19 @@ GvpSpec upd_spec(const pf_config& c, int layer, int nt, int j);
 GvpSpec head_spec(const pf_config& c, int k);
 TensorList expected_tensors(const pf_config& c);       // state-dict order: the order of the flat parameter vector
 
+// The flat parameter vector of the gradient path (all tensors in state-dict order) and the offsets into it that the gradient
+// path reads on every call, resolved once by pf_commit_weights.  param_offsets fills both from a tensor list (expected_tensors(c));
+// a name the table needs that the list lacks is an error (PF_ERR_STATE, err set): no entry is ever -1.
+typedef std::vector<std::pair<std::string, std::pair<size_t, size_t>>> FlatLayout;     // name -> (offset, numel)
+struct ParamOffsets {
+    int out_w = 0, out_b = 0;               // to_scalar_output
+    int enc[2][4] = {};                     // per node type the encoder's 0.weight, 0.bias, 2.weight, 2.bias
+    std::vector<int> ln;                    // [layer][nt][4]: ln1_w ln1_b ln2_w ln2_b (message_layer_norms, update_layer_norms)
+    std::vector<int> gvp;                   // [for_each_gvp order][6]: Wh, Wu, to_feats_out.0.{weight, bias}, scalar_to_vector_gates.{weight, bias}
+    std::vector<int> edge_fx;               // [layer][message GVP level]: k_bwd_edge_level's shape class (BwdEdgeLevelParams::fx), 0: generic
+};
+int param_offsets(const pf_config& c, const TensorList& tensors, FlatLayout& layout, ParamOffsets& out, std::string& err);
+
 // every GVP in the order of the GvpW / GvpT / WideGvp tables: message GVPs [layer][etype][j], update GVPs [layer][ntype][j], the noise head's
 template <typename Fn>
 void for_each_gvp(const pf_config& c, Fn fn) {

@@ -1,6 +1,7 @@
 // pack_check -- the weight packer (csrc/pf_pack.cpp) on the CPU: packs seeded random tensors for a handful of configurations
 // and checks what a wrong index would break.  Built and run by tests/test_pack_host.py (host only, under the address and
 // undefined-behaviour sanitizers; once as is and once with -DN16_SPLIT=1).  Exit status 0: every check held.
+// Also the flat parameter layout and the offsets the gradient path reads per call (param_offsets), per configuration.
 //   pack_check [--dump DIR]      --dump: also writes DIR/cfg<k>.w / .map / .split (the packed image, the gather map, the split table)
 #include <cstdio>
 #include <cstring>
@@ -198,6 +199,63 @@ static void check_values(const Case& cs, const PackedModel& pm, const std::vecto
     }
 }
 
+// The flat layout and the table of offsets the gradient path reads (param_offsets): every entry against a lookup by name that
+// walks the layout, the layout against the cumulative sizes of the expected tensors, every shape class against msg_spec
+static void check_offsets(const Case& cs, const TensorList& exp) {
+    const pf_config& c = cs.c;
+    FlatLayout lay;
+    ParamOffsets po;
+    std::string err;
+    const int rc = param_offsets(c, exp, lay, po, err);
+    CHECK(rc == PF_OK && err.empty(), "param_offsets: %d (%s)", rc, err.c_str());
+    if (rc != PF_OK) return;
+    CHECK(lay.size() == exp.size(), "the layout has %zu tensors, expected %zu", lay.size(), exp.size());
+    size_t off = 0;
+    for (size_t i = 0; i < exp.size() && i < lay.size(); ++i) {
+        size_t numel = 1;
+        for (int64_t d : exp[i].second) numel *= (size_t)d;
+        CHECK(lay[i].first == exp[i].first && lay[i].second.first == off && lay[i].second.second == numel, "layout[%zu] = (%s, %zu, %zu), expected (%s, %zu, %zu)",
+              i, lay[i].first.c_str(), lay[i].second.first, lay[i].second.second, exp[i].first.c_str(), off, numel);
+        off += numel;
+    }
+    auto at = [&](const std::string& name) {
+        for (const auto& kv : lay) if (kv.first == name) return (long)kv.second.first;
+        CHECK(false, "%s is not in the layout", name.c_str());
+        return -1L;
+    };
+    auto same = [&](const char* what, int got, const std::string& name) { CHECK(got >= 0 && (long)got == at(name), "%s = %d, %s sits at %ld", what, got, name.c_str(), at(name)); };
+    const std::string head = "dynamics.noise_predictor.noise_predictor.to_scalar_output.";
+    same("out_w", po.out_w, head + "weight"); same("out_b", po.out_b, head + "bias");
+    const char* const enc_t[4] = {"0.weight", "0.bias", "2.weight", "2.bias"};
+    for (int nt = 0; nt < 2; ++nt)
+        for (int k = 0; k < 4; ++k) same("enc", po.enc[nt][k], std::string("dynamics.") + kNtKey[nt] + "_encoder." + enc_t[k]);
+    CHECK(po.ln.size() == (size_t)c.n_convs * 8, "ln has %zu entries", po.ln.size());
+    const char* const ln_t[4] = {"message_layer_norms", "message_layer_norms", "update_layer_norms", "update_layer_norms"};
+    for (size_t i = 0; i < po.ln.size(); ++i) {
+        const int l = (int)(i / 8), nt = (int)(i / 4 % 2), k = (int)(i % 4);
+        same("ln", po.ln[i], conv_prefix(l) + ln_t[k] + "." + kNtKey[nt] + ".feat_norm." + (k % 2 ? "bias" : "weight"));
+    }
+    std::vector<GvpSpec> specs;
+    for_each_gvp(c, [&](const GvpSpec& g) { specs.push_back(g); });
+    CHECK(po.gvp.size() == 6 * specs.size(), "gvp has %zu entries for %zu GVPs", po.gvp.size(), specs.size());
+    const char* const gvp_t[6] = {"Wh", "Wu", "to_feats_out.0.weight", "to_feats_out.0.bias", "scalar_to_vector_gates.weight", "scalar_to_vector_gates.bias"};
+    for (size_t i = 0; i < po.gvp.size() && i < 6 * specs.size(); ++i) same("gvp", po.gvp[i], specs[i / 6].prefix + gvp_t[i % 6]);
+    // shape classes: 1 = every etype's GVP is (16, 16, 128, 128), 2 = (17, 16, 144, 128), else 0 -- at other widths always 0
+    CHECK(po.edge_fx.size() == (size_t)c.n_convs * c.n_message_gvps, "edge_fx has %zu entries", po.edge_fx.size());
+    for (size_t i = 0; i < po.edge_fx.size(); ++i) {
+        const int l = (int)i / c.n_message_gvps, j = (int)i % c.n_message_gvps;
+        int cls = -1;
+        for (int et = 0; et < 4; ++et) {
+            const GvpSpec g = msg_spec(c, l, et, j);
+            const int k = (g.vi == 16 && g.vo == 16 && g.si == 128 && g.so == 128) ? 1 : ((g.vi == 17 && g.vo == 16 && g.si == 144 && g.so == 128) ? 2 : 0);
+            cls = (et == 0 || cls == k) ? k : 0;
+        }
+        CHECK(po.edge_fx[i] == cls, "edge_fx[%d][%d] = %d, msg_spec says %d", l, j, po.edge_fx[i], cls);
+        if (!cs.spec) CHECK(po.edge_fx[i] == 0, "edge_fx[%d][%d] = %d at widths %d / %d", l, j, po.edge_fx[i], c.n_hidden_scalars, c.vector_size);
+        else CHECK(po.edge_fx[i] == (j == 0 ? 2 : 1), "edge_fx[%d][%d] = %d at the specialised widths", l, j, po.edge_fx[i]);
+    }
+}
+
 static void dump(const std::string& path, const void* p, size_t bytes) {
     FILE* f = fopen(path.c_str(), "wb");
     if (!f || fwrite(p, 1, bytes, f) != bytes) { printf("cannot write %s\n", path.c_str()); ++g_fail; }
@@ -244,6 +302,7 @@ int main(int argc, char** argv) {
         if (rc == PF_OK) {
             check_values(cs, pm, flat, exp);
             check_layout(cs, pm);
+            check_offsets(cs, exp);
             if (dump_dir) {
                 const std::string b = std::string(dump_dir) + "/cfg" + std::to_string(k + 1);
                 dump(b + ".w", pm.w.data(), pm.w.size() * sizeof(float));
@@ -270,6 +329,18 @@ int main(int argc, char** argv) {
         CHECK(pack_model(c, r2, true, false, pm, err) == PF_ERR_WEIGHT && err == "wrong shape for dynamics.prot_encoder.0.bias", "shape: %s", err.c_str());
         RawMap r3 = raw; r3["extra.weight"] = RawTensor{{1}, {1.f}};
         CHECK(pack_model(c, r3, true, false, pm, err) == PF_ERR_WEIGHT && err == "unexpected weight tensor extra.weight", "unexpected: %s", err.c_str());
+    }
+    {   // a list that lacks a name the offsets table needs is rejected with a message, never answered with -1
+        const pf_config c = base_config();
+        TensorList cut = expected_tensors(c);
+        cut.pop_back();                     // to_scalar_output.bias
+        FlatLayout lay; ParamOffsets po; std::string err;
+        CHECK(param_offsets(c, cut, lay, po, err) == PF_ERR_STATE &&
+              err == "internal: parameter dynamics.noise_predictor.noise_predictor.to_scalar_output.bias is not in the flat layout", "truncated list: %s", err.c_str());
+        cut = expected_tensors(c);
+        cut.erase(cut.begin() + 9);         // the first message GVP's Wu
+        CHECK(param_offsets(c, cut, lay, po, err) == PF_ERR_STATE && err.find("edge_message_fns.pharm_ff_pharm.0.Wu is not in the flat layout") != std::string::npos,
+              "list without a GVP tensor: %s", err.c_str());
     }
     printf(g_fail ? "pack_check: %d check(s) FAILED\n" : "pack_check: all checks passed\n", g_fail);
     return g_fail ? 1 : 0;
