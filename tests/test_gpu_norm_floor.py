@@ -344,7 +344,9 @@ def grad_reference(key, c, drop):
 
 
 def record_budget(what, got, g32, g64):
-    """every tensor's error against the fp64 oracle's gradient as a ratio to max(e32, 2**-22); recorded, not asserted"""
+    """every tensor's error against the fp64 oracle's gradient as a ratio to max(e32, 2**-22); recorded, not asserted here --
+    tests/test_gpu_grad_budget.py asserts it, per 16 x 16 block and with a unit from several reference draws
+    (grad_budget.gradients_within_budget)"""
     rows = []
     for k, r64 in g64.items():
         m = float(r64.abs().max()) if r64.numel() else 0.0
