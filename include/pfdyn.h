@@ -287,6 +287,16 @@ int pf_train_forward(pf_handle* h, const float* dev_prot_x /*[Np,3] or NULL*/, c
                      float* dev_eps_h, float* dev_eps_x, pf_stream stream);
 int pf_train_backward(pf_handle* h, const float* dev_g_eps_h /*[Nf,pharm_nf]*/, const float* dev_g_eps_x /*[Nf,3]*/,
                       float* dev_grad /*[n_params]*/, pf_stream stream);
+/* pf_train_backward + the gradient of the same scalar w.r.t. the inputs of that forward: the center coordinates and the center
+ * feature rows as passed to pf_train_forward.  Either output pointer may be NULL; with both NULL the call IS pf_train_backward.
+ * Every element of a requested output is stored (nothing is accumulated), on the caller's stream, the same bits on every run.
+ * The edge sets are piecewise constant in the coordinates and carry no gradient (as torch on the reference); t and the protein
+ * coordinates get none.  Width-generic training leg only (pf_train_set_family(h, PF_TRAIN_FAMILY_WIDE): fp32, every supported
+ * width, a 128 / 16 handle included): on the tuned family a non-NULL output pointer is PF_ERR_ARG, nothing is launched and the
+ * kept forward stays good for pf_train_backward.  The forward keeps its own copy of the coordinates: the caller's buffers need
+ * not outlive pf_train_forward. */
+int pf_train_backward_inputs(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad /*[n_params]*/,
+                             float* dev_g_pharm_x /*[Nf,3] or NULL*/, float* dev_g_pharm_h /*[Nf,pharm_nf] or NULL*/, pf_stream stream);
 /* The loss around the dynamics, fused (PharmacophoreDiff.forward, pharmacodiff.py:162-243; pf_train_loss_forward: the noise
  * parameterisation of both outputs, pf_train_loss_forward_ep: every combination of endpoint_param_coord /
  * endpoint_param_feat, see below): per graph the COM of the clean centers is taken

@@ -71,6 +71,7 @@ SYMBOLS = {
     "pf_param_layout": (ctypes.c_int, [_P, _I32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "pf_train_forward": (ctypes.c_int, [_P, _P, _P, _P, _P, _F, ctypes.c_uint32, _P, _P, _P]),
     "pf_train_backward": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    "pf_train_backward_inputs": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "pf_train_loss_forward": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,
                                              ctypes.c_int32, ctypes.c_float, ctypes.c_uint32, _P, _P]),
     "pf_train_loss_forward_ep": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,

@@ -107,6 +107,7 @@ void pfk_wt_chain(const WtChainParams* p, int edge, hipStream_t s);
 void pfk_wt_norm(const WtNormParams* p, hipStream_t s);
 void pfk_wt_head_out(const WtHeadOutParams* p, hipStream_t s);
 void pfk_wt_encode(const WtEncParams* p, hipStream_t s);
+void pfk_wt_center_sum(const WtCenterSumParams* p, hipStream_t s);
 void pfk_wt_reduce(const float* gpart, int gstride, float* grad, int nparams, hipStream_t s);
 }
 
@@ -489,6 +490,8 @@ struct pf_handle {
         float *G_s[2], *G_v[2];             // dL/d(layer output / input), ping-pong [N]
         float *gch_s, *gch_v, *gres_s, *gres_v, *gagg_s, *gagg_v;   // per node: chain gradient, residual branch, aggregate
         float *ges, *gev;                   // per edge slot: gradient between two message-chain levels
+        float *xkeep, *gdiff;               // input gradients: the coordinates the forward read (float4 [N]); per conv layer and
+                                            // edge slot dL/d(x_src - x_dst) [Ecap][3]
         float *gpart, *fix;
         float *st_h[2], *st_v[2], *msg_s, *msg_v;   // the training forward's own layer states [N] and message rows [Ecap]: the
                                                     // inference buffers (and what the tuned kernels expect in them) stay untouched
@@ -903,6 +906,8 @@ static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream
         build_done(h, false);
     }
     h->last_family.assign(c.n_convs, 64);
+    // the gradient of the edge geometry reads the coordinates again (pf_train_backward_inputs): xn moves with the next call
+    if (train) pfk_copy(reinterpret_cast<const float*>(h->d_xn), h->wt.xkeep, (size_t)h->N * 4, s);
     int cur = 0;
     for (int l = 0; l < c.n_convs; ++l) {
         const bool last = l == c.n_convs - 1;
@@ -2377,6 +2382,7 @@ static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
         take(w.gch_s, N * S); take(w.gch_v, N * V3); take(w.gres_s, N * S); take(w.gres_v, N * V3);
         take(w.gagg_s, N * S); take(w.gagg_v, N * V3);
         take(w.ges, Es * ES); take(w.gev, Es * EV);
+        take(w.xkeep, N * 4); take(w.gdiff, L * Es * 3);
         take(w.gpart, (size_t)PFWT_NB * gstride); take(w.fix, 64);
         for (int a = 0; a < 2; ++a) { take(w.st_h[a], N * S); take(w.st_v[a], N * V3); }
         take(w.msg_s, Es * S); take(w.msg_v, Es * V3);
@@ -2628,7 +2634,19 @@ static WtNormParams wt_norm_params(const pf_handle* h, const LayerTiles& lt, int
     n.stream = l * 2 + which; n.use_norm = which ? 0 : 1;
     return n;
 }
-static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* g_eps_x, float* dev_grad, hipStream_t s) {
+// the centers' sums of the per-edge dL/d(x_src - x_dst) rows of every conv layer
+static WtCenterSumParams wt_center_sum_params(const pf_handle* h, float* g_x) {
+    WtCenterSumParams p{};
+    p.Np = h->Np; p.Nf = h->Nf; p.N = h->N; p.B = h->B; p.L = h->cfg.n_convs;
+    p.g_diff = h->wt.gdiff; p.layer_stride = h->wt.Es;
+    p.in_start = h->d_in_start; p.in_cnt = h->d_in_cnt; p.reg = h->d_reg; p.dyn_cnt = h->d_dyn_cnt;
+    p.esrc = h->d_esrc; p.gid = h->d_gid; p.g_x = g_x;
+    return p;
+}
+// g_x / g_h: dL/d(center coordinates) [Nf][3] / dL/d(center feature rows) [Nf][pharm_nf] of the same scalar, or NULL -- with both
+// NULL the launches and every bit of the parameter gradient are those of the plain backward
+static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* g_eps_x, float* dev_grad, float* g_x, float* g_h,
+                               hipStream_t s) {
     const pf_config& c = h->cfg;
     const int L = c.n_convs, N = h->N, S = c.n_hidden_scalars, V = c.vector_size, V3 = 3 * V, ES = S + PF_R, EV = V3 + 3;
     const int nm = c.n_message_gvps, nu = c.n_update_gvps, nh = c.n_noise_gvps;
@@ -2642,6 +2660,8 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
     PF_HIP(h, hipMemsetAsync(w.gpart, 0, (size_t)PFWT_NB * wc.gstride * sizeof(float), s));
     PF_HIP(h, hipMemsetAsync(h->d_wtA, 0, h->wtA_capacity, s));
     pfk_fix_scale(g_eps_h, h->Nf * c.pharm_nf, g_eps_x, h->Nf * 3, w.fix, s);
+    // (a layer's level-0 launch stores the rows of the slots it walks; the others -- the last layer's fp slots -- stay zero)
+    if (g_x) PF_HIP(h, hipMemsetAsync(w.gdiff, 0, (size_t)L * w.Es * 3 * sizeof(float), s));
     int a = 0;
     {   // head: to_scalar_output, then its levels; the first level's input gradient is dL/d(last layer output) of the centers
         WtHeadOutParams p{};
@@ -2693,6 +2713,10 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
             q.esrc = h->d_esrc; q.edst = h->d_edst; q.gagg_s = w.gagg_s; q.gagg_v = w.gagg_v;
             q.in_cnt = h->d_in_cnt; q.pp_slot = lt.pp_slot; q.norm_mode = c.message_norm_mode; q.l0 = l == 0;
             q.A_h = w.A_h; q.A_v = w.A_v; q.fix = w.fix;
+            if (g_x && lv == 0) {
+                q.g_diff = w.gdiff + (size_t)l * w.Es * 3; q.xn = reinterpret_cast<const float4*>(w.xkeep);
+                q.rbf_sigma = rbf_params(c, q.rbf_mu, nullptr);
+            }
             ProfScope ps(h, pf_handle::K_BWD_EDGE_LEVEL, s);
             pfk_wt_chain(&q, 1, s);
         }
@@ -2705,8 +2729,12 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
         p.c = wc; p.Np = h->Np; p.Nf = h->Nf; p.rec_nf = c.rec_nf; p.pharm_nf = c.pharm_nf;
         p.prot_h0 = h->d_prot_h0; p.pharm_h = h->d_pharm_h; p.t = h->d_t; p.gid = h->d_gid;
         for (int nt = 0; nt < 2; ++nt) { p.o_w[nt] = h->po.enc[nt][0]; p.o_b[nt] = h->po.enc[nt][1]; p.o_lw[nt] = h->po.enc[nt][2]; p.o_lb[nt] = h->po.enc[nt][3]; }
-        p.G_h = w.G_s[a];
+        p.G_h = w.G_s[a]; p.g_pharm_h = g_h;
         pfk_wt_encode(&p, s);
+    }
+    if (g_x) {
+        const WtCenterSumParams p = wt_center_sum_params(h, g_x);
+        pfk_wt_center_sum(&p, s);
     }
     pfk_wt_reduce(w.gpart, wc.gstride, dev_grad, (int)h->nparams, s);
     hipError_t e = hipGetLastError();
@@ -2949,14 +2977,19 @@ static void bwd_encoders(BwdCall& bc) {
     pfk_bwd_encode(&p, bc.rp.enc_grid, bc.s);
 }
 
-int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, pf_stream stream) {
-    PF_TRAIN_WIDTH_GUARD(h, __func__);
+// pf_train_backward (g_pharm_x == g_pharm_h == NULL) and pf_train_backward_inputs; who: the entry, for the messages
+static int train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, float* g_pharm_x,
+                          float* g_pharm_h, pf_stream stream, const char* who) {
+    PF_TRAIN_WIDTH_GUARD(h, who);
     int rc = check_ready(h, true);
     if (rc) return rc;
-    if (!h->t_have_fwd) PF_FAIL(h, PF_ERR_STATE, "pf_train_backward: no pf_train_forward on this batch");
-    if (!dev_g_eps_h || !dev_g_eps_x || !dev_grad) PF_FAIL(h, PF_ERR_ARG, "pf_train_backward: null argument");
-    if (h->n_tseg < 0) PF_FAIL(h, PF_ERR_ARG, "pf_train_backward: the gradient path supports n_convs <= 4");
-    if (h->train_wide) return wide_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, (hipStream_t)stream);
+    if (!h->t_have_fwd) PF_FAIL(h, PF_ERR_STATE, "%s: no pf_train_forward on this batch", who);
+    if (!dev_g_eps_h || !dev_g_eps_x || !dev_grad) PF_FAIL(h, PF_ERR_ARG, "%s: null argument", who);
+    if (h->n_tseg < 0) PF_FAIL(h, PF_ERR_ARG, "%s: the gradient path supports n_convs <= 4", who);
+    if ((g_pharm_x || g_pharm_h) && !h->train_wide)      // refused before anything is launched: the kept forward stays usable
+        PF_FAIL(h, PF_ERR_ARG, "%s: gradients w.r.t. the center coordinates and features are computed by the width-generic training "
+                               "leg only (pf_train_set_family(PF_TRAIN_FAMILY_WIDE), fp32, every supported width)", who);
+    if (h->train_wide) return wide_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, g_pharm_x, g_pharm_h, (hipStream_t)stream);
     const int L = h->cfg.n_convs;
     BwdCall bc{};
     bc.h = h; bc.s = (hipStream_t)stream; bc.g_eps_h = dev_g_eps_h; bc.g_eps_x = dev_g_eps_x;
@@ -2981,6 +3014,16 @@ int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g
     if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     h->tA_dirty = false;
     return PF_OK;
+}
+
+int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, pf_stream stream) {
+    return train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, nullptr, nullptr, stream, __func__);
+}
+
+int pf_train_backward_inputs(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, float* dev_g_pharm_x,
+                             float* dev_g_pharm_h, pf_stream stream) {
+    if (!dev_g_pharm_x && !dev_g_pharm_h) return pf_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, stream);
+    return train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, dev_g_pharm_x, dev_g_pharm_h, stream, __func__);
 }
 
 int pf_train_set_precision(pf_handle* h, int32_t precision) {

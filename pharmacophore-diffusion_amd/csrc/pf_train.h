@@ -236,6 +236,10 @@ struct WtChainParams {
     const int* in_cnt; int pp_slot, norm_mode, l0;
     long long* A_h; long long* A_v;          // level 0: fixed-point sums of dL/d(h_src, v_src) per source node [N][S], [N][V][3]
     const float* fix;                        // pfk_fix_scale
+    // level 0, input gradients requested (g_diff != NULL): dL/d(x_src - x_dst) of every valid edge row whose etype touches a
+    // center (ff, pf, fp) goes to g_diff[edge slot][3]; xn: the coordinates the training forward read
+    float* g_diff; const float4* xn;
+    float rbf_mu[PF_R]; float rbf_sigma;
 };
 struct WtNormParams {        // backward of one GVPLayerNorm of a conv layer and of the GVPDropout in front of / behind it
     WtCommon c;
@@ -261,4 +265,16 @@ struct WtEncParams {
     const float* prot_h0; const float* pharm_h; const float* t; const int* gid;
     int o_w[2], o_b[2], o_lw[2], o_lb[2];    // 0 prot, 1 pharm
     const float* G_h;                        // dL/d(encoder output) [N][S]
+    float* g_pharm_h;                        // dL/d(the centers' feature rows) [Nf][pharm_nf] (the t column is not an input), or NULL
+};
+// dL/d(center coordinates): per center the g_diff rows of its edges over all conv layers, in (layer, etype, slot) order -- minus
+// the rows of its ff and pf in-edges (the center is the destination: the in-edge ranges of the node update), plus the rows of
+// the ff and fp slots of its graph whose source it is (the graph's regions are walked and the source compared)
+struct WtCenterSumParams {
+    int Np, Nf, N, B, L;
+    const float* g_diff; size_t layer_stride;   // [L][layer_stride = edge slots][3]
+    const int* in_start; const int* in_cnt;     // [4][N]: slot 0 of a center its ff, slot 1 its pf in-edges
+    const int* reg; const int* dyn_cnt;         // [etype][B]: start and count of each graph's region
+    const int* esrc; const int* gid;
+    float* g_x;                                 // [Nf][3]: every element is stored
 };

@@ -9,7 +9,9 @@
 //                   only), the update-chain levels, the message-chain levels -- each level a launch, last level first
 //   k_wt_norm       a GVPLayerNorm with the GVPDropout beside it: "post" (LayerNorm 2, residual dropout) in front of the update
 //                   chain's backward, "pre" (LayerNorm 1, message dropout, the message norm) behind it
-//   k_wt_encode     the two encoders
+//   k_wt_encode     the two encoders (and, when asked for, dL/d(the centers' feature rows))
+//   k_wt_center_sum only when dL/d(center coordinates) is asked for: the level-0 launches of the message chains then also leave
+//                   dL/d(x_src - x_dst) per edge slot (wt_edge_geometry), and this launch sums every center's rows in a fixed order
 //   k_wt_reduce     the workgroups' gradient copies summed in index order: every element of the gradient vector is stored
 // A level is recomputed from its kept input (Vh, sh, z, a, the gates), then differentiated:
 //   dgate = sum_c dVout Vu, dVu = dVout gate, dpre = dgate gate', dWg += dpre (x) a, da = dA + Wg^T dpre, dz = da SiLU'(z),
@@ -121,6 +123,30 @@ __host__ __device__ inline WtLay wt_lay(int S, int V, bool edge) {
 __host__ __device__ inline size_t wt_chain_lds_floats(int S, int V, bool edge) {
     const WtLay L = wt_lay(S, V, edge);
     return (size_t)R * (L.ld + 3 * L.lz + 5 * L.vs + 2 * L.gw) + 4 * R;
+}
+
+// The edge geometry's backward (gvp.py:474-480, _rbf :26-41, _norm_no_nan :12-19) for one edge row of a level-0 message chain:
+// diff = x_src - x_dst, n2 = |diff|^2, d = sqrt(max(n2, 1e-8)) + 1e-8, u = diff / d, rbf_k = exp(-((d - mu_k) / sigma)^2); given
+// g_rbf [PF_R] and g_u [3],
+//   g_d = sum_k g_rbf[k] rbf_k (-2 (d - mu_k) / sigma^2) - (g_u . diff) / d^2,  g_diff = g_u / d + (n2 > 1e-8 ? g_d diff / sqrt(n2) : 0)
+// (nothing through the clamped norm).  diff, n2 and d in k_wide_edge's arithmetic, so the clamp decides as the forward's did; the
+// rbf values as the forward kept them; the few sums of a row in fp64, rounded once.
+__device__ __forceinline__ void wt_edge_geometry(const WtChainParams& p, int s, int d, int slot, const float* g_rbf, const float* g_u) {
+    const float4 xs = p.xn[s], xd = p.xn[d];
+    const float dx = xs.x - xd.x, dy = xs.y - xd.y, dz = xs.z - xd.z;
+    const float n2 = (dx * dx + dy * dy) + dz * dz;
+    const float dist = sqrtf(fmaxf(n2, 1e-8f)) + 1e-8f;
+    const float* rbf = p.sv_s + (size_t)(slot - p.sv_base) * p.sv_ls + p.c.S;
+    const double dd = (double)dist, sg = (double)p.rbf_sigma;
+    double gd = 0.0;
+#pragma unroll
+    for (int k = 0; k < PF_R; ++k) gd += (double)g_rbf[k] * (double)rbf[k] * (-2.0 * (dd - (double)p.rbf_mu[k]) / (sg * sg));
+    gd -= ((double)g_u[0] * dx + (double)g_u[1] * dy + (double)g_u[2] * dz) / (dd * dd);
+    const double m = n2 > 1e-8f ? gd / sqrt((double)n2) : 0.0;
+    float* o = p.g_diff + (size_t)slot * 3;
+    o[0] = (float)((double)g_u[0] / dd + m * dx);
+    o[1] = (float)((double)g_u[1] / dd + m * dy);
+    o[2] = (float)((double)g_u[2] / dd + m * dz);
 }
 
 template <bool EDGE>
@@ -337,6 +363,7 @@ __global__ __launch_bounds__(256) void k_wt_chain(const WtChainParams p) {
                         atomicAdd(reinterpret_cast<unsigned long long*>(p.A_v + (size_t)src[r] * 3 * V + q),
                                   (unsigned long long)__float2ll_rn(dv[r * vs + 3 + q] * fs));
                     }
+                if (p.g_diff && ty != ET_PP && tid < nv) wt_edge_geometry(p, src[tid], dst[tid], rid[tid], in + tid * ld + S, dv + tid * vs);
             } else {
                 for (int i = tid; i < nv * si; i += 256) {
                     const int r = i / si, f = i - r * si;
@@ -548,6 +575,41 @@ __global__ __launch_bounds__(256) void k_wt_encode(const WtEncParams p) {
             gp[p.o_lw[nt] + f] += sw;
             gp[p.o_lb[nt] + f] += sl;
         }
+        if (nt && p.g_pharm_h)                  // dL/dh_t = dz W over the feature columns
+            for (int idx = tid; idx < tn * nf; idx += 256) {
+                const int rr = idx / nf, k = idx - rr * nf;
+                float s = 0.f;
+                for (int f = 0; f < S; ++f) s = fmaf(dzb[rr * lz + f], w[f * K + k], s);
+                p.g_pharm_h[(size_t)(n0 - p.Np + rr) * nf + k] = s;
+            }
+    }
+}
+
+// one wave per center (WtCenterSumParams): every lane takes every 64th slot of a range, fp64 partial sums, one fixed tree at the end
+__global__ __launch_bounds__(256) void k_wt_center_sum(const WtCenterSumParams p) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= p.Nf) return;
+    const int n = p.Np + i, g = p.gid[n];
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int l = 0; l < p.L; ++l) {
+        const float* gd = p.g_diff + (size_t)l * p.layer_stride * 3;
+        for (int k = 0; k < 2; ++k) {           // destination of its ff, then its pf in-edges
+            const int st = p.in_start[k * p.N + n], c = p.in_cnt[k * p.N + n];
+            for (int e = st + lane; e < st + c; e += 64)
+                for (int q = 0; q < 3; ++q) a[q] -= (double)gd[(size_t)e * 3 + q];
+        }
+        for (int k = 0; k < 2; ++k) {           // source among its graph's ff, then fp slots
+            const int et = k == 0 ? ET_FF : ET_FP;
+            const int st = p.reg[et * p.B + g], c = p.dyn_cnt[et * p.B + g];
+            for (int e = st + lane; e < st + c; e += 64)
+                if (p.esrc[e] == n)
+                    for (int q = 0; q < 3; ++q) a[q] += (double)gd[(size_t)e * 3 + q];
+        }
+    }
+    for (int q = 0; q < 3; ++q) {
+        double s = a[q];
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) p.g_x[(size_t)i * 3 + q] = (float)s;
     }
 }
 
@@ -588,6 +650,10 @@ void pfk_wt_encode(const WtEncParams* p, hipStream_t s) {
     const size_t bytes = ((size_t)2 * PFW_ROWS * (p->c.S + 1) + PFW_ROWS * 17) * sizeof(float);
     (void)hipFuncSetAttribute((const void*)k_wt_encode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     hipLaunchKernelGGL(k_wt_encode, dim3(std::min(PFWT_NB, tiles)), dim3(256), bytes, s, *p);
+}
+void pfk_wt_center_sum(const WtCenterSumParams* p, hipStream_t s) {
+    if (p->Nf == 0) return;
+    hipLaunchKernelGGL(k_wt_center_sum, dim3((p->Nf + 3) / 4), dim3(256), 0, s, *p);
 }
 void pfk_wt_reduce(const float* gpart, int gstride, float* grad, int nparams, hipStream_t s) {
     if (nparams == 0) return;

@@ -198,15 +198,25 @@ class PfEngine:
                      "pf_train_forward")
         return eps_h, eps_x
 
-    def train_backward(self, g_eps_h, g_eps_x):
-        """d(loss)/d(parameters) as one flat vector (see param_layout) given d(loss)/d(eps)."""
+    def train_backward(self, g_eps_h, g_eps_x, input_grads=False):
+        """d(loss)/d(parameters) as one flat vector (see param_layout) given d(loss)/d(eps).  input_grads: also the gradient
+        w.r.t. the inputs of the last train_forward -- returns (grad, g_x_t [Nf, 3], g_h_t [Nf, pharm_nf]); True asks for both,
+        a pair of flags (x_t, h_t) for either (the other comes back as None).  Wide training family only."""
         gh, gx = _f32(g_eps_h, self.device), _f32(g_eps_x, self.device)
         if not hasattr(self, "n_params"):
             self.param_layout()
         grad = torch.empty(self.n_params, device=self.device)
+        if input_grads is False:
+            with torch.cuda.device(self.device):
+                self._ck(self.lib.pf_train_backward(self._h, _dptr(gh), _dptr(gx), _dptr(grad), _stream_ptr()), "pf_train_backward")
+            return grad
+        want_x, want_h = (True, True) if input_grads is True else (bool(input_grads[0]), bool(input_grads[1]))
+        g_x_t = torch.empty(self.Nf, 3, device=self.device) if want_x else None
+        g_h_t = torch.empty(self.Nf, self.pharm_nf, device=self.device) if want_h else None
         with torch.cuda.device(self.device):
-            self._ck(self.lib.pf_train_backward(self._h, _dptr(gh), _dptr(gx), _dptr(grad), _stream_ptr()), "pf_train_backward")
-        return grad
+            self._ck(self.lib.pf_train_backward_inputs(self._h, _dptr(gh), _dptr(gx), _dptr(grad), _dptr(g_x_t), _dptr(g_h_t),
+                                                       _stream_ptr()), "pf_train_backward_inputs")
+        return grad, g_x_t, g_h_t
 
     def train_loss_forward(self, pharm_x0, pharm_h0, t_int, eps_x, eps_h, alpha_tab, sigma_tab, n_timesteps, feat_norm,
                            remove_com=True, weighted_loss=False, dropout=0.0, seed=0, ep_coord=False, ep_feat=False):

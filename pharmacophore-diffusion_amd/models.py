@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import dataclasses
 import math
+import warnings
 from math import ceil
 from pathlib import Path
 from typing import Dict, List, Optional, Union
@@ -136,21 +137,28 @@ class PharmRecGVP(nn.Module):
         self.noise_predictor = NoisePredictionBlock(in_scalar_dim, out_scalar_dim, in_vector_dim, n_noise_gvps)
 
 
+_warned_no_input_grads = False
+
+
 class _DynamicsFn(torch.autograd.Function):
     """PharmRecDynamicsGVP.forward as one autograd node: forward = pf_train_forward (train-mode dropout inside the
     kernels), backward = pf_train_backward, which returns d(loss)/d(parameter) for every parameter as one flat vector.
-    The inputs (x_t, h_t, t, coordinates) get no gradient: nothing upstream of them is trainable
-    (pharmacodiff.py:162-243)."""
+    x_t and h_t get their gradient too when they require one and the engine is on the wide training family
+    (set_train_family('wide'): pf_train_backward_inputs); on the tuned family they get None, with one warning per
+    process.  The edge sets are piecewise constant in x_t and carry no gradient, as in the reference; t and the protein
+    coordinates get none."""
 
     @staticmethod
     def forward(ctx, mod, eng, x_t, h_t, t, prot_x, dropout, seed, flat_leaf):
         eps_h, eps_x = eng.train_forward(x_t, h_t, t, prot_x=prot_x, dropout=dropout, seed=seed)
         mod._fwd_token += 1
         ctx.mod, ctx.eng, ctx.token = mod, eng, mod._fwd_token
+        ctx.in_like = tuple((a.shape, a.dtype, a.device) if torch.is_tensor(a) else None for a in (x_t, h_t))
         return eps_h, eps_x
 
     @staticmethod
     def backward(ctx, g_h, g_x):
+        global _warned_no_input_grads
         mod, eng = ctx.mod, ctx.eng
         if ctx.token != mod._fwd_token:
             raise RuntimeError("backward of a PharmRecDynamicsGVP call that is not the most recent training forward: "
@@ -160,7 +168,19 @@ class _DynamicsFn(torch.autograd.Function):
         # ONE gradient for autograd: the flat vector, for the flat leaf that aliases every parameter (244 separate
         # gradient views and AccumulateGrad nodes cost 1.4 ms of host time per step -- more than the device could hide);
         # the hooks of the leaf re-bind each parameter's .grad to its slice (PharmRecDynamicsGVP._bind_grads)
-        return (None,) * 8 + (eng.train_backward(g_h, g_x),)
+        want = (ctx.needs_input_grad[2], ctx.needs_input_grad[3])
+        if not any(want):
+            return (None,) * 8 + (eng.train_backward(g_h, g_x),)
+        if eng.train_family() != "wide":
+            if not _warned_no_input_grads:
+                _warned_no_input_grads = True
+                warnings.warn("x_t / h_t require a gradient, but the tuned training family computes parameter gradients only: "
+                              "they get none.  set_train_family('wide') selects the family that differentiates the inputs.")
+            return (None,) * 8 + (eng.train_backward(g_h, g_x),)
+        grads = eng.train_backward(g_h, g_x, input_grads=want)
+        g_in = [None if g is None else g.to(device=like[2], dtype=like[1]).reshape(like[0])
+                for g, like in zip(grads[1:], ctx.in_like)]
+        return (None, None, g_in[0], g_in[1], None, None, None, None, grads[0])
 
 
 class _LossFn(torch.autograd.Function):
