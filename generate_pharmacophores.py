@@ -36,6 +36,9 @@ _FLAGS = [
     ('--pin_what', dict(choices=['both', 'position', 'type'], default='both', help='what of the pinned centers is fixed')),
     ('--pin_resamples', dict(type=int, default=None, help='with --pinned_centers: denoise every stretch of --pin_jump levels this many times, re-noising it in between, so that the free centers can react to the pinned ones (default 1: no resampling; a run costs about this many times the steps)')),
     ('--pin_jump', dict(type=int, default=None, help='with --pinned_centers: levels per resampled stretch (default 10)')),
+    ('--restraints', dict(type=Path, default=None, help='guided sampling: a text file with one restraint per line, "attract|repel x y z radius weight [center|*]" in the receptor\'s frame (# starts a comment): keep centers out of / pull a center into a sphere; a guided step costs several times a default one')),
+    ('--guide_scale', dict(type=float, default=None, help='with --restraints: strength of the guidance (default 1)')),
+    ('--guide_clip', dict(type=float, default=None, help='with --restraints: largest shift of a center per step in angstroms (default 0: no clip)')),
     ('--metrics', dict(action='store_true', help='print the validity of the samples against receptor pharmacophore features')),
 ]
 
@@ -51,6 +54,16 @@ def parse_arguments(argv=None):
             parser.error(f'--{flag} needs --pinned_centers')
         if v is not None and v < 1:
             parser.error(f'--{flag} must be at least 1, got {v}')
+    for flag in ('guide_scale', 'guide_clip'):
+        v = getattr(a, flag)
+        if v is not None and a.restraints is None:
+            parser.error(f'--{flag} needs --restraints')
+        if v is not None and not v >= 0:
+            parser.error(f'--{flag} must not be negative, got {v}')
+    a.guide_scale = 1.0 if a.guide_scale is None else a.guide_scale
+    a.guide_clip = 0.0 if a.guide_clip is None else a.guide_clip
+    if a.restraints is not None and a.pin_resamples is not None and a.pin_resamples > 1:
+        parser.error('--restraints together with --pin_resamples > 1: guidance with resampling jumps is not supported')
     a.pin_resamples = 1 if a.pin_resamples is None else a.pin_resamples
     a.pin_jump = 10 if a.pin_jump is None else a.pin_jump
     problems = []
@@ -68,6 +81,14 @@ def parse_arguments(argv=None):
         small = [n for n in a.pharm_sizes if n < k]
         if small:
             problems.append(f'--pharm_sizes {small} below the {k} centers of --pinned_centers')
+    a.restraint_list = None
+    if a.restraints is not None:
+        from pharmacoforge_amd.pocket_io import read_restraints
+        a.restraint_list = read_restraints(a.restraints)
+        named = [c for _, c, _, _, _ in a.restraint_list if c is not None]
+        small = [n for n in a.pharm_sizes if named and n <= max(named)]
+        if small:
+            problems.append(f'--pharm_sizes {small} do not reach center {max(named)} named in --restraints')
     if problems:
         raise ValueError('; '.join(problems))
     if a.ref_ligand_file is not None and a.residue_list:
@@ -75,12 +96,12 @@ def parse_arguments(argv=None):
     return a
 
 
-def pinned_sizes(sizes, k):
-    """Sizes drawn uniformly may fall below the k pinned centers: those are raised to k, with a note."""
+def pinned_sizes(sizes, k, what='pinned centers'):
+    """Sizes drawn uniformly may fall below the k pinned centers (or the centers --restraints names): those are raised to k, with a note."""
     sizes = [int(n) for n in sizes]
     raised = sum(n < k for n in sizes)
     if raised:
-        print(f'note: {raised} drawn size(s) below the {k} pinned centers raised to {k}', file=sys.stderr)
+        print(f'note: {raised} drawn size(s) below the {k} {what} raised to {k}', file=sys.stderr)
     return [max(n, k) for n in sizes]
 
 
@@ -140,19 +161,24 @@ def main(argv=None):
                                      pharm_pin_x=pin_x.to(device),
                                      pharm_pin_h=torch.nn.functional.one_hot(pin_types, model.n_pharm_feats).float().to(device))
 
+    k_named = 0
+    if args.restraint_list:
+        k_named = 1 + max([c for _, c, _, _, _ in args.restraint_list if c is not None], default=-1)
     t0 = time.time()
     pharms = []
     while len(pharms) < args.samples_per_pocket:
         n = min(args.samples_per_pocket - len(pharms), args.max_batch_size)
         sizes = args.pharm_sizes or model.pharm_size_dist.sample_uniformly(args.samples_per_pocket)
-        if k_pin and not args.pharm_sizes:
-            sizes = pinned_sizes(sizes, k_pin)
+        if max(k_pin, k_named) and not args.pharm_sizes:
+            sizes = pinned_sizes(sizes, max(k_pin, k_named), 'pinned centers' if k_pin >= k_named else 'centers named in --restraints')
         # like the reference (:329-333, utils/unorganized_utils.py:48) every chunk reads the size list from its start
         copies = pfa.batch(pfa.copy_graph(pocket, n, pharm_feats_per_copy=sizes))
         com = pocket.pharm_x0.repeat(n, 1) if args.use_ref_lig_com else None
         with torch.no_grad():
             pharms += model.sample_given_receptor(copies, init_pharm_com=com, visualize_trajectory=args.visualize_trajectory,
-                                                  pin_resamples=args.pin_resamples, pin_jump=args.pin_jump)
+                                                  pin_resamples=args.pin_resamples, pin_jump=args.pin_jump,
+                                                  restraints=[args.restraint_list] * n if args.restraint_list else None,
+                                                  guide_scale=args.guide_scale, guide_clip=args.guide_clip)
     elapsed = time.time() - t0
 
     (pocket_dir / 'sample_time.txt').write_text(f'{elapsed:.2f}')

@@ -269,6 +269,60 @@ int pf_sample_pinned_resampled(pf_handle* h, int32_t n_ops, const int32_t* host_
                                const float* dev_pin_h, int32_t endpoint_param_coord, int32_t endpoint_param_feat, float feat_norm_constant,
                                float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream);
 
+/* -- guided sampling: restraint energies steer the centers (reconstruction guidance; no reference counterpart) ------------------
+ * A guided run is a pinned run (pf_sample_begin_pinned's state; the flags may all be zero) plus a set of restraints per graph.
+ * A restraint is (kind, center, p[3], r, w): kind 0 attract / 1 repel; center a local center index in [0, nf_g) or -1 for every
+ * center of the graph; p in the CALLER's frame, as pin_x is; r >= 0, w >= 0.  For a center f it applies to, with y_f the predicted
+ * clean center in the caller's frame and rho = |y_f - p| (plain sqrtf):
+ *     attract:  E = w * max(0, rho - r)^2      dE/dy_f =  2 w max(0, rho - r) (y_f - p) / rho
+ *     repel  :  E = w * max(0, r - rho)^2      dE/dy_f = -2 w max(0, r - rho) (y_f - p) / rho          rho == 0: the gradient is 0
+ * (both C1).  Step i handles s = T-1-i, with D[g] as in a pinned run (caller's frame = sampler frame + D, taken before this step's
+ * shift) and alpha_t, sigma_t of level t = s+1 (pf_guide_coef):
+ *     eps        = dynamics(z_t, t)                      the width-generic training forward, dropout 0 (it keeps what the VJP reads)
+ *     x0_hat[f]  = (x_t[f] - sigma_t eps_x[f]) / alpha_t   noise parameterisation;   = eps_x[f]   endpoint_param_coord
+ *     y_f        = x0_hat[f] + D[g]
+ *     g0[f]      = sum over the graph's restraints j that apply to f, j ascending, of dE_j/dy_f          (fp32, this order)
+ *     E[g]       = sum over f ascending, j ascending, of E_j(y_f)
+ *     J(u)       = d(sum eps_x . u)/d x_t: the VJP of the dynamics (pf_dynamics_input_vjp's g_pharm_x with g_eps_h = 0)
+ *     grad[f]    = g0[f] / alpha_t - (sigma_t / alpha_t) J(g0)[f]   noise parameterisation;   = J(g0)[f]   endpoint_param_coord
+ *     shift[f]   = guide_scale * coef.sigma^2 * grad[f]   (posterior mean + scale * posterior variance * grad log p, log p = -E)
+ *     if guide_clip > 0 and |shift[f]| > guide_clip:  shift[f] *= guide_clip / |shift[f]|
+ *     x_s[f]     = (the usual p(z_s | z_t) value) - shift[f]
+ * then the pin selects (a position-pinned center ignores its shift) and the COM removal, exactly as in a pinned step.  One rounding
+ * per operation.  Features are not guided (h_s is the plain update).  D[g] is a constant for d(y)/d(x_t), and the edge sets carry
+ * no gradient (pf_train_backward_inputs).  A graph without restraints has g0 = 0 and, in the noise parameterisation, shift = 0
+ * exactly.
+ * The handle must be on PF_TRAIN_FAMILY_WIDE (otherwise PF_ERR_STATE: call pf_train_set_family first); a 128 / 16 handle's unguided
+ * runs stay on the tuned kernels.  pf_sample_begin_guided takes pf_sample_begin_pinned's arguments and HOST arrays restr_ptr[B+1]
+ * (graph g owns restraints [restr_ptr[g], restr_ptr[g+1])), restr_kind[n], restr_center[n], restr_p[n][3], restr_r[n], restr_w[n].
+ * Everything is validated on the host before anything is enqueued (kind, center range, finite p, r / w / scale / clip >= 0, at most
+ * 256 restraints per graph): a failure is PF_ERR_ARG and leaves the handle as it was.  The restraints travel through a pinned
+ * staging buffer into one allocation of the handle, kept and grown like the pin arrays; the host arrays may be freed on return.
+ * A guided run ends at the next begin of any kind or the next bind.  Inside it pf_denoise_step, pf_denoise_step_pinned and
+ * pf_renoise_step return PF_ERR_STATE (guidance with resampling jumps is not supported), and so does pf_denoise_step_guided outside
+ * it.  A guided step costs the training forward, two small launches and the inputs-only backward, all on the caller's stream
+ * without host synchronisation; pf_debug_kernel_family(h, n_convs) reports 0 after it.
+ * pf_sample_guided: pf_sample_pinned's arguments + host_guide_coef[n_steps] (entry i: s = T-1-i), the restraint arrays, scale, clip,
+ * and dev_energy [n_steps, B] (optional): E[g] as step i computed it. */
+typedef struct pf_guide_coef { float alpha_t; float sigma_t; } pf_guide_coef;      /* alpha / sigma(gamma((s+1)/T)), fp32, computed by the host */
+int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com /*[B,3] or NULL*/, const float* dev_noise0 /*[Nf,3+pharm_nf]*/,
+                           const int32_t* dev_pin_flags /*[Nf], 0..3*/, const float* dev_pin_x /*[Nf,3]*/, const float* dev_pin_h /*[Nf,pharm_nf]*/,
+                           float feat_norm_constant, const int32_t* host_restr_ptr /*[B+1]*/, const int32_t* host_restr_kind /*[n]*/,
+                           const int32_t* host_restr_center /*[n]*/, const float* host_restr_p /*[n,3]*/, const float* host_restr_r /*[n]*/,
+                           const float* host_restr_w /*[n]*/, float guide_scale, float guide_clip, pf_stream stream);
+int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_coef* pin_coef, const pf_guide_coef* guide_coef,
+                           const float* dev_noise /*[Nf,3+pharm_nf]*/, int32_t endpoint_param_coord, int32_t endpoint_param_feat, pf_stream stream);
+int pf_sample_guided(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef,
+                     const pf_guide_coef* host_guide_coef, const float* dev_noise, const float* dev_init_pharm_com,
+                     const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h, int32_t endpoint_param_coord,
+                     int32_t endpoint_param_feat, float feat_norm_constant, const int32_t* host_restr_ptr, const int32_t* host_restr_kind,
+                     const int32_t* host_restr_center, const float* host_restr_p, const float* host_restr_r, const float* host_restr_w,
+                     float guide_scale, float guide_clip, float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h,
+                     float* dev_energy /*[n_steps,B] or NULL*/, pf_stream stream);
+/* tests: the last guided step's vectors, each nullable -- g0, grad, shift [Nf,3] (a position-pinned center's rows are what it
+ * ignored) and E [B]; PF_ERR_STATE when no guided step has run on this batch */
+int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* dev_shift, float* dev_energy, pf_stream stream);
+
 /* -- training step: gradients of the dynamics (autograd through PharmRecDynamicsGVP.forward, ------
  *    dynamics_gvp.py:131-185, as used by PharmacophoreDiff.forward / training_step, pharmacodiff.py:162-276)
  * Parameters and gradients are exchanged as ONE flat fp32 vector in the reference's state-dict order
@@ -297,6 +351,14 @@ int pf_train_backward(pf_handle* h, const float* dev_g_eps_h /*[Nf,pharm_nf]*/, 
  * not outlive pf_train_forward. */
 int pf_train_backward_inputs(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad /*[n_params]*/,
                              float* dev_g_pharm_x /*[Nf,3] or NULL*/, float* dev_g_pharm_h /*[Nf,pharm_nf] or NULL*/, pf_stream stream);
+/* The gradients w.r.t. the inputs ALONE: pf_train_backward_inputs without the parameter gradient (what a guided sampling step
+ * needs).  Nothing of the weight-gradient work is done -- the workgroups' gradient copies are neither cleared nor summed, and the
+ * gradient kernels run in a form without their weight-gradient products.  Same preconditions as pf_train_backward_inputs (wide
+ * family, a kept pf_train_forward; it may be called any number of times on one forward, before or after a full backward); at least
+ * one output must be non-NULL (else PF_ERR_ARG).  Every element of a requested output is stored, with the bits
+ * pf_train_backward_inputs stores. */
+int pf_dynamics_input_vjp(pf_handle* h, const float* dev_g_eps_h /*[Nf,pharm_nf]*/, const float* dev_g_eps_x /*[Nf,3]*/,
+                          float* dev_g_pharm_x /*[Nf,3] or NULL*/, float* dev_g_pharm_h /*[Nf,pharm_nf] or NULL*/, pf_stream stream);
 /* The loss around the dynamics, fused (PharmacophoreDiff.forward, pharmacodiff.py:162-243; pf_train_loss_forward: the noise
  * parameterisation of both outputs, pf_train_loss_forward_ep: every combination of endpoint_param_coord /
  * endpoint_param_feat, see below): per graph the COM of the clean centers is taken

@@ -38,6 +38,10 @@ class PfRenoiseCoef(ctypes.Structure):
     _fields_ = [("alpha_t_given_s", ctypes.c_float), ("sigma_t_given_s", ctypes.c_float)]
 
 
+class PfGuideCoef(ctypes.Structure):
+    _fields_ = [("alpha_t", ctypes.c_float), ("sigma_t", ctypes.c_float)]
+
+
 # every symbol include/pfdyn.h declares: (name, restype, argtypes)
 _P, _I32, _I64, _F = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 SYMBOLS = {
@@ -67,6 +71,13 @@ SYMBOLS = {
     "pf_renoise_step": (ctypes.c_int, [_P, ctypes.POINTER(PfRenoiseCoef), _P, _P]),
     "pf_sample_pinned_resampled": (ctypes.c_int, [_P, _I32, ctypes.POINTER(_I32), ctypes.POINTER(PfStepCoef), ctypes.POINTER(PfPinCoef),
                                                   ctypes.POINTER(PfRenoiseCoef), _P, _P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P]),
+    "pf_sample_begin_guided": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _F, _F, _P]),
+    "pf_denoise_step_guided": (ctypes.c_int, [_P, ctypes.POINTER(PfStepCoef), ctypes.POINTER(PfPinCoef), ctypes.POINTER(PfGuideCoef), _P,
+                                              _I32, _I32, _P]),
+    "pf_sample_guided": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PfStepCoef), ctypes.POINTER(PfPinCoef), ctypes.POINTER(PfGuideCoef), _P, _P,
+                                        _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "pf_debug_last_guidance": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "pf_dynamics_input_vjp": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "pf_param_count": (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "pf_param_layout": (ctypes.c_int, [_P, _I32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "pf_train_forward": (ctypes.c_int, [_P, _P, _P, _P, _P, _F, ctypes.c_uint32, _P, _P, _P]),

@@ -540,6 +540,29 @@ struct PinParams {
 struct RenoiseParams {
     float alpha_ts, sigma_ts;  // alpha_{a|b}, sigma_{a|b} (pf_renoise_coef)
 };
+// guided sampling (pf_denoise_step_guided): restraint energies on the predicted clean centers.  k_guide_grad reads GuideParams
+// (of StepParams: the graph pointers, xn and eps_x) and leaves g0 = dE/dy per center, E per graph and the frame offset D per graph;
+// the guided update (k_step_update_guided) reads GuideShiftParams: g0, the VJP of the dynamics J(g0) and D
+struct GuideParams {
+    const int* restr_ptr;      // [B + 1]  graph g owns restraints [restr_ptr[g], restr_ptr[g + 1])
+    const int* restr_kind;     // [n]      0 attract, 1 repel
+    const int* restr_center;   // [n]      local center index, or -1: every center of the graph
+    const float* restr_p;      // [n][3]   caller's frame
+    const float* restr_r; const float* restr_w;
+    const float* com_init;     // [B][3]   mean of the original protein coordinates (pf_sample_begin)
+    float alpha_t, sigma_t;    // pf_guide_coef
+    int ep_coord;
+    float* g0;                 // [Nf][3]
+    float* energy;             // [B]
+    float* traj_energy;        // [B] row of the caller's trajectory of energies, or NULL
+    float* D;                  // [B][3]
+};
+struct GuideShiftParams {
+    const float* g0; const float* jx;   // [Nf][3] each
+    const float* D;            // [B][3], as k_guide_grad left it
+    float alpha_t, sigma_t, scale, clip;
+    float* grad; float* shift; // [Nf][3] each: what the step applied (pf_debug_last_guidance); a position-pinned center's row is what it ignored
+};
 #ifdef __HIPCC__
 // The p(z_s | z_t) update of sample_p_zs_given_zt (pharmacodiff.py:397-426) for ONE value -- coordinate or feature -- and the only place
 // it is written: the generic update, the latency-optimised one (center threads / feature lanes) and the center hoist's copy all call

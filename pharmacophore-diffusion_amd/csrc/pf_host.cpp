@@ -66,6 +66,8 @@ void pfk_step_update(const StepParams* p, hipStream_t s);
 void pfk_step_build(const StepParams* sp, const BuildParams* bp, int fast, hipStream_t s);
 void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const BuildParams* bp, hipStream_t s);
 void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s);
+void pfk_step_update_guided(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, hipStream_t s);
+void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s);
 void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s);
 void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s);
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
@@ -103,10 +105,10 @@ void pfk_wide_pack(const float* flat, const WidePackJob* jobs, int n_jobs, float
 void pfk_wide_edge(const WideEdgeParams* p, int train, hipStream_t s);
 void pfk_wide_node(const WideNodeParams* p, int train, hipStream_t s);
 // its gradient kernels (pf_wide_train.hip)
-void pfk_wt_chain(const WtChainParams* p, int edge, hipStream_t s);
-void pfk_wt_norm(const WtNormParams* p, hipStream_t s);
-void pfk_wt_head_out(const WtHeadOutParams* p, hipStream_t s);
-void pfk_wt_encode(const WtEncParams* p, hipStream_t s);
+void pfk_wt_chain(const WtChainParams* p, int edge, int wgrad, hipStream_t s);
+void pfk_wt_norm(const WtNormParams* p, int wgrad, hipStream_t s);
+void pfk_wt_head_out(const WtHeadOutParams* p, int wgrad, hipStream_t s);
+void pfk_wt_encode(const WtEncParams* p, int wgrad, hipStream_t s);
 void pfk_wt_center_sum(const WtCenterSumParams* p, hipStream_t s);
 void pfk_wt_reduce(const float* gpart, int gstride, float* grad, int nparams, hipStream_t s);
 }
@@ -362,6 +364,8 @@ struct pf_handle {
     unsigned long long* d_pa_chk = nullptr; // [3] violations, kept groups checked, kept groups behind a changed prefix (per handle, cumulative)
     bool no_fixed_shapes = false;           // PFDYN_NO_FIXED_SHAPES: k_bwd_edge_level reads every level's GVP shape from the table (the A/B of its FX forms)
     ScaleArgs pend_scale{}; bool has_pend_scale = false;    // loss_backward -> pf_train_backward: the unit gradients' scaling, not yet launched
+    bool vjp_full_kernels = false;          // PFDYN_VJP_FULL_KERNELS: the inputs-only backward launches the full pass's kernel forms (the A/B of the
+                                            // kernel-level skip; the host-level skip -- no clear, no reduce -- stays)
     bool no_fix_fuse = false;               // PFDYN_NO_FIX_FUSE: k_fix_apply and k_enc_group as two launches (the A/B of k_fix_enc_group)
     bool train_bf16 = false;                // pf_train_set_precision: the bf16 leg (dense Linears of the message chains' forward and of every
                                             // gradient kernel on bf16 matrix instructions; PFDYN_TRAIN_BF16=1 sets it at creation)
@@ -376,6 +380,19 @@ struct pf_handle {
     void* d_pin = nullptr; size_t pin_capacity = 0;
     int* d_pin_flags = nullptr; float *d_pin_x = nullptr, *d_pin_h = nullptr;
     float pin_feat_norm = 1.f;
+    // guided run (pf_sample_begin_guided): a pinned run plus restraint energies per graph.  The restraints are staged in pinned host
+    // memory (restr_ev: the last upload that reads the staging buffer) and live in one device allocation, kept and grown like d_pin:
+    // restr_ptr [B + 1], kind [n], center [n], p [n][3], r [n], w [n].  d_guide: what a guided step leaves -- g0, J(g0), grad, shift
+    // [Nf][3] each, the zero g_eps_h [Nf][pharm_nf], E [B], D [B][3]
+    bool guided = false;
+    void* d_restr = nullptr; size_t restr_capacity = 0;
+    void* restr_stage = nullptr; size_t restr_stage_capacity = 0; hipEvent_t restr_ev = nullptr;
+    int n_restr = 0;
+    float guide_scale = 0.f, guide_clip = 0.f;
+    void* d_guide = nullptr; size_t guide_capacity = 0;
+    float *d_g0 = nullptr, *d_gjx = nullptr, *d_ggrad = nullptr, *d_gshift = nullptr, *d_gzero = nullptr, *d_genergy = nullptr, *d_gD = nullptr;
+    bool guide_have = false;                // a guided step has run on this batch: pf_debug_last_guidance has something to return
+    float* guide_traj_energy = nullptr;     // pf_sample_guided: row i of the caller's [n_steps][B] for the step in flight
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
@@ -430,6 +447,7 @@ struct pf_handle {
         if (const char* e = getenv("PFDYN_TRAIN_NODE_RECOMPUTE")) train_node_save = atoi(e) == 0;
         if (const char* e = getenv("PFDYN_TRAIN_BF16")) train_bf16 = atoi(e) != 0;
         if (const char* e = getenv("PFDYN_NO_FIX_FUSE")) no_fix_fuse = atoi(e) != 0;
+        if (const char* e = getenv("PFDYN_VJP_FULL_KERNELS")) vjp_full_kernels = atoi(e) != 0;
         if (const char* e = getenv("PFDYN_NO_FIXED_SHAPES")) no_fixed_shapes = atoi(e) != 0;
         pol.from_env();
     }
@@ -1473,6 +1491,10 @@ void pf_destroy(pf_handle* h) {
     if (h->d_l0c) (void)hipFree(h->d_l0c);
     if (h->d_ptab) (void)hipFree(h->d_ptab);
     if (h->d_pin) (void)hipFree(h->d_pin);
+    if (h->d_restr) (void)hipFree(h->d_restr);
+    if (h->d_guide) (void)hipFree(h->d_guide);
+    if (h->restr_stage) (void)hipHostFree(h->restr_stage);
+    if (h->restr_ev) (void)hipEventDestroy(h->restr_ev);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
     for (int k = 0; k < 2; ++k) {
         if (h->d_tab[k]) (void)hipFree(h->d_tab[k]);
@@ -1801,7 +1823,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     if (fr.host_onehot >= 0) { h->l0_state = fr.host_onehot ? 1 : 2; h->l0_onehot = fr.host_onehot == 1; }
     h->zs_version = 0; h->zs_batch_coords = false; h->coords_custom = false;
     h->have_batch = true;
-    h->sampling = false; h->pinned = false;
+    h->sampling = false; h->pinned = false; h->guided = false; h->guide_have = false;
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
 }
@@ -1928,7 +1950,7 @@ int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* 
         h->snap_cur = 0;
     }
     h->coords_custom = false;               // a rigid translate of the batch's own coordinates from here on
-    h->sampling = true; h->pinned = false;
+    h->sampling = true; h->pinned = false; h->guided = false;
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
 }
@@ -1950,6 +1972,7 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
     if (rc) return rc;
     if (!coef || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step: null argument");
     if (!h->sampling) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step before pf_sample_begin");
+    if (h->guided) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step inside a guided run (pf_sample_begin_guided): use pf_denoise_step_guided");
     if (h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step inside a pinned run (pf_sample_begin_pinned): use pf_denoise_step_pinned");
     hipStream_t s = (hipStream_t)stream;
     StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
@@ -2008,6 +2031,7 @@ int pf_denoise_step_pinned(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     if (rc) return rc;
     if (!coef || !pin || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_pinned: null argument");
     if (!h->sampling || !h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_pinned outside a pinned run (pf_sample_begin_pinned)");
+    if (h->guided) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_pinned inside a guided run (pf_sample_begin_guided): use pf_denoise_step_guided");
     hipStream_t s = (hipStream_t)stream;
     const StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
     PinParams q{};
@@ -2034,6 +2058,7 @@ int pf_renoise_step(pf_handle* h, const pf_renoise_coef* coef, const float* dev_
     if (rc) return rc;
     if (!coef || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_renoise_step: null argument");
     if (!h->sampling || !h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_renoise_step outside a pinned run (pf_sample_begin_pinned)");
+    if (h->guided) PF_FAIL(h, PF_ERR_STATE, "pf_renoise_step inside a guided run: guidance with resampling jumps is not supported");
     hipStream_t s = (hipStream_t)stream;
     StepParams sp{};
     sp.B = h->B; sp.Np_tot = h->Np; sp.prot_ptr = h->d_prot_ptr; sp.pharm_ptr = h->d_pharm_ptr;
@@ -2644,9 +2669,14 @@ static WtCenterSumParams wt_center_sum_params(const pf_handle* h, float* g_x) {
     return p;
 }
 // g_x / g_h: dL/d(center coordinates) [Nf][3] / dL/d(center feature rows) [Nf][pharm_nf] of the same scalar, or NULL -- with both
-// NULL the launches and every bit of the parameter gradient are those of the plain backward
+// NULL the launches and every bit of the parameter gradient are those of the plain backward.
+// dev_grad == NULL: the inputs-only pass (pf_dynamics_input_vjp, a guided step).  The gradient copies are neither cleared nor summed,
+// every kernel runs in its form without weight-gradient products, and the encoders' backward runs only for g_h (its center tiles).
+// The per-row gradients take the same operations in both forms: g_x and g_h are the full pass's bits
 static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* g_eps_x, float* dev_grad, float* g_x, float* g_h,
                                hipStream_t s) {
+    const bool full = dev_grad != nullptr;
+    const int wg = (full || h->vjp_full_kernels) ? 1 : 0;      // the kernels' form (PFDYN_VJP_FULL_KERNELS: sums into copies nobody reads)
     const pf_config& c = h->cfg;
     const int L = c.n_convs, N = h->N, S = c.n_hidden_scalars, V = c.vector_size, V3 = 3 * V, ES = S + PF_R, EV = V3 + 3;
     const int nm = c.n_message_gvps, nu = c.n_update_gvps, nh = c.n_noise_gvps;
@@ -2657,7 +2687,7 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
         pfk_scale_loss(a.gx, a.nx, a.a, a.a2, a.gh, a.nh, a.b, a.b2, s);
         h->has_pend_scale = false;
     }
-    PF_HIP(h, hipMemsetAsync(w.gpart, 0, (size_t)PFWT_NB * wc.gstride * sizeof(float), s));
+    if (full) PF_HIP(h, hipMemsetAsync(w.gpart, 0, (size_t)PFWT_NB * wc.gstride * sizeof(float), s));
     PF_HIP(h, hipMemsetAsync(h->d_wtA, 0, h->wtA_capacity, s));
     pfk_fix_scale(g_eps_h, h->Nf * c.pharm_nf, g_eps_x, h->Nf * 3, w.fix, s);
     // (a layer's level-0 launch stores the rows of the slots it walks; the others -- the last layer's fp slots -- stay zero)
@@ -2668,7 +2698,7 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
         p.c = wc; p.Np = h->Np; p.Nf = h->Nf; p.pharm_nf = c.pharm_nf; p.g_eps_h = g_eps_h; p.g_eps_x = g_eps_x; p.h64 = w.h64;
         p.o_Wout = h->po.out_w; p.o_bout = h->po.out_b;
         p.up_s = w.gch_s; p.up_v = w.gch_v; p.up_ls = S; p.up_lv = V3;
-        pfk_wt_head_out(&p, s);
+        pfk_wt_head_out(&p, wg, s);
         const size_t Nf1 = (size_t)std::max(h->Nf, 1);
         for (int lv = nh - 1; lv >= 0; --lv) {
             WtChainParams q = wt_chain_params(h, h->d_gvpt + h->head_base(), 0, nh, lv, w.hsv_s + (size_t)lv * Nf1 * S,
@@ -2676,7 +2706,7 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
             q.ntiles = h->d_node_tiles; q.n_tiles = h->n_node_tiles_last; q.row_ids = h->d_act_ids; q.sv_base = h->Np;
             if (lv == 0) { q.out_s = w.G_s[a]; q.out_v = w.G_v[a]; }
             ProfScope ps(h, pf_handle::K_BWD_HEAD, s);
-            pfk_wt_chain(&q, 0, s);
+            pfk_wt_chain(&q, 0, wg, s);
         }
     }
     for (int l = L - 1; l >= 0; --l) {
@@ -2688,7 +2718,7 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
             n.dyA_s = w.G_s[a]; n.dyA_v = w.G_v[a];
             n.out1_s = w.gres_s; n.out1_v = w.gres_v; n.out2_s = w.gch_s; n.out2_v = w.gch_v;
             ProfScope ps(h, pf_handle::K_BWD_NODE, s);
-            pfk_wt_norm(&n, s);
+            pfk_wt_norm(&n, wg, s);
         }
         for (int lv = nu - 1; lv >= 0; --lv) {
             const size_t row0 = ((size_t)l * nu + lv) * N;
@@ -2696,14 +2726,14 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
                                               w.gch_s, w.gch_v, S, V3);
             q.ntiles = lt.ntiles; q.n_tiles = lt.n_ntiles; q.row_ids = h->d_act_ids;
             ProfScope ps(h, pf_handle::K_BWD_NODE, s);
-            pfk_wt_chain(&q, 0, s);
+            pfk_wt_chain(&q, 0, wg, s);
         }
         {   // the residual joins, LayerNorm 1, the message dropout and norm: dL/d(layer input) (residual path), dL/d(aggregate)
             WtNormParams n = wt_norm_params(h, lt, l, 0);
             n.dyA_s = w.gch_s; n.dyA_v = w.gch_v; n.dyB_s = w.gres_s; n.dyB_v = w.gres_v;
             n.out1_s = w.G_s[a ^ 1]; n.out1_v = w.G_v[a ^ 1]; n.out2_s = w.gagg_s; n.out2_v = w.gagg_v;
             ProfScope ps(h, pf_handle::K_BWD_NODE, s);
-            pfk_wt_norm(&n, s);
+            pfk_wt_norm(&n, wg, s);
         }
         for (int lv = nm - 1; lv >= 0; --lv) {
             const size_t row0 = ((size_t)l * nm + lv) * w.Es;
@@ -2718,25 +2748,25 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
                 q.rbf_sigma = rbf_params(c, q.rbf_mu, nullptr);
             }
             ProfScope ps(h, pf_handle::K_BWD_EDGE_LEVEL, s);
-            pfk_wt_chain(&q, 1, s);
+            pfk_wt_chain(&q, 1, wg, s);
         }
         pfk_fix_apply(w.A_h, w.G_s[a ^ 1], (size_t)N * S, w.fix, s);
         if (l != 0) pfk_fix_apply(w.A_v, w.G_v[a ^ 1], (size_t)N * V3, w.fix, s);      // conv layer 0 has no vector input
         a ^= 1;
     }
-    {
+    if (full || g_h) {
         WtEncParams p{};
         p.c = wc; p.Np = h->Np; p.Nf = h->Nf; p.rec_nf = c.rec_nf; p.pharm_nf = c.pharm_nf;
         p.prot_h0 = h->d_prot_h0; p.pharm_h = h->d_pharm_h; p.t = h->d_t; p.gid = h->d_gid;
         for (int nt = 0; nt < 2; ++nt) { p.o_w[nt] = h->po.enc[nt][0]; p.o_b[nt] = h->po.enc[nt][1]; p.o_lw[nt] = h->po.enc[nt][2]; p.o_lb[nt] = h->po.enc[nt][3]; }
         p.G_h = w.G_s[a]; p.g_pharm_h = g_h;
-        pfk_wt_encode(&p, s);
+        pfk_wt_encode(&p, wg, s);
     }
     if (g_x) {
         const WtCenterSumParams p = wt_center_sum_params(h, g_x);
         pfk_wt_center_sum(&p, s);
     }
-    pfk_wt_reduce(w.gpart, wc.gstride, dev_grad, (int)h->nparams, s);
+    if (full) pfk_wt_reduce(w.gpart, wc.gstride, dev_grad, (int)h->nparams, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return PF_OK;
@@ -3024,6 +3054,210 @@ int pf_train_backward_inputs(pf_handle* h, const float* dev_g_eps_h, const float
                              float* dev_g_pharm_h, pf_stream stream) {
     if (!dev_g_pharm_x && !dev_g_pharm_h) return pf_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, stream);
     return train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, dev_g_pharm_x, dev_g_pharm_h, stream, __func__);
+}
+
+// The VJP of the dynamics w.r.t. the inputs of the kept forward alone: wide_train_backward without a parameter gradient
+int pf_dynamics_input_vjp(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_g_pharm_x, float* dev_g_pharm_h,
+                          pf_stream stream) {
+    PF_TRAIN_WIDTH_GUARD(h, __func__);
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!h->t_have_fwd) PF_FAIL(h, PF_ERR_STATE, "pf_dynamics_input_vjp: no pf_train_forward on this batch");
+    if (!dev_g_eps_h || !dev_g_eps_x) PF_FAIL(h, PF_ERR_ARG, "pf_dynamics_input_vjp: null argument");
+    if (!dev_g_pharm_x && !dev_g_pharm_h) PF_FAIL(h, PF_ERR_ARG, "pf_dynamics_input_vjp: at least one of dev_g_pharm_x / dev_g_pharm_h must be given");
+    if (h->n_tseg < 0) PF_FAIL(h, PF_ERR_ARG, "pf_dynamics_input_vjp: the gradient path supports n_convs <= 4");
+    if (!h->train_wide)
+        PF_FAIL(h, PF_ERR_ARG, "pf_dynamics_input_vjp: gradients w.r.t. the center coordinates and features are computed by the width-generic "
+                               "training leg only (pf_train_set_family(PF_TRAIN_FAMILY_WIDE), fp32, every supported width)");
+    return wide_train_backward(h, dev_g_eps_h, dev_g_eps_x, nullptr, dev_g_pharm_x, dev_g_pharm_h, (hipStream_t)stream);
+}
+
+// ---- guided sampling: restraint energies on the predicted clean centers steer the reverse steps (reconstruction guidance) ----
+// every check of pf_sample_begin_guided's own arguments, before anything is enqueued or the handle changes
+static int guide_validate(pf_handle* h, const int32_t* rptr, const int32_t* kind, const int32_t* center, const float* p, const float* r,
+                          const float* w, float scale, float clip) {
+    const char* who = "pf_sample_begin_guided";
+    if (!rptr) PF_FAIL(h, PF_ERR_ARG, "%s: null restr_ptr", who);
+    if (!(scale >= 0.f) || !std::isfinite(scale)) PF_FAIL(h, PF_ERR_ARG, "%s: guide_scale must be finite and >= 0", who);
+    if (!(clip >= 0.f) || !std::isfinite(clip)) PF_FAIL(h, PF_ERR_ARG, "%s: guide_clip must be finite and >= 0 (0: no clip)", who);
+    if (rptr[0] != 0) PF_FAIL(h, PF_ERR_ARG, "%s: restr_ptr[0] must be 0", who);
+    for (int g = 0; g < h->B; ++g) {
+        const int n = rptr[g + 1] - rptr[g];
+        if (n < 0) PF_FAIL(h, PF_ERR_ARG, "%s: restr_ptr decreases at graph %d", who, g);
+        if (n > 256) PF_FAIL(h, PF_ERR_ARG, "%s: graph %d has %d restraints (at most 256 per graph)", who, g, n);
+    }
+    const int n = rptr[h->B];
+    if (n > 0 && (!kind || !center || !p || !r || !w)) PF_FAIL(h, PF_ERR_ARG, "%s: null restraint array", who);
+    for (int g = 0; g < h->B; ++g) {
+        const int nf_g = h->h_pharm_ptr[g + 1] - h->h_pharm_ptr[g];
+        for (int j = rptr[g]; j < rptr[g + 1]; ++j) {
+            if (kind[j] != 0 && kind[j] != 1) PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d has kind %d (0 attract, 1 repel)", who, j, (int)kind[j]);
+            if (center[j] < -1 || center[j] >= nf_g)
+                PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d names center %d of graph %d, which has %d (-1: every center)", who, j, (int)center[j], g, nf_g);
+            for (int c = 0; c < 3; ++c)
+                if (!std::isfinite(p[(size_t)j * 3 + c])) PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d has a non-finite point", who, j);
+            if (!(r[j] >= 0.f) || !std::isfinite(r[j])) PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d: the radius must be finite and >= 0", who, j);
+            if (!(w[j] >= 0.f) || !std::isfinite(w[j])) PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d: the weight must be finite and >= 0", who, j);
+        }
+    }
+    return PF_OK;
+}
+
+int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
+                           const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, const int32_t* host_restr_ptr,
+                           const int32_t* host_restr_kind, const int32_t* host_restr_center, const float* host_restr_p,
+                           const float* host_restr_r, const float* host_restr_w, float guide_scale, float guide_clip, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!dev_noise0) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null noise");
+    if (!dev_pin_flags || !dev_pin_x || !dev_pin_h) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null pin array");
+    if (!(feat_norm_constant > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: feat_norm_constant must be positive");
+    if (!h->train_wide)
+        PF_FAIL(h, PF_ERR_STATE, "pf_sample_begin_guided: a guided step runs the width-generic training forward and its input gradients: "
+                                 "call pf_train_set_family(h, PF_TRAIN_FAMILY_WIDE) first");
+    if ((rc = guide_validate(h, host_restr_ptr, host_restr_kind, host_restr_center, host_restr_p, host_restr_r, host_restr_w, guide_scale,
+                             guide_clip)) != PF_OK) return rc;
+    if (const int lim = train_limits_ok(h)) return lim;
+    hipStream_t s = (hipStream_t)stream;
+    // the restraints: staged in pinned memory in the device layout, then one copy
+    const size_t B1 = (size_t)h->B + 1, n = (size_t)host_restr_ptr[h->B], n1 = std::max<size_t>(n, 1);
+    const size_t words = B1 + n1 * 7, bytes = words * 4;
+    if (h->restr_ev) PF_HIP(h, hipEventSynchronize(h->restr_ev));      // the last upload has read the staging buffer
+    if (bytes > h->restr_stage_capacity) {
+        if (h->restr_stage) { (void)hipHostFree(h->restr_stage); h->restr_stage = nullptr; h->restr_stage_capacity = 0; }
+        PF_HIP(h, hipHostMalloc(&h->restr_stage, bytes * 2, hipHostMallocDefault));
+        h->restr_stage_capacity = bytes * 2;
+    }
+    if (bytes > h->restr_capacity) {
+        if (h->d_restr) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(h->d_restr)); h->d_restr = nullptr; h->restr_capacity = 0; }
+        PF_HIP(h, hipMalloc(&h->d_restr, bytes * 2));
+        h->restr_capacity = bytes * 2;
+    }
+    const size_t nf1 = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
+    const size_t gwords = nf1 * (12 + nh) + (size_t)h->B * 4;
+    if (gwords * 4 > h->guide_capacity) {
+        if (h->d_guide) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(h->d_guide)); h->d_guide = nullptr; h->guide_capacity = 0; }
+        PF_HIP(h, hipMalloc(&h->d_guide, gwords * 4));
+        h->guide_capacity = gwords * 4;
+    }
+    if (!h->restr_ev) PF_HIP(h, hipEventCreateWithFlags(&h->restr_ev, hipEventDisableTiming));
+    rc = pf_sample_begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, stream);
+    if (rc) return rc;
+    {
+        int32_t* st = (int32_t*)h->restr_stage;
+        std::memcpy(st, host_restr_ptr, B1 * 4);
+        if (n) {
+            std::memcpy(st + B1, host_restr_kind, n * 4);
+            std::memcpy(st + B1 + n1, host_restr_center, n * 4);
+            std::memcpy(st + B1 + 2 * n1, host_restr_p, n * 12);
+            std::memcpy(st + B1 + 5 * n1, host_restr_r, n * 4);
+            std::memcpy(st + B1 + 6 * n1, host_restr_w, n * 4);
+        }
+        PF_HIP(h, hipMemcpyAsync(h->d_restr, st, bytes, hipMemcpyHostToDevice, s));
+        PF_HIP(h, hipEventRecord(h->restr_ev, s));
+    }
+    h->n_restr = (int)n;
+    float* gq = (float*)h->d_guide;
+    h->d_g0 = gq; h->d_gjx = gq + nf1 * 3; h->d_ggrad = gq + nf1 * 6; h->d_gshift = gq + nf1 * 9; h->d_gzero = gq + nf1 * 12;
+    h->d_genergy = h->d_gzero + nf1 * nh; h->d_gD = h->d_genergy + h->B;
+    PF_HIP(h, hipMemsetAsync(h->d_guide, 0, gwords * 4, s));          // (the zero g_eps_h of every step's VJP; nothing writes it)
+    h->guide_scale = guide_scale; h->guide_clip = guide_clip;
+    h->guide_traj_energy = nullptr;
+    h->guided = true; h->guide_have = false;
+    return PF_OK;
+}
+
+// One denoising step of a guided run: the width-generic training forward (dropout 0: it keeps what the VJP reads), k_guide_grad, the
+// inputs-only backward with g_eps_x = g0 and the zero g_eps_h, k_step_update_guided.  The update runs alone: the width-generic
+// training forward builds its own edges on every call (run_dynamics_wide: `if (!h->edges_built)`, and it leaves edges_built false),
+// on a 128 / 16 handle too, so no form of this step builds the next call's edges and edges_built stays false behind it
+int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_coef* pin, const pf_guide_coef* gc, const float* dev_noise,
+                           int32_t ep_coord, int32_t ep_feat, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!coef || !pin || !gc || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_guided: null argument");
+    if (!h->sampling || !h->guided) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_guided outside a guided run (pf_sample_begin_guided)");
+    if (!h->train_wide) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_guided: the training family was switched inside the guided run (pf_train_set_family)");
+    if (!(gc->alpha_t > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_guided: alpha_t must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    const StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
+    if ((rc = train_begin(h, 0.f, 0u, s, __func__)) != PF_OK) return rc;
+    h->wt_common.mask_override = nullptr;       // dropout 0, whatever a test left in pf_debug_set_dropout_masks
+    ++h->step_id;
+    h->edges_built = false; h->rec_valid = false;
+    rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, true, nullptr);
+    h->t_have_fwd = false;                      // (the kept forward is this step's: d_t does not hold its timestep)
+    if (rc) return rc;
+    GuideParams gq{};
+    const size_t B1 = (size_t)h->B + 1, n1 = (size_t)std::max(h->n_restr, 1);
+    const int32_t* base = (const int32_t*)h->d_restr;
+    gq.restr_ptr = base; gq.restr_kind = base + B1; gq.restr_center = base + B1 + n1;
+    gq.restr_p = (const float*)(base + B1 + 2 * n1); gq.restr_r = (const float*)(base + B1 + 5 * n1); gq.restr_w = (const float*)(base + B1 + 6 * n1);
+    gq.com_init = h->d_com_init; gq.alpha_t = gc->alpha_t; gq.sigma_t = gc->sigma_t; gq.ep_coord = ep_coord;
+    gq.g0 = h->d_g0; gq.energy = h->d_genergy; gq.traj_energy = h->guide_traj_energy; gq.D = h->d_gD;
+    pfk_guide_grad(&sp, &gq, s);
+    if ((rc = wide_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s)) != PF_OK) return rc;
+    PinParams q{};
+    q.flags = h->d_pin_flags; q.pin_x = h->d_pin_x; q.pin_h = h->d_pin_h; q.com_init = h->d_com_init;
+    q.alpha_s = pin->alpha_s; q.sigma_s = pin->sigma_s; q.feat_norm = h->pin_feat_norm;
+    GuideShiftParams gs{};
+    gs.g0 = h->d_g0; gs.jx = h->d_gjx; gs.D = h->d_gD; gs.alpha_t = gc->alpha_t; gs.sigma_t = gc->sigma_t;
+    gs.scale = h->guide_scale; gs.clip = h->guide_clip; gs.grad = h->d_ggrad; gs.shift = h->d_gshift;
+    { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update_guided(&sp, &q, &gs, s); }
+    h->edges_built = false; h->rec_valid = false;          // the centers moved: the next dynamics call builds
+    h->tail_done = false; h->last_tail = 0;
+    h->snap_cur = -1; h->cen_valid = false; h->spec_valid = false;
+    h->guide_have = true;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
+}
+
+int pf_sample_guided(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef,
+                     const pf_guide_coef* host_guide_coef, const float* dev_noise, const float* dev_init_pharm_com,
+                     const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h, int32_t ep_coord, int32_t ep_feat,
+                     float feat_norm_constant, const int32_t* host_restr_ptr, const int32_t* host_restr_kind, const int32_t* host_restr_center,
+                     const float* host_restr_p, const float* host_restr_r, const float* host_restr_w, float guide_scale, float guide_clip,
+                     float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, float* dev_energy, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (n_steps < 0 || (n_steps && (!host_coef || !host_pin_coef || !host_guide_coef)) || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_sample_guided: bad argument");
+    const size_t row = (size_t)h->Nf * (3 + h->cfg.pharm_nf);
+    const size_t fx = (size_t)h->Nf * 3, fh = (size_t)h->Nf * h->cfg.pharm_nf;
+    rc = pf_sample_begin_guided(h, dev_init_pharm_com, dev_noise, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, host_restr_ptr,
+                                host_restr_kind, host_restr_center, host_restr_p, host_restr_r, host_restr_w, guide_scale, guide_clip, stream);
+    if (rc) return rc;
+    if (dev_traj_x || dev_traj_h) {
+        rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x, dev_traj_h, stream);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < n_steps; ++i) {
+        h->guide_traj_energy = dev_energy ? dev_energy + (size_t)i * h->B : nullptr;
+        rc = pf_denoise_step_guided(h, host_coef + i, host_pin_coef + i, host_guide_coef + i, dev_noise + (size_t)(i + 1) * row, ep_coord, ep_feat, stream);
+        h->guide_traj_energy = nullptr;
+        if (rc) return rc;
+        if (dev_traj_x || dev_traj_h) {
+            rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x ? dev_traj_x + (size_t)(i + 1) * fx : nullptr,
+                                 dev_traj_h ? dev_traj_h + (size_t)(i + 1) * fh : nullptr, stream);
+            if (rc) return rc;
+        }
+    }
+    pfk_pin_restore(h->d_pin_flags, h->d_pin_x, h->d_pin_h, h->Nf, h->cfg.pharm_nf, dev_traj_x ? dev_traj_x + (size_t)n_steps * fx : nullptr,
+                    dev_traj_h ? dev_traj_h + (size_t)n_steps * fh : nullptr, (hipStream_t)stream);
+    return pf_sample_end(h, feat_norm_constant, dev_x0, dev_h0, stream);
+}
+
+int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* dev_shift, float* dev_energy, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!h->guide_have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_guidance: no guided step on this batch");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nb = (size_t)h->Nf * 3 * 4;
+    if (dev_g0 && nb) PF_HIP(h, hipMemcpyAsync(dev_g0, h->d_g0, nb, hipMemcpyDeviceToDevice, s));
+    if (dev_grad && nb) PF_HIP(h, hipMemcpyAsync(dev_grad, h->d_ggrad, nb, hipMemcpyDeviceToDevice, s));
+    if (dev_shift && nb) PF_HIP(h, hipMemcpyAsync(dev_shift, h->d_gshift, nb, hipMemcpyDeviceToDevice, s));
+    if (dev_energy && h->B) PF_HIP(h, hipMemcpyAsync(dev_energy, h->d_genergy, (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
+    return PF_OK;
 }
 
 int pf_train_set_precision(pf_handle* h, int32_t precision) {

@@ -1870,14 +1870,41 @@ __device__ __forceinline__ float pf_pin_value(const float given, const float nz,
     const float a = alpha_s * given, n = sigma_s * nz;
     return a + n;
 }
-__device__ __forceinline__ void pinned_update_body(const StepParams& p, const PinParams& q, const int g) {
+// The guided step's move (reconstruction guidance, pf_denoise_step_guided) for one center: the gradient of the restraint energy
+// w.r.t. x_t from g0 = dE/dy and the dynamics' VJP J(g0), the shift of the posterior mean, and its clip.  One rounding per
+// operation, like pf_feat_update.  gr / sh: what the step applies (also stored for pf_debug_last_guidance)
+__device__ __forceinline__ void pf_guide_shift(const float* g0, const float* jx, const float alpha_t, const float sigma_t, const int ep_coord,
+                                               const float sigma_post, const float scale, const float clip, float* gr, float* sh) {
+#pragma clang fp contract(off)
+    const float ratio = sigma_t / alpha_t;
+    const float s2 = sigma_post * sigma_post;
+    const float k = scale * s2;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (ep_coord) gr[c] = jx[c];
+        else { const float a = g0[c] / alpha_t, b = ratio * jx[c]; gr[c] = a - b; }
+        sh[c] = k * gr[c];
+    }
+    const float n = sqrtf((sh[0] * sh[0] + sh[1] * sh[1]) + sh[2] * sh[2]);
+    if (clip > 0.f && n > clip) {
+        const float f = clip / n;
+        sh[0] *= f; sh[1] *= f; sh[2] *= f;
+    }
+}
+// GUIDED: pinned_update_body with one more input -- the guided step's shift is taken off a free center's p(z_s | z_t) value in front
+// of the selects, and D[g] is the one k_guide_grad left (the same reduction of the same rows, which nobody has moved in between).
+// Without it: the pinned kernels' code as it was
+template <bool GUIDED>
+__device__ __forceinline__ void pinned_update_body(const StepParams& p, const PinParams& q, const GuideShiftParams* gs, const int g) {
     __shared__ float com[3];
     __shared__ float red[4][3];
     __shared__ float dfr[3];                            // D[g]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
     const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
-    if (wave == 0) {
+    if constexpr (GUIDED) {
+        if (tid < 3) dfr[tid] = gs->D[3 * g + tid];
+    } else if (wave == 0) {
         float ax = 0.f, ay = 0.f, az = 0.f;
         for (int i = p0 + lane; i < p1; i += 64) { const float4 x = p.xn[i]; ax += x.x; ay += x.y; az += x.z; }
 #pragma unroll
@@ -1900,6 +1927,15 @@ __device__ __forceinline__ void pinned_update_body(const StepParams& p, const Pi
             const float e = p.eps_x[(size_t)f * 3 + c];
             m[c] = (flag & 1) ? pf_pin_value(q.pin_x[(size_t)f * 3 + c] - dfr[c], nz[c], q.alpha_s, q.sigma_s)
                               : pf_feat_update(xi[c], e, nz[c], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_coord);
+        }
+        if constexpr (GUIDED) {
+            float gr[3], sh[3];
+            pf_guide_shift(gs->g0 + (size_t)f * 3, gs->jx + (size_t)f * 3, gs->alpha_t, gs->sigma_t, p.ep_coord, p.sigma, gs->scale, gs->clip, gr, sh);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                gs->grad[(size_t)f * 3 + c] = gr[c]; gs->shift[(size_t)f * 3 + c] = sh[c];
+                if (!(flag & 1)) m[c] -= sh[c];         // (a position-pinned center ignores its shift)
+            }
         }
         p.xn[p.Np_tot + f] = make_float4(m[0], m[1], m[2], 0.f);
         sx += m[0]; sy += m[1]; sz += m[2];
@@ -1931,11 +1967,112 @@ __device__ __forceinline__ void pinned_update_body(const StepParams& p, const Pi
         p.xn[i] = x;
     }
 }
-__global__ __launch_bounds__(256) void k_step_update_pinned(const StepParams p, const PinParams q) { pinned_update_body(p, q, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_step_update_pinned(const StepParams p, const PinParams q) { pinned_update_body<false>(p, q, nullptr, blockIdx.x); }
 __global__ __launch_bounds__(256) void k_step_build_pinned(const StepParams sp, const PinParams q, const BuildParams bp) {
-    pinned_update_body(sp, q, blockIdx.x);
+    pinned_update_body<false>(sp, q, nullptr, blockIdx.x);
     __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
     build_body(bp, blockIdx.x);
+}
+// the guided step's update, alone: its dynamics call is the width-generic training forward, which builds its own edges
+__global__ __launch_bounds__(256) void k_step_update_guided(const StepParams p, const PinParams q, const GuideShiftParams gs) {
+    pinned_update_body<true>(p, q, &gs, blockIdx.x);
+}
+// ---------------------------------------------------------------------------------------------
+// Guided sampling (pf_denoise_step_guided): restraint energies on the predicted clean centers, in the caller's frame.
+//   y_f = x0_hat[f] + D[g],  x0_hat = (x_t - sigma_t eps_x) / alpha_t (noise parameterisation) or eps_x (endpoint)
+//   attract: E = w max(0, rho - r)^2   repel: E = w max(0, r - rho)^2   rho = |y_f - p|;  rho == 0: no gradient
+// One workgroup per graph.  D[g] as in pinned_update_body (wave 0, k_segment_mean's order).  One thread per center walks the
+// graph's restraints in ascending order and stores g0[f] = sum_j dE_j/dy_f; thread 0 then sums E over (f ascending, j ascending).
+// A launch starts with cold caches: the thread's center rows and wave 0's first protein row are requested before the first wait
+// (4.12.1 of DESIGN.md), so the reduction in front costs no round trip of its own.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void pf_guide_y(const float x[3], const float e[3], const float* D, const float alpha_t, const float sigma_t,
+                                           const int ep_coord, float y[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float x0;
+        if (ep_coord) x0 = e[c];
+        else { const float se = sigma_t * e[c], d = x[c] - se; x0 = d / alpha_t; }
+        y[c] = x0 + D[c];
+    }
+}
+// E_j(y) and dE_j/dy of one restraint (kind 0 attract, 1 repel)
+__device__ __forceinline__ float pf_restraint(const int kind, const float* pt, const float r, const float w, const float y[3], float g[3]) {
+#pragma clang fp contract(off)
+    const float dx = y[0] - pt[0], dy = y[1] - pt[1], dz = y[2] - pt[2];
+    const float rho = sqrtf((dx * dx + dy * dy) + dz * dz);
+    const float d = kind ? r - rho : rho - r;
+    const float m = fmaxf(0.f, d);
+    g[0] = 0.f; g[1] = 0.f; g[2] = 0.f;
+    if (rho > 0.f) {
+        float c = ((2.0f * w) * m) / rho;
+        if (kind) c = -c;
+        g[0] = c * dx; g[1] = c * dy; g[2] = c * dz;
+    }
+    return w * (m * m);
+}
+__global__ __launch_bounds__(256) void k_guide_grad(const StepParams p, const GuideParams q) {
+    __shared__ float dfr[3];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
+    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
+    const int r0 = q.restr_ptr[g], r1 = q.restr_ptr[g + 1];
+    const int fa = f0 + tid;
+    const bool own = fa < f1, own_p = wave == 0 && p0 + lane < p1;
+    float4 xa = make_float4(0.f, 0.f, 0.f, 0.f), pa = make_float4(0.f, 0.f, 0.f, 0.f);
+    float ea[3] = {0.f, 0.f, 0.f};
+    if (own) { xa = p.xn[p.Np_tot + fa]; for (int c = 0; c < 3; ++c) ea[c] = p.eps_x[(size_t)fa * 3 + c]; }
+    if (own_p) pa = p.xn[p0 + lane];
+    asm volatile("" :: "v"((xa.x + xa.y) + (xa.z + ea[0]) + (ea[1] + ea[2])), "v"(pa.x) : "memory");      // every row is requested before the first wait
+    if (wave == 0) {
+        float ax = 0.f, ay = 0.f, az = 0.f;
+        if (own_p) { ax += pa.x; ay += pa.y; az += pa.z; }
+        for (int i = p0 + lane + 64; i < p1; i += 64) { const float4 x = p.xn[i]; ax += x.x; ay += x.y; az += x.z; }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o); }
+        if (lane == 0) {
+            const float n = (float)max(p1 - p0, 1);
+            dfr[0] = q.com_init[3 * g] - ax / n; dfr[1] = q.com_init[3 * g + 1] - ay / n; dfr[2] = q.com_init[3 * g + 2] - az / n;
+            q.D[3 * g] = dfr[0]; q.D[3 * g + 1] = dfr[1]; q.D[3 * g + 2] = dfr[2];
+        }
+    }
+    __syncthreads();
+    for (int f = fa; f < f1; f += 256) {
+        float x[3] = {xa.x, xa.y, xa.z}, e[3] = {ea[0], ea[1], ea[2]};
+        if (f != fa) {
+            const float4 xv = p.xn[p.Np_tot + f];
+            x[0] = xv.x; x[1] = xv.y; x[2] = xv.z;
+            for (int c = 0; c < 3; ++c) e[c] = p.eps_x[(size_t)f * 3 + c];
+        }
+        float y[3], acc[3] = {0.f, 0.f, 0.f};
+        pf_guide_y(x, e, dfr, q.alpha_t, q.sigma_t, q.ep_coord, y);
+        for (int j = r0; j < r1; ++j) {
+            const int ci = q.restr_center[j];
+            if (ci >= 0 && ci != f - f0) continue;
+            float gj[3];
+            (void)pf_restraint(q.restr_kind[j], q.restr_p + (size_t)j * 3, q.restr_r[j], q.restr_w[j], y, gj);
+            acc[0] += gj[0]; acc[1] += gj[1]; acc[2] += gj[2];
+        }
+        for (int c = 0; c < 3; ++c) q.g0[(size_t)f * 3 + c] = acc[c];
+    }
+    if (tid == 0) {                                     // the graph's energy: one thread, (f ascending, j ascending)
+        float E = 0.f;
+        for (int f = f0; f < f1 && r1 > r0; ++f) {
+            const float4 xv = p.xn[p.Np_tot + f];
+            const float x[3] = {xv.x, xv.y, xv.z};
+            const float e[3] = {p.eps_x[(size_t)f * 3], p.eps_x[(size_t)f * 3 + 1], p.eps_x[(size_t)f * 3 + 2]};
+            float y[3], gj[3];
+            pf_guide_y(x, e, dfr, q.alpha_t, q.sigma_t, q.ep_coord, y);
+            for (int j = r0; j < r1; ++j) {
+                const int ci = q.restr_center[j];
+                if (ci >= 0 && ci != f - f0) continue;
+                E += pf_restraint(q.restr_kind[j], q.restr_p + (size_t)j * 3, q.restr_r[j], q.restr_w[j], y, gj);
+            }
+        }
+        q.energy[g] = E;
+        if (q.traj_energy) q.traj_energy[g] = E;
+    }
 }
 // ---------------------------------------------------------------------------------------------
 // Resampling jump of a pinned run (pf_renoise_step): the whole state of graph g goes from level b back up to level a > b,
@@ -2205,6 +2342,14 @@ void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const Build
 void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s) {
     if (p->B == 0) return;
     hipLaunchKernelGGL(k_step_update_pinned, dim3(p->B), dim3(256), 0, s, *p, *q);
+}
+void pfk_step_update_guided(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, hipStream_t s) {
+    if (p->B == 0) return;
+    hipLaunchKernelGGL(k_step_update_guided, dim3(p->B), dim3(256), 0, s, *p, *q, *gs);
+}
+void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s) {
+    if (p->B == 0) return;
+    hipLaunchKernelGGL(k_guide_grad, dim3(p->B), dim3(256), 0, s, *p, *q);
 }
 void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s) {
     if (sp->B == 0) return;

@@ -149,7 +149,9 @@ __device__ __forceinline__ void wt_edge_geometry(const WtChainParams& p, int s, 
     o[2] = (float)((double)g_u[2] / dd + m * dz);
 }
 
-template <bool EDGE>
+// WG: the weight-gradient products (the full pass).  Without it (the inputs-only pass: pf_dynamics_input_vjp, a guided step) the
+// kernel forms no pointer into the gradient copies and skips every dW product; dL/d(input) takes the same operations either way
+template <bool EDGE, bool WG>
 __global__ __launch_bounds__(256) void k_wt_chain(const WtChainParams p) {
     extern __shared__ float lds[];
     const int S = p.c.S, V = p.c.V, tid = threadIdx.x;
@@ -170,7 +172,8 @@ __global__ __launch_bounds__(256) void k_wt_chain(const WtChainParams p) {
     int* src = rid + R;
     int* dst = src + R;
     float* sc = reinterpret_cast<float*>(dst + R);
-    float* gp = p.c.gpart + (size_t)blockIdx.x * p.c.gstride;
+    float* gp = nullptr;
+    if constexpr (WG) gp = p.c.gpart + (size_t)blockIdx.x * p.c.gstride;
     const float* W = p.c.W;
     for (int ti = blockIdx.x; ti < p.n_tiles; ti += gridDim.x) {
         int nvalid, ty, e0 = 0, n0 = 0, ids = 0;
@@ -283,13 +286,15 @@ __global__ __launch_bounds__(256) void k_wt_chain(const WtChainParams p) {
                 d[0] *= g; d[1] *= g; d[2] *= g;
             }
             __syncthreads();
-            wt_outer(dpre, gw, vo, a, lz, so, gp + G.o_Wg);
-            if (tid < vo) {
-                float s = 0.f;
-                for (int r = 0; r < R; ++r) s += dpre[r * gw + tid];
-                gp[G.o_bg + tid] += s;
+            if constexpr (WG) {
+                wt_outer(dpre, gw, vo, a, lz, so, gp + G.o_Wg);
+                if (tid < vo) {
+                    float s = 0.f;
+                    for (int r = 0; r < R; ++r) s += dpre[r * gw + tid];
+                    gp[G.o_bg + tid] += s;
+                }
+                __syncthreads();
             }
-            __syncthreads();
             // da = dA + Wg^T dpre, dz = da SiLU'(z) (into z)
             for (int i = tid; i < R * so; i += 256) {
                 const int r = i / so, f = i - r * so;
@@ -299,13 +304,15 @@ __global__ __launch_bounds__(256) void k_wt_chain(const WtChainParams p) {
                 z[r * lz + f] = acc * s * (1.0f + zz * (1.0f - s));
             }
             __syncthreads();
-            wt_outer(z, lz, so, in, ld, K, gp + G.o_Wm);
-            for (int f = tid; f < so; f += 256) {
-                float s = 0.f;
-                for (int r = 0; r < R; ++r) s += z[r * lz + f];
-                gp[G.o_bm + f] += s;
+            if constexpr (WG) {
+                wt_outer(z, lz, so, in, ld, K, gp + G.o_Wm);
+                for (int f = tid; f < so; f += 256) {
+                    float s = 0.f;
+                    for (int r = 0; r < R; ++r) s += z[r * lz + f];
+                    gp[G.o_bm + f] += s;
+                }
+                __syncthreads();
             }
-            __syncthreads();
             wt_lin_t(z, lz, so, W + G.o_Wm, K, in, ld);          // d[s, sh] over the input
             __syncthreads();
             // dVh = Wu dVu + dsh Vh / sh (nothing through a clamped norm)
@@ -320,27 +327,29 @@ __global__ __launch_bounds__(256) void k_wt_chain(const WtChainParams p) {
                 dvh[r * vs + q] = acc;
             }
             __syncthreads();
-            for (int i = tid; i < H * vo; i += 256) {
-                const int k = i / vo, u = i - k * vo;
-                float s = 0.f;
-                for (int r = 0; r < R; ++r) {
-                    const float* x = vh + r * vs + 3 * k;
-                    const float* d = dv + r * vs + 3 * u;
-                    s += x[0] * d[0] + x[1] * d[1] + x[2] * d[2];
+            if constexpr (WG) {
+                for (int i = tid; i < H * vo; i += 256) {
+                    const int k = i / vo, u = i - k * vo;
+                    float s = 0.f;
+                    for (int r = 0; r < R; ++r) {
+                        const float* x = vh + r * vs + 3 * k;
+                        const float* d = dv + r * vs + 3 * u;
+                        s += x[0] * d[0] + x[1] * d[1] + x[2] * d[2];
+                    }
+                    gp[G.o_Wu + i] += s;
                 }
-                gp[G.o_Wu + i] += s;
-            }
-            for (int i = tid; i < vi * H; i += 256) {
-                const int k = i / H, hh = i - k * H;
-                float s = 0.f;
-                for (int r = 0; r < R; ++r) {
-                    const float* x = vin + r * vs + 3 * k;
-                    const float* d = dvh + r * vs + 3 * hh;
-                    s += x[0] * d[0] + x[1] * d[1] + x[2] * d[2];
+                for (int i = tid; i < vi * H; i += 256) {
+                    const int k = i / H, hh = i - k * H;
+                    float s = 0.f;
+                    for (int r = 0; r < R; ++r) {
+                        const float* x = vin + r * vs + 3 * k;
+                        const float* d = dvh + r * vs + 3 * hh;
+                        s += x[0] * d[0] + x[1] * d[1] + x[2] * d[2];
+                    }
+                    gp[G.o_Wh + i] += s;
                 }
-                gp[G.o_Wh + i] += s;
+                __syncthreads();
             }
-            __syncthreads();
             for (int i = tid; i < R * vi * 3; i += 256) {       // dV = Wh dVh (over dVu)
                 const int r = i / (vi * 3), q = i - r * vi * 3, k = q / 3, c = q - k * 3;
                 const float* d = dvh + r * vs + c;
@@ -379,11 +388,13 @@ __global__ __launch_bounds__(256) void k_wt_chain(const WtChainParams p) {
 }
 
 // GVPLayerNorm (gvp.py:159-166, wide_layernorm's arithmetic) backward for the rows of a node tile list, eight lanes per row
+template <bool WG>
 __global__ __launch_bounds__(256) void k_wt_norm(const WtNormParams p) {
     __shared__ float s_mean[PFW_ROWS], s_rstd[PFW_ROWS];
     __shared__ int s_node[PFW_ROWS];
     const int S = p.c.S, V = p.c.V, V3 = 3 * V, tid = threadIdx.x;
-    float* gp = p.c.gpart + (size_t)blockIdx.x * p.c.gstride;
+    float* gp = nullptr;
+    if constexpr (WG) gp = p.c.gpart + (size_t)blockIdx.x * p.c.gstride;
     const float* W = p.c.W;
     for (int ti = blockIdx.x; ti < p.n_tiles; ti += gridDim.x) {
         const NodeTile t = p.tiles[ti];
@@ -454,28 +465,30 @@ __global__ __launch_bounds__(256) void k_wt_norm(const WtNormParams p) {
                     p.out2_v[(size_t)n * V3 + 3 * u + c] = dx * m;
                 }
             }
-        __syncthreads();
-        if (sub == 0) { s_mean[r] = mean; s_rstd[r] = rstd; s_node[r] = n; }
-        __syncthreads();
-        // the norm's weight and bias: sums over the tile's rows in row order
-        for (int f = tid; f < S; f += 256) {
-            float sw = 0.f, sb = 0.f;
-            for (int rr = 0; rr < tn; ++rr) {
-                const size_t o = (size_t)s_node[rr] * S + f;
-                const float dy = p.dyA_s[o] + (p.dyB_s ? p.dyB_s[o] : 0.f);
-                sw = fmaf(dy, (p.x_s[o] - s_mean[rr]) * s_rstd[rr], sw);
-                sb += dy;
+        if constexpr (WG) {
+            __syncthreads();
+            if (sub == 0) { s_mean[r] = mean; s_rstd[r] = rstd; s_node[r] = n; }
+            __syncthreads();
+            // the norm's weight and bias: sums over the tile's rows in row order
+            for (int f = tid; f < S; f += 256) {
+                float sw = 0.f, sb = 0.f;
+                for (int rr = 0; rr < tn; ++rr) {
+                    const size_t o = (size_t)s_node[rr] * S + f;
+                    const float dy = p.dyA_s[o] + (p.dyB_s ? p.dyB_s[o] : 0.f);
+                    sw = fmaf(dy, (p.x_s[o] - s_mean[rr]) * s_rstd[rr], sw);
+                    sb += dy;
+                }
+                gp[p.o_lw[nt] + f] += sw;
+                gp[p.o_lb[nt] + f] += sb;
             }
-            gp[p.o_lw[nt] + f] += sw;
-            gp[p.o_lb[nt] + f] += sb;
+            __syncthreads();
         }
-        __syncthreads();
     }
 }
 
+template <bool WG>
 __global__ __launch_bounds__(256) void k_wt_head_out(const WtHeadOutParams p) {
     const int tid = threadIdx.x, nf = p.pharm_nf;
-    float* gp = p.c.gpart + (size_t)blockIdx.x * p.c.gstride;
     const float* W = p.c.W;
     for (int i = blockIdx.x; i < p.Nf; i += gridDim.x) {
         const size_t n = (size_t)p.Np + i;
@@ -485,31 +498,37 @@ __global__ __launch_bounds__(256) void k_wt_head_out(const WtHeadOutParams p) {
             p.up_s[n * p.up_ls + tid] = acc;
         } else if (tid < 67) p.up_v[n * p.up_lv + (tid - 64)] = p.g_eps_x[(size_t)i * 3 + (tid - 64)];
     }
-    for (int idx = tid; idx < nf * 64; idx += 256) {
-        const int k = idx >> 6, f = idx & 63;
-        float acc = 0.f;
-        for (int i = blockIdx.x; i < p.Nf; i += gridDim.x) acc = fmaf(p.g_eps_h[(size_t)i * nf + k], p.h64[(size_t)i * 64 + f], acc);
-        gp[p.o_Wout + idx] += acc;
-    }
-    if (tid < nf) {
-        float acc = 0.f;
-        for (int i = blockIdx.x; i < p.Nf; i += gridDim.x) acc += p.g_eps_h[(size_t)i * nf + tid];
-        gp[p.o_bout + tid] += acc;
+    if constexpr (WG) {
+        float* gp = p.c.gpart + (size_t)blockIdx.x * p.c.gstride;
+        for (int idx = tid; idx < nf * 64; idx += 256) {
+            const int k = idx >> 6, f = idx & 63;
+            float acc = 0.f;
+            for (int i = blockIdx.x; i < p.Nf; i += gridDim.x) acc = fmaf(p.g_eps_h[(size_t)i * nf + k], p.h64[(size_t)i * 64 + f], acc);
+            gp[p.o_Wout + idx] += acc;
+        }
+        if (tid < nf) {
+            float acc = 0.f;
+            for (int i = blockIdx.x; i < p.Nf; i += gridDim.x) acc += p.g_eps_h[(size_t)i * nf + tid];
+            gp[p.o_bout + tid] += acc;
+        }
     }
 }
 
 // Linear(nf + 1 -> S) + SiLU + LayerNorm of every node (dynamics_gvp.py:107-117, 143-151): tiles of 32 nodes of one type,
 // eight lanes per row; LDS: z (later the normalised rows) and dz [32][S + 1] each, the inputs [32][17]
+// (WG false: only dL/d(the centers' feature rows) is wanted -- the protein tiles have nothing to do)
+template <bool WG>
 __global__ __launch_bounds__(256) void k_wt_encode(const WtEncParams p) {
     extern __shared__ float lds[];
     const int S = p.c.S, lz = S + 1, tid = threadIdx.x;
     float* zb = lds;
     float* dzb = zb + PFW_ROWS * lz;
     float* xin = dzb + PFW_ROWS * lz;
-    float* gp = p.c.gpart + (size_t)blockIdx.x * p.c.gstride;
+    float* gp = nullptr;
+    if constexpr (WG) gp = p.c.gpart + (size_t)blockIdx.x * p.c.gstride;
     const float* W = p.c.W;
     const int tp = (p.Np + PFW_ROWS - 1) / PFW_ROWS, tf = (p.Nf + PFW_ROWS - 1) / PFW_ROWS;
-    for (int ti = blockIdx.x; ti < tp + tf; ti += gridDim.x) {
+    for (int ti = (WG ? 0 : tp) + blockIdx.x; ti < tp + tf; ti += gridDim.x) {
         const int nt = ti >= tp ? 1 : 0;
         const int n0 = nt ? p.Np + (ti - tp) * PFW_ROWS : ti * PFW_ROWS;
         const int tn = min(PFW_ROWS, (nt ? p.Np + p.Nf : p.Np) - n0);
@@ -559,21 +578,23 @@ __global__ __launch_bounds__(256) void k_wt_encode(const WtEncParams p) {
             zb[r * lz + f] = live ? xh : 0.f;
         }
         __syncthreads();
-        for (int idx = tid; idx < S * K; idx += 256) {
-            const int f = idx / K, k = idx - f * K;
-            float s = 0.f;
-            for (int rr = 0; rr < tn; ++rr) s = fmaf(dzb[rr * lz + f], xin[rr * 17 + k], s);
-            gp[p.o_w[nt] + idx] += s;
-        }
-        for (int f = tid; f < S; f += 256) {
-            float sb = 0.f, sw = 0.f, sl = 0.f;
-            for (int rr = 0; rr < tn; ++rr) {
-                const float d = p.G_h[(size_t)(n0 + rr) * S + f];
-                sb += dzb[rr * lz + f]; sw = fmaf(d, zb[rr * lz + f], sw); sl += d;
+        if constexpr (WG) {
+            for (int idx = tid; idx < S * K; idx += 256) {
+                const int f = idx / K, k = idx - f * K;
+                float s = 0.f;
+                for (int rr = 0; rr < tn; ++rr) s = fmaf(dzb[rr * lz + f], xin[rr * 17 + k], s);
+                gp[p.o_w[nt] + idx] += s;
             }
-            gp[p.o_b[nt] + f] += sb;
-            gp[p.o_lw[nt] + f] += sw;
-            gp[p.o_lb[nt] + f] += sl;
+            for (int f = tid; f < S; f += 256) {
+                float sb = 0.f, sw = 0.f, sl = 0.f;
+                for (int rr = 0; rr < tn; ++rr) {
+                    const float d = p.G_h[(size_t)(n0 + rr) * S + f];
+                    sb += dzb[rr * lz + f]; sw = fmaf(d, zb[rr * lz + f], sw); sl += d;
+                }
+                gp[p.o_b[nt] + f] += sb;
+                gp[p.o_lw[nt] + f] += sw;
+                gp[p.o_lb[nt] + f] += sl;
+            }
         }
         if (nt && p.g_pharm_h)                  // dL/dh_t = dz W over the feature columns
             for (int idx = tid; idx < tn * nf; idx += 256) {
@@ -626,7 +647,8 @@ __global__ __launch_bounds__(256) void k_wt_reduce(const float* gpart, const int
 extern "C" {
 size_t pfk_wt_chain_lds_bytes(int S, int V, int edge) { return wt_chain_lds_floats(S, V, edge != 0) * sizeof(float); }
 
-void pfk_wt_chain(const WtChainParams* p, int edge, hipStream_t s) {
+// wgrad: 1 the full pass, 0 the inputs-only pass (no weight-gradient products: c.gpart is not read)
+void pfk_wt_chain(const WtChainParams* p, int edge, int wgrad, hipStream_t s) {
     if (p->n_tiles == 0) return;
     const size_t bytes = pfk_wt_chain_lds_bytes(p->c.S, p->c.V, edge);
     const int grid = std::min(PFWT_NB, p->n_tiles);
@@ -634,22 +656,28 @@ void pfk_wt_chain(const WtChainParams* p, int edge, hipStream_t s) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), bytes, s, *p);
     };
-    if (edge) go(k_wt_chain<true>); else go(k_wt_chain<false>);
+    if (wgrad) { if (edge) go(k_wt_chain<true, true>); else go(k_wt_chain<false, true>); }
+    else { if (edge) go(k_wt_chain<true, false>); else go(k_wt_chain<false, false>); }
 }
-void pfk_wt_norm(const WtNormParams* p, hipStream_t s) {
+void pfk_wt_norm(const WtNormParams* p, int wgrad, hipStream_t s) {
     if (p->n_tiles == 0) return;
-    hipLaunchKernelGGL(k_wt_norm, dim3(std::min(PFWT_NB, p->n_tiles)), dim3(256), 0, s, *p);
+    if (wgrad) hipLaunchKernelGGL(k_wt_norm<true>, dim3(std::min(PFWT_NB, p->n_tiles)), dim3(256), 0, s, *p);
+    else hipLaunchKernelGGL(k_wt_norm<false>, dim3(std::min(PFWT_NB, p->n_tiles)), dim3(256), 0, s, *p);
 }
-void pfk_wt_head_out(const WtHeadOutParams* p, hipStream_t s) {
+void pfk_wt_head_out(const WtHeadOutParams* p, int wgrad, hipStream_t s) {
     if (p->Nf == 0) return;
-    hipLaunchKernelGGL(k_wt_head_out, dim3(std::min(PFWT_NB, p->Nf)), dim3(256), 0, s, *p);
+    if (wgrad) hipLaunchKernelGGL(k_wt_head_out<true>, dim3(std::min(PFWT_NB, p->Nf)), dim3(256), 0, s, *p);
+    else hipLaunchKernelGGL(k_wt_head_out<false>, dim3(std::min(PFWT_NB, p->Nf)), dim3(256), 0, s, *p);
 }
-void pfk_wt_encode(const WtEncParams* p, hipStream_t s) {
-    const int tiles = (p->Np + PFW_ROWS - 1) / PFW_ROWS + (p->Nf + PFW_ROWS - 1) / PFW_ROWS;
+void pfk_wt_encode(const WtEncParams* p, int wgrad, hipStream_t s) {
+    const int tiles = (wgrad ? (p->Np + PFW_ROWS - 1) / PFW_ROWS : 0) + (p->Nf + PFW_ROWS - 1) / PFW_ROWS;
     if (tiles == 0) return;
     const size_t bytes = ((size_t)2 * PFW_ROWS * (p->c.S + 1) + PFW_ROWS * 17) * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)k_wt_encode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    hipLaunchKernelGGL(k_wt_encode, dim3(std::min(PFWT_NB, tiles)), dim3(256), bytes, s, *p);
+    auto go = [&](auto kern) {
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        hipLaunchKernelGGL(kern, dim3(std::min(PFWT_NB, tiles)), dim3(256), bytes, s, *p);
+    };
+    if (wgrad) go(k_wt_encode<true>); else go(k_wt_encode<false>);
 }
 void pfk_wt_center_sum(const WtCenterSumParams* p, hipStream_t s) {
     if (p->Nf == 0) return;

@@ -218,6 +218,18 @@ class PfEngine:
                                                        _stream_ptr()), "pf_train_backward_inputs")
         return grad, g_x_t, g_h_t
 
+    def input_vjp(self, g_eps_h, g_eps_x, want=(True, True)):
+        """The gradients of sum(eps_h * g_eps_h) + sum(eps_x * g_eps_x) w.r.t. the inputs of the last train_forward ALONE
+        (pf_dynamics_input_vjp): (g_x_t [Nf, 3], g_h_t [Nf, pharm_nf]), None where ``want`` says no.  No parameter gradient is
+        formed; the bits are those of train_backward(..., input_grads=...).  Wide training family only."""
+        gh, gx = _f32(g_eps_h, self.device), _f32(g_eps_x, self.device)
+        g_x_t = torch.empty(self.Nf, 3, device=self.device) if want[0] else None
+        g_h_t = torch.empty(self.Nf, self.pharm_nf, device=self.device) if want[1] else None
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_dynamics_input_vjp(self._h, _dptr(gh), _dptr(gx), _dptr(g_x_t), _dptr(g_h_t), _stream_ptr()),
+                     "pf_dynamics_input_vjp")
+        return g_x_t, g_h_t
+
     def train_loss_forward(self, pharm_x0, pharm_h0, t_int, eps_x, eps_h, alpha_tab, sigma_tab, n_timesteps, feat_norm,
                            remove_com=True, weighted_loss=False, dropout=0.0, seed=0, ep_coord=False, ep_feat=False):
         """PharmacophoreDiff.forward (pharmacodiff.py:162-243) around the bound batch as one call: COM removal, noising, the
@@ -394,6 +406,43 @@ class PfEngine:
                 raise ValueError(f"op {i} of the plan is {op!r}: expected ('denoise', s) or ('renoise', b, a)")
         return coef_arr, pin_arr, op_arr, re_arr
 
+    @staticmethod
+    def guide_coef_array(guide_coef: Dict[str, torch.Tensor], order):
+        """guide_coef: per-s tensors (schedule.guide_coefficients); order: iterable of s (the same as coef_array's)."""
+        order = list(order)
+        arr = (L.PfGuideCoef * max(len(order), 1))()
+        for i, s in enumerate(order):
+            arr[i] = L.PfGuideCoef(float(guide_coef["alpha_t"][s]), float(guide_coef["sigma_t"][s]))
+        return arr
+
+    def _restraints(self, restraints):
+        """restraints: one list (or None) per graph of (kind, center, point, radius, weight) -- kind 'attract' / 'repel' (or 0 / 1),
+        center a local center index or None / -1 / '*' for every center of the graph, point three coordinates in the caller's
+        frame.  Returns the host arrays of pf_sample_begin_guided (numpy; the library validates the values)."""
+        import numpy as np
+        if len(restraints) != self.B:
+            raise ValueError(f"restraints must have one entry per graph ({self.B}), got {len(restraints)}")
+        ptr, kind, center, pt, rad, wt = [0], [], [], [], [], []
+        names = {"attract": 0, "repel": 1, 0: 0, 1: 1}
+        for rs in restraints:
+            for k, c, p, r, w in (rs or []):
+                if isinstance(k, str) and k not in names:
+                    raise ValueError(f"a restraint's kind is 'attract' or 'repel', got {k!r}")
+                kind.append(names[k] if k in names else int(k))
+                center.append(-1 if c is None or c == "*" else int(c))
+                pt.append([float(v) for v in p])
+                if len(pt[-1]) != 3:
+                    raise ValueError("a restraint's point has three coordinates")
+                rad.append(float(r)); wt.append(float(w))
+            ptr.append(len(kind))
+        return (np.asarray(ptr, dtype=np.int32), np.asarray(kind, dtype=np.int32), np.asarray(center, dtype=np.int32),
+                np.ascontiguousarray(np.asarray(pt, dtype=np.float32).reshape(-1, 3)), np.asarray(rad, dtype=np.float32),
+                np.asarray(wt, dtype=np.float32))
+
+    def _free_pins(self):
+        """the pin arrays of a run that pins nothing (a guided run is a pinned run whose flags may all be zero)"""
+        return (torch.zeros(self.Nf, dtype=torch.int32), torch.zeros(self.Nf, 3), torch.zeros(self.Nf, self.pharm_nf))
+
     def _pins(self, pins):
         """(flags [Nf] 0..3, positions [Nf,3] in the caller's frame, feature rows [Nf,pharm_nf]) as device tensors."""
         flags, px, ph = pins
@@ -403,13 +452,24 @@ class PfEngine:
             raise ValueError(f"pins must be (flags [{self.Nf}], positions [{self.Nf}, 3], feature rows [{self.Nf}, {self.pharm_nf}])")
         return flags, px, ph
 
-    def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0):
+    def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0, restraints=None, guide_scale=1.0,
+                     guide_clip=0.0):
         """pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
-        denoise_step(..., pin_coef=...); feat_norm_constant is what the given feature rows are divided by."""
+        denoise_step(..., pin_coef=...); feat_norm_constant is what the given feature rows are divided by.
+        restraints (one list or None per graph, see _restraints): a guided run (pf_sample_begin_guided) -- its steps are
+        guided_step; the caller has selected the wide training family (set_train_family('wide')); pins are optional."""
         nz = _f32(noise0, self.device)
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         self._keep = [nz, com]
         with torch.cuda.device(self.device):
+            if restraints is not None:
+                fl, px, ph = self._pins(pins if pins is not None else self._free_pins())
+                rp, rk, rc, rx, rr, rw = self._restraints(restraints)
+                self._ck(self.lib.pf_sample_begin_guided(self._h, _dptr(com), _dptr(nz), _dptr(fl), _dptr(px), _dptr(ph),
+                                                         float(feat_norm_constant), rp.ctypes.data, rk.ctypes.data, rc.ctypes.data,
+                                                         rx.ctypes.data, rr.ctypes.data, rw.ctypes.data, float(guide_scale),
+                                                         float(guide_clip), _stream_ptr()), "pf_sample_begin_guided")
+                return
             if pins is not None:
                 fl, px, ph = self._pins(pins)
                 self._ck(self.lib.pf_sample_begin_pinned(self._h, _dptr(com), _dptr(nz), _dptr(fl), _dptr(px), _dptr(ph),
@@ -435,6 +495,23 @@ class PfEngine:
             self._ck(self.lib.pf_denoise_step(self._h, ctypes.byref(coef_struct), _dptr(nz), int(ep_coord), int(ep_feat),
                                               _stream_ptr()), "pf_denoise_step")
 
+    def guided_step(self, coef_struct, pin_coef, guide_coef, noise, ep_coord=False, ep_feat=False):
+        """One step of a guided run (pf_denoise_step_guided): coef_struct / pin_coef / guide_coef are this step's entries of
+        coef_array / pin_coef_array / guide_coef_array."""
+        nz = _f32(noise, self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_denoise_step_guided(self._h, ctypes.byref(coef_struct), ctypes.byref(pin_coef), ctypes.byref(guide_coef),
+                                                     _dptr(nz), int(ep_coord), int(ep_feat), _stream_ptr()), "pf_denoise_step_guided")
+
+    def last_guidance(self):
+        """(g0 [Nf, 3], grad [Nf, 3], shift [Nf, 3], E [B]) of the last guided step (pf_debug_last_guidance)."""
+        g0, gr, sh = (torch.empty(self.Nf, 3, device=self.device) for _ in range(3))
+        en = torch.empty(self.B, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_debug_last_guidance(self._h, _dptr(g0), _dptr(gr), _dptr(sh), _dptr(en), _stream_ptr()),
+                     "pf_debug_last_guidance")
+        return g0, gr, sh, en
+
     def renoise_step(self, coef, noise):
         """One resampling jump of a pinned run (pf_renoise_step): coef is a PfRenoiseCoef (an entry of renoise_coef_array)."""
         nz = _f32(noise, self.device)
@@ -459,12 +536,24 @@ class PfEngine:
         return x, hh
 
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
-               feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None):
+               feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None, restraints=None,
+               guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False):
         """pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned.
         plan = (op_arr, renoise_arr) (plan_arrays; n_steps is then the number of ops and coef_arr / pin_coef_arr have one entry
-        per op): pf_sample_pinned_resampled."""
+        per op): pf_sample_pinned_resampled.
+        restraints (one list or None per graph, see _restraints) with pin_coef_arr and guide_coef_arr (guide_coef_array): a guided
+        run, pf_sample_guided -- pins are optional, a plan is refused.  The run is made on the wide training family; the family
+        the engine was on is restored afterwards, also on error.  energies: the restraint energies [n_steps, B] come back
+        behind the other outputs."""
         if plan is not None and pins is None:
             raise ValueError("a plan needs pins: resampling runs inside a pinned run (all flags zero pins nothing)")
+        if restraints is not None:
+            if plan is not None:
+                raise ValueError("guidance together with resampling jumps is not supported")
+            if pin_coef_arr is None or guide_coef_arr is None:
+                raise ValueError("a guided run needs pin_coef_arr (PfEngine.pin_coef_array) and guide_coef_arr (PfEngine.guide_coef_array)")
+            return self._sample_guided(coef_arr, n_steps, noise, init_pharm_com, ep_coord, ep_feat, feat_norm_constant, trajectory,
+                                       pins, pin_coef_arr, restraints, guide_coef_arr, guide_scale, guide_clip, energies)
         nz = _f32(noise, self.device)
         assert nz.shape[0] >= n_steps + 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
@@ -498,6 +587,40 @@ class PfEngine:
                                         float(feat_norm_constant), _dptr(x0), _dptr(h0), _dptr(tx), _dptr(th),
                                         _stream_ptr()), "pf_sample")
         return (x0, h0, tx, th) if trajectory else (x0, h0)
+
+    def _sample_guided(self, coef_arr, n_steps, noise, init_pharm_com, ep_coord, ep_feat, feat_norm_constant, trajectory, pins,
+                       pin_coef_arr, restraints, guide_coef_arr, guide_scale, guide_clip, energies):
+        nz = _f32(noise, self.device)
+        assert nz.shape[0] >= n_steps + 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
+        if len(coef_arr) < n_steps or len(pin_coef_arr) < n_steps or len(guide_coef_arr) < n_steps:
+            raise ValueError(f"a guided run of {n_steps} steps needs {n_steps} entries in each of its three coefficient arrays")
+        com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
+        fl, px, ph = self._pins(pins if pins is not None else self._free_pins())
+        rp, rk, rc, rx, rr, rw = self._restraints(restraints)
+        x0 = torch.empty(self.Nf, 3, device=self.device)
+        h0 = torch.empty(self.Nf, self.pharm_nf, device=self.device)
+        tx = th = en = None
+        if trajectory:
+            tx = torch.empty(n_steps + 1, self.Nf, 3, device=self.device)
+            th = torch.empty(n_steps + 1, self.Nf, self.pharm_nf, device=self.device)
+        if energies:
+            en = torch.empty(max(n_steps, 1), self.B, device=self.device)[:n_steps]
+        family = self.train_family()
+        if family != "wide":
+            self.set_train_family("wide")
+        try:
+            with torch.cuda.device(self.device):
+                self._ck(self.lib.pf_sample_guided(self._h, n_steps, coef_arr, pin_coef_arr, guide_coef_arr, _dptr(nz), _dptr(com),
+                                                   _dptr(fl), _dptr(px), _dptr(ph), int(ep_coord), int(ep_feat), float(feat_norm_constant),
+                                                   rp.ctypes.data, rk.ctypes.data, rc.ctypes.data, rx.ctypes.data, rr.ctypes.data,
+                                                   rw.ctypes.data, float(guide_scale), float(guide_clip), _dptr(x0), _dptr(h0),
+                                                   _dptr(tx), _dptr(th), _dptr(en) if n_steps else None, _stream_ptr()),
+                         "pf_sample_guided")
+        finally:
+            if family != "wide":
+                self.set_train_family(family)
+        out = (x0, h0, tx, th) if trajectory else (x0, h0)
+        return out + (en,) if energies else out
 
     def sample_status(self):
         """Validity of the sampling runs that ended on this handle since the last call (pf_sample_status): raises PfError when a

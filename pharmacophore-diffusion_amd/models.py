@@ -29,7 +29,7 @@ import torch.nn.functional as F
 from .analysis import SampleAnalyzer, SampledPharmacophore
 from .engine import PfEngine
 from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_graph, get_batch_idxs, unbatch
-from .schedule import (PredefinedNoiseSchedule, alpha as _alpha, pin_coefficients, renoise_coefficients, resample_plan,
+from .schedule import (PredefinedNoiseSchedule, alpha as _alpha, guide_coefficients, pin_coefficients, renoise_coefficients, resample_plan,
                        sigma as _sigma, sigma_and_alpha_t_given_s, step_coefficients)
 
 try:  # subclass LightningModule when Lightning is importable (drop-in for train.py / load_from_checkpoint)
@@ -765,7 +765,8 @@ class PharmacophoreDiff(_Base):
     # -- sampling (pharmacodiff.py:433-514) ------------------------------------------------------
     @torch.no_grad()
     def sample_given_receptor(self, g, init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
-                              noise: torch.Tensor = None, pin_resamples: int = 1, pin_jump: int = 10) -> List[SampledPharmacophore]:
+                              noise: torch.Tensor = None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None,
+                              guide_scale: float = 1.0, guide_clip: float = 0.0) -> List[SampledPharmacophore]:
         """Reverse diffusion for a batch of pocket graphs; the whole T-step loop is enqueued on the
         current HIP stream by pf_sample (no host synchronisation inside the loop).
 
@@ -780,9 +781,14 @@ class PharmacophoreDiff(_Base):
         come back bit for bit; the free centers are placed around them.  With ``pin_resamples`` r > 1 such a run is
         pf_sample_pinned_resampled: every stretch of ``pin_jump`` levels is re-noised to its upper level and denoised again,
         r times in all (schedule.resample_plan), so that the free centers can react to the given ones; it has n_ops ~ r T ops
-        and ``noise`` must then have n_ops + 1 rows.  A graph batch without a flag set ignores both."""
+        and ``noise`` must then have n_ops + 1 rows.  A graph batch without a flag set ignores both.
+
+        ``restraints``: None, or one list (or None) per graph of the batch of (kind, center, point, radius, weight) (see
+        ``sample``): with a restraint in it the run is pf_sample_guided with ``guide_scale`` / ``guide_clip``."""
         return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, init_pharm_com, visualize_trajectory, noise,
-                                                                           pin_resamples=pin_resamples, pin_jump=pin_jump)))
+                                                                           pin_resamples=pin_resamples, pin_jump=pin_jump,
+                                                                           restraints=restraints, guide_scale=guide_scale,
+                                                                           guide_clip=guide_clip)))
 
     def _plan_arrays(self, jump: int, resamples: int):
         """(n_ops, coef_arr, pin_coef_arr, op_arr, renoise_arr) of a resampled pinned run at this model's T: a few thousand
@@ -798,15 +804,20 @@ class PharmacophoreDiff(_Base):
         return self._plan_arr[1]
 
     def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0,
-                        pin_resamples: int = 1, pin_jump: int = 10):
+                        pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0, guide_clip: float = 0.0):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
-        current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine)."""
+        current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  ``restraints``: None or one
+        list (or None) per graph of the batch; a batch takes the guided path (pf_sample_guided) only when one of them holds a
+        restraint, as with pin flags."""
         g = as_pocket_graph(g)
         dev = self.device
         T, Nf, nf = self.n_timesteps, g.num_nodes("pharm"), self.n_pharm_feats
         if pin_resamples < 1 or pin_jump < 1:
             raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
         has_pins = g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
+        guided = restraints is not None and any(len(r) > 0 for r in restraints if r is not None)
+        if guided and pin_resamples > 1:
+            raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
         if has_pins and pin_resamples > 1:
             return self._sample_enqueue_resampled(g, init_pharm_com, visualize_trajectory, noise, lane, pin_resamples, pin_jump)
         if noise is None:
@@ -821,10 +832,19 @@ class PharmacophoreDiff(_Base):
             self._coef_arr = (T, eng.coef_array(coef, reversed(range(T))))
         arr = self._coef_arr[1]
         pin_kw = {}
-        if g.pharm_pin is not None and bool((g.pharm_pin != 0).any()):
+        if guided or (g.pharm_pin is not None and bool((g.pharm_pin != 0).any())):
             if getattr(self, "_pin_arr", None) is None or self._pin_arr[0] != T:
                 self._pin_arr = (T, eng.pin_coef_array(pin_coefficients(self.gamma.gamma, T), reversed(range(T))))
-            pin_kw = {"pins": (g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h), "pin_coef_arr": self._pin_arr[1]}
+            pin_kw = {"pin_coef_arr": self._pin_arr[1]}
+            if g.pharm_pin is not None:
+                pin_kw["pins"] = (g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h)
+        if guided:
+            if len(restraints) != g.batch_size:
+                raise ValueError(f"restraints lists {len(restraints)} entries for a batch of {g.batch_size} graphs")
+            if getattr(self, "_guide_arr", None) is None or self._guide_arr[0] != T:
+                self._guide_arr = (T, eng.guide_coef_array(guide_coefficients(self.gamma.gamma, T), reversed(range(T))))
+            pin_kw.update(restraints=restraints, guide_coef_arr=self._guide_arr[1], guide_scale=float(guide_scale),
+                          guide_clip=float(guide_clip))
         com = None
         if init_pharm_com is not None:
             com = init_pharm_com if init_pharm_com.is_cuda else init_pharm_com.float().pin_memory().to(dev, non_blocking=True)
@@ -925,7 +945,8 @@ class PharmacophoreDiff(_Base):
     def sample(self, ref_graphs: List[PocketGraph], n_pharms: List[List[int]], max_batch_size: int = 32,
                init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
                rank: int = 0, world_size: int = 1, noise=None, lanes: int = None,
-               pinned=None, pin_resamples: int = 1, pin_jump: int = 10) -> List[List[SampledPharmacophore]]:
+               pinned=None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0,
+               guide_clip: float = 0.0) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -948,6 +969,15 @@ class PharmacophoreDiff(_Base):
         free centers can react to the given ones; its noise has n_ops + 1 rows.  Batches of free graphs run the default path with
         T + 1 rows, as without them.
 
+        ``restraints``: None, or one entry per pocket -- None or a list of (kind, center, point, radius, weight) with kind
+        'attract' / 'repel', center a center index of the pharmacophore or None for every center, point in the pocket's frame
+        (pocket_io.parse_restraints reads them from text).  Copies of a pocket share its restraints.  A batch with a restraint
+        runs guided (pf_sample_guided: restraint energies on the predicted clean centers shift every step's posterior mean by
+        ``guide_scale`` times the posterior variance times the energy's gradient through the network, each center's shift
+        clipped to ``guide_clip`` angstroms when that is positive); its steps run the width-generic training forward and its
+        input gradients and cost several times a default step.  Batches without one run the default path.
+        Composes with ``pinned``; together with ``pin_resamples`` > 1 it is a ValueError.
+
         ``lanes`` (default ``self.sample_lanes``; None = 2, or 4 when the batches hold at most 32 graphs): batches in flight at
         once, each on its own HIP stream and handle.  Four of
         the five launches of a batched step occupy part of the chip, so independent batches overlap (2 lanes: +16 % at
@@ -959,6 +989,20 @@ class PharmacophoreDiff(_Base):
             return []
         if pin_resamples < 1 or pin_jump < 1:
             raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
+        if restraints is not None:
+            if len(restraints) != n_receptors:
+                raise ValueError(f"restraints lists {len(restraints)} entries for {n_receptors} pockets")
+            restraints = [list(r) if r else None for r in restraints]
+            if not any(restraints):
+                restraints = None
+            elif pin_resamples > 1:
+                raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
+            for r, rs in enumerate(restraints or []):
+                for _, c, _, _, _ in (rs or []):
+                    if c is not None and c != "*" and int(c) >= 0:
+                        small = [int(n) for n in n_pharms[r] if int(n) <= int(c)]
+                        if small:
+                            raise ValueError(f"pocket {r}: a restraint names center {int(c)} but sizes {small} were requested")
         if pinned is not None:
             ref_graphs = self._with_pins(ref_graphs, n_pharms, pinned)
         if init_pharm_com is None:
@@ -1024,8 +1068,10 @@ class PharmacophoreDiff(_Base):
                 else:
                     nz = noise[bi]
                 # the bind is asynchronous (stream-ordered behind the lane's previous batch), nothing here waits for the device
+                batch_r = [restraints[graph_ref_idx[i]] for i in idx] if restraints is not None else None
                 enq = self._sample_enqueue(batch_g, init_coms, visualize_trajectory, nz, lane=lane,
-                                           pin_resamples=pin_resamples, pin_jump=pin_jump)
+                                           pin_resamples=pin_resamples, pin_jump=pin_jump, restraints=batch_r,
+                                           guide_scale=guide_scale, guide_clip=guide_clip)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on

@@ -348,3 +348,46 @@ def process_ligand_and_pocket(rec_file: Path, output_dir: Optional[Path], prot_e
     if output_dir is not None:
         write_pocket_file(pocket_residues, Path(output_dir) / 'pocket.pdb')
     return g
+
+
+# ---- restraints of a guided run (generate_pharmacophores.py --restraints) ------------------------------------------------
+def parse_restraints(text: str, source: str = "restraints"):
+    """One restraint per line: ``attract|repel x y z radius weight [center|*]`` -- a point in the receptor's frame (angstroms), the
+    radius of the sphere around it, the weight of the energy, and the index of the center it applies to (default ``*``: every
+    center).  ``#`` starts a comment; blank lines are skipped.  Returns [(kind, center or None, (x, y, z), radius, weight)], the form
+    PharmacophoreDiff.sample(restraints=...) takes per pocket.  Errors carry the line number."""
+    import math
+    out = []
+    for no, raw in enumerate(text.splitlines(), 1):
+        line = raw.split("#", 1)[0].strip()
+        if not line:
+            continue
+        tok = line.split()
+        where = f"{source}, line {no}"
+        if tok[0] not in ("attract", "repel"):
+            raise ValueError(f"{where}: a restraint starts with 'attract' or 'repel', got {tok[0]!r}")
+        if len(tok) not in (6, 7):
+            raise ValueError(f"{where}: expected '{tok[0]} x y z radius weight [center|*]', got {len(tok)} fields")
+        try:
+            x, y, z, r, w = (float(v) for v in tok[1:6])
+        except ValueError:
+            raise ValueError(f"{where}: x y z radius weight must be numbers, got {' '.join(tok[1:6])!r}") from None
+        if not all(math.isfinite(v) for v in (x, y, z, r, w)):
+            raise ValueError(f"{where}: x y z radius weight must be finite")
+        if r < 0 or w < 0:
+            raise ValueError(f"{where}: radius and weight must not be negative, got {r:g} and {w:g}")
+        center = None
+        if len(tok) == 7 and tok[6] != "*":
+            try:
+                center = int(tok[6])
+            except ValueError:
+                raise ValueError(f"{where}: the center is an index or '*', got {tok[6]!r}") from None
+            if center < 0:
+                raise ValueError(f"{where}: the center index must not be negative, got {center}")
+        out.append((tok[0], center, (x, y, z), r, w))
+    return out
+
+
+def read_restraints(path):
+    with open(path) as f:
+        return parse_restraints(f.read(), source=str(path))

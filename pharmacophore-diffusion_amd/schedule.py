@@ -98,6 +98,16 @@ def pin_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, tor
     return {"alpha_s": alpha(g_s), "sigma_s": sigma(g_s)}
 
 
+def guide_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, torch.Tensor]:
+    """Noise level of z_t, t = s + 1, for all s at once (index = s), fp32 on the host: alpha_t = alpha(gamma((s + 1) / T)) and
+    sigma_t = sigma(gamma((s + 1) / T)) -- what a guided step predicts the clean centers with, x0_hat = (x_t - sigma_t eps_x) /
+    alpha_t (pf_denoise_step_guided, pf_guide_coef)."""
+    g = gamma_table.detach().float().cpu()
+    t = (torch.arange(timesteps) + 1).float() / timesteps
+    g_t = g[torch.round(t * timesteps).long()]
+    return {"alpha_t": alpha(g_t), "sigma_t": sigma(g_t)}
+
+
 def resample_plan(timesteps: int, jump: int, resamples: int):
     """The op list of a pinned run with resampling jumps (include/pfdyn.h, "pinned runs with resampling jumps"): levels run
     T -> 0 in segments (a, b) of length ``jump`` (the last one possibly shorter); every segment is denoised, D(a-1) ... D(b), and
