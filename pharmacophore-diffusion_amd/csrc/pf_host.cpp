@@ -229,6 +229,9 @@ struct LaunchPolicy {
     }
 };
 
+// which sampling run is in progress on a handle (run_guard: what each entry point accepts)
+enum RunKind { RUN_NONE = 0, RUN_PLAIN, RUN_PINNED, RUN_GUIDED };
+
 struct pf_handle {
     LaunchPolicy pol;
     pf_config cfg{};
@@ -373,10 +376,9 @@ struct pf_handle {
     std::vector<float*> t_nsv_z, t_nsv_g, t_nsv_v;  // per conv layer: update-chain levels saved by the training forward [n_update_gvps][2 N][128 / 16 / 48]
     std::vector<char> t_node_saved;         // ... by the last pf_train_forward
     std::vector<int> t_grp;                 // per conv layer: slots per message partial-row group of the last training forward
-    bool sampling = false;
+    RunKind run = RUN_NONE;                 // set by the three pf_sample_begin* calls, reset by a bind
     // pinned centers (pf_sample_begin_pinned): the run in progress replaces the flagged centers every step; the handle's own copy of
     // the caller's arrays (one allocation, kept and reused: flags [Nf], positions [Nf][3], feature rows [Nf][pharm_nf])
-    bool pinned = false;
     void* d_pin = nullptr; size_t pin_capacity = 0;
     int* d_pin_flags = nullptr; float *d_pin_x = nullptr, *d_pin_h = nullptr;
     float pin_feat_norm = 1.f;
@@ -384,7 +386,6 @@ struct pf_handle {
     // memory (restr_ev: the last upload that reads the staging buffer) and live in one device allocation, kept and grown like d_pin:
     // restr_ptr [B + 1], kind [n], center [n], p [n][3], r [n], w [n].  d_guide: what a guided step leaves -- g0, J(g0), grad, shift
     // [Nf][3] each, the zero g_eps_h [Nf][pharm_nf], E [B], D [B][3]
-    bool guided = false;
     void* d_restr = nullptr; size_t restr_capacity = 0;
     void* restr_stage = nullptr; size_t restr_stage_capacity = 0; hipEvent_t restr_ev = nullptr;
     int n_restr = 0;
@@ -678,7 +679,7 @@ static BuildParams build_params(pf_handle* h, bool share = false) {
     bp.ff_k = c.ff_k; bp.pf_k = c.pf_k;
     bp.r2_ff = c.cutoff_ff * c.cutoff_ff; bp.r2_pf = c.cutoff_pf * c.cutoff_pf;
     bp.gnorm = h->d_gnorm; bp.pp_cnt = h->d_pp_cnt; bp.pfq_cnt = h->d_pfq_cnt; bp.norm_mode = c.message_norm_mode;
-    if (h->pa_spec && h->sampling && h->d_pa_stamp && !share) { bp.pa_stamp = h->d_pa_stamp; bp.step_id = h->step_id; bp.pa_same = h->d_pa_same; }
+    if (h->pa_spec && h->run != RUN_NONE && h->d_pa_stamp && !share) { bp.pa_stamp = h->d_pa_stamp; bp.step_id = h->step_id; bp.pa_same = h->d_pa_same; }
     bp.act_ids = prune_layer(h) >= 0 ? h->d_act_ids : nullptr; bp.reg_act = h->d_reg_act;
     bp.eorig = h->d_eorig;
     bp.pa_static = share ? h->d_pa_static : nullptr;
@@ -1066,7 +1067,7 @@ static void edge_n16_form(DynCall& dc, int l) {
         e.ptab16_off[et] = et == ET_PP ? c.rec_nf * PF_S : (et == ET_PF ? 2 * c.rec_nf * PF_S : -1);
     }
     if (l == 0) { e.zs = nullptr; dc.rgp = 4; h->last_hoist = 16; }      // (ptab / ptype / l0_gid were set by edge_launch)
-    if (l == 0 && dc.step != nullptr && h->sampling && !h->coords_custom) {
+    if (l == 0 && dc.step != nullptr && h->run != RUN_NONE && !h->coords_custom) {
         // a sampling run: pp geometry from the original coordinates (the same bits in every step, with or without the rows
         // computed ahead; no race with the build that shifts xn under the speculative items)
         e.x0_static = h->d_prot_x0;
@@ -1823,7 +1824,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     if (fr.host_onehot >= 0) { h->l0_state = fr.host_onehot ? 1 : 2; h->l0_onehot = fr.host_onehot == 1; }
     h->zs_version = 0; h->zs_batch_coords = false; h->coords_custom = false;
     h->have_batch = true;
-    h->sampling = false; h->pinned = false; h->guided = false; h->guide_have = false;
+    h->run = RUN_NONE; h->guide_have = false;
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
 }
@@ -1950,20 +1951,98 @@ int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* 
         h->snap_cur = 0;
     }
     h->coords_custom = false;               // a rigid translate of the batch's own coordinates from here on
-    h->sampling = true; h->pinned = false; h->guided = false;
+    h->run = RUN_PLAIN;
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
 }
 
-// the p(z_s | z_t) update's parameters of one denoising step (h_snap_out is the caller's)
-static StepParams step_params(const pf_handle* h, const pf_step_coef* coef, const float* dev_noise, int32_t ep_coord, int32_t ep_feat) {
+// ---- the sampler's run state: one guard for the entry points that need a run in progress ----
+// One row per run kind: its name, the call that begins it, and what it tells a caller that belongs to a lesser kind -- the step
+// to use instead, and what becomes of a resampling jump.  The kinds are ordered by what they add: a guided run is a pinned run
+// is a plain run, so a caller's kind below the run's is "inside", above it "outside".
+static const struct { const char *name, *begin, *step, *jump; } RUN_ROWS[] = {
+    {nullptr, nullptr, nullptr, nullptr},
+    {"plain", "pf_sample_begin", "use pf_denoise_step", nullptr},
+    {"pinned", "pf_sample_begin_pinned", "use pf_denoise_step_pinned", "use pf_renoise_step"},
+    {"guided", "pf_sample_begin_guided", "use pf_denoise_step_guided", "guidance with resampling jumps is not supported"},
+};
+// who: the caller; needs: the run kind it belongs to (RUN_NONE: any run in progress will do); jump: the caller is a resampling jump
+static int run_guard(pf_handle* h, const char* who, RunKind needs, bool jump = false) {
+    if (needs == RUN_NONE ? h->run != RUN_NONE : h->run == needs) return PF_OK;
+    if (needs == RUN_NONE) PF_FAIL(h, PF_ERR_STATE, "no sampling run in progress");
+    if (h->run > needs) PF_FAIL(h, PF_ERR_STATE, "%s inside a %s run (%s): %s", who, RUN_ROWS[h->run].name, RUN_ROWS[h->run].begin,
+                                jump ? RUN_ROWS[h->run].jump : RUN_ROWS[h->run].step);
+    if (needs == RUN_PLAIN) PF_FAIL(h, PF_ERR_STATE, "%s before pf_sample_begin", who);
+    PF_FAIL(h, PF_ERR_STATE, "%s outside a %s run (%s)", who, RUN_ROWS[needs].name, RUN_ROWS[needs].begin);
+}
+
+// ---- one builder per parameter struct of a step ----
+// what every move reads: the batch, the state and the step's noise (a re-noise move reads nothing else)
+static StepParams step_params_base(const pf_handle* h, const float* dev_noise) {
     StepParams sp{};
     sp.B = h->B; sp.Np_tot = h->Np; sp.prot_ptr = h->d_prot_ptr; sp.pharm_ptr = h->d_pharm_ptr;
-    sp.xn = h->d_xn; sp.pharm_h = h->d_pharm_h; sp.eps_h = h->d_eps_h; sp.eps_x = h->d_eps_x; sp.noise = dev_noise;
-    sp.nf = h->cfg.pharm_nf;
+    sp.xn = h->d_xn; sp.pharm_h = h->d_pharm_h; sp.noise = dev_noise; sp.nf = h->cfg.pharm_nf;
+    return sp;
+}
+// the p(z_s | z_t) update's parameters of one denoising step (h_snap_out is the caller's)
+static StepParams step_params(const pf_handle* h, const pf_step_coef* coef, const float* dev_noise, int32_t ep_coord, int32_t ep_feat) {
+    StepParams sp = step_params_base(h, dev_noise);
+    sp.eps_h = h->d_eps_h; sp.eps_x = h->d_eps_x;
     sp.a_ts = coef->alpha_t_given_s; sp.var = coef->var_terms; sp.sigma = coef->sigma;
     sp.ep_zt = coef->ep_zt; sp.ep_pred = coef->ep_pred; sp.ep_coord = ep_coord; sp.ep_feat = ep_feat;
     return sp;
+}
+// the run's pin arrays at this step's noise level (pinned and guided steps)
+static PinParams pin_params(const pf_handle* h, const pf_pin_coef* pin) {
+    PinParams q{};
+    q.flags = h->d_pin_flags; q.pin_x = h->d_pin_x; q.pin_h = h->d_pin_h; q.com_init = h->d_com_init;
+    q.alpha_s = pin->alpha_s; q.sigma_s = pin->sigma_s; q.feat_norm = h->pin_feat_norm;
+    return q;
+}
+
+// ---- one step end ----
+// The move a step's own last launch makes.  build_form: the move has an "update + edge build in one launch" form (the guided
+// move has none: the width-generic training forward in front of it builds its own edges on every call)
+struct StepMove {
+    enum Kind { PLAIN, PINNED, RENOISE, GUIDED } kind;
+    bool build_form;
+    const PinParams* pin;                   // PINNED, GUIDED
+    const RenoiseParams* renoise;           // RENOISE
+    const GuideShiftParams* shift;          // GUIDED
+    int snap_next;                          // PLAIN: the snapshot sp.h_snap_out is (center hoist)
+};
+// What every op calls after its dynamics call (if it has one): the move, unless the dynamics call's tail or merged launch made
+// it already; what the move leaves of the edges; what survives of the work done ahead (snapshot, center hoist, speculative rows)
+static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipStream_t s) {
+    const bool plain = mv.kind == StepMove::PLAIN;
+    const bool moved = plain && h->tail_done;       // (only a plain step hands its StepParams to run_dynamics)
+    if (!moved) {
+        // the move + the edges of the next dynamics call in one launch, or the move alone
+        const bool build = mv.build_form && encoders_on_the_fly(h), share = build && share_next(h);
+        const BuildParams bp = build ? build_params(h, share) : BuildParams{};
+        {
+            ProfScope ps(h, pf_handle::K_STEP, s);
+            switch (mv.kind) {
+            case StepMove::PLAIN: if (build) pfk_step_build(&sp, &bp, step_build_fast_ok(h) ? 1 : 0, s); else pfk_step_update(&sp, s); break;
+            case StepMove::PINNED: if (build) pfk_step_build_pinned(&sp, mv.pin, &bp, s); else pfk_step_update_pinned(&sp, mv.pin, s); break;
+            case StepMove::RENOISE: if (build) pfk_step_build_renoise(&sp, mv.renoise, &bp, s); else pfk_step_update_renoise(&sp, mv.renoise, s); break;
+            case StepMove::GUIDED: pfk_step_update_guided(&sp, mv.pin, mv.shift, s); break;
+            }
+        }
+        if (build) build_done(h, share);
+        else h->rec_valid = false;                  // the centers moved: the next dynamics call builds
+        h->edges_built = build;
+    }
+    // a re-noise move has no dynamics call in front of it that would have reset these
+    if (!plain) { h->tail_done = false; h->last_tail = 0; }
+    // the work done ahead is for the state the merged launch of a plain step left: every other move invalidates it
+    const bool ahead = plain && h->tail_done && h->last_tail == 2;
+    h->snap_cur = (ahead && sp.h_snap_out) ? mv.snap_next : -1;
+    if (h->snap_cur < 0) h->cen_valid = false;
+    if (!ahead) h->spec_valid = false;
+    const hipError_t e = moved ? hipSuccess : hipGetLastError();     // (run_dynamics has checked the tail and merged launches)
+    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
 }
 
 int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noise, int32_t ep_coord, int32_t ep_feat,
@@ -1971,9 +2050,7 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!coef || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step: null argument");
-    if (!h->sampling) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step before pf_sample_begin");
-    if (h->guided) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step inside a guided run (pf_sample_begin_guided): use pf_denoise_step_guided");
-    if (h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step inside a pinned run (pf_sample_begin_pinned): use pf_denoise_step_pinned");
+    if ((rc = run_guard(h, __func__, RUN_PLAIN)) != PF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
     // center hoist: the updated features also go to the snapshot the NEXT step's hoist workgroups read (they must not race with that
@@ -1983,16 +2060,17 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
     sp.h_snap_out = (h->cen_hoist && h->d_snap[0] && h->pk.l0c_off != 0) ? h->d_snap[snap_next] : nullptr;
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, &sp);      // every graph of the batch is at the same t
     if (rc) return rc;
-    h->snap_cur = (sp.h_snap_out && h->tail_done && h->last_tail == 2) ? snap_next : -1;
-    if (h->snap_cur < 0) h->cen_valid = false;
-    if (h->tail_done) return PF_OK;         // the tail launch did the update and built the next call's edges
-    if (encoders_on_the_fly(h)) {           // update + the edges of the next dynamics call in one launch
-        const bool share = share_next(h);
-        const BuildParams bp = build_params(h, share);
-        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_build(&sp, &bp, step_build_fast_ok(h) ? 1 : 0, s); }
-        build_done(h, share);
-        h->edges_built = true;
-    } else { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update(&sp, s); }
+    return step_end(h, sp, StepMove{StepMove::PLAIN, true, nullptr, nullptr, nullptr, snap_next}, s);
+}
+
+// A run's device scratch (d_pin, d_restr, d_guide): kept while `need` bytes fit, else replaced by one of `want` bytes.  Launches
+// of an earlier run on this stream may still read it, so replacing it waits for the caller's STREAM -- not for the device as
+// grow_buffer does: several lanes sample on one device at once
+static int grow_run_scratch(pf_handle* h, void** buf, size_t* cap, size_t need, size_t want, hipStream_t s) {
+    if (need <= *cap) return PF_OK;
+    if (*buf) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(*buf)); *buf = nullptr; *cap = 0; }
+    PF_HIP(h, hipMalloc(buf, want));
+    *cap = want;
     return PF_OK;
 }
 
@@ -2007,11 +2085,7 @@ int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const 
     hipStream_t s = (hipStream_t)stream;
     const size_t nf = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
     const size_t bytes = nf * 4 * (1 + 3 + nh);
-    if (bytes > h->pin_capacity) {
-        if (h->d_pin) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(h->d_pin)); h->d_pin = nullptr; h->pin_capacity = 0; }
-        PF_HIP(h, hipMalloc(&h->d_pin, bytes));
-        h->pin_capacity = bytes;
-    }
+    if ((rc = grow_run_scratch(h, &h->d_pin, &h->pin_capacity, bytes, bytes, s)) != PF_OK) return rc;
     h->d_pin_flags = (int*)h->d_pin; h->d_pin_x = (float*)h->d_pin + nf; h->d_pin_h = h->d_pin_x + nf * 3;
     if (h->Nf > 0) {
         PF_HIP(h, hipMemcpyAsync(h->d_pin_flags, dev_pin_flags, (size_t)h->Nf * 4, hipMemcpyDeviceToDevice, s));
@@ -2019,7 +2093,7 @@ int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const 
         PF_HIP(h, hipMemcpyAsync(h->d_pin_h, dev_pin_h, (size_t)h->Nf * nh * 4, hipMemcpyDeviceToDevice, s));
     }
     h->pin_feat_norm = feat_norm_constant;
-    h->pinned = true;
+    h->run = RUN_PINNED;
     return PF_OK;
 }
 
@@ -2030,25 +2104,14 @@ int pf_denoise_step_pinned(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!coef || !pin || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_pinned: null argument");
-    if (!h->sampling || !h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_pinned outside a pinned run (pf_sample_begin_pinned)");
-    if (h->guided) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_pinned inside a guided run (pf_sample_begin_guided): use pf_denoise_step_guided");
+    if ((rc = run_guard(h, __func__, RUN_PINNED)) != PF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
-    PinParams q{};
-    q.flags = h->d_pin_flags; q.pin_x = h->d_pin_x; q.pin_h = h->d_pin_h; q.com_init = h->d_com_init;
-    q.alpha_s = pin->alpha_s; q.sigma_s = pin->sigma_s; q.feat_norm = h->pin_feat_norm;
+    const PinParams q = pin_params(h, pin);
     ++h->step_id;
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, nullptr);
     if (rc) return rc;
-    if (encoders_on_the_fly(h)) {           // update + the edges of the next dynamics call in one launch
-        const bool share = share_next(h);
-        const BuildParams bp = build_params(h, share);
-        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_build_pinned(&sp, &q, &bp, s); }
-        build_done(h, share);
-        h->edges_built = true;
-    } else { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update_pinned(&sp, &q, s); }
-    h->snap_cur = -1; h->cen_valid = false; h->spec_valid = false;
-    return PF_OK;
+    return step_end(h, sp, StepMove{StepMove::PINNED, true, &q, nullptr, nullptr, -1}, s);
 }
 
 // Resampling jump of a pinned run: the whole state goes from level b back up to level a with one launch and no dynamics call
@@ -2057,30 +2120,12 @@ int pf_renoise_step(pf_handle* h, const pf_renoise_coef* coef, const float* dev_
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!coef || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_renoise_step: null argument");
-    if (!h->sampling || !h->pinned) PF_FAIL(h, PF_ERR_STATE, "pf_renoise_step outside a pinned run (pf_sample_begin_pinned)");
-    if (h->guided) PF_FAIL(h, PF_ERR_STATE, "pf_renoise_step inside a guided run: guidance with resampling jumps is not supported");
-    hipStream_t s = (hipStream_t)stream;
-    StepParams sp{};
-    sp.B = h->B; sp.Np_tot = h->Np; sp.prot_ptr = h->d_prot_ptr; sp.pharm_ptr = h->d_pharm_ptr;
-    sp.xn = h->d_xn; sp.pharm_h = h->d_pharm_h; sp.noise = dev_noise; sp.nf = h->cfg.pharm_nf;
+    if ((rc = run_guard(h, __func__, RUN_PINNED, true)) != PF_OK) return rc;
+    const StepParams sp = step_params_base(h, dev_noise);
     RenoiseParams r{};
     r.alpha_ts = coef->alpha_t_given_s; r.sigma_ts = coef->sigma_t_given_s;
     ++h->step_id;
-    if (encoders_on_the_fly(h)) {           // forward move + the edges of the next dynamics call in one launch
-        const bool share = share_next(h);
-        const BuildParams bp = build_params(h, share);
-        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_build_renoise(&sp, &r, &bp, s); }
-        build_done(h, share);
-        h->edges_built = true;
-    } else {
-        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update_renoise(&sp, &r, s); }
-        h->edges_built = false; h->rec_valid = false;      // the centers moved: the next dynamics call builds
-    }
-    h->tail_done = false; h->last_tail = 0;
-    h->snap_cur = -1; h->cen_valid = false; h->spec_valid = false;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return PF_OK;
+    return step_end(h, sp, StepMove{StepMove::RENOISE, true, nullptr, &r, nullptr, -1}, (hipStream_t)stream);
 }
 
 int pf_prepare_timesteps(pf_handle* h, const float* host_t, int32_t n, pf_stream stream) {
@@ -2096,7 +2141,7 @@ int pf_prepare_timesteps(pf_handle* h, const float* host_t, int32_t n, pf_stream
 int pf_sample_frame(pf_handle* h, float feat_norm_constant, float* dev_x, float* dev_h, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
-    if (!h->sampling) PF_FAIL(h, PF_ERR_STATE, "no sampling run in progress");
+    if ((rc = run_guard(h, __func__, RUN_NONE)) != PF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     pfk_segment_mean(h->d_xn, h->d_prot_ptr, 0, h->B, h->d_com_tmp, s);
     if (dev_x) pfk_export_coords(h->d_xn, h->Np, h->Nf, h->d_gid, h->d_com_init, h->d_com_tmp, dev_x, s);
@@ -2104,11 +2149,15 @@ int pf_sample_frame(pf_handle* h, float feat_norm_constant, float* dev_x, float*
     return PF_OK;
 }
 
+// a pinned (or guided) run returns the given values bit for bit: x_0 / h_0 and the last trajectory frame
+static void pin_restore(pf_handle* h, float* dev_x, float* dev_h, pf_stream stream) {
+    if (h->run >= RUN_PINNED) pfk_pin_restore(h->d_pin_flags, h->d_pin_x, h->d_pin_h, h->Nf, h->cfg.pharm_nf, dev_x, dev_h, (hipStream_t)stream);
+}
+
 int pf_sample_end(pf_handle* h, float feat_norm_constant, float* dev_x0, float* dev_h0, pf_stream stream) {
     // x_0 = x_t - protein COM + initial protein COM ; h_0 = h_t * norm constant  (pharmacodiff.py:480-488)
     int rc = pf_sample_frame(h, feat_norm_constant, dev_x0, dev_h0, stream);
-    // a pinned run returns the given values bit for bit
-    if (rc == PF_OK && h->pinned) pfk_pin_restore(h->d_pin_flags, h->d_pin_x, h->d_pin_h, h->Nf, h->cfg.pharm_nf, dev_x0, dev_h0, (hipStream_t)stream);
+    if (rc == PF_OK) pin_restore(h, dev_x0, dev_h0, stream);
     // the exchange's cumulative time-out count travels with the results: once the caller has waited for x_0 / h_0 it is on
     // the host too, and pf_sample_status judges THIS run without touching the device
     if (rc == PF_OK && h->d_xstat)
@@ -2138,70 +2187,73 @@ int pf_debug_xchg_fault(pf_handle* h, int32_t drop_word, int32_t poll_max) {
     return PF_OK;
 }
 
-// the whole loop of pf_sample / pf_sample_pinned (host_pin_coef != NULL: a pinned run with the three pin arrays) /
-// pf_sample_pinned_resampled (host_op != NULL: op i is a denoising step, 0, or a resampling jump, 1; NULL: every op is a step)
-static int sample_loop(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef, const float* dev_noise,
-                       const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h,
-                       int32_t ep_coord, int32_t ep_feat, float feat_norm_constant,
-                       float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream,
-                       const int32_t* host_op = nullptr, const pf_renoise_coef* host_renoise = nullptr) {
+// One whole run, as the four pf_sample* entry points describe it.  kind: which begin and which step; op: NULL (every op is a
+// denoising step) or per op 0 (a step) / 1 (a resampling jump); the coefficient arrays have one entry per op, read where the
+// op's kind needs it; pin_*: RUN_PINNED and RUN_GUIDED; restr_* / guide_*: RUN_GUIDED; traj_* / energy: optional outputs
+struct SampleRun {
+    RunKind kind; int32_t n_ops; const int32_t* op;
+    const pf_step_coef* coef; const pf_pin_coef* pin_coef; const pf_renoise_coef* renoise; const pf_guide_coef* guide_coef;
+    const float *noise, *com;
+    const int32_t* pin_flags; const float *pin_x, *pin_h;
+    const int32_t *restr_ptr, *restr_kind, *restr_center; const float *restr_p, *restr_r, *restr_w; float guide_scale, guide_clip;
+    int32_t ep_coord, ep_feat; float feat_norm;
+    float *x0, *h0, *traj_x, *traj_h, *energy;
+};
+// the whole loop of pf_sample / pf_sample_pinned / pf_sample_pinned_resampled / pf_sample_guided
+static int sample_loop(pf_handle* h, const SampleRun& r, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
-    if (n_steps < 0 || (n_steps && !host_coef) || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_sample: bad argument");
-    const bool pinned = dev_pin_flags != nullptr;
-    if (pinned && n_steps && !host_pin_coef) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null host_pin_coef");
-    for (int i = 0; host_op && i < n_steps; ++i) {
-        if (host_op[i] != 0 && host_op[i] != 1) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: op %d has kind %d (0 denoise, 1 renoise)", i, (int)host_op[i]);
-        if (host_op[i] == 1 && !host_renoise) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: null host_renoise");
+    const bool pinned = r.kind >= RUN_PINNED, guided = r.kind == RUN_GUIDED;
+    const int n_ops = r.n_ops;
+    if (n_ops < 0 || (n_ops && (!r.coef || (guided && (!r.pin_coef || !r.guide_coef)))) || !r.noise)
+        PF_FAIL(h, PF_ERR_ARG, "%s: bad argument", guided ? "pf_sample_guided" : "pf_sample");
+    if (pinned && n_ops && !r.pin_coef) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null host_pin_coef");
+    for (int i = 0; r.op && i < n_ops; ++i) {
+        if (r.op[i] != 0 && r.op[i] != 1) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: op %d has kind %d (0 denoise, 1 renoise)", i, (int)r.op[i]);
+        if (r.op[i] == 1 && !r.renoise) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: null host_renoise");
     }
     const size_t row = (size_t)h->Nf * (3 + h->cfg.pharm_nf);
     const size_t fx = (size_t)h->Nf * 3, fh = (size_t)h->Nf * h->cfg.pharm_nf;
-    rc = pinned ? pf_sample_begin_pinned(h, dev_init_pharm_com, dev_noise, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, stream)
-                : pf_sample_begin(h, dev_init_pharm_com, dev_noise, stream);
+    if (guided) rc = pf_sample_begin_guided(h, r.com, r.noise, r.pin_flags, r.pin_x, r.pin_h, r.feat_norm, r.restr_ptr, r.restr_kind, r.restr_center,
+                                            r.restr_p, r.restr_r, r.restr_w, r.guide_scale, r.guide_clip, stream);
+    else if (pinned) rc = pf_sample_begin_pinned(h, r.com, r.noise, r.pin_flags, r.pin_x, r.pin_h, r.feat_norm, stream);
+    else rc = pf_sample_begin(h, r.com, r.noise, stream);
     if (rc) return rc;
-    if (dev_traj_x || dev_traj_h) {
-        rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x, dev_traj_h, stream);
-        if (rc) return rc;
-    }
-    {
+    const bool traj = r.traj_x || r.traj_h;
+    auto frame = [&](int i) { return pf_sample_frame(h, r.feat_norm, r.traj_x ? r.traj_x + (size_t)i * fx : nullptr, r.traj_h ? r.traj_h + (size_t)i * fh : nullptr, stream); };
+    if (traj && (rc = frame(0)) != PF_OK) return rc;
+    if (!guided) {      // (a guided step's dynamics call is a training forward: nothing is hoisted or computed ahead for it)
         std::vector<float> tv;                  // the denoising steps' timesteps in op order
-        tv.reserve(n_steps);
-        for (int i = 0; i < n_steps; ++i) if (!host_op || host_op[i] == 0) tv.push_back(host_coef[i].t);
+        tv.reserve(n_ops);
+        for (int i = 0; i < n_ops; ++i) if (!r.op || r.op[i] == 0) tv.push_back(r.coef[i].t);
         rc = pf_prepare_timesteps(h, tv.data(), (int32_t)tv.size(), stream);
         if (rc) return rc;
     }
-    for (int i = 0; i < n_steps; ++i) {
-        const float* nz = dev_noise + (size_t)(i + 1) * row;
-        if (host_op && host_op[i] == 1) rc = pf_renoise_step(h, host_renoise + i, nz, stream);
-        else rc = pinned ? pf_denoise_step_pinned(h, host_coef + i, host_pin_coef + i, nz, ep_coord, ep_feat, stream)
-                         : pf_denoise_step(h, host_coef + i, nz, ep_coord, ep_feat, stream);
+    for (int i = 0; i < n_ops; ++i) {
+        const float* nz = r.noise + (size_t)(i + 1) * row;
+        if (r.op && r.op[i] == 1) rc = pf_renoise_step(h, r.renoise + i, nz, stream);
+        else if (guided) {
+            h->guide_traj_energy = r.energy ? r.energy + (size_t)i * h->B : nullptr;
+            rc = pf_denoise_step_guided(h, r.coef + i, r.pin_coef + i, r.guide_coef + i, nz, r.ep_coord, r.ep_feat, stream);
+            h->guide_traj_energy = nullptr;
+        } else rc = pinned ? pf_denoise_step_pinned(h, r.coef + i, r.pin_coef + i, nz, r.ep_coord, r.ep_feat, stream)
+                           : pf_denoise_step(h, r.coef + i, nz, r.ep_coord, r.ep_feat, stream);
         if (rc) return rc;
-        if (dev_traj_x || dev_traj_h) {
-            rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x ? dev_traj_x + (size_t)(i + 1) * fx : nullptr,
-                                 dev_traj_h ? dev_traj_h + (size_t)(i + 1) * fh : nullptr, stream);
-            if (rc) return rc;
-        }
+        if (traj && (rc = frame(i + 1)) != PF_OK) return rc;
     }
-    // the last frame of a pinned run carries the given values like x_0 / h_0 do (frame n_steps == x_0 / h_0, as in unpinned runs)
-    if (pinned) pfk_pin_restore(h->d_pin_flags, h->d_pin_x, h->d_pin_h, h->Nf, h->cfg.pharm_nf, dev_traj_x ? dev_traj_x + (size_t)n_steps * fx : nullptr,
-                                dev_traj_h ? dev_traj_h + (size_t)n_steps * fh : nullptr, (hipStream_t)stream);
-    return pf_sample_end(h, feat_norm_constant, dev_x0, dev_h0, stream);
+    // the last frame of a pinned run carries the given values like x_0 / h_0 do (frame n_ops == x_0 / h_0, as in unpinned runs)
+    pin_restore(h, r.traj_x ? r.traj_x + (size_t)n_ops * fx : nullptr, r.traj_h ? r.traj_h + (size_t)n_ops * fh : nullptr, stream);
+    return pf_sample_end(h, r.feat_norm, r.x0, r.h0, stream);
 }
 
 int pf_sample(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const float* dev_noise,
               const float* dev_init_pharm_com, int32_t ep_coord, int32_t ep_feat, float feat_norm_constant,
               float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
-    return sample_loop(h, n_steps, host_coef, nullptr, dev_noise, dev_init_pharm_com, nullptr, nullptr, nullptr, ep_coord, ep_feat,
-                       feat_norm_constant, dev_x0, dev_h0, dev_traj_x, dev_traj_h, stream);
-}
-
-int pf_sample_pinned(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef, const float* dev_noise,
-                     const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h,
-                     int32_t ep_coord, int32_t ep_feat, float feat_norm_constant, float* dev_x0, float* dev_h0,
-                     float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
-    if (h && (!dev_pin_flags || !dev_pin_x || !dev_pin_h)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null pin array");
-    return sample_loop(h, n_steps, host_coef, host_pin_coef, dev_noise, dev_init_pharm_com, dev_pin_flags, dev_pin_x, dev_pin_h, ep_coord, ep_feat,
-                       feat_norm_constant, dev_x0, dev_h0, dev_traj_x, dev_traj_h, stream);
+    SampleRun r{};
+    r.kind = RUN_PLAIN; r.n_ops = n_steps; r.coef = host_coef; r.noise = dev_noise; r.com = dev_init_pharm_com;
+    r.ep_coord = ep_coord; r.ep_feat = ep_feat; r.feat_norm = feat_norm_constant;
+    r.x0 = dev_x0; r.h0 = dev_h0; r.traj_x = dev_traj_x; r.traj_h = dev_traj_h;
+    return sample_loop(h, r, stream);
 }
 
 int pf_sample_pinned_resampled(pf_handle* h, int32_t n_ops, const int32_t* host_op, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef,
@@ -2210,8 +2262,25 @@ int pf_sample_pinned_resampled(pf_handle* h, int32_t n_ops, const int32_t* host_
                                float feat_norm_constant, float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
     if (h && (!dev_pin_flags || !dev_pin_x || !dev_pin_h)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: null pin array");
     if (h && n_ops > 0 && !host_op) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: null host_op");
-    return sample_loop(h, n_ops, host_coef, host_pin_coef, dev_noise, dev_init_pharm_com, dev_pin_flags, dev_pin_x, dev_pin_h, ep_coord, ep_feat,
-                       feat_norm_constant, dev_x0, dev_h0, dev_traj_x, dev_traj_h, stream, host_op, host_renoise);
+    SampleRun r{};
+    r.kind = RUN_PINNED; r.n_ops = n_ops; r.op = host_op; r.coef = host_coef; r.pin_coef = host_pin_coef; r.renoise = host_renoise;
+    r.noise = dev_noise; r.com = dev_init_pharm_com; r.pin_flags = dev_pin_flags; r.pin_x = dev_pin_x; r.pin_h = dev_pin_h;
+    r.ep_coord = ep_coord; r.ep_feat = ep_feat; r.feat_norm = feat_norm_constant;
+    r.x0 = dev_x0; r.h0 = dev_h0; r.traj_x = dev_traj_x; r.traj_h = dev_traj_h;
+    return sample_loop(h, r, stream);
+}
+
+int pf_sample_pinned(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef, const float* dev_noise,
+                     const float* dev_init_pharm_com, const int32_t* dev_pin_flags, const float* dev_pin_x, const float* dev_pin_h,
+                     int32_t ep_coord, int32_t ep_feat, float feat_norm_constant, float* dev_x0, float* dev_h0,
+                     float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
+    if (h && (!dev_pin_flags || !dev_pin_x || !dev_pin_h)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null pin array");
+    SampleRun r{};
+    r.kind = RUN_PINNED; r.n_ops = n_steps; r.coef = host_coef; r.pin_coef = host_pin_coef;
+    r.noise = dev_noise; r.com = dev_init_pharm_com; r.pin_flags = dev_pin_flags; r.pin_x = dev_pin_x; r.pin_h = dev_pin_h;
+    r.ep_coord = ep_coord; r.ep_feat = ep_feat; r.feat_norm = feat_norm_constant;
+    r.x0 = dev_x0; r.h0 = dev_h0; r.traj_x = dev_traj_x; r.traj_h = dev_traj_h;
+    return sample_loop(h, r, stream);
 }
 
 int64_t pf_debug_get_edges(pf_handle* h, int32_t etype, int32_t* host_src, int32_t* host_dst, int64_t capacity,
@@ -3073,6 +3142,18 @@ int pf_dynamics_input_vjp(pf_handle* h, const float* dev_g_eps_h, const float* d
 }
 
 // ---- guided sampling: restraint energies on the predicted clean centers steer the reverse steps (reconstruction guidance) ----
+// The restraint block (d_restr and its staging buffer), in 32-bit words: restr_ptr [B + 1], kind [n1], center [n1], p [n1][3],
+// r [n1], w [n1] with n1 = max(n, 1)
+struct RestrLayout {
+    size_t B1, n1;
+    RestrLayout(int B, int n) : B1((size_t)B + 1), n1((size_t)std::max(n, 1)) {}
+    size_t kind() const { return B1; }
+    size_t center() const { return B1 + n1; }
+    size_t p() const { return B1 + 2 * n1; }
+    size_t r() const { return B1 + 5 * n1; }
+    size_t w() const { return B1 + 6 * n1; }
+    size_t words() const { return B1 + 7 * n1; }
+};
 // every check of pf_sample_begin_guided's own arguments, before anything is enqueued or the handle changes
 static int guide_validate(pf_handle* h, const int32_t* rptr, const int32_t* kind, const int32_t* center, const float* p, const float* r,
                           const float* w, float scale, float clip) {
@@ -3120,38 +3201,31 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     if (const int lim = train_limits_ok(h)) return lim;
     hipStream_t s = (hipStream_t)stream;
     // the restraints: staged in pinned memory in the device layout, then one copy
-    const size_t B1 = (size_t)h->B + 1, n = (size_t)host_restr_ptr[h->B], n1 = std::max<size_t>(n, 1);
-    const size_t words = B1 + n1 * 7, bytes = words * 4;
+    const size_t n = (size_t)host_restr_ptr[h->B];
+    const RestrLayout rl(h->B, (int)n);
+    const size_t bytes = rl.words() * 4;
     if (h->restr_ev) PF_HIP(h, hipEventSynchronize(h->restr_ev));      // the last upload has read the staging buffer
     if (bytes > h->restr_stage_capacity) {
         if (h->restr_stage) { (void)hipHostFree(h->restr_stage); h->restr_stage = nullptr; h->restr_stage_capacity = 0; }
         PF_HIP(h, hipHostMalloc(&h->restr_stage, bytes * 2, hipHostMallocDefault));
         h->restr_stage_capacity = bytes * 2;
     }
-    if (bytes > h->restr_capacity) {
-        if (h->d_restr) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(h->d_restr)); h->d_restr = nullptr; h->restr_capacity = 0; }
-        PF_HIP(h, hipMalloc(&h->d_restr, bytes * 2));
-        h->restr_capacity = bytes * 2;
-    }
+    if ((rc = grow_run_scratch(h, &h->d_restr, &h->restr_capacity, bytes, bytes * 2, s)) != PF_OK) return rc;
     const size_t nf1 = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
     const size_t gwords = nf1 * (12 + nh) + (size_t)h->B * 4;
-    if (gwords * 4 > h->guide_capacity) {
-        if (h->d_guide) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(h->d_guide)); h->d_guide = nullptr; h->guide_capacity = 0; }
-        PF_HIP(h, hipMalloc(&h->d_guide, gwords * 4));
-        h->guide_capacity = gwords * 4;
-    }
+    if ((rc = grow_run_scratch(h, &h->d_guide, &h->guide_capacity, gwords * 4, gwords * 4, s)) != PF_OK) return rc;
     if (!h->restr_ev) PF_HIP(h, hipEventCreateWithFlags(&h->restr_ev, hipEventDisableTiming));
     rc = pf_sample_begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, stream);
     if (rc) return rc;
     {
         int32_t* st = (int32_t*)h->restr_stage;
-        std::memcpy(st, host_restr_ptr, B1 * 4);
+        std::memcpy(st, host_restr_ptr, rl.B1 * 4);
         if (n) {
-            std::memcpy(st + B1, host_restr_kind, n * 4);
-            std::memcpy(st + B1 + n1, host_restr_center, n * 4);
-            std::memcpy(st + B1 + 2 * n1, host_restr_p, n * 12);
-            std::memcpy(st + B1 + 5 * n1, host_restr_r, n * 4);
-            std::memcpy(st + B1 + 6 * n1, host_restr_w, n * 4);
+            std::memcpy(st + rl.kind(), host_restr_kind, n * 4);
+            std::memcpy(st + rl.center(), host_restr_center, n * 4);
+            std::memcpy(st + rl.p(), host_restr_p, n * 12);
+            std::memcpy(st + rl.r(), host_restr_r, n * 4);
+            std::memcpy(st + rl.w(), host_restr_w, n * 4);
         }
         PF_HIP(h, hipMemcpyAsync(h->d_restr, st, bytes, hipMemcpyHostToDevice, s));
         PF_HIP(h, hipEventRecord(h->restr_ev, s));
@@ -3163,7 +3237,7 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     PF_HIP(h, hipMemsetAsync(h->d_guide, 0, gwords * 4, s));          // (the zero g_eps_h of every step's VJP; nothing writes it)
     h->guide_scale = guide_scale; h->guide_clip = guide_clip;
     h->guide_traj_energy = nullptr;
-    h->guided = true; h->guide_have = false;
+    h->run = RUN_GUIDED; h->guide_have = false;
     return PF_OK;
 }
 
@@ -3176,7 +3250,7 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!coef || !pin || !gc || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_guided: null argument");
-    if (!h->sampling || !h->guided) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_guided outside a guided run (pf_sample_begin_guided)");
+    if ((rc = run_guard(h, __func__, RUN_GUIDED)) != PF_OK) return rc;
     if (!h->train_wide) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_guided: the training family was switched inside the guided run (pf_train_set_family)");
     if (!(gc->alpha_t > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_guided: alpha_t must be positive");
     hipStream_t s = (hipStream_t)stream;
@@ -3189,28 +3263,20 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     h->t_have_fwd = false;                      // (the kept forward is this step's: d_t does not hold its timestep)
     if (rc) return rc;
     GuideParams gq{};
-    const size_t B1 = (size_t)h->B + 1, n1 = (size_t)std::max(h->n_restr, 1);
+    const RestrLayout rl(h->B, h->n_restr);
     const int32_t* base = (const int32_t*)h->d_restr;
-    gq.restr_ptr = base; gq.restr_kind = base + B1; gq.restr_center = base + B1 + n1;
-    gq.restr_p = (const float*)(base + B1 + 2 * n1); gq.restr_r = (const float*)(base + B1 + 5 * n1); gq.restr_w = (const float*)(base + B1 + 6 * n1);
+    gq.restr_ptr = base; gq.restr_kind = base + rl.kind(); gq.restr_center = base + rl.center();
+    gq.restr_p = (const float*)(base + rl.p()); gq.restr_r = (const float*)(base + rl.r()); gq.restr_w = (const float*)(base + rl.w());
     gq.com_init = h->d_com_init; gq.alpha_t = gc->alpha_t; gq.sigma_t = gc->sigma_t; gq.ep_coord = ep_coord;
     gq.g0 = h->d_g0; gq.energy = h->d_genergy; gq.traj_energy = h->guide_traj_energy; gq.D = h->d_gD;
     pfk_guide_grad(&sp, &gq, s);
     if ((rc = wide_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s)) != PF_OK) return rc;
-    PinParams q{};
-    q.flags = h->d_pin_flags; q.pin_x = h->d_pin_x; q.pin_h = h->d_pin_h; q.com_init = h->d_com_init;
-    q.alpha_s = pin->alpha_s; q.sigma_s = pin->sigma_s; q.feat_norm = h->pin_feat_norm;
+    const PinParams q = pin_params(h, pin);
     GuideShiftParams gs{};
     gs.g0 = h->d_g0; gs.jx = h->d_gjx; gs.D = h->d_gD; gs.alpha_t = gc->alpha_t; gs.sigma_t = gc->sigma_t;
     gs.scale = h->guide_scale; gs.clip = h->guide_clip; gs.grad = h->d_ggrad; gs.shift = h->d_gshift;
-    { ProfScope ps(h, pf_handle::K_STEP, s); pfk_step_update_guided(&sp, &q, &gs, s); }
-    h->edges_built = false; h->rec_valid = false;          // the centers moved: the next dynamics call builds
-    h->tail_done = false; h->last_tail = 0;
-    h->snap_cur = -1; h->cen_valid = false; h->spec_valid = false;
     h->guide_have = true;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return PF_OK;
+    return step_end(h, sp, StepMove{StepMove::GUIDED, false, &q, nullptr, &gs, -1}, s);
 }
 
 int pf_sample_guided(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef,
@@ -3219,32 +3285,14 @@ int pf_sample_guided(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coe
                      float feat_norm_constant, const int32_t* host_restr_ptr, const int32_t* host_restr_kind, const int32_t* host_restr_center,
                      const float* host_restr_p, const float* host_restr_r, const float* host_restr_w, float guide_scale, float guide_clip,
                      float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, float* dev_energy, pf_stream stream) {
-    int rc = check_ready(h, true);
-    if (rc) return rc;
-    if (n_steps < 0 || (n_steps && (!host_coef || !host_pin_coef || !host_guide_coef)) || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_sample_guided: bad argument");
-    const size_t row = (size_t)h->Nf * (3 + h->cfg.pharm_nf);
-    const size_t fx = (size_t)h->Nf * 3, fh = (size_t)h->Nf * h->cfg.pharm_nf;
-    rc = pf_sample_begin_guided(h, dev_init_pharm_com, dev_noise, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, host_restr_ptr,
-                                host_restr_kind, host_restr_center, host_restr_p, host_restr_r, host_restr_w, guide_scale, guide_clip, stream);
-    if (rc) return rc;
-    if (dev_traj_x || dev_traj_h) {
-        rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x, dev_traj_h, stream);
-        if (rc) return rc;
-    }
-    for (int i = 0; i < n_steps; ++i) {
-        h->guide_traj_energy = dev_energy ? dev_energy + (size_t)i * h->B : nullptr;
-        rc = pf_denoise_step_guided(h, host_coef + i, host_pin_coef + i, host_guide_coef + i, dev_noise + (size_t)(i + 1) * row, ep_coord, ep_feat, stream);
-        h->guide_traj_energy = nullptr;
-        if (rc) return rc;
-        if (dev_traj_x || dev_traj_h) {
-            rc = pf_sample_frame(h, feat_norm_constant, dev_traj_x ? dev_traj_x + (size_t)(i + 1) * fx : nullptr,
-                                 dev_traj_h ? dev_traj_h + (size_t)(i + 1) * fh : nullptr, stream);
-            if (rc) return rc;
-        }
-    }
-    pfk_pin_restore(h->d_pin_flags, h->d_pin_x, h->d_pin_h, h->Nf, h->cfg.pharm_nf, dev_traj_x ? dev_traj_x + (size_t)n_steps * fx : nullptr,
-                    dev_traj_h ? dev_traj_h + (size_t)n_steps * fh : nullptr, (hipStream_t)stream);
-    return pf_sample_end(h, feat_norm_constant, dev_x0, dev_h0, stream);
+    SampleRun r{};
+    r.kind = RUN_GUIDED; r.n_ops = n_steps; r.coef = host_coef; r.pin_coef = host_pin_coef; r.guide_coef = host_guide_coef;
+    r.noise = dev_noise; r.com = dev_init_pharm_com; r.pin_flags = dev_pin_flags; r.pin_x = dev_pin_x; r.pin_h = dev_pin_h;
+    r.restr_ptr = host_restr_ptr; r.restr_kind = host_restr_kind; r.restr_center = host_restr_center;
+    r.restr_p = host_restr_p; r.restr_r = host_restr_r; r.restr_w = host_restr_w; r.guide_scale = guide_scale; r.guide_clip = guide_clip;
+    r.ep_coord = ep_coord; r.ep_feat = ep_feat; r.feat_norm = feat_norm_constant;
+    r.x0 = dev_x0; r.h0 = dev_h0; r.traj_x = dev_traj_x; r.traj_h = dev_traj_h; r.energy = dev_energy;
+    return sample_loop(h, r, stream);
 }
 
 int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* dev_shift, float* dev_energy, pf_stream stream) {

@@ -355,32 +355,35 @@ class PfEngine:
 
     # -- sampling ------------------------------------------------------------------------------
     @staticmethod
+    def _struct_array(struct, tabs: Dict[str, torch.Tensor], order):
+        """ctypes array of ``struct``, one entry per element of ``order`` (at least one): entry i takes every field from
+        tabs[field][order[i]]; an element None leaves its entry zero."""
+        order = list(order)
+        arr = (struct * max(len(order), 1))()
+        for i, s in enumerate(order):
+            if s is not None:
+                arr[i] = struct(*(float(tabs[f][s]) for f, _ in struct._fields_))
+        return arr
+
+    @staticmethod
     def coef_array(coef: Dict[str, torch.Tensor], order):
         """coef: per-s tensors (host logic of the diffusion wrapper); order: iterable of s."""
-        order = list(order)
-        arr = (L.PfStepCoef * max(len(order), 1))()
-        for i, s in enumerate(order):
-            arr[i] = L.PfStepCoef(float(coef["t"][s]), float(coef["alpha_t_given_s"][s]), float(coef["var_terms"][s]),
-                                  float(coef["sigma"][s]), float(coef["ep_zt"][s]), float(coef["ep_pred"][s]))
-        return arr
+        return PfEngine._struct_array(L.PfStepCoef, coef, order)
 
     @staticmethod
     def pin_coef_array(pin_coef: Dict[str, torch.Tensor], order):
         """pin_coef: per-s tensors (schedule.pin_coefficients); order: iterable of s (the same as coef_array's)."""
-        order = list(order)
-        arr = (L.PfPinCoef * max(len(order), 1))()
-        for i, s in enumerate(order):
-            arr[i] = L.PfPinCoef(float(pin_coef["alpha_s"][s]), float(pin_coef["sigma_s"][s]))
-        return arr
+        return PfEngine._struct_array(L.PfPinCoef, pin_coef, order)
 
     @staticmethod
     def renoise_coef_array(renoise_coef: Dict[str, torch.Tensor], n=None):
         """renoise_coef: per-pair tensors (schedule.renoise_coefficients); entry i of the array is pair i."""
-        n = len(renoise_coef["alpha_t_given_s"]) if n is None else n
-        arr = (L.PfRenoiseCoef * max(n, 1))()
-        for i in range(n):
-            arr[i] = L.PfRenoiseCoef(float(renoise_coef["alpha_t_given_s"][i]), float(renoise_coef["sigma_t_given_s"][i]))
-        return arr
+        return PfEngine._struct_array(L.PfRenoiseCoef, renoise_coef, range(len(renoise_coef["alpha_t_given_s"]) if n is None else n))
+
+    @staticmethod
+    def guide_coef_array(guide_coef: Dict[str, torch.Tensor], order):
+        """guide_coef: per-s tensors (schedule.guide_coefficients); order: iterable of s (the same as coef_array's)."""
+        return PfEngine._struct_array(L.PfGuideCoef, guide_coef, order)
 
     @staticmethod
     def plan_arrays(plan, coef, pin_coef, renoise_coef):
@@ -388,32 +391,15 @@ class PfEngine:
         op_arr, renoise_arr), each with one entry per op.  coef / pin_coef: per-s tensors (coef_array / pin_coef_array);
         renoise_coef: schedule.renoise_coefficients of the plan's renoise ops in plan order.  The entries an op's kind does
         not read are zero."""
-        n = len(plan)
-        coef_arr, pin_arr = (L.PfStepCoef * max(n, 1))(), (L.PfPinCoef * max(n, 1))()
-        op_arr, re_arr = (ctypes.c_int32 * max(n, 1))(), (L.PfRenoiseCoef * max(n, 1))()
-        k = 0
         for i, op in enumerate(plan):
-            if op[0] == "denoise":
-                s = op[1]
-                coef_arr[i] = L.PfStepCoef(float(coef["t"][s]), float(coef["alpha_t_given_s"][s]), float(coef["var_terms"][s]),
-                                           float(coef["sigma"][s]), float(coef["ep_zt"][s]), float(coef["ep_pred"][s]))
-                pin_arr[i] = L.PfPinCoef(float(pin_coef["alpha_s"][s]), float(pin_coef["sigma_s"][s]))
-            elif op[0] == "renoise":
-                op_arr[i] = 1
-                re_arr[i] = L.PfRenoiseCoef(float(renoise_coef["alpha_t_given_s"][k]), float(renoise_coef["sigma_t_given_s"][k]))
-                k += 1
-            else:
+            if op[0] not in ("denoise", "renoise"):
                 raise ValueError(f"op {i} of the plan is {op!r}: expected ('denoise', s) or ('renoise', b, a)")
-        return coef_arr, pin_arr, op_arr, re_arr
-
-    @staticmethod
-    def guide_coef_array(guide_coef: Dict[str, torch.Tensor], order):
-        """guide_coef: per-s tensors (schedule.guide_coefficients); order: iterable of s (the same as coef_array's)."""
-        order = list(order)
-        arr = (L.PfGuideCoef * max(len(order), 1))()
-        for i, s in enumerate(order):
-            arr[i] = L.PfGuideCoef(float(guide_coef["alpha_t"][s]), float(guide_coef["sigma_t"][s]))
-        return arr
+        steps = [op[1] if op[0] == "denoise" else None for op in plan]
+        pairs = iter(range(len(plan)))
+        jumps = [next(pairs) if op[0] == "renoise" else None for op in plan]
+        op_arr = (ctypes.c_int32 * max(len(plan), 1))(*[int(j is not None) for j in jumps])
+        return (PfEngine._struct_array(L.PfStepCoef, coef, steps), PfEngine._struct_array(L.PfPinCoef, pin_coef, steps), op_arr,
+                PfEngine._struct_array(L.PfRenoiseCoef, renoise_coef, jumps))
 
     def _restraints(self, restraints):
         """restraints: one list (or None) per graph of (kind, center, point, radius, weight) -- kind 'attract' / 'repel' (or 0 / 1),
@@ -452,6 +438,16 @@ class PfEngine:
             raise ValueError(f"pins must be (flags [{self.Nf}], positions [{self.Nf}, 3], feature rows [{self.Nf}, {self.pharm_nf}])")
         return flags, px, ph
 
+    def _run_inputs(self, pins, restraints):
+        """What a run's kind adds to its begin call, as ctypes arguments: the three device pin arrays (a pinned run; a guided run
+        too, all flags zero when it has no pins) and the six host restraint arrays (a guided run).  Returns (pin arguments,
+        restraint arguments, the tensors and arrays they point into); a tuple is empty where the kind has none."""
+        if pins is None and restraints is None:
+            return (), (), ()
+        fl = self._pins(pins if pins is not None else self._free_pins())
+        rs = self._restraints(restraints) if restraints is not None else ()
+        return tuple(_dptr(t) for t in fl), tuple(a.ctypes.data for a in rs), fl + rs
+
     def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0, restraints=None, guide_scale=1.0,
                      guide_clip=0.0):
         """pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
@@ -461,21 +457,16 @@ class PfEngine:
         nz = _f32(noise0, self.device)
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         self._keep = [nz, com]
+        pin, restr, _alive = self._run_inputs(pins, restraints)
         with torch.cuda.device(self.device):
             if restraints is not None:
-                fl, px, ph = self._pins(pins if pins is not None else self._free_pins())
-                rp, rk, rc, rx, rr, rw = self._restraints(restraints)
-                self._ck(self.lib.pf_sample_begin_guided(self._h, _dptr(com), _dptr(nz), _dptr(fl), _dptr(px), _dptr(ph),
-                                                         float(feat_norm_constant), rp.ctypes.data, rk.ctypes.data, rc.ctypes.data,
-                                                         rx.ctypes.data, rr.ctypes.data, rw.ctypes.data, float(guide_scale),
-                                                         float(guide_clip), _stream_ptr()), "pf_sample_begin_guided")
-                return
-            if pins is not None:
-                fl, px, ph = self._pins(pins)
-                self._ck(self.lib.pf_sample_begin_pinned(self._h, _dptr(com), _dptr(nz), _dptr(fl), _dptr(px), _dptr(ph),
-                                                         float(feat_norm_constant), _stream_ptr()), "pf_sample_begin_pinned")
-                return
-            self._ck(self.lib.pf_sample_begin(self._h, _dptr(com), _dptr(nz), _stream_ptr()), "pf_sample_begin")
+                self._ck(self.lib.pf_sample_begin_guided(self._h, _dptr(com), _dptr(nz), *pin, float(feat_norm_constant), *restr,
+                                                         float(guide_scale), float(guide_clip), _stream_ptr()), "pf_sample_begin_guided")
+            elif pins is not None:
+                self._ck(self.lib.pf_sample_begin_pinned(self._h, _dptr(com), _dptr(nz), *pin, float(feat_norm_constant), _stream_ptr()),
+                         "pf_sample_begin_pinned")
+            else:
+                self._ck(self.lib.pf_sample_begin(self._h, _dptr(com), _dptr(nz), _stream_ptr()), "pf_sample_begin")
 
     def prepare_timesteps(self, coef_arr, n=None):
         """Optional before a loop of denoise_step calls: the timesteps the loop will visit (pf_prepare_timesteps)."""
@@ -518,18 +509,26 @@ class PfEngine:
         with torch.cuda.device(self.device):
             self._ck(self.lib.pf_renoise_step(self._h, ctypes.byref(coef), _dptr(nz), _stream_ptr()), "pf_renoise_step")
 
-    def sample_end(self, feat_norm_constant=1.0):
-        """x_0 / h_0 of the run in progress (pf_sample_end); a pinned run returns its given values bit for bit."""
+    def _sample_outputs(self, frames=0, energy_rows=None):
+        """(x [Nf, 3], h [Nf, pharm_nf], trajectory x, trajectory h, energies) on the device; the trajectory arrays have ``frames``
+        leading rows (0: None), the energies ``energy_rows`` x B (None: None)."""
         x = torch.empty(self.Nf, 3, device=self.device)
         hh = torch.empty(self.Nf, self.pharm_nf, device=self.device)
+        tx = torch.empty(frames, self.Nf, 3, device=self.device) if frames else None
+        th = torch.empty(frames, self.Nf, self.pharm_nf, device=self.device) if frames else None
+        en = None if energy_rows is None else torch.empty(max(energy_rows, 1), self.B, device=self.device)[:energy_rows]
+        return x, hh, tx, th, en
+
+    def sample_end(self, feat_norm_constant=1.0):
+        """x_0 / h_0 of the run in progress (pf_sample_end); a pinned run returns its given values bit for bit."""
+        x, hh = self._sample_outputs()[:2]
         with torch.cuda.device(self.device):
             self._ck(self.lib.pf_sample_end(self._h, float(feat_norm_constant), _dptr(x), _dptr(hh), _stream_ptr()),
                      "pf_sample_end")
         return x, hh
 
     def sample_frame(self, feat_norm_constant=1.0):
-        x = torch.empty(self.Nf, 3, device=self.device)
-        hh = torch.empty(self.Nf, self.pharm_nf, device=self.device)
+        x, hh = self._sample_outputs()[:2]
         with torch.cuda.device(self.device):
             self._ck(self.lib.pf_sample_frame(self._h, float(feat_norm_constant), _dptr(x), _dptr(hh), _stream_ptr()),
                      "pf_sample_frame")
@@ -545,82 +544,46 @@ class PfEngine:
         run, pf_sample_guided -- pins are optional, a plan is refused.  The run is made on the wide training family; the family
         the engine was on is restored afterwards, also on error.  energies: the restraint energies [n_steps, B] come back
         behind the other outputs."""
+        guided = restraints is not None
         if plan is not None and pins is None:
             raise ValueError("a plan needs pins: resampling runs inside a pinned run (all flags zero pins nothing)")
-        if restraints is not None:
-            if plan is not None:
-                raise ValueError("guidance together with resampling jumps is not supported")
-            if pin_coef_arr is None or guide_coef_arr is None:
-                raise ValueError("a guided run needs pin_coef_arr (PfEngine.pin_coef_array) and guide_coef_arr (PfEngine.guide_coef_array)")
-            return self._sample_guided(coef_arr, n_steps, noise, init_pharm_com, ep_coord, ep_feat, feat_norm_constant, trajectory,
-                                       pins, pin_coef_arr, restraints, guide_coef_arr, guide_scale, guide_clip, energies)
+        if guided and plan is not None:
+            raise ValueError("guidance together with resampling jumps is not supported")
+        if guided and (pin_coef_arr is None or guide_coef_arr is None):
+            raise ValueError("a guided run needs pin_coef_arr (PfEngine.pin_coef_array) and guide_coef_arr (PfEngine.guide_coef_array)")
         nz = _f32(noise, self.device)
         assert nz.shape[0] >= n_steps + 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
-        com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
-        x0 = torch.empty(self.Nf, 3, device=self.device)
-        h0 = torch.empty(self.Nf, self.pharm_nf, device=self.device)
-        tx = th = None
-        if trajectory:
-            tx = torch.empty(n_steps + 1, self.Nf, 3, device=self.device)
-            th = torch.empty(n_steps + 1, self.Nf, self.pharm_nf, device=self.device)
-        if pins is not None:
-            if pin_coef_arr is None:
-                raise ValueError("a pinned run needs pin_coef_arr (PfEngine.pin_coef_array)")
-            fl, px, ph = self._pins(pins)
-            if plan is not None:
-                op_arr, re_arr = plan
-                if len(op_arr) < n_steps or len(re_arr) < n_steps or len(coef_arr) < n_steps or len(pin_coef_arr) < n_steps:
-                    raise ValueError(f"a plan of {n_steps} ops needs {n_steps} entries in each of its four arrays")
-                with torch.cuda.device(self.device):
-                    self._ck(self.lib.pf_sample_pinned_resampled(self._h, n_steps, op_arr, coef_arr, pin_coef_arr, re_arr, _dptr(nz),
-                                                                 _dptr(com), _dptr(fl), _dptr(px), _dptr(ph), int(ep_coord), int(ep_feat),
-                                                                 float(feat_norm_constant), _dptr(x0), _dptr(h0), _dptr(tx), _dptr(th),
-                                                                 _stream_ptr()), "pf_sample_pinned_resampled")
-                return (x0, h0, tx, th) if trajectory else (x0, h0)
-            with torch.cuda.device(self.device):
-                self._ck(self.lib.pf_sample_pinned(self._h, n_steps, coef_arr, pin_coef_arr, _dptr(nz), _dptr(com), _dptr(fl),
-                                                   _dptr(px), _dptr(ph), int(ep_coord), int(ep_feat), float(feat_norm_constant),
-                                                   _dptr(x0), _dptr(h0), _dptr(tx), _dptr(th), _stream_ptr()), "pf_sample_pinned")
-            return (x0, h0, tx, th) if trajectory else (x0, h0)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.pf_sample(self._h, n_steps, coef_arr, _dptr(nz), _dptr(com), int(ep_coord), int(ep_feat),
-                                        float(feat_norm_constant), _dptr(x0), _dptr(h0), _dptr(tx), _dptr(th),
-                                        _stream_ptr()), "pf_sample")
-        return (x0, h0, tx, th) if trajectory else (x0, h0)
-
-    def _sample_guided(self, coef_arr, n_steps, noise, init_pharm_com, ep_coord, ep_feat, feat_norm_constant, trajectory, pins,
-                       pin_coef_arr, restraints, guide_coef_arr, guide_scale, guide_clip, energies):
-        nz = _f32(noise, self.device)
-        assert nz.shape[0] >= n_steps + 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
-        if len(coef_arr) < n_steps or len(pin_coef_arr) < n_steps or len(guide_coef_arr) < n_steps:
+        if pins is not None and pin_coef_arr is None:
+            raise ValueError("a pinned run needs pin_coef_arr (PfEngine.pin_coef_array)")
+        if guided and min(len(coef_arr), len(pin_coef_arr), len(guide_coef_arr)) < n_steps:
             raise ValueError(f"a guided run of {n_steps} steps needs {n_steps} entries in each of its three coefficient arrays")
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
-        fl, px, ph = self._pins(pins if pins is not None else self._free_pins())
-        rp, rk, rc, rx, rr, rw = self._restraints(restraints)
-        x0 = torch.empty(self.Nf, 3, device=self.device)
-        h0 = torch.empty(self.Nf, self.pharm_nf, device=self.device)
-        tx = th = en = None
-        if trajectory:
-            tx = torch.empty(n_steps + 1, self.Nf, 3, device=self.device)
-            th = torch.empty(n_steps + 1, self.Nf, self.pharm_nf, device=self.device)
-        if energies:
-            en = torch.empty(max(n_steps, 1), self.B, device=self.device)[:n_steps]
-        family = self.train_family()
+        pin, restr, _alive = self._run_inputs(pins, restraints)
+        if plan is not None and min(len(plan[0]), len(plan[1]), len(coef_arr), len(pin_coef_arr)) < n_steps:
+            raise ValueError(f"a plan of {n_steps} ops needs {n_steps} entries in each of its four arrays")
+        x0, h0, tx, th, en = self._sample_outputs(n_steps + 1 if trajectory else 0, n_steps if guided and energies else None)
+        state, eps = (_dptr(nz), _dptr(com)) + pin, (int(ep_coord), int(ep_feat), float(feat_norm_constant))
+        outs = (_dptr(x0), _dptr(h0), _dptr(tx), _dptr(th))
+        if guided:
+            name, args = "pf_sample_guided", (coef_arr, pin_coef_arr, guide_coef_arr) + state + eps + restr + (
+                float(guide_scale), float(guide_clip)) + outs + (_dptr(en) if n_steps else None,)
+        elif plan is not None:
+            name, args = "pf_sample_pinned_resampled", (plan[0], coef_arr, pin_coef_arr, plan[1]) + state + eps + outs
+        elif pins is not None:
+            name, args = "pf_sample_pinned", (coef_arr, pin_coef_arr) + state + eps + outs
+        else:
+            name, args = "pf_sample", (coef_arr,) + state + eps + outs
+        family = self.train_family() if guided else "wide"       # a guided step runs the wide training forward and its input gradients
         if family != "wide":
             self.set_train_family("wide")
         try:
             with torch.cuda.device(self.device):
-                self._ck(self.lib.pf_sample_guided(self._h, n_steps, coef_arr, pin_coef_arr, guide_coef_arr, _dptr(nz), _dptr(com),
-                                                   _dptr(fl), _dptr(px), _dptr(ph), int(ep_coord), int(ep_feat), float(feat_norm_constant),
-                                                   rp.ctypes.data, rk.ctypes.data, rc.ctypes.data, rx.ctypes.data, rr.ctypes.data,
-                                                   rw.ctypes.data, float(guide_scale), float(guide_clip), _dptr(x0), _dptr(h0),
-                                                   _dptr(tx), _dptr(th), _dptr(en) if n_steps else None, _stream_ptr()),
-                         "pf_sample_guided")
+                self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
         finally:
             if family != "wide":
                 self.set_train_family(family)
         out = (x0, h0, tx, th) if trajectory else (x0, h0)
-        return out + (en,) if energies else out
+        return out + (en,) if guided and energies else out
 
     def sample_status(self):
         """Validity of the sampling runs that ended on this handle since the last call (pf_sample_status): raises PfError when a

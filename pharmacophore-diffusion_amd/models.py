@@ -722,6 +722,7 @@ class PharmacophoreDiff(_Base):
         if pl is not None:
             self.save_hyperparameters()
         self._coef = None
+        self._arrays = {}                       # _host_arrays
 
     # -- Lightning-free conveniences ----------------------------------------------------------
     if pl is None:
@@ -790,86 +791,66 @@ class PharmacophoreDiff(_Base):
                                                                            restraints=restraints, guide_scale=guide_scale,
                                                                            guide_clip=guide_clip)))
 
+    def _host_arrays(self, key, build):
+        """The ctypes arrays of a run at this model's T (500-1000 structs an array; a plan's, a few thousand): built once per key."""
+        key = (self.n_timesteps,) + tuple(key)
+        if key not in self._arrays:
+            self._arrays[key] = build()
+        return self._arrays[key]
+
+    def _step_arrays(self, name):
+        """coef / pin / guide: that per-step coefficient array of a run that visits s = T-1 .. 0"""
+        T = self.n_timesteps
+        tabs, array = {"coef": (self.step_coefficients, PfEngine.coef_array),
+                       "pin": (lambda: pin_coefficients(self.gamma.gamma, T), PfEngine.pin_coef_array),
+                       "guide": (lambda: guide_coefficients(self.gamma.gamma, T), PfEngine.guide_coef_array)}[name]
+        return self._host_arrays((name,), lambda: array(tabs(), reversed(range(T))))
+
     def _plan_arrays(self, jump: int, resamples: int):
-        """(n_ops, coef_arr, pin_coef_arr, op_arr, renoise_arr) of a resampled pinned run at this model's T: a few thousand
-        ctypes structs, built once per (T, jump, resamples)."""
-        key = (self.n_timesteps, int(jump), int(resamples))
-        if getattr(self, "_plan_arr", None) is None or self._plan_arr[0] != key:
+        """(n_ops, coef_arr, pin_coef_arr, op_arr, renoise_arr) of a resampled pinned run at this model's T, per (jump, resamples)."""
+        def build():
             T = self.n_timesteps
             plan = resample_plan(T, jump, resamples)
             pairs = [(op[1], op[2]) for op in plan if op[0] == "renoise"]
-            arrs = PfEngine.plan_arrays(plan, self.step_coefficients(), pin_coefficients(self.gamma.gamma, T),
-                                        renoise_coefficients(self.gamma.gamma, T, pairs))
-            self._plan_arr = (key, (len(plan),) + tuple(arrs))
-        return self._plan_arr[1]
+            return (len(plan),) + tuple(PfEngine.plan_arrays(plan, self.step_coefficients(), pin_coefficients(self.gamma.gamma, T),
+                                                             renoise_coefficients(self.gamma.gamma, T, pairs)))
+        return self._host_arrays(("plan", int(jump), int(resamples)), build)
 
     def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0,
                         pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0, guide_clip: float = 0.0):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
         current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  ``restraints``: None or one
         list (or None) per graph of the batch; a batch takes the guided path (pf_sample_guided) only when one of them holds a
-        restraint, as with pin flags."""
+        restraint, as with pin flags.  A batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled."""
         g = as_pocket_graph(g)
         dev = self.device
-        T, Nf, nf = self.n_timesteps, g.num_nodes("pharm"), self.n_pharm_feats
+        n_ops, Nf, nf = self.n_timesteps, g.num_nodes("pharm"), self.n_pharm_feats
         if pin_resamples < 1 or pin_jump < 1:
             raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
         has_pins = g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
         guided = restraints is not None and any(len(r) > 0 for r in restraints if r is not None)
         if guided and pin_resamples > 1:
             raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
+        kw = {}
         if has_pins and pin_resamples > 1:
-            return self._sample_enqueue_resampled(g, init_pharm_com, visualize_trajectory, noise, lane, pin_resamples, pin_jump)
-        if noise is None:
-            noise = torch.randn(T + 1, Nf, 3 + nf, device=dev)
-        if lane == 0:
-            eng = self.dynamics.bind_graph(g)
+            n_ops, arr, parr, op_arr, re_arr = self._plan_arrays(pin_jump, pin_resamples)
+            if noise is not None and noise.shape[0] != n_ops + 1:
+                raise ValueError(f"a resampled pinned run of {n_ops} ops (T = {self.n_timesteps}, jump {pin_jump}, resamples {pin_resamples}) "
+                                 f"needs {n_ops + 1} noise rows, got {noise.shape[0]}")
+            kw = {"pin_coef_arr": parr, "plan": (op_arr, re_arr)}
         else:
-            eng = self.dynamics.lane_engine(lane)
-            eng.set_batch(g.prot_x, g.prot_h, g.prot_ptr, g.pharm_ptr, g.pp_src, g.pp_dst, pocket_uid=g.pocket_uid)
-        coef = self.step_coefficients()
-        if getattr(self, "_coef_arr", None) is None or self._coef_arr[0] != T:      # 500-1000 ctypes structs: built once
-            self._coef_arr = (T, eng.coef_array(coef, reversed(range(T))))
-        arr = self._coef_arr[1]
-        pin_kw = {}
-        if guided or (g.pharm_pin is not None and bool((g.pharm_pin != 0).any())):
-            if getattr(self, "_pin_arr", None) is None or self._pin_arr[0] != T:
-                self._pin_arr = (T, eng.pin_coef_array(pin_coefficients(self.gamma.gamma, T), reversed(range(T))))
-            pin_kw = {"pin_coef_arr": self._pin_arr[1]}
-            if g.pharm_pin is not None:
-                pin_kw["pins"] = (g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h)
+            arr = self._step_arrays("coef")
+            if guided or has_pins:
+                kw = {"pin_coef_arr": self._step_arrays("pin")}
+        if kw and g.pharm_pin is not None:
+            kw["pins"] = (g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h)
         if guided:
             if len(restraints) != g.batch_size:
                 raise ValueError(f"restraints lists {len(restraints)} entries for a batch of {g.batch_size} graphs")
-            if getattr(self, "_guide_arr", None) is None or self._guide_arr[0] != T:
-                self._guide_arr = (T, eng.guide_coef_array(guide_coefficients(self.gamma.gamma, T), reversed(range(T))))
-            pin_kw.update(restraints=restraints, guide_coef_arr=self._guide_arr[1], guide_scale=float(guide_scale),
-                          guide_clip=float(guide_clip))
-        com = None
-        if init_pharm_com is not None:
-            com = init_pharm_com if init_pharm_com.is_cuda else init_pharm_com.float().pin_memory().to(dev, non_blocking=True)
-        res = eng.sample(arr, T, noise if noise.is_cuda else noise.float().pin_memory().to(dev, non_blocking=True),
-                         init_pharm_com=com, ep_coord=self.endpoint_param_coord,
-                         ep_feat=self.endpoint_param_feat, feat_norm_constant=float(self.pharm_feat_norm_constant),
-                         trajectory=visualize_trajectory, **pin_kw)
-        # results go to pinned host memory with copies enqueued right behind the batch's kernels, and an event marks their
-        # completion: whatever is enqueued afterwards (the next batch) does not delay the fetch of this one
-        host = tuple(None if r is None else torch.empty(r.shape, dtype=r.dtype, pin_memory=True).copy_(r, non_blocking=True)
-                     for r in res)
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(dev))
-        return g, host, visualize_trajectory, done, eng
-
-    def _sample_enqueue_resampled(self, g, init_pharm_com, visualize_trajectory, noise, lane, pin_resamples, pin_jump):
-        """_sample_enqueue for a batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled."""
-        dev = self.device
-        Nf, nf = g.num_nodes("pharm"), self.n_pharm_feats
-        n_ops, arr, parr, op_arr, re_arr = self._plan_arrays(pin_jump, pin_resamples)
+            kw.update(restraints=restraints, guide_coef_arr=self._step_arrays("guide"), guide_scale=float(guide_scale),
+                      guide_clip=float(guide_clip))
         if noise is None:
             noise = torch.randn(n_ops + 1, Nf, 3 + nf, device=dev)
-        elif noise.shape[0] != n_ops + 1:
-            raise ValueError(f"a resampled pinned run of {n_ops} ops (T = {self.n_timesteps}, jump {pin_jump}, resamples {pin_resamples}) "
-                             f"needs {n_ops + 1} noise rows, got {noise.shape[0]}")
         if lane == 0:
             eng = self.dynamics.bind_graph(g)
         else:
@@ -881,8 +862,9 @@ class PharmacophoreDiff(_Base):
         res = eng.sample(arr, n_ops, noise if noise.is_cuda else noise.float().pin_memory().to(dev, non_blocking=True),
                          init_pharm_com=com, ep_coord=self.endpoint_param_coord,
                          ep_feat=self.endpoint_param_feat, feat_norm_constant=float(self.pharm_feat_norm_constant),
-                         trajectory=visualize_trajectory, pins=(g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h), pin_coef_arr=parr,
-                         plan=(op_arr, re_arr))
+                         trajectory=visualize_trajectory, **kw)
+        # results go to pinned host memory with copies enqueued right behind the batch's kernels, and an event marks their
+        # completion: whatever is enqueued afterwards (the next batch) does not delay the fetch of this one
         host = tuple(None if r is None else torch.empty(r.shape, dtype=r.dtype, pin_memory=True).copy_(r, non_blocking=True)
                      for r in res)
         done = torch.cuda.Event()

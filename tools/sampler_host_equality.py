@@ -1,0 +1,183 @@
+"""sampler_host_equality.py -- what the sampler's host code enqueues, as one line per case: run it once per build of the library
+(PFDYN_LIB selects the build, one process each) and compare the two outputs line for line.  A refactor of the host code that
+sequences the sampling launches must leave every line unchanged; the sampler is bitwise repeatable (the suite asserts it), so a
+line that differs is a bug, not a tolerance question.
+
+Cases: run kind (plain, pinned, pinned with all flags zero, resampled with jump 3 and 2 resamples, guided, guided with pins)  x
+entry (the whole-loop C call, the step API driven op by op)  x  batch (two graphs of 12 and 20 atoms with 2 and 3 centers; 32
+copies of one 20-atom pocket with 3..8 centers, the size at which the default plain step takes its merged launch with a center
+hoist)  x  n_convs 1 / 2 / 3  x  environment (read when the handle is created: every case creates its own).  T = 12; the noise
+is seeded.
+
+A line holds: a sha256 over x_0, h_0, both trajectory arrays, last_eps() and, for guided runs, the energies and last_guidance();
+ahead() after the step in the middle of the run (step API) or after the run (whole loop); kernel_family(0) and l0_hoist(); and the
+launch counts per kernel class of a second pass of the same case on the same handle, through the step API with every kernel class
+profiled (profiling the step class switches the merged launch off, hence a second pass; only the counts are printed, times are not
+reproducible).
+
+    python tools/sampler_host_equality.py [--out FILE] [--only SUBSTRING]"""
+import argparse
+import hashlib
+import itertools
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+T, JUMP, RESAMPLES, PREC = 12, 3, 2, 0.25
+KINDS = ("plain", "pinned", "pinned0", "resampled", "guided", "guided_pins")
+ENVS = ("default", "PFDYN_NO_ENC_FLY=1", "PFDYN_NO_CENTER_HOIST=1", "PFDYN_NO_PA_SPEC=1", "PFDYN_NO_FAST_BUILD=1", "PFDYN_TAIL_FORM=16",
+        "PFDYN_WIDE=1")
+_cache = {}
+
+
+def digest(tensors):
+    m = hashlib.sha256()
+    for t in tensors:
+        m.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return m.hexdigest()[:32]
+
+
+def batch_of(name):
+    """(pockets' tensors, prot_ptr, pharm_ptr, COM per graph, COM per center) -- 'two': 12 and 20 atoms, 2 and 3 centers; 'copies': 32 x 20 atoms"""
+    from pharmacoforge_amd import synthetic
+    if name not in _cache:
+        if name == "two":
+            pockets, nfs = [synthetic.synthetic_pocket(21, 12), synthetic.synthetic_pocket(22, 20)], [2, 3]
+        else:
+            pockets, nfs = [synthetic.synthetic_pocket(22, 20)] * 32, [3 + g % 6 for g in range(32)]
+        ptr = lambda ns: torch.tensor([0] + list(itertools.accumulate(ns)))
+        com = torch.stack([p[0].mean(0) for p in pockets])
+        _cache[name] = (torch.cat([p[0] for p in pockets]), torch.cat([p[1] for p in pockets]), ptr([p[0].shape[0] for p in pockets]), ptr(nfs),
+                        com + 0.5, com.repeat_interleave(torch.tensor(nfs), 0))
+    return _cache[name]
+
+
+def schedule_arrays(eng, kind):
+    """(n_ops, op kinds or None, coef_arr, pin_arr, renoise_arr, guide_arr), one entry per op"""
+    from pharmacoforge_amd import schedule
+    gamma = schedule.PredefinedNoiseSchedule("polynomial_2", T, PREC).gamma.detach()
+    coef, pin = schedule.step_coefficients(gamma, T), schedule.pin_coefficients(gamma, T)
+    if kind == "resampled":
+        plan = schedule.resample_plan(T, JUMP, RESAMPLES)
+        pairs = [(op[1], op[2]) for op in plan if op[0] == "renoise"]
+        arr, parr, op_arr, re_arr = eng.plan_arrays(plan, coef, pin, schedule.renoise_coefficients(gamma, T, pairs))
+        return len(plan), op_arr, arr, parr, re_arr, None
+    order = list(reversed(range(T)))
+    return T, None, eng.coef_array(coef, order), eng.pin_coef_array(pin, order), None, eng.guide_coef_array(schedule.guide_coefficients(gamma, T), order)
+
+
+def step_api(eng, kind, sched, noise, com, pins, restraints, mid_ahead):
+    """the run op by op: (x_0, h_0, frames x, frames h) and, in mid_ahead, ahead() after the middle op"""
+    n_ops, op_arr, arr, parr, re_arr, garr = sched
+    guided = restraints is not None
+    family = eng.train_family()
+    if guided:
+        eng.set_train_family("wide")
+    try:
+        eng.sample_begin(noise[0], init_pharm_com=com, pins=pins, restraints=restraints, guide_scale=1.5, guide_clip=0.5)
+        fx, fh = ([t] for t in eng.sample_frame())
+        if not guided:
+            eng.prepare_timesteps([arr[i] for i in range(n_ops) if op_arr is None or op_arr[i] == 0])
+        for i in range(n_ops):
+            if op_arr is not None and op_arr[i] == 1:
+                eng.renoise_step(re_arr[i], noise[i + 1])
+            elif guided:
+                eng.guided_step(arr[i], parr[i], garr[i], noise[i + 1])
+            else:
+                eng.denoise_step(arr[i], noise[i + 1], pin_coef=parr[i] if pins is not None else None)
+            if i == n_ops // 2:
+                mid_ahead.update(eng.ahead())
+            x, h = eng.sample_frame()
+            fx.append(x); fh.append(h)
+        x0, h0 = eng.sample_end()
+    finally:
+        if guided:
+            eng.set_train_family(family)
+    return x0, h0, torch.stack(fx), torch.stack(fh)
+
+
+def run_case(pfa, kind, entry, batch, n_convs, env):
+    from pharmacoforge_amd import synthetic
+    key, _, val = env.partition("=")
+    if val:
+        os.environ[key] = val
+    try:
+        eng = pfa.PfEngine(n_convs=n_convs)
+    finally:
+        os.environ.pop(key, None)
+    if ("sd", n_convs) not in _cache:
+        _cache["sd", n_convs] = synthetic.make_state_dict(3, n_convs=n_convs)
+    eng.load_state_dict(_cache["sd", n_convs])
+    prot_x, prot_h, prot_ptr, pharm_ptr, com, com_f = batch_of(batch)
+    if ("pp", batch) not in _cache:
+        _cache["pp", batch] = eng.build_pp_edges(prot_x, prot_ptr)
+    eng.set_batch(prot_x, prot_h, prot_ptr, pharm_ptr, *_cache["pp", batch])
+    B, Nf, nf = int(pharm_ptr.numel() - 1), int(pharm_ptr[-1]), eng.pharm_nf
+    sched = schedule_arrays(eng, kind)
+    n_ops = sched[0]
+    gen = torch.Generator().manual_seed(7)
+    noise = torch.randn(n_ops + 1, Nf, 3 + nf, generator=gen).to(eng.device)
+    pins = restraints = None
+    if kind in ("pinned", "pinned0", "resampled", "guided_pins"):
+        flags = torch.zeros(Nf, dtype=torch.int32)
+        if kind != "pinned0":
+            flags[pharm_ptr[:-1]] = 3                   # the first center of every graph: position and type; the second: position
+            flags[pharm_ptr[:-1] + 1] = 1
+        pins = (flags, com_f + 1.5 * torch.randn(Nf, 3, generator=gen),
+                torch.nn.functional.one_hot(torch.randint(0, nf, (Nf,), generator=gen), nf).float())
+    guided = kind.startswith("guided")
+    if guided:
+        restraints = [[("attract", 0, (com[g] + torch.tensor([1.5, -0.5, -0.5])).tolist(), 1.0, 1.0),
+                       ("repel", None, (com[g] - torch.tensor([0.5, 1.5, 0.5])).tolist(), 2.0, 0.5)] if g % 2 == 0 else None for g in range(B)]
+    mid = {}
+    try:
+        if entry == "loop":
+            kw = {}
+            if pins is not None or guided:
+                kw.update(pins=pins, pin_coef_arr=sched[3])
+            if kind == "resampled":
+                kw.update(plan=(sched[1], sched[4]))
+            if guided:
+                kw.update(restraints=restraints, guide_coef_arr=sched[5], guide_scale=1.5, guide_clip=0.5, energies=True)
+            out = eng.sample(sched[2], n_ops, noise, init_pharm_com=com, trajectory=True, **kw)
+            mid = eng.ahead()
+        else:
+            out = step_api(eng, kind, sched, noise, com, pins, restraints, mid)
+        out = tuple(out) + tuple(eng.last_eps()) + (tuple(eng.last_guidance()) if guided else ())
+        line = f"{digest(out)} ahead {[int(v) for v in mid.values()]} family {eng.kernel_family(0)} l0_hoist {eng.l0_hoist()}"
+        eng.profile_enable((1 << len(eng.KERNEL_CLASSES)) - 1)
+        step_api(eng, kind, sched, noise, com, pins, restraints, {})
+        line += f" launches {[int(n) for _, n in eng.profile_read().values()]}"
+        torch.cuda.synchronize()
+        eng.sample_status()
+        return line
+    except pfa.PfError as e:
+        return "refused: " + str(e).splitlines()[0]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None, help="also write the lines to this file")
+    ap.add_argument("--only", default=None, help="run the cases whose name contains this")
+    args = ap.parse_args()
+    import pharmacoforge_amd as pfa
+    torch.zeros(1, device="cuda")
+    lines = ["library " + pfa._lib.load().pf_version().decode()]
+    for n_convs, env, batch, kind, entry in itertools.product((1, 2, 3), ENVS, ("two", "copies"), KINDS, ("loop", "steps")):
+        name = f"convs{n_convs} {env} {batch} {kind} {entry}"
+        if args.only and args.only not in name:
+            continue
+        lines.append(f"{name}: {run_case(pfa, kind, entry, batch, n_convs, env)}")
+        print(lines[-1], flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
