@@ -39,6 +39,9 @@ _FLAGS = [
     ('--restraints', dict(type=Path, default=None, help='guided sampling: a text file with one restraint per line, "attract|repel x y z radius weight [center|*]" in the receptor\'s frame (# starts a comment): keep centers out of / pull a center into a sphere; a guided step costs several times a default one')),
     ('--guide_scale', dict(type=float, default=None, help='with --restraints: strength of the guidance (default 1)')),
     ('--guide_clip', dict(type=float, default=None, help='with --restraints: largest shift of a center per step in angstroms (default 0: no clip)')),
+    ('--seed_pharmacophore', dict(type=Path, default=None, help='seeded sampling: one xyz frame in the pharms.xyz format; every sample is a variation of it (the frame is noised forward to --seed_level and only the steps below that level are run)')),
+    ('--seed_level', dict(type=int, default=None, help='with --seed_pharmacophore: the level 1..T the seed is noised to; small: close analogues, large: loose ones')),
+    ('--seed_keep', dict(type=str, default=None, help='with --seed_pharmacophore: comma-separated indices of seed centers that stay fixed in position and type, e.g. 0,2')),
     ('--metrics', dict(action='store_true', help='print the validity of the samples against receptor pharmacophore features')),
 ]
 
@@ -50,7 +53,7 @@ def parse_arguments(argv=None):
     a = parser.parse_args(argv)
     for flag in ('pin_resamples', 'pin_jump'):
         v = getattr(a, flag)
-        if v is not None and a.pinned_centers is None:
+        if v is not None and a.pinned_centers is None and a.seed_keep is None:     # (a seeded run with --seed_keep is a pinned run)
             parser.error(f'--{flag} needs --pinned_centers')
         if v is not None and v < 1:
             parser.error(f'--{flag} must be at least 1, got {v}')
@@ -64,6 +67,32 @@ def parse_arguments(argv=None):
     a.guide_clip = 0.0 if a.guide_clip is None else a.guide_clip
     if a.restraints is not None and a.pin_resamples is not None and a.pin_resamples > 1:
         parser.error('--restraints together with --pin_resamples > 1: guidance with resampling jumps is not supported')
+    a.seed_centers = None
+    a.seed_keep_list = None
+    if a.seed_pharmacophore is None:
+        for flag in ('seed_level', 'seed_keep'):
+            if getattr(a, flag) is not None:
+                parser.error(f'--{flag} needs --seed_pharmacophore')
+    else:
+        if a.seed_level is None:
+            parser.error('--seed_pharmacophore needs --seed_level')
+        if a.seed_level < 1:
+            parser.error(f'--seed_level must be at least 1, got {a.seed_level}')
+        if a.pinned_centers is not None:
+            parser.error('--seed_pharmacophore together with --pinned_centers: use --seed_keep')
+        from pharmacoforge_amd.analysis import read_pinned_centers
+        a.seed_centers = read_pinned_centers(a.seed_pharmacophore)
+        n_seed = len(a.seed_centers[1])
+        if any(n != n_seed for n in a.pharm_sizes):
+            parser.error(f'--pharm_sizes {a.pharm_sizes} differ from the {n_seed} centers of --seed_pharmacophore')
+        if a.seed_keep is not None:
+            try:
+                a.seed_keep_list = [int(v) for v in a.seed_keep.split(',') if v.strip()]
+            except ValueError:
+                parser.error(f'--seed_keep is a comma-separated list of center indices, got {a.seed_keep!r}')
+            bad = [i for i in a.seed_keep_list if not 0 <= i < n_seed]
+            if bad:
+                parser.error(f'--seed_keep {bad} outside the {n_seed} centers of --seed_pharmacophore')
     a.pin_resamples = 1 if a.pin_resamples is None else a.pin_resamples
     a.pin_jump = 10 if a.pin_jump is None else a.pin_jump
     problems = []
@@ -169,7 +198,9 @@ def main(argv=None):
     while len(pharms) < args.samples_per_pocket:
         n = min(args.samples_per_pocket - len(pharms), args.max_batch_size)
         sizes = args.pharm_sizes or model.pharm_size_dist.sample_uniformly(args.samples_per_pocket)
-        if max(k_pin, k_named) and not args.pharm_sizes:
+        if args.seed_centers is not None:                # every sample has the seed's size
+            sizes = [len(args.seed_centers[1])] * args.samples_per_pocket
+        elif max(k_pin, k_named) and not args.pharm_sizes:
             sizes = pinned_sizes(sizes, max(k_pin, k_named), 'pinned centers' if k_pin >= k_named else 'centers named in --restraints')
         # like the reference (:329-333, utils/unorganized_utils.py:48) every chunk reads the size list from its start
         copies = pfa.batch(pfa.copy_graph(pocket, n, pharm_feats_per_copy=sizes))
@@ -178,7 +209,9 @@ def main(argv=None):
             pharms += model.sample_given_receptor(copies, init_pharm_com=com, visualize_trajectory=args.visualize_trajectory,
                                                   pin_resamples=args.pin_resamples, pin_jump=args.pin_jump,
                                                   restraints=[args.restraint_list] * n if args.restraint_list else None,
-                                                  guide_scale=args.guide_scale, guide_clip=args.guide_clip)
+                                                  guide_scale=args.guide_scale, guide_clip=args.guide_clip,
+                                                  seeds=[args.seed_centers] * n if args.seed_centers is not None else None, seed_level=args.seed_level,
+                                                  seed_keep=[args.seed_keep_list] * n if args.seed_keep_list else None)
     elapsed = time.time() - t0
 
     (pocket_dir / 'sample_time.txt').write_text(f'{elapsed:.2f}')

@@ -323,6 +323,33 @@ int pf_sample_guided(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coe
  * ignored) and E [B]; PF_ERR_STATE when no guided step has run on this batch */
 int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* dev_shift, float* dev_energy, pf_stream stream);
 
+/* -- seeded sampling: start the reverse process from a given pharmacophore (partial diffusion; no reference counterpart) ----------
+ * The given sample is noised forward to an intermediate level a, 1 <= a <= T, and only the reverse steps a-1 .. 0 are run: a small
+ * a gives close analogues of the seed, a large a loose ones.
+ * Arming.  pf_sample_seed_next is optional and comes after a bind.  It arms the NEXT begin on the handle, of any kind:
+ * pf_sample_begin, pf_sample_begin_pinned, pf_sample_begin_guided, or a begin made inside a whole-loop entry.  That begin consumes
+ * the seed on entry, whether it then succeeds or is rejected (the rule of pf_set_pocket_groups); a whole-loop entry that rejects its
+ * own arguments before it reaches its begin leaves the seed armed.  A bind in between discards the seed, and a second call replaces
+ * it.  The two arrays are copied into handle-owned run scratch on `stream` (kept and grown like the pin arrays); the caller may free
+ * them once the stream has passed the call.
+ * Argument errors.  PF_ERR_ARG for a null argument, for a non-finite coefficient, for alpha_a <= 0, for sigma_a < 0, and for
+ * feat_norm_constant <= 0.  In each of these cases the handle and any run in progress are untouched.
+ * A seeded begin does what the begin does today: the protein is shifted by init_pharm_com, or by its own mean.  Then, in place of
+ * "state := noise0", for every graph g and center f:
+ *     D[g]  = c_init[g] - (mean of the graph's current protein rows)          the pinned step's reduction, in its order
+ *     x[f]  = alpha_a * (seed_x[f] - D[g])              + sigma_a * noise0_x[f]
+ *     h[f]  = alpha_a * (seed_h[f] / feat_norm_constant) + sigma_a * noise0_h[f]
+ * One rounding per operation, FP contraction off, as in a pinned step.  Then the COM of all centers of the graph is removed from
+ * centers and protein, in the reduction order of pf_denoise_step's update.  One launch (k_step_build_seed: the move + the generic
+ * edge build; k_step_update_seed for the width-generic family and every configuration whose next dynamics call builds its own edges).
+ * The rest of the run.  The caller passes n_steps = a and the coefficient entries for s = a-1 .. 0.  Nothing else in the run
+ * changes: a seeded plain run takes the default path's steps, merged last launch and center hoist included.  The initial frame of
+ * a trajectory is the noised seed.  Pins in a seeded pinned run act from the first step on, as today: the begin does not look at
+ * the flags.  At most 64 centers per graph can be bound, so the kernels' path for more than 256 centers of a graph is never taken. */
+typedef struct pf_seed_coef { float alpha_a; float sigma_a; } pf_seed_coef;   /* alpha / sigma(gamma(a/T)), fp32, computed by the host */
+int pf_sample_seed_next(pf_handle* h, const pf_seed_coef* coef, const float* dev_seed_x /*[Nf,3], caller's frame*/,
+                        const float* dev_seed_h /*[Nf,pharm_nf], raw rows*/, float feat_norm_constant, pf_stream stream);
+
 /* -- training step: gradients of the dynamics (autograd through PharmRecDynamicsGVP.forward, ------
  *    dynamics_gvp.py:131-185, as used by PharmacophoreDiff.forward / training_step, pharmacodiff.py:162-276)
  * Parameters and gradients are exchanged as ONE flat fp32 vector in the reference's state-dict order

@@ -540,6 +540,14 @@ struct PinParams {
 struct RenoiseParams {
     float alpha_ts, sigma_ts;  // alpha_{a|b}, sigma_{a|b} (pf_renoise_coef)
 };
+// seeded begin (pf_sample_seed_next): z_a = alpha_a * seed + sigma_a * noise0, the seed taken into the sampler's frame first; of
+// StepParams it reads the graph pointers, xn, pharm_h, noise (the initial draw), nf and h_snap_out
+struct SeedParams {
+    const float* seed_x;       // [Nf][3]   given positions, caller's frame
+    const float* seed_h;       // [Nf][nf]  given feature rows, raw (divided by feat_norm here)
+    const float* com_init;     // [B][3]    mean of the original protein coordinates (pf_sample_begin)
+    float alpha_a, sigma_a, feat_norm;
+};
 // guided sampling (pf_denoise_step_guided): restraint energies on the predicted clean centers.  k_guide_grad reads GuideParams
 // (of StepParams: the graph pointers, xn and eps_x) and leaves g0 = dE/dy per center, E per graph and the frame offset D per graph;
 // the guided update (k_step_update_guided) reads GuideShiftParams: g0, the VJP of the dynamics J(g0) and D

@@ -70,6 +70,8 @@ void pfk_step_update_guided(const StepParams* p, const PinParams* q, const Guide
 void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s);
 void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s);
 void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s);
+void pfk_step_build_seed(const StepParams* sp, const SeedParams* q, const BuildParams* bp, hipStream_t s);
+void pfk_step_update_seed(const StepParams* p, const SeedParams* q, hipStream_t s);
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s);
@@ -382,6 +384,13 @@ struct pf_handle {
     void* d_pin = nullptr; size_t pin_capacity = 0;
     int* d_pin_flags = nullptr; float *d_pin_x = nullptr, *d_pin_h = nullptr;
     float pin_feat_norm = 1.f;
+    // seeded begin (pf_sample_seed_next): the handle's own copy of the caller's seed (one allocation, kept and grown like d_pin:
+    // positions [Nf][3], feature rows [Nf][pharm_nf]) and its level's coefficients.  seed_armed: the next begin starts from it;
+    // taken off the handle on that begin's entry, dropped by a bind
+    void* d_seed = nullptr; size_t seed_capacity = 0;
+    float *d_seed_x = nullptr, *d_seed_h = nullptr;
+    float seed_alpha = 1.f, seed_sigma = 0.f, seed_feat_norm = 1.f;
+    bool seed_armed = false;
     // guided run (pf_sample_begin_guided): a pinned run plus restraint energies per graph.  The restraints are staged in pinned host
     // memory (restr_ev: the last upload that reads the staging buffer) and live in one device allocation, kept and grown like d_pin:
     // restr_ptr [B + 1], kind [n], center [n], p [n][3], r [n], w [n].  d_guide: what a guided step leaves -- g0, J(g0), grad, shift
@@ -1492,6 +1501,7 @@ void pf_destroy(pf_handle* h) {
     if (h->d_l0c) (void)hipFree(h->d_l0c);
     if (h->d_ptab) (void)hipFree(h->d_ptab);
     if (h->d_pin) (void)hipFree(h->d_pin);
+    if (h->d_seed) (void)hipFree(h->d_seed);
     if (h->d_restr) (void)hipFree(h->d_restr);
     if (h->d_guide) (void)hipFree(h->d_guide);
     if (h->restr_stage) (void)hipHostFree(h->restr_stage);
@@ -1672,6 +1682,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     // can fail, so that a rejected bind never leaves it behind for the next, unrelated batch
     pfbind::BindInputs in;
     if (h) in.rep.swap(h->pending_rep);
+    if (h) h->seed_armed = false;               // (so does a seed: pf_sample_seed_next comes after the bind it is for)
     int rc = check_ready(h, false);
     if (rc) return rc;
     const bool from_host = host_prot_x != nullptr;
@@ -1834,6 +1845,7 @@ int pf_set_pocket_batch(pf_handle* h, int32_t B, const int32_t* prot_ptr, const 
                         const int32_t* pp_dst, pf_stream stream) {
     if (h && (!dev_prot_x || !dev_prot_h)) {
         h->pending_rep.clear();                  // a pocket-group claim never outlives the bind it was made for, rejected or not
+        h->seed_armed = false;
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch: bad argument");
     }
     return set_pocket_batch_impl(h, B, prot_ptr, pharm_ptr, dev_prot_x, dev_prot_h, nullptr, nullptr, n_pp, pp_src, pp_dst, stream);
@@ -1844,6 +1856,7 @@ int pf_set_pocket_batch_host(pf_handle* h, int32_t B, const int32_t* prot_ptr, c
                              const int32_t* pp_dst, pf_stream stream) {
     if (h && (!host_prot_x || !host_prot_h)) {
         h->pending_rep.clear();
+        h->seed_armed = false;
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch_host: bad argument");
     }
     return set_pocket_batch_impl(h, B, prot_ptr, pharm_ptr, nullptr, nullptr, host_prot_x, host_prot_h, n_pp, pp_src, pp_dst, stream);
@@ -1925,7 +1938,16 @@ int pf_dynamics_forward(pf_handle* h, const float* dev_prot_x, const float* dev_
     return run_dynamics(h, dev_eps_h, dev_eps_x, s);
 }
 
-int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, pf_stream stream) {
+// Seeded begin (pf_sample_seed_next): the seed arms the NEXT begin of any kind.  Every public begin takes it off the handle on
+// entry -- before it can reject anything -- and hands `seeded` down to the begin it is built on
+static bool take_seed(pf_handle* h) {
+    const bool armed = h && h->seed_armed;
+    if (h) h->seed_armed = false;
+    return armed;
+}
+static int seed_move(pf_handle* h, const float* dev_noise0, hipStream_t s);
+
+static int begin_plain(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, bool seeded, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_noise0) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin: null noise");
@@ -1943,17 +1965,21 @@ int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* 
     pfk_segment_mean(h->d_xn, h->d_prot_ptr, 0, h->B, h->d_com_init, s);
     const float* shift = dev_init_pharm_com ? dev_init_pharm_com : h->d_com_init;      // :448-452
     pfk_load_coords(h->d_prot_x0, h->d_xn, h->Np, h->d_gid, shift, -1.f, s);
-    pfk_load_noise0(dev_noise0, h->d_xn + h->Np, h->d_pharm_h, h->Nf, h->cfg.pharm_nf, s);  // :455-456
+    if (!seeded) pfk_load_noise0(dev_noise0, h->d_xn + h->Np, h->d_pharm_h, h->Nf, h->cfg.pharm_nf, s);  // :455-456
     h->cen_valid = false; h->snap_cur = -1;
     h->spec_valid = false; h->step_id += 2;      // (a gap: no stamp of the run before reads as "the previous step")
-    if (h->cen_hoist && h->d_snap[0] && h->pk.l0c_off != 0) {      // center hoist: the features as they are, for the first step's hoist workgroups
+    if (!seeded && h->cen_hoist && h->d_snap[0] && h->pk.l0c_off != 0) {      // center hoist: the features as they are, for the first step's hoist workgroups
         pfk_copy(h->d_pharm_h, h->d_snap[0], (size_t)h->Nf * h->cfg.pharm_nf, s);
         h->snap_cur = 0;
     }
     h->coords_custom = false;               // a rigid translate of the batch's own coordinates from here on
     h->run = RUN_PLAIN;
     h->edges_built = false; h->rec_valid = false;
-    return PF_OK;
+    // a seeded begin: the state is the noised seed, made by a move of the step end (which also writes the snapshot, after the move)
+    return seeded ? seed_move(h, dev_noise0, s) : PF_OK;
+}
+int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, pf_stream stream) {
+    return begin_plain(h, dev_init_pharm_com, dev_noise0, take_seed(h), stream);
 }
 
 // ---- the sampler's run state: one guard for the entry points that need a run in progress ----
@@ -2004,12 +2030,13 @@ static PinParams pin_params(const pf_handle* h, const pf_pin_coef* pin) {
 // The move a step's own last launch makes.  build_form: the move has an "update + edge build in one launch" form (the guided
 // move has none: the width-generic training forward in front of it builds its own edges on every call)
 struct StepMove {
-    enum Kind { PLAIN, PINNED, RENOISE, GUIDED } kind;
+    enum Kind { PLAIN, PINNED, RENOISE, GUIDED, SEED } kind;
     bool build_form;
     const PinParams* pin;                   // PINNED, GUIDED
     const RenoiseParams* renoise;           // RENOISE
     const GuideShiftParams* shift;          // GUIDED
-    int snap_next;                          // PLAIN: the snapshot sp.h_snap_out is (center hoist)
+    int snap_next;                          // PLAIN, SEED: the snapshot sp.h_snap_out is (center hoist)
+    const SeedParams* seed = nullptr;       // SEED
 };
 // What every op calls after its dynamics call (if it has one): the move, unless the dynamics call's tail or merged launch made
 // it already; what the move leaves of the edges; what survives of the work done ahead (snapshot, center hoist, speculative rows)
@@ -2027,6 +2054,7 @@ static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipS
             case StepMove::PINNED: if (build) pfk_step_build_pinned(&sp, mv.pin, &bp, s); else pfk_step_update_pinned(&sp, mv.pin, s); break;
             case StepMove::RENOISE: if (build) pfk_step_build_renoise(&sp, mv.renoise, &bp, s); else pfk_step_update_renoise(&sp, mv.renoise, s); break;
             case StepMove::GUIDED: pfk_step_update_guided(&sp, mv.pin, mv.shift, s); break;
+            case StepMove::SEED: if (build) pfk_step_build_seed(&sp, mv.seed, &bp, s); else pfk_step_update_seed(&sp, mv.seed, s); break;
             }
         }
         if (build) build_done(h, share);
@@ -2035,9 +2063,10 @@ static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipS
     }
     // a re-noise move has no dynamics call in front of it that would have reset these
     if (!plain) { h->tail_done = false; h->last_tail = 0; }
-    // the work done ahead is for the state the merged launch of a plain step left: every other move invalidates it
+    // the work done ahead is for the state the merged launch of a plain step left: every other move invalidates it.  The seed
+    // move opens a run: nothing is ahead of it, and the snapshot it wrote holds the features as they are now
     const bool ahead = plain && h->tail_done && h->last_tail == 2;
-    h->snap_cur = (ahead && sp.h_snap_out) ? mv.snap_next : -1;
+    h->snap_cur = ((ahead || mv.kind == StepMove::SEED) && sp.h_snap_out) ? mv.snap_next : -1;
     if (h->snap_cur < 0) h->cen_valid = false;
     if (!ahead) h->spec_valid = false;
     const hipError_t e = moved ? hipSuccess : hipGetLastError();     // (run_dynamics has checked the tail and merged launches)
@@ -2063,7 +2092,18 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
     return step_end(h, sp, StepMove{StepMove::PLAIN, true, nullptr, nullptr, nullptr, snap_next}, s);
 }
 
-// A run's device scratch (d_pin, d_restr, d_guide): kept while `need` bytes fit, else replaced by one of `want` bytes.  Launches
+// The seeded begin's move (pf_sample_seed_next): every center becomes the seed noised to the run's first level with the initial
+// draw; the snapshot the first plain step's hoist workgroups read is written by the move itself
+static int seed_move(pf_handle* h, const float* dev_noise0, hipStream_t s) {
+    StepParams sp = step_params_base(h, dev_noise0);
+    sp.h_snap_out = (h->cen_hoist && h->d_snap[0] && h->pk.l0c_off != 0) ? h->d_snap[0] : nullptr;
+    SeedParams q{};
+    q.seed_x = h->d_seed_x; q.seed_h = h->d_seed_h; q.com_init = h->d_com_init;
+    q.alpha_a = h->seed_alpha; q.sigma_a = h->seed_sigma; q.feat_norm = h->seed_feat_norm;
+    return step_end(h, sp, StepMove{StepMove::SEED, true, nullptr, nullptr, nullptr, 0, &q}, s);
+}
+
+// A run's device scratch (d_pin, d_restr, d_guide, d_seed): kept while `need` bytes fit, else replaced by one of `want` bytes.  Launches
 // of an earlier run on this stream may still read it, so replacing it waits for the caller's STREAM -- not for the device as
 // grow_buffer does: several lanes sample on one device at once
 static int grow_run_scratch(pf_handle* h, void** buf, size_t* cap, size_t need, size_t want, hipStream_t s) {
@@ -2076,11 +2116,11 @@ static int grow_run_scratch(pf_handle* h, void** buf, size_t* cap, size_t need, 
 
 // Pinned centers: pf_sample_begin, then the handle's own copy of the caller's pin arrays (stream-ordered; the caller may free its
 // arrays once the stream has passed this call).  The run is pinned until the next pf_sample_begin / _pinned or bind
-int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
-                           const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, pf_stream stream) {
+static int begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
+                        const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, bool seeded, pf_stream stream) {
     if (h && (!dev_pin_flags || !dev_pin_x || !dev_pin_h)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_pinned: null pin array");
     if (h && !(feat_norm_constant > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_pinned: feat_norm_constant must be positive");
-    int rc = pf_sample_begin(h, dev_init_pharm_com, dev_noise0, stream);
+    int rc = begin_plain(h, dev_init_pharm_com, dev_noise0, seeded, stream);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t nf = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
@@ -2094,6 +2134,35 @@ int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const 
     }
     h->pin_feat_norm = feat_norm_constant;
     h->run = RUN_PINNED;
+    return PF_OK;
+}
+int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
+                           const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, pf_stream stream) {
+    return begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, take_seed(h), stream);
+}
+
+// Arms the next begin with a seed (the semantics: pfdyn.h).  Every argument check runs before anything is touched; the two arrays
+// become the handle's own (stream-ordered copies into run scratch), so a run in progress -- which reads none of it -- goes on
+int pf_sample_seed_next(pf_handle* h, const pf_seed_coef* coef, const float* dev_seed_x, const float* dev_seed_h, float feat_norm_constant,
+                        pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!coef || !dev_seed_x || !dev_seed_h) PF_FAIL(h, PF_ERR_ARG, "pf_sample_seed_next: null argument");
+    if (!std::isfinite(coef->alpha_a) || !std::isfinite(coef->sigma_a) || !(coef->alpha_a > 0.f) || coef->sigma_a < 0.f)
+        PF_FAIL(h, PF_ERR_ARG, "pf_sample_seed_next: alpha_a must be finite and > 0, sigma_a finite and >= 0");
+    if (!(feat_norm_constant > 0.f) || !std::isfinite(feat_norm_constant)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_seed_next: feat_norm_constant must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nf = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
+    const size_t bytes = nf * 4 * (3 + nh);
+    h->seed_armed = false;                  // (a seed armed before and not yet used is replaced, also when the copies below fail)
+    if ((rc = grow_run_scratch(h, &h->d_seed, &h->seed_capacity, bytes, bytes, s)) != PF_OK) return rc;
+    h->d_seed_x = (float*)h->d_seed; h->d_seed_h = h->d_seed_x + nf * 3;
+    if (h->Nf > 0) {
+        PF_HIP(h, hipMemcpyAsync(h->d_seed_x, dev_seed_x, (size_t)h->Nf * 3 * 4, hipMemcpyDeviceToDevice, s));
+        PF_HIP(h, hipMemcpyAsync(h->d_seed_h, dev_seed_h, (size_t)h->Nf * nh * 4, hipMemcpyDeviceToDevice, s));
+    }
+    h->seed_alpha = coef->alpha_a; h->seed_sigma = coef->sigma_a; h->seed_feat_norm = feat_norm_constant;
+    h->seed_armed = true;
     return PF_OK;
 }
 
@@ -3188,6 +3257,7 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
                            const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, const int32_t* host_restr_ptr,
                            const int32_t* host_restr_kind, const int32_t* host_restr_center, const float* host_restr_p,
                            const float* host_restr_r, const float* host_restr_w, float guide_scale, float guide_clip, pf_stream stream) {
+    const bool seeded = take_seed(h);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_noise0) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null noise");
@@ -3215,7 +3285,7 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     const size_t gwords = nf1 * (12 + nh) + (size_t)h->B * 4;
     if ((rc = grow_run_scratch(h, &h->d_guide, &h->guide_capacity, gwords * 4, gwords * 4, s)) != PF_OK) return rc;
     if (!h->restr_ev) PF_HIP(h, hipEventCreateWithFlags(&h->restr_ev, hipEventDisableTiming));
-    rc = pf_sample_begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, stream);
+    rc = begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, seeded, stream);
     if (rc) return rc;
     {
         int32_t* st = (int32_t*)h->restr_stage;

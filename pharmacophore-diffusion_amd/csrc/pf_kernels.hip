@@ -2165,6 +2165,123 @@ __global__ __launch_bounds__(256) void k_step_build_renoise(const StepParams sp,
     __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
     build_body(bp, blockIdx.x);
 }
+// ---------------------------------------------------------------------------------------------
+// Seeded begin (pf_sample_seed_next): in place of "state := noise0", every center of graph g becomes the caller's seed noised
+// forward to level a, z_a = alpha_a * seed + sigma_a * noise0 -- pf_pin_value's arithmetic with every center flagged 3.  Seed
+// positions are in the caller's frame, so D[g] is reduced first as pinned_update_body does (wave 0, k_segment_mean's order);
+// then the COM of all centers is removed from centers and protein in step_update_body's reduction order.  renoise_body's
+// form: after the graph's four pointers every row the thread needs -- its center's seed and noise rows, its first protein row
+// (wave 0's also serve the reduction), the graph's c_init -- is requested before the first wait, and the new coordinates stay
+// in registers between the two passes.  The state's own rows are not read: whatever the previous run left in them is dead.
+// The feature rows also go to the center-hoist snapshot (h_snap_out) the first step's hoist workgroups read.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void seed_body(const StepParams& p, const SeedParams& q, const int g) {
+    __shared__ float com[3];
+    __shared__ float red[4][3];
+    __shared__ float dfr[3];                            // D[g]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
+    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
+    const int fa = f0 + tid, ia = p0 + tid;            // the thread's first center and first atom
+    const bool own_f = fa < f1, own_i = ia < p1;
+    float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (own_i) pa = p.xn[ia];                           // wave 0: the reduction's first row; shifted behind the third barrier
+    float ci[3] = {0.f, 0.f, 0.f};
+    if (tid == 0) for (int c = 0; c < 3; ++c) ci[c] = q.com_init[3 * g + c];
+    float sv[3] = {0.f, 0.f, 0.f}, nx[3] = {0.f, 0.f, 0.f};
+    float hv[8], nv[8];                                 // the first eight features (pharm_nf is 6 in every shipped configuration)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { hv[j] = 0.f; nv[j] = 0.f; }
+    if (own_f) {
+        const float* __restrict__ nz = p.noise + (size_t)fa * (3 + p.nf);
+        const float* __restrict__ sh = q.seed_h + (size_t)fa * p.nf;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { sv[c] = q.seed_x[(size_t)fa * 3 + c]; nx[c] = nz[c]; }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) if (j < p.nf) { hv[j] = sh[j]; nv[j] = nz[3 + j]; }
+    }
+    {   // every row is requested before the first wait (an empty asm the compiler cannot move the loads across, as in pf_stepbuild.h)
+        float pin = ((sv[0] + sv[1]) + (sv[2] + nx[0])) + (nx[1] + nx[2]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pin += hv[j] + nv[j];
+        asm volatile("" :: "v"(pin), "v"(pa.x), "v"((ci[0] + ci[1]) + ci[2]) : "memory");
+    }
+    if (wave == 0) {
+        float ax = 0.f, ay = 0.f, az = 0.f;
+        if (own_i) { ax += pa.x; ay += pa.y; az += pa.z; }
+        for (int i = ia + 64; i < p1; i += 64) { const float4 x = p.xn[i]; ax += x.x; ay += x.y; az += x.z; }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o); }
+        if (lane == 0) {
+            const float n = (float)max(p1 - p0, 1);
+            dfr[0] = ci[0] - ax / n; dfr[1] = ci[1] - ay / n; dfr[2] = ci[2] - az / n;
+        }
+    }
+    __syncthreads();                                    // (the protein rows are not written before the third barrier below)
+    float m[3] = {0.f, 0.f, 0.f};
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    if (own_f) {
+        const float* __restrict__ nz = p.noise + (size_t)fa * (3 + p.nf);
+        const float* __restrict__ sh = q.seed_h + (size_t)fa * p.nf;
+        float* __restrict__ hr = p.pharm_h + (size_t)fa * p.nf;
+        float* __restrict__ hs = p.h_snap_out ? p.h_snap_out + (size_t)fa * p.nf : nullptr;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) if (j < p.nf) {
+            const float hn = pf_pin_value(hv[j] / q.feat_norm, nv[j], q.alpha_a, q.sigma_a);
+            hr[j] = hn;
+            if (hs) hs[j] = hn;
+        }
+        for (int k = 8; k < p.nf; ++k) {
+            const float hn = pf_pin_value(sh[k] / q.feat_norm, nz[3 + k], q.alpha_a, q.sigma_a);
+            hr[k] = hn;
+            if (hs) hs[k] = hn;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m[c] = pf_pin_value(sv[c] - dfr[c], nx[c], q.alpha_a, q.sigma_a);
+        sx += m[0]; sy += m[1]; sz += m[2];
+    }
+    for (int f = fa + 256; f < f1; f += 256) {          // more than 256 centers in the graph: through memory, as step_update_body does
+        const float* nz = p.noise + (size_t)f * (3 + p.nf);
+        float w[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) w[c] = pf_pin_value(q.seed_x[(size_t)f * 3 + c] - dfr[c], nz[c], q.alpha_a, q.sigma_a);
+        p.xn[p.Np_tot + f] = make_float4(w[0], w[1], w[2], 0.f);
+        sx += w[0]; sy += w[1]; sz += w[2];
+        for (int k = 0; k < p.nf; ++k) {
+            const float hn = pf_pin_value(q.seed_h[(size_t)f * p.nf + k] / q.feat_norm, nz[3 + k], q.alpha_a, q.sigma_a);
+            p.pharm_h[(size_t)f * p.nf + k] = hn;
+            if (p.h_snap_out) p.h_snap_out[(size_t)f * p.nf + k] = hn;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
+    __syncthreads();
+    if (tid == 0) {
+        const float n = (float)max(f1 - f0, 1);
+        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
+    }
+    __syncthreads();
+    const float cx = com[0], cy = com[1], cz = com[2];
+    if (own_f) p.xn[p.Np_tot + fa] = make_float4(m[0] - cx, m[1] - cy, m[2] - cz, 0.f);
+    for (int f = fa + 256; f < f1; f += 256) {
+        float4 x = p.xn[p.Np_tot + f];
+        x.x -= cx; x.y -= cy; x.z -= cz;
+        p.xn[p.Np_tot + f] = x;
+    }
+    if (own_i) { pa.x -= cx; pa.y -= cy; pa.z -= cz; p.xn[ia] = pa; }
+    for (int i = ia + 256; i < p1; i += 256) {
+        float4 x = p.xn[i];
+        x.x -= cx; x.y -= cy; x.z -= cz;
+        p.xn[i] = x;
+    }
+}
+__global__ __launch_bounds__(256) void k_step_update_seed(const StepParams p, const SeedParams q) { seed_body(p, q, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_step_build_seed(const StepParams sp, const SeedParams q, const BuildParams bp) {
+    seed_body(sp, q, blockIdx.x);
+    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
+    build_body(bp, blockIdx.x);
+}
 // the given values back, bit for bit (pf_sample_end and the last trajectory frame of a pinned run); out_x / out_h may be NULL
 __global__ void k_pin_restore(const int* __restrict__ flags, const float* __restrict__ pin_x, const float* __restrict__ pin_h,
                               const int n, const int nf, float* __restrict__ out_x, float* __restrict__ out_h) {
@@ -2358,6 +2475,14 @@ void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const 
 void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s) {
     if (p->B == 0) return;
     hipLaunchKernelGGL(k_step_update_renoise, dim3(p->B), dim3(256), 0, s, *p, *r);
+}
+void pfk_step_build_seed(const StepParams* sp, const SeedParams* q, const BuildParams* bp, hipStream_t s) {
+    if (sp->B == 0) return;
+    hipLaunchKernelGGL(k_step_build_seed, dim3(sp->B), dim3(256), 0, s, *sp, *q, *bp);
+}
+void pfk_step_update_seed(const StepParams* p, const SeedParams* q, hipStream_t s) {
+    if (p->B == 0) return;
+    hipLaunchKernelGGL(k_step_update_seed, dim3(p->B), dim3(256), 0, s, *p, *q);
 }
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s) {
     if (n == 0 || (!out_x && !out_h)) return;

@@ -448,9 +448,33 @@ class PfEngine:
         rs = self._restraints(restraints) if restraints is not None else ()
         return tuple(_dptr(t) for t in fl), tuple(a.ctypes.data for a in rs), fl + rs
 
+    @staticmethod
+    def seed_coef_struct(seed_coef):
+        """A PfSeedCoef from schedule.seed_coefficients' dict, an (alpha_a, sigma_a) pair or a PfSeedCoef."""
+        if isinstance(seed_coef, L.PfSeedCoef):
+            return seed_coef
+        if isinstance(seed_coef, dict):
+            seed_coef = (seed_coef["alpha_a"], seed_coef["sigma_a"])
+        a, sg = seed_coef
+        return L.PfSeedCoef(float(a), float(sg))
+
+    def seed_next(self, seed_x, seed_h, seed_coef, feat_norm_constant=1.0):
+        """Arms the next begin on this engine -- sample_begin or sample, of any run kind -- with a seed (pf_sample_seed_next): the
+        run starts from seed_x [Nf, 3] (caller's frame) / seed_h [Nf, pharm_nf] (raw rows, divided by feat_norm_constant) noised
+        to the level of seed_coef (schedule.seed_coefficients) and makes only that level's steps.  That begin consumes the seed,
+        accepted or not; a set_batch in between discards it."""
+        sx, sh = _f32(seed_x, self.device), _f32(seed_h, self.device)
+        if sx.shape != (self.Nf, 3) or sh.shape != (self.Nf, self.pharm_nf):
+            raise ValueError(f"a seed is (positions [{self.Nf}, 3], feature rows [{self.Nf}, {self.pharm_nf}])")
+        coef = self.seed_coef_struct(seed_coef)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_sample_seed_next(self._h, ctypes.byref(coef), _dptr(sx), _dptr(sh), float(feat_norm_constant),
+                                                  _stream_ptr()), "pf_sample_seed_next")
+
     def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0, restraints=None, guide_scale=1.0,
-                     guide_clip=0.0):
-        """pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
+                     guide_clip=0.0, seed=None):
+        """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the begin.
+        pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
         denoise_step(..., pin_coef=...); feat_norm_constant is what the given feature rows are divided by.
         restraints (one list or None per graph, see _restraints): a guided run (pf_sample_begin_guided) -- its steps are
         guided_step; the caller has selected the wide training family (set_train_family('wide')); pins are optional."""
@@ -458,6 +482,8 @@ class PfEngine:
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         self._keep = [nz, com]
         pin, restr, _alive = self._run_inputs(pins, restraints)
+        if seed is not None:
+            self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
         with torch.cuda.device(self.device):
             if restraints is not None:
                 self._ck(self.lib.pf_sample_begin_guided(self._h, _dptr(com), _dptr(nz), *pin, float(feat_norm_constant), *restr,
@@ -536,8 +562,10 @@ class PfEngine:
 
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
                feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None, restraints=None,
-               guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False):
-        """pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned.
+               guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False, seed=None):
+        """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the run -- n_steps is
+        then the seed's level a, and coef_arr (and the other per-step arrays) hold the entries of s = a-1 .. 0.
+        pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned.
         plan = (op_arr, renoise_arr) (plan_arrays; n_steps is then the number of ops and coef_arr / pin_coef_arr have one entry
         per op): pf_sample_pinned_resampled.
         restraints (one list or None per graph, see _restraints) with pin_coef_arr and guide_coef_arr (guide_coef_array): a guided
@@ -577,6 +605,8 @@ class PfEngine:
         if family != "wide":
             self.set_train_family("wide")
         try:
+            if seed is not None:
+                self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
             with torch.cuda.device(self.device):
                 self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
         finally:

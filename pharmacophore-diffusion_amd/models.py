@@ -30,7 +30,7 @@ from .analysis import SampleAnalyzer, SampledPharmacophore
 from .engine import PfEngine
 from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_graph, get_batch_idxs, unbatch
 from .schedule import (PredefinedNoiseSchedule, alpha as _alpha, guide_coefficients, pin_coefficients, renoise_coefficients, resample_plan,
-                       sigma as _sigma, sigma_and_alpha_t_given_s, step_coefficients)
+                       seed_coefficients, sigma as _sigma, sigma_and_alpha_t_given_s, step_coefficients)
 
 try:  # subclass LightningModule when Lightning is importable (drop-in for train.py / load_from_checkpoint)
     import pytorch_lightning as pl
@@ -767,7 +767,8 @@ class PharmacophoreDiff(_Base):
     @torch.no_grad()
     def sample_given_receptor(self, g, init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
                               noise: torch.Tensor = None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None,
-                              guide_scale: float = 1.0, guide_clip: float = 0.0) -> List[SampledPharmacophore]:
+                              guide_scale: float = 1.0, guide_clip: float = 0.0, seeds=None, seed_level: int = None,
+                              seed_keep=None) -> List[SampledPharmacophore]:
         """Reverse diffusion for a batch of pocket graphs; the whole T-step loop is enqueued on the
         current HIP stream by pf_sample (no host synchronisation inside the loop).
 
@@ -785,11 +786,35 @@ class PharmacophoreDiff(_Base):
         and ``noise`` must then have n_ops + 1 rows.  A graph batch without a flag set ignores both.
 
         ``restraints``: None, or one list (or None) per graph of the batch of (kind, center, point, radius, weight) (see
-        ``sample``): with a restraint in it the run is pf_sample_guided with ``guide_scale`` / ``guide_clip``."""
+        ``sample``): with a restraint in it the run is pf_sample_guided with ``guide_scale`` / ``guide_clip``.
+
+        ``seeds`` with ``seed_level`` a (and optionally ``seed_keep``): a seeded run (pf_sample_seed_next) -- one (x [n,3], types
+        [n]) per graph of the batch, n that graph's number of centers; the run starts from the seeds noised to level a and makes
+        the steps a-1 .. 0, so ``noise`` has a + 1 rows (n_ops + 1 with ``pin_resamples`` > 1, whose plan then starts at a).
+        ``seed_keep``: per graph, the seed centers that stay fixed in position and type (see ``sample``)."""
+        if (seeds is None) != (seed_level is None):
+            raise ValueError("seeds and seed_level go together: a seeded run needs both")
+        if seeds is None and seed_keep is not None:
+            raise ValueError("seed_keep without seeds")
+        if seeds is not None:
+            g = as_pocket_graph(g)
+            self._check_seed_level(seed_level)
+            if g.pharm_pin is not None:
+                raise ValueError("seeds together with pinned centers: use seed_keep")
+            if len(seeds) != g.batch_size or (seed_keep is not None and len(seed_keep) != g.batch_size):
+                raise ValueError(f"seeds (and seed_keep) need one entry per graph of the batch ({g.batch_size})")
+            sizes = (g.pharm_ptr[1:] - g.pharm_ptr[:-1]).tolist()
+            for r, sd in enumerate(seeds):
+                if sd is None:
+                    raise ValueError(f"pocket {r} has no seed: a seeded run needs one seed per pocket")
+            fields = [self._seed_fields(r, sizes[r], seeds[r], None if seed_keep is None else seed_keep[r]) for r in range(g.batch_size)]
+            dev = g.prot_x.device
+            g = dataclasses.replace(g, **{name: torch.cat([f[i] for f in fields]).to(dev)
+                                          for i, name in enumerate(("pharm_pin", "pharm_pin_x", "pharm_pin_h"))})
         return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, init_pharm_com, visualize_trajectory, noise,
                                                                            pin_resamples=pin_resamples, pin_jump=pin_jump,
                                                                            restraints=restraints, guide_scale=guide_scale,
-                                                                           guide_clip=guide_clip)))
+                                                                           guide_clip=guide_clip, seed_level=seed_level)))
 
     def _host_arrays(self, key, build):
         """The ctypes arrays of a run at this model's T (500-1000 structs an array; a plan's, a few thousand): built once per key."""
@@ -798,33 +823,94 @@ class PharmacophoreDiff(_Base):
             self._arrays[key] = build()
         return self._arrays[key]
 
-    def _step_arrays(self, name):
-        """coef / pin / guide: that per-step coefficient array of a run that visits s = T-1 .. 0"""
+    def _step_arrays(self, name, top=None):
+        """coef / pin / guide: that per-step coefficient array of a run that visits s = top-1 .. 0 (top None: T; a seeded run's
+        top is its seed level)"""
         T = self.n_timesteps
         tabs, array = {"coef": (self.step_coefficients, PfEngine.coef_array),
                        "pin": (lambda: pin_coefficients(self.gamma.gamma, T), PfEngine.pin_coef_array),
                        "guide": (lambda: guide_coefficients(self.gamma.gamma, T), PfEngine.guide_coef_array)}[name]
-        return self._host_arrays((name,), lambda: array(tabs(), reversed(range(T))))
+        if top is None or int(top) == T:
+            return self._host_arrays((name,), lambda: array(tabs(), reversed(range(T))))
+        return self._host_arrays((name, int(top)), lambda: array(tabs(), reversed(range(int(top)))))
 
-    def _plan_arrays(self, jump: int, resamples: int):
-        """(n_ops, coef_arr, pin_coef_arr, op_arr, renoise_arr) of a resampled pinned run at this model's T, per (jump, resamples)."""
+    def _plan_arrays(self, jump: int, resamples: int, top=None):
+        """(n_ops, coef_arr, pin_coef_arr, op_arr, renoise_arr) of a resampled pinned run from level ``top`` down (None: this
+        model's T; a seeded run's top is its seed level), per (jump, resamples, top)."""
+        T = self.n_timesteps
+        top = T if top is None else int(top)
+
         def build():
-            T = self.n_timesteps
-            plan = resample_plan(T, jump, resamples)
+            plan = resample_plan(top, jump, resamples)
             pairs = [(op[1], op[2]) for op in plan if op[0] == "renoise"]
             return (len(plan),) + tuple(PfEngine.plan_arrays(plan, self.step_coefficients(), pin_coefficients(self.gamma.gamma, T),
                                                              renoise_coefficients(self.gamma.gamma, T, pairs)))
-        return self._host_arrays(("plan", int(jump), int(resamples)), build)
+        return self._host_arrays(("plan", int(jump), int(resamples), top), build)
+
+    def _check_seed_level(self, seed_level):
+        if not 1 <= int(seed_level) <= self.n_timesteps:
+            raise ValueError(f"seed_level must satisfy 1 <= seed_level <= {self.n_timesteps}, got {seed_level}")
+        return int(seed_level)
+
+    def _seed_fields(self, r, n, seed, keep):
+        """The pin fields that carry one graph's seed: (flags [n], x [n,3], one-hot rows [n,nf]) from seed = (x [n,3], types [n])
+        and keep = the seed center indices that stay fixed (flag 3; None: none).  ``r`` names the pocket in errors."""
+        x, types = seed
+        x = torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3)
+        types = torch.as_tensor(types, dtype=torch.int64).reshape(-1)
+        k = int(x.shape[0])
+        if types.numel() != k:
+            raise ValueError(f"pocket {r}: the seed has {k} positions and {types.numel()} types")
+        if k != int(n):
+            raise ValueError(f"pocket {r}: the seed has {k} centers but a pharmacophore of {int(n)} was requested "
+                             "(seeds of a different size than the sample are not supported)")
+        if k and (int(types.min()) < 0 or int(types.max()) >= self.n_pharm_feats):
+            raise ValueError(f"pocket {r}: seed types must be in 0..{self.n_pharm_feats - 1}")
+        flags = torch.zeros(k, dtype=torch.int32)
+        for i in (keep or []):
+            if not 0 <= int(i) < k:
+                raise ValueError(f"pocket {r}: seed_keep names center {int(i)} of a seed of {k}")
+            flags[int(i)] = 3
+        return flags, x, F.one_hot(types, self.n_pharm_feats).float()
+
+    def _with_seeds(self, ref_graphs, n_pharms, seeds, seed_keep):
+        """sample(seeds=...): per pocket (x [n,3] in the pocket's frame, types [n] type indices).  The seed rides on the pin
+        fields, which then hold values for ALL centers; seed_keep becomes the flags (3 for kept centers, 0 for the rest)."""
+        if len(seeds) != len(ref_graphs):
+            raise ValueError(f"seeds lists {len(seeds)} entries for {len(ref_graphs)} pockets")
+        if seed_keep is not None and len(seed_keep) != len(ref_graphs):
+            raise ValueError(f"seed_keep lists {len(seed_keep)} entries for {len(ref_graphs)} pockets")
+        for r, sd in enumerate(seeds):
+            if sd is None:
+                raise ValueError(f"pocket {r} has no seed: a seeded run needs one seed per pocket")
+        out = []
+        for r, (g, sd) in enumerate(zip(ref_graphs, seeds)):
+            k = int(torch.as_tensor(sd[0]).reshape(-1, 3).shape[0])
+            other = [int(n) for n in n_pharms[r] if int(n) != k]
+            if other:
+                raise ValueError(f"pocket {r}: the seed has {k} centers but sizes {other} were requested")
+            flags, x, h = self._seed_fields(r, k, sd, None if seed_keep is None else seed_keep[r])
+            dev = g.prot_x.device
+            out.append(dataclasses.replace(g, pharm_pin=flags.to(dev), pharm_pin_x=x.to(dev), pharm_pin_h=h.to(dev)))
+        return out
 
     def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0,
-                        pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0, guide_clip: float = 0.0):
+                        pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0, guide_clip: float = 0.0,
+                        seed_level: int = None):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
         current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  ``restraints``: None or one
         list (or None) per graph of the batch; a batch takes the guided path (pf_sample_guided) only when one of them holds a
-        restraint, as with pin flags.  A batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled."""
+        restraint, as with pin flags.  A batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled.
+        ``seed_level`` a: a seeded run -- the graph's pharm_pin_x / pharm_pin_h hold the seed of EVERY center (the flags say which
+        of them stay fixed), the run starts at level a (pf_sample_seed_next) and its arrays hold the steps a-1 .. 0."""
         g = as_pocket_graph(g)
         dev = self.device
-        n_ops, Nf, nf = self.n_timesteps, g.num_nodes("pharm"), self.n_pharm_feats
+        top = None
+        if seed_level is not None:
+            top = self._check_seed_level(seed_level)
+            if g.pharm_pin_x is None or g.pharm_pin_h is None:
+                raise ValueError("a seeded run needs the seed on the graph's pharm_pin_x / pharm_pin_h")
+        n_ops, Nf, nf = (self.n_timesteps if top is None else top), g.num_nodes("pharm"), self.n_pharm_feats
         if pin_resamples < 1 or pin_jump < 1:
             raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
         has_pins = g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
@@ -833,21 +919,25 @@ class PharmacophoreDiff(_Base):
             raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
         kw = {}
         if has_pins and pin_resamples > 1:
-            n_ops, arr, parr, op_arr, re_arr = self._plan_arrays(pin_jump, pin_resamples)
+            n_ops, arr, parr, op_arr, re_arr = self._plan_arrays(pin_jump, pin_resamples, top)
             if noise is not None and noise.shape[0] != n_ops + 1:
                 raise ValueError(f"a resampled pinned run of {n_ops} ops (T = {self.n_timesteps}, jump {pin_jump}, resamples {pin_resamples}) "
                                  f"needs {n_ops + 1} noise rows, got {noise.shape[0]}")
             kw = {"pin_coef_arr": parr, "plan": (op_arr, re_arr)}
         else:
-            arr = self._step_arrays("coef")
+            arr = self._step_arrays("coef", top)
             if guided or has_pins:
-                kw = {"pin_coef_arr": self._step_arrays("pin")}
+                kw = {"pin_coef_arr": self._step_arrays("pin", top)}
         if kw and g.pharm_pin is not None:
             kw["pins"] = (g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h)
+        if top is not None:
+            if noise is not None and noise.shape[0] != n_ops + 1:
+                raise ValueError(f"a seeded run of {n_ops} ops (seed level {top}) needs {n_ops + 1} noise rows, got {noise.shape[0]}")
+            kw["seed"] = (g.pharm_pin_x, g.pharm_pin_h, seed_coefficients(self.gamma.gamma, self.n_timesteps, top))
         if guided:
             if len(restraints) != g.batch_size:
                 raise ValueError(f"restraints lists {len(restraints)} entries for a batch of {g.batch_size} graphs")
-            kw.update(restraints=restraints, guide_coef_arr=self._step_arrays("guide"), guide_scale=float(guide_scale),
+            kw.update(restraints=restraints, guide_coef_arr=self._step_arrays("guide", top), guide_scale=float(guide_scale),
                       guide_clip=float(guide_clip))
         if noise is None:
             noise = torch.randn(n_ops + 1, Nf, 3 + nf, device=dev)
@@ -928,7 +1018,7 @@ class PharmacophoreDiff(_Base):
                init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
                rank: int = 0, world_size: int = 1, noise=None, lanes: int = None,
                pinned=None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0,
-               guide_clip: float = 0.0) -> List[List[SampledPharmacophore]]:
+               guide_clip: float = 0.0, seeds=None, seed_level: int = None, seed_keep=None) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -960,6 +1050,14 @@ class PharmacophoreDiff(_Base):
         input gradients and cost several times a default step.  Batches without one run the default path.
         Composes with ``pinned``; together with ``pin_resamples`` > 1 it is a ValueError.
 
+        ``seeds`` with ``seed_level`` a, 1 <= a <= T: variations of given pharmacophores (partial diffusion, pf_sample_seed_next)
+        -- one (x [n,3], types [n]) per pocket, every pocket must have one and every requested size of it must equal n.  Each
+        seed is noised forward to level a and only the steps a-1 .. 0 are run: a small a gives close analogues, a large a loose
+        ones, and the run costs a / T of a default run.  Its noise has a + 1 rows.  Copies of a pocket share its seed.
+        ``seed_keep``: None, or per pocket a list of seed center indices that stay fixed in position and type -- the run is then
+        a pinned run with these centers flagged, and they come back bit for bit.  With ``pin_resamples`` > 1 such a run follows
+        schedule.resample_plan(a, j, r); with ``restraints`` it is guided.  Together with ``pinned`` it is a ValueError.
+
         ``lanes`` (default ``self.sample_lanes``; None = 2, or 4 when the batches hold at most 32 graphs): batches in flight at
         once, each on its own HIP stream and handle.  Four of
         the five launches of a batched step occupy part of the chip, so independent batches overlap (2 lanes: +16 % at
@@ -985,8 +1083,18 @@ class PharmacophoreDiff(_Base):
                         small = [int(n) for n in n_pharms[r] if int(n) <= int(c)]
                         if small:
                             raise ValueError(f"pocket {r}: a restraint names center {int(c)} but sizes {small} were requested")
+        if (seeds is None) != (seed_level is None):
+            raise ValueError("seeds and seed_level go together: a seeded run needs both")
+        if seeds is None and seed_keep is not None:
+            raise ValueError("seed_keep without seeds")
+        if seeds is not None and pinned is not None:
+            raise ValueError("seeds together with pinned: use seed_keep")
         if pinned is not None:
             ref_graphs = self._with_pins(ref_graphs, n_pharms, pinned)
+        top = None
+        if seeds is not None:
+            top = self._check_seed_level(seed_level)
+            ref_graphs = self._with_seeds(ref_graphs, n_pharms, seeds, seed_keep)
         if init_pharm_com is None:
             init_pharm_com = torch.stack([g.prot_x.mean(dim=0) for g in ref_graphs], dim=0)
         # the requested graphs in pocket order: (pocket, number of centers); the copies themselves are made batch by batch
@@ -1041,9 +1149,9 @@ class PharmacophoreDiff(_Base):
             init_coms = coms_dev[idx[0]:idx[-1] + 1]
             lane = k % n_lanes
             with torch.cuda.stream(streams[lane]):
-                rows = T + 1
+                rows = (T if top is None else top) + 1
                 if pin_resamples > 1 and batch_g.pharm_pin is not None and bool((batch_g.pharm_pin != 0).any()):
-                    rows = self._plan_arrays(pin_jump, pin_resamples)[0] + 1
+                    rows = self._plan_arrays(pin_jump, pin_resamples, top)[0] + 1
                 if noise is None:
                     gen = torch.Generator(device=self.device).manual_seed(base_seed + bi)
                     nz = torch.randn(rows, batch_g.num_nodes("pharm"), 3 + nf, device=self.device, generator=gen)
@@ -1053,7 +1161,7 @@ class PharmacophoreDiff(_Base):
                 batch_r = [restraints[graph_ref_idx[i]] for i in idx] if restraints is not None else None
                 enq = self._sample_enqueue(batch_g, init_coms, visualize_trajectory, nz, lane=lane,
                                            pin_resamples=pin_resamples, pin_jump=pin_jump, restraints=batch_r,
-                                           guide_scale=guide_scale, guide_clip=guide_clip)
+                                           guide_scale=guide_scale, guide_clip=guide_clip, seed_level=top)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on

@@ -108,6 +108,19 @@ def guide_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, t
     return {"alpha_t": alpha(g_t), "sigma_t": sigma(g_t)}
 
 
+def seed_coefficients(gamma_table: torch.Tensor, timesteps: int, level: int) -> Dict[str, torch.Tensor]:
+    """Noise level a = ``level`` of a seeded run's first state, fp32 on the host: alpha_a = alpha(gamma(a / T)) and sigma_a =
+    sigma(gamma(a / T)) -- what a seeded begin noises the given pharmacophore with, z_a = alpha_a seed + sigma_a noise0
+    (pf_sample_seed_next, pf_seed_coef).  The run then makes the steps s = a-1 .. 0."""
+    level = int(level)
+    if not 1 <= level <= timesteps:
+        raise ValueError(f"a seed level must satisfy 1 <= level <= {timesteps}, got {level}")
+    g = gamma_table.detach().float().cpu()
+    a = torch.tensor(level).float() / timesteps
+    g_a = g[torch.round(a * timesteps).long()]
+    return {"alpha_a": alpha(g_a), "sigma_a": sigma(g_a)}
+
+
 def resample_plan(timesteps: int, jump: int, resamples: int):
     """The op list of a pinned run with resampling jumps (include/pfdyn.h, "pinned runs with resampling jumps"): levels run
     T -> 0 in segments (a, b) of length ``jump`` (the last one possibly shorter); every segment is denoised, D(a-1) ... D(b), and
