@@ -42,6 +42,10 @@ _FLAGS = [
     ('--seed_pharmacophore', dict(type=Path, default=None, help='seeded sampling: one xyz frame in the pharms.xyz format; every sample is a variation of it (the frame is noised forward to --seed_level and only the steps below that level are run)')),
     ('--seed_level', dict(type=int, default=None, help='with --seed_pharmacophore: the level 1..T the seed is noised to; small: close analogues, large: loose ones')),
     ('--seed_keep', dict(type=str, default=None, help='with --seed_pharmacophore: comma-separated indices of seed centers that stay fixed in position and type, e.g. 0,2')),
+    ('--score_samples', dict(type=int, default=None, help='score the drawn samples with the model at this many noise levels (stratified over 1..T) and write scores.tsv, one line per sample in the order of pharms.xyz; lower per-center score is better')),
+    ('--keep_best', dict(type=int, default=None, help='with --score_samples: write only this many samples, best (lowest per-center score) first')),
+    ('--score_pharmacophores', dict(type=Path, default=None, help='no sampling: score every frame of this file (pharms.xyz format) against the pocket and write scores.tsv; --score_samples gives the number of levels (default: every level); with the --seed, --score_samples, --score_weighting and --max_batch_size of the run that wrote the file, and its frames in their order, this reproduces that run\'s scores.tsv (the noise of a score is drawn per device batch)')),
+    ('--score_weighting', dict(choices=['uniform', 'vlb'], default=None, help='weights of the levels in a score: uniform (default; the per-graph training loss) or vlb (the diffusion terms of the variational bound)')),
     ('--metrics', dict(action='store_true', help='print the validity of the samples against receptor pharmacophore features')),
 ]
 
@@ -95,6 +99,34 @@ def parse_arguments(argv=None):
                 parser.error(f'--seed_keep {bad} outside the {n_seed} centers of --seed_pharmacophore')
     a.pin_resamples = 1 if a.pin_resamples is None else a.pin_resamples
     a.pin_jump = 10 if a.pin_jump is None else a.pin_jump
+    for flag in ('score_samples', 'keep_best'):
+        v = getattr(a, flag)
+        if v is not None and v < 1:
+            parser.error(f'--{flag} must be at least 1, got {v}')
+    if a.keep_best is not None and a.score_samples is None:
+        parser.error('--keep_best needs --score_samples')
+    if a.keep_best is not None and a.score_pharmacophores is not None:
+        parser.error('--keep_best together with --score_pharmacophores: nothing is sampled, scores.tsv lists every frame')
+    if a.keep_best is not None and a.visualize_trajectory:
+        parser.error('--keep_best together with --visualize_trajectory: trajectories are written per sample index')
+    if a.score_weighting is not None and a.score_samples is None and a.score_pharmacophores is None:
+        parser.error('--score_weighting needs --score_samples or --score_pharmacophores')
+    a.score_weighting = 'uniform' if a.score_weighting is None else a.score_weighting
+    a.score_frames = None
+    if a.score_pharmacophores is not None:
+        given = [f for f in ('--samples_per_pocket', '--pharm_sizes', '--visualize_trajectory', '--pinned_centers', '--restraints',
+                             '--seed_pharmacophore', '--use_ref_lig_com', '--metrics')
+                 if getattr(a, f[2:]) not in (parser.get_default(f[2:]), None)]
+        if given:
+            parser.error(f'--score_pharmacophores samples nothing: {" ".join(given)} make no sense with it')
+        from pharmacoforge_amd.analysis import read_pharmacophores
+        try:
+            a.score_frames = read_pharmacophores(a.score_pharmacophores)
+        except (OSError, ValueError) as e:
+            parser.error(f'--score_pharmacophores: {e}')
+        big = [i for i, (x, _) in enumerate(a.score_frames) if len(x) > 64]
+        if big:
+            parser.error(f'--score_pharmacophores: frame(s) {big} have more than 64 centers')
     problems = []
     if (a.ckpt is None) == (a.model_dir is None):
         problems.append('give exactly one of --ckpt and --model_dir')
@@ -155,6 +187,25 @@ def load_model(pfa, ckpt, config, device):
     return model.to(device).eval()
 
 
+def score_frames(pfa, model, pocket, frames, args):
+    """PharmacophoreScore of every (positions, types) frame against the pocket: --score_samples levels stratified over 1..T (every
+    level without it), --score_weighting, noise seeded by --seed."""
+    T = model.n_timesteps
+    k = T if args.score_samples is None else min(args.score_samples, T)
+    with torch.no_grad():
+        return model.score([pocket], [frames], levels=pfa.schedule.score_levels(T, k), weighting=args.score_weighting, seed=args.seed,
+                           max_batch_size=args.max_batch_size)[0]
+
+
+def write_scores(path, indices, scores):
+    """scores.tsv: one line per pharmacophore, in the order of pharms.xyz (or of the scored file)"""
+    lines = ['\t'.join(('index', 'centers', 'total', 'per_center', 'pos', 'feat', 'position_error', 'type_accuracy'))]
+    for i, s in zip(indices, scores):
+        lines.append('\t'.join((str(i), str(s.n_centers), f'{s.total:.6g}', f'{s.per_center:.6g}', f'{s.pos:.6g}', f'{s.feat:.6g}',
+                                f'{s.position_error:.6g}', f'{s.type_accuracy:.4f}')))
+    Path(path).write_text('\n'.join(lines) + '\n')
+
+
 def main(argv=None):
     import pharmacoforge_amd as pfa
     from pharmacoforge_amd.pocket_io import get_prot_atom_ph_type_maps, process_ligand_and_pocket
@@ -179,6 +230,12 @@ def main(argv=None):
                                        residue_list=args.residue_list, prot_element_map=prot_element_map,
                                        graph_cutoffs=config['graph']['graph_cutoffs'],
                                        pocket_cutoff=config['dataset']['pocket_cutoff'], remove_hydrogen=True).to(device)
+
+    if args.score_frames is not None:            # no sampling: the frames of the file against this pocket
+        scores = score_frames(pfa, model, pocket, args.score_frames, args)
+        write_scores(pocket_dir / 'scores.tsv', range(len(scores)), scores)
+        print(f'{name}: {len(scores)} pharmacophores scored')
+        return
 
     k_pin = 0
     if args.pinned is not None:              # the pinned centers ride on the pocket graph: the first k centers of every copy
@@ -223,6 +280,16 @@ def main(argv=None):
     for src in (args.receptor_file, args.ref_ligand_file):
         if src is not None:
             shutil.copy(src, ref_dir / src.name)
+    if args.score_samples is not None:
+        # the scores describe the frames as pharms.xyz holds them (three decimals, argmax types): scoring that file again
+        # (--score_pharmacophores) with the same seed and levels gives the same numbers
+        frames = [ph.as_written() for ph in pharms]
+        scores = score_frames(pfa, model, pocket, frames, args)
+        order = list(range(len(pharms)))
+        if args.keep_best is not None:
+            order = sorted(order, key=lambda i: (scores[i].per_center, i))[:args.keep_best]
+        pharms, scores = [pharms[i] for i in order], [scores[i] for i in order]
+        write_scores(pocket_dir / 'scores.tsv', range(len(scores)), scores)
     if args.visualize_trajectory:
         for i, ph in enumerate(pharms):
             ph.traj_to_xyz(pocket_dir / f'pharm_{i}_traj.xyz')

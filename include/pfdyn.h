@@ -350,6 +350,48 @@ typedef struct pf_seed_coef { float alpha_a; float sigma_a; } pf_seed_coef;   /*
 int pf_sample_seed_next(pf_handle* h, const pf_seed_coef* coef, const float* dev_seed_x /*[Nf,3], caller's frame*/,
                         const float* dev_seed_h /*[Nf,pharm_nf], raw rows*/, float feat_norm_constant, pf_stream stream);
 
+/* -- scoring: how plausible are GIVEN pharmacophores for the bound pockets (the per-level terms of PharmacophoreDiff.forward,
+ *    pharmacodiff.py:162-243, per graph and at levels the caller chooses; the reference reduces them to batch means) -----------
+ * The candidates are the centers of the bound batch: graph g's candidate has pharm_ptr[g+1] - pharm_ptr[g] centers, positions
+ * dev_pharm_x0 in the CALLER's frame (the frame of the bound pocket coordinates), rows dev_pharm_h0 the raw type one-hots
+ * (divided by feat_norm inside).  For every level l = 0 .. n_levels-1, in order, with t = host_levels[l].t_int (0 <= t <= T):
+ *   prepare   per graph the COM of the clean centers is taken off the centers and off the BOUND pocket coordinates (:176-183; never
+ *             off what the level before left), z_t = alpha[t] x0 + sigma[t] eps for coordinates and features (:186-197; one rounding
+ *             per operation) with eps = row l of dev_noise in the sampler's layout, and the COM of the noised centers is removed
+ *             from centers and pocket when remove_com (:199-205)
+ *   dynamics  the inference forward at the uniform timestep t / T -- the handle's inference family at every supported width, conv
+ *             layer 0's per-timestep tables of all levels made up front (64 timesteps per launch), a pocket-group claim of the
+ *             bind honoured (copies of a pocket share conv layer 0's protein->protein messages at each level).  No training
+ *             workspace and no pf_train_set_family
+ *   evaluate  per graph, summed over its centers f in a fixed order (the same bits on every run), the four forms of
+ *             pf_train_loss_forward_ep WITHOUT any weight or division:
+ *               pos   sum |eps_x - dyn_x|^2 (:217), or sum |dyn_x + COM2 - x0c|^2 with endpoint_param_coord (:210-215)
+ *               feat  sum |eps_h - dyn_h|^2 (:208), or sum cross_entropy(dyn_h, argmax h0) with endpoint_param_feat (:204-206)
+ *               err   sum |x0_pred - x0c|^2 (:219, :235), x0c the clean center shifted by the first COM only
+ *               hits  centers whose predicted type (first maximum; :209, :237) is the clean type
+ *             dev_terms[l][g] = {pos, feat, err, hits} (when given) and
+ *             dev_score[g]    = {sum_l w_pos[l] * pos, sum_l w_feat[l] * feat}, added in level order; the first level STORES, so
+ *             dev_score need not be initialised.  Nothing is divided by the number of centers: the caller normalises.
+ * The whole call is enqueued on `stream` without host synchronisation, like pf_sample; a level costs the forward's launches plus
+ * two small ones (k_score_prepare, k_score_eval: one workgroup per graph).  Everything is checked before anything is launched:
+ * PF_ERR_ARG for a null argument (dev_terms may be NULL), n_levels < 1, n_timesteps < 1, a t_int outside 0..T, feat_norm <= 0, a
+ * batch without centers, pharm_nf > 8, a false pocket-group claim about device rows (its verdict is waited for here, as the first
+ * sharing call of the batch would); PF_ERR_STATE without a batch and while a sampling run holds the handle -- from any
+ * pf_sample_begin* (or whole-loop entry) until the next bind: the run's state is the handle's state, and the run goes on
+ * unharmed after the refusal.
+ * What the call leaves: the sampling state machine as it was (no run; a seed armed with pf_sample_seed_next stays armed), and the
+ * coordinates held by the handle are the bound ones again, so a sampling run made afterwards gives the bits it gives without the
+ * call in front.  A kept pf_train_forward / pf_train_loss_forward does NOT survive (unlike behind pf_dynamics_forward, which
+ * leaves the flag alone): the levels overwrite the coordinates and dynamic edges a backward would read, so a backward call
+ * afterwards is PF_ERR_STATE.  The score is no likelihood: it has no L_0 term, no prior term and no size prior -- totals compare
+ * candidates of one size, across sizes divide by the number of centers. */
+typedef struct pf_score_level { int32_t t_int; float w_pos; float w_feat; } pf_score_level;   /* host */
+int pf_score(pf_handle* h, const float* dev_pharm_x0 /*[Nf,3], caller's frame*/, const float* dev_pharm_h0 /*[Nf,pharm_nf] raw one-hots*/,
+             int32_t n_levels, const pf_score_level* host_levels, const float* dev_noise /*[n_levels, Nf, 3+pharm_nf], x columns first*/,
+             const float* dev_alpha /*[T+1]*/, const float* dev_sigma /*[T+1]*/, int32_t n_timesteps, float feat_norm, int32_t remove_com,
+             int32_t endpoint_param_coord, int32_t endpoint_param_feat,
+             float* dev_score /*[B,2]*/, float* dev_terms /*[n_levels,B,4] or NULL*/, pf_stream stream);
+
 /* -- training step: gradients of the dynamics (autograd through PharmRecDynamicsGVP.forward, ------
  *    dynamics_gvp.py:131-185, as used by PharmacophoreDiff.forward / training_step, pharmacodiff.py:162-276)
  * Parameters and gradients are exchanged as ONE flat fp32 vector in the reference's state-dict order
@@ -488,7 +530,7 @@ int pf_debug_conv_layer(pf_handle* h, int32_t layer, const float* dev_prot_x, co
 /* per-kernel timing with HIP events recorded on the caller's stream around every launch of the
  * selected kernel classes (bit k of kernel_mask): 0 encode, 1 build_edges (0 and 1 share one launch unless
  * either is being timed), 2 edge_msg (one wave per tile), 3 node_update (one wave per tile), 4 noise_head,
- * 5 step_update, 6 edge_msg_coop, 7 node_update_coop (four waves per tile: launches with few tiles),
+ * 5 step_update (in a pf_score call: its two kernels, k_score_prepare and k_score_eval), 6 edge_msg_coop, 7 node_update_coop (four waves per tile: launches with few tiles),
  * 8 edge_msg_coop of the last conv layer (when n_convs > 1).  pf_profile_read synchronises `stream`, returns the summed device
  * time [ms] and launch count per class since the last read, and resets the counters; pf_profile_enable only changes the
  * mask, so a caller can bracket a subset of its calls (a pair of event records costs ~10 us of stream time). */

@@ -46,6 +46,10 @@ class PfSeedCoef(ctypes.Structure):
     _fields_ = [("alpha_a", ctypes.c_float), ("sigma_a", ctypes.c_float)]
 
 
+class PfScoreLevel(ctypes.Structure):
+    _fields_ = [("t_int", ctypes.c_int32), ("w_pos", ctypes.c_float), ("w_feat", ctypes.c_float)]
+
+
 # every symbol include/pfdyn.h declares: (name, restype, argtypes)
 _P, _I32, _I64, _F = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 SYMBOLS = {
@@ -81,6 +85,7 @@ SYMBOLS = {
     "pf_sample_guided": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PfStepCoef), ctypes.POINTER(PfPinCoef), ctypes.POINTER(PfGuideCoef), _P, _P,
                                         _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "pf_sample_seed_next": (ctypes.c_int, [_P, ctypes.POINTER(PfSeedCoef), _P, _P, _F, _P]),
+    "pf_score": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.POINTER(PfScoreLevel), _P, _P, _P, _I32, _F, _I32, _I32, _I32, _P, _P, _P]),
     "pf_debug_last_guidance": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "pf_dynamics_input_vjp": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "pf_param_count": (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),

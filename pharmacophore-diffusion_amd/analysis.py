@@ -48,6 +48,61 @@ def read_pinned_centers(filename):
     return torch.tensor(pos, dtype=torch.float32), torch.tensor(types, dtype=torch.int64)
 
 
+def read_pharmacophores(filename):
+    """Every frame of a file in the pharms.xyz format (consecutive frames: the center count, then `element x y z` per center;
+    blank lines are ignored) -> [(positions [k,3] fp32, type indices [k])], in file order: pharmacophores to be scored.
+    read_pinned_centers stays the one-frame reader."""
+    lines = [ln.strip() for ln in Path(filename).read_text().splitlines() if ln.strip()]
+    if not lines:
+        raise ValueError(f"{filename}: empty file")
+    frames, i = [], 0
+    while i < len(lines):
+        try:
+            k = int(lines[i])
+        except ValueError:
+            raise ValueError(f"{filename}: frame {len(frames)} must start with its center count, got {lines[i]!r}") from None
+        if k < 1 or i + 1 + k > len(lines):
+            raise ValueError(f"{filename}: frame {len(frames)} announces {k} centers, {len(lines) - i - 1} lines follow")
+        pos, types = [], []
+        for ln in lines[i + 1:i + 1 + k]:
+            tok = ln.split()
+            if len(tok) != 4 or tok[0] not in _XYZ_ELEMENTS:
+                raise ValueError(f"{filename}: bad center line {ln!r} (element x y z, elements {' '.join(_XYZ_ELEMENTS)})")
+            try:
+                pos.append([float(v) for v in tok[1:]])
+            except ValueError:
+                raise ValueError(f"{filename}: bad coordinates in {ln!r}") from None
+            types.append(_XYZ_ELEMENTS.index(tok[0]))
+        frames.append((torch.tensor(pos, dtype=torch.float32), torch.tensor(types, dtype=torch.int64)))
+        i += 1 + k
+    return frames
+
+
+class PharmacophoreScore:
+    """How plausible the trained model finds one pharmacophore for its pocket (PharmacophoreDiff.score, pf_score): the candidate
+    is noised to L levels and the error of the network's prediction at each is a term of the model's variational bound.
+    ``terms`` [L, 4]: per level the sums over the centers of the position term, the feature term, the squared error of the
+    predicted clean centers and the number of centers whose predicted type is the given one.  ``pos`` / ``feat``: the weighted sums
+    of the first two over the levels; ``total`` their sum; ``per_center`` = total / centers -- LOWER IS BETTER.  Totals compare
+    candidates of one size only (there is no size prior in them): across sizes use per_center.  ``position_error`` and
+    ``type_accuracy``: means over levels and centers."""
+    __slots__ = ("n_centers", "levels", "pos", "feat", "total", "per_center", "position_error", "type_accuracy", "terms")
+
+    def __init__(self, n_centers: int, levels, pos: float, feat: float, terms: torch.Tensor):
+        self.n_centers, self.levels = int(n_centers), [int(t) for t in levels]
+        self.pos, self.feat = float(pos), float(feat)
+        self.total = self.pos + self.feat
+        self.per_center = self.total / self.n_centers
+        self.terms = terms
+        denom = float(self.n_centers * max(len(self.levels), 1))
+        self.position_error = float(terms[:, 2].double().sum()) / denom
+        self.type_accuracy = float(terms[:, 3].double().sum()) / denom
+
+    def __repr__(self):
+        return (f"PharmacophoreScore(centers={self.n_centers}, levels={len(self.levels)}, total={self.total:.6g}, "
+                f"per_center={self.per_center:.6g}, position_error={self.position_error:.6g}, type_accuracy={self.type_accuracy:.4f})")
+
+
 def _emit(text: str, filename):
     """Return the text, or write it when a file name is given (the reference's writers do the same)."""
     if filename is None:
@@ -77,6 +132,7 @@ class SampledPharmacophore:
         pin = getattr(g, "pharm_pin", None)
         self.pinned = torch.zeros(self.n_ph_centers, dtype=torch.int32) if pin is None else pin.to("cpu", torch.int32)
         self.pos_frames, self.feat_frames = traj_frames if traj_frames is not None else (None, None)
+        self.score: Optional[PharmacophoreScore] = None  # set by PharmacophoreDiff.sample(..., score_levels=K)
 
     def _names(self, type_indices) -> List[str]:
         return [self.pharm_type_map[k] for k in torch.as_tensor(type_indices).tolist()]
@@ -86,6 +142,13 @@ class SampledPharmacophore:
 
     def to_xyz_file(self, filename: str = None):
         return _emit(self.pharm_to_xyz(self.ph_coords, self.ph_types), filename)
+
+    def as_written(self):
+        """(positions [n,3] fp32, type indices [n]) as to_xyz_file writes them and read_pharmacophores reads them back: three
+        decimals per coordinate, argmax types"""
+        rows = torch.as_tensor(self.ph_coords, dtype=torch.float64).reshape(-1, 3).tolist()
+        return (torch.tensor([[float(f"{v:.3f}") for v in r] for r in rows], dtype=torch.float32).reshape(-1, 3),
+                self.ph_feats_idxs.to(torch.int64).clone())
 
     def traj_to_xyz(self, filename: str = None):
         if self.pos_frames is None or self.feat_frames is None:

@@ -20,6 +20,7 @@
 #include "pf_bind.h"
 #include "pf_pack.h"
 #include "pf_train.h"
+#include "pf_score.h"
 
 using namespace pfpack;
 
@@ -92,6 +93,8 @@ void pfk_n16_split_words(const float* flat, const int4* tab, size_t n, float* pa
 void pfk_pack_gvp(const float* W, const GvpT* g, int n_gvps, float* out_b, float* out_f, const ScaleArgs* sa, hipStream_t s);
 void pfk_loss_prepare(const LossParams* p, hipStream_t s);
 void pfk_loss_eval(const LossParams* p, int ep_coord, int ep_feat, hipStream_t s);
+void pfk_score_prepare(const ScoreParams* p, hipStream_t s);
+void pfk_score_eval(const ScoreParams* p, int ep_coord, int ep_feat, hipStream_t s);
 void pfk_scale_loss(float* gx, int nx, const float* a, const float* a2, float* gh, int nh, const float* b, const float* b2, hipStream_t s);
 void pfk_compact_node_rows(const NodeTile* tiles, int ntiles, const int* dyn_cnt, const int* row_ids, int N, int* list, int cap, int* ucnt,
                            hipStream_t s);
@@ -2350,6 +2353,68 @@ int pf_sample_pinned(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coe
     r.ep_coord = ep_coord; r.ep_feat = ep_feat; r.feat_norm = feat_norm_constant;
     r.x0 = dev_x0; r.h0 = dev_h0; r.traj_x = dev_traj_x; r.traj_h = dev_traj_h;
     return sample_loop(h, r, stream);
+}
+
+// ---- scoring: the per-level terms of the variational bound for GIVEN pharmacophores (include/pfdyn.h: pf_score) ----
+// A level is k_score_prepare + the inference forward at the uniform timestep t_int / T + k_score_eval (pf_score.hip).  The pocket
+// of every graph is the bound one translated rigidly (by the two COMs of its candidate), as in a sampling run: conv layer 0's
+// pocket-side constants (zs: functions of coordinate DIFFERENCES inside one pocket) hold for every level, and so does a
+// pocket-group claim -- coords_custom stays false, as behind pf_sample_begin.  They are made anew once per call and dropped
+// behind it, so that the call's bits depend on its arguments alone and a later run's on its own.
+int pf_score(pf_handle* h, const float* dev_pharm_x0, const float* dev_pharm_h0, int32_t n_levels, const pf_score_level* host_levels,
+             const float* dev_noise, const float* dev_alpha, const float* dev_sigma, int32_t n_timesteps, float feat_norm,
+             int32_t remove_com, int32_t endpoint_param_coord, int32_t endpoint_param_feat, float* dev_score, float* dev_terms,
+             pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (h->run != RUN_NONE)
+        PF_FAIL(h, PF_ERR_STATE, "pf_score inside a %s run (%s): the run's state is the handle's; bind the batch again to end the run", RUN_ROWS[h->run].name,
+                RUN_ROWS[h->run].begin);
+    if (!dev_pharm_x0 || !dev_pharm_h0 || !host_levels || !dev_noise || !dev_alpha || !dev_sigma || !dev_score) PF_FAIL(h, PF_ERR_ARG, "pf_score: null argument");
+    if (n_levels < 1) PF_FAIL(h, PF_ERR_ARG, "pf_score: n_levels %d (at least one level)", (int)n_levels);
+    if (n_timesteps < 1 || !(feat_norm > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_score: bad n_timesteps / feat_norm");
+    for (int l = 0; l < n_levels; ++l)
+        if (host_levels[l].t_int < 0 || host_levels[l].t_int > n_timesteps)
+            PF_FAIL(h, PF_ERR_ARG, "pf_score: level %d has t_int %d outside 0..%d", l, (int)host_levels[l].t_int, (int)n_timesteps);
+    if (h->Nf == 0) PF_FAIL(h, PF_ERR_ARG, "pf_score: the batch has no pharmacophore centers (nothing to score)");
+    if (h->cfg.pharm_nf > 8) PF_FAIL(h, PF_ERR_ARG, "pf_score: pharm_nf %d (the evaluation kernel holds at most 8 feature columns)", (int)h->cfg.pharm_nf);
+    // a pocket-group claim about DEVICE rows: its verdict is read here (the wait the first sharing call makes anyway), so that a false
+    // claim too is refused before anything is launched
+    if (h->share_ok && h->share_check == 0) (void)share_now(h);
+    if (h->share_check == 2)
+        PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_groups: the claim made for this batch is false -- a graph differs from its representative in "
+                               "coordinates or features (compared on the device); bind the batch again without the claim");
+    hipStream_t s = (hipStream_t)stream;
+    // a kept training forward does not survive: every level overwrites the coordinates and dynamic edges its backward reads again
+    h->t_have_fwd = false; h->t_have_loss = false;
+    h->coords_custom = false; h->zs_batch_coords = false;
+    std::vector<float> tv((size_t)n_levels);
+    for (int l = 0; l < n_levels; ++l) tv[l] = (float)host_levels[l].t_int / (float)n_timesteps;
+    // conv layer 0's per-timestep tables of every level up front, 64 timesteps per launch (the resident cache holds L0_PTAB_SLOTS: what is
+    // beyond is computed when its level arrives); the sampler's plan (pf_prepare_timesteps' other half) is not this call's to set
+    if (l0_hoist_ok(h)) l0_prepare_t(h, tv.data(), std::min<int>(n_levels, L0_PTAB_SLOTS - 64), s);
+    ScoreParams sp{};
+    sp.B = h->B; sp.Np = h->Np; sp.nf = h->cfg.pharm_nf; sp.remove_com = remove_com != 0; sp.feat_norm = feat_norm;
+    sp.prot_ptr = h->d_prot_ptr; sp.pharm_ptr = h->d_pharm_ptr; sp.prot_x0 = h->d_prot_x0;
+    sp.x0 = dev_pharm_x0; sp.h0 = dev_pharm_h0; sp.alpha_tab = dev_alpha; sp.sigma_tab = dev_sigma;
+    sp.xn = h->d_xn; sp.pharm_h = h->d_pharm_h; sp.dyn_h = h->d_eps_h; sp.dyn_x = h->d_eps_x; sp.score = dev_score;
+    const size_t row = (size_t)h->Nf * (3 + h->cfg.pharm_nf);
+    for (int l = 0; l < n_levels && rc == PF_OK; ++l) {
+        sp.t_int = host_levels[l].t_int; sp.w_pos = host_levels[l].w_pos; sp.w_feat = host_levels[l].w_feat; sp.first = l == 0;
+        sp.noise = dev_noise + (size_t)l * row;
+        sp.terms = dev_terms ? dev_terms + (size_t)l * h->B * 4 : nullptr;
+        h->edges_built = false; h->rec_valid = false;      // the centers moved, and each pocket with them
+        { ProfScope ps(h, pf_handle::K_STEP, s); pfk_score_prepare(&sp, s); }      // (class 5 of pf_profile_read: what a level adds to its forward)
+        rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &tv[l], false);
+        if (rc == PF_OK) { ProfScope ps(h, pf_handle::K_STEP, s); pfk_score_eval(&sp, endpoint_param_coord != 0, endpoint_param_feat != 0, s); }
+    }
+    // the handle holds the bound coordinates again, as the bind left them
+    pfk_load_coords(h->d_prot_x0, h->d_xn, h->Np, h->d_gid, nullptr, 0.f, s);
+    h->edges_built = false; h->rec_valid = false; h->zs_batch_coords = false;
+    if (rc) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return PF_OK;
 }
 
 int64_t pf_debug_get_edges(pf_handle* h, int32_t etype, int32_t* host_src, int32_t* host_dst, int64_t capacity,

@@ -622,6 +622,36 @@ class PfEngine:
         n = ctypes.c_int32()
         self._ck(self.lib.pf_sample_status(self._h, ctypes.byref(n)), "pf_sample_status")
 
+    # -- scoring ------------------------------------------------------------------------------
+    def score(self, x0, h0, levels, noise, w_pos, w_feat, alpha_tab, sigma_tab, n_timesteps, feat_norm=1.0, remove_com=True,
+              ep_coord=False, ep_feat=False, terms=True):
+        """pf_score on the bound batch: the candidates are its centers -- x0 [Nf, 3] in the frame of the bound pockets, h0
+        [Nf, pharm_nf] raw type one-hots.  levels: L integers in 0..n_timesteps; noise [L, Nf, 3 + pharm_nf] (x columns first), one
+        row per level; w_pos / w_feat: L weights each (schedule.score_weights); alpha_tab / sigma_tab: [n_timesteps + 1].
+        Returns (score [B, 2] = sum over levels of w_pos * pos and w_feat * feat, terms [L, B, 4] = pos, feat, err, hits per level
+        and graph, or None), device tensors; nothing is divided by the number of centers.  Refused (PfError) while a sampling run
+        holds the engine: bind the batch again first."""
+        x, hh = _f32(x0, self.device), _f32(h0, self.device)
+        lv = [int(t) for t in levels]
+        L_ = len(lv)
+        if len(w_pos) != L_ or len(w_feat) != L_:
+            raise ValueError(f"score: {L_} levels need {L_} weights of each kind, got {len(w_pos)} and {len(w_feat)}")
+        nz = _f32(noise, self.device)
+        if x.shape != (self.Nf, 3) or hh.shape != (self.Nf, self.pharm_nf) or nz.shape != (L_, self.Nf, 3 + self.pharm_nf):
+            raise ValueError(f"score: x0 [{self.Nf}, 3], h0 [{self.Nf}, {self.pharm_nf}] and noise [{L_}, {self.Nf}, {3 + self.pharm_nf}] "
+                             f"expected, got {tuple(x.shape)}, {tuple(hh.shape)}, {tuple(nz.shape)}")
+        al, sg = _f32(alpha_tab, self.device), _f32(sigma_tab, self.device)
+        if al.numel() != n_timesteps + 1 or sg.numel() != n_timesteps + 1:
+            raise ValueError(f"score: the alpha / sigma tables have n_timesteps + 1 = {n_timesteps + 1} entries")
+        arr = (L.PfScoreLevel * max(L_, 1))(*[L.PfScoreLevel(t, float(a), float(b)) for t, a, b in zip(lv, w_pos, w_feat)])
+        score = torch.empty(self.B, 2, device=self.device)
+        tm = torch.empty(L_, self.B, 4, device=self.device) if terms else None
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_score(self._h, _dptr(x), _dptr(hh), L_, arr, _dptr(nz), _dptr(al), _dptr(sg), int(n_timesteps),
+                                       float(feat_norm), int(bool(remove_com)), int(bool(ep_coord)), int(bool(ep_feat)), _dptr(score),
+                                       _dptr(tm), _stream_ptr()), "pf_score")
+        return score, tm
+
     # -- introspection -------------------------------------------------------------------------
     def get_edges(self, etype: int):
         with torch.cuda.device(self.device):

@@ -26,9 +26,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .analysis import SampleAnalyzer, SampledPharmacophore
+from .analysis import PharmacophoreScore, SampleAnalyzer, SampledPharmacophore
 from .engine import PfEngine
 from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_graph, get_batch_idxs, unbatch
+from .schedule import score_levels as _score_levels, score_weights as _score_weights
 from .schedule import (PredefinedNoiseSchedule, alpha as _alpha, guide_coefficients, pin_coefficients, renoise_coefficients, resample_plan,
                        seed_coefficients, sigma as _sigma, sigma_and_alpha_t_given_s, step_coefficients)
 
@@ -1018,7 +1019,8 @@ class PharmacophoreDiff(_Base):
                init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
                rank: int = 0, world_size: int = 1, noise=None, lanes: int = None,
                pinned=None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0,
-               guide_clip: float = 0.0, seeds=None, seed_level: int = None, seed_keep=None) -> List[List[SampledPharmacophore]]:
+               guide_clip: float = 0.0, seeds=None, seed_level: int = None, seed_keep=None,
+               score_levels: int = None) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -1061,7 +1063,14 @@ class PharmacophoreDiff(_Base):
         ``lanes`` (default ``self.sample_lanes``; None = 2, or 4 when the batches hold at most 32 graphs): batches in flight at
         once, each on its own HIP stream and handle.  Four of
         the five launches of a batched step occupy part of the chip, so independent batches overlap (2 lanes: +16 % at
-        batches of 128, +34 % at batches of 32; 4 lanes: +27 % / +58 %); a batch's result does not depend on the lane it ran on."""
+        batches of 128, +34 % at batches of 32; 4 lanes: +27 % / +58 %); a batch's result does not depend on the lane it ran on.
+
+        ``score_levels`` K: every returned SampledPharmacophore carries ``.score``, the PharmacophoreScore of its final frame at K
+        stratified levels (score(), uniform weighting, seed 0) -- a second pass behind the sampling, which it leaves bit for bit
+        as it is without.  None (the default): no scoring, ``.score`` stays None."""
+        if score_levels is not None and not 1 <= int(score_levels) <= self.n_timesteps:
+            raise ValueError(f"score_levels must satisfy 1 <= K <= {self.n_timesteps}, got {score_levels}")
+        scored_graphs = ref_graphs
         from .sharding import shard_by_work
         ref_graphs = [as_pocket_graph(g) for g in ref_graphs]
         n_receptors = len(ref_graphs)
@@ -1174,7 +1183,79 @@ class PharmacophoreDiff(_Base):
         for rec_idx in range(n_receptors):
             start, end = end, end + len(n_pharms[rec_idx])
             per_pocket.append([sampled[i] for i in range(start, end) if i in sampled])
+        if score_levels is not None:
+            cands = [[(p.ph_coords, p.ph_feats_idxs) for p in ps] for ps in per_pocket]
+            scores = self.score(scored_graphs, cands, levels=_score_levels(self.n_timesteps, int(score_levels)), max_batch_size=max_batch_size)
+            for ps, sc in zip(per_pocket, scores):
+                for p, v in zip(ps, sc):
+                    p.score = v
         return per_pocket
+
+    # -- scoring given pharmacophores (pf_score) ---------------------------------------------------
+    def score(self, ref_graphs: List[PocketGraph], pharmacophores, levels=None, weighting: str = 'uniform', noise=None, seed: int = 0,
+              max_batch_size: int = 32) -> List[List[PharmacophoreScore]]:
+        """How plausible the model finds GIVEN pharmacophores for their pockets.  ``pharmacophores[i]``: a list of (x [n,3] in the
+        frame of pocket i, types [n] type indices).  Every candidate is noised to each of ``levels`` (default: every level
+        1 .. T; schedule.score_levels(T, K) for a stratified subset) and the network's prediction error there is a term of its
+        variational bound; the terms are weighted (``weighting``: 'uniform' -- the per-graph training loss, every
+        parameterisation -- or 'vlb', schedule.score_weights) and summed.  Batches are built as sample() builds them: one copy
+        of the pocket per candidate, in pocket order, cut into batches of ``max_batch_size``; copies of a pocket share conv
+        layer 0's protein->protein messages.  ``noise``: None -- batch i draws [L, Nf_i, 3 + nf] Gaussians from a
+        torch.Generator(seed + i) on the host, so a candidate's score depends on the batch it is in only through its noise: the same
+        candidates in the same order with the same ``max_batch_size`` and seed give the same scores --;
+        or a list with one such tensor per batch.  Returns, per pocket, a list of PharmacophoreScore (LOWER per_center is
+        better; totals compare candidates of one size, there is no size prior in them).  A candidate of more than 64 centers,
+        or of none, is a ValueError naming it."""
+        # (pins a graph may carry are the sampler's: a scoring bind takes none)
+        ref_graphs = [dataclasses.replace(as_pocket_graph(g), pharm_pin=None, pharm_pin_x=None, pharm_pin_h=None) for g in ref_graphs]
+        if len(pharmacophores) != len(ref_graphs):
+            raise ValueError(f"pharmacophores lists {len(pharmacophores)} entries for {len(ref_graphs)} pockets")
+        T, nf = self.n_timesteps, self.n_pharm_feats
+        lv = _score_levels(T) if levels is None else [int(t) for t in levels]
+        if not lv or min(lv) < 0 or max(lv) > T:
+            raise ValueError(f"levels must be a non-empty list of integers in 0..{T}")
+        w_pos, w_feat = _score_weights(self.gamma.gamma, T, lv, weighting, bool(self.endpoint_param_coord), bool(self.endpoint_param_feat))
+        flat = []                                       # (pocket, x, one-hot rows)
+        for r, cands in enumerate(pharmacophores):
+            for j, (x, types) in enumerate(cands):
+                x = torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3)
+                types = torch.as_tensor(types, dtype=torch.int64).reshape(-1)
+                n = int(x.shape[0])
+                if n < 1 or n > 64:
+                    raise ValueError(f"pocket {r}, pharmacophore {j}: {n} centers (a candidate has 1 to 64)")
+                if types.numel() != n or int(types.min()) < 0 or int(types.max()) >= nf:
+                    raise ValueError(f"pocket {r}, pharmacophore {j}: {n} positions need {n} types in 0..{nf - 1}")
+                flat.append((r, x.cpu(), F.one_hot(types.cpu(), nf).float()))
+        out = [[] for _ in ref_graphs]
+        tabs = self._loss_tables()
+        for bi, s0 in enumerate(range(0, len(flat), max_batch_size)):
+            chunk = flat[s0:s0 + max_batch_size]
+            gs, a = [], 0
+            while a < len(chunk):                       # runs of one pocket: one copy_graph call each (its copies share a pocket_uid)
+                b = a
+                while b < len(chunk) and chunk[b][0] == chunk[a][0]:
+                    b += 1
+                gs.extend(copy_graph(ref_graphs[chunk[a][0]], n_copies=b - a,
+                                     pharm_feats_per_copy=torch.tensor([c[1].shape[0] for c in chunk[a:b]])))
+                a = b
+            g = batch_graphs(gs)
+            x0, h0 = torch.cat([c[1] for c in chunk]), torch.cat([c[2] for c in chunk])
+            Nf = int(x0.shape[0])
+            if noise is None:
+                nz = torch.randn(len(lv), Nf, 3 + nf, generator=torch.Generator().manual_seed(int(seed) + bi))
+            else:
+                nz = noise[bi]
+                if tuple(nz.shape) != (len(lv), Nf, 3 + nf):
+                    raise ValueError(f"batch {bi}: noise of shape {(len(lv), Nf, 3 + nf)} expected, got {tuple(nz.shape)}")
+            self.dynamics._batch_key = None             # always a fresh bind: a sampling run may hold the handle on this very batch
+            eng = self.dynamics.bind_graph(g)
+            sc, tm = eng.score(x0, h0, lv, nz, w_pos, w_feat, tabs[0], tabs[1], T, feat_norm=float(self.pharm_feat_norm_constant),
+                               remove_com=bool(self.remove_com), ep_coord=bool(self.endpoint_param_coord),
+                               ep_feat=bool(self.endpoint_param_feat), terms=True)
+            sc, tm = sc.cpu(), tm.cpu()
+            for k, c in enumerate(chunk):
+                out[c[0]].append(PharmacophoreScore(c[1].shape[0], lv, sc[k, 0], sc[k, 1], tm[:, k, :].clone()))
+        return out
 
     # -- training-loss forward (pharmacodiff.py:162-243), evaluation only ---------------------------
     def _check_injected_t(self, t_int, B):

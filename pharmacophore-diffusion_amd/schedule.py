@@ -157,3 +157,50 @@ def renoise_coefficients(gamma_table: torch.Tensor, timesteps: int, pairs) -> Di
     g_a = g[torch.round(a_int.float() / timesteps * timesteps).long()]
     _, s_ab, a_ab, _ = sigma_and_alpha_t_given_s(g_a, g_b)
     return {"alpha_t_given_s": a_ab, "sigma_t_given_s": s_ab}
+
+
+def score_levels(timesteps: int, n=None):
+    """The noise levels a scoring call visits (PharmacophoreDiff.score, pf_score): every level 1 .. T without ``n``; with it, n
+    levels stratified evenly over 1 .. T -- level i lies in the i-th of n equal parts of (0, T]: its middle rounded up, or the
+    part's last integer where that falls outside --, deterministic, ascending, without repeats; n = T gives every level."""
+    T = int(timesteps)
+    if T < 1:
+        raise ValueError(f"score_levels: timesteps must be at least 1, got {timesteps}")
+    if n is None:
+        return list(range(1, T + 1))
+    n = int(n)
+    if not 1 <= n <= T:
+        raise ValueError(f"score_levels: n must satisfy 1 <= n <= {T}, got {n}")
+    return [min(-((-(2 * i + 1) * T) // (2 * n)), ((i + 1) * T) // n) for i in range(n)]
+
+
+def score_weights(gamma_table: torch.Tensor, timesteps: int, levels, kind: str = "uniform", ep_coord: bool = False, ep_feat: bool = False):
+    """(w_pos, w_feat): the weight of every level's position and feature term in a score, fp32 arrays of len(levels), computed in
+    float64 from the gamma table.
+    'uniform': 1 / len(levels) -- the score estimates the per-graph training loss (sum over centers, mean over levels); valid for
+    all four parameterisations.
+    'vlb': the diffusion terms of the variational bound times T / len(levels), so that a subset of the levels estimates the full
+    sum.  With s = t - 1: 0.5 * expm1(gamma_t - gamma_s) for a noise-parameterised output (0.5 * (SNR(s) / SNR(t) - 1) on the noise
+    error), 0.5 * (exp(-gamma_s) - exp(-gamma_t)) for the endpoint coordinate output (0.5 * (SNR(s) - SNR(t)) on the error of the
+    predicted clean center).  A cross-entropy has no such weight (ep_feat) and level 0 has no s: ValueError."""
+    lv = np.asarray([int(t) for t in levels], dtype=np.int64)
+    if lv.size == 0:
+        raise ValueError("score_weights: at least one level")
+    T = int(timesteps)
+    if lv.min() < 0 or lv.max() > T:
+        raise ValueError(f"score_weights: levels must lie in 0..{T}")
+    if kind == "uniform":
+        w = np.full(lv.size, 1.0 / lv.size, dtype=np.float64)
+        return w.astype(np.float32), w.astype(np.float32)
+    if kind != "vlb":
+        raise ValueError(f"score_weights: kind must be 'uniform' or 'vlb', got {kind!r}")
+    if ep_feat:
+        raise ValueError("score_weights: 'vlb' has no weight for an endpoint feature output (a cross-entropy); use 'uniform'")
+    if lv.min() < 1:
+        raise ValueError("score_weights: 'vlb' weights need levels >= 1 (level 0 has no s = t - 1)")
+    g = gamma_table.detach().cpu().double().numpy()
+    g_t, g_s = g[lv], g[lv - 1]
+    scale = float(T) / lv.size
+    noise = 0.5 * np.expm1(g_t - g_s) * scale
+    w_pos = 0.5 * (np.exp(-g_s) - np.exp(-g_t)) * scale if ep_coord else noise
+    return w_pos.astype(np.float32), noise.astype(np.float32)
