@@ -42,6 +42,10 @@ _FLAGS = [
     ('--seed_pharmacophore', dict(type=Path, default=None, help='seeded sampling: one xyz frame in the pharms.xyz format; every sample is a variation of it (the frame is noised forward to --seed_level and only the steps below that level are run)')),
     ('--seed_level', dict(type=int, default=None, help='with --seed_pharmacophore: the level 1..T the seed is noised to; small: close analogues, large: loose ones')),
     ('--seed_keep', dict(type=str, default=None, help='with --seed_pharmacophore: comma-separated indices of seed centers that stay fixed in position and type, e.g. 0,2')),
+    ('--sample_steps', dict(type=int, default=None, help='few-step sampling: visit only this many of the T levels (from --seed_level down in a seeded run); how good such samples are depends on the trained weights')),
+    ('--sampler', dict(choices=['ancestral', 'ddim', 'multistep'], default=None, help='with --sample_steps: ancestral (default; the posterior between the visited levels), ddim (--eta, default 0: no injected noise) or multistep (second-order multistep solver; composes with --seed_pharmacophore only)')),
+    ('--eta', dict(type=float, default=None, help='with --sample_steps --sampler ddim: share of the posterior noise injected, 0..1 (default 0)')),
+    ('--spacing', dict(choices=['uniform', 'quadratic', 'logsnr'], default=None, help='with --sample_steps: how the visited levels are spread (default uniform; quadratic is denser near level 0, logsnr uniform in the log signal-to-noise ratio)')),
     ('--score_samples', dict(type=int, default=None, help='score the drawn samples with the model at this many noise levels (stratified over 1..T) and write scores.tsv, one line per sample in the order of pharms.xyz; lower per-center score is better')),
     ('--keep_best', dict(type=int, default=None, help='with --score_samples: write only this many samples, best (lowest per-center score) first')),
     ('--score_pharmacophores', dict(type=Path, default=None, help='no sampling: score every frame of this file (pharms.xyz format) against the pocket and write scores.tsv; --score_samples gives the number of levels (default: every level); with the --seed, --score_samples, --score_weighting and --max_batch_size of the run that wrote the file, and its frames in their order, this reproduces that run\'s scores.tsv (the noise of a score is drawn per device batch)')),
@@ -97,6 +101,23 @@ def parse_arguments(argv=None):
             bad = [i for i in a.seed_keep_list if not 0 <= i < n_seed]
             if bad:
                 parser.error(f'--seed_keep {bad} outside the {n_seed} centers of --seed_pharmacophore')
+    if a.sample_steps is None:
+        for flag in ('sampler', 'eta', 'spacing'):
+            if getattr(a, flag) is not None:
+                parser.error(f'--{flag} needs --sample_steps')
+    else:
+        if a.sample_steps < 1:
+            parser.error(f'--sample_steps must be at least 1, got {a.sample_steps}')
+        if a.seed_level is not None and a.sample_steps > a.seed_level:
+            parser.error(f'--sample_steps {a.sample_steps} exceeds --seed_level {a.seed_level}')
+        if a.pin_resamples is not None and a.pin_resamples > 1:
+            parser.error('--sample_steps together with --pin_resamples > 1: resampling jumps over a strided plan are not supported')
+        if a.eta is not None and a.sampler != 'ddim':
+            parser.error('--eta needs --sampler ddim')
+        if a.eta is not None and not 0.0 <= a.eta <= 1.0:
+            parser.error(f'--eta must lie in 0..1, got {a.eta}')
+        if a.sampler == 'multistep' and (a.pinned_centers is not None or a.restraints is not None or a.seed_keep is not None):
+            parser.error('--sampler multistep composes with --seed_pharmacophore only: no --pinned_centers, --seed_keep or --restraints')
     a.pin_resamples = 1 if a.pin_resamples is None else a.pin_resamples
     a.pin_jump = 10 if a.pin_jump is None else a.pin_jump
     for flag in ('score_samples', 'keep_best'):
@@ -268,7 +289,8 @@ def main(argv=None):
                                                   restraints=[args.restraint_list] * n if args.restraint_list else None,
                                                   guide_scale=args.guide_scale, guide_clip=args.guide_clip,
                                                   seeds=[args.seed_centers] * n if args.seed_centers is not None else None, seed_level=args.seed_level,
-                                                  seed_keep=[args.seed_keep_list] * n if args.seed_keep_list else None)
+                                                  seed_keep=[args.seed_keep_list] * n if args.seed_keep_list else None,
+                                                  sample_steps=args.sample_steps, sampler=args.sampler, eta=args.eta, spacing=args.spacing)
     elapsed = time.time() - t0
 
     (pocket_dir / 'sample_time.txt').write_text(f'{elapsed:.2f}')

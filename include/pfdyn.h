@@ -350,6 +350,39 @@ typedef struct pf_seed_coef { float alpha_a; float sigma_a; } pf_seed_coef;   /*
 int pf_sample_seed_next(pf_handle* h, const pf_seed_coef* coef, const float* dev_seed_x /*[Nf,3], caller's frame*/,
                         const float* dev_seed_h /*[Nf,pharm_nf], raw rows*/, float feat_norm_constant, pf_stream stream);
 
+/* -- few-step sampling: strided schedules and a second-order multistep move (no reference counterpart) ---------------------------
+ * Strided first-order runs need nothing new here: pf_step_coef is computed by the host for any pair of levels (s, t), s < t, and
+ * pf_prepare_timesteps / pf_sample take any list of t, so an ancestral or DDIM run over a subset of the levels is pf_sample (or
+ * its pinned, guided and seeded forms) with fewer entries, on the default path's launches.
+ * The multistep move.  A second-order multistep solver of the probability-flow ODE (DPM-Solver++ 2M for an endpoint output, its
+ * noise-prediction twin for a noise output) is, per block of the state (x: coordinates, h: features),
+ *     z_s = (cz * z_t + c0 * o_t) + c1 * o_prev
+ * with o_t the network's output for that block AS IT IS (noise, or the clean value under an endpoint parameterisation) and
+ * o_prev the output of the step before.  All solver knowledge is in the host's coefficients; the device knows this form only.
+ * One rounding per operation, FP contraction off.  No noise is drawn or read.  Then the COM of all centers of the graph is
+ * removed from centers and protein, in the reduction order of pf_denoise_step's update.
+ * History.  The handle keeps one buffer [Nf, 3 + pharm_nf] with the previous outputs, written by the move itself.  It is valid
+ * after a multistep step and invalid after every begin, every bind and every other move.  Where c1 == 0 (both blocks are judged
+ * on their own) it is not read and may hold anything.  A step with a non-zero c1 and no valid history fails with PF_ERR_STATE
+ * before any launch; the run goes on as if the call had not been made.  A non-finite coefficient is PF_ERR_ARG.
+ * pf_denoise_step_ms is legal inside a plain run (after pf_sample_begin, seeded or not), and plain and multistep steps may
+ * alternate.  Like a pinned step it runs the separate launches -- one more than the default step -- and ends with one launch
+ * of its own (k_step_build_ms: the move + the generic edge build; k_step_update_ms for the width-generic family and every
+ * configuration whose next dynamics call builds its own edges); nothing is computed ahead across it.
+ * pf_sample_ms is the whole run: begin with dev_noise0 [Nf, 3 + pharm_nf] (ONE row: the initial draw), n_steps multistep steps,
+ * end.  Trajectories have n_steps + 1 frames.  Pinned and guided runs have no multistep move.
+ * Few-step QUALITY is a property of trained weights and is not measured by this project. */
+typedef struct pf_ms_coef {
+    float t;                    /* l_i / T : the timestep fed to the dynamics */
+    float cz_x, c0_x, c1_x;     /* coordinates */
+    float cz_h, c0_h, c1_h;     /* features */
+} pf_ms_coef;
+int pf_denoise_step_ms(pf_handle* h, const pf_ms_coef* coef, pf_stream stream);
+int pf_sample_ms(pf_handle* h, int32_t n_steps, const pf_ms_coef* host_coef, const float* dev_noise0 /*[Nf,3+pharm_nf]*/,
+                 const float* dev_init_pharm_com /*[B,3] or NULL*/, float feat_norm_constant,
+                 float* dev_x0 /*[Nf,3]*/, float* dev_h0 /*[Nf,pharm_nf]*/,
+                 float* dev_traj_x /*[n_steps+1,Nf,3] or NULL*/, float* dev_traj_h /*[n_steps+1,Nf,pharm_nf] or NULL*/, pf_stream stream);
+
 /* -- scoring: how plausible are GIVEN pharmacophores for the bound pockets (the per-level terms of PharmacophoreDiff.forward,
  *    pharmacodiff.py:162-243, per graph and at levels the caller chooses; the reference reduces them to batch means) -----------
  * The candidates are the centers of the bound batch: graph g's candidate has pharm_ptr[g+1] - pharm_ptr[g] centers, positions

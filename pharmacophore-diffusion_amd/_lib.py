@@ -46,6 +46,11 @@ class PfSeedCoef(ctypes.Structure):
     _fields_ = [("alpha_a", ctypes.c_float), ("sigma_a", ctypes.c_float)]
 
 
+class PfMsCoef(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_float), ("cz_x", ctypes.c_float), ("c0_x", ctypes.c_float), ("c1_x", ctypes.c_float),
+                ("cz_h", ctypes.c_float), ("c0_h", ctypes.c_float), ("c1_h", ctypes.c_float)]
+
+
 class PfScoreLevel(ctypes.Structure):
     _fields_ = [("t_int", ctypes.c_int32), ("w_pos", ctypes.c_float), ("w_feat", ctypes.c_float)]
 
@@ -85,6 +90,8 @@ SYMBOLS = {
     "pf_sample_guided": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PfStepCoef), ctypes.POINTER(PfPinCoef), ctypes.POINTER(PfGuideCoef), _P, _P,
                                         _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "pf_sample_seed_next": (ctypes.c_int, [_P, ctypes.POINTER(PfSeedCoef), _P, _P, _F, _P]),
+    "pf_denoise_step_ms": (ctypes.c_int, [_P, ctypes.POINTER(PfMsCoef), _P]),
+    "pf_sample_ms": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PfMsCoef), _P, _P, _F, _P, _P, _P, _P, _P]),
     "pf_score": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.POINTER(PfScoreLevel), _P, _P, _P, _I32, _F, _I32, _I32, _I32, _P, _P, _P]),
     "pf_debug_last_guidance": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "pf_dynamics_input_vjp": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),

@@ -548,6 +548,12 @@ struct SeedParams {
     const float* com_init;     // [B][3]    mean of the original protein coordinates (pf_sample_begin)
     float alpha_a, sigma_a, feat_norm;
 };
+// multistep move (pf_denoise_step_ms): z_s = cz * z_t + c0 * o_t + c1 * o_prev per block (x: coordinates, h: features), o the
+// network's output as it is; of StepParams it reads the graph pointers, xn, pharm_h, eps_x, eps_h and nf only (no noise)
+struct MsParams {
+    float* hist;               // [Nf][3 + nf]  the previous step's outputs; written by every move, read only where c1 != 0
+    float cz_x, c0_x, c1_x, cz_h, c0_h, c1_h;   // pf_ms_coef
+};
 // guided sampling (pf_denoise_step_guided): restraint energies on the predicted clean centers.  k_guide_grad reads GuideParams
 // (of StepParams: the graph pointers, xn and eps_x) and leaves g0 = dE/dy per center, E per graph and the frame offset D per graph;
 // the guided update (k_step_update_guided) reads GuideShiftParams: g0, the VJP of the dynamics J(g0) and D
@@ -585,6 +591,18 @@ __device__ __forceinline__ float pf_feat_update(const float hv, const float e, c
     else { const float a = hv / a_ts, b = var * e; mu = a - b; }
     const float n = sigma * nz;
     return mu + n;
+}
+// The multistep move for ONE value, written once like pf_feat_update and with FP contraction off: (cz * z + c0 * o) + c1 * o_prev,
+// one rounding per operation.  `second` is c1 != 0, uniform over the launch: without it o_prev is not looked at, so whatever the
+// history holds -- NaN included -- cannot reach the state (0 * NaN is NaN)
+__device__ __forceinline__ float pf_ms_update(const float z, const float o, const float o_prev, const float cz, const float c0,
+                                              const float c1, const bool second) {
+#pragma clang fp contract(off)
+    const float a = cz * z, b = c0 * o;
+    const float first = a + b;
+    if (!second) return first;
+    const float c = c1 * o_prev;
+    return first + c;
 }
 #endif
 

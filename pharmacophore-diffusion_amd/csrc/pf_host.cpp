@@ -73,6 +73,8 @@ void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const 
 void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s);
 void pfk_step_build_seed(const StepParams* sp, const SeedParams* q, const BuildParams* bp, hipStream_t s);
 void pfk_step_update_seed(const StepParams* p, const SeedParams* q, hipStream_t s);
+void pfk_step_build_ms(const StepParams* sp, const MsParams* q, const BuildParams* bp, hipStream_t s);
+void pfk_step_update_ms(const StepParams* p, const MsParams* q, hipStream_t s);
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s);
@@ -394,6 +396,11 @@ struct pf_handle {
     float *d_seed_x = nullptr, *d_seed_h = nullptr;
     float seed_alpha = 1.f, seed_sigma = 0.f, seed_feat_norm = 1.f;
     bool seed_armed = false;
+    // multistep move (pf_denoise_step_ms): the previous step's outputs [Nf][3 + pharm_nf], written by the move itself (one
+    // allocation, kept and grown like d_pin).  ms_hist_valid: the last move of the run in progress was a multistep move, so the
+    // buffer holds that step's outputs; cleared by every begin, every bind and every other move
+    void* d_ms_hist = nullptr; size_t ms_hist_capacity = 0;
+    bool ms_hist_valid = false;
     // guided run (pf_sample_begin_guided): a pinned run plus restraint energies per graph.  The restraints are staged in pinned host
     // memory (restr_ev: the last upload that reads the staging buffer) and live in one device allocation, kept and grown like d_pin:
     // restr_ptr [B + 1], kind [n], center [n], p [n][3], r [n], w [n].  d_guide: what a guided step leaves -- g0, J(g0), grad, shift
@@ -1505,6 +1512,7 @@ void pf_destroy(pf_handle* h) {
     if (h->d_ptab) (void)hipFree(h->d_ptab);
     if (h->d_pin) (void)hipFree(h->d_pin);
     if (h->d_seed) (void)hipFree(h->d_seed);
+    if (h->d_ms_hist) (void)hipFree(h->d_ms_hist);
     if (h->d_restr) (void)hipFree(h->d_restr);
     if (h->d_guide) (void)hipFree(h->d_guide);
     if (h->restr_stage) (void)hipHostFree(h->restr_stage);
@@ -1686,6 +1694,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     pfbind::BindInputs in;
     if (h) in.rep.swap(h->pending_rep);
     if (h) h->seed_armed = false;               // (so does a seed: pf_sample_seed_next comes after the bind it is for)
+    if (h) h->ms_hist_valid = false;            // (and the multistep history: it belongs to a run on the batch before)
     int rc = check_ready(h, false);
     if (rc) return rc;
     const bool from_host = host_prot_x != nullptr;
@@ -1977,6 +1986,7 @@ static int begin_plain(pf_handle* h, const float* dev_init_pharm_com, const floa
     }
     h->coords_custom = false;               // a rigid translate of the batch's own coordinates from here on
     h->run = RUN_PLAIN;
+    h->ms_hist_valid = false;               // a run begins without a previous output
     h->edges_built = false; h->rec_valid = false;
     // a seeded begin: the state is the noised seed, made by a move of the step end (which also writes the snapshot, after the move)
     return seeded ? seed_move(h, dev_noise0, s) : PF_OK;
@@ -2033,13 +2043,14 @@ static PinParams pin_params(const pf_handle* h, const pf_pin_coef* pin) {
 // The move a step's own last launch makes.  build_form: the move has an "update + edge build in one launch" form (the guided
 // move has none: the width-generic training forward in front of it builds its own edges on every call)
 struct StepMove {
-    enum Kind { PLAIN, PINNED, RENOISE, GUIDED, SEED } kind;
+    enum Kind { PLAIN, PINNED, RENOISE, GUIDED, SEED, MS } kind;
     bool build_form;
     const PinParams* pin;                   // PINNED, GUIDED
     const RenoiseParams* renoise;           // RENOISE
     const GuideShiftParams* shift;          // GUIDED
     int snap_next;                          // PLAIN, SEED: the snapshot sp.h_snap_out is (center hoist)
     const SeedParams* seed = nullptr;       // SEED
+    const MsParams* ms = nullptr;           // MS
 };
 // What every op calls after its dynamics call (if it has one): the move, unless the dynamics call's tail or merged launch made
 // it already; what the move leaves of the edges; what survives of the work done ahead (snapshot, center hoist, speculative rows)
@@ -2058,6 +2069,7 @@ static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipS
             case StepMove::RENOISE: if (build) pfk_step_build_renoise(&sp, mv.renoise, &bp, s); else pfk_step_update_renoise(&sp, mv.renoise, s); break;
             case StepMove::GUIDED: pfk_step_update_guided(&sp, mv.pin, mv.shift, s); break;
             case StepMove::SEED: if (build) pfk_step_build_seed(&sp, mv.seed, &bp, s); else pfk_step_update_seed(&sp, mv.seed, s); break;
+            case StepMove::MS: if (build) pfk_step_build_ms(&sp, mv.ms, &bp, s); else pfk_step_update_ms(&sp, mv.ms, s); break;
             }
         }
         if (build) build_done(h, share);
@@ -2066,6 +2078,8 @@ static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipS
     }
     // a re-noise move has no dynamics call in front of it that would have reset these
     if (!plain) { h->tail_done = false; h->last_tail = 0; }
+    // the multistep history holds the outputs of the step in front of this move only if that move wrote it
+    h->ms_hist_valid = mv.kind == StepMove::MS;
     // the work done ahead is for the state the merged launch of a plain step left: every other move invalidates it.  The seed
     // move opens a run: nothing is ahead of it, and the snapshot it wrote holds the features as they are now
     const bool ahead = plain && h->tail_done && h->last_tail == 2;
@@ -2200,6 +2214,33 @@ int pf_renoise_step(pf_handle* h, const pf_renoise_coef* coef, const float* dev_
     return step_end(h, sp, StepMove{StepMove::RENOISE, true, nullptr, &r, nullptr, -1}, (hipStream_t)stream);
 }
 
+// One multistep step inside a plain run.  As in a pinned step the dynamics call is sequenced WITHOUT a step; the step ends with one
+// launch of its own: the linear move, which also stores this step's outputs as the history, and, with the encoders on the fly, the
+// generic edge build.  A non-zero c1 needs the outputs of a multistep step right in front of this one: refused before any launch
+int pf_denoise_step_ms(pf_handle* h, const pf_ms_coef* coef, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!coef) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_ms: null argument");
+    if ((rc = run_guard(h, __func__, RUN_PLAIN)) != PF_OK) return rc;
+    const float cs[6] = {coef->cz_x, coef->c0_x, coef->c1_x, coef->cz_h, coef->c0_h, coef->c1_h};
+    for (float c : cs) if (!std::isfinite(c)) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_ms: a coefficient is not finite");
+    if ((coef->c1_x != 0.f || coef->c1_h != 0.f) && !h->ms_hist_valid)
+        PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_ms: c1 != 0 needs the outputs of a multistep step right in front of this one (the first "
+                                 "step of a run, and the first after any other move, must have c1 == 0)");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = (size_t)std::max(h->Nf, 1) * 4 * (3 + (size_t)h->cfg.pharm_nf);
+    if ((rc = grow_run_scratch(h, &h->d_ms_hist, &h->ms_hist_capacity, bytes, bytes, s)) != PF_OK) return rc;
+    StepParams sp = step_params_base(h, nullptr);
+    sp.eps_h = h->d_eps_h; sp.eps_x = h->d_eps_x;
+    MsParams q{};
+    q.hist = (float*)h->d_ms_hist;
+    q.cz_x = coef->cz_x; q.c0_x = coef->c0_x; q.c1_x = coef->c1_x; q.cz_h = coef->cz_h; q.c0_h = coef->c0_h; q.c1_h = coef->c1_h;
+    ++h->step_id;
+    rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, nullptr);
+    if (rc) return rc;
+    return step_end(h, sp, StepMove{StepMove::MS, true, nullptr, nullptr, nullptr, -1, nullptr, &q}, s);
+}
+
 int pf_prepare_timesteps(pf_handle* h, const float* host_t, int32_t n, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
@@ -2265,6 +2306,7 @@ int pf_debug_xchg_fault(pf_handle* h, int32_t drop_word, int32_t poll_max) {
 struct SampleRun {
     RunKind kind; int32_t n_ops; const int32_t* op;
     const pf_step_coef* coef; const pf_pin_coef* pin_coef; const pf_renoise_coef* renoise; const pf_guide_coef* guide_coef;
+    const pf_ms_coef* ms_coef;              // RUN_PLAIN only: every op is a multistep step, and noise is the initial draw alone
     const float *noise, *com;
     const int32_t* pin_flags; const float *pin_x, *pin_h;
     const int32_t *restr_ptr, *restr_kind, *restr_center; const float *restr_p, *restr_r, *restr_w; float guide_scale, guide_clip;
@@ -2277,8 +2319,9 @@ static int sample_loop(pf_handle* h, const SampleRun& r, pf_stream stream) {
     if (rc) return rc;
     const bool pinned = r.kind >= RUN_PINNED, guided = r.kind == RUN_GUIDED;
     const int n_ops = r.n_ops;
-    if (n_ops < 0 || (n_ops && (!r.coef || (guided && (!r.pin_coef || !r.guide_coef)))) || !r.noise)
-        PF_FAIL(h, PF_ERR_ARG, "%s: bad argument", guided ? "pf_sample_guided" : "pf_sample");
+    const bool ms = r.ms_coef != nullptr;
+    if (n_ops < 0 || (n_ops && ((!r.coef && !ms) || (guided && (!r.pin_coef || !r.guide_coef)))) || !r.noise)
+        PF_FAIL(h, PF_ERR_ARG, "%s: bad argument", guided ? "pf_sample_guided" : ms ? "pf_sample_ms" : "pf_sample");
     if (pinned && n_ops && !r.pin_coef) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned: null host_pin_coef");
     for (int i = 0; r.op && i < n_ops; ++i) {
         if (r.op[i] != 0 && r.op[i] != 1) PF_FAIL(h, PF_ERR_ARG, "pf_sample_pinned_resampled: op %d has kind %d (0 denoise, 1 renoise)", i, (int)r.op[i]);
@@ -2297,13 +2340,15 @@ static int sample_loop(pf_handle* h, const SampleRun& r, pf_stream stream) {
     if (!guided) {      // (a guided step's dynamics call is a training forward: nothing is hoisted or computed ahead for it)
         std::vector<float> tv;                  // the denoising steps' timesteps in op order
         tv.reserve(n_ops);
-        for (int i = 0; i < n_ops; ++i) if (!r.op || r.op[i] == 0) tv.push_back(r.coef[i].t);
+        for (int i = 0; i < n_ops; ++i) if (!r.op || r.op[i] == 0) tv.push_back(ms ? r.ms_coef[i].t : r.coef[i].t);
         rc = pf_prepare_timesteps(h, tv.data(), (int32_t)tv.size(), stream);
         if (rc) return rc;
     }
     for (int i = 0; i < n_ops; ++i) {
-        const float* nz = r.noise + (size_t)(i + 1) * row;
-        if (r.op && r.op[i] == 1) rc = pf_renoise_step(h, r.renoise + i, nz, stream);
+        // this op's noise row; a multistep run has the initial draw alone and reads no other
+        const float* nz = ms ? nullptr : r.noise + (size_t)(i + 1) * row;
+        if (ms) rc = pf_denoise_step_ms(h, r.ms_coef + i, stream);
+        else if (r.op && r.op[i] == 1) rc = pf_renoise_step(h, r.renoise + i, nz, stream);
         else if (guided) {
             h->guide_traj_energy = r.energy ? r.energy + (size_t)i * h->B : nullptr;
             rc = pf_denoise_step_guided(h, r.coef + i, r.pin_coef + i, r.guide_coef + i, nz, r.ep_coord, r.ep_feat, stream);
@@ -2324,6 +2369,17 @@ int pf_sample(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, cons
     SampleRun r{};
     r.kind = RUN_PLAIN; r.n_ops = n_steps; r.coef = host_coef; r.noise = dev_noise; r.com = dev_init_pharm_com;
     r.ep_coord = ep_coord; r.ep_feat = ep_feat; r.feat_norm = feat_norm_constant;
+    r.x0 = dev_x0; r.h0 = dev_h0; r.traj_x = dev_traj_x; r.traj_h = dev_traj_h;
+    return sample_loop(h, r, stream);
+}
+
+int pf_sample_ms(pf_handle* h, int32_t n_steps, const pf_ms_coef* host_coef, const float* dev_noise0, const float* dev_init_pharm_com,
+                 float feat_norm_constant, float* dev_x0, float* dev_h0, float* dev_traj_x, float* dev_traj_h, pf_stream stream) {
+    if (h && n_steps > 0 && !host_coef) PF_FAIL(h, PF_ERR_ARG, "pf_sample_ms: null host_coef");
+    static const pf_ms_coef none{};
+    SampleRun r{};
+    r.kind = RUN_PLAIN; r.n_ops = n_steps; r.ms_coef = host_coef ? host_coef : &none; r.noise = dev_noise0; r.com = dev_init_pharm_com;
+    r.feat_norm = feat_norm_constant;
     r.x0 = dev_x0; r.h0 = dev_h0; r.traj_x = dev_traj_x; r.traj_h = dev_traj_h;
     return sample_loop(h, r, stream);
 }

@@ -1857,6 +1857,70 @@ __global__ __launch_bounds__(256) void k_step_build(const StepParams sp, const B
 }
 
 // ---------------------------------------------------------------------------------------------
+// Multistep move (pf_denoise_step_ms): step_update_body with the linear combination pf_ms_update in place of pf_feat_update and
+// no noise read.  The thread that reads an element's output also stores it as that element's history, for the next multistep
+// move; the history is read only where c1 != 0.  The COM of the graph's centers and its removal from centers and protein are
+// step_update_body's, in its reduction order.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void ms_update_body(const StepParams& p, const MsParams& q, const int g) {
+    __shared__ float com[3];
+    __shared__ float red[4][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
+    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
+    const bool sec_x = q.c1_x != 0.f, sec_h = q.c1_h != 0.f;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int f = f0 + tid; f < f1; f += 256) {
+        const float4 x = p.xn[p.Np_tot + f];
+        float* hs = q.hist + (size_t)f * (3 + p.nf);
+        float m[3];
+        const float xi[3] = {x.x, x.y, x.z};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float e = p.eps_x[(size_t)f * 3 + c];
+            const float ep = sec_x ? hs[c] : 0.f;
+            m[c] = pf_ms_update(xi[c], e, ep, q.cz_x, q.c0_x, q.c1_x, sec_x);
+            hs[c] = e;
+        }
+        p.xn[p.Np_tot + f] = make_float4(m[0], m[1], m[2], 0.f);
+        sx += m[0]; sy += m[1]; sz += m[2];
+        for (int k = 0; k < p.nf; ++k) {
+            const float hv = p.pharm_h[(size_t)f * p.nf + k];
+            const float e = p.eps_h[(size_t)f * p.nf + k];
+            const float ep = sec_h ? hs[3 + k] : 0.f;
+            p.pharm_h[(size_t)f * p.nf + k] = pf_ms_update(hv, e, ep, q.cz_h, q.c0_h, q.c1_h, sec_h);
+            hs[3 + k] = e;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
+    __syncthreads();
+    if (tid == 0) {
+        const float n = (float)max(f1 - f0, 1);
+        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
+    }
+    __syncthreads();
+    const float cx = com[0], cy = com[1], cz = com[2];
+    for (int f = f0 + tid; f < f1; f += 256) {
+        float4 x = p.xn[p.Np_tot + f];
+        x.x -= cx; x.y -= cy; x.z -= cz;
+        p.xn[p.Np_tot + f] = x;
+    }
+    for (int i = p0 + tid; i < p1; i += 256) {
+        float4 x = p.xn[i];
+        x.x -= cx; x.y -= cy; x.z -= cz;
+        p.xn[i] = x;
+    }
+}
+__global__ __launch_bounds__(256) void k_step_update_ms(const StepParams p, const MsParams q) { ms_update_body(p, q, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_step_build_ms(const StepParams sp, const MsParams q, const BuildParams bp) {
+    ms_update_body(sp, q, blockIdx.x);
+    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
+    build_body(bp, blockIdx.x);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Pinned centers (replacement conditioning, pf_denoise_step_pinned): step_update_body with two selects in front of its
 // stores.  A center whose position is given (flag bit 0) becomes the given position noised to this step's level,
 // z_s = alpha_s * given + sigma_s * noise, with the step's own noise draw (its posterior sample is discarded); likewise a
@@ -2483,6 +2547,14 @@ void pfk_step_build_seed(const StepParams* sp, const SeedParams* q, const BuildP
 void pfk_step_update_seed(const StepParams* p, const SeedParams* q, hipStream_t s) {
     if (p->B == 0) return;
     hipLaunchKernelGGL(k_step_update_seed, dim3(p->B), dim3(256), 0, s, *p, *q);
+}
+void pfk_step_build_ms(const StepParams* sp, const MsParams* q, const BuildParams* bp, hipStream_t s) {
+    if (sp->B == 0) return;
+    hipLaunchKernelGGL(k_step_build_ms, dim3(sp->B), dim3(256), 0, s, *sp, *q, *bp);
+}
+void pfk_step_update_ms(const StepParams* p, const MsParams* q, hipStream_t s) {
+    if (p->B == 0) return;
+    hipLaunchKernelGGL(k_step_update_ms, dim3(p->B), dim3(256), 0, s, *p, *q);
 }
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s) {
     if (n == 0 || (!out_x && !out_h)) return;

@@ -386,6 +386,12 @@ class PfEngine:
         return PfEngine._struct_array(L.PfGuideCoef, guide_coef, order)
 
     @staticmethod
+    def ms_coef_array(ms_coef: Dict[str, torch.Tensor], order=None):
+        """ms_coef: per-step tensors (schedule.multistep_coefficients); entry i of the array is step order[i] (default: every
+        step, in order)."""
+        return PfEngine._struct_array(L.PfMsCoef, ms_coef, range(len(ms_coef["t"])) if order is None else order)
+
+    @staticmethod
     def plan_arrays(plan, coef, pin_coef, renoise_coef):
         """The four host arrays of pf_sample_pinned_resampled for ``plan`` (schedule.resample_plan): (coef_arr, pin_coef_arr,
         op_arr, renoise_arr), each with one entry per op.  coef / pin_coef: per-s tensors (coef_array / pin_coef_array);
@@ -512,6 +518,12 @@ class PfEngine:
             self._ck(self.lib.pf_denoise_step(self._h, ctypes.byref(coef_struct), _dptr(nz), int(ep_coord), int(ep_feat),
                                               _stream_ptr()), "pf_denoise_step")
 
+    def ms_step(self, ms_coef_struct):
+        """One multistep step inside a plain run (pf_denoise_step_ms): ms_coef_struct is this step's entry of ms_coef_array.  No
+        noise is read.  A non-zero c1 needs a multistep step right in front of it (PfError, PF_ERR_STATE; the run goes on)."""
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_denoise_step_ms(self._h, ctypes.byref(ms_coef_struct), _stream_ptr()), "pf_denoise_step_ms")
+
     def guided_step(self, coef_struct, pin_coef, guide_coef, noise, ep_coord=False, ep_feat=False):
         """One step of a guided run (pf_denoise_step_guided): coef_struct / pin_coef / guide_coef are this step's entries of
         coef_array / pin_coef_array / guide_coef_array."""
@@ -562,7 +574,7 @@ class PfEngine:
 
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
                feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None, restraints=None,
-               guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False, seed=None):
+               guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False, seed=None, ms_coef_arr=None):
         """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the run -- n_steps is
         then the seed's level a, and coef_arr (and the other per-step arrays) hold the entries of s = a-1 .. 0.
         pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned.
@@ -571,8 +583,27 @@ class PfEngine:
         restraints (one list or None per graph, see _restraints) with pin_coef_arr and guide_coef_arr (guide_coef_array): a guided
         run, pf_sample_guided -- pins are optional, a plan is refused.  The run is made on the wide training family; the family
         the engine was on is restored afterwards, also on error.  energies: the restraint energies [n_steps, B] come back
-        behind the other outputs."""
+        behind the other outputs.
+        ms_coef_arr (ms_coef_array): a multistep run, pf_sample_ms -- coef_arr is not read (None), noise needs its first row only
+        (the initial draw), and the parameterisation is in the coefficients; seeds compose, pins, plans and restraints are refused."""
         guided = restraints is not None
+        if ms_coef_arr is not None:
+            if pins is not None or plan is not None or guided:
+                raise ValueError("a multistep run composes with seeds only: no pins, resampling plan or restraints")
+            if len(ms_coef_arr) < n_steps:
+                raise ValueError(f"a multistep run of {n_steps} steps needs {n_steps} entries in ms_coef_arr")
+            nz = _f32(noise, self.device)
+            if nz.dim() == 2:
+                nz = nz[None]
+            assert nz.shape[0] >= 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
+            com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
+            x0, h0, tx, th, _ = self._sample_outputs(n_steps + 1 if trajectory else 0)
+            if seed is not None:
+                self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
+            with torch.cuda.device(self.device):
+                self._ck(self.lib.pf_sample_ms(self._h, n_steps, ms_coef_arr, _dptr(nz), _dptr(com), float(feat_norm_constant), _dptr(x0),
+                                               _dptr(h0), _dptr(tx), _dptr(th), _stream_ptr()), "pf_sample_ms")
+            return (x0, h0, tx, th) if trajectory else (x0, h0)
         if plan is not None and pins is None:
             raise ValueError("a plan needs pins: resampling runs inside a pinned run (all flags zero pins nothing)")
         if guided and plan is not None:

@@ -32,6 +32,7 @@ from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_gra
 from .schedule import score_levels as _score_levels, score_weights as _score_weights
 from .schedule import (PredefinedNoiseSchedule, alpha as _alpha, guide_coefficients, pin_coefficients, renoise_coefficients, resample_plan,
                        seed_coefficients, sigma as _sigma, sigma_and_alpha_t_given_s, step_coefficients)
+from .schedule import level_plan, multistep_coefficients, strided_coefficients
 
 try:  # subclass LightningModule when Lightning is importable (drop-in for train.py / load_from_checkpoint)
     import pytorch_lightning as pl
@@ -769,7 +770,8 @@ class PharmacophoreDiff(_Base):
     def sample_given_receptor(self, g, init_pharm_com: torch.Tensor = None, visualize_trajectory: bool = False,
                               noise: torch.Tensor = None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None,
                               guide_scale: float = 1.0, guide_clip: float = 0.0, seeds=None, seed_level: int = None,
-                              seed_keep=None) -> List[SampledPharmacophore]:
+                              seed_keep=None, sample_steps: int = None, sampler: str = None, eta: float = None,
+                              spacing: str = None) -> List[SampledPharmacophore]:
         """Reverse diffusion for a batch of pocket graphs; the whole T-step loop is enqueued on the
         current HIP stream by pf_sample (no host synchronisation inside the loop).
 
@@ -792,7 +794,14 @@ class PharmacophoreDiff(_Base):
         ``seeds`` with ``seed_level`` a (and optionally ``seed_keep``): a seeded run (pf_sample_seed_next) -- one (x [n,3], types
         [n]) per graph of the batch, n that graph's number of centers; the run starts from the seeds noised to level a and makes
         the steps a-1 .. 0, so ``noise`` has a + 1 rows (n_ops + 1 with ``pin_resamples`` > 1, whose plan then starts at a).
-        ``seed_keep``: per graph, the seed centers that stay fixed in position and type (see ``sample``)."""
+        ``seed_keep``: per graph, the seed centers that stay fixed in position and type (see ``sample``).
+
+        ``sample_steps`` N with ``sampler`` / ``eta`` / ``spacing``: a few-step run (see ``sample``) -- ``noise`` has N + 1 rows for
+        the first-order samplers and 1 row for 'multistep'; trajectories have N + 1 frames."""
+        g = as_pocket_graph(g)
+        fewstep = self._fewstep(sample_steps, sampler, eta, spacing, pin_resamples=pin_resamples, seed_level=seed_level,
+                                pins=(g.pharm_pin is not None and bool((g.pharm_pin != 0).any())) or seed_keep is not None,
+                                restraints=restraints is not None and any(len(r) > 0 for r in restraints if r is not None))
         if (seeds is None) != (seed_level is None):
             raise ValueError("seeds and seed_level go together: a seeded run needs both")
         if seeds is None and seed_keep is not None:
@@ -815,7 +824,62 @@ class PharmacophoreDiff(_Base):
         return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, init_pharm_com, visualize_trajectory, noise,
                                                                            pin_resamples=pin_resamples, pin_jump=pin_jump,
                                                                            restraints=restraints, guide_scale=guide_scale,
-                                                                           guide_clip=guide_clip, seed_level=seed_level)))
+                                                                           guide_clip=guide_clip, seed_level=seed_level,
+                                                                           fewstep=fewstep)))
+
+    def _fewstep(self, sample_steps, sampler, eta, spacing, pin_resamples=1, seed_level=None, pins=False, restraints=False):
+        """The few-step keywords of sample / sample_given_receptor, checked before any device work: None without sample_steps,
+        else (N, sampler, eta, spacing).  'ancestral' is eta = 1 (the default sampler), 'ddim' defaults to eta = 0, 'multistep'
+        takes no eta and composes with seeds only."""
+        if sample_steps is None:
+            if sampler is not None or eta is not None or spacing is not None:
+                raise ValueError("sampler, eta and spacing belong to a few-step run: pass sample_steps")
+            return None
+        sampler = "ancestral" if sampler is None else sampler
+        spacing = "uniform" if spacing is None else spacing
+        if sampler not in ("ancestral", "ddim", "multistep"):
+            raise ValueError(f"sampler must be 'ancestral', 'ddim' or 'multistep', got {sampler!r}")
+        if spacing not in ("uniform", "quadratic", "logsnr"):
+            raise ValueError(f"spacing must be 'uniform', 'quadratic' or 'logsnr', got {spacing!r}")
+        if pin_resamples > 1:
+            raise ValueError("sample_steps together with pin_resamples > 1: resampling jumps over a strided plan are not supported")
+        top = self.n_timesteps if seed_level is None else self._check_seed_level(seed_level)
+        if not 1 <= int(sample_steps) <= top:
+            raise ValueError(f"sample_steps must satisfy 1 <= sample_steps <= {top} (T, or the seed level of a seeded run), got {sample_steps}")
+        if sampler == "multistep":
+            if eta is not None:
+                raise ValueError("sampler 'multistep' injects no noise and takes no eta")
+            if pins or restraints:
+                raise ValueError("sampler 'multistep' composes with seeds only: pinned centers (seed_keep included) and restraints "
+                                 "need a first-order sampler ('ancestral' or 'ddim')")
+            eta = 0.0
+        elif sampler == "ancestral":
+            if eta is not None and float(eta) != 1.0:
+                raise ValueError("sampler 'ancestral' is eta = 1; use sampler='ddim' for another eta")
+            eta = 1.0
+        else:
+            eta = 0.0 if eta is None else float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"eta must lie in [0, 1], got {eta}")
+        return int(sample_steps), sampler, float(eta), spacing
+
+    def _fewstep_arrays(self, name, fewstep, top=None):
+        """coef / pin / guide / ms: that per-step array of a few-step run, keyed by its plan (N, spacing, top) -- and by eta for the
+        first-order coefficients, by the parameterisation for the multistep ones."""
+        T = self.n_timesteps
+        N, _, eta, spacing = fewstep
+        top = T if top is None else int(top)
+        gam = self.gamma.gamma
+        levels = self._host_arrays(("levels", N, spacing, top), lambda: level_plan(T, N, spacing, top, gamma_table=gam))
+        if name == "levels":
+            return levels
+        build = {"coef": lambda: PfEngine.coef_array(strided_coefficients(gam, T, levels, eta), range(N)),
+                 "pin": lambda: PfEngine.pin_coef_array(pin_coefficients(gam, T, levels), range(N)),
+                 "guide": lambda: PfEngine.guide_coef_array(guide_coefficients(gam, T, levels), range(N)),
+                 "ms": lambda: PfEngine.ms_coef_array(multistep_coefficients(gam, T, levels, bool(self.endpoint_param_coord),
+                                                                             bool(self.endpoint_param_feat)))}[name]
+        extra = {"coef": (eta,), "ms": (bool(self.endpoint_param_coord), bool(self.endpoint_param_feat))}.get(name, ())
+        return self._host_arrays((name, "fewstep", N, spacing, top) + extra, build)
 
     def _host_arrays(self, key, build):
         """The ctypes arrays of a run at this model's T (500-1000 structs an array; a plan's, a few thousand): built once per key."""
@@ -897,13 +961,14 @@ class PharmacophoreDiff(_Base):
 
     def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0,
                         pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0, guide_clip: float = 0.0,
-                        seed_level: int = None):
+                        seed_level: int = None, fewstep=None):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
         current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  ``restraints``: None or one
         list (or None) per graph of the batch; a batch takes the guided path (pf_sample_guided) only when one of them holds a
         restraint, as with pin flags.  A batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled.
         ``seed_level`` a: a seeded run -- the graph's pharm_pin_x / pharm_pin_h hold the seed of EVERY center (the flags say which
-        of them stay fixed), the run starts at level a (pf_sample_seed_next) and its arrays hold the steps a-1 .. 0."""
+        of them stay fixed), the run starts at level a (pf_sample_seed_next) and its arrays hold the steps a-1 .. 0.
+        ``fewstep`` (_fewstep): the run visits the N + 1 levels of a plan from T (or a) down; 'multistep': pf_sample_ms."""
         g = as_pocket_graph(g)
         dev = self.device
         top = None
@@ -919,29 +984,41 @@ class PharmacophoreDiff(_Base):
         if guided and pin_resamples > 1:
             raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
         kw = {}
-        if has_pins and pin_resamples > 1:
+        ms = fewstep is not None and fewstep[1] == "multistep"
+        step_arrays = self._step_arrays if fewstep is None else (lambda name, top: self._fewstep_arrays(name, fewstep, top))
+        if fewstep is not None:
+            n_ops = fewstep[0]
+            if pin_resamples > 1:
+                raise ValueError("sample_steps together with pin_resamples > 1: resampling jumps over a strided plan are not supported")
+            if ms and (has_pins or guided):
+                raise ValueError("sampler 'multistep' composes with seeds only: no pinned centers, no restraints")
+        if fewstep is not None and noise is not None and noise.shape[0] != (1 if ms else n_ops + 1):
+            raise ValueError(f"a {fewstep[1]} run of {n_ops} steps needs {1 if ms else n_ops + 1} noise row(s), got {noise.shape[0]}")
+        if ms:
+            arr, kw = None, {"ms_coef_arr": step_arrays("ms", top)}
+        elif has_pins and pin_resamples > 1:
             n_ops, arr, parr, op_arr, re_arr = self._plan_arrays(pin_jump, pin_resamples, top)
             if noise is not None and noise.shape[0] != n_ops + 1:
                 raise ValueError(f"a resampled pinned run of {n_ops} ops (T = {self.n_timesteps}, jump {pin_jump}, resamples {pin_resamples}) "
                                  f"needs {n_ops + 1} noise rows, got {noise.shape[0]}")
             kw = {"pin_coef_arr": parr, "plan": (op_arr, re_arr)}
         else:
-            arr = self._step_arrays("coef", top)
+            arr = step_arrays("coef", top)
             if guided or has_pins:
-                kw = {"pin_coef_arr": self._step_arrays("pin", top)}
-        if kw and g.pharm_pin is not None:
+                kw = {"pin_coef_arr": step_arrays("pin", top)}
+        if "pin_coef_arr" in kw and g.pharm_pin is not None:       # (a seeded multistep run carries its seed on these fields: no pins)
             kw["pins"] = (g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h)
         if top is not None:
-            if noise is not None and noise.shape[0] != n_ops + 1:
+            if fewstep is None and noise is not None and noise.shape[0] != n_ops + 1:
                 raise ValueError(f"a seeded run of {n_ops} ops (seed level {top}) needs {n_ops + 1} noise rows, got {noise.shape[0]}")
             kw["seed"] = (g.pharm_pin_x, g.pharm_pin_h, seed_coefficients(self.gamma.gamma, self.n_timesteps, top))
         if guided:
             if len(restraints) != g.batch_size:
                 raise ValueError(f"restraints lists {len(restraints)} entries for a batch of {g.batch_size} graphs")
-            kw.update(restraints=restraints, guide_coef_arr=self._step_arrays("guide", top), guide_scale=float(guide_scale),
+            kw.update(restraints=restraints, guide_coef_arr=step_arrays("guide", top), guide_scale=float(guide_scale),
                       guide_clip=float(guide_clip))
         if noise is None:
-            noise = torch.randn(n_ops + 1, Nf, 3 + nf, device=dev)
+            noise = torch.randn(1 if ms else n_ops + 1, Nf, 3 + nf, device=dev)
         if lane == 0:
             eng = self.dynamics.bind_graph(g)
         else:
@@ -1020,7 +1097,8 @@ class PharmacophoreDiff(_Base):
                rank: int = 0, world_size: int = 1, noise=None, lanes: int = None,
                pinned=None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0,
                guide_clip: float = 0.0, seeds=None, seed_level: int = None, seed_keep=None,
-               score_levels: int = None) -> List[List[SampledPharmacophore]]:
+               score_levels: int = None, sample_steps: int = None, sampler: str = None, eta: float = None,
+               spacing: str = None) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -1060,6 +1138,16 @@ class PharmacophoreDiff(_Base):
         a pinned run with these centers flagged, and they come back bit for bit.  With ``pin_resamples`` > 1 such a run follows
         schedule.resample_plan(a, j, r); with ``restraints`` it is guided.  Together with ``pinned`` it is a ValueError.
 
+        ``sample_steps`` N: a few-step run -- the reverse process visits only the N + 1 levels of schedule.level_plan(T, N,
+        ``spacing``) ('uniform', 'quadratic' or 'logsnr'; from the seed level down in a seeded run, which needs N <= a) and costs
+        N network evaluations.  ``sampler``: 'ancestral' (the default; the reference's posterior between the plan's levels, eta = 1),
+        'ddim' (``eta`` in [0, 1], default 0: no injected noise) -- both run the default path's steps with strided coefficients
+        (schedule.strided_coefficients) and compose with ``pinned``, ``restraints`` and ``seeds``; their noise has N + 1 rows -- or
+        'multistep' (a second-order multistep solver of the probability-flow ODE, schedule.multistep_coefficients and
+        pf_sample_ms: 1 noise row, the initial draw), which composes with ``seeds`` only: with pins (``seed_keep`` included) or
+        restraints it is a ValueError.  Together with ``pin_resamples`` > 1 every few-step run is a ValueError.  Trajectories have
+        N + 1 frames.  How good an N-step sample is depends on the trained weights and is not measured by this project.
+
         ``lanes`` (default ``self.sample_lanes``; None = 2, or 4 when the batches hold at most 32 graphs): batches in flight at
         once, each on its own HIP stream and handle.  Four of
         the five launches of a batched step occupy part of the chip, so independent batches overlap (2 lanes: +16 % at
@@ -1070,6 +1158,9 @@ class PharmacophoreDiff(_Base):
         as it is without.  None (the default): no scoring, ``.score`` stays None."""
         if score_levels is not None and not 1 <= int(score_levels) <= self.n_timesteps:
             raise ValueError(f"score_levels must satisfy 1 <= K <= {self.n_timesteps}, got {score_levels}")
+        fewstep = self._fewstep(sample_steps, sampler, eta, spacing, pin_resamples=pin_resamples, seed_level=seed_level,
+                                pins=pinned is not None and any(p is not None for p in pinned) or seed_keep is not None,
+                                restraints=restraints is not None and any(restraints))
         scored_graphs = ref_graphs
         from .sharding import shard_by_work
         ref_graphs = [as_pocket_graph(g) for g in ref_graphs]
@@ -1159,6 +1250,8 @@ class PharmacophoreDiff(_Base):
             lane = k % n_lanes
             with torch.cuda.stream(streams[lane]):
                 rows = (T if top is None else top) + 1
+                if fewstep is not None:
+                    rows = 1 if fewstep[1] == "multistep" else fewstep[0] + 1
                 if pin_resamples > 1 and batch_g.pharm_pin is not None and bool((batch_g.pharm_pin != 0).any()):
                     rows = self._plan_arrays(pin_jump, pin_resamples, top)[0] + 1
                 if noise is None:
@@ -1170,7 +1263,7 @@ class PharmacophoreDiff(_Base):
                 batch_r = [restraints[graph_ref_idx[i]] for i in idx] if restraints is not None else None
                 enq = self._sample_enqueue(batch_g, init_coms, visualize_trajectory, nz, lane=lane,
                                            pin_resamples=pin_resamples, pin_jump=pin_jump, restraints=batch_r,
-                                           guide_scale=guide_scale, guide_clip=guide_clip, seed_level=top)
+                                           guide_scale=guide_scale, guide_clip=guide_clip, seed_level=top, fewstep=fewstep)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on

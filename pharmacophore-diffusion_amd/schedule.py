@@ -88,22 +88,25 @@ def step_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, to
             "ep_zt": a_ts * (sig_s ** 2) / (sig_t ** 2), "ep_pred": a_s * s2_ts / (sig_t ** 2)}
 
 
-def pin_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, torch.Tensor]:
+def pin_coefficients(gamma_table: torch.Tensor, timesteps: int, levels=None) -> Dict[str, torch.Tensor]:
     """Noise level of z_s for all s at once (index = s), fp32 on the host: alpha_s = alpha(gamma(s / T)) and
-    sigma_s = sigma(gamma(s / T)) -- what a pinned run noises its given centers with (pf_denoise_step_pinned)."""
+    sigma_s = sigma(gamma(s / T)) -- what a pinned run noises its given centers with (pf_denoise_step_pinned).
+    levels (a plan, level_plan): the same table selected at the plan's steps -- index = step i, s = l_{i+1}."""
     g = gamma_table.detach().float().cpu()
-    s_int = torch.arange(timesteps)
+    s_int = torch.arange(timesteps) if levels is None else torch.tensor(_plan_levels(timesteps, levels)[1:], dtype=torch.long)
     s = s_int.float() / timesteps
     g_s = g[torch.round(s * timesteps).long()]
     return {"alpha_s": alpha(g_s), "sigma_s": sigma(g_s)}
 
 
-def guide_coefficients(gamma_table: torch.Tensor, timesteps: int) -> Dict[str, torch.Tensor]:
+def guide_coefficients(gamma_table: torch.Tensor, timesteps: int, levels=None) -> Dict[str, torch.Tensor]:
     """Noise level of z_t, t = s + 1, for all s at once (index = s), fp32 on the host: alpha_t = alpha(gamma((s + 1) / T)) and
     sigma_t = sigma(gamma((s + 1) / T)) -- what a guided step predicts the clean centers with, x0_hat = (x_t - sigma_t eps_x) /
-    alpha_t (pf_denoise_step_guided, pf_guide_coef)."""
+    alpha_t (pf_denoise_step_guided, pf_guide_coef).
+    levels (a plan, level_plan): the same table selected at the plan's steps -- index = step i, t = l_i."""
     g = gamma_table.detach().float().cpu()
-    t = (torch.arange(timesteps) + 1).float() / timesteps
+    t_int = torch.arange(timesteps) + 1 if levels is None else torch.tensor(_plan_levels(timesteps, levels)[:-1], dtype=torch.long)
+    t = t_int.float() / timesteps
     g_t = g[torch.round(t * timesteps).long()]
     return {"alpha_t": alpha(g_t), "sigma_t": sigma(g_t)}
 
@@ -204,3 +207,118 @@ def score_weights(gamma_table: torch.Tensor, timesteps: int, levels, kind: str =
     noise = 0.5 * np.expm1(g_t - g_s) * scale
     w_pos = 0.5 * (np.exp(-g_s) - np.exp(-g_t)) * scale if ep_coord else noise
     return w_pos.astype(np.float32), noise.astype(np.float32)
+
+
+# ---- few-step sampling: a plan of levels, first-order coefficients for any pair of levels, second-order multistep coefficients ----
+def _plan_levels(timesteps: int, levels):
+    """``levels`` as a list of ints, checked: timesteps >= l_0 > l_1 > ... > l_N >= 0 with N >= 1."""
+    lv = [int(l) for l in levels]
+    if len(lv) < 2:
+        raise ValueError("a plan has at least two levels")
+    if lv[0] > int(timesteps) or lv[-1] < 0 or any(a <= b for a, b in zip(lv[:-1], lv[1:])):
+        raise ValueError(f"a plan's levels must descend strictly inside {int(timesteps)}..0, got {lv}")
+    return lv
+
+
+def level_plan(timesteps: int, n_steps: int, spacing: str = "uniform", top=None, gamma_table=None):
+    """The levels a few-step run visits: integers top = l_0 > l_1 > ... > l_N = 0 with N = n_steps; step i goes from l_i to l_{i+1}.
+    top defaults to T (a seeded run passes its seed level).  spacing: 'uniform' in the level index; 'quadratic', l = top (1 - i/N)^2,
+    denser near 0; 'logsnr', uniform in lambda = -gamma / 2 between the two ends (needs gamma_table), each target taken to the level
+    whose lambda is nearest.  Rounding collisions are resolved the same way every time: one pass down from l_0 (no level at or above
+    its predecessor), one pass up from l_N = 0 (no level at or below its successor); 1 <= N <= top leaves room for both.  N = top
+    gives every level."""
+    T = int(timesteps)
+    top = T if top is None else int(top)
+    if not 1 <= top <= T:
+        raise ValueError(f"level_plan: top must satisfy 1 <= top <= {T}, got {top}")
+    N = int(n_steps)
+    if not 1 <= N <= top:
+        raise ValueError(f"level_plan: n_steps must satisfy 1 <= n_steps <= {top}, got {n_steps}")
+    u = np.arange(N + 1, dtype=np.float64) / N
+    if spacing == "uniform":
+        lv = np.rint(top * (1.0 - u))
+    elif spacing == "quadratic":
+        lv = np.rint(top * (1.0 - u) ** 2)
+    elif spacing == "logsnr":
+        if gamma_table is None:
+            raise ValueError("level_plan: spacing 'logsnr' needs gamma_table")
+        lam = -0.5 * gamma_table.detach().cpu().double().numpy()[:top + 1]
+        target = lam[top] + (lam[0] - lam[top]) * u
+        lv = np.array([int(np.argmin(np.abs(lam - x))) for x in target], dtype=np.float64)   # (the first of equals: the lowest level)
+    else:
+        raise ValueError(f"level_plan: spacing must be 'uniform', 'quadratic' or 'logsnr', got {spacing!r}")
+    lv = [int(x) for x in lv]
+    lv[0], lv[-1] = top, 0
+    for i in range(1, N):
+        lv[i] = min(lv[i], lv[i - 1] - 1)
+    for i in range(N - 1, 0, -1):
+        lv[i] = max(lv[i], lv[i + 1] + 1)
+    return lv
+
+
+def strided_coefficients(gamma_table: torch.Tensor, timesteps: int, levels, eta: float = 1.0) -> Dict[str, torch.Tensor]:
+    """The fields of step_coefficients for the steps of a plan: entry i is the pair (s, t) = (l_{i+1}, l_i), t = l_i / T.
+    eta = 1: the reference's posterior evaluated at (s, t) (pharmacodiff.py:387-420 with a general s), fp32 in its op order -- a
+    unit-stride plan gives step_coefficients' arrays bit for bit.  0 <= eta < 1: the DDIM family on the SAME struct, float64 cast to
+    fp32: with s_eta = eta sigma_{t|s} sigma_s / sigma_t and k = sqrt(sigma_s^2 - s_eta^2), alpha_t_given_s = alpha_t / alpha_s,
+    var_terms = sigma_t / alpha_{t|s} - k, sigma = s_eta, ep_zt = k / sigma_t, ep_pred = alpha_s - k alpha_t / sigma_t (at eta = 1
+    these are the posterior's expressions)."""
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"strided_coefficients: eta must lie in [0, 1], got {eta}")
+    lv = _plan_levels(timesteps, levels)
+    g = gamma_table.detach().float().cpu()
+    s_int, t_int = torch.tensor(lv[1:], dtype=torch.long), torch.tensor(lv[:-1], dtype=torch.long)
+    s = s_int.float() / timesteps
+    t = t_int.float() / timesteps
+    if eta == 1.0:
+        # torch's vectorised kernels may round an element differently in a vector's body and in its scalar tail (softplus does), so
+        # "the same expression" is bit for bit the same only at the same position of a tensor of the same length: every pair is
+        # evaluated at position s of step_coefficients' own T-long tensors, with t = s + 1 wherever the plan does not say otherwise
+        t_of = torch.arange(timesteps) + 1
+        t_of[s_int] = t_int
+        t_all = t_of.float() / timesteps
+        g_s = g[torch.round(torch.arange(timesteps).float() / timesteps * timesteps).long()]
+        g_t = g[torch.round(t_all * timesteps).long()]
+        s2_ts, s_ts, a_ts, a_s = sigma_and_alpha_t_given_s(g_t, g_s)
+        sig_s, sig_t = sigma(g_s), sigma(g_t)
+        full = {"alpha_t_given_s": a_ts, "var_terms": s2_ts / a_ts / sig_t, "sigma": s_ts * sig_s / sig_t,
+                "ep_zt": a_ts * (sig_s ** 2) / (sig_t ** 2), "ep_pred": a_s * s2_ts / (sig_t ** 2)}
+        out = {name: v[s_int] for name, v in full.items()}
+        out.update(t=t, s=s)
+        return out
+    g_s, g_t = g[torch.round(s * timesteps).long()].double(), g[torch.round(t * timesteps).long()].double()
+    _, s_ts, a_ts, a_s = sigma_and_alpha_t_given_s(g_t, g_s)
+    sig_s, sig_t, a_t = sigma(g_s), sigma(g_t), alpha(g_t)
+    s_eta = eta * s_ts * sig_s / sig_t
+    k = torch.sqrt(sig_s ** 2 - s_eta ** 2)
+    out = {"alpha_t_given_s": a_t / a_s, "var_terms": sig_t / a_ts - k, "sigma": s_eta, "ep_zt": k / sig_t, "ep_pred": a_s - k * a_t / sig_t}
+    out = {name: v.float() for name, v in out.items()}
+    out.update(t=t, s=s)
+    return out
+
+
+def multistep_coefficients(gamma_table: torch.Tensor, timesteps: int, levels, ep_coord: bool = False, ep_feat: bool = False) -> Dict[str, torch.Tensor]:
+    """Per step i of a plan (t = l_i, s = l_{i+1}, prev = l_{i-1}) and per block -- x: coordinates, h: features -- the triple of the
+    linear move z_s = cz z_t + c0 o_t + c1 o_prev (pf_ms_coef), o the network's output for the block as it is.  With lambda =
+    -gamma / 2, h = lambda_s - lambda_t, r = (lambda_t - lambda_prev) / h:
+      noise block:                       cz = alpha_s / alpha_t, c0 = -sigma_s expm1(h) (1 + 1/(2r)),  c1 = sigma_s expm1(h) / (2r)
+      endpoint block (DPM-Solver++ 2M):  cz = sigma_s / sigma_t, c0 = -alpha_s expm1(-h) (1 + 1/(2r)), c1 = alpha_s expm1(-h) / (2r)
+    The first step (no history) and the last (to level 0) are first-order: the 1/(2r) terms dropped, c1 = 0 exactly.  float64 cast
+    to fp32; all solver knowledge is here, the device knows the linear form only."""
+    lv = _plan_levels(timesteps, levels)
+    n = len(lv) - 1
+    g = gamma_table.detach().float().cpu().double()[torch.tensor(lv, dtype=torch.long)]
+    lam, al, sg = -0.5 * g, alpha(g), sigma(g)
+    h = lam[1:] - lam[:-1]
+    inv2r = torch.zeros(n, dtype=torch.float64)
+    for i in range(1, n - 1):
+        inv2r[i] = 0.5 * float(h[i]) / float(lam[i] - lam[i - 1])
+    a_t, a_s, s_t, s_s = al[:-1], al[1:], sg[:-1], sg[1:]
+    eps_blk = (a_s / a_t, -s_s * torch.expm1(h) * (1.0 + inv2r), s_s * torch.expm1(h) * inv2r)
+    end_blk = (s_s / s_t, -a_s * torch.expm1(-h) * (1.0 + inv2r), a_s * torch.expm1(-h) * inv2r)
+    out = {"t": torch.tensor(lv[:-1], dtype=torch.long).float() / timesteps}
+    for blk, ep in (("x", ep_coord), ("h", ep_feat)):
+        for name, v in zip(("cz", "c0", "c1"), end_blk if ep else eps_blk):
+            out[f"{name}_{blk}"] = (v + 0.0).float()          # (+ 0.0: a dropped term is +0, never -0)
+    return out

@@ -35,6 +35,10 @@ _FLAGS = [
     ('--use_ref_pharm_com', dict(action='store_true', help='start the centers at the reference pharmacophore\'s mean position')),
     ('--visualize_trajectory', dict(action='store_true', help='write every denoising frame, one xyz file per sample')),
     ('--metrics', dict(action='store_true', help='validity and feature-type counts over all samples of all ranks')),
+    ('--sample_steps', dict(type=int, default=None, help='few-step sampling: visit only this many of the T levels; how good such samples are depends on the trained weights')),
+    ('--sampler', dict(choices=['ancestral', 'ddim', 'multistep'], default=None, help='with --sample_steps: ancestral (default), ddim (--eta, default 0) or multistep (second-order multistep solver)')),
+    ('--eta', dict(type=float, default=None, help='with --sample_steps --sampler ddim: share of the posterior noise injected, 0..1 (default 0)')),
+    ('--spacing', dict(choices=['uniform', 'quadratic', 'logsnr'], default=None, help='with --sample_steps: how the visited levels are spread (default uniform)')),
     ('--pockets_per_call', dict(type=int, default=64, help='pockets whose samples are batched together (not in the reference)')),
 ]
 
@@ -48,6 +52,12 @@ def parse_arguments(argv=None):
         raise ValueError('no model given: pass --ckpt or --model_dir')
     if a.pharm_sizes and len(a.pharm_sizes) != a.samples_per_pocket:
         raise ValueError(f'--pharm_sizes lists {len(a.pharm_sizes)} sizes for --samples_per_pocket {a.samples_per_pocket}')
+    if a.sample_steps is None and (a.sampler is not None or a.eta is not None or a.spacing is not None):
+        raise ValueError('--sampler, --eta and --spacing need --sample_steps')
+    if a.sample_steps is not None and a.sample_steps < 1:
+        raise ValueError(f'--sample_steps must be at least 1, got {a.sample_steps}')
+    if a.eta is not None and (a.sampler != 'ddim' or not 0.0 <= a.eta <= 1.0):
+        raise ValueError('--eta needs --sampler ddim and a value in 0..1')
     if a.dataset_idx_as_start and (a.dataset_idx is None or a.dataset_size is None):
         raise ValueError('--dataset_idx_as_start needs both --dataset_idx and --dataset_size')
     return a
@@ -134,7 +144,8 @@ def main(argv=None):
         coms = torch.stack([g.pharm_x0.mean(dim=0) for g in graphs]) if args.use_ref_pharm_com else None
         with torch.no_grad():
             per_pocket = model.sample(graphs, sizes, max_batch_size=args.max_batch_size, init_pharm_com=coms,
-                                      visualize_trajectory=args.visualize_trajectory)
+                                      visualize_trajectory=args.visualize_trajectory, sample_steps=args.sample_steps,
+                                      sampler=args.sampler, eta=args.eta, spacing=args.spacing)
         seconds = (time.time() - t0) / len(chunk)
         for idx, pharms in zip(chunk, per_pocket):
             write_pocket(out_root, dataset, idx, pharms, seconds, args.visualize_trajectory)
