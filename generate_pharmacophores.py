@@ -39,6 +39,7 @@ _FLAGS = [
     ('--restraints', dict(type=Path, default=None, help='guided sampling: a text file with one restraint per line, "attract|repel x y z radius weight [center|*]" in the receptor\'s frame (# starts a comment): keep centers out of / pull a center into a sphere; a guided step costs several times a default one')),
     ('--guide_scale', dict(type=float, default=None, help='with --restraints: strength of the guidance (default 1)')),
     ('--guide_clip', dict(type=float, default=None, help='with --restraints: largest shift of a center per step in angstroms (default 0: no clip)')),
+    ('--guide_family', dict(choices=['wide', 'tuned'], default=None, help='with --restraints: the kernels of a guided step\'s training forward and input gradients -- wide (default; every model width) or tuned (models of n_hidden_scalars 128 / vector_size 16: the tuned gradient kernels)')),
     ('--seed_pharmacophore', dict(type=Path, default=None, help='seeded sampling: one xyz frame in the pharms.xyz format; every sample is a variation of it (the frame is noised forward to --seed_level and only the steps below that level are run)')),
     ('--seed_level', dict(type=int, default=None, help='with --seed_pharmacophore: the level 1..T the seed is noised to; small: close analogues, large: loose ones')),
     ('--seed_keep', dict(type=str, default=None, help='with --seed_pharmacophore: comma-separated indices of seed centers that stay fixed in position and type, e.g. 0,2')),
@@ -71,6 +72,9 @@ def parse_arguments(argv=None):
             parser.error(f'--{flag} needs --restraints')
         if v is not None and not v >= 0:
             parser.error(f'--{flag} must not be negative, got {v}')
+    if a.guide_family is not None and a.restraints is None:
+        parser.error('--guide_family needs --restraints')
+    a.guide_family = 'wide' if a.guide_family is None else a.guide_family
     a.guide_scale = 1.0 if a.guide_scale is None else a.guide_scale
     a.guide_clip = 0.0 if a.guide_clip is None else a.guide_clip
     if a.restraints is not None and a.pin_resamples is not None and a.pin_resamples > 1:
@@ -287,7 +291,7 @@ def main(argv=None):
             pharms += model.sample_given_receptor(copies, init_pharm_com=com, visualize_trajectory=args.visualize_trajectory,
                                                   pin_resamples=args.pin_resamples, pin_jump=args.pin_jump,
                                                   restraints=[args.restraint_list] * n if args.restraint_list else None,
-                                                  guide_scale=args.guide_scale, guide_clip=args.guide_clip,
+                                                  guide_scale=args.guide_scale, guide_clip=args.guide_clip, guide_family=args.guide_family,
                                                   seeds=[args.seed_centers] * n if args.seed_centers is not None else None, seed_level=args.seed_level,
                                                   seed_keep=[args.seed_keep_list] * n if args.seed_keep_list else None,
                                                   sample_steps=args.sample_steps, sampler=args.sampler, eta=args.eta, spacing=args.spacing)

@@ -292,7 +292,10 @@ int pf_sample_pinned_resampled(pf_handle* h, int32_t n_ops, const int32_t* host_
  * per operation.  Features are not guided (h_s is the plain update).  D[g] is a constant for d(y)/d(x_t), and the edge sets carry
  * no gradient (pf_train_backward_inputs).  A graph without restraints has g0 = 0 and, in the noise parameterisation, shift = 0
  * exactly.
- * The handle must be on PF_TRAIN_FAMILY_WIDE (otherwise PF_ERR_STATE: call pf_train_set_family first); a 128 / 16 handle's unguided
+ * The handle must be on PF_TRAIN_FAMILY_WIDE (otherwise PF_ERR_STATE: call pf_train_set_family first) -- or, a 128 / 16 handle, on
+ * PF_TRAIN_FAMILY_TUNED with pf_train_set_input_grads(h, 1): the step's training forward and inputs-only backward then run on the
+ * tuned kernels (fp32; PF_ERR_ARG with PF_TRAIN_BF16 selected).  The run records the family and the switch it began on, and a step
+ * after either changed is PF_ERR_STATE.  A 128 / 16 handle's unguided
  * runs stay on the tuned kernels.  pf_sample_begin_guided takes pf_sample_begin_pinned's arguments and HOST arrays restr_ptr[B+1]
  * (graph g owns restraints [restr_ptr[g], restr_ptr[g+1])), restr_kind[n], restr_center[n], restr_p[n][3], restr_r[n], restr_w[n].
  * Everything is validated on the host before anything is enqueued (kind, center range, finite p, r / w / scale / clip >= 0, at most
@@ -447,18 +450,21 @@ int pf_train_backward(pf_handle* h, const float* dev_g_eps_h /*[Nf,pharm_nf]*/, 
  * feature rows as passed to pf_train_forward.  Either output pointer may be NULL; with both NULL the call IS pf_train_backward.
  * Every element of a requested output is stored (nothing is accumulated), on the caller's stream, the same bits on every run.
  * The edge sets are piecewise constant in the coordinates and carry no gradient (as torch on the reference); t and the protein
- * coordinates get none.  Width-generic training leg only (pf_train_set_family(h, PF_TRAIN_FAMILY_WIDE): fp32, every supported
- * width, a 128 / 16 handle included): on the tuned family a non-NULL output pointer is PF_ERR_ARG, nothing is launched and the
- * kept forward stays good for pf_train_backward.  The forward keeps its own copy of the coordinates: the caller's buffers need
- * not outlive pf_train_forward. */
+ * coordinates get none.  On the width-generic training leg (pf_train_set_family(h, PF_TRAIN_FAMILY_WIDE): fp32, every supported
+ * width, a 128 / 16 handle included), and on the tuned family once pf_train_set_input_grads(h, 1) is set (fp32): without that
+ * switch a non-NULL output pointer on the tuned family is PF_ERR_ARG, nothing is launched and the kept forward stays good for
+ * pf_train_backward.  The forward keeps its own copy of the coordinates: the caller's buffers need not outlive pf_train_forward.
+ * The parameter gradient has the bits pf_train_backward gives, with the switch on or off. */
 int pf_train_backward_inputs(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad /*[n_params]*/,
                              float* dev_g_pharm_x /*[Nf,3] or NULL*/, float* dev_g_pharm_h /*[Nf,pharm_nf] or NULL*/, pf_stream stream);
 /* The gradients w.r.t. the inputs ALONE: pf_train_backward_inputs without the parameter gradient (what a guided sampling step
  * needs).  Nothing of the weight-gradient work is done -- the workgroups' gradient copies are neither cleared nor summed, and the
  * gradient kernels run in a form without their weight-gradient products.  Same preconditions as pf_train_backward_inputs (wide
- * family, a kept pf_train_forward; it may be called any number of times on one forward, before or after a full backward); at least
- * one output must be non-NULL (else PF_ERR_ARG).  Every element of a requested output is stored, with the bits
- * pf_train_backward_inputs stores. */
+ * family, or the tuned one with pf_train_set_input_grads; a kept pf_train_forward; it may be called any number of times on one
+ * forward, before or after a full backward); at least one output must be non-NULL (else PF_ERR_ARG).  Every element of a
+ * requested output is stored, with the bits pf_train_backward_inputs stores.  On the tuned family the reduces and the encoders'
+ * protein tiles are left out, but the gradient kernels run in their full form: their weight-gradient products land in the
+ * workgroups' gradient copies, which nobody sums (a later full backward stores every copy it reads anew). */
 int pf_dynamics_input_vjp(pf_handle* h, const float* dev_g_eps_h /*[Nf,pharm_nf]*/, const float* dev_g_eps_x /*[Nf,3]*/,
                           float* dev_g_pharm_x /*[Nf,3] or NULL*/, float* dev_g_pharm_h /*[Nf,pharm_nf] or NULL*/, pf_stream stream);
 /* The loss around the dynamics, fused (PharmacophoreDiff.forward, pharmacodiff.py:162-243; pf_train_loss_forward: the noise
@@ -537,6 +543,20 @@ int pf_train_get_precision(pf_handle* h, int32_t* precision);
 #define PF_TRAIN_FAMILY_WIDE 1
 int pf_train_set_family(pf_handle* h, int32_t family);
 int pf_train_get_family(pf_handle* h, int32_t* family);
+/* Input gradients on the tuned family (off after pf_create).  On, with PF_TRAIN_FAMILY_TUNED and PF_TRAIN_F32 selected,
+ * pf_train_backward_inputs fills dev_g_pharm_x / dev_g_pharm_h, pf_dynamics_input_vjp runs the tuned backward without a parameter
+ * gradient, and pf_sample_begin_guided / pf_denoise_step_guided / pf_sample_guided accept the handle: a guided step is then the
+ * tuned training forward at dropout 0, k_guide_grad, the tuned inputs-only backward and the sampler update.  How: the level-0
+ * launch of every conv layer's message chains (k_bwd_edge_level) also leaves dL/d(x_src - x_dst) per edge slot, which one launch
+ * sums per center in a fixed order (fp64 lanes, no atomics: the same bits on every run); the encoders' backward stores
+ * dL/d(feature rows).  With PF_TRAIN_BF16 selected these entries answer PF_ERR_ARG before anything is launched (call
+ * pf_train_set_precision(h, PF_TRAIN_F32)); the kept forward stays usable.  The switch means nothing on the wide family, which
+ * always has input gradients, and changes no bit of a parameter gradient.  It owns its buffer ([n_convs][edge slots][3] floats,
+ * cleared per pass, grown like a run's scratch), released when switched off (which waits for the device).  A guided run records
+ * the family and the switch it began on: a step after either changed is PF_ERR_STATE.  Off, every entry behaves as before the
+ * switch existed.  on must be 0 or 1 (else PF_ERR_ARG; PF_ERR_ARG also for a NULL handle). */
+int pf_train_set_input_grads(pf_handle* h, int32_t on);
+int pf_train_get_input_grads(pf_handle* h, int32_t* on);
 /* tests: make the following pf_train_forward / pf_train_backward calls on this batch use the given multipliers
  * [n_convs][2][N][144] -- under PF_TRAIN_FAMILY_WIDE [n_convs][2][N][n_hidden_scalars + vector_size] -- (layout of
  * pf_debug_dropout_mask) instead of the built-in generator; NULL restores it.  The library cannot see the buffer's size.  The

@@ -116,8 +116,10 @@ void pfk_wt_chain(const WtChainParams* p, int edge, int wgrad, hipStream_t s);
 void pfk_wt_norm(const WtNormParams* p, int wgrad, hipStream_t s);
 void pfk_wt_head_out(const WtHeadOutParams* p, int wgrad, hipStream_t s);
 void pfk_wt_encode(const WtEncParams* p, int wgrad, hipStream_t s);
-void pfk_wt_center_sum(const WtCenterSumParams* p, hipStream_t s);
 void pfk_wt_reduce(const float* gpart, int gstride, float* grad, int nparams, hipStream_t s);
+// both training families (pf_wide_train.hip; the kernel reads the edge-slot layout they share): dL/d(center coordinates) from the
+// per-edge dL/d(x_src - x_dst) rows their level-0 launches leave
+void pfk_wt_center_sum(const WtCenterSumParams* p, hipStream_t s);
 }
 
 namespace {
@@ -411,6 +413,7 @@ struct pf_handle {
     float guide_scale = 0.f, guide_clip = 0.f;
     void* d_guide = nullptr; size_t guide_capacity = 0;
     float *d_g0 = nullptr, *d_gjx = nullptr, *d_ggrad = nullptr, *d_gshift = nullptr, *d_gzero = nullptr, *d_genergy = nullptr, *d_gD = nullptr;
+    bool guide_wide = true, guide_in_grads = false;   // the training family and the input-gradient switch the guided run began on
     bool guide_have = false;                // a guided step has run on this batch: pf_debug_last_guidance has something to return
     float* guide_traj_energy = nullptr;     // pf_sample_guided: row i of the caller's [n_steps][B] for the step in flight
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
@@ -514,6 +517,11 @@ struct pf_handle {
     // pf_train_set_family: the width-generic training leg (pf_wide.hip's training form, pf_wide_train.hip) and its workspace --
     // like d_tws one allocation that outlives the batch, carved again for every new batch (ensure_wide_train_ws)
     bool train_wide = false;
+    // pf_train_set_input_grads: the tuned family's fp32 backward also gives dL/d(center coordinates, feature rows).  The switch owns
+    // d_gdiff, the per-edge dL/d(x_src - x_dst) rows [n_convs][max(Ecap, 1)][3] of a pass's level-0 launches: cleared per pass, kept
+    // and grown like a run's scratch (grow_run_scratch), released when the switch goes off
+    bool train_in_grads = false;
+    void* d_gdiff = nullptr; size_t gdiff_capacity = 0;
     // a handle of the specialised widths carries no width-generic packing (inference stays on the tuned kernels): its wide training
     // leg builds the WideGvp table on first use (ensure_wide_pack) -- Wh, Wu and the biases read from d_flat as stored, to_feats_out
     // and the gate Linear packed on the device into d_wpk whenever w_version moved
@@ -1515,6 +1523,7 @@ void pf_destroy(pf_handle* h) {
     if (h->d_ms_hist) (void)hipFree(h->d_ms_hist);
     if (h->d_restr) (void)hipFree(h->d_restr);
     if (h->d_guide) (void)hipFree(h->d_guide);
+    if (h->d_gdiff) (void)hipFree(h->d_gdiff);
     if (h->restr_stage) (void)hipHostFree(h->restr_stage);
     if (h->restr_ev) (void)hipEventDestroy(h->restr_ev);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
@@ -2918,11 +2927,12 @@ static WtNormParams wt_norm_params(const pf_handle* h, const LayerTiles& lt, int
     n.stream = l * 2 + which; n.use_norm = which ? 0 : 1;
     return n;
 }
-// the centers' sums of the per-edge dL/d(x_src - x_dst) rows of every conv layer
-static WtCenterSumParams wt_center_sum_params(const pf_handle* h, float* g_x) {
+// the centers' sums of the per-edge dL/d(x_src - x_dst) rows of every conv layer (g_diff [n_convs][layer_stride][3]: the wide leg's
+// or the tuned family's -- the kernel reads the edge-slot layout the two share)
+static WtCenterSumParams wt_center_sum_params(const pf_handle* h, const float* g_diff, size_t layer_stride, float* g_x) {
     WtCenterSumParams p{};
     p.Np = h->Np; p.Nf = h->Nf; p.N = h->N; p.B = h->B; p.L = h->cfg.n_convs;
-    p.g_diff = h->wt.gdiff; p.layer_stride = h->wt.Es;
+    p.g_diff = g_diff; p.layer_stride = layer_stride;
     p.in_start = h->d_in_start; p.in_cnt = h->d_in_cnt; p.reg = h->d_reg; p.dyn_cnt = h->d_dyn_cnt;
     p.esrc = h->d_esrc; p.gid = h->d_gid; p.g_x = g_x;
     return p;
@@ -3022,7 +3032,7 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
         pfk_wt_encode(&p, wg, s);
     }
     if (g_x) {
-        const WtCenterSumParams p = wt_center_sum_params(h, g_x);
+        const WtCenterSumParams p = wt_center_sum_params(h, w.gdiff, w.Es, g_x);
         pfk_wt_center_sum(&p, s);
     }
     if (full) pfk_wt_reduce(w.gpart, wc.gstride, dev_grad, (int)h->nparams, s);
@@ -3036,6 +3046,10 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
 // named for what it launches, every parameter struct has one builder, and which tiles a layer walks is layer_tiles' to say.
 struct BwdCall {
     pf_handle* h; hipStream_t s; const float *g_eps_h, *g_eps_x;
+    // pf_train_set_input_grads: dL/d(center coordinates) [Nf][3], dL/d(center feature rows) [Nf][pharm_nf], or NULL.  full: the pass
+    // has a parameter gradient to give (false: pf_dynamics_input_vjp and the guided step -- no reduce, early or final, and the
+    // encoders' backward only for g_h, on its center tiles)
+    float *g_x, *g_h; bool full;
     bool side_on;                           // the side stream is another stream than the caller's (always, unless the caller passes it)
     TrainCommon tc;                         // h->t_common with this call's k_pack_gvp tables
     ReduceParams rp;                        // the final reduce; the early one is a copy with its own class mask
@@ -3045,6 +3059,8 @@ struct BwdCall {
     unsigned early_mask;                    // classes the early reduce summed
 };
 static int bwd_grid(int nb, int ntiles) { return ntiles > 0 ? std::max(1, std::min(nb, 2 * ntiles)) : 0; }
+// edge slots per conv layer in d_gdiff
+static size_t gdiff_layer_stride(const pf_handle* h) { return (size_t)std::max<int64_t>(h->Ecap, 1); }
 // (the encoders' backward differentiates the protein rows grouped by (graph, element) when the features can be one-hots)
 static bool enc_grouped(const pf_handle* h) { return h->cfg.rec_nf <= 16 && h->Np > 0; }
 // which gradient copies hold what: the grid of every launch of the pass, known before the first one
@@ -3090,6 +3106,13 @@ static void bwd_work_lists(BwdCall& bc, int l, hipStream_t on) {
     pfk_compact_node_rows(lt.ntiles, lt.n_ntiles, h->d_dyn_cnt, h->d_act_ids, h->N, h->t_ulist + h->t_ulist_cap * l, h->t_ucap, h->t_ccnt + 96 + 4 * l, on);
     pfk_compact_rows(lt.etiles, lt.et_tile0, lt.n_et, h->d_dyn_cnt, h->t_clist + h->t_clist_cap * l, h->t_ccnt + 16 * l, on);
 }
+// The per-edge dL/d(x_src - x_dst) rows of all conv layers: a level-0 launch stores the rows of the slots it walks, the others (the
+// last layer's fp slots, slots past a region's live count) must read as zeros in the centers' sums.  Cleared once per pass, in the
+// batch that clears the last layer's input gradients
+static void bwd_add_gdiff_clear(const BwdCall& bc, ZeroBatch& zb) {
+    const pf_handle* h = bc.h;
+    if (bc.g_x) zb.add(h->d_gdiff, (size_t)h->cfg.n_convs * gdiff_layer_stride(h) * 3 * sizeof(float));
+}
 // The work lists depend on the forward's edge counts only: they are built on the side stream while the head's backward runs on
 // the caller's.  Two groups: what the first layer of the loop needs at once (its work lists, its cleared input gradients: cmp_ev[1]),
 // then the rest (the fixed-point scale, first read by that layer's edge kernels; the other layers' lists: cmp_ev[2], waited for
@@ -3109,6 +3132,7 @@ static int bwd_side_lists(BwdCall& bc) {
         ZeroBatch zb(side);
         zb.add(h->t_G_h[1], (size_t)h->N * PF_S * 4);
         if (L - 1 != 0) zb.add(h->t_G_v[1], (size_t)h->N * 48 * 4);
+        bwd_add_gdiff_clear(bc, zb);
         zb.flush();
         bc.first_clear_done = true;
         PF_HIP(h, hipEventRecord(h->cmp_ev[1], side));
@@ -3169,6 +3193,7 @@ static void bwd_node_launch(BwdCall& bc, int l) {
         ZeroBatch zb(bc.s);
         zb.add(h->t_G_h[bc.a ^ 1], (size_t)h->N * PF_S * 4);
         if (l != 0) zb.add(h->t_G_v[bc.a ^ 1], (size_t)h->N * 48 * 4);      // (conv layer 0 has no vector input: nobody writes or reads that gradient)
+        if (last) bwd_add_gdiff_clear(bc, zb);
         zb.flush();
     }
     const BwdNodeParams n = bwd_node_params(bc, l);
@@ -3195,7 +3220,7 @@ static BwdEdgeLevelParams bwd_edge_params(const BwdCall& bc, int l) {
     e.sv_stride = (size_t)std::max<int64_t>(h->Ecap, 1);
     e.gs_buf = h->t_gs_buf; e.gv_buf = h->t_gv_buf;
     e.g = h->d_gvpt + h->msg_base(l, 0); e.n_gvps = c.n_message_gvps;
-    rbf_params(c, e.rbf_mu, &e.rbf_inv_sigma);
+    e.rbf_sigma = rbf_params(c, e.rbf_mu, &e.rbf_inv_sigma);
     e.l0 = l == 0;
     e.A_h = h->t_A_h; e.A_v = h->t_A_v; e.fix = h->t_fix;
     e.wpack = h->d_wpack + (size_t)h->msg_base(l, 0) * PFT_WPACK_FLOATS;
@@ -3208,6 +3233,8 @@ static void bwd_edge_levels(BwdCall& bc, int l) {
     for (int lv = nm - 1; lv >= 0; --lv) {
         e.level = lv;
         e.fx = h->no_fixed_shapes ? 0 : h->po.edge_fx[(size_t)l * nm + lv];
+        // level 0 with dL/d(center coordinates) asked for: the launch with the geometry epilogue, into this layer's rows of d_gdiff
+        e.g_diff = (bc.g_x && lv == 0) ? (float*)h->d_gdiff + (size_t)l * gdiff_layer_stride(h) * 3 : nullptr;
         ProfScope ps(h, pf_handle::K_BWD_EDGE_LEVEL, bc.s);
         pfk_bwd_edge_level(&e, h->t_nblk, bc.s);
     }
@@ -3262,26 +3289,44 @@ static void bwd_encoders(BwdCall& bc) {
     p.G_h = h->t_G_h[bc.a];
     p.B = h->B; p.onehot_flag = h->d_l0flag;
     p.Gg = enc_grouped(h) ? h->t_Gg : nullptr;
-    if (p.Gg && !bc.enc_grouped_done) pfk_enc_group(p.G_h, h->d_prot_ptr, h->d_ptype, h->B, c.rec_nf, h->t_Gg, bc.s);
+    p.g_pharm_h = bc.g_h; p.pharm_only = bc.full ? 0 : 1;
+    if (p.Gg && !bc.enc_grouped_done && bc.full) pfk_enc_group(p.G_h, h->d_prot_ptr, h->d_ptype, h->B, c.rec_nf, h->t_Gg, bc.s);
     pfk_bwd_encode(&p, bc.rp.enc_grid, bc.s);
 }
+// dL/d(center coordinates): the centers' sums of the rows the level-0 launches left in d_gdiff
+static void bwd_center_sum(BwdCall& bc) {
+    const pf_handle* h = bc.h;
+    const WtCenterSumParams p = wt_center_sum_params(h, (const float*)h->d_gdiff, gdiff_layer_stride(h), bc.g_x);
+    pfk_wt_center_sum(&p, bc.s);
+}
 
-// pf_train_backward (g_pharm_x == g_pharm_h == NULL) and pf_train_backward_inputs; who: the entry, for the messages
-static int train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, float* g_pharm_x,
-                          float* g_pharm_h, pf_stream stream, const char* who) {
-    PF_TRAIN_WIDTH_GUARD(h, who);
-    int rc = check_ready(h, true);
-    if (rc) return rc;
-    if (!h->t_have_fwd) PF_FAIL(h, PF_ERR_STATE, "%s: no pf_train_forward on this batch", who);
-    if (!dev_g_eps_h || !dev_g_eps_x || !dev_grad) PF_FAIL(h, PF_ERR_ARG, "%s: null argument", who);
-    if (h->n_tseg < 0) PF_FAIL(h, PF_ERR_ARG, "%s: the gradient path supports n_convs <= 4", who);
-    if ((g_pharm_x || g_pharm_h) && !h->train_wide)      // refused before anything is launched: the kept forward stays usable
+// Input gradients on the tuned family (the wide family always has them): the switch, and fp32.  Refused before anything is
+// launched: the kept forward stays usable
+static int tuned_input_grads_guard(pf_handle* h, const char* who) {
+    if (h->train_wide) return PF_OK;
+    if (!h->train_in_grads)
         PF_FAIL(h, PF_ERR_ARG, "%s: gradients w.r.t. the center coordinates and features are computed by the width-generic training "
                                "leg only (pf_train_set_family(PF_TRAIN_FAMILY_WIDE), fp32, every supported width)", who);
-    if (h->train_wide) return wide_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, g_pharm_x, g_pharm_h, (hipStream_t)stream);
+    if (h->train_bf16)
+        PF_FAIL(h, PF_ERR_ARG, "%s: the tuned family's input gradients (pf_train_set_input_grads) are fp32 only: "
+                               "pf_train_set_precision(PF_TRAIN_F32) first", who);
+    return PF_OK;
+}
+// The tuned family's backward of the kept forward.  dev_grad == NULL: the inputs-only pass (pf_dynamics_input_vjp, a guided step) --
+// the same launches without the reduces (the kernels run in their full form: their weight-gradient products land in gradient
+// copies nobody sums) and the encoders' backward only for g_h.  g_x / g_h as in wide_train_backward; with both NULL and a dev_grad
+// the launches are the plain backward's
+static int tuned_train_backward(pf_handle* h, const float* g_eps_h, const float* g_eps_x, float* dev_grad, float* g_x, float* g_h,
+                                hipStream_t s) {
+    int rc;
     const int L = h->cfg.n_convs;
     BwdCall bc{};
-    bc.h = h; bc.s = (hipStream_t)stream; bc.g_eps_h = dev_g_eps_h; bc.g_eps_x = dev_g_eps_x;
+    bc.h = h; bc.s = s; bc.g_eps_h = g_eps_h; bc.g_eps_x = g_eps_x;
+    bc.g_x = g_x; bc.g_h = g_h; bc.full = dev_grad != nullptr;
+    if (g_x) {
+        const size_t need = (size_t)L * gdiff_layer_stride(h) * 3 * sizeof(float);
+        if ((rc = grow_run_scratch(h, &h->d_gdiff, &h->gdiff_capacity, need, need + need / 8, s)) != PF_OK) return rc;
+    }
     if ((rc = bwd_prologue(bc, dev_grad)) != PF_OK || (rc = bwd_side_lists(bc)) != PF_OK) return rc;
     bwd_head_launch(bc);
     if (bc.side_on) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[1], 0));       // the side stream's first group
@@ -3293,16 +3338,33 @@ static int train_backward(pf_handle* h, const float* dev_g_eps_h, const float* d
         if (last && bc.side_on) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[2], 0));      // the side stream's second group
         bwd_edge_levels(bc, l);
         bwd_fix_join(bc, l);
-        if (last && L >= 2 && bc.side_on && (rc = bwd_early_reduce(bc, l)) != PF_OK) return rc;
+        if (bc.full && last && L >= 2 && bc.side_on && (rc = bwd_early_reduce(bc, l)) != PF_OK) return rc;
     }
-    bwd_encoders(bc);
-    bc.rp.cls_mask = ~bc.early_mask;
-    pfk_train_reduce(&bc.rp, bc.s);
-    if (bc.early_mask) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[1], 0));       // the gradient is complete on the caller's stream
+    if (bc.full || bc.g_h) bwd_encoders(bc);
+    if (bc.g_x) bwd_center_sum(bc);
+    if (bc.full) {
+        bc.rp.cls_mask = ~bc.early_mask;
+        pfk_train_reduce(&bc.rp, bc.s);
+        if (bc.early_mask) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[1], 0));       // the gradient is complete on the caller's stream
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     h->tA_dirty = false;
     return PF_OK;
+}
+
+// pf_train_backward (g_pharm_x == g_pharm_h == NULL) and pf_train_backward_inputs; who: the entry, for the messages
+static int train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, float* g_pharm_x,
+                          float* g_pharm_h, pf_stream stream, const char* who) {
+    PF_TRAIN_WIDTH_GUARD(h, who);
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!h->t_have_fwd) PF_FAIL(h, PF_ERR_STATE, "%s: no pf_train_forward on this batch", who);
+    if (!dev_g_eps_h || !dev_g_eps_x || !dev_grad) PF_FAIL(h, PF_ERR_ARG, "%s: null argument", who);
+    if (h->n_tseg < 0) PF_FAIL(h, PF_ERR_ARG, "%s: the gradient path supports n_convs <= 4", who);
+    if ((g_pharm_x || g_pharm_h) && (rc = tuned_input_grads_guard(h, who)) != PF_OK) return rc;
+    if (h->train_wide) return wide_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, g_pharm_x, g_pharm_h, (hipStream_t)stream);
+    return tuned_train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, g_pharm_x, g_pharm_h, (hipStream_t)stream);
 }
 
 int pf_train_backward(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_grad, pf_stream stream) {
@@ -3315,7 +3377,7 @@ int pf_train_backward_inputs(pf_handle* h, const float* dev_g_eps_h, const float
     return train_backward(h, dev_g_eps_h, dev_g_eps_x, dev_grad, dev_g_pharm_x, dev_g_pharm_h, stream, __func__);
 }
 
-// The VJP of the dynamics w.r.t. the inputs of the kept forward alone: wide_train_backward without a parameter gradient
+// The VJP of the dynamics w.r.t. the inputs of the kept forward alone: the selected family's backward without a parameter gradient
 int pf_dynamics_input_vjp(pf_handle* h, const float* dev_g_eps_h, const float* dev_g_eps_x, float* dev_g_pharm_x, float* dev_g_pharm_h,
                           pf_stream stream) {
     PF_TRAIN_WIDTH_GUARD(h, __func__);
@@ -3325,9 +3387,8 @@ int pf_dynamics_input_vjp(pf_handle* h, const float* dev_g_eps_h, const float* d
     if (!dev_g_eps_h || !dev_g_eps_x) PF_FAIL(h, PF_ERR_ARG, "pf_dynamics_input_vjp: null argument");
     if (!dev_g_pharm_x && !dev_g_pharm_h) PF_FAIL(h, PF_ERR_ARG, "pf_dynamics_input_vjp: at least one of dev_g_pharm_x / dev_g_pharm_h must be given");
     if (h->n_tseg < 0) PF_FAIL(h, PF_ERR_ARG, "pf_dynamics_input_vjp: the gradient path supports n_convs <= 4");
-    if (!h->train_wide)
-        PF_FAIL(h, PF_ERR_ARG, "pf_dynamics_input_vjp: gradients w.r.t. the center coordinates and features are computed by the width-generic "
-                               "training leg only (pf_train_set_family(PF_TRAIN_FAMILY_WIDE), fp32, every supported width)");
+    if ((rc = tuned_input_grads_guard(h, __func__)) != PF_OK) return rc;
+    if (!h->train_wide) return tuned_train_backward(h, dev_g_eps_h, dev_g_eps_x, nullptr, dev_g_pharm_x, dev_g_pharm_h, (hipStream_t)stream);
     return wide_train_backward(h, dev_g_eps_h, dev_g_eps_x, nullptr, dev_g_pharm_x, dev_g_pharm_h, (hipStream_t)stream);
 }
 
@@ -3384,9 +3445,10 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     if (!dev_noise0) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null noise");
     if (!dev_pin_flags || !dev_pin_x || !dev_pin_h) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null pin array");
     if (!(feat_norm_constant > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: feat_norm_constant must be positive");
-    if (!h->train_wide)
+    if (!h->train_wide && !(h->spec && h->train_in_grads))
         PF_FAIL(h, PF_ERR_STATE, "pf_sample_begin_guided: a guided step runs the width-generic training forward and its input gradients: "
                                  "call pf_train_set_family(h, PF_TRAIN_FAMILY_WIDE) first");
+    if ((rc = tuned_input_grads_guard(h, "pf_sample_begin_guided")) != PF_OK) return rc;      // (the tuned family: fp32)
     if ((rc = guide_validate(h, host_restr_ptr, host_restr_kind, host_restr_center, host_restr_p, host_restr_r, host_restr_w, guide_scale,
                              guide_clip)) != PF_OK) return rc;
     if (const int lim = train_limits_ok(h)) return lim;
@@ -3429,25 +3491,31 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     h->guide_scale = guide_scale; h->guide_clip = guide_clip;
     h->guide_traj_energy = nullptr;
     h->run = RUN_GUIDED; h->guide_have = false;
+    h->guide_wide = h->train_wide; h->guide_in_grads = h->train_in_grads;
     return PF_OK;
 }
 
-// One denoising step of a guided run: the width-generic training forward (dropout 0: it keeps what the VJP reads), k_guide_grad, the
-// inputs-only backward with g_eps_x = g0 and the zero g_eps_h, k_step_update_guided.  The update runs alone: the width-generic
-// training forward builds its own edges on every call (run_dynamics_wide: `if (!h->edges_built)`, and it leaves edges_built false),
-// on a 128 / 16 handle too, so no form of this step builds the next call's edges and edges_built stays false behind it
+// One denoising step of a guided run: the training forward of the family the run began on (dropout 0: it keeps what the VJP reads),
+// k_guide_grad, that family's inputs-only backward with g_eps_x = g0 and the zero g_eps_h, k_step_update_guided.  The update runs
+// alone: the width-generic training forward builds its own edges on every call (run_dynamics_wide: `if (!h->edges_built)`, and it
+// leaves edges_built false), on a 128 / 16 handle too, and so does the tuned training forward (dyn_prologue's training forms), so no
+// form of this step builds the next call's edges and edges_built stays false behind it
 int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_coef* pin, const pf_guide_coef* gc, const float* dev_noise,
                            int32_t ep_coord, int32_t ep_feat, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!coef || !pin || !gc || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_guided: null argument");
     if ((rc = run_guard(h, __func__, RUN_GUIDED)) != PF_OK) return rc;
-    if (!h->train_wide) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_guided: the training family was switched inside the guided run (pf_train_set_family)");
+    if (h->train_wide != h->guide_wide) PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_guided: the training family was switched inside the guided run (pf_train_set_family)");
+    if (!h->train_wide && h->train_in_grads != h->guide_in_grads)
+        PF_FAIL(h, PF_ERR_STATE, "pf_denoise_step_guided: the input-gradient switch was changed inside the guided run (pf_train_set_input_grads)");
+    if (!h->train_wide && (rc = tuned_input_grads_guard(h, __func__)) != PF_OK) return rc;
     if (!(gc->alpha_t > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_denoise_step_guided: alpha_t must be positive");
     hipStream_t s = (hipStream_t)stream;
     const StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
     if ((rc = train_begin(h, 0.f, 0u, s, __func__)) != PF_OK) return rc;
     h->wt_common.mask_override = nullptr;       // dropout 0, whatever a test left in pf_debug_set_dropout_masks
+    h->t_common.mask_override = nullptr;
     ++h->step_id;
     h->edges_built = false; h->rec_valid = false;
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, true, nullptr);
@@ -3461,7 +3529,9 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     gq.com_init = h->d_com_init; gq.alpha_t = gc->alpha_t; gq.sigma_t = gc->sigma_t; gq.ep_coord = ep_coord;
     gq.g0 = h->d_g0; gq.energy = h->d_genergy; gq.traj_energy = h->guide_traj_energy; gq.D = h->d_gD;
     pfk_guide_grad(&sp, &gq, s);
-    if ((rc = wide_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s)) != PF_OK) return rc;
+    rc = h->train_wide ? wide_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s)
+                       : tuned_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s);
+    if (rc) return rc;
     const PinParams q = pin_params(h, pin);
     GuideShiftParams gs{};
     gs.g0 = h->d_g0; gs.jx = h->d_gjx; gs.D = h->d_gD; gs.alpha_t = gc->alpha_t; gs.sigma_t = gc->sigma_t;
@@ -3536,6 +3606,23 @@ int pf_train_set_family(pf_handle* h, int32_t family) {
     h->t_have_fwd = false;                       // a forward of the other family is not this backward's
     h->t_have_loss = false;
     h->t_ws_ready = false; h->wt_ready = false;  // (the two legs' workspaces share the loss-buffer fields: whoever runs next carves again)
+    return PF_OK;
+}
+
+int pf_train_set_input_grads(pf_handle* h, int32_t on) {
+    if (!h) return PF_ERR_ARG;
+    if (on != 0 && on != 1) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_input_grads: on must be 0 or 1");
+    if (!on && h->d_gdiff) {
+        (void)hipDeviceSynchronize();            // a pass in flight may still write the rows
+        (void)hipFree(h->d_gdiff); h->d_gdiff = nullptr; h->gdiff_capacity = 0;
+    }
+    h->train_in_grads = on != 0;                 // (a kept forward stays good: the forward is the same with the switch on or off)
+    return PF_OK;
+}
+
+int pf_train_get_input_grads(pf_handle* h, int32_t* on) {
+    if (!h || !on) return PF_ERR_ARG;
+    *on = h->train_in_grads ? 1 : 0;
     return PF_OK;
 }
 

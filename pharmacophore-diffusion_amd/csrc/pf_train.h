@@ -157,6 +157,9 @@ struct BwdEdgeLevelParams {
     const float* wpack;                      // k_pack_gvp input-gradient fragments of this layer's message GVPs [et][level][PFT_WPACK_FLOATS]
     float rbf_mu[PF_R]; float rbf_inv_sigma;
     int l0;
+    // level 0 with input gradients requested (pf_train_set_input_grads; k_bwd_edge_level's GX): dL/d(x_src - x_dst) of every valid
+    // row of an etype that touches a center (ff, pf, fp) is stored at g_diff[edge slot][3] of this conv layer; NULL: the GX = false kernels
+    float* g_diff; float rbf_sigma;
 };
 
 struct BwdEncodeParams {
@@ -169,6 +172,8 @@ struct BwdEncodeParams {
     int B;
     const float* Gg;                         // k_enc_group: G_h summed per (graph, element) [B][rec_nf][128], or NULL (rec_nf > 16)
     const int* onehot_flag;                  // device: 0 iff every protein feature row is an element one-hot (k_l0_types at bind time)
+    float* g_pharm_h;                        // dL/d(the centers' feature rows) [Nf][pharm_nf] (the t column is not an input), or NULL
+    int pharm_only;                          // the inputs-only pass: the protein tiles are not walked (nobody reads their weight gradients)
 };
 
 // the loss around the dynamics (k_loss_prepare / k_loss_eval, pf_train_loss_forward / _ep)
@@ -267,6 +272,7 @@ struct WtEncParams {
     const float* G_h;                        // dL/d(encoder output) [N][S]
     float* g_pharm_h;                        // dL/d(the centers' feature rows) [Nf][pharm_nf] (the t column is not an input), or NULL
 };
+// (both training families: k_bwd_edge_level<.., GX> leaves the same rows on the tuned one)
 // dL/d(center coordinates): per center the g_diff rows of its edges over all conv layers, in (layer, etype, slot) order -- minus
 // the rows of its ff and pf in-edges (the center is the destination: the in-edge ranges of the node update), plus the rows of
 // the ff and fp slots of its graph whose source it is (the graph's regions are walked and the source compared)

@@ -1296,7 +1296,18 @@ __device__ __forceinline__ void mmcol(const int mts, FA a, FB b, FC c, const int
 
 // FX: the level's GVP shape as compile-time constants (1: message GVPs above the first -- 16 vector channels in / hidden / out, 128
 // scalars in; 2: the first message GVP -- 17 channels in / hidden, 144 scalars in; 0: read from the table), BwdEdgeLevelParams::fx
-template <bool BF16, int FX>
+// GX only: diff [3], n2 and d of every row of the pass as the unpack phase computed them (the registers they came from are
+// overwritten by the fetch-ahead before the epilogue runs); the GX = false kernels have no such array
+template <bool GX>
+__device__ __forceinline__ float* e2_geo_lds() {
+    if constexpr (GX) {
+        __shared__ float geo[ER * 5];
+        return geo;
+    } else return nullptr;
+}
+// GX: the geometry epilogue of a level-0 launch (BwdEdgeLevelParams::g_diff; fp32, FX == 2 or 0 only).  GX = false is the kernel
+// without it, statement for statement
+template <bool BF16, int FX, bool GX>
 __global__ __launch_bounds__(NT, 1) void k_bwd_edge_level(const BwdEdgeLevelParams p) {
     __shared__ __attribute__((aligned(16))) float Zb[ER * E2_ZS];
     __shared__ __attribute__((aligned(16))) float Sin[ER * E2_SS];
@@ -1307,6 +1318,7 @@ __global__ __launch_bounds__(NT, 1) void k_bwd_edge_level(const BwdEdgeLevelPara
     __shared__ float sWh[32 * E2_WHS], sWu[32 * 16], sWg[16 * 128];
     __shared__ int s_src[ER], s_e[ER], s_tnv[E2_TILES];
     __shared__ int s_slot[E2_TILES * ER];            // edge slots of this round's passes (dense row list, k_compact_rows)
+    float* const s_geo = e2_geo_lds<GX>();
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
     const int tid_ = tid;
@@ -1320,6 +1332,9 @@ __global__ __launch_bounds__(NT, 1) void k_bwd_edge_level(const BwdEdgeLevelPara
         if ((int)blockIdx.x >= b0 && (int)blockIdx.x < b0 + nbk) { et = e; nb = nbk; my = blockIdx.x - b0; cnt_et = p.ccnt[e]; }
     }
     if (et < 0) return;                              // block-uniform: more gradient copies than work
+    // (GX: the block's place among its etype's blocks is uniform but selected per lane above; in a vector register it is the one
+    // value the FX == 0 form had no room for across the round loop)
+    if constexpr (GX) my = __builtin_amdgcn_readfirstlane(my);
     const int* rlist = p.clist + (size_t)(p.et_tile0[et] - p.et_tile0[0]) * 32;
     const int nrows = p.ccnt[8 + et];
     const GvpT g = p.g[et * p.n_gvps + p.level];
@@ -1458,6 +1473,10 @@ __global__ __launch_bounds__(NT, 1) void k_bwd_edge_level(const BwdEdgeLevelPara
                         const float d = t_sqrt(fmaxf(dx * dx + dy * dy + dz * dz, 1e-8f)) + 1e-8f;
                         const float rd = __builtin_amdgcn_rcpf(d);
                         Vin[tid * VWS + 0] = dx * rd; Vin[tid * VWS + 1] = dy * rd; Vin[tid * VWS + 2] = dz * rd;
+                        if constexpr (GX) {
+                            float* q = s_geo + tid * 5;
+                            q[0] = dx; q[1] = dy; q[2] = dz; q[3] = dx * dx + dy * dy + dz * dz; q[4] = d;
+                        }
                         for (int k = 0; k < PF_R; ++k) {
                             const float z = (d - p.rbf_mu[k]) * p.rbf_inv_sigma;
                             Sin[tid * E2_SS + PF_S + k] = __expf(-(z * z));
@@ -1704,7 +1723,8 @@ __global__ __launch_bounds__(NT, 1) void k_bwd_edge_level(const BwdEdgeLevelPara
                 // (as Vh -> Vu above); dWu on waves 6, 7
                 if (wv < 6) {
                     E2_PHASE();
-                    const bool want_vi = !(firstl && p.l0);          // conv layer 0 has no vector input: nobody reads gVi there
+                    // conv layer 0 has no vector input: nobody reads gVi there -- but the geometry epilogue, whose g_u is its channel 0
+                    const bool want_vi = GX || !(firstl && p.l0);
                     float bv[4];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) bv[u] = gVo[(rb + li) * VWS + (4 * u + kq) * 3 + cw];
@@ -1783,6 +1803,38 @@ __global__ __launch_bounds__(NT, 1) void k_bwd_edge_level(const BwdEdgeLevelPara
                         if (row < nv) p.gv_buf[(size_t)s_e[row] * 48 + q] = gVi[row * VWS + q];
                     }
                 } else {
+                    if constexpr (GX) {
+                        // The edge geometry's backward, one lane per valid row (pf_wide_train.hip: wt_edge_geometry has the
+                        // mathematics): g_rbf = gS[128 .. 143] and g_u = channel 0 of gVi, both UNSCALED (fix_scale belongs to the
+                        // scatter below); rbf as the unpack phase left it in Sin; the 19 products in fp64, rounded once
+                        if (et != ET_PP && tid < nv) {
+                            const int row = tid;
+                            const float* q = s_geo + row * 5;
+                            const float dx = q[0], dy = q[1], dz = q[2], n2 = q[3];
+                            // (sigma passes through an opaque copy and the sum over the centres stays a loop: converted to fp64 from the
+                            // kernel arguments, sigma and the centres are invariants of the pass loop that the compiler keeps in vector
+                            // registers across it, and unrolled the 16 fp64 quotients are in flight together -- either way the kernel,
+                            // which sits at 256 registers without the epilogue, spills)
+                            float sgf = p.rbf_sigma;
+                            asm volatile("" : "+v"(sgf));
+                            const double dd = (double)q[4], sg = (double)sgf;
+                            const float* g_rbf = gS + row * E2_SS + PF_S;
+                            const float* rbf = Sin + row * E2_SS + PF_S;
+                            const float* g_u = gVi + row * VWS;
+                            // (three fp64 quotients in all -- 1 / d, -2 / sigma^2, 1 / sqrt(n2) -- each needs a dozen registers while it runs)
+                            const double rd = 1.0 / dd, c2 = -2.0 / (sg * sg);
+                            double gd = 0.0;
+#pragma unroll 1
+                            for (int k = 0; k < PF_R; ++k) gd += (double)g_rbf[k] * (double)rbf[k] * (c2 * (dd - (double)p.rbf_mu[k]));
+                            gd -= ((double)g_u[0] * dx + (double)g_u[1] * dy + (double)g_u[2] * dz) * (rd * rd);
+                            const double m = n2 > 1e-8f ? gd / sqrt((double)n2) : 0.0;
+                            float* o = p.g_diff + (size_t)s_e[row] * 3;
+                            o[0] = (float)((double)g_u[0] * rd + m * dx);
+                            o[1] = (float)((double)g_u[1] * rd + m * dy);
+                            o[2] = (float)((double)g_u[2] * rd + m * dz);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);       // (the scatter's loads stay behind the epilogue: interleaved, one more register is live)
+                    }
                     for (int idx = tid; idx < ER * 128; idx += NT) {
                         const int row = idx >> 7, f = idx & 127;
                         if (row < nv) atomicAdd(reinterpret_cast<unsigned long long*>(p.A_h + (size_t)s_src[row] * PF_S + f),
@@ -1930,7 +1982,7 @@ __global__ __launch_bounds__(NT) void k_bwd_encode(const BwdEncodeParams p) {
     // upstream gradient is the sum over the atoms of that element (k_enc_group) -- 2,816 rows instead of 65,536 at config 5.
     const bool grouped = p.Gg != nullptr && p.onehot_flag[0] == 0;          // block-uniform
     const int n_prot_rows = grouped ? p.B * p.rec_nf : p.Np;
-    const int tiles_prot = (n_prot_rows + TR - 1) / TR, tiles_pharm = (p.Nf + TR - 1) / TR;
+    const int tiles_prot = p.pharm_only ? 0 : (n_prot_rows + TR - 1) / TR, tiles_pharm = (p.Nf + TR - 1) / TR;
     for (int ti = blockIdx.x; ti < tiles_prot + tiles_pharm; ti += gridDim.x) {
         const int nt = ti < tiles_prot ? 0 : 1;
         const int first = nt ? p.Np + (ti - tiles_prot) * TR : ti * TR;
@@ -1950,7 +2002,12 @@ __global__ __launch_bounds__(NT) void k_bwd_encode(const BwdEncodeParams p) {
                 const int r = idx >> 7, f = idx & 127;
                 if (r < nv && Gat(r, f) != 0.f) nz = 1;
             }
-            if (!__syncthreads_or(nz)) continue;       // block-uniform
+            if (!__syncthreads_or(nz)) {               // block-uniform
+                // (dL/dh_t of such center rows -- every row of a graph without restraints in a guided step -- is a stored zero)
+                if (nt && p.g_pharm_h)
+                    for (int idx = tid; idx < nv * nf; idx += NT) p.g_pharm_h[(size_t)(first - p.Np) * nf + idx] = 0.f;
+                continue;
+            }
         }
         for (int idx = tid; idx < TR * K; idx += NT) {
             const int row = idx / K, k = idx - row * K;
@@ -2005,6 +2062,13 @@ __global__ __launch_bounds__(NT) void k_bwd_encode(const BwdEncodeParams p) {
             }
         }
         __syncthreads();
+        if (nt && p.g_pharm_h)                  // dL/dh_t = dz W over the feature columns (o ascending), valid rows only
+            for (int idx = tid; idx < nv * nf; idx += NT) {
+                const int r = idx / nf, k = idx - r * nf;
+                float s = 0.f;
+                for (int o = 0; o < 128; ++o) s = fmaf(gq[r * ZS + o], W[ow + o * K + k], s);
+                p.g_pharm_h[(size_t)(first - p.Np + r) * nf + k] = s;
+            }
         for (int idx = tid; idx < 128 * K; idx += NT) {
             const int o = idx / K, k = idx - o * K;
             float s = 0.f;
@@ -2403,8 +2467,12 @@ void pfk_bwd_node(const BwdNodeParams* p, int nblocks, hipStream_t s) {
 void pfk_bwd_edge_level(const BwdEdgeLevelParams* p, int nblocks, hipStream_t s) {
     if (nblocks == 0 || p->et_tile0[p->n_et] == p->et_tile0[0]) return;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(NT), 0, s, *p); };
-    if (p->c.bf16) { if (p->fx == 1) go(k_bwd_edge_level<true, 1>); else if (p->fx == 2) go(k_bwd_edge_level<true, 2>); else go(k_bwd_edge_level<true, 0>); }
-    else { if (p->fx == 1) go(k_bwd_edge_level<false, 1>); else if (p->fx == 2) go(k_bwd_edge_level<false, 2>); else go(k_bwd_edge_level<false, 0>); }
+    if (p->g_diff) {        // level 0 with the geometry epilogue (the host sets it there only, and never on the bf16 leg)
+        if (p->fx == 2) go(k_bwd_edge_level<false, 2, true>); else go(k_bwd_edge_level<false, 0, true>);
+        return;
+    }
+    if (p->c.bf16) { if (p->fx == 1) go(k_bwd_edge_level<true, 1, false>); else if (p->fx == 2) go(k_bwd_edge_level<true, 2, false>); else go(k_bwd_edge_level<true, 0, false>); }
+    else { if (p->fx == 1) go(k_bwd_edge_level<false, 1, false>); else if (p->fx == 2) go(k_bwd_edge_level<false, 2, false>); else go(k_bwd_edge_level<false, 0, false>); }
 }
 void pfk_compact_node_rows(const NodeTile* tiles, int ntiles, const int* dyn_cnt, const int* row_ids, int N, int* list, int cap, int* ucnt,
                            hipStream_t s) {

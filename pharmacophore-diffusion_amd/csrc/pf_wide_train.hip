@@ -607,6 +607,7 @@ __global__ __launch_bounds__(256) void k_wt_encode(const WtEncParams p) {
 }
 
 // one wave per center (WtCenterSumParams): every lane takes every 64th slot of a range, fp64 partial sums, one fixed tree at the end
+// (also the tuned family's, pf_train_set_input_grads: it reads nothing of the wide workspace but g_diff, which the caller names)
 __global__ __launch_bounds__(256) void k_wt_center_sum(const WtCenterSumParams p) {
     const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= p.Nf) return;

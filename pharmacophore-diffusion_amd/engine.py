@@ -201,7 +201,8 @@ class PfEngine:
     def train_backward(self, g_eps_h, g_eps_x, input_grads=False):
         """d(loss)/d(parameters) as one flat vector (see param_layout) given d(loss)/d(eps).  input_grads: also the gradient
         w.r.t. the inputs of the last train_forward -- returns (grad, g_x_t [Nf, 3], g_h_t [Nf, pharm_nf]); True asks for both,
-        a pair of flags (x_t, h_t) for either (the other comes back as None).  Wide training family only."""
+        a pair of flags (x_t, h_t) for either (the other comes back as None).  On the wide training family, or on the tuned one
+        (fp32) with set_train_input_grads(True)."""
         gh, gx = _f32(g_eps_h, self.device), _f32(g_eps_x, self.device)
         if not hasattr(self, "n_params"):
             self.param_layout()
@@ -221,7 +222,8 @@ class PfEngine:
     def input_vjp(self, g_eps_h, g_eps_x, want=(True, True)):
         """The gradients of sum(eps_h * g_eps_h) + sum(eps_x * g_eps_x) w.r.t. the inputs of the last train_forward ALONE
         (pf_dynamics_input_vjp): (g_x_t [Nf, 3], g_h_t [Nf, pharm_nf]), None where ``want`` says no.  No parameter gradient is
-        formed; the bits are those of train_backward(..., input_grads=...).  Wide training family only."""
+        formed; the bits are those of train_backward(..., input_grads=...).  On the wide training family, or on the tuned one
+        (fp32) with set_train_input_grads(True)."""
         gh, gx = _f32(g_eps_h, self.device), _f32(g_eps_x, self.device)
         g_x_t = torch.empty(self.Nf, 3, device=self.device) if want[0] else None
         g_h_t = torch.empty(self.Nf, self.pharm_nf, device=self.device) if want[1] else None
@@ -329,6 +331,45 @@ class PfEngine:
         out = ctypes.c_int32(0)
         self._ck(self.lib.pf_train_get_family(self._h, ctypes.byref(out)), "pf_train_get_family")
         return "wide" if out.value == 1 else "tuned"
+
+    def set_train_input_grads(self, on):
+        """Input gradients on the tuned training family (pf_train_set_input_grads; off by default): train_backward(...,
+        input_grads=...), input_vjp and guided runs then work on a 128 / 16 handle's tuned kernels, fp32 only.  The wide family
+        always has them; switched off, the buffers the switch owns are released."""
+        self._ck(self.lib.pf_train_set_input_grads(self._h, 1 if on else 0), "pf_train_set_input_grads")
+
+    def train_input_grads(self):
+        out = ctypes.c_int32(0)
+        self._ck(self.lib.pf_train_get_input_grads(self._h, ctypes.byref(out)), "pf_train_get_input_grads")
+        return bool(out.value)
+
+    GUIDE_FAMILIES = ("wide", "tuned")
+
+    def _check_guide_family(self, guide_family):
+        """The kernel family of a guided run's steps: 'wide' (default) or 'tuned' (a 128 / 16 handle's tuned training forward and
+        input gradients).  Checked here, before any library call."""
+        if guide_family not in self.GUIDE_FAMILIES:
+            raise ValueError(f"guide_family must be 'wide' or 'tuned', got {guide_family!r}")
+        if guide_family == "tuned" and (self.cfg.n_hidden_scalars, self.cfg.vector_size) != (128, 16):
+            raise ValueError("guide_family='tuned' needs the tuned kernels' widths (n_hidden_scalars 128 / vector_size 16); this engine has "
+                             f"{self.cfg.n_hidden_scalars} / {self.cfg.vector_size}: use guide_family='wide'")
+        return guide_family
+
+    def _arm_guide_family(self, guide_family):
+        """Select the training family (and, for 'tuned', the input-gradient switch) of a guided run; returns what to hand to
+        _restore_guide_family."""
+        before = (self.train_family(), self.train_input_grads())
+        if before[0] != guide_family:
+            self.set_train_family(guide_family)
+        if guide_family == "tuned" and not before[1]:
+            self.set_train_input_grads(True)
+        return before
+
+    def _restore_guide_family(self, before):
+        if self.train_input_grads() != before[1]:
+            self.set_train_input_grads(before[1])
+        if self.train_family() != before[0]:
+            self.set_train_family(before[0])
 
     def mask_columns(self):
         """columns of a dropout-mask row: n_hidden_scalars + vector_size on the wide training leg, 144 on the tuned one"""
@@ -478,16 +519,25 @@ class PfEngine:
                                                   _stream_ptr()), "pf_sample_seed_next")
 
     def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0, restraints=None, guide_scale=1.0,
-                     guide_clip=0.0, seed=None):
+                     guide_clip=0.0, seed=None, guide_family=None):
         """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the begin.
         pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
         denoise_step(..., pin_coef=...); feat_norm_constant is what the given feature rows are divided by.
         restraints (one list or None per graph, see _restraints): a guided run (pf_sample_begin_guided) -- its steps are
-        guided_step; the caller has selected the wide training family (set_train_family('wide')); pins are optional."""
+        guided_step; the caller has selected the wide training family (set_train_family('wide')); pins are optional.
+        guide_family 'wide' / 'tuned' (guided runs only; None: the caller has selected the family): selects that training family --
+        for 'tuned', a 128 / 16 handle, also the input-gradient switch -- and leaves it selected: the run's steps need it, and the
+        caller restores what it had once the run has ended."""
+        if guide_family is not None:
+            self._check_guide_family(guide_family)
+            if restraints is None:
+                raise ValueError("guide_family applies to guided runs (restraints=...)")
         nz = _f32(noise0, self.device)
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         self._keep = [nz, com]
         pin, restr, _alive = self._run_inputs(pins, restraints)
+        if guide_family is not None:
+            self._arm_guide_family(guide_family)
         if seed is not None:
             self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
         with torch.cuda.device(self.device):
@@ -574,7 +624,8 @@ class PfEngine:
 
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
                feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None, restraints=None,
-               guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False, seed=None, ms_coef_arr=None):
+               guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False, seed=None, ms_coef_arr=None,
+               guide_family="wide"):
         """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the run -- n_steps is
         then the seed's level a, and coef_arr (and the other per-step arrays) hold the entries of s = a-1 .. 0.
         pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned.
@@ -583,10 +634,13 @@ class PfEngine:
         restraints (one list or None per graph, see _restraints) with pin_coef_arr and guide_coef_arr (guide_coef_array): a guided
         run, pf_sample_guided -- pins are optional, a plan is refused.  The run is made on the wide training family; the family
         the engine was on is restored afterwards, also on error.  energies: the restraint energies [n_steps, B] come back
-        behind the other outputs.
+        behind the other outputs.  guide_family='tuned' (a 128 / 16 handle, else ValueError before any call) makes the run on
+        the tuned training family with its input-gradient switch armed; family and switch are restored afterwards, also on error.
         ms_coef_arr (ms_coef_array): a multistep run, pf_sample_ms -- coef_arr is not read (None), noise needs its first row only
         (the initial draw), and the parameterisation is in the coefficients; seeds compose, pins, plans and restraints are refused."""
         guided = restraints is not None
+        if guide_family not in PfEngine.GUIDE_FAMILIES:
+            raise ValueError(f"guide_family must be 'wide' or 'tuned', got {guide_family!r}")
         if ms_coef_arr is not None:
             if pins is not None or plan is not None or guided:
                 raise ValueError("a multistep run composes with seeds only: no pins, resampling plan or restraints")
@@ -610,6 +664,8 @@ class PfEngine:
             raise ValueError("guidance together with resampling jumps is not supported")
         if guided and (pin_coef_arr is None or guide_coef_arr is None):
             raise ValueError("a guided run needs pin_coef_arr (PfEngine.pin_coef_array) and guide_coef_arr (PfEngine.guide_coef_array)")
+        if guided:
+            self._check_guide_family(guide_family)
         nz = _f32(noise, self.device)
         assert nz.shape[0] >= n_steps + 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
         if pins is not None and pin_coef_arr is None:
@@ -632,6 +688,17 @@ class PfEngine:
             name, args = "pf_sample_pinned", (coef_arr, pin_coef_arr) + state + eps + outs
         else:
             name, args = "pf_sample", (coef_arr,) + state + eps + outs
+        if guided and guide_family == "tuned":     # the tuned training forward and its input gradients
+            before = self._arm_guide_family("tuned")
+            try:
+                if seed is not None:
+                    self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
+                with torch.cuda.device(self.device):
+                    self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
+            finally:
+                self._restore_guide_family(before)
+            out = (x0, h0, tx, th) if trajectory else (x0, h0)
+            return out + (en,) if energies else out
         family = self.train_family() if guided else "wide"       # a guided step runs the wide training forward and its input gradients
         if family != "wide":
             self.set_train_family("wide")

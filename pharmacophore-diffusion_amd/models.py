@@ -146,8 +146,8 @@ class _DynamicsFn(torch.autograd.Function):
     """PharmRecDynamicsGVP.forward as one autograd node: forward = pf_train_forward (train-mode dropout inside the
     kernels), backward = pf_train_backward, which returns d(loss)/d(parameter) for every parameter as one flat vector.
     x_t and h_t get their gradient too when they require one and the engine is on the wide training family
-    (set_train_family('wide'): pf_train_backward_inputs); on the tuned family they get None, with one warning per
-    process.  The edge sets are piecewise constant in x_t and carry no gradient, as in the reference; t and the protein
+    (set_train_family('wide'): pf_train_backward_inputs) or on the tuned one with set_train_input_grads(True); on the tuned
+    family without that switch they get None, with one warning per process.  The edge sets are piecewise constant in x_t and carry no gradient, as in the reference; t and the protein
     coordinates get none."""
 
     @staticmethod
@@ -173,11 +173,12 @@ class _DynamicsFn(torch.autograd.Function):
         want = (ctx.needs_input_grad[2], ctx.needs_input_grad[3])
         if not any(want):
             return (None,) * 8 + (eng.train_backward(g_h, g_x),)
-        if eng.train_family() != "wide":
+        if eng.train_family() != "wide" and not eng.train_input_grads():
             if not _warned_no_input_grads:
                 _warned_no_input_grads = True
                 warnings.warn("x_t / h_t require a gradient, but the tuned training family computes parameter gradients only: "
-                              "they get none.  set_train_family('wide') selects the family that differentiates the inputs.")
+                              "they get none.  set_train_family('wide') selects the family that differentiates the inputs; "
+                              "set_train_input_grads(True) makes the tuned family do it.")
             return (None,) * 8 + (eng.train_backward(g_h, g_x),)
         grads = eng.train_backward(g_h, g_x, input_grads=want)
         g_in = [None if g is None else g.to(device=like[2], dtype=like[1]).reshape(like[0])
@@ -274,6 +275,7 @@ class PharmRecDynamicsGVP(nn.Module):
             self._engine = PfEngine(device=dev, **self._arch)
             self._engine.set_train_precision(getattr(self, "train_precision", "f32"))
             self._engine.set_train_family(getattr(self, "train_family", "tuned"))
+            self._engine.set_train_input_grads(getattr(self, "train_input_grads", False))
             self._join_prefetch()
             self.__dict__["_twin"] = None           # (prefetch_graph makes a new one on this device)
             self._weights_stamp = None
@@ -318,6 +320,18 @@ class PharmRecDynamicsGVP(nn.Module):
         if twin is not None:
             self._join_prefetch()
             twin.set_train_family(self.train_family)
+
+    def set_train_input_grads(self, on: bool):
+        """Input gradients on the tuned training family (off by default): with it on, x_t / h_t that require a gradient get one
+        from the tuned kernels (fp32 only), as they do on the wide family.  Off, the tuned family gives them None with one
+        warning per process."""
+        self.train_input_grads = bool(on)
+        if self._engine is not None:
+            self._engine.set_train_input_grads(self.train_input_grads)
+        twin = self.__dict__.get("_twin")
+        if twin is not None:
+            self._join_prefetch()
+            twin.set_train_input_grads(self.train_input_grads)
 
     def lane_engine(self, lane: int) -> PfEngine:
         """Engine of sampling lane ``lane``: lane 0 is engine(); further lanes are extra handles (own workspace) that carry
@@ -495,6 +509,7 @@ class PharmRecDynamicsGVP(nn.Module):
             twin.load_state_dict({k: v for k, v in self.state_dict().items()}, prefix="")
             twin.set_train_precision(getattr(self, "train_precision", "f32"))
             twin.set_train_family(getattr(self, "train_family", "tuned"))
+            twin.set_train_input_grads(getattr(self, "train_input_grads", False))
             self.__dict__["_twin"] = twin
         stream = torch.cuda.current_stream(twin.device)
         pf = {"key": key, "static": static, "err": None}
@@ -771,7 +786,7 @@ class PharmacophoreDiff(_Base):
                               noise: torch.Tensor = None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None,
                               guide_scale: float = 1.0, guide_clip: float = 0.0, seeds=None, seed_level: int = None,
                               seed_keep=None, sample_steps: int = None, sampler: str = None, eta: float = None,
-                              spacing: str = None) -> List[SampledPharmacophore]:
+                              spacing: str = None, guide_family: str = "wide") -> List[SampledPharmacophore]:
         """Reverse diffusion for a batch of pocket graphs; the whole T-step loop is enqueued on the
         current HIP stream by pf_sample (no host synchronisation inside the loop).
 
@@ -789,7 +804,8 @@ class PharmacophoreDiff(_Base):
         and ``noise`` must then have n_ops + 1 rows.  A graph batch without a flag set ignores both.
 
         ``restraints``: None, or one list (or None) per graph of the batch of (kind, center, point, radius, weight) (see
-        ``sample``): with a restraint in it the run is pf_sample_guided with ``guide_scale`` / ``guide_clip``.
+        ``sample``): with a restraint in it the run is pf_sample_guided with ``guide_scale`` / ``guide_clip``, on the kernel
+        family ``guide_family`` names ('wide', the default, or 'tuned': see ``sample``).
 
         ``seeds`` with ``seed_level`` a (and optionally ``seed_keep``): a seeded run (pf_sample_seed_next) -- one (x [n,3], types
         [n]) per graph of the batch, n that graph's number of centers; the run starts from the seeds noised to level a and makes
@@ -799,6 +815,7 @@ class PharmacophoreDiff(_Base):
         ``sample_steps`` N with ``sampler`` / ``eta`` / ``spacing``: a few-step run (see ``sample``) -- ``noise`` has N + 1 rows for
         the first-order samplers and 1 row for 'multistep'; trajectories have N + 1 frames."""
         g = as_pocket_graph(g)
+        self._check_guide_family(guide_family)
         fewstep = self._fewstep(sample_steps, sampler, eta, spacing, pin_resamples=pin_resamples, seed_level=seed_level,
                                 pins=(g.pharm_pin is not None and bool((g.pharm_pin != 0).any())) or seed_keep is not None,
                                 restraints=restraints is not None and any(len(r) > 0 for r in restraints if r is not None))
@@ -825,7 +842,18 @@ class PharmacophoreDiff(_Base):
                                                                            pin_resamples=pin_resamples, pin_jump=pin_jump,
                                                                            restraints=restraints, guide_scale=guide_scale,
                                                                            guide_clip=guide_clip, seed_level=seed_level,
-                                                                           fewstep=fewstep)))
+                                                                           fewstep=fewstep, guide_family=guide_family)))
+
+    def _check_guide_family(self, guide_family):
+        """``guide_family`` of sample / sample_given_receptor, checked before any device work: 'wide' (default) or 'tuned', which
+        needs the tuned kernels' widths (n_hidden_scalars 128 / vector_size 16)."""
+        if guide_family not in PfEngine.GUIDE_FAMILIES:
+            raise ValueError(f"guide_family must be 'wide' or 'tuned', got {guide_family!r}")
+        arch = self.dynamics._arch
+        if guide_family == "tuned" and (arch.get("n_hidden_scalars", 128), arch.get("vector_size", 16)) != (128, 16):
+            raise ValueError("guide_family='tuned' needs n_hidden_scalars 128 / vector_size 16; this model has "
+                             f"{arch.get('n_hidden_scalars', 128)} / {arch.get('vector_size', 16)}: use guide_family='wide'")
+        return guide_family
 
     def _fewstep(self, sample_steps, sampler, eta, spacing, pin_resamples=1, seed_level=None, pins=False, restraints=False):
         """The few-step keywords of sample / sample_given_receptor, checked before any device work: None without sample_steps,
@@ -961,7 +989,7 @@ class PharmacophoreDiff(_Base):
 
     def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0,
                         pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0, guide_clip: float = 0.0,
-                        seed_level: int = None, fewstep=None):
+                        seed_level: int = None, fewstep=None, guide_family: str = "wide"):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
         current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  ``restraints``: None or one
         list (or None) per graph of the batch; a batch takes the guided path (pf_sample_guided) only when one of them holds a
@@ -1016,7 +1044,7 @@ class PharmacophoreDiff(_Base):
             if len(restraints) != g.batch_size:
                 raise ValueError(f"restraints lists {len(restraints)} entries for a batch of {g.batch_size} graphs")
             kw.update(restraints=restraints, guide_coef_arr=step_arrays("guide", top), guide_scale=float(guide_scale),
-                      guide_clip=float(guide_clip))
+                      guide_clip=float(guide_clip), guide_family=guide_family)
         if noise is None:
             noise = torch.randn(1 if ms else n_ops + 1, Nf, 3 + nf, device=dev)
         if lane == 0:
@@ -1098,7 +1126,7 @@ class PharmacophoreDiff(_Base):
                pinned=None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0,
                guide_clip: float = 0.0, seeds=None, seed_level: int = None, seed_keep=None,
                score_levels: int = None, sample_steps: int = None, sampler: str = None, eta: float = None,
-               spacing: str = None) -> List[List[SampledPharmacophore]]:
+               spacing: str = None, guide_family: str = "wide") -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -1128,6 +1156,8 @@ class PharmacophoreDiff(_Base):
         ``guide_scale`` times the posterior variance times the energy's gradient through the network, each center's shift
         clipped to ``guide_clip`` angstroms when that is positive); its steps run the width-generic training forward and its
         input gradients and cost several times a default step.  Batches without one run the default path.
+        ``guide_family``: 'wide' (the default) or 'tuned' -- a model of the tuned widths (128 / 16) then runs the guided steps'
+        training forward and input gradients on the tuned kernels; any other model is a ValueError.
         Composes with ``pinned``; together with ``pin_resamples`` > 1 it is a ValueError.
 
         ``seeds`` with ``seed_level`` a, 1 <= a <= T: variations of given pharmacophores (partial diffusion, pf_sample_seed_next)
@@ -1158,6 +1188,7 @@ class PharmacophoreDiff(_Base):
         as it is without.  None (the default): no scoring, ``.score`` stays None."""
         if score_levels is not None and not 1 <= int(score_levels) <= self.n_timesteps:
             raise ValueError(f"score_levels must satisfy 1 <= K <= {self.n_timesteps}, got {score_levels}")
+        self._check_guide_family(guide_family)
         fewstep = self._fewstep(sample_steps, sampler, eta, spacing, pin_resamples=pin_resamples, seed_level=seed_level,
                                 pins=pinned is not None and any(p is not None for p in pinned) or seed_keep is not None,
                                 restraints=restraints is not None and any(restraints))
@@ -1263,7 +1294,8 @@ class PharmacophoreDiff(_Base):
                 batch_r = [restraints[graph_ref_idx[i]] for i in idx] if restraints is not None else None
                 enq = self._sample_enqueue(batch_g, init_coms, visualize_trajectory, nz, lane=lane,
                                            pin_resamples=pin_resamples, pin_jump=pin_jump, restraints=batch_r,
-                                           guide_scale=guide_scale, guide_clip=guide_clip, seed_level=top, fewstep=fewstep)
+                                           guide_scale=guide_scale, guide_clip=guide_clip, seed_level=top, fewstep=fewstep,
+                                           guide_family=guide_family)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on

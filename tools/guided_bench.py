@@ -8,6 +8,7 @@ tools/pinned_bench.py's batch).  Legs, each on its own handle in this one proces
   wide      an unguided step of a handle created under PFDYN_WIDE=1: the width-generic INFERENCE forward + k_step_update.  The
             fair yardstick: a guided step's forward is the width-generic training forward
   guided    2 centers pinned, and per graph a repel sphere on all centers plus an attract on one
+  guided_tuned  the same run with guide_family="tuned": the tuned training forward and the tuned inputs-only backward
 The timed windows of --steps steps (HIP events around the window, after --warmup steps) alternate between the legs --rounds
 times; the figure of a leg is the median of its windows (all of them are listed: their spread is the tool's run-to-run spread).
 
@@ -17,6 +18,8 @@ Part 2, the backward alone, at that shape and at the config-5 shape of tools/inp
   vjp         pf_dynamics_input_vjp, g_x alone: no clear, no reduce, kernels without their weight-gradient products
   vjp_host    the same entry on a handle created under PFDYN_VJP_FULL_KERNELS=1: no clear, no reduce, but the full pass's kernels
               (what the host-level skip alone would give)
+  tuned_plain / tuned_full / tuned_vjp   a handle on the tuned family with pf_train_set_input_grads: pf_train_backward,
+              pf_train_backward_inputs with g_x, pf_dynamics_input_vjp with g_x (the full kernels without the reduces)
 HIP events around every call; per leg the median over all calls and the [smallest .. largest] median of consecutive chunks of 20.
 
     python tools/guided_bench.py [--out profiles/guided/guided_bench.json]"""
@@ -32,7 +35,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-LEGS = ("default", "pinned", "wide", "guided")
+LEGS = ("default", "pinned", "wide", "guided", "guided_tuned")
 
 
 class Leg:
@@ -64,18 +67,19 @@ class Leg:
         self.noise = torch.empty(n_all + 1, B * n_pharm, 9, device=dev).normal_(generator=gen)
         pins = restraints = None
         com = prot_x.reshape(B, n_prot, 3).mean(dim=1)
-        if name in ("pinned", "guided"):
+        guided = self.guided = name.startswith("guided")
+        if name == "pinned" or guided:
             flags = torch.zeros(B, n_pharm, dtype=torch.int32)
             flags[:, :args.n_pinned] = 3
             pin_x = (com[:, None] + 1.5 * torch.randn(B, n_pharm, 3, device=dev, generator=gen)).reshape(-1, 3)
             pin_h = torch.nn.functional.one_hot(torch.randint(0, 6, (B * n_pharm,), device=dev, generator=gen), 6).float()
             pins = (flags.reshape(-1), pin_x, pin_h)
-        if name == "guided":
-            eng.set_train_family("wide")
+        if guided:
             c = com.cpu()
             restraints = [[("repel", None, c[g].tolist(), 3.0, 1.0), ("attract", n_pharm - 1, (c[g] + 3.0).tolist(), 1.5, 1.0)]
                           for g in range(B)]
-        eng.sample_begin(self.noise[0], pins=pins, restraints=restraints, guide_scale=1.0, guide_clip=1.0)
+        eng.sample_begin(self.noise[0], pins=pins, restraints=restraints, guide_scale=1.0, guide_clip=1.0,
+                         guide_family={"guided": "wide", "guided_tuned": "tuned"}.get(name))
         self.pos = 0
         self.windows = []
 
@@ -83,7 +87,7 @@ class Leg:
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         for i in range(self.pos, self.pos + n):
-            if self.name == "guided":
+            if self.guided:
                 self.eng.guided_step(self.carr[i], self.parr[i], self.garr[i], self.noise[i + 1])
             else:
                 self.eng.denoise_step(self.carr[i], self.noise[i + 1], pin_coef=self.parr[i] if self.name == "pinned" else None)
@@ -123,9 +127,18 @@ def backward_legs(pfa, synthetic, batch, n_prot, sizes, dropout, calls, warmup):
         pp_src, pp_dst = eng.build_pp_edges(prot_x.to(dev), prot_ptr)
         eng.set_batch(prot_x, prot_h, prot_ptr, pharm_ptr, pp_src, pp_dst)
         eng.train_forward(x_t, h_t, t, dropout=dropout, seed=7)
+    tuned = engs["tuned"] = pfa.PfEngine(device=dev)
+    tuned.load_state_dict(synthetic.make_state_dict(0))
+    tuned.set_train_input_grads(True)
+    pp_src, pp_dst = tuned.build_pp_edges(prot_x.to(dev), prot_ptr)
+    tuned.set_batch(prot_x, prot_h, prot_ptr, pharm_ptr, pp_src, pp_dst)
+    tuned.train_forward(x_t, h_t, t, dropout=dropout, seed=7)
     calls_of = {"full": lambda: engs["this"].train_backward(w_h, w_x, input_grads=(True, False)),
                 "vjp": lambda: engs["this"].input_vjp(w_h, w_x, want=(True, False)),
-                "vjp_host": lambda: engs["host_skip"].input_vjp(w_h, w_x, want=(True, False))}
+                "vjp_host": lambda: engs["host_skip"].input_vjp(w_h, w_x, want=(True, False)),
+                "tuned_plain": lambda: tuned.train_backward(w_h, w_x),
+                "tuned_full": lambda: tuned.train_backward(w_h, w_x, input_grads=(True, False)),
+                "tuned_vjp": lambda: tuned.input_vjp(w_h, w_x, want=(True, False))}
     times = {k: [] for k in calls_of}
     for i in range(warmup + calls):
         for name, fn in calls_of.items():
@@ -137,7 +150,9 @@ def backward_legs(pfa, synthetic, batch, n_prot, sizes, dropout, calls, warmup):
             if i >= warmup:
                 times[name].append(a.elapsed_time(b))
     same = torch.equal(calls_of["full"]()[1], calls_of["vjp"]()[0]) and torch.equal(calls_of["vjp"]()[0], calls_of["vjp_host"]()[0])
-    out = {"shape": {"batch": B, "n_prot": n_prot, "centers": Nf, "dropout": dropout}, "g_x_bitwise_equal": bool(same)}
+    same_tuned = torch.equal(calls_of["tuned_full"]()[1], calls_of["tuned_vjp"]()[0])
+    out = {"shape": {"batch": B, "n_prot": n_prot, "centers": Nf, "dropout": dropout}, "g_x_bitwise_equal": bool(same),
+           "tuned_g_x_bitwise_equal": bool(same_tuned)}
     out.update({k: chunks(v) for k, v in times.items()})
     return out
 
@@ -172,6 +187,8 @@ def main():
     s = out["step"]
     for k in ("default", "pinned", "wide"):
         s[f"guided_over_{k}"] = round(s["guided"]["step_us"] / s[k]["step_us"], 3)
+    for k in ("default", "pinned", "guided"):
+        s[f"guided_tuned_over_{k}"] = round(s["guided_tuned"]["step_us"] / s[k]["step_us"], 3)
     del legs
     torch.cuda.empty_cache()
     out["backward_config2"] = backward_legs(pfa, synthetic, args.batch, args.n_prot, [args.n_pharm] * args.batch, 0.0, args.calls, 10)

@@ -7,6 +7,9 @@ Legs, each in a fresh process (the library is chosen when the package is importe
              and last, so that the spread the tool reports for it is a run-to-run one
   this       this tree's library: pf_train_backward ("none") and pf_train_backward_inputs with both outputs ("both"), the
              calls alternating
+  this, tuned  (--tuned) the same batch on the tuned family with pf_train_set_input_grads, in the "this" process: pf_train_backward
+             ("tuned none"), pf_train_backward_inputs with both outputs ("tuned both") and pf_dynamics_input_vjp ("tuned vjp": the
+             inputs-only mode -- the full kernels without the reduces)
 One training forward, then --warmup backward calls, then --calls timed ones per leg, HIP events around every call.  Per leg the
 median over all calls and the medians of consecutive chunks of 20 calls.  Writes profiles/input_grads/backward_cost.txt."""
 import argparse
@@ -52,12 +55,26 @@ def child(args):
     w_h, w_x = torch.randn(Nf, 6, generator=gen).cuda(), torch.randn(Nf, 3, generator=gen).cuda()
     eng.train_forward(x_t, h_t, t, dropout=0.1, seed=7)
     legs = {"none": False, "both": True} if (args.child == "this" and has_entry) else {"none": False}
-    times = {k: [] for k in legs}
+    calls = {name: ((lambda: eng.train_backward(w_h, w_x, input_grads=True)) if flag else (lambda: eng.train_backward(w_h, w_x)))
+             for name, flag in legs.items()}
+    if args.tuned and args.child == "this":
+        tuned = pfa.PfEngine(device="cuda:0", pharm_nf=6, rec_nf=11, vector_size=V, n_convs=2, n_hidden_scalars=S, message_norm='mean',
+                             ff_k=0, pf_k=5, n_message_gvps=3, n_update_gvps=2, n_noise_gvps=4,
+                             graph_cutoffs={'pp': 3.5, 'pf': 8, 'fp': 8, 'ff': 9})
+        tuned.load_state_dict({k: v for k, v in synthetic.make_state_dict(0, n_hidden_scalars=S, vector_size=V).items()
+                               if k.startswith("dynamics.")})
+        tuned.set_train_input_grads(True)
+        tuned.set_batch(prot_x, prot_h, prot_ptr, pharm_ptr, pp_src, pp_dst)
+        tuned.train_forward(x_t, h_t, t, dropout=0.1, seed=7)
+        calls.update({"tuned none": lambda: tuned.train_backward(w_h, w_x),
+                      "tuned both": lambda: tuned.train_backward(w_h, w_x, input_grads=True),
+                      "tuned vjp": lambda: tuned.input_vjp(w_h, w_x)})
+    times = {k: [] for k in calls}
     for i in range(args.warmup + args.calls):
-        for name, flag in legs.items():
+        for name, fn in calls.items():
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            eng.train_backward(w_h, w_x, input_grads=flag) if flag else eng.train_backward(w_h, w_x)
+            fn()
             b.record()
             torch.cuda.synchronize()
             if i >= args.warmup:
@@ -76,7 +93,7 @@ def run_child(args, which, lib):
     if lib:
         env["PFDYN_LIB"] = lib
     cmd = [sys.executable, os.path.abspath(__file__), "--child", which, "--calls", str(args.calls), "--warmup", str(args.warmup),
-           "--batch", str(args.batch), "--n-prot", str(args.n_prot)]
+           "--batch", str(args.batch), "--n-prot", str(args.n_prot)] + (["--tuned"] if args.tuned else [])
     out = subprocess.run(cmd, env=env, check=True, capture_output=True, text=True, timeout=args.child_timeout).stdout
     return json.loads(next(line for line in out.splitlines() if line.startswith("RESULT "))[7:])
 
@@ -89,6 +106,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--n-prot", type=int, default=256)
     ap.add_argument("--child-timeout", type=int, default=240)
+    ap.add_argument("--tuned", action="store_true", help="also the tuned family's legs (pf_train_set_input_grads)")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "input_grads", "backward_cost.txt"))
     args = ap.parse_args()
@@ -110,6 +128,11 @@ def main():
         rows[f"parent, run {i + 1} (pf_train_backward)"] = summary(p["times"]["none"])
     rows["this commit, no input gradients (pf_train_backward)"] = summary(this["times"]["none"])
     rows["this commit, both input gradients (pf_train_backward_inputs)"] = summary(this["times"]["both"])
+    for k, label in (("tuned none", "this commit, tuned family, no input gradients (pf_train_backward)"),
+                     ("tuned both", "this commit, tuned family, both (pf_train_backward_inputs)"),
+                     ("tuned vjp", "this commit, tuned family, inputs only (pf_dynamics_input_vjp)")):
+        if k in this["times"]:
+            rows[label] = summary(this["times"][k])
     for name, (med, lo, hi, n) in rows.items():
         lines.append(f"  {name:62s} {med:8.3f}   [{lo:.3f} .. {hi:.3f}]   {n} calls")
     none, both = rows["this commit, no input gradients (pf_train_backward)"][0], rows["this commit, both input gradients (pf_train_backward_inputs)"][0]
