@@ -52,6 +52,7 @@ _FLAGS = [
     ('--score_pharmacophores', dict(type=Path, default=None, help='no sampling: score every frame of this file (pharms.xyz format) against the pocket and write scores.tsv; --score_samples gives the number of levels (default: every level); with the --seed, --score_samples, --score_weighting and --max_batch_size of the run that wrote the file, and its frames in their order, this reproduces that run\'s scores.tsv (the noise of a score is drawn per device batch)')),
     ('--score_weighting', dict(choices=['uniform', 'vlb'], default=None, help='weights of the levels in a score: uniform (default; the per-graph training loss) or vlb (the diffusion terms of the variational bound)')),
     ('--metrics', dict(action='store_true', help='print the validity of the samples against receptor pharmacophore features')),
+    ('--use_ema', dict(action='store_true', help="sample from the checkpoint's EMA weights (its 'ema_state_dict', written by train.py with ema_decay set) instead of the training weights")),
 ]
 
 
@@ -204,11 +205,14 @@ def locate_run(args):
     raise FileNotFoundError(f'{run_dir} holds neither config.yaml nor config.yml')
 
 
-def load_model(pfa, ckpt, config, device):
+def load_model(pfa, ckpt, config, device, use_ema=False):
     try:
         model = pfa.PharmacophoreDiff.load_from_checkpoint(ckpt)
     except TypeError:              # checkpoints written before ph_type_map became a hyper-parameter
         model = pfa.PharmacophoreDiff.load_from_checkpoint(ckpt, ph_type_map=config['dataset']['ph_type_map'])
+    if use_ema:
+        model.load_ema_weights(ckpt)
+        print(f"sampling from the EMA weights of {ckpt}", flush=True)
     return model.to(device).eval()
 
 
@@ -246,7 +250,7 @@ def main(argv=None):
     print(f'{device=}', flush=True)
     torch.manual_seed(args.seed)
     prot_element_map, _ = get_prot_atom_ph_type_maps(config['dataset'])
-    model = load_model(pfa, ckpt, config, device)
+    model = load_model(pfa, ckpt, config, device, use_ema=args.use_ema)
 
     name = args.receptor_name or args.receptor_file.name.split('.')[0]
     pocket_dir = Path(args.output_dir) / name

@@ -515,6 +515,42 @@ int pf_get_flat_params(pf_handle* h, float* dev_flat /*[n_params]*/, pf_stream s
  * step counts from 1. */
 int pf_adam_step(pf_handle* h, float* dev_params, const float* dev_grad, float* dev_exp_avg, float* dev_exp_avg_sq,
                  int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay, pf_stream stream);
+/* The guarded optimiser step: pf_adam_step's Adam on gi = grad[i] * grad_scale * coef, behind a norm of the whole gradient
+ * that is taken on the device (sum of squares in fp64, fixed reduction order: the same input gives the same bits).
+ *   clip_mode PF_CLIP_NONE   coef = 1
+ *             PF_CLIP_NORM   coef = min(1, clip / (grad_scale * norm + 1e-6f)), fp32: torch.nn.utils.clip_grad_norm_(max_norm = clip)
+ *             PF_CLIP_VALUE  coef = 1, gi clamped to [-clip, clip] behind the scale: torch.nn.utils.clip_grad_value_
+ * then the L2 weight decay and Adam as in pf_adam_step.  grad_scale: 1 / N for a gradient summed over N micro-batches.
+ * A non-finite norm (some grad[i] is inf or NaN, or the norm exceeds the fp32 range) SKIPS the step: parameters, both moments,
+ * the EMA vector and the handle's weights keep their bits, the skipped counter goes up, the applied counter does not.  The bias
+ * corrections use the applied count, which lives in the state block: the host needs no synchronisation to learn of a skip.
+ * dev_ema (or NULL): ema[i] += (1 - ema_decay) * (new parameter - ema[i]) in the same pass.
+ * dev_state: PF_OPTIM_STATE_BYTES of caller-owned device memory, 8-byte aligned, set up by pf_optim_state_init (applied_steps:
+ * 0 for a fresh run, the checkpoint's count on a resume):
+ *   byte  0  int64  applied steps            byte  8  int64  skipped steps
+ *   byte 16  float  norm of the last call's scaled gradient (grad_scale * norm)
+ *   byte 20  float  coef of the last call (0 when it was skipped)
+ *   byte 24  int32  1 iff the last call's norm was finite (the step was applied)
+ *   byte 28  float  1 - beta1^applied, byte 32  float  sqrt(1 - beta2^applied) of the last applied step; the rest is reserved.
+ * Options are checked on the host before anything is enqueued (all finite, 0 <= beta < 1, clip >= 0, 0 <= ema_decay < 1,
+ * grad_scale > 0, a known clip_mode): PF_ERR_ARG, nothing touched.  pf_adam_step_guarded then refreshes the handle's weights from
+ * dev_params like pf_adam_step.  pf_debug_optim_step runs the same launches on caller vectors of any length n >= 1 and leaves
+ * the handle's weights alone; pf_debug_optim_chunk is the number of elements one workgroup reduces (tests reach its edges). */
+#define PF_CLIP_NONE 0
+#define PF_CLIP_NORM 1
+#define PF_CLIP_VALUE 2
+#define PF_OPTIM_STATE_BYTES 64
+typedef struct pf_optim_opts {
+    float lr, beta1, beta2, eps, weight_decay, grad_scale;
+    int32_t clip_mode;
+    float clip, ema_decay;
+} pf_optim_opts;
+int pf_optim_state_init(pf_handle* h, void* dev_state, int64_t applied_steps, pf_stream stream);
+int pf_adam_step_guarded(pf_handle* h, float* dev_params, const float* dev_grad, float* dev_exp_avg, float* dev_exp_avg_sq,
+                         float* dev_ema, void* dev_state, const pf_optim_opts* opts, pf_stream stream);
+int pf_debug_optim_step(pf_handle* h, int64_t n, float* dev_params, const float* dev_grad, float* dev_exp_avg,
+                        float* dev_exp_avg_sq, float* dev_ema, void* dev_state, const pf_optim_opts* opts, pf_stream stream);
+int pf_debug_optim_chunk(void);
 /* Arithmetic of the training step's dense Linears.  The reference trains in fp32 (pharmacodiff.py:162-263; gvp.py:96,101 force
  * .float()) and PF_TRAIN_F32 -- the default, and the only mode the parity tests against the reference's gradients use -- does
  * the same.  PF_TRAIN_BF16 (BASELINE config 5's "bf16" leg; no reference counterpart) runs to_feats_out and

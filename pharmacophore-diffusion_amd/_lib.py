@@ -55,6 +55,16 @@ class PfScoreLevel(ctypes.Structure):
     _fields_ = [("t_int", ctypes.c_int32), ("w_pos", ctypes.c_float), ("w_feat", ctypes.c_float)]
 
 
+class PfOptimOpts(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("grad_scale", ctypes.c_float), ("clip_mode", ctypes.c_int32),
+                ("clip", ctypes.c_float), ("ema_decay", ctypes.c_float)]
+
+
+PF_CLIP_NONE, PF_CLIP_NORM, PF_CLIP_VALUE = 0, 1, 2
+PF_OPTIM_STATE_BYTES = 64
+
+
 # every symbol include/pfdyn.h declares: (name, restype, argtypes)
 _P, _I32, _I64, _F = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 SYMBOLS = {
@@ -109,6 +119,10 @@ SYMBOLS = {
     "pf_set_flat_params": (ctypes.c_int, [_P, _P, _P]),
     "pf_get_flat_params": (ctypes.c_int, [_P, _P, _P]),
     "pf_adam_step": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
+    "pf_optim_state_init": (ctypes.c_int, [_P, _P, _I64, _P]),
+    "pf_adam_step_guarded": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(PfOptimOpts), _P]),
+    "pf_debug_optim_step": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _P, _P, ctypes.POINTER(PfOptimOpts), _P]),
+    "pf_debug_optim_chunk": (ctypes.c_int, []),
     "pf_train_set_precision": (ctypes.c_int, [_P, _I32]),
     "pf_train_get_precision": (ctypes.c_int, [_P, ctypes.POINTER(_I32)]),
     "pf_train_set_family": (ctypes.c_int, [_P, _I32]),

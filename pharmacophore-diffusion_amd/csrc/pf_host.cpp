@@ -21,6 +21,7 @@
 #include "pf_pack.h"
 #include "pf_train.h"
 #include "pf_score.h"
+#include "pf_optim.h"
 
 using namespace pfpack;
 
@@ -522,6 +523,8 @@ struct pf_handle {
     // and grown like a run's scratch (grow_run_scratch), released when the switch goes off
     bool train_in_grads = false;
     void* d_gdiff = nullptr; size_t gdiff_capacity = 0;
+    // pf_adam_step_guarded / pf_debug_optim_step: one fp64 partial per chunk of the gradient (grown on demand, kept)
+    double* d_optim_part = nullptr; size_t optim_part_cap = 0;
     // a handle of the specialised widths carries no width-generic packing (inference stays on the tuned kernels): its wide training
     // leg builds the WideGvp table on first use (ensure_wide_pack) -- Wh, Wu and the biases read from d_flat as stored, to_feats_out
     // and the gate Linear packed on the device into d_wpk whenever w_version moved
@@ -1524,6 +1527,7 @@ void pf_destroy(pf_handle* h) {
     if (h->d_restr) (void)hipFree(h->d_restr);
     if (h->d_guide) (void)hipFree(h->d_guide);
     if (h->d_gdiff) (void)hipFree(h->d_gdiff);
+    if (h->d_optim_part) (void)hipFree(h->d_optim_part);
     if (h->restr_stage) (void)hipHostFree(h->restr_stage);
     if (h->restr_ev) (void)hipEventDestroy(h->restr_ev);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
@@ -2788,6 +2792,70 @@ int pf_adam_step(pf_handle* h, float* dev_params, const float* dev_grad, float* 
              (float)std::sqrt(bc2), mirror ? h->d_flat : nullptr, s);
     return set_flat_params_impl(h, dev_params, stream, mirror);
 }
+
+// the guarded step's options, checked before anything is enqueued
+static int optim_check(pf_handle* h, const char* who, const void* p, const void* g, const void* m, const void* v, const void* state,
+                       const pf_optim_opts* o) {
+    if (!p || !g || !m || !v || !state || !o) PF_FAIL(h, PF_ERR_ARG, "%s: null argument", who);
+    if (reinterpret_cast<uintptr_t>(state) & 7) PF_FAIL(h, PF_ERR_ARG, "%s: the state block must be 8-byte aligned", who);
+    for (float x : {o->lr, o->beta1, o->beta2, o->eps, o->weight_decay, o->grad_scale, o->clip, o->ema_decay})
+        if (!std::isfinite(x)) PF_FAIL(h, PF_ERR_ARG, "%s: non-finite option", who);
+    if (o->beta1 < 0.f || o->beta1 >= 1.f || o->beta2 < 0.f || o->beta2 >= 1.f) PF_FAIL(h, PF_ERR_ARG, "%s: betas must be in [0, 1)", who);
+    if (!(o->grad_scale > 0.f)) PF_FAIL(h, PF_ERR_ARG, "%s: grad_scale must be > 0", who);
+    if (o->clip < 0.f) PF_FAIL(h, PF_ERR_ARG, "%s: clip must be >= 0", who);
+    if (o->ema_decay < 0.f || o->ema_decay >= 1.f) PF_FAIL(h, PF_ERR_ARG, "%s: ema_decay must be in [0, 1)", who);
+    if (o->clip_mode != PF_CLIP_NONE && o->clip_mode != PF_CLIP_NORM && o->clip_mode != PF_CLIP_VALUE)
+        PF_FAIL(h, PF_ERR_ARG, "%s: unknown clip_mode %d", who, (int)o->clip_mode);
+    return PF_OK;
+}
+
+// norm, finalising launch and guarded Adam on vectors of length n (pf_optim.hip)
+static int optim_launch(pf_handle* h, size_t n, float* p, const float* g, float* m, float* v, float* ema, float* mirror, void* state,
+                        const pf_optim_opts* o, hipStream_t s) {
+    const size_t n_part = (n + PFO_CHUNK - 1) / PFO_CHUNK;
+    if (n_part > h->optim_part_cap) {
+        if (h->d_optim_part) { (void)hipFree(h->d_optim_part); h->d_optim_part = nullptr; h->optim_part_cap = 0; }
+        PF_HIP(h, hipMalloc((void**)&h->d_optim_part, n_part * sizeof(double)));
+        h->optim_part_cap = n_part;
+    }
+    OptimParams P{};
+    P.p = p; P.g = g; P.m = m; P.v = v; P.ema = ema; P.mirror = mirror; P.n = n;
+    P.lr = o->lr; P.b1 = o->beta1; P.b2 = o->beta2; P.eps = o->eps; P.wd = o->weight_decay; P.grad_scale = o->grad_scale;
+    P.clip_mode = o->clip_mode; P.clip = o->clip; P.ema_decay = o->ema_decay;
+    P.partials = h->d_optim_part; P.state = (OptimState*)state;
+    pfk_optim_step(P, s);
+    return PF_OK;
+}
+
+int pf_optim_state_init(pf_handle* h, void* dev_state, int64_t applied_steps, pf_stream stream) {
+    if (!h) return PF_ERR_ARG;
+    if (!dev_state || (reinterpret_cast<uintptr_t>(dev_state) & 7) || applied_steps < 0)
+        PF_FAIL(h, PF_ERR_ARG, "pf_optim_state_init: bad argument");
+    pfk_optim_state_init((OptimState*)dev_state, (long long)applied_steps, (hipStream_t)stream);
+    return PF_OK;
+}
+
+int pf_adam_step_guarded(pf_handle* h, float* dev_params, const float* dev_grad, float* dev_exp_avg, float* dev_exp_avg_sq,
+                         float* dev_ema, void* dev_state, const pf_optim_opts* opts, pf_stream stream) {
+    int rc = check_ready(h, false);
+    if (rc) return rc;
+    if ((rc = optim_check(h, "pf_adam_step_guarded", dev_params, dev_grad, dev_exp_avg, dev_exp_avg_sq, dev_state, opts)) != PF_OK) return rc;
+    const bool mirror = h->d_map != nullptr && dev_params != h->d_flat;
+    if ((rc = optim_launch(h, h->nparams, dev_params, dev_grad, dev_exp_avg, dev_exp_avg_sq, dev_ema, mirror ? h->d_flat : nullptr,
+                           dev_state, opts, (hipStream_t)stream)) != PF_OK) return rc;
+    return set_flat_params_impl(h, dev_params, stream, mirror);          // (a skipped step re-gathers the unchanged values)
+}
+
+int pf_debug_optim_step(pf_handle* h, int64_t n, float* dev_params, const float* dev_grad, float* dev_exp_avg,
+                        float* dev_exp_avg_sq, float* dev_ema, void* dev_state, const pf_optim_opts* opts, pf_stream stream) {
+    if (!h) return PF_ERR_ARG;
+    int rc = optim_check(h, "pf_debug_optim_step", dev_params, dev_grad, dev_exp_avg, dev_exp_avg_sq, dev_state, opts);
+    if (rc) return rc;
+    if (n < 1) PF_FAIL(h, PF_ERR_ARG, "pf_debug_optim_step: n must be >= 1");
+    return optim_launch(h, (size_t)n, dev_params, dev_grad, dev_exp_avg, dev_exp_avg_sq, dev_ema, nullptr, dev_state, opts, (hipStream_t)stream);
+}
+
+int pf_debug_optim_chunk(void) { return PFO_CHUNK; }
 
 int pf_get_flat_params(pf_handle* h, float* dev_flat, pf_stream stream) {
     int rc = check_ready(h, false);

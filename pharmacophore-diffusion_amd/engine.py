@@ -305,6 +305,64 @@ class PfEngine:
                                            float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                            _stream_ptr()), "pf_adam_step")
 
+    # -- the guarded optimiser step (pf_adam_step_guarded): clipping, non-finite skip, EMA, grad_scale -------------------
+    def optim_state(self, applied_steps=0):
+        """A fresh state block of the guarded step (PF_OPTIM_STATE_BYTES on the device, pf_optim_state_init): applied_steps is 0
+        for a new run, the checkpoint's count on a resume."""
+        state = torch.empty(L.PF_OPTIM_STATE_BYTES // 8, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_optim_state_init(self._h, _dptr(state), int(applied_steps), _stream_ptr()), "pf_optim_state_init")
+        return state
+
+    @staticmethod
+    def read_optim_state(state):
+        """The state block as a dict (applied, skipped, norm, coef, finite).  Copies it to the host: SYNCHRONISES."""
+        raw = state.cpu().numpy().tobytes()
+        import struct
+        applied, skipped, norm, coef, finite = struct.unpack_from("<qqffi", raw, 0)
+        return {"applied": applied, "skipped": skipped, "norm": norm, "coef": coef, "finite": bool(finite)}
+
+    @staticmethod
+    def _optim_opts(lr, betas, eps, weight_decay, grad_scale, clip_norm, clip_value, ema_decay):
+        if clip_norm is not None and clip_value is not None:
+            raise ValueError("clip_norm and clip_value are mutually exclusive")
+        mode, clip = ((L.PF_CLIP_NORM, clip_norm) if clip_norm is not None else
+                      (L.PF_CLIP_VALUE, clip_value) if clip_value is not None else (L.PF_CLIP_NONE, 0.0))
+        return L.PfOptimOpts(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale),
+                             int(mode), float(clip), float(ema_decay or 0.0))
+
+    def _optim_vectors(self, n, params, grad, exp_avg, exp_avg_sq, ema, state):
+        for t in (params, grad, exp_avg, exp_avg_sq) + ((ema,) if ema is not None else ()):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+        assert state.is_cuda and state.dtype == torch.int64 and state.numel() * 8 == L.PF_OPTIM_STATE_BYTES
+
+    def adam_step_guarded(self, params, grad, exp_avg, exp_avg_sq, state, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                          grad_scale=1.0, clip_norm=None, clip_value=None, ema=None, ema_decay=0.0):
+        """Guarded fused Adam on flat device vectors (in place) + refresh of the engine's weights from ``params``: the gradient is
+        scaled by grad_scale, clipped by its norm (clip_norm, torch's clip_grad_norm_) or by value (clip_value, clip_grad_value_);
+        a non-finite gradient skips the step on the device (nothing is written, the state block counts it); ``ema`` receives
+        ema += (1 - ema_decay) * (p_new - ema).  ``state``: optim_state().  No host synchronisation."""
+        if not hasattr(self, "n_params"):
+            self.param_layout()
+        self._optim_vectors(self.n_params, params, grad, exp_avg, exp_avg_sq, ema, state)
+        opts = self._optim_opts(lr, betas, eps, weight_decay, grad_scale, clip_norm, clip_value, ema_decay)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_adam_step_guarded(self._h, _dptr(params), _dptr(grad), _dptr(exp_avg), _dptr(exp_avg_sq), _dptr(ema),
+                                                   _dptr(state), ctypes.byref(opts), _stream_ptr()), "pf_adam_step_guarded")
+
+    def debug_optim_step(self, params, grad, exp_avg, exp_avg_sq, state, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                         grad_scale=1.0, clip_norm=None, clip_value=None, ema=None, ema_decay=0.0):
+        """The launches of adam_step_guarded on caller vectors of any length >= 1; the engine's weights are not touched."""
+        self._optim_vectors(params.numel(), params, grad, exp_avg, exp_avg_sq, ema, state)
+        opts = self._optim_opts(lr, betas, eps, weight_decay, grad_scale, clip_norm, clip_value, ema_decay)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_debug_optim_step(self._h, params.numel(), _dptr(params), _dptr(grad), _dptr(exp_avg), _dptr(exp_avg_sq),
+                                                  _dptr(ema), _dptr(state), ctypes.byref(opts), _stream_ptr()), "pf_debug_optim_step")
+
+    def optim_chunk(self):
+        """Elements of the gradient that one workgroup of the guarded step reduces (pf_debug_optim_chunk)."""
+        return int(self.lib.pf_debug_optim_chunk())
+
     def set_train_precision(self, precision):
         """'f32' (default; what the reference trains in) or 'bf16' (the labelled bf16 leg: dense Linears of the message chains'
         forward and of the gradient kernels on bf16 matrix instructions, fp32 accumulation, fp32 master weights)."""

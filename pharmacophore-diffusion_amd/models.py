@@ -14,6 +14,7 @@ eager / CPU fallback -- without the HIP library and a GPU the calls raise.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import math
 import warnings
@@ -355,6 +356,11 @@ class PharmRecDynamicsGVP(nn.Module):
     def _stamp(self):
         return tuple(p._version for p, _, _ in self._flat_views)
 
+    def _named_views(self):
+        """[(parameter name, parameter)] in the order of _flat_views"""
+        name_of = {id(p): k for k, p in self.named_parameters()}
+        return [(name_of[id(p)], p) for p, _, _ in self._flat_views]
+
     def _views_intact(self) -> bool:
         # (an address inside the flat vector's allocation implies its device)
         base = self._flat.data_ptr()
@@ -555,16 +561,127 @@ class PharmRecDynamicsGVP(nn.Module):
         return _DynamicsFn.apply(self, eng, x_t, h_t, timestep, prot_x, p_drop, seed, self.__dict__["_flat_leaf"])
 
 
+def flat_to_named(flat, layout, shapes):
+    """{name: tensor} from a flat vector: ``layout`` = [(name, offset, numel)] (PfEngine.param_layout order), ``shapes`` = {name:
+    shape}.  Each tensor is a copy."""
+    return {name: flat[off:off + n].reshape(tuple(shapes[name])).clone() for name, off, n in layout}
+
+
 class FlatAdam:
     """Adam over a PharmRecDynamicsGVP as ONE fused HIP kernel on the flat parameter vector (pf_adam_step) instead of
     a multi-tensor update over 244 tensors: same update rule as torch.optim.Adam(lr, betas, eps, weight_decay)
-    (pharmacodiff.py:253).  Uses the flat gradient of the last backward (or of allreduce_gradients)."""
+    (pharmacodiff.py:253).  Uses the flat gradient of the last backward (or of allreduce_gradients).
 
-    def __init__(self, dynamics: "PharmRecDynamicsGVP", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    The guarded step (pf_adam_step_guarded) is taken when any of ``clip_norm`` (torch.nn.utils.clip_grad_norm_'s max_norm),
+    ``clip_value`` (clip_grad_value_; the two exclude each other, as in Lightning), ``ema_decay`` is given, or when ``step`` gets a
+    ``grad_scale`` other than 1 (a gradient accumulated over N micro-batches: 1 / N); from then on the optimiser stays on it.
+    It norms the whole gradient on the device, SKIPS a step whose gradient holds an inf or NaN (parameters, moments and EMA keep
+    their bits; the bias corrections count applied steps only) and keeps ``ema``, a flat exponential moving average of the
+    parameters that starts from them at the first guarded step (``ema_warmup``: decay min(d, (1 + k) / (10 + k)) at call k).
+    None of this synchronises the host; the counters and the last norm live in a device block that last_grad_norm(),
+    last_clip_coef(), skipped_steps() and applied_steps() read -- those four DO synchronise.  Without any of the new arguments
+    the class runs pf_adam_step as before, bit for bit."""
+
+    def __init__(self, dynamics: "PharmRecDynamicsGVP", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 clip_norm=None, clip_value=None, ema_decay=None, ema_warmup=False):
         self.dyn, self.lr, self.betas, self.eps, self.weight_decay = dynamics, lr, betas, eps, weight_decay
         self.t = 0
         self.exp_avg = self.exp_avg_sq = None
         self.param_groups = [{'lr': lr}]            # what LR schedulers / loggers look at
+        self._set_options(clip_norm, clip_value, ema_decay, ema_warmup)
+        self.ema = None                             # flat EMA of the parameters (guarded step with ema_decay)
+        self._state = None                          # the guarded step's device block (PfEngine.optim_state)
+        self._calls = 0                             # step() calls on the guarded path, skipped ones included (ema_warmup's k)
+
+    def _set_options(self, clip_norm, clip_value, ema_decay, ema_warmup):
+        if clip_norm is not None and clip_value is not None:
+            raise ValueError("FlatAdam: clip_norm and clip_value are mutually exclusive (gradient_clip_algorithm is 'norm' OR 'value')")
+        for name, v in (("clip_norm", clip_norm), ("clip_value", clip_value)):
+            if v is not None and not (float(v) >= 0 and math.isfinite(float(v))):
+                raise ValueError(f"FlatAdam: {name} must be a finite number >= 0, got {v!r}")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"FlatAdam: ema_decay must be in [0, 1), got {ema_decay!r}")
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.clip_value = None if clip_value is None else float(clip_value)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+
+    @property
+    def guarded(self) -> bool:
+        return self._state is not None or self.clip_norm is not None or self.clip_value is not None or self.ema_decay is not None
+
+    def _ensure_guard_state(self, eng):
+        if self._state is None:
+            self._state = eng.optim_state(self.t)
+        if self.ema_decay is not None and self.ema is None:
+            self.ema = self.dyn._flat.detach().clone()
+
+    def _read_state(self):
+        return None if self._state is None else PfEngine.read_optim_state(self._state)
+
+    def applied_steps(self) -> int:
+        """Optimiser steps that were applied (skipped ones not counted).  Reads the device block: SYNCHRONISES."""
+        st = self._read_state()
+        return self.t if st is None else int(st["applied"])
+
+    def skipped_steps(self) -> int:
+        """Steps skipped for a non-finite gradient since this object (or its state on a resume) was set up.  SYNCHRONISES."""
+        st = self._read_state()
+        return 0 if st is None else int(st["skipped"])
+
+    def last_grad_norm(self):
+        """Norm of the last guarded step's gradient after grad_scale, before clipping (inf / nan when it was skipped); None
+        before the first guarded step.  SYNCHRONISES."""
+        st = self._read_state()
+        return None if st is None else float(st["norm"])
+
+    def last_clip_coef(self):
+        """The factor the last guarded step put on the gradient (1 without norm clipping, 0 when it was skipped).  SYNCHRONISES."""
+        st = self._read_state()
+        return None if st is None else float(st["coef"])
+
+    def ema_decay_at(self, k: int) -> float:
+        d = self.ema_decay or 0.0
+        return min(d, (1.0 + k) / (10.0 + k)) if self.ema_warmup else d
+
+    def ema_state_dict(self):
+        """The EMA weights as named tensors (state-dict keys of the model, 'dynamics.' prefix; on the host), or None without
+        ema_decay.  Before the first guarded step the EMA is the parameters."""
+        if self.ema_decay is None:
+            return None
+        self.dyn.engine()
+        flat = self.dyn._flat if self.ema is None else self.ema
+        return flat_to_named(flat.detach().cpu(), [("dynamics." + k, off, n) for (k, _), (_, off, n)
+                                                   in zip(self.dyn._named_views(), self.dyn._flat_views)],
+                             {"dynamics." + k: p.shape for k, p in self.dyn._named_views()})
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model runs on the EMA weights (validation, sampling): they are swapped into the flat parameter
+        vector and the engine is refreshed; on exit -- also on an exception -- the training weights are back bit for bit.  No
+        optimiser step and no backward of an earlier forward inside it."""
+        if self.ema_decay is None:
+            raise RuntimeError("FlatAdam.ema_weights(): this optimiser keeps no EMA (ema_decay is None)")
+        dyn = self.dyn
+        dyn.engine()
+        if self.ema is None:                        # no guarded step yet: the EMA is the parameters
+            yield
+            return
+        keep = dyn._flat.detach().clone()
+
+        def put(src):
+            dyn._join_prefetch()
+            with torch.no_grad():
+                dyn._flat.copy_(src)
+            dyn._engine.set_flat_params(dyn._flat)
+            dyn._weights_stamp = dyn._stamp()
+            for ent in dyn.__dict__.get("_lane_engines", {}).values():
+                ent[1] = None                       # further sampling lanes re-read the flat vector
+        put(self.ema)
+        try:
+            yield
+        finally:
+            put(keep)
 
     def zero_grad(self, set_to_none: bool = False, lazy: bool = False):
         """Default (``set_to_none=False``): the flat gradient is zeroed IN PLACE -- one small kernel; the 244 parameters'
@@ -601,18 +718,27 @@ class FlatAdam:
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.dyn._flat), torch.zeros_like(self.dyn._flat)
         if t is not None:
             self.t = int(t)
+            if self._state is not None:             # the device block counts from the given step (skipped starts at 0)
+                self._state = self.dyn._engine.optim_state(self.t)
         if lr is not None:
             self.param_groups[0]['lr'] = float(lr)
 
     def state_dict_meta(self):
-        return self.t, self.param_groups[0]['lr']
+        return self.applied_steps(), self.param_groups[0]['lr']
 
     def state_dict(self):
+        """'step' is the APPLIED step count (on the guarded path it is read from the device: synchronises)."""
         self.ensure_state()
-        return {'state': {'step': self.t, 'exp_avg': self.exp_avg.detach().cpu(), 'exp_avg_sq': self.exp_avg_sq.detach().cpu()},
-                'param_groups': [{'lr': self.param_groups[0]['lr'], 'betas': self.betas, 'eps': self.eps,
-                                  'weight_decay': self.weight_decay}],
-                'layout': 'flat vector in pf_param_layout order'}
+        sd = {'state': {'step': self.applied_steps(), 'exp_avg': self.exp_avg.detach().cpu(), 'exp_avg_sq': self.exp_avg_sq.detach().cpu()},
+              'param_groups': [{'lr': self.param_groups[0]['lr'], 'betas': self.betas, 'eps': self.eps,
+                                'weight_decay': self.weight_decay}],
+              'layout': 'flat vector in pf_param_layout order'}
+        if self.guarded:
+            sd['guard'] = {'clip_norm': self.clip_norm, 'clip_value': self.clip_value, 'ema_decay': self.ema_decay,
+                           'ema_warmup': self.ema_warmup, 'calls': self._calls, 'skipped': self.skipped_steps()}
+            if self.ema is not None:
+                sd['state']['ema'] = self.ema.detach().cpu()
+        return sd
 
     def load_state_dict(self, sd):
         """Accepts this class's own state (flat moment vectors, marked by 'layout') and the per-parameter state of
@@ -620,12 +746,21 @@ class FlatAdam:
         Adam(self.parameters())): parameter i of that optimiser is tensor i of the flat layout (state-dict order, the
         empty dummy_param included); parameters without an entry (never stepped) keep zero moments."""
         st, pg = sd['state'], sd['param_groups'][0]
+        self.ema = None                             # states without an EMA vector: it starts from the parameters
         if 'layout' in sd:
             self.ensure_state(st['step'], pg['lr'])
             if st['exp_avg'].numel() != self.exp_avg.numel():
                 raise ValueError("FlatAdam.load_state_dict: moment vectors do not match this model's parameter count")
             self.exp_avg.copy_(st['exp_avg'])
             self.exp_avg_sq.copy_(st['exp_avg_sq'])
+            guard = sd.get('guard')
+            if guard is not None:                   # the state's options replace the constructor's; the step count goes to the device
+                self._set_options(guard.get('clip_norm'), guard.get('clip_value'), guard.get('ema_decay'), guard.get('ema_warmup', False))
+                self._calls = int(guard.get('calls', st['step']))
+                if st.get('ema') is not None and self.ema_decay is not None:
+                    if st['ema'].numel() != self.exp_avg.numel():
+                        raise ValueError("FlatAdam.load_state_dict: the EMA vector does not match this model's parameter count")
+                    self.ema = st['ema'].to(self.exp_avg.device, torch.float32).clone()
         else:
             # parameter i of that optimiser = the i-th entry of the model's parameters(): PharmacophoreDiff's list is
             # gamma.gamma (a frozen nn.Parameter upstream, pharmacodiff.py:662-664: never stepped) followed by the dynamics
@@ -654,7 +789,8 @@ class FlatAdam:
         self.betas, self.eps = tuple(pg.get('betas', self.betas)), pg.get('eps', self.eps)
         self.weight_decay = pg.get('weight_decay', self.weight_decay)
 
-    def step(self):
+    def step(self, grad_scale: float = 1.0):
+        """One optimiser step on the flat gradient times ``grad_scale`` (1 / N after N accumulated micro-batches)."""
         dyn = self.dyn
         g = getattr(dyn, "_last_flat_grad", None)
         if g is None:
@@ -668,7 +804,8 @@ class FlatAdam:
         if fast:
             base = dyn._flat.data_ptr()
             ends = (dyn._flat_views[0], dyn._flat_views[-1])
-            fast = all(p.data_ptr() == base + 4 * off for p, off, _ in ends) and (self.t % 64 != 63 or dyn._views_intact())
+            tick = self._calls if self._state is not None else self.t
+            fast = all(p.data_ptr() == base + 4 * off for p, off, _ in ends) and (tick % 64 != 63 or dyn._views_intact())
         if not fast:
             eng = dyn.engine()
             if g.numel() != dyn._flat.numel() or g.device != dyn._flat.device:
@@ -678,6 +815,15 @@ class FlatAdam:
             eng = dyn._engine
         if self.exp_avg is None:
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(dyn._flat), torch.zeros_like(dyn._flat)
+        if self.guarded or float(grad_scale) != 1.0:
+            # clipping, the non-finite skip, the EMA stream and the scale in the library's three launches; the applied step count
+            # stays on the device (self.t is not advanced: applied_steps() reads it)
+            self._ensure_guard_state(eng)
+            eng.adam_step_guarded(dyn._flat, g, self.exp_avg, self.exp_avg_sq, self._state, self.param_groups[0]['lr'], self.betas,
+                                  self.eps, self.weight_decay, grad_scale=grad_scale, clip_norm=self.clip_norm,
+                                  clip_value=self.clip_value, ema=self.ema, ema_decay=self.ema_decay_at(self._calls))
+            self._calls += 1
+            return
         self.t += 1
         eng.adam_step(dyn._flat, g, self.exp_avg, self.exp_avg_sq, self.t, self.param_groups[0]['lr'], self.betas, self.eps,
                       self.weight_decay)
@@ -760,10 +906,38 @@ class PharmacophoreDiff(_Base):
         def log_dict(self, *a, **k):
             pass
 
-    def save_checkpoint(self, path, **extra):
+    def save_checkpoint(self, path, ema_state_dict=None, **extra):
         """Write a file ``load_from_checkpoint`` (ours or Lightning's) can read.  ``extra``: further top-level entries in
-        Lightning's checkpoint vocabulary ('epoch', 'global_step', 'optimizer_states', 'lr_schedulers')."""
+        Lightning's checkpoint vocabulary ('epoch', 'global_step', 'optimizer_states', 'lr_schedulers').  ``ema_state_dict``
+        (FlatAdam.ema_state_dict()): the EMA weights as named tensors, stored under 'ema_state_dict' for load_ema_weights."""
+        if ema_state_dict is not None:
+            extra = dict(extra, ema_state_dict=ema_state_dict)
         torch.save({"state_dict": self.state_dict(), "hyper_parameters": self._hparams_dict, **extra}, str(path))
+
+    def load_ema_weights(self, path_or_dict):
+        """Replace the dynamics' weights with the EMA weights of a checkpoint (a path, a loaded checkpoint dict, or the named
+        tensors themselves).  A checkpoint without them raises a KeyError that names the missing key, 'ema_state_dict'."""
+        src = path_or_dict
+        if not isinstance(src, dict):
+            src = torch.load(str(src), map_location="cpu", weights_only=False)
+        if "ema_state_dict" in src:
+            ema = src["ema_state_dict"]
+        elif "state_dict" in src or "hyper_parameters" in src or not src:
+            raise KeyError("load_ema_weights: the checkpoint has no 'ema_state_dict' entry (it was written without EMA weights: "
+                           "train with ema_decay set)")
+        else:
+            ema = src
+        own = self.state_dict()
+        unknown = [k for k in ema if k not in own]
+        if unknown:
+            raise KeyError(f"load_ema_weights: 'ema_state_dict' names tensors this model does not have: {unknown[:3]}")
+        for k, v in ema.items():
+            if tuple(v.shape) != tuple(own[k].shape):
+                raise ValueError(f"load_ema_weights: {k} has shape {tuple(v.shape)}, the model's is {tuple(own[k].shape)}")
+        with torch.no_grad():
+            for k, v in ema.items():
+                own[k].copy_(v)                     # state_dict() tensors alias the parameters (views of the flat vector on a GPU)
+        return self
 
     # -- small algebra (pharmacodiff.py:80-86, 140-160) ----------------------------------------
     def sigma(self, gamma):

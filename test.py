@@ -40,6 +40,7 @@ _FLAGS = [
     ('--eta', dict(type=float, default=None, help='with --sample_steps --sampler ddim: share of the posterior noise injected, 0..1 (default 0)')),
     ('--spacing', dict(choices=['uniform', 'quadratic', 'logsnr'], default=None, help='with --sample_steps: how the visited levels are spread (default uniform)')),
     ('--pockets_per_call', dict(type=int, default=64, help='pockets whose samples are batched together (not in the reference)')),
+    ('--use_ema', dict(action='store_true', help="sample from the checkpoint's EMA weights ('ema_state_dict') instead of the training weights")),
 ]
 
 
@@ -127,7 +128,7 @@ def main(argv=None):
     dm = data_module_from_config(config)
     dm.setup('fit' if args.split == 'train' else 'test')
     dataset = dm.train_dataset if args.split == 'train' else dm.val_dataset
-    model = load_model(pfa, ckpt, config, device)
+    model = load_model(pfa, ckpt, config, device, use_ema=args.use_ema)
 
     pockets = selected_pockets(args, len(dataset))
     # pockets are independent units; a pocket's cost is its pp edge count times its sample count (sizes 3-8 change it by

@@ -12,8 +12,15 @@ Data parallel, one process per GPU (``torchrun --nproc-per-node N train.py ...``
   * the validation loss is summed over the ranks before the plateau logic, so every rank takes the same LR decision;
   * rank 0 writes the checkpoint, which carries the optimiser moments, step count, learning rate, epoch and plateau
     state next to the weights; ``--resume`` restores all of them (a Lightning checkpoint's 'optimizer_states' /
-    'lr_schedulers' / 'epoch' / 'global_step' keys are used for that)."""
+    'lr_schedulers' / 'epoch' / 'global_step' keys are used for that).
+
+Optimiser settings (optim_options): ``training.trainer_args.gradient_clip_val`` / ``gradient_clip_algorithm`` ('norm' by
+default, or 'value') and ``accumulate_grad_batches`` mean what they mean to Lightning's Trainer; ``training.clip_value`` /
+``--clip_value`` clip by value; ``training.ema_decay`` / ``--ema_decay`` (``--ema_warmup``) keep an exponential moving average
+of the weights, under which validation and the checkpoint's 'ema_state_dict' run.  Any of them puts the step on FlatAdam's guarded
+entry, which also skips a step whose gradient is not finite; other trainer arguments are named once and ignored."""
 import argparse
+import contextlib
 import os
 from datetime import datetime
 from pathlib import Path
@@ -35,6 +42,48 @@ def _collective(fn, t, **kw):
     return t
 
 
+HANDLED_TRAINER_ARGS = ('max_epochs', 'gradient_clip_val', 'gradient_clip_algorithm', 'accumulate_grad_batches')
+
+
+def optim_options(config, args=None):
+    """What the config and the command line ask of the optimiser step, as a dict: clip_norm, clip_value (at most one is set),
+    accumulate (micro-batches per step, >= 1), ema_decay (or None), ema_warmup, ignored (names of the trainer arguments this
+    driver does not act on).  Needs no GPU.  ``args``: the parsed command line (clip_value, ema_decay, ema_warmup) or None."""
+    training = config.get('training') or {}
+    ta = dict(training.get('trainer_args') or {})
+    clip_norm = clip_value = None
+    gcv = ta.get('gradient_clip_val')
+    algo = ta.get('gradient_clip_algorithm') or 'norm'
+    if algo not in ('norm', 'value'):
+        raise ValueError(f"trainer_args.gradient_clip_algorithm must be 'norm' or 'value', got {algo!r}")
+    if gcv is not None and float(gcv) > 0:          # Lightning: None or 0 = no clipping
+        if algo == 'norm':
+            clip_norm = float(gcv)
+        else:
+            clip_value = float(gcv)
+    cv = getattr(args, 'clip_value', None)
+    if cv is None:
+        cv = training.get('clip_value')
+    if cv is not None:
+        if clip_norm is not None or clip_value is not None:
+            raise ValueError("both trainer_args.gradient_clip_val and clip_value (training.clip_value / --clip_value) are set: "
+                             "choose one way of clipping")
+        clip_value = float(cv)
+    acc = ta.get('accumulate_grad_batches')
+    acc = 1 if acc is None else int(acc)
+    if acc < 1:
+        raise ValueError(f"trainer_args.accumulate_grad_batches must be >= 1, got {acc}")
+    ema = getattr(args, 'ema_decay', None)
+    if ema is None:
+        ema = training.get('ema_decay')
+    if ema is not None and not 0.0 <= float(ema) < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1), got {ema!r}")
+    return {'clip_norm': clip_norm, 'clip_value': clip_value, 'accumulate': acc,
+            'ema_decay': None if ema is None else float(ema),
+            'ema_warmup': bool(getattr(args, 'ema_warmup', False) or training.get('ema_warmup', False)),
+            'ignored': sorted(k for k in ta if k not in HANDLED_TRAINER_ARGS)}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--config', type=str, required=True)
@@ -52,6 +101,11 @@ def main():
     p.add_argument('--train_family', choices=['auto', 'tuned', 'wide'], default='auto',
                    help="gradient kernels: tuned (n_hidden_scalars 128 / vector_size 16 only), wide (the width-generic fp32 leg, every "
                         "supported width pair) or auto: wide iff the config's widths are not 128 / 16")
+    p.add_argument('--clip_value', type=float, default=None, help='max gradient value for clipping')
+    p.add_argument('--ema_decay', type=float, default=None,
+                   help='keep an exponential moving average of the weights with this decay; validation, sampling and the '
+                        "checkpoint's ema_state_dict use it")
+    p.add_argument('--ema_warmup', action='store_true', help='EMA decay min(d, (1 + k) / (10 + k)) at optimiser call k')
     args = p.parse_args()
     with open(args.config) as f:
         _dyn = (yaml.load(f, Loader=yaml.FullLoader).get('dynamics') or {})
@@ -93,7 +147,15 @@ def main():
     print(f"training leg: {family} ({'width-generic fp32 kernels' if family == 'wide' else 'kernels specialised to 128 / 16'}; "
           f"n_hidden_scalars {widths[0]}, vector_size {widths[1]})", flush=True)
     lr_cfg = config['lr_scheduler']
-    opt = pfa.FlatAdam(model.dynamics, lr=lr_cfg['base_lr'], weight_decay=lr_cfg.get('weight_decay', 0.0))
+    oo = optim_options(config, args)
+    if oo['ignored'] and rank == 0:
+        print("trainer_args not acted on by this driver: " + ", ".join(oo['ignored']), flush=True)
+    n_acc = oo['accumulate']
+    opt = pfa.FlatAdam(model.dynamics, lr=lr_cfg['base_lr'], weight_decay=lr_cfg.get('weight_decay', 0.0), clip_norm=oo['clip_norm'],
+                       clip_value=oo['clip_value'], ema_decay=oo['ema_decay'], ema_warmup=oo['ema_warmup'])
+    if (opt.guarded or n_acc > 1) and rank == 0:
+        print(f"guarded optimiser step: clip_norm {oo['clip_norm']} clip_value {oo['clip_value']} accumulate_grad_batches {n_acc} "
+              f"ema_decay {oo['ema_decay']}" + (" (warm-up)" if oo['ema_warmup'] else ""), flush=True)
     plateau = dict(lr_cfg.get('reducelronplateau', {}))
     best, bad_epochs, step, first_epoch = float('inf'), 0, 0, 0
     if args.resume is not None:
@@ -117,8 +179,19 @@ def main():
         best, bad_epochs, step, first_epoch = meta[1:]
         _collective(dist.broadcast, opt.exp_avg, src=0)
         _collective(dist.broadcast, opt.exp_avg_sq, src=0)
+        if opt.ema_decay is not None:                            # the EMA vector (rank 0's, or its parameters) and the call count
+            guard = [opt._calls, opt.ema is not None] if rank == 0 else [None, None]
+            dist.broadcast_object_list(guard, src=0)
+            opt._calls = guard[0]
+            if guard[1]:
+                if opt.ema is None:
+                    opt.ema = torch.empty_like(model.dynamics._flat)
+                _collective(dist.broadcast, opt.ema, src=0)
+            else:
+                opt.ema = None
     if args.seed is not None:
         torch.manual_seed(args.seed + 1000003 * (rank + 1))      # from here on: per-rank data order, noise, dropout
+    guarded = opt.guarded or n_acc > 1               # (a resumed state may carry guard options of its own)
     dm = data_module_from_config(config)
     dm.setup('fit')
     run_dir = Path(config['training']['output_dir']) / f"{config['wandb']['name'].replace(' ', '_')}_{datetime.now():%Y-%m-%d_%H-%M-%S}"
@@ -145,23 +218,32 @@ def main():
             g = nxt
             nxt = next(batches, None)
             nxt = None if nxt is None else nxt.to(dev)
-            opt.zero_grad(lazy=True)
+            if i % n_acc == 0:                                   # first micro-batch of a group: the deferred clear; the rest accumulate
+                opt.zero_grad(lazy=True)
             loss = model.training_step(g, i)
             if nxt is not None and args.bind_prefetch:
                 model.dynamics.prefetch_graph(nxt)
             loss.backward()
+            if (i + 1) % n_acc != 0 and nxt is not None:         # (a short last group of an epoch steps with what it has)
+                continue
             if world > 1:
                 model.dynamics.allreduce_gradients()
-            opt.step()
+            if guarded:
+                opt.step(grad_scale=1.0 / n_acc)
+            else:
+                opt.step()
             step += 1
             if rank == 0 and step % 50 == 0:
-                print(f"epoch {epoch} step {step} " + " ".join(f"{k}={float(v):.4f}" for k, v in model.last_metrics.items()), flush=True)
+                extra = f" grad_norm={opt.last_grad_norm():.4f} skipped={opt.skipped_steps()}" if guarded else ""
+                print(f"epoch {epoch} step {step} " + " ".join(f"{k}={float(v):.4f}" for k, v in model.last_metrics.items()) + extra,
+                      flush=True)
             if args.max_steps and step >= args.max_steps:
                 stop = True
                 break
         model.eval()
         acc = torch.zeros(2, dtype=torch.float64)
-        with torch.no_grad():
+        # validation (and whatever validation_step samples and analyses) on the EMA weights when there are any
+        with (opt.ema_weights() if opt.ema_decay is not None else contextlib.nullcontext()), torch.no_grad():
             for i, g in enumerate(dm.val_dataloader()):
                 if i % world != rank:                            # validation batches dealt over the ranks
                     continue
@@ -188,11 +270,22 @@ def main():
             _collective(dist.all_reduce, hi, op=dist.ReduceOp.MAX)
             if not torch.equal(lo, hi):
                 raise RuntimeError(f"replicas diverged after epoch {epoch}: parameter checksums differ by {(hi - lo).tolist()}")
+            if opt.ema is not None:
+                e = opt.ema
+                esig = torch.stack([e.double().sum(), e.double().abs().sum(), e[::997].double().square().sum()])
+                lo, hi = esig.clone(), esig.clone()
+                _collective(dist.all_reduce, lo, op=dist.ReduceOp.MIN)
+                _collective(dist.all_reduce, hi, op=dist.ReduceOp.MAX)
+                if not torch.equal(lo, hi):
+                    raise RuntimeError(f"replicas diverged after epoch {epoch}: EMA checksums differ by {(hi - lo).tolist()}")
             if rank == 0:
                 print(f"epoch {epoch}: replicas identical on {world} ranks (checksum {float(sig[0]):.9e})", flush=True)
         if rank == 0:
-            print(f"epoch {epoch}: val total loss {val:.5f} lr {opt.param_groups[0]['lr']:.2e}", flush=True)
+            print(f"epoch {epoch}: val total loss {val:.5f} lr {opt.param_groups[0]['lr']:.2e}"
+                  + (f" grad_norm {opt.last_grad_norm():.4f} skipped {opt.skipped_steps()}" if guarded and opt.last_grad_norm() is not None
+                     else ""), flush=True)
             model.save_checkpoint(run_dir / 'checkpoints' / 'last.ckpt', epoch=epoch, global_step=step,
+                                  ema_state_dict=opt.ema_state_dict(),
                                   optimizer_states=[opt.state_dict()],
                                   lr_schedulers=[{'best': best, 'num_bad_epochs': bad_epochs}])
         if stop:
