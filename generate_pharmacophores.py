@@ -37,9 +37,11 @@ _FLAGS = [
     ('--pin_resamples', dict(type=int, default=None, help='with --pinned_centers: denoise every stretch of --pin_jump levels this many times, re-noising it in between, so that the free centers can react to the pinned ones (default 1: no resampling; a run costs about this many times the steps)')),
     ('--pin_jump', dict(type=int, default=None, help='with --pinned_centers: levels per resampled stretch (default 10)')),
     ('--restraints', dict(type=Path, default=None, help='guided sampling: a text file with one restraint per line, "attract|repel x y z radius weight [center|*]" in the receptor\'s frame (# starts a comment): keep centers out of / pull a center into a sphere; a guided step costs several times a default one')),
-    ('--guide_scale', dict(type=float, default=None, help='with --restraints: strength of the guidance (default 1)')),
-    ('--guide_clip', dict(type=float, default=None, help='with --restraints: largest shift of a center per step in angstroms (default 0: no clip)')),
-    ('--guide_family', dict(choices=['wide', 'tuned'], default=None, help='with --restraints: the kernels of a guided step\'s training forward and input gradients -- wide (default; every model width) or tuned (models of n_hidden_scalars 128 / vector_size 16: the tuned gradient kernels)')),
+    ('--avoid_clashes', dict(type=float, nargs='?', const=2.0, default=None, metavar='R', help='guided sampling: keep the centers out of the pocket\'s own atoms -- a center of the predicted clean sample within R angstroms of an atom (default 2.0) is pushed out; every batch then runs guided, which costs several times a default step')),
+    ('--clash_weight', dict(type=float, default=None, help='with --avoid_clashes: weight of the clash energy (default 1)')),
+    ('--guide_scale', dict(type=float, default=None, help='with --restraints or --avoid_clashes: strength of the guidance (default 1)')),
+    ('--guide_clip', dict(type=float, default=None, help='with --restraints or --avoid_clashes: largest shift of a center per step in angstroms (default 0: no clip)')),
+    ('--guide_family', dict(choices=['wide', 'tuned'], default=None, help='with --restraints or --avoid_clashes: the kernels of a guided step\'s training forward and input gradients -- wide (default; every model width) or tuned (models of n_hidden_scalars 128 / vector_size 16: the tuned gradient kernels)')),
     ('--seed_pharmacophore', dict(type=Path, default=None, help='seeded sampling: one xyz frame in the pharms.xyz format; every sample is a variation of it (the frame is noised forward to --seed_level and only the steps below that level are run)')),
     ('--seed_level', dict(type=int, default=None, help='with --seed_pharmacophore: the level 1..T the seed is noised to; small: close analogues, large: loose ones')),
     ('--seed_keep', dict(type=str, default=None, help='with --seed_pharmacophore: comma-separated indices of seed centers that stay fixed in position and type, e.g. 0,2')),
@@ -67,14 +69,24 @@ def parse_arguments(argv=None):
             parser.error(f'--{flag} needs --pinned_centers')
         if v is not None and v < 1:
             parser.error(f'--{flag} must be at least 1, got {v}')
+    guided = a.restraints is not None or a.avoid_clashes is not None
     for flag in ('guide_scale', 'guide_clip'):
         v = getattr(a, flag)
-        if v is not None and a.restraints is None:
-            parser.error(f'--{flag} needs --restraints')
+        if v is not None and not guided:
+            parser.error(f'--{flag} needs --restraints or --avoid_clashes')
         if v is not None and not v >= 0:
             parser.error(f'--{flag} must not be negative, got {v}')
-    if a.guide_family is not None and a.restraints is None:
-        parser.error('--guide_family needs --restraints')
+    if a.guide_family is not None and not guided:
+        parser.error('--guide_family needs --restraints or --avoid_clashes')
+    if a.clash_weight is not None and a.avoid_clashes is None:
+        parser.error('--clash_weight needs --avoid_clashes')
+    for flag in ('avoid_clashes', 'clash_weight'):
+        v = getattr(a, flag)
+        if v is not None and not (v >= 0 and v < float('inf')):
+            parser.error(f'--{flag} must be finite and not negative, got {v}')
+    a.clash_weight = 1.0 if a.clash_weight is None else a.clash_weight
+    if a.avoid_clashes is not None and a.pin_resamples is not None and a.pin_resamples > 1:
+        parser.error('--avoid_clashes together with --pin_resamples > 1: guidance with resampling jumps is not supported')
     a.guide_family = 'wide' if a.guide_family is None else a.guide_family
     a.guide_scale = 1.0 if a.guide_scale is None else a.guide_scale
     a.guide_clip = 0.0 if a.guide_clip is None else a.guide_clip
@@ -121,8 +133,8 @@ def parse_arguments(argv=None):
             parser.error('--eta needs --sampler ddim')
         if a.eta is not None and not 0.0 <= a.eta <= 1.0:
             parser.error(f'--eta must lie in 0..1, got {a.eta}')
-        if a.sampler == 'multistep' and (a.pinned_centers is not None or a.restraints is not None or a.seed_keep is not None):
-            parser.error('--sampler multistep composes with --seed_pharmacophore only: no --pinned_centers, --seed_keep or --restraints')
+        if a.sampler == 'multistep' and (a.pinned_centers is not None or guided or a.seed_keep is not None):
+            parser.error('--sampler multistep composes with --seed_pharmacophore only: no --pinned_centers, --seed_keep, --restraints or --avoid_clashes')
     a.pin_resamples = 1 if a.pin_resamples is None else a.pin_resamples
     a.pin_jump = 10 if a.pin_jump is None else a.pin_jump
     for flag in ('score_samples', 'keep_best'):
@@ -226,12 +238,17 @@ def score_frames(pfa, model, pocket, frames, args):
                            max_batch_size=args.max_batch_size)[0]
 
 
-def write_scores(path, indices, scores):
-    """scores.tsv: one line per pharmacophore, in the order of pharms.xyz (or of the scored file)"""
-    lines = ['\t'.join(('index', 'centers', 'total', 'per_center', 'pos', 'feat', 'position_error', 'type_accuracy'))]
-    for i, s in zip(indices, scores):
-        lines.append('\t'.join((str(i), str(s.n_centers), f'{s.total:.6g}', f'{s.per_center:.6g}', f'{s.pos:.6g}', f'{s.feat:.6g}',
-                                f'{s.position_error:.6g}', f'{s.type_accuracy:.4f}')))
+def write_scores(path, indices, scores, clashes=None):
+    """scores.tsv: one line per pharmacophore, in the order of pharms.xyz (or of the scored file).  clashes (a pocket field was on):
+    per pharmacophore (final clash energy, clashing (center, atom) pairs), two more columns"""
+    head = ('index', 'centers', 'total', 'per_center', 'pos', 'feat', 'position_error', 'type_accuracy')
+    lines = ['\t'.join(head + (('clash_energy', 'clashes') if clashes is not None else ()))]
+    for k, (i, s) in enumerate(zip(indices, scores)):
+        row = (str(i), str(s.n_centers), f'{s.total:.6g}', f'{s.per_center:.6g}', f'{s.pos:.6g}', f'{s.feat:.6g}',
+               f'{s.position_error:.6g}', f'{s.type_accuracy:.4f}')
+        if clashes is not None:
+            row += (f'{clashes[k][0]:.6g}', str(clashes[k][1]))
+        lines.append('\t'.join(row))
     Path(path).write_text('\n'.join(lines) + '\n')
 
 
@@ -279,6 +296,9 @@ def main(argv=None):
     k_named = 0
     if args.restraint_list:
         k_named = 1 + max([c for _, c, _, _, _ in args.restraint_list if c is not None], default=-1)
+    field = None
+    if args.avoid_clashes is not None:       # PDB input has no receptor features: the clash term alone
+        field = pfa.PocketField(clash_radius=args.avoid_clashes, clash_weight=args.clash_weight, comp_weight=0.0)
     t0 = time.time()
     pharms = []
     while len(pharms) < args.samples_per_pocket:
@@ -298,13 +318,20 @@ def main(argv=None):
                                                   guide_scale=args.guide_scale, guide_clip=args.guide_clip, guide_family=args.guide_family,
                                                   seeds=[args.seed_centers] * n if args.seed_centers is not None else None, seed_level=args.seed_level,
                                                   seed_keep=[args.seed_keep_list] * n if args.seed_keep_list else None,
-                                                  sample_steps=args.sample_steps, sampler=args.sampler, eta=args.eta, spacing=args.spacing)
+                                                  sample_steps=args.sample_steps, sampler=args.sampler, eta=args.eta, spacing=args.spacing,
+                                                  pocket_field=field)
     elapsed = time.time() - t0
 
     (pocket_dir / 'sample_time.txt').write_text(f'{elapsed:.2f}')
     with open(pocket_dir / 'sample_time.pkl', 'wb') as f:
         pickle.dump([elapsed], f)
     print(f'{name}: {len(pharms)} pharmacophores in {elapsed:.2f} s ({elapsed / len(pharms):.3f} s each)')
+    clashes = None
+    if field is not None:                    # the final clash energy and the clashing (center, atom) pairs of every sample
+        from pharmacoforge_amd.analysis import clash_energy
+        clashes = [clash_energy(ph.ph_coords, pocket.prot_x, args.avoid_clashes, args.clash_weight) for ph in pharms]
+        print(f'{name}: clash energy per sample ' + ' '.join(f'{e:.3g}' for e, _ in clashes)
+              + '; clashing pairs ' + ' '.join(str(c) for _, c in clashes))
     ref_dir = pocket_dir / 'reference_files'
     ref_dir.mkdir(exist_ok=True)
     for src in (args.receptor_file, args.ref_ligand_file):
@@ -319,7 +346,7 @@ def main(argv=None):
         if args.keep_best is not None:
             order = sorted(order, key=lambda i: (scores[i].per_center, i))[:args.keep_best]
         pharms, scores = [pharms[i] for i in order], [scores[i] for i in order]
-        write_scores(pocket_dir / 'scores.tsv', range(len(scores)), scores)
+        write_scores(pocket_dir / 'scores.tsv', range(len(scores)), scores, None if clashes is None else [clashes[i] for i in order])
     if args.visualize_trajectory:
         for i, ph in enumerate(pharms):
             ph.traj_to_xyz(pocket_dir / f'pharm_{i}_traj.xyz')

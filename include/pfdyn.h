@@ -326,6 +326,44 @@ int pf_sample_guided(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coe
  * ignored) and E [B]; PF_ERR_STATE when no guided step has run on this batch */
 int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* dev_shift, float* dev_energy, pf_stream stream);
 
+/* -- pocket field: clash avoidance and complementarity energies next to a guided run's restraints (no reference counterpart) ------
+ * A guided run may carry a pocket field: two energies that come from the pocket itself and are added to the restraints' (there may
+ * be none of those) in the formulas above -- x0_hat, y_f = x0_hat[f] + D[g], g0, E[g], grad, shift.  Every element is optional.
+ * Clash.  HOST radii atom_r[Np_tot] >= 0 (0: the atom is inert) and a weight w_clash >= 0.  With a_i the CURRENT protein row of
+ * the sampler's frame and rho = |x0_hat[f] - a_i| (the sampler's frame: x0_hat and a_i are both there, and the distance is the one
+ * of the caller's frame), for every center f and every atom i of its graph:
+ *     E       += w_clash * max(0, atom_r[i] - rho)^2
+ *     dE/dy_f  = -2 w_clash max(0, atom_r[i] - rho) (x0_hat[f] - a_i) / rho,   0 when rho == 0
+ * Complementarity.  Per graph receptor features (q_j, u_j) in the caller's frame: HOST ph_ptr[B+1], ph_x[n][3], ph_type[n] with
+ * 0 <= ph_type < pharm_nf; a HOST match table M[pharm_nf][pharm_nf] (0 / 1: a center of type t is matched by a receptor feature
+ * of type u) and distances d[pharm_nf] >= 0; w_comp >= 0, kappa > 0, type_sharpness >= 0.  Center f has type weights
+ *     p_f = softmax_t(type_sharpness * h0_hat[f]),  h0_hat = (h_t - sigma_t eps_h) / alpha_t, or eps_h under endpoint_param_feat
+ * which are constants of the differentiation (features stay unguided; the VJP's g_eps_h stays zero).  For every type t whose set
+ * S_t = {j : M[t][u_j]} is non-empty in the graph, with rho_j = |y_f - q_j|:
+ *     rho~ = -(1/kappa) log sum_{j in S_t} exp(-kappa rho_j)     (evaluated with the largest exponent subtracted)
+ *     s_j  = the softmax weights of that sum,  m = max(0, rho~ - d[t])
+ *     E       += w_comp p_ft m^2
+ *     dE/dy_f += w_comp p_ft 2 m sum_j s_j (y_f - q_j) / rho_j   (a term with rho_j == 0 contributes 0)
+ * rho~ <= min_j rho_j: a center with a matching feature of type-t partners within d[t] -- what the validity metric counts as
+ * matched -- pays nothing for t.  The converse holds up to log|S_t| / kappa: a center that pays nothing for t has its nearest
+ * partner within d[t] + log|S_t| / kappa.  Both energies are C1.
+ * Totals.  g0[f] = (restraints' sum + clash gradient) + complementarity gradient; E[g] likewise, and dev_energy's rows hold the
+ * total.  The VJP, shift, clip, pin selects and COM removal are unchanged.  A graph without features, and atoms of radius 0,
+ * contribute exact zeros.  The sums' order is fixed: the same bits on every run.
+ * Arming.  pf_guide_field_next comes after a bind and arms the NEXT pf_sample_begin_guided (also the one inside pf_sample_guided),
+ * which consumes it, accepted or not; the field ends with that run.  atom_r NULL: no clash term; ph_ptr NULL: no complementarity
+ * term (the arrays behind it are then not read).  It validates on the host before anything is touched -- finite, non-negative
+ * radii, weights and distances; kappa > 0; types in range; a table of 0 / 1; ph_ptr[0] == 0, monotone, at most 4096 features per
+ * graph: a failure is PF_ERR_ARG with a message and leaves the handle as it was (a field armed before stays armed).  The arrays are
+ * copied into a handle-owned pinned buffer before the call returns.  The begin of any other run kind while a field is armed
+ * returns PF_ERR_STATE and drops the arming; so does a bind (silently).  A run in progress is not touched by any of this.
+ * pf_debug_last_field: the three components of the last guided step per graph, [B][3]: restraints, clash, complementarity
+ * (their sum in that order is E[g]); PF_ERR_STATE when the last guided step on this batch had no field. */
+int pf_guide_field_next(pf_handle* h, const float* host_atom_r /*[Np_tot] or NULL*/, float w_clash, const int32_t* host_ph_ptr /*[B+1] or NULL*/,
+                        const float* host_ph_x /*[n,3]*/, const int32_t* host_ph_type /*[n]*/, const int32_t* host_match /*[pharm_nf,pharm_nf]*/,
+                        const float* host_dist /*[pharm_nf]*/, float w_comp, float kappa, float type_sharpness);
+int pf_debug_last_field(pf_handle* h, float* dev_E3 /*[B,3]*/, pf_stream stream);
+
 /* -- seeded sampling: start the reverse process from a given pharmacophore (partial diffusion; no reference counterpart) ----------
  * The given sample is noised forward to an intermediate level a, 1 <= a <= T, and only the reverse steps a-1 .. 0 are run: a small
  * a gives close analogues of the seed, a large a loose ones.

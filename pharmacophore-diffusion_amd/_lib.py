@@ -104,6 +104,8 @@ SYMBOLS = {
     "pf_sample_ms": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PfMsCoef), _P, _P, _F, _P, _P, _P, _P, _P]),
     "pf_score": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.POINTER(PfScoreLevel), _P, _P, _P, _I32, _F, _I32, _I32, _I32, _P, _P, _P]),
     "pf_debug_last_guidance": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "pf_guide_field_next": (ctypes.c_int, [_P, _P, _F, _P, _P, _P, _P, _P, _F, _F, _F]),
+    "pf_debug_last_field": (ctypes.c_int, [_P, _P, _P]),
     "pf_dynamics_input_vjp": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "pf_param_count": (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "pf_param_layout": (ctypes.c_int, [_P, _I32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),

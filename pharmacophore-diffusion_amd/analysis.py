@@ -173,6 +173,27 @@ _MATCHING_DIST = {"Aromatic": 7, "Hydrophobic": 5, "HydrogenAcceptor": 4, "Hydro
                   "PositiveIon": 5}
 
 
+def complementarity_tables():
+    """(match [6, 6] int32, dist [6] float32) in ph_idx_to_type's order: match[t][u] == 1 where a center of type t is matched by
+    a receptor feature of type u, dist[t] the distance within which it counts -- _MATCHING_TYPES / _MATCHING_DIST as the
+    tables the pocket field's complementarity term takes (PfEngine.field_next)."""
+    match = torch.tensor([[int(u in _MATCHING_TYPES[t]) for u in ph_idx_to_type] for t in ph_idx_to_type], dtype=torch.int32)
+    dist = torch.tensor([float(_MATCHING_DIST[t]) for t in ph_idx_to_type], dtype=torch.float32)
+    return match, dist
+
+
+def clash_energy(ph_coords, prot_x, radius=2.0, weight=1.0):
+    """(energy, clashing pairs) of centers [n, 3] against atoms [m, 3], both in the pocket's frame, in fp64: the pocket field's
+    clash term, weight * max(0, radius - distance)^2 over all (center, atom) pairs, and the number of pairs inside the radius.
+    ``radius``: a float or a per-atom tensor [m]."""
+    x, a = torch.as_tensor(ph_coords).double().reshape(-1, 3), torch.as_tensor(prot_x).double().reshape(-1, 3).cpu()
+    if x.shape[0] == 0 or a.shape[0] == 0:
+        return 0.0, 0
+    r = torch.as_tensor(radius).double().reshape(-1).cpu()
+    gap = torch.clamp(r[None] - torch.cdist(x.cpu(), a), min=0)
+    return float(weight) * float((gap * gap).sum()), int((gap > 0).sum())
+
+
 def compute_complementarity(pharm_types, pharm_pos, prot_ph_types, prot_ph_pos, return_count=False):
     """metrics.py:53-86: number (or fraction) of centers with a complementary receptor feature within
     the type-specific distance."""

@@ -577,6 +577,23 @@ struct GuideShiftParams {
     float alpha_t, sigma_t, scale, clip;
     float* grad; float* shift; // [Nf][3] each: what the step applied (pf_debug_last_guidance); a position-pinned center's row is what it ignored
 };
+// the pocket field of a guided run (pf_guide_field_next; the block's layout: pf_field.h): what k_guide_field reads -- of StepParams
+// the graph pointers, xn, pharm_h, eps_x, eps_h and nf -- and adds into, behind k_guide_grad
+struct FieldParams {
+    const float* atom_r;       // [Np]
+    const int* ph_ptr;         // [B + 1]
+    const float4* ph_xt;       // [n]  position in the caller's frame; .w: the type (an integer's bits)
+    const int* match;          // [nf][nf]  match[t][u] != 0: a center of type t is matched by a receptor feature of type u
+    const float* dist;         // [nf]
+    float w_clash, w_comp, kappa, type_sharpness;
+    float alpha_t, sigma_t;    // pf_guide_coef
+    int ep_coord, ep_feat;
+    const float* D;            // [B][3], as k_guide_grad left it
+    float* g0;                 // [Nf][3]  added into
+    float* energy;             // [B]      added into
+    float* traj_energy;        // [B] row of the caller's trajectory of energies, or NULL (rewritten with the total)
+    float* E3;                 // [B][3]   restraints, clash, complementarity
+};
 #ifdef __HIPCC__
 // The p(z_s | z_t) update of sample_p_zs_given_zt (pharmacodiff.py:397-426) for ONE value -- coordinate or feature -- and the only place
 // it is written: the generic update, the latency-optimised one (center threads / feature lanes) and the center hoist's copy all call

@@ -22,6 +22,7 @@
 #include "pf_train.h"
 #include "pf_score.h"
 #include "pf_optim.h"
+#include "pf_field.h"
 
 using namespace pfpack;
 
@@ -70,6 +71,7 @@ void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const Build
 void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s);
 void pfk_step_update_guided(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, hipStream_t s);
 void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s);
+void pfk_guide_field(const StepParams* p, const FieldParams* q, hipStream_t s);
 void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s);
 void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s);
 void pfk_step_build_seed(const StepParams* sp, const SeedParams* q, const BuildParams* bp, hipStream_t s);
@@ -417,6 +419,16 @@ struct pf_handle {
     bool guide_wide = true, guide_in_grads = false;   // the training family and the input-gradient switch the guided run began on
     bool guide_have = false;                // a guided step has run on this batch: pf_debug_last_guidance has something to return
     float* guide_traj_energy = nullptr;     // pf_sample_guided: row i of the caller's [n_steps][B] for the step in flight
+    // pocket field (pf_guide_field_next): clash and complementarity energies next to a guided run's restraints.  Arming validates
+    // and packs the caller's host arrays into pinned memory in the block's layout (pf_field.h; field_ev: the last upload that read
+    // the staging buffer); the next pf_sample_begin_guided uploads it into one device allocation, kept and grown like d_restr, and
+    // the run's steps launch k_guide_field behind k_guide_grad.  field_arm: what is armed; field_run: what the run in progress uses
+    struct FieldScalars { int n = 0; float w_clash = 0.f, w_comp = 0.f, kappa = 1.f, type_sharpness = 0.f; };
+    void* field_stage = nullptr; size_t field_stage_capacity = 0; hipEvent_t field_ev = nullptr;
+    void* d_field = nullptr; size_t field_capacity = 0;
+    bool field_armed = false, field_on = false;
+    bool field_have = false;                // the last guided step on this batch launched k_guide_field: pf_debug_last_field
+    FieldScalars field_arm, field_run;
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
@@ -1530,6 +1542,9 @@ void pf_destroy(pf_handle* h) {
     if (h->d_optim_part) (void)hipFree(h->d_optim_part);
     if (h->restr_stage) (void)hipHostFree(h->restr_stage);
     if (h->restr_ev) (void)hipEventDestroy(h->restr_ev);
+    if (h->d_field) (void)hipFree(h->d_field);
+    if (h->field_stage) (void)hipHostFree(h->field_stage);
+    if (h->field_ev) (void)hipEventDestroy(h->field_ev);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
     for (int k = 0; k < 2; ++k) {
         if (h->d_tab[k]) (void)hipFree(h->d_tab[k]);
@@ -1707,6 +1722,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     pfbind::BindInputs in;
     if (h) in.rep.swap(h->pending_rep);
     if (h) h->seed_armed = false;               // (so does a seed: pf_sample_seed_next comes after the bind it is for)
+    if (h) h->field_armed = false;              // (and a pocket field: its arrays are sized by the batch it was armed on)
     if (h) h->ms_hist_valid = false;            // (and the multistep history: it belongs to a run on the batch before)
     int rc = check_ready(h, false);
     if (rc) return rc;
@@ -1861,6 +1877,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     h->zs_version = 0; h->zs_batch_coords = false; h->coords_custom = false;
     h->have_batch = true;
     h->run = RUN_NONE; h->guide_have = false;
+    h->field_on = false; h->field_have = false;
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
 }
@@ -1870,7 +1887,7 @@ int pf_set_pocket_batch(pf_handle* h, int32_t B, const int32_t* prot_ptr, const 
                         const int32_t* pp_dst, pf_stream stream) {
     if (h && (!dev_prot_x || !dev_prot_h)) {
         h->pending_rep.clear();                  // a pocket-group claim never outlives the bind it was made for, rejected or not
-        h->seed_armed = false;
+        h->seed_armed = false; h->field_armed = false;
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch: bad argument");
     }
     return set_pocket_batch_impl(h, B, prot_ptr, pharm_ptr, dev_prot_x, dev_prot_h, nullptr, nullptr, n_pp, pp_src, pp_dst, stream);
@@ -1881,7 +1898,7 @@ int pf_set_pocket_batch_host(pf_handle* h, int32_t B, const int32_t* prot_ptr, c
                              const int32_t* pp_dst, pf_stream stream) {
     if (h && (!host_prot_x || !host_prot_h)) {
         h->pending_rep.clear();
-        h->seed_armed = false;
+        h->seed_armed = false; h->field_armed = false;
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch_host: bad argument");
     }
     return set_pocket_batch_impl(h, B, prot_ptr, pharm_ptr, nullptr, nullptr, host_prot_x, host_prot_h, n_pp, pp_src, pp_dst, stream);
@@ -1971,6 +1988,18 @@ static bool take_seed(pf_handle* h) {
     return armed;
 }
 static int seed_move(pf_handle* h, const float* dev_noise0, hipStream_t s);
+// Pocket field (pf_guide_field_next): it arms the next GUIDED begin, which takes it off the handle on entry like a seed; the begin
+// of any other run kind drops it and says so
+static bool take_field(pf_handle* h) {
+    const bool armed = h && h->field_armed;
+    if (h) h->field_armed = false;
+    return armed;
+}
+static int refuse_field(pf_handle* h, const char* who) {
+    if (take_field(h)) PF_FAIL(h, PF_ERR_STATE, "%s while a pocket field is armed (pf_guide_field_next arms pf_sample_begin_guided / pf_sample_guided "
+                                                "only): the arming is dropped", who);
+    return PF_OK;
+}
 
 static int begin_plain(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, bool seeded, pf_stream stream) {
     int rc = check_ready(h, true);
@@ -1999,13 +2028,16 @@ static int begin_plain(pf_handle* h, const float* dev_init_pharm_com, const floa
     }
     h->coords_custom = false;               // a rigid translate of the batch's own coordinates from here on
     h->run = RUN_PLAIN;
+    h->field_on = false;                    // a pocket field ends with its run
     h->ms_hist_valid = false;               // a run begins without a previous output
     h->edges_built = false; h->rec_valid = false;
     // a seeded begin: the state is the noised seed, made by a move of the step end (which also writes the snapshot, after the move)
     return seeded ? seed_move(h, dev_noise0, s) : PF_OK;
 }
 int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, pf_stream stream) {
-    return begin_plain(h, dev_init_pharm_com, dev_noise0, take_seed(h), stream);
+    const bool seeded = take_seed(h);
+    if (const int rc = refuse_field(h, "pf_sample_begin")) return rc;
+    return begin_plain(h, dev_init_pharm_com, dev_noise0, seeded, stream);
 }
 
 // ---- the sampler's run state: one guard for the entry points that need a run in progress ----
@@ -2168,7 +2200,9 @@ static int begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const flo
 }
 int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
                            const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, pf_stream stream) {
-    return begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, take_seed(h), stream);
+    const bool seeded = take_seed(h);
+    if (const int rc = refuse_field(h, "pf_sample_begin_pinned")) return rc;
+    return begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, seeded, stream);
 }
 
 // Arms the next begin with a seed (the semantics: pfdyn.h).  Every argument check runs before anything is touched; the two arrays
@@ -3507,7 +3541,7 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
                            const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, const int32_t* host_restr_ptr,
                            const int32_t* host_restr_kind, const int32_t* host_restr_center, const float* host_restr_p,
                            const float* host_restr_r, const float* host_restr_w, float guide_scale, float guide_clip, pf_stream stream) {
-    const bool seeded = take_seed(h);
+    const bool seeded = take_seed(h), fielded = take_field(h);
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!dev_noise0) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null noise");
@@ -3536,6 +3570,8 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     const size_t gwords = nf1 * (12 + nh) + (size_t)h->B * 4;
     if ((rc = grow_run_scratch(h, &h->d_guide, &h->guide_capacity, gwords * 4, gwords * 4, s)) != PF_OK) return rc;
     if (!h->restr_ev) PF_HIP(h, hipEventCreateWithFlags(&h->restr_ev, hipEventDisableTiming));
+    const pffield::FieldLayout fl(h->Np, h->B, h->field_arm.n, h->cfg.pharm_nf);
+    if (fielded && (rc = grow_run_scratch(h, &h->d_field, &h->field_capacity, fl.words() * 4, fl.words() * 8, s)) != PF_OK) return rc;
     rc = begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, seeded, stream);
     if (rc) return rc;
     {
@@ -3552,13 +3588,19 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
         PF_HIP(h, hipEventRecord(h->restr_ev, s));
     }
     h->n_restr = (int)n;
+    if (fielded) {                          // the armed field becomes this run's: one copy out of the staging buffer
+        PF_HIP(h, hipMemcpyAsync(h->d_field, h->field_stage, fl.upload_words() * 4, hipMemcpyHostToDevice, s));
+        PF_HIP(h, hipEventRecord(h->field_ev, s));
+        h->field_run = h->field_arm;
+        h->field_on = true;
+    }
     float* gq = (float*)h->d_guide;
     h->d_g0 = gq; h->d_gjx = gq + nf1 * 3; h->d_ggrad = gq + nf1 * 6; h->d_gshift = gq + nf1 * 9; h->d_gzero = gq + nf1 * 12;
     h->d_genergy = h->d_gzero + nf1 * nh; h->d_gD = h->d_genergy + h->B;
     PF_HIP(h, hipMemsetAsync(h->d_guide, 0, gwords * 4, s));          // (the zero g_eps_h of every step's VJP; nothing writes it)
     h->guide_scale = guide_scale; h->guide_clip = guide_clip;
     h->guide_traj_energy = nullptr;
-    h->run = RUN_GUIDED; h->guide_have = false;
+    h->run = RUN_GUIDED; h->guide_have = false; h->field_have = false;
     h->guide_wide = h->train_wide; h->guide_in_grads = h->train_in_grads;
     return PF_OK;
 }
@@ -3597,6 +3639,20 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     gq.com_init = h->d_com_init; gq.alpha_t = gc->alpha_t; gq.sigma_t = gc->sigma_t; gq.ep_coord = ep_coord;
     gq.g0 = h->d_g0; gq.energy = h->d_genergy; gq.traj_energy = h->guide_traj_energy; gq.D = h->d_gD;
     pfk_guide_grad(&sp, &gq, s);
+    if (h->field_on) {                          // the pocket field adds into g0 and E (one more launch; none without a field)
+        const pffield::FieldLayout fl(h->Np, h->B, h->field_run.n, h->cfg.pharm_nf);
+        const float* fb = (const float*)h->d_field;
+        FieldParams fq{};
+        fq.ph_xt = (const float4*)(fb + fl.ph_xt()); fq.atom_r = fb + fl.atom_r(); fq.ph_ptr = (const int*)(fb + fl.ph_ptr());
+        fq.match = (const int*)(fb + fl.match()); fq.dist = fb + fl.dist();
+        fq.w_clash = h->field_run.w_clash; fq.w_comp = h->field_run.w_comp; fq.kappa = h->field_run.kappa;
+        fq.type_sharpness = h->field_run.type_sharpness;
+        fq.alpha_t = gc->alpha_t; fq.sigma_t = gc->sigma_t; fq.ep_coord = ep_coord; fq.ep_feat = ep_feat;
+        fq.D = h->d_gD; fq.g0 = h->d_g0; fq.energy = h->d_genergy; fq.traj_energy = h->guide_traj_energy;
+        fq.E3 = (float*)h->d_field + fl.e3();
+        pfk_guide_field(&sp, &fq, s);
+    }
+    h->field_have = h->field_on;
     rc = h->train_wide ? wide_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s)
                        : tuned_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s);
     if (rc) return rc;
@@ -3634,6 +3690,45 @@ int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* 
     if (dev_grad && nb) PF_HIP(h, hipMemcpyAsync(dev_grad, h->d_ggrad, nb, hipMemcpyDeviceToDevice, s));
     if (dev_shift && nb) PF_HIP(h, hipMemcpyAsync(dev_shift, h->d_gshift, nb, hipMemcpyDeviceToDevice, s));
     if (dev_energy && h->B) PF_HIP(h, hipMemcpyAsync(dev_energy, h->d_genergy, (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
+    return PF_OK;
+}
+
+// Arms the next guided begin with a pocket field (the semantics: pfdyn.h).  Every check runs before anything is touched (pf_field.h,
+// host only); then the arrays are packed into the handle's pinned staging buffer -- after the last upload out of it has been
+// waited for -- and stay there until that begin uploads them on its own stream.  A run in progress reads none of it and goes on
+int pf_guide_field_next(pf_handle* h, const float* host_atom_r, float w_clash, const int32_t* host_ph_ptr, const float* host_ph_x,
+                        const int32_t* host_ph_type, const int32_t* host_match, const float* host_dist, float w_comp, float kappa,
+                        float type_sharpness) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    const pffield::FieldArgs a{host_atom_r, w_clash, host_ph_ptr, host_ph_x, host_ph_type, host_match, host_dist, w_comp, kappa, type_sharpness};
+    char msg[256];
+    if (!pffield::validate(a, h->B, h->Np, h->cfg.pharm_nf, msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
+    const int n = pffield::n_features(a, h->B);
+    const pffield::FieldLayout fl(h->Np, h->B, n, h->cfg.pharm_nf);
+    const size_t bytes = fl.upload_words() * 4;
+    if (h->field_ev) PF_HIP(h, hipEventSynchronize(h->field_ev));      // the last upload has read the staging buffer
+    else PF_HIP(h, hipEventCreateWithFlags(&h->field_ev, hipEventDisableTiming));
+    h->field_armed = false;                 // (a field armed before and not yet used is replaced, also when the allocation below fails)
+    if (bytes > h->field_stage_capacity) {
+        if (h->field_stage) { (void)hipHostFree(h->field_stage); h->field_stage = nullptr; h->field_stage_capacity = 0; }
+        PF_HIP(h, hipHostMalloc(&h->field_stage, bytes * 2, hipHostMallocDefault));
+        h->field_stage_capacity = bytes * 2;
+    }
+    pffield::pack(a, h->B, h->Np, h->cfg.pharm_nf, (uint32_t*)h->field_stage);
+    h->field_arm.n = n; h->field_arm.w_clash = w_clash; h->field_arm.w_comp = w_comp; h->field_arm.kappa = kappa;
+    h->field_arm.type_sharpness = type_sharpness;
+    h->field_armed = true;
+    return PF_OK;
+}
+
+int pf_debug_last_field(pf_handle* h, float* dev_E3, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!h->guide_have || !h->field_have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_field: no guided step with a pocket field on this batch");
+    if (!dev_E3) PF_FAIL(h, PF_ERR_ARG, "pf_debug_last_field: null argument");
+    const pffield::FieldLayout fl(h->Np, h->B, h->field_run.n, h->cfg.pharm_nf);
+    if (h->B) PF_HIP(h, hipMemcpyAsync(dev_E3, (const float*)h->d_field + fl.e3(), (size_t)h->B * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PF_OK;
 }
 

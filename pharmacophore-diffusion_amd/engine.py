@@ -576,8 +576,54 @@ class PfEngine:
             self._ck(self.lib.pf_sample_seed_next(self._h, ctypes.byref(coef), _dptr(sx), _dptr(sh), float(feat_norm_constant),
                                                   _stream_ptr()), "pf_sample_seed_next")
 
+    def field_next(self, atom_r=None, w_clash=0.0, ph=None, match=None, dist=None, w_comp=0.0, kappa=4.0, type_sharpness=0.0):
+        """Arms the next guided begin on this engine -- sample_begin(restraints=...) or sample(restraints=...) -- with a pocket
+        field (pf_guide_field_next; the energies: include/pfdyn.h).  atom_r [Np] (or a float for every atom; None: no clash term)
+        with w_clash; ph = (ph_ptr [B + 1], ph_x [n, 3] in the caller's frame, ph_type [n]) (None: no complementarity term) with
+        match [pharm_nf, pharm_nf] (0 / 1), dist [pharm_nf], w_comp, kappa and type_sharpness.  Host arrays (tensors, numpy or
+        lists); the library validates the values (PfError, PF_ERR_ARG) and copies them before this returns.  The begin of any
+        other run kind while a field is armed is a PfError (PF_ERR_STATE) and drops it; set_batch drops it silently."""
+        import numpy as np
+        host = lambda v, d, shape: np.ascontiguousarray(np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=d).reshape(shape))
+        keep, none = [], ctypes.c_void_p(None)
+        def arg(v, d, shape):
+            if v is None:
+                return none
+            keep.append(host(v, d, shape))
+            return keep[-1].ctypes.data
+        if atom_r is not None and not torch.is_tensor(atom_r) and np.ndim(atom_r) == 0:
+            atom_r = np.full(self.Np, float(atom_r), dtype=np.float32)
+        if atom_r is not None:
+            atom_r = host(atom_r, np.float32, -1)
+            if atom_r.shape[0] != self.Np:
+                raise ValueError(f"atom_r has one radius per atom ({self.Np})")
+        ptr = xs = ty = None
+        if ph is not None:
+            ptr, xs, ty = ph
+            ptr = host(ptr, np.int32, -1)
+            if ptr.shape != (self.B + 1,):
+                raise ValueError(f"ph_ptr has B + 1 = {self.B + 1} entries")
+            n = max(int(ptr[-1]), 0)
+            xs, ty = host(xs, np.float32, (-1, 3)), host(ty, np.int32, -1)
+            if xs.shape[0] < n or ty.shape[0] < n:
+                raise ValueError(f"ph_ptr names {n} receptor features; ph_x / ph_type hold {xs.shape[0]} / {ty.shape[0]}")
+            if match is None or dist is None:
+                raise ValueError("receptor features need the match table and the distances")
+        nf = self.pharm_nf
+        args = (arg(atom_r, np.float32, -1), float(w_clash), arg(ptr, np.int32, -1), arg(xs, np.float32, (-1, 3)), arg(ty, np.int32, -1),
+                arg(match, np.int32, (nf, nf)), arg(dist, np.float32, (nf,)), float(w_comp), float(kappa), float(type_sharpness))
+        self._ck(self.lib.pf_guide_field_next(self._h, *args), "pf_guide_field_next")
+
+    def last_field_energies(self):
+        """[B, 3] of the last guided step with a pocket field: the restraints', the clash and the complementarity energy per
+        graph (pf_debug_last_field); their sum in that order is last_guidance()'s E."""
+        e3 = torch.empty(self.B, 3, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_debug_last_field(self._h, _dptr(e3), _stream_ptr()), "pf_debug_last_field")
+        return e3
+
     def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0, restraints=None, guide_scale=1.0,
-                     guide_clip=0.0, seed=None, guide_family=None):
+                     guide_clip=0.0, seed=None, guide_family=None, field=None):
         """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the begin.
         pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
         denoise_step(..., pin_coef=...); feat_norm_constant is what the given feature rows are divided by.
@@ -585,7 +631,10 @@ class PfEngine:
         guided_step; the caller has selected the wide training family (set_train_family('wide')); pins are optional.
         guide_family 'wide' / 'tuned' (guided runs only; None: the caller has selected the family): selects that training family --
         for 'tuned', a 128 / 16 handle, also the input-gradient switch -- and leaves it selected: the run's steps need it, and the
-        caller restores what it had once the run has ended."""
+        caller restores what it had once the run has ended.
+        field (a dict of field_next's arguments): a guided run with a pocket field, also without restraints."""
+        if field is not None and restraints is None:
+            restraints = [None] * self.B
         if guide_family is not None:
             self._check_guide_family(guide_family)
             if restraints is None:
@@ -598,6 +647,8 @@ class PfEngine:
             self._arm_guide_family(guide_family)
         if seed is not None:
             self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
+        if field is not None:
+            self.field_next(**field)
         with torch.cuda.device(self.device):
             if restraints is not None:
                 self._ck(self.lib.pf_sample_begin_guided(self._h, _dptr(com), _dptr(nz), *pin, float(feat_norm_constant), *restr,
@@ -683,8 +734,9 @@ class PfEngine:
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
                feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None, restraints=None,
                guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False, seed=None, ms_coef_arr=None,
-               guide_family="wide"):
-        """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the run -- n_steps is
+               guide_family="wide", field=None):
+        """field (a dict of field_next's arguments): the guided run carries a pocket field; restraints are then optional.
+        seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the run -- n_steps is
         then the seed's level a, and coef_arr (and the other per-step arrays) hold the entries of s = a-1 .. 0.
         pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned.
         plan = (op_arr, renoise_arr) (plan_arrays; n_steps is then the number of ops and coef_arr / pin_coef_arr have one entry
@@ -696,12 +748,14 @@ class PfEngine:
         the tuned training family with its input-gradient switch armed; family and switch are restored afterwards, also on error.
         ms_coef_arr (ms_coef_array): a multistep run, pf_sample_ms -- coef_arr is not read (None), noise needs its first row only
         (the initial draw), and the parameterisation is in the coefficients; seeds compose, pins, plans and restraints are refused."""
+        if field is not None and restraints is None and ms_coef_arr is None:
+            restraints = [None] * self.B
         guided = restraints is not None
         if guide_family not in PfEngine.GUIDE_FAMILIES:
             raise ValueError(f"guide_family must be 'wide' or 'tuned', got {guide_family!r}")
         if ms_coef_arr is not None:
-            if pins is not None or plan is not None or guided:
-                raise ValueError("a multistep run composes with seeds only: no pins, resampling plan or restraints")
+            if pins is not None or plan is not None or guided or field is not None:
+                raise ValueError("a multistep run composes with seeds only: no pins, resampling plan, restraints or pocket field")
             if len(ms_coef_arr) < n_steps:
                 raise ValueError(f"a multistep run of {n_steps} steps needs {n_steps} entries in ms_coef_arr")
             nz = _f32(noise, self.device)
@@ -751,6 +805,8 @@ class PfEngine:
             try:
                 if seed is not None:
                     self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
+                if field is not None:
+                    self.field_next(**field)
                 with torch.cuda.device(self.device):
                     self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
             finally:
@@ -763,6 +819,8 @@ class PfEngine:
         try:
             if seed is not None:
                 self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
+            if field is not None:
+                self.field_next(**field)
             with torch.cuda.device(self.device):
                 self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
         finally:

@@ -844,6 +844,23 @@ class PharmSizeDistribution:
 
 
 # ---------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class PocketField:
+    """Pocket-derived guidance of a sampling run (PharmacophoreDiff.sample(pocket_field=...); the energies: include/pfdyn.h,
+    "pocket field").  ``clash_radius``: None (no clash term), a float for every atom, or a per-atom tensor ([n_atoms] of the pocket;
+    for several pockets a list with one entry per pocket) -- a center of the predicted clean sample inside that radius of an atom
+    is pushed out with ``clash_weight``; a radius of 0 makes an atom inert.  ``comp_weight`` > 0: a center of type t is pulled to
+    within the matching distance of a complementary receptor feature (the graph's prot_ph_x / prot_ph_h; the table and the
+    distances are analysis._MATCHING_TYPES / _MATCHING_DIST, what SampleAnalyzer's validity counts); ``kappa`` (1 / angstrom) is
+    the sharpness of the soft minimum over the matching features, ``type_sharpness`` that of the soft type assignment, on
+    one-hot-scaled features (the model multiplies it by its pharm_feat_norm_constant)."""
+    clash_radius: object = 2.0
+    clash_weight: float = 1.0
+    comp_weight: float = 0.0
+    kappa: float = 4.0
+    type_sharpness: float = 4.0
+
+
 class PharmacophoreDiff(_Base):
     """Drop-in for pharmacoforge.models.pharmacodiff.PharmacophoreDiff on the sampling / evaluation
     path.  Constructor arguments, attribute names, state-dict keys ('gamma.gamma', 'dynamics.*') and
@@ -960,7 +977,7 @@ class PharmacophoreDiff(_Base):
                               noise: torch.Tensor = None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None,
                               guide_scale: float = 1.0, guide_clip: float = 0.0, seeds=None, seed_level: int = None,
                               seed_keep=None, sample_steps: int = None, sampler: str = None, eta: float = None,
-                              spacing: str = None, guide_family: str = "wide") -> List[SampledPharmacophore]:
+                              spacing: str = None, guide_family: str = "wide", pocket_field=None) -> List[SampledPharmacophore]:
         """Reverse diffusion for a batch of pocket graphs; the whole T-step loop is enqueued on the
         current HIP stream by pf_sample (no host synchronisation inside the loop).
 
@@ -979,7 +996,8 @@ class PharmacophoreDiff(_Base):
 
         ``restraints``: None, or one list (or None) per graph of the batch of (kind, center, point, radius, weight) (see
         ``sample``): with a restraint in it the run is pf_sample_guided with ``guide_scale`` / ``guide_clip``, on the kernel
-        family ``guide_family`` names ('wide', the default, or 'tuned': see ``sample``).
+        family ``guide_family`` names ('wide', the default, or 'tuned': see ``sample``).  ``pocket_field`` (a PocketField whose
+        per-atom radii, if any, cover the batch's atoms): the run is guided also without restraints (see ``sample``).
 
         ``seeds`` with ``seed_level`` a (and optionally ``seed_keep``): a seeded run (pf_sample_seed_next) -- one (x [n,3], types
         [n]) per graph of the batch, n that graph's number of centers; the run starts from the seeds noised to level a and makes
@@ -992,7 +1010,8 @@ class PharmacophoreDiff(_Base):
         self._check_guide_family(guide_family)
         fewstep = self._fewstep(sample_steps, sampler, eta, spacing, pin_resamples=pin_resamples, seed_level=seed_level,
                                 pins=(g.pharm_pin is not None and bool((g.pharm_pin != 0).any())) or seed_keep is not None,
-                                restraints=restraints is not None and any(len(r) > 0 for r in restraints if r is not None))
+                                restraints=pocket_field is not None
+                                or (restraints is not None and any(len(r) > 0 for r in restraints if r is not None)))
         if (seeds is None) != (seed_level is None):
             raise ValueError("seeds and seed_level go together: a seeded run needs both")
         if seeds is None and seed_keep is not None:
@@ -1016,7 +1035,49 @@ class PharmacophoreDiff(_Base):
                                                                            pin_resamples=pin_resamples, pin_jump=pin_jump,
                                                                            restraints=restraints, guide_scale=guide_scale,
                                                                            guide_clip=guide_clip, seed_level=seed_level,
-                                                                           fewstep=fewstep, guide_family=guide_family)))
+                                                                           fewstep=fewstep, guide_family=guide_family,
+                                                                           field=self._field_for_batch(g, pocket_field))))
+
+    def _field_for_batch(self, g, pocket_field, radii=None):
+        """PfEngine.field_next's arguments for a batched graph and a PocketField (None: None), checked before any device work.
+        ``radii``: per graph of the batch a float or that graph's per-atom tensor (None: pocket_field.clash_radius for the whole
+        batch).  Receptor features are the graphs' prot_ph_x (the pocket's frame) with the types prot_ph_h's argmax."""
+        pf = pocket_field
+        if pf is None:
+            return None
+        if not isinstance(pf, PocketField):
+            raise ValueError(f"pocket_field must be a PocketField, got {type(pf).__name__}")
+        from .analysis import complementarity_tables
+        kw = dict(kappa=float(pf.kappa), type_sharpness=float(pf.type_sharpness) * float(self.pharm_feat_norm_constant),
+                  w_clash=float(pf.clash_weight), w_comp=float(pf.comp_weight))
+        counts = (g.prot_ptr[1:] - g.prot_ptr[:-1]).tolist()
+        if radii is None and pf.clash_radius is not None:
+            r = pf.clash_radius
+            if torch.is_tensor(r):
+                if r.numel() != int(g.prot_ptr[-1]):
+                    raise ValueError(f"clash_radius has {r.numel()} entries for a batch of {int(g.prot_ptr[-1])} atoms")
+                kw["atom_r"] = r.detach().float().reshape(-1).cpu()
+            else:
+                kw["atom_r"] = float(r)
+        elif radii is not None:
+            rows = []
+            for i, (r, n) in enumerate(zip(radii, counts)):
+                if torch.is_tensor(r):
+                    if r.numel() != n:
+                        raise ValueError(f"clash_radius has {r.numel()} entries for a pocket of {n} atoms (graph {i} of the batch)")
+                    rows.append(r.detach().float().reshape(-1).cpu())
+                else:
+                    rows.append(torch.full((n,), float(r)))
+            kw["atom_r"] = torch.cat(rows) if rows else torch.zeros(0)
+        if float(pf.comp_weight) > 0:
+            if g.prot_ph_x is None or g.prot_ph_h is None or g.prot_ph_ptr is None:
+                raise ValueError("comp_weight > 0 needs receptor features on the graphs (prot_ph_x / prot_ph_h), and these have none: "
+                                 "PDB input carries no receptor features; use comp_weight = 0 or a dataset graph")
+            match, dist = complementarity_tables()
+            if self.n_pharm_feats != match.shape[0]:
+                raise ValueError(f"the complementarity tables are for {match.shape[0]} feature types; this model has {self.n_pharm_feats}")
+            kw.update(ph=(g.prot_ph_ptr.cpu(), g.prot_ph_x.detach().float().cpu(), g.prot_ph_h.detach().argmax(dim=1).cpu()), match=match, dist=dist)
+        return kw
 
     def _check_guide_family(self, guide_family):
         """``guide_family`` of sample / sample_given_receptor, checked before any device work: 'wide' (default) or 'tuned', which
@@ -1163,11 +1224,11 @@ class PharmacophoreDiff(_Base):
 
     def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0,
                         pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0, guide_clip: float = 0.0,
-                        seed_level: int = None, fewstep=None, guide_family: str = "wide"):
+                        seed_level: int = None, fewstep=None, guide_family: str = "wide", field=None):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
         current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  ``restraints``: None or one
         list (or None) per graph of the batch; a batch takes the guided path (pf_sample_guided) only when one of them holds a
-        restraint, as with pin flags.  A batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled.
+        restraint, as with pin flags, or when ``field`` (_field_for_batch) is given.  A batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled.
         ``seed_level`` a: a seeded run -- the graph's pharm_pin_x / pharm_pin_h hold the seed of EVERY center (the flags say which
         of them stay fixed), the run starts at level a (pf_sample_seed_next) and its arrays hold the steps a-1 .. 0.
         ``fewstep`` (_fewstep): the run visits the N + 1 levels of a plan from T (or a) down; 'multistep': pf_sample_ms."""
@@ -1182,7 +1243,7 @@ class PharmacophoreDiff(_Base):
         if pin_resamples < 1 or pin_jump < 1:
             raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
         has_pins = g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
-        guided = restraints is not None and any(len(r) > 0 for r in restraints if r is not None)
+        guided = (restraints is not None and any(len(r) > 0 for r in restraints if r is not None)) or field is not None
         if guided and pin_resamples > 1:
             raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
         kw = {}
@@ -1215,6 +1276,10 @@ class PharmacophoreDiff(_Base):
                 raise ValueError(f"a seeded run of {n_ops} ops (seed level {top}) needs {n_ops + 1} noise rows, got {noise.shape[0]}")
             kw["seed"] = (g.pharm_pin_x, g.pharm_pin_h, seed_coefficients(self.gamma.gamma, self.n_timesteps, top))
         if guided:
+            if restraints is None:
+                restraints = [None] * g.batch_size
+            if field is not None:
+                kw["field"] = field
             if len(restraints) != g.batch_size:
                 raise ValueError(f"restraints lists {len(restraints)} entries for a batch of {g.batch_size} graphs")
             kw.update(restraints=restraints, guide_coef_arr=step_arrays("guide", top), guide_scale=float(guide_scale),
@@ -1300,7 +1365,7 @@ class PharmacophoreDiff(_Base):
                pinned=None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0,
                guide_clip: float = 0.0, seeds=None, seed_level: int = None, seed_keep=None,
                score_levels: int = None, sample_steps: int = None, sampler: str = None, eta: float = None,
-               spacing: str = None, guide_family: str = "wide") -> List[List[SampledPharmacophore]]:
+               spacing: str = None, guide_family: str = "wide", pocket_field=None) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -1334,6 +1399,12 @@ class PharmacophoreDiff(_Base):
         training forward and input gradients on the tuned kernels; any other model is a ValueError.
         Composes with ``pinned``; together with ``pin_resamples`` > 1 it is a ValueError.
 
+        ``pocket_field``: None or a PocketField -- clash avoidance against the pocket's own atoms and / or complementarity to its
+        receptor features, added to the restraints' energy.  EVERY batch then runs guided, with or without
+        restraints; it composes with ``pinned``, ``restraints``, ``seeds`` and ``sample_steps`` with 'ancestral' / 'ddim', and is
+        refused like restraints with sampler 'multistep' and with ``pin_resamples`` > 1.  ``comp_weight`` > 0 on graphs without
+        prot_ph_x / prot_ph_h is a ValueError.  Coordinates only: features stay unguided.
+
         ``seeds`` with ``seed_level`` a, 1 <= a <= T: variations of given pharmacophores (partial diffusion, pf_sample_seed_next)
         -- one (x [n,3], types [n]) per pocket, every pocket must have one and every requested size of it must equal n.  Each
         seed is noised forward to level a and only the steps a-1 .. 0 are run: a small a gives close analogues, a large a loose
@@ -1365,7 +1436,7 @@ class PharmacophoreDiff(_Base):
         self._check_guide_family(guide_family)
         fewstep = self._fewstep(sample_steps, sampler, eta, spacing, pin_resamples=pin_resamples, seed_level=seed_level,
                                 pins=pinned is not None and any(p is not None for p in pinned) or seed_keep is not None,
-                                restraints=restraints is not None and any(restraints))
+                                restraints=(restraints is not None and any(restraints)) or pocket_field is not None)
         scored_graphs = ref_graphs
         from .sharding import shard_by_work
         ref_graphs = [as_pocket_graph(g) for g in ref_graphs]
@@ -1388,6 +1459,25 @@ class PharmacophoreDiff(_Base):
                         small = [int(n) for n in n_pharms[r] if int(n) <= int(c)]
                         if small:
                             raise ValueError(f"pocket {r}: a restraint names center {int(c)} but sizes {small} were requested")
+        radii = None
+        if pocket_field is not None:
+            if not isinstance(pocket_field, PocketField):
+                raise ValueError(f"pocket_field must be a PocketField, got {type(pocket_field).__name__}")
+            if pin_resamples > 1:
+                raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
+            r = pocket_field.clash_radius
+            if r is not None:
+                radii = list(r) if isinstance(r, (list, tuple)) else [r] * n_receptors
+                if len(radii) != n_receptors:
+                    raise ValueError(f"clash_radius lists {len(radii)} entries for {n_receptors} pockets")
+                for i, (ri, gi) in enumerate(zip(radii, ref_graphs)):
+                    if torch.is_tensor(ri) and ri.numel() != gi.num_nodes("prot"):
+                        raise ValueError(f"pocket {i}: clash_radius has {ri.numel()} entries for {gi.num_nodes('prot')} atoms")
+            if float(pocket_field.comp_weight) > 0:
+                for i, gi in enumerate(ref_graphs):
+                    if gi.prot_ph_x is None or gi.prot_ph_h is None:
+                        raise ValueError(f"pocket {i} has no receptor features (prot_ph_x / prot_ph_h): comp_weight > 0 needs them "
+                                         "(PDB input carries none; use comp_weight = 0 or a dataset graph)")
         if (seeds is None) != (seed_level is None):
             raise ValueError("seeds and seed_level go together: a seeded run needs both")
         if seeds is None and seed_keep is not None:
@@ -1466,10 +1556,11 @@ class PharmacophoreDiff(_Base):
                     nz = noise[bi]
                 # the bind is asynchronous (stream-ordered behind the lane's previous batch), nothing here waits for the device
                 batch_r = [restraints[graph_ref_idx[i]] for i in idx] if restraints is not None else None
+                field = self._field_for_batch(batch_g, pocket_field, None if radii is None else [radii[graph_ref_idx[i]] for i in idx])
                 enq = self._sample_enqueue(batch_g, init_coms, visualize_trajectory, nz, lane=lane,
                                            pin_resamples=pin_resamples, pin_jump=pin_jump, restraints=batch_r,
                                            guide_scale=guide_scale, guide_clip=guide_clip, seed_level=top, fewstep=fewstep,
-                                           guide_family=guide_family)
+                                           guide_family=guide_family, field=field)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on

@@ -39,6 +39,12 @@ _FLAGS = [
     ('--sampler', dict(choices=['ancestral', 'ddim', 'multistep'], default=None, help='with --sample_steps: ancestral (default), ddim (--eta, default 0) or multistep (second-order multistep solver)')),
     ('--eta', dict(type=float, default=None, help='with --sample_steps --sampler ddim: share of the posterior noise injected, 0..1 (default 0)')),
     ('--spacing', dict(choices=['uniform', 'quadratic', 'logsnr'], default=None, help='with --sample_steps: how the visited levels are spread (default uniform)')),
+    ('--avoid_clashes', dict(type=float, nargs='?', const=2.0, default=None, metavar='R', help='guided sampling: keep the centers out of the pocket\'s own atoms, R angstroms around each (default 2.0); a guided step costs several times a default one')),
+    ('--clash_weight', dict(type=float, default=None, help='with --avoid_clashes: weight of the clash energy (default 1)')),
+    ('--guide_complementarity', dict(type=float, default=None, metavar='W', help='guided sampling: pull every center to within the matching distance of a complementary receptor feature of the dataset graph, with weight W (what --metrics counts as validity)')),
+    ('--guide_scale', dict(type=float, default=None, help='with --avoid_clashes or --guide_complementarity: strength of the guidance (default 1)')),
+    ('--guide_clip', dict(type=float, default=None, help='with --avoid_clashes or --guide_complementarity: largest shift of a center per step in angstroms (default 0: no clip)')),
+    ('--guide_family', dict(choices=['wide', 'tuned'], default=None, help='with --avoid_clashes or --guide_complementarity: the kernels of a guided step (wide: every model width, the default; tuned: models of n_hidden_scalars 128 / vector_size 16)')),
     ('--pockets_per_call', dict(type=int, default=64, help='pockets whose samples are batched together (not in the reference)')),
     ('--use_ema', dict(action='store_true', help="sample from the checkpoint's EMA weights ('ema_state_dict') instead of the training weights")),
 ]
@@ -59,6 +65,25 @@ def parse_arguments(argv=None):
         raise ValueError(f'--sample_steps must be at least 1, got {a.sample_steps}')
     if a.eta is not None and (a.sampler != 'ddim' or not 0.0 <= a.eta <= 1.0):
         raise ValueError('--eta needs --sampler ddim and a value in 0..1')
+    guided = a.avoid_clashes is not None or a.guide_complementarity is not None
+    for flag in ('guide_scale', 'guide_clip', 'guide_family'):
+        if getattr(a, flag) is not None and not guided:
+            raise ValueError(f'--{flag} needs --avoid_clashes or --guide_complementarity')
+    if a.clash_weight is not None and a.avoid_clashes is None:
+        raise ValueError('--clash_weight needs --avoid_clashes')
+    for flag in ('avoid_clashes', 'clash_weight', 'guide_complementarity', 'guide_scale', 'guide_clip'):
+        v = getattr(a, flag)
+        if v is not None and not (v >= 0 and v < float('inf')):
+            raise ValueError(f'--{flag} must be finite and not negative, got {v}')
+    if guided and a.sampler == 'multistep':
+        raise ValueError('--sampler multistep takes no guidance: no --avoid_clashes or --guide_complementarity')
+    a.pocket_field = None
+    if guided:
+        a.pocket_field = dict(clash_radius=a.avoid_clashes, clash_weight=1.0 if a.clash_weight is None else a.clash_weight,
+                              comp_weight=0.0 if a.guide_complementarity is None else a.guide_complementarity)
+    a.guide_scale = 1.0 if a.guide_scale is None else a.guide_scale
+    a.guide_clip = 0.0 if a.guide_clip is None else a.guide_clip
+    a.guide_family = 'wide' if a.guide_family is None else a.guide_family
     if a.dataset_idx_as_start and (a.dataset_idx is None or a.dataset_size is None):
         raise ValueError('--dataset_idx_as_start needs both --dataset_idx and --dataset_size')
     return a
@@ -146,11 +171,18 @@ def main(argv=None):
         with torch.no_grad():
             per_pocket = model.sample(graphs, sizes, max_batch_size=args.max_batch_size, init_pharm_com=coms,
                                       visualize_trajectory=args.visualize_trajectory, sample_steps=args.sample_steps,
-                                      sampler=args.sampler, eta=args.eta, spacing=args.spacing)
+                                      sampler=args.sampler, eta=args.eta, spacing=args.spacing,
+                                      pocket_field=None if args.pocket_field is None else pfa.PocketField(**args.pocket_field),
+                                      guide_scale=args.guide_scale, guide_clip=args.guide_clip, guide_family=args.guide_family)
         seconds = (time.time() - t0) / len(chunk)
         for idx, pharms in zip(chunk, per_pocket):
             write_pocket(out_root, dataset, idx, pharms, seconds, args.visualize_trajectory)
             all_pharms += pharms
+            if args.avoid_clashes is not None and rank == 0:       # the final clash energy and clashing pairs of every sample
+                from pharmacoforge_amd.analysis import clash_energy
+                cl = [clash_energy(ph.ph_coords, ph.g.prot_x, args.avoid_clashes, args.pocket_field['clash_weight']) for ph in pharms]
+                print(f'pocket {idx}: clash energy per sample ' + ' '.join(f'{e:.3g}' for e, _ in cl)
+                      + '; clashing pairs ' + ' '.join(str(c) for _, c in cl), flush=True)
         if rank == 0:
             print(f'pockets {chunk[0]}..{chunk[-1]}: {seconds:.3f} s per pocket, '
                   f'{seconds / max(args.samples_per_pocket, 1):.4f} s per pharmacophore', flush=True)
