@@ -692,7 +692,9 @@ int pf_debug_kernel_family(pf_handle* h, int32_t layer, int32_t* rows_per_wave);
  * NOT compute -- they were computed ahead and the update + build found their graphs' regions unchanged; out[1] = "pa" edges computed
  * ahead; out[2] = 1 if the centers' encoder outputs and h_src products were left in tables (center hoist), out[3] = centers covered.
  * Also: pf_debug_kernel_family(layer = n_convs + 1) = 1 when the LAST call's ff / fp items started from those tables, (n_convs + 2) = 1
- * when it skipped regions computed ahead.  Synchronises the stream. */
+ * when it skipped regions computed ahead, (n_convs + 3) = the item maps of the LAST call's n16 launches: bit 0 conv layer 0 mapped its
+ * ff / pf / fp items by arithmetic (k_n16_edge_u), bit 1 the fused launch did (k_n16_fused_u), bit 2 its items started from edge records.
+ * Synchronises the stream. */
 int pf_debug_ahead(pf_handle* h, int64_t* out /*[4]*/, pf_stream stream);
 /* the check of the rows computed ahead (PFDYN_PA_CHECK=1 at pf_create; zeros otherwise), cumulative since the handle's first batch:
  * violations[0] = kept "pa" groups (those a conv-layer-0 launch skipped: j < min(pa_same[g], groups of g)) that the speculative

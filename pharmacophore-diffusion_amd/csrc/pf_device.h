@@ -371,6 +371,9 @@ struct FusedParams {
     pf_gcf upd_pharm; int upd_pharm_stride;          // the centers' update chain alone (store items)
     const float* htab; int htab_gstride;             // protein encoder output per element type (table 3 of the timestep's slot)
     const int* ptype;
+    const float* hcen;                               // center hoist: the centers' encoder outputs [Nf][128] (residual input of their node update), or NULL
+    // (everything above is what an item reads in front of its first matrix instruction -- n16_fused_args fetches it in one block of
+    // scalar loads: kept together at the front, on the segment's first lines)
     float* h_out; float* v_out;                      // conv layer 1's input state: written for the centers (the node + head launch reads it)
     const int* pharm_ptr; int Np, n_edge_items;      // store items: graph g's centers; items [0, n_edge_items) are edge items
     int xcd_split, nff_cap, npf_cap;                 // XCD-aware item assignment (k_n16_fused): capacities of the ff / pf regions in 16-slot groups
@@ -381,7 +384,6 @@ struct FusedParams {
     // prologue otherwise collects in two dependent round trips -- slot -> (source, destination) -> the source's in-edge descriptors,
     // element type and both coordinates -- in one
     const int4* rec;
-    const float* hcen;                               // center hoist: the centers' encoder outputs [Nf][128] (residual input of their node update), or NULL
 };
 
 // n16 tail launch (pf_n16.hip: k_n16_tail; pf_denoise_step only): ONE workgroup per graph runs the last conv layer's node

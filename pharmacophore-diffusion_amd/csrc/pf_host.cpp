@@ -366,6 +366,8 @@ struct pf_handle {
     int *d_pa_stamp = nullptr, *d_pa_same = nullptr;
     bool e0_saved = false; EdgeParams e0{}; EncodeParams ep0{}; int e0_groups = 0;
     int last_spec = 0;                      // the last dynamics call skipped "pa" regions computed ahead (pf_debug_kernel_family(n_convs + 2): 1)
+    int last_forms = 0;                     // item maps of the last dynamics call's n16 launches (pf_debug_kernel_family(n_convs + 3)): bit 0 conv layer 0 ran
+                                            // k_n16_edge_u, bit 1 the fused launch ran k_n16_fused_u, bit 2 the fused launch's items started from edge records
                                             // when the next one begins: a time-out there is reported, late but never silently
     int* d_pa_cnt = nullptr;                // [B] the kind-3 counts conv layer 0 consumed (EdgeParams::cnt_snap): the speculative items' map
     // test knobs.  PFDYN_PA_SPEC_SPLIT=k: the speculative items leave the merged launch; items w < k run in a launch of their
@@ -940,7 +942,7 @@ static int ensure_wide_pack(pf_handle* h, hipStream_t s) {
 static int run_dynamics_wide(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s, const float* t_scalar, bool train = false) {
     const pf_config& c = h->cfg;
     h->tail_done = false; h->last_tail = 0; h->last_hoist = 0;
-    h->cen_valid = false; h->last_cen = false; h->spec_valid = false; h->last_spec = 0; h->e0_saved = false;
+    h->cen_valid = false; h->last_cen = false; h->spec_valid = false; h->last_spec = 0; h->last_forms = 0; h->e0_saved = false;
     // a pocket-group claim is verified as on the specialised path; the family then computes every graph itself
     if (!train && h->share_ok && h->share_check == 0) (void)share_now(h);
     if (!train && h->share_check == 2)
@@ -1126,7 +1128,11 @@ static void edge_n16_form(DynCall& dc, int l) {
     bool uni = l == 0 && h->pol.fused_uni && !shared && e.reg == h->d_reg && e.nreg == 4 * h->B && h->B <= 64 && !e.pa_abs && !e.need &&
                uniform_regions(h, 3, stride, cap);
     for (int et = 0; et < 3 && uni; ++et) { grp[et] = (cap[et] + 15) / 16; uni = grp[et] > 0 && grp[et] < 8; }      // (three bits each)
+    // k_n16_edge_u reaches pa_skip through the preloaded address of dyn_cnt, as an int offset (pfk_n16_edge): d_pa_same and d_dyn_cnt are
+    // both carved from the workspace d_ws, so the offset is small -- a layout that breaks this takes the work-list form, here and there
+    if (uni && e.pa_skip) { const long long off = (long long)(e.pa_skip - e.dyn_cnt); uni = off != 0 && off > -0x40000000LL && off < 0x40000000LL; }
     if (uni) {
+        h->last_forms |= 1;
         for (int et = 0; et < 3; ++et) e.uni_base[et] = h->h_reg[(size_t)et * h->B];
         e.uni_s01 = stride[0] | (stride[1] << 16);
         e.uni_s2g = stride[2] | (grp[0] << 16) | (grp[1] << 19) | (grp[2] << 22) | ((h->B - 1) << 25);
@@ -1206,6 +1212,7 @@ static void edge_launch(DynCall& dc, int l) {
         if (uni) {
             fz.uni_ff_base = h->h_reg[0]; fz.uni_pf_base = h->h_reg[(size_t)h->B];
             fz.uni_strides = stride[0] | (stride[1] << 16); fz.uni_groups = ((cap[0] + 15) / 16) | (((cap[1] + 15) / 16) << 8);
+            h->last_forms |= 2 | (fz.rec ? 4 : 0);      // (k_n16_fused has no record path: its items chase their end points)
         }
         h->last_family[l] = 17;                      // pf_debug_kernel_family: 16-row items with conv layer 0's node update in front
         { ProfScope ps(h, pf_handle::K_EDGE_LAST, s); pfk_n16_fused(&e, &fz, &dc.ep, s); }
@@ -1403,7 +1410,7 @@ static int run_dynamics(pf_handle* h, float* eps_h, float* eps_x, hipStream_t s,
     h->cen_valid = false; h->last_cen = false;
     // rows computed ahead for this call's "pa" regions (the speculative items of the previous step's merged launch)
     dc.spec_have = !train && h->spec_valid && h->edges_built && t_scalar != nullptr && *t_scalar == h->spec_t && h->spec_wver == h->w_version;
-    h->spec_valid = false; h->last_spec = 0; h->e0_saved = false;
+    h->spec_valid = false; h->last_spec = 0; h->last_forms = 0; h->e0_saved = false;
     if (!train) n16_refresh(h, s);
     dc.ep = encode_params(h, t_scalar, train ? h->t_H[0] : h->d_h[0]);
     if (const int rc = dyn_prologue(dc)) return rc;
@@ -3852,6 +3859,10 @@ int pf_debug_pa_check(pf_handle* h, int64_t* out, pf_stream stream) {
 
 int pf_debug_kernel_family(pf_handle* h, int32_t layer, int32_t* rows_per_wave) {
     if (!h || !rows_per_wave) return PF_ERR_ARG;
+    if (layer == (int)h->last_family.size() + 3 && layer > 3) {  // four past: the item maps of the n16 launches (pf_handle::last_forms)
+        *rows_per_wave = h->last_forms;
+        return PF_OK;
+    }
     if (layer == (int)h->last_family.size() + 2 && layer > 2) {  // three past: 1 when the last call skipped "pa" regions whose rows had been computed ahead
         *rows_per_wave = h->last_spec;
         return PF_OK;

@@ -48,6 +48,23 @@ using namespace pfn16;
 
 namespace {
 
+// a wave-uniform value, held in a scalar register and opaque to the compiler from here on: what was loaded for it has arrived here,
+// and no later transformation looks through it
+template <class T> __device__ __forceinline__ void n16_pin(T& x) { asm volatile("" : "+s"(x)); }
+// One dword out of every 32 bytes of a launch's EdgeParams, requested with a "pa" item's first loads (n16_args_touch) and taken behind the
+// work-list scan, which waits for those loads anyway (n16_args_arrived): the fields the item reads further down -- streams, tables,
+// coordinates, one scalar load each with a wait of its own on the dependent path, on five different lines of the segment -- then
+// hit the scalar cache instead of going to memory one after the other (k_n16_edge_u 10.11 -> 9.99 us at config 2; the same in
+// front of the static items measured +0.14 us: they wait for their count at once, and with it for all of these).
+__device__ __forceinline__ int n16_args_touch(const EdgeParams& p) {
+    const int* w = reinterpret_cast<const int*>(&p);
+    int t = 0;
+#pragma unroll
+    for (unsigned i = 0; i < sizeof(EdgeParams) / 4; i += 8) t |= w[i];
+    return t;
+}
+__device__ __forceinline__ void n16_args_arrived(const int t) { asm volatile("" : : "s"(t)); }
+
 // grid: one workgroup per 16-slot group (compact work list: the w-th non-empty group; tile lists: two groups per tile)
 // The leading scalar arguments repeat the fields of p that the work-list scan needs: they are preloaded into scalar
 // registers with the wave (-mllvm -amdgpu-kernarg-preload-count, Makefile), so the scan's loads leave without waiting for
@@ -161,10 +178,13 @@ __global__ __launch_bounds__(256) void k_n16_edge(const int* __restrict__ a_dyn_
 // wave starts (groups beyond a region's count leave at once); the "pa" items behind them keep the work-list scan, over B regions
 // instead of 4 B.  Same item order as k_n16_edge's compact list: ff, pf, fp, pa.
 //   a_s01 = stride_ff | stride_pf << 16; a_s2g = stride_fp | groups_ff << 16 | groups_pf << 19 | groups_fp << 22 | (graphs - 1) << 25
-//   (the first eight arguments are preloaded: everything the static items' first loads need; a_reg, for the "pa" scan, is not)
+//   a_pa_off = EdgeParams::pa_skip - dyn_cnt in ints (both live in the handle's workspace), or 0: no rows were computed ahead
+//   (all ten leading arguments are preloaded -- 14 of the 16 user scalar registers with the segment's address --: everything the static
+//   items' first loads and the "pa" scan's one batch of loads need)
+//   (the four addresses first: an address behind an odd number of ints is padded to eight bytes, and the padding takes a register)
 __global__ __launch_bounds__(256) void k_n16_edge_u(const int* __restrict__ a_dyn_cnt, const int* __restrict__ a_esrc,
-                                                    const int* __restrict__ a_edst, const int a_b0, const int a_b1, const int a_b2,
-                                                    const int a_s01, const int a_s2g, const int* __restrict__ a_reg,
+                                                    const int* __restrict__ a_edst, const int* __restrict__ a_reg, const int a_b0,
+                                                    const int a_b1, const int a_b2, const int a_s01, const int a_s2g, const int a_pa_off,
                                                     const EdgeParams p, const EncodeParams ep) {
     __shared__ N16Lds lds;
     const int lane = threadIdx.x & 63;
@@ -180,7 +200,9 @@ __global__ __launch_bounds__(256) void k_n16_edge_u(const int* __restrict__ a_dy
     const int gff = (a_s2g >> 16) & 7, gpf = (a_s2g >> 19) & 7, gfp = (a_s2g >> 22) & 7, a_B = (int)((unsigned)a_s2g >> 25) + 1;
     const int nff = a_B * gff, npf = a_B * gpf, nfp = a_B * gfp;
     int w = (int)blockIdx.x;
-    if (p.cnt_snap && w == 0 && threadIdx.x < 64 && lane < a_B) p.cnt_snap[lane] = a_dyn_cnt[3 * a_B + lane];      // (EdgeParams::cnt_snap)
+    // (EdgeParams::cnt_snap; the workgroup test first: the pointer is not among the preloaded arguments, and tested first its load
+    // and the wait for it stood in front of every item of the launch)
+    if (w == 0 && threadIdx.x < 64 && lane < a_B && p.cnt_snap) p.cnt_snap[lane] = a_dyn_cnt[3 * a_B + lane];
 #ifdef EDGE_U_SWAP                                        // (diagnostic: ff and fp items trade places in the grid; needs nff == nfp)
     if (w < nff) w += nff + npf; else if (w >= nff + npf && w < nff + npf + nfp) w -= nff + npf;
 #endif
@@ -206,21 +228,31 @@ __global__ __launch_bounds__(256) void k_n16_edge_u(const int* __restrict__ a_dy
     }
     // ---- "pa" items: the (w - static items)-th non-empty 16-slot group of the B regions of kind 3 (one scan pass: B <= 64)
     w -= nff + npf + nfp;
-    const int r = 3 * a_B + min(lane, a_B - 1);
-    const int c = lane < a_B ? a_dyn_cnt[r] : 0;
-    // the leading groups of this graph's region whose rows were computed ahead by the previous step's last launch and still apply
-    // (BuildParams::pa_same: all of them when the graph's active set did not change, those in front of the first change otherwise)
-    const int keep = p.pa_skip ? min(p.pa_skip[min(lane, a_B - 1)], (c + 15) >> 4) : 0;
-    const int rs = a_reg[r];
+    // one batch of loads through preloaded addresses, requested the moment the wave starts: the regions' counts and starts, and the
+    // leading groups of each graph's region whose rows were computed ahead by the previous step's last launch and still apply
+    // (BuildParams::pa_same: all of them when the graph's active set did not change, those in front of the first change otherwise;
+    // none computed ahead: the count is read a second time and masked away -- the mask opaque to the compiler, which otherwise makes
+    // the load conditional and puts a branch, with a wait for the counts, in front of it)
+    const int gl = min(lane, a_B - 1);
+    const int r = 3 * a_B + gl;
+    int has_keep = __builtin_amdgcn_readfirstlane(a_pa_off ? -1 : 0);
+    n16_pin(has_keep);
+    const int c_raw = a_dyn_cnt[r], keep_raw = a_dyn_cnt[a_pa_off ? a_pa_off + gl : r], rs = a_reg[r];
+    const int touched = n16_args_touch(p);
+    const int c = lane < a_B ? c_raw : 0;
+    const int keep = min(keep_raw, (c + 15) >> 4) & has_keep;
     const int ng = ((c + 15) >> 4) - keep;
     int incl = ng;
     incl += dpp_i<0x111>(incl); incl += dpp_i<0x112>(incl); incl += dpp_i<0x114>(incl); incl += dpp_i<0x118>(incl);
     incl += dpp_ir<0x142, 0xa>(incl); incl += dpp_ir<0x143, 0xc>(incl);
     const unsigned long long m = __ballot(incl > w);
-    if (!m) return;                                      // workgroup-uniform: beyond the last group
-    const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
+    // (the region's start is picked in FRONT of the exit: used behind it only, the compiler moves the load of the starts behind the
+    // branch -- a round trip of its own behind the scan)
+    const int l = __builtin_amdgcn_readfirstlane(max(__ffsll((long long)m) - 1, 0));
     const int first = __builtin_amdgcn_readlane(incl - ng, l);
     const int cnt = __builtin_amdgcn_readlane(c, l), start = __builtin_amdgcn_readlane(rs, l);
+    n16_args_arrived(touched);
+    if (!m) return;                                      // workgroup-uniform: beyond the last group
     const int loc = (w - first + __builtin_amdgcn_readlane(keep, l)) << 4;
     const int e0 = start + loc;
     const int nv = __builtin_amdgcn_readfirstlane(min(16, cnt - loc));
@@ -402,62 +434,95 @@ __device__ __forceinline__ void n16_quarters_to_rows(const f32x4 (&Q)[2], float 
     }
 }
 
-// descriptors of a node's in-edges in conv layer 0 (slot 0: ff | fp; second segment: pf of a center, the pp / "pa" edges of an atom)
-__device__ __forceinline__ void n16_node_desc_l0(const FusedParams& f, const int node, const int nt, NodeDesc& nd) {
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-        const int slot = sl == 0 ? 0 : (nt == 0 ? f.pp_slot : 1);
-        nd.st[sl] = f.in_start[slot * f.N + node];
-        nd.cn[sl] = f.in_cnt[slot * f.N + node];
-        nd.gm[sl] = (sl == 0 ? f.grp : (nt == 0 ? f.grp_pa : f.grp)) - 1;
+// What an item of the fused launch reads of the kernel-argument segment in front of its first matrix instruction, selected for the
+// item's etype / node type.  n16_fused_args requests all of it in ONE block of scalar loads -- at wave start, next to the item's first
+// vector loads -- and pins the values in scalar registers: left at their uses, the compiler fetched each field where it was read, and
+// every such load stood with a wait of its own on the item's dependent path (norm_mode, zero_row, hcen, the LayerNorm pointers ...:
+// six waits between "item known" and the first v_mfma).  The per-type entries are picked by their offset in the segment (the type is
+// known from the item's number alone), not by a load that waits for another.
+struct FusedArgs {
+    pf_gcf chain; int chain_stride;                       // [update chain of the source type][message chain] (store items: the update chain)
+    pf_gcf ln1_w, ln1_b, ln2_w, ln2_b;
+    const float* msg_s; const float* msg_v; int zero_row, gm0, gm1;
+    const int* gid; const float* gnorm; int B, norm_mode; float norm_value;
+    const float* htab; int htab_gstride; const float* hcen; int n_upd, Np;
+    // CHASE only: what an item without an edge record collects its sources' descriptors, types and coordinates from
+    const int* in_start; const int* in_cnt; int N, slot1; const int* ptype; const float4* xn;
+};
+template <bool CHASE>
+__device__ __forceinline__ FusedArgs n16_fused_args(const EdgeParams& p, const FusedParams& f, const EncodeParams& ep, const int et, const bool store) {
+    const int nt = (store || et == ET_FF) ? 1 : 0;       // (workgroup-uniform)
+    FusedArgs k{};
+    k.chain = store ? f.upd_pharm : f.chain[et]; k.chain_stride = store ? f.upd_pharm_stride : f.chain_stride[et];
+    k.ln1_w = f.ln1_w[nt]; k.ln1_b = f.ln1_b[nt]; k.ln2_w = f.ln2_w[nt]; k.ln2_b = f.ln2_b[nt];
+    k.msg_s = f.msg_s; k.msg_v = f.msg_v; k.zero_row = f.zero_row; k.gm0 = f.grp; k.gm1 = nt == 0 ? f.grp_pa : f.grp;
+    k.gid = f.gid; k.gnorm = f.gnorm; k.B = f.B; k.norm_mode = f.norm_mode;
+    int nval = __float_as_int(f.norm_value);
+    k.htab = f.htab; k.htab_gstride = f.htab_gstride; k.hcen = f.hcen; k.n_upd = f.n_upd; k.Np = ep.Np;
+    if constexpr (CHASE) {
+        k.in_start = f.in_start; k.in_cnt = f.in_cnt; k.N = f.N; k.slot1 = nt == 0 ? f.pp_slot : 1; k.ptype = f.ptype; k.xn = p.xn;
+        n16_pin(k.in_start); n16_pin(k.in_cnt); n16_pin(k.N); n16_pin(k.slot1); n16_pin(k.ptype); n16_pin(k.xn);
     }
+    n16_pin(k.chain); n16_pin(k.chain_stride); n16_pin(k.ln1_w); n16_pin(k.ln1_b); n16_pin(k.ln2_w); n16_pin(k.ln2_b);
+    n16_pin(k.msg_s); n16_pin(k.msg_v); n16_pin(k.zero_row); n16_pin(k.gm0); n16_pin(k.gm1);
+    n16_pin(k.gid); n16_pin(k.gnorm); n16_pin(k.B); n16_pin(k.norm_mode); n16_pin(nval);
+    n16_pin(k.htab); n16_pin(k.htab_gstride); n16_pin(k.hcen); n16_pin(k.n_upd); n16_pin(k.Np);
+    k.norm_value = __int_as_float(nval);
+    k.gm0 -= 1; k.gm1 -= 1;
+    return k;
+}
+
+// descriptors of a node's in-edges in conv layer 0 (slot 0: ff | fp; second segment: pf of a center, the pp / "pa" edges of an atom)
+__device__ __forceinline__ void n16_node_desc_l0(const FusedArgs& k, const int node, NodeDesc& nd) {
+    nd.st[0] = k.in_start[node]; nd.cn[0] = k.in_cnt[node]; nd.gm[0] = k.gm0;
+    nd.st[1] = k.in_start[k.slot1 * k.N + node]; nd.cn[1] = k.in_cnt[k.slot1 * k.N + node]; nd.gm[1] = k.gm1;
 }
 // (nd: n16_node_desc_l0 of the node; pty: f.ptype[node] of an atom -- both requested by the caller together with whatever
 // else it loads at that level, so that a workgroup's prologue is four dependent round trips: work list, edge slots, descriptors
 // + coordinates + types, rows)
-__device__ __forceinline__ void n16_node_update_l0(const FusedParams& f, const EncodeParams& ep, N16Ring& ring, const int node, const int nt,
+__device__ __forceinline__ void n16_node_update_l0(const FusedArgs& k, const EncodeParams& ep, N16Ring& ring, const int node, const int nt,
                                                    const NodeDesc& nd, const int pty, float (&XS)[32], float (&VB)[4], N16Lds* lds,
                                                    const int lane, const int wq, int& sk) {
     const int g = lane >> 4;
     // one batch of loads: the partial rows (this wave's quarter) and, for an atom, its quarter of the residual input -- the
     // encoder output of its element type, a row of the timestep's type table
-    const N16LnPre lnq = n16_ln_request(f.ln1_w[nt], f.ln1_b[nt], f.ln2_w[nt], f.ln2_b[nt], lane, wq);
+    const N16LnPre lnq = n16_ln_request(k.ln1_w, k.ln1_b, k.ln2_w, k.ln2_b, lane, wq);
     RowQ rq;
-    n16_rows_load(f.msg_s, f.msg_v, f.zero_row, nd, rq, lane, wq);
+    n16_rows_load(k.msg_s, k.msg_v, k.zero_row, nd, rq, lane, wq);
     f32x4 Hq[2];
     Hq[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; Hq[1] = Hq[0];
     if (nt == 0) {
-        pf_gcf hp = (pf_gcf)f.htab + (f.htab_gstride ? (size_t)f.gid[node] * f.htab_gstride : 0) + (size_t)pty * PF_S + 32 * wq + 4 * g;
+        pf_gcf hp = (pf_gcf)k.htab + (k.htab_gstride ? (size_t)k.gid[node] * k.htab_gstride : 0) + (size_t)pty * PF_S + 32 * wq + 4 * g;
         Hq[0] = *reinterpret_cast<const f32x4 PF_AS1*>(hp);
         Hq[1] = *reinterpret_cast<const f32x4 PF_AS1*>(hp + 16);
     }
     float inv_norm = 1.0f;
-    if (f.norm_mode == 1) inv_norm = 1.0f / f.norm_value;
-    else if (f.norm_mode == 2) inv_norm = 1.0f / f.gnorm[nt * f.B + f.gid[node]];
+    if (k.norm_mode == 1) inv_norm = 1.0f / k.norm_value;
+    else if (k.norm_mode == 2) inv_norm = 1.0f / k.gnorm[nt * k.B + k.gid[node]];
     // a center's residual input: a row of the center hoist's table (this wave's quarter, with the row loads), or encoded on the fly
     // (its own exchange through lds->s, closed by a barrier) under the row loads
     float H[32];
-    const bool enc_here = nt != 0 && f.hcen == nullptr;                 // workgroup-uniform
-    if (nt != 0 && f.hcen != nullptr) {
-        pf_gcf hp = (pf_gcf)f.hcen + (size_t)(node - ep.Np) * PF_S + 32 * wq + 4 * g;
+    const bool enc_here = nt != 0 && k.hcen == nullptr;                 // workgroup-uniform
+    if (nt != 0 && k.hcen != nullptr) {
+        pf_gcf hp = (pf_gcf)k.hcen + (size_t)(node - k.Np) * PF_S + 32 * wq + 4 * g;
         Hq[0] = *reinterpret_cast<const f32x4 PF_AS1*>(hp);
         Hq[1] = *reinterpret_cast<const f32x4 PF_AS1*>(hp + 16);
     }
     if (enc_here) {
-        const float tt = ep.t ? ((pf_gcf)ep.t)[f.gid[node]] : ep.t_scalar;
+        const float tt = ep.t ? ((pf_gcf)ep.t)[k.gid[node]] : ep.t_scalar;
         n16_encode_pharm(ep, (pf_gcf)ep.pharm_h + (size_t)(node - ep.Np) * ep.pharm_nf, tt, H, lds, lane, wq);
     }
     f32x4 Q[2];
-    n16_rows_sum(f.msg_s, f.msg_v, f.zero_row, f.norm_mode, nd, rq, Q, VB, lds, lane, wq);
+    n16_rows_sum(k.msg_s, k.msg_v, k.zero_row, k.norm_mode, nd, rq, Q, VB, lds, lane, wq);
     N16_STAMP(sk, lane, wq);                              // partial rows summed
-    N16_CUT_AT(FUSED_CUT, 2, Q[0][0] + VB[0] + Hq[0][0], f.h_out);
+    N16_CUT_AT(FUSED_CUT, 2, Q[0][0] + VB[0] + Hq[0][0], const_cast<float*>(k.msg_s));
 #pragma unroll
     for (int r = 0; r < 4; ++r) { Q[0][r] = fmaf(Q[0][r], inv_norm, Hq[0][r]); Q[1][r] = fmaf(Q[1][r], inv_norm, Hq[1][r]); }
     n16_ln_stage(lnq, lds, lane, wq);                    // (in front of the exchange's barrier)
     n16_quarters_to_rows(Q, XS, lds, lane, wq);          // (the first LayerNorm's barrier closes the reads)
     if (enc_here) {
 #pragma unroll
-        for (int k = 0; k < 32; ++k) XS[k] += H[k];
+        for (int i = 0; i < 32; ++i) XS[i] += H[i];
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) VB[r] = wq < 3 ? VB[r] * inv_norm : 0.f;
@@ -465,35 +530,39 @@ __device__ __forceinline__ void n16_node_update_l0(const FusedParams& f, const E
     N16_STAMP(sk, lane, wq);                              // residual input + first LayerNorm
     float Xr[32], Vr[4];
 #pragma unroll
-    for (int k = 0; k < 32; ++k) Xr[k] = XS[k];
+    for (int i = 0; i < 32; ++i) Xr[i] = XS[i];
 #pragma unroll
     for (int r = 0; r < 4; ++r) Vr[r] = VB[r];
     N16In none{};
     f32x4 S[2];
     S[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; S[1] = S[0];
     N16P XP;
-    n16_gen_run<0>(f.n_upd, ring, XS, XP, VB, none, S, lds, lane, wq, sk);
+    n16_gen_run<0>(k.n_upd, ring, XS, XP, VB, none, S, lds, lane, wq, sk);
     n16_gate_flush(VB, lds, lane, wq);
 #pragma unroll
-    for (int k = 0; k < 32; ++k) XS[k] += Xr[k];
+    for (int i = 0; i < 32; ++i) XS[i] += Xr[i];
 #pragma unroll
     for (int r = 0; r < 4; ++r) VB[r] += Vr[r];
     n16_layernorm<true>(nullptr, nullptr, XS, VB, lds, lane, wq, 1);
 }
 
 // ---- store item of the fused launch: the centers [16 part, 16 part + 16) of graph gq
-__device__ __forceinline__ void n16_fused_store_item(const FusedParams& f, const EncodeParams& ep, N16Lds* lds, const int gq, const int part,
-                                                     float (&XS)[32], float (&VB)[4], const int lane, const int wq, int& sk) {
+__device__ __forceinline__ void n16_fused_store_item(const EdgeParams& p, const FusedParams& f, const EncodeParams& ep, N16Lds* lds,
+                                                     const int gq, const int part, float (&XS)[32], float (&VB)[4], const int lane,
+                                                     const int wq, int& sk) {
     const int g = lane >> 4, j = lane & 15;
-    const int f0 = f.pharm_ptr[gq], nf = f.pharm_ptr[gq + 1] - f0;
+    const int* pptr = f.pharm_ptr; int Np = f.Np;
+    const FusedArgs k = n16_fused_args<true>(p, f, ep, (int)ET_FF, true);      // (the same block of scalar loads as pharm_ptr and Np)
+    n16_pin(pptr); n16_pin(Np);
+    const int f0 = pptr[gq], nf = pptr[gq + 1] - f0;
     const int nv = __builtin_amdgcn_readfirstlane(min(16, nf - 16 * part));
     if (nv <= 0) return;                                 // workgroup-uniform
-    const int node = f.Np + f0 + 16 * part + min(j, nv - 1);
+    const int node = Np + f0 + 16 * part + min(j, nv - 1);
     N16Ring ring;
-    ring_start(ring, f.upd_pharm + (size_t)wq * f.upd_pharm_stride, lane);
+    ring_start(ring, k.chain + (size_t)wq * k.chain_stride, lane);
     NodeDesc nd;
-    n16_node_desc_l0(f, node, 1, nd);
-    n16_node_update_l0(f, ep, ring, node, 1, nd, 0, XS, VB, lds, lane, wq, sk);
+    n16_node_desc_l0(k, node, nd);
+    n16_node_update_l0(k, ep, ring, node, 1, nd, 0, XS, VB, lds, lane, wq, sk);
     if (j < nv && wq == 0) {
         float* hp = f.h_out + (size_t)node * PF_S + 4 * g;
 #pragma unroll
@@ -507,11 +576,11 @@ __device__ __forceinline__ void n16_fused_store_item(const FusedParams& f, const
 }
 // ---- edge item of the fused launch: row j = edge slot e (source src, destination dst; rows beyond nv shadow row nv - 1)
 // rec: the row's edge record (FusedParams::rec: three 16-byte words) or NULL
-__device__ __forceinline__ void n16_fused_edge_item(const EdgeParams& p, const FusedParams& f, const EncodeParams& ep, N16Lds* lds, const int e,
-                                                    const int src, const int dst, const int nv, const int et, float (&XS)[32],
+// k: n16_fused_args of the item's etype (with the CHASE fields when rec is NULL); ring: started on k.chain by the caller, with its
+// first loads
+__device__ __forceinline__ void n16_fused_edge_item(const EdgeParams& p, const FusedArgs& k, const EncodeParams& ep, N16Ring& ring, N16Lds* lds,
+                                                    const int e, const int src, const int dst, const int nv, const int et, float (&XS)[32],
                                                     float (&VB)[4], const int lane, const int wq, int& sk, const int4* rec = nullptr) {
-    N16Ring ring;
-    ring_start(ring, f.chain[et] + (size_t)wq * f.chain_stride[et], lane);
     N16Rows rw;
     rw.e = e;
     rw.dst = dst;
@@ -522,16 +591,16 @@ __device__ __forceinline__ void n16_fused_edge_item(const EdgeParams& p, const F
         rw.xs = make_float4(__builtin_bit_cast(float, rec[0].x), __builtin_bit_cast(float, rec[0].y), __builtin_bit_cast(float, rec[0].z), 0.f);
         rw.xd = make_float4(__builtin_bit_cast(float, rec[1].x), __builtin_bit_cast(float, rec[1].y), __builtin_bit_cast(float, rec[1].z), 0.f);
         nd.st[0] = rec[2].x; nd.cn[0] = rec[2].y; nd.st[1] = rec[2].z; nd.cn[1] = rec[2].w;
-        nd.gm[0] = f.grp - 1; nd.gm[1] = (nt == 0 ? f.grp_pa : f.grp) - 1;
+        nd.gm[0] = k.gm0; nd.gm[1] = k.gm1;
         pty = (int)((unsigned)rec[0].w >> 24);
     } else {
         // one level of loads: coordinates, the source's in-edge descriptors, its element type
-        rw.xs = p.xn[src]; rw.xd = p.xn[dst];
-        n16_node_desc_l0(f, src, nt, nd);
-        pty = nt == 0 ? f.ptype[src] : 0;
+        rw.xs = k.xn[src]; rw.xd = k.xn[dst];
+        n16_node_desc_l0(k, src, nd);
+        pty = nt == 0 ? k.ptype[src] : 0;
     }
-    n16_node_update_l0(f, ep, ring, src, nt, nd, pty, XS, VB, lds, lane, wq, sk);
-    N16_CUT_AT(FUSED_CUT, 3, XS[0] + VB[0] + rw.xs.x + rw.xd.x, f.h_out);
+    n16_node_update_l0(k, ep, ring, src, nt, nd, pty, XS, VB, lds, lane, wq, sk);
+    N16_CUT_AT(FUSED_CUT, 3, XS[0] + VB[0] + rw.xs.x + rw.xd.x, const_cast<float*>(k.msg_s));
     f32x4 S[2];
     S[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; S[1] = S[0];
     n16_edge_chain<N16_M0F>(p, ring, rw, XS, VB, S, lds, nv, lane, wq, sk);
@@ -550,7 +619,7 @@ __global__ __launch_bounds__(256) void k_n16_fused(const int* __restrict__ a_dyn
     int sk = 2 << 8;
     N16_STAMP(sk, lane, wq);                              // kernel entry
     float XS[32], VB[4];
-    auto store_item = [&](const int gq, const int part) { n16_fused_store_item(f, ep, &lds, gq, part, XS, VB, lane, wq, sk); };
+    auto store_item = [&](const int gq, const int part) { n16_fused_store_item(p, f, ep, &lds, gq, part, XS, VB, lane, wq, sk); };
     int e0, nv, et;
     if (f.xcd_split) {
         // XCD-aware assignment (workgroup b runs on XCD b % 8): ff edge items and the store items -- the centers' side: they stream
@@ -637,7 +706,11 @@ __global__ __launch_bounds__(256) void k_n16_fused(const int* __restrict__ a_dyn
     N16_STAMP(sk, lane, wq);                              // item known
     N16_CUT_AT(FUSED_CUT, 1, (float)(e0 + nv), f.h_out);
     const int e = e0 + min(j, nv - 1);
-    n16_fused_edge_item(p, f, ep, &lds, e, p.esrc[e], p.edst[e], nv, et, XS, VB, lane, wq, sk);
+    const int src = p.esrc[e], dst = p.edst[e];
+    const FusedArgs k = n16_fused_args<true>(p, f, ep, et, false);      // (under the end points' round trip)
+    N16Ring ring;
+    ring_start(ring, k.chain + (size_t)wq * k.chain_stride, lane);
+    n16_fused_edge_item(p, k, ep, ring, &lds, e, src, dst, nv, et, XS, VB, lane, wq, sk);
 }
 
 // The same launch when every graph of the batch has regions of one capacity (all graphs with the same number of centers: the
@@ -648,10 +721,11 @@ __global__ __launch_bounds__(256) void k_n16_fused(const int* __restrict__ a_dyn
 // Groups beyond a region's count leave at once (capacity tiling).  XCD assignment as in k_n16_fused's xcd_split form.
 //   a_strides = stride_ff | stride_pf << 16 (slots between consecutive graphs' regions);
 //   a_groups  = groups_ff | groups_pf << 8 | B << 16
+//   a_rec     = FusedParams::rec (the eighth preloaded argument: 14 of the 16 user scalar registers with the segment's address)
 __global__ __launch_bounds__(256) void k_n16_fused_u(const int* __restrict__ a_dyn_cnt, const int* __restrict__ a_esrc,
                                                      const int* __restrict__ a_edst, const int a_ff_base, const int a_pf_base,
-                                                     const int a_strides, const int a_groups, const EdgeParams p,
-                                                     const FusedParams f, const EncodeParams ep) {
+                                                     const int a_strides, const int a_groups, const int4* __restrict__ a_rec,
+                                                     const EdgeParams p, const FusedParams f, const EncodeParams ep) {
     __shared__ N16Lds lds;
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -670,7 +744,7 @@ __global__ __launch_bounds__(256) void k_n16_fused_u(const int* __restrict__ a_d
     if (x < 4) {
         const int idx = 4 * kq + x;
         if (idx >= a_B * nffg) {
-            if (idx - a_B * nffg < a_B) n16_fused_store_item(f, ep, &lds, idx - a_B * nffg, 0, XS, VB, lane, wq, sk);
+            if (idx - a_B * nffg < a_B) n16_fused_store_item(p, f, ep, &lds, idx - a_B * nffg, 0, XS, VB, lane, wq, sk);
             return;
         }
         const int g = idx / nffg;
@@ -683,33 +757,58 @@ __global__ __launch_bounds__(256) void k_n16_fused_u(const int* __restrict__ a_d
         k = w - g * npfg;
         et = ET_PF; cidx = a_B + g; e0 = a_pf_base + g * (int)((unsigned)a_strides >> 16) + 16 * k;
     }
-    // one level: the region's count and the 16 slots of the group (inside the region's 32-aligned capacity whatever the count;
-    // slots beyond the count hold stale ids, which are never dereferenced: the rows beyond nv shadow row nv - 1)
-    const int cnt = a_dyn_cnt[cidx];
-    if (f.rec) {                                         // (kernel-uniform) the slots' edge records instead of their end points: one level less
-        const int4* rp = f.rec + (size_t)3 * (e0 + j);
+    // one level, all of it addressed from preloaded arguments and requested before the first wait: the region's count and the 16 slots
+    // of the group -- their records or their end points.  The slots lie inside the region's 32-ALIGNED capacity whatever the count:
+    // groups = ceil(capacity / 16), so 16 * groups can pass the capacity itself (30 -> 32) but not its round-up to 32, and
+    // pf_bind.cpp starts every region on a multiple of 32 slots -- the loads of a whole group beyond the count stay inside the
+    // arrays (at worst in the padding in front of the next region); such slots hold stale records / ids, which are never
+    // dereferenced: the rows beyond nv shadow row nv - 1.
+    if (a_rec) {                                         // (kernel-uniform) the slots' edge records instead of their end points: one level less
+        // The count gates only the early exit and the shadowing.  Here it comes through the vector memory path like the records: a
+        // scalar load would hold the wait for the kernel arguments below until it is back.  The weights' first quads leave under all of it.
+        const int cnt = __builtin_amdgcn_readfirstlane((int)__builtin_amdgcn_raw_buffer_load_b32(
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(a_dyn_cnt), 0, 0x7fffffff, 0x00020000), 4 * cidx, 0, 0));
+        const int4* rp = a_rec + (size_t)3 * (e0 + j);
         int4 r[3] = {rp[0], rp[1], rp[2]};
+        const FusedArgs ka = n16_fused_args<false>(p, f, ep, et, false);
+        N16Ring ring;
+        ring_start(ring, ka.chain + (size_t)wq * ka.chain_stride, lane);
         const int nv = __builtin_amdgcn_readfirstlane(min(16, cnt - 16 * k));
-        if (nv <= 0) return;                             // workgroup-uniform
-        N16_STAMP(sk, lane, wq);                          // item known
-        const int jj = min(j, nv - 1);
+        const int jj = min(j, max(nv, 1) - 1);
         const int from = 4 * ((lane & 48) | jj);         // (rows beyond nv shadow row nv - 1: its record, through the LDS crossbar)
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
             r[u].x = __builtin_amdgcn_ds_bpermute(from, r[u].x); r[u].y = __builtin_amdgcn_ds_bpermute(from, r[u].y);
             r[u].z = __builtin_amdgcn_ds_bpermute(from, r[u].z); r[u].w = __builtin_amdgcn_ds_bpermute(from, r[u].w);
         }
-        n16_fused_edge_item(p, f, ep, &lds, e0 + jj, r[0].w & 0xffffff, r[1].w, nv, et, XS, VB, lane, wq, sk, r);
+        // The early exit stands BEHIND the shadowing, and names the weights' quads in a store that never executes (counts are not
+        // negative): loads whose values are used on one side of a branch only are moved behind it by the compiler -- the records
+        // behind the wait for the count, the quads behind the records' arrival.  A group beyond the count leaves one round trip later,
+        // off every item's path.
+        if (nv <= 0) {                                   // workgroup-uniform
+            if (cnt < -0x40000000) {
+                float keep = 0.f;
+                static_for<0, N16_D>([&](auto I) { keep += ring.q[decltype(I)::value][0]; });
+                *p.msg_s = keep;
+            }
+            return;
+        }
+        N16_STAMP(sk, lane, wq);                          // item known
+        n16_fused_edge_item(p, ka, ep, ring, &lds, e0 + jj, r[0].w & 0xffffff, r[1].w, nv, et, XS, VB, lane, wq, sk, r);
         return;
     }
+    const int cnt = a_dyn_cnt[cidx];
     const int src_raw = a_esrc[e0 + j], dst_raw = a_edst[e0 + j];
     const int nv = __builtin_amdgcn_readfirstlane(min(16, cnt - 16 * k));
     if (nv <= 0) return;                                 // workgroup-uniform
     N16_STAMP(sk, lane, wq);                              // item known
+    const FusedArgs ka = n16_fused_args<true>(p, f, ep, et, false);
+    N16Ring ring;
+    ring_start(ring, ka.chain + (size_t)wq * ka.chain_stride, lane);
     const int jj = min(j, nv - 1);
     const int from = 4 * ((lane & 48) | jj);
     const int src = __builtin_amdgcn_ds_bpermute(from, src_raw), dst = __builtin_amdgcn_ds_bpermute(from, dst_raw);
-    n16_fused_edge_item(p, f, ep, &lds, e0 + jj, src, dst, nv, et, XS, VB, lane, wq, sk);
+    n16_fused_edge_item(p, ka, ep, ring, &lds, e0 + jj, src, dst, nv, et, XS, VB, lane, wq, sk);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -931,11 +1030,14 @@ void pfk_n16_edge(const EdgeParams* p, const EncodeParams* enc, int layer0, hipS
     const int grid = p->nreg > 0 ? p->ngroups_sel : p->ntiles * 2;
     if (grid <= 0) return;
     const EncodeParams noenc{};
-    if (layer0 && p->uni_s2g != 0) {                     // ff / pf / fp regions at fixed strides: arithmetic tiling (k_n16_edge_u)
+    // (k_n16_edge_u reaches pa_skip through dyn_cnt's preloaded address: both live in the handle's workspace; anything else takes the work-list form)
+    const long long pa_off = p->pa_skip ? (long long)(p->pa_skip - p->dyn_cnt) : 0;
+    const bool pa_off_ok = !p->pa_skip || (pa_off != 0 && pa_off > -0x40000000LL && pa_off < 0x40000000LL);
+    if (layer0 && p->uni_s2g != 0 && pa_off_ok) {        // ff / pf / fp regions at fixed strides: arithmetic tiling (k_n16_edge_u)
         const int B = p->regB;
         const int nstat = B * (((p->uni_s2g >> 16) & 7) + ((p->uni_s2g >> 19) & 7) + ((p->uni_s2g >> 22) & 7));
-        hipLaunchKernelGGL(k_n16_edge_u, dim3(nstat + p->uni_pa_groups), dim3(256), 0, s, p->dyn_cnt, p->esrc, p->edst, p->uni_base[0],
-                           p->uni_base[1], p->uni_base[2], p->uni_s01, p->uni_s2g, p->reg, *p, *enc);
+        hipLaunchKernelGGL(k_n16_edge_u, dim3(nstat + p->uni_pa_groups), dim3(256), 0, s, p->dyn_cnt, p->esrc, p->edst, p->reg, p->uni_base[0],
+                           p->uni_base[1], p->uni_base[2], p->uni_s01, p->uni_s2g, (int)pa_off, *p, *enc);
         return;
     }
     if (layer0) hipLaunchKernelGGL((k_n16_edge<true>), dim3(grid), dim3(256), 0, s, p->dyn_cnt, p->reg, p->nreg, p->regB, p->pa_abs, *p, *enc);
@@ -958,7 +1060,7 @@ void pfk_n16_fused(const EdgeParams* p, const FusedParams* f, const EncodeParams
         const int grid_u = 8 * std::max((f->B * nffg + f->B + 3) / 4, (f->B * npfg + 3) / 4);
         if (grid_u > 0)
             hipLaunchKernelGGL(k_n16_fused_u, dim3(grid_u), dim3(256), 0, s, p->dyn_cnt, p->esrc, p->edst, f->uni_ff_base, f->uni_pf_base,
-                               f->uni_strides, f->uni_groups | (f->B << 16), *p, *f, *enc);
+                               f->uni_strides, f->uni_groups | (f->B << 16), f->rec, *p, *f, *enc);
         return;
     }
     int grid = f->n_edge_items + f->B * (PF_MAXF / 16);
