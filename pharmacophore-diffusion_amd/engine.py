@@ -1,5 +1,6 @@
 """PfEngine: one libpfdyn handle per (process, GPU).  Marshals torch tensors (device memory owned
 by PyTorch) and the current torch HIP stream into the C ABI of include/pfdyn.h."""
+import contextlib
 import ctypes
 from typing import Dict, Optional
 
@@ -429,6 +430,23 @@ class PfEngine:
         if self.train_family() != before[0]:
             self.set_train_family(before[0])
 
+    @contextlib.contextmanager
+    def _armed(self, guide_family, seed, field, feat_norm_constant, restore=True):
+        """What the begin of a run consumes, armed in one order for sample and sample_begin: the training family of a guided run
+        (guide_family None: an unguided run, nothing is selected; 'tuned' takes its input-gradient switch along), then the seed
+        (seed_next), then the pocket field (field_next).  On exit, also on error, family and switch are what they were;
+        restore=False leaves them selected (sample_begin: the run's steps need them, its caller restores)."""
+        before = self._arm_guide_family(guide_family) if guide_family is not None else None
+        try:
+            if seed is not None:
+                self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
+            if field is not None:
+                self.field_next(**field)
+            yield
+        finally:
+            if restore and before is not None:
+                self._restore_guide_family(before)
+
     def mask_columns(self):
         """columns of a dropout-mask row: n_hidden_scalars + vector_size on the wide training leg, 144 on the tuned one"""
         return self.cfg.n_hidden_scalars + self.cfg.vector_size if self.train_family() == "wide" else 144
@@ -643,13 +661,7 @@ class PfEngine:
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         self._keep = [nz, com]
         pin, restr, _alive = self._run_inputs(pins, restraints)
-        if guide_family is not None:
-            self._arm_guide_family(guide_family)
-        if seed is not None:
-            self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
-        if field is not None:
-            self.field_next(**field)
-        with torch.cuda.device(self.device):
+        with self._armed(guide_family, seed, field, feat_norm_constant, restore=False), torch.cuda.device(self.device):
             if restraints is not None:
                 self._ck(self.lib.pf_sample_begin_guided(self._h, _dptr(com), _dptr(nz), *pin, float(feat_norm_constant), *restr,
                                                          float(guide_scale), float(guide_clip), _stream_ptr()), "pf_sample_begin_guided")
@@ -748,84 +760,49 @@ class PfEngine:
         the tuned training family with its input-gradient switch armed; family and switch are restored afterwards, also on error.
         ms_coef_arr (ms_coef_array): a multistep run, pf_sample_ms -- coef_arr is not read (None), noise needs its first row only
         (the initial draw), and the parameterisation is in the coefficients; seeds compose, pins, plans and restraints are refused."""
-        if field is not None and restraints is None and ms_coef_arr is None:
+        ms, (op_arr, renoise_arr) = ms_coef_arr is not None, plan or (None, None)
+        if field is not None and restraints is None and not ms:
             restraints = [None] * self.B
         guided = restraints is not None
         if guide_family not in PfEngine.GUIDE_FAMILIES:
             raise ValueError(f"guide_family must be 'wide' or 'tuned', got {guide_family!r}")
-        if ms_coef_arr is not None:
-            if pins is not None or plan is not None or guided or field is not None:
-                raise ValueError("a multistep run composes with seeds only: no pins, resampling plan, restraints or pocket field")
-            if len(ms_coef_arr) < n_steps:
-                raise ValueError(f"a multistep run of {n_steps} steps needs {n_steps} entries in ms_coef_arr")
-            nz = _f32(noise, self.device)
-            if nz.dim() == 2:
-                nz = nz[None]
-            assert nz.shape[0] >= 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
-            com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
-            x0, h0, tx, th, _ = self._sample_outputs(n_steps + 1 if trajectory else 0)
-            if seed is not None:
-                self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
-            with torch.cuda.device(self.device):
-                self._ck(self.lib.pf_sample_ms(self._h, n_steps, ms_coef_arr, _dptr(nz), _dptr(com), float(feat_norm_constant), _dptr(x0),
-                                               _dptr(h0), _dptr(tx), _dptr(th), _stream_ptr()), "pf_sample_ms")
-            return (x0, h0, tx, th) if trajectory else (x0, h0)
+        if ms and (pins is not None or plan is not None or guided or field is not None):
+            raise ValueError("a multistep run composes with seeds only: no pins, resampling plan, restraints or pocket field")
         if plan is not None and pins is None:
             raise ValueError("a plan needs pins: resampling runs inside a pinned run (all flags zero pins nothing)")
         if guided and plan is not None:
             raise ValueError("guidance together with resampling jumps is not supported")
         if guided and (pin_coef_arr is None or guide_coef_arr is None):
             raise ValueError("a guided run needs pin_coef_arr (PfEngine.pin_coef_array) and guide_coef_arr (PfEngine.guide_coef_array)")
-        if guided:
-            self._check_guide_family(guide_family)
-        nz = _f32(noise, self.device)
-        assert nz.shape[0] >= n_steps + 1 and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
         if pins is not None and pin_coef_arr is None:
             raise ValueError("a pinned run needs pin_coef_arr (PfEngine.pin_coef_array)")
-        if guided and min(len(coef_arr), len(pin_coef_arr), len(guide_coef_arr)) < n_steps:
-            raise ValueError(f"a guided run of {n_steps} steps needs {n_steps} entries in each of its three coefficient arrays")
+        if guided:
+            self._check_guide_family(guide_family)
+        kind = "multistep" if ms else "guided" if guided else "resampled" if plan is not None else "pinned" if pins is not None else "plain"
+        per_op = {"multistep": dict(ms_coef_arr=ms_coef_arr),
+                  "guided": dict(coef_arr=coef_arr, pin_coef_arr=pin_coef_arr, guide_coef_arr=guide_coef_arr),
+                  "resampled": dict(coef_arr=coef_arr, pin_coef_arr=pin_coef_arr, op_arr=op_arr, renoise_arr=renoise_arr)}.get(kind, {})
+        short = [k for k, a in per_op.items() if len(a) < n_steps]
+        if short:
+            raise ValueError(f"a {kind} run of {n_steps} ops needs {n_steps} entries in each of its per-op arrays; too short: {', '.join(short)}")
+        nz = _f32(noise, self.device)
+        if ms and nz.dim() == 2:
+            nz = nz[None]
+        assert nz.shape[0] >= (1 if ms else n_steps + 1) and nz.shape[1] == self.Nf and nz.shape[2] == 3 + self.pharm_nf
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         pin, restr, _alive = self._run_inputs(pins, restraints)
-        if plan is not None and min(len(plan[0]), len(plan[1]), len(coef_arr), len(pin_coef_arr)) < n_steps:
-            raise ValueError(f"a plan of {n_steps} ops needs {n_steps} entries in each of its four arrays")
         x0, h0, tx, th, en = self._sample_outputs(n_steps + 1 if trajectory else 0, n_steps if guided and energies else None)
         state, eps = (_dptr(nz), _dptr(com)) + pin, (int(ep_coord), int(ep_feat), float(feat_norm_constant))
         outs = (_dptr(x0), _dptr(h0), _dptr(tx), _dptr(th))
-        if guided:
-            name, args = "pf_sample_guided", (coef_arr, pin_coef_arr, guide_coef_arr) + state + eps + restr + (
-                float(guide_scale), float(guide_clip)) + outs + (_dptr(en) if n_steps else None,)
-        elif plan is not None:
-            name, args = "pf_sample_pinned_resampled", (plan[0], coef_arr, pin_coef_arr, plan[1]) + state + eps + outs
-        elif pins is not None:
-            name, args = "pf_sample_pinned", (coef_arr, pin_coef_arr) + state + eps + outs
-        else:
-            name, args = "pf_sample", (coef_arr,) + state + eps + outs
-        if guided and guide_family == "tuned":     # the tuned training forward and its input gradients
-            before = self._arm_guide_family("tuned")
-            try:
-                if seed is not None:
-                    self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
-                if field is not None:
-                    self.field_next(**field)
-                with torch.cuda.device(self.device):
-                    self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
-            finally:
-                self._restore_guide_family(before)
-            out = (x0, h0, tx, th) if trajectory else (x0, h0)
-            return out + (en,) if energies else out
-        family = self.train_family() if guided else "wide"       # a guided step runs the wide training forward and its input gradients
-        if family != "wide":
-            self.set_train_family("wide")
-        try:
-            if seed is not None:
-                self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
-            if field is not None:
-                self.field_next(**field)
-            with torch.cuda.device(self.device):
-                self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
-        finally:
-            if family != "wide":
-                self.set_train_family(family)
+        name, args = {
+            "plain": ("pf_sample", (coef_arr,) + state + eps + outs),
+            "pinned": ("pf_sample_pinned", (coef_arr, pin_coef_arr) + state + eps + outs),
+            "resampled": ("pf_sample_pinned_resampled", (op_arr, coef_arr, pin_coef_arr, renoise_arr) + state + eps + outs),
+            "guided": ("pf_sample_guided", (coef_arr, pin_coef_arr, guide_coef_arr) + state + eps + restr
+                       + (float(guide_scale), float(guide_clip)) + outs + (_dptr(en) if n_steps else None,)),
+            "multistep": ("pf_sample_ms", (ms_coef_arr,) + state + eps[2:] + outs)}[kind]
+        with self._armed(guide_family if guided else None, seed, field, feat_norm_constant), torch.cuda.device(self.device):
+            self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
         out = (x0, h0, tx, th) if trajectory else (x0, h0)
         return out + (en,) if guided and energies else out
 

@@ -861,6 +861,44 @@ class PocketField:
     type_sharpness: float = 4.0
 
 
+@dataclasses.dataclass(frozen=True)
+class RunSpec:
+    """What the keywords of sample / sample_given_receptor ask for, resolved and checked once per call
+    (PharmacophoreDiff._run_spec applies every composition rule); host values only.  ``top``: the level the run starts at, T or
+    a seeded run's seed level.  ``fewstep``: None or (N, sampler, eta, spacing) (_fewstep).  ``guided``: restraints or a pocket
+    field are present somewhere in the call.  What a single batch runs follows from it and two facts of the batch: batch()."""
+    T: int
+    top: int
+    seeded: bool
+    fewstep: Optional[tuple]
+    pin_resamples: int
+    pin_jump: int
+    guide_scale: float
+    guide_clip: float
+    guide_family: str
+    guided: bool
+
+    def batch(self, m, has_pins, guided):
+        """One batch's run, given whether a pin flag is set in it and whether it is guided (a restraint in it, or a pocket field):
+        (kind, n_ops, noise rows, coef_arr, the further array keywords of PfEngine.sample).  kind: 'multistep' (pf_sample_ms; 1
+        row, the initial draw), 'resampled' (a flag and pin_resamples > 1: pf_sample_pinned_resampled over
+        schedule.resample_plan(top, jump, resamples)), else 'guided', 'pinned' or 'plain'; these visit top (few-step: N) levels
+        and read one row more.  The arrays are the model's cached ones (``m``: _step_arrays, _fewstep_arrays, _plan_arrays)."""
+        few, top = self.fewstep, self.top
+        arrays = m._step_arrays if few is None else (lambda name, top: m._fewstep_arrays(name, few, top))
+        n_ops = top if few is None else few[0]
+        if few is not None and few[1] == "multistep":
+            return "multistep", n_ops, 1, None, {"ms_coef_arr": arrays("ms", top)}
+        if has_pins and self.pin_resamples > 1:
+            n_ops, arr, parr, op_arr, re_arr = m._plan_arrays(self.pin_jump, self.pin_resamples, top)
+            return "resampled", n_ops, n_ops + 1, arr, {"pin_coef_arr": parr, "plan": (op_arr, re_arr)}
+        kw = {"pin_coef_arr": arrays("pin", top)} if guided or has_pins else {}
+        if guided:
+            kw.update(guide_coef_arr=arrays("guide", top), guide_scale=self.guide_scale, guide_clip=self.guide_clip,
+                      guide_family=self.guide_family)
+        return "guided" if guided else "pinned" if has_pins else "plain", n_ops, n_ops + 1, arrays("coef", top), kw
+
+
 class PharmacophoreDiff(_Base):
     """Drop-in for pharmacoforge.models.pharmacodiff.PharmacophoreDiff on the sampling / evaluation
     path.  Constructor arguments, attribute names, state-dict keys ('gamma.gamma', 'dynamics.*') and
@@ -1007,36 +1045,58 @@ class PharmacophoreDiff(_Base):
         ``sample_steps`` N with ``sampler`` / ``eta`` / ``spacing``: a few-step run (see ``sample``) -- ``noise`` has N + 1 rows for
         the first-order samplers and 1 row for 'multistep'; trajectories have N + 1 frames."""
         g = as_pocket_graph(g)
+        spec = self._run_spec(pins=self._has_pins(g), guided=self._guided(restraints, pocket_field), pinned=g.pharm_pin is not None,
+                              pin_resamples=pin_resamples, pin_jump=pin_jump, guide_scale=guide_scale, guide_clip=guide_clip,
+                              seeds=seeds, seed_level=seed_level, seed_keep=seed_keep, sample_steps=sample_steps, sampler=sampler,
+                              eta=eta, spacing=spacing, guide_family=guide_family)
+        if seeds is not None:
+            sizes = (g.pharm_ptr[1:] - g.pharm_ptr[:-1]).tolist()
+            fields = self._seed_fields([[n] for n in sizes], seeds, seed_keep, batch=True)
+            g = self._with_pin_fields(g, *(torch.cat(f) for f in zip(*fields)))
+        return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, spec, init_pharm_com, visualize_trajectory, noise,
+                                                                           restraints=restraints,
+                                                                           field=self._field_for_batch(g, pocket_field))))
+
+    @staticmethod
+    def _has_pins(g):
+        """a graph (of one pocket, or batched) carries a pin flag that is set: what makes a run pinned"""
+        return g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
+
+    @staticmethod
+    def _guided(restraints, field):
+        """a pocket field, or a restraint in one of the per-pocket / per-graph lists (None or empty: none): what makes a run guided"""
+        return field is not None or (restraints is not None and any(restraints))
+
+    @staticmethod
+    def _with_pin_fields(g, flags, x, h):
+        dev = g.prot_x.device
+        return dataclasses.replace(g, pharm_pin=flags.to(dev), pharm_pin_x=x.to(dev), pharm_pin_h=h.to(dev))
+
+    def _run_spec(self, pins, guided, pinned=False, pin_resamples=1, pin_jump=10, guide_scale=1.0, guide_clip=0.0, seeds=None,
+                  seed_level=None, seed_keep=None, score_levels=None, sample_steps=None, sampler=None, eta=None, spacing=None,
+                  guide_family="wide"):
+        """The RunSpec of one sample / sample_given_receptor call from its keywords; every rule on how they compose is applied
+        here, once, before any device work.  The two callers differ in where they look: ``pins`` -- a pin is present (an entry of
+        ``pinned``; a flag set on the batched graph), ``guided`` (_guided), ``pinned`` -- pin fields were given at all."""
+        if score_levels is not None and not 1 <= int(score_levels) <= self.n_timesteps:
+            raise ValueError(f"score_levels must satisfy 1 <= K <= {self.n_timesteps}, got {score_levels}")
         self._check_guide_family(guide_family)
         fewstep = self._fewstep(sample_steps, sampler, eta, spacing, pin_resamples=pin_resamples, seed_level=seed_level,
-                                pins=(g.pharm_pin is not None and bool((g.pharm_pin != 0).any())) or seed_keep is not None,
-                                restraints=pocket_field is not None
-                                or (restraints is not None and any(len(r) > 0 for r in restraints if r is not None)))
+                                pins=pins or seed_keep is not None, restraints=guided)
+        if pin_resamples < 1 or pin_jump < 1:
+            raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
+        if guided and pin_resamples > 1:
+            raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
         if (seeds is None) != (seed_level is None):
             raise ValueError("seeds and seed_level go together: a seeded run needs both")
         if seeds is None and seed_keep is not None:
             raise ValueError("seed_keep without seeds")
-        if seeds is not None:
-            g = as_pocket_graph(g)
-            self._check_seed_level(seed_level)
-            if g.pharm_pin is not None:
-                raise ValueError("seeds together with pinned centers: use seed_keep")
-            if len(seeds) != g.batch_size or (seed_keep is not None and len(seed_keep) != g.batch_size):
-                raise ValueError(f"seeds (and seed_keep) need one entry per graph of the batch ({g.batch_size})")
-            sizes = (g.pharm_ptr[1:] - g.pharm_ptr[:-1]).tolist()
-            for r, sd in enumerate(seeds):
-                if sd is None:
-                    raise ValueError(f"pocket {r} has no seed: a seeded run needs one seed per pocket")
-            fields = [self._seed_fields(r, sizes[r], seeds[r], None if seed_keep is None else seed_keep[r]) for r in range(g.batch_size)]
-            dev = g.prot_x.device
-            g = dataclasses.replace(g, **{name: torch.cat([f[i] for f in fields]).to(dev)
-                                          for i, name in enumerate(("pharm_pin", "pharm_pin_x", "pharm_pin_h"))})
-        return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, init_pharm_com, visualize_trajectory, noise,
-                                                                           pin_resamples=pin_resamples, pin_jump=pin_jump,
-                                                                           restraints=restraints, guide_scale=guide_scale,
-                                                                           guide_clip=guide_clip, seed_level=seed_level,
-                                                                           fewstep=fewstep, guide_family=guide_family,
-                                                                           field=self._field_for_batch(g, pocket_field))))
+        if seeds is not None and pinned:
+            raise ValueError("seeds together with pinned centers: use seed_keep")
+        T = int(self.n_timesteps)
+        return RunSpec(T=T, top=T if seeds is None else self._check_seed_level(seed_level), seeded=seeds is not None, fewstep=fewstep,
+                       pin_resamples=int(pin_resamples), pin_jump=int(pin_jump), guide_scale=float(guide_scale),
+                       guide_clip=float(guide_clip), guide_family=guide_family, guided=bool(guided))
 
     def _field_for_batch(self, g, pocket_field, radii=None):
         """PfEngine.field_next's arguments for a batched graph and a PocketField (None: None), checked before any device work.
@@ -1180,112 +1240,80 @@ class PharmacophoreDiff(_Base):
             raise ValueError(f"seed_level must satisfy 1 <= seed_level <= {self.n_timesteps}, got {seed_level}")
         return int(seed_level)
 
-    def _seed_fields(self, r, n, seed, keep):
-        """The pin fields that carry one graph's seed: (flags [n], x [n,3], one-hot rows [n,nf]) from seed = (x [n,3], types [n])
-        and keep = the seed center indices that stay fixed (flag 3; None: none).  ``r`` names the pocket in errors."""
-        x, types = seed
-        x = torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3)
-        types = torch.as_tensor(types, dtype=torch.int64).reshape(-1)
-        k = int(x.shape[0])
-        if types.numel() != k:
-            raise ValueError(f"pocket {r}: the seed has {k} positions and {types.numel()} types")
-        if k != int(n):
-            raise ValueError(f"pocket {r}: the seed has {k} centers but a pharmacophore of {int(n)} was requested "
-                             "(seeds of a different size than the sample are not supported)")
-        if k and (int(types.min()) < 0 or int(types.max()) >= self.n_pharm_feats):
-            raise ValueError(f"pocket {r}: seed types must be in 0..{self.n_pharm_feats - 1}")
-        flags = torch.zeros(k, dtype=torch.int32)
-        for i in (keep or []):
-            if not 0 <= int(i) < k:
-                raise ValueError(f"pocket {r}: seed_keep names center {int(i)} of a seed of {k}")
-            flags[int(i)] = 3
-        return flags, x, F.one_hot(types, self.n_pharm_feats).float()
-
-    def _with_seeds(self, ref_graphs, n_pharms, seeds, seed_keep):
-        """sample(seeds=...): per pocket (x [n,3] in the pocket's frame, types [n] type indices).  The seed rides on the pin
-        fields, which then hold values for ALL centers; seed_keep becomes the flags (3 for kept centers, 0 for the rest)."""
-        if len(seeds) != len(ref_graphs):
-            raise ValueError(f"seeds lists {len(seeds)} entries for {len(ref_graphs)} pockets")
-        if seed_keep is not None and len(seed_keep) != len(ref_graphs):
-            raise ValueError(f"seed_keep lists {len(seed_keep)} entries for {len(ref_graphs)} pockets")
+    def _seed_fields(self, sizes, seeds, seed_keep, batch=False):
+        """The pin fields that carry the seeds: per entry r a (flags [n], x [n,3], one-hot rows [n,nf]) from seeds[r] = (x [n,3],
+        types [n]) and seed_keep[r] = the seed center indices that stay fixed (flag 3; seed_keep None: none).  An entry is a pocket
+        of sample, or (``batch``, which only words the errors) a graph of sample_given_receptor's batch; sizes[r] lists the
+        pharmacophore sizes requested of it, and each must be the seed's."""
+        n = len(sizes)
+        for name, v in (("seeds", seeds), ("seed_keep", seed_keep)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"seeds (and seed_keep) need one entry per graph of the batch ({n})" if batch
+                                 else f"{name} lists {len(v)} entries for {n} pockets")
         for r, sd in enumerate(seeds):
             if sd is None:
                 raise ValueError(f"pocket {r} has no seed: a seeded run needs one seed per pocket")
         out = []
-        for r, (g, sd) in enumerate(zip(ref_graphs, seeds)):
-            k = int(torch.as_tensor(sd[0]).reshape(-1, 3).shape[0])
-            other = [int(n) for n in n_pharms[r] if int(n) != k]
+        for r, (x, types) in enumerate(seeds):
+            x = torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3)
+            types = torch.as_tensor(types, dtype=torch.int64).reshape(-1)
+            k = int(x.shape[0])
+            other = [int(s) for s in sizes[r] if int(s) != k]
             if other:
-                raise ValueError(f"pocket {r}: the seed has {k} centers but sizes {other} were requested")
-            flags, x, h = self._seed_fields(r, k, sd, None if seed_keep is None else seed_keep[r])
-            dev = g.prot_x.device
-            out.append(dataclasses.replace(g, pharm_pin=flags.to(dev), pharm_pin_x=x.to(dev), pharm_pin_h=h.to(dev)))
+                raise ValueError(f"pocket {r}: the seed has {k} centers but " + (
+                    f"a pharmacophore of {other[0]} was requested (seeds of a different size than the sample are not supported)"
+                    if batch else f"sizes {other} were requested"))
+            if types.numel() != k:
+                raise ValueError(f"pocket {r}: the seed has {k} positions and {types.numel()} types")
+            if k and (int(types.min()) < 0 or int(types.max()) >= self.n_pharm_feats):
+                raise ValueError(f"pocket {r}: seed types must be in 0..{self.n_pharm_feats - 1}")
+            flags = torch.zeros(k, dtype=torch.int32)
+            for i in (seed_keep[r] if seed_keep is not None else None) or []:
+                if not 0 <= int(i) < k:
+                    raise ValueError(f"pocket {r}: seed_keep names center {int(i)} of a seed of {k}")
+                flags[int(i)] = 3
+            out.append((flags, x, F.one_hot(types, self.n_pharm_feats).float()))
         return out
 
-    def _sample_enqueue(self, g, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0,
-                        pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0, guide_clip: float = 0.0,
-                        seed_level: int = None, fewstep=None, guide_family: str = "wide", field=None):
+    def _with_seeds(self, ref_graphs, n_pharms, seeds, seed_keep):
+        """sample(seeds=...): per pocket (x [n,3] in the pocket's frame, types [n] type indices).  The seed rides on the pin
+        fields, which then hold values for ALL centers; seed_keep becomes the flags (3 for kept centers, 0 for the rest)."""
+        return [self._with_pin_fields(g, *f) for g, f in zip(ref_graphs, self._seed_fields(n_pharms, seeds, seed_keep))]
+
+    def _sample_enqueue(self, g, spec, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0, restraints=None,
+                        field=None, generator=None):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
-        current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  ``restraints``: None or one
-        list (or None) per graph of the batch; a batch takes the guided path (pf_sample_guided) only when one of them holds a
-        restraint, as with pin flags, or when ``field`` (_field_for_batch) is given.  A batch with a flag set and pin_resamples > 1: pf_sample_pinned_resampled.
-        ``seed_level`` a: a seeded run -- the graph's pharm_pin_x / pharm_pin_h hold the seed of EVERY center (the flags say which
-        of them stay fixed), the run starts at level a (pf_sample_seed_next) and its arrays hold the steps a-1 .. 0.
-        ``fewstep`` (_fewstep): the run visits the N + 1 levels of a plan from T (or a) down; 'multistep': pf_sample_ms."""
+        current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  What runs is ``spec``'s answer
+        for this batch (RunSpec.batch): a pin flag set on the graph makes it pinned, a restraint in ``restraints`` (None or one
+        list or None per graph of the batch) or ``field`` (_field_for_batch) guided.  A seeded run's graph holds the seed of EVERY
+        center on pharm_pin_x / pharm_pin_h (the flags say which of them stay fixed).  ``noise`` None: the rows the run reads, one
+        torch.randn on the model's device from ``generator``."""
         g = as_pocket_graph(g)
         dev = self.device
-        top = None
-        if seed_level is not None:
-            top = self._check_seed_level(seed_level)
-            if g.pharm_pin_x is None or g.pharm_pin_h is None:
-                raise ValueError("a seeded run needs the seed on the graph's pharm_pin_x / pharm_pin_h")
-        n_ops, Nf, nf = (self.n_timesteps if top is None else top), g.num_nodes("pharm"), self.n_pharm_feats
-        if pin_resamples < 1 or pin_jump < 1:
-            raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
-        has_pins = g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
-        guided = (restraints is not None and any(len(r) > 0 for r in restraints if r is not None)) or field is not None
-        if guided and pin_resamples > 1:
-            raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
-        kw = {}
-        ms = fewstep is not None and fewstep[1] == "multistep"
-        step_arrays = self._step_arrays if fewstep is None else (lambda name, top: self._fewstep_arrays(name, fewstep, top))
-        if fewstep is not None:
-            n_ops = fewstep[0]
-            if pin_resamples > 1:
-                raise ValueError("sample_steps together with pin_resamples > 1: resampling jumps over a strided plan are not supported")
-            if ms and (has_pins or guided):
-                raise ValueError("sampler 'multistep' composes with seeds only: no pinned centers, no restraints")
-        if fewstep is not None and noise is not None and noise.shape[0] != (1 if ms else n_ops + 1):
-            raise ValueError(f"a {fewstep[1]} run of {n_ops} steps needs {1 if ms else n_ops + 1} noise row(s), got {noise.shape[0]}")
-        if ms:
-            arr, kw = None, {"ms_coef_arr": step_arrays("ms", top)}
-        elif has_pins and pin_resamples > 1:
-            n_ops, arr, parr, op_arr, re_arr = self._plan_arrays(pin_jump, pin_resamples, top)
-            if noise is not None and noise.shape[0] != n_ops + 1:
-                raise ValueError(f"a resampled pinned run of {n_ops} ops (T = {self.n_timesteps}, jump {pin_jump}, resamples {pin_resamples}) "
-                                 f"needs {n_ops + 1} noise rows, got {noise.shape[0]}")
-            kw = {"pin_coef_arr": parr, "plan": (op_arr, re_arr)}
-        else:
-            arr = step_arrays("coef", top)
-            if guided or has_pins:
-                kw = {"pin_coef_arr": step_arrays("pin", top)}
+        guided = self._guided(restraints, field)
+        kind, n_ops, rows, arr, kw = spec.batch(self, self._has_pins(g), guided)
+        if noise is not None and noise.shape[0] != rows:
+            if spec.fewstep is not None:
+                raise ValueError(f"a {spec.fewstep[1]} run of {n_ops} steps needs {rows} noise row(s), got {noise.shape[0]}")
+            if kind == "resampled":
+                raise ValueError(f"a resampled pinned run of {n_ops} ops (T = {spec.T}, jump {spec.pin_jump}, resamples "
+                                 f"{spec.pin_resamples}) needs {rows} noise rows, got {noise.shape[0]}")
+            if spec.seeded:
+                raise ValueError(f"a seeded run of {n_ops} ops (seed level {spec.top}) needs {rows} noise rows, got {noise.shape[0]}")
+            # (a full-length unseeded run has always ignored extra rows; the engine asserts that there are enough)
         if "pin_coef_arr" in kw and g.pharm_pin is not None:       # (a seeded multistep run carries its seed on these fields: no pins)
             kw["pins"] = (g.pharm_pin, g.pharm_pin_x, g.pharm_pin_h)
-        if top is not None:
-            if fewstep is None and noise is not None and noise.shape[0] != n_ops + 1:
-                raise ValueError(f"a seeded run of {n_ops} ops (seed level {top}) needs {n_ops + 1} noise rows, got {noise.shape[0]}")
-            kw["seed"] = (g.pharm_pin_x, g.pharm_pin_h, seed_coefficients(self.gamma.gamma, self.n_timesteps, top))
+        if spec.seeded:
+            kw["seed"] = (g.pharm_pin_x, g.pharm_pin_h, seed_coefficients(self.gamma.gamma, self.n_timesteps, spec.top))
         if guided:
-            if restraints is None:
-                restraints = [None] * g.batch_size
-            if field is not None:
-                kw["field"] = field
+            restraints = [None] * g.batch_size if restraints is None else restraints
             if len(restraints) != g.batch_size:
                 raise ValueError(f"restraints lists {len(restraints)} entries for a batch of {g.batch_size} graphs")
-            kw.update(restraints=restraints, guide_coef_arr=step_arrays("guide", top), guide_scale=float(guide_scale),
-                      guide_clip=float(guide_clip), guide_family=guide_family)
+            kw["restraints"] = restraints
+            if field is not None:
+                kw["field"] = field
         if noise is None:
-            noise = torch.randn(1 if ms else n_ops + 1, Nf, 3 + nf, device=dev)
+            noise = torch.randn(rows, g.num_nodes("pharm"), 3 + self.n_pharm_feats, device=dev, generator=generator)
         if lane == 0:
             eng = self.dynamics.bind_graph(g)
         else:
@@ -1354,9 +1382,7 @@ class PharmacophoreDiff(_Base):
             small = [int(n) for n in n_pharms[r] if int(n) < k]
             if small:
                 raise ValueError(f"pocket {r}: {k} centers are pinned but sizes {small} were requested")
-            dev = g.prot_x.device
-            out.append(dataclasses.replace(g, pharm_pin=flags.to(dev), pharm_pin_x=x.to(dev),
-                                           pharm_pin_h=F.one_hot(types, self.n_pharm_feats).float().to(dev)))
+            out.append(self._with_pin_fields(g, flags, x, F.one_hot(types, self.n_pharm_feats).float()))
         return out
 
     def sample(self, ref_graphs: List[PocketGraph], n_pharms: List[List[int]], max_batch_size: int = 32,
@@ -1431,28 +1457,23 @@ class PharmacophoreDiff(_Base):
         ``score_levels`` K: every returned SampledPharmacophore carries ``.score``, the PharmacophoreScore of its final frame at K
         stratified levels (score(), uniform weighting, seed 0) -- a second pass behind the sampling, which it leaves bit for bit
         as it is without.  None (the default): no scoring, ``.score`` stays None."""
-        if score_levels is not None and not 1 <= int(score_levels) <= self.n_timesteps:
-            raise ValueError(f"score_levels must satisfy 1 <= K <= {self.n_timesteps}, got {score_levels}")
-        self._check_guide_family(guide_family)
-        fewstep = self._fewstep(sample_steps, sampler, eta, spacing, pin_resamples=pin_resamples, seed_level=seed_level,
-                                pins=pinned is not None and any(p is not None for p in pinned) or seed_keep is not None,
-                                restraints=(restraints is not None and any(restraints)) or pocket_field is not None)
+        spec = self._run_spec(pins=pinned is not None and any(p is not None for p in pinned),
+                              guided=self._guided(restraints, pocket_field), pinned=pinned is not None, pin_resamples=pin_resamples,
+                              pin_jump=pin_jump, guide_scale=guide_scale, guide_clip=guide_clip, seeds=seeds, seed_level=seed_level,
+                              seed_keep=seed_keep, score_levels=score_levels, sample_steps=sample_steps, sampler=sampler, eta=eta,
+                              spacing=spacing, guide_family=guide_family)
         scored_graphs = ref_graphs
         from .sharding import shard_by_work
         ref_graphs = [as_pocket_graph(g) for g in ref_graphs]
         n_receptors = len(ref_graphs)
         if n_receptors == 0:
             return []
-        if pin_resamples < 1 or pin_jump < 1:
-            raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
         if restraints is not None:
             if len(restraints) != n_receptors:
                 raise ValueError(f"restraints lists {len(restraints)} entries for {n_receptors} pockets")
             restraints = [list(r) if r else None for r in restraints]
             if not any(restraints):
                 restraints = None
-            elif pin_resamples > 1:
-                raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
             for r, rs in enumerate(restraints or []):
                 for _, c, _, _, _ in (rs or []):
                     if c is not None and c != "*" and int(c) >= 0:
@@ -1463,8 +1484,6 @@ class PharmacophoreDiff(_Base):
         if pocket_field is not None:
             if not isinstance(pocket_field, PocketField):
                 raise ValueError(f"pocket_field must be a PocketField, got {type(pocket_field).__name__}")
-            if pin_resamples > 1:
-                raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
             r = pocket_field.clash_radius
             if r is not None:
                 radii = list(r) if isinstance(r, (list, tuple)) else [r] * n_receptors
@@ -1478,17 +1497,9 @@ class PharmacophoreDiff(_Base):
                     if gi.prot_ph_x is None or gi.prot_ph_h is None:
                         raise ValueError(f"pocket {i} has no receptor features (prot_ph_x / prot_ph_h): comp_weight > 0 needs them "
                                          "(PDB input carries none; use comp_weight = 0 or a dataset graph)")
-        if (seeds is None) != (seed_level is None):
-            raise ValueError("seeds and seed_level go together: a seeded run needs both")
-        if seeds is None and seed_keep is not None:
-            raise ValueError("seed_keep without seeds")
-        if seeds is not None and pinned is not None:
-            raise ValueError("seeds together with pinned: use seed_keep")
         if pinned is not None:
             ref_graphs = self._with_pins(ref_graphs, n_pharms, pinned)
-        top = None
         if seeds is not None:
-            top = self._check_seed_level(seed_level)
             ref_graphs = self._with_seeds(ref_graphs, n_pharms, seeds, seed_keep)
         if init_pharm_com is None:
             init_pharm_com = torch.stack([g.prot_x.mean(dim=0) for g in ref_graphs], dim=0)
@@ -1515,7 +1526,6 @@ class PharmacophoreDiff(_Base):
             mine = shard_by_work(work, world_size)[rank]
         else:
             mine = list(range(len(batches)))
-        T, nf = self.n_timesteps, self.n_pharm_feats
         base_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if noise is None else 0
         # every graph's initial center of mass on the device with ONE copy before the pipeline starts (a batch is a
         # contiguous range of graphs); per-batch host -> device copies would each wait for the batch in flight
@@ -1544,23 +1554,13 @@ class PharmacophoreDiff(_Base):
             init_coms = coms_dev[idx[0]:idx[-1] + 1]
             lane = k % n_lanes
             with torch.cuda.stream(streams[lane]):
-                rows = (T if top is None else top) + 1
-                if fewstep is not None:
-                    rows = 1 if fewstep[1] == "multistep" else fewstep[0] + 1
-                if pin_resamples > 1 and batch_g.pharm_pin is not None and bool((batch_g.pharm_pin != 0).any()):
-                    rows = self._plan_arrays(pin_jump, pin_resamples, top)[0] + 1
-                if noise is None:
-                    gen = torch.Generator(device=self.device).manual_seed(base_seed + bi)
-                    nz = torch.randn(rows, batch_g.num_nodes("pharm"), 3 + nf, device=self.device, generator=gen)
-                else:
-                    nz = noise[bi]
+                # the noise rows this batch's run reads (RunSpec.batch) are drawn from its own generator, or given
+                gen = torch.Generator(device=self.device).manual_seed(base_seed + bi) if noise is None else None
                 # the bind is asynchronous (stream-ordered behind the lane's previous batch), nothing here waits for the device
                 batch_r = [restraints[graph_ref_idx[i]] for i in idx] if restraints is not None else None
                 field = self._field_for_batch(batch_g, pocket_field, None if radii is None else [radii[graph_ref_idx[i]] for i in idx])
-                enq = self._sample_enqueue(batch_g, init_coms, visualize_trajectory, nz, lane=lane,
-                                           pin_resamples=pin_resamples, pin_jump=pin_jump, restraints=batch_r,
-                                           guide_scale=guide_scale, guide_clip=guide_clip, seed_level=top, fewstep=fewstep,
-                                           guide_family=guide_family, field=field)
+                enq = self._sample_enqueue(batch_g, spec, init_coms, visualize_trajectory, None if noise is None else noise[bi],
+                                           lane=lane, restraints=batch_r, field=field, generator=gen)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on
