@@ -279,6 +279,11 @@ int main(int argc, char** argv) {
         cases.push_back({"64/32 wide", c, false, true});
         c = base_config(); c.n_hidden_scalars = 256; c.vector_size = 32;
         cases.push_back({"256/32 wide", c, false, true});
+        // feature counts at the ends of pf_create's range (tests/test_gpu_feature_counts.py runs them on the device)
+        c = base_config(); c.pharm_nf = 1; c.rec_nf = 1;
+        cases.push_back({"pharm_nf 1, rec_nf 1, spec and wide", c, true, true});
+        c = base_config(); c.pharm_nf = 16; c.rec_nf = 40;
+        cases.push_back({"pharm_nf 16, rec_nf 40, spec and wide", c, true, true});
     }
     for (size_t k = 0; k < cases.size(); ++k) {
         const Case& cs = cases[k];

@@ -64,8 +64,11 @@ def level_terms(batch, st, dyn_h, dyn_x, ep_coord, ep_feat):
         feat = (st.eps_h - dyn_h).square().sum(dim=1)
         pred_rows = (st.h_t - st.s * dyn_h) / st.a
     hit = (pred_rows.argmax(dim=1) == clean).to(pos.dtype)
-    top = pred_rows.topk(2, dim=1).values
-    margin = (top[:, 0] - top[:, 1]) / pred_rows.abs().max(dim=1).values
+    if pred_rows.shape[1] >= 2:
+        top = pred_rows.topk(2, dim=1).values
+        margin = (top[:, 0] - top[:, 1]) / pred_rows.abs().max(dim=1).values
+    else:                                   # one type: there is no runner-up, the prediction cannot be another
+        margin = torch.ones_like(pos)
     out = torch.zeros(batch.batch_size, 4, dtype=pos.dtype)
     for q, v in enumerate((pos, feat, err, hit)):
         out[:, q].index_add_(0, bidx, v)

@@ -1,4 +1,5 @@
-"""The weight packer on the CPU (csrc/pf_pack.cpp): tests/pack_check.cpp packs seeded tensors for seven configurations and checks
+"""The weight packer on the CPU (csrc/pf_pack.cpp): tests/pack_check.cpp packs seeded tensors for nine configurations (two of them
+at the ends of the feature-count range: pharm_nf / rec_nf 1 / 1 and 16 / 40) and checks
 every packed element against the gather map, the split table, the layout's offsets and extents -- compiled host-only under the
 address and undefined-behaviour sanitizers and run as a program of its own, once as the default build and once with -DN16_SPLIT=1."""
 import os
