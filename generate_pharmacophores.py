@@ -37,6 +37,10 @@ _FLAGS = [
     ('--pin_resamples', dict(type=int, default=None, help='with --pinned_centers: denoise every stretch of --pin_jump levels this many times, re-noising it in between, so that the free centers can react to the pinned ones (default 1: no resampling; a run costs about this many times the steps)')),
     ('--pin_jump', dict(type=int, default=None, help='with --pinned_centers: levels per resampled stretch (default 10)')),
     ('--restraints', dict(type=Path, default=None, help='guided sampling: a text file with one restraint per line, "attract|repel x y z radius weight [center|*]" in the receptor\'s frame (# starts a comment): keep centers out of / pull a center into a sphere; a guided step costs several times a default one')),
+    ('--type_restraints', dict(type=Path, default=None, help='guided sampling of the types: a text file with one type restraint per line, "type NAME|INDEX x y z radius weight [center|*]" in the receptor\'s frame (# starts a comment): a center inside the sphere takes that type or is pushed out (radius 0: no spatial condition); with an attract restraint on the same sphere: "a center of this type within radius of the point"')),
+    ('--guide_type_scale', dict(type=float, default=None, help='with --type_restraints: strength of the guidance of the feature rows (default 1)')),
+    ('--guide_type_clip', dict(type=float, default=None, help='with --type_restraints: largest Euclidean norm of a feature row\'s shift per step (default 0: no clip)')),
+    ('--type_sharpness', dict(type=float, default=None, help='with --type_restraints: sharpness of the soft type assignment on one-hot-scaled features (default 4)')),
     ('--avoid_clashes', dict(type=float, nargs='?', const=2.0, default=None, metavar='R', help='guided sampling: keep the centers out of the pocket\'s own atoms -- a center of the predicted clean sample within R angstroms of an atom (default 2.0) is pushed out; every batch then runs guided, which costs several times a default step')),
     ('--clash_weight', dict(type=float, default=None, help='with --avoid_clashes: weight of the clash energy (default 1)')),
     ('--guide_scale', dict(type=float, default=None, help='with --restraints or --avoid_clashes: strength of the guidance (default 1)')),
@@ -69,15 +73,26 @@ def parse_arguments(argv=None):
             parser.error(f'--{flag} needs --pinned_centers')
         if v is not None and v < 1:
             parser.error(f'--{flag} must be at least 1, got {v}')
-    guided = a.restraints is not None or a.avoid_clashes is not None
+    guided = a.restraints is not None or a.avoid_clashes is not None or a.type_restraints is not None
+    for flag in ('guide_type_scale', 'guide_type_clip', 'type_sharpness'):
+        v = getattr(a, flag)
+        if v is not None and a.type_restraints is None:
+            parser.error(f'--{flag} needs --type_restraints')
+        if v is not None and not (v >= 0 and v < float('inf')):
+            parser.error(f'--{flag} must be finite and not negative, got {v}')
+    if a.type_restraints is not None and a.pin_resamples is not None and a.pin_resamples > 1:
+        parser.error('--type_restraints together with --pin_resamples > 1: guidance with resampling jumps is not supported')
+    a.guide_type_scale = 1.0 if a.guide_type_scale is None else a.guide_type_scale
+    a.guide_type_clip = 0.0 if a.guide_type_clip is None else a.guide_type_clip
+    a.type_sharpness = 4.0 if a.type_sharpness is None else a.type_sharpness
     for flag in ('guide_scale', 'guide_clip'):
         v = getattr(a, flag)
         if v is not None and not guided:
-            parser.error(f'--{flag} needs --restraints or --avoid_clashes')
+            parser.error(f'--{flag} needs --restraints, --avoid_clashes or --type_restraints')
         if v is not None and not v >= 0:
             parser.error(f'--{flag} must not be negative, got {v}')
     if a.guide_family is not None and not guided:
-        parser.error('--guide_family needs --restraints or --avoid_clashes')
+        parser.error('--guide_family needs --restraints, --avoid_clashes or --type_restraints')
     if a.clash_weight is not None and a.avoid_clashes is None:
         parser.error('--clash_weight needs --avoid_clashes')
     for flag in ('avoid_clashes', 'clash_weight'):
@@ -134,7 +149,7 @@ def parse_arguments(argv=None):
         if a.eta is not None and not 0.0 <= a.eta <= 1.0:
             parser.error(f'--eta must lie in 0..1, got {a.eta}')
         if a.sampler == 'multistep' and (a.pinned_centers is not None or guided or a.seed_keep is not None):
-            parser.error('--sampler multistep composes with --seed_pharmacophore only: no --pinned_centers, --seed_keep, --restraints or --avoid_clashes')
+            parser.error('--sampler multistep composes with --seed_pharmacophore only: no --pinned_centers, --seed_keep, --restraints, --type_restraints or --avoid_clashes')
     a.pin_resamples = 1 if a.pin_resamples is None else a.pin_resamples
     a.pin_jump = 10 if a.pin_jump is None else a.pin_jump
     for flag in ('score_samples', 'keep_best'):
@@ -153,6 +168,7 @@ def parse_arguments(argv=None):
     a.score_frames = None
     if a.score_pharmacophores is not None:
         given = [f for f in ('--samples_per_pocket', '--pharm_sizes', '--visualize_trajectory', '--pinned_centers', '--restraints',
+                             '--type_restraints',
                              '--seed_pharmacophore', '--use_ref_lig_com', '--metrics')
                  if getattr(a, f[2:]) not in (parser.get_default(f[2:]), None)]
         if given:
@@ -188,6 +204,14 @@ def parse_arguments(argv=None):
         small = [n for n in a.pharm_sizes if named and n <= max(named)]
         if small:
             problems.append(f'--pharm_sizes {small} do not reach center {max(named)} named in --restraints')
+    a.type_restraint_list = None
+    if a.type_restraints is not None:
+        from pharmacoforge_amd.pocket_io import read_type_restraints
+        a.type_restraint_list = read_type_restraints(a.type_restraints)
+        named = [c for _, c, _, _, _ in a.type_restraint_list if c is not None]
+        small = [n for n in a.pharm_sizes if named and n <= max(named)]
+        if small:
+            problems.append(f'--pharm_sizes {small} do not reach center {max(named)} named in --type_restraints')
     if problems:
         raise ValueError('; '.join(problems))
     if a.ref_ligand_file is not None and a.residue_list:
@@ -238,16 +262,20 @@ def score_frames(pfa, model, pocket, frames, args):
                            max_batch_size=args.max_batch_size)[0]
 
 
-def write_scores(path, indices, scores, clashes=None):
+def write_scores(path, indices, scores, clashes=None, type_energies=None):
     """scores.tsv: one line per pharmacophore, in the order of pharms.xyz (or of the scored file).  clashes (a pocket field was on):
-    per pharmacophore (final clash energy, clashing (center, atom) pairs), two more columns"""
+    per pharmacophore (final clash energy, clashing (center, atom) pairs), two more columns; type_energies (type restraints were
+    given): per pharmacophore the final type energy, one more column"""
     head = ('index', 'centers', 'total', 'per_center', 'pos', 'feat', 'position_error', 'type_accuracy')
-    lines = ['\t'.join(head + (('clash_energy', 'clashes') if clashes is not None else ()))]
+    lines = ['\t'.join(head + (('clash_energy', 'clashes') if clashes is not None else ())
+                       + (('type_energy',) if type_energies is not None else ()))]
     for k, (i, s) in enumerate(zip(indices, scores)):
         row = (str(i), str(s.n_centers), f'{s.total:.6g}', f'{s.per_center:.6g}', f'{s.pos:.6g}', f'{s.feat:.6g}',
                f'{s.position_error:.6g}', f'{s.type_accuracy:.4f}')
         if clashes is not None:
             row += (f'{clashes[k][0]:.6g}', str(clashes[k][1]))
+        if type_energies is not None:
+            row += (f'{type_energies[k]:.6g}',)
         lines.append('\t'.join(row))
     Path(path).write_text('\n'.join(lines) + '\n')
 
@@ -296,6 +324,10 @@ def main(argv=None):
     k_named = 0
     if args.restraint_list:
         k_named = 1 + max([c for _, c, _, _, _ in args.restraint_list if c is not None], default=-1)
+    type_guidance = None
+    if args.type_restraint_list:
+        k_named = max(k_named, 1 + max([c for _, c, _, _, _ in args.type_restraint_list if c is not None], default=-1))
+        type_guidance = pfa.TypeGuidance(scale=args.guide_type_scale, clip=args.guide_type_clip, sharpness=args.type_sharpness)
     field = None
     if args.avoid_clashes is not None:       # PDB input has no receptor features: the clash term alone
         field = pfa.PocketField(clash_radius=args.avoid_clashes, clash_weight=args.clash_weight, comp_weight=0.0)
@@ -319,7 +351,9 @@ def main(argv=None):
                                                   seeds=[args.seed_centers] * n if args.seed_centers is not None else None, seed_level=args.seed_level,
                                                   seed_keep=[args.seed_keep_list] * n if args.seed_keep_list else None,
                                                   sample_steps=args.sample_steps, sampler=args.sampler, eta=args.eta, spacing=args.spacing,
-                                                  pocket_field=field)
+                                                  pocket_field=field,
+                                                  type_restraints=[args.type_restraint_list] * n if args.type_restraint_list else None,
+                                                  type_guidance=type_guidance)
     elapsed = time.time() - t0
 
     (pocket_dir / 'sample_time.txt').write_text(f'{elapsed:.2f}')
@@ -332,6 +366,12 @@ def main(argv=None):
         clashes = [clash_energy(ph.ph_coords, pocket.prot_x, args.avoid_clashes, args.clash_weight) for ph in pharms]
         print(f'{name}: clash energy per sample ' + ' '.join(f'{e:.3g}' for e, _ in clashes)
               + '; clashing pairs ' + ' '.join(str(c) for _, c in clashes))
+    type_energies = None
+    if args.type_restraint_list:             # the final type energy of every sample
+        from pharmacoforge_amd.analysis import type_restraint_energy
+        rows = [(model._type_index(t), c, p, r, w) for t, c, p, r, w in args.type_restraint_list]
+        type_energies = [type_restraint_energy(ph.ph_coords, ph.g.pharm_h0, rows, args.type_sharpness) for ph in pharms]
+        print(f'{name}: type energy per sample ' + ' '.join(f'{e:.3g}' for e in type_energies))
     ref_dir = pocket_dir / 'reference_files'
     ref_dir.mkdir(exist_ok=True)
     for src in (args.receptor_file, args.ref_ligand_file):
@@ -346,7 +386,8 @@ def main(argv=None):
         if args.keep_best is not None:
             order = sorted(order, key=lambda i: (scores[i].per_center, i))[:args.keep_best]
         pharms, scores = [pharms[i] for i in order], [scores[i] for i in order]
-        write_scores(pocket_dir / 'scores.tsv', range(len(scores)), scores, None if clashes is None else [clashes[i] for i in order])
+        write_scores(pocket_dir / 'scores.tsv', range(len(scores)), scores, None if clashes is None else [clashes[i] for i in order],
+                     None if type_energies is None else [type_energies[i] for i in order])
     if args.visualize_trajectory:
         for i, ph in enumerate(pharms):
             ph.traj_to_xyz(pocket_dir / f'pharm_{i}_traj.xyz')

@@ -338,7 +338,7 @@ int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* 
  * 0 <= ph_type < pharm_nf; a HOST match table M[pharm_nf][pharm_nf] (0 / 1: a center of type t is matched by a receptor feature
  * of type u) and distances d[pharm_nf] >= 0; w_comp >= 0, kappa > 0, type_sharpness >= 0.  Center f has type weights
  *     p_f = softmax_t(type_sharpness * h0_hat[f]),  h0_hat = (h_t - sigma_t eps_h) / alpha_t, or eps_h under endpoint_param_feat
- * which are constants of the differentiation (features stay unguided; the VJP's g_eps_h stays zero).  For every type t whose set
+ * which are constants of the differentiation (the VJP's g_eps_h stays zero) unless type guidance's comp_types is on, below.  For every type t whose set
  * S_t = {j : M[t][u_j]} is non-empty in the graph, with rho_j = |y_f - q_j|:
  *     rho~ = -(1/kappa) log sum_{j in S_t} exp(-kappa rho_j)     (evaluated with the largest exponent subtracted)
  *     s_j  = the softmax weights of that sum,  m = max(0, rho~ - d[t])
@@ -363,6 +363,49 @@ int pf_guide_field_next(pf_handle* h, const float* host_atom_r /*[Np_tot] or NUL
                         const float* host_ph_x /*[n,3]*/, const int32_t* host_ph_type /*[n]*/, const int32_t* host_match /*[pharm_nf,pharm_nf]*/,
                         const float* host_dist /*[pharm_nf]*/, float w_comp, float kappa, float type_sharpness);
 int pf_debug_last_field(pf_handle* h, float* dev_E3 /*[B,3]*/, pf_stream stream);
+
+/* -- type guidance: a guided run also steers the centers' feature rows (no reference counterpart) --------------------------------
+ * The names are those above: x0_hat, y_f = x0_hat[f] + D[g], alpha_t, sigma_t, coef.sigma.
+ * Predicted clean features.  h0_hat[f] = (h_t[f] - sigma_t eps_h[f]) / alpha_t, or eps_h[f] under endpoint_param_feat;
+ * p_f = softmax_k(s * h0_hat[f][k]) with s = type_sharpness, the maximum subtracted first.
+ * Type restraint (center, type c, p[3], r, w): center a local index or -1 for every center of the graph, 0 <= c < pharm_nf, p in
+ * the caller's frame, r, w >= 0, at most 256 per graph.  Window: omega = 1 when r == 0 (no spatial condition), otherwise
+ * q = max(0, 1 - rho^2 / r^2), omega = q^2, rho^2 = |y_f - p|^2 (no square root; C1 and compact).
+ *     CE = log(sum_k exp(s h0_hat[k] - max)) + max - s h0_hat[c]         (= -log p_fc)
+ *     E  = w omega CE
+ *     dE/dh0_hat[k] = w omega s (p_fk - [k == c])
+ *     dE/dy_f       = w CE (2 q) (-2 (y_f - p) / r^2),   exactly zero when r == 0 or q == 0
+ * Inside the sphere a center either takes type c or is pushed out; with an attract restraint on the same sphere this reads "a
+ * center of type c within r of p".
+ * Complementarity with a type gradient (comp_types, and a pocket field with features and w_comp > 0).  m_t is the pocket field's
+ * hinge for a type whose set S_t is non-empty in the graph and m_t = unmatched (>= 0, default 0) for a type whose set is empty:
+ *     dE/dh0_hat[f][k] = w_comp s p_fk (m_k^2 - sum_t p_ft m_t^2)
+ * E_comp and its coordinate gradient keep their bits; w_comp sum_f sum_{t: S_t empty} p_ft unmatched^2 is counted under the type
+ * energy, not in pf_debug_last_field's three components.  comp_types without such a field is accepted and inert.
+ * Totals.  g0_h[f] = the restraints' term (j ascending) + the complementarity term; E_type[g] = type restraints + unmatched term;
+ * E[g] = (((E_restr + E_clash) + E_comp) + E_type); g0[f] gains the windows' coordinate term behind the field's.
+ * Through the network.  phi_x = -sigma_t / alpha_t (noise parameterisation) or 1 (endpoint_param_coord); phi_h likewise from
+ * endpoint_param_feat.  The VJP runs once with g_eps_x = g0 and g_eps_h = (phi_h / phi_x) g0_h and returns J_x, J_h:
+ *     grad_x     = [g0 / alpha_t, noise only] + phi_x J_x           (the guided step's expression)
+ *     grad_h[f]  = [g0_h[f] / alpha_t, noise feat only] + phi_x J_h[f]
+ *     shift_h[f] = feat_scale * coef.sigma^2 * grad_h[f], clipped to Euclidean norm feat_clip over the row when feat_clip > 0
+ *     h_s[f]     = (the usual value) - shift_h[f]   unless the center's type is pinned (flag & 2)
+ * One rounding per operation.  J_h carries the coordinate energies too: with feat_scale > 0 the feature rows follow every energy
+ * of the run; feat_scale == 0 leaves them where the run without the arming puts them, bit for bit.
+ * Arming.  pf_guide_types_next comes after a bind and arms the NEXT pf_sample_begin_guided (also the one inside pf_sample_guided),
+ * which consumes it, accepted or not; it ends with that run.  host_ptr NULL: no type restraint.  Validation on the host before
+ * anything is touched -- ranges against the bound pharm_ptr, finite values, non-negative r, w, scale, clip, sharpness and
+ * unmatched, the per-graph cap: a failure is PF_ERR_ARG and leaves the handle as it was.  When a pocket field is armed too, both
+ * type_sharpness values must agree or the begin returns PF_ERR_ARG.  The begin of any other run kind while it is armed returns
+ * PF_ERR_STATE and drops the arming; so does a bind (silently).  Without type restraints no k_guide_types launch is made, without
+ * comp_types the pocket field's launch is the one it was; a guided run without the arming executes exactly the launches it did.
+ * pf_debug_last_type_guidance: the last guided step's g0_h, grad_h, shift_h [Nf,pharm_nf] (a type-pinned center's rows are what
+ * it ignored) and E_type [B], each nullable; PF_ERR_STATE when the last guided step on this batch ran without the arming. */
+int pf_guide_types_next(pf_handle* h, const int32_t* host_ptr /*[B+1] or NULL*/, const int32_t* host_center /*[n]*/,
+                        const int32_t* host_type /*[n]*/, const float* host_p /*[n,3]*/, const float* host_r /*[n]*/,
+                        const float* host_w /*[n]*/, float feat_scale, float feat_clip, float type_sharpness, int32_t comp_types,
+                        float unmatched);
+int pf_debug_last_type_guidance(pf_handle* h, float* dev_g0_h, float* dev_grad_h, float* dev_shift_h, float* dev_E_type, pf_stream stream);
 
 /* -- seeded sampling: start the reverse process from a given pharmacophore (partial diffusion; no reference counterpart) ----------
  * The given sample is noised forward to an intermediate level a, 1 <= a <= T, and only the reverse steps a-1 .. 0 are run: a small

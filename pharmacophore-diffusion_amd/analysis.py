@@ -194,6 +194,29 @@ def clash_energy(ph_coords, prot_x, radius=2.0, weight=1.0):
     return float(weight) * float((gap * gap).sum()), int((gap > 0).sum())
 
 
+def type_restraint_energy(ph_coords, ph_feats, type_restraints, sharpness=4.0):
+    """Energy of type restraints on centers [n, 3] (the pocket's frame) with feature rows [n, nf] (one-hot scale: a sample's
+    h_0), in fp64: the sum over restraints (type index, center or None, point, radius, weight) and the centers each applies to of
+    weight * omega * -log softmax(sharpness * row)[type], omega = 1 for radius 0, else max(0, 1 - rho^2 / radius^2)^2 with rho the
+    distance to the point -- the type guidance's restraint term (include/pfdyn.h) on final values."""
+    x = torch.as_tensor(ph_coords).double().reshape(-1, 3).cpu()
+    h = torch.as_tensor(ph_feats).double().cpu().reshape(x.shape[0], -1)
+    if x.shape[0] == 0:
+        return 0.0
+    ce = -torch.log_softmax(float(sharpness) * h, dim=1)
+    total = 0.0
+    for t, center, point, radius, weight in (type_restraints or []):
+        rows = range(x.shape[0]) if center is None or center == "*" or int(center) < 0 else [int(center)]
+        p = torch.as_tensor([float(v) for v in point], dtype=torch.float64)
+        for f in rows:
+            omega = 1.0
+            if float(radius) > 0:
+                q = max(0.0, 1.0 - float(((x[f] - p) ** 2).sum()) / float(radius) ** 2)
+                omega = q * q
+            total += float(weight) * omega * float(ce[f, int(t)])
+    return total
+
+
 def compute_complementarity(pharm_types, pharm_pos, prot_ph_types, prot_ph_pos, return_count=False):
     """metrics.py:53-86: number (or fraction) of centers with a complementary receptor feature within
     the type-specific distance."""

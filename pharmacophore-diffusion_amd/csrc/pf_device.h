@@ -596,6 +596,39 @@ struct FieldParams {
     float* traj_energy;        // [B] row of the caller's trajectory of energies, or NULL (rewritten with the total)
     float* E3;                 // [B][3]   restraints, clash, complementarity
 };
+// type guidance of a guided run (pf_guide_types_next; the block's layout: pf_types.h).  k_guide_types reads TypeParams -- of
+// StepParams the graph pointers, xn, pharm_h, eps_x, eps_h and nf -- behind k_guide_grad and k_guide_field: it adds the windows'
+// coordinate term into g0 and leaves g0_h = dE/dh0_hat per center, gs_h = (phi_h / phi_x) g0_h (the VJP's g_eps_h) and E_type
+struct TypeParams {
+    const int* ptr;            // [B + 1]  graph g owns type restraints [ptr[g], ptr[g + 1])
+    const int* center;         // [n]      local center index, or -1: every center of the graph
+    const int* type;           // [n]      the type asked for
+    const float* p;            // [n][3]   caller's frame
+    const float* r; const float* w;
+    float sharp;               // type_sharpness
+    float alpha_t, sigma_t;    // pf_guide_coef
+    int ep_coord, ep_feat;
+    const float* D;            // [B][3], as k_guide_grad left it
+    float* g0;                 // [Nf][3]  added into
+    float* g0_h;               // [Nf][nf] written; with E3 set it holds the complementarity term on entry, which is added behind
+    float* gs_h;               // [Nf][nf] written
+    float* E_type;             // [B]      written; with E3 set it holds the unmatched term on entry, which is added behind
+    float* energy;             // [B]      rewritten with the total
+    float* traj_energy;        // [B] row of the caller's trajectory of energies, or NULL (rewritten with the total)
+    const float* E3;           // [B][3] of the TYPES form of k_guide_field in front, or NULL: energy[g] is the sum so far
+};
+// what the TYPES form of k_guide_field leaves next to FieldParams' outputs: the complementarity energy's feature gradient
+struct FieldTypeParams {
+    float unmatched;           // m_t of a type whose set S_t is empty in the graph
+    float* g0_h; float* gs_h;  // [Nf][nf] each, written
+    float* E_type;             // [B] written: w_comp sum_f sum_{t: S_t empty} p_ft unmatched^2
+};
+// the feature shift of the guided update's third form (k_step_update_guided_types), next to GuideShiftParams
+struct GuideFeatParams {
+    const float* g0_h; const float* jh;     // [Nf][nf] each: dE/dh0_hat and the VJP's g_pharm_h
+    float scale, clip;                      // feat_scale, feat_clip
+    float* grad_h; float* shift_h;          // [Nf][nf] each: what the step applied (pf_debug_last_type_guidance); a type-pinned center's row is what it ignored
+};
 #ifdef __HIPCC__
 // The p(z_s | z_t) update of sample_p_zs_given_zt (pharmacodiff.py:397-426) for ONE value -- coordinate or feature -- and the only place
 // it is written: the generic update, the latency-optimised one (center threads / feature lanes) and the center hoist's copy all call

@@ -23,6 +23,7 @@
 #include "pf_score.h"
 #include "pf_optim.h"
 #include "pf_field.h"
+#include "pf_types.h"
 
 using namespace pfpack;
 
@@ -72,6 +73,9 @@ void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t
 void pfk_step_update_guided(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, hipStream_t s);
 void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s);
 void pfk_guide_field(const StepParams* p, const FieldParams* q, hipStream_t s);
+void pfk_guide_field_types(const StepParams* p, const FieldParams* q, const FieldTypeParams* ft, hipStream_t s);
+void pfk_guide_types(const StepParams* p, const TypeParams* q, hipStream_t s);
+void pfk_step_update_guided_types(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, const GuideFeatParams* gf, hipStream_t s);
 void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s);
 void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s);
 void pfk_step_build_seed(const StepParams* sp, const SeedParams* q, const BuildParams* bp, hipStream_t s);
@@ -431,6 +435,17 @@ struct pf_handle {
     bool field_armed = false, field_on = false;
     bool field_have = false;                // the last guided step on this batch launched k_guide_field: pf_debug_last_field
     FieldScalars field_arm, field_run;
+    // type guidance (pf_guide_types_next): typed restraints on the predicted clean feature rows, the complementarity energy's
+    // feature gradient and the feature shift of the step end.  Armed, staged (pf_types.h) and uploaded like the pocket field.
+    // d_tguide: what an armed step leaves -- g0_h, gs_h = (phi_h / phi_x) g0_h, J_h, grad_h, shift_h [Nf][pharm_nf] each, E_type [B]
+    struct TypeScalars { int n = 0; float feat_scale = 0.f, feat_clip = 0.f, type_sharpness = 0.f; bool comp = false; float unmatched = 0.f; };
+    void* types_stage = nullptr; size_t types_stage_capacity = 0; hipEvent_t types_ev = nullptr;
+    void* d_types = nullptr; size_t types_capacity = 0;
+    void* d_tguide = nullptr; size_t tguide_capacity = 0;
+    bool types_armed = false, types_on = false;
+    bool types_live = false;                // that step's launches wrote g0_h / E_type (else they are zeros)
+    bool types_have = false;                // the last guided step on this batch ran with type guidance: pf_debug_last_type_guidance
+    TypeScalars types_arm, types_run;
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
@@ -1552,6 +1567,10 @@ void pf_destroy(pf_handle* h) {
     if (h->d_field) (void)hipFree(h->d_field);
     if (h->field_stage) (void)hipHostFree(h->field_stage);
     if (h->field_ev) (void)hipEventDestroy(h->field_ev);
+    if (h->d_types) (void)hipFree(h->d_types);
+    if (h->d_tguide) (void)hipFree(h->d_tguide);
+    if (h->types_stage) (void)hipHostFree(h->types_stage);
+    if (h->types_ev) (void)hipEventDestroy(h->types_ev);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
     for (int k = 0; k < 2; ++k) {
         if (h->d_tab[k]) (void)hipFree(h->d_tab[k]);
@@ -1730,6 +1749,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     if (h) in.rep.swap(h->pending_rep);
     if (h) h->seed_armed = false;               // (so does a seed: pf_sample_seed_next comes after the bind it is for)
     if (h) h->field_armed = false;              // (and a pocket field: its arrays are sized by the batch it was armed on)
+    if (h) h->types_armed = false;              // (and type guidance: its restraints name this batch's centers)
     if (h) h->ms_hist_valid = false;            // (and the multistep history: it belongs to a run on the batch before)
     int rc = check_ready(h, false);
     if (rc) return rc;
@@ -1885,6 +1905,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     h->have_batch = true;
     h->run = RUN_NONE; h->guide_have = false;
     h->field_on = false; h->field_have = false;
+    h->types_on = false; h->types_have = false;
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
 }
@@ -1894,7 +1915,7 @@ int pf_set_pocket_batch(pf_handle* h, int32_t B, const int32_t* prot_ptr, const 
                         const int32_t* pp_dst, pf_stream stream) {
     if (h && (!dev_prot_x || !dev_prot_h)) {
         h->pending_rep.clear();                  // a pocket-group claim never outlives the bind it was made for, rejected or not
-        h->seed_armed = false; h->field_armed = false;
+        h->seed_armed = false; h->field_armed = false; h->types_armed = false;
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch: bad argument");
     }
     return set_pocket_batch_impl(h, B, prot_ptr, pharm_ptr, dev_prot_x, dev_prot_h, nullptr, nullptr, n_pp, pp_src, pp_dst, stream);
@@ -1905,7 +1926,7 @@ int pf_set_pocket_batch_host(pf_handle* h, int32_t B, const int32_t* prot_ptr, c
                              const int32_t* pp_dst, pf_stream stream) {
     if (h && (!host_prot_x || !host_prot_h)) {
         h->pending_rep.clear();
-        h->seed_armed = false; h->field_armed = false;
+        h->seed_armed = false; h->field_armed = false; h->types_armed = false;
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch_host: bad argument");
     }
     return set_pocket_batch_impl(h, B, prot_ptr, pharm_ptr, nullptr, nullptr, host_prot_x, host_prot_h, n_pp, pp_src, pp_dst, stream);
@@ -2002,9 +2023,18 @@ static bool take_field(pf_handle* h) {
     if (h) h->field_armed = false;
     return armed;
 }
+// Type guidance (pf_guide_types_next): armed, taken and refused like the pocket field
+static bool take_types(pf_handle* h) {
+    const bool armed = h && h->types_armed;
+    if (h) h->types_armed = false;
+    return armed;
+}
 static int refuse_field(pf_handle* h, const char* who) {
-    if (take_field(h)) PF_FAIL(h, PF_ERR_STATE, "%s while a pocket field is armed (pf_guide_field_next arms pf_sample_begin_guided / pf_sample_guided "
-                                                "only): the arming is dropped", who);
+    const bool fielded = take_field(h), typed = take_types(h);
+    if (fielded) PF_FAIL(h, PF_ERR_STATE, "%s while a pocket field is armed (pf_guide_field_next arms pf_sample_begin_guided / pf_sample_guided "
+                                          "only): the arming is dropped", who);
+    if (typed) PF_FAIL(h, PF_ERR_STATE, "%s while type guidance is armed (pf_guide_types_next arms pf_sample_begin_guided / pf_sample_guided "
+                                        "only): the arming is dropped", who);
     return PF_OK;
 }
 
@@ -2036,6 +2066,7 @@ static int begin_plain(pf_handle* h, const float* dev_init_pharm_com, const floa
     h->coords_custom = false;               // a rigid translate of the batch's own coordinates from here on
     h->run = RUN_PLAIN;
     h->field_on = false;                    // a pocket field ends with its run
+    h->types_on = false;                    // (and type guidance)
     h->ms_hist_valid = false;               // a run begins without a previous output
     h->edges_built = false; h->rec_valid = false;
     // a seeded begin: the state is the noised seed, made by a move of the step end (which also writes the snapshot, after the move)
@@ -2103,6 +2134,7 @@ struct StepMove {
     int snap_next;                          // PLAIN, SEED: the snapshot sp.h_snap_out is (center hoist)
     const SeedParams* seed = nullptr;       // SEED
     const MsParams* ms = nullptr;           // MS
+    const GuideFeatParams* feat = nullptr;  // GUIDED with type guidance: the update's feature-shift form
 };
 // What every op calls after its dynamics call (if it has one): the move, unless the dynamics call's tail or merged launch made
 // it already; what the move leaves of the edges; what survives of the work done ahead (snapshot, center hoist, speculative rows)
@@ -2119,7 +2151,10 @@ static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipS
             case StepMove::PLAIN: if (build) pfk_step_build(&sp, &bp, step_build_fast_ok(h) ? 1 : 0, s); else pfk_step_update(&sp, s); break;
             case StepMove::PINNED: if (build) pfk_step_build_pinned(&sp, mv.pin, &bp, s); else pfk_step_update_pinned(&sp, mv.pin, s); break;
             case StepMove::RENOISE: if (build) pfk_step_build_renoise(&sp, mv.renoise, &bp, s); else pfk_step_update_renoise(&sp, mv.renoise, s); break;
-            case StepMove::GUIDED: pfk_step_update_guided(&sp, mv.pin, mv.shift, s); break;
+            case StepMove::GUIDED:
+                if (mv.feat) pfk_step_update_guided_types(&sp, mv.pin, mv.shift, mv.feat, s);
+                else pfk_step_update_guided(&sp, mv.pin, mv.shift, s);
+                break;
             case StepMove::SEED: if (build) pfk_step_build_seed(&sp, mv.seed, &bp, s); else pfk_step_update_seed(&sp, mv.seed, s); break;
             case StepMove::MS: if (build) pfk_step_build_ms(&sp, mv.ms, &bp, s); else pfk_step_update_ms(&sp, mv.ms, s); break;
             }
@@ -3548,9 +3583,12 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
                            const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, const int32_t* host_restr_ptr,
                            const int32_t* host_restr_kind, const int32_t* host_restr_center, const float* host_restr_p,
                            const float* host_restr_r, const float* host_restr_w, float guide_scale, float guide_clip, pf_stream stream) {
-    const bool seeded = take_seed(h), fielded = take_field(h);
+    const bool seeded = take_seed(h), fielded = take_field(h), typed = take_types(h);
     int rc = check_ready(h, true);
     if (rc) return rc;
+    if (fielded && typed && h->field_arm.type_sharpness != h->types_arm.type_sharpness)
+        PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: the pocket field's type_sharpness (%g) and the type guidance's (%g) must agree",
+                (double)h->field_arm.type_sharpness, (double)h->types_arm.type_sharpness);
     if (!dev_noise0) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null noise");
     if (!dev_pin_flags || !dev_pin_x || !dev_pin_h) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null pin array");
     if (!(feat_norm_constant > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: feat_norm_constant must be positive");
@@ -3579,6 +3617,10 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     if (!h->restr_ev) PF_HIP(h, hipEventCreateWithFlags(&h->restr_ev, hipEventDisableTiming));
     const pffield::FieldLayout fl(h->Np, h->B, h->field_arm.n, h->cfg.pharm_nf);
     if (fielded && (rc = grow_run_scratch(h, &h->d_field, &h->field_capacity, fl.words() * 4, fl.words() * 8, s)) != PF_OK) return rc;
+    const pftypes::TypesLayout tl(h->B, h->types_arm.n);
+    const size_t twords = nf1 * nh * 5 + (size_t)h->B;
+    if (typed && (rc = grow_run_scratch(h, &h->d_types, &h->types_capacity, tl.words() * 4, tl.words() * 8, s)) != PF_OK) return rc;
+    if (typed && (rc = grow_run_scratch(h, &h->d_tguide, &h->tguide_capacity, twords * 4, twords * 4, s)) != PF_OK) return rc;
     rc = begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, seeded, stream);
     if (rc) return rc;
     {
@@ -3601,13 +3643,20 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
         h->field_run = h->field_arm;
         h->field_on = true;
     }
+    if (typed) {                            // the armed type guidance becomes this run's
+        PF_HIP(h, hipMemcpyAsync(h->d_types, h->types_stage, tl.words() * 4, hipMemcpyHostToDevice, s));
+        PF_HIP(h, hipEventRecord(h->types_ev, s));
+        PF_HIP(h, hipMemsetAsync(h->d_tguide, 0, twords * 4, s));
+        h->types_run = h->types_arm;
+        h->types_on = true;
+    }
     float* gq = (float*)h->d_guide;
     h->d_g0 = gq; h->d_gjx = gq + nf1 * 3; h->d_ggrad = gq + nf1 * 6; h->d_gshift = gq + nf1 * 9; h->d_gzero = gq + nf1 * 12;
     h->d_genergy = h->d_gzero + nf1 * nh; h->d_gD = h->d_genergy + h->B;
     PF_HIP(h, hipMemsetAsync(h->d_guide, 0, gwords * 4, s));          // (the zero g_eps_h of every step's VJP; nothing writes it)
     h->guide_scale = guide_scale; h->guide_clip = guide_clip;
     h->guide_traj_energy = nullptr;
-    h->run = RUN_GUIDED; h->guide_have = false; h->field_have = false;
+    h->run = RUN_GUIDED; h->guide_have = false; h->field_have = false; h->types_have = false;
     h->guide_wide = h->train_wide; h->guide_in_grads = h->train_in_grads;
     return PF_OK;
 }
@@ -3646,6 +3695,13 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     gq.com_init = h->d_com_init; gq.alpha_t = gc->alpha_t; gq.sigma_t = gc->sigma_t; gq.ep_coord = ep_coord;
     gq.g0 = h->d_g0; gq.energy = h->d_genergy; gq.traj_energy = h->guide_traj_energy; gq.D = h->d_gD;
     pfk_guide_grad(&sp, &gq, s);
+    // type guidance's buffers of this step (d_tguide): g0_h, gs_h, J_h, grad_h, shift_h, E_type
+    const size_t tn = h->types_on ? (size_t)std::max(h->Nf, 1) * (size_t)h->cfg.pharm_nf : 0;     // (no arming: no buffer, nothing reads these)
+    float* const tg_g0h = (float*)h->d_tguide;
+    float *const tg_gsh = tg_g0h + tn, *const tg_jh = tg_g0h + 2 * tn, *const tg_grh = tg_g0h + 3 * tn, *const tg_shh = tg_g0h + 4 * tn;
+    float* const tg_E = tg_g0h + 5 * tn;
+    bool comp_types = false;
+    const float* e3 = nullptr;
     if (h->field_on) {                          // the pocket field adds into g0 and E (one more launch; none without a field)
         const pffield::FieldLayout fl(h->Np, h->B, h->field_run.n, h->cfg.pharm_nf);
         const float* fb = (const float*)h->d_field;
@@ -3657,18 +3713,52 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
         fq.alpha_t = gc->alpha_t; fq.sigma_t = gc->sigma_t; fq.ep_coord = ep_coord; fq.ep_feat = ep_feat;
         fq.D = h->d_gD; fq.g0 = h->d_g0; fq.energy = h->d_genergy; fq.traj_energy = h->guide_traj_energy;
         fq.E3 = (float*)h->d_field + fl.e3();
-        pfk_guide_field(&sp, &fq, s);
+        comp_types = h->types_on && h->types_run.comp && h->field_run.n > 0 && h->field_run.w_comp > 0.f;
+        if (comp_types) {                       // the TYPES form: the complementarity energy leaves its feature gradient too
+            FieldTypeParams ft{};
+            ft.unmatched = h->types_run.unmatched; ft.g0_h = tg_g0h; ft.gs_h = tg_gsh; ft.E_type = tg_E;
+            pfk_guide_field_types(&sp, &fq, &ft, s);
+            e3 = fq.E3;
+        } else pfk_guide_field(&sp, &fq, s);
     }
     h->field_have = h->field_on;
-    rc = h->train_wide ? wide_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s)
-                       : tuned_train_backward(h, h->d_gzero, h->d_g0, nullptr, h->d_gjx, nullptr, s);
+    const bool restr_types = h->types_on && h->types_run.n > 0;
+    if (restr_types) {                          // type restraints: one more launch, behind the field's
+        const pftypes::TypesLayout tl(h->B, h->types_run.n);
+        const int32_t* tb = (const int32_t*)h->d_types;
+        TypeParams tq{};
+        tq.ptr = tb + tl.ptr(); tq.center = tb + tl.center(); tq.type = tb + tl.type();
+        tq.p = (const float*)(tb + tl.p()); tq.r = (const float*)(tb + tl.r()); tq.w = (const float*)(tb + tl.w());
+        tq.sharp = h->types_run.type_sharpness; tq.alpha_t = gc->alpha_t; tq.sigma_t = gc->sigma_t; tq.ep_coord = ep_coord; tq.ep_feat = ep_feat;
+        tq.D = h->d_gD; tq.g0 = h->d_g0; tq.g0_h = tg_g0h; tq.gs_h = tg_gsh; tq.E_type = tg_E; tq.energy = h->d_genergy;
+        tq.traj_energy = h->guide_traj_energy; tq.E3 = e3;
+        pfk_guide_types(&sp, &tq, s);
+    }
+    // the VJP's g_eps_h: (phi_h / phi_x) g0_h where a launch above left one, else the stored zeros; g_pharm_h only with the arming
+    const bool live_h = comp_types || restr_types;
+    const float* g_eps_h = live_h ? tg_gsh : h->d_gzero;
+    float* g_h = h->types_on ? tg_jh : nullptr;
+    if (g_h && h->B) {
+        // the encoders' backward recomputes their forward from pharm_h and d_t, and this step's forward took its timestep as a
+        // scalar: d_t gets it now (nothing else reads d_t before the next call that loads it: t_have_fwd is false from here on)
+        uint32_t bits; memcpy(&bits, &coef->t, 4);
+        PF_HIP(h, hipMemsetD32Async((hipDeviceptr_t)h->d_t, (int)bits, (size_t)h->B, s));
+    }
+    rc = h->train_wide ? wide_train_backward(h, g_eps_h, h->d_g0, nullptr, h->d_gjx, g_h, s)
+                       : tuned_train_backward(h, g_eps_h, h->d_g0, nullptr, h->d_gjx, g_h, s);
     if (rc) return rc;
     const PinParams q = pin_params(h, pin);
     GuideShiftParams gs{};
     gs.g0 = h->d_g0; gs.jx = h->d_gjx; gs.D = h->d_gD; gs.alpha_t = gc->alpha_t; gs.sigma_t = gc->sigma_t;
     gs.scale = h->guide_scale; gs.clip = h->guide_clip; gs.grad = h->d_ggrad; gs.shift = h->d_gshift;
+    GuideFeatParams gf{};
+    gf.g0_h = live_h ? tg_g0h : h->d_gzero; gf.jh = tg_jh; gf.scale = h->types_run.feat_scale; gf.clip = h->types_run.feat_clip;
+    gf.grad_h = tg_grh; gf.shift_h = tg_shh;
     h->guide_have = true;
-    return step_end(h, sp, StepMove{StepMove::GUIDED, false, &q, nullptr, &gs, -1}, s);
+    h->types_have = h->types_on; h->types_live = live_h;
+    StepMove mv{StepMove::GUIDED, false, &q, nullptr, &gs, -1};
+    if (h->types_on) mv.feat = &gf;
+    return step_end(h, sp, mv, s);
 }
 
 int pf_sample_guided(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, const pf_pin_coef* host_pin_coef,
@@ -3726,6 +3816,55 @@ int pf_guide_field_next(pf_handle* h, const float* host_atom_r, float w_clash, c
     h->field_arm.n = n; h->field_arm.w_clash = w_clash; h->field_arm.w_comp = w_comp; h->field_arm.kappa = kappa;
     h->field_arm.type_sharpness = type_sharpness;
     h->field_armed = true;
+    return PF_OK;
+}
+
+// Arms the next guided begin with type guidance (the semantics: pfdyn.h), in pf_guide_field_next's manner: every check first
+// (pf_types.h, host only), then the arrays are packed into the handle's pinned staging buffer, where they stay until that begin
+// uploads them on its own stream.  A run in progress reads none of it and goes on
+int pf_guide_types_next(pf_handle* h, const int32_t* host_ptr, const int32_t* host_center, const int32_t* host_type, const float* host_p,
+                        const float* host_r, const float* host_w, float feat_scale, float feat_clip, float type_sharpness,
+                        int32_t comp_types, float unmatched) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    const pftypes::TypesArgs a{host_ptr, host_center, host_type, host_p, host_r, host_w, feat_scale, feat_clip, type_sharpness, comp_types, unmatched};
+    char msg[256];
+    if (!pftypes::validate(a, h->B, h->h_pharm_ptr.data(), h->cfg.pharm_nf, msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
+    const int n = pftypes::n_restraints(a, h->B);
+    const pftypes::TypesLayout tl(h->B, n);
+    const size_t bytes = tl.words() * 4;
+    if (h->types_ev) PF_HIP(h, hipEventSynchronize(h->types_ev));      // the last upload has read the staging buffer
+    else PF_HIP(h, hipEventCreateWithFlags(&h->types_ev, hipEventDisableTiming));
+    h->types_armed = false;                 // (an arming not yet used is replaced, also when the allocation below fails)
+    if (bytes > h->types_stage_capacity) {
+        if (h->types_stage) { (void)hipHostFree(h->types_stage); h->types_stage = nullptr; h->types_stage_capacity = 0; }
+        PF_HIP(h, hipHostMalloc(&h->types_stage, bytes * 2, hipHostMallocDefault));
+        h->types_stage_capacity = bytes * 2;
+    }
+    pftypes::pack(a, h->B, (uint32_t*)h->types_stage);
+    h->types_arm.n = n; h->types_arm.feat_scale = feat_scale; h->types_arm.feat_clip = feat_clip;
+    h->types_arm.type_sharpness = type_sharpness; h->types_arm.comp = comp_types != 0; h->types_arm.unmatched = unmatched;
+    h->types_armed = true;
+    return PF_OK;
+}
+
+int pf_debug_last_type_guidance(pf_handle* h, float* dev_g0_h, float* dev_grad_h, float* dev_shift_h, float* dev_E_type, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!h->guide_have || !h->types_have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_type_guidance: no guided step with type guidance on this batch");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t tn = (size_t)std::max(h->Nf, 1) * (size_t)h->cfg.pharm_nf, nb = (size_t)h->Nf * (size_t)h->cfg.pharm_nf * 4;
+    const float* base = (const float*)h->d_tguide;
+    if (dev_g0_h && nb) {
+        if (h->types_live) PF_HIP(h, hipMemcpyAsync(dev_g0_h, base, nb, hipMemcpyDeviceToDevice, s));
+        else PF_HIP(h, hipMemsetAsync(dev_g0_h, 0, nb, s));
+    }
+    if (dev_grad_h && nb) PF_HIP(h, hipMemcpyAsync(dev_grad_h, base + 3 * tn, nb, hipMemcpyDeviceToDevice, s));
+    if (dev_shift_h && nb) PF_HIP(h, hipMemcpyAsync(dev_shift_h, base + 4 * tn, nb, hipMemcpyDeviceToDevice, s));
+    if (dev_E_type && h->B) {
+        if (h->types_live) PF_HIP(h, hipMemcpyAsync(dev_E_type, base + 5 * tn, (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
+        else PF_HIP(h, hipMemsetAsync(dev_E_type, 0, (size_t)h->B * 4, s));
+    }
     return PF_OK;
 }
 

@@ -1955,11 +1955,41 @@ __device__ __forceinline__ void pf_guide_shift(const float* g0, const float* jx,
         sh[0] *= f; sh[1] *= f; sh[2] *= f;
     }
 }
+// The feature half of the guided move (type guidance, pf_guide_types_next) for one center's row of nf entries:
+//   grad_h = [g0_h / alpha_t, noise parameterisation of the features only] + phi_x J_h,  phi_x = -sigma_t / alpha_t or 1 (endpoint coordinates)
+//   shift_h = (feat_scale sigma_post^2) grad_h, clipped to the Euclidean norm `clip` over the row
+// It stores grad_h and the UNCLIPPED shift_h and returns the clip's factor (1: no clip).  One rounding per operation; the norm sums k ascending
+__device__ __forceinline__ float pf_guide_shift_h(const float* g0h, const float* jh, const int nf, const float alpha_t, const float sigma_t,
+                                                  const int ep_coord, const int ep_feat, const float sigma_post, const float scale,
+                                                  const float clip, float* gr, float* sh) {
+#pragma clang fp contract(off)
+    const float ratio = sigma_t / alpha_t;
+    const float s2 = sigma_post * sigma_post;
+    const float k = scale * s2;
+    float n2 = 0.f;
+    for (int c = 0; c < nf; ++c) {
+        const float j = jh[c];
+        float b;
+        if (ep_coord) b = j;
+        else { const float rj = ratio * j; b = -rj; }
+        float gv = b;
+        if (!ep_feat) { const float a = g0h[c] / alpha_t; gv = a + b; }
+        const float sv = k * gv;
+        gr[c] = gv; sh[c] = sv;
+        const float q = sv * sv;
+        n2 += q;
+    }
+    const float n = sqrtf(n2);
+    return (clip > 0.f && n > clip) ? clip / n : 1.0f;
+}
 // GUIDED: pinned_update_body with one more input -- the guided step's shift is taken off a free center's p(z_s | z_t) value in front
 // of the selects, and D[g] is the one k_guide_grad left (the same reduction of the same rows, which nobody has moved in between).
 // Without it: the pinned kernels' code as it was
-template <bool GUIDED>
-__device__ __forceinline__ void pinned_update_body(const StepParams& p, const PinParams& q, const GuideShiftParams* gs, const int g) {
+// FEAT (a guided run with type guidance, pf_guide_types_next): the feature rows are guided too -- a free center's feature row loses
+// shift_h in front of the `flag & 2` select, as its position loses the shift in front of `flag & 1`
+template <bool GUIDED, bool FEAT = false>
+__device__ __forceinline__ void pinned_update_body(const StepParams& p, const PinParams& q, const GuideShiftParams* gs, const int g,
+                                                   const GuideFeatParams* gf = nullptr) {
     __shared__ float com[3];
     __shared__ float red[4][3];
     __shared__ float dfr[3];                            // D[g]
@@ -2003,11 +2033,20 @@ __device__ __forceinline__ void pinned_update_body(const StepParams& p, const Pi
         }
         p.xn[p.Np_tot + f] = make_float4(m[0], m[1], m[2], 0.f);
         sx += m[0]; sy += m[1]; sz += m[2];
+        float hf = 1.0f;                                // FEAT: the clip's factor of this row
+        if constexpr (FEAT) hf = pf_guide_shift_h(gf->g0_h + (size_t)f * p.nf, gf->jh + (size_t)f * p.nf, p.nf, gs->alpha_t, gs->sigma_t, p.ep_coord,
+                                                  p.ep_feat, p.sigma, gf->scale, gf->clip, gf->grad_h + (size_t)f * p.nf, gf->shift_h + (size_t)f * p.nf);
         for (int k = 0; k < p.nf; ++k) {
             const float hv = p.pharm_h[(size_t)f * p.nf + k];
             const float e = p.eps_h[(size_t)f * p.nf + k];
+            float fr = pf_feat_update(hv, e, nz[3 + k], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_feat);
+            if constexpr (FEAT) {
+                float sh = gf->shift_h[(size_t)f * p.nf + k];          // (this thread's own store, unclipped)
+                if (hf != 1.0f) { sh *= hf; gf->shift_h[(size_t)f * p.nf + k] = sh; }
+                fr -= sh;
+            }
             p.pharm_h[(size_t)f * p.nf + k] = (flag & 2) ? pf_pin_value(q.pin_h[(size_t)f * p.nf + k] / q.feat_norm, nz[3 + k], q.alpha_s, q.sigma_s)
-                                                         : pf_feat_update(hv, e, nz[3 + k], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_feat);
+                                                         : fr;
         }
     }
 #pragma unroll
@@ -2040,6 +2079,11 @@ __global__ __launch_bounds__(256) void k_step_build_pinned(const StepParams sp, 
 // the guided step's update, alone: its dynamics call is the width-generic training forward, which builds its own edges
 __global__ __launch_bounds__(256) void k_step_update_guided(const StepParams p, const PinParams q, const GuideShiftParams gs) {
     pinned_update_body<true>(p, q, &gs, blockIdx.x);
+}
+// ... and with type guidance armed: the feature rows take their shift as well
+__global__ __launch_bounds__(256) void k_step_update_guided_types(const StepParams p, const PinParams q, const GuideShiftParams gs,
+                                                                  const GuideFeatParams gf) {
+    pinned_update_body<true, true>(p, q, &gs, blockIdx.x, &gf);
 }
 // ---------------------------------------------------------------------------------------------
 // Guided sampling (pf_denoise_step_guided): restraint energies on the predicted clean centers, in the caller's frame.
@@ -2527,6 +2571,10 @@ void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t
 void pfk_step_update_guided(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, hipStream_t s) {
     if (p->B == 0) return;
     hipLaunchKernelGGL(k_step_update_guided, dim3(p->B), dim3(256), 0, s, *p, *q, *gs);
+}
+void pfk_step_update_guided_types(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, const GuideFeatParams* gf, hipStream_t s) {
+    if (p->B <= 0) return;
+    hipLaunchKernelGGL(k_step_update_guided_types, dim3(p->B), dim3(256), 0, s, *p, *q, *gs, *gf);
 }
 void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s) {
     if (p->B == 0) return;

@@ -431,17 +431,20 @@ class PfEngine:
             self.set_train_family(before[0])
 
     @contextlib.contextmanager
-    def _armed(self, guide_family, seed, field, feat_norm_constant, restore=True):
+    def _armed(self, guide_family, seed, field, feat_norm_constant, restore=True, types=None):
         """What the begin of a run consumes, armed in one order for sample and sample_begin: the training family of a guided run
         (guide_family None: an unguided run, nothing is selected; 'tuned' takes its input-gradient switch along), then the seed
-        (seed_next), then the pocket field (field_next).  On exit, also on error, family and switch are what they were;
-        restore=False leaves them selected (sample_begin: the run's steps need them, its caller restores)."""
+        (seed_next), then the pocket field (field_next), then type guidance (types_next).  On exit, also on error, family and
+        switch are what they were; restore=False leaves them selected (sample_begin: the run's steps need them, its caller
+        restores)."""
         before = self._arm_guide_family(guide_family) if guide_family is not None else None
         try:
             if seed is not None:
                 self.seed_next(seed[0], seed[1], seed[2], feat_norm_constant)
             if field is not None:
                 self.field_next(**field)
+            if types is not None:
+                self.types_next(**types)
             yield
         finally:
             if restore and before is not None:
@@ -640,8 +643,52 @@ class PfEngine:
             self._ck(self.lib.pf_debug_last_field(self._h, _dptr(e3), _stream_ptr()), "pf_debug_last_field")
         return e3
 
+    def types_next(self, restraints=None, scale=1.0, clip=0.0, sharpness=0.0, complementarity=False, unmatched=0.0):
+        """Arms the next guided begin on this engine with type guidance (pf_guide_types_next; the semantics: include/pfdyn.h):
+        the run's feature rows are steered too.  restraints: None, or one list (or None) per graph of (type index, center, point,
+        radius, weight) -- center a local center index or None / -1 / '*' for every center of the graph, point three coordinates
+        in the caller's frame, radius 0: no spatial condition.  scale / clip: the feature shift's scale and the Euclidean norm a
+        row's shift is clipped to (0: no clip); sharpness: that of the soft type assignment (it must equal an armed pocket
+        field's); complementarity: the pocket field's complementarity energy also steers the types, a type without a partner in
+        the pocket costing ``unmatched``^2.  The library validates the values (PfError, PF_ERR_ARG) and copies them before this
+        returns.  The begin of any other run kind while it is armed is a PfError (PF_ERR_STATE) and drops it; set_batch drops it
+        silently."""
+        import numpy as np
+        none = ctypes.c_void_p(None)
+        args = (none,) * 6
+        keep = ()
+        if restraints is not None:
+            if len(restraints) != self.B:
+                raise ValueError(f"type restraints must have one entry per graph ({self.B}), got {len(restraints)}")
+            ptr, center, ty, pt, rad, wt = [0], [], [], [], [], []
+            for rs in restraints:
+                for t, c, p, r, w in (rs or []):
+                    ty.append(int(t))
+                    center.append(-1 if c is None or c == "*" else int(c))
+                    pt.append([float(v) for v in p])
+                    if len(pt[-1]) != 3:
+                        raise ValueError("a type restraint's point has three coordinates")
+                    rad.append(float(r)); wt.append(float(w))
+                ptr.append(len(ty))
+            keep = (np.asarray(ptr, dtype=np.int32), np.asarray(center, dtype=np.int32), np.asarray(ty, dtype=np.int32),
+                    np.ascontiguousarray(np.asarray(pt, dtype=np.float32).reshape(-1, 3)), np.asarray(rad, dtype=np.float32),
+                    np.asarray(wt, dtype=np.float32))
+            args = tuple(a.ctypes.data for a in keep)
+        self._ck(self.lib.pf_guide_types_next(self._h, *args, float(scale), float(clip), float(sharpness), int(bool(complementarity)),
+                                              float(unmatched)), "pf_guide_types_next")
+
+    def last_type_guidance(self):
+        """(g0_h, grad_h, shift_h [Nf, pharm_nf], E_type [B]) of the last guided step with type guidance
+        (pf_debug_last_type_guidance); a type-pinned center's rows are what it ignored."""
+        g0, gr, sh = (torch.empty(self.Nf, self.pharm_nf, device=self.device) for _ in range(3))
+        en = torch.empty(self.B, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_debug_last_type_guidance(self._h, _dptr(g0), _dptr(gr), _dptr(sh), _dptr(en), _stream_ptr()),
+                     "pf_debug_last_type_guidance")
+        return g0, gr, sh, en
+
     def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0, restraints=None, guide_scale=1.0,
-                     guide_clip=0.0, seed=None, guide_family=None, field=None):
+                     guide_clip=0.0, seed=None, guide_family=None, field=None, types=None):
         """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the begin.
         pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
         denoise_step(..., pin_coef=...); feat_norm_constant is what the given feature rows are divided by.
@@ -650,8 +697,9 @@ class PfEngine:
         guide_family 'wide' / 'tuned' (guided runs only; None: the caller has selected the family): selects that training family --
         for 'tuned', a 128 / 16 handle, also the input-gradient switch -- and leaves it selected: the run's steps need it, and the
         caller restores what it had once the run has ended.
-        field (a dict of field_next's arguments): a guided run with a pocket field, also without restraints."""
-        if field is not None and restraints is None:
+        field (a dict of field_next's arguments): a guided run with a pocket field, also without restraints.
+        types (a dict of types_next's arguments): a guided run with type guidance, also without restraints."""
+        if (field is not None or types is not None) and restraints is None:
             restraints = [None] * self.B
         if guide_family is not None:
             self._check_guide_family(guide_family)
@@ -661,7 +709,7 @@ class PfEngine:
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         self._keep = [nz, com]
         pin, restr, _alive = self._run_inputs(pins, restraints)
-        with self._armed(guide_family, seed, field, feat_norm_constant, restore=False), torch.cuda.device(self.device):
+        with self._armed(guide_family, seed, field, feat_norm_constant, restore=False, types=types), torch.cuda.device(self.device):
             if restraints is not None:
                 self._ck(self.lib.pf_sample_begin_guided(self._h, _dptr(com), _dptr(nz), *pin, float(feat_norm_constant), *restr,
                                                          float(guide_scale), float(guide_clip), _stream_ptr()), "pf_sample_begin_guided")
@@ -746,8 +794,9 @@ class PfEngine:
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
                feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None, restraints=None,
                guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False, seed=None, ms_coef_arr=None,
-               guide_family="wide", field=None):
+               guide_family="wide", field=None, types=None):
         """field (a dict of field_next's arguments): the guided run carries a pocket field; restraints are then optional.
+        types (a dict of types_next's arguments): the guided run steers the feature rows too; restraints are then optional.
         seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the run -- n_steps is
         then the seed's level a, and coef_arr (and the other per-step arrays) hold the entries of s = a-1 .. 0.
         pins = (flags, positions, feature rows) with pin_coef_arr (pin_coef_array, coef_arr's order): pf_sample_pinned.
@@ -761,13 +810,13 @@ class PfEngine:
         ms_coef_arr (ms_coef_array): a multistep run, pf_sample_ms -- coef_arr is not read (None), noise needs its first row only
         (the initial draw), and the parameterisation is in the coefficients; seeds compose, pins, plans and restraints are refused."""
         ms, (op_arr, renoise_arr) = ms_coef_arr is not None, plan or (None, None)
-        if field is not None and restraints is None and not ms:
+        if (field is not None or types is not None) and restraints is None and not ms:
             restraints = [None] * self.B
         guided = restraints is not None
         if guide_family not in PfEngine.GUIDE_FAMILIES:
             raise ValueError(f"guide_family must be 'wide' or 'tuned', got {guide_family!r}")
-        if ms and (pins is not None or plan is not None or guided or field is not None):
-            raise ValueError("a multistep run composes with seeds only: no pins, resampling plan, restraints or pocket field")
+        if ms and (pins is not None or plan is not None or guided or field is not None or types is not None):
+            raise ValueError("a multistep run composes with seeds only: no pins, resampling plan, restraints, pocket field or type guidance")
         if plan is not None and pins is None:
             raise ValueError("a plan needs pins: resampling runs inside a pinned run (all flags zero pins nothing)")
         if guided and plan is not None:
@@ -801,7 +850,7 @@ class PfEngine:
             "guided": ("pf_sample_guided", (coef_arr, pin_coef_arr, guide_coef_arr) + state + eps + restr
                        + (float(guide_scale), float(guide_clip)) + outs + (_dptr(en) if n_steps else None,)),
             "multistep": ("pf_sample_ms", (ms_coef_arr,) + state + eps[2:] + outs)}[kind]
-        with self._armed(guide_family if guided else None, seed, field, feat_norm_constant), torch.cuda.device(self.device):
+        with self._armed(guide_family if guided else None, seed, field, feat_norm_constant, types=types), torch.cuda.device(self.device):
             self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
         out = (x0, h0, tx, th) if trajectory else (x0, h0)
         return out + (en,) if guided and energies else out

@@ -861,6 +861,22 @@ class PocketField:
     type_sharpness: float = 4.0
 
 
+@dataclasses.dataclass
+class TypeGuidance:
+    """Guidance of the centers' feature rows in a guided run (PharmacophoreDiff.sample(type_restraints=..., type_guidance=...);
+    the semantics: include/pfdyn.h, "type guidance").  ``scale``: the feature shift's scale (0: the rows stay where the run
+    without it puts them); ``clip`` > 0: a row's shift is clipped to that Euclidean norm; ``sharpness``: that of the soft type
+    assignment, on one-hot-scaled features (the model multiplies it by its pharm_feat_norm_constant) -- None: the pocket field's
+    when there is one, else 4; with a pocket field the two must agree.  ``complementarity``: the pocket field's complementarity
+    energy steers the types as well (it needs a PocketField with comp_weight > 0); a type without any partner in the pocket then
+    costs ``unmatched``^2 per unit of comp_weight."""
+    scale: float = 1.0
+    clip: float = 0.0
+    sharpness: Optional[float] = None
+    complementarity: bool = False
+    unmatched: float = 0.0
+
+
 @dataclasses.dataclass(frozen=True)
 class RunSpec:
     """What the keywords of sample / sample_given_receptor ask for, resolved and checked once per call
@@ -877,6 +893,14 @@ class RunSpec:
     guide_clip: float
     guide_family: str
     guided: bool
+    types: Optional[tuple] = None               # None, or types_next's scalars (scale, clip, sharpness, complementarity, unmatched)
+
+    def types_kwargs(self, type_restraints):
+        """PfEngine.types_next's arguments of a guided batch (None: the call has no type guidance)"""
+        if self.types is None:
+            return None
+        scale, clip, sharp, comp, unmatched = self.types
+        return dict(restraints=type_restraints, scale=scale, clip=clip, sharpness=sharp, complementarity=comp, unmatched=unmatched)
 
     def batch(self, m, has_pins, guided):
         """One batch's run, given whether a pin flag is set in it and whether it is guided (a restraint in it, or a pocket field):
@@ -1015,7 +1039,8 @@ class PharmacophoreDiff(_Base):
                               noise: torch.Tensor = None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None,
                               guide_scale: float = 1.0, guide_clip: float = 0.0, seeds=None, seed_level: int = None,
                               seed_keep=None, sample_steps: int = None, sampler: str = None, eta: float = None,
-                              spacing: str = None, guide_family: str = "wide", pocket_field=None) -> List[SampledPharmacophore]:
+                              spacing: str = None, guide_family: str = "wide", pocket_field=None, type_restraints=None,
+                              type_guidance=None) -> List[SampledPharmacophore]:
         """Reverse diffusion for a batch of pocket graphs; the whole T-step loop is enqueued on the
         current HIP stream by pf_sample (no host synchronisation inside the loop).
 
@@ -1036,6 +1061,8 @@ class PharmacophoreDiff(_Base):
         ``sample``): with a restraint in it the run is pf_sample_guided with ``guide_scale`` / ``guide_clip``, on the kernel
         family ``guide_family`` names ('wide', the default, or 'tuned': see ``sample``).  ``pocket_field`` (a PocketField whose
         per-atom radii, if any, cover the batch's atoms): the run is guided also without restraints (see ``sample``).
+        ``type_restraints``: None, or one list (or None) per graph of the batch of (type, center, point, radius, weight), with
+        ``type_guidance`` (a TypeGuidance): the run steers the feature rows too (see ``sample``).
 
         ``seeds`` with ``seed_level`` a (and optionally ``seed_keep``): a seeded run (pf_sample_seed_next) -- one (x [n,3], types
         [n]) per graph of the batch, n that graph's number of centers; the run starts from the seeds noised to level a and makes
@@ -1045,17 +1072,21 @@ class PharmacophoreDiff(_Base):
         ``sample_steps`` N with ``sampler`` / ``eta`` / ``spacing``: a few-step run (see ``sample``) -- ``noise`` has N + 1 rows for
         the first-order samplers and 1 row for 'multistep'; trajectories have N + 1 frames."""
         g = as_pocket_graph(g)
-        spec = self._run_spec(pins=self._has_pins(g), guided=self._guided(restraints, pocket_field), pinned=g.pharm_pin is not None,
+        type_restraints = self._type_restraints(type_restraints, g.batch_size, "graphs")
+        spec = self._run_spec(pins=self._has_pins(g), guided=self._guided(restraints, pocket_field, type_restraints),
+                              pinned=g.pharm_pin is not None,
                               pin_resamples=pin_resamples, pin_jump=pin_jump, guide_scale=guide_scale, guide_clip=guide_clip,
                               seeds=seeds, seed_level=seed_level, seed_keep=seed_keep, sample_steps=sample_steps, sampler=sampler,
-                              eta=eta, spacing=spacing, guide_family=guide_family)
+                              eta=eta, spacing=spacing, guide_family=guide_family, pocket_field=pocket_field,
+                              type_guidance=type_guidance, typed=type_restraints is not None)
         if seeds is not None:
             sizes = (g.pharm_ptr[1:] - g.pharm_ptr[:-1]).tolist()
             fields = self._seed_fields([[n] for n in sizes], seeds, seed_keep, batch=True)
             g = self._with_pin_fields(g, *(torch.cat(f) for f in zip(*fields)))
         return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, spec, init_pharm_com, visualize_trajectory, noise,
                                                                            restraints=restraints,
-                                                                           field=self._field_for_batch(g, pocket_field))))
+                                                                           field=self._field_for_batch(g, pocket_field),
+                                                                           type_restraints=type_restraints)))
 
     @staticmethod
     def _has_pins(g):
@@ -1063,9 +1094,41 @@ class PharmacophoreDiff(_Base):
         return g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
 
     @staticmethod
-    def _guided(restraints, field):
-        """a pocket field, or a restraint in one of the per-pocket / per-graph lists (None or empty: none): what makes a run guided"""
-        return field is not None or (restraints is not None and any(restraints))
+    def _guided(restraints, field, type_restraints=None):
+        """a pocket field, or a restraint or type restraint in one of the per-pocket / per-graph lists (None or empty: none): what
+        makes a run guided"""
+        return (field is not None or (restraints is not None and any(restraints))
+                or (type_restraints is not None and any(type_restraints)))
+
+    def _type_index(self, t):
+        """a type restraint's type: an index, or a name of the model's ph_type_map"""
+        if isinstance(t, str):
+            if t not in self.ph_type_map:
+                raise ValueError(f"a type restraint names type {t!r}; this model's types are {list(self.ph_type_map)}")
+            return list(self.ph_type_map).index(t)
+        t = int(t)
+        if not 0 <= t < self.n_pharm_feats:
+            raise ValueError(f"a type restraint's type index must be in 0..{self.n_pharm_feats - 1}, got {t}")
+        return t
+
+    def _type_restraints(self, type_restraints, n, what):
+        """``type_restraints`` of sample / sample_given_receptor, checked before any device work: None when there is none, else one
+        list or None per pocket / graph of (type index, center or None, point, radius, weight)"""
+        if type_restraints is None:
+            return None
+        if len(type_restraints) != n:
+            raise ValueError(f"type_restraints lists {len(type_restraints)} entries for {n} {what}")
+        out = []
+        for rs in type_restraints:
+            rows = []
+            for row in (rs or []):
+                if len(row) != 5:
+                    raise ValueError(f"a type restraint is (type, center, point, radius, weight), got {row!r}")
+                t, c, p, r, w = row
+                rows.append((self._type_index(t), None if c is None or c == "*" or int(c) < 0 else int(c), tuple(float(v) for v in p),
+                             float(r), float(w)))
+            out.append(rows or None)
+        return out if any(out) else None
 
     @staticmethod
     def _with_pin_fields(g, flags, x, h):
@@ -1074,10 +1137,12 @@ class PharmacophoreDiff(_Base):
 
     def _run_spec(self, pins, guided, pinned=False, pin_resamples=1, pin_jump=10, guide_scale=1.0, guide_clip=0.0, seeds=None,
                   seed_level=None, seed_keep=None, score_levels=None, sample_steps=None, sampler=None, eta=None, spacing=None,
-                  guide_family="wide"):
+                  guide_family="wide", pocket_field=None, type_guidance=None, typed=False):
         """The RunSpec of one sample / sample_given_receptor call from its keywords; every rule on how they compose is applied
         here, once, before any device work.  The two callers differ in where they look: ``pins`` -- a pin is present (an entry of
-        ``pinned``; a flag set on the batched graph), ``guided`` (_guided), ``pinned`` -- pin fields were given at all."""
+        ``pinned``; a flag set on the batched graph), ``guided`` (_guided), ``pinned`` -- pin fields were given at all.  ``typed``: a type
+        restraint is present; ``type_guidance``: None or a TypeGuidance (``typed`` alone means TypeGuidance()); ``pocket_field``:
+        the call's, for the rules that tie the two."""
         if score_levels is not None and not 1 <= int(score_levels) <= self.n_timesteps:
             raise ValueError(f"score_levels must satisfy 1 <= K <= {self.n_timesteps}, got {score_levels}")
         self._check_guide_family(guide_family)
@@ -1087,6 +1152,24 @@ class PharmacophoreDiff(_Base):
             raise ValueError(f"pin_resamples and pin_jump must be at least 1, got {pin_resamples} and {pin_jump}")
         if guided and pin_resamples > 1:
             raise ValueError("restraints together with pin_resamples > 1: guidance with resampling jumps is not supported")
+        types = None
+        if type_guidance is not None or typed:
+            tg = TypeGuidance() if type_guidance is None else type_guidance
+            if not isinstance(tg, TypeGuidance):
+                raise ValueError(f"type_guidance must be a TypeGuidance, got {type(tg).__name__}")
+            field_sharp = None if pocket_field is None else float(getattr(pocket_field, "type_sharpness", 4.0))
+            sharp = float(tg.sharpness) if tg.sharpness is not None else 4.0 if field_sharp is None else field_sharp
+            if field_sharp is not None and sharp != field_sharp:
+                raise ValueError(f"type_guidance.sharpness ({sharp}) and pocket_field.type_sharpness ({field_sharp}) must agree")
+            if tg.complementarity and not (pocket_field is not None and float(getattr(pocket_field, "comp_weight", 0.0)) > 0):
+                raise ValueError("type_guidance.complementarity needs a pocket_field with comp_weight > 0")
+            for name in ("scale", "clip", "unmatched"):
+                if not float(getattr(tg, name)) >= 0:
+                    raise ValueError(f"type_guidance.{name} must be >= 0, got {getattr(tg, name)}")
+            if not sharp >= 0:
+                raise ValueError(f"type_guidance.sharpness must be >= 0, got {sharp}")
+            types = (float(tg.scale), float(tg.clip), sharp * float(self.pharm_feat_norm_constant), bool(tg.complementarity),
+                     float(tg.unmatched))
         if (seeds is None) != (seed_level is None):
             raise ValueError("seeds and seed_level go together: a seeded run needs both")
         if seeds is None and seed_keep is not None:
@@ -1096,7 +1179,7 @@ class PharmacophoreDiff(_Base):
         T = int(self.n_timesteps)
         return RunSpec(T=T, top=T if seeds is None else self._check_seed_level(seed_level), seeded=seeds is not None, fewstep=fewstep,
                        pin_resamples=int(pin_resamples), pin_jump=int(pin_jump), guide_scale=float(guide_scale),
-                       guide_clip=float(guide_clip), guide_family=guide_family, guided=bool(guided))
+                       guide_clip=float(guide_clip), guide_family=guide_family, guided=bool(guided), types=types)
 
     def _field_for_batch(self, g, pocket_field, radii=None):
         """PfEngine.field_next's arguments for a batched graph and a PocketField (None: None), checked before any device work.
@@ -1281,7 +1364,7 @@ class PharmacophoreDiff(_Base):
         return [self._with_pin_fields(g, *f) for g, f in zip(ref_graphs, self._seed_fields(n_pharms, seeds, seed_keep))]
 
     def _sample_enqueue(self, g, spec, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0, restraints=None,
-                        field=None, generator=None):
+                        field=None, generator=None, type_restraints=None):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
         current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  What runs is ``spec``'s answer
         for this batch (RunSpec.batch): a pin flag set on the graph makes it pinned, a restraint in ``restraints`` (None or one
@@ -1290,7 +1373,7 @@ class PharmacophoreDiff(_Base):
         torch.randn on the model's device from ``generator``."""
         g = as_pocket_graph(g)
         dev = self.device
-        guided = self._guided(restraints, field)
+        guided = self._guided(restraints, field, type_restraints)
         kind, n_ops, rows, arr, kw = spec.batch(self, self._has_pins(g), guided)
         if noise is not None and noise.shape[0] != rows:
             if spec.fewstep is not None:
@@ -1312,6 +1395,11 @@ class PharmacophoreDiff(_Base):
             kw["restraints"] = restraints
             if field is not None:
                 kw["field"] = field
+            if type_restraints is not None and len(type_restraints) != g.batch_size:
+                raise ValueError(f"type_restraints lists {len(type_restraints)} entries for a batch of {g.batch_size} graphs")
+            types = spec.types_kwargs(type_restraints)      # (every guided batch of a call with type guidance carries it)
+            if types is not None:
+                kw["types"] = types
         if noise is None:
             noise = torch.randn(rows, g.num_nodes("pharm"), 3 + self.n_pharm_feats, device=dev, generator=generator)
         if lane == 0:
@@ -1391,7 +1479,8 @@ class PharmacophoreDiff(_Base):
                pinned=None, pin_resamples: int = 1, pin_jump: int = 10, restraints=None, guide_scale: float = 1.0,
                guide_clip: float = 0.0, seeds=None, seed_level: int = None, seed_keep=None,
                score_levels: int = None, sample_steps: int = None, sampler: str = None, eta: float = None,
-               spacing: str = None, guide_family: str = "wide", pocket_field=None) -> List[List[SampledPharmacophore]]:
+               spacing: str = None, guide_family: str = "wide", pocket_field=None, type_restraints=None,
+               type_guidance=None) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -1429,7 +1518,18 @@ class PharmacophoreDiff(_Base):
         receptor features, added to the restraints' energy.  EVERY batch then runs guided, with or without
         restraints; it composes with ``pinned``, ``restraints``, ``seeds`` and ``sample_steps`` with 'ancestral' / 'ddim', and is
         refused like restraints with sampler 'multistep' and with ``pin_resamples`` > 1.  ``comp_weight`` > 0 on graphs without
-        prot_ph_x / prot_ph_h is a ValueError.  Coordinates only: features stay unguided.
+        prot_ph_x / prot_ph_h is a ValueError.  On its own it steers coordinates only.
+
+        ``type_restraints``: None, or one entry per pocket -- None or a list of (type, center, point, radius, weight): type a name
+        of the model's ph_type_map or an index, center a center index or None for every center, point in the pocket's frame,
+        radius 0 for no spatial condition (pocket_io.parse_type_restraints reads them from text).  Inside the sphere a center
+        takes that type or is pushed out; together with an 'attract' restraint on the same sphere: "a center of this
+        type within radius of point".  Copies of a pocket share its type restraints; a batch with one runs guided.
+        ``type_guidance``: None or a TypeGuidance -- scale, clip and sharpness of the feature guidance, and ``complementarity``:
+        the pocket field's complementarity energy steers the types too (without a ``pocket_field`` with comp_weight > 0 a
+        ValueError).  Every guided batch of a call with type guidance carries it.  Composes with ``pinned`` (a type-pinned center
+        keeps its type), ``restraints``, ``pocket_field``, ``seeds``, first-order ``sample_steps`` and both ``guide_family``
+        values; refused like restraints with sampler 'multistep' and with ``pin_resamples`` > 1.
 
         ``seeds`` with ``seed_level`` a, 1 <= a <= T: variations of given pharmacophores (partial diffusion, pf_sample_seed_next)
         -- one (x [n,3], types [n]) per pocket, every pocket must have one and every requested size of it must equal n.  Each
@@ -1457,11 +1557,20 @@ class PharmacophoreDiff(_Base):
         ``score_levels`` K: every returned SampledPharmacophore carries ``.score``, the PharmacophoreScore of its final frame at K
         stratified levels (score(), uniform weighting, seed 0) -- a second pass behind the sampling, which it leaves bit for bit
         as it is without.  None (the default): no scoring, ``.score`` stays None."""
+        type_restraints = self._type_restraints(type_restraints, len(ref_graphs), "pockets")
         spec = self._run_spec(pins=pinned is not None and any(p is not None for p in pinned),
-                              guided=self._guided(restraints, pocket_field), pinned=pinned is not None, pin_resamples=pin_resamples,
+                              guided=self._guided(restraints, pocket_field, type_restraints), pinned=pinned is not None,
+                              pin_resamples=pin_resamples,
                               pin_jump=pin_jump, guide_scale=guide_scale, guide_clip=guide_clip, seeds=seeds, seed_level=seed_level,
                               seed_keep=seed_keep, score_levels=score_levels, sample_steps=sample_steps, sampler=sampler, eta=eta,
-                              spacing=spacing, guide_family=guide_family)
+                              spacing=spacing, guide_family=guide_family, pocket_field=pocket_field, type_guidance=type_guidance,
+                              typed=type_restraints is not None)
+        for r, rs in enumerate(type_restraints or []):
+            for _, c, _, _, _ in (rs or []):
+                if c is not None:
+                    small = [int(n) for n in n_pharms[r] if int(n) <= c]
+                    if small:
+                        raise ValueError(f"pocket {r}: a type restraint names center {c} but sizes {small} were requested")
         scored_graphs = ref_graphs
         from .sharding import shard_by_work
         ref_graphs = [as_pocket_graph(g) for g in ref_graphs]
@@ -1559,8 +1668,9 @@ class PharmacophoreDiff(_Base):
                 # the bind is asynchronous (stream-ordered behind the lane's previous batch), nothing here waits for the device
                 batch_r = [restraints[graph_ref_idx[i]] for i in idx] if restraints is not None else None
                 field = self._field_for_batch(batch_g, pocket_field, None if radii is None else [radii[graph_ref_idx[i]] for i in idx])
+                batch_t = [type_restraints[graph_ref_idx[i]] for i in idx] if type_restraints is not None else None
                 enq = self._sample_enqueue(batch_g, spec, init_coms, visualize_trajectory, None if noise is None else noise[bi],
-                                           lane=lane, restraints=batch_r, field=field, generator=gen)
+                                           lane=lane, restraints=batch_r, field=field, generator=gen, type_restraints=batch_t)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on

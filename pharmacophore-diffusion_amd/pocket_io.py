@@ -391,3 +391,52 @@ def parse_restraints(text: str, source: str = "restraints"):
 def read_restraints(path):
     with open(path) as f:
         return parse_restraints(f.read(), source=str(path))
+
+
+def parse_type_restraints(text: str, source: str = "type restraints"):
+    """One type restraint per line: ``type NAME|INDEX x y z radius weight [center|*]`` -- the feature type asked for (a name of the
+    model's type map or an index), a point in the receptor's frame (angstroms), the radius of the sphere around it (0: no spatial
+    condition), the weight of the energy, and the index of the center it applies to (default ``*``: every center).  ``#`` starts a
+    comment; blank lines are skipped.  Returns [(type, center or None, (x, y, z), radius, weight)], the form
+    PharmacophoreDiff.sample(type_restraints=...) takes per pocket (a name stays a string: the model resolves it).  Errors carry the
+    line number."""
+    import math
+    out = []
+    for no, raw in enumerate(text.splitlines(), 1):
+        line = raw.split("#", 1)[0].strip()
+        if not line:
+            continue
+        tok = line.split()
+        where = f"{source}, line {no}"
+        if tok[0] != "type":
+            raise ValueError(f"{where}: a type restraint starts with 'type', got {tok[0]!r}")
+        if len(tok) not in (7, 8):
+            raise ValueError(f"{where}: expected 'type NAME|INDEX x y z radius weight [center|*]', got {len(tok)} fields")
+        ty = tok[1]
+        if ty.lstrip("+-").isdigit():
+            ty = int(ty)
+            if ty < 0:
+                raise ValueError(f"{where}: the type index must not be negative, got {ty}")
+        try:
+            x, y, z, r, w = (float(v) for v in tok[2:7])
+        except ValueError:
+            raise ValueError(f"{where}: x y z radius weight must be numbers, got {' '.join(tok[2:7])!r}") from None
+        if not all(math.isfinite(v) for v in (x, y, z, r, w)):
+            raise ValueError(f"{where}: x y z radius weight must be finite")
+        if r < 0 or w < 0:
+            raise ValueError(f"{where}: radius and weight must not be negative, got {r:g} and {w:g}")
+        center = None
+        if len(tok) == 8 and tok[7] != "*":
+            try:
+                center = int(tok[7])
+            except ValueError:
+                raise ValueError(f"{where}: the center is an index or '*', got {tok[7]!r}") from None
+            if center < 0:
+                raise ValueError(f"{where}: the center index must not be negative, got {center}")
+        out.append((ty, center, (x, y, z), r, w))
+    return out
+
+
+def read_type_restraints(path):
+    with open(path) as f:
+        return parse_type_restraints(f.read(), source=str(path))

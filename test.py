@@ -45,6 +45,12 @@ _FLAGS = [
     ('--guide_scale', dict(type=float, default=None, help='with --avoid_clashes or --guide_complementarity: strength of the guidance (default 1)')),
     ('--guide_clip', dict(type=float, default=None, help='with --avoid_clashes or --guide_complementarity: largest shift of a center per step in angstroms (default 0: no clip)')),
     ('--guide_family', dict(choices=['wide', 'tuned'], default=None, help='with --avoid_clashes or --guide_complementarity: the kernels of a guided step (wide: every model width, the default; tuned: models of n_hidden_scalars 128 / vector_size 16)')),
+    ('--type_restraints', dict(type=Path, default=None, help='guided sampling of the types: a text file with one type restraint per line, "type NAME|INDEX x y z radius weight [center|*]" (# starts a comment), applied to every pocket in its own frame (radius 0: no spatial condition)')),
+    ('--guide_type_scale', dict(type=float, default=None, help='with --type_restraints or --guide_complementarity_types: strength of the guidance of the feature rows (default 1)')),
+    ('--guide_type_clip', dict(type=float, default=None, help='with --type_restraints or --guide_complementarity_types: largest Euclidean norm of a feature row\'s shift per step (default 0: no clip)')),
+    ('--type_sharpness', dict(type=float, default=None, help='with --type_restraints or --guide_complementarity_types: sharpness of the soft type assignment on one-hot-scaled features (default 4)')),
+    ('--guide_complementarity_types', dict(action='store_true', help='with --guide_complementarity: the complementarity energy steers the centers\' types too, so that a center next to an acceptor can become a donor')),
+    ('--comp_unmatched', dict(type=float, default=None, metavar='U', help='with --guide_complementarity_types: what a type without any partner in the pocket costs, as a distance beyond its matching distance (default 0)')),
     ('--pockets_per_call', dict(type=int, default=64, help='pockets whose samples are batched together (not in the reference)')),
     ('--use_ema', dict(action='store_true', help="sample from the checkpoint's EMA weights ('ema_state_dict') instead of the training weights")),
 ]
@@ -65,10 +71,36 @@ def parse_arguments(argv=None):
         raise ValueError(f'--sample_steps must be at least 1, got {a.sample_steps}')
     if a.eta is not None and (a.sampler != 'ddim' or not 0.0 <= a.eta <= 1.0):
         raise ValueError('--eta needs --sampler ddim and a value in 0..1')
-    guided = a.avoid_clashes is not None or a.guide_complementarity is not None
+    typed = a.type_restraints is not None or a.guide_complementarity_types
+    guided = a.avoid_clashes is not None or a.guide_complementarity is not None or a.type_restraints is not None
+    for flag in ('guide_type_scale', 'guide_type_clip', 'type_sharpness'):
+        if getattr(a, flag) is not None and not typed:
+            raise ValueError(f'--{flag} needs --type_restraints or --guide_complementarity_types')
+    if a.guide_complementarity_types and not (a.guide_complementarity is not None and a.guide_complementarity > 0):
+        raise ValueError('--guide_complementarity_types needs --guide_complementarity with a positive weight')
+    if a.comp_unmatched is not None and not a.guide_complementarity_types:
+        raise ValueError('--comp_unmatched needs --guide_complementarity_types')
+    for flag in ('guide_type_scale', 'guide_type_clip', 'type_sharpness', 'comp_unmatched'):
+        v = getattr(a, flag)
+        if v is not None and not (v >= 0 and v < float('inf')):
+            raise ValueError(f'--{flag} must be finite and not negative, got {v}')
+    a.type_restraint_list, a.type_guidance = None, None
+    if a.type_restraints is not None:
+        from pharmacoforge_amd.pocket_io import read_type_restraints
+        a.type_restraint_list = read_type_restraints(a.type_restraints)
+        named = [c for _, c, _, _, _ in a.type_restraint_list if c is not None]
+        small = [n for n in (a.pharm_sizes or []) if named and n <= max(named)]
+        if small:
+            raise ValueError(f'--pharm_sizes {small} do not reach center {max(named)} named in --type_restraints')
+    if typed:
+        a.type_guidance = dict(scale=1.0 if a.guide_type_scale is None else a.guide_type_scale,
+                               clip=0.0 if a.guide_type_clip is None else a.guide_type_clip,
+                               sharpness=4.0 if a.type_sharpness is None else a.type_sharpness,
+                               complementarity=bool(a.guide_complementarity_types),
+                               unmatched=0.0 if a.comp_unmatched is None else a.comp_unmatched)
     for flag in ('guide_scale', 'guide_clip', 'guide_family'):
         if getattr(a, flag) is not None and not guided:
-            raise ValueError(f'--{flag} needs --avoid_clashes or --guide_complementarity')
+            raise ValueError(f'--{flag} needs --avoid_clashes, --guide_complementarity or --type_restraints')
     if a.clash_weight is not None and a.avoid_clashes is None:
         raise ValueError('--clash_weight needs --avoid_clashes')
     for flag in ('avoid_clashes', 'clash_weight', 'guide_complementarity', 'guide_scale', 'guide_clip'):
@@ -76,9 +108,9 @@ def parse_arguments(argv=None):
         if v is not None and not (v >= 0 and v < float('inf')):
             raise ValueError(f'--{flag} must be finite and not negative, got {v}')
     if guided and a.sampler == 'multistep':
-        raise ValueError('--sampler multistep takes no guidance: no --avoid_clashes or --guide_complementarity')
+        raise ValueError('--sampler multistep takes no guidance: no --avoid_clashes, --guide_complementarity or --type_restraints')
     a.pocket_field = None
-    if guided:
+    if a.avoid_clashes is not None or a.guide_complementarity is not None:
         a.pocket_field = dict(clash_radius=a.avoid_clashes, clash_weight=1.0 if a.clash_weight is None else a.clash_weight,
                               comp_weight=0.0 if a.guide_complementarity is None else a.guide_complementarity)
     a.guide_scale = 1.0 if a.guide_scale is None else a.guide_scale
@@ -173,7 +205,9 @@ def main(argv=None):
                                       visualize_trajectory=args.visualize_trajectory, sample_steps=args.sample_steps,
                                       sampler=args.sampler, eta=args.eta, spacing=args.spacing,
                                       pocket_field=None if args.pocket_field is None else pfa.PocketField(**args.pocket_field),
-                                      guide_scale=args.guide_scale, guide_clip=args.guide_clip, guide_family=args.guide_family)
+                                      guide_scale=args.guide_scale, guide_clip=args.guide_clip, guide_family=args.guide_family,
+                                      type_restraints=[args.type_restraint_list] * len(graphs) if args.type_restraint_list else None,
+                                      type_guidance=None if args.type_guidance is None else pfa.TypeGuidance(**args.type_guidance))
         seconds = (time.time() - t0) / len(chunk)
         for idx, pharms in zip(chunk, per_pocket):
             write_pocket(out_root, dataset, idx, pharms, seconds, args.visualize_trajectory)
@@ -183,6 +217,11 @@ def main(argv=None):
                 cl = [clash_energy(ph.ph_coords, ph.g.prot_x, args.avoid_clashes, args.pocket_field['clash_weight']) for ph in pharms]
                 print(f'pocket {idx}: clash energy per sample ' + ' '.join(f'{e:.3g}' for e, _ in cl)
                       + '; clashing pairs ' + ' '.join(str(c) for _, c in cl), flush=True)
+            if args.type_restraint_list and rank == 0:             # the final type energy of every sample
+                from pharmacoforge_amd.analysis import type_restraint_energy
+                rows = [(model._type_index(t), c, p, r, w) for t, c, p, r, w in args.type_restraint_list]
+                te = [type_restraint_energy(ph.ph_coords, ph.g.pharm_h0, rows, args.type_guidance['sharpness']) for ph in pharms]
+                print(f'pocket {idx}: type energy per sample ' + ' '.join(f'{e:.3g}' for e in te), flush=True)
         if rank == 0:
             print(f'pockets {chunk[0]}..{chunk[-1]}: {seconds:.3f} s per pocket, '
                   f'{seconds / max(args.samples_per_pocket, 1):.4f} s per pharmacophore', flush=True)
