@@ -299,7 +299,7 @@ int pf_sample_pinned_resampled(pf_handle* h, int32_t n_ops, const int32_t* host_
  * runs stay on the tuned kernels.  pf_sample_begin_guided takes pf_sample_begin_pinned's arguments and HOST arrays restr_ptr[B+1]
  * (graph g owns restraints [restr_ptr[g], restr_ptr[g+1])), restr_kind[n], restr_center[n], restr_p[n][3], restr_r[n], restr_w[n].
  * Everything is validated on the host before anything is enqueued (kind, center range, finite p, r / w / scale / clip >= 0, at most
- * 256 restraints per graph): a failure is PF_ERR_ARG and leaves the handle as it was.  The restraints travel through a pinned
+ * 256 restraints per graph; csrc/pf_restr.h): a failure is PF_ERR_ARG and leaves the handle as it was.  The restraints travel through a pinned
  * staging buffer into one allocation of the handle, kept and grown like the pin arrays; the host arrays may be freed on return.
  * A guided run ends at the next begin of any kind or the next bind.  Inside it pf_denoise_step, pf_denoise_step_pinned and
  * pf_renoise_step return PF_ERR_STATE (guidance with resampling jumps is not supported), and so does pf_denoise_step_guided outside

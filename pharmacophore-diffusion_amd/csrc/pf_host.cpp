@@ -23,6 +23,7 @@
 #include "pf_score.h"
 #include "pf_optim.h"
 #include "pf_field.h"
+#include "pf_restr.h"
 #include "pf_types.h"
 
 using namespace pfpack;
@@ -248,6 +249,10 @@ struct LaunchPolicy {
 // which sampling run is in progress on a handle (run_guard: what each entry point accepts)
 enum RunKind { RUN_NONE = 0, RUN_PLAIN, RUN_PINNED, RUN_GUIDED };
 
+// A block of host arrays that a guided begin uploads in one copy (the restraints, the pocket field, type guidance): packed into pinned
+// memory in the device layout, then copied into one device allocation, kept and grown like d_pin.  ev: the last upload out of `stage`
+struct StagedBlock { void* stage = nullptr; size_t stage_capacity = 0; hipEvent_t ev = nullptr; void* dev = nullptr; size_t capacity = 0; };
+
 struct pf_handle {
     LaunchPolicy pol;
     pf_config cfg{};
@@ -412,40 +417,33 @@ struct pf_handle {
     // buffer holds that step's outputs; cleared by every begin, every bind and every other move
     void* d_ms_hist = nullptr; size_t ms_hist_capacity = 0;
     bool ms_hist_valid = false;
-    // guided run (pf_sample_begin_guided): a pinned run plus restraint energies per graph.  The restraints are staged in pinned host
-    // memory (restr_ev: the last upload that reads the staging buffer) and live in one device allocation, kept and grown like d_pin:
-    // restr_ptr [B + 1], kind [n], center [n], p [n][3], r [n], w [n].  d_guide: what a guided step leaves -- g0, J(g0), grad, shift
-    // [Nf][3] each, the zero g_eps_h [Nf][pharm_nf], E [B], D [B][3]
-    void* d_restr = nullptr; size_t restr_capacity = 0;
-    void* restr_stage = nullptr; size_t restr_stage_capacity = 0; hipEvent_t restr_ev = nullptr;
+    // guided run (pf_sample_begin_guided): a pinned run plus restraint energies per graph.  restr: the restraint block (pf_restr.h),
+    // packed at begin.  d_guide: what a guided step leaves (pf_restr.h: GuideWork), kept and grown like d_pin
+    StagedBlock restr;
     int n_restr = 0;
     float guide_scale = 0.f, guide_clip = 0.f;
     void* d_guide = nullptr; size_t guide_capacity = 0;
-    float *d_g0 = nullptr, *d_gjx = nullptr, *d_ggrad = nullptr, *d_gshift = nullptr, *d_gzero = nullptr, *d_genergy = nullptr, *d_gD = nullptr;
     bool guide_wide = true, guide_in_grads = false;   // the training family and the input-gradient switch the guided run began on
     bool guide_have = false;                // a guided step has run on this batch: pf_debug_last_guidance has something to return
     float* guide_traj_energy = nullptr;     // pf_sample_guided: row i of the caller's [n_steps][B] for the step in flight
     // pocket field (pf_guide_field_next): clash and complementarity energies next to a guided run's restraints.  Arming validates
-    // and packs the caller's host arrays into pinned memory in the block's layout (pf_field.h; field_ev: the last upload that read
-    // the staging buffer); the next pf_sample_begin_guided uploads it into one device allocation, kept and grown like d_restr, and
-    // the run's steps launch k_guide_field behind k_guide_grad.  field_arm: what is armed; field_run: what the run in progress uses
-    struct FieldScalars { int n = 0; float w_clash = 0.f, w_comp = 0.f, kappa = 1.f, type_sharpness = 0.f; };
-    void* field_stage = nullptr; size_t field_stage_capacity = 0; hipEvent_t field_ev = nullptr;
-    void* d_field = nullptr; size_t field_capacity = 0;
-    bool field_armed = false, field_on = false;
-    bool field_have = false;                // the last guided step on this batch launched k_guide_field: pf_debug_last_field
-    FieldScalars field_arm, field_run;
+    // and packs the caller's host arrays into the block's staging buffer in its layout (pf_field.h); the next pf_sample_begin_guided
+    // uploads it, and the run's steps launch k_guide_field behind k_guide_grad.  armed: the next guided begin takes `arm`; on: the
+    // run in progress uses `run`; have: the last guided step on this batch launched k_guide_field (pf_debug_last_field)
+    struct FieldSource {
+        StagedBlock blk; bool armed = false, on = false, have = false;
+        struct Scalars { int n = 0; float w_clash = 0.f, w_comp = 0.f, kappa = 1.f, type_sharpness = 0.f; } arm, run;
+    } field;
     // type guidance (pf_guide_types_next): typed restraints on the predicted clean feature rows, the complementarity energy's
     // feature gradient and the feature shift of the step end.  Armed, staged (pf_types.h) and uploaded like the pocket field.
-    // d_tguide: what an armed step leaves -- g0_h, gs_h = (phi_h / phi_x) g0_h, J_h, grad_h, shift_h [Nf][pharm_nf] each, E_type [B]
-    struct TypeScalars { int n = 0; float feat_scale = 0.f, feat_clip = 0.f, type_sharpness = 0.f; bool comp = false; float unmatched = 0.f; };
-    void* types_stage = nullptr; size_t types_stage_capacity = 0; hipEvent_t types_ev = nullptr;
-    void* d_types = nullptr; size_t types_capacity = 0;
-    void* d_tguide = nullptr; size_t tguide_capacity = 0;
-    bool types_armed = false, types_on = false;
-    bool types_live = false;                // that step's launches wrote g0_h / E_type (else they are zeros)
-    bool types_have = false;                // the last guided step on this batch ran with type guidance: pf_debug_last_type_guidance
-    TypeScalars types_arm, types_run;
+    // d_tguide: what an armed step leaves (pf_restr.h: TypeWork).  have: the last guided step on this batch ran with type guidance
+    // (pf_debug_last_type_guidance); live: that step's launches wrote g0_h / E_type (else they are zeros)
+    struct TypesSource {
+        StagedBlock blk;
+        void* d_tguide = nullptr; size_t tguide_capacity = 0;
+        bool armed = false, on = false, have = false, live = false;
+        struct Scalars { int n = 0; float feat_scale = 0.f, feat_clip = 0.f, type_sharpness = 0.f; bool comp = false; float unmatched = 0.f; } arm, run;
+    } types;
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
@@ -1544,6 +1542,8 @@ int pf_create(const pf_config* cfg, pf_handle** out) {
     return PF_OK;
 }
 
+static void staged_free(StagedBlock& b) { if (b.dev) (void)hipFree(b.dev); if (b.stage) (void)hipHostFree(b.stage); if (b.ev) (void)hipEventDestroy(b.ev); }
+
 void pf_destroy(pf_handle* h) {
     if (!h) return;
     free_ws(h);
@@ -1558,19 +1558,11 @@ void pf_destroy(pf_handle* h) {
     if (h->d_pin) (void)hipFree(h->d_pin);
     if (h->d_seed) (void)hipFree(h->d_seed);
     if (h->d_ms_hist) (void)hipFree(h->d_ms_hist);
-    if (h->d_restr) (void)hipFree(h->d_restr);
     if (h->d_guide) (void)hipFree(h->d_guide);
     if (h->d_gdiff) (void)hipFree(h->d_gdiff);
     if (h->d_optim_part) (void)hipFree(h->d_optim_part);
-    if (h->restr_stage) (void)hipHostFree(h->restr_stage);
-    if (h->restr_ev) (void)hipEventDestroy(h->restr_ev);
-    if (h->d_field) (void)hipFree(h->d_field);
-    if (h->field_stage) (void)hipHostFree(h->field_stage);
-    if (h->field_ev) (void)hipEventDestroy(h->field_ev);
-    if (h->d_types) (void)hipFree(h->d_types);
-    if (h->d_tguide) (void)hipFree(h->d_tguide);
-    if (h->types_stage) (void)hipHostFree(h->types_stage);
-    if (h->types_ev) (void)hipEventDestroy(h->types_ev);
+    for (StagedBlock* b : {&h->restr, &h->field.blk, &h->types.blk}) staged_free(*b);
+    if (h->types.d_tguide) (void)hipFree(h->types.d_tguide);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
     for (int k = 0; k < 2; ++k) {
         if (h->d_tab[k]) (void)hipFree(h->d_tab[k]);
@@ -1737,6 +1729,15 @@ static void set_batch_pointers(pf_handle* h, const pfbind::BindPlan& p, char* ba
     h->d_pa_cnt = (int*)at(oz.pacnt); h->d_pa_gstamp = h->pa_check ? (int*)at(oz.pagst) : nullptr;
 }
 
+// ---- what arms the next begin (a seed: any begin; a pocket field and type guidance: a guided begin) and what a run leaves ----
+// take: every public begin takes each arming off the handle on entry, before it can reject anything.  A bind drops every arming,
+// rejected or not, and ends with no guided run on the batch (no source on, nothing for the pf_debug_last_* readers); a plain
+// begin ends the guidance sources with their run
+static bool take(bool& armed) { const bool was = armed; armed = false; return was; }
+static void drop_armings(pf_handle* h) { h->seed_armed = h->field.armed = h->types.armed = false; }
+static void no_guided_run(pf_handle* h) { h->guide_have = h->field.on = h->field.have = h->types.on = h->types.have = false; }
+static void end_guidance_sources(pf_handle* h) { h->field.on = h->types.on = false; }
+
 // prot_x / prot_h come either as device pointers (copied on the stream) or as host pointers (staged with the tables).
 // The arithmetic is pf_bind.cpp's (host only, checked on the CPU by tests/bind_check.cpp); this function owns the handle,
 // the HIP resources and the enqueueing.
@@ -1747,9 +1748,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     // can fail, so that a rejected bind never leaves it behind for the next, unrelated batch
     pfbind::BindInputs in;
     if (h) in.rep.swap(h->pending_rep);
-    if (h) h->seed_armed = false;               // (so does a seed: pf_sample_seed_next comes after the bind it is for)
-    if (h) h->field_armed = false;              // (and a pocket field: its arrays are sized by the batch it was armed on)
-    if (h) h->types_armed = false;              // (and type guidance: its restraints name this batch's centers)
+    if (h) drop_armings(h);                     // (so do a seed, a pocket field and type guidance: they are sized by and name the batch they came behind)
     if (h) h->ms_hist_valid = false;            // (and the multistep history: it belongs to a run on the batch before)
     int rc = check_ready(h, false);
     if (rc) return rc;
@@ -1903,9 +1902,7 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     if (fr.host_onehot >= 0) { h->l0_state = fr.host_onehot ? 1 : 2; h->l0_onehot = fr.host_onehot == 1; }
     h->zs_version = 0; h->zs_batch_coords = false; h->coords_custom = false;
     h->have_batch = true;
-    h->run = RUN_NONE; h->guide_have = false;
-    h->field_on = false; h->field_have = false;
-    h->types_on = false; h->types_have = false;
+    h->run = RUN_NONE; no_guided_run(h);
     h->edges_built = false; h->rec_valid = false;
     return PF_OK;
 }
@@ -1915,7 +1912,7 @@ int pf_set_pocket_batch(pf_handle* h, int32_t B, const int32_t* prot_ptr, const 
                         const int32_t* pp_dst, pf_stream stream) {
     if (h && (!dev_prot_x || !dev_prot_h)) {
         h->pending_rep.clear();                  // a pocket-group claim never outlives the bind it was made for, rejected or not
-        h->seed_armed = false; h->field_armed = false; h->types_armed = false;
+        drop_armings(h);
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch: bad argument");
     }
     return set_pocket_batch_impl(h, B, prot_ptr, pharm_ptr, dev_prot_x, dev_prot_h, nullptr, nullptr, n_pp, pp_src, pp_dst, stream);
@@ -1926,7 +1923,7 @@ int pf_set_pocket_batch_host(pf_handle* h, int32_t B, const int32_t* prot_ptr, c
                              const int32_t* pp_dst, pf_stream stream) {
     if (h && (!host_prot_x || !host_prot_h)) {
         h->pending_rep.clear();
-        h->seed_armed = false; h->field_armed = false; h->types_armed = false;
+        drop_armings(h);
         PF_FAIL(h, PF_ERR_ARG, "pf_set_pocket_batch_host: bad argument");
     }
     return set_pocket_batch_impl(h, B, prot_ptr, pharm_ptr, nullptr, nullptr, host_prot_x, host_prot_h, n_pp, pp_src, pp_dst, stream);
@@ -2008,29 +2005,11 @@ int pf_dynamics_forward(pf_handle* h, const float* dev_prot_x, const float* dev_
     return run_dynamics(h, dev_eps_h, dev_eps_x, s);
 }
 
-// Seeded begin (pf_sample_seed_next): the seed arms the NEXT begin of any kind.  Every public begin takes it off the handle on
-// entry -- before it can reject anything -- and hands `seeded` down to the begin it is built on
-static bool take_seed(pf_handle* h) {
-    const bool armed = h && h->seed_armed;
-    if (h) h->seed_armed = false;
-    return armed;
-}
 static int seed_move(pf_handle* h, const float* dev_noise0, hipStream_t s);
-// Pocket field (pf_guide_field_next): it arms the next GUIDED begin, which takes it off the handle on entry like a seed; the begin
-// of any other run kind drops it and says so
-static bool take_field(pf_handle* h) {
-    const bool armed = h && h->field_armed;
-    if (h) h->field_armed = false;
-    return armed;
-}
-// Type guidance (pf_guide_types_next): armed, taken and refused like the pocket field
-static bool take_types(pf_handle* h) {
-    const bool armed = h && h->types_armed;
-    if (h) h->types_armed = false;
-    return armed;
-}
+// A pocket field and type guidance arm the next GUIDED begin; the begin of any other run kind drops them and says so.  (A seed
+// arms the next begin of any kind, which hands `seeded` down to the begin it is built on)
 static int refuse_field(pf_handle* h, const char* who) {
-    const bool fielded = take_field(h), typed = take_types(h);
+    const bool fielded = h && take(h->field.armed), typed = h && take(h->types.armed);
     if (fielded) PF_FAIL(h, PF_ERR_STATE, "%s while a pocket field is armed (pf_guide_field_next arms pf_sample_begin_guided / pf_sample_guided "
                                           "only): the arming is dropped", who);
     if (typed) PF_FAIL(h, PF_ERR_STATE, "%s while type guidance is armed (pf_guide_types_next arms pf_sample_begin_guided / pf_sample_guided "
@@ -2065,15 +2044,14 @@ static int begin_plain(pf_handle* h, const float* dev_init_pharm_com, const floa
     }
     h->coords_custom = false;               // a rigid translate of the batch's own coordinates from here on
     h->run = RUN_PLAIN;
-    h->field_on = false;                    // a pocket field ends with its run
-    h->types_on = false;                    // (and type guidance)
+    end_guidance_sources(h);
     h->ms_hist_valid = false;               // a run begins without a previous output
     h->edges_built = false; h->rec_valid = false;
     // a seeded begin: the state is the noised seed, made by a move of the step end (which also writes the snapshot, after the move)
     return seeded ? seed_move(h, dev_noise0, s) : PF_OK;
 }
 int pf_sample_begin(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, pf_stream stream) {
-    const bool seeded = take_seed(h);
+    const bool seeded = h && take(h->seed_armed);
     if (const int rc = refuse_field(h, "pf_sample_begin")) return rc;
     return begin_plain(h, dev_init_pharm_com, dev_noise0, seeded, stream);
 }
@@ -2207,7 +2185,7 @@ static int seed_move(pf_handle* h, const float* dev_noise0, hipStream_t s) {
     return step_end(h, sp, StepMove{StepMove::SEED, true, nullptr, nullptr, nullptr, 0, &q}, s);
 }
 
-// A run's device scratch (d_pin, d_restr, d_guide, d_seed): kept while `need` bytes fit, else replaced by one of `want` bytes.  Launches
+// A run's device scratch (d_pin, d_guide, d_seed, a staged block's device buffer): kept while `need` bytes fit, else replaced by one of `want` bytes.  Launches
 // of an earlier run on this stream may still read it, so replacing it waits for the caller's STREAM -- not for the device as
 // grow_buffer does: several lanes sample on one device at once
 static int grow_run_scratch(pf_handle* h, void** buf, size_t* cap, size_t need, size_t want, hipStream_t s) {
@@ -2215,6 +2193,22 @@ static int grow_run_scratch(pf_handle* h, void** buf, size_t* cap, size_t need, 
     if (*buf) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(*buf)); *buf = nullptr; *cap = 0; }
     PF_HIP(h, hipMalloc(buf, want));
     *cap = want;
+    return PF_OK;
+}
+// A StagedBlock.  Reserve: the last upload has read the staging buffer, which then holds `bytes` (grown to twice that) for the caller to
+// pack into.  Upload: one copy into the device buffer -- which the caller grew (grow_run_scratch) before its begin enqueued anything
+static int staged_reserve(pf_handle* h, StagedBlock& b, size_t bytes) {
+    if (b.ev) PF_HIP(h, hipEventSynchronize(b.ev));
+    else PF_HIP(h, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+    if (bytes <= b.stage_capacity) return PF_OK;
+    if (b.stage) { (void)hipHostFree(b.stage); b.stage = nullptr; b.stage_capacity = 0; }
+    PF_HIP(h, hipHostMalloc(&b.stage, bytes * 2, hipHostMallocDefault));
+    b.stage_capacity = bytes * 2;
+    return PF_OK;
+}
+static int staged_upload(pf_handle* h, StagedBlock& b, size_t bytes, hipStream_t s) {
+    PF_HIP(h, hipMemcpyAsync(b.dev, b.stage, bytes, hipMemcpyHostToDevice, s));
+    PF_HIP(h, hipEventRecord(b.ev, s));
     return PF_OK;
 }
 
@@ -2242,7 +2236,7 @@ static int begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const flo
 }
 int pf_sample_begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
                            const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, pf_stream stream) {
-    const bool seeded = take_seed(h);
+    const bool seeded = h && take(h->seed_armed);
     if (const int rc = refuse_field(h, "pf_sample_begin_pinned")) return rc;
     return begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, seeded, stream);
 }
@@ -3537,58 +3531,20 @@ int pf_dynamics_input_vjp(pf_handle* h, const float* dev_g_eps_h, const float* d
 }
 
 // ---- guided sampling: restraint energies on the predicted clean centers steer the reverse steps (reconstruction guidance) ----
-// The restraint block (d_restr and its staging buffer), in 32-bit words: restr_ptr [B + 1], kind [n1], center [n1], p [n1][3],
-// r [n1], w [n1] with n1 = max(n, 1)
-struct RestrLayout {
-    size_t B1, n1;
-    RestrLayout(int B, int n) : B1((size_t)B + 1), n1((size_t)std::max(n, 1)) {}
-    size_t kind() const { return B1; }
-    size_t center() const { return B1 + n1; }
-    size_t p() const { return B1 + 2 * n1; }
-    size_t r() const { return B1 + 5 * n1; }
-    size_t w() const { return B1 + 6 * n1; }
-    size_t words() const { return B1 + 7 * n1; }
-};
-// every check of pf_sample_begin_guided's own arguments, before anything is enqueued or the handle changes
-static int guide_validate(pf_handle* h, const int32_t* rptr, const int32_t* kind, const int32_t* center, const float* p, const float* r,
-                          const float* w, float scale, float clip) {
-    const char* who = "pf_sample_begin_guided";
-    if (!rptr) PF_FAIL(h, PF_ERR_ARG, "%s: null restr_ptr", who);
-    if (!(scale >= 0.f) || !std::isfinite(scale)) PF_FAIL(h, PF_ERR_ARG, "%s: guide_scale must be finite and >= 0", who);
-    if (!(clip >= 0.f) || !std::isfinite(clip)) PF_FAIL(h, PF_ERR_ARG, "%s: guide_clip must be finite and >= 0 (0: no clip)", who);
-    if (rptr[0] != 0) PF_FAIL(h, PF_ERR_ARG, "%s: restr_ptr[0] must be 0", who);
-    for (int g = 0; g < h->B; ++g) {
-        const int n = rptr[g + 1] - rptr[g];
-        if (n < 0) PF_FAIL(h, PF_ERR_ARG, "%s: restr_ptr decreases at graph %d", who, g);
-        if (n > 256) PF_FAIL(h, PF_ERR_ARG, "%s: graph %d has %d restraints (at most 256 per graph)", who, g, n);
-    }
-    const int n = rptr[h->B];
-    if (n > 0 && (!kind || !center || !p || !r || !w)) PF_FAIL(h, PF_ERR_ARG, "%s: null restraint array", who);
-    for (int g = 0; g < h->B; ++g) {
-        const int nf_g = h->h_pharm_ptr[g + 1] - h->h_pharm_ptr[g];
-        for (int j = rptr[g]; j < rptr[g + 1]; ++j) {
-            if (kind[j] != 0 && kind[j] != 1) PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d has kind %d (0 attract, 1 repel)", who, j, (int)kind[j]);
-            if (center[j] < -1 || center[j] >= nf_g)
-                PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d names center %d of graph %d, which has %d (-1: every center)", who, j, (int)center[j], g, nf_g);
-            for (int c = 0; c < 3; ++c)
-                if (!std::isfinite(p[(size_t)j * 3 + c])) PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d has a non-finite point", who, j);
-            if (!(r[j] >= 0.f) || !std::isfinite(r[j])) PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d: the radius must be finite and >= 0", who, j);
-            if (!(w[j] >= 0.f) || !std::isfinite(w[j])) PF_FAIL(h, PF_ERR_ARG, "%s: restraint %d: the weight must be finite and >= 0", who, j);
-        }
-    }
-    return PF_OK;
-}
+// The restraint block, its checks and its packing, and the layouts of the two workspaces a step writes: pf_restr.h (host only)
+static pfrestr::GuideWork guide_work(const pf_handle* h) { return pfrestr::GuideWork(h->Nf, h->cfg.pharm_nf, h->B); }
+static pfrestr::TypeWork type_work(const pf_handle* h) { return pfrestr::TypeWork(h->Nf, h->cfg.pharm_nf, h->B); }
 
 int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
                            const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, const int32_t* host_restr_ptr,
                            const int32_t* host_restr_kind, const int32_t* host_restr_center, const float* host_restr_p,
                            const float* host_restr_r, const float* host_restr_w, float guide_scale, float guide_clip, pf_stream stream) {
-    const bool seeded = take_seed(h), fielded = take_field(h), typed = take_types(h);
+    const bool seeded = h && take(h->seed_armed), fielded = h && take(h->field.armed), typed = h && take(h->types.armed);
     int rc = check_ready(h, true);
     if (rc) return rc;
-    if (fielded && typed && h->field_arm.type_sharpness != h->types_arm.type_sharpness)
+    if (fielded && typed && h->field.arm.type_sharpness != h->types.arm.type_sharpness)
         PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: the pocket field's type_sharpness (%g) and the type guidance's (%g) must agree",
-                (double)h->field_arm.type_sharpness, (double)h->types_arm.type_sharpness);
+                (double)h->field.arm.type_sharpness, (double)h->types.arm.type_sharpness);
     if (!dev_noise0) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null noise");
     if (!dev_pin_flags || !dev_pin_x || !dev_pin_h) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: null pin array");
     if (!(feat_norm_constant > 0.f)) PF_FAIL(h, PF_ERR_ARG, "pf_sample_begin_guided: feat_norm_constant must be positive");
@@ -3596,69 +3552,97 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
         PF_FAIL(h, PF_ERR_STATE, "pf_sample_begin_guided: a guided step runs the width-generic training forward and its input gradients: "
                                  "call pf_train_set_family(h, PF_TRAIN_FAMILY_WIDE) first");
     if ((rc = tuned_input_grads_guard(h, "pf_sample_begin_guided")) != PF_OK) return rc;      // (the tuned family: fp32)
-    if ((rc = guide_validate(h, host_restr_ptr, host_restr_kind, host_restr_center, host_restr_p, host_restr_r, host_restr_w, guide_scale,
-                             guide_clip)) != PF_OK) return rc;
+    const pfrestr::RestrArgs a{host_restr_ptr, host_restr_kind, host_restr_center, host_restr_p, host_restr_r, host_restr_w, guide_scale, guide_clip};
+    char msg[256];
+    if (!pfrestr::validate(a, h->B, h->h_pharm_ptr.data(), msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
     if (const int lim = train_limits_ok(h)) return lim;
     hipStream_t s = (hipStream_t)stream;
-    // the restraints: staged in pinned memory in the device layout, then one copy
-    const size_t n = (size_t)host_restr_ptr[h->B];
-    const RestrLayout rl(h->B, (int)n);
-    const size_t bytes = rl.words() * 4;
-    if (h->restr_ev) PF_HIP(h, hipEventSynchronize(h->restr_ev));      // the last upload has read the staging buffer
-    if (bytes > h->restr_stage_capacity) {
-        if (h->restr_stage) { (void)hipHostFree(h->restr_stage); h->restr_stage = nullptr; h->restr_stage_capacity = 0; }
-        PF_HIP(h, hipHostMalloc(&h->restr_stage, bytes * 2, hipHostMallocDefault));
-        h->restr_stage_capacity = bytes * 2;
-    }
-    if ((rc = grow_run_scratch(h, &h->d_restr, &h->restr_capacity, bytes, bytes * 2, s)) != PF_OK) return rc;
-    const size_t nf1 = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
-    const size_t gwords = nf1 * (12 + nh) + (size_t)h->B * 4;
-    if ((rc = grow_run_scratch(h, &h->d_guide, &h->guide_capacity, gwords * 4, gwords * 4, s)) != PF_OK) return rc;
-    if (!h->restr_ev) PF_HIP(h, hipEventCreateWithFlags(&h->restr_ev, hipEventDisableTiming));
-    const pffield::FieldLayout fl(h->Np, h->B, h->field_arm.n, h->cfg.pharm_nf);
-    if (fielded && (rc = grow_run_scratch(h, &h->d_field, &h->field_capacity, fl.words() * 4, fl.words() * 8, s)) != PF_OK) return rc;
-    const pftypes::TypesLayout tl(h->B, h->types_arm.n);
-    const size_t twords = nf1 * nh * 5 + (size_t)h->B;
-    if (typed && (rc = grow_run_scratch(h, &h->d_types, &h->types_capacity, tl.words() * 4, tl.words() * 8, s)) != PF_OK) return rc;
-    if (typed && (rc = grow_run_scratch(h, &h->d_tguide, &h->tguide_capacity, twords * 4, twords * 4, s)) != PF_OK) return rc;
+    // every staging reservation and every device growth before anything is enqueued; the uploads behind begin_pinned
+    const int n = pfrestr::n_restraints(a, h->B), nh = h->cfg.pharm_nf;
+    const size_t bytes = pfrestr::RestrLayout(h->B, n).words() * 4;
+    if ((rc = staged_reserve(h, h->restr, bytes)) != PF_OK) return rc;
+    if ((rc = grow_run_scratch(h, &h->restr.dev, &h->restr.capacity, bytes, bytes * 2, s)) != PF_OK) return rc;
+    const size_t gbytes = guide_work(h).words() * 4, tbytes = type_work(h).words() * 4;
+    if ((rc = grow_run_scratch(h, &h->d_guide, &h->guide_capacity, gbytes, gbytes, s)) != PF_OK) return rc;
+    const pffield::FieldLayout fl(h->Np, h->B, h->field.arm.n, nh);
+    if (fielded && (rc = grow_run_scratch(h, &h->field.blk.dev, &h->field.blk.capacity, fl.words() * 4, fl.words() * 8, s)) != PF_OK) return rc;
+    const size_t types_bytes = pftypes::TypesLayout(h->B, h->types.arm.n).words() * 4;
+    if (typed && (rc = grow_run_scratch(h, &h->types.blk.dev, &h->types.blk.capacity, types_bytes, types_bytes * 2, s)) != PF_OK) return rc;
+    if (typed && (rc = grow_run_scratch(h, &h->types.d_tguide, &h->types.tguide_capacity, tbytes, tbytes, s)) != PF_OK) return rc;
     rc = begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, seeded, stream);
     if (rc) return rc;
-    {
-        int32_t* st = (int32_t*)h->restr_stage;
-        std::memcpy(st, host_restr_ptr, rl.B1 * 4);
-        if (n) {
-            std::memcpy(st + rl.kind(), host_restr_kind, n * 4);
-            std::memcpy(st + rl.center(), host_restr_center, n * 4);
-            std::memcpy(st + rl.p(), host_restr_p, n * 12);
-            std::memcpy(st + rl.r(), host_restr_r, n * 4);
-            std::memcpy(st + rl.w(), host_restr_w, n * 4);
-        }
-        PF_HIP(h, hipMemcpyAsync(h->d_restr, st, bytes, hipMemcpyHostToDevice, s));
-        PF_HIP(h, hipEventRecord(h->restr_ev, s));
-    }
-    h->n_restr = (int)n;
+    pfrestr::pack(a, h->B, (uint32_t*)h->restr.stage);
+    if ((rc = staged_upload(h, h->restr, bytes, s)) != PF_OK) return rc;
+    h->n_restr = n;
     if (fielded) {                          // the armed field becomes this run's: one copy out of the staging buffer
-        PF_HIP(h, hipMemcpyAsync(h->d_field, h->field_stage, fl.upload_words() * 4, hipMemcpyHostToDevice, s));
-        PF_HIP(h, hipEventRecord(h->field_ev, s));
-        h->field_run = h->field_arm;
-        h->field_on = true;
+        if ((rc = staged_upload(h, h->field.blk, fl.upload_words() * 4, s)) != PF_OK) return rc;
+        h->field.run = h->field.arm; h->field.on = true;
     }
     if (typed) {                            // the armed type guidance becomes this run's
-        PF_HIP(h, hipMemcpyAsync(h->d_types, h->types_stage, tl.words() * 4, hipMemcpyHostToDevice, s));
-        PF_HIP(h, hipEventRecord(h->types_ev, s));
-        PF_HIP(h, hipMemsetAsync(h->d_tguide, 0, twords * 4, s));
-        h->types_run = h->types_arm;
-        h->types_on = true;
+        if ((rc = staged_upload(h, h->types.blk, types_bytes, s)) != PF_OK) return rc;
+        PF_HIP(h, hipMemsetAsync(h->types.d_tguide, 0, tbytes, s));
+        h->types.run = h->types.arm; h->types.on = true;
     }
-    float* gq = (float*)h->d_guide;
-    h->d_g0 = gq; h->d_gjx = gq + nf1 * 3; h->d_ggrad = gq + nf1 * 6; h->d_gshift = gq + nf1 * 9; h->d_gzero = gq + nf1 * 12;
-    h->d_genergy = h->d_gzero + nf1 * nh; h->d_gD = h->d_genergy + h->B;
-    PF_HIP(h, hipMemsetAsync(h->d_guide, 0, gwords * 4, s));          // (the zero g_eps_h of every step's VJP; nothing writes it)
+    PF_HIP(h, hipMemsetAsync(h->d_guide, 0, gbytes, s));              // (the zero g_eps_h of every step's VJP; nothing writes it)
     h->guide_scale = guide_scale; h->guide_clip = guide_clip;
     h->guide_traj_energy = nullptr;
-    h->run = RUN_GUIDED; h->guide_have = false; h->field_have = false; h->types_have = false;
+    h->run = RUN_GUIDED; h->guide_have = false; h->field.have = false; h->types.have = false;
     h->guide_wide = h->train_wide; h->guide_in_grads = h->train_in_grads;
     return PF_OK;
+}
+
+// ---- the guided step's launches: one builder per parameter struct ----
+// what they share: the step's coefficients, the two workspaces and their layouts (g: d_guide; t: d_tguide, null without type guidance: no builder reads it)
+struct GuideStep { float alpha_t, sigma_t; int ep_coord, ep_feat; pfrestr::GuideWork gw; float* g; pfrestr::TypeWork tw; float* t; };
+static const auto guide_shared = [](const pf_handle* h, const GuideStep& st, auto& q) {      // q: GuideParams, FieldParams, TypeParams
+    q.alpha_t = st.alpha_t; q.sigma_t = st.sigma_t; q.ep_coord = st.ep_coord;
+    q.D = st.g + st.gw.D(); q.g0 = st.g + st.gw.g0(); q.energy = st.g + st.gw.energy(); q.traj_energy = h->guide_traj_energy;
+};
+static GuideParams guide_params(const pf_handle* h, const GuideStep& st) {
+    GuideParams q{};
+    const pfrestr::RestrLayout rl(h->B, h->n_restr);
+    const int32_t* base = (const int32_t*)h->restr.dev;
+    q.restr_ptr = base + rl.ptr(); q.restr_kind = base + rl.kind(); q.restr_center = base + rl.center();
+    q.restr_p = (const float*)(base + rl.p()); q.restr_r = (const float*)(base + rl.r()); q.restr_w = (const float*)(base + rl.w());
+    q.com_init = h->d_com_init;
+    guide_shared(h, st, q);
+    return q;
+}
+static FieldParams field_params(const pf_handle* h, const GuideStep& st) {
+    FieldParams q{};
+    const pffield::FieldLayout fl(h->Np, h->B, h->field.run.n, h->cfg.pharm_nf);
+    float* fb = (float*)h->field.blk.dev;
+    q.ph_xt = (const float4*)(fb + fl.ph_xt()); q.atom_r = fb + fl.atom_r(); q.ph_ptr = (const int*)(fb + fl.ph_ptr());
+    q.match = (const int*)(fb + fl.match()); q.dist = fb + fl.dist(); q.E3 = fb + fl.e3();
+    const auto& r = h->field.run;
+    q.w_clash = r.w_clash; q.w_comp = r.w_comp; q.kappa = r.kappa; q.type_sharpness = r.type_sharpness;
+    q.ep_feat = st.ep_feat;
+    guide_shared(h, st, q);
+    return q;
+}
+static FieldTypeParams field_type_params(const pf_handle* h, const GuideStep& st) {        // unmatched, g0_h, gs_h, E_type
+    return {h->types.run.unmatched, st.t + st.tw.g0_h(), st.t + st.tw.gs_h(), st.t + st.tw.E_type()};
+}
+// e3: the E3 of the field launch's TYPES form in front, or null
+static TypeParams type_params(const pf_handle* h, const GuideStep& st, const float* e3) {
+    TypeParams q{};
+    const pftypes::TypesLayout tl(h->B, h->types.run.n);
+    const int32_t* tb = (const int32_t*)h->types.blk.dev;
+    q.ptr = tb + tl.ptr(); q.center = tb + tl.center(); q.type = tb + tl.type();
+    q.p = (const float*)(tb + tl.p()); q.r = (const float*)(tb + tl.r()); q.w = (const float*)(tb + tl.w());
+    q.sharp = h->types.run.type_sharpness; q.ep_feat = st.ep_feat;
+    q.g0_h = st.t + st.tw.g0_h(); q.gs_h = st.t + st.tw.gs_h(); q.E_type = st.t + st.tw.E_type(); q.E3 = e3;
+    guide_shared(h, st, q);
+    return q;
+}
+static GuideShiftParams guide_shift_params(const pf_handle* h, const GuideStep& st) {      // g0, jx, D, alpha_t, sigma_t, scale, clip, grad, shift
+    const pfrestr::GuideWork& w = st.gw;
+    return {st.g + w.g0(), st.g + w.jx(), st.g + w.D(), st.alpha_t, st.sigma_t, h->guide_scale, h->guide_clip, st.g + w.grad(), st.g + w.shift()};
+}
+// live_h: a launch of this step left a g0_h (else the stored zeros stand in).  g0_h, jh, scale, clip, grad_h, shift_h
+static GuideFeatParams guide_feat_params(const pf_handle* h, const GuideStep& st, bool live_h) {
+    const pfrestr::TypeWork& w = st.tw;
+    return {live_h ? st.t + w.g0_h() : st.g + st.gw.zero(), st.t + w.j_h(), h->types.run.feat_scale, h->types.run.feat_clip, st.t + w.grad_h(), st.t + w.shift_h()};
 }
 
 // One denoising step of a guided run: the training forward of the family the run began on (dropout 0: it keeps what the VJP reads),
@@ -3687,77 +3671,46 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, true, nullptr);
     h->t_have_fwd = false;                      // (the kept forward is this step's: d_t does not hold its timestep)
     if (rc) return rc;
-    GuideParams gq{};
-    const RestrLayout rl(h->B, h->n_restr);
-    const int32_t* base = (const int32_t*)h->d_restr;
-    gq.restr_ptr = base; gq.restr_kind = base + rl.kind(); gq.restr_center = base + rl.center();
-    gq.restr_p = (const float*)(base + rl.p()); gq.restr_r = (const float*)(base + rl.r()); gq.restr_w = (const float*)(base + rl.w());
-    gq.com_init = h->d_com_init; gq.alpha_t = gc->alpha_t; gq.sigma_t = gc->sigma_t; gq.ep_coord = ep_coord;
-    gq.g0 = h->d_g0; gq.energy = h->d_genergy; gq.traj_energy = h->guide_traj_energy; gq.D = h->d_gD;
+    const GuideStep st{gc->alpha_t, gc->sigma_t, ep_coord, ep_feat, guide_work(h), (float*)h->d_guide, type_work(h), h->types.on ? (float*)h->types.d_tguide : nullptr};
+    float *const g0 = st.g + st.gw.g0(), *const jx = st.g + st.gw.jx();
+    const GuideParams gq = guide_params(h, st);
     pfk_guide_grad(&sp, &gq, s);
-    // type guidance's buffers of this step (d_tguide): g0_h, gs_h, J_h, grad_h, shift_h, E_type
-    const size_t tn = h->types_on ? (size_t)std::max(h->Nf, 1) * (size_t)h->cfg.pharm_nf : 0;     // (no arming: no buffer, nothing reads these)
-    float* const tg_g0h = (float*)h->d_tguide;
-    float *const tg_gsh = tg_g0h + tn, *const tg_jh = tg_g0h + 2 * tn, *const tg_grh = tg_g0h + 3 * tn, *const tg_shh = tg_g0h + 4 * tn;
-    float* const tg_E = tg_g0h + 5 * tn;
     bool comp_types = false;
     const float* e3 = nullptr;
-    if (h->field_on) {                          // the pocket field adds into g0 and E (one more launch; none without a field)
-        const pffield::FieldLayout fl(h->Np, h->B, h->field_run.n, h->cfg.pharm_nf);
-        const float* fb = (const float*)h->d_field;
-        FieldParams fq{};
-        fq.ph_xt = (const float4*)(fb + fl.ph_xt()); fq.atom_r = fb + fl.atom_r(); fq.ph_ptr = (const int*)(fb + fl.ph_ptr());
-        fq.match = (const int*)(fb + fl.match()); fq.dist = fb + fl.dist();
-        fq.w_clash = h->field_run.w_clash; fq.w_comp = h->field_run.w_comp; fq.kappa = h->field_run.kappa;
-        fq.type_sharpness = h->field_run.type_sharpness;
-        fq.alpha_t = gc->alpha_t; fq.sigma_t = gc->sigma_t; fq.ep_coord = ep_coord; fq.ep_feat = ep_feat;
-        fq.D = h->d_gD; fq.g0 = h->d_g0; fq.energy = h->d_genergy; fq.traj_energy = h->guide_traj_energy;
-        fq.E3 = (float*)h->d_field + fl.e3();
-        comp_types = h->types_on && h->types_run.comp && h->field_run.n > 0 && h->field_run.w_comp > 0.f;
+    if (h->field.on) {                          // the pocket field adds into g0 and E (one more launch; none without a field)
+        const FieldParams fq = field_params(h, st);
+        comp_types = h->types.on && h->types.run.comp && h->field.run.n > 0 && h->field.run.w_comp > 0.f;
         if (comp_types) {                       // the TYPES form: the complementarity energy leaves its feature gradient too
-            FieldTypeParams ft{};
-            ft.unmatched = h->types_run.unmatched; ft.g0_h = tg_g0h; ft.gs_h = tg_gsh; ft.E_type = tg_E;
+            const FieldTypeParams ft = field_type_params(h, st);
             pfk_guide_field_types(&sp, &fq, &ft, s);
             e3 = fq.E3;
         } else pfk_guide_field(&sp, &fq, s);
     }
-    h->field_have = h->field_on;
-    const bool restr_types = h->types_on && h->types_run.n > 0;
+    h->field.have = h->field.on;
+    const bool restr_types = h->types.on && h->types.run.n > 0;
     if (restr_types) {                          // type restraints: one more launch, behind the field's
-        const pftypes::TypesLayout tl(h->B, h->types_run.n);
-        const int32_t* tb = (const int32_t*)h->d_types;
-        TypeParams tq{};
-        tq.ptr = tb + tl.ptr(); tq.center = tb + tl.center(); tq.type = tb + tl.type();
-        tq.p = (const float*)(tb + tl.p()); tq.r = (const float*)(tb + tl.r()); tq.w = (const float*)(tb + tl.w());
-        tq.sharp = h->types_run.type_sharpness; tq.alpha_t = gc->alpha_t; tq.sigma_t = gc->sigma_t; tq.ep_coord = ep_coord; tq.ep_feat = ep_feat;
-        tq.D = h->d_gD; tq.g0 = h->d_g0; tq.g0_h = tg_g0h; tq.gs_h = tg_gsh; tq.E_type = tg_E; tq.energy = h->d_genergy;
-        tq.traj_energy = h->guide_traj_energy; tq.E3 = e3;
+        const TypeParams tq = type_params(h, st, e3);
         pfk_guide_types(&sp, &tq, s);
     }
     // the VJP's g_eps_h: (phi_h / phi_x) g0_h where a launch above left one, else the stored zeros; g_pharm_h only with the arming
     const bool live_h = comp_types || restr_types;
-    const float* g_eps_h = live_h ? tg_gsh : h->d_gzero;
-    float* g_h = h->types_on ? tg_jh : nullptr;
+    const float* g_eps_h = live_h ? st.t + st.tw.gs_h() : st.g + st.gw.zero();
+    float* g_h = h->types.on ? st.t + st.tw.j_h() : nullptr;
     if (g_h && h->B) {
         // the encoders' backward recomputes their forward from pharm_h and d_t, and this step's forward took its timestep as a
         // scalar: d_t gets it now (nothing else reads d_t before the next call that loads it: t_have_fwd is false from here on)
         uint32_t bits; memcpy(&bits, &coef->t, 4);
         PF_HIP(h, hipMemsetD32Async((hipDeviceptr_t)h->d_t, (int)bits, (size_t)h->B, s));
     }
-    rc = h->train_wide ? wide_train_backward(h, g_eps_h, h->d_g0, nullptr, h->d_gjx, g_h, s)
-                       : tuned_train_backward(h, g_eps_h, h->d_g0, nullptr, h->d_gjx, g_h, s);
+    rc = h->train_wide ? wide_train_backward(h, g_eps_h, g0, nullptr, jx, g_h, s) : tuned_train_backward(h, g_eps_h, g0, nullptr, jx, g_h, s);
     if (rc) return rc;
     const PinParams q = pin_params(h, pin);
-    GuideShiftParams gs{};
-    gs.g0 = h->d_g0; gs.jx = h->d_gjx; gs.D = h->d_gD; gs.alpha_t = gc->alpha_t; gs.sigma_t = gc->sigma_t;
-    gs.scale = h->guide_scale; gs.clip = h->guide_clip; gs.grad = h->d_ggrad; gs.shift = h->d_gshift;
-    GuideFeatParams gf{};
-    gf.g0_h = live_h ? tg_g0h : h->d_gzero; gf.jh = tg_jh; gf.scale = h->types_run.feat_scale; gf.clip = h->types_run.feat_clip;
-    gf.grad_h = tg_grh; gf.shift_h = tg_shh;
+    const GuideShiftParams gs = guide_shift_params(h, st);
+    const GuideFeatParams gf = h->types.on ? guide_feat_params(h, st, live_h) : GuideFeatParams{};
     h->guide_have = true;
-    h->types_have = h->types_on; h->types_live = live_h;
+    h->types.have = h->types.on; h->types.live = live_h;
     StepMove mv{StepMove::GUIDED, false, &q, nullptr, &gs, -1};
-    if (h->types_on) mv.feat = &gf;
+    if (h->types.on) mv.feat = &gf;
     return step_end(h, sp, mv, s);
 }
 
@@ -3783,10 +3736,12 @@ int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* 
     if (!h->guide_have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_guidance: no guided step on this batch");
     hipStream_t s = (hipStream_t)stream;
     const size_t nb = (size_t)h->Nf * 3 * 4;
-    if (dev_g0 && nb) PF_HIP(h, hipMemcpyAsync(dev_g0, h->d_g0, nb, hipMemcpyDeviceToDevice, s));
-    if (dev_grad && nb) PF_HIP(h, hipMemcpyAsync(dev_grad, h->d_ggrad, nb, hipMemcpyDeviceToDevice, s));
-    if (dev_shift && nb) PF_HIP(h, hipMemcpyAsync(dev_shift, h->d_gshift, nb, hipMemcpyDeviceToDevice, s));
-    if (dev_energy && h->B) PF_HIP(h, hipMemcpyAsync(dev_energy, h->d_genergy, (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
+    const pfrestr::GuideWork gw = guide_work(h);
+    const float* g = (const float*)h->d_guide;
+    if (dev_g0 && nb) PF_HIP(h, hipMemcpyAsync(dev_g0, g + gw.g0(), nb, hipMemcpyDeviceToDevice, s));
+    if (dev_grad && nb) PF_HIP(h, hipMemcpyAsync(dev_grad, g + gw.grad(), nb, hipMemcpyDeviceToDevice, s));
+    if (dev_shift && nb) PF_HIP(h, hipMemcpyAsync(dev_shift, g + gw.shift(), nb, hipMemcpyDeviceToDevice, s));
+    if (dev_energy && h->B) PF_HIP(h, hipMemcpyAsync(dev_energy, g + gw.energy(), (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
     return PF_OK;
 }
 
@@ -3803,19 +3758,11 @@ int pf_guide_field_next(pf_handle* h, const float* host_atom_r, float w_clash, c
     if (!pffield::validate(a, h->B, h->Np, h->cfg.pharm_nf, msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
     const int n = pffield::n_features(a, h->B);
     const pffield::FieldLayout fl(h->Np, h->B, n, h->cfg.pharm_nf);
-    const size_t bytes = fl.upload_words() * 4;
-    if (h->field_ev) PF_HIP(h, hipEventSynchronize(h->field_ev));      // the last upload has read the staging buffer
-    else PF_HIP(h, hipEventCreateWithFlags(&h->field_ev, hipEventDisableTiming));
-    h->field_armed = false;                 // (a field armed before and not yet used is replaced, also when the allocation below fails)
-    if (bytes > h->field_stage_capacity) {
-        if (h->field_stage) { (void)hipHostFree(h->field_stage); h->field_stage = nullptr; h->field_stage_capacity = 0; }
-        PF_HIP(h, hipHostMalloc(&h->field_stage, bytes * 2, hipHostMallocDefault));
-        h->field_stage_capacity = bytes * 2;
-    }
-    pffield::pack(a, h->B, h->Np, h->cfg.pharm_nf, (uint32_t*)h->field_stage);
-    h->field_arm.n = n; h->field_arm.w_clash = w_clash; h->field_arm.w_comp = w_comp; h->field_arm.kappa = kappa;
-    h->field_arm.type_sharpness = type_sharpness;
-    h->field_armed = true;
+    h->field.armed = false;                 // (a field armed before and not yet used is replaced, also when the allocation below fails)
+    if ((rc = staged_reserve(h, h->field.blk, fl.upload_words() * 4)) != PF_OK) return rc;
+    pffield::pack(a, h->B, h->Np, h->cfg.pharm_nf, (uint32_t*)h->field.blk.stage);
+    h->field.arm = {n, w_clash, w_comp, kappa, type_sharpness};
+    h->field.armed = true;
     return PF_OK;
 }
 
@@ -3831,38 +3778,30 @@ int pf_guide_types_next(pf_handle* h, const int32_t* host_ptr, const int32_t* ho
     char msg[256];
     if (!pftypes::validate(a, h->B, h->h_pharm_ptr.data(), h->cfg.pharm_nf, msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
     const int n = pftypes::n_restraints(a, h->B);
-    const pftypes::TypesLayout tl(h->B, n);
-    const size_t bytes = tl.words() * 4;
-    if (h->types_ev) PF_HIP(h, hipEventSynchronize(h->types_ev));      // the last upload has read the staging buffer
-    else PF_HIP(h, hipEventCreateWithFlags(&h->types_ev, hipEventDisableTiming));
-    h->types_armed = false;                 // (an arming not yet used is replaced, also when the allocation below fails)
-    if (bytes > h->types_stage_capacity) {
-        if (h->types_stage) { (void)hipHostFree(h->types_stage); h->types_stage = nullptr; h->types_stage_capacity = 0; }
-        PF_HIP(h, hipHostMalloc(&h->types_stage, bytes * 2, hipHostMallocDefault));
-        h->types_stage_capacity = bytes * 2;
-    }
-    pftypes::pack(a, h->B, (uint32_t*)h->types_stage);
-    h->types_arm.n = n; h->types_arm.feat_scale = feat_scale; h->types_arm.feat_clip = feat_clip;
-    h->types_arm.type_sharpness = type_sharpness; h->types_arm.comp = comp_types != 0; h->types_arm.unmatched = unmatched;
-    h->types_armed = true;
+    h->types.armed = false;                 // (an arming not yet used is replaced, also when the allocation below fails)
+    if ((rc = staged_reserve(h, h->types.blk, pftypes::TypesLayout(h->B, n).words() * 4)) != PF_OK) return rc;
+    pftypes::pack(a, h->B, (uint32_t*)h->types.blk.stage);
+    h->types.arm = {n, feat_scale, feat_clip, type_sharpness, comp_types != 0, unmatched};
+    h->types.armed = true;
     return PF_OK;
 }
 
 int pf_debug_last_type_guidance(pf_handle* h, float* dev_g0_h, float* dev_grad_h, float* dev_shift_h, float* dev_E_type, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
-    if (!h->guide_have || !h->types_have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_type_guidance: no guided step with type guidance on this batch");
+    if (!h->guide_have || !h->types.have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_type_guidance: no guided step with type guidance on this batch");
     hipStream_t s = (hipStream_t)stream;
-    const size_t tn = (size_t)std::max(h->Nf, 1) * (size_t)h->cfg.pharm_nf, nb = (size_t)h->Nf * (size_t)h->cfg.pharm_nf * 4;
-    const float* base = (const float*)h->d_tguide;
+    const size_t nb = (size_t)h->Nf * (size_t)h->cfg.pharm_nf * 4;
+    const pfrestr::TypeWork tw = type_work(h);
+    const float* t = (const float*)h->types.d_tguide;
     if (dev_g0_h && nb) {
-        if (h->types_live) PF_HIP(h, hipMemcpyAsync(dev_g0_h, base, nb, hipMemcpyDeviceToDevice, s));
+        if (h->types.live) PF_HIP(h, hipMemcpyAsync(dev_g0_h, t + tw.g0_h(), nb, hipMemcpyDeviceToDevice, s));
         else PF_HIP(h, hipMemsetAsync(dev_g0_h, 0, nb, s));
     }
-    if (dev_grad_h && nb) PF_HIP(h, hipMemcpyAsync(dev_grad_h, base + 3 * tn, nb, hipMemcpyDeviceToDevice, s));
-    if (dev_shift_h && nb) PF_HIP(h, hipMemcpyAsync(dev_shift_h, base + 4 * tn, nb, hipMemcpyDeviceToDevice, s));
+    if (dev_grad_h && nb) PF_HIP(h, hipMemcpyAsync(dev_grad_h, t + tw.grad_h(), nb, hipMemcpyDeviceToDevice, s));
+    if (dev_shift_h && nb) PF_HIP(h, hipMemcpyAsync(dev_shift_h, t + tw.shift_h(), nb, hipMemcpyDeviceToDevice, s));
     if (dev_E_type && h->B) {
-        if (h->types_live) PF_HIP(h, hipMemcpyAsync(dev_E_type, base + 5 * tn, (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
+        if (h->types.live) PF_HIP(h, hipMemcpyAsync(dev_E_type, t + tw.E_type(), (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
         else PF_HIP(h, hipMemsetAsync(dev_E_type, 0, (size_t)h->B * 4, s));
     }
     return PF_OK;
@@ -3871,10 +3810,10 @@ int pf_debug_last_type_guidance(pf_handle* h, float* dev_g0_h, float* dev_grad_h
 int pf_debug_last_field(pf_handle* h, float* dev_E3, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
-    if (!h->guide_have || !h->field_have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_field: no guided step with a pocket field on this batch");
+    if (!h->guide_have || !h->field.have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_field: no guided step with a pocket field on this batch");
     if (!dev_E3) PF_FAIL(h, PF_ERR_ARG, "pf_debug_last_field: null argument");
-    const pffield::FieldLayout fl(h->Np, h->B, h->field_run.n, h->cfg.pharm_nf);
-    if (h->B) PF_HIP(h, hipMemcpyAsync(dev_E3, (const float*)h->d_field + fl.e3(), (size_t)h->B * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    const pffield::FieldLayout fl(h->Np, h->B, h->field.run.n, h->cfg.pharm_nf);
+    if (h->B) PF_HIP(h, hipMemcpyAsync(dev_E3, (const float*)h->field.blk.dev + fl.e3(), (size_t)h->B * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PF_OK;
 }
 

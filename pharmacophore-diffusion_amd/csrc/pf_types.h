@@ -1,16 +1,12 @@
 // Type guidance of a guided run (pf_guide_types_next; semantics in include/pfdyn.h, "type guidance", and DESIGN 4.24): typed
 // restraints on the predicted clean feature rows and the switch that gives the complementarity energy its feature gradient.
 // This header is host only -- no HIP runtime call, no handle: the layout of the restraint block, every check of the caller's
-// arrays, and the packing into the staging buffer (tests/types_check.cpp runs all three without a GPU).  What the kernels read is
-// pf_device.h's TypeParams.
+// arrays, and the packing into the staging buffer (tests/types_check.cpp runs all three without a GPU).  The block is the one the
+// spatial restraints use (pf_restr.h); here are the names of its columns, the scalars' checks and the type column's.  What the
+// kernels read is pf_device.h's TypeParams.
 #pragma once
-#include <cmath>
-#include <cstddef>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
+#include "pf_restr.h"
 
-#define PF_TYPES_MAX_PER_GRAPH 256      // type restraints per graph
 #define PF_TYPES_MAX_TYPES 16           // pharm_nf (pf_create's own limit)
 
 namespace pftypes {
@@ -24,20 +20,10 @@ struct TypesArgs {
     float unmatched;
 };
 
-// The restraint block (the device allocation and its staging buffer), in 32-bit words:
+// The restraint block (the device allocation and its staging buffer) is pf_restr.h's, its integer columns named center, type:
 //   ptr [B + 1]  center [n1]  type [n1]  p [n1][3]  r [n1]  w [n1]
-// with n1 = max(n, 1).  All of it is uploaded
-struct TypesLayout {
-    size_t B1, n1;
-    TypesLayout(int B, int n) : B1((size_t)B + 1), n1((size_t)(n > 1 ? n : 1)) {}
-    size_t ptr() const { return 0; }
-    size_t center() const { return B1; }
-    size_t type() const { return B1 + n1; }
-    size_t p() const { return B1 + 2 * n1; }
-    size_t r() const { return B1 + 5 * n1; }
-    size_t w() const { return B1 + 6 * n1; }
-    size_t words() const { return B1 + 7 * n1; }
-};
+struct TypesLayout : pfrestr::BlockLayout { using BlockLayout::BlockLayout; size_t center() const { return col_a(); } size_t type() const { return col_b(); } };
+inline pfrestr::Block block(const TypesArgs& a) { return pfrestr::Block{a.ptr, a.center, a.type, a.p, a.r, a.w}; }
 
 #define PF_TYPES_BAD(...) do { std::snprintf(msg, msg_len, __VA_ARGS__); return false; } while (0)
 
@@ -52,27 +38,11 @@ inline bool validate(const TypesArgs& a, int B, const int32_t* pharm_ptr, int nt
     if (!(a.unmatched >= 0.f) || !std::isfinite(a.unmatched)) PF_TYPES_BAD("%s: unmatched must be finite and >= 0", who);
     if (a.comp_types != 0 && a.comp_types != 1) PF_TYPES_BAD("%s: comp_types must be 0 or 1", who);
     if (!a.ptr) return true;
-    if (a.ptr[0] != 0) PF_TYPES_BAD("%s: ptr[0] must be 0", who);
-    for (int g = 0; g < B; ++g) {
-        const int n = a.ptr[g + 1] - a.ptr[g];
-        if (n < 0) PF_TYPES_BAD("%s: ptr decreases at graph %d", who, g);
-        if (n > PF_TYPES_MAX_PER_GRAPH) PF_TYPES_BAD("%s: graph %d has %d type restraints (at most %d per graph)", who, g, n, PF_TYPES_MAX_PER_GRAPH);
-    }
-    const int n = a.ptr[B];
-    if (n > 0 && (!a.center || !a.type || !a.p || !a.r || !a.w)) PF_TYPES_BAD("%s: null type restraint array", who);
-    for (int g = 0; g < B; ++g) {
-        const int nf_g = pharm_ptr[g + 1] - pharm_ptr[g];
-        for (int j = a.ptr[g]; j < a.ptr[g + 1]; ++j) {
-            if (a.center[j] < -1 || a.center[j] >= nf_g)
-                PF_TYPES_BAD("%s: type restraint %d names center %d of graph %d, which has %d (-1: every center)", who, j, (int)a.center[j], g, nf_g);
-            if (a.type[j] < 0 || a.type[j] >= nt) PF_TYPES_BAD("%s: type restraint %d has type %d (0 .. %d)", who, j, (int)a.type[j], nt - 1);
-            for (int c = 0; c < 3; ++c)
-                if (!std::isfinite(a.p[(size_t)j * 3 + c])) PF_TYPES_BAD("%s: type restraint %d has a non-finite point", who, j);
-            if (!(a.r[j] >= 0.f) || !std::isfinite(a.r[j])) PF_TYPES_BAD("%s: type restraint %d: the radius must be finite and >= 0", who, j);
-            if (!(a.w[j] >= 0.f) || !std::isfinite(a.w[j])) PF_TYPES_BAD("%s: type restraint %d: the weight must be finite and >= 0", who, j);
-        }
-    }
-    return true;
+    const pfrestr::Words t{who, "type restraint", "ptr"};
+    return pfrestr::validate_block(block(a), a.center, B, pharm_ptr, t, [&](int j, char* msg, size_t msg_len) {
+        if (a.type[j] < 0 || a.type[j] >= nt) PF_TYPES_BAD("%s: type restraint %d has type %d (0 .. %d)", who, j, (int)a.type[j], nt - 1);
+        return true;
+    }, msg, msg_len);
 }
 #undef PF_TYPES_BAD
 
@@ -80,17 +50,6 @@ inline int n_restraints(const TypesArgs& a, int B) { return a.ptr ? a.ptr[B] : 0
 
 // Validated arguments into the staging buffer, in the block's layout (words() words are written).  No restraint array: no
 // restraint in any graph
-inline void pack(const TypesArgs& a, int B, uint32_t* st) {
-    const int n = n_restraints(a, B);
-    const TypesLayout tl(B, n);
-    std::memset(st, 0, tl.words() * 4);
-    if (!a.ptr || n == 0) return;
-    std::memcpy(st + tl.ptr(), a.ptr, tl.B1 * 4);
-    std::memcpy(st + tl.center(), a.center, (size_t)n * 4);
-    std::memcpy(st + tl.type(), a.type, (size_t)n * 4);
-    std::memcpy(st + tl.p(), a.p, (size_t)n * 12);
-    std::memcpy(st + tl.r(), a.r, (size_t)n * 4);
-    std::memcpy(st + tl.w(), a.w, (size_t)n * 4);
-}
+inline void pack(const TypesArgs& a, int B, uint32_t* st) { pfrestr::pack_block(block(a), B, st); }
 
 }  // namespace pftypes

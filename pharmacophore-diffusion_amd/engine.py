@@ -527,29 +527,37 @@ class PfEngine:
         return (PfEngine._struct_array(L.PfStepCoef, coef, steps), PfEngine._struct_array(L.PfPinCoef, pin_coef, steps), op_arr,
                 PfEngine._struct_array(L.PfRenoiseCoef, renoise_coef, jumps))
 
-    def _restraints(self, restraints):
-        """restraints: one list (or None) per graph of (kind, center, point, radius, weight) -- kind 'attract' / 'repel' (or 0 / 1),
-        center a local center index or None / -1 / '*' for every center of the graph, point three coordinates in the caller's
-        frame.  Returns the host arrays of pf_sample_begin_guided (numpy; the library validates the values)."""
+    def _restraint_arrays(self, restraints, tag, tag_first, noun):
+        """The one parser of restraint lists: one list (or None) per graph of (tag, center, point, radius, weight) -- center a local center
+        index or None / -1 / '*' for every center of the graph, point three coordinates in the caller's frame.  ``tag`` reads the first entry as
+        an integer, ``tag_first``: its column stands before the centers', ``noun``: a row in the ValueErrors.  Returns the six host arrays (numpy)."""
         import numpy as np
         if len(restraints) != self.B:
-            raise ValueError(f"restraints must have one entry per graph ({self.B}), got {len(restraints)}")
-        ptr, kind, center, pt, rad, wt = [0], [], [], [], [], []
-        names = {"attract": 0, "repel": 1, 0: 0, 1: 1}
+            raise ValueError(f"{noun}s must have one entry per graph ({self.B}), got {len(restraints)}")
+        ptr, tags, center, pt, rad, wt = [0], [], [], [], [], []
         for rs in restraints:
             for k, c, p, r, w in (rs or []):
-                if isinstance(k, str) and k not in names:
-                    raise ValueError(f"a restraint's kind is 'attract' or 'repel', got {k!r}")
-                kind.append(names[k] if k in names else int(k))
+                tags.append(tag(k))
                 center.append(-1 if c is None or c == "*" else int(c))
                 pt.append([float(v) for v in p])
                 if len(pt[-1]) != 3:
-                    raise ValueError("a restraint's point has three coordinates")
+                    raise ValueError(f"a {noun}'s point has three coordinates")
                 rad.append(float(r)); wt.append(float(w))
-            ptr.append(len(kind))
-        return (np.asarray(ptr, dtype=np.int32), np.asarray(kind, dtype=np.int32), np.asarray(center, dtype=np.int32),
+            ptr.append(len(tags))
+        cols = (tags, center) if tag_first else (center, tags)
+        return (np.asarray(ptr, dtype=np.int32), *(np.asarray(c, dtype=np.int32) for c in cols),
                 np.ascontiguousarray(np.asarray(pt, dtype=np.float32).reshape(-1, 3)), np.asarray(rad, dtype=np.float32),
                 np.asarray(wt, dtype=np.float32))
+
+    def _restraints(self, restraints):
+        """restraints: one list (or None) per graph of (kind, center, point, radius, weight) -- kind 'attract' / 'repel' (or 0 / 1).
+        Returns the host arrays of pf_sample_begin_guided: ptr, kind, center, point, radius, weight."""
+        names = {"attract": 0, "repel": 1, 0: 0, 1: 1}
+        def kind(k):
+            if isinstance(k, str) and k not in names:
+                raise ValueError(f"a restraint's kind is 'attract' or 'repel', got {k!r}")
+            return names[k] if k in names else int(k)
+        return self._restraint_arrays(restraints, kind, True, "restraint")
 
     def _free_pins(self):
         """the pin arrays of a run that pins nothing (a guided run is a pinned run whose flags may all be zero)"""
@@ -653,27 +661,8 @@ class PfEngine:
         the pocket costing ``unmatched``^2.  The library validates the values (PfError, PF_ERR_ARG) and copies them before this
         returns.  The begin of any other run kind while it is armed is a PfError (PF_ERR_STATE) and drops it; set_batch drops it
         silently."""
-        import numpy as np
-        none = ctypes.c_void_p(None)
-        args = (none,) * 6
-        keep = ()
-        if restraints is not None:
-            if len(restraints) != self.B:
-                raise ValueError(f"type restraints must have one entry per graph ({self.B}), got {len(restraints)}")
-            ptr, center, ty, pt, rad, wt = [0], [], [], [], [], []
-            for rs in restraints:
-                for t, c, p, r, w in (rs or []):
-                    ty.append(int(t))
-                    center.append(-1 if c is None or c == "*" else int(c))
-                    pt.append([float(v) for v in p])
-                    if len(pt[-1]) != 3:
-                        raise ValueError("a type restraint's point has three coordinates")
-                    rad.append(float(r)); wt.append(float(w))
-                ptr.append(len(ty))
-            keep = (np.asarray(ptr, dtype=np.int32), np.asarray(center, dtype=np.int32), np.asarray(ty, dtype=np.int32),
-                    np.ascontiguousarray(np.asarray(pt, dtype=np.float32).reshape(-1, 3)), np.asarray(rad, dtype=np.float32),
-                    np.asarray(wt, dtype=np.float32))
-            args = tuple(a.ctypes.data for a in keep)
+        keep = self._restraint_arrays(restraints, int, False, "type restraint") if restraints is not None else ()
+        args = tuple(a.ctypes.data for a in keep) or (ctypes.c_void_p(None),) * 6
         self._ck(self.lib.pf_guide_types_next(self._h, *args, float(scale), float(clip), float(sharpness), int(bool(complementarity)),
                                               float(unmatched)), "pf_guide_types_next")
 

@@ -9,14 +9,17 @@ entry (the whole-loop C call, the step API driven op by op)  x  batch (two graph
 copies of one 20-atom pocket with 3..8 centers, the size at which the default plain step takes its merged launch with a center
 hoist)  x  n_convs 1 / 2 / 3  x  environment (read when the handle is created: every case creates its own).  T = 12; the noise
 is seeded.  Five further kinds -- seeded (seed level 5), multistep and seeded_multistep (4 steps; the step entry makes them with
-ms_step), guided_field (a pocket field with a clash radius, no restraints), guided_tuned (guide_family="tuned") -- run with the
+ms_step), guided_field (a pocket field with a clash radius, no restraints), guided_tuned (guide_family="tuned"), guided_types (type
+restraints only, one graph in two without any, feat_scale 1) and guided_field_types (a pocket field with receptor features and
+w_comp > 0 plus type guidance with complementarity=True and unmatched 1.5: the TYPES form of the field launch) -- run with the
 default environment and PFDYN_WIDE=1 only.
 
 --model adds one line per model-level case (MODEL_CASES), a sha256 over every returned pharmacophore's x_0, h_0 and score, through
 PharmacophoreDiff.sample and through sample_given_receptor on the batch of the same graphs, each with drawn noise
 (torch.manual_seed, noise=None) and with given noise: the "two" batch, T = 12, n_convs 2, default environment.
 
-A line holds: a sha256 over x_0, h_0, both trajectory arrays, last_eps() and, for guided runs, the energies and last_guidance();
+A line holds: a sha256 over x_0, h_0, both trajectory arrays, last_eps() and, for guided runs, the energies and last_guidance(), with a pocket field last_field_energies(), with type guidance
+last_type_guidance();
 ahead() after the step in the middle of the run (step API) or after the run (whole loop); kernel_family(0) and l0_hoist(); and the
 launch counts per kernel class of a second pass of the same case on the same handle, through the step API with every kernel class
 profiled (profiling the step class switches the merged launch off, hence a second pass; only the counts are printed, times are not
@@ -38,7 +41,7 @@ import torch  # noqa: E402
 T, JUMP, RESAMPLES, PREC = 12, 3, 2, 0.25
 SEED_LEVEL, MS_STEPS = 5, 4
 KINDS = ("plain", "pinned", "pinned0", "resampled", "guided", "guided_pins")
-FRONT_KINDS = ("seeded", "multistep", "seeded_multistep", "guided_field", "guided_tuned")     # (default environment and PFDYN_WIDE=1)
+FRONT_KINDS = ("seeded", "multistep", "seeded_multistep", "guided_field", "guided_tuned", "guided_types", "guided_field_types")     # (default environment and PFDYN_WIDE=1)
 FIELD = dict(atom_r=1.5, w_clash=1.0)
 ENVS = ("default", "PFDYN_NO_ENC_FLY=1", "PFDYN_NO_CENTER_HOIST=1", "PFDYN_NO_PA_SPEC=1", "PFDYN_NO_FAST_BUILD=1", "PFDYN_TAIL_FORM=16",
         "PFDYN_WIDE=1")
@@ -85,12 +88,12 @@ def schedule_arrays(eng, kind):
     return top, None, eng.coef_array(coef, order), eng.pin_coef_array(pin, order), None, eng.guide_coef_array(schedule.guide_coefficients(gamma, T), order)
 
 
-def step_api(eng, kind, sched, noise, com, pins, restraints, mid_ahead, seed=None, field=None):
+def step_api(eng, kind, sched, noise, com, pins, restraints, mid_ahead, seed=None, field=None, types=None):
     """the run op by op: (x_0, h_0, frames x, frames h) and, in mid_ahead, ahead() after the middle op"""
     n_ops, op_arr, arr, parr, re_arr, garr = sched
-    guided = restraints is not None or field is not None
+    guided = restraints is not None or field is not None or types is not None
     family, grads = eng.train_family(), eng.train_input_grads()
-    kw = {k: v for k, v in (("seed", seed), ("field", field)) if v is not None}
+    kw = {k: v for k, v in (("seed", seed), ("field", field), ("types", types)) if v is not None}
     if kind == "guided_tuned":
         kw["guide_family"] = "tuned"
     elif guided:
@@ -143,7 +146,7 @@ def run_case(pfa, kind, entry, batch, n_convs, env):
     n_ops = sched[0]
     gen = torch.Generator().manual_seed(7)
     noise = torch.randn(n_ops + 1, Nf, 3 + nf, generator=gen).to(eng.device)
-    pins = restraints = seed = field = None
+    pins = restraints = seed = field = types = None
     if kind.startswith("seeded"):
         from pharmacoforge_amd import schedule
         gamma = schedule.PredefinedNoiseSchedule("polynomial_2", T, PREC).gamma.detach()
@@ -151,6 +154,15 @@ def run_case(pfa, kind, entry, batch, n_convs, env):
                 schedule.seed_coefficients(gamma, T, SEED_LEVEL))
     if kind == "guided_field":
         field = FIELD
+    if kind == "guided_types":
+        types = dict(restraints=[[(1, None, (com[g] + torch.tensor([0.5, 0.5, -1.0])).tolist(), 6.0, 1.0), (2, 0, (0.0, 0.0, 0.0), 0.0, 0.5)]
+                                 if g % 2 == 0 else None for g in range(B)], scale=1.0, clip=1.0, sharpness=4.0)
+    if kind == "guided_field_types":
+        from pharmacoforge_amd.analysis import complementarity_tables
+        match, dist = complementarity_tables()
+        ph = ([3 * g for g in range(B + 1)], com.repeat_interleave(3, 0) + 3.0 * torch.randn(3 * B, 3, generator=gen), torch.randint(0, nf, (3 * B,), generator=gen))
+        field = dict(FIELD, ph=ph, match=match, dist=dist, w_comp=0.25, kappa=4.0, type_sharpness=4.0)
+        types = dict(scale=1.0, clip=1.0, sharpness=4.0, complementarity=True, unmatched=1.5)
     if kind in ("pinned", "pinned0", "resampled", "guided_pins"):
         flags = torch.zeros(Nf, dtype=torch.int32)
         if kind != "pinned0":
@@ -159,13 +171,13 @@ def run_case(pfa, kind, entry, batch, n_convs, env):
         pins = (flags, com_f + 1.5 * torch.randn(Nf, 3, generator=gen),
                 torch.nn.functional.one_hot(torch.randint(0, nf, (Nf,), generator=gen), nf).float())
     guided = kind.startswith("guided")
-    if guided and field is None:
+    if guided and field is None and types is None:
         restraints = [[("attract", 0, (com[g] + torch.tensor([1.5, -0.5, -0.5])).tolist(), 1.0, 1.0),
                        ("repel", None, (com[g] - torch.tensor([0.5, 1.5, 0.5])).tolist(), 2.0, 0.5)] if g % 2 == 0 else None for g in range(B)]
     mid, steps_sched = {}, sched
     try:
         if entry == "loop":
-            kw = {k: v for k, v in (("seed", seed), ("field", field)) if v is not None}
+            kw = {k: v for k, v in (("seed", seed), ("field", field), ("types", types)) if v is not None}
             if kind == "guided_tuned":
                 kw["guide_family"] = "tuned"
             if kind.endswith("multistep"):
@@ -179,11 +191,12 @@ def run_case(pfa, kind, entry, batch, n_convs, env):
             out = eng.sample(sched[2], n_ops, noise, init_pharm_com=com, trajectory=True, **kw)
             mid = eng.ahead()
         else:
-            out = step_api(eng, kind, sched, noise, com, pins, restraints, mid, seed, field)
+            out = step_api(eng, kind, sched, noise, com, pins, restraints, mid, seed, field, types)
         out = tuple(out) + tuple(eng.last_eps()) + (tuple(eng.last_guidance()) if guided else ()) + ((eng.last_field_energies(),) if field else ())
+        out += tuple(eng.last_type_guidance()) if types else ()
         line = f"{digest(out)} ahead {[int(v) for v in mid.values()]} family {eng.kernel_family(0)} l0_hoist {eng.l0_hoist()}"
         eng.profile_enable((1 << len(eng.KERNEL_CLASSES)) - 1)
-        step_api(eng, kind, steps_sched, noise, com, pins, restraints, {}, seed, field)
+        step_api(eng, kind, steps_sched, noise, com, pins, restraints, {}, seed, field, types)
         line += f" launches {[int(n) for _, n in eng.profile_read().values()]}"
         torch.cuda.synchronize()
         eng.sample_status()
