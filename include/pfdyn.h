@@ -221,7 +221,7 @@ int pf_sample(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coef, cons
  * and reused, and grows -- with a stream synchronisation -- only when a batch has more centers).  The run is pinned until the next
  * pf_sample_begin / pf_sample_begin_pinned / pf_set_pocket_batch: inside it pf_denoise_step returns PF_ERR_STATE, and so does
  * pf_denoise_step_pinned outside it.  A pinned step never takes the tail or merged launches of pf_denoise_step: its dynamics call
- * is followed by one launch of its own (k_step_build_pinned: the update above + the generic edge build; k_step_update_pinned for the
+ * is followed by one launch of its own (k_step_build<MovePinned>: the update above + the generic edge build; k_step_update<MovePinned> for the
  * width-generic family), so it costs one launch per step more than the default path, and pf_debug_kernel_family(h, n_convs)
  * reports 0 after it.  Unpinned runs are not affected.
  * pf_sample_pinned: pf_sample's arguments + host_pin_coef[n_steps] (entry i: s = T-1-i) + the three pin arrays. */
@@ -254,8 +254,8 @@ int pf_sample_pinned(pf_handle* h, int32_t n_steps, const pf_step_coef* host_coe
  * caller's frame enters.  A pinned center needs no special case: at level b it holds the given value noised to level b, the forward
  * move gives it the right marginal at level a, and the following D op replaces it anyway.
  * pf_renoise_step is valid only inside a pinned run (outside one: PF_ERR_STATE; a caller who wants resampling without pins begins a
- * pinned run with all flags zero); a null argument is PF_ERR_ARG.  It makes no dynamics call: one launch (k_step_build_renoise: the
- * move + the generic edge build; k_step_update_renoise for the width-generic family and every configuration whose next dynamics call
+ * pinned run with all flags zero); a null argument is PF_ERR_ARG.  It makes no dynamics call: one launch (k_step_build<MoveRenoise>: the
+ * move + the generic edge build; k_step_update<MoveRenoise> for the width-generic family and every configuration whose next dynamics call
  * builds its own edges), on the caller's stream, no host synchronisation.  pf_debug_kernel_family(h, n_convs) reports 0 after it.
  * pf_sample_pinned_resampled: pf_sample_pinned's arguments with n_ops in place of n_steps, plus host_op[n_ops] (0 denoise, 1 renoise;
  * anything else: PF_ERR_ARG before anything is enqueued) and host_renoise[n_ops].  host_coef[i] and host_pin_coef[i] are read for op
@@ -424,8 +424,8 @@ int pf_debug_last_type_guidance(pf_handle* h, float* dev_g0_h, float* dev_grad_h
  *     x[f]  = alpha_a * (seed_x[f] - D[g])              + sigma_a * noise0_x[f]
  *     h[f]  = alpha_a * (seed_h[f] / feat_norm_constant) + sigma_a * noise0_h[f]
  * One rounding per operation, FP contraction off, as in a pinned step.  Then the COM of all centers of the graph is removed from
- * centers and protein, in the reduction order of pf_denoise_step's update.  One launch (k_step_build_seed: the move + the generic
- * edge build; k_step_update_seed for the width-generic family and every configuration whose next dynamics call builds its own edges).
+ * centers and protein, in the reduction order of pf_denoise_step's update.  One launch (k_step_build<MoveSeed>: the move + the generic
+ * edge build; k_step_update<MoveSeed> for the width-generic family and every configuration whose next dynamics call builds its own edges).
  * The rest of the run.  The caller passes n_steps = a and the coefficient entries for s = a-1 .. 0.  Nothing else in the run
  * changes: a seeded plain run takes the default path's steps, merged last launch and center hoist included.  The initial frame of
  * a trajectory is the noised seed.  Pins in a seeded pinned run act from the first step on, as today: the begin does not look at
@@ -451,7 +451,7 @@ int pf_sample_seed_next(pf_handle* h, const pf_seed_coef* coef, const float* dev
  * before any launch; the run goes on as if the call had not been made.  A non-finite coefficient is PF_ERR_ARG.
  * pf_denoise_step_ms is legal inside a plain run (after pf_sample_begin, seeded or not), and plain and multistep steps may
  * alternate.  Like a pinned step it runs the separate launches -- one more than the default step -- and ends with one launch
- * of its own (k_step_build_ms: the move + the generic edge build; k_step_update_ms for the width-generic family and every
+ * of its own (k_step_build<MoveMs>: the move + the generic edge build; k_step_update<MoveMs> for the width-generic family and every
  * configuration whose next dynamics call builds its own edges); nothing is computed ahead across it.
  * pf_sample_ms is the whole run: begin with dev_noise0 [Nf, 3 + pharm_nf] (ONE row: the initial draw), n_steps multistep steps,
  * end.  Trajectories have n_steps + 1 frames.  Pinned and guided runs have no multistep move.

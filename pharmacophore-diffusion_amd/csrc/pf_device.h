@@ -558,7 +558,7 @@ struct MsParams {
 };
 // guided sampling (pf_denoise_step_guided): restraint energies on the predicted clean centers.  k_guide_grad reads GuideParams
 // (of StepParams: the graph pointers, xn and eps_x) and leaves g0 = dE/dy per center, E per graph and the frame offset D per graph;
-// the guided update (k_step_update_guided) reads GuideShiftParams: g0, the VJP of the dynamics J(g0) and D
+// the guided move (k_step_update<MoveGuided>) reads GuideShiftParams: g0, the VJP of the dynamics J(g0) and D
 struct GuideParams {
     const int* restr_ptr;      // [B + 1]  graph g owns restraints [restr_ptr[g], restr_ptr[g + 1])
     const int* restr_kind;     // [n]      0 attract, 1 repel
@@ -623,11 +623,21 @@ struct FieldTypeParams {
     float* g0_h; float* gs_h;  // [Nf][nf] each, written
     float* E_type;             // [B] written: w_comp sum_f sum_{t: S_t empty} p_ft unmatched^2
 };
-// the feature shift of the guided update's third form (k_step_update_guided_types), next to GuideShiftParams
+// the feature shift of the guided move with type guidance (k_step_update<MoveGuided<true>>), next to GuideShiftParams
 struct GuideFeatParams {
     const float* g0_h; const float* jh;     // [Nf][nf] each: dE/dh0_hat and the VJP's g_pharm_h
     float scale, clip;                      // feat_scale, feat_clip
     float* grad_h; float* shift_h;          // [Nf][nf] each: what the step applied (pf_debug_last_type_guidance); a type-pinned center's row is what it ignored
+};
+// the move a sampler step ends with (pfk_step_move; the moves: pf_stepmove.h): the tag and the parameters that move reads
+struct StepMoveArgs {
+    enum Kind { PLAIN, MS, PINNED, GUIDED, GUIDED_TYPES, RENOISE, SEED } kind;
+    MsParams ms;               // MS
+    PinParams pin;             // PINNED, GUIDED, GUIDED_TYPES
+    GuideShiftParams shift;    // GUIDED, GUIDED_TYPES
+    GuideFeatParams feat;      // GUIDED_TYPES
+    RenoiseParams renoise;     // RENOISE
+    SeedParams seed;           // SEED
 };
 #ifdef __HIPCC__
 // The p(z_s | z_t) update of sample_p_zs_given_zt (pharmacodiff.py:397-426) for ONE value -- coordinate or feature -- and the only place

@@ -67,22 +67,12 @@ void pfk_verify_copies(const float* x0, const float* h0, const int* gid, const i
                        int* flag, hipStream_t s);
 void pfk_scale_copy(const float* src, float* dst, size_t n, float sc, hipStream_t s);
 void pfk_segment_mean(const float4* xn, const int* ptr, int base, int B, float* out, hipStream_t s);
-void pfk_step_update(const StepParams* p, hipStream_t s);
-void pfk_step_build(const StepParams* sp, const BuildParams* bp, int fast, hipStream_t s);
-void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const BuildParams* bp, hipStream_t s);
-void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s);
-void pfk_step_update_guided(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, hipStream_t s);
+void pfk_step_build_fast(const StepParams* sp, const BuildParams* bp, hipStream_t s);
+void pfk_step_move(const StepParams* sp, const StepMoveArgs* a, const BuildParams* bp /* NULL: the move alone */, hipStream_t s);
 void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s);
 void pfk_guide_field(const StepParams* p, const FieldParams* q, hipStream_t s);
 void pfk_guide_field_types(const StepParams* p, const FieldParams* q, const FieldTypeParams* ft, hipStream_t s);
 void pfk_guide_types(const StepParams* p, const TypeParams* q, hipStream_t s);
-void pfk_step_update_guided_types(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, const GuideFeatParams* gf, hipStream_t s);
-void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s);
-void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s);
-void pfk_step_build_seed(const StepParams* sp, const SeedParams* q, const BuildParams* bp, hipStream_t s);
-void pfk_step_update_seed(const StepParams* p, const SeedParams* q, hipStream_t s);
-void pfk_step_build_ms(const StepParams* sp, const MsParams* q, const BuildParams* bp, hipStream_t s);
-void pfk_step_update_ms(const StepParams* p, const MsParams* q, hipStream_t s);
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s);
@@ -2104,20 +2094,15 @@ static PinParams pin_params(const pf_handle* h, const pf_pin_coef* pin) {
 // The move a step's own last launch makes.  build_form: the move has an "update + edge build in one launch" form (the guided
 // move has none: the width-generic training forward in front of it builds its own edges on every call)
 struct StepMove {
-    enum Kind { PLAIN, PINNED, RENOISE, GUIDED, SEED, MS } kind;
-    bool build_form;
-    const PinParams* pin;                   // PINNED, GUIDED
-    const RenoiseParams* renoise;           // RENOISE
-    const GuideShiftParams* shift;          // GUIDED
-    int snap_next;                          // PLAIN, SEED: the snapshot sp.h_snap_out is (center hoist)
-    const SeedParams* seed = nullptr;       // SEED
-    const MsParams* ms = nullptr;           // MS
-    const GuideFeatParams* feat = nullptr;  // GUIDED with type guidance: the update's feature-shift form
+    StepMoveArgs args{};                    // the tag and what the move's kernel reads (pf_device.h)
+    bool build_form = true;
+    int snap_next = -1;                     // PLAIN, SEED: the snapshot sp.h_snap_out is (center hoist)
 };
 // What every op calls after its dynamics call (if it has one): the move, unless the dynamics call's tail or merged launch made
 // it already; what the move leaves of the edges; what survives of the work done ahead (snapshot, center hoist, speculative rows)
 static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipStream_t s) {
-    const bool plain = mv.kind == StepMove::PLAIN;
+    const StepMoveArgs::Kind kind = mv.args.kind;
+    const bool plain = kind == StepMoveArgs::PLAIN;
     const bool moved = plain && h->tail_done;       // (only a plain step hands its StepParams to run_dynamics)
     if (!moved) {
         // the move + the edges of the next dynamics call in one launch, or the move alone
@@ -2125,17 +2110,8 @@ static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipS
         const BuildParams bp = build ? build_params(h, share) : BuildParams{};
         {
             ProfScope ps(h, pf_handle::K_STEP, s);
-            switch (mv.kind) {
-            case StepMove::PLAIN: if (build) pfk_step_build(&sp, &bp, step_build_fast_ok(h) ? 1 : 0, s); else pfk_step_update(&sp, s); break;
-            case StepMove::PINNED: if (build) pfk_step_build_pinned(&sp, mv.pin, &bp, s); else pfk_step_update_pinned(&sp, mv.pin, s); break;
-            case StepMove::RENOISE: if (build) pfk_step_build_renoise(&sp, mv.renoise, &bp, s); else pfk_step_update_renoise(&sp, mv.renoise, s); break;
-            case StepMove::GUIDED:
-                if (mv.feat) pfk_step_update_guided_types(&sp, mv.pin, mv.shift, mv.feat, s);
-                else pfk_step_update_guided(&sp, mv.pin, mv.shift, s);
-                break;
-            case StepMove::SEED: if (build) pfk_step_build_seed(&sp, mv.seed, &bp, s); else pfk_step_update_seed(&sp, mv.seed, s); break;
-            case StepMove::MS: if (build) pfk_step_build_ms(&sp, mv.ms, &bp, s); else pfk_step_update_ms(&sp, mv.ms, s); break;
-            }
+            if (plain && build && step_build_fast_ok(h)) pfk_step_build_fast(&sp, &bp, s);
+            else pfk_step_move(&sp, &mv.args, build ? &bp : nullptr, s);
         }
         if (build) build_done(h, share);
         else h->rec_valid = false;                  // the centers moved: the next dynamics call builds
@@ -2144,11 +2120,11 @@ static int step_end(pf_handle* h, const StepParams& sp, const StepMove& mv, hipS
     // a re-noise move has no dynamics call in front of it that would have reset these
     if (!plain) { h->tail_done = false; h->last_tail = 0; }
     // the multistep history holds the outputs of the step in front of this move only if that move wrote it
-    h->ms_hist_valid = mv.kind == StepMove::MS;
+    h->ms_hist_valid = kind == StepMoveArgs::MS;
     // the work done ahead is for the state the merged launch of a plain step left: every other move invalidates it.  The seed
     // move opens a run: nothing is ahead of it, and the snapshot it wrote holds the features as they are now
     const bool ahead = plain && h->tail_done && h->last_tail == 2;
-    h->snap_cur = ((ahead || mv.kind == StepMove::SEED) && sp.h_snap_out) ? mv.snap_next : -1;
+    h->snap_cur = ((ahead || kind == StepMoveArgs::SEED) && sp.h_snap_out) ? mv.snap_next : -1;
     if (h->snap_cur < 0) h->cen_valid = false;
     if (!ahead) h->spec_valid = false;
     const hipError_t e = moved ? hipSuccess : hipGetLastError();     // (run_dynamics has checked the tail and merged launches)
@@ -2171,7 +2147,9 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
     sp.h_snap_out = (h->cen_hoist && h->d_snap[0] && h->pk.l0c_off != 0) ? h->d_snap[snap_next] : nullptr;
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, &sp);      // every graph of the batch is at the same t
     if (rc) return rc;
-    return step_end(h, sp, StepMove{StepMove::PLAIN, true, nullptr, nullptr, nullptr, snap_next}, s);
+    StepMove mv;
+    mv.args.kind = StepMoveArgs::PLAIN; mv.snap_next = snap_next;
+    return step_end(h, sp, mv, s);
 }
 
 // The seeded begin's move (pf_sample_seed_next): every center becomes the seed noised to the run's first level with the initial
@@ -2179,10 +2157,12 @@ int pf_denoise_step(pf_handle* h, const pf_step_coef* coef, const float* dev_noi
 static int seed_move(pf_handle* h, const float* dev_noise0, hipStream_t s) {
     StepParams sp = step_params_base(h, dev_noise0);
     sp.h_snap_out = (h->cen_hoist && h->d_snap[0] && h->pk.l0c_off != 0) ? h->d_snap[0] : nullptr;
-    SeedParams q{};
+    StepMove mv;
+    mv.args.kind = StepMoveArgs::SEED; mv.snap_next = 0;
+    SeedParams& q = mv.args.seed;
     q.seed_x = h->d_seed_x; q.seed_h = h->d_seed_h; q.com_init = h->d_com_init;
     q.alpha_a = h->seed_alpha; q.sigma_a = h->seed_sigma; q.feat_norm = h->seed_feat_norm;
-    return step_end(h, sp, StepMove{StepMove::SEED, true, nullptr, nullptr, nullptr, 0, &q}, s);
+    return step_end(h, sp, mv, s);
 }
 
 // A run's device scratch (d_pin, d_guide, d_seed, a staged block's device buffer): kept while `need` bytes fit, else replaced by one of `want` bytes.  Launches
@@ -2276,25 +2256,27 @@ int pf_denoise_step_pinned(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     if ((rc = run_guard(h, __func__, RUN_PINNED)) != PF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const StepParams sp = step_params(h, coef, dev_noise, ep_coord, ep_feat);
-    const PinParams q = pin_params(h, pin);
+    StepMove mv;
+    mv.args.kind = StepMoveArgs::PINNED; mv.args.pin = pin_params(h, pin);
     ++h->step_id;
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, nullptr);
     if (rc) return rc;
-    return step_end(h, sp, StepMove{StepMove::PINNED, true, &q, nullptr, nullptr, -1}, s);
+    return step_end(h, sp, mv, s);
 }
 
 // Resampling jump of a pinned run: the whole state goes from level b back up to level a with one launch and no dynamics call
-// (k_step_build_renoise: the forward move + the generic edge build; k_step_update_renoise where the next dynamics call builds its own edges)
+// (k_step_build<MoveRenoise>: the forward move + the generic edge build; k_step_update<MoveRenoise> where the next dynamics call builds its own edges)
 int pf_renoise_step(pf_handle* h, const pf_renoise_coef* coef, const float* dev_noise, pf_stream stream) {
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (!coef || !dev_noise) PF_FAIL(h, PF_ERR_ARG, "pf_renoise_step: null argument");
     if ((rc = run_guard(h, __func__, RUN_PINNED, true)) != PF_OK) return rc;
     const StepParams sp = step_params_base(h, dev_noise);
-    RenoiseParams r{};
-    r.alpha_ts = coef->alpha_t_given_s; r.sigma_ts = coef->sigma_t_given_s;
+    StepMove mv;
+    mv.args.kind = StepMoveArgs::RENOISE;
+    mv.args.renoise.alpha_ts = coef->alpha_t_given_s; mv.args.renoise.sigma_ts = coef->sigma_t_given_s;
     ++h->step_id;
-    return step_end(h, sp, StepMove{StepMove::RENOISE, true, nullptr, &r, nullptr, -1}, (hipStream_t)stream);
+    return step_end(h, sp, mv, (hipStream_t)stream);
 }
 
 // One multistep step inside a plain run.  As in a pinned step the dynamics call is sequenced WITHOUT a step; the step ends with one
@@ -2315,13 +2297,15 @@ int pf_denoise_step_ms(pf_handle* h, const pf_ms_coef* coef, pf_stream stream) {
     if ((rc = grow_run_scratch(h, &h->d_ms_hist, &h->ms_hist_capacity, bytes, bytes, s)) != PF_OK) return rc;
     StepParams sp = step_params_base(h, nullptr);
     sp.eps_h = h->d_eps_h; sp.eps_x = h->d_eps_x;
-    MsParams q{};
+    StepMove mv;
+    mv.args.kind = StepMoveArgs::MS;
+    MsParams& q = mv.args.ms;
     q.hist = (float*)h->d_ms_hist;
     q.cz_x = coef->cz_x; q.c0_x = coef->c0_x; q.c1_x = coef->c1_x; q.cz_h = coef->cz_h; q.c0_h = coef->c0_h; q.c1_h = coef->c1_h;
     ++h->step_id;
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, nullptr);
     if (rc) return rc;
-    return step_end(h, sp, StepMove{StepMove::MS, true, nullptr, nullptr, nullptr, -1, nullptr, &q}, s);
+    return step_end(h, sp, mv, s);
 }
 
 int pf_prepare_timesteps(pf_handle* h, const float* host_t, int32_t n, pf_stream stream) {
@@ -3646,7 +3630,7 @@ static GuideFeatParams guide_feat_params(const pf_handle* h, const GuideStep& st
 }
 
 // One denoising step of a guided run: the training forward of the family the run began on (dropout 0: it keeps what the VJP reads),
-// k_guide_grad, that family's inputs-only backward with g_eps_x = g0 and the zero g_eps_h, k_step_update_guided.  The update runs
+// k_guide_grad, that family's inputs-only backward with g_eps_x = g0 and the zero g_eps_h, k_step_update<MoveGuided>.  The update runs
 // alone: the width-generic training forward builds its own edges on every call (run_dynamics_wide: `if (!h->edges_built)`, and it
 // leaves edges_built false), on a 128 / 16 handle too, and so does the tuned training forward (dyn_prologue's training forms), so no
 // form of this step builds the next call's edges and edges_built stays false behind it
@@ -3704,13 +3688,13 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     }
     rc = h->train_wide ? wide_train_backward(h, g_eps_h, g0, nullptr, jx, g_h, s) : tuned_train_backward(h, g_eps_h, g0, nullptr, jx, g_h, s);
     if (rc) return rc;
-    const PinParams q = pin_params(h, pin);
-    const GuideShiftParams gs = guide_shift_params(h, st);
-    const GuideFeatParams gf = h->types.on ? guide_feat_params(h, st, live_h) : GuideFeatParams{};
+    StepMove mv;
+    mv.build_form = false;
+    mv.args.kind = h->types.on ? StepMoveArgs::GUIDED_TYPES : StepMoveArgs::GUIDED;
+    mv.args.pin = pin_params(h, pin); mv.args.shift = guide_shift_params(h, st);
+    if (h->types.on) mv.args.feat = guide_feat_params(h, st, live_h);
     h->guide_have = true;
     h->types.have = h->types.on; h->types.live = live_h;
-    StepMove mv{StepMove::GUIDED, false, &q, nullptr, &gs, -1};
-    if (h->types.on) mv.feat = &gf;
     return step_end(h, sp, mv, s);
 }
 

@@ -1320,6 +1320,7 @@ __device__ unsigned long long* g_build_stamps = nullptr;      // [B][32]
 // k_n16_tail, pf_n16.hip, runs the same body behind its noise head)
 #define SB_STAMP(k) BSTAMP(k)
 #include "pf_stepbuild.h"
+#include "pf_stepmove.h"
 using pfsb::sqdist_rn; using pfsb::dkey; using pfsb::wave_min_u64; using pfsb::wave_incl_scan_u32;
 // exclusive scan of one value per thread over a 256-thread block; returns this thread's offset, *total receives the
 // block total.  The value packs three counters (bits 0-15, 16-27, 28-63: the fp edges, the active-atom list and its pp
@@ -1776,67 +1777,31 @@ __global__ __launch_bounds__(64) void k_segment_mean(const float4* xn, const int
     }
 }
 
-// z_s = mu + sigma * noise ; remove the pharmacophore COM from pharm and prot coordinates
-// (pharmacodiff.py:413-429).  One workgroup per graph.
-__device__ __forceinline__ void step_update_body(const StepParams& p, const int g) {
-    __shared__ float com[3];
-    __shared__ float red[4][3];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
-    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int f = f0 + tid; f < f1; f += 256) {
-        const float4 x = p.xn[p.Np_tot + f];
-        const float* nz = p.noise + (size_t)f * (3 + p.nf);
-        float m[3];
-        const float xi[3] = {x.x, x.y, x.z};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float e = p.eps_x[(size_t)f * 3 + c];
-            m[c] = pf_feat_update(xi[c], e, nz[c], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_coord);      // (pf_device.h: the one place the update is written)
-        }
-        p.xn[p.Np_tot + f] = make_float4(m[0], m[1], m[2], 0.f);
-        sx += m[0]; sy += m[1]; sz += m[2];
-        for (int k = 0; k < p.nf; ++k) {
-            const float hv = p.pharm_h[(size_t)f * p.nf + k];
-            const float e = p.eps_h[(size_t)f * p.nf + k];
-            p.pharm_h[(size_t)f * p.nf + k] = pf_feat_update(hv, e, nz[3 + k], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_feat);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
-    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
-    __syncthreads();
-    if (tid == 0) {
-        const float n = (float)max(f1 - f0, 1);
-        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
-    }
-    __syncthreads();
-    const float cx = com[0], cy = com[1], cz = com[2];
-    for (int f = f0 + tid; f < f1; f += 256) {
-        float4 x = p.xn[p.Np_tot + f];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[p.Np_tot + f] = x;
-    }
-    for (int i = p0 + tid; i < p1; i += 256) {
-        float4 x = p.xn[i];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[i] = x;
-    }
-}
-__global__ __launch_bounds__(256) void k_step_update(const StepParams p) { step_update_body(p, blockIdx.x); }
-// p(z_s | z_t) update of graph g and, on the new coordinates, the dynamic edges of the NEXT dynamics call: both are
-// one-workgroup-per-graph kernels, and with the encoders computed on the fly by the row-group kernels the edge build is
-// all that a step's first launch would do -- one launch less per denoising step.
 // ---------------------------------------------------------------------------------------------
-// k_step_build_fast: the same update + edge build for the common shape (kNN pf edges, pockets of at most 512 atoms, one
+// The move a step ends with (pf_stepmove.h: one skeleton, one struct per run kind), alone or with the dynamic edges of the NEXT
+// dynamics call built on the new coordinates: both are one-workgroup-per-graph bodies, and with the encoders computed on the fly by
+// the row-group kernels the edge build is all that a step's first launch would do -- one launch less per denoising step.
+// ---------------------------------------------------------------------------------------------
+template <class M>
+__global__ __launch_bounds__(256) void k_step_update(const StepParams sp, const M mv) {
+    step_move_body(sp, mv, blockIdx.x);
+}
+template <class M>
+__global__ __launch_bounds__(256) void k_step_build(const StepParams sp, const M mv, const BuildParams bp) {
+    BSTAMP(0);                                         // kernel start
+    step_move_body(sp, mv, blockIdx.x);
+    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
+    build_body(bp, blockIdx.x);
+}
+// ---------------------------------------------------------------------------------------------
+// k_step_build_fast: the plain move + edge build for the common shape (kNN pf edges, pockets of at most 512 atoms, one
 // atom per thread), organised around what a launch actually pays for here: every launch starts with cold caches (each
 // XCD's L2 is invalidated at kernel boundaries), a dependent global round trip costs ~2,000 cycles, and __syncthreads
-// drains every outstanding load.  The generic bodies above make ~10 dependent trips per graph (44 k cycles); this
+// drains every outstanding load.  The generic build_body makes a dependent trip per phase (~10 per graph with the move in front, 44 k cycles); this
 // kernel makes three: (A) the graph's pointers and regions, (B) every input row -- pharm state, eps, noise, protein
 // coordinates, the static in-edge descriptors -- (C) the static pp sources of the thread's atom.  The updated
 // coordinates stay in LDS for the neighbour searches (8 waves: one pharmacophore center each), and nothing is read back
-// from global memory.  Results are identical to k_step_build (same arithmetic, same orderings).
+// from global memory.  Results are identical to k_step_build<MovePlain> (same arithmetic, same orderings).
 // ---------------------------------------------------------------------------------------------
 // (the body: pf_stepbuild.h.  The leading scalar arguments repeat the fields round trip (A) needs: preloaded into scalar
 // registers with the wave, -mllvm -amdgpu-kernarg-preload-count in the Makefile, so (A) does not wait for the kernel-argument segment)
@@ -1849,247 +1814,11 @@ __global__ __launch_bounds__(512) void k_step_build_fast(const int* __restrict__
     pfsb::step_build_fast_body<512>(g, a_prot_ptr, a_pharm_ptr, a_reg, a_B, a_Np_tot, sp, p, eps, L);
 }
 
-__global__ __launch_bounds__(256) void k_step_build(const StepParams sp, const BuildParams bp) {
-    BSTAMP(0);                                         // kernel start
-    step_update_body(sp, blockIdx.x);
-    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
-    build_body(bp, blockIdx.x);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Multistep move (pf_denoise_step_ms): step_update_body with the linear combination pf_ms_update in place of pf_feat_update and
-// no noise read.  The thread that reads an element's output also stores it as that element's history, for the next multistep
-// move; the history is read only where c1 != 0.  The COM of the graph's centers and its removal from centers and protein are
-// step_update_body's, in its reduction order.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ms_update_body(const StepParams& p, const MsParams& q, const int g) {
-    __shared__ float com[3];
-    __shared__ float red[4][3];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
-    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
-    const bool sec_x = q.c1_x != 0.f, sec_h = q.c1_h != 0.f;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int f = f0 + tid; f < f1; f += 256) {
-        const float4 x = p.xn[p.Np_tot + f];
-        float* hs = q.hist + (size_t)f * (3 + p.nf);
-        float m[3];
-        const float xi[3] = {x.x, x.y, x.z};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float e = p.eps_x[(size_t)f * 3 + c];
-            const float ep = sec_x ? hs[c] : 0.f;
-            m[c] = pf_ms_update(xi[c], e, ep, q.cz_x, q.c0_x, q.c1_x, sec_x);
-            hs[c] = e;
-        }
-        p.xn[p.Np_tot + f] = make_float4(m[0], m[1], m[2], 0.f);
-        sx += m[0]; sy += m[1]; sz += m[2];
-        for (int k = 0; k < p.nf; ++k) {
-            const float hv = p.pharm_h[(size_t)f * p.nf + k];
-            const float e = p.eps_h[(size_t)f * p.nf + k];
-            const float ep = sec_h ? hs[3 + k] : 0.f;
-            p.pharm_h[(size_t)f * p.nf + k] = pf_ms_update(hv, e, ep, q.cz_h, q.c0_h, q.c1_h, sec_h);
-            hs[3 + k] = e;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
-    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
-    __syncthreads();
-    if (tid == 0) {
-        const float n = (float)max(f1 - f0, 1);
-        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
-    }
-    __syncthreads();
-    const float cx = com[0], cy = com[1], cz = com[2];
-    for (int f = f0 + tid; f < f1; f += 256) {
-        float4 x = p.xn[p.Np_tot + f];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[p.Np_tot + f] = x;
-    }
-    for (int i = p0 + tid; i < p1; i += 256) {
-        float4 x = p.xn[i];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[i] = x;
-    }
-}
-__global__ __launch_bounds__(256) void k_step_update_ms(const StepParams p, const MsParams q) { ms_update_body(p, q, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_step_build_ms(const StepParams sp, const MsParams q, const BuildParams bp) {
-    ms_update_body(sp, q, blockIdx.x);
-    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
-    build_body(bp, blockIdx.x);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Pinned centers (replacement conditioning, pf_denoise_step_pinned): step_update_body with two selects in front of its
-// stores.  A center whose position is given (flag bit 0) becomes the given position noised to this step's level,
-// z_s = alpha_s * given + sigma_s * noise, with the step's own noise draw (its posterior sample is discarded); likewise a
-// center whose feature row is given (bit 1).  Given positions are in the caller's frame: sampler frame = caller's frame - D,
-// D = mean of the original protein coordinates - mean of the graph's CURRENT protein rows (pf_sample_frame's rule), so the
-// workgroup first reduces the current mean -- wave 0, in k_segment_mean's order.  Free centers take pf_feat_update as in
-// step_update_body and the COM sum keeps its reduction order.  One rounding per operation, as in pf_feat_update.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pf_pin_value(const float given, const float nz, const float alpha_s, const float sigma_s) {
-#pragma clang fp contract(off)
-    const float a = alpha_s * given, n = sigma_s * nz;
-    return a + n;
-}
-// The guided step's move (reconstruction guidance, pf_denoise_step_guided) for one center: the gradient of the restraint energy
-// w.r.t. x_t from g0 = dE/dy and the dynamics' VJP J(g0), the shift of the posterior mean, and its clip.  One rounding per
-// operation, like pf_feat_update.  gr / sh: what the step applies (also stored for pf_debug_last_guidance)
-__device__ __forceinline__ void pf_guide_shift(const float* g0, const float* jx, const float alpha_t, const float sigma_t, const int ep_coord,
-                                               const float sigma_post, const float scale, const float clip, float* gr, float* sh) {
-#pragma clang fp contract(off)
-    const float ratio = sigma_t / alpha_t;
-    const float s2 = sigma_post * sigma_post;
-    const float k = scale * s2;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (ep_coord) gr[c] = jx[c];
-        else { const float a = g0[c] / alpha_t, b = ratio * jx[c]; gr[c] = a - b; }
-        sh[c] = k * gr[c];
-    }
-    const float n = sqrtf((sh[0] * sh[0] + sh[1] * sh[1]) + sh[2] * sh[2]);
-    if (clip > 0.f && n > clip) {
-        const float f = clip / n;
-        sh[0] *= f; sh[1] *= f; sh[2] *= f;
-    }
-}
-// The feature half of the guided move (type guidance, pf_guide_types_next) for one center's row of nf entries:
-//   grad_h = [g0_h / alpha_t, noise parameterisation of the features only] + phi_x J_h,  phi_x = -sigma_t / alpha_t or 1 (endpoint coordinates)
-//   shift_h = (feat_scale sigma_post^2) grad_h, clipped to the Euclidean norm `clip` over the row
-// It stores grad_h and the UNCLIPPED shift_h and returns the clip's factor (1: no clip).  One rounding per operation; the norm sums k ascending
-__device__ __forceinline__ float pf_guide_shift_h(const float* g0h, const float* jh, const int nf, const float alpha_t, const float sigma_t,
-                                                  const int ep_coord, const int ep_feat, const float sigma_post, const float scale,
-                                                  const float clip, float* gr, float* sh) {
-#pragma clang fp contract(off)
-    const float ratio = sigma_t / alpha_t;
-    const float s2 = sigma_post * sigma_post;
-    const float k = scale * s2;
-    float n2 = 0.f;
-    for (int c = 0; c < nf; ++c) {
-        const float j = jh[c];
-        float b;
-        if (ep_coord) b = j;
-        else { const float rj = ratio * j; b = -rj; }
-        float gv = b;
-        if (!ep_feat) { const float a = g0h[c] / alpha_t; gv = a + b; }
-        const float sv = k * gv;
-        gr[c] = gv; sh[c] = sv;
-        const float q = sv * sv;
-        n2 += q;
-    }
-    const float n = sqrtf(n2);
-    return (clip > 0.f && n > clip) ? clip / n : 1.0f;
-}
-// GUIDED: pinned_update_body with one more input -- the guided step's shift is taken off a free center's p(z_s | z_t) value in front
-// of the selects, and D[g] is the one k_guide_grad left (the same reduction of the same rows, which nobody has moved in between).
-// Without it: the pinned kernels' code as it was
-// FEAT (a guided run with type guidance, pf_guide_types_next): the feature rows are guided too -- a free center's feature row loses
-// shift_h in front of the `flag & 2` select, as its position loses the shift in front of `flag & 1`
-template <bool GUIDED, bool FEAT = false>
-__device__ __forceinline__ void pinned_update_body(const StepParams& p, const PinParams& q, const GuideShiftParams* gs, const int g,
-                                                   const GuideFeatParams* gf = nullptr) {
-    __shared__ float com[3];
-    __shared__ float red[4][3];
-    __shared__ float dfr[3];                            // D[g]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
-    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
-    if constexpr (GUIDED) {
-        if (tid < 3) dfr[tid] = gs->D[3 * g + tid];
-    } else if (wave == 0) {
-        float ax = 0.f, ay = 0.f, az = 0.f;
-        for (int i = p0 + lane; i < p1; i += 64) { const float4 x = p.xn[i]; ax += x.x; ay += x.y; az += x.z; }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o); }
-        if (lane == 0) {
-            const float n = (float)max(p1 - p0, 1);
-            dfr[0] = q.com_init[3 * g] - ax / n; dfr[1] = q.com_init[3 * g + 1] - ay / n; dfr[2] = q.com_init[3 * g + 2] - az / n;
-        }
-    }
-    __syncthreads();                                    // (the protein rows are not written before the second barrier below)
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int f = f0 + tid; f < f1; f += 256) {
-        const float4 x = p.xn[p.Np_tot + f];
-        const float* nz = p.noise + (size_t)f * (3 + p.nf);
-        const int flag = q.flags[f];
-        float m[3];
-        const float xi[3] = {x.x, x.y, x.z};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float e = p.eps_x[(size_t)f * 3 + c];
-            m[c] = (flag & 1) ? pf_pin_value(q.pin_x[(size_t)f * 3 + c] - dfr[c], nz[c], q.alpha_s, q.sigma_s)
-                              : pf_feat_update(xi[c], e, nz[c], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_coord);
-        }
-        if constexpr (GUIDED) {
-            float gr[3], sh[3];
-            pf_guide_shift(gs->g0 + (size_t)f * 3, gs->jx + (size_t)f * 3, gs->alpha_t, gs->sigma_t, p.ep_coord, p.sigma, gs->scale, gs->clip, gr, sh);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                gs->grad[(size_t)f * 3 + c] = gr[c]; gs->shift[(size_t)f * 3 + c] = sh[c];
-                if (!(flag & 1)) m[c] -= sh[c];         // (a position-pinned center ignores its shift)
-            }
-        }
-        p.xn[p.Np_tot + f] = make_float4(m[0], m[1], m[2], 0.f);
-        sx += m[0]; sy += m[1]; sz += m[2];
-        float hf = 1.0f;                                // FEAT: the clip's factor of this row
-        if constexpr (FEAT) hf = pf_guide_shift_h(gf->g0_h + (size_t)f * p.nf, gf->jh + (size_t)f * p.nf, p.nf, gs->alpha_t, gs->sigma_t, p.ep_coord,
-                                                  p.ep_feat, p.sigma, gf->scale, gf->clip, gf->grad_h + (size_t)f * p.nf, gf->shift_h + (size_t)f * p.nf);
-        for (int k = 0; k < p.nf; ++k) {
-            const float hv = p.pharm_h[(size_t)f * p.nf + k];
-            const float e = p.eps_h[(size_t)f * p.nf + k];
-            float fr = pf_feat_update(hv, e, nz[3 + k], p.a_ts, p.var, p.sigma, p.ep_zt, p.ep_pred, p.ep_feat);
-            if constexpr (FEAT) {
-                float sh = gf->shift_h[(size_t)f * p.nf + k];          // (this thread's own store, unclipped)
-                if (hf != 1.0f) { sh *= hf; gf->shift_h[(size_t)f * p.nf + k] = sh; }
-                fr -= sh;
-            }
-            p.pharm_h[(size_t)f * p.nf + k] = (flag & 2) ? pf_pin_value(q.pin_h[(size_t)f * p.nf + k] / q.feat_norm, nz[3 + k], q.alpha_s, q.sigma_s)
-                                                         : fr;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
-    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
-    __syncthreads();
-    if (tid == 0) {
-        const float n = (float)max(f1 - f0, 1);
-        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
-    }
-    __syncthreads();
-    const float cx = com[0], cy = com[1], cz = com[2];
-    for (int f = f0 + tid; f < f1; f += 256) {
-        float4 x = p.xn[p.Np_tot + f];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[p.Np_tot + f] = x;
-    }
-    for (int i = p0 + tid; i < p1; i += 256) {
-        float4 x = p.xn[i];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[i] = x;
-    }
-}
-__global__ __launch_bounds__(256) void k_step_update_pinned(const StepParams p, const PinParams q) { pinned_update_body<false>(p, q, nullptr, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_step_build_pinned(const StepParams sp, const PinParams q, const BuildParams bp) {
-    pinned_update_body<false>(sp, q, nullptr, blockIdx.x);
-    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
-    build_body(bp, blockIdx.x);
-}
-// the guided step's update, alone: its dynamics call is the width-generic training forward, which builds its own edges
-__global__ __launch_bounds__(256) void k_step_update_guided(const StepParams p, const PinParams q, const GuideShiftParams gs) {
-    pinned_update_body<true>(p, q, &gs, blockIdx.x);
-}
-// ... and with type guidance armed: the feature rows take their shift as well
-__global__ __launch_bounds__(256) void k_step_update_guided_types(const StepParams p, const PinParams q, const GuideShiftParams gs,
-                                                                  const GuideFeatParams gf) {
-    pinned_update_body<true, true>(p, q, &gs, blockIdx.x, &gf);
-}
 // ---------------------------------------------------------------------------------------------
 // Guided sampling (pf_denoise_step_guided): restraint energies on the predicted clean centers, in the caller's frame.
 //   y_f = x0_hat[f] + D[g],  x0_hat = (x_t - sigma_t eps_x) / alpha_t (noise parameterisation) or eps_x (endpoint)
 //   attract: E = w max(0, rho - r)^2   repel: E = w max(0, r - rho)^2   rho = |y_f - p|;  rho == 0: no gradient
-// One workgroup per graph.  D[g] as in pinned_update_body (wave 0, k_segment_mean's order).  One thread per center walks the
+// One workgroup per graph.  D[g]: frame_offset (pf_stepmove.h), also stored for the guided move.  One thread per center walks the
 // graph's restraints in ascending order and stores g0[f] = sum_j dE_j/dy_f; thread 0 then sums E over (f ascending, j ascending).
 // A launch starts with cold caches: the thread's center rows and wave 0's first protein row are requested before the first wait
 // (4.12.1 of DESIGN.md), so the reduction in front costs no round trip of its own.
@@ -2134,16 +1863,10 @@ __global__ __launch_bounds__(256) void k_guide_grad(const StepParams p, const Gu
     if (own_p) pa = p.xn[p0 + lane];
     asm volatile("" :: "v"((xa.x + xa.y) + (xa.z + ea[0]) + (ea[1] + ea[2])), "v"(pa.x) : "memory");      // every row is requested before the first wait
     if (wave == 0) {
-        float ax = 0.f, ay = 0.f, az = 0.f;
-        if (own_p) { ax += pa.x; ay += pa.y; az += pa.z; }
-        for (int i = p0 + lane + 64; i < p1; i += 64) { const float4 x = p.xn[i]; ax += x.x; ay += x.y; az += x.z; }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o); }
-        if (lane == 0) {
-            const float n = (float)max(p1 - p0, 1);
-            dfr[0] = q.com_init[3 * g] - ax / n; dfr[1] = q.com_init[3 * g + 1] - ay / n; dfr[2] = q.com_init[3 * g + 2] - az / n;
-            q.D[3 * g] = dfr[0]; q.D[3 * g + 1] = dfr[1]; q.D[3 * g + 2] = dfr[2];
-        }
+        const float ci[3] = {q.com_init[3 * g], q.com_init[3 * g + 1], q.com_init[3 * g + 2]};
+        float d[3];
+        frame_offset(p.xn, p0, p1, lane, pa, ci, d);
+        if (lane == 0) for (int c = 0; c < 3; ++c) { dfr[c] = d[c]; q.D[3 * g + c] = d[c]; }
     }
     __syncthreads();
     for (int f = fa; f < f1; f += 256) {
@@ -2181,214 +1904,6 @@ __global__ __launch_bounds__(256) void k_guide_grad(const StepParams p, const Gu
         q.energy[g] = E;
         if (q.traj_energy) q.traj_energy[g] = E;
     }
-}
-// ---------------------------------------------------------------------------------------------
-// Resampling jump of a pinned run (pf_renoise_step): the whole state of graph g goes from level b back up to level a > b,
-// z_a = alpha_{a|b} * z_b + sigma_{a|b} * noise, for every center -- pinned or free -- and for coordinates and feature rows
-// alike; then the COM of all centers is removed from centers and protein in step_update_body's reduction order.  Nothing of the
-// caller's frame enters, so no protein mean is reduced in front.  A launch starts with cold caches and a dependent global round
-// trip is its unit of cost: after the graph's four pointers every row the thread needs -- its center's state and noise, its
-// first protein row -- is requested before the first barrier, and the updated coordinates stay in registers between the two
-// passes (only a graph of more than 256 centers reads the rows beyond the thread's first back, its own stores).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pf_renoise_value(const float z, const float nz, const float alpha_ts, const float sigma_ts) {
-#pragma clang fp contract(off)
-    const float a = alpha_ts * z, n = sigma_ts * nz;
-    return a + n;
-}
-__device__ __forceinline__ void renoise_body(const StepParams& p, const RenoiseParams& r, const int g) {
-    __shared__ float com[3];
-    __shared__ float red[4][3];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
-    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
-    const int fa = f0 + tid, ia = p0 + tid;            // the thread's first center and first atom
-    const bool own_f = fa < f1, own_i = ia < p1;
-    float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (own_i) pa = p.xn[ia];                           // shifted behind the second barrier
-    float m[3] = {0.f, 0.f, 0.f};
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    if (own_f) {
-        const float* __restrict__ nz = p.noise + (size_t)fa * (3 + p.nf);
-        float* __restrict__ hr = p.pharm_h + (size_t)fa * p.nf;
-        const float4 xa = p.xn[p.Np_tot + fa];
-        const float nx[3] = {nz[0], nz[1], nz[2]};
-        float hv[8], nv[8];                             // the first eight features (pharm_nf is 6 in every shipped configuration)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const bool in = j < p.nf;
-            hv[j] = in ? hr[j] : 0.f; nv[j] = in ? nz[3 + j] : 0.f;
-        }
-        {   // every row is requested before the first wait (an empty asm the compiler cannot move the loads across, as in pf_stepbuild.h)
-            float pin = ((xa.x + xa.y) + (xa.z + nx[0])) + (nx[1] + nx[2]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pin += hv[j] + nv[j];
-            asm volatile("" :: "v"(pin), "v"(pa.x) : "memory");
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) if (j < p.nf) hr[j] = pf_renoise_value(hv[j], nv[j], r.alpha_ts, r.sigma_ts);
-        for (int k = 8; k < p.nf; ++k) hr[k] = pf_renoise_value(hr[k], nz[3 + k], r.alpha_ts, r.sigma_ts);
-        m[0] = pf_renoise_value(xa.x, nx[0], r.alpha_ts, r.sigma_ts);
-        m[1] = pf_renoise_value(xa.y, nx[1], r.alpha_ts, r.sigma_ts);
-        m[2] = pf_renoise_value(xa.z, nx[2], r.alpha_ts, r.sigma_ts);
-        sx += m[0]; sy += m[1]; sz += m[2];
-    }
-    for (int f = fa + 256; f < f1; f += 256) {          // more than 256 centers in the graph: through memory, as step_update_body does
-        const float4 x = p.xn[p.Np_tot + f];
-        const float* nz = p.noise + (size_t)f * (3 + p.nf);
-        const float q0 = pf_renoise_value(x.x, nz[0], r.alpha_ts, r.sigma_ts);
-        const float q1 = pf_renoise_value(x.y, nz[1], r.alpha_ts, r.sigma_ts);
-        const float q2 = pf_renoise_value(x.z, nz[2], r.alpha_ts, r.sigma_ts);
-        p.xn[p.Np_tot + f] = make_float4(q0, q1, q2, 0.f);
-        sx += q0; sy += q1; sz += q2;
-        for (int k = 0; k < p.nf; ++k)
-            p.pharm_h[(size_t)f * p.nf + k] = pf_renoise_value(p.pharm_h[(size_t)f * p.nf + k], nz[3 + k], r.alpha_ts, r.sigma_ts);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
-    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
-    __syncthreads();
-    if (tid == 0) {
-        const float n = (float)max(f1 - f0, 1);
-        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
-    }
-    __syncthreads();
-    const float cx = com[0], cy = com[1], cz = com[2];
-    if (own_f) p.xn[p.Np_tot + fa] = make_float4(m[0] - cx, m[1] - cy, m[2] - cz, 0.f);
-    for (int f = fa + 256; f < f1; f += 256) {
-        float4 x = p.xn[p.Np_tot + f];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[p.Np_tot + f] = x;
-    }
-    if (own_i) { pa.x -= cx; pa.y -= cy; pa.z -= cz; p.xn[ia] = pa; }
-    for (int i = ia + 256; i < p1; i += 256) {
-        float4 x = p.xn[i];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[i] = x;
-    }
-}
-__global__ __launch_bounds__(256) void k_step_update_renoise(const StepParams p, const RenoiseParams r) { renoise_body(p, r, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_step_build_renoise(const StepParams sp, const RenoiseParams r, const BuildParams bp) {
-    renoise_body(sp, r, blockIdx.x);
-    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
-    build_body(bp, blockIdx.x);
-}
-// ---------------------------------------------------------------------------------------------
-// Seeded begin (pf_sample_seed_next): in place of "state := noise0", every center of graph g becomes the caller's seed noised
-// forward to level a, z_a = alpha_a * seed + sigma_a * noise0 -- pf_pin_value's arithmetic with every center flagged 3.  Seed
-// positions are in the caller's frame, so D[g] is reduced first as pinned_update_body does (wave 0, k_segment_mean's order);
-// then the COM of all centers is removed from centers and protein in step_update_body's reduction order.  renoise_body's
-// form: after the graph's four pointers every row the thread needs -- its center's seed and noise rows, its first protein row
-// (wave 0's also serve the reduction), the graph's c_init -- is requested before the first wait, and the new coordinates stay
-// in registers between the two passes.  The state's own rows are not read: whatever the previous run left in them is dead.
-// The feature rows also go to the center-hoist snapshot (h_snap_out) the first step's hoist workgroups read.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void seed_body(const StepParams& p, const SeedParams& q, const int g) {
-    __shared__ float com[3];
-    __shared__ float red[4][3];
-    __shared__ float dfr[3];                            // D[g]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int f0 = p.pharm_ptr[g], f1 = p.pharm_ptr[g + 1];
-    const int p0 = p.prot_ptr[g], p1 = p.prot_ptr[g + 1];
-    const int fa = f0 + tid, ia = p0 + tid;            // the thread's first center and first atom
-    const bool own_f = fa < f1, own_i = ia < p1;
-    float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (own_i) pa = p.xn[ia];                           // wave 0: the reduction's first row; shifted behind the third barrier
-    float ci[3] = {0.f, 0.f, 0.f};
-    if (tid == 0) for (int c = 0; c < 3; ++c) ci[c] = q.com_init[3 * g + c];
-    float sv[3] = {0.f, 0.f, 0.f}, nx[3] = {0.f, 0.f, 0.f};
-    float hv[8], nv[8];                                 // the first eight features (pharm_nf is 6 in every shipped configuration)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { hv[j] = 0.f; nv[j] = 0.f; }
-    if (own_f) {
-        const float* __restrict__ nz = p.noise + (size_t)fa * (3 + p.nf);
-        const float* __restrict__ sh = q.seed_h + (size_t)fa * p.nf;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { sv[c] = q.seed_x[(size_t)fa * 3 + c]; nx[c] = nz[c]; }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) if (j < p.nf) { hv[j] = sh[j]; nv[j] = nz[3 + j]; }
-    }
-    {   // every row is requested before the first wait (an empty asm the compiler cannot move the loads across, as in pf_stepbuild.h)
-        float pin = ((sv[0] + sv[1]) + (sv[2] + nx[0])) + (nx[1] + nx[2]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pin += hv[j] + nv[j];
-        asm volatile("" :: "v"(pin), "v"(pa.x), "v"((ci[0] + ci[1]) + ci[2]) : "memory");
-    }
-    if (wave == 0) {
-        float ax = 0.f, ay = 0.f, az = 0.f;
-        if (own_i) { ax += pa.x; ay += pa.y; az += pa.z; }
-        for (int i = ia + 64; i < p1; i += 64) { const float4 x = p.xn[i]; ax += x.x; ay += x.y; az += x.z; }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o); }
-        if (lane == 0) {
-            const float n = (float)max(p1 - p0, 1);
-            dfr[0] = ci[0] - ax / n; dfr[1] = ci[1] - ay / n; dfr[2] = ci[2] - az / n;
-        }
-    }
-    __syncthreads();                                    // (the protein rows are not written before the third barrier below)
-    float m[3] = {0.f, 0.f, 0.f};
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    if (own_f) {
-        const float* __restrict__ nz = p.noise + (size_t)fa * (3 + p.nf);
-        const float* __restrict__ sh = q.seed_h + (size_t)fa * p.nf;
-        float* __restrict__ hr = p.pharm_h + (size_t)fa * p.nf;
-        float* __restrict__ hs = p.h_snap_out ? p.h_snap_out + (size_t)fa * p.nf : nullptr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) if (j < p.nf) {
-            const float hn = pf_pin_value(hv[j] / q.feat_norm, nv[j], q.alpha_a, q.sigma_a);
-            hr[j] = hn;
-            if (hs) hs[j] = hn;
-        }
-        for (int k = 8; k < p.nf; ++k) {
-            const float hn = pf_pin_value(sh[k] / q.feat_norm, nz[3 + k], q.alpha_a, q.sigma_a);
-            hr[k] = hn;
-            if (hs) hs[k] = hn;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) m[c] = pf_pin_value(sv[c] - dfr[c], nx[c], q.alpha_a, q.sigma_a);
-        sx += m[0]; sy += m[1]; sz += m[2];
-    }
-    for (int f = fa + 256; f < f1; f += 256) {          // more than 256 centers in the graph: through memory, as step_update_body does
-        const float* nz = p.noise + (size_t)f * (3 + p.nf);
-        float w[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) w[c] = pf_pin_value(q.seed_x[(size_t)f * 3 + c] - dfr[c], nz[c], q.alpha_a, q.sigma_a);
-        p.xn[p.Np_tot + f] = make_float4(w[0], w[1], w[2], 0.f);
-        sx += w[0]; sy += w[1]; sz += w[2];
-        for (int k = 0; k < p.nf; ++k) {
-            const float hn = pf_pin_value(q.seed_h[(size_t)f * p.nf + k] / q.feat_norm, nz[3 + k], q.alpha_a, q.sigma_a);
-            p.pharm_h[(size_t)f * p.nf + k] = hn;
-            if (p.h_snap_out) p.h_snap_out[(size_t)f * p.nf + k] = hn;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
-    if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; }
-    __syncthreads();
-    if (tid == 0) {
-        const float n = (float)max(f1 - f0, 1);
-        for (int c = 0; c < 3; ++c) com[c] = (f1 > f0) ? (((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / n) : 0.f;
-    }
-    __syncthreads();
-    const float cx = com[0], cy = com[1], cz = com[2];
-    if (own_f) p.xn[p.Np_tot + fa] = make_float4(m[0] - cx, m[1] - cy, m[2] - cz, 0.f);
-    for (int f = fa + 256; f < f1; f += 256) {
-        float4 x = p.xn[p.Np_tot + f];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[p.Np_tot + f] = x;
-    }
-    if (own_i) { pa.x -= cx; pa.y -= cy; pa.z -= cz; p.xn[ia] = pa; }
-    for (int i = ia + 256; i < p1; i += 256) {
-        float4 x = p.xn[i];
-        x.x -= cx; x.y -= cy; x.z -= cz;
-        p.xn[i] = x;
-    }
-}
-__global__ __launch_bounds__(256) void k_step_update_seed(const StepParams p, const SeedParams q) { seed_body(p, q, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_step_build_seed(const StepParams sp, const SeedParams q, const BuildParams bp) {
-    seed_body(sp, q, blockIdx.x);
-    __syncthreads();                                   // this workgroup's coordinate writes are visible to all its waves
-    build_body(bp, blockIdx.x);
 }
 // the given values back, bit for bit (pf_sample_end and the last trajectory frame of a pinned run); out_x / out_h may be NULL
 __global__ void k_pin_restore(const int* __restrict__ flags, const float* __restrict__ pin_x, const float* __restrict__ pin_h,
@@ -2442,6 +1957,13 @@ __global__ __launch_bounds__(256) void k_pp_radius(const float4* xn, const int* 
 // ---------------------------------------------------------------------------------------------
 // launch helpers (called from pf_host.cpp)
 // ---------------------------------------------------------------------------------------------
+template <class M>
+static void launch_move(const StepParams* sp, const M& mv, const BuildParams* bp, hipStream_t s) {
+    if constexpr (M::BUILD_FORM) {
+        if (bp) { hipLaunchKernelGGL(k_step_build<M>, dim3(sp->B), dim3(256), 0, s, *sp, mv, *bp); return; }
+    }
+    hipLaunchKernelGGL(k_step_update<M>, dim3(sp->B), dim3(256), 0, s, *sp, mv);
+}
 extern "C" {
 #ifdef PF_STAMPS
 int pfk_build_set_stamp_buffer(unsigned long long* dev) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_build_stamps), &dev, sizeof(dev)); }
@@ -2551,58 +2073,27 @@ void pfk_segment_mean(const float4* xn, const int* ptr, int base, int B, float* 
     if (B == 0) return;
     hipLaunchKernelGGL(k_segment_mean, dim3(B), dim3(64), 0, s, xn, ptr, base, out);
 }
-void pfk_step_build(const StepParams* sp, const BuildParams* bp, int fast, hipStream_t s) {
+// the plain move's fast form (step_build_fast_ok)
+void pfk_step_build_fast(const StepParams* sp, const BuildParams* bp, hipStream_t s) {
     if (sp->B == 0) return;
-    if (fast) hipLaunchKernelGGL(k_step_build_fast, dim3(sp->B), dim3(512), 0, s, bp->prot_ptr, bp->pharm_ptr, bp->reg, bp->B, bp->Np_tot, *sp, *bp);
-    else hipLaunchKernelGGL(k_step_build, dim3(sp->B), dim3(256), 0, s, *sp, *bp);
+    hipLaunchKernelGGL(k_step_build_fast, dim3(sp->B), dim3(512), 0, s, bp->prot_ptr, bp->pharm_ptr, bp->reg, bp->B, bp->Np_tot, *sp, *bp);
 }
-void pfk_step_update(const StepParams* p, hipStream_t s) {
-    if (p->B == 0) return;
-    hipLaunchKernelGGL(k_step_update, dim3(p->B), dim3(256), 0, s, *p);
-}
-void pfk_step_build_pinned(const StepParams* sp, const PinParams* q, const BuildParams* bp, hipStream_t s) {
-    if (sp->B == 0) return;
-    hipLaunchKernelGGL(k_step_build_pinned, dim3(sp->B), dim3(256), 0, s, *sp, *q, *bp);
-}
-void pfk_step_update_pinned(const StepParams* p, const PinParams* q, hipStream_t s) {
-    if (p->B == 0) return;
-    hipLaunchKernelGGL(k_step_update_pinned, dim3(p->B), dim3(256), 0, s, *p, *q);
-}
-void pfk_step_update_guided(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, hipStream_t s) {
-    if (p->B == 0) return;
-    hipLaunchKernelGGL(k_step_update_guided, dim3(p->B), dim3(256), 0, s, *p, *q, *gs);
-}
-void pfk_step_update_guided_types(const StepParams* p, const PinParams* q, const GuideShiftParams* gs, const GuideFeatParams* gf, hipStream_t s) {
-    if (p->B <= 0) return;
-    hipLaunchKernelGGL(k_step_update_guided_types, dim3(p->B), dim3(256), 0, s, *p, *q, *gs, *gf);
+// every move of the sampler (StepMoveArgs: the tag and that move's parameters); bp NULL: the move alone
+void pfk_step_move(const StepParams* sp, const StepMoveArgs* a, const BuildParams* bp, hipStream_t s) {
+    if (sp->B <= 0) return;
+    switch (a->kind) {
+    case StepMoveArgs::PLAIN: launch_move(sp, MovePlain{}, bp, s); break;
+    case StepMoveArgs::MS: { MoveMs m; m.q = a->ms; launch_move(sp, m, bp, s); break; }
+    case StepMoveArgs::PINNED: { MovePinned m; m.q = a->pin; launch_move(sp, m, bp, s); break; }
+    case StepMoveArgs::GUIDED: { MoveGuided<false> m; m.q = a->pin; m.gs = a->shift; m.gf = a->feat; launch_move(sp, m, bp, s); break; }
+    case StepMoveArgs::GUIDED_TYPES: { MoveGuided<true> m; m.q = a->pin; m.gs = a->shift; m.gf = a->feat; launch_move(sp, m, bp, s); break; }
+    case StepMoveArgs::RENOISE: { MoveRenoise m; m.q = a->renoise; launch_move(sp, m, bp, s); break; }
+    case StepMoveArgs::SEED: { MoveSeed m; m.q = a->seed; launch_move(sp, m, bp, s); break; }
+    }
 }
 void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s) {
     if (p->B == 0) return;
     hipLaunchKernelGGL(k_guide_grad, dim3(p->B), dim3(256), 0, s, *p, *q);
-}
-void pfk_step_build_renoise(const StepParams* sp, const RenoiseParams* r, const BuildParams* bp, hipStream_t s) {
-    if (sp->B == 0) return;
-    hipLaunchKernelGGL(k_step_build_renoise, dim3(sp->B), dim3(256), 0, s, *sp, *r, *bp);
-}
-void pfk_step_update_renoise(const StepParams* p, const RenoiseParams* r, hipStream_t s) {
-    if (p->B == 0) return;
-    hipLaunchKernelGGL(k_step_update_renoise, dim3(p->B), dim3(256), 0, s, *p, *r);
-}
-void pfk_step_build_seed(const StepParams* sp, const SeedParams* q, const BuildParams* bp, hipStream_t s) {
-    if (sp->B == 0) return;
-    hipLaunchKernelGGL(k_step_build_seed, dim3(sp->B), dim3(256), 0, s, *sp, *q, *bp);
-}
-void pfk_step_update_seed(const StepParams* p, const SeedParams* q, hipStream_t s) {
-    if (p->B == 0) return;
-    hipLaunchKernelGGL(k_step_update_seed, dim3(p->B), dim3(256), 0, s, *p, *q);
-}
-void pfk_step_build_ms(const StepParams* sp, const MsParams* q, const BuildParams* bp, hipStream_t s) {
-    if (sp->B == 0) return;
-    hipLaunchKernelGGL(k_step_build_ms, dim3(sp->B), dim3(256), 0, s, *sp, *q, *bp);
-}
-void pfk_step_update_ms(const StepParams* p, const MsParams* q, hipStream_t s) {
-    if (p->B == 0) return;
-    hipLaunchKernelGGL(k_step_update_ms, dim3(p->B), dim3(256), 0, s, *p, *q);
 }
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s) {
     if (n == 0 || (!out_x && !out_h)) return;

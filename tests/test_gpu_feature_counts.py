@@ -13,7 +13,7 @@ of ten or more.  (pharm_nf, rec_nf) and why:
     (16, 40)    SB_MAXNF; no n16 tail packing; the exchange row holds 19 of 20 words
     (6, 127) / (6, 130)   the static hoist's gate rec_nf < 128 on and off (pf_k = 16)
     (7, 33)     radius pf edges (pf_k = 0): an atom is the source of many pf edges, the type tables serve them without the fused launch
-    (9, 11)     the first pharm_nf beyond the eight features the renoise and seed moves keep in registers
+    (9, 11)     the first pharm_nf beyond the eight features a move keeps in registers (pf_stepmove.h; the pinned move: six)
 
 Tolerances are the suite's own: a dynamics call 2e-4 + 2e-4 |ref| plus the fp64 budget of helpers.check_live, edge sets exact,
 sampler states 2e-4 (i + 1) after step i, whole runs 5e-3, gradients per 16 x 16 block inside grad_budget's fp64 budget, the
@@ -283,8 +283,8 @@ def test_other_step_kinds(pharm_nf, rec_nf, kind, monkeypatch):
     """A pinned run with one resampling jump (D(23) D(22) R(22 -> 24) D(23)), a seeded run from level 4 and a second-order
     multistep run over 24, 18, 12, 6, 0 at T = 24, precision 0.25: x_0, h_0 and every frame against the CPU compositions of
     resample_ref / seeded_ref / fewstep_ref at rtol = atol = 5e-3 (test_gpu_resample.check_run, test_gpu_seeded.check); and the
-    same run on the generic update + build bodies (PFDYN_NO_FAST_BUILD=1) bit for bit.  pharm_nf 9 and 16: the renoise and seed
-    moves keep eight features in registers and loop over the rest."""
+    same run on the generic update + build bodies (PFDYN_NO_FAST_BUILD=1) bit for bit.  pharm_nf 9 and 16: the moves
+    keep eight features (pinned: six) in registers and loop over the rest."""
     from test_gpu_seeded import check
     # (the plain steps of a seeded run end on the merged launch, which leaves the center-hoist tables; they equal the on-the-fly
     # encoding up to summation order, not bit for bit: test_sampler_run_center_hoist compares them)

@@ -289,7 +289,7 @@ def test_seeded_multistep_run():
 
 # 8. the width-generic family
 def test_width_generic_family():
-    """(64, 32), N = 4 of 12: the move runs alone (k_step_update_ms), the family builds its own edges; multistep and strided"""
+    """(64, 32), N = 4 of 12: the move runs alone (k_step_update<MoveMs>), the family builds its own edges; multistep and strided"""
     import guidance_ref as G
     cfg, sd, k, batch, noise, pins, com, _ = G.wide_case()
     n_t, N, fnorm = G.WIDE_T, 4, 2.0

@@ -644,7 +644,7 @@ def test_endpoint_parameterisation_step_live_head():
 def test_fused_update_and_edge_build_variants_agree(case, monkeypatch):
     """A denoising step ends with k_step_build_fast (sampler update + the next call's edge build, one atom per
     thread, three dependent global round trips) when pf edges are kNN and pockets have at most 512 atoms.  It must
-    reproduce the generic bodies (PFDYN_NO_FAST_BUILD=1: k_step_build) and the separate launches of the tile-kernel
+    reproduce the generic bodies (PFDYN_NO_FAST_BUILD=1: k_step_build<MovePlain>) and the separate launches of the tile-kernel
     path bit for bit: same edge sets, same orderings, same arithmetic -- ragged batch, several steps.  (The optional tail
     launch, which runs the same fast body behind the node update + head: test_gpu_n16.py::test_tail_launch_steps_equal_separate_launches.)"""
     monkeypatch.setenv("PFDYN_NO_CENTER_HOIST", "1")       # (only the merged launch leaves the center-hoist tables: its own test compares them)

@@ -180,7 +180,7 @@ def test_step_api_equals_whole_loop_and_state_errors():
 
 
 def test_width_generic_family():
-    """(64, 32): the update runs alone (k_step_update_pinned), the family launches its own encoders and edge build.  The given
+    """(64, 32): the update runs alone (k_step_update<MovePinned>), the family launches its own encoders and edge build.  The given
     rows are divided by a feat_norm_constant of 2 here."""
     n_t, fnorm = 20, 2.0
     cfg = O.DynamicsConfig(n_hidden_scalars=64, vector_size=32)

@@ -185,7 +185,7 @@ def test_step_api_and_state():
 
 
 def test_width_generic_family():
-    """(64, 32): the move runs alone (k_step_update_renoise), the family launches its own encoders and edge build.  T = 12, jump 4,
+    """(64, 32): the move runs alone (k_step_update<MoveRenoise>), the family launches its own encoders and edge build.  T = 12, jump 4,
     resamples 2: 27 ops.  The given rows are divided by a feat_norm_constant of 2.  Measured on the MI355X, worst |error|: 1.4e-6."""
     n_t, fnorm = 12, 2.0
     cfg = O.DynamicsConfig(n_hidden_scalars=64, vector_size=32)

@@ -127,7 +127,7 @@ def test_guided_run():
 
 
 def test_width_generic_family():
-    """(64, 32): the move runs alone (k_step_update_seed), the family launches its own encoders and edge build.  A plain and a
+    """(64, 32): the move runs alone (k_step_update<MoveSeed>), the family launches its own encoders and edge build.  A plain and a
     pinned run at a = 7 of T = 12; the given rows are divided by a feat_norm_constant of 2."""
     G, cfg, sd, batch, noise, seed, pins, com, _ = wide_inputs()
     a, n_t, fnorm = 7, G.WIDE_T, 2.0

@@ -5,7 +5,7 @@ Part 1, the step, at the shape of BASELINE.json config 2 (B = 32 pockets of 256 
 tools/pinned_bench.py's batch).  Legs, each on its own handle in this one process:
   default   the unguided step as shipped (tuned kernels, merged last launch)
   pinned    the pinned step, 2 of every graph's 6 centers pinned
-  wide      an unguided step of a handle created under PFDYN_WIDE=1: the width-generic INFERENCE forward + k_step_update.  The
+  wide      an unguided step of a handle created under PFDYN_WIDE=1: the width-generic INFERENCE forward + k_step_update<MovePlain>.  The
             fair yardstick: a guided step's forward is the width-generic training forward
   guided    2 centers pinned, and per graph a repel sphere on all centers plus an attract on one
   guided_tuned  the same run with guide_family="tuned": the tuned training forward and the tuned inputs-only backward

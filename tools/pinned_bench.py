@@ -3,7 +3,7 @@
 
 Legs: `default` -- the unpinned step as shipped (merged last launch); `separate` -- the unpinned step under PFDYN_HS_BUILD=0
 (node + head launch, then the update + build launch: the launches a pinned step makes, on the unpinned code -- the yardstick);
-`separate_generic` -- the same with PFDYN_NO_FAST_BUILD=1 as well, i.e. the generic update + build bodies a pinned step is built
+`separate_generic` -- the same with PFDYN_NO_FAST_BUILD=1 as well, i.e. the generic move + build bodies (k_step_build<MovePlain>) a pinned step is built
 from (what the latency-optimised k_step_build_fast saves); `pinned` -- 2 of every graph's 6 centers pinned (position and type).
 Every leg has its own handle; the timed windows of --steps steps (HIP events around the window, after --warmup steps) alternate
 between the legs --rounds times, and the figure of a leg is the median of its windows (all of them are listed).  Behind the timed
@@ -13,7 +13,7 @@ class, which says where a leg's extra time sits (not for `default`: timing the u
 --resamples R --jump J add the `resampled` leg: the pinned leg's batch driven through the head of schedule.resample_plan(500, J, R)
 (pf_renoise_step between the stretches).  It reports the whole run's time per op (HIP events around --rounds windows of --steps
 ops, median) and, from a pass with HIP events around every launch read back op by op, the median duration of the re-noise launch
-next to that of k_step_build_pinned from the same run."""
+next to that of k_step_build<MovePinned> from the same run."""
 import argparse
 import json
 import os

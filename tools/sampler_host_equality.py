@@ -7,8 +7,10 @@ commit: a refactor of the Python front is checked by running it from both trees.
 Cases: run kind (plain, pinned, pinned with all flags zero, resampled with jump 3 and 2 resamples, guided, guided with pins)  x
 entry (the whole-loop C call, the step API driven op by op)  x  batch (two graphs of 12 and 20 atoms with 2 and 3 centers; 32
 copies of one 20-atom pocket with 3..8 centers, the size at which the default plain step takes its merged launch with a center
-hoist)  x  n_convs 1 / 2 / 3  x  environment (read when the handle is created: every case creates its own).  T = 12; the noise
-is seeded.  Five further kinds -- seeded (seed level 5), multistep and seeded_multistep (4 steps; the step entry makes them with
+hoist; at n_convs 2 only, `edge`: four graphs of 300 / 70 / 33 / 48 atoms with 64 / 1 / 17 / 2 centers, which reach what the small
+batches cannot -- the stride-64 loop of the frame offset, the stride-256 loop over the protein rows, lanes 8..63 of the move's
+center mapping, a graph with a single center)  x  n_convs 1 / 2 / 3  x  environment (read when the handle is created: every case
+creates its own).  T = 12; the noise is seeded.  Five further kinds -- seeded (seed level 5), multistep and seeded_multistep (4 steps; the step entry makes them with
 ms_step), guided_field (a pocket field with a clash radius, no restraints), guided_tuned (guide_family="tuned"), guided_types (type
 restraints only, one graph in two without any, feat_scale 1) and guided_field_types (a pocket field with receptor features and
 w_comp > 0 plus type guidance with complementarity=True and unmatched 1.5: the TYPES form of the field launch) -- run with the
@@ -61,6 +63,8 @@ def batch_of(name):
     if name not in _cache:
         if name == "two":
             pockets, nfs = [synthetic.synthetic_pocket(21, 12), synthetic.synthetic_pocket(22, 20)], [2, 3]
+        elif name == "edge":
+            pockets, nfs = [synthetic.synthetic_pocket(23 + g, n) for g, n in enumerate((300, 70, 33, 48))], [64, 1, 17, 2]
         else:
             pockets, nfs = [synthetic.synthetic_pocket(22, 20)] * 32, [3 + g % 6 for g in range(32)]
         ptr = lambda ns: torch.tensor([0] + list(itertools.accumulate(ns)))
@@ -167,7 +171,7 @@ def run_case(pfa, kind, entry, batch, n_convs, env):
         flags = torch.zeros(Nf, dtype=torch.int32)
         if kind != "pinned0":
             flags[pharm_ptr[:-1]] = 3                   # the first center of every graph: position and type; the second: position
-            flags[pharm_ptr[:-1] + 1] = 1
+            flags[pharm_ptr[:-1][pharm_ptr[1:] - pharm_ptr[:-1] >= 2] + 1] = 1
         pins = (flags, com_f + 1.5 * torch.randn(Nf, 3, generator=gen),
                 torch.nn.functional.one_hot(torch.randint(0, nf, (Nf,), generator=gen), nf).float())
     guided = kind.startswith("guided")
@@ -272,9 +276,9 @@ def main():
     import pharmacoforge_amd as pfa
     torch.zeros(1, device="cuda")
     lines = ["library " + pfa._lib.load().pf_version().decode()]
-    for n_convs, env, batch, kind, entry in itertools.product((1, 2, 3), ENVS, ("two", "copies"), KINDS + FRONT_KINDS, ("loop", "steps")):
+    for n_convs, env, batch, kind, entry in itertools.product((1, 2, 3), ENVS, ("two", "copies", "edge"), KINDS + FRONT_KINDS, ("loop", "steps")):
         name = f"convs{n_convs} {env} {batch} {kind} {entry}"
-        if (args.only and args.only not in name) or (kind in FRONT_KINDS and env not in ("default", "PFDYN_WIDE=1")):
+        if (args.only and args.only not in name) or (kind in FRONT_KINDS and env not in ("default", "PFDYN_WIDE=1")) or (batch == "edge" and n_convs != 2):
             continue
         lines.append(f"{name}: {run_case(pfa, kind, entry, batch, n_convs, env)}")
         print(lines[-1], flush=True)
