@@ -41,6 +41,9 @@ _FLAGS = [
     ('--guide_type_scale', dict(type=float, default=None, help='with --type_restraints: strength of the guidance of the feature rows (default 1)')),
     ('--guide_type_clip', dict(type=float, default=None, help='with --type_restraints: largest Euclidean norm of a feature row\'s shift per step (default 0: no clip)')),
     ('--type_sharpness', dict(type=float, default=None, help='with --type_restraints: sharpness of the soft type assignment on one-hot-scaled features (default 4)')),
+    ('--pair_restraints', dict(type=Path, default=None, help='guided sampling: a text file with one pair restraint per line, "pair I|* J|* LO HI|inf WEIGHT" (# starts a comment): the two centers (*: every center) of one sample are held LO to HI angstroms apart')),
+    ('--min_separation', dict(type=float, default=None, metavar='D', help='guided sampling: no two centers of a sample closer than D angstroms (the pair restraint "* * D inf W"); every batch then runs guided, which costs several times a default step')),
+    ('--separation_weight', dict(type=float, default=None, metavar='W', help='with --min_separation: weight of its energy (default 1)')),
     ('--avoid_clashes', dict(type=float, nargs='?', const=2.0, default=None, metavar='R', help='guided sampling: keep the centers out of the pocket\'s own atoms -- a center of the predicted clean sample within R angstroms of an atom (default 2.0) is pushed out; every batch then runs guided, which costs several times a default step')),
     ('--clash_weight', dict(type=float, default=None, help='with --avoid_clashes: weight of the clash energy (default 1)')),
     ('--guide_scale', dict(type=float, default=None, help='with --restraints or --avoid_clashes: strength of the guidance (default 1)')),
@@ -73,7 +76,17 @@ def parse_arguments(argv=None):
             parser.error(f'--{flag} needs --pinned_centers')
         if v is not None and v < 1:
             parser.error(f'--{flag} must be at least 1, got {v}')
-    guided = a.restraints is not None or a.avoid_clashes is not None or a.type_restraints is not None
+    paired = a.pair_restraints is not None or a.min_separation is not None
+    guided = a.restraints is not None or a.avoid_clashes is not None or a.type_restraints is not None or paired
+    if a.separation_weight is not None and a.min_separation is None:
+        parser.error('--separation_weight needs --min_separation')
+    for flag in ('min_separation', 'separation_weight'):
+        v = getattr(a, flag)
+        if v is not None and not (v >= 0 and v < float('inf')):
+            parser.error(f'--{flag} must be finite and not negative, got {v}')
+    if paired and a.pin_resamples is not None and a.pin_resamples > 1:
+        parser.error('--pair_restraints / --min_separation together with --pin_resamples > 1: guidance with resampling jumps is not supported')
+    a.separation_weight = 1.0 if a.separation_weight is None else a.separation_weight
     for flag in ('guide_type_scale', 'guide_type_clip', 'type_sharpness'):
         v = getattr(a, flag)
         if v is not None and a.type_restraints is None:
@@ -88,11 +101,11 @@ def parse_arguments(argv=None):
     for flag in ('guide_scale', 'guide_clip'):
         v = getattr(a, flag)
         if v is not None and not guided:
-            parser.error(f'--{flag} needs --restraints, --avoid_clashes or --type_restraints')
+            parser.error(f'--{flag} needs --restraints, --avoid_clashes, --type_restraints, --pair_restraints or --min_separation')
         if v is not None and not v >= 0:
             parser.error(f'--{flag} must not be negative, got {v}')
     if a.guide_family is not None and not guided:
-        parser.error('--guide_family needs --restraints, --avoid_clashes or --type_restraints')
+        parser.error('--guide_family needs --restraints, --avoid_clashes, --type_restraints, --pair_restraints or --min_separation')
     if a.clash_weight is not None and a.avoid_clashes is None:
         parser.error('--clash_weight needs --avoid_clashes')
     for flag in ('avoid_clashes', 'clash_weight'):
@@ -149,7 +162,7 @@ def parse_arguments(argv=None):
         if a.eta is not None and not 0.0 <= a.eta <= 1.0:
             parser.error(f'--eta must lie in 0..1, got {a.eta}')
         if a.sampler == 'multistep' and (a.pinned_centers is not None or guided or a.seed_keep is not None):
-            parser.error('--sampler multistep composes with --seed_pharmacophore only: no --pinned_centers, --seed_keep, --restraints, --type_restraints or --avoid_clashes')
+            parser.error('--sampler multistep composes with --seed_pharmacophore only: no --pinned_centers, --seed_keep, --restraints, --type_restraints, --pair_restraints, --min_separation or --avoid_clashes')
     a.pin_resamples = 1 if a.pin_resamples is None else a.pin_resamples
     a.pin_jump = 10 if a.pin_jump is None else a.pin_jump
     for flag in ('score_samples', 'keep_best'):
@@ -168,7 +181,7 @@ def parse_arguments(argv=None):
     a.score_frames = None
     if a.score_pharmacophores is not None:
         given = [f for f in ('--samples_per_pocket', '--pharm_sizes', '--visualize_trajectory', '--pinned_centers', '--restraints',
-                             '--type_restraints',
+                             '--type_restraints', '--pair_restraints', '--min_separation',
                              '--seed_pharmacophore', '--use_ref_lig_com', '--metrics')
                  if getattr(a, f[2:]) not in (parser.get_default(f[2:]), None)]
         if given:
@@ -212,6 +225,14 @@ def parse_arguments(argv=None):
         small = [n for n in a.pharm_sizes if named and n <= max(named)]
         if small:
             problems.append(f'--pharm_sizes {small} do not reach center {max(named)} named in --type_restraints')
+    a.pair_restraint_list = None
+    if a.pair_restraints is not None:
+        from pharmacoforge_amd.pocket_io import read_pair_restraints
+        a.pair_restraint_list = read_pair_restraints(a.pair_restraints)
+        named = [c for i, j, _, _, _ in a.pair_restraint_list for c in (i, j) if c is not None]
+        small = [n for n in a.pharm_sizes if named and n <= max(named)]
+        if small:
+            problems.append(f'--pharm_sizes {small} do not reach center {max(named)} named in --pair_restraints')
     if problems:
         raise ValueError('; '.join(problems))
     if a.ref_ligand_file is not None and a.residue_list:
@@ -262,13 +283,15 @@ def score_frames(pfa, model, pocket, frames, args):
                            max_batch_size=args.max_batch_size)[0]
 
 
-def write_scores(path, indices, scores, clashes=None, type_energies=None):
+def write_scores(path, indices, scores, clashes=None, type_energies=None, pair_energies=None):
     """scores.tsv: one line per pharmacophore, in the order of pharms.xyz (or of the scored file).  clashes (a pocket field was on):
     per pharmacophore (final clash energy, clashing (center, atom) pairs), two more columns; type_energies (type restraints were
-    given): per pharmacophore the final type energy, one more column"""
+    given): per pharmacophore the final type energy, one more column; pair_energies (pair restraints or a minimum separation were
+    given): per pharmacophore the final pair energy, one more column"""
     head = ('index', 'centers', 'total', 'per_center', 'pos', 'feat', 'position_error', 'type_accuracy')
     lines = ['\t'.join(head + (('clash_energy', 'clashes') if clashes is not None else ())
-                       + (('type_energy',) if type_energies is not None else ()))]
+                       + (('type_energy',) if type_energies is not None else ())
+                       + (('pair_energy',) if pair_energies is not None else ()))]
     for k, (i, s) in enumerate(zip(indices, scores)):
         row = (str(i), str(s.n_centers), f'{s.total:.6g}', f'{s.per_center:.6g}', f'{s.pos:.6g}', f'{s.feat:.6g}',
                f'{s.position_error:.6g}', f'{s.type_accuracy:.4f}')
@@ -276,6 +299,8 @@ def write_scores(path, indices, scores, clashes=None, type_energies=None):
             row += (f'{clashes[k][0]:.6g}', str(clashes[k][1]))
         if type_energies is not None:
             row += (f'{type_energies[k]:.6g}',)
+        if pair_energies is not None:
+            row += (f'{pair_energies[k]:.6g}',)
         lines.append('\t'.join(row))
     Path(path).write_text('\n'.join(lines) + '\n')
 
@@ -328,6 +353,8 @@ def main(argv=None):
     if args.type_restraint_list:
         k_named = max(k_named, 1 + max([c for _, c, _, _, _ in args.type_restraint_list if c is not None], default=-1))
         type_guidance = pfa.TypeGuidance(scale=args.guide_type_scale, clip=args.guide_type_clip, sharpness=args.type_sharpness)
+    if args.pair_restraint_list:
+        k_named = max(k_named, 1 + max([c for i, j, _, _, _ in args.pair_restraint_list for c in (i, j) if c is not None], default=-1))
     field = None
     if args.avoid_clashes is not None:       # PDB input has no receptor features: the clash term alone
         field = pfa.PocketField(clash_radius=args.avoid_clashes, clash_weight=args.clash_weight, comp_weight=0.0)
@@ -353,7 +380,9 @@ def main(argv=None):
                                                   sample_steps=args.sample_steps, sampler=args.sampler, eta=args.eta, spacing=args.spacing,
                                                   pocket_field=field,
                                                   type_restraints=[args.type_restraint_list] * n if args.type_restraint_list else None,
-                                                  type_guidance=type_guidance)
+                                                  type_guidance=type_guidance,
+                                                  pair_restraints=[args.pair_restraint_list] * n if args.pair_restraint_list else None,
+                                                  min_separation=args.min_separation, separation_weight=args.separation_weight)
     elapsed = time.time() - t0
 
     (pocket_dir / 'sample_time.txt').write_text(f'{elapsed:.2f}')
@@ -372,6 +401,11 @@ def main(argv=None):
         rows = [(model._type_index(t), c, p, r, w) for t, c, p, r, w in args.type_restraint_list]
         type_energies = [type_restraint_energy(ph.ph_coords, ph.g.pharm_h0, rows, args.type_sharpness) for ph in pharms]
         print(f'{name}: type energy per sample ' + ' '.join(f'{e:.3g}' for e in type_energies))
+    pair_energies = None
+    if args.pair_restraint_list or args.min_separation is not None:     # the final pair energy of every sample
+        pair_energies = [ph.pair_energy for ph in pharms]
+        print(f'{name}: pair energy per sample ' + ' '.join(f'{e:.3g}' for e in pair_energies)
+              + '; violated pairs ' + ' '.join(str(ph.pair_violations) for ph in pharms))
     ref_dir = pocket_dir / 'reference_files'
     ref_dir.mkdir(exist_ok=True)
     for src in (args.receptor_file, args.ref_ligand_file):
@@ -387,7 +421,8 @@ def main(argv=None):
             order = sorted(order, key=lambda i: (scores[i].per_center, i))[:args.keep_best]
         pharms, scores = [pharms[i] for i in order], [scores[i] for i in order]
         write_scores(pocket_dir / 'scores.tsv', range(len(scores)), scores, None if clashes is None else [clashes[i] for i in order],
-                     None if type_energies is None else [type_energies[i] for i in order])
+                     None if type_energies is None else [type_energies[i] for i in order],
+                     None if pair_energies is None else [pair_energies[i] for i in order])
     if args.visualize_trajectory:
         for i, ph in enumerate(pharms):
             ph.traj_to_xyz(pocket_dir / f'pharm_{i}_traj.xyz')

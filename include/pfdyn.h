@@ -407,6 +407,43 @@ int pf_guide_types_next(pf_handle* h, const int32_t* host_ptr /*[B+1] or NULL*/,
                         float unmatched);
 int pf_debug_last_type_guidance(pf_handle* h, float* dev_g0_h, float* dev_grad_h, float* dev_shift_h, float* dev_E_type, pf_stream stream);
 
+/* -- pair guidance: distance restraints between two centers of one sample (no reference counterpart) ------------------------------
+ * Every energy above is a sum over single centers; a pair restraint relates two centers of the same graph: "centers 0 and 3 five
+ * to seven angstroms apart", "no two centers closer than 3".  The names are those above: x0_hat, D[g], alpha_t, sigma_t.
+ * Pair restraint of graph g: (i, j, lo, hi, w).  i, j local center indices in [0, nf_g) or -1 for "every center"; with both given,
+ * i != j; 0 <= lo <= hi, lo finite, hi finite or +inf (no upper bound); w >= 0 and finite; at most 256 per graph
+ * (PF_PAIRS_MAX_PER_GRAPH).  The unordered pairs {a, b}, a != b, it covers: both given, {i, j}; one wildcard, {i, b} for every
+ * b != i; both wildcards, every a < b.  A graph with fewer than two centers has no pairs and contributes exact zeros.
+ * The point of center f.  y_f = x0_hat[f] + D[g] for a free center; y_f = pin_x[f] for a position-pinned one (flag bit 0): the
+ * given position, in the caller's frame, a constant -- what the network predicts for a pinned center is not where it will be.
+ * For a covered pair, d = y_a - y_b, rho = sqrtf((dx*dx + dy*dy) + dz*dz), one rounding per operation:
+ *     m_lo = max(0, lo - rho)      m_hi = max(0, rho - hi)      (hi = +inf: m_hi = 0)
+ *     E       = w (m_lo^2 + m_hi^2)
+ *     dE/dy_a = ((2 w) (m_hi - m_lo) / rho) d,   dE/dy_b = -dE/dy_a,   both 0 when rho == 0
+ * A position-pinned center receives no pair gradient: its g_pair row is exactly zero; the pair still counts in E and its free
+ * partner still gets its half of the gradient.
+ * Totals and their order.  For center f the terms of its covered partners are taken restraints ascending and, within a restraint,
+ * partners b ascending, in four partial sums by (b & 3) that meet as (s0 + s1) + (s2 + s3): that is g_pair[f]; e_f is the same
+ * sum of E over the pairs with f < b; E_pair[g] = sum_f e_f, f ascending, summed by one thread.  The pair launch (k_guide_pairs)
+ * is the last one in front of the VJP, behind k_guide_grad, the pocket field's launch and k_guide_types:
+ *     g0[f] += g_pair[f]          E[g] = ((((E_restr + E_clash) + E_comp) + E_type) + E_pair)
+ * dev_energy's row is rewritten with the total; pf_debug_last_field's three components and E_type keep their meaning and their
+ * bits.  The VJP, shift, clip, pin selects and COM removal are unchanged; the pair energies do not depend on the features.
+ * Arming: pf_guide_types_next's rules.  pf_guide_pairs_next comes after a bind and arms the NEXT pf_sample_begin_guided (also the
+ * one inside pf_sample_guided), which consumes it, accepted or not; it ends with that run.  HOST arrays ptr[B+1] (graph g owns
+ * restraints [ptr[g], ptr[g+1])), i, j, lo, hi, w [n], copied before the call returns.  Validation on the host before anything is
+ * touched (csrc/pf_pairs.h): a failure is PF_ERR_ARG with a message and leaves the handle as it was -- an earlier arming stays
+ * armed.  The begin of any other run kind while it is armed returns PF_ERR_STATE and drops the arming; a bind drops it silently;
+ * a run in progress is untouched.  host_ptr NULL, or no restraint in any graph: accepted and inert -- no pair launch is made and
+ * the guided run executes exactly the launches it did.  The block goes through the guided begin's staged upload into an
+ * allocation of the handle, kept and grown like the pin arrays.
+ * pf_debug_last_pairs: the last guided step's g_pair [Nf,3] and E_pair [B], each nullable; PF_ERR_STATE when the last guided step
+ * on this batch made no pair launch. */
+#define PF_PAIRS_MAX_PER_GRAPH 256
+int pf_guide_pairs_next(pf_handle* h, const int32_t* host_ptr /*[B+1] or NULL*/, const int32_t* host_i /*[n]*/, const int32_t* host_j /*[n]*/,
+                        const float* host_lo /*[n]*/, const float* host_hi /*[n]*/, const float* host_w /*[n]*/);
+int pf_debug_last_pairs(pf_handle* h, float* dev_g_pair /*[Nf,3]*/, float* dev_E_pair /*[B]*/, pf_stream stream);
+
 /* -- seeded sampling: start the reverse process from a given pharmacophore (partial diffusion; no reference counterpart) ----------
  * The given sample is noised forward to an intermediate level a, 1 <= a <= T, and only the reverse steps a-1 .. 0 are run: a small
  * a gives close analogues of the seed, a large a loose ones.

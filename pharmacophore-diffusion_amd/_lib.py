@@ -108,6 +108,8 @@ SYMBOLS = {
     "pf_debug_last_field": (ctypes.c_int, [_P, _P, _P]),
     "pf_guide_types_next": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _I32, _F]),
     "pf_debug_last_type_guidance": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "pf_guide_pairs_next": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "pf_debug_last_pairs": (ctypes.c_int, [_P, _P, _P, _P]),
     "pf_dynamics_input_vjp": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "pf_param_count": (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "pf_param_layout": (ctypes.c_int, [_P, _I32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),

@@ -133,6 +133,9 @@ class SampledPharmacophore:
         self.pinned = torch.zeros(self.n_ph_centers, dtype=torch.int32) if pin is None else pin.to("cpu", torch.int32)
         self.pos_frames, self.feat_frames = traj_frames if traj_frames is not None else (None, None)
         self.score: Optional[PharmacophoreScore] = None  # set by PharmacophoreDiff.sample(..., score_levels=K)
+        # set by PharmacophoreDiff.sample(..., pair_restraints= / min_separation=): pair_restraint_energy of the final centers
+        self.pair_energy: Optional[float] = None
+        self.pair_violations: Optional[int] = None
 
     def _names(self, type_indices) -> List[str]:
         return [self.pharm_type_map[k] for k in torch.as_tensor(type_indices).tolist()]
@@ -215,6 +218,40 @@ def type_restraint_energy(ph_coords, ph_feats, type_restraints, sharpness=4.0):
                 omega = q * q
             total += float(weight) * omega * float(ce[f, int(t)])
     return total
+
+
+def pair_restraint_energy(ph_coords, pair_restraints):
+    """(energy, violated pairs) of pair restraints on centers [n, 3], in fp64: the sum over restraints (i, j, lo, hi, weight) --
+    i, j center indices, or None / '*' / a negative index for every center -- and the unordered pairs {a, b}, a != b, each covers
+    ({i, j}; with one wildcard {i, b} for every b != i; with two every a < b) of weight * (max(0, lo - rho)^2 + max(0, rho - hi)^2),
+    rho the pair's distance, hi = inf: no upper bound -- the pair guidance's energy (include/pfdyn.h) on final values -- and the
+    number of (restraint, pair) combinations whose distance lies outside lo .. hi.  Fewer than two centers: (0.0, 0)."""
+    x = torch.as_tensor(ph_coords).double().reshape(-1, 3).cpu()
+    n = x.shape[0]
+    if n < 2 or not pair_restraints:
+        return 0.0, 0
+    rho = (x[:, None, :] - x[None, :, :]).pow(2).sum(dim=2).sqrt()
+    upper = torch.triu(torch.ones(n, n, dtype=torch.bool), diagonal=1)
+    index = lambda c: -1 if c is None or c == "*" or int(c) < 0 else int(c)
+    total, violated = 0.0, 0
+    for i, j, lo, hi, weight in pair_restraints:
+        i, j = index(i), index(j)
+        if max(i, j) >= n:
+            raise ValueError(f"a pair restraint names center {max(i, j)} of {n}")
+        cover = torch.zeros(n, n, dtype=torch.bool)
+        if i >= 0 and j >= 0:
+            cover[min(i, j), max(i, j)] = i != j
+        elif i >= 0 or j >= 0:
+            c = max(i, j)
+            cover[c, :] = True
+            cover[:, c] = True
+        else:
+            cover[:, :] = True
+        cover &= upper
+        m_lo, m_hi = (float(lo) - rho).clamp(min=0), (rho - float(hi)).clamp(min=0)
+        total += float(weight) * float((m_lo * m_lo + m_hi * m_hi)[cover].sum())
+        violated += int(((m_lo > 0) | (m_hi > 0))[cover].sum())
+    return total, violated
 
 
 def compute_complementarity(pharm_types, pharm_pos, prot_ph_types, prot_ph_pos, return_count=False):

@@ -629,6 +629,25 @@ struct GuideFeatParams {
     float scale, clip;                      // feat_scale, feat_clip
     float* grad_h; float* shift_h;          // [Nf][nf] each: what the step applied (pf_debug_last_type_guidance); a type-pinned center's row is what it ignored
 };
+// pair guidance of a guided run (pf_guide_pairs_next; the block's layout: pf_pairs.h).  k_guide_pairs reads PairParams -- of
+// StepParams the graph pointers, xn and eps_x -- behind k_guide_grad, k_guide_field and k_guide_types: it leaves g_pair = the pair
+// energies' dE/dy per center and E_pair per graph, and adds them into g0 and the total
+struct PairParams {
+    const int* ptr;            // [B + 1]  graph g owns pair restraints [ptr[g], ptr[g + 1])
+    const int* i; const int* j;            // [n] each: local center index, or -1: every center of the graph
+    const float* lo; const float* hi;      // [n] each: the hinge opens below lo and above hi (+inf: no upper bound)
+    const float* w;            // [n]
+    const int* flags;          // [Nf]     the run's pin flags; bit 0: y_f is pin_x[f], and the center takes no pair gradient
+    const float* pin_x;        // [Nf][3]  caller's frame
+    float alpha_t, sigma_t;    // pf_guide_coef
+    int ep_coord;
+    const float* D;            // [B][3], as k_guide_grad left it
+    float* g0;                 // [Nf][3]  added into
+    float* g_pair;             // [Nf][3]  written
+    float* E_pair;             // [B]      written
+    float* energy;             // [B]      added into
+    float* traj_energy;        // [B] row of the caller's trajectory of energies, or NULL (rewritten with the total)
+};
 // the move a sampler step ends with (pfk_step_move; the moves: pf_stepmove.h): the tag and the parameters that move reads
 struct StepMoveArgs {
     enum Kind { PLAIN, MS, PINNED, GUIDED, GUIDED_TYPES, RENOISE, SEED } kind;

@@ -25,6 +25,7 @@
 #include "pf_field.h"
 #include "pf_restr.h"
 #include "pf_types.h"
+#include "pf_pairs.h"
 
 using namespace pfpack;
 
@@ -73,6 +74,7 @@ void pfk_guide_grad(const StepParams* p, const GuideParams* q, hipStream_t s);
 void pfk_guide_field(const StepParams* p, const FieldParams* q, hipStream_t s);
 void pfk_guide_field_types(const StepParams* p, const FieldParams* q, const FieldTypeParams* ft, hipStream_t s);
 void pfk_guide_types(const StepParams* p, const TypeParams* q, hipStream_t s);
+void pfk_guide_pairs(const StepParams* p, const PairParams* q, hipStream_t s);
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s);
@@ -434,6 +436,15 @@ struct pf_handle {
         bool armed = false, on = false, have = false, live = false;
         struct Scalars { int n = 0; float feat_scale = 0.f, feat_clip = 0.f, type_sharpness = 0.f; bool comp = false; float unmatched = 0.f; } arm, run;
     } types;
+    // pair guidance (pf_guide_pairs_next): distance restraints between two centers of a graph.  Armed, staged (pf_pairs.h) and
+    // uploaded like type guidance.  d_pguide: what a step with pair restraints leaves (pf_pairs.h: PairWork).  on: the run in
+    // progress carries n_run > 0 pair restraints; have: the last guided step on this batch launched k_guide_pairs (pf_debug_last_pairs)
+    struct PairsSource {
+        StagedBlock blk;
+        void* d_pguide = nullptr; size_t pguide_capacity = 0;
+        bool armed = false, on = false, have = false;
+        int n_arm = 0, n_run = 0;
+    } pairs;
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
@@ -1551,8 +1562,9 @@ void pf_destroy(pf_handle* h) {
     if (h->d_guide) (void)hipFree(h->d_guide);
     if (h->d_gdiff) (void)hipFree(h->d_gdiff);
     if (h->d_optim_part) (void)hipFree(h->d_optim_part);
-    for (StagedBlock* b : {&h->restr, &h->field.blk, &h->types.blk}) staged_free(*b);
+    for (StagedBlock* b : {&h->restr, &h->field.blk, &h->types.blk, &h->pairs.blk}) staged_free(*b);
     if (h->types.d_tguide) (void)hipFree(h->types.d_tguide);
+    if (h->pairs.d_pguide) (void)hipFree(h->pairs.d_pguide);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
     for (int k = 0; k < 2; ++k) {
         if (h->d_tab[k]) (void)hipFree(h->d_tab[k]);
@@ -1724,9 +1736,9 @@ static void set_batch_pointers(pf_handle* h, const pfbind::BindPlan& p, char* ba
 // rejected or not, and ends with no guided run on the batch (no source on, nothing for the pf_debug_last_* readers); a plain
 // begin ends the guidance sources with their run
 static bool take(bool& armed) { const bool was = armed; armed = false; return was; }
-static void drop_armings(pf_handle* h) { h->seed_armed = h->field.armed = h->types.armed = false; }
-static void no_guided_run(pf_handle* h) { h->guide_have = h->field.on = h->field.have = h->types.on = h->types.have = false; }
-static void end_guidance_sources(pf_handle* h) { h->field.on = h->types.on = false; }
+static void drop_armings(pf_handle* h) { h->seed_armed = h->field.armed = h->types.armed = h->pairs.armed = false; }
+static void no_guided_run(pf_handle* h) { h->guide_have = h->field.on = h->field.have = h->types.on = h->types.have = h->pairs.on = h->pairs.have = false; }
+static void end_guidance_sources(pf_handle* h) { h->field.on = h->types.on = h->pairs.on = false; }
 
 // prot_x / prot_h come either as device pointers (copied on the stream) or as host pointers (staged with the tables).
 // The arithmetic is pf_bind.cpp's (host only, checked on the CPU by tests/bind_check.cpp); this function owns the handle,
@@ -1996,14 +2008,16 @@ int pf_dynamics_forward(pf_handle* h, const float* dev_prot_x, const float* dev_
 }
 
 static int seed_move(pf_handle* h, const float* dev_noise0, hipStream_t s);
-// A pocket field and type guidance arm the next GUIDED begin; the begin of any other run kind drops them and says so.  (A seed
+// A pocket field, type guidance and pair guidance arm the next GUIDED begin; the begin of any other run kind drops them and says so.  (A seed
 // arms the next begin of any kind, which hands `seeded` down to the begin it is built on)
 static int refuse_field(pf_handle* h, const char* who) {
-    const bool fielded = h && take(h->field.armed), typed = h && take(h->types.armed);
+    const bool fielded = h && take(h->field.armed), typed = h && take(h->types.armed), paired = h && take(h->pairs.armed);
     if (fielded) PF_FAIL(h, PF_ERR_STATE, "%s while a pocket field is armed (pf_guide_field_next arms pf_sample_begin_guided / pf_sample_guided "
                                           "only): the arming is dropped", who);
     if (typed) PF_FAIL(h, PF_ERR_STATE, "%s while type guidance is armed (pf_guide_types_next arms pf_sample_begin_guided / pf_sample_guided "
                                         "only): the arming is dropped", who);
+    if (paired) PF_FAIL(h, PF_ERR_STATE, "%s while pair guidance is armed (pf_guide_pairs_next arms pf_sample_begin_guided / pf_sample_guided "
+                                         "only): the arming is dropped", who);
     return PF_OK;
 }
 
@@ -3518,12 +3532,14 @@ int pf_dynamics_input_vjp(pf_handle* h, const float* dev_g_eps_h, const float* d
 // The restraint block, its checks and its packing, and the layouts of the two workspaces a step writes: pf_restr.h (host only)
 static pfrestr::GuideWork guide_work(const pf_handle* h) { return pfrestr::GuideWork(h->Nf, h->cfg.pharm_nf, h->B); }
 static pfrestr::TypeWork type_work(const pf_handle* h) { return pfrestr::TypeWork(h->Nf, h->cfg.pharm_nf, h->B); }
+static pfpairs::PairWork pair_work(const pf_handle* h) { return pfpairs::PairWork(h->Nf, h->B); }
 
 int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const float* dev_noise0, const int32_t* dev_pin_flags,
                            const float* dev_pin_x, const float* dev_pin_h, float feat_norm_constant, const int32_t* host_restr_ptr,
                            const int32_t* host_restr_kind, const int32_t* host_restr_center, const float* host_restr_p,
                            const float* host_restr_r, const float* host_restr_w, float guide_scale, float guide_clip, pf_stream stream) {
     const bool seeded = h && take(h->seed_armed), fielded = h && take(h->field.armed), typed = h && take(h->types.armed);
+    const bool paired = h && take(h->pairs.armed) && h->pairs.n_arm > 0;     // (an arming without a restraint is inert: nothing of it runs)
     int rc = check_ready(h, true);
     if (rc) return rc;
     if (fielded && typed && h->field.arm.type_sharpness != h->types.arm.type_sharpness)
@@ -3553,6 +3569,9 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     const size_t types_bytes = pftypes::TypesLayout(h->B, h->types.arm.n).words() * 4;
     if (typed && (rc = grow_run_scratch(h, &h->types.blk.dev, &h->types.blk.capacity, types_bytes, types_bytes * 2, s)) != PF_OK) return rc;
     if (typed && (rc = grow_run_scratch(h, &h->types.d_tguide, &h->types.tguide_capacity, tbytes, tbytes, s)) != PF_OK) return rc;
+    const size_t pairs_bytes = pfpairs::PairsLayout(h->B, h->pairs.n_arm).words() * 4, pbytes = pair_work(h).words() * 4;
+    if (paired && (rc = grow_run_scratch(h, &h->pairs.blk.dev, &h->pairs.blk.capacity, pairs_bytes, pairs_bytes * 2, s)) != PF_OK) return rc;
+    if (paired && (rc = grow_run_scratch(h, &h->pairs.d_pguide, &h->pairs.pguide_capacity, pbytes, pbytes, s)) != PF_OK) return rc;
     rc = begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, seeded, stream);
     if (rc) return rc;
     pfrestr::pack(a, h->B, (uint32_t*)h->restr.stage);
@@ -3567,10 +3586,14 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
         PF_HIP(h, hipMemsetAsync(h->types.d_tguide, 0, tbytes, s));
         h->types.run = h->types.arm; h->types.on = true;
     }
+    if (paired) {                           // the armed pair restraints become this run's
+        if ((rc = staged_upload(h, h->pairs.blk, pairs_bytes, s)) != PF_OK) return rc;
+        h->pairs.n_run = h->pairs.n_arm; h->pairs.on = true;
+    }
     PF_HIP(h, hipMemsetAsync(h->d_guide, 0, gbytes, s));              // (the zero g_eps_h of every step's VJP; nothing writes it)
     h->guide_scale = guide_scale; h->guide_clip = guide_clip;
     h->guide_traj_energy = nullptr;
-    h->run = RUN_GUIDED; h->guide_have = false; h->field.have = false; h->types.have = false;
+    h->run = RUN_GUIDED; h->guide_have = false; h->field.have = false; h->types.have = false; h->pairs.have = false;
     h->guide_wide = h->train_wide; h->guide_in_grads = h->train_in_grads;
     return PF_OK;
 }
@@ -3578,7 +3601,7 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
 // ---- the guided step's launches: one builder per parameter struct ----
 // what they share: the step's coefficients, the two workspaces and their layouts (g: d_guide; t: d_tguide, null without type guidance: no builder reads it)
 struct GuideStep { float alpha_t, sigma_t; int ep_coord, ep_feat; pfrestr::GuideWork gw; float* g; pfrestr::TypeWork tw; float* t; };
-static const auto guide_shared = [](const pf_handle* h, const GuideStep& st, auto& q) {      // q: GuideParams, FieldParams, TypeParams
+static const auto guide_shared = [](const pf_handle* h, const GuideStep& st, auto& q) {      // q: GuideParams, FieldParams, TypeParams, PairParams
     q.alpha_t = st.alpha_t; q.sigma_t = st.sigma_t; q.ep_coord = st.ep_coord;
     q.D = st.g + st.gw.D(); q.g0 = st.g + st.gw.g0(); q.energy = st.g + st.gw.energy(); q.traj_energy = h->guide_traj_energy;
 };
@@ -3616,6 +3639,18 @@ static TypeParams type_params(const pf_handle* h, const GuideStep& st, const flo
     q.p = (const float*)(tb + tl.p()); q.r = (const float*)(tb + tl.r()); q.w = (const float*)(tb + tl.w());
     q.sharp = h->types.run.type_sharpness; q.ep_feat = st.ep_feat;
     q.g0_h = st.t + st.tw.g0_h(); q.gs_h = st.t + st.tw.gs_h(); q.E_type = st.t + st.tw.E_type(); q.E3 = e3;
+    guide_shared(h, st, q);
+    return q;
+}
+static PairParams pair_params(const pf_handle* h, const GuideStep& st) {
+    PairParams q{};
+    const pfpairs::PairsLayout pl(h->B, h->pairs.n_run);
+    const int32_t* pb = (const int32_t*)h->pairs.blk.dev;
+    q.ptr = pb + pl.ptr(); q.i = pb + pl.i(); q.j = pb + pl.j();
+    q.lo = (const float*)(pb + pl.lo()); q.hi = (const float*)(pb + pl.hi()); q.w = (const float*)(pb + pl.w());
+    q.flags = h->d_pin_flags; q.pin_x = h->d_pin_x;
+    const pfpairs::PairWork pw = pair_work(h);
+    q.g_pair = (float*)h->pairs.d_pguide + pw.g_pair(); q.E_pair = (float*)h->pairs.d_pguide + pw.E_pair();
     guide_shared(h, st, q);
     return q;
 }
@@ -3676,6 +3711,11 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
         const TypeParams tq = type_params(h, st, e3);
         pfk_guide_types(&sp, &tq, s);
     }
+    if (h->pairs.on) {                          // pair restraints: one more launch, the last in front of the VJP
+        const PairParams pq = pair_params(h, st);
+        pfk_guide_pairs(&sp, &pq, s);
+    }
+    h->pairs.have = h->pairs.on;
     // the VJP's g_eps_h: (phi_h / phi_x) g0_h where a launch above left one, else the stored zeros; g_pharm_h only with the arming
     const bool live_h = comp_types || restr_types;
     const float* g_eps_h = live_h ? st.t + st.tw.gs_h() : st.g + st.gw.zero();
@@ -3788,6 +3828,37 @@ int pf_debug_last_type_guidance(pf_handle* h, float* dev_g0_h, float* dev_grad_h
         if (h->types.live) PF_HIP(h, hipMemcpyAsync(dev_E_type, t + tw.E_type(), (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
         else PF_HIP(h, hipMemsetAsync(dev_E_type, 0, (size_t)h->B * 4, s));
     }
+    return PF_OK;
+}
+
+// Arms the next guided begin with pair restraints (the semantics: pfdyn.h), in pf_guide_types_next's manner: every check first
+// (pf_pairs.h, host only), then the arrays are packed into the handle's pinned staging buffer, where they stay until that begin
+// uploads them on its own stream.  A run in progress reads none of it and goes on
+int pf_guide_pairs_next(pf_handle* h, const int32_t* host_ptr, const int32_t* host_i, const int32_t* host_j, const float* host_lo,
+                        const float* host_hi, const float* host_w) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    const pfpairs::PairsArgs a{host_ptr, host_i, host_j, host_lo, host_hi, host_w};
+    char msg[256];
+    if (!pfpairs::validate(a, h->B, h->h_pharm_ptr.data(), msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
+    const int n = pfpairs::n_restraints(a, h->B);
+    h->pairs.armed = false;                 // (an arming not yet used is replaced, also when the allocation below fails)
+    if ((rc = staged_reserve(h, h->pairs.blk, pfpairs::PairsLayout(h->B, n).words() * 4)) != PF_OK) return rc;
+    pfpairs::pack(a, h->B, (uint32_t*)h->pairs.blk.stage);
+    h->pairs.n_arm = n;
+    h->pairs.armed = true;
+    return PF_OK;
+}
+
+int pf_debug_last_pairs(pf_handle* h, float* dev_g_pair, float* dev_E_pair, pf_stream stream) {
+    int rc = check_ready(h, true);
+    if (rc) return rc;
+    if (!h->guide_have || !h->pairs.have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_pairs: no guided step with pair restraints on this batch");
+    hipStream_t s = (hipStream_t)stream;
+    const pfpairs::PairWork pw = pair_work(h);
+    const float* d = (const float*)h->pairs.d_pguide;
+    if (dev_g_pair && h->Nf) PF_HIP(h, hipMemcpyAsync(dev_g_pair, d + pw.g_pair(), (size_t)h->Nf * 3 * 4, hipMemcpyDeviceToDevice, s));
+    if (dev_E_pair && h->B) PF_HIP(h, hipMemcpyAsync(dev_E_pair, d + pw.E_pair(), (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
     return PF_OK;
 }
 

@@ -431,10 +431,10 @@ class PfEngine:
             self.set_train_family(before[0])
 
     @contextlib.contextmanager
-    def _armed(self, guide_family, seed, field, feat_norm_constant, restore=True, types=None):
+    def _armed(self, guide_family, seed, field, feat_norm_constant, restore=True, types=None, pairs=None):
         """What the begin of a run consumes, armed in one order for sample and sample_begin: the training family of a guided run
         (guide_family None: an unguided run, nothing is selected; 'tuned' takes its input-gradient switch along), then the seed
-        (seed_next), then the pocket field (field_next), then type guidance (types_next).  On exit, also on error, family and
+        (seed_next), then the pocket field (field_next), then type guidance (types_next), then pair guidance (pairs_next).  On exit, also on error, family and
         switch are what they were; restore=False leaves them selected (sample_begin: the run's steps need them, its caller
         restores)."""
         before = self._arm_guide_family(guide_family) if guide_family is not None else None
@@ -445,6 +445,8 @@ class PfEngine:
                 self.field_next(**field)
             if types is not None:
                 self.types_next(**types)
+            if pairs is not None:
+                self.pairs_next(pairs)
             yield
         finally:
             if restore and before is not None:
@@ -676,8 +678,46 @@ class PfEngine:
                      "pf_debug_last_type_guidance")
         return g0, gr, sh, en
 
+    def pairs_next(self, restraints=None):
+        """Arms the next guided begin on this engine with pair restraints (pf_guide_pairs_next; the semantics: include/pfdyn.h):
+        distance restraints between two centers of one graph.  restraints: None, or one list (or None) per graph of
+        (i, j, lo, hi, weight) -- i, j local center indices, or None / '*' / a negative index for every center; the energy is
+        weight * (max(0, lo - rho)^2 + max(0, rho - hi)^2) on the distance rho of every covered pair, hi = inf: no upper bound.
+        The library validates the values (PfError, PF_ERR_ARG) and copies them before this returns.  None, or no restraint in any
+        graph, is accepted and inert.  The begin of any other run kind while it is armed is a PfError (PF_ERR_STATE) and drops it;
+        set_batch drops it silently."""
+        import numpy as np
+        if restraints is None:
+            args = (ctypes.c_void_p(None),) * 6
+            keep = ()
+        else:
+            if len(restraints) != self.B:
+                raise ValueError(f"pair restraints must have one entry per graph ({self.B}), got {len(restraints)}")
+            index = lambda c: -1 if c is None or c == "*" or int(c) < 0 else int(c)
+            ptr, ci, cj, lo, hi, wt = [0], [], [], [], [], []
+            for rs in restraints:
+                for row in (rs or []):
+                    if len(row) != 5:
+                        raise ValueError(f"a pair restraint is (i, j, lo, hi, weight), got {row!r}")
+                    i, j, a, b, w = row
+                    ci.append(index(i)); cj.append(index(j)); lo.append(float(a)); hi.append(float(b)); wt.append(float(w))
+                ptr.append(len(ci))
+            keep = (np.asarray(ptr, dtype=np.int32), np.asarray(ci, dtype=np.int32), np.asarray(cj, dtype=np.int32),
+                    np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32), np.asarray(wt, dtype=np.float32))
+            args = tuple(a.ctypes.data for a in keep)
+        self._ck(self.lib.pf_guide_pairs_next(self._h, *args), "pf_guide_pairs_next")     # (keep: the arrays live until here)
+
+    def last_pair_guidance(self):
+        """(g_pair [Nf, 3], E_pair [B]) of the last guided step with pair restraints (pf_debug_last_pairs): the pair energies'
+        gradient w.r.t. the centers' points (a position-pinned center's row is zero) and their sum per graph."""
+        gp = torch.empty(self.Nf, 3, device=self.device)
+        en = torch.empty(self.B, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_debug_last_pairs(self._h, _dptr(gp), _dptr(en), _stream_ptr()), "pf_debug_last_pairs")
+        return gp, en
+
     def sample_begin(self, noise0, init_pharm_com=None, pins=None, feat_norm_constant=1.0, restraints=None, guide_scale=1.0,
-                     guide_clip=0.0, seed=None, guide_family=None, field=None, types=None):
+                     guide_clip=0.0, seed=None, guide_family=None, field=None, types=None, pairs=None):
         """seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the begin.
         pins = (flags, positions, feature rows): a pinned run (pf_sample_begin_pinned) -- its steps are
         denoise_step(..., pin_coef=...); feat_norm_constant is what the given feature rows are divided by.
@@ -687,8 +727,9 @@ class PfEngine:
         for 'tuned', a 128 / 16 handle, also the input-gradient switch -- and leaves it selected: the run's steps need it, and the
         caller restores what it had once the run has ended.
         field (a dict of field_next's arguments): a guided run with a pocket field, also without restraints.
-        types (a dict of types_next's arguments): a guided run with type guidance, also without restraints."""
-        if (field is not None or types is not None) and restraints is None:
+        types (a dict of types_next's arguments): a guided run with type guidance, also without restraints.
+        pairs (pairs_next's argument): a guided run with pair restraints, also without restraints."""
+        if (field is not None or types is not None or pairs is not None) and restraints is None:
             restraints = [None] * self.B
         if guide_family is not None:
             self._check_guide_family(guide_family)
@@ -698,7 +739,7 @@ class PfEngine:
         com = _f32(init_pharm_com, self.device) if init_pharm_com is not None else None
         self._keep = [nz, com]
         pin, restr, _alive = self._run_inputs(pins, restraints)
-        with self._armed(guide_family, seed, field, feat_norm_constant, restore=False, types=types), torch.cuda.device(self.device):
+        with self._armed(guide_family, seed, field, feat_norm_constant, restore=False, types=types, pairs=pairs), torch.cuda.device(self.device):
             if restraints is not None:
                 self._ck(self.lib.pf_sample_begin_guided(self._h, _dptr(com), _dptr(nz), *pin, float(feat_norm_constant), *restr,
                                                          float(guide_scale), float(guide_clip), _stream_ptr()), "pf_sample_begin_guided")
@@ -783,8 +824,10 @@ class PfEngine:
     def sample(self, coef_arr, n_steps, noise, init_pharm_com=None, ep_coord=False, ep_feat=False,
                feat_norm_constant=1.0, trajectory=False, pins=None, pin_coef_arr=None, plan=None, restraints=None,
                guide_coef_arr=None, guide_scale=1.0, guide_clip=0.0, energies=False, seed=None, ms_coef_arr=None,
-               guide_family="wide", field=None, types=None):
-        """field (a dict of field_next's arguments): the guided run carries a pocket field; restraints are then optional.
+               guide_family="wide", field=None, types=None, pairs=None):
+        """pairs (pairs_next's argument: one list or None per graph of (i, j, lo, hi, weight)): the guided run carries pair
+        restraints; restraints are then optional.
+        field (a dict of field_next's arguments): the guided run carries a pocket field; restraints are then optional.
         types (a dict of types_next's arguments): the guided run steers the feature rows too; restraints are then optional.
         seed = (seed_x, seed_h, seed_coef): seed_next with this call's feat_norm_constant, in front of the run -- n_steps is
         then the seed's level a, and coef_arr (and the other per-step arrays) hold the entries of s = a-1 .. 0.
@@ -799,13 +842,13 @@ class PfEngine:
         ms_coef_arr (ms_coef_array): a multistep run, pf_sample_ms -- coef_arr is not read (None), noise needs its first row only
         (the initial draw), and the parameterisation is in the coefficients; seeds compose, pins, plans and restraints are refused."""
         ms, (op_arr, renoise_arr) = ms_coef_arr is not None, plan or (None, None)
-        if (field is not None or types is not None) and restraints is None and not ms:
+        if (field is not None or types is not None or pairs is not None) and restraints is None and not ms:
             restraints = [None] * self.B
         guided = restraints is not None
         if guide_family not in PfEngine.GUIDE_FAMILIES:
             raise ValueError(f"guide_family must be 'wide' or 'tuned', got {guide_family!r}")
-        if ms and (pins is not None or plan is not None or guided or field is not None or types is not None):
-            raise ValueError("a multistep run composes with seeds only: no pins, resampling plan, restraints, pocket field or type guidance")
+        if ms and (pins is not None or plan is not None or guided or field is not None or types is not None or pairs is not None):
+            raise ValueError("a multistep run composes with seeds only: no pins, resampling plan, restraints, pocket field, type or pair guidance")
         if plan is not None and pins is None:
             raise ValueError("a plan needs pins: resampling runs inside a pinned run (all flags zero pins nothing)")
         if guided and plan is not None:
@@ -839,7 +882,7 @@ class PfEngine:
             "guided": ("pf_sample_guided", (coef_arr, pin_coef_arr, guide_coef_arr) + state + eps + restr
                        + (float(guide_scale), float(guide_clip)) + outs + (_dptr(en) if n_steps else None,)),
             "multistep": ("pf_sample_ms", (ms_coef_arr,) + state + eps[2:] + outs)}[kind]
-        with self._armed(guide_family if guided else None, seed, field, feat_norm_constant, types=types), torch.cuda.device(self.device):
+        with self._armed(guide_family if guided else None, seed, field, feat_norm_constant, types=types, pairs=pairs), torch.cuda.device(self.device):
             self._ck(getattr(self.lib, name)(self._h, n_steps, *args, _stream_ptr()), name)
         out = (x0, h0, tx, th) if trajectory else (x0, h0)
         return out + (en,) if guided and energies else out

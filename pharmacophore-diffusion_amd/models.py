@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .analysis import PharmacophoreScore, SampleAnalyzer, SampledPharmacophore
+from .analysis import PharmacophoreScore, SampleAnalyzer, SampledPharmacophore, pair_restraint_energy
 from .engine import PfEngine
 from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_graph, get_batch_idxs, unbatch
 from .schedule import score_levels as _score_levels, score_weights as _score_weights
@@ -894,6 +894,18 @@ class RunSpec:
     guide_family: str
     guided: bool
     types: Optional[tuple] = None               # None, or types_next's scalars (scale, clip, sharpness, complementarity, unmatched)
+    separation: Optional[tuple] = None          # None, or (d, w) of min_separation: the pair restraint (*, *, d, inf, w) on every graph
+
+    def pairs_arg(self, pair_restraints, n_graphs):
+        """PfEngine.pairs_next's argument of a guided batch: its graphs' pair restraints (None or one list or None per graph) with
+        the minimum separation's row appended to every graph; None: the call has neither"""
+        if pair_restraints is None and self.separation is None:
+            return None
+        rows = [list(r or []) for r in (pair_restraints if pair_restraints is not None else [None] * n_graphs)]
+        if self.separation is not None:
+            d, w = self.separation
+            rows = [r + [(None, None, d, math.inf, w)] for r in rows]
+        return [r or None for r in rows]
 
     def types_kwargs(self, type_restraints):
         """PfEngine.types_next's arguments of a guided batch (None: the call has no type guidance)"""
@@ -1040,7 +1052,8 @@ class PharmacophoreDiff(_Base):
                               guide_scale: float = 1.0, guide_clip: float = 0.0, seeds=None, seed_level: int = None,
                               seed_keep=None, sample_steps: int = None, sampler: str = None, eta: float = None,
                               spacing: str = None, guide_family: str = "wide", pocket_field=None, type_restraints=None,
-                              type_guidance=None) -> List[SampledPharmacophore]:
+                              type_guidance=None, pair_restraints=None, min_separation: float = None,
+                              separation_weight: float = 1.0) -> List[SampledPharmacophore]:
         """Reverse diffusion for a batch of pocket graphs; the whole T-step loop is enqueued on the
         current HIP stream by pf_sample (no host synchronisation inside the loop).
 
@@ -1063,6 +1076,8 @@ class PharmacophoreDiff(_Base):
         per-atom radii, if any, cover the batch's atoms): the run is guided also without restraints (see ``sample``).
         ``type_restraints``: None, or one list (or None) per graph of the batch of (type, center, point, radius, weight), with
         ``type_guidance`` (a TypeGuidance): the run steers the feature rows too (see ``sample``).
+        ``pair_restraints``: None, or one list (or None) per graph of the batch of (i, j, lo, hi, weight); ``min_separation`` d
+        with ``separation_weight``: (*, *, d, inf, weight) on every graph (see ``sample``).
 
         ``seeds`` with ``seed_level`` a (and optionally ``seed_keep``): a seeded run (pf_sample_seed_next) -- one (x [n,3], types
         [n]) per graph of the batch, n that graph's number of centers; the run starts from the seeds noised to level a and makes
@@ -1073,12 +1088,16 @@ class PharmacophoreDiff(_Base):
         the first-order samplers and 1 row for 'multistep'; trajectories have N + 1 frames."""
         g = as_pocket_graph(g)
         type_restraints = self._type_restraints(type_restraints, g.batch_size, "graphs")
-        spec = self._run_spec(pins=self._has_pins(g), guided=self._guided(restraints, pocket_field, type_restraints),
+        pair_restraints = self._pair_restraints(pair_restraints, g.batch_size, "graphs",
+                                                [[n] for n in (g.pharm_ptr[1:] - g.pharm_ptr[:-1]).tolist()], int(min_separation is not None))
+        spec = self._run_spec(pins=self._has_pins(g),
+                              guided=self._guided(restraints, pocket_field, type_restraints, pair_restraints, min_separation),
                               pinned=g.pharm_pin is not None,
                               pin_resamples=pin_resamples, pin_jump=pin_jump, guide_scale=guide_scale, guide_clip=guide_clip,
                               seeds=seeds, seed_level=seed_level, seed_keep=seed_keep, sample_steps=sample_steps, sampler=sampler,
                               eta=eta, spacing=spacing, guide_family=guide_family, pocket_field=pocket_field,
-                              type_guidance=type_guidance, typed=type_restraints is not None)
+                              type_guidance=type_guidance, typed=type_restraints is not None, min_separation=min_separation,
+                              separation_weight=separation_weight)
         if seeds is not None:
             sizes = (g.pharm_ptr[1:] - g.pharm_ptr[:-1]).tolist()
             fields = self._seed_fields([[n] for n in sizes], seeds, seed_keep, batch=True)
@@ -1086,7 +1105,8 @@ class PharmacophoreDiff(_Base):
         return self._sample_finish(self._sample_fetch(self._sample_enqueue(g, spec, init_pharm_com, visualize_trajectory, noise,
                                                                            restraints=restraints,
                                                                            field=self._field_for_batch(g, pocket_field),
-                                                                           type_restraints=type_restraints)))
+                                                                           type_restraints=type_restraints,
+                                                                           pair_restraints=pair_restraints)))
 
     @staticmethod
     def _has_pins(g):
@@ -1094,11 +1114,45 @@ class PharmacophoreDiff(_Base):
         return g.pharm_pin is not None and bool((g.pharm_pin != 0).any())
 
     @staticmethod
-    def _guided(restraints, field, type_restraints=None):
-        """a pocket field, or a restraint or type restraint in one of the per-pocket / per-graph lists (None or empty: none): what
-        makes a run guided"""
-        return (field is not None or (restraints is not None and any(restraints))
-                or (type_restraints is not None and any(type_restraints)))
+    def _guided(restraints, field, type_restraints=None, pair_restraints=None, min_separation=None):
+        """a pocket field or a minimum separation, or a restraint, type restraint or pair restraint in one of the per-pocket /
+        per-graph lists (None or empty: none): what makes a run guided"""
+        return (field is not None or min_separation is not None or (restraints is not None and any(restraints))
+                or (type_restraints is not None and any(type_restraints)) or (pair_restraints is not None and any(pair_restraints)))
+
+    @staticmethod
+    def _pair_restraints(pair_restraints, n, what, sizes=None, extra=0):
+        """``pair_restraints`` of sample / sample_given_receptor, checked before any device work: None when there is none, else one
+        list or None per pocket / graph of (i or None, j or None, lo, hi, weight).  ``sizes``: per entry the numbers of centers
+        asked for; an index that one of them does not have is an error here.  ``extra``: rows the call adds to every graph (a minimum
+        separation's), which count towards the library's 256 per graph."""
+        if pair_restraints is None:
+            return None
+        if len(pair_restraints) != n:
+            raise ValueError(f"pair_restraints lists {len(pair_restraints)} entries for {n} {what}")
+        index = lambda c: None if c is None or c == "*" or int(c) < 0 else int(c)
+        out = []
+        for r, rs in enumerate(pair_restraints):
+            rows = []
+            for row in (rs or []):
+                if len(row) != 5:
+                    raise ValueError(f"a pair restraint is (i, j, lo, hi, weight), got {row!r}")
+                i, j, lo, hi, w = index(row[0]), index(row[1]), float(row[2]), float(row[3]), float(row[4])
+                if i is not None and i == j:
+                    raise ValueError(f"a pair restraint names two different centers, got {i} twice")
+                if not (0 <= lo < math.inf and lo <= hi):
+                    raise ValueError(f"a pair restraint needs 0 <= lo <= hi with lo finite (hi = inf: no upper bound), got lo {lo}, hi {hi}")
+                if not 0 <= w < math.inf:
+                    raise ValueError(f"a pair restraint's weight must be finite and >= 0, got {w}")
+                for c in (i, j):
+                    small = [int(m) for m in (sizes[r] if sizes is not None else []) if c is not None and int(m) <= c]
+                    if small:
+                        raise ValueError(f"{what[:-1]} {r}: a pair restraint names center {c} but sizes {small} were requested")
+                rows.append((i, j, lo, hi, w))
+            if len(rows) + extra > 256:
+                raise ValueError(f"{what[:-1]} {r}: {len(rows)} pair restraints{' and a minimum separation' if extra else ''} (at most 256 per graph)")
+            out.append(rows or None)
+        return out if any(out) else None
 
     def _type_index(self, t):
         """a type restraint's type: an index, or a name of the model's ph_type_map"""
@@ -1137,12 +1191,13 @@ class PharmacophoreDiff(_Base):
 
     def _run_spec(self, pins, guided, pinned=False, pin_resamples=1, pin_jump=10, guide_scale=1.0, guide_clip=0.0, seeds=None,
                   seed_level=None, seed_keep=None, score_levels=None, sample_steps=None, sampler=None, eta=None, spacing=None,
-                  guide_family="wide", pocket_field=None, type_guidance=None, typed=False):
+                  guide_family="wide", pocket_field=None, type_guidance=None, typed=False, min_separation=None, separation_weight=1.0):
         """The RunSpec of one sample / sample_given_receptor call from its keywords; every rule on how they compose is applied
         here, once, before any device work.  The two callers differ in where they look: ``pins`` -- a pin is present (an entry of
         ``pinned``; a flag set on the batched graph), ``guided`` (_guided), ``pinned`` -- pin fields were given at all.  ``typed``: a type
         restraint is present; ``type_guidance``: None or a TypeGuidance (``typed`` alone means TypeGuidance()); ``pocket_field``:
-        the call's, for the rules that tie the two."""
+        the call's, for the rules that tie the two.  ``min_separation`` d with ``separation_weight`` w: the pair restraint
+        (*, *, d, inf, w) on every graph, which makes every batch guided (the callers' ``guided`` says so: _guided)."""
         if score_levels is not None and not 1 <= int(score_levels) <= self.n_timesteps:
             raise ValueError(f"score_levels must satisfy 1 <= K <= {self.n_timesteps}, got {score_levels}")
         self._check_guide_family(guide_family)
@@ -1170,6 +1225,16 @@ class PharmacophoreDiff(_Base):
                 raise ValueError(f"type_guidance.sharpness must be >= 0, got {sharp}")
             types = (float(tg.scale), float(tg.clip), sharp * float(self.pharm_feat_norm_constant), bool(tg.complementarity),
                      float(tg.unmatched))
+        separation = None
+        if min_separation is not None:
+            d, w = float(min_separation), float(separation_weight)
+            if not 0 <= d < math.inf:
+                raise ValueError(f"min_separation must be finite and >= 0, got {min_separation}")
+            if not 0 <= w < math.inf:
+                raise ValueError(f"separation_weight must be finite and >= 0, got {separation_weight}")
+            if not guided:
+                raise ValueError("min_separation makes every batch guided: the caller's guided must say so")
+            separation = (d, w)
         if (seeds is None) != (seed_level is None):
             raise ValueError("seeds and seed_level go together: a seeded run needs both")
         if seeds is None and seed_keep is not None:
@@ -1179,7 +1244,7 @@ class PharmacophoreDiff(_Base):
         T = int(self.n_timesteps)
         return RunSpec(T=T, top=T if seeds is None else self._check_seed_level(seed_level), seeded=seeds is not None, fewstep=fewstep,
                        pin_resamples=int(pin_resamples), pin_jump=int(pin_jump), guide_scale=float(guide_scale),
-                       guide_clip=float(guide_clip), guide_family=guide_family, guided=bool(guided), types=types)
+                       guide_clip=float(guide_clip), guide_family=guide_family, guided=bool(guided), types=types, separation=separation)
 
     def _field_for_batch(self, g, pocket_field, radii=None):
         """PfEngine.field_next's arguments for a batched graph and a PocketField (None: None), checked before any device work.
@@ -1364,16 +1429,17 @@ class PharmacophoreDiff(_Base):
         return [self._with_pin_fields(g, *f) for g, f in zip(ref_graphs, self._seed_fields(n_pharms, seeds, seed_keep))]
 
     def _sample_enqueue(self, g, spec, init_pharm_com=None, visualize_trajectory=False, noise=None, lane: int = 0, restraints=None,
-                        field=None, generator=None, type_restraints=None):
+                        field=None, generator=None, type_restraints=None, pair_restraints=None):
         """First half of sample_given_receptor: upload the batch and enqueue the whole reverse process (asynchronous) on the
         current stream; ``lane`` > 0: on that lane's own handle (PharmRecDynamicsGVP.lane_engine).  What runs is ``spec``'s answer
         for this batch (RunSpec.batch): a pin flag set on the graph makes it pinned, a restraint in ``restraints`` (None or one
-        list or None per graph of the batch) or ``field`` (_field_for_batch) guided.  A seeded run's graph holds the seed of EVERY
+        list or None per graph of the batch), in ``type_restraints`` or ``pair_restraints``, ``field`` (_field_for_batch) or the
+        spec's minimum separation guided.  A seeded run's graph holds the seed of EVERY
         center on pharm_pin_x / pharm_pin_h (the flags say which of them stay fixed).  ``noise`` None: the rows the run reads, one
         torch.randn on the model's device from ``generator``."""
         g = as_pocket_graph(g)
         dev = self.device
-        guided = self._guided(restraints, field, type_restraints)
+        guided = self._guided(restraints, field, type_restraints, pair_restraints, spec.separation)
         kind, n_ops, rows, arr, kw = spec.batch(self, self._has_pins(g), guided)
         if noise is not None and noise.shape[0] != rows:
             if spec.fewstep is not None:
@@ -1400,6 +1466,11 @@ class PharmacophoreDiff(_Base):
             types = spec.types_kwargs(type_restraints)      # (every guided batch of a call with type guidance carries it)
             if types is not None:
                 kw["types"] = types
+            if pair_restraints is not None and len(pair_restraints) != g.batch_size:
+                raise ValueError(f"pair_restraints lists {len(pair_restraints)} entries for a batch of {g.batch_size} graphs")
+            pairs = spec.pairs_arg(pair_restraints, g.batch_size)
+            if pairs is not None:
+                kw["pairs"] = pairs
         if noise is None:
             noise = torch.randn(rows, g.num_nodes("pharm"), 3 + self.n_pharm_feats, device=dev, generator=generator)
         if lane == 0:
@@ -1420,19 +1491,20 @@ class PharmacophoreDiff(_Base):
                      for r in res)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
-        return g, host, visualize_trajectory, done, eng
+        return g, host, visualize_trajectory, done, eng, kw.get("pairs")
 
     def _sample_fetch(self, pending):
         """Results of an enqueued batch on the host (waits for that batch only).  The run's validity word arrived with them
         (pf_sample_end): an exchange time-out inside a merged launch raises PfError HERE, before anything is built from x_0 / h_0."""
-        g, host, traj, done, eng = pending
+        g, host, traj, done, eng, pairs = pending
         done.synchronize()
         eng.sample_status()
-        return g, host, traj
+        return g, host, traj, pairs
 
     def _sample_finish(self, pending) -> List[SampledPharmacophore]:
         """Second half: per-graph SampledPharmacophores (host work only once the results are fetched)."""
         g, res, visualize_trajectory = pending[:3]
+        pairs = pending[3] if len(pending) > 3 else None        # the batch's pair restraints per graph: their final energy goes along
         x0, h0 = res[0].cpu(), res[1].cpu()
         traj_x = res[2].cpu() if visualize_trajectory else None
         traj_h = res[3].cpu() if visualize_trajectory else None
@@ -1445,6 +1517,8 @@ class PharmacophoreDiff(_Base):
             if visualize_trajectory:
                 kwargs["traj_frames"] = (traj_x[:, f0:f1], traj_h[:, f0:f1])
             out.append(SampledPharmacophore(**kwargs))
+            if pairs is not None:
+                out[-1].pair_energy, out[-1].pair_violations = pair_restraint_energy(x0[f0:f1], pairs[gi])
         return out
 
     def _with_pins(self, ref_graphs, n_pharms, pinned):
@@ -1480,7 +1554,8 @@ class PharmacophoreDiff(_Base):
                guide_clip: float = 0.0, seeds=None, seed_level: int = None, seed_keep=None,
                score_levels: int = None, sample_steps: int = None, sampler: str = None, eta: float = None,
                spacing: str = None, guide_family: str = "wide", pocket_field=None, type_restraints=None,
-               type_guidance=None) -> List[List[SampledPharmacophore]]:
+               type_guidance=None, pair_restraints=None, min_separation: float = None,
+               separation_weight: float = 1.0) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -1531,6 +1606,18 @@ class PharmacophoreDiff(_Base):
         keeps its type), ``restraints``, ``pocket_field``, ``seeds``, first-order ``sample_steps`` and both ``guide_family``
         values; refused like restraints with sampler 'multistep' and with ``pin_resamples`` > 1.
 
+        ``pair_restraints``: None, or one entry per pocket -- None or a list of (i, j, lo, hi, weight): i, j center indices of the
+        pharmacophore, or None / '*' / a negative index for every center; the distance of every covered pair of centers of one
+        sample is held in lo .. hi (hi = inf: no upper bound) by weight * (max(0, lo - rho)^2 + max(0, rho - hi)^2) on the
+        predicted clean centers (pocket_io.parse_pair_restraints reads them from text).  A position-pinned center
+        stands at its given position and is not moved.  Copies of a pocket share its pair restraints; a batch with one runs guided.
+        ``min_separation`` d with ``separation_weight`` w (default 1): "no two centers closer than d" -- (*, *, d, inf, w) on
+        every graph, behind its pair restraints.  EVERY batch then runs guided, like a pocket field.  Both compose with
+        ``pinned``, ``restraints``, ``pocket_field``, ``type_restraints``, ``seeds``, first-order ``sample_steps`` and both
+        ``guide_family`` values; refused like restraints with sampler 'multistep' and with ``pin_resamples`` > 1.  An index that a
+        requested size does not have is a ValueError.  Every returned SampledPharmacophore of a batch that carried pair restraints
+        has ``pair_energy`` / ``pair_violations``: analysis.pair_restraint_energy of its final centers.
+
         ``seeds`` with ``seed_level`` a, 1 <= a <= T: variations of given pharmacophores (partial diffusion, pf_sample_seed_next)
         -- one (x [n,3], types [n]) per pocket, every pocket must have one and every requested size of it must equal n.  Each
         seed is noised forward to level a and only the steps a-1 .. 0 are run: a small a gives close analogues, a large a loose
@@ -1558,13 +1645,15 @@ class PharmacophoreDiff(_Base):
         stratified levels (score(), uniform weighting, seed 0) -- a second pass behind the sampling, which it leaves bit for bit
         as it is without.  None (the default): no scoring, ``.score`` stays None."""
         type_restraints = self._type_restraints(type_restraints, len(ref_graphs), "pockets")
+        pair_restraints = self._pair_restraints(pair_restraints, len(ref_graphs), "pockets", n_pharms, int(min_separation is not None))
         spec = self._run_spec(pins=pinned is not None and any(p is not None for p in pinned),
-                              guided=self._guided(restraints, pocket_field, type_restraints), pinned=pinned is not None,
+                              guided=self._guided(restraints, pocket_field, type_restraints, pair_restraints, min_separation),
+                              pinned=pinned is not None,
                               pin_resamples=pin_resamples,
                               pin_jump=pin_jump, guide_scale=guide_scale, guide_clip=guide_clip, seeds=seeds, seed_level=seed_level,
                               seed_keep=seed_keep, score_levels=score_levels, sample_steps=sample_steps, sampler=sampler, eta=eta,
                               spacing=spacing, guide_family=guide_family, pocket_field=pocket_field, type_guidance=type_guidance,
-                              typed=type_restraints is not None)
+                              typed=type_restraints is not None, min_separation=min_separation, separation_weight=separation_weight)
         for r, rs in enumerate(type_restraints or []):
             for _, c, _, _, _ in (rs or []):
                 if c is not None:
@@ -1669,8 +1758,10 @@ class PharmacophoreDiff(_Base):
                 batch_r = [restraints[graph_ref_idx[i]] for i in idx] if restraints is not None else None
                 field = self._field_for_batch(batch_g, pocket_field, None if radii is None else [radii[graph_ref_idx[i]] for i in idx])
                 batch_t = [type_restraints[graph_ref_idx[i]] for i in idx] if type_restraints is not None else None
+                batch_p = [pair_restraints[graph_ref_idx[i]] for i in idx] if pair_restraints is not None else None
                 enq = self._sample_enqueue(batch_g, spec, init_coms, visualize_trajectory, None if noise is None else noise[bi],
-                                           lane=lane, restraints=batch_r, field=field, generator=gen, type_restraints=batch_t)
+                                           lane=lane, restraints=batch_r, field=field, generator=gen, type_restraints=batch_t,
+                                           pair_restraints=batch_p)
             pending.append((idx, enq))
             if len(pending) > n_lanes:                  # every lane has a batch queued behind the one it runs: fetch the oldest
                 i0, e0 = pending.pop(0)                 # (its lane goes straight into the batch just enqueued) and split it on

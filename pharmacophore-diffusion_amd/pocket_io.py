@@ -440,3 +440,52 @@ def parse_type_restraints(text: str, source: str = "type restraints"):
 def read_type_restraints(path):
     with open(path) as f:
         return parse_type_restraints(f.read(), source=str(path))
+
+
+def parse_pair_restraints(text: str, source: str = "pair restraints"):
+    """One pair restraint per line: ``pair I|* J|* LO HI|inf WEIGHT`` -- two center indices of the pharmacophore (``*``: every
+    center), the distance range in angstroms the pair is held in (``inf``: no upper bound) and the weight of the energy.  ``#``
+    starts a comment; blank lines are skipped.  Returns [(i or None, j or None, lo, hi, weight)], the form
+    PharmacophoreDiff.sample(pair_restraints=...) takes per pocket.  Errors carry the line number."""
+    import math
+    out = []
+    for no, raw in enumerate(text.splitlines(), 1):
+        line = raw.split("#", 1)[0].strip()
+        if not line:
+            continue
+        tok = line.split()
+        where = f"{source}, line {no}"
+        if tok[0] != "pair":
+            raise ValueError(f"{where}: a pair restraint starts with 'pair', got {tok[0]!r}")
+        if len(tok) != 6:
+            raise ValueError(f"{where}: expected 'pair I|* J|* LO HI|inf WEIGHT', got {len(tok)} fields")
+        centers = []
+        for t in tok[1:3]:
+            if t == "*":
+                centers.append(None)
+                continue
+            try:
+                centers.append(int(t))
+            except ValueError:
+                raise ValueError(f"{where}: a center is an index or '*', got {t!r}") from None
+            if centers[-1] < 0:
+                raise ValueError(f"{where}: a center index must not be negative, got {centers[-1]}")
+        if centers[0] is not None and centers[0] == centers[1]:
+            raise ValueError(f"{where}: a pair names two different centers, got {centers[0]} twice")
+        try:
+            lo, hi, w = (float(v) for v in tok[3:6])
+        except ValueError:
+            raise ValueError(f"{where}: LO HI WEIGHT must be numbers (HI may be inf), got {' '.join(tok[3:6])!r}") from None
+        if not (math.isfinite(lo) and lo >= 0):
+            raise ValueError(f"{where}: LO must be finite and not negative, got {lo:g}")
+        if not hi >= lo:
+            raise ValueError(f"{where}: HI must not be below LO (inf: no upper bound), got {lo:g} and {hi:g}")
+        if not (math.isfinite(w) and w >= 0):
+            raise ValueError(f"{where}: WEIGHT must be finite and not negative, got {w:g}")
+        out.append((centers[0], centers[1], lo, hi, w))
+    return out
+
+
+def read_pair_restraints(path):
+    with open(path) as f:
+        return parse_pair_restraints(f.read(), source=str(path))
