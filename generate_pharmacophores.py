@@ -60,6 +60,13 @@ _FLAGS = [
     ('--keep_best', dict(type=int, default=None, help='with --score_samples: write only this many samples, best (lowest per-center score) first')),
     ('--score_pharmacophores', dict(type=Path, default=None, help='no sampling: score every frame of this file (pharms.xyz format) against the pocket and write scores.tsv; --score_samples gives the number of levels (default: every level); with the --seed, --score_samples, --score_weighting and --max_batch_size of the run that wrote the file, and its frames in their order, this reproduces that run\'s scores.tsv (the noise of a score is drawn per device batch)')),
     ('--score_weighting', dict(choices=['uniform', 'vlb'], default=None, help='weights of the levels in a score: uniform (default; the per-graph training loss) or vlb (the diffusion terms of the variational bound)')),
+    ('--consensus', dict(action='store_true', help='analyse the drawn samples as a set: write consensus.xyz (one frame per cluster of similar samples, largest first: the cluster centroid\'s centers at the mean of their partners in the members, with the share of members that have one as a fifth column) and clusters.tsv (sample index, cluster, is-centroid, neighbour count, mean center support)')),
+    ('--consensus_sigma', dict(type=float, default=None, metavar='A', help='with --consensus / --consensus_of / --keep_diverse: width of the Gaussians of the similarity between two samples, angstroms (default 1.0)')),
+    ('--consensus_tolerance', dict(type=float, default=None, metavar='A', help='with --consensus / --consensus_of: two centers of one type within this distance are the same center (default 1.5)')),
+    ('--consensus_threshold', dict(type=float, default=None, metavar='S', help='with --consensus / --consensus_of: samples at least this similar (0..1) are neighbours in the clustering (default 0.5)')),
+    ('--min_support', dict(type=float, default=None, metavar='F', help='with --consensus / --consensus_of: consensus.xyz lists the centers found in at least this share of a cluster\'s members (default 0.5)')),
+    ('--keep_diverse', dict(type=int, default=None, metavar='K', help='write only K samples chosen by max-min selection on the similarity (each next one the least similar to those chosen, starting from the largest cluster\'s centroid); with --keep_best: the best N first, then K diverse among them')),
+    ('--consensus_of', dict(type=Path, default=None, metavar='FILE', help='no sampling, no receptor_file, no checkpoint: analyse the frames of this file (pharms.xyz format, all of one pocket) as --consensus does and write consensus.xyz and clusters.tsv')),
     ('--metrics', dict(action='store_true', help='print the validity of the samples against receptor pharmacophore features')),
     ('--use_ema', dict(action='store_true', help="sample from the checkpoint's EMA weights (its 'ema_state_dict', written by train.py with ema_decay set) instead of the training weights")),
 ]
@@ -67,9 +74,59 @@ _FLAGS = [
 
 def parse_arguments(argv=None):
     parser = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    argv = sys.argv[1:] if argv is None else list(argv)
+    file_only = any(str(v) == '--consensus_of' or str(v).startswith('--consensus_of=') for v in argv)
     for flag, kw in _FLAGS:
+        if flag == 'receptor_file' and file_only:           # --consensus_of reads no receptor: the positional may be left out
+            kw = dict(kw, nargs='?', default=None)
         parser.add_argument(flag, **kw)
     a = parser.parse_args(argv)
+    analysed = a.consensus or a.consensus_of is not None
+    for flag in ('consensus_sigma', 'consensus_tolerance', 'consensus_threshold', 'min_support'):
+        v = getattr(a, flag)
+        if v is not None and not (analysed or (flag == 'consensus_sigma' and a.keep_diverse is not None)):
+            parser.error(f'--{flag} needs --consensus or --consensus_of' + (' or --keep_diverse' if flag == 'consensus_sigma' else ''))
+        if v is not None and not (v >= 0 and v < float('inf')):
+            parser.error(f'--{flag} must be finite and not negative, got {v}')
+    if a.consensus_sigma is not None and not a.consensus_sigma > 0:
+        parser.error(f'--consensus_sigma must be positive, got {a.consensus_sigma}')
+    for flag in ('consensus_threshold', 'min_support'):
+        if getattr(a, flag) is not None and getattr(a, flag) > 1:
+            parser.error(f'--{flag} must lie in 0..1, got {getattr(a, flag)}')
+    a.consensus_sigma = 1.0 if a.consensus_sigma is None else a.consensus_sigma
+    a.consensus_tolerance = 1.5 if a.consensus_tolerance is None else a.consensus_tolerance
+    a.consensus_threshold = 0.5 if a.consensus_threshold is None else a.consensus_threshold
+    a.min_support = 0.5 if a.min_support is None else a.min_support
+    if a.keep_diverse is not None and a.keep_diverse < 1:
+        parser.error(f'--keep_diverse must be at least 1, got {a.keep_diverse}')
+    if a.keep_diverse is not None and a.visualize_trajectory:
+        parser.error('--keep_diverse together with --visualize_trajectory: trajectories are written per sample index')
+    if a.keep_diverse is not None and (a.score_pharmacophores is not None or a.consensus_of is not None):
+        parser.error('--keep_diverse together with --score_pharmacophores / --consensus_of: nothing is sampled, every frame is listed')
+    a.consensus_frames = None
+    if a.consensus_of is not None:
+        given = [f for f in ('receptor_file', '--ckpt', '--model_dir', '--ref_ligand_file', '--residue_list', '--samples_per_pocket', '--pharm_sizes',
+                             '--visualize_trajectory', '--pinned_centers', '--restraints', '--type_restraints', '--pair_restraints',
+                             '--min_separation', '--avoid_clashes', '--seed_pharmacophore', '--sample_steps', '--score_samples',
+                             '--score_pharmacophores', '--use_ref_lig_com', '--metrics', '--use_ema', '--consensus')
+                 if getattr(a, f.lstrip('-')) not in (parser.get_default(f.lstrip('-')), None)]
+        if given:
+            parser.error(f'--consensus_of samples nothing and reads no receptor or checkpoint: {" ".join(given)} make no sense with it')
+        from pharmacoforge_amd.analysis import read_pharmacophores
+        try:
+            a.consensus_frames = read_pharmacophores(a.consensus_of)
+        except (OSError, ValueError) as e:
+            parser.error(f'--consensus_of: {e}')
+        big = [i for i, (x, _) in enumerate(a.consensus_frames) if len(x) > 64]
+        if big:
+            parser.error(f'--consensus_of: frame(s) {big} have more than 64 centers')
+        if len(a.consensus_frames) > 1024:
+            parser.error(f'--consensus_of: {len(a.consensus_frames)} frames (a set has at most 1024 samples)')
+        return a
+    if (a.consensus or a.keep_diverse is not None) and a.samples_per_pocket > 1024:
+        parser.error(f'--consensus / --keep_diverse: --samples_per_pocket {a.samples_per_pocket} (a set has at most 1024 samples)')
+    if a.consensus and a.score_pharmacophores is not None:
+        parser.error('--consensus together with --score_pharmacophores: nothing is sampled; --consensus_of analyses a file')
     for flag in ('pin_resamples', 'pin_jump'):
         v = getattr(a, flag)
         if v is not None and a.pinned_centers is None and a.seed_keep is None:     # (a seeded run with --seed_keep is a pinned run)
@@ -305,11 +362,38 @@ def write_scores(path, indices, scores, clashes=None, type_energies=None, pair_e
     Path(path).write_text('\n'.join(lines) + '\n')
 
 
+def analyse_set(pfa, frames, args, engine=None):
+    """The SampleSet of (positions, types) frames of one pocket under the --consensus_* options: on the engine's device, or on
+    the host without one."""
+    return pfa.sample_sets([frames], engine, sigma=args.consensus_sigma, tolerance=args.consensus_tolerance,
+                           threshold=args.consensus_threshold, min_support=args.min_support)[0]
+
+
+def write_consensus(pocket_dir, sset, picks=None):
+    """consensus.xyz and clusters.tsv of a SampleSet; picks (--keep_diverse): one more column, the rank of each sample among the
+    picks or -1"""
+    (pocket_dir / 'consensus.xyz').write_text(sset.consensus_xyz())
+    rows = sset.clusters_tsv().splitlines()
+    if picks is not None:
+        rank = {a: k for k, a in enumerate(picks)}
+        rows = [rows[0] + '\tpick'] + [f'{row}\t{rank.get(a, -1)}' for a, row in enumerate(rows[1:])]
+    (pocket_dir / 'clusters.tsv').write_text('\n'.join(rows) + '\n')
+
+
 def main(argv=None):
     import pharmacoforge_amd as pfa
     from pharmacoforge_amd.pocket_io import get_prot_atom_ph_type_maps, process_ligand_and_pocket
 
     args = parse_arguments(argv)
+    if args.consensus_frames is not None:       # no sampling, no receptor, no checkpoint: the frames of the file as one set
+        name = args.receptor_name or args.consensus_of.name.split('.')[0]
+        pocket_dir = Path(args.output_dir) / name
+        pocket_dir.mkdir(parents=True, exist_ok=True)
+        engine = pfa.PfEngine(pharm_nf=len(pfa.SampledPharmacophore.type_idx_to_elem)) if torch.cuda.is_available() else None
+        sset = analyse_set(pfa, args.consensus_frames, args, engine)
+        write_consensus(pocket_dir, sset)
+        print(f'{name}: {sset.n_samples} pharmacophores in {len(sset.clusters)} clusters, sizes ' + ' '.join(str(c.size) for c in sset.clusters))
+        return
     for path, what in ((args.receptor_file, 'receptor'), (args.ref_ligand_file, 'ligand')):
         if path is not None and not path.exists():
             raise ValueError(f'{what} file {path} not found')
@@ -411,15 +495,29 @@ def main(argv=None):
     for src in (args.receptor_file, args.ref_ligand_file):
         if src is not None:
             shutil.copy(src, ref_dir / src.name)
+    order, scores = list(range(len(pharms))), None
     if args.score_samples is not None:
         # the scores describe the frames as pharms.xyz holds them (three decimals, argmax types): scoring that file again
         # (--score_pharmacophores) with the same seed and levels gives the same numbers
         frames = [ph.as_written() for ph in pharms]
         scores = score_frames(pfa, model, pocket, frames, args)
-        order = list(range(len(pharms)))
         if args.keep_best is not None:
             order = sorted(order, key=lambda i: (scores[i].per_center, i))[:args.keep_best]
-        pharms, scores = [pharms[i] for i in order], [scores[i] for i in order]
+    if args.consensus or args.keep_diverse is not None:
+        # the set is what pharms.xyz would hold without --keep_diverse (the best N with --keep_best), as written: --consensus_of on
+        # that file gives the same analysis.  clusters.tsv numbers the samples of that set
+        sset = analyse_set(pfa, [pharms[i].as_written() for i in order], args, model.dynamics.engine())
+        picks = None if args.keep_diverse is None else sset.pick_diverse(args.keep_diverse)
+        if args.consensus:
+            write_consensus(pocket_dir, sset, picks)
+            print(f'{name}: {len(sset.clusters)} clusters, sizes ' + ' '.join(str(c.size) for c in sset.clusters))
+        if picks is not None:
+            order = [order[a] for a in picks]
+            print(f'{name}: --keep_diverse kept samples ' + ' '.join(str(a) for a in picks))
+    if scores is not None or args.keep_diverse is not None:
+        pharms = [pharms[i] for i in order]
+    if scores is not None:
+        scores = [scores[i] for i in order]
         write_scores(pocket_dir / 'scores.tsv', range(len(scores)), scores, None if clashes is None else [clashes[i] for i in order],
                      None if type_energies is None else [type_energies[i] for i in order],
                      None if pair_energies is None else [pair_energies[i] for i in order])

@@ -444,6 +444,42 @@ int pf_guide_pairs_next(pf_handle* h, const int32_t* host_ptr /*[B+1] or NULL*/,
                         const float* host_lo /*[n]*/, const float* host_hi /*[n]*/, const float* host_w /*[n]*/);
 int pf_debug_last_pairs(pf_handle* h, float* dev_g_pair /*[Nf,3]*/, float* dev_E_pair /*[B]*/, pf_stream stream);
 
+/* -- sample sets: what the samples of one pocket agree on (no reference counterpart) ---------------------------------
+ * A set is the S samples of one pocket, 1 <= S <= 1024; sample a has n_a centers, 1 <= n_a <= 64, positions x_ai in the caller's
+ * frame and integer types t_ai in [0, pharm_nf).  All samples of a pocket live in the pocket's frame: nothing is aligned, and sets
+ * of different pockets do not compare.  Type identity is exact.  With sigma > 0, tolerance >= 0 and threshold in [0, 1]:
+ *   overlap      O(a,b) = sum_i sum_j [t_ai == t_bj] exp(-|x_ai - x_bj|^2 / (2 sigma^2))
+ *   similarity   sim(a,b) = O(a,b) / (O(a,a) + O(b,b) - O(a,b)); the matrix is bitwise symmetric with exactly 1.0f on the diagonal
+ *                and values in [0, 1] (min(., 1) against rounding; two identical samples give exactly 1)
+ *   support      support(a,i) = number of samples b != a of the set with a center of type t_ai within tolerance (<=) of x_ai
+ *   clusters     Taylor-Butina: adj(a,b) = a != b and sim(a,b) >= threshold on the fp32 values as written, count(a) = sum_b adj(a,b);
+ *                samples are visited in the order (-count, index); an unassigned sample becomes the centroid of a new cluster (ids
+ *                in order of creation) and takes every still unassigned neighbour; counts are not updated as samples leave
+ *   consensus    of cluster c with centroid sample m, per center i of m: the members b of c ascending (m included) each give their
+ *                nearest center of type t_mi within tolerance of x_mi (ties: the lowest j); cnt_i counts them, the consensus
+ *                position is their fp32 sum in that order divided by cnt_i
+ * P sets per call.  HOST arrays set_ptr [P+1] (set p owns samples [set_ptr[p], set_ptr[p+1])) and center_ptr [S+1] (sample s owns
+ * centers [center_ptr[s], center_ptr[s+1])), copied before the call returns.  DEVICE arrays: dev_x [N,3], dev_type [N] int32 in;
+ * out dev_sim [sum S_p^2] (set p's S_p x S_p matrix row-major, the sets one after the other; NULL: kept in the handle's
+ * workspace), dev_support [N] int32, dev_label [S] (cluster id within the set), dev_centroid / dev_size [S] (cluster c of set p
+ * sits at slot set_ptr[p] + c: the centroid's sample index within the set and the member count; slots beyond n_clusters hold -1),
+ * dev_n_clusters [P], dev_cons_x [N,3] and dev_cons_cnt [N] int32 (filled for the centers of centroid samples, zero elsewhere).
+ * Validation on the host before anything is launched (csrc/pf_sset.h): pointers start at 0 and do not decrease, 1 <= S_p <= 1024,
+ * 1 <= n_a <= 64, sum S_p^2 <= 2^26, finite options in range -- a failure is PF_ERR_ARG with a message.  The types are on the
+ * device: the kernel counts those outside [0, pharm_nf), the host reads the count behind the launches (the call waits for the
+ * stream) and reports PF_ERR_ARG; the outputs then mean nothing.
+ * The call needs no committed weights and no bound batch, owns its workspace (grown on demand, freed by pf_destroy) and touches no
+ * run state: between two sampling runs, inside one, or while a batch is bound, it changes nothing those see.  Every output has
+ * the same bits on every run, and a set's outputs do not depend on the other sets of the call. */
+#define PF_SSET_MAX_SAMPLES 1024
+#define PF_SSET_MAX_CENTERS 64
+typedef struct pf_sset_opts { float sigma; float tolerance; float threshold; } pf_sset_opts;
+int pf_sample_set_analyze(pf_handle* h, int32_t P, const int32_t* host_set_ptr /*[P+1]*/, const int32_t* host_center_ptr /*[S+1]*/,
+                          const float* dev_x /*[N,3]*/, const int32_t* dev_type /*[N]*/, const pf_sset_opts* opts,
+                          float* dev_sim /*[sum S_p^2] or NULL*/, int32_t* dev_support /*[N]*/, int32_t* dev_label /*[S]*/,
+                          int32_t* dev_centroid /*[S]*/, int32_t* dev_size /*[S]*/, int32_t* dev_n_clusters /*[P]*/,
+                          float* dev_cons_x /*[N,3]*/, int32_t* dev_cons_cnt /*[N]*/, pf_stream stream);
+
 /* -- seeded sampling: start the reverse process from a given pharmacophore (partial diffusion; no reference counterpart) ----------
  * The given sample is noised forward to an intermediate level a, 1 <= a <= T, and only the reverse steps a-1 .. 0 are run: a small
  * a gives close analogues of the seed, a large a loose ones.

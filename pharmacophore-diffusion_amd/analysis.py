@@ -311,3 +311,273 @@ class SampleAnalyzer:
         if process_group is not None:
             counts = _allreduce_sum(counts, process_group, device)
         return counts
+
+
+# ---- sample sets: what the samples of one pocket agree on (include/pfdyn.h "sample sets"; DESIGN 4.26) ----------------------------
+# The CPU product path of pf_sample_set_analyze, same definitions, usable without a GPU.  A set is a list of samples, each
+# (positions [n, 3], type indices [n]) in the pocket's frame; nothing is aligned, and type identity is exact.
+
+SSET_MAX_SAMPLES, SSET_MAX_CENTERS = 1024, 64
+
+
+def _sset_samples(samples, dtype=torch.float32):
+    """[(x [n, 3] dtype, types [n] int64)] on the host from (x, types) pairs or SampledPharmacophore objects, limits checked."""
+    out = []
+    for s in samples:
+        x, t = (s.ph_coords, s.ph_feats_idxs) if hasattr(s, "ph_coords") else s
+        x = torch.as_tensor(x).detach().to("cpu", dtype).reshape(-1, 3)
+        t = torch.as_tensor(t).detach().to("cpu", torch.int64).reshape(-1)
+        if x.shape[0] != t.shape[0]:
+            raise ValueError(f"sample {len(out)}: {x.shape[0]} positions for {t.shape[0]} types")
+        if not 1 <= x.shape[0] <= SSET_MAX_CENTERS:
+            raise ValueError(f"sample {len(out)} has {x.shape[0]} centers (1 to {SSET_MAX_CENTERS} per sample)")
+        out.append((x, t))
+    if not 1 <= len(out) <= SSET_MAX_SAMPLES:
+        raise ValueError(f"a sample set has {len(out)} samples (1 to {SSET_MAX_SAMPLES} per set)")
+    return out
+
+
+def _sset_options(sigma=1.0, tolerance=1.5, threshold=0.5):
+    import math
+    sigma, tolerance, threshold = float(sigma), float(tolerance), float(threshold)
+    if not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError("sigma must be finite and > 0")
+    if not (math.isfinite(tolerance) and tolerance >= 0):
+        raise ValueError("tolerance must be finite and >= 0")
+    if not 0.0 <= threshold <= 1.0:
+        raise ValueError("threshold must be in [0, 1]")
+    return sigma, tolerance, threshold
+
+
+def _sset_padded(samples):
+    """x [S, m, 3], types [S, m] (padding: -1 - sample index, equal to no type), n [S]"""
+    S, m = len(samples), max(x.shape[0] for x, _ in samples)
+    X = torch.zeros(S, m, 3, dtype=samples[0][0].dtype)
+    T = -1 - torch.arange(S, dtype=torch.int64)[:, None].repeat(1, m)
+    for a, (x, t) in enumerate(samples):
+        X[a, :x.shape[0]], T[a, :x.shape[0]] = x, t
+    return X, T, torch.tensor([x.shape[0] for x, _ in samples])
+
+
+def _sset_rows(X, T, rows):
+    """squared distances [r, S, m, m] and same-type mask between the centers of samples `rows` and those of every sample; a padded
+    center (a negative type) matches nothing, not even itself"""
+    d = X[rows][:, None, :, None, :] - X[None, :, None, :, :]
+    same = (T[rows][:, None, :, None] == T[None, :, None, :]) & (T[rows] >= 0)[:, None, :, None]
+    return (d * d).sum(dim=-1), same
+
+
+def sample_set_similarity(samples, sigma=1.0, dtype=torch.float32):
+    """The typed Gaussian-overlap Tanimoto matrix [S, S] of a set: O(a,b) = sum_i sum_j [t_ai == t_bj] exp(-|x_ai - x_bj|^2 /
+    (2 sigma^2)), sim(a,b) = O(a,b) / (O(a,a) + O(b,b) - O(a,b)).  Each unordered pair is computed once and stored to both
+    places; the diagonal is exactly 1."""
+    samples = _sset_samples(samples, dtype)
+    sigma = _sset_options(sigma=sigma)[0]
+    X, T, _ = _sset_padded(samples)
+    S, m = X.shape[0], X.shape[1]
+    O = torch.zeros(S, S, dtype=dtype)
+    step = max(1, (1 << 22) // (S * m * m))
+    for a0 in range(0, S, step):
+        rows = torch.arange(a0, min(a0 + step, S))
+        d2, same = _sset_rows(X, T, rows)
+        O[rows] = (torch.exp(-d2 / (2.0 * sigma * sigma)) * same).sum(dim=(2, 3))
+    self_o = torch.diagonal(O).clone()
+    up = torch.triu(O, diagonal=1)
+    sim = (up / (self_o[:, None] + self_o[None, :] - up)).clamp(max=1.0)       # (an ulp of rounding between near-identical samples)
+    sim = torch.triu(sim, diagonal=1)
+    sim = sim + sim.T
+    sim.fill_diagonal_(1.0)
+    return sim
+
+
+def sample_set_support(samples, tolerance=1.5):
+    """One int64 tensor [n_a] per sample: support(a, i) = the number of samples b != a of the set with a center of type t_ai within
+    `tolerance` (<=) of x_ai."""
+    samples = _sset_samples(samples, torch.float64)
+    tol = _sset_options(tolerance=tolerance)[1]
+    X, T, n = _sset_padded(samples)
+    S, m = X.shape[0], X.shape[1]
+    sup = torch.zeros(S, m, dtype=torch.int64)
+    step = max(1, (1 << 22) // (S * m * m))
+    for a0 in range(0, S, step):
+        rows = torch.arange(a0, min(a0 + step, S))
+        d2, same = _sset_rows(X, T, rows)
+        hit = ((d2 <= tol * tol) & same).any(dim=3)                     # [r, S, m]: center i of row sample has a partner in sample b
+        hit[torch.arange(rows.shape[0]), rows] = False
+        sup[rows] = hit.sum(dim=1)
+    return [sup[a, :int(n[a])].clone() for a in range(S)]
+
+
+def butina_clusters(sim, threshold=0.5):
+    """Taylor-Butina on a similarity matrix [S, S], the values compared as they are: adj(a,b) = a != b and sim(a,b) >= threshold,
+    count(a) = sum_b adj(a,b); samples are visited in the order (-count, index); an unassigned sample becomes the centroid of a
+    new cluster (ids in order of creation) and takes every still unassigned neighbour.  Counts are not updated as samples
+    leave: the result depends on that order by design.  Returns (labels [S] int64, centroids, sizes, counts [S])."""
+    sim = torch.as_tensor(sim).detach().cpu()
+    S = sim.shape[0]
+    if sim.dim() != 2 or sim.shape[1] != S or S < 1:
+        raise ValueError(f"a square similarity matrix is required, got {tuple(sim.shape)}")
+    thr = torch.tensor(_sset_options(threshold=threshold)[2], dtype=sim.dtype)
+    adj = sim >= thr
+    adj.fill_diagonal_(False)
+    counts = adj.sum(dim=1)
+    order = sorted(range(S), key=lambda a: (-int(counts[a]), a))
+    labels = torch.full((S,), -1, dtype=torch.int64)
+    centroids, sizes = [], []
+    for a in order:
+        if labels[a] >= 0:
+            continue
+        take = adj[a] & (labels < 0)
+        take[a] = True
+        labels[take] = len(centroids)
+        centroids.append(a)
+        sizes.append(int(take.sum()))
+    return labels, centroids, sizes, counts
+
+
+def cluster_consensus(samples, labels, centroids, tolerance=1.5, dtype=torch.float32):
+    """Per cluster c (centroid sample m = centroids[c]) and center i of m: the members of c in ascending index (m included) each
+    give their nearest center of type t_mi within `tolerance` of x_mi (ties: the lowest index); their positions are summed in
+    that order in `dtype` and divided by their number.  Returns one (positions [n_m, 3], types [n_m], counts [n_m] int64) per
+    cluster; counts / cluster size is the consensus support."""
+    samples = _sset_samples(samples, dtype)
+    tol = _sset_options(tolerance=tolerance)[1]
+    tol2 = torch.tensor(tol * tol, dtype=dtype)
+    labels = torch.as_tensor(labels).cpu()
+    out = []
+    for c, m in enumerate(centroids):
+        xm, tm = samples[int(m)]
+        pos, cnt = torch.zeros_like(xm), torch.zeros(xm.shape[0], dtype=torch.int64)
+        for b in torch.nonzero(labels == c).reshape(-1).tolist():
+            xb, tb = samples[b]
+            d = xm[:, None, :] - xb[None, :, :]
+            d2 = (d * d).sum(dim=-1)
+            ok = (tm[:, None] == tb[None, :]) & (d2 <= tol2)
+            j = torch.where(ok, d2, torch.full_like(d2, float("inf"))).argmin(dim=1)        # (argmin: the first of equals)
+            got = ok.any(dim=1)
+            pos = pos + torch.where(got[:, None], xb[j], torch.zeros_like(xm))
+            cnt = cnt + got.to(torch.int64)
+        out.append((pos / cnt.clamp(min=1).to(dtype)[:, None], tm.clone(), cnt))
+    return out
+
+
+def pick_diverse(sim, k, first=None):
+    """Max-min selection of k samples on a similarity matrix: after `first`, the next pick is the sample with the largest minimum
+    distance 1 - sim to those chosen (ties: the lowest index).  `first` defaults to the centroid of the largest Butina cluster at
+    the default threshold (ties: the first made).  Returns the chosen indices in order of choice; at most S of them."""
+    sim = torch.as_tensor(sim).detach().cpu().double()
+    S = sim.shape[0]
+    if int(k) < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    if first is None:
+        _, centroids, sizes, _ = butina_clusters(sim)
+        first = centroids[max(range(len(sizes)), key=lambda c: (sizes[c], -c))]
+    first = int(first)
+    if not 0 <= first < S:
+        raise ValueError(f"first = {first} is not a sample of the set ({S})")
+    chosen = [first]
+    far = 1.0 - sim[first]
+    far[first] = -1.0
+    while len(chosen) < min(int(k), S):
+        nxt = int(torch.argmax(far))            # (argmax: the first of equals)
+        chosen.append(nxt)
+        far = torch.minimum(far, 1.0 - sim[nxt])
+        far[chosen] = -1.0
+    return chosen
+
+
+class ConsensusPharmacophore:
+    """The consensus of one cluster of a sample set: the centers of the cluster's centroid sample, each moved to the mean of its
+    nearest same-type partners in the members, with the fraction of members that have one.  ``centroid``: the centroid's sample
+    index within the set; ``members``: the cluster's sample indices, ascending; ``positions`` [n, 3], ``types`` [n] (indices),
+    ``counts`` [n] and ``support`` [n] = counts / len(members).  It is the centroid's consensus, not a re-fit."""
+    __slots__ = ("cluster", "centroid", "members", "positions", "types", "counts", "support")
+
+    def __init__(self, cluster, centroid, members, positions, types, counts):
+        self.cluster, self.centroid, self.members = int(cluster), int(centroid), [int(b) for b in members]
+        self.positions = torch.as_tensor(positions).detach().to("cpu", torch.float32).reshape(-1, 3)
+        self.types = torch.as_tensor(types).detach().to("cpu", torch.int64).reshape(-1)
+        self.counts = torch.as_tensor(counts).detach().to("cpu", torch.int64).reshape(-1)
+        self.support = self.counts.double() / max(len(self.members), 1)
+
+    @property
+    def size(self):
+        return len(self.members)
+
+    def to_xyz_file(self, filename: str = None, min_support: float = 0.0):
+        """One frame in the pharms.xyz format with the support as a trailing column: the number of centers written, then
+        `element x y z support` per center whose support is at least ``min_support``."""
+        keep = [i for i in range(self.types.shape[0]) if float(self.support[i]) >= float(min_support)]
+        rows = self.positions.double().tolist()
+        body = "".join(f"{_XYZ_ELEMENTS[int(self.types[i])]} {rows[i][0]:.3f} {rows[i][1]:.3f} {rows[i][2]:.3f} {float(self.support[i]):.3f}\n"
+                       for i in keep)
+        return _emit(f"{len(keep)}\n" + body, filename)
+
+    def __repr__(self):
+        return f"ConsensusPharmacophore(cluster={self.cluster}, centroid={self.centroid}, size={self.size}, centers={self.types.shape[0]})"
+
+
+class SampleSet:
+    """What the S samples of one pocket agree on.  ``similarity`` [S, S] fp32; ``support``: one int64 tensor per sample, the
+    number of other samples that hold each of its centers; ``labels`` [S]: the Butina cluster id of each sample (ids in order
+    of creation); ``neighbour_counts`` [S]; ``clusters``: ConsensusPharmacophore objects, largest first, ties by id;
+    ``pick_diverse(k)``: max-min selection starting from the largest cluster's centroid.  ``options``: sigma, tolerance,
+    threshold, min_support."""
+
+    def __init__(self, similarity, support, labels, centroids, consensus, neighbour_counts=None, options=None):
+        self.similarity = torch.as_tensor(similarity).detach().to("cpu", torch.float32)
+        self.support = [torch.as_tensor(s).detach().to("cpu", torch.int64) for s in support]
+        self.labels = torch.as_tensor(labels).detach().to("cpu", torch.int64)
+        self.options = dict(options or {})
+        if neighbour_counts is None:
+            adj = self.similarity >= torch.tensor(float(self.options.get("threshold", 0.5)), dtype=torch.float32)
+            adj.fill_diagonal_(False)
+            neighbour_counts = adj.sum(dim=1)
+        self.neighbour_counts = torch.as_tensor(neighbour_counts).detach().to("cpu", torch.int64)
+        made = [ConsensusPharmacophore(c, m, torch.nonzero(self.labels == c).reshape(-1).tolist(), *consensus[c])
+                for c, m in enumerate(centroids)]
+        self.clusters = sorted(made, key=lambda c: (-c.size, c.cluster))
+
+    @property
+    def n_samples(self):
+        return int(self.labels.shape[0])
+
+    @property
+    def centroids(self):
+        """centroid sample index of every cluster, by cluster id"""
+        return [c.centroid for c in sorted(self.clusters, key=lambda c: c.cluster)]
+
+    def mean_support(self):
+        """one float per sample: the mean support of its centers, as a fraction of the other samples (0 for a set of one)"""
+        other = max(self.n_samples - 1, 1)
+        return [float(s.double().mean()) / other for s in self.support]
+
+    def pick_diverse(self, k, first=None):
+        return pick_diverse(self.similarity, k, first=self.clusters[0].centroid if first is None else first)
+
+    def consensus_xyz(self, min_support=None):
+        """every cluster's frame (ConsensusPharmacophore.to_xyz_file), largest cluster first"""
+        f = float(self.options.get("min_support", 0.5)) if min_support is None else float(min_support)
+        return "".join(c.to_xyz_file(min_support=f) for c in self.clusters)
+
+    def clusters_tsv(self):
+        """sample index, cluster, is-centroid, neighbour count, mean center support -- one row per sample"""
+        cents, ms = set(self.centroids), self.mean_support()
+        rows = ["sample\tcluster\tis_centroid\tneighbours\tmean_support\n"]
+        for a in range(self.n_samples):
+            rows.append(f"{a}\t{int(self.labels[a])}\t{int(a in cents)}\t{int(self.neighbour_counts[a])}\t{ms[a]:.4f}\n")
+        return "".join(rows)
+
+    def __repr__(self):
+        return f"SampleSet(samples={self.n_samples}, clusters={len(self.clusters)}, largest={self.clusters[0].size})"
+
+
+def analyze_sample_set(samples, sigma=1.0, tolerance=1.5, threshold=0.5, min_support=0.5):
+    """The SampleSet of one pocket's samples, computed on the host (the device path: PharmacophoreDiff.consensus)."""
+    sigma, tolerance, threshold = _sset_options(sigma, tolerance, threshold)
+    samples = _sset_samples(samples)
+    sim = sample_set_similarity(samples, sigma)
+    labels, centroids, _, counts = butina_clusters(sim, threshold)
+    return SampleSet(sim, sample_set_support(samples, tolerance), labels, centroids,
+                     cluster_consensus(samples, labels, centroids, tolerance), counts,
+                     dict(sigma=sigma, tolerance=tolerance, threshold=threshold, min_support=float(min_support)))

@@ -26,6 +26,7 @@
 #include "pf_restr.h"
 #include "pf_types.h"
 #include "pf_pairs.h"
+#include "pf_sset.h"
 
 using namespace pfpack;
 
@@ -75,6 +76,7 @@ void pfk_guide_field(const StepParams* p, const FieldParams* q, hipStream_t s);
 void pfk_guide_field_types(const StepParams* p, const FieldParams* q, const FieldTypeParams* ft, hipStream_t s);
 void pfk_guide_types(const StepParams* p, const TypeParams* q, hipStream_t s);
 void pfk_guide_pairs(const StepParams* p, const PairParams* q, hipStream_t s);
+void pfk_sset_analyze(const SsetParams* q, int work_items, hipStream_t s);
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s);
@@ -445,6 +447,13 @@ struct pf_handle {
         bool armed = false, on = false, have = false;
         int n_arm = 0, n_run = 0;
     } pairs;
+    // sample-set analysis (pf_sample_set_analyze): no run state -- the packed pointer block (pf_sset.h), the similarity matrices of a
+    // call that passes no buffer for them, the status word and its pinned host copy.  Grown on demand, freed in pf_destroy
+    struct SsetWork {
+        StagedBlock blk;
+        void* d_sim = nullptr; size_t sim_capacity = 0;
+        int32_t* d_status = nullptr; int32_t* status_host = nullptr;
+    } sset;
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
@@ -1562,7 +1571,10 @@ void pf_destroy(pf_handle* h) {
     if (h->d_guide) (void)hipFree(h->d_guide);
     if (h->d_gdiff) (void)hipFree(h->d_gdiff);
     if (h->d_optim_part) (void)hipFree(h->d_optim_part);
-    for (StagedBlock* b : {&h->restr, &h->field.blk, &h->types.blk, &h->pairs.blk}) staged_free(*b);
+    for (StagedBlock* b : {&h->restr, &h->field.blk, &h->types.blk, &h->pairs.blk, &h->sset.blk}) staged_free(*b);
+    if (h->sset.d_sim) (void)hipFree(h->sset.d_sim);
+    if (h->sset.d_status) (void)hipFree(h->sset.d_status);
+    if (h->sset.status_host) (void)hipHostFree(h->sset.status_host);
     if (h->types.d_tguide) (void)hipFree(h->types.d_tguide);
     if (h->pairs.d_pguide) (void)hipFree(h->pairs.d_pguide);
     for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
@@ -3859,6 +3871,56 @@ int pf_debug_last_pairs(pf_handle* h, float* dev_g_pair, float* dev_E_pair, pf_s
     const float* d = (const float*)h->pairs.d_pguide;
     if (dev_g_pair && h->Nf) PF_HIP(h, hipMemcpyAsync(dev_g_pair, d + pw.g_pair(), (size_t)h->Nf * 3 * 4, hipMemcpyDeviceToDevice, s));
     if (dev_E_pair && h->B) PF_HIP(h, hipMemcpyAsync(dev_E_pair, d + pw.E_pair(), (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
+    return PF_OK;
+}
+
+// ---- sample sets (include/pfdyn.h: "sample sets") ----
+// Reads the handle's config (pharm_nf) and its own workspace, nothing else: no weights, no batch, no run state.  The call waits
+// for the stream at its end: the status word (types outside [0, pharm_nf), counted by k_sset_overlap's staging) is the host's to read
+static_assert(sizeof(pf_sset_opts) == sizeof(pf_sset_opts_host), "pf_sset.h restates pf_sset_opts");
+int pf_sample_set_analyze(pf_handle* h, int32_t P, const int32_t* host_set_ptr, const int32_t* host_center_ptr, const float* dev_x,
+                          const int32_t* dev_type, const pf_sset_opts* opts, float* dev_sim, int32_t* dev_support, int32_t* dev_label,
+                          int32_t* dev_centroid, int32_t* dev_size, int32_t* dev_n_clusters, float* dev_cons_x, int32_t* dev_cons_cnt,
+                          pf_stream stream) {
+    if (!h) return PF_ERR_ARG;
+    const pfsset::SsetArgs a{P, host_set_ptr, host_center_ptr, reinterpret_cast<const pf_sset_opts_host*>(opts)};
+    char msg[256];
+    if (!pfsset::validate(a, msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
+    if (!dev_x || !dev_type || !dev_support || !dev_label || !dev_centroid || !dev_size || !dev_n_clusters || !dev_cons_x || !dev_cons_cnt)
+        PF_FAIL(h, PF_ERR_ARG, "pf_sample_set_analyze: null device array (only dev_sim may be NULL)");
+    const pfsset::SsetPlan pl = pfsset::plan(a);
+    const pfsset::SsetLayout lay(pl.P, pl.S);
+    hipStream_t s = (hipStream_t)stream;
+    pf_handle::SsetWork& w = h->sset;
+    int rc;
+    const size_t blk_bytes = lay.words() * 4, sim_bytes = (size_t)pl.sim_floats * 4;
+    if ((rc = staged_reserve(h, w.blk, blk_bytes)) != PF_OK) return rc;
+    if ((rc = grow_run_scratch(h, &w.blk.dev, &w.blk.capacity, blk_bytes, blk_bytes * 2, s)) != PF_OK) return rc;
+    if (!dev_sim && (rc = grow_run_scratch(h, &w.d_sim, &w.sim_capacity, sim_bytes, sim_bytes, s)) != PF_OK) return rc;
+    if (!w.d_status) PF_HIP(h, hipMalloc((void**)&w.d_status, 4));
+    if (!w.status_host) PF_HIP(h, hipHostMalloc((void**)&w.status_host, 4, hipHostMallocDefault));
+    pfsset::pack(a, (uint32_t*)w.blk.stage);
+    if ((rc = staged_upload(h, w.blk, blk_bytes, s)) != PF_OK) return rc;
+    const int32_t* d = (const int32_t*)w.blk.dev;
+    SsetParams q{};
+    q.P = pl.P; q.S = pl.S; q.N = pl.N; q.nf = h->cfg.pharm_nf;
+    q.set_ptr = d + lay.set_ptr(); q.sim_ptr = d + lay.sim_ptr(); q.work_ptr = d + lay.work_ptr(); q.center_ptr = d + lay.center_ptr();
+    q.x = dev_x; q.type = dev_type; q.inv_2s2 = pl.inv_2s2; q.tol2 = pl.tol2; q.threshold = pl.threshold;
+    q.sim = dev_sim ? dev_sim : (float*)w.d_sim;
+    q.support = dev_support; q.label = dev_label; q.centroid = dev_centroid; q.size = dev_size; q.n_clusters = dev_n_clusters;
+    q.cons_x = dev_cons_x; q.cons_cnt = dev_cons_cnt; q.status = w.d_status;
+    PF_HIP(h, hipMemsetAsync(w.d_status, 0, 4, s));
+    PF_HIP(h, hipMemsetAsync(dev_support, 0, (size_t)pl.N * 4, s));
+    PF_HIP(h, hipMemsetAsync(dev_cons_x, 0, (size_t)pl.N * 12, s));
+    PF_HIP(h, hipMemsetAsync(dev_cons_cnt, 0, (size_t)pl.N * 4, s));
+    pfk_sset_analyze(&q, (int)pl.work_items, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    PF_HIP(h, hipMemcpyAsync(w.status_host, w.d_status, 4, hipMemcpyDeviceToHost, s));
+    PF_HIP(h, hipStreamSynchronize(s));
+    if (*w.status_host != 0)
+        PF_FAIL(h, PF_ERR_ARG, "pf_sample_set_analyze: %d centers have a type outside [0, %d) (counted on the device; the outputs mean nothing)",
+                (int)*w.status_host, (int)h->cfg.pharm_nf);
     return PF_OK;
 }
 

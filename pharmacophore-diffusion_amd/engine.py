@@ -925,6 +925,41 @@ class PfEngine:
         return score, tm
 
     # -- introspection -------------------------------------------------------------------------
+    def sample_set(self, x, types, set_ptr, center_ptr, sigma=1.0, tolerance=1.5, threshold=0.5, want_similarity=True):
+        """Analyses P sample sets in one call (pf_sample_set_analyze; the definitions: include/pfdyn.h, "sample sets"): the typed
+        Gaussian-overlap Tanimoto between the samples of each set, per-center support, Taylor-Butina clusters and the consensus of
+        each cluster.  x [N, 3] and types [N] (integers in [0, pharm_nf)) are the centers of all samples, sample s owning rows
+        [center_ptr[s], center_ptr[s+1]) and set p the samples [set_ptr[p], set_ptr[p+1]) -- both pointer arrays on the host.
+        Returns a dict of device tensors: similarity [sum S_p^2] (the sets' row-major matrices one after the other; None with
+        want_similarity=False), support [N], label [S], centroid [S], size [S] (cluster c of set p at set_ptr[p] + c, -1 beyond
+        n_clusters), n_clusters [P], cons_x [N, 3], cons_cnt [N].  Needs no weights and no bound batch and touches no run."""
+        sp, cp = _i32_host(torch.as_tensor(set_ptr)), _i32_host(torch.as_tensor(center_ptr))
+        P = int(sp.shape[0]) - 1
+        if P < 1 or sp.ndim != 1 or cp.ndim != 1 or cp.shape[0] < 1:
+            raise ValueError("sample_set: set_ptr [P + 1] and center_ptr [S + 1] with at least one set")
+        S, N = int(cp.shape[0]) - 1, int(cp[-1])
+        if int(sp[-1]) != S:
+            raise ValueError(f"sample_set: set_ptr ends at {int(sp[-1])}, center_ptr describes {S} samples")
+        xd = _f32(torch.as_tensor(x), self.device).reshape(-1, 3)
+        td = torch.as_tensor(types).detach().to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        if N < 0 or xd.shape[0] != N or td.shape[0] != N:
+            raise ValueError(f"sample_set: center_ptr ends at {N}, x has {xd.shape[0]} rows and types {td.shape[0]}")
+        n_sim = sum(int(b - a) ** 2 for a, b in zip(sp[:-1], sp[1:]))
+        i32 = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        sim = torch.empty(n_sim, device=self.device) if want_similarity and 0 < n_sim <= L.PF_SSET_MAX_SIM else None
+        out = {"similarity": sim, "support": i32(N), "label": i32(S), "centroid": i32(S), "size": i32(S), "n_clusters": i32(P),
+               "cons_x": torch.empty(max(N, 1), 3, device=self.device), "cons_cnt": i32(N)}
+        opts = L.PfSsetOpts(float(sigma), float(tolerance), float(threshold))
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_sample_set_analyze(self._h, P, sp.ctypes.data, cp.ctypes.data, _dptr(xd), _dptr(td), ctypes.byref(opts),
+                                                    _dptr(sim), _dptr(out["support"]), _dptr(out["label"]), _dptr(out["centroid"]),
+                                                    _dptr(out["size"]), _dptr(out["n_clusters"]), _dptr(out["cons_x"]),
+                                                    _dptr(out["cons_cnt"]), _stream_ptr()), "pf_sample_set_analyze")
+        for k, n in (("support", N), ("cons_cnt", N), ("label", S), ("centroid", S), ("size", S)):
+            out[k] = out[k][:n]
+        out["cons_x"] = out["cons_x"][:N]
+        return out
+
     def get_edges(self, etype: int):
         with torch.cuda.device(self.device):
             n = self._ck(self.lib.pf_debug_get_edges(self._h, etype, None, None, 0, _stream_ptr()), "pf_debug_get_edges")

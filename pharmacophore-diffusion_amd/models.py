@@ -28,6 +28,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .analysis import PharmacophoreScore, SampleAnalyzer, SampledPharmacophore, pair_restraint_energy
+from .analysis import SampleSet, _sset_options, _sset_samples, analyze_sample_set
+from ._lib import PF_SSET_MAX_SIM as SSET_MAX_SIM      # floats of all similarity matrices of one pf_sample_set_analyze call
 from .engine import PfEngine
 from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_graph, get_batch_idxs, unbatch
 from .schedule import score_levels as _score_levels, score_weights as _score_weights
@@ -833,6 +835,58 @@ class FlatAdam:
         # next engine() upload the flat vector once more, which is correct either way.)
 
 
+
+def sample_sets(per_pocket_samples, engine: Optional[PfEngine] = None, sigma: float = 1.0, tolerance: float = 1.5,
+                threshold: float = 0.5, min_support: float = 0.5) -> List[Optional[SampleSet]]:
+    """One SampleSet per pocket (None for a pocket without samples) from per-pocket lists of SampledPharmacophore objects or
+    (x [n, 3], type indices [n]) pairs, each pocket's samples in that pocket's frame.  With an ``engine`` the sets are analysed
+    on its device (PfEngine.sample_set, pf_sample_set_analyze): many pockets per call, a new call whenever the similarity
+    matrices of the next pocket would take the call over its cap of 2^26 floats.  Without one: analysis.analyze_sample_set on
+    the host, same definitions."""
+    sigma, tolerance, threshold = _sset_options(sigma, tolerance, threshold)
+    opts = dict(sigma=sigma, tolerance=tolerance, threshold=threshold, min_support=float(min_support))
+    pockets = [_sset_samples(ps) if len(ps) else None for ps in per_pocket_samples]
+    out: List[Optional[SampleSet]] = [None] * len(pockets)
+    if engine is None:
+        for r, ps in enumerate(pockets):
+            if ps is not None:
+                out[r] = analyze_sample_set(ps, **opts)
+        return out
+    chunk, floats = [], 0
+
+    def flush():
+        if not chunk:
+            return
+        samples = [s for r in chunk for s in pockets[r]]
+        set_ptr = np.concatenate([[0], np.cumsum([len(pockets[r]) for r in chunk])]).astype(np.int32)
+        center_ptr = np.concatenate([[0], np.cumsum([s[0].shape[0] for s in samples])]).astype(np.int32)
+        res = engine.sample_set(torch.cat([s[0] for s in samples]), torch.cat([s[1] for s in samples]), set_ptr, center_ptr,
+                                sigma=sigma, tolerance=tolerance, threshold=threshold)
+        res = {k: v.cpu() for k, v in res.items()}
+        at = 0
+        for p, r in enumerate(chunk):
+            s0, s1 = int(set_ptr[p]), int(set_ptr[p + 1])
+            S, k = s1 - s0, int(res["n_clusters"][p])
+            rows = lambda a: slice(int(center_ptr[s0 + a]), int(center_ptr[s0 + a + 1]))
+            centroids = res["centroid"][s0:s0 + k].tolist()
+            cons = [(res["cons_x"][rows(m)], pockets[r][m][1], res["cons_cnt"][rows(m)]) for m in centroids]
+            out[r] = SampleSet(res["similarity"][at:at + S * S].reshape(S, S), [res["support"][rows(a)] for a in range(S)],
+                               res["label"][s0:s1], centroids, cons, None, opts)
+            at += S * S
+        chunk.clear()
+
+    for r, ps in enumerate(pockets):
+        if ps is None:
+            continue
+        if floats + len(ps) ** 2 > SSET_MAX_SIM:
+            flush()
+            floats = 0
+        chunk.append(r)
+        floats += len(ps) ** 2
+    flush()
+    return out
+
+
 class PharmSizeDistribution:
     """pharmacoforge/models/n_nodes_dist.py:7-14 (sample_uniformly only; sample_variety is broken upstream)."""
 
@@ -1555,7 +1609,7 @@ class PharmacophoreDiff(_Base):
                score_levels: int = None, sample_steps: int = None, sampler: str = None, eta: float = None,
                spacing: str = None, guide_family: str = "wide", pocket_field=None, type_restraints=None,
                type_guidance=None, pair_restraints=None, min_separation: float = None,
-               separation_weight: float = 1.0) -> List[List[SampledPharmacophore]]:
+               separation_weight: float = 1.0, consensus=None) -> List[List[SampledPharmacophore]]:
         """pharmacodiff.py:516-578: one pocket copy per requested pharmacophore, flattened in pocket order and cut into
         batches of ``max_batch_size`` in list order.
 
@@ -1643,7 +1697,11 @@ class PharmacophoreDiff(_Base):
 
         ``score_levels`` K: every returned SampledPharmacophore carries ``.score``, the PharmacophoreScore of its final frame at K
         stratified levels (score(), uniform weighting, seed 0) -- a second pass behind the sampling, which it leaves bit for bit
-        as it is without.  None (the default): no scoring, ``.score`` stays None."""
+        as it is without.  None (the default): no scoring, ``.score`` stays None.
+
+        ``consensus``: True, or a dict of consensus()'s keywords -- the call returns (samples, sets), sets being consensus() of the
+        samples this rank returns, one SampleSet per pocket (None for a pocket of which it holds none); the sampling is bit for
+        bit what it is without.  None / False (the default): the samples alone, as before."""
         type_restraints = self._type_restraints(type_restraints, len(ref_graphs), "pockets")
         pair_restraints = self._pair_restraints(pair_restraints, len(ref_graphs), "pockets", n_pharms, int(min_separation is not None))
         spec = self._run_spec(pins=pinned is not None and any(p is not None for p in pinned),
@@ -1665,7 +1723,7 @@ class PharmacophoreDiff(_Base):
         ref_graphs = [as_pocket_graph(g) for g in ref_graphs]
         n_receptors = len(ref_graphs)
         if n_receptors == 0:
-            return []
+            return ([], []) if consensus else []
         if restraints is not None:
             if len(restraints) != n_receptors:
                 raise ValueError(f"restraints lists {len(restraints)} entries for {n_receptors} pockets")
@@ -1780,7 +1838,24 @@ class PharmacophoreDiff(_Base):
             for ps, sc in zip(per_pocket, scores):
                 for p, v in zip(ps, sc):
                     p.score = v
+        if consensus:
+            return per_pocket, self.consensus(per_pocket, **(consensus if isinstance(consensus, dict) else {}))
         return per_pocket
+
+    # -- what the samples of a pocket agree on (pf_sample_set_analyze) ------------------------------
+    def consensus(self, per_pocket_samples, sigma: float = 1.0, tolerance: float = 1.5, threshold: float = 0.5,
+                  min_support: float = 0.5, device=None) -> List[Optional[SampleSet]]:
+        """One SampleSet per pocket from what sample() returns (per pocket a list of SampledPharmacophore) or from per-pocket lists
+        of (x [n, 3], type indices [n]) pairs: the typed Gaussian-overlap Tanimoto (``sigma``) between the samples of a pocket,
+        the support of every center (the number of other samples with a center of its type within ``tolerance``), Taylor-Butina
+        clusters at ``threshold`` and the consensus pharmacophore of each cluster, whose centers print when their support is at
+        least ``min_support``.  Samples of one pocket share its frame and nothing is aligned: sets of different
+        pockets do not compare.  A set has at most 1024 samples of at most 64 centers (ValueError).  Runs on the device when the
+        model is on one (many pockets per call, chunked under the call's cap), else on the host through analysis.py;
+        ``device``: 'cpu' forces the host path.  A pocket without samples gives None."""
+        dev = torch.device(device) if device is not None else self.device
+        eng = self.dynamics.engine() if torch.device(dev).type == "cuda" else None
+        return sample_sets(per_pocket_samples, eng, sigma, tolerance, threshold, min_support)
 
     # -- scoring given pharmacophores (pf_score) ---------------------------------------------------
     def score(self, ref_graphs: List[PocketGraph], pharmacophores, levels=None, weighting: str = 'uniform', noise=None, seed: int = 0,

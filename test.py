@@ -56,6 +56,7 @@ _FLAGS = [
     ('--comp_unmatched', dict(type=float, default=None, metavar='U', help='with --guide_complementarity_types: what a type without any partner in the pocket costs, as a distance beyond its matching distance (default 0)')),
     ('--pockets_per_call', dict(type=int, default=64, help='pockets whose samples are batched together (not in the reference)')),
     ('--use_ema', dict(action='store_true', help="sample from the checkpoint's EMA weights ('ema_state_dict') instead of the training weights")),
+    ('--consensus', dict(action='store_true', help='analyse the samples of every pocket as a set (similarity, clusters, consensus; default options): writes consensus.xyz and clusters.tsv per pocket and adds clusters_per_pocket and mean_support to the summary over all ranks')),
 ]
 
 
@@ -68,6 +69,8 @@ def parse_arguments(argv=None):
         raise ValueError('no model given: pass --ckpt or --model_dir')
     if a.pharm_sizes and len(a.pharm_sizes) != a.samples_per_pocket:
         raise ValueError(f'--pharm_sizes lists {len(a.pharm_sizes)} sizes for --samples_per_pocket {a.samples_per_pocket}')
+    if a.consensus and a.samples_per_pocket > 1024:
+        raise ValueError(f'--consensus: --samples_per_pocket {a.samples_per_pocket} (a set has at most 1024 samples)')
     if a.sample_steps is None and (a.sampler is not None or a.eta is not None or a.spacing is not None):
         raise ValueError('--sampler, --eta and --spacing need --sample_steps')
     if a.sample_steps is not None and a.sample_steps < 1:
@@ -212,6 +215,7 @@ def main(argv=None):
     epp = dataset.pp_edge_counts()
     mine = [pockets[j] for j in shard_by_work([float(epp[i] + 1) * args.samples_per_pocket for i in pockets], world)[rank]]
     all_pharms = []
+    set_counts = torch.zeros(4, dtype=torch.float64)       # --consensus: pockets, clusters, samples, sum of the samples' mean support
     for c0 in range(0, len(mine), args.pockets_per_call):
         chunk = mine[c0:c0 + args.pockets_per_call]
         t0 = time.time()
@@ -228,11 +232,20 @@ def main(argv=None):
                                       type_restraints=[args.type_restraint_list] * len(graphs) if args.type_restraint_list else None,
                                       type_guidance=None if args.type_guidance is None else pfa.TypeGuidance(**args.type_guidance),
                                       pair_restraints=[args.pair_restraint_list] * len(graphs) if args.pair_restraint_list else None,
-                                      min_separation=args.min_separation, separation_weight=args.separation_weight)
+                                      min_separation=args.min_separation, separation_weight=args.separation_weight,
+                                      consensus=args.consensus)
+        sets = None
+        if args.consensus:
+            per_pocket, sets = per_pocket
         seconds = (time.time() - t0) / len(chunk)
         for idx, pharms in zip(chunk, per_pocket):
             write_pocket(out_root, dataset, idx, pharms, seconds, args.visualize_trajectory)
             all_pharms += pharms
+            if sets is not None and sets[chunk.index(idx)] is not None:
+                sset = sets[chunk.index(idx)]
+                (out_root / f'pocket_{idx}' / 'consensus.xyz').write_text(sset.consensus_xyz())
+                (out_root / f'pocket_{idx}' / 'clusters.tsv').write_text(sset.clusters_tsv())
+                set_counts += torch.tensor([1.0, len(sset.clusters), sset.n_samples, sum(sset.mean_support())], dtype=torch.float64)
             if args.avoid_clashes is not None and rank == 0:       # the final clash energy and clashing pairs of every sample
                 from pharmacoforge_amd.analysis import clash_energy
                 cl = [clash_energy(ph.ph_coords, ph.g.prot_x, args.avoid_clashes, args.pocket_field['clash_weight']) for ph in pharms]
@@ -259,6 +272,15 @@ def main(argv=None):
             with open(out_root / 'metrics.pkl', 'wb') as f:
                 pickle.dump(metrics, f)
             (out_root / f'pharm_counts_{args.dataset_idx}.txt').write_text(str(freqs.tolist()))
+    if args.consensus:
+        if group is not None:
+            from pharmacoforge_amd.analysis import _allreduce_sum
+            set_counts = _allreduce_sum(set_counts, group, device)
+        summary = {'clusters_per_pocket': float(set_counts[1] / set_counts[0]) if set_counts[0] > 0 else 0.0,
+                   'mean_support': float(set_counts[3] / set_counts[2]) if set_counts[2] > 0 else 0.0}
+        if rank == 0:
+            print(summary)
+            (out_root / 'consensus_summary.txt').write_text('\n'.join(f'{k}: {v:.3f}' for k, v in summary.items()))
     if world > 1:
         torch.distributed.destroy_process_group()
 
