@@ -820,6 +820,10 @@ int pf_debug_pa_check(pf_handle* h, int64_t* violations /*[3]*/, pf_stream strea
 /* the exchange time-outs of k_rg_node_hs_build counted on this handle since it was created (cumulative; pf_sample_status is the
  * product-path check and reports new ones per run).  Synchronises the device. */
 int pf_debug_xchg_timeouts(pf_handle* h, int32_t* n);
+/* what this process holds through the library's handles right now: live allocations and their bytes, device and pinned memory
+ * together (every handle; no handle needed).  Unlike hipMemGetInfo it counts nothing of other processes on the device, so a caller
+ * can check that pf_destroy gave everything back: both numbers return to what they were before pf_create. */
+int pf_debug_live_memory(int64_t* n_allocations, int64_t* n_bytes);
 /* diagnostic: drop_word != 0 makes the producers of the merged launch skip one exchange word (word 0 of center 0), so that its
  * consumer times out; poll_max > 0 shortens the poll bound (default 65,536 rounds) so that a forced time-out costs microseconds.
  * (0, 0) restores the product behaviour.  tests/test_gpu_n16.py: the time-out must surface on the same run. */

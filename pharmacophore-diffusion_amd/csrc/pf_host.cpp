@@ -27,6 +27,7 @@
 #include "pf_types.h"
 #include "pf_pairs.h"
 #include "pf_sset.h"
+#include "pf_mem.h"
 
 using namespace pfpack;
 
@@ -243,26 +244,52 @@ struct LaunchPolicy {
 // which sampling run is in progress on a handle (run_guard: what each entry point accepts)
 enum RunKind { RUN_NONE = 0, RUN_PLAIN, RUN_PINNED, RUN_GUIDED };
 
-// A block of host arrays that a guided begin uploads in one copy (the restraints, the pocket field, type guidance): packed into pinned
-// memory in the device layout, then copied into one device allocation, kept and grown like d_pin.  ev: the last upload out of `stage`
-struct StagedBlock { void* stage = nullptr; size_t stage_capacity = 0; hipEvent_t ev = nullptr; void* dev = nullptr; size_t capacity = 0; };
+// What owns the handle's memory, events and streams (pf_mem.h).  StagedBlock: a block of host arrays that a guided begin uploads in
+// one copy (the restraints, the pocket field, type guidance) -- its device buffer is kept and grown like d_pin
+using pfmem::DevArr; using pfmem::DevBuf; using pfmem::Event; using pfmem::PinnedArr; using pfmem::PinnedBuf; using pfmem::StagedBlock;
+using pfmem::Stream; using pfmem::Wait;
 
 struct pf_handle {
+    // ---- optional per-kernel timing with HIP events on the caller's stream (pf_profile_*)
+    // classes 0..8: pf_profile_read (inference path); 9..12: pf_profile_read_train (gradient kernels)
+    enum { K_ENCODE = 0, K_BUILD, K_EDGE, K_NODE, K_HEAD, K_STEP, K_EDGE_COOP, K_NODE_COOP, K_EDGE_LAST,
+           K_BWD_HEAD, K_BWD_NODE, K_BWD_EDGE_LEVEL, K_BWD_REST, K_NUM };
+    // ---- streams, events and the two alternating pairs.  Members are destroyed in reverse order of declaration, and these are
+    // declared first: every buffer further down goes before them, then the pairs (buffer, then events), the events, the streams
+    Stream s_copy;                          // the table section's upload (below)
+    Stream s_side;                          // side stream of the backward pass (work lists, early gradient sums, encoders): NOT the copy
+                                            // stream -- the next bind's upload must not queue behind the end of this backward
+    std::vector<std::pair<Event, Event>> prof_ev[K_NUM];
+    Event cmp_ev[3];                        // the backward pass's side stream against the caller's (bwd_side_lists, bwd_early_reduce)
+    Event l0flag_ev;                        // the read-back into l0flag_host
+    // pf_set_pocket_batch stages every host-built table in pinned memory, in the layout of the workspace's table section,
+    // and uploads it with ONE asynchronous copy (two staging buffers alternate; a buffer is reused only after the copy that
+    // read it has completed: ev)
+    struct StageSlot { Event ev; PinnedBuf buf; } stage[2];
+    int stage_next = 0;
+    // The table section lives in two device buffers of its own that alternate between binds, and its upload runs on a
+    // copy stream: a training loop binds a new batch every step, and on the caller's stream the ~8 MB copy would sit
+    // between two steps (0.14 ms of a 2 ms step) instead of under the previous step's kernels.  guard: everything
+    // that read the buffer has finished (recorded on the caller's stream at the start of the bind after the one that
+    // used it; forgotten when the buffer is replaced); up: the upload into it is complete (the caller's stream waits for it).
+    struct TabSlot { Event guard, up; DevBuf buf; } tab[2];
+    int tab_next = 0;
+
     LaunchPolicy pol;
     pf_config cfg{};
     // width-generic family (pf_wide.hip): every inference call of a handle whose widths are not (128, 16) runs on it, and so does
     // a (128, 16) handle created under PFDYN_WIDE=1.  spec: the widths of the specialised kernels -- their weights are packed and
     // training is available; wide: inference goes to run_dynamics_wide
     bool spec = true, wide = false;
-    WideGvp* d_wgvp = nullptr;              // device table of the width-generic GVPs (same indexing as d_gvp)
+    DevArr<WideGvp> d_wgvp;                 // device table of the width-generic GVPs (same indexing as d_gvp)
     std::string err;
     std::map<std::string, RawTensor> raw;
     bool committed = false;
 
     // ---- packed weights (one device allocation)
-    float* d_w = nullptr;
+    DevArr<float> d_w;
     PackLayout pk;                          // where everything sits in d_w (pf_pack.h): offsets and strides in floats
-    GvpW* d_gvp = nullptr;                  // table of all GvpW
+    DevArr<GvpW> d_gvp;                     // table of all GvpW
     std::vector<GvpW> h_gvp;
     // indices into the GvpW table
     int msg_base(int layer, int et) const { return ((layer * 4 + et) * cfg.n_message_gvps); }
@@ -288,33 +315,10 @@ struct pf_handle {
     EdgeTile* d_edge_tiles_act = nullptr;
     NodeTile* d_node_tiles_act = nullptr;
     int *d_act_ids = nullptr, *d_reg_act = nullptr;   // last conv layer: only what feeds the pharm nodes
-    void* d_ws = nullptr;                   // one allocation, carved below
-    size_t ws_capacity = 0;                 // bytes behind d_ws: kept across pocket batches while it is large enough
-    // pf_set_pocket_batch stages every host-built table in pinned memory, in the layout of the workspace's table section,
-    // and uploads it with ONE asynchronous copy on the caller's stream (two staging buffers alternate; a buffer is reused
-    // only after the copy that read it has completed)
-    void* stage[2] = {nullptr, nullptr};
-    size_t stage_cap[2] = {0, 0};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    int stage_next = 0;
-    // The table section lives in two device buffers of its own that alternate between binds, and its upload runs on a
-    // copy stream: a training loop binds a new batch every step, and on the caller's stream the ~8 MB copy would sit
-    // between two steps (0.14 ms of a 2 ms step) instead of under the previous step's kernels.  tab_guard[w]: everything
-    // that read buffer w has finished (recorded on the caller's stream at the start of the bind after the one that
-    // used w); tab_up[w]: the upload into w is complete (the caller's stream waits for it).
-    void* d_tab[2] = {nullptr, nullptr};
-    size_t tab_cap[2] = {0, 0};
-    hipEvent_t tab_guard[2] = {nullptr, nullptr}, tab_up[2] = {nullptr, nullptr};
-    bool tab_guard_set[2] = {false, false};
-    int tab_next = 0;
-    hipStream_t s_copy = nullptr;
-    hipStream_t s_side = nullptr;           // side stream of the backward pass (work lists, early gradient sums, encoders): NOT the copy
-                                            // stream -- the next bind's upload must not queue behind the end of this backward
+    DevBuf d_ws;                            // one allocation, carved below; kept across pocket batches while it is large enough
     // one-hot check of the protein features (static hoist): 0 unknown (device flag pending), 1 one-hot, 2 not
     int l0_state = 0;
-    int* l0flag_host = nullptr;             // pinned; written by an async copy of d_l0flag
-    hipEvent_t l0flag_ev = nullptr;
-    size_t tws_capacity = 0;                // bytes behind d_tws (kept across batches like d_ws)
+    PinnedArr<int> l0flag_host;             // written by an async copy of d_l0flag
     int *d_prot_ptr = nullptr, *d_pharm_ptr = nullptr, *d_gid = nullptr, *d_reg = nullptr, *d_dyn_cnt = nullptr,
         *d_esrc = nullptr, *d_edst = nullptr, *d_in_start = nullptr, *d_in_cnt = nullptr, *d_pp_cnt = nullptr;
     EdgeTile* d_edge_tiles = nullptr;
@@ -346,8 +350,8 @@ struct pf_handle {
     bool t_head_saved = false;              // ... by the last pf_train_forward
     unsigned int* d_xchg = nullptr;         // exchange words of the merged launch [Nf centers][PF_XCHG_STRIDE]: part of the workspace (carved per
                                             // bind), set to PF_XCHG_EMPTY by every pf_sample_begin on the caller's stream, re-armed word by word by the consumers
-    int* d_xstat = nullptr;                 // [1] time-outs of the exchange since the handle was created (cumulative, never cleared: no race with a run in flight)
-    int* xstat_host = nullptr;              // pinned; an async copy of d_xstat follows every sampling run (pf_sample_end)
+    DevArr<int> d_xstat;                    // [1] time-outs of the exchange since the handle was created (cumulative, never cleared: no race with a run in flight)
+    PinnedArr<int> xstat_host;              // an async copy of d_xstat follows every sampling run (pf_sample_end)
     int xstat_ack = 0;                      // the count already reported (pf_sample_status / pf_sample_begin / pf_debug_xchg_timeouts)
     int xchg_fault = 0, xchg_poll_max = 0;  // diagnostics (pf_debug_xchg_fault)
     // center hoist (CenHoistParams; pf_cenhoist.h; its streams and L0C block: pk.n16_l0h, pk.l0c_off): the per-batch
@@ -381,7 +385,7 @@ struct pf_handle {
     bool pa_check = false;
     int pa_serial = 0, spec_serial = 0;
     int* d_pa_gstamp = nullptr;             // [Ecap / 16 + 1] in the workspace (PFDYN_PA_CHECK only)
-    unsigned long long* d_pa_chk = nullptr; // [3] violations, kept groups checked, kept groups behind a changed prefix (per handle, cumulative)
+    DevArr<unsigned long long> d_pa_chk;    // [3] violations, kept groups checked, kept groups behind a changed prefix (per handle, cumulative)
     bool no_fixed_shapes = false;           // PFDYN_NO_FIXED_SHAPES: k_bwd_edge_level reads every level's GVP shape from the table (the A/B of its FX forms)
     ScaleArgs pend_scale{}; bool has_pend_scale = false;    // loss_backward -> pf_train_backward: the unit gradients' scaling, not yet launched
     bool vjp_full_kernels = false;          // PFDYN_VJP_FULL_KERNELS: the inputs-only backward launches the full pass's kernel forms (the A/B of the
@@ -396,27 +400,27 @@ struct pf_handle {
     RunKind run = RUN_NONE;                 // set by the three pf_sample_begin* calls, reset by a bind
     // pinned centers (pf_sample_begin_pinned): the run in progress replaces the flagged centers every step; the handle's own copy of
     // the caller's arrays (one allocation, kept and reused: flags [Nf], positions [Nf][3], feature rows [Nf][pharm_nf])
-    void* d_pin = nullptr; size_t pin_capacity = 0;
+    DevBuf d_pin;
     int* d_pin_flags = nullptr; float *d_pin_x = nullptr, *d_pin_h = nullptr;
     float pin_feat_norm = 1.f;
     // seeded begin (pf_sample_seed_next): the handle's own copy of the caller's seed (one allocation, kept and grown like d_pin:
     // positions [Nf][3], feature rows [Nf][pharm_nf]) and its level's coefficients.  seed_armed: the next begin starts from it;
     // taken off the handle on that begin's entry, dropped by a bind
-    void* d_seed = nullptr; size_t seed_capacity = 0;
+    DevBuf d_seed;
     float *d_seed_x = nullptr, *d_seed_h = nullptr;
     float seed_alpha = 1.f, seed_sigma = 0.f, seed_feat_norm = 1.f;
     bool seed_armed = false;
     // multistep move (pf_denoise_step_ms): the previous step's outputs [Nf][3 + pharm_nf], written by the move itself (one
     // allocation, kept and grown like d_pin).  ms_hist_valid: the last move of the run in progress was a multistep move, so the
     // buffer holds that step's outputs; cleared by every begin, every bind and every other move
-    void* d_ms_hist = nullptr; size_t ms_hist_capacity = 0;
+    DevBuf d_ms_hist;
     bool ms_hist_valid = false;
     // guided run (pf_sample_begin_guided): a pinned run plus restraint energies per graph.  restr: the restraint block (pf_restr.h),
     // packed at begin.  d_guide: what a guided step leaves (pf_restr.h: GuideWork), kept and grown like d_pin
     StagedBlock restr;
     int n_restr = 0;
     float guide_scale = 0.f, guide_clip = 0.f;
-    void* d_guide = nullptr; size_t guide_capacity = 0;
+    DevBuf d_guide;
     bool guide_wide = true, guide_in_grads = false;   // the training family and the input-gradient switch the guided run began on
     bool guide_have = false;                // a guided step has run on this batch: pf_debug_last_guidance has something to return
     float* guide_traj_energy = nullptr;     // pf_sample_guided: row i of the caller's [n_steps][B] for the step in flight
@@ -434,7 +438,7 @@ struct pf_handle {
     // (pf_debug_last_type_guidance); live: that step's launches wrote g0_h / E_type (else they are zeros)
     struct TypesSource {
         StagedBlock blk;
-        void* d_tguide = nullptr; size_t tguide_capacity = 0;
+        DevBuf d_tguide;
         bool armed = false, on = false, have = false, live = false;
         struct Scalars { int n = 0; float feat_scale = 0.f, feat_clip = 0.f, type_sharpness = 0.f; bool comp = false; float unmatched = 0.f; } arm, run;
     } types;
@@ -443,16 +447,16 @@ struct pf_handle {
     // progress carries n_run > 0 pair restraints; have: the last guided step on this batch launched k_guide_pairs (pf_debug_last_pairs)
     struct PairsSource {
         StagedBlock blk;
-        void* d_pguide = nullptr; size_t pguide_capacity = 0;
+        DevBuf d_pguide;
         bool armed = false, on = false, have = false;
         int n_arm = 0, n_run = 0;
     } pairs;
     // sample-set analysis (pf_sample_set_analyze): no run state -- the packed pointer block (pf_sset.h), the similarity matrices of a
-    // call that passes no buffer for them, the status word and its pinned host copy.  Grown on demand, freed in pf_destroy
+    // call that passes no buffer for them, the status word and its pinned host copy.  Grown on demand, kept
     struct SsetWork {
         StagedBlock blk;
-        void* d_sim = nullptr; size_t sim_capacity = 0;
-        int32_t* d_status = nullptr; int32_t* status_host = nullptr;
+        DevBuf d_sim;
+        DevArr<int32_t> d_status; PinnedArr<int32_t> status_host;
     } sset;
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
@@ -464,7 +468,7 @@ struct pf_handle {
     bool n16_stale = false;
     // -DN16_SPLIT builds: the main quads of the n16 streams hold bf16 planes, two weights per 32-bit word -- not a gather (PackedModel::
     // split_tab); n16_refresh re-derives those words from the flat vector behind the gather (k_n16_split_words)
-    int4* d_split_tab = nullptr; size_t n_split_tab = 0;
+    DevArr<int4> d_split_tab; size_t n_split_tab = 0;
     bool tail_done = false;                 // the last run_dynamics call of a denoising step also did the step's update + build
     int last_tail = 0;                      // pf_debug_kernel_family(layer = n_convs): 0 / 4 (k_rg_tail) / 16 (k_n16_tail)
     float *d_msg_s2 = nullptr, *d_msg_v2 = nullptr;   // the last conv layer's message rows when conv layer 0's are still being read (fused launch)
@@ -477,8 +481,8 @@ struct pf_handle {
     bool l0_onehot = false;                 // every protein feature row of the batch is an element one-hot
     bool coords_custom = false;             // protein coordinates came from the caller of this call (not the batch's own)
     bool zs_batch_coords = false;           // d_zs was computed from (a rigid translate of) the batch's coordinates
-    float* d_l0c = nullptr;                 // [32]
-    float* d_ptab = nullptr;                // [L0_PTAB_SLOTS][L0_NTAB][rec_nf][128] tables of the timesteps seen (scalar-t calls)
+    DevArr<float> d_l0c;                    // [32]
+    DevArr<float> d_ptab;                   // [L0_PTAB_SLOTS][L0_NTAB][rec_nf][128] tables of the timesteps seen (scalar-t calls)
     std::unordered_map<uint32_t, int> ptab_slot;
     int *d_eorig = nullptr, *d_ptype = nullptr, *d_l0flag = nullptr;
     // edge records of the ff / pf slots (BuildParams::rec / FusedParams::rec): written by the merged launch's update + build for the next
@@ -514,13 +518,13 @@ struct pf_handle {
     }
 
     // ---- gradient path (pf_train_*): flat parameter vector in state-dict order, GvpT tables, per-layer activations
-    float* d_flat = nullptr;
+    DevArr<float> d_flat;
     size_t nparams = 0;
     FlatLayout flat_layout;                 // name -> (offset, numel), state-dict order
-    GvpT* d_gvpt = nullptr;                 // same indexing as the GvpW table
-    int* d_map = nullptr;                   // packed element -> flat parameter index (-1: zero): PackedModel::map
+    DevArr<GvpT> d_gvpt;                    // same indexing as the GvpW table
+    DevArr<int> d_map;                      // packed element -> flat parameter index (-1: zero): PackedModel::map
     size_t n_packed = 0;
-    void* d_tws = nullptr;                  // training workspace of the current batch (allocated on first use)
+    DevBuf d_tws;                           // training workspace of the current batch (allocated on first use, kept across batches like d_ws)
     std::vector<float*> t_H, t_V, t_msg_s, t_msg_v;
     std::vector<float*> t_sv_z, t_sv_g, t_sv_v;     // per layer: [n_message_gvps][Ecap] rows saved by the forward
     float *t_gs_buf = nullptr, *t_gv_buf = nullptr;
@@ -530,14 +534,13 @@ struct pf_handle {
           *t_gpart = nullptr, *t_geps_h = nullptr, *t_geps_x = nullptr;
     long long *t_A_h = nullptr, *t_A_v = nullptr;      // fixed-point accumulators of the level-0 scatter (kept clear between uses)
     float* d_lpart = nullptr;               // k_loss_eval's arrival counter (first 64 bytes) + partial sums: in the workspace's zero section
-    void* d_tA = nullptr;                   // their own allocation: it outlives the batches, so "kept clear" holds across them
-    size_t tA_capacity = 0;                 // bytes
+    DevBuf d_tA;                            // their own allocation: it outlives the batches, so "kept clear" holds across them
     bool tA_dirty = false;                  // a backward pass stopped between the scatter and pfk_fix_apply
     int enc_begin = 0, enc_n = 0;           // flat range of the encoders' parameters (contiguous: the first tensors of the state dict)
     float* t_gpart_enc = nullptr;
-    TensorSeg* d_tseg = nullptr; int n_tseg = 0;   // class of every parameter tensor (pf_train.h: which gradient copies hold it)
+    DevArr<TensorSeg> d_tseg; int n_tseg = 0;   // class of every parameter tensor (pf_train.h: which gradient copies hold it)
     int n_gvpt = 0;                         // entries of d_gvpt (message, update, head GVPs)
-    float* d_wpack = nullptr;               // k_pack_gvp tables of every GVP (input-gradient fragments, then forward fragments); valid for w_version == wpack_version
+    DevArr<float> d_wpack;                  // k_pack_gvp tables of every GVP (input-gradient fragments, then forward fragments); valid for w_version == wpack_version
     uint64_t wpack_version = ~0ull;
     float *t_lx0c = nullptr, *t_lag = nullptr, *t_lsg = nullptr, *t_lcom2 = nullptr, *t_lgx = nullptr, *t_lgh = nullptr, *t_lout = nullptr;   // pf_train_loss_forward
     bool t_have_loss = false;
@@ -545,7 +548,6 @@ struct pf_handle {
     int* t_ulist = nullptr;                 // dense per-type row list of the layer being differentiated (k_compact_node_rows; counts: t_ccnt[97], [98])
     int t_ucap = 0;
     size_t t_clist_cap = 0, t_ulist_cap = 0;   // ints per conv layer in t_clist / t_ulist (one list per layer: they are built ahead, on the side stream)
-    hipEvent_t cmp_ev[3] = {nullptr, nullptr, nullptr};
     int *t_clist = nullptr, *t_ccnt = nullptr;   // dense list of the valid edge slots of the layer being differentiated (k_compact_rows), counts
     float* t_fix = nullptr;                 // [2] scale / inverse scale of the current backward call
     int t_nblk = 0;
@@ -557,17 +559,17 @@ struct pf_handle {
     bool train_wide = false;
     // pf_train_set_input_grads: the tuned family's fp32 backward also gives dL/d(center coordinates, feature rows).  The switch owns
     // d_gdiff, the per-edge dL/d(x_src - x_dst) rows [n_convs][max(Ecap, 1)][3] of a pass's level-0 launches: cleared per pass, kept
-    // and grown like a run's scratch (grow_run_scratch), released when the switch goes off
+    // and grown like a run's scratch (reserve behind Wait::on(the caller's stream)), released when the switch goes off
     bool train_in_grads = false;
-    void* d_gdiff = nullptr; size_t gdiff_capacity = 0;
+    DevBuf d_gdiff;
     // pf_adam_step_guarded / pf_debug_optim_step: one fp64 partial per chunk of the gradient (grown on demand, kept)
-    double* d_optim_part = nullptr; size_t optim_part_cap = 0;
+    DevArr<double> d_optim_part;
     // a handle of the specialised widths carries no width-generic packing (inference stays on the tuned kernels): its wide training
     // leg builds the WideGvp table on first use (ensure_wide_pack) -- Wh, Wu and the biases read from d_flat as stored, to_feats_out
     // and the gate Linear packed on the device into d_wpk whenever w_version moved
-    float* d_wpk = nullptr; WidePackJob* d_wpk_jobs = nullptr; int n_wpk_jobs = 0; uint64_t wpk_version = ~0ull;
-    void* d_wtws = nullptr; size_t wtws_capacity = 0; bool wt_ready = false;
-    void* d_wtA = nullptr; size_t wtA_capacity = 0;      // the fixed-point accumulators [N][S], [N][V][3] (int64), zero between passes
+    DevArr<float> d_wpk; DevArr<WidePackJob> d_wpk_jobs; int n_wpk_jobs = 0; uint64_t wpk_version = ~0ull;
+    DevBuf d_wtws; bool wt_ready = false;
+    DevBuf d_wtA;                           // the fixed-point accumulators [N][S], [N][V][3] (int64), zero between passes
     struct WtWs {
         float *esv_s, *esv_v;               // per conv layer [n_message_gvps][Ecap] level inputs of the message chains
         float *x1_s, *x1_v, *x2_s, *x2_v;   // per conv layer [N] rows in front of the two GVPLayerNorms
@@ -589,13 +591,7 @@ struct pf_handle {
     // offsets into the flat vector that every training call reads, resolved by name once per commit (pf_pack.h: param_offsets) --
     // the training step is host-bound with a new batch every step, and looking ~26 names up per backward pass was 50-100 us of it
     ParamOffsets po;
-
-    // ---- optional per-kernel timing with HIP events on the caller's stream (pf_profile_*)
-    // classes 0..8: pf_profile_read (inference path); 9..12: pf_profile_read_train (gradient kernels)
-    enum { K_ENCODE = 0, K_BUILD, K_EDGE, K_NODE, K_HEAD, K_STEP, K_EDGE_COOP, K_NODE_COOP, K_EDGE_LAST,
-           K_BWD_HEAD, K_BWD_NODE, K_BWD_EDGE_LEVEL, K_BWD_REST, K_NUM };
-    unsigned prof_mask = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[K_NUM];
+    unsigned prof_mask = 0;                 // pf_profile_*: which classes are timed, and how many of prof_ev's pairs this window used
     size_t prof_used[K_NUM] = {};
 };
 
@@ -615,23 +611,20 @@ namespace {
         if (_e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
     } while (0)
 
-// Replaces the device buffer behind *slot with a copy of v (an empty v leaves the slot null).
+// Replaces the device buffer with a copy of v (an empty v leaves it empty).
 template <typename T>
-static hipError_t upload(T** slot, const std::vector<T>& v) {
-    if (*slot) { (void)hipFree(*slot); *slot = nullptr; }
+static hipError_t upload(DevArr<T>& buf, const std::vector<T>& v) {
+    buf.release();
     if (v.empty()) return hipSuccess;
-    const hipError_t e = hipMalloc((void**)slot, v.size() * sizeof(T));
-    return e != hipSuccess ? e : hipMemcpy(*slot, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    const hipError_t e = buf.reserve(v.size() * sizeof(T), v.size() * sizeof(T), Wait::none());
+    return e != hipSuccess ? e : hipMemcpy(buf, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 // keep_ws: the inference workspace stays allocated (pf_set_pocket_batch re-carves it when the next batch fits: a
-// hipMalloc / hipFree pair of a few hundred MB per batch costs milliseconds)
+// free / allocate pair of a few hundred MB per batch costs milliseconds)
 static void free_ws(pf_handle* h, bool keep_ws = false) {
-    if (h->d_ws && !keep_ws) { (void)hipFree(h->d_ws); h->d_ws = nullptr; h->ws_capacity = 0; h->d_xchg = nullptr; h->d_lpart = nullptr; h->d_xchg2 = nullptr; h->d_cen_h = h->d_cen_p = nullptr; h->d_snap[0] = h->d_snap[1] = nullptr; h->d_pa_stamp = h->d_pa_same = nullptr; h->d_pa_cnt = h->d_pa_gstamp = nullptr; }
-    if (h->d_tws && !keep_ws) { (void)hipFree(h->d_tws); h->d_tws = nullptr; h->tws_capacity = 0; }
-    if (h->d_tA && !keep_ws) { (void)hipFree(h->d_tA); h->d_tA = nullptr; h->tA_capacity = 0; }
-    if (h->d_wtws && !keep_ws) { (void)hipFree(h->d_wtws); h->d_wtws = nullptr; h->wtws_capacity = 0; }
-    if (h->d_wtA && !keep_ws) { (void)hipFree(h->d_wtA); h->d_wtA = nullptr; h->wtA_capacity = 0; }
+    if (h->d_ws && !keep_ws) { h->d_ws.release(); h->d_xchg = nullptr; h->d_lpart = nullptr; h->d_xchg2 = nullptr; h->d_cen_h = h->d_cen_p = nullptr; h->d_snap[0] = h->d_snap[1] = nullptr; h->d_pa_stamp = h->d_pa_same = nullptr; h->d_pa_cnt = h->d_pa_gstamp = nullptr; }
+    if (!keep_ws) for (DevBuf* b : {&h->d_tws, &h->d_tA, &h->d_wtws, &h->d_wtA}) b->release();
     h->t_ws_ready = false;
     h->wt_ready = false;
     h->t_have_fwd = false;
@@ -660,34 +653,16 @@ struct Carver {
     size_t bytes() const { return (size_t)(cur - base); }
 };
 
-// An allocation that outlives the batches (a hipFree / hipMalloc pair of a few hundred MB per batch costs milliseconds, and
-// a training loop binds a new batch every step): kept while *cap >= need, else replaced by one of `want` bytes -- the head
-// room that lets the next batch of similar size fit.  Launches of earlier batches may still read a device buffer, so
-// replacing one waits for the device; a pinned host buffer's reader is the caller's to wait for.  *grew: the contents are gone.
-static int grow_buffer(pf_handle* h, void** buf, size_t* cap, size_t need, size_t want, bool pinned, bool* grew = nullptr) {
-    if (*cap >= need) return PF_OK;
-    if (!pinned) PF_HIP(h, hipDeviceSynchronize());
-    if (*buf) { (void)(pinned ? hipHostFree(*buf) : hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    PF_HIP(h, pinned ? hipHostMalloc(buf, want, hipHostMallocDefault) : hipMalloc(buf, want));
-    *cap = want;
-    if (grew) *grew = true;
-    return PF_OK;
-}
-
 struct ProfScope {
     pf_handle* h; int k; hipStream_t s; bool on;
     ProfScope(pf_handle* h_, int k_, hipStream_t s_) : h(h_), k(k_), s(s_), on((h_->prof_mask >> k_) & 1u) {
         if (!on) return;
-        if (h->prof_used[k] == h->prof_ev[k].size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
-            h->prof_ev[k].push_back({a, b});
-        }
-        (void)hipEventRecord(h->prof_ev[k][h->prof_used[k]].first, s);
+        if (h->prof_used[k] == h->prof_ev[k].size()) h->prof_ev[k].emplace_back(Event(true), Event(true));   // (timing events)
+        if (h->prof_ev[k][h->prof_used[k]].first.record(s) != hipSuccess) on = false;
     }
     ~ProfScope() {
         if (!on) return;
-        (void)hipEventRecord(h->prof_ev[k][h->prof_used[k]].second, s);
+        (void)h->prof_ev[k][h->prof_used[k]].second.record(s);
         h->prof_used[k]++;
     }
 };
@@ -720,7 +695,7 @@ static LayerTiles layer_tiles(const pf_handle* h, int l) { return layer_tiles(h,
 static bool share_now(pf_handle* h) {
     const pf_config& c = h->cfg;
     if (h->share_ok && h->share_check == 0) {        // device rows: the comparison's verdict arrived with the one-hot flag
-        if (h->l0flag_ev) (void)hipEventSynchronize(h->l0flag_ev);
+        (void)h->l0flag_ev.sync();
         h->share_check = (h->l0flag_host && h->l0flag_host[1] == 0) ? 1 : 2;
     }
     if (h->share_check == 2) return false;           // (run_dynamics fails the call: a false claim is the caller's bug, not a mode)
@@ -857,7 +832,7 @@ static bool encoders_on_the_fly(const pf_handle* h) {
 // static hoist waits for it (callers that pass the element types themselves never wait).
 static void l0_resolve_onehot(pf_handle* h) {
     if (h->l0_state != 0) return;
-    if (h->l0flag_ev) (void)hipEventSynchronize(h->l0flag_ev);
+    (void)h->l0flag_ev.sync();
     h->l0_state = (h->Np > 0 && h->l0flag_host && *h->l0flag_host == 0) ? 1 : 2;
     h->l0_onehot = h->l0_state == 1;
 }
@@ -943,12 +918,12 @@ static int ensure_wide_pack(pf_handle* h, hipStream_t s) {
             tab.push_back(w);
         });
         if (total >= (size_t)1 << 31) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_family: the model is too large for the width-generic packing");
-        if (h->d_wpk) { (void)hipFree(h->d_wpk); h->d_wpk = nullptr; }
-        PF_HIP(h, hipMalloc((void**)&h->d_wpk, std::max<size_t>(total, 1) * sizeof(float)));
-        PF_HIP(h, upload(&h->d_wpk_jobs, jobs));
+        h->d_wpk.release();
+        PF_HIP(h, h->d_wpk.reserve(std::max<size_t>(total, 1) * sizeof(float), std::max<size_t>(total, 1) * sizeof(float), Wait::none()));
+        PF_HIP(h, upload(h->d_wpk_jobs, jobs));
         h->n_wpk_jobs = (int)jobs.size();
         for (size_t i = 0; i < tab.size(); ++i) { tab[i].wm = h->d_wpk + jobs[2 * i].dst; tab[i].wg = h->d_wpk + jobs[2 * i + 1].dst; }
-        PF_HIP(h, upload(&h->d_wgvp, tab));
+        PF_HIP(h, upload(h->d_wgvp, tab));
         h->wpk_version = ~0ull;
     }
     if (h->wpk_version != h->w_version) {
@@ -1552,44 +1527,9 @@ int pf_create(const pf_config* cfg, pf_handle** out) {
     return PF_OK;
 }
 
-static void staged_free(StagedBlock& b) { if (b.dev) (void)hipFree(b.dev); if (b.stage) (void)hipHostFree(b.stage); if (b.ev) (void)hipEventDestroy(b.ev); }
-
+// (what the handle owns frees itself: pf_mem.h; the order: where pf_handle declares its streams and events)
 void pf_destroy(pf_handle* h) {
     if (!h) return;
-    free_ws(h);
-    for (void* p : {(void*)h->d_w, (void*)h->d_gvp, (void*)h->d_wgvp, (void*)h->d_wpk, (void*)h->d_wpk_jobs, (void*)h->d_flat, (void*)h->d_wpack,
-                    (void*)h->d_tseg, (void*)h->d_gvpt, (void*)h->d_map, (void*)h->d_split_tab})
-        if (p) (void)hipFree(p);             // what pf_commit_weights and ensure_wide_pack allocated
-    if (h->d_xstat) (void)hipFree(h->d_xstat);
-    if (h->d_pa_chk) (void)hipFree(h->d_pa_chk);
-    if (h->xstat_host) (void)hipHostFree(h->xstat_host);
-    if (h->d_l0c) (void)hipFree(h->d_l0c);
-    if (h->d_ptab) (void)hipFree(h->d_ptab);
-    if (h->d_pin) (void)hipFree(h->d_pin);
-    if (h->d_seed) (void)hipFree(h->d_seed);
-    if (h->d_ms_hist) (void)hipFree(h->d_ms_hist);
-    if (h->d_guide) (void)hipFree(h->d_guide);
-    if (h->d_gdiff) (void)hipFree(h->d_gdiff);
-    if (h->d_optim_part) (void)hipFree(h->d_optim_part);
-    for (StagedBlock* b : {&h->restr, &h->field.blk, &h->types.blk, &h->pairs.blk, &h->sset.blk}) staged_free(*b);
-    if (h->sset.d_sim) (void)hipFree(h->sset.d_sim);
-    if (h->sset.d_status) (void)hipFree(h->sset.d_status);
-    if (h->sset.status_host) (void)hipHostFree(h->sset.status_host);
-    if (h->types.d_tguide) (void)hipFree(h->types.d_tguide);
-    if (h->pairs.d_pguide) (void)hipFree(h->pairs.d_pguide);
-    for (int k = 0; k < 2; ++k) { if (h->stage[k]) (void)hipHostFree(h->stage[k]); if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]); }
-    for (int k = 0; k < 2; ++k) {
-        if (h->d_tab[k]) (void)hipFree(h->d_tab[k]);
-        if (h->tab_guard[k]) (void)hipEventDestroy(h->tab_guard[k]);
-        if (h->tab_up[k]) (void)hipEventDestroy(h->tab_up[k]);
-    }
-    for (int k = 0; k < 3; ++k) if (h->cmp_ev[k]) (void)hipEventDestroy(h->cmp_ev[k]);
-    if (h->s_copy) (void)hipStreamDestroy(h->s_copy);
-    if (h->s_side) (void)hipStreamDestroy(h->s_side);
-    if (h->l0flag_host) (void)hipHostFree(h->l0flag_host);
-    if (h->l0flag_ev) (void)hipEventDestroy(h->l0flag_ev);
-    for (int k = 0; k < pf_handle::K_NUM; ++k)
-        for (auto& ev : h->prof_ev[k]) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     delete h;
 }
 
@@ -1635,9 +1575,9 @@ int pf_commit_weights(pf_handle* h) {
     h->n_upd_tot = c.n_convs * 2 * c.n_update_gvps;
     h->n_packed = pm.w.size();
     h->n_split_tab = pm.split_tab.size();
-    PF_HIP(h, upload(&h->d_w, pm.w));
-    PF_HIP(h, upload(&h->d_map, pm.map));
-    PF_HIP(h, upload(&h->d_split_tab, pm.split_tab));
+    PF_HIP(h, upload(h->d_w, pm.w));
+    PF_HIP(h, upload(h->d_map, pm.map));
+    PF_HIP(h, upload(h->d_split_tab, pm.split_tab));
     h->h_gvp.clear();
     for (const GvpOff& o : pm.gvp) {
         GvpW g;
@@ -1646,11 +1586,11 @@ int pf_commit_weights(pf_handle* h) {
         g.a_gate = h->d_w + o.a_gate; g.b_gate = h->d_w + o.b_gate;
         h->h_gvp.push_back(g);
     }
-    PF_HIP(h, upload(&h->d_gvp, h->h_gvp));
+    PF_HIP(h, upload(h->d_gvp, h->h_gvp));
     h->nparams = flat.size();
-    PF_HIP(h, upload(&h->d_flat, flat));
+    PF_HIP(h, upload(h->d_flat, flat));
     h->n_tseg = c.n_convs <= 4 ? (int)segs.size() : -1;
-    PF_HIP(h, upload(&h->d_tseg, segs));
+    PF_HIP(h, upload(h->d_tseg, segs));
     std::vector<GvpT> tab;              // where each GVP's tensors sit in the flat vector
     for_each_gvp(c, [&](const GvpSpec& g) {
         const int* o = &h->po.gvp[6 * tab.size()];
@@ -1662,13 +1602,11 @@ int pf_commit_weights(pf_handle* h) {
     });
     tab.back().sig = 0;                 // the walk ends with the noise head's last GVP (pf_create: n_noise_gvps >= 1): no sigmoid on its vector gate
     h->n_gvpt = (int)tab.size();
-    PF_HIP(h, upload(&h->d_gvpt, tab));
+    PF_HIP(h, upload(h->d_gvpt, tab));
     // per-handle allocations; what was derived from the old weights goes (ensure_wide_pack / the backward build theirs again on the new d_flat)
-    if (h->d_wpack) { (void)hipFree(h->d_wpack); h->d_wpack = nullptr; }
+    h->d_wpack.release();
     h->wpack_version = ~0ull;
-    if (h->d_wgvp) { (void)hipFree(h->d_wgvp); h->d_wgvp = nullptr; }
-    if (h->d_wpk) { (void)hipFree(h->d_wpk); h->d_wpk = nullptr; }
-    if (h->d_wpk_jobs) { (void)hipFree(h->d_wpk_jobs); h->d_wpk_jobs = nullptr; }
+    h->d_wgvp.release(); h->d_wpk.release(); h->d_wpk_jobs.release();
     if (h->wide) {          // a handle of the family: its table points into d_w, and the gather map keeps that fresh
         std::vector<WideGvp> wtab;
         for_each_gvp(c, [&](const GvpSpec& g) {
@@ -1678,11 +1616,12 @@ int pf_commit_weights(pf_handle* h) {
             w.vi = g.vi; w.vo = g.vo; w.si = g.si; w.so = g.so;
             wtab.push_back(w);
         });
-        PF_HIP(h, upload(&h->d_wgvp, wtab));
+        PF_HIP(h, upload(h->d_wgvp, wtab));
     }
-    if (!h->d_l0c) PF_HIP(h, hipMalloc((void**)&h->d_l0c, 32 * sizeof(float)));
-    if (h->d_ptab) { (void)hipFree(h->d_ptab); h->d_ptab = nullptr; }
-    if (h->spec) PF_HIP(h, hipMalloc((void**)&h->d_ptab, (size_t)L0_PTAB_SLOTS * L0_NTAB * c.rec_nf * PF_S * sizeof(float)));
+    PF_HIP(h, h->d_l0c.reserve(32 * sizeof(float), 32 * sizeof(float), Wait::none()));
+    h->d_ptab.release();
+    const size_t ptab_bytes = (size_t)L0_PTAB_SLOTS * L0_NTAB * c.rec_nf * PF_S * sizeof(float);
+    if (h->spec) PF_HIP(h, h->d_ptab.reserve(ptab_bytes, ptab_bytes, Wait::none()));
     h->t_have_fwd = false;
     ++h->w_version;
     h->committed = true;
@@ -1800,45 +1739,39 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     const size_t S = (size_t)c.n_hidden_scalars, V3 = (size_t)3 * c.vector_size;
     mark();      // 1: host tables built
     // ---- 4. the workspace, the table buffer of this bind and the staging buffer
-    bool fresh = false;           // (launches of the previous batch may still read the old workspace: grow_buffer waits for them)
-    rc = grow_buffer(h, &h->d_ws, &h->ws_capacity, p.ws_bytes + 4096, p.ws_bytes + p.ws_bytes / 8 + 4096, false, &fresh);
-    if (rc) return rc;
+    bool fresh = false;           // (launches of the previous batch may still read the old workspace: the device wait)
+    PF_HIP(h, h->d_ws.reserve(p.ws_bytes + 4096, p.ws_bytes + p.ws_bytes / 8 + 4096, Wait::device(), &fresh));
     if (!h->d_xstat) {                                           // once per handle: the exchange's time-out counter and its pinned mirror
-        PF_HIP(h, hipMalloc((void**)&h->d_xstat, 64));
+        PF_HIP(h, h->d_xstat.reserve(64, 64, Wait::none()));
         PF_HIP(h, hipMemset(h->d_xstat, 0, 64));
-        PF_HIP(h, hipHostMalloc((void**)&h->xstat_host, 64, hipHostMallocDefault));
+        PF_HIP(h, h->xstat_host.reserve(64, 64, Wait::none()));
         *h->xstat_host = 0; h->xstat_ack = 0;
     }
-    const int tw = h->tab_next;
+    pf_handle::TabSlot& tab = h->tab[h->tab_next];
+    pf_handle::TabSlot& tab_other = h->tab[h->tab_next ^ 1];
     h->tab_next ^= 1;
-    if (!h->s_copy) PF_HIP(h, hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking));
-    for (int k = 0; k < 2; ++k) {
-        if (!h->tab_guard[k]) PF_HIP(h, hipEventCreateWithFlags(&h->tab_guard[k], hipEventDisableTiming));
-        if (!h->tab_up[k]) PF_HIP(h, hipEventCreateWithFlags(&h->tab_up[k], hipEventDisableTiming));
-    }
+    hipStream_t s_copy;
+    PF_HIP(h, h->s_copy.get(&s_copy));
     bool tab_grew = false;        // (launches of two binds ago may still read the old buffer)
-    rc = grow_buffer(h, &h->d_tab[tw], &h->tab_cap[tw], p.table_total + 4096, p.table_total + p.table_total / 8 + 4096, false, &tab_grew);
-    if (rc) return rc;
-    if (tab_grew) h->tab_guard_set[tw] = false;
+    PF_HIP(h, tab.buf.reserve(p.table_total + 4096, p.table_total + p.table_total / 8 + 4096, Wait::device(), &tab_grew));
+    if (tab_grew) tab.guard.forget();
     // ---- 5. the pointers, from the plan's offsets
-    char* const base = reinterpret_cast<char*>(h->d_ws);
-    char* const tbase = reinterpret_cast<char*>(h->d_tab[tw]);
+    char* const base = h->d_ws.as<char>();
+    char* const tbase = tab.buf.as<char>();
     set_batch_pointers(h, p, base, tbase);
     if (h->pa_check && !h->d_pa_chk) {                           // once per handle: the check's counters
-        PF_HIP(h, hipMalloc((void**)&h->d_pa_chk, 3 * sizeof(unsigned long long)));
+        PF_HIP(h, h->d_pa_chk.reserve(3 * sizeof(unsigned long long), 3 * sizeof(unsigned long long), Wait::none()));
         PF_HIP(h, hipMemset(h->d_pa_chk, 0, 3 * sizeof(unsigned long long)));
     }
     mark();      // 2: workspace ready
     // the tables are staged in pinned memory and uploaded with one asynchronous copy
-    const int sb = h->stage_next;
+    pf_handle::StageSlot& stage = h->stage[h->stage_next];
     h->stage_next ^= 1;
-    if (!h->stage_ev[sb]) PF_HIP(h, hipEventCreateWithFlags(&h->stage_ev[sb], hipEventDisableTiming));
-    else PF_HIP(h, hipEventSynchronize(h->stage_ev[sb]));       // the copy that last read this buffer (two binds ago) is done
-    rc = grow_buffer(h, &h->stage[sb], &h->stage_cap[sb], p.table_bytes, p.table_bytes + p.table_bytes / 4 + 4096, true);
-    if (rc) return rc;
+    PF_HIP(h, stage.ev.sync());                                  // the copy that last read this buffer (two binds ago) is done
+    PF_HIP(h, stage.buf.reserve(p.table_bytes, p.table_bytes + p.table_bytes / 4 + 4096, Wait::none()));
     mark();      // 3: staging buffer ready
     // ---- 6. the table section, built in the staging buffer itself; a false pocket-group claim is rejected here
-    char* const st = reinterpret_cast<char*>(h->stage[sb]);
+    char* const st = stage.buf.as<char>();
     pfbind::FillResult fr;
     rc = pfbind::fill_tables(p, in, st, fr, berr);
     if (rc) { h->err = berr.msg; return rc; }
@@ -1851,13 +1784,12 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     // ---- 7. the upload: on the copy stream, once everything that read this table buffer (the bind before the previous one and
     // its steps) has finished; the caller's stream continues when it has arrived.  The guard of the OTHER buffer is recorded
     // now: what is enqueued on the caller's stream at this point is everything that reads it.
-    if (h->tab_guard_set[tw]) PF_HIP(h, hipStreamWaitEvent(h->s_copy, h->tab_guard[tw], 0));
-    PF_HIP(h, hipEventRecord(h->tab_guard[tw ^ 1], s));
-    h->tab_guard_set[tw ^ 1] = true;
-    PF_HIP(h, hipMemcpyAsync(tbase, st, p.table_bytes, hipMemcpyHostToDevice, h->s_copy));
-    PF_HIP(h, hipEventRecord(h->stage_ev[sb], h->s_copy));
-    PF_HIP(h, hipEventRecord(h->tab_up[tw], h->s_copy));
-    PF_HIP(h, hipStreamWaitEvent(s, h->tab_up[tw], 0));
+    PF_HIP(h, tab.guard.hold(s_copy));
+    PF_HIP(h, tab_other.guard.record(s));
+    PF_HIP(h, hipMemcpyAsync(tbase, st, p.table_bytes, hipMemcpyHostToDevice, s_copy));
+    PF_HIP(h, stage.ev.record(s_copy));
+    PF_HIP(h, tab.up.record(s_copy));
+    PF_HIP(h, tab.up.hold(s));
     mark();      // 5: upload enqueued
     // ---- 8. the clears and the four launches.  Message rows: the node kernels read only rows the edge kernels of the same
     // layer wrote (the last slot of every aligned group a destination's segment touches) and the all-zero row Ecap, so a
@@ -1902,12 +1834,11 @@ static int set_pocket_batch_impl(pf_handle* h, int32_t B, const int32_t* prot_pt
     }
     // ---- 9. the read-back: the one-hot verdict of k_l0_types comes back through pinned memory; nobody waits for it here
     // (l0_resolve_onehot)
-    if (!h->l0flag_host) PF_HIP(h, hipHostMalloc((void**)&h->l0flag_host, 64, hipHostMallocDefault));
-    if (!h->l0flag_ev) PF_HIP(h, hipEventCreateWithFlags(&h->l0flag_ev, hipEventDisableTiming));
-    else PF_HIP(h, hipEventSynchronize(h->l0flag_ev));           // the previous bind's read-back (long done) before its target is reused
+    PF_HIP(h, h->l0flag_host.reserve(64, 64, Wait::none()));
+    PF_HIP(h, h->l0flag_ev.sync());                              // the previous bind's read-back (long done) before its target is reused
     h->l0flag_host[0] = 1; h->l0flag_host[1] = 1;
     PF_HIP(h, hipMemcpyAsync(h->l0flag_host, h->d_l0flag, 8, hipMemcpyDeviceToHost, s));
-    PF_HIP(h, hipEventRecord(h->l0flag_ev, s));
+    PF_HIP(h, h->l0flag_ev.record(s));
     mark();      // 6: everything enqueued
     if (timing) fprintf(stderr, "[pf_set_pocket_batch] B=%d checks+tables %.2f ws %.2f stage-wait %.2f index arrays (in staging) %.2f upload %.2f launches+waits %.2f ms (fresh %d, %zu MB)\n",
                         B, tm[1] - tm[0], tm[2] - tm[1], tm[3] - tm[2], tm[4] - tm[3], tm[5] - tm[4], tm[6] - tm[5], (int)fresh, p.ws_bytes >> 20);
@@ -1963,40 +1894,33 @@ int64_t pf_build_pp_edges(pf_handle* h, int32_t B, const int32_t* prot_ptr, cons
     if (!h || B < 1 || !prot_ptr || !dev_prot_x) return PF_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int Np = prot_ptr[B];
-    float4* xn = nullptr; int *dptr = nullptr, *ddeg = nullptr, *doff = nullptr, *dsrc = nullptr, *ddst = nullptr;
+    DevArr<float4> xn; DevArr<int> dptr, ddeg, doff, dsrc, ddst;     // (every return frees them)
     std::vector<int> deg(std::max(Np, 1)), off(std::max(Np, 1) + 1, 0);
     int64_t total = 0;
-    int rc = PF_OK;
-    auto cleanup = [&]() {
-        if (xn) (void)hipFree(xn); if (dptr) (void)hipFree(dptr); if (ddeg) (void)hipFree(ddeg);
-        if (doff) (void)hipFree(doff); if (dsrc) (void)hipFree(dsrc); if (ddst) (void)hipFree(ddst);
-    };
-#define PF_HIP2(call) do { hipError_t _e = (call); if (_e != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(_e); cleanup(); return PF_ERR_HIP; } } while (0)
-    PF_HIP2(hipMalloc((void**)&xn, (size_t)std::max(Np, 1) * 16));
-    PF_HIP2(hipMalloc((void**)&dptr, (size_t)(B + 1) * 4));
-    PF_HIP2(hipMalloc((void**)&ddeg, (size_t)std::max(Np, 1) * 4));
-    PF_HIP2(hipMalloc((void**)&doff, (size_t)std::max(Np, 1) * 4));
-    PF_HIP2(hipMemcpy(dptr, prot_ptr, (size_t)(B + 1) * 4, hipMemcpyHostToDevice));
+    auto alloc = [](auto& b, size_t bytes) { return b.reserve(bytes, bytes, Wait::none()); };
+    PF_HIP(h, alloc(xn, (size_t)std::max(Np, 1) * 16));
+    PF_HIP(h, alloc(dptr, (size_t)(B + 1) * 4));
+    PF_HIP(h, alloc(ddeg, (size_t)std::max(Np, 1) * 4));
+    PF_HIP(h, alloc(doff, (size_t)std::max(Np, 1) * 4));
+    PF_HIP(h, hipMemcpy(dptr, prot_ptr, (size_t)(B + 1) * 4, hipMemcpyHostToDevice));
     pfk_load_coords(dev_prot_x, xn, Np, nullptr, nullptr, 0.f, s);
     const float r2 = h->cfg.cutoff_pp * h->cfg.cutoff_pp;
     pfk_pp_radius(xn, dptr, B, r2, max_nb, ddeg, nullptr, nullptr, nullptr, 0, s);
-    PF_HIP2(hipStreamSynchronize(s));
-    PF_HIP2(hipMemcpy(deg.data(), ddeg, (size_t)Np * 4, hipMemcpyDeviceToHost));
+    PF_HIP(h, hipStreamSynchronize(s));
+    PF_HIP(h, hipMemcpy(deg.data(), ddeg, (size_t)Np * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < Np; ++i) { off[i] = (int)total; total += deg[i]; }
     if (host_src && host_dst) {
-        if (capacity < total) { cleanup(); h->err = "pf_build_pp_edges: capacity too small"; return PF_ERR_ARG; }
+        if (capacity < total) PF_FAIL(h, PF_ERR_ARG, "pf_build_pp_edges: capacity too small");
         if (total > 0) {
-            PF_HIP2(hipMalloc((void**)&dsrc, (size_t)total * 4));
-            PF_HIP2(hipMalloc((void**)&ddst, (size_t)total * 4));
-            PF_HIP2(hipMemcpy(doff, off.data(), (size_t)Np * 4, hipMemcpyHostToDevice));
+            PF_HIP(h, alloc(dsrc, (size_t)total * 4));
+            PF_HIP(h, alloc(ddst, (size_t)total * 4));
+            PF_HIP(h, hipMemcpy(doff, off.data(), (size_t)Np * 4, hipMemcpyHostToDevice));
             pfk_pp_radius(xn, dptr, B, r2, max_nb, ddeg, doff, dsrc, ddst, 1, s);
-            PF_HIP2(hipStreamSynchronize(s));
-            PF_HIP2(hipMemcpy(host_src, dsrc, (size_t)total * 4, hipMemcpyDeviceToHost));
-            PF_HIP2(hipMemcpy(host_dst, ddst, (size_t)total * 4, hipMemcpyDeviceToHost));
+            PF_HIP(h, hipStreamSynchronize(s));
+            PF_HIP(h, hipMemcpy(host_src, dsrc, (size_t)total * 4, hipMemcpyDeviceToHost));
+            PF_HIP(h, hipMemcpy(host_dst, ddst, (size_t)total * 4, hipMemcpyDeviceToHost));
         }
     }
-    (void)rc;
-    cleanup();
     return total;
 }
 
@@ -2191,32 +2115,9 @@ static int seed_move(pf_handle* h, const float* dev_noise0, hipStream_t s) {
     return step_end(h, sp, mv, s);
 }
 
-// A run's device scratch (d_pin, d_guide, d_seed, a staged block's device buffer): kept while `need` bytes fit, else replaced by one of `want` bytes.  Launches
-// of an earlier run on this stream may still read it, so replacing it waits for the caller's STREAM -- not for the device as
-// grow_buffer does: several lanes sample on one device at once
-static int grow_run_scratch(pf_handle* h, void** buf, size_t* cap, size_t need, size_t want, hipStream_t s) {
-    if (need <= *cap) return PF_OK;
-    if (*buf) { PF_HIP(h, hipStreamSynchronize(s)); PF_HIP(h, hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    PF_HIP(h, hipMalloc(buf, want));
-    *cap = want;
-    return PF_OK;
-}
-// A StagedBlock.  Reserve: the last upload has read the staging buffer, which then holds `bytes` (grown to twice that) for the caller to
-// pack into.  Upload: one copy into the device buffer -- which the caller grew (grow_run_scratch) before its begin enqueued anything
-static int staged_reserve(pf_handle* h, StagedBlock& b, size_t bytes) {
-    if (b.ev) PF_HIP(h, hipEventSynchronize(b.ev));
-    else PF_HIP(h, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
-    if (bytes <= b.stage_capacity) return PF_OK;
-    if (b.stage) { (void)hipHostFree(b.stage); b.stage = nullptr; b.stage_capacity = 0; }
-    PF_HIP(h, hipHostMalloc(&b.stage, bytes * 2, hipHostMallocDefault));
-    b.stage_capacity = bytes * 2;
-    return PF_OK;
-}
-static int staged_upload(pf_handle* h, StagedBlock& b, size_t bytes, hipStream_t s) {
-    PF_HIP(h, hipMemcpyAsync(b.dev, b.stage, bytes, hipMemcpyHostToDevice, s));
-    PF_HIP(h, hipEventRecord(b.ev, s));
-    return PF_OK;
-}
+// A run's device scratch (d_pin, d_guide, d_seed, a staged block's device buffer) is kept while it fits.  Launches of an earlier run
+// on the caller's stream may still read it, so replacing it waits for that STREAM (Wait::on(s)) -- not for the device as a bind's
+// buffers do: several lanes sample on one device at once
 
 // Pinned centers: pf_sample_begin, then the handle's own copy of the caller's pin arrays (stream-ordered; the caller may free its
 // arrays once the stream has passed this call).  The run is pinned until the next pf_sample_begin / _pinned or bind
@@ -2229,8 +2130,8 @@ static int begin_pinned(pf_handle* h, const float* dev_init_pharm_com, const flo
     hipStream_t s = (hipStream_t)stream;
     const size_t nf = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
     const size_t bytes = nf * 4 * (1 + 3 + nh);
-    if ((rc = grow_run_scratch(h, &h->d_pin, &h->pin_capacity, bytes, bytes, s)) != PF_OK) return rc;
-    h->d_pin_flags = (int*)h->d_pin; h->d_pin_x = (float*)h->d_pin + nf; h->d_pin_h = h->d_pin_x + nf * 3;
+    PF_HIP(h, h->d_pin.reserve(bytes, bytes, Wait::on(s)));
+    h->d_pin_flags = h->d_pin.as<int>(); h->d_pin_x = h->d_pin.as<float>() + nf; h->d_pin_h = h->d_pin_x + nf * 3;
     if (h->Nf > 0) {
         PF_HIP(h, hipMemcpyAsync(h->d_pin_flags, dev_pin_flags, (size_t)h->Nf * 4, hipMemcpyDeviceToDevice, s));
         PF_HIP(h, hipMemcpyAsync(h->d_pin_x, dev_pin_x, (size_t)h->Nf * 3 * 4, hipMemcpyDeviceToDevice, s));
@@ -2261,8 +2162,8 @@ int pf_sample_seed_next(pf_handle* h, const pf_seed_coef* coef, const float* dev
     const size_t nf = (size_t)std::max(h->Nf, 1), nh = (size_t)h->cfg.pharm_nf;
     const size_t bytes = nf * 4 * (3 + nh);
     h->seed_armed = false;                  // (a seed armed before and not yet used is replaced, also when the copies below fail)
-    if ((rc = grow_run_scratch(h, &h->d_seed, &h->seed_capacity, bytes, bytes, s)) != PF_OK) return rc;
-    h->d_seed_x = (float*)h->d_seed; h->d_seed_h = h->d_seed_x + nf * 3;
+    PF_HIP(h, h->d_seed.reserve(bytes, bytes, Wait::on(s)));
+    h->d_seed_x = h->d_seed.as<float>(); h->d_seed_h = h->d_seed_x + nf * 3;
     if (h->Nf > 0) {
         PF_HIP(h, hipMemcpyAsync(h->d_seed_x, dev_seed_x, (size_t)h->Nf * 3 * 4, hipMemcpyDeviceToDevice, s));
         PF_HIP(h, hipMemcpyAsync(h->d_seed_h, dev_seed_h, (size_t)h->Nf * nh * 4, hipMemcpyDeviceToDevice, s));
@@ -2320,13 +2221,13 @@ int pf_denoise_step_ms(pf_handle* h, const pf_ms_coef* coef, pf_stream stream) {
                                  "step of a run, and the first after any other move, must have c1 == 0)");
     hipStream_t s = (hipStream_t)stream;
     const size_t bytes = (size_t)std::max(h->Nf, 1) * 4 * (3 + (size_t)h->cfg.pharm_nf);
-    if ((rc = grow_run_scratch(h, &h->d_ms_hist, &h->ms_hist_capacity, bytes, bytes, s)) != PF_OK) return rc;
+    PF_HIP(h, h->d_ms_hist.reserve(bytes, bytes, Wait::on(s)));
     StepParams sp = step_params_base(h, nullptr);
     sp.eps_h = h->d_eps_h; sp.eps_x = h->d_eps_x;
     StepMove mv;
     mv.args.kind = StepMoveArgs::MS;
     MsParams& q = mv.args.ms;
-    q.hist = (float*)h->d_ms_hist;
+    q.hist = h->d_ms_hist.as<float>();
     q.cz_x = coef->cz_x; q.c0_x = coef->c0_x; q.c1_x = coef->c1_x; q.cz_h = coef->cz_h; q.c0_h = coef->c0_h; q.c1_h = coef->c1_h;
     ++h->step_id;
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, false, nullptr);
@@ -2678,7 +2579,7 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
     bool fresh = false;
     size_t bytes = 0;
     for (int pass = 0; pass < 2; ++pass) {
-        Carver w(pass ? h->d_tws : nullptr);
+        Carver w(pass ? h->d_tws.get() : nullptr);
         for (int l = 0; l <= L; ++l) { w.take(h->t_H[l], (size_t)N * PF_S); w.take(h->t_V[l], (size_t)N * 48); }
         for (int l = 0; l < L; ++l) { w.take(h->t_msg_s[l], E1 * PF_S); w.take(h->t_msg_v[l], E1 * 48); }
         for (int a = 0; a < 2; ++a) { w.take(h->t_G_h[a], (size_t)N * PF_S); w.take(h->t_G_v[a], (size_t)N * 48); }
@@ -2697,22 +2598,20 @@ static int ensure_train_ws(pf_handle* h, hipStream_t s) {
         for (int l = 0; l < L; ++l) { w.take(h->t_sv_z[l], ng * Es * PF_S); w.take(h->t_sv_g[l], ng * Es * 16); w.take(h->t_sv_v[l], ng * Es * 48); }
         w.take(h->t_gs_buf, Es * PF_S); w.take(h->t_gv_buf, Es * 48);
         if (pass == 0) {
-            // like d_ws the allocation outlives the batch: a training loop binds a new batch every step, and a hipFree / hipMalloc
+            // like d_ws the allocation outlives the batch: a training loop binds a new batch every step, and a free / allocate
             // pair of a few GB (plus clearing it) per step cost two orders of magnitude more than the step itself
             bytes = w.bytes();
-            const int rc = grow_buffer(h, &h->d_tws, &h->tws_capacity, bytes + 4096, bytes + bytes / 8 + 4096, false, &fresh);
-            if (rc) return rc;
+            PF_HIP(h, h->d_tws.reserve(bytes + 4096, bytes + bytes / 8 + 4096, Wait::device(), &fresh));
         } else if (w.bytes() != bytes)
             PF_FAIL(h, PF_ERR_STATE, "training workspace: carved %zu bytes, counted %zu", w.bytes(), bytes);
     }
     {
         // int64 accumulators [N][128] and [N][48]: cleared when allocated, pfk_fix_apply leaves every element it read at zero
         const size_t a_bytes = ((size_t)N * PF_S * 8 + 255) / 256 * 256, need_a = a_bytes + (size_t)N * 48 * 8;
-        const int rc = grow_buffer(h, &h->d_tA, &h->tA_capacity, need_a, need_a + need_a / 8, false, &h->tA_dirty);
-        if (rc) return rc;
-        if (h->tA_dirty) { PF_HIP(h, hipMemsetAsync(h->d_tA, 0, h->tA_capacity, s)); h->tA_dirty = false; }
-        h->t_A_h = reinterpret_cast<long long*>(h->d_tA);
-        h->t_A_v = reinterpret_cast<long long*>(reinterpret_cast<char*>(h->d_tA) + a_bytes);
+        PF_HIP(h, h->d_tA.reserve(need_a, need_a + need_a / 8, Wait::device(), &h->tA_dirty));
+        if (h->tA_dirty) { PF_HIP(h, hipMemsetAsync(h->d_tA.get(), 0, h->d_tA.capacity(), s)); h->tA_dirty = false; }
+        h->t_A_h = h->d_tA.as<long long>();
+        h->t_A_v = reinterpret_cast<long long*>(h->d_tA.as<char>() + a_bytes);
     }
     // message buffers: the zero row (index Ecap) must read as zeros; V[0] is the all-zero initial vector state
     // (only rows written by the same forward and the zero row are ever read: a reused allocation needs just that row)
@@ -2749,7 +2648,7 @@ static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
     // two passes over one list: sizes, then pointers
     size_t bytes = 0;
     for (int pass = 0; pass < 2; ++pass) {
-        Carver cv(pass ? h->d_wtws : nullptr);
+        Carver cv(pass ? h->d_wtws.get() : nullptr);
         auto take = [&](float*& dst, size_t n) { cv.take(dst, n); };
         take(w.esv_s, L * nm * Es * ES); take(w.esv_v, L * nm * Es * EV);
         take(w.x1_s, L * N * S); take(w.x1_v, L * N * V3); take(w.x2_s, L * N * S); take(w.x2_v, L * N * V3);
@@ -2767,18 +2666,16 @@ static int ensure_wide_train_ws(pf_handle* h, hipStream_t s) {
         take(h->t_lgx, (size_t)h->Nf * 3); take(h->t_lgh, (size_t)h->Nf * c.pharm_nf); take(h->t_lout, 64);
         if (pass == 0) {
             bytes = cv.bytes();
-            const int rc = grow_buffer(h, &h->d_wtws, &h->wtws_capacity, bytes + 4096, bytes + bytes / 8 + 4096, false);
-            if (rc) return rc;
+            PF_HIP(h, h->d_wtws.reserve(bytes + 4096, bytes + bytes / 8 + 4096, Wait::device()));
         } else if (cv.bytes() != bytes)
             PF_FAIL(h, PF_ERR_STATE, "width-generic training workspace: carved %zu bytes, counted %zu", cv.bytes(), bytes);
     }
     w.Es = Es;
     const size_t a_bytes = (N * S * 8 + 255) / 256 * 256, need_a = a_bytes + N * V3 * 8;
-    const int rc_a = grow_buffer(h, &h->d_wtA, &h->wtA_capacity, need_a, need_a + need_a / 8, false);
-    if (rc_a) return rc_a;
-    PF_HIP(h, hipMemsetAsync(h->d_wtA, 0, h->wtA_capacity, s));
-    w.A_h = reinterpret_cast<long long*>(h->d_wtA);
-    w.A_v = reinterpret_cast<long long*>(reinterpret_cast<char*>(h->d_wtA) + a_bytes);
+    PF_HIP(h, h->d_wtA.reserve(need_a, need_a + need_a / 8, Wait::device()));
+    PF_HIP(h, hipMemsetAsync(h->d_wtA.get(), 0, h->d_wtA.capacity(), s));
+    w.A_h = h->d_wtA.as<long long>();
+    w.A_v = reinterpret_cast<long long*>(h->d_wtA.as<char>() + a_bytes);
     h->t_ws_ready = false;                       // (the specialised leg's carve owns the same loss-buffer fields)
     h->wt_ready = true;
     return PF_OK;
@@ -2893,11 +2790,7 @@ static int optim_check(pf_handle* h, const char* who, const void* p, const void*
 static int optim_launch(pf_handle* h, size_t n, float* p, const float* g, float* m, float* v, float* ema, float* mirror, void* state,
                         const pf_optim_opts* o, hipStream_t s) {
     const size_t n_part = (n + PFO_CHUNK - 1) / PFO_CHUNK;
-    if (n_part > h->optim_part_cap) {
-        if (h->d_optim_part) { (void)hipFree(h->d_optim_part); h->d_optim_part = nullptr; h->optim_part_cap = 0; }
-        PF_HIP(h, hipMalloc((void**)&h->d_optim_part, n_part * sizeof(double)));
-        h->optim_part_cap = n_part;
-    }
+    PF_HIP(h, h->d_optim_part.reserve(n_part * sizeof(double), n_part * sizeof(double), Wait::none()));
     OptimParams P{};
     P.p = p; P.g = g; P.m = m; P.v = v; P.ema = ema; P.mirror = mirror; P.n = n;
     P.lr = o->lr; P.b1 = o->beta1; P.b2 = o->beta2; P.eps = o->eps; P.wd = o->weight_decay; P.grad_scale = o->grad_scale;
@@ -3105,7 +2998,7 @@ static int wide_train_backward(pf_handle* h, const float* g_eps_h, const float* 
         h->has_pend_scale = false;
     }
     if (full) PF_HIP(h, hipMemsetAsync(w.gpart, 0, (size_t)PFWT_NB * wc.gstride * sizeof(float), s));
-    PF_HIP(h, hipMemsetAsync(h->d_wtA, 0, h->wtA_capacity, s));
+    PF_HIP(h, hipMemsetAsync(h->d_wtA.get(), 0, h->d_wtA.capacity(), s));
     pfk_fix_scale(g_eps_h, h->Nf * c.pharm_nf, g_eps_x, h->Nf * 3, w.fix, s);
     // (a layer's level-0 launch stores the rows of the slots it walks; the others -- the last layer's fp slots -- stay zero)
     if (g_x) PF_HIP(h, hipMemsetAsync(w.gdiff, 0, (size_t)L * w.Es * 3 * sizeof(float), s));
@@ -3198,7 +3091,7 @@ struct BwdCall {
     // has a parameter gradient to give (false: pf_dynamics_input_vjp and the guided step -- no reduce, early or final, and the
     // encoders' backward only for g_h, on its center tiles)
     float *g_x, *g_h; bool full;
-    bool side_on;                           // the side stream is another stream than the caller's (always, unless the caller passes it)
+    hipStream_t side; bool side_on;         // the handle's side stream; it is another stream than the caller's (always, unless the caller passes it)
     TrainCommon tc;                         // h->t_common with this call's k_pack_gvp tables
     ReduceParams rp;                        // the final reduce; the early one is a copy with its own class mask
     int a;                                  // t_G_*[a]: dL/d(output) of the layer being differentiated, [a ^ 1]: dL/d(its input)
@@ -3233,7 +3126,8 @@ static int bwd_prologue(BwdCall& bc, float* dev_grad) {
     h->has_pend_scale = false;
     if (h->wpack_version != h->w_version) {
         const int ng = h->n_gvpt;
-        if (!h->d_wpack) PF_HIP(h, hipMalloc((void**)&h->d_wpack, (size_t)2 * std::max(ng, 1) * PFT_WPACK_FLOATS * sizeof(float)));
+        const size_t wpack_bytes = (size_t)2 * std::max(ng, 1) * PFT_WPACK_FLOATS * sizeof(float);       // (released by every commit)
+        PF_HIP(h, h->d_wpack.reserve(wpack_bytes, wpack_bytes, Wait::none()));
         pfk_pack_gvp(h->d_flat, h->d_gvpt, ng, h->d_wpack, h->d_wpack + (size_t)ng * PFT_WPACK_FLOATS, scale_now ? &h->pend_scale : nullptr, bc.s);
         h->wpack_version = h->w_version;
     } else if (scale_now) {
@@ -3243,7 +3137,7 @@ static int bwd_prologue(BwdCall& bc, float* dev_grad) {
     h->t_common.wpack_b = h->d_wpack; h->t_common.wpack_f = h->d_wpack + (size_t)h->n_gvpt * PFT_WPACK_FLOATS;
     bc.tc = h->t_common;
     bc.rp = reduce_params(h, dev_grad);
-    if (h->tA_dirty) PF_HIP(h, hipMemsetAsync(h->d_tA, 0, h->tA_capacity, bc.s));      // an earlier pass stopped half way
+    if (h->tA_dirty) PF_HIP(h, hipMemsetAsync(h->d_tA.get(), 0, h->d_tA.capacity(), bc.s));      // an earlier pass stopped half way
     h->tA_dirty = true;
     return PF_OK;
 }
@@ -3259,7 +3153,7 @@ static void bwd_work_lists(BwdCall& bc, int l, hipStream_t on) {
 // batch that clears the last layer's input gradients
 static void bwd_add_gdiff_clear(const BwdCall& bc, ZeroBatch& zb) {
     const pf_handle* h = bc.h;
-    if (bc.g_x) zb.add(h->d_gdiff, (size_t)h->cfg.n_convs * gdiff_layer_stride(h) * 3 * sizeof(float));
+    if (bc.g_x) zb.add(h->d_gdiff.get(), (size_t)h->cfg.n_convs * gdiff_layer_stride(h) * 3 * sizeof(float));
 }
 // The work lists depend on the forward's edge counts only: they are built on the side stream while the head's backward runs on
 // the caller's.  Two groups: what the first layer of the loop needs at once (its work lists, its cleared input gradients: cmp_ev[1]),
@@ -3268,12 +3162,10 @@ static void bwd_add_gdiff_clear(const BwdCall& bc, ZeroBatch& zb) {
 static int bwd_side_lists(BwdCall& bc) {
     pf_handle* h = bc.h;
     const int L = h->cfg.n_convs;
-    for (int k = 0; k < 3; ++k)
-        if (!h->cmp_ev[k]) PF_HIP(h, hipEventCreateWithFlags(&h->cmp_ev[k], hipEventDisableTiming));
-    if (!h->s_side) PF_HIP(h, hipStreamCreateWithFlags(&h->s_side, hipStreamNonBlocking));
-    hipStream_t side = h->s_side;
+    PF_HIP(h, h->s_side.get(&bc.side));
+    hipStream_t side = bc.side;
     bc.side_on = side != bc.s;
-    if (bc.side_on) { PF_HIP(h, hipEventRecord(h->cmp_ev[0], bc.s)); PF_HIP(h, hipStreamWaitEvent(side, h->cmp_ev[0], 0)); }
+    if (bc.side_on) { PF_HIP(h, h->cmp_ev[0].record(bc.s)); PF_HIP(h, h->cmp_ev[0].hold(side)); }
     bwd_work_lists(bc, L - 1, side);
     if (bc.side_on) {
         // the first layer of the loop receives its input gradients in G[1]: cleared here, under the head's backward
@@ -3283,11 +3175,11 @@ static int bwd_side_lists(BwdCall& bc) {
         bwd_add_gdiff_clear(bc, zb);
         zb.flush();
         bc.first_clear_done = true;
-        PF_HIP(h, hipEventRecord(h->cmp_ev[1], side));
+        PF_HIP(h, h->cmp_ev[1].record(side));
     }
     pfk_fix_scale(bc.g_eps_h, h->Nf * h->cfg.pharm_nf, bc.g_eps_x, h->Nf * 3, h->t_fix, side);
     for (int l = L - 2; l >= 0; --l) bwd_work_lists(bc, l, side);
-    if (bc.side_on) PF_HIP(h, hipEventRecord(h->cmp_ev[2], side));
+    if (bc.side_on) PF_HIP(h, h->cmp_ev[2].record(side));
     return PF_OK;
 }
 // (the head kernel stores dL/d(last layer output) for every pharm row, and the last layer's node kernel reads those rows
@@ -3382,7 +3274,7 @@ static void bwd_edge_levels(BwdCall& bc, int l) {
         e.level = lv;
         e.fx = h->no_fixed_shapes ? 0 : h->po.edge_fx[(size_t)l * nm + lv];
         // level 0 with dL/d(center coordinates) asked for: the launch with the geometry epilogue, into this layer's rows of d_gdiff
-        e.g_diff = (bc.g_x && lv == 0) ? (float*)h->d_gdiff + (size_t)l * gdiff_layer_stride(h) * 3 : nullptr;
+        e.g_diff = (bc.g_x && lv == 0) ? h->d_gdiff.as<float>() + (size_t)l * gdiff_layer_stride(h) * 3 : nullptr;
         ProfScope ps(h, pf_handle::K_BWD_EDGE_LEVEL, bc.s);
         pfk_bwd_edge_level(&e, h->t_nblk, bc.s);
     }
@@ -3419,10 +3311,10 @@ static int bwd_early_reduce(BwdCall& bc, int l) {
     ReduceParams early = bc.rp;
     early.cls_mask = (1u << PFT_CLS_HEAD) | (1u << (PFT_CLS_NODE + l));
     for (int et = 0; et < 4; ++et) early.cls_mask |= 1u << (PFT_CLS_MSG + l * 4 + et);
-    PF_HIP(h, hipEventRecord(h->cmp_ev[0], bc.s));
-    PF_HIP(h, hipStreamWaitEvent(h->s_side, h->cmp_ev[0], 0));
-    pfk_train_reduce(&early, h->s_side);
-    PF_HIP(h, hipEventRecord(h->cmp_ev[1], h->s_side));
+    PF_HIP(h, h->cmp_ev[0].record(bc.s));
+    PF_HIP(h, h->cmp_ev[0].hold(bc.side));
+    pfk_train_reduce(&early, bc.side);
+    PF_HIP(h, h->cmp_ev[1].record(bc.side));
     bc.early_mask = early.cls_mask;
     return PF_OK;
 }
@@ -3444,7 +3336,7 @@ static void bwd_encoders(BwdCall& bc) {
 // dL/d(center coordinates): the centers' sums of the rows the level-0 launches left in d_gdiff
 static void bwd_center_sum(BwdCall& bc) {
     const pf_handle* h = bc.h;
-    const WtCenterSumParams p = wt_center_sum_params(h, (const float*)h->d_gdiff, gdiff_layer_stride(h), bc.g_x);
+    const WtCenterSumParams p = wt_center_sum_params(h, h->d_gdiff.as<const float>(), gdiff_layer_stride(h), bc.g_x);
     pfk_wt_center_sum(&p, bc.s);
 }
 
@@ -3473,17 +3365,17 @@ static int tuned_train_backward(pf_handle* h, const float* g_eps_h, const float*
     bc.g_x = g_x; bc.g_h = g_h; bc.full = dev_grad != nullptr;
     if (g_x) {
         const size_t need = (size_t)L * gdiff_layer_stride(h) * 3 * sizeof(float);
-        if ((rc = grow_run_scratch(h, &h->d_gdiff, &h->gdiff_capacity, need, need + need / 8, s)) != PF_OK) return rc;
+        PF_HIP(h, h->d_gdiff.reserve(need, need + need / 8, Wait::on(s)));
     }
     if ((rc = bwd_prologue(bc, dev_grad)) != PF_OK || (rc = bwd_side_lists(bc)) != PF_OK) return rc;
     bwd_head_launch(bc);
-    if (bc.side_on) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[1], 0));       // the side stream's first group
+    if (bc.side_on) PF_HIP(h, h->cmp_ev[1].hold(bc.s));       // the side stream's first group
     // The last conv layer's output is read on the pharm nodes only (dynamics_gvp.py:91), the layer before it only where the last
     // one reads it (the pharm nodes and the active atoms): every other row has a zero gradient and, as in the forward, no work
     for (int l = L - 1; l >= 0; --l, bc.a ^= 1) {
         const bool last = l == L - 1;
         bwd_node_launch(bc, l);
-        if (last && bc.side_on) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[2], 0));      // the side stream's second group
+        if (last && bc.side_on) PF_HIP(h, h->cmp_ev[2].hold(bc.s));      // the side stream's second group
         bwd_edge_levels(bc, l);
         bwd_fix_join(bc, l);
         if (bc.full && last && L >= 2 && bc.side_on && (rc = bwd_early_reduce(bc, l)) != PF_OK) return rc;
@@ -3493,7 +3385,7 @@ static int tuned_train_backward(pf_handle* h, const float* g_eps_h, const float*
     if (bc.full) {
         bc.rp.cls_mask = ~bc.early_mask;
         pfk_train_reduce(&bc.rp, bc.s);
-        if (bc.early_mask) PF_HIP(h, hipStreamWaitEvent(bc.s, h->cmp_ev[1], 0));       // the gradient is complete on the caller's stream
+        if (bc.early_mask) PF_HIP(h, h->cmp_ev[1].hold(bc.s));       // the gradient is complete on the caller's stream
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
@@ -3572,37 +3464,37 @@ int pf_sample_begin_guided(pf_handle* h, const float* dev_init_pharm_com, const 
     // every staging reservation and every device growth before anything is enqueued; the uploads behind begin_pinned
     const int n = pfrestr::n_restraints(a, h->B), nh = h->cfg.pharm_nf;
     const size_t bytes = pfrestr::RestrLayout(h->B, n).words() * 4;
-    if ((rc = staged_reserve(h, h->restr, bytes)) != PF_OK) return rc;
-    if ((rc = grow_run_scratch(h, &h->restr.dev, &h->restr.capacity, bytes, bytes * 2, s)) != PF_OK) return rc;
+    PF_HIP(h, h->restr.reserve(bytes));
+    PF_HIP(h, h->restr.dev.reserve(bytes, bytes * 2, Wait::on(s)));
     const size_t gbytes = guide_work(h).words() * 4, tbytes = type_work(h).words() * 4;
-    if ((rc = grow_run_scratch(h, &h->d_guide, &h->guide_capacity, gbytes, gbytes, s)) != PF_OK) return rc;
+    PF_HIP(h, h->d_guide.reserve(gbytes, gbytes, Wait::on(s)));
     const pffield::FieldLayout fl(h->Np, h->B, h->field.arm.n, nh);
-    if (fielded && (rc = grow_run_scratch(h, &h->field.blk.dev, &h->field.blk.capacity, fl.words() * 4, fl.words() * 8, s)) != PF_OK) return rc;
+    if (fielded) PF_HIP(h, h->field.blk.dev.reserve(fl.words() * 4, fl.words() * 8, Wait::on(s)));
     const size_t types_bytes = pftypes::TypesLayout(h->B, h->types.arm.n).words() * 4;
-    if (typed && (rc = grow_run_scratch(h, &h->types.blk.dev, &h->types.blk.capacity, types_bytes, types_bytes * 2, s)) != PF_OK) return rc;
-    if (typed && (rc = grow_run_scratch(h, &h->types.d_tguide, &h->types.tguide_capacity, tbytes, tbytes, s)) != PF_OK) return rc;
+    if (typed) PF_HIP(h, h->types.blk.dev.reserve(types_bytes, types_bytes * 2, Wait::on(s)));
+    if (typed) PF_HIP(h, h->types.d_tguide.reserve(tbytes, tbytes, Wait::on(s)));
     const size_t pairs_bytes = pfpairs::PairsLayout(h->B, h->pairs.n_arm).words() * 4, pbytes = pair_work(h).words() * 4;
-    if (paired && (rc = grow_run_scratch(h, &h->pairs.blk.dev, &h->pairs.blk.capacity, pairs_bytes, pairs_bytes * 2, s)) != PF_OK) return rc;
-    if (paired && (rc = grow_run_scratch(h, &h->pairs.d_pguide, &h->pairs.pguide_capacity, pbytes, pbytes, s)) != PF_OK) return rc;
+    if (paired) PF_HIP(h, h->pairs.blk.dev.reserve(pairs_bytes, pairs_bytes * 2, Wait::on(s)));
+    if (paired) PF_HIP(h, h->pairs.d_pguide.reserve(pbytes, pbytes, Wait::on(s)));
     rc = begin_pinned(h, dev_init_pharm_com, dev_noise0, dev_pin_flags, dev_pin_x, dev_pin_h, feat_norm_constant, seeded, stream);
     if (rc) return rc;
-    pfrestr::pack(a, h->B, (uint32_t*)h->restr.stage);
-    if ((rc = staged_upload(h, h->restr, bytes, s)) != PF_OK) return rc;
+    pfrestr::pack(a, h->B, h->restr.stage.as<uint32_t>());
+    PF_HIP(h, h->restr.upload(bytes, s));
     h->n_restr = n;
     if (fielded) {                          // the armed field becomes this run's: one copy out of the staging buffer
-        if ((rc = staged_upload(h, h->field.blk, fl.upload_words() * 4, s)) != PF_OK) return rc;
+        PF_HIP(h, h->field.blk.upload(fl.upload_words() * 4, s));
         h->field.run = h->field.arm; h->field.on = true;
     }
     if (typed) {                            // the armed type guidance becomes this run's
-        if ((rc = staged_upload(h, h->types.blk, types_bytes, s)) != PF_OK) return rc;
-        PF_HIP(h, hipMemsetAsync(h->types.d_tguide, 0, tbytes, s));
+        PF_HIP(h, h->types.blk.upload(types_bytes, s));
+        PF_HIP(h, hipMemsetAsync(h->types.d_tguide.get(), 0, tbytes, s));
         h->types.run = h->types.arm; h->types.on = true;
     }
     if (paired) {                           // the armed pair restraints become this run's
-        if ((rc = staged_upload(h, h->pairs.blk, pairs_bytes, s)) != PF_OK) return rc;
+        PF_HIP(h, h->pairs.blk.upload(pairs_bytes, s));
         h->pairs.n_run = h->pairs.n_arm; h->pairs.on = true;
     }
-    PF_HIP(h, hipMemsetAsync(h->d_guide, 0, gbytes, s));              // (the zero g_eps_h of every step's VJP; nothing writes it)
+    PF_HIP(h, hipMemsetAsync(h->d_guide.get(), 0, gbytes, s));              // (the zero g_eps_h of every step's VJP; nothing writes it)
     h->guide_scale = guide_scale; h->guide_clip = guide_clip;
     h->guide_traj_energy = nullptr;
     h->run = RUN_GUIDED; h->guide_have = false; h->field.have = false; h->types.have = false; h->pairs.have = false;
@@ -3620,7 +3512,7 @@ static const auto guide_shared = [](const pf_handle* h, const GuideStep& st, aut
 static GuideParams guide_params(const pf_handle* h, const GuideStep& st) {
     GuideParams q{};
     const pfrestr::RestrLayout rl(h->B, h->n_restr);
-    const int32_t* base = (const int32_t*)h->restr.dev;
+    const int32_t* base = h->restr.dev.as<const int32_t>();
     q.restr_ptr = base + rl.ptr(); q.restr_kind = base + rl.kind(); q.restr_center = base + rl.center();
     q.restr_p = (const float*)(base + rl.p()); q.restr_r = (const float*)(base + rl.r()); q.restr_w = (const float*)(base + rl.w());
     q.com_init = h->d_com_init;
@@ -3630,7 +3522,7 @@ static GuideParams guide_params(const pf_handle* h, const GuideStep& st) {
 static FieldParams field_params(const pf_handle* h, const GuideStep& st) {
     FieldParams q{};
     const pffield::FieldLayout fl(h->Np, h->B, h->field.run.n, h->cfg.pharm_nf);
-    float* fb = (float*)h->field.blk.dev;
+    float* fb = h->field.blk.dev.as<float>();
     q.ph_xt = (const float4*)(fb + fl.ph_xt()); q.atom_r = fb + fl.atom_r(); q.ph_ptr = (const int*)(fb + fl.ph_ptr());
     q.match = (const int*)(fb + fl.match()); q.dist = fb + fl.dist(); q.E3 = fb + fl.e3();
     const auto& r = h->field.run;
@@ -3646,7 +3538,7 @@ static FieldTypeParams field_type_params(const pf_handle* h, const GuideStep& st
 static TypeParams type_params(const pf_handle* h, const GuideStep& st, const float* e3) {
     TypeParams q{};
     const pftypes::TypesLayout tl(h->B, h->types.run.n);
-    const int32_t* tb = (const int32_t*)h->types.blk.dev;
+    const int32_t* tb = h->types.blk.dev.as<const int32_t>();
     q.ptr = tb + tl.ptr(); q.center = tb + tl.center(); q.type = tb + tl.type();
     q.p = (const float*)(tb + tl.p()); q.r = (const float*)(tb + tl.r()); q.w = (const float*)(tb + tl.w());
     q.sharp = h->types.run.type_sharpness; q.ep_feat = st.ep_feat;
@@ -3657,12 +3549,12 @@ static TypeParams type_params(const pf_handle* h, const GuideStep& st, const flo
 static PairParams pair_params(const pf_handle* h, const GuideStep& st) {
     PairParams q{};
     const pfpairs::PairsLayout pl(h->B, h->pairs.n_run);
-    const int32_t* pb = (const int32_t*)h->pairs.blk.dev;
+    const int32_t* pb = h->pairs.blk.dev.as<const int32_t>();
     q.ptr = pb + pl.ptr(); q.i = pb + pl.i(); q.j = pb + pl.j();
     q.lo = (const float*)(pb + pl.lo()); q.hi = (const float*)(pb + pl.hi()); q.w = (const float*)(pb + pl.w());
     q.flags = h->d_pin_flags; q.pin_x = h->d_pin_x;
     const pfpairs::PairWork pw = pair_work(h);
-    q.g_pair = (float*)h->pairs.d_pguide + pw.g_pair(); q.E_pair = (float*)h->pairs.d_pguide + pw.E_pair();
+    q.g_pair = h->pairs.d_pguide.as<float>() + pw.g_pair(); q.E_pair = h->pairs.d_pguide.as<float>() + pw.E_pair();
     guide_shared(h, st, q);
     return q;
 }
@@ -3702,7 +3594,7 @@ int pf_denoise_step_guided(pf_handle* h, const pf_step_coef* coef, const pf_pin_
     rc = run_dynamics(h, h->d_eps_h, h->d_eps_x, s, &coef->t, true, nullptr);
     h->t_have_fwd = false;                      // (the kept forward is this step's: d_t does not hold its timestep)
     if (rc) return rc;
-    const GuideStep st{gc->alpha_t, gc->sigma_t, ep_coord, ep_feat, guide_work(h), (float*)h->d_guide, type_work(h), h->types.on ? (float*)h->types.d_tguide : nullptr};
+    const GuideStep st{gc->alpha_t, gc->sigma_t, ep_coord, ep_feat, guide_work(h), h->d_guide.as<float>(), type_work(h), h->types.on ? h->types.d_tguide.as<float>() : nullptr};
     float *const g0 = st.g + st.gw.g0(), *const jx = st.g + st.gw.jx();
     const GuideParams gq = guide_params(h, st);
     pfk_guide_grad(&sp, &gq, s);
@@ -3773,7 +3665,7 @@ int pf_debug_last_guidance(pf_handle* h, float* dev_g0, float* dev_grad, float* 
     hipStream_t s = (hipStream_t)stream;
     const size_t nb = (size_t)h->Nf * 3 * 4;
     const pfrestr::GuideWork gw = guide_work(h);
-    const float* g = (const float*)h->d_guide;
+    const float* g = h->d_guide.as<const float>();
     if (dev_g0 && nb) PF_HIP(h, hipMemcpyAsync(dev_g0, g + gw.g0(), nb, hipMemcpyDeviceToDevice, s));
     if (dev_grad && nb) PF_HIP(h, hipMemcpyAsync(dev_grad, g + gw.grad(), nb, hipMemcpyDeviceToDevice, s));
     if (dev_shift && nb) PF_HIP(h, hipMemcpyAsync(dev_shift, g + gw.shift(), nb, hipMemcpyDeviceToDevice, s));
@@ -3795,8 +3687,8 @@ int pf_guide_field_next(pf_handle* h, const float* host_atom_r, float w_clash, c
     const int n = pffield::n_features(a, h->B);
     const pffield::FieldLayout fl(h->Np, h->B, n, h->cfg.pharm_nf);
     h->field.armed = false;                 // (a field armed before and not yet used is replaced, also when the allocation below fails)
-    if ((rc = staged_reserve(h, h->field.blk, fl.upload_words() * 4)) != PF_OK) return rc;
-    pffield::pack(a, h->B, h->Np, h->cfg.pharm_nf, (uint32_t*)h->field.blk.stage);
+    PF_HIP(h, h->field.blk.reserve(fl.upload_words() * 4));
+    pffield::pack(a, h->B, h->Np, h->cfg.pharm_nf, h->field.blk.stage.as<uint32_t>());
     h->field.arm = {n, w_clash, w_comp, kappa, type_sharpness};
     h->field.armed = true;
     return PF_OK;
@@ -3815,8 +3707,8 @@ int pf_guide_types_next(pf_handle* h, const int32_t* host_ptr, const int32_t* ho
     if (!pftypes::validate(a, h->B, h->h_pharm_ptr.data(), h->cfg.pharm_nf, msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
     const int n = pftypes::n_restraints(a, h->B);
     h->types.armed = false;                 // (an arming not yet used is replaced, also when the allocation below fails)
-    if ((rc = staged_reserve(h, h->types.blk, pftypes::TypesLayout(h->B, n).words() * 4)) != PF_OK) return rc;
-    pftypes::pack(a, h->B, (uint32_t*)h->types.blk.stage);
+    PF_HIP(h, h->types.blk.reserve(pftypes::TypesLayout(h->B, n).words() * 4));
+    pftypes::pack(a, h->B, h->types.blk.stage.as<uint32_t>());
     h->types.arm = {n, feat_scale, feat_clip, type_sharpness, comp_types != 0, unmatched};
     h->types.armed = true;
     return PF_OK;
@@ -3829,7 +3721,7 @@ int pf_debug_last_type_guidance(pf_handle* h, float* dev_g0_h, float* dev_grad_h
     hipStream_t s = (hipStream_t)stream;
     const size_t nb = (size_t)h->Nf * (size_t)h->cfg.pharm_nf * 4;
     const pfrestr::TypeWork tw = type_work(h);
-    const float* t = (const float*)h->types.d_tguide;
+    const float* t = h->types.d_tguide.as<const float>();
     if (dev_g0_h && nb) {
         if (h->types.live) PF_HIP(h, hipMemcpyAsync(dev_g0_h, t + tw.g0_h(), nb, hipMemcpyDeviceToDevice, s));
         else PF_HIP(h, hipMemsetAsync(dev_g0_h, 0, nb, s));
@@ -3855,8 +3747,8 @@ int pf_guide_pairs_next(pf_handle* h, const int32_t* host_ptr, const int32_t* ho
     if (!pfpairs::validate(a, h->B, h->h_pharm_ptr.data(), msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
     const int n = pfpairs::n_restraints(a, h->B);
     h->pairs.armed = false;                 // (an arming not yet used is replaced, also when the allocation below fails)
-    if ((rc = staged_reserve(h, h->pairs.blk, pfpairs::PairsLayout(h->B, n).words() * 4)) != PF_OK) return rc;
-    pfpairs::pack(a, h->B, (uint32_t*)h->pairs.blk.stage);
+    PF_HIP(h, h->pairs.blk.reserve(pfpairs::PairsLayout(h->B, n).words() * 4));
+    pfpairs::pack(a, h->B, h->pairs.blk.stage.as<uint32_t>());
     h->pairs.n_arm = n;
     h->pairs.armed = true;
     return PF_OK;
@@ -3868,7 +3760,7 @@ int pf_debug_last_pairs(pf_handle* h, float* dev_g_pair, float* dev_E_pair, pf_s
     if (!h->guide_have || !h->pairs.have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_pairs: no guided step with pair restraints on this batch");
     hipStream_t s = (hipStream_t)stream;
     const pfpairs::PairWork pw = pair_work(h);
-    const float* d = (const float*)h->pairs.d_pguide;
+    const float* d = h->pairs.d_pguide.as<const float>();
     if (dev_g_pair && h->Nf) PF_HIP(h, hipMemcpyAsync(dev_g_pair, d + pw.g_pair(), (size_t)h->Nf * 3 * 4, hipMemcpyDeviceToDevice, s));
     if (dev_E_pair && h->B) PF_HIP(h, hipMemcpyAsync(dev_E_pair, d + pw.E_pair(), (size_t)h->B * 4, hipMemcpyDeviceToDevice, s));
     return PF_OK;
@@ -3892,21 +3784,20 @@ int pf_sample_set_analyze(pf_handle* h, int32_t P, const int32_t* host_set_ptr, 
     const pfsset::SsetLayout lay(pl.P, pl.S);
     hipStream_t s = (hipStream_t)stream;
     pf_handle::SsetWork& w = h->sset;
-    int rc;
     const size_t blk_bytes = lay.words() * 4, sim_bytes = (size_t)pl.sim_floats * 4;
-    if ((rc = staged_reserve(h, w.blk, blk_bytes)) != PF_OK) return rc;
-    if ((rc = grow_run_scratch(h, &w.blk.dev, &w.blk.capacity, blk_bytes, blk_bytes * 2, s)) != PF_OK) return rc;
-    if (!dev_sim && (rc = grow_run_scratch(h, &w.d_sim, &w.sim_capacity, sim_bytes, sim_bytes, s)) != PF_OK) return rc;
-    if (!w.d_status) PF_HIP(h, hipMalloc((void**)&w.d_status, 4));
-    if (!w.status_host) PF_HIP(h, hipHostMalloc((void**)&w.status_host, 4, hipHostMallocDefault));
-    pfsset::pack(a, (uint32_t*)w.blk.stage);
-    if ((rc = staged_upload(h, w.blk, blk_bytes, s)) != PF_OK) return rc;
-    const int32_t* d = (const int32_t*)w.blk.dev;
+    PF_HIP(h, w.blk.reserve(blk_bytes));
+    PF_HIP(h, w.blk.dev.reserve(blk_bytes, blk_bytes * 2, Wait::on(s)));
+    if (!dev_sim) PF_HIP(h, w.d_sim.reserve(sim_bytes, sim_bytes, Wait::on(s)));
+    PF_HIP(h, w.d_status.reserve(4, 4, Wait::none()));
+    PF_HIP(h, w.status_host.reserve(4, 4, Wait::none()));
+    pfsset::pack(a, w.blk.stage.as<uint32_t>());
+    PF_HIP(h, w.blk.upload(blk_bytes, s));
+    const int32_t* d = w.blk.dev.as<const int32_t>();
     SsetParams q{};
     q.P = pl.P; q.S = pl.S; q.N = pl.N; q.nf = h->cfg.pharm_nf;
     q.set_ptr = d + lay.set_ptr(); q.sim_ptr = d + lay.sim_ptr(); q.work_ptr = d + lay.work_ptr(); q.center_ptr = d + lay.center_ptr();
     q.x = dev_x; q.type = dev_type; q.inv_2s2 = pl.inv_2s2; q.tol2 = pl.tol2; q.threshold = pl.threshold;
-    q.sim = dev_sim ? dev_sim : (float*)w.d_sim;
+    q.sim = dev_sim ? dev_sim : w.d_sim.as<float>();
     q.support = dev_support; q.label = dev_label; q.centroid = dev_centroid; q.size = dev_size; q.n_clusters = dev_n_clusters;
     q.cons_x = dev_cons_x; q.cons_cnt = dev_cons_cnt; q.status = w.d_status;
     PF_HIP(h, hipMemsetAsync(w.d_status, 0, 4, s));
@@ -3930,7 +3821,7 @@ int pf_debug_last_field(pf_handle* h, float* dev_E3, pf_stream stream) {
     if (!h->guide_have || !h->field.have) PF_FAIL(h, PF_ERR_STATE, "pf_debug_last_field: no guided step with a pocket field on this batch");
     if (!dev_E3) PF_FAIL(h, PF_ERR_ARG, "pf_debug_last_field: null argument");
     const pffield::FieldLayout fl(h->Np, h->B, h->field.run.n, h->cfg.pharm_nf);
-    if (h->B) PF_HIP(h, hipMemcpyAsync(dev_E3, (const float*)h->field.blk.dev + fl.e3(), (size_t)h->B * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (h->B) PF_HIP(h, hipMemcpyAsync(dev_E3, h->field.blk.dev.as<const float>() + fl.e3(), (size_t)h->B * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PF_OK;
 }
 
@@ -3959,13 +3850,8 @@ int pf_train_set_family(pf_handle* h, int32_t family) {
     if (h->train_wide != (family == PF_TRAIN_FAMILY_WIDE)) {
         // the leg that is left gives its workspace back (several GB at a training batch); it is allocated again on that leg's next use
         (void)hipDeviceSynchronize();
-        if (family == PF_TRAIN_FAMILY_WIDE) {
-            if (h->d_tws) { (void)hipFree(h->d_tws); h->d_tws = nullptr; h->tws_capacity = 0; }
-            if (h->d_tA) { (void)hipFree(h->d_tA); h->d_tA = nullptr; h->tA_capacity = 0; }
-        } else {
-            if (h->d_wtws) { (void)hipFree(h->d_wtws); h->d_wtws = nullptr; h->wtws_capacity = 0; }
-            if (h->d_wtA) { (void)hipFree(h->d_wtA); h->d_wtA = nullptr; h->wtA_capacity = 0; }
-        }
+        if (family == PF_TRAIN_FAMILY_WIDE) { h->d_tws.release(); h->d_tA.release(); }
+        else { h->d_wtws.release(); h->d_wtA.release(); }
     }
     h->train_wide = family == PF_TRAIN_FAMILY_WIDE;
     h->t_have_fwd = false;                       // a forward of the other family is not this backward's
@@ -3979,7 +3865,7 @@ int pf_train_set_input_grads(pf_handle* h, int32_t on) {
     if (on != 0 && on != 1) PF_FAIL(h, PF_ERR_ARG, "pf_train_set_input_grads: on must be 0 or 1");
     if (!on && h->d_gdiff) {
         (void)hipDeviceSynchronize();            // a pass in flight may still write the rows
-        (void)hipFree(h->d_gdiff); h->d_gdiff = nullptr; h->gdiff_capacity = 0;
+        h->d_gdiff.release();
     }
     h->train_in_grads = on != 0;                 // (a kept forward stays good: the forward is the same with the switch on or off)
     return PF_OK;
@@ -4093,6 +3979,13 @@ int pf_debug_xchg_timeouts(pf_handle* h, int32_t* n) {
     return PF_OK;
 }
 
+int pf_debug_live_memory(int64_t* n_allocations, int64_t* n_bytes) {
+    if (!n_allocations || !n_bytes) return PF_ERR_ARG;
+    *n_allocations = pfmem::HipRuntime::live_allocations.load();
+    *n_bytes = pfmem::HipRuntime::live_bytes.load();
+    return PF_OK;
+}
+
 int pf_debug_chain(pf_handle* h, int32_t kind, int32_t layer, int32_t sub, int32_t n_rows, const float* dev_s_in, const float* dev_v_in,
                    float* dev_s_out, float* dev_v_out, pf_stream stream) {
     if (h && !h->spec) PF_FAIL(h, PF_ERR_ARG, "%s: specialised to n_hidden_scalars 128 / vector_size 16", __func__);
@@ -4156,7 +4049,10 @@ static int profile_read_range(pf_handle* h, int k0, int k1, double* total_ms, in
         double tot = 0.0;
         for (size_t i = 0; i < h->prof_used[k]; ++i) {
             float ms = 0.f;
-            PF_HIP(h, hipEventElapsedTime(&ms, h->prof_ev[k][i].first, h->prof_ev[k][i].second));
+            hipEvent_t a, b;
+            PF_HIP(h, h->prof_ev[k][i].first.get(&a));
+            PF_HIP(h, h->prof_ev[k][i].second.get(&b));
+            PF_HIP(h, hipEventElapsedTime(&ms, a, b));
             tot += ms;
         }
         total_ms[k - k0] = tot;

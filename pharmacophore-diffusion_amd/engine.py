@@ -1021,6 +1021,15 @@ class PfEngine:
         self._ck(self.lib.pf_debug_xchg_timeouts(self._h, ctypes.byref(r)), "pf_debug_xchg_timeouts")
         return int(r.value)
 
+    @staticmethod
+    def live_memory():
+        """(allocations, bytes) this process holds through the library's handles right now, device and pinned memory together
+        (pf_debug_live_memory): every engine counts, other processes on the device do not."""
+        n, b = ctypes.c_int64(), ctypes.c_int64()
+        if L.load().pf_debug_live_memory(ctypes.byref(n), ctypes.byref(b)) < 0:
+            raise L.PfError("pf_debug_live_memory failed")
+        return int(n.value), int(b.value)
+
     def xchg_fault(self, drop_word: bool, poll_max: int = 0):
         """Diagnostic (pf_debug_xchg_fault): make the merged launch's producers skip one exchange word / shorten the poll bound."""
         self._ck(self.lib.pf_debug_xchg_fault(self._h, int(bool(drop_word)), int(poll_max)), "pf_debug_xchg_fault")
