@@ -67,6 +67,13 @@ _FLAGS = [
     ('--min_support', dict(type=float, default=None, metavar='F', help='with --consensus / --consensus_of: consensus.xyz lists the centers found in at least this share of a cluster\'s members (default 0.5)')),
     ('--keep_diverse', dict(type=int, default=None, metavar='K', help='write only K samples chosen by max-min selection on the similarity (each next one the least similar to those chosen, starting from the largest cluster\'s centroid); with --keep_best: the best N first, then K diverse among them')),
     ('--consensus_of', dict(type=Path, default=None, metavar='FILE', help='no sampling, no receptor_file, no checkpoint: analyse the frames of this file (pharms.xyz format, all of one pocket) as --consensus does and write consensus.xyz and clusters.tsv')),
+    ('--screen_library', dict(type=Path, default=None, metavar='FILE', help='screen a pharmacophore library (the frames of this file, pharms.xyz format, 1 to 32 centers each) against the written samples, or with --consensus against the consensus pharmacophores: every entry is superposed rigidly onto every query (proper rotations, exact types, at most 16 query centers); writes hits.tsv (query, rank, entry name, sim, matched, n_q) and hits_aligned.xyz (the hit entries in the pocket\'s frame, one frame per hit)')),
+    ('--screen_top', dict(type=int, default=None, metavar='K', help='with --screen_library: hits listed per query (default 10)')),
+    ('--screen_min_match', dict(type=float, default=None, metavar='F', help='with --screen_library: only entries that match at least this share (0..1) of the query\'s centers qualify (default 0)')),
+    ('--screen_sigma', dict(type=float, default=None, metavar='A', help='with --screen_library: width of the Gaussians of the similarity, angstroms (default 1.0)')),
+    ('--screen_tolerance', dict(type=float, default=None, metavar='A', help='with --screen_library: a query center is matched by a same-type entry center within this distance (default 1.5)')),
+    ('--screen_refine', dict(type=int, default=None, metavar='R', help='with --screen_library: refinement rounds behind the best three-point superposition, 0..16 (default 4)')),
+    ('--screen_queries', dict(type=Path, default=None, metavar='FILE', help='with --screen_library; no sampling, no receptor_file, no checkpoint: the frames of this file (pharms.xyz format) are the queries')),
     ('--metrics', dict(action='store_true', help='print the validity of the samples against receptor pharmacophore features')),
     ('--use_ema', dict(action='store_true', help="sample from the checkpoint's EMA weights (its 'ema_state_dict', written by train.py with ema_decay set) instead of the training weights")),
 ]
@@ -75,7 +82,7 @@ _FLAGS = [
 def parse_arguments(argv=None):
     parser = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     argv = sys.argv[1:] if argv is None else list(argv)
-    file_only = any(str(v) == '--consensus_of' or str(v).startswith('--consensus_of=') for v in argv)
+    file_only = any(str(v) == f or str(v).startswith(f + '=') for v in argv for f in ('--consensus_of', '--screen_queries'))
     for flag, kw in _FLAGS:
         if flag == 'receptor_file' and file_only:           # --consensus_of reads no receptor: the positional may be left out
             kw = dict(kw, nargs='?', default=None)
@@ -99,6 +106,49 @@ def parse_arguments(argv=None):
     a.min_support = 0.5 if a.min_support is None else a.min_support
     if a.keep_diverse is not None and a.keep_diverse < 1:
         parser.error(f'--keep_diverse must be at least 1, got {a.keep_diverse}')
+    for flag in ('screen_top', 'screen_min_match', 'screen_sigma', 'screen_tolerance', 'screen_refine', 'screen_queries'):
+        if getattr(a, flag) is not None and a.screen_library is None:
+            parser.error(f'--{flag} needs --screen_library')
+    a.screen_top = 10 if a.screen_top is None else a.screen_top
+    a.screen_min_match = 0.0 if a.screen_min_match is None else a.screen_min_match
+    a.screen_sigma = 1.0 if a.screen_sigma is None else a.screen_sigma
+    a.screen_tolerance = 1.5 if a.screen_tolerance is None else a.screen_tolerance
+    a.screen_refine = 4 if a.screen_refine is None else a.screen_refine
+    if a.screen_top < 1:
+        parser.error(f'--screen_top must be at least 1, got {a.screen_top}')
+    if not 0.0 <= a.screen_min_match <= 1.0:
+        parser.error(f'--screen_min_match must lie in 0..1, got {a.screen_min_match}')
+    if not (0 < a.screen_sigma < float('inf')):
+        parser.error(f'--screen_sigma must be positive and finite, got {a.screen_sigma}')
+    if not (0 <= a.screen_tolerance < float('inf')):
+        parser.error(f'--screen_tolerance must be finite and not negative, got {a.screen_tolerance}')
+    if not 0 <= a.screen_refine <= 16:
+        parser.error(f'--screen_refine must lie in 0..16, got {a.screen_refine}')
+    a.screen_lib, a.screen_query_frames = None, None
+    if a.screen_library is not None:
+        from pharmacoforge_amd.analysis import PharmacophoreLibrary, read_pharmacophores
+        try:
+            a.screen_lib = PharmacophoreLibrary.from_file(a.screen_library)
+            if a.screen_queries is not None:
+                a.screen_query_frames = read_pharmacophores(a.screen_queries)
+        except (OSError, ValueError) as e:
+            parser.error(f'--screen_library / --screen_queries: {e}')
+        if len(a.screen_lib) == 0:
+            parser.error(f'--screen_library: no frame of {a.screen_library} has 1 to 32 centers')
+        if a.visualize_trajectory or a.score_pharmacophores is not None:
+            parser.error('--screen_library together with --visualize_trajectory / --score_pharmacophores: no pharms.xyz is written to screen')
+    if a.screen_query_frames is not None:
+        given = [f for f in ('receptor_file', '--ckpt', '--model_dir', '--ref_ligand_file', '--residue_list', '--samples_per_pocket', '--pharm_sizes',
+                             '--pinned_centers', '--restraints', '--type_restraints', '--pair_restraints', '--min_separation', '--avoid_clashes',
+                             '--seed_pharmacophore', '--sample_steps', '--score_samples', '--use_ref_lig_com', '--metrics', '--use_ema', '--consensus',
+                             '--consensus_of', '--keep_diverse')
+                 if getattr(a, f.lstrip('-')) not in (parser.get_default(f.lstrip('-')), None)]
+        if given:
+            parser.error(f'--screen_queries samples nothing and reads no receptor or checkpoint: {" ".join(given)} make no sense with it')
+        a.consensus_frames = None
+        return a
+    if a.screen_library is not None and a.consensus_of is not None:
+        parser.error('--screen_library together with --consensus_of: screen the consensus.xyz it writes with --screen_queries')
     if a.keep_diverse is not None and a.visualize_trajectory:
         parser.error('--keep_diverse together with --visualize_trajectory: trajectories are written per sample index')
     if a.keep_diverse is not None and (a.score_pharmacophores is not None or a.consensus_of is not None):
@@ -380,11 +430,40 @@ def write_consensus(pocket_dir, sset, picks=None):
     (pocket_dir / 'clusters.tsv').write_text('\n'.join(rows) + '\n')
 
 
+def screen_and_write(pfa, pocket_dir, queries, labels, args, engine=None):
+    """--screen_library: the library against `queries` ((positions, types) pairs, named by `labels`) on the engine's device, or on
+    the host without one; writes hits.tsv and hits_aligned.xyz and returns the hit lists.  Queries outside 1..16 centers are left
+    out (reported)."""
+    keep = [k for k, (x, _) in enumerate(queries) if 1 <= len(x) <= 16]
+    if len(keep) < len(queries):
+        print(f'--screen_library: {len(queries) - len(keep)} queries outside 1..16 centers are not screened')
+    hits = pfa.screen_library([queries[k] for k in keep], args.screen_lib, engine, top_k=args.screen_top, min_match=args.screen_min_match,
+                              sigma=args.screen_sigma, tolerance=args.screen_tolerance, refine=args.screen_refine)
+    rows, frames = ['query\trank\tentry\tsim\tmatched\tn_q'], []
+    for k, hs in zip(keep, hits):
+        for rank, h in enumerate(hs):
+            rows.append(f'{labels[k]}\t{rank}\t{h.name}\t{h.sim:.6f}\t{h.n_matched}\t{len(queries[k][0])}')
+            frames.append(h.to_xyz_file())
+    (pocket_dir / 'hits.tsv').write_text('\n'.join(rows) + '\n')
+    (pocket_dir / 'hits_aligned.xyz').write_text(''.join(frames))
+    if args.screen_lib.dropped:
+        print(f'--screen_library: {args.screen_lib.dropped} frames outside 1..32 centers were dropped')
+    return hits
+
+
 def main(argv=None):
     import pharmacoforge_amd as pfa
     from pharmacoforge_amd.pocket_io import get_prot_atom_ph_type_maps, process_ligand_and_pocket
 
     args = parse_arguments(argv)
+    if args.screen_query_frames is not None:    # no sampling, no receptor, no checkpoint: the frames of the file are the queries
+        name = args.receptor_name or args.screen_queries.name.split('.')[0]
+        pocket_dir = Path(args.output_dir) / name
+        pocket_dir.mkdir(parents=True, exist_ok=True)
+        engine = pfa.PfEngine(pharm_nf=len(pfa.SampledPharmacophore.type_idx_to_elem)) if torch.cuda.is_available() else None
+        hits = screen_and_write(pfa, pocket_dir, args.screen_query_frames, list(range(len(args.screen_query_frames))), args, engine)
+        print(f'{name}: {len(args.screen_query_frames)} queries against {len(args.screen_lib)} library entries, {sum(len(h) for h in hits)} hits listed')
+        return
     if args.consensus_frames is not None:       # no sampling, no receptor, no checkpoint: the frames of the file as one set
         name = args.receptor_name or args.consensus_of.name.split('.')[0]
         pocket_dir = Path(args.output_dir) / name
@@ -526,6 +605,15 @@ def main(argv=None):
             ph.traj_to_xyz(pocket_dir / f'pharm_{i}_traj.xyz')
     else:
         (pocket_dir / 'pharms.xyz').write_text(''.join(ph.to_xyz_file() for ph in pharms))
+    if args.screen_lib is not None:
+        if args.consensus:                       # the consensus pharmacophores as consensus.xyz lists them
+            keep = lambda c: [i for i in range(c.types.shape[0]) if float(c.support[i]) >= args.min_support]
+            queries = [(c.positions[keep(c)], c.types[keep(c)]) for c in sset.clusters]
+            labels = [f'cluster_{c.cluster}' for c in sset.clusters]
+        else:                                    # the samples as pharms.xyz holds them
+            queries, labels = [ph.as_written() for ph in pharms], list(range(len(pharms)))
+        hits = screen_and_write(pfa, pocket_dir, queries, labels, args, model.dynamics.engine())
+        print(f'{name}: {len(queries)} queries against {len(args.screen_lib)} library entries, {sum(len(h) for h in hits)} hits listed')
     if args.metrics:
         print(pfa.SampleAnalyzer().analyze(pharms))
 

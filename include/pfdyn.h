@@ -480,6 +480,45 @@ int pf_sample_set_analyze(pf_handle* h, int32_t P, const int32_t* host_set_ptr /
                           int32_t* dev_centroid /*[S]*/, int32_t* dev_size /*[S]*/, int32_t* dev_n_clusters /*[P]*/,
                           float* dev_cons_x /*[N,3]*/, int32_t* dev_cons_cnt /*[N]*/, pf_stream stream);
 
+/* -- pharmacophore alignment: superpose library entries onto queries and rank them (no reference counterpart) --------
+ * A query is (x [n_q,3], t [n_q]) with 1 <= n_q <= 16, a library entry (y [n_l,3], u [n_l]) with 1 <= n_l <= 32; types are integers
+ * in [0, pharm_nf) and match exactly.  Options: sigma > 0 (Gaussian width, 1.0), tolerance >= 0 (matching distance, 1.5), refine in
+ * 0..16 (refinement rounds, 4), min_area > 0 (smallest |cross product| of a triplet, 1.0 A^2).  Per (query, entry) pair:
+ *   seeds        in lexicographic order of (i, j, k, a, b, c): every query triplet i < j < k and ordered triple of distinct entry
+ *                centers (a, b, c) with u_a = t_i, u_b = t_j, u_c = t_k; | d(x_i,x_j) - d(y_a,y_b) | <= 2 tolerance and likewise for
+ *                (i,k)/(a,c) and (j,k)/(b,c); |(x_j - x_i) x (x_k - x_i)| >= min_area and |(y_b - y_a) x (y_c - y_a)| >= min_area
+ *                (collinear triplets fix no rotation).  A seed's transform (R, s) is the proper rotation (det +1) and translation
+ *                that minimise sum |R y + s - x|^2 over its three correspondences
+ *   overlap      O = sum_p sum_q [t_p == u_q] exp(-|x_p - (R y_q + s)|^2 / (2 sigma^2)), the typed overlap of the sample sets;
+ *                the best seed has the largest O, on a tie the earliest in the enumeration order
+ *   refinement   from the best seed up to `refine` rounds: weights w_pq = [t_p == u_q] exp(-|x_p - (R y_q + s)|^2 / (2 sigma^2)) at
+ *                the current transform, the weighted least-squares proper rotation and translation over all same-type pairs, the
+ *                new overlap O'; accepted when O' >= O, otherwise the refinement stops
+ *   outputs      sim = O / (O_qq + O_ll - O), at most 1 (O_qq, O_ll: the self overlaps); n_matched = the number of query centers
+ *                with a same-type entry center within tolerance (<=) after the transform; n_seeds; the transform as 12 floats, R
+ *                row-major then s, mapping the entry's frame into the query's.  n_seeds = 0 (every pharmacophore of one or two
+ *                centers, every entry without three non-collinear type-compatible centers): sim = 0, n_matched = 0, the identity
+ * The result is the best of a discrete seed set plus a local refinement, not a global optimum.  Rotations are proper: a mirror
+ * image is a different pharmacophore.
+ * Q queries against L entries per call, every pair.  HOST arrays q_ptr [Q+1] and l_ptr [L+1] (query k owns the centers
+ * [q_ptr[k], q_ptr[k+1]) of dev_qx / dev_qtype, entries likewise), copied before the call returns.  DEVICE arrays: in dev_qx [Nq,3],
+ * dev_qtype [Nq] int32, dev_lx [Nl,3], dev_ltype [Nl]; out dev_sim, dev_matched, dev_n_seeds [Q,L] row-major and dev_transform
+ * [Q,L,12] (NULL: not written; the other outputs are the same either way).
+ * Validation on the host before anything is launched (csrc/pf_align.h): Q, L >= 1, Q * L <= 2^24, pointers start at 0 and do not
+ * decrease, center counts within the caps, finite options in range -- a failure is PF_ERR_ARG with a message.  The types are on the
+ * device: a kernel counts those outside [0, pharm_nf), the host reads the count behind the launches (the call waits for the
+ * stream) and reports PF_ERR_ARG; the outputs then mean nothing.
+ * The call needs no committed weights and no bound batch, owns its workspace (grown on demand, freed by pf_destroy) and touches no
+ * run state: between two sampling runs, inside one, or while a batch is bound, it changes nothing those see.  fp32 throughout;
+ * every output has the same bits on every run, and a pair's outputs do not depend on the other pairs of the call. */
+#define PF_ALIGN_MAX_QUERY_CENTERS 16
+#define PF_ALIGN_MAX_ENTRY_CENTERS 32
+typedef struct pf_align_opts { float sigma; float tolerance; int32_t refine; float min_area; } pf_align_opts;
+int pf_pharm_align(pf_handle* h, int32_t Q, const int32_t* host_q_ptr /*[Q+1]*/, int32_t L, const int32_t* host_l_ptr /*[L+1]*/,
+                   const float* dev_qx /*[Nq,3]*/, const int32_t* dev_qtype /*[Nq]*/, const float* dev_lx /*[Nl,3]*/,
+                   const int32_t* dev_ltype /*[Nl]*/, const pf_align_opts* opts, float* dev_sim /*[Q,L]*/, int32_t* dev_matched /*[Q,L]*/,
+                   int32_t* dev_n_seeds /*[Q,L]*/, float* dev_transform /*[Q,L,12] or NULL*/, pf_stream stream);
+
 /* -- seeded sampling: start the reverse process from a given pharmacophore (partial diffusion; no reference counterpart) ----------
  * The given sample is noised forward to an intermediate level a, 1 <= a <= T, and only the reverse steps a-1 .. 0 are run: a small
  * a gives close analogues of the seed, a large a loose ones.

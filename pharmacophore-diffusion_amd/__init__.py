@@ -16,11 +16,13 @@ try:  # host-side mirror of the reference API (needs only torch)
     from .graph import PocketGraph, batch, unbatch, build_initial_complex_graph, copy_graph  # noqa: F401
     from .models import (GVP, GVPLayerNorm, GVPMultiEdgeConv, NoisePredictionBlock, PharmRecGVP,  # noqa: F401
                          PharmRecDynamicsGVP, PharmacophoreDiff, PredefinedNoiseSchedule, PharmSizeDistribution,
-                         FlatAdam, PocketField, TypeGuidance, model_from_config, sample_sets)
+                         FlatAdam, PocketField, TypeGuidance, model_from_config, sample_sets, screen_library)
     from .analysis import SampledPharmacophore, SampleAnalyzer, write_pharmacophore_file  # noqa: F401
     from .analysis import ConsensusPharmacophore, SampleSet  # noqa: F401
+    from .analysis import PharmacophoreLibrary, ScreenHit  # noqa: F401
     __all__ += ["PocketGraph", "batch", "unbatch", "build_initial_complex_graph", "copy_graph", "PharmRecDynamicsGVP",
                 "PharmacophoreDiff", "PocketField", "TypeGuidance", "FlatAdam", "PredefinedNoiseSchedule", "SampledPharmacophore", "SampleAnalyzer",
-                "model_from_config", "SampleSet", "ConsensusPharmacophore", "sample_sets"]
+                "model_from_config", "SampleSet", "ConsensusPharmacophore", "sample_sets", "PharmacophoreLibrary", "ScreenHit",
+                "screen_library"]
 except ImportError as _e:   # pragma: no cover  (only while the package is being bootstrapped)
     _host_api_error = _e

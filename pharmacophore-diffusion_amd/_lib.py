@@ -65,7 +65,12 @@ class PfSsetOpts(ctypes.Structure):
     _fields_ = [("sigma", ctypes.c_float), ("tolerance", ctypes.c_float), ("threshold", ctypes.c_float)]
 
 
+class PfAlignOpts(ctypes.Structure):
+    _fields_ = [("sigma", ctypes.c_float), ("tolerance", ctypes.c_float), ("refine", ctypes.c_int32), ("min_area", ctypes.c_float)]
+
+
 PF_SSET_MAX_SAMPLES, PF_SSET_MAX_CENTERS, PF_SSET_MAX_SIM = 1024, 64, 1 << 26
+PF_ALIGN_MAX_QUERY_CENTERS, PF_ALIGN_MAX_ENTRY_CENTERS, PF_ALIGN_MAX_PAIRS = 16, 32, 1 << 24
 PF_CLIP_NONE, PF_CLIP_NORM, PF_CLIP_VALUE = 0, 1, 2
 PF_OPTIM_STATE_BYTES = 64
 
@@ -116,6 +121,7 @@ SYMBOLS = {
     "pf_guide_pairs_next": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "pf_debug_last_pairs": (ctypes.c_int, [_P, _P, _P, _P]),
     "pf_sample_set_analyze": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, ctypes.POINTER(PfSsetOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pf_pharm_align": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _P, _P, ctypes.POINTER(PfAlignOpts), _P, _P, _P, _P, _P]),
     "pf_dynamics_input_vjp": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "pf_param_count": (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     "pf_param_layout": (ctypes.c_int, [_P, _I32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),

@@ -581,3 +581,252 @@ def analyze_sample_set(samples, sigma=1.0, tolerance=1.5, threshold=0.5, min_sup
     return SampleSet(sim, sample_set_support(samples, tolerance), labels, centroids,
                      cluster_consensus(samples, labels, centroids, tolerance), counts,
                      dict(sigma=sigma, tolerance=tolerance, threshold=threshold, min_support=float(min_support)))
+
+
+# ---- pharmacophore alignment: superpose a library onto queries and rank it (include/pfdyn.h "pharmacophore alignment")
+# The CPU product path of pf_pharm_align, same definition, usable without a GPU: per (query, entry) pair the best of the three-point
+# superpositions by typed Gaussian overlap, refined by weighted least squares.  Proper rotations only (Horn's quaternion), types
+# match exactly; the result is the best of a discrete seed set plus a local refinement, not a global optimum.
+
+ALIGN_MAX_QUERY_CENTERS, ALIGN_MAX_ENTRY_CENTERS, ALIGN_MAX_PAIRS, ALIGN_MAX_REFINE = 16, 32, 1 << 24, 16
+
+
+def _align_options(sigma=1.0, tolerance=1.5, refine=4, min_area=1.0):
+    import math
+    sigma, tolerance, min_area = float(sigma), float(tolerance), float(min_area)
+    if not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError("sigma must be finite and > 0")
+    if not (math.isfinite(tolerance) and tolerance >= 0):
+        raise ValueError("tolerance must be finite and >= 0")
+    if int(refine) != refine or not 0 <= int(refine) <= ALIGN_MAX_REFINE:
+        raise ValueError(f"refine must be an integer in [0, {ALIGN_MAX_REFINE}]")
+    if not (math.isfinite(min_area) and min_area > 0):
+        raise ValueError("min_area must be finite and > 0")
+    return sigma, tolerance, int(refine), min_area
+
+
+def _align_item(s, dtype=torch.float32):
+    """(x [n, 3] dtype, types [n] int64) on the host from a SampledPharmacophore, a ConsensusPharmacophore or an (x, types) pair"""
+    if hasattr(s, "ph_coords"):
+        x, t = s.ph_coords, s.ph_feats_idxs
+    elif hasattr(s, "positions") and hasattr(s, "types"):
+        x, t = s.positions, s.types
+    else:
+        x, t = s
+    x = torch.as_tensor(x).detach().to("cpu", dtype).reshape(-1, 3)
+    t = torch.as_tensor(t).detach().to("cpu", torch.int64).reshape(-1)
+    if x.shape[0] != t.shape[0]:
+        raise ValueError(f"{x.shape[0]} positions for {t.shape[0]} types")
+    return x, t
+
+
+def _align_queries(queries, dtype=torch.float32):
+    out = [_align_item(s, dtype) for s in queries]
+    for k, (x, _) in enumerate(out):
+        if not 1 <= x.shape[0] <= ALIGN_MAX_QUERY_CENTERS:
+            raise ValueError(f"query {k} has {x.shape[0]} centers (1 to {ALIGN_MAX_QUERY_CENTERS} per query)")
+    return out
+
+
+def _horn_rotation(S):
+    """S [n, 3, 3] = sum w (y - yc)(x - xc)^T -> the proper rotations R [n, 3, 3] with x ~ R y: the unit quaternion is the
+    eigenvector of the largest eigenvalue of Horn's symmetric 4 x 4 matrix"""
+    Sxx, Sxy, Sxz, Syx, Syy, Syz, Szx, Szy, Szz = (S[:, a, b] for a in range(3) for b in range(3))
+    N = torch.stack([torch.stack([Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx], -1),
+                     torch.stack([Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz], -1),
+                     torch.stack([Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy], -1),
+                     torch.stack([Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz], -1)], -2)
+    w, x, y, z = torch.linalg.eigh(N)[1][:, :, -1].unbind(-1)              # eigenvalues ascend: the last column
+    return torch.stack([torch.stack([w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)], -1),
+                        torch.stack([2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)], -1),
+                        torch.stack([2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z], -1)], -2)
+
+
+def _align_fit(Y, X, W):
+    """weighted least squares over corresponding points Y, X [n, m, 3] with weights W [n, m]: R [n, 3, 3], s [n, 3], X ~ R Y + s"""
+    Wn = W / W.sum(dim=1, keepdim=True)
+    yc, xc = (Wn[..., None] * Y).sum(dim=1), (Wn[..., None] * X).sum(dim=1)
+    S = torch.einsum("nm,nma,nmb->nab", W, Y - yc[:, None], X - xc[:, None])
+    R = _horn_rotation(S)
+    return R, xc - torch.einsum("nab,nb->na", R, yc)
+
+
+def _align_overlap(x, y, same, R, s, inv_2s2):
+    d2 = ((x[None, :, None, :] - (torch.einsum("nab,lb->nla", R, y) + s[:, None, :])[:, None, :, :]) ** 2).sum(-1)
+    return (torch.exp(-d2 * inv_2s2) * same[None]).sum(dim=(1, 2)), d2
+
+
+def _align_seeds(x, t, y, u, tolerance, min_area):
+    """(query triplets [n, 3], entry triples [n, 3]) in enumeration order (i, j, k, a, b, c)"""
+    nq = t.shape[0]
+    dq, dl = torch.cdist(x, x), torch.cdist(y, y)
+    where = [torch.nonzero(u == k).reshape(-1) for k in range(int(max(t.max(), u.max())) + 1)] if nq else []
+    qs, ls = [], []
+    for i in range(nq):
+        for j in range(i + 1, nq):
+            for k in range(j + 1, nq):
+                A, B, C = where[int(t[i])], where[int(t[j])], where[int(t[k])]
+                if not (len(A) and len(B) and len(C)):
+                    continue
+                if torch.linalg.cross(x[j] - x[i], x[k] - x[i]).norm() < min_area:
+                    continue
+                a, b, c = (v.reshape(-1) for v in torch.meshgrid(A, B, C, indexing="ij"))
+                ok = (a != b) & (a != c) & (b != c)
+                ok &= ((dq[i, j] - dl[a, b]).abs() <= 2 * tolerance) & ((dq[i, k] - dl[a, c]).abs() <= 2 * tolerance) & ((dq[j, k] - dl[b, c]).abs() <= 2 * tolerance)
+                a, b, c = a[ok], b[ok], c[ok]
+                ok = torch.linalg.cross(y[b] - y[a], y[c] - y[a]).norm(dim=-1) >= min_area
+                if ok.any():
+                    ls.append(torch.stack([a[ok], b[ok], c[ok]], -1))
+                    qs.append(torch.tensor([i, j, k]).expand(ls[-1].shape[0], 3))
+    if not qs:
+        return torch.zeros(0, 3, dtype=torch.int64), torch.zeros(0, 3, dtype=torch.int64)
+    return torch.cat(qs), torch.cat(ls)
+
+
+def align_pair(x, t, y, u, sigma=1.0, tolerance=1.5, refine=4, min_area=1.0, dtype=torch.float64):
+    """One (query, entry) pair by the definition of pf_pharm_align, on the host at `dtype`: returns (sim, n_matched, n_seeds,
+    transform [12] = R row-major then s, entry frame -> query frame).  No seed: (0.0, 0, 0, identity)."""
+    sigma, tolerance, refine, min_area = _align_options(sigma, tolerance, refine, min_area)
+    (x, t), (y, u) = _align_item((x, t), dtype), _align_item((y, u), dtype)
+    qs, ls = _align_seeds(x, t, y, u, tolerance, min_area)
+    n = int(qs.shape[0])
+    if n == 0:
+        return 0.0, 0, 0, torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=dtype)
+    inv = 1.0 / (2.0 * sigma * sigma)
+    same = t[:, None] == u[None, :]
+    O, R, s = None, None, None
+    for c0 in range(0, n, 8192):
+        q_, l_ = qs[c0:c0 + 8192], ls[c0:c0 + 8192]
+        Rc, sc = _align_fit(y[l_], x[q_], torch.ones(q_.shape, dtype=dtype))
+        Oc, _ = _align_overlap(x, y, same, Rc, sc, inv)
+        m = int(torch.nonzero(Oc == Oc.max())[0])                           # the first of equals
+        if O is None or Oc[m] > O:
+            O, R, s = Oc[m], Rc[m], sc[m]
+    p_, q_ = torch.nonzero(same, as_tuple=True)
+    for _ in range(refine):
+        _, d2 = _align_overlap(x, y, same, R[None], s[None], inv)
+        w = torch.exp(-d2[0] * inv)[p_, q_]
+        R2, s2 = _align_fit(y[q_][None], x[p_][None], w[None])
+        O2, _ = _align_overlap(x, y, same, R2, s2, inv)
+        if not bool(O2[0] >= O):
+            break
+        O, R, s = O2[0], R2[0], s2[0]
+    eye = torch.eye(3, dtype=dtype)[None]
+    zero = torch.zeros(1, 3, dtype=dtype)
+    oqq = _align_overlap(x, x, t[:, None] == t[None, :], eye, zero, inv)[0][0]
+    oll = _align_overlap(y, y, u[:, None] == u[None, :], eye, zero, inv)[0][0]
+    _, d2 = _align_overlap(x, y, same, R[None], s[None], inv)
+    matched = int(((d2[0] <= tolerance * tolerance) & same).any(dim=1).sum())
+    return min(float(O / (oqq + oll - O)), 1.0), matched, n, torch.cat([R.reshape(-1), s])
+
+
+def align_pharmacophores(queries, library, sigma=1.0, tolerance=1.5, refine=4, min_area=1.0, dtype=torch.float32):
+    """Every query against every library entry on the host (the device path: PfEngine.align, PharmacophoreDiff.screen).  `queries`:
+    samples, ConsensusPharmacophore objects or (x, types) pairs of 1 to 16 centers; `library`: a PharmacophoreLibrary or such a
+    list, entries of 1 to 32 centers.  Returns a dict: sim [Q, L] (dtype), n_matched [Q, L], n_seeds [Q, L] int64, transform
+    [Q, L, 12]."""
+    opts = _align_options(sigma, tolerance, refine, min_area)
+    qs = _align_queries(queries, dtype)
+    lib = library if isinstance(library, PharmacophoreLibrary) else PharmacophoreLibrary(library)
+    Q, L = len(qs), len(lib)
+    out = dict(sim=torch.zeros(Q, L, dtype=dtype), n_matched=torch.zeros(Q, L, dtype=torch.int64), n_seeds=torch.zeros(Q, L, dtype=torch.int64),
+               transform=torch.zeros(Q, L, 12, dtype=dtype))
+    for a, (x, t) in enumerate(qs):
+        for b in range(L):
+            y, u = lib[b]
+            out["sim"][a, b], out["n_matched"][a, b], out["n_seeds"][a, b], out["transform"][a, b] = align_pair(x, t, y, u, *opts, dtype=dtype)
+    return out
+
+
+class PharmacophoreLibrary:
+    """Known pharmacophores to screen against: entries (positions [n, 3] fp32, type indices [n]) of 1 to 32 centers each, with
+    ``names``.  ``dropped``: how many offered entries lay outside 1..32 centers (from_dataset / from_file drop them and count;
+    the constructor refuses them).  ``to(device)`` packs the centers once and uploads them, for many screening calls."""
+
+    def __init__(self, entries, names=None, dropped=0):
+        self.entries = [_align_item(e) for e in entries]
+        for k, (x, _) in enumerate(self.entries):
+            if not 1 <= x.shape[0] <= ALIGN_MAX_ENTRY_CENTERS:
+                raise ValueError(f"entry {k} has {x.shape[0]} centers (1 to {ALIGN_MAX_ENTRY_CENTERS} per library entry)")
+        self.names = [str(n) for n in names] if names is not None else [f"entry_{k}" for k in range(len(self.entries))]
+        if len(self.names) != len(self.entries):
+            raise ValueError(f"{len(self.names)} names for {len(self.entries)} entries")
+        self.dropped = int(dropped)
+        self._packed = None
+
+    @staticmethod
+    def _kept(entries, names):
+        keep = [k for k, (x, _) in enumerate(entries) if 1 <= torch.as_tensor(x).reshape(-1, 3).shape[0] <= ALIGN_MAX_ENTRY_CENTERS]
+        return PharmacophoreLibrary([entries[k] for k in keep], [names[k] for k in keep], dropped=len(entries) - len(keep))
+
+    @classmethod
+    def from_file(cls, path):
+        """the frames of a file in the pharms.xyz format (read_pharmacophores), named <file stem>:<frame index>"""
+        frames = read_pharmacophores(path)
+        return cls._kept(frames, [f"{Path(path).stem}:{k}" for k in range(len(frames))])
+
+    @classmethod
+    def from_dataset(cls, dataset):
+        """each pocket's ligand pharmacophore of a ProteinPharmacophoreDataset (pharm_pos / pharm_feat), named by the pocket's
+        protein file where the dataset has the names, else pocket_<index>.  ``index``: the pocket index of every kept entry."""
+        entries, names = [], []
+        for i in range(int(dataset.pharm_idx.shape[0])):
+            ps, pe = (int(v) for v in dataset.pharm_idx[i])
+            entries.append((dataset.pharm_pos[ps:pe].float(), dataset.pharm_feat[ps:pe].long()))
+            have = getattr(dataset, "prot_file_names", None)
+            names.append(str(have[i]) if have and i < len(have) else f"pocket_{i}")
+        lib = cls._kept(entries, names)
+        lib.index = [k for k, (x, _) in enumerate(entries) if 1 <= x.shape[0] <= ALIGN_MAX_ENTRY_CENTERS]
+        return lib
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __getitem__(self, k):
+        return self.entries[k]
+
+    def packed(self):
+        """(x [N, 3] fp32, types [N] int32, ptr [L + 1] int32 on the host): the library as pf_pharm_align takes it"""
+        if self._packed is None:
+            ptr = torch.zeros(len(self) + 1, dtype=torch.int32)
+            if len(self):
+                ptr[1:] = torch.cumsum(torch.tensor([x.shape[0] for x, _ in self.entries]), 0)
+                self._packed = (torch.cat([x for x, _ in self.entries]), torch.cat([t for _, t in self.entries]).to(torch.int32), ptr)
+            else:
+                self._packed = (torch.zeros(0, 3), torch.zeros(0, dtype=torch.int32), ptr)
+        return self._packed
+
+    def to(self, device):
+        x, t, ptr = self.packed()
+        self._packed = (x.to(device), t.to(device), ptr)
+        return self
+
+    def __repr__(self):
+        return f"PharmacophoreLibrary(entries={len(self)}, dropped={self.dropped})"
+
+
+class ScreenHit:
+    """One library entry superposed onto a query: ``entry`` (index in the library), ``name``, ``sim``, ``n_matched`` and
+    ``transform`` [12] (R row-major, then s: entry frame -> query frame).  ``aligned()`` gives the entry's centers in the query's
+    frame."""
+    __slots__ = ("entry", "name", "sim", "n_matched", "transform", "_centers")
+
+    def __init__(self, entry, name, sim, n_matched, transform, centers=None):
+        self.entry, self.name, self.sim, self.n_matched = int(entry), str(name), float(sim), int(n_matched)
+        self.transform = torch.as_tensor(transform).detach().to("cpu", torch.float32).reshape(12)
+        self._centers = centers
+
+    def aligned(self):
+        """(positions [n, 3] fp32 in the query's frame, type indices [n])"""
+        if self._centers is None:
+            raise ValueError("this hit does not hold its entry's centers")
+        y, u = self._centers
+        R, s = self.transform[:9].reshape(3, 3).double(), self.transform[9:].double()
+        return (y.double() @ R.T + s).float(), u.clone()
+
+    def to_xyz_file(self, filename: str = None):
+        y, u = self.aligned()
+        return _emit(_xyz_block([_XYZ_ELEMENTS[int(k)] for k in u], y), filename)
+
+    def __repr__(self):
+        return f"ScreenHit(entry={self.entry}, name={self.name!r}, sim={self.sim:.4f}, n_matched={self.n_matched})"

@@ -27,6 +27,7 @@
 #include "pf_types.h"
 #include "pf_pairs.h"
 #include "pf_sset.h"
+#include "pf_align.h"
 #include "pf_mem.h"
 
 using namespace pfpack;
@@ -78,6 +79,7 @@ void pfk_guide_field_types(const StepParams* p, const FieldParams* q, const Fiel
 void pfk_guide_types(const StepParams* p, const TypeParams* q, hipStream_t s);
 void pfk_guide_pairs(const StepParams* p, const PairParams* q, hipStream_t s);
 void pfk_sset_analyze(const SsetParams* q, int work_items, hipStream_t s);
+void pfk_pharm_align(const AlignParams* q, hipStream_t s);
 void pfk_pin_restore(const int* flags, const float* pin_x, const float* pin_h, int n, int nf, float* out_x, float* out_h, hipStream_t s);
 void pfk_export_coords(const float4* xn, int base, int n, const int* gid, const float* add, const float* sub,
                        float* out, hipStream_t s);
@@ -458,6 +460,13 @@ struct pf_handle {
         DevBuf d_sim;
         DevArr<int32_t> d_status; PinnedArr<int32_t> status_host;
     } sset;
+    // pharmacophore alignment (pf_pharm_align): no run state either -- the packed pointer block (pf_align.h), the self overlaps of
+    // the call's queries and entries, the status word and its pinned host copy.  Grown on demand, kept
+    struct AlignWork {
+        StagedBlock blk;
+        DevBuf d_self;
+        DevArr<int32_t> d_status; PinnedArr<int32_t> status_host;
+    } align;
     int max_np = 0, max_nf = 0;             // largest pocket of the batch, most centers in a graph
     bool edges_built = false;               // the dynamic edges of the current coordinates exist (built by k_step_build)
     bool edges_share = false;               // ... in the pocket-sharing form (no pa copies)
@@ -3811,6 +3820,51 @@ int pf_sample_set_analyze(pf_handle* h, int32_t P, const int32_t* host_set_ptr, 
     PF_HIP(h, hipStreamSynchronize(s));
     if (*w.status_host != 0)
         PF_FAIL(h, PF_ERR_ARG, "pf_sample_set_analyze: %d centers have a type outside [0, %d) (counted on the device; the outputs mean nothing)",
+                (int)*w.status_host, (int)h->cfg.pharm_nf);
+    return PF_OK;
+}
+
+// ---- pharmacophore alignment (include/pfdyn.h: "pharmacophore alignment") ----
+// The contract of pf_sample_set_analyze: the handle's config (pharm_nf) and its own workspace, nothing else; the call waits for the
+// stream at its end to read the status word (types outside [0, pharm_nf), counted by k_align_self)
+static_assert(sizeof(pf_align_opts) == sizeof(pf_align_opts_host), "pf_align.h restates pf_align_opts");
+int pf_pharm_align(pf_handle* h, int32_t Q, const int32_t* host_q_ptr, int32_t L, const int32_t* host_l_ptr, const float* dev_qx,
+                   const int32_t* dev_qtype, const float* dev_lx, const int32_t* dev_ltype, const pf_align_opts* opts, float* dev_sim,
+                   int32_t* dev_matched, int32_t* dev_n_seeds, float* dev_transform, pf_stream stream) {
+    if (!h) return PF_ERR_ARG;
+    const pfalign::AlignArgs a{Q, host_q_ptr, L, host_l_ptr, reinterpret_cast<const pf_align_opts_host*>(opts)};
+    char msg[256];
+    if (!pfalign::validate(a, msg, sizeof msg)) PF_FAIL(h, PF_ERR_ARG, "%s", msg);
+    if (!dev_qx || !dev_qtype || !dev_lx || !dev_ltype || !dev_sim || !dev_matched || !dev_n_seeds)
+        PF_FAIL(h, PF_ERR_ARG, "pf_pharm_align: null device array (only dev_transform may be NULL)");
+    const pfalign::AlignPlan pl = pfalign::plan(a);
+    const pfalign::AlignLayout lay(pl.Q, pl.L);
+    hipStream_t s = (hipStream_t)stream;
+    pf_handle::AlignWork& w = h->align;
+    const size_t blk_bytes = lay.words() * 4, self_bytes = ((size_t)pl.Q + pl.L) * 4;
+    PF_HIP(h, w.blk.reserve(blk_bytes));
+    PF_HIP(h, w.blk.dev.reserve(blk_bytes, blk_bytes * 2, Wait::on(s)));
+    PF_HIP(h, w.d_self.reserve(self_bytes, self_bytes * 2, Wait::on(s)));
+    PF_HIP(h, w.d_status.reserve(4, 4, Wait::none()));
+    PF_HIP(h, w.status_host.reserve(4, 4, Wait::none()));
+    pfalign::pack(a, w.blk.stage.as<uint32_t>());
+    PF_HIP(h, w.blk.upload(blk_bytes, s));
+    const int32_t* d = w.blk.dev.as<const int32_t>();
+    AlignParams q{};
+    q.Q = pl.Q; q.L = pl.L; q.nf = h->cfg.pharm_nf; q.refine = pl.refine;
+    q.q_ptr = d + lay.q_ptr(); q.l_ptr = d + lay.l_ptr();
+    q.qx = dev_qx; q.qt = dev_qtype; q.lx = dev_lx; q.lt = dev_ltype;
+    q.inv_2s2 = pl.inv_2s2; q.tol2 = pl.tol2; q.seed_tol = pl.seed_tol; q.min_area = pl.min_area;
+    q.self = w.d_self.as<float>(); q.sim = dev_sim; q.matched = dev_matched; q.n_seeds = dev_n_seeds; q.transform = dev_transform;
+    q.status = w.d_status;
+    PF_HIP(h, hipMemsetAsync(w.d_status, 0, 4, s));
+    pfk_pharm_align(&q, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) PF_FAIL(h, PF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    PF_HIP(h, hipMemcpyAsync(w.status_host, w.d_status, 4, hipMemcpyDeviceToHost, s));
+    PF_HIP(h, hipStreamSynchronize(s));
+    if (*w.status_host != 0)
+        PF_FAIL(h, PF_ERR_ARG, "pf_pharm_align: %d centers have a type outside [0, %d) (counted on the device; the outputs mean nothing)",
                 (int)*w.status_host, (int)h->cfg.pharm_nf);
     return PF_OK;
 }

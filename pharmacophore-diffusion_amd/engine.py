@@ -960,6 +960,39 @@ class PfEngine:
         out["cons_x"] = out["cons_x"][:N]
         return out
 
+    def align(self, qx, qtypes, q_ptr, lx, ltypes, l_ptr, sigma=1.0, tolerance=1.5, refine=4, min_area=1.0, want_transform=True):
+        """Superposes L library entries onto Q queries, every pair, in one call (pf_pharm_align; the definition: include/pfdyn.h,
+        "pharmacophore alignment").  qx [Nq, 3] and qtypes [Nq] are the centers of all queries, query k owning rows
+        [q_ptr[k], q_ptr[k+1]); lx, ltypes and l_ptr describe the entries likewise -- both pointer arrays on the host, the center
+        arrays anywhere (tensors already on the engine's device in fp32 / int32 are passed as they are, so a library is uploaded
+        once for many calls).  Returns a dict of device tensors: sim [Q, L], n_matched [Q, L] int32, n_seeds [Q, L] int32 and
+        transform [Q, L, 12] (R row-major, then s: entry frame -> query frame; None with want_transform=False).  Needs no weights
+        and no bound batch and touches no run."""
+        qp, lp = _i32_host(torch.as_tensor(q_ptr)), _i32_host(torch.as_tensor(l_ptr))
+        if qp.ndim != 1 or lp.ndim != 1 or qp.shape[0] < 2 or lp.shape[0] < 2:
+            raise ValueError("align: q_ptr [Q + 1] and l_ptr [L + 1] with at least one query and one entry")
+        Q, Lc = int(qp.shape[0]) - 1, int(lp.shape[0]) - 1
+        dev = lambda x, t: (_f32(torch.as_tensor(x), self.device).reshape(-1, 3),
+                            torch.as_tensor(t).detach().to(device=self.device, dtype=torch.int32).contiguous().reshape(-1))
+        (xq, tq), (xl, tl) = dev(qx, qtypes), dev(lx, ltypes)
+        for what, ptr, x, t in (("q", qp, xq, tq), ("l", lp, xl, tl)):
+            if int(ptr[-1]) < 0 or x.shape[0] != int(ptr[-1]) or t.shape[0] != int(ptr[-1]):
+                raise ValueError(f"align: {what}_ptr ends at {int(ptr[-1])}, the positions have {x.shape[0]} rows and the types {t.shape[0]}")
+        n = Q * Lc if Q * Lc <= L.PF_ALIGN_MAX_PAIRS else 1          # (above the cap the library rejects the call: nothing is written)
+        out = {"sim": torch.empty(n, device=self.device), "n_matched": torch.empty(n, dtype=torch.int32, device=self.device),
+               "n_seeds": torch.empty(n, dtype=torch.int32, device=self.device),
+               "transform": torch.empty(n, 12, device=self.device) if want_transform else None}
+        opts = L.PfAlignOpts(float(sigma), float(tolerance), int(refine), float(min_area))
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.pf_pharm_align(self._h, Q, qp.ctypes.data, Lc, lp.ctypes.data, _dptr(xq), _dptr(tq), _dptr(xl), _dptr(tl),
+                                             ctypes.byref(opts), _dptr(out["sim"]), _dptr(out["n_matched"]), _dptr(out["n_seeds"]),
+                                             _dptr(out["transform"]), _stream_ptr()), "pf_pharm_align")
+        for k in ("sim", "n_matched", "n_seeds"):
+            out[k] = out[k].reshape(Q, Lc)
+        if want_transform:
+            out["transform"] = out["transform"].reshape(Q, Lc, 12)
+        return out
+
     def get_edges(self, etype: int):
         with torch.cuda.device(self.device):
             n = self._ck(self.lib.pf_debug_get_edges(self._h, etype, None, None, 0, _stream_ptr()), "pf_debug_get_edges")

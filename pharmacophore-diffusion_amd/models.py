@@ -29,6 +29,7 @@ import torch.nn.functional as F
 
 from .analysis import PharmacophoreScore, SampleAnalyzer, SampledPharmacophore, pair_restraint_energy
 from .analysis import SampleSet, _sset_options, _sset_samples, analyze_sample_set
+from .analysis import (ALIGN_MAX_PAIRS, PharmacophoreLibrary, ScreenHit, _align_options, _align_queries, align_pharmacophores)
 from ._lib import PF_SSET_MAX_SIM as SSET_MAX_SIM      # floats of all similarity matrices of one pf_sample_set_analyze call
 from .engine import PfEngine
 from .graph import PocketGraph, as_pocket_graph, batch as batch_graphs, copy_graph, get_batch_idxs, unbatch
@@ -834,6 +835,55 @@ class FlatAdam:
         # counters here was 40 us of host time per step; a parameter modified in place between the forward and this call makes the
         # next engine() upload the flat vector once more, which is correct either way.)
 
+
+
+def screen_library(queries, library, engine: Optional[PfEngine] = None, top_k: int = 10, min_match: float = 0.0, sigma: float = 1.0,
+                   tolerance: float = 1.5, refine: int = 4, min_area: float = 1.0, max_pairs: int = ALIGN_MAX_PAIRS) -> List[List[ScreenHit]]:
+    """One list of ScreenHit per query, best first: every library entry is superposed onto every query, the entries
+    with n_matched >= ceil(min_match * n_q) qualify, and the ``top_k`` of them by (sim descending, entry index) are returned.
+    ``queries``: samples, ConsensusPharmacophore objects or (x, types) pairs of at most 16 centers (ValueError above);
+    ``library``: a PharmacophoreLibrary (or a list of entries).  With an ``engine`` the pairs are computed on its device
+    (PfEngine.align, pf_pharm_align), the library uploaded once; without one by analysis.align_pharmacophores on the host, same
+    definition.  Either way the work is cut into calls of at most ``max_pairs`` (the call's cap, 2^24) pairs."""
+    opts = dict(zip(("sigma", "tolerance", "refine", "min_area"), _align_options(sigma, tolerance, refine, min_area)))
+    qs = _align_queries(queries)
+    lib = library if isinstance(library, PharmacophoreLibrary) else PharmacophoreLibrary(library)
+    if not 0.0 <= float(min_match) <= 1.0:
+        raise ValueError("min_match must be in [0, 1]")
+    max_pairs = int(max_pairs)
+    if not 1 <= max_pairs <= ALIGN_MAX_PAIRS:
+        raise ValueError(f"max_pairs must be in [1, {ALIGN_MAX_PAIRS}]")
+    Q, L = len(qs), len(lib)
+    if Q == 0 or L == 0:
+        return [[] for _ in range(Q)]
+    sim, matched = torch.zeros(Q, L), torch.zeros(Q, L, dtype=torch.int64)
+    xf = torch.zeros(Q, L, 12)
+    q_step = min(Q, max_pairs)
+    l_step = max(1, max_pairs // q_step)
+    if engine is not None:
+        lx, lt, lptr = lib.packed()
+        lx, lt = lx.to(engine.device, torch.float32), lt.to(engine.device, torch.int32)
+    for q0 in range(0, Q, q_step):
+        qc = qs[q0:q0 + q_step]
+        for l0 in range(0, L, l_step):
+            l1 = min(l0 + l_step, L)
+            if engine is None:
+                r = align_pharmacophores(qc, lib.entries[l0:l1], **opts)
+            else:
+                qptr = np.concatenate([[0], np.cumsum([x.shape[0] for x, _ in qc])]).astype(np.int32)
+                c0, c1 = int(lptr[l0]), int(lptr[l1])
+                r = engine.align(torch.cat([x for x, _ in qc]), torch.cat([t for _, t in qc]), qptr, lx[c0:c1], lt[c0:c1],
+                                 (lptr[l0:l1 + 1] - lptr[l0]).numpy(), **opts)
+            sim[q0:q0 + len(qc), l0:l1] = r["sim"].cpu().float()
+            matched[q0:q0 + len(qc), l0:l1] = r["n_matched"].cpu().long()
+            xf[q0:q0 + len(qc), l0:l1] = r["transform"].cpu().float()
+    out = []
+    for a, (x, _) in enumerate(qs):
+        need = math.ceil(float(min_match) * x.shape[0] - 1e-9)
+        ok = [b for b in range(L) if int(matched[a, b]) >= need]
+        ok.sort(key=lambda b: (-float(sim[a, b]), b))
+        out.append([ScreenHit(b, lib.names[b], sim[a, b], matched[a, b], xf[a, b], lib[b]) for b in ok[:int(top_k)]])
+    return out
 
 
 def sample_sets(per_pocket_samples, engine: Optional[PfEngine] = None, sigma: float = 1.0, tolerance: float = 1.5,
@@ -1856,6 +1906,20 @@ class PharmacophoreDiff(_Base):
         dev = torch.device(device) if device is not None else self.device
         eng = self.dynamics.engine() if torch.device(dev).type == "cuda" else None
         return sample_sets(per_pocket_samples, eng, sigma, tolerance, threshold, min_support)
+
+    # -- screening a pharmacophore library (pf_pharm_align) -------------------------------------------
+    def screen(self, queries, library, top_k: int = 10, min_match: float = 0.0, sigma: float = 1.0, tolerance: float = 1.5,
+               refine: int = 4, device=None) -> List[List[ScreenHit]]:
+        """One list of ScreenHit per query, best first: ``library`` (a PharmacophoreLibrary) is superposed rigidly onto every
+        query -- samples, ConsensusPharmacophore objects or (x, types) pairs of at most 16 centers (ValueError above that cap) --
+        and ranked by the typed Gaussian-overlap Tanimoto of the sample sets (``sigma``) after the superposition.
+        Only entries with n_matched >= ceil(min_match * n_q) qualify (n_matched: query centers with a same-type entry center
+        within ``tolerance``); the order is by sim, then entry index; ``refine``: refinement rounds.  Proper rotations only and
+        exact types; the result is the best of a discrete seed set plus a local refinement.  Runs on the device when the model
+        is on one (chunked under the call's pair cap), else on the host through analysis.py; ``device``: 'cpu' forces the host."""
+        dev = torch.device(device) if device is not None else self.device
+        eng = self.dynamics.engine() if torch.device(dev).type == "cuda" else None
+        return screen_library(queries, library, eng, top_k, min_match, sigma, tolerance, refine)
 
     # -- scoring given pharmacophores (pf_score) ---------------------------------------------------
     def score(self, ref_graphs: List[PocketGraph], pharmacophores, levels=None, weighting: str = 'uniform', noise=None, seed: int = 0,

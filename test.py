@@ -56,6 +56,7 @@ _FLAGS = [
     ('--comp_unmatched', dict(type=float, default=None, metavar='U', help='with --guide_complementarity_types: what a type without any partner in the pocket costs, as a distance beyond its matching distance (default 0)')),
     ('--pockets_per_call', dict(type=int, default=64, help='pockets whose samples are batched together (not in the reference)')),
     ('--use_ema', dict(action='store_true', help="sample from the checkpoint's EMA weights ('ema_state_dict') instead of the training weights")),
+    ('--screen_self', dict(action='store_true', help='screen the ligand pharmacophores of the split (1 to 32 centers each) against every pocket\'s samples (rigid superposition, default options): per pocket the rank of the pocket\'s own ligand among the hits of its best sample -- the sample most similar to that ligand -- and self_rank_median and self_top10 over all ranks, written to screen_self.tsv and screen_summary.txt')),
     ('--consensus', dict(action='store_true', help='analyse the samples of every pocket as a set (similarity, clusters, consensus; default options): writes consensus.xyz and clusters.tsv per pocket and adds clusters_per_pocket and mean_support to the summary over all ranks')),
 ]
 
@@ -188,6 +189,19 @@ def write_pocket(out_root, dataset, idx, pharms, seconds, trajectories):
         (pocket_dir / 'pharms.xyz').write_text(''.join(ph.to_xyz_file() for ph in pharms))
 
 
+def self_rank(pfa, model, library, own, pharms):
+    """--screen_self: (rank, sample, sim) of library entry `own` -- the pocket's own ligand pharmacophore -- among the hits of the
+    pocket's best sample: the sample (of 1 to 16 centers) most similar to that entry after the superposition; the rank is 1-based
+    over the whole library.  None when the ligand is not in the library or no sample can be a query."""
+    usable = [k for k, ph in enumerate(pharms) if 1 <= ph.n_ph_centers <= 16]
+    if own is None or not usable:
+        return None
+    hits = model.screen([pharms[k] for k in usable], library, top_k=len(library))
+    place = [next(r for r, h in enumerate(hs) if h.entry == own) for hs in hits]
+    best = max(range(len(usable)), key=lambda a: (hits[a][place[a]].sim, -a))
+    return place[best] + 1, usable[best], hits[best][place[best]].sim
+
+
 def main(argv=None):
     import pharmacoforge_amd as pfa
     from pharmacoforge_amd.dataset import data_module_from_config
@@ -216,6 +230,13 @@ def main(argv=None):
     mine = [pockets[j] for j in shard_by_work([float(epp[i] + 1) * args.samples_per_pocket for i in pockets], world)[rank]]
     all_pharms = []
     set_counts = torch.zeros(4, dtype=torch.float64)       # --consensus: pockets, clusters, samples, sum of the samples' mean support
+    library, self_rows = None, []
+    if args.screen_self:                                   # the split's ligand pharmacophores, uploaded once
+        library = pfa.PharmacophoreLibrary.from_dataset(dataset).to(device)
+        entry_of = {pocket: k for k, pocket in enumerate(library.index)}
+        rank_hist = torch.zeros(len(library) + 1, dtype=torch.float64)      # rank_hist[r]: pockets whose own ligand has rank r (1-based)
+        if rank == 0:
+            print(f'--screen_self: {len(library)} library entries, {library.dropped} ligand pharmacophores outside 1..32 centers dropped', flush=True)
     for c0 in range(0, len(mine), args.pockets_per_call):
         chunk = mine[c0:c0 + args.pockets_per_call]
         t0 = time.time()
@@ -246,6 +267,11 @@ def main(argv=None):
                 (out_root / f'pocket_{idx}' / 'consensus.xyz').write_text(sset.consensus_xyz())
                 (out_root / f'pocket_{idx}' / 'clusters.tsv').write_text(sset.clusters_tsv())
                 set_counts += torch.tensor([1.0, len(sset.clusters), sset.n_samples, sum(sset.mean_support())], dtype=torch.float64)
+            if library is not None:
+                r = self_rank(pfa, model, library, entry_of.get(idx), pharms)
+                if r is not None:
+                    rank_hist[r[0]] += 1
+                    self_rows.append(f'{idx}\t{r[0]}\t{r[1]}\t{r[2]:.6f}')
             if args.avoid_clashes is not None and rank == 0:       # the final clash energy and clashing pairs of every sample
                 from pharmacoforge_amd.analysis import clash_energy
                 cl = [clash_energy(ph.ph_coords, ph.g.prot_x, args.avoid_clashes, args.pocket_field['clash_weight']) for ph in pharms]
@@ -281,6 +307,19 @@ def main(argv=None):
         if rank == 0:
             print(summary)
             (out_root / 'consensus_summary.txt').write_text('\n'.join(f'{k}: {v:.3f}' for k, v in summary.items()))
+    if library is not None:
+        (out_root / f'screen_self_rank{rank}.tsv' if world > 1 else out_root / 'screen_self.tsv').write_text(
+            'pocket\tself_rank\tbest_sample\tsim\n' + ''.join(row + '\n' for row in self_rows))
+        if group is not None:
+            from pharmacoforge_amd.analysis import _allreduce_sum
+            rank_hist = _allreduce_sum(rank_hist, group, device)
+        n = float(rank_hist.sum())
+        below = torch.cumsum(rank_hist, 0)
+        summary = {'self_rank_median': float(torch.nonzero(below >= n / 2)[0]) if n > 0 else 0.0,        # the lower median
+                   'self_top10': float(rank_hist[:11].sum() / n) if n > 0 else 0.0, 'pockets_ranked': n}
+        if rank == 0:
+            print(summary)
+            (out_root / 'screen_summary.txt').write_text('\n'.join(f'{k}: {v:.3f}' for k, v in summary.items()))
     if world > 1:
         torch.distributed.destroy_process_group()
 
